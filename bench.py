@@ -14,6 +14,14 @@ Workload at every N (weak scaling): BASELINE.json configs[1], B = 128 impression
 H = 50 clicks, C = 5 candidates, L = 30 tokens, V = 70,000, D = 300, 15 heads, Q = 200.
 Rank 0 prints ONE JSON line.
 
+A plain run does only what that line's headline needs: set-up, `--warmup W` untimed steps, exactly `--steps K` timed steps, the
+result line (`metric`, `value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step`, ...).  `--full` adds everything else the
+benchmark measures, after the timed region: the instrumented pass behind `roofline`, `prepare_ms`, `grad_exchange` (N > 1) and, at
+world 1, `forward_only`, `f32_engine`, `lstur`, `plm`, `multi_gpu_prediction` and `cpu_baseline` (`--no-extras` /
+`--no-cpu-baseline` trim that list).  `--dump-outputs DIR` writes what the last timed step's `model_step` handed its caller --
+the loss, the scores of the valid candidate slots and their targets -- as float32 `DIR/<name>.npy` (rank 0; inputs, initial
+weights and dropout seeds are seeded, so two builds run with the same arguments compare output for output).
+
 `--gpus N` with N > 1 and no launcher environment (WORLD_SIZE unset) re-executes itself under
 `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1` (one rank per GPU
 over RCCL), so the same command line works with and without an external launcher.
@@ -288,6 +296,32 @@ def self_launch(n_gpus: int) -> int:
     return subprocess.call(cmd, env=env)
 
 
+def capture_step_outputs(mod, store):
+    """--dump-outputs: wraps ``mod.model_step`` for ONE call (the last timed step) and keeps, by reference (no device work, no
+    copy), what it hands its caller: the loss, the scores of the valid candidate slots and their targets."""
+    orig = mod.model_step
+
+    def model_step(batch):
+        out = orig(batch)
+        store.update(loss=out[0], preds=out[1], targets=out[2])
+        del mod.model_step                     # the class method again from the next call on
+        return out
+
+    mod.model_step = model_step
+
+
+def dump_outputs(path, store):
+    """Writes what ``capture_step_outputs`` kept as float32 ``<name>.npy``.  (Not the parameters: Adam normalises the gradient,
+    so entries whose true gradient is zero -- the key third of every ``in_proj_bias``, which softmax cannot see -- move by up
+    to ``lr`` per step on rounding noise of the backward's atomic sums and differ from run to run; the scores of the last step
+    carry every earlier update that the model's output depends on.)"""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    for name in ("loss", "preds", "targets"):
+        np.save(os.path.join(path, name + ".npy"), store[name].detach().float().reshape(-1).cpu().numpy())
+    print(f"bench.py: wrote loss / preds / targets of the last timed step to {path}", file=sys.stderr)
+
+
 def git_head():
     try:
         return subprocess.check_output(["git", "-C", ROOT, "rev-parse", "--short=12", "HEAD"], stderr=subprocess.DEVNULL).decode().strip()
@@ -315,9 +349,16 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=10)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline also the instrumented pass (roofline), prepare_ms, grad_exchange (N > 1) and the "
+                         "world-1 extras (forward_only, f32_engine, lstur, plm, multi_gpu_prediction, cpu_baseline)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned to its caller (loss, scores of the valid candidate "
+                         "slots, their targets) as float32 DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip cpu_baseline")
     ap.add_argument("--no-extras", action="store_true",
-                    help="only the timed region (profiling runs): skip forward_only / f32_engine / cpu_baseline")
+                    help="--full: only the timed region and the instrumented pass (profiling runs): skip forward_only / "
+                         "f32_engine / lstur / plm / multi_gpu_prediction / cpu_baseline")
     ap.add_argument("--engine", choices=["f32", "bf16x3"], default="bf16x3",
                     help="projection-GEMM engine: exact fp32 MFMA, or fp32 via 3 bf16 MFMAs per product")
     ap.add_argument("--workload", choices=sorted(WORKLOADS), default="mindsmall",
@@ -328,6 +369,8 @@ def main():
                          "auto = per step whichever of the three trainer.predicted_wire_ms prices lowest (dense stays the default: it is the "
                          "one exchange whose RCCL calls have run on hardware, at world size 1)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if args.grad_exchange is None:
         # dense all-reduce for every workload: it is the one exchange whose RCCL calls have run on hardware (at world size 1; no
         # multi-GPU node was available to any round).  `--grad-exchange auto` prices the three exchanges per step
@@ -385,35 +428,41 @@ def main():
     barrier()
     t0 = time.perf_counter()
     marks[0].record()
+    last = {}
     for i in range(args.steps):
+        if args.dump_outputs and rank == 0 and i == args.steps - 1:
+            capture_step_outputs(mod, last)
         trainer.step(batches[(args.warmup + i) % N_BATCHES], batches[(args.warmup + i + 1) % N_BATCHES])
         marks[i + 1].record()
     barrier()
     dt = time.perf_counter() - t0
     step_ms = [marks[i].elapsed_time(marks[i + 1]) for i in range(args.steps)]
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last)
 
-    # ---- second, instrumented pass (NOT the headline, feeds `roofline` only): HIP events around the dominant kernel
-    # (nrl_prof, recorded on the launch stream) ----
-    lib.nrl_prof_enable(1)
-    if hasattr(trainer.reduce, "measure"):
-        # (N > 1: event pairs around every wait for a collective -- how much of the exchange the backward did not hide; zeros at
-        #  world 1.  In this pass only: the timed region above carries no such instrumentation)
-        trainer.reduce.reset_exposed_wait()
-        trainer.reduce.measure = True
-    for i in range(args.steps):
-        trainer.step(batches[i % N_BATCHES], batches[(i + 1) % N_BATCHES])
-    barrier()
-    if hasattr(trainer.reduce, "measure"):
-        trainer.reduce.measure = False
-    tot_ms, launches, flops = ctypes.c_double(), ctypes.c_int64(), ctypes.c_double()
-    lib.nrl_prof_read(ctypes.byref(tot_ms), ctypes.byref(launches), ctypes.byref(flops))
-    lib.nrl_prof_enable(0)
-    # what the id bookkeeping inside the step costs (measured after the timed region)
-    t1 = time.perf_counter()
-    for i in range(20):
-        prepare_batch(batches[i % N_BATCHES], VOCAB)
-    torch.cuda.synchronize()
-    prepare_ms = (time.perf_counter() - t1) / 20 * 1e3
+    if args.full:
+        # ---- second, instrumented pass (NOT the headline, feeds `roofline` only): HIP events around the dominant kernel
+        # (nrl_prof, recorded on the launch stream) ----
+        lib.nrl_prof_enable(1)
+        if hasattr(trainer.reduce, "measure"):
+            # (N > 1: event pairs around every wait for a collective -- how much of the exchange the backward did not hide; zeros at
+            #  world 1.  In this pass only: the timed region above carries no such instrumentation)
+            trainer.reduce.reset_exposed_wait()
+            trainer.reduce.measure = True
+        for i in range(args.steps):
+            trainer.step(batches[i % N_BATCHES], batches[(i + 1) % N_BATCHES])
+        barrier()
+        if hasattr(trainer.reduce, "measure"):
+            trainer.reduce.measure = False
+        tot_ms, launches, flops = ctypes.c_double(), ctypes.c_int64(), ctypes.c_double()
+        lib.nrl_prof_read(ctypes.byref(tot_ms), ctypes.byref(launches), ctypes.byref(flops))
+        lib.nrl_prof_enable(0)
+        # what the id bookkeeping inside the step costs (measured after the timed region)
+        t1 = time.perf_counter()
+        for i in range(20):
+            prepare_batch(batches[i % N_BATCHES], VOCAB)
+        torch.cuda.synchronize()
+        prepare_ms = (time.perf_counter() - t1) / 20 * 1e3
 
     median_ms = statistics.median(step_ms)
     if distributed:
@@ -427,62 +476,63 @@ def main():
         mean_value = world * B_PER_GPU * args.steps / dt
         median_value = world * B_PER_GPU / (median_ms * 1e-3)
         value = median_value if args.steps >= 50 else mean_value
-        avg_s = tot_ms.value * 1e-3 / max(1, launches.value)
-        tflops = (flops.value / max(1, launches.value)) / avg_s / 1e12 if avg_s > 0 else None
-        # The dominant kernel of the step and its ALGORITHMIC work (no materialised
-        # intermediates): per launch it needs the ids (8 B per token) and the gathered embedding rows (1200 B per
-        # token) -- 0.255 GB at B = 128 -- and 2*M*3D*D (+ the per-head L x L attention it now contains) FLOPs.
-        algo_bytes = M_ROWS * 8 + M_ROWS * D * 4
-        fused = args.engine == "bf16x3" and os.environ.get("NRL_NEWS_FUSED", "1") != "0"
-        pmc_name = "pmc_news_fused_fwd_bf16x3.json" if fused else f"pmc_in_proj_fwd_{args.engine}.json"
-        traffic, step_bytes, prof_meta = None, None, None
-        pmc = os.path.join(ROOT, "profiles", pmc_name)
         build_id = lib.nrl_build_id().decode()
-        if os.path.exists(pmc) and args.workload == "mindsmall":
-            j = json.load(open(pmc))
-            traffic, step_bytes = j.get("hbm_bytes_per_launch"), j.get("hbm_bytes_per_step")
-            # the counters are a committed profile (rocprofv3 PMC passes cannot run inside the timed process): say which
-            # build of the kernels they were taken on, and whether that is the build running now
-            prof_meta = {"file": "profiles/" + pmc_name, "git_head": j.get("git_head"), "build_id": j.get("build_id"),
-                         "matches_running_build": j.get("build_id") == build_id}
-            if not prof_meta["matches_running_build"]:
-                print(f"bench.py: WARNING: {pmc_name} was taken on build {j.get('build_id')}, the library running now is "
-                      f"{build_id}: `traffic` / `counter_bytes` may be stale (tools/profile_round.sh regenerates them)", file=sys.stderr)
-        if args.engine == "f32":
-            # exact fp32 MFMA: intensity (114 GFLOP / 0.255 GB) >> ridge 25 FLOP/B -> MFMA-bound
-            roof = {"bound": "mfma", "kernel": "gemm_f32_kernel<4,2,2,5,16,KCGather,KCPlain,EpiLinear> (in-projection "
-                                              "forward with fused embedding gather + dropout)",
-                    "achieved": round(tflops, 2), "peak": FP32_MFMA_PEAK_TFLOPS, "unit": "TFLOP/s",
-                    "frac": round(tflops / FP32_MFMA_PEAK_TFLOPS, 4)}
-        else:
-            # bf16x3: every fp32 product is three bf16 MFMA products; against section 8(d)'s bytes the binding
-            # roofline is the matrix pipe (3 x 122 GFLOP on 2.5 PF = 0.146 ms vs 0.255 GB over 8 TB/s = 0.032 ms)
-            name = ("news_fused_fwd_kernel<20, true> (embedding gather + dropout + in-projection + per-head token "
-                    "attention in one launch)") if fused else \
-                   "gemm_bf16x3_kernel<4,2,4,5,KCGather,KCSplit,EpiLinear> (in-projection forward with fused gather)"
-            issued = 3.0 * tflops
-            roof = {"bound": "mfma", "kernel": name, "achieved": round(issued, 1), "peak": BF16_MFMA_PEAK_TFLOPS,
-                    "unit": "TFLOP/s", "frac": round(issued / BF16_MFMA_PEAK_TFLOPS, 4),
-                    "algorithmic_fp32_TFLOPs": round(tflops, 1),
-                    "hbm_view": {"algorithmic_GBps": round(algo_bytes / avg_s / 1e9, 1), "peak_GBps": HBM_PEAK_GBPS,
-                                 "frac": round(algo_bytes / avg_s / 1e9 / HBM_PEAK_GBPS, 4)}}
-        roof["algorithmic_bytes_per_launch"] = algo_bytes
-        # whole step against the survey's algorithmic model: 4.49 GFLOP and 11.7 MB per impression (fp32-equivalent)
-        step_s = median_ms * 1e-3
-        step_flops = 4.49e9 * B_PER_GPU
-        roof["step"] = {"algorithmic_flops": step_flops, "algorithmic_bytes": 11.7e6 * B_PER_GPU,
-                        "counter_bytes": step_bytes,
-                        "frac_of_bf16x3_peak": round(3 * step_flops / step_s / 1e12 / BF16_MFMA_PEAK_TFLOPS, 4),
-                        "frac_of_hbm_peak_algorithmic": round(11.7e6 * B_PER_GPU / step_s / 1e9 / HBM_PEAK_GBPS, 4)}
-        roof.update({"traffic": traffic, "traffic_profile": prof_meta, "launches": launches.value,
-                     "avg_launch_ms": round(avg_s * 1e3, 4), "measured": "HIP events on the launch stream, instrumented second pass (value / median come from the clean timed region)"})
+        if args.full:
+            avg_s = tot_ms.value * 1e-3 / max(1, launches.value)
+            tflops = (flops.value / max(1, launches.value)) / avg_s / 1e12 if avg_s > 0 else None
+            # The dominant kernel of the step and its ALGORITHMIC work (no materialised
+            # intermediates): per launch it needs the ids (8 B per token) and the gathered embedding rows (1200 B per
+            # token) -- 0.255 GB at B = 128 -- and 2*M*3D*D (+ the per-head L x L attention it now contains) FLOPs.
+            algo_bytes = M_ROWS * 8 + M_ROWS * D * 4
+            fused = args.engine == "bf16x3" and os.environ.get("NRL_NEWS_FUSED", "1") != "0"
+            pmc_name = "pmc_news_fused_fwd_bf16x3.json" if fused else f"pmc_in_proj_fwd_{args.engine}.json"
+            traffic, step_bytes, prof_meta = None, None, None
+            pmc = os.path.join(ROOT, "profiles", pmc_name)
+            if os.path.exists(pmc) and args.workload == "mindsmall":
+                j = json.load(open(pmc))
+                traffic, step_bytes = j.get("hbm_bytes_per_launch"), j.get("hbm_bytes_per_step")
+                # the counters are a committed profile (rocprofv3 PMC passes cannot run inside the timed process): say which
+                # build of the kernels they were taken on, and whether that is the build running now
+                prof_meta = {"file": "profiles/" + pmc_name, "git_head": j.get("git_head"), "build_id": j.get("build_id"),
+                             "matches_running_build": j.get("build_id") == build_id}
+                if not prof_meta["matches_running_build"]:
+                    print(f"bench.py: WARNING: {pmc_name} was taken on build {j.get('build_id')}, the library running now is "
+                          f"{build_id}: `traffic` / `counter_bytes` may be stale (tools/profile_round.sh regenerates them)", file=sys.stderr)
+            if args.engine == "f32":
+                # exact fp32 MFMA: intensity (114 GFLOP / 0.255 GB) >> ridge 25 FLOP/B -> MFMA-bound
+                roof = {"bound": "mfma", "kernel": "gemm_f32_kernel<4,2,2,5,16,KCGather,KCPlain,EpiLinear> (in-projection "
+                                                  "forward with fused embedding gather + dropout)",
+                        "achieved": round(tflops, 2), "peak": FP32_MFMA_PEAK_TFLOPS, "unit": "TFLOP/s",
+                        "frac": round(tflops / FP32_MFMA_PEAK_TFLOPS, 4)}
+            else:
+                # bf16x3: every fp32 product is three bf16 MFMA products; against section 8(d)'s bytes the binding
+                # roofline is the matrix pipe (3 x 122 GFLOP on 2.5 PF = 0.146 ms vs 0.255 GB over 8 TB/s = 0.032 ms)
+                name = ("news_fused_fwd_kernel<20, true> (embedding gather + dropout + in-projection + per-head token "
+                        "attention in one launch)") if fused else \
+                       "gemm_bf16x3_kernel<4,2,4,5,KCGather,KCSplit,EpiLinear> (in-projection forward with fused gather)"
+                issued = 3.0 * tflops
+                roof = {"bound": "mfma", "kernel": name, "achieved": round(issued, 1), "peak": BF16_MFMA_PEAK_TFLOPS,
+                        "unit": "TFLOP/s", "frac": round(issued / BF16_MFMA_PEAK_TFLOPS, 4),
+                        "algorithmic_fp32_TFLOPs": round(tflops, 1),
+                        "hbm_view": {"algorithmic_GBps": round(algo_bytes / avg_s / 1e9, 1), "peak_GBps": HBM_PEAK_GBPS,
+                                     "frac": round(algo_bytes / avg_s / 1e9 / HBM_PEAK_GBPS, 4)}}
+            roof["algorithmic_bytes_per_launch"] = algo_bytes
+            # whole step against the survey's algorithmic model: 4.49 GFLOP and 11.7 MB per impression (fp32-equivalent)
+            step_s = median_ms * 1e-3
+            step_flops = 4.49e9 * B_PER_GPU
+            roof["step"] = {"algorithmic_flops": step_flops, "algorithmic_bytes": 11.7e6 * B_PER_GPU,
+                            "counter_bytes": step_bytes,
+                            "frac_of_bf16x3_peak": round(3 * step_flops / step_s / 1e12 / BF16_MFMA_PEAK_TFLOPS, 4),
+                            "frac_of_hbm_peak_algorithmic": round(11.7e6 * B_PER_GPU / step_s / 1e9 / HBM_PEAK_GBPS, 4)}
+            roof.update({"traffic": traffic, "traffic_profile": prof_meta, "launches": launches.value,
+                         "avg_launch_ms": round(avg_s * 1e3, 4), "measured": "HIP events on the launch stream, instrumented second pass (value / median come from the clean timed region)"})
         out = {
             "metric": "impressions/sec (train step) NRMS MINDlarge-shape" if args.workload == "mindlarge"
                       else "impressions/sec (train step) NRMS MINDsmall-shape", "value": round(value, 1),
             "unit": "impressions/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
             "ms_per_step": round(dt / args.steps * 1e3, 4),
             "median_ms_per_step": round(median_ms, 4), "value_basis": "median step" if args.steps >= 50 else "mean of the timed region",
-            "mean_value": round(mean_value, 1), "prepare_ms": round(prepare_ms, 4),
+            "mean_value": round(mean_value, 1),
             "rccl_ranks": dist.get_world_size() if distributed else 1,
             "higher_is_better": True, "scaling": "weak",
             "vs_baseline": None, "dtype": "f32" if args.engine == "f32" else "f32 (projections: 3xbf16 split MFMA)",
@@ -492,9 +542,11 @@ def main():
                        "optimizer": ("lazy-dense table Adam (bit-identical to dense Adam after flush), rolling flush period 64; "
                                      "dense Adam kernel for the non-table parameters") if trainer.lazy_tables else "dense Adam"},
             "build_id": build_id, "git_head": git_head() or "none on this box (no .git in the snapshot): build_id is the content hash of the kernel sources",
-            "roofline": roof,
         }
-        if distributed:
+        if args.full:
+            out["prepare_ms"] = round(prepare_ms, 4)
+            out["roofline"] = roof
+        if distributed and args.full:
             # self-diagnosing multi-GPU line: the exchange that ran, its bytes on the wire per rank, the
             # wire time the xGMI model predicts for it and the MEASURED time the launch stream spent blocked on it, next to the
             # overlap window it had; what the one-GPU step of this same build takes is `multi_gpu_prediction.compute_ms` of a
@@ -512,7 +564,7 @@ def main():
                               "measured_exposed_wait_ms": gx["measured"]["exposed_wait_ms_per_step"],
                               "steps_measured": gx["measured"]["steps_measured"]}
             out["grad_exchange"] = gx
-        if world == 1 and not args.no_extras:
+        if args.full and world == 1 and not args.no_extras:
             # the forward-only (evaluation-mode) rate of the same workload, outside the timed region
             mod.eval()
             with torch.no_grad():
@@ -561,7 +613,7 @@ def main():
                                                            "gathered per position; news vectors torch.equal to the table-less forward"},
                                    "without_token_table_ms": round(plain_ms, 4)}
         unforked_ms = None
-        if world == 1 and not args.no_extras:
+        if args.full and world == 1 and not args.no_extras:
             # the one-GPU step as a rank of an N > 1 job runs it: `news_fork` off (trainer.NRMSTrainer switches it off on more than one
             # rank, so that all three weight gradients stay in the window the gradient exchange hides in) -- the compute term of
             # `multi_gpu_prediction`
@@ -580,7 +632,7 @@ def main():
                 unforked_ms = statistics.median(ev[i].elapsed_time(ev[i + 1]) for i in range(30))
             finally:
                 _lib.set_option("news_fork", was)
-        if world == 1 and args.engine != "f32" and not args.no_extras:
+        if args.full and world == 1 and args.engine != "f32" and not args.no_extras:
             # the exact-fp32 projection engine on the same workload (extra key, outside the timed region), with its own
             # roofline: the in-projection GEMM with the fused gather, against the fp32 MFMA peak
             _lib.set_gemm_engine("f32")
@@ -612,7 +664,7 @@ def main():
                     "achieved": round(tf32, 2), "peak": FP32_MFMA_PEAK_TFLOPS, "unit": "TFLOP/s",
                     "frac": round(tf32 / FP32_MFMA_PEAK_TFLOPS, 4), "avg_launch_ms": round(dms / dl, 4), "launches": dl,
                     "step_frac_of_fp32_mfma_peak": round(step_flops / d32 / 1e12 / FP32_MFMA_PEAK_TFLOPS, 4)}
-        if world == 1 and not args.no_extras:
+        if args.full and world == 1 and not args.no_extras:
             # the other single-GPU configurations of BASELINE.json, driver-timed (outside the timed region)
             del trainer, mod, batches
             torch.cuda.empty_cache()
@@ -622,7 +674,7 @@ def main():
                 except Exception as e:                     # an extra must never cost the headline line
                     out[key] = {"error": f"{type(e).__name__}: {e}"[:300]}
                 torch.cuda.empty_cache()
-        if not distributed and not args.no_extras:
+        if args.full and not distributed and not args.no_extras:
             # host-only model of the 8-GPU step.  LAST of the device-side extras on purpose (round 6): its host work (sort-based
             # torch.unique over 1.7 M ids on the framework's thread pool, nine times) was what set off the ~85 ms stall that
             # rounds 4-5 saw once inside the evaluation loop that used to follow it -- tools/eval_idle_probe.py:
@@ -634,7 +686,7 @@ def main():
                     "fork: %.4f ms)" % (unforked_ms, median_ms)) if unforked_ms else "this run's one-GPU step"
             except Exception as e:                         # an extra must never cost the headline line
                 out["multi_gpu_prediction"] = {"error": f"{type(e).__name__}: {e}"[:200]}
-        if world == 1 and not args.no_cpu_baseline and not args.no_extras:
+        if args.full and world == 1 and not args.no_cpu_baseline and not args.no_extras:
             out["cpu_baseline"] = cpu_baseline()
         print(json.dumps(out), flush=True)
     if distributed:

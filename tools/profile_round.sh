@@ -10,7 +10,7 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$R/gpurun_out/profiles
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-BENCH="python $R/bench.py --steps 10 --warmup 3 --no-extras --engine $ENGINE"
+BENCH="python $R/bench.py --steps 10 --warmup 3 --full --no-extras --engine $ENGINE"
 export NRL_PROFILE_STEPS=23   # 3 warm-up + 10 timed + 10 instrumented (bench.py second pass)
 # 1. per-kernel time (kernel trace + stats only)
 rocprofv3 --kernel-trace --stats -f csv -d $OUT/${TAG}_trace -o $TAG -- $BENCH > $OUT/${TAG}_trace.log 2>&1
