@@ -65,7 +65,9 @@ class MHSAAddAtt(nn.Module):
     # VOCABULARY id and per weight version instead of once per position and forward.  The result is torch.equal to the table-less
     # forward.  Two ways in:
     #   * ``with encoder.token_table():`` -- the caller vouches that the weights do not change inside (an evaluation epoch:
-    #     ``AbstractRecommender.on_validation_epoch_start`` / ``_end``, ``evaluation.NewsVectorCache.build``);
+    #     ``AbstractRecommender.on_validation_epoch_start`` / ``_end``, ``evaluation.NewsVectorCache.build``).  The table lives
+    #     for the scope: the first forward inside always builds it (weights written between two epochs through ``p.data`` -- an
+    #     EMA swap, a foreign optimizer -- move no key) and leaving the outermost scope frees it (one build per epoch);
     #   * automatically, for forwards with the module in eval mode under ``torch.no_grad()``, keyed on every parameter's storage
     #     and version counter and on this library's optimizer-step generation -- for TRAINABLE weights only while this
     #     library's optimizer is the writer (``ops_blocks.step_images_allowed``: a foreign ``p.data`` writer moves no counter),
@@ -74,21 +76,27 @@ class MHSAAddAtt(nn.Module):
     TOKEN_TABLE_USES = {"built": 0, "forwards": 0}
 
     def _token_table_key(self, params):
-        return (tuple((t.data_ptr(), t._version, tuple(t.shape)) for t in params[:-1]), _lib.engine_code(), _lib.options_word(),
+        return (tuple((t.data_ptr(), t._version, tuple(t.shape), ops_blocks.tensor_serial(t)) for t in params[:-1]),
+                _lib.engine_code(), _lib.options_word(),
                 ops_blocks._IMAGE_GENERATION[0], ops_blocks._STEP_GENERATION[0], int(self.num_heads))
 
     def token_table(self):
-        """Context manager: forwards inside (eval mode, no grad) run from ONE table built at the first of them."""
+        """Context manager: forwards inside (eval mode, no grad) run from ONE table built at the first of them; the table is
+        dropped when the outermost scope ends."""
         import contextlib
 
         @contextlib.contextmanager
         def scope():
             prev = self._tt_pinned
+            if not prev:
+                self._tt_key = None
             self._tt_pinned = True
             try:
                 yield self
             finally:
                 self._tt_pinned = prev
+                if not prev:
+                    self.drop_token_table()
         return scope()
 
     def drop_token_table(self) -> None:

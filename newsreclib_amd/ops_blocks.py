@@ -4,9 +4,11 @@ from __future__ import annotations
 
 import contextlib
 import ctypes
+import itertools
 import weakref
 
 import torch
+from torch.optim.optimizer import register_optimizer_step_post_hook
 
 from . import _lib
 from ._lib import NrlAddAttGrads, NrlAddAttParams
@@ -654,6 +656,16 @@ def next_optimizer_step() -> None:
     _STEP_GENERATION[0] += 1
 
 
+def _torch_optimizer_stepped(_optimizer, _args, _kwargs) -> None:
+    # torch.optim.Adam(fused=True) writes its parameters without moving their version counters (found on the MI355X: a trainable
+    # weight's per-step images and the automatic token table then served the pre-step weights), and any other torch optimizer
+    # might too: every torch.optim step ends the step images of every trainable weight, as this library's own optimizer does
+    next_optimizer_step()
+
+
+register_optimizer_step_post_hook(_torch_optimizer_stepped)
+
+
 def register_step_driver(driver=None, params=()) -> None:
     """Called by an optimizer that promises ``next_optimizer_step()`` before every parameter write (trainer.FusedAdam): `driver` is
     the optimizer (kept weakly), `params` the parameters it writes.  Without arguments: a process-wide promise for every weight."""
@@ -701,6 +713,21 @@ def step_images_allowed(*weights) -> bool:
     return all(_owned_by_live_driver(w) for w in trainable)
 
 
+_TENSOR_SERIALS = itertools.count(1)
+
+
+def tensor_serial(t: torch.Tensor) -> int:
+    """A number that names the tensor OBJECT ``t`` for as long as it lives (kept on the object itself).  Part of every weight-derived
+    cache key next to the storage address and the version counter: a Parameter freed and replaced by a new one very likely gets the
+    same address back from the caching allocator, and a fresh tensor's version counter can equal the old one's -- an address and a
+    version alone would then name the new weight with the old weight's key."""
+    s = getattr(t, "_nrl_serial", None)
+    if s is None:
+        s = next(_TENSOR_SERIALS)
+        t._nrl_serial = s
+    return s
+
+
 def invalidate_frozen_images() -> None:
     """Drops every cached weight image of every ``FrozenImages`` (a generation counter that is part of their keys): call it
     after writing a frozen weight through a path no version counter sees (``w.data.copy_()``, raw-pointer writes)."""
@@ -710,7 +737,7 @@ def invalidate_frozen_images() -> None:
 class FrozenImages:
     """The matrix-core weight images of ONE frozen ``nn.Linear`` weight, kept across calls (``nrl_linear_fwd_img`` /
     ``nrl_linear_bwd_img``): the forward's and the backward's (transposed) image each in its own buffer, rebuilt when the
-    weight tensor was modified in place or replaced (its version counter / storage address), when the engine or the
+    weight tensor was modified in place or replaced (its version counter / storage address / ``tensor_serial``), when the engine or the
     kernel-selection switches changed, after ``invalidate()`` (``NrlLinear`` calls it from ``load_state_dict`` and whenever
     it sees the weight trainable, so a trained-then-refrozen layer never meets an old image) or after the module-wide
     ``invalidate_frozen_images()``.  For weights NO optimizer updates: the fused Adam writes parameters through raw
@@ -720,9 +747,9 @@ class FrozenImages:
 
     def __init__(self, allow_trainable: bool = False):
         # allow_trainable: images of a TRAINABLE weight, valid within one optimizer step (the PLM encoder is called twice per
-        # step -- history, candidates -- and every trainable projection rebuilt its forward and its backward image in both
-        # calls).  Sound only because every writer of such a weight moves the key: torch.optim's in-place updates bump the
-        # tensor's version counter, this library's FusedAdam bumps the module-wide generation (``begin_step``).
+        # calls).  Sound only because every writer of such a weight moves the key: every torch.optim step bumps the module-wide
+        # generation (a global step hook: the fused torch Adam moves no version counter), this library's FusedAdam bumps it too
+        # (``begin_step``).
         self._buf = {}
         self._key = {}
         self._allow_trainable = bool(allow_trainable)
@@ -735,7 +762,7 @@ class FrozenImages:
         if w.requires_grad and not self._allow_trainable:
             self.invalidate()
             return None, 0, None
-        key = (w.data_ptr(), w._version, tuple(w.shape), _lib.engine_code(), _lib.options_word(), str(device),
+        key = (w.data_ptr(), w._version, tuple(w.shape), tensor_serial(w), _lib.engine_code(), _lib.options_word(), str(device),
                _IMAGE_GENERATION[0], _STEP_GENERATION[0] if self._allow_trainable else 0, bool(w.requires_grad))
         buf = self._buf.get(which)
         if buf is None or buf.device != device:
@@ -754,7 +781,7 @@ class FrozenImages:
         if trainable and not self._allow_trainable:
             self.invalidate()
             return None, 0, None
-        key = (tuple((w.data_ptr(), w._version, tuple(w.shape), bool(w.requires_grad)) for w in weights), _lib.engine_code(),
+        key = (tuple((w.data_ptr(), w._version, tuple(w.shape), tensor_serial(w), bool(w.requires_grad)) for w in weights), _lib.engine_code(),
                _lib.options_word(), str(device), _IMAGE_GENERATION[0], _STEP_GENERATION[0] if self._allow_trainable else 0)
         buf = self._buf.get(which)
         if buf is None or buf.device != device or buf.numel() < nbytes:

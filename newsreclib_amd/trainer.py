@@ -1076,6 +1076,7 @@ class NRMSTrainer:
         if next_batch is None or self._side is None or not hasattr(self.module, "_prepare"):
             self._next = None
             return
+        cache = {}
         main = torch.cuda.current_stream()
         self._side.wait_stream(main)           # (this step's begin(): marks written, rows caught up; last step's update)
         world = dist.get_world_size(self.group) if dist.is_available() and dist.is_initialized() else 1
@@ -1087,15 +1088,16 @@ class NRMSTrainer:
             if world == 1:
                 # the ids of every lazy table are built HERE, on the stream that just produced x_all (an encoder registered under
                 # several attributes concatenates them: on the launch stream that read raced the side stream's writes, and the
-                # fresh tensor never matched the hint -- round-5 advisor), and kept on the prepared batch: the next ``step``
-                # hands ``begin`` the SAME tensor, which is how a hint is recognised
-                cache = nb.setdefault("_lazy_ids", {})
+                # fresh tensor never matched the hint -- round-5 advisor), and kept by the trainer next to the batch they were
+                # built from: the next ``step`` hands ``begin`` the SAME tensor, which is how a hint is recognised.  (Not on the
+                # batch dict: ``_prepare`` returns a caller's already-prepared dict as it is, and a dict reused with refilled ids
+                # or handed to another trainer would carry ids that no longer name its rows.)
                 for i, (tab, ids_of) in enumerate(self.lazy_tables):
                     ids = ids_of(nb)
                     ids.record_stream(main)
                     cache[i] = ids
                     tab.hint(ids, self._side)
-        self._next = (next_batch, nb)
+        self._next = (next_batch, nb, cache)
 
     def _prefetch_pending(self) -> None:
         nb, self._pending_next = getattr(self, "_pending_next", None), None
@@ -1108,11 +1110,12 @@ class NRMSTrainer:
         the optimizer arithmetic is bit-identical to the in-line form (``test_lazy_table_adam_early_catch_up_is_bit_identical_to_
         dense_adam``); two RUNS of a step still differ at the 1e-7 level, as any two runs do (the backward's atomics)."""
         nxt = getattr(self, "_next", None)
+        cached = {}                            # lazy-table ids built by the prefetch of THIS batch
         if nxt is not None:
             if not getattr(self, "_side_joined", False) and self._side is not None:
                 torch.cuda.current_stream().wait_stream(self._side)     # (no end-of-backward join happened: join here)
             if nxt[0] is batch:
-                batch = nxt[1]
+                batch, cached = nxt[1], nxt[2]
         self._next = None
         self._side_joined = False
         # (nn.Module.train() walks every submodule and rebinds the flag: 80 us of host time per step when called blindly; the
@@ -1133,7 +1136,6 @@ class NRMSTrainer:
                 xa = batch.get("x_all", {})
                 if torch.is_tensor(xa.get("title")):
                     self.reduce.prepare(xa["title"], xa.get("title_order"))
-            cached = batch.get("_lazy_ids") or {}
             for i, (tab, ids_of) in enumerate(self.lazy_tables):
                 ids = cached.get(i)
                 tab.begin(ids if ids is not None else ids_of(batch), self._side)

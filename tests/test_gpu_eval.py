@@ -339,8 +339,9 @@ def test_news_vector_cache_and_epoch_hooks_use_the_token_table():
     uses = MHSAAddAtt.TOKEN_TABLE_USES
     b0 = uses["built"]
     vec = NewsVectorCache(mod, table, chunk=100).build()
-    assert uses["built"] == b0 + 1
+    assert uses["built"] == b0 + 1                          # one build per build() (the table is freed when it returns)
     te = mod.news_encoder.text_encoders["title"]
+    assert te._tt_buf is None
     orig = te.token_table
     import contextlib
     te.token_table = lambda: contextlib.nullcontext()       # the same pass with the table out of the way
@@ -362,7 +363,7 @@ def test_news_vector_cache_and_epoch_hooks_use_the_token_table():
         mod.validation_step(batch, 0)
         s1 = mod.forward(batch)
     mod.on_validation_epoch_end()
-    assert uses["forwards"] >= f0 + 2 and not te._tt_pinned
+    assert uses["forwards"] >= f0 + 2 and not te._tt_pinned and te._tt_buf is None
     os.environ["NRL_TOKEN_TABLE"] = "0"
     try:
         with torch.no_grad():
@@ -373,7 +374,10 @@ def test_news_vector_cache_and_epoch_hooks_use_the_token_table():
 
 def test_token_table_under_inference_mode(monkeypatch):
     """Lightning runs validation / test steps under ``torch.inference_mode()`` by default: the table route (key built from the
-    parameters' version counters, buffers allocated as inference tensors and reused later under ``no_grad``) must work there."""
+    parameters' version counters, buffers allocated as inference tensors) must work there, and the next scope under ``no_grad``
+    must not depend on what the inference-mode scope left behind.  Rule: one table build per outermost ``token_table()`` scope,
+    freed when the scope ends."""
+    from newsreclib_amd.news_encoder import MHSAAddAtt
     from newsreclib_amd import _lib
     _lib.set_gemm_engine("bf16x3")
     rng = np.random.default_rng(11)
@@ -383,9 +387,13 @@ def test_token_table_under_inference_mode(monkeypatch):
     with torch.no_grad():
         plain = enc(ids)
     monkeypatch.delenv("NRL_TOKEN_TABLE")
+    uses = MHSAAddAtt.TOKEN_TABLE_USES
+    b0 = uses["built"]
     with torch.inference_mode():
         with enc.token_table():
             a = enc(ids)
-    with torch.no_grad(), enc.token_table():                 # the buffer built under inference mode serves the next epoch too
+    assert enc._tt_buf is None and uses["built"] == b0 + 1   # the inference-mode table ends with its scope ...
+    with torch.no_grad(), enc.token_table():                 # ... and the next epoch builds its own under no_grad
         b = enc(ids)
+    assert uses["built"] == b0 + 2
     assert torch.equal(a, plain) and torch.equal(b, plain)
