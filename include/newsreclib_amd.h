@@ -597,6 +597,96 @@ int nrl_sdpa_bwd(const float* q, const float* k, const float* v, const uint8_t* 
                  const float* lse, int64_t n_batch, int32_t seq_len, int32_t num_heads, int32_t head_dim, float scale,
                  double p_drop, uint64_t seed, uint32_t stream0, float* dq, float* dk, float* dv, void* stream);
 
+/* ---- NPA (npa_module.py:208-252): personalized attention ----------------------------------------------------------------
+ * Dropout streams of one NPA step (seed shared; flat indices row-major over the named shapes):
+ *   stream0      x = dropout(emb[ids])            (N, L, D)   N = history rows then candidate rows
+ *   stream0 + 1  c = dropout(relu(conv(x)))       (N, L, F)
+ *   stream0 + 2  u = dropout(E_u[user_idx])       (B, U)      UserProjection
+ *   stream0 + 3  history text query  dropout      (B, Pw)     first CNNPersAtt call
+ *   stream0 + 4  candidate text query dropout     (B, Pw)     second CNNPersAtt call
+ *   stream0 + 5  news query dropout               (B, Pn)     user encoder
+ * The encoder takes stream0; nrl_npa_user_queries_* take the base of their four streams (stream0 + 2 above). */
+
+/* CNNPersAtt.forward (text.py:376-392) over the history and candidate rows in one call: ids (N, L) -> out (N, F).
+ * x and c as nrl_cnn_encoder_fwd (`p` supplies conv_weight / conv_bias and the dims; its att_* fields and query_dim are
+ * ignored); then row n attends over ALL L tokens (pad tokens included, as the reference) with the query row
+ * queries[owner[n]] of the (n_queries, F) table: s_t = q . c_t, w = softmax(s), out = sum_t w_t c_t.  owner (N) int32;
+ * a row whose owner is outside [0, n_queries) gets a zero query. */
+size_t nrl_npa_encoder_workspace_bytes(int64_t n_news, int32_t seq_len, int32_t embed_dim, int32_t num_filters,
+                                       int32_t window);
+int nrl_npa_encoder_fwd(const NrlCnnParams* p, const float* emb_table, int64_t vocab, const int64_t* ids, int64_t n_news,
+                        int32_t seq_len, const float* queries, const int32_t* owner, int64_t n_queries, double p_drop,
+                        uint64_t seed, uint32_t stream0, int32_t save_for_backward, float* out, void* ws, size_t ws_bytes,
+                        void* stream);
+/* Backward: adds into g->conv_weight, g->conv_bias and d_emb_table (the att_* fields of `g` are ignored); WRITES
+ * d_queries (n_queries, F) = the sum of the rows' query gradients over the row ranges [query_offsets[i], query_offsets[i+1])
+ * (n_queries + 1 int64, rows of one query contiguous), summed in row order.  sorted_positions as nrl_cnn_encoder_bwd. */
+int nrl_npa_encoder_bwd(const NrlCnnParams* p, const NrlCnnGrads* g, float* d_emb_table, int64_t vocab, const int64_t* ids,
+                        const int64_t* sorted_positions, int64_t n_news, int32_t seq_len, const float* queries,
+                        const int32_t* owner, const int64_t* query_offsets, int64_t n_queries, double p_drop,
+                        uint64_t seed, uint32_t stream0, const float* d_out, float* d_queries, void* ws, size_t ws_bytes,
+                        void* stream);
+
+/* Every per-user query of an NPA step in one launch.  Field <-> reference state_dict key:
+ *   user_table        user_projection.user_embed                                                   (num_users, U)
+ *   text_proj_*       news_encoder.text_query_projection.preference_query_projection.{weight,bias}   (Pw, U), (Pw)
+ *   text_att_*        news_encoder.personalized_attention.preference_query_projection.{weight,bias}  (F, Pw), (F)
+ *   news_proj_*       user_encoder.news_query_projection.preference_query_projection.{weight,bias}   (Pn, U), (Pn)
+ *   news_att_*        user_encoder.personalized_attention.preference_query_projection.{weight,bias}  (F, Pn), (F)
+ * news_* NULL: late fusion (no user encoder).  Any U (no multiple-of-4 rule). */
+typedef struct NrlNpaQueryParams {
+  const float* user_table;
+  const float* text_proj_weight;
+  const float* text_proj_bias;
+  const float* text_att_weight;
+  const float* text_att_bias;
+  const float* news_proj_weight;
+  const float* news_proj_bias;
+  const float* news_att_weight;
+  const float* news_att_bias;
+  int64_t num_users;
+  int32_t user_dim;        /* U */
+  int32_t text_query_dim;  /* Pw */
+  int32_t news_query_dim;  /* Pn */
+  int32_t num_filters;     /* F */
+} NrlNpaQueryParams;
+
+typedef struct NrlNpaQueryGrads { /* accumulators, kernels ADD */
+  float* user_table;
+  float* text_proj_weight;
+  float* text_proj_bias;
+  float* text_att_weight;
+  float* text_att_bias;
+  float* news_proj_weight;
+  float* news_proj_bias;
+  float* news_att_weight;
+  float* news_att_bias;
+} NrlNpaQueryGrads;
+
+/* u = dropout(E_u[user_idx]) (stream0); per user b:
+ *   text_queries[b]     = tanh(W_ta dropout(relu(W_tp u + b_tp)) + b_ta)   dropout stream0 + 1 (history)
+ *   text_queries[B + b] = the same with dropout stream0 + 2                (candidates)
+ *   news_queries[b]     = tanh(W_na dropout(relu(W_np u + b_np)) + b_na)   dropout stream0 + 3 (NULL under late fusion)
+ * user_idx (B) int64; an index outside [0, num_users) reads a zero user vector and gets no gradient. */
+size_t nrl_npa_user_queries_workspace_bytes(const NrlNpaQueryParams* p, int64_t batch);
+int nrl_npa_user_queries_fwd(const NrlNpaQueryParams* p, const int64_t* user_idx, int64_t batch, double p_drop,
+                             uint64_t seed, uint32_t stream0, float* text_queries, float* news_queries, void* stream);
+/* Recomputes the forward and adds every gradient into `g`; a user that appears in several impressions of the batch gets the
+ * sum over them, in batch order (no float atomics anywhere). */
+int nrl_npa_user_queries_bwd(const NrlNpaQueryParams* p, const NrlNpaQueryGrads* g, const int64_t* user_idx, int64_t batch,
+                             double p_drop, uint64_t seed, uint32_t stream0, const float* d_text_queries,
+                             const float* d_news_queries, void* ws, size_t ws_bytes, void* stream);
+
+/* NPA user encoder (user/npa.py:48-60) on the ragged history rows hist (n_hist, dim), rows of user b in
+ * [hist_offsets[b], hist_offsets[b+1]): the reference runs it on the to_dense_batch output, so each user's softmax also
+ * counts (max_hist - n_b) zero rows with score 0 -- a user's vector depends on the longest history of the batch.
+ * out (B, dim) = sum_i w_i hist_i.  _bwd WRITES d_hist (n_hist, dim) and d_queries (B, dim). */
+int nrl_personalized_user_attention_fwd(const float* hist, const int64_t* hist_offsets, int64_t batch, int32_t max_hist,
+                                        int32_t dim, const float* queries, float* out, void* stream);
+int nrl_personalized_user_attention_bwd(const float* hist, const int64_t* hist_offsets, int64_t batch, int32_t max_hist,
+                                        int32_t dim, const float* queries, const float* d_out, float* d_hist,
+                                        float* d_queries, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -48,6 +48,20 @@ class NrlCnnGrads(ctypes.Structure):
                 ("att_bias", c_void_p), ("att_query", c_void_p)]
 
 
+class NrlNpaQueryParams(ctypes.Structure):
+    _fields_ = [("user_table", c_void_p), ("text_proj_weight", c_void_p), ("text_proj_bias", c_void_p),
+                ("text_att_weight", c_void_p), ("text_att_bias", c_void_p), ("news_proj_weight", c_void_p),
+                ("news_proj_bias", c_void_p), ("news_att_weight", c_void_p), ("news_att_bias", c_void_p),
+                ("num_users", c_int64), ("user_dim", c_int32), ("text_query_dim", c_int32), ("news_query_dim", c_int32),
+                ("num_filters", c_int32)]
+
+
+class NrlNpaQueryGrads(ctypes.Structure):
+    _fields_ = [("user_table", c_void_p), ("text_proj_weight", c_void_p), ("text_proj_bias", c_void_p),
+                ("text_att_weight", c_void_p), ("text_att_bias", c_void_p), ("news_proj_weight", c_void_p),
+                ("news_proj_bias", c_void_p), ("news_att_weight", c_void_p), ("news_att_bias", c_void_p)]
+
+
 class NrlGruParams(ctypes.Structure):
     _fields_ = [("weight_ih", c_void_p), ("weight_hh", c_void_p), ("bias_ih", c_void_p), ("bias_hh", c_void_p),
                 ("input_dim", c_int32), ("hidden_dim", c_int32)]
@@ -151,6 +165,23 @@ SIGNATURES = {
                                            POINTER(NrlBlockGrads), c_void_p, c_int64, c_void_p, c_void_p, c_int64,
                                            c_int32, c_double, c_uint64, c_uint32, c_void_p, c_void_p, c_size_t,
                                            c_void_p]),
+    "nrl_npa_encoder_workspace_bytes": (c_size_t, [c_int64, c_int32, c_int32, c_int32, c_int32]),
+    "nrl_npa_encoder_fwd": (c_int32, [POINTER(NrlCnnParams), c_void_p, c_int64, c_void_p, c_int64, c_int32, c_void_p,
+                                      c_void_p, c_int64, c_double, c_uint64, c_uint32, c_int32, c_void_p, c_void_p,
+                                      c_size_t, c_void_p]),
+    "nrl_npa_encoder_bwd": (c_int32, [POINTER(NrlCnnParams), POINTER(NrlCnnGrads), c_void_p, c_int64, c_void_p,
+                                      c_void_p, c_int64, c_int32, c_void_p, c_void_p, c_void_p, c_int64, c_double,
+                                      c_uint64, c_uint32, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "nrl_npa_user_queries_workspace_bytes": (c_size_t, [POINTER(NrlNpaQueryParams), c_int64]),
+    "nrl_npa_user_queries_fwd": (c_int32, [POINTER(NrlNpaQueryParams), c_void_p, c_int64, c_double, c_uint64, c_uint32,
+                                           c_void_p, c_void_p, c_void_p]),
+    "nrl_npa_user_queries_bwd": (c_int32, [POINTER(NrlNpaQueryParams), POINTER(NrlNpaQueryGrads), c_void_p, c_int64,
+                                           c_double, c_uint64, c_uint32, c_void_p, c_void_p, c_void_p, c_size_t,
+                                           c_void_p]),
+    "nrl_personalized_user_attention_fwd": (c_int32, [c_void_p, c_void_p, c_int64, c_int32, c_int32, c_void_p, c_void_p,
+                                                      c_void_p]),
+    "nrl_personalized_user_attention_bwd": (c_int32, [c_void_p, c_void_p, c_int64, c_int32, c_int32, c_void_p, c_void_p,
+                                                      c_void_p, c_void_p, c_void_p]),
     "nrl_embedding_rows_fwd": (c_int32, [c_void_p, c_void_p, c_int64, c_int32, c_double, c_uint64, c_uint32,
                                          c_void_p, c_void_p]),
     "nrl_embedding_rows_bwd": (c_int32, [c_void_p, c_void_p, c_int64, c_int32, c_double, c_uint64, c_uint32,

@@ -356,6 +356,49 @@ static int gru_check(const NrlGruParams* p, int64_t B, int64_t T, GruShape* s) {
   return NRL_OK;
 }
 
+// dx[m, d] = dropout1 * sum_{t', f} dc[m + t' - pad', f] Wc[f, (W-1-t')*D + d], then the table gradient from dx (or scattered
+// straight into the table without sorted positions).  dc in fp32 rows, or ONLY as planes when dc_pl.
+static int cnn_dx_table_grad(const NrlCnnParams* p, const CnnShape& s, const CnnWs& w, const CnnRp& rp, bool dc_pl,
+                             const int64_t* ids, const int64_t* sorted_positions, const Dropout& drop1, float* d_emb_table,
+                             hipStream_t st) {
+  const int KF = s.W * s.F;
+  const KCWindow a{w.dc, s.M, s.F, s.L, s.W, s.W - 1 - s.pad};
+  const RCConvT b_rc{p->conv_weight, s.F, s.D, s.W, (int64_t)s.D};
+  const int Kp = (KF + 31) / 32 * 32;
+  uint16_t* hi = w.planes_conv_t;
+  uint16_t* lo = hi + 32;
+  const RpImage* rpd = rp.on ? &rp.conv_d : nullptr;
+  if (cur_engine() == ENGINE_BF16X3 && !rp.on) {
+    const int64_t total = (int64_t)s.D * Kp;
+    hipLaunchKernelGGL(split_conv_weight_t_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st,
+                       p->conv_weight, s.F, s.D, s.W, Kp, hi);
+    NRL_LAUNCH_CHECK();
+  }
+  static const bool live_env = [] { const char* e = getenv("NRL_LIVE_ROWS"); return !(e != nullptr && e[0] == '0'); }();
+  if (sorted_positions != nullptr && rpd != nullptr && live_env) {
+    // dx for the LIVE token rows only (id != 0), compact in position order: the padding id has no table gradient and
+    // nothing else reads dx.  The list of live positions goes into the tanh / d_pre buffer (dead by now).
+    NRL_REQUIRE((size_t)s.M * s.Q >= live_compact_ints(s.M), "cnn_encoder_bwd: scratch for the live-row list");
+    const int32_t *list = nullptr, *cidx = nullptr, *n_live = nullptr;
+    NRL_TRY(live_compact(ids, s.M, reinterpret_cast<int32_t*>(w.t), &list, &cidx, &n_live, st));
+    if (dc_pl) {
+      const int ncb_dc = cnn_ncb_dc(s);
+      const KCWindowPlanes ap{w.dpl, s.M, s.L, 2 * cnn_conv_kt(s), ncb_dc, s.W, s.W - 1 - s.pad};
+      NRL_TRY(rp_dispatch(KCWindowLivePlanes{ap, list, n_live}, rp.conv_dp, EpiDxLive{w.dx, s.D, drop1, list}, s.M, s.D,
+                          s.W * 16 * ncb_dc, st));
+    } else {
+    NRL_TRY(rp_dispatch(KCWindowLive{a, list, n_live}, *rpd, EpiDxLive{w.dx, s.D, drop1, list}, s.M, s.D, KF, st));
+    }
+    NRL_TRY(embedding_grad_sorted(w.dx, ids, sorted_positions, s.M, s.D, d_emb_table, st, cidx));
+  } else if (sorted_positions != nullptr) {
+    NRL_TRY(gemm_any(a, b_rc, hi, lo, 2 * Kp, EpiLinear{w.dx, s.D, nullptr, 0, drop1, s.D}, s.M, s.D, KF, st, rpd));
+    NRL_TRY(embedding_grad_sorted(w.dx, ids, sorted_positions, s.M, s.D, d_emb_table, st));
+  } else {
+    NRL_TRY(gemm_any(a, b_rc, hi, lo, 2 * Kp, EpiScatter{d_emb_table, ids, s.D, drop1}, s.M, s.D, KF, st, rpd));
+  }
+  return NRL_OK;
+}
+
 }  // namespace nrl
 
 using namespace nrl;
@@ -448,7 +491,6 @@ int nrl_cnn_encoder_bwd(const NrlCnnParams* p, const NrlCnnGrads* g, float* d_em
   NRL_TRY(cnn_carve(ws, ws_bytes, s, &w));
   hipStream_t st = (hipStream_t)stream;
   const Dropout drop1 = make_dropout(p_drop, seed, stream0), drop2 = make_dropout(p_drop, seed, stream0 + 1);
-  const int KF = s.W * s.F;
   const SplitWeight sa = planes_view(w.planes_att, s.Q, s.F);
   CnnRp rp;
   NRL_TRY(cnn_rp_images(p, s, w, false, &rp, st));        // built by the forward; weights unchanged since
@@ -485,44 +527,7 @@ int nrl_cnn_encoder_bwd(const NrlCnnParams* p, const NrlCnnGrads* g, float* d_em
   NRL_TRY(gemm_wgrad(w.t, s.Q, w.c, s.F, g->att_weight, g->att_bias, s.M, st));
   }
   NRL_TRY(cnn_conv_wgrad(s, w, w.dc, w.x, s.F, g->conv_weight, g->conv_bias, st, x_pl, dc_pl));
-  // dx[m, d] = dropout1 * sum_{t', f} dc[m + t' - pad', f] Wc[f, (W-1-t')*D + d]
-  {
-    const KCWindow a{w.dc, s.M, s.F, s.L, s.W, s.W - 1 - s.pad};
-    const RCConvT b_rc{p->conv_weight, s.F, s.D, s.W, (int64_t)s.D};
-    const int Kp = (KF + 31) / 32 * 32;
-    uint16_t* hi = w.planes_conv_t;
-    uint16_t* lo = hi + 32;
-    const RpImage* rpd = rp.on ? &rp.conv_d : nullptr;
-    if (cur_engine() == ENGINE_BF16X3 && !rp.on) {
-      const int64_t total = (int64_t)s.D * Kp;
-      hipLaunchKernelGGL(split_conv_weight_t_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st,
-                         p->conv_weight, s.F, s.D, s.W, Kp, hi);
-      NRL_LAUNCH_CHECK();
-    }
-    static const bool live_env = [] { const char* e = getenv("NRL_LIVE_ROWS"); return !(e != nullptr && e[0] == '0'); }();
-    if (sorted_positions != nullptr && rpd != nullptr && live_env) {
-      // dx for the LIVE token rows only (id != 0), compact in position order: the padding id has no table gradient and
-      // nothing else reads dx.  The list of live positions goes into the tanh / d_pre buffer (dead by now).
-      NRL_REQUIRE((size_t)s.M * s.Q >= live_compact_ints(s.M), "cnn_encoder_bwd: scratch for the live-row list");
-      const int32_t *list = nullptr, *cidx = nullptr, *n_live = nullptr;
-      NRL_TRY(live_compact(ids, s.M, reinterpret_cast<int32_t*>(w.t), &list, &cidx, &n_live, st));
-      if (dc_pl) {
-        const int ncb_dc = cnn_ncb_dc(s);
-        const KCWindowPlanes ap{w.dpl, s.M, s.L, 2 * cnn_conv_kt(s), ncb_dc, s.W, s.W - 1 - s.pad};
-        NRL_TRY(rp_dispatch(KCWindowLivePlanes{ap, list, n_live}, rp.conv_dp, EpiDxLive{w.dx, s.D, drop1, list}, s.M, s.D,
-                            s.W * 16 * ncb_dc, st));
-      } else {
-      NRL_TRY(rp_dispatch(KCWindowLive{a, list, n_live}, *rpd, EpiDxLive{w.dx, s.D, drop1, list}, s.M, s.D, KF, st));
-      }
-      NRL_TRY(embedding_grad_sorted(w.dx, ids, sorted_positions, s.M, s.D, d_emb_table, st, cidx));
-    } else if (sorted_positions != nullptr) {
-      NRL_TRY(gemm_any(a, b_rc, hi, lo, 2 * Kp, EpiLinear{w.dx, s.D, nullptr, 0, drop1, s.D}, s.M, s.D, KF, st, rpd));
-      NRL_TRY(embedding_grad_sorted(w.dx, ids, sorted_positions, s.M, s.D, d_emb_table, st));
-    } else {
-      NRL_TRY(gemm_any(a, b_rc, hi, lo, 2 * Kp, EpiScatter{d_emb_table, ids, s.D, drop1}, s.M, s.D, KF, st, rpd));
-    }
-  }
-  return NRL_OK;
+  return cnn_dx_table_grad(p, s, w, rp, dc_pl, ids, sorted_positions, drop1, d_emb_table, st);
 }
 
 // ---- CNN + multi-head self-attention + additive attention text encoder (CenNewsRec) ----------------------
@@ -749,6 +754,109 @@ int nrl_gru_bwd(const NrlGruParams* p, const NrlGruGrads* g, const float* hist, 
   NRL_TRY(gemm_wgrad(w.g, 3 * Hd, w.x_tm, Din, g->weight_ih, g->bias_ih, T * B, st));
   NRL_TRY(gemm_wgrad(w.dgh, 3 * Hd, w.hs, Hd, g->weight_hh, g->bias_hh, T * B, st));
   return NRL_OK;
+}
+
+}  // extern "C"
+
+// ---- NPA text encoder (CNNPersAtt, text.py:376-392): the convolution stages of nrl_cnn_encoder_* and the personalized pooling --
+// (the additive-attention buffers of the CNN workspace are not used: Q = 16 sizes only the scratch of the live-row list)
+static CnnShape npa_shape(int64_t n_news, int L, int D, int F, int W) {
+  CnnShape s;
+  s.N = n_news; s.L = L; s.M = n_news * L; s.D = D; s.F = F; s.W = W; s.Q = 16; s.pad = (W - 1) / 2;
+  return s;
+}
+
+static int npa_check(const NrlCnnParams* p, int64_t n_news, int L, const float* queries, const int32_t* owner,
+                     int64_t n_queries, CnnShape* s) {
+  NRL_REQUIRE(p != nullptr && p->conv_weight && p->conv_bias && queries && owner, "npa_encoder: null argument");
+  NRL_REQUIRE(p->embed_dim > 0 && p->embed_dim % 4 == 0, "embed_dim must be a positive multiple of 4");
+  NRL_REQUIRE(p->num_filters > 0 && p->num_filters % 4 == 0, "num_filters must be a positive multiple of 4");
+  NRL_REQUIRE(p->window >= 1 && p->window <= 7 && p->window % 2 == 1, "window must be odd and <= 7");
+  NRL_REQUIRE(n_news >= 0 && L > 0 && n_queries >= 0, "bad news batch shape");
+  NRL_REQUIRE(((uintptr_t)p->conv_weight & 15) == 0 && ((uintptr_t)queries & 15) == 0, "weights must be 16-byte aligned");
+  *s = npa_shape(n_news, L, p->embed_dim, p->num_filters, p->window);
+  NRL_REQUIRE(s->M * (int64_t)(s->D > s->F ? s->D : s->F) < (1LL << 32), "dropout index space is 32-bit");
+  return NRL_OK;
+}
+
+static size_t npa_ws_floats(const CnnShape& s) { return cnn_ws_floats(s) + align_up((size_t)s.N * s.F, 64); }
+
+extern "C" {
+
+size_t nrl_npa_encoder_workspace_bytes(int64_t n_news, int32_t seq_len, int32_t embed_dim, int32_t num_filters,
+                                       int32_t window) {
+  return npa_ws_floats(npa_shape(n_news, seq_len, embed_dim, num_filters, window)) * sizeof(float);
+}
+
+int nrl_npa_encoder_fwd(const NrlCnnParams* p, const float* emb_table, int64_t vocab, const int64_t* ids, int64_t n_news,
+                        int32_t seq_len, const float* queries, const int32_t* owner, int64_t n_queries, double p_drop,
+                        uint64_t seed, uint32_t stream0, int32_t save_for_backward, float* out, void* ws, size_t ws_bytes,
+                        void* stream) {
+  (void)vocab;
+  CnnShape s;
+  NRL_TRY(npa_check(p, n_news, seq_len, queries, owner, n_queries, &s));
+  NRL_REQUIRE(emb_table && ids && out, "npa_encoder_fwd: null argument");
+  NRL_REQUIRE(p_drop >= 0.0 && p_drop < 1.0, "p_drop must be in [0, 1)");
+  if (s.M == 0) return NRL_OK;
+  NRL_REQUIRE(ws_bytes >= npa_ws_floats(s) * sizeof(float), "npa_encoder_fwd: workspace too small");
+  CnnWs w;
+  NRL_TRY(cnn_carve(ws, ws_bytes, s, &w));
+  hipStream_t st = (hipStream_t)stream;
+  const Dropout drop1 = make_dropout(p_drop, seed, stream0), drop2 = make_dropout(p_drop, seed, stream0 + 1);
+  const int KD = s.W * s.D;
+  SplitWeight sc = planes_view(w.planes_conv, s.F, KD);
+  CnnRp rp;
+  NRL_TRY(cnn_rp_images(p, s, w, true, &rp, st));
+  if (cur_engine() == ENGINE_BF16X3 && !rp.on) NRL_TRY(split_weight(p->conv_weight, s.F, KD, w.planes_conv, &sc, st));
+  // x = dropout(emb[ids]); c = dropout(relu(conv(x) + b))             (text.py:377-383), as nrl_cnn_encoder_fwd
+  const EpiLinear epi_c{w.c, s.F, p->conv_bias, 2, drop2, s.F};
+  if (cnn_x_planes_on(s) && rp.on && w.xpl != nullptr) {
+    const int ncb_x = cnn_ncb_x(s), nrb = 2 * cnn_conv_kt(s);
+    NRL_TRY(launch_embedding_rows_planes(emb_table, ids, s.N, s.L, s.D, ncb_x, nrb, drop1, w.xpl, st));
+    NRL_TRY(rp_dispatch(KCWindowPlanes{w.xpl, s.M, s.L, nrb, ncb_x, s.W, s.pad}, rp.conv_f, epi_c, s.M, s.F,
+                        s.W * 16 * ncb_x, st));
+  } else {
+    NRL_TRY(embedding_rows_fwd(emb_table, ids, s.M, s.D, drop1, 0, w.x, st));
+    const KCWindow a{w.x, s.M, s.D, s.L, s.W, s.pad};
+    if (cur_engine() == ENGINE_BF16X3) {
+      NRL_TRY(gemm_any(a, KCPlain{p->conv_weight, KD, s.F}, sc.hi, sc.lo, sc.ld, epi_c, s.M, s.F, KD, st,
+                       rp.on ? &rp.conv_f : nullptr));
+    } else {
+      NRL_TRY(launch_gemm<NRL_TILE>(a, KCPlain{p->conv_weight, KD, s.F}, epi_c, s.M, s.F, KD, 1, st));
+    }
+  }
+  // w = softmax_t(queries[owner[n]] . c_t); out = sum_t w_t c_t     (attention.py:244-259)
+  return npa_pool_fwd(w.c, queries, owner, n_queries, s.N, s.L, s.F, save_for_backward != 0 ? w.w : nullptr, out, st);
+}
+
+int nrl_npa_encoder_bwd(const NrlCnnParams* p, const NrlCnnGrads* g, float* d_emb_table, int64_t vocab, const int64_t* ids,
+                        const int64_t* sorted_positions, int64_t n_news, int32_t seq_len, const float* queries,
+                        const int32_t* owner, const int64_t* query_offsets, int64_t n_queries, double p_drop,
+                        uint64_t seed, uint32_t stream0, const float* d_out, float* d_queries, void* ws, size_t ws_bytes,
+                        void* stream) {
+  (void)vocab;
+  CnnShape s;
+  NRL_TRY(npa_check(p, n_news, seq_len, queries, owner, n_queries, &s));
+  NRL_REQUIRE(g && g->conv_weight && g->conv_bias, "null CNN gradient pointer");
+  NRL_REQUIRE(d_emb_table && ids && d_out && d_queries && query_offsets, "npa_encoder_bwd: null argument");
+  hipStream_t st = (hipStream_t)stream;
+  if (s.M == 0) {
+    if (n_queries > 0) NRL_HIP(hipMemsetAsync(d_queries, 0, (size_t)n_queries * s.F * sizeof(float), st));
+    return NRL_OK;
+  }
+  NRL_REQUIRE(ws_bytes >= npa_ws_floats(s) * sizeof(float), "npa_encoder_bwd: workspace too small");
+  CnnWs w;
+  NRL_TRY(cnn_carve(ws, ws_bytes, s, &w));
+  float* dq = reinterpret_cast<float*>(ws) + cnn_ws_floats(s);
+  const Dropout drop1 = make_dropout(p_drop, seed, stream0), drop2 = make_dropout(p_drop, seed, stream0 + 1);
+  CnnRp rp;
+  NRL_TRY(cnn_rp_images(p, s, w, false, &rp, st));        // built by the forward; weights unchanged since
+  const bool x_pl = cnn_x_planes_on(s) && rp.on && w.xpl != nullptr;
+  // dc = (w d_out + ds q) * dropout2 * [c > 0] (pre-ReLU, fp32 rows), dq per row; then the per-query sums
+  NRL_TRY(npa_pool_bwd(d_out, w.c, w.w, queries, owner, n_queries, s.N, s.L, s.F, drop2, w.dc, dq, st));
+  NRL_TRY(npa_query_grad(dq, query_offsets, n_queries, s.F, d_queries, st));
+  NRL_TRY(cnn_conv_wgrad(s, w, w.dc, w.x, s.F, g->conv_weight, g->conv_bias, st, x_pl, false));
+  return cnn_dx_table_grad(p, s, w, rp, false, ids, sorted_positions, drop1, d_emb_table, st);
 }
 
 }  // extern "C"

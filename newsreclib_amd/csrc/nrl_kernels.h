@@ -51,6 +51,15 @@ int pool_bwd_pre(const float* d_out, const float* y, const float* w, float* t_dp
                  const float* q_a, float* dq_a, int64_t groups, int S, int Q, int D,
                  hipStream_t stream, void* dpre_planes = nullptr, const void* y_planes = nullptr);
 
+// NPA text-encoder pooling (nrl_npa.hip): row n of c (N, L, F) attends with query row Qw[owner[n]] over all L tokens;
+// w (N, L) is written when not null.  _bwd writes the conv pre-activation gradient dc (N, L, F) (times dropout2 and the ReLU
+// gate [c > 0]) and the per-row query gradient dq (N, F); npa_query_grad sums dq over rows [seg[i], seg[i+1]) into dQw[i].
+int npa_pool_fwd(const float* c, const float* Qw, const int32_t* owner, int64_t n_queries, int64_t N, int L, int F,
+                 float* w, float* out, hipStream_t stream);
+int npa_pool_bwd(const float* d_out, const float* c, const float* w, const float* Qw, const int32_t* owner,
+                 int64_t n_queries, int64_t N, int L, int F, Dropout drop2, float* dc, float* dq, hipStream_t stream);
+int npa_query_grad(const float* dq, const int64_t* seg, int64_t n_queries, int F, float* dQw, hipStream_t stream);
+
 int to_dense_fwd(const float* x, const int64_t* offsets, int64_t B, int64_t max_len, int D,
                  float* dense, hipStream_t stream);
 int to_dense_bwd(const float* d_dense, const int64_t* offsets, int64_t B, int64_t max_len, int D,

@@ -220,6 +220,46 @@ class CNNMHSAAddAtt(nn.Module):
                                                 stream0, bufs if any(b is not None for b in bufs) else None, order)
 
 
+class CNNPersAtt(nn.Module):
+    """NPA text encoder (reference text.py:312-392): embedding lookup -> dropout -> Conv1d over tokens -> ReLU -> dropout ->
+    personalized attention with one query per (user, call) as one HIP pipeline (``nrl_npa_encoder_fwd``/``_bwd``).  The
+    text query itself (``text_query_projection`` + the query side of ``personalized_attention``) is computed for every
+    user of the batch by ``ops_npa.NpaUserQueriesFn``; ``forward`` takes that table.  ``cnn`` is an ``nn.Conv1d`` as in
+    the reference, permuted to the kernels' (F, W, D) order on the way in."""
+
+    def __init__(self, pretrained_embeddings: torch.Tensor, text_embed_dim: int, user_embed_dim: int, num_filters: int,
+                 window_size: int, query_dim: int, dropout_probability: float) -> None:
+        super().__init__()
+        from .npa_layers import PersonalizedAttention, UserPreferenceQueryProjection
+        if not isinstance(dropout_probability, float):
+            raise ValueError(
+                f"Expected keyword argument `dropout_probability` to be a `float` but got {dropout_probability}")
+        if window_size != 3:
+            raise NotImplementedError("the reference hard-codes padding=1 (text.py:361): only window_size=3 keeps the "
+                                      "token count the personalized attention runs over")
+        self.embedding_layer = nn.Embedding.from_pretrained(
+            torch.as_tensor(pretrained_embeddings, dtype=torch.float32), freeze=False, padding_idx=0)
+        self.cnn = nn.Conv1d(in_channels=text_embed_dim, out_channels=num_filters, kernel_size=window_size, padding=1)
+        self.text_query_projection = UserPreferenceQueryProjection(
+            user_embed_dim=user_embed_dim, preference_query_dim=query_dim, dropout_probability=dropout_probability)
+        self.personalized_attention = PersonalizedAttention(preference_query_dim=query_dim, num_filters=num_filters)
+        self.dropout = nn.Dropout(dropout_probability)
+
+    def forward(self, text: torch.Tensor, queries: torch.Tensor, owner: torch.Tensor, offsets: torch.Tensor,
+                seed: Optional[int] = None, order: Optional[torch.Tensor] = None, stream0: int = 0) -> torch.Tensor:
+        """text (N, L); queries (Q, F) tanh'd text queries; owner (N) int32 query row of each news row; offsets (Q + 1)
+        the contiguous row range of each query."""
+        from . import ops_npa
+        p = float(self.dropout.p) if self.training else 0.0
+        if p > 0.0 and seed is None:
+            seed = _draw_seed()
+        w_c = self.cnn.weight.permute(0, 2, 1).contiguous().unsqueeze(1)      # (F, D, W) -> (F, 1, W, D)
+        emb = self.embedding_layer.weight
+        bufs = (getattr(emb, "main_grad", None), None, getattr(self.cnn.bias, "main_grad", None))
+        return ops_npa.NpaEncoderFn.apply(text, emb, w_c, self.cnn.bias, queries, owner, offsets, p, seed or 0, stream0,
+                                          bufs if any(b is not None for b in bufs) else None, order)
+
+
 class LinearEncoder(nn.Module):
     """Category encoder (reference category.py:9-80) for the configuration the recommenders in scope use
     (LSTUR, lstur_module.py:173-183): a trainable ``nn.Embedding(padding_idx=0)`` lookup, no dropout, no

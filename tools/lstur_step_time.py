@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Times the LSTUR (BASELINE config 5) or NAML (--model naml) train step on one GPU: B users x 50 clicks, title 30 + abstract 50
+"""Times the LSTUR (BASELINE config 5), NAML (--model naml) or NPA (--model npa: title only, 45,215 users) train step on one GPU: B users x 50 clicks, title 30 + abstract 50
 tokens, CNN 300 filters x window 3, GRU 700.  Prints ms/step and impressions/s; with --breakdown also the
 per-kernel time from torch.profiler-free HIP events around the module's stages."""
 import argparse
@@ -19,7 +19,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--vocab", type=int, default=70000)
     ap.add_argument("--engine", default="bf16x3")
-    ap.add_argument("--model", default="lstur", choices=["lstur", "naml", "cen", "mins"])
+    ap.add_argument("--model", default="lstur", choices=["lstur", "naml", "cen", "mins", "npa"])
     args = ap.parse_args()
     from functools import partial
 
@@ -72,6 +72,15 @@ def main():
             num_gru_channels=6, top_k_list=[5, 10], num_categ_classes=18, num_sent_classes=3, save_recs=False,
             recs_fpath=None, optimizer=partial(torch.optim.Adam, lr=1e-4), scheduler=None,
             pretrained_embeddings=emb).cuda()
+    if args.model == "npa":    # configs/model/npa.yaml
+        from newsreclib_amd.npa_module import NPAModule
+        mod = NPAModule(
+            outputs={"train": [], "val": [], "test": []}, dual_loss_training=False, dual_loss_coef=None,
+            loss="cross_entropy_loss", late_fusion=False, temperature=None, pretrained_embeddings_path=None,
+            text_embed_dim=300, user_embed_dim=50, num_users=45214, num_filters=400, window_size=3,
+            word_pref_query_dim=200, news_pref_query_dim=200, dropout_probability=0.2, top_k_list=[5, 10],
+            num_categ_classes=18, num_sent_classes=3, save_recs=False, recs_fpath=None,
+            optimizer=partial(torch.optim.Adam, lr=1e-4), scheduler=None, pretrained_embeddings=emb).cuda()
     trainer = NRMSTrainer(mod, lr=1e-4)
     batch = add_lstur_fields(make_batch(args.batch, vocab=args.vocab, mode="fixed", seed=1, device="cuda"), args.vocab,
                              19, 45215, 50, seed=2)
