@@ -687,6 +687,94 @@ int nrl_personalized_user_attention_bwd(const float* hist, const int64_t* hist_o
                                         int32_t dim, const float* queries, const float* d_out, float* d_hist,
                                         float* d_queries, void* stream);
 
+/* ---- DKN (dkn_module.py:207-240): knowledge-aware CNN news encoder + candidate-aware user attention -------------------
+ * Field <-> reference state_dict key (news_encoder.*):
+ *   word_table        text_embedding_layer.weight      (vocab, D)
+ *   entity_table      entity_embedding_layer.weight    (num_entities, Ed)
+ *   context_table     context_embedding_layer.weight   (num_entities, Ed); NULL: use_context = False (2 channels)
+ *   transform_matrix  transform_matrix                 (Ed, D)
+ *   transform_bias    transform_bias                   (D)
+ *   conv_image[i]     conv_filters.{windows[i]}.weight (F, C, W, D) repacked as (F, W, C, D): the windowed GEMM's K order
+ *   conv_bias[i]      conv_filters.{windows[i]}.bias   (F)
+ * No dropout anywhere in DKN. */
+typedef struct NrlDknParams {
+  const float* word_table;
+  const float* entity_table;
+  const float* context_table;
+  const float* transform_matrix;
+  const float* transform_bias;
+  const float* conv_image[4];
+  const float* conv_bias[4];
+  int32_t windows[4];
+  int32_t num_windows;
+  int32_t word_dim;    /* D */
+  int32_t entity_dim;  /* Ed */
+  int32_t num_filters; /* F */
+} NrlDknParams;
+
+typedef struct NrlDknGrads { /* accumulators, kernels ADD; conv_weight[i] in the reference (F, C, W, D) layout */
+  float* word_table;
+  float* entity_table;
+  float* context_table;
+  float* transform_matrix;
+  float* transform_bias;
+  float* conv_weight[4];
+  float* conv_bias[4];
+} NrlDknGrads;
+
+/* KCNN.forward (news.py:255-299) on ids / entity_ids (N, L) int64 -> out (N, num_windows * F), windows in order, and the
+ * argmax (N, num_windows * F) uint8 of each max over time (the first maximal position).  Window W has L - W + 1 valid
+ * positions (no padding); W > L is refused.  The workspace of the forward must reach the backward unchanged. */
+size_t nrl_dkn_encoder_workspace_bytes(const NrlDknParams* p, int64_t n_news, int32_t seq_len);
+int nrl_dkn_encoder_fwd(const NrlDknParams* p, const int64_t* ids, const int64_t* entity_ids, int64_t n_news,
+                        int32_t seq_len, float* out, uint8_t* argmax, void* ws, size_t ws_bytes, void* stream);
+/* Backward: adds every gradient into `g`.  sorted_positions / entity_sorted_positions: the id-sorted visiting orders
+ * (nrl_sort_positions) of ids and entity_ids; the entity and context tables share the second.  Row 0 of every table gets
+ * nothing.  Only the convolution weight gradient (split-K) and the table gradients add partial sums atomically. */
+int nrl_dkn_encoder_bwd(const NrlDknParams* p, const NrlDknGrads* g, const int64_t* ids, const int64_t* sorted_positions,
+                        const int64_t* entity_ids, const int64_t* entity_sorted_positions, int64_t n_news, int32_t seq_len,
+                        const float* out, const uint8_t* argmax, const float* d_out, void* ws, size_t ws_bytes,
+                        void* stream);
+
+/* DKN UserEncoder (user/dkn.py:40-107) + DNNPredictor (click_predictor.py:14-45) on ragged rows: hist (n_hist, dim) with
+ * hist_offsets (B + 1), cand (n_cand, dim) with cand_offsets (B + 1).  Field <-> reference key:
+ *   att_w1, att_b1, att_w2, att_b2      user_encoder.dnn.{0,1}.{weight,bias}     (Hd, 2 dim), (Hd), (1, Hd), (1)
+ *   pred_w1, pred_b1, pred_w2, pred_b2  click_predictor.dnn.{0,2}.{weight,bias}  (Hd, 2 dim), (Hd), (1, Hd), (1)
+ * scores (B, max_cand): 0 at padded candidates; user (B, dim) the user vector of every valid candidate (the affine attention
+ * DNN makes it the same for all of them).  max_hist <= 1024, dim <= 1024, Hd <= 64.  _bwd WRITES d_hist and d_cand and
+ * adds the parameter gradients (att_b1, att_b2 and att_w1[:, :dim] get exactly zero) in a fixed order: no float atomics. */
+typedef struct NrlDknClickParams {
+  const float* att_w1;
+  const float* att_b1;
+  const float* att_w2;
+  const float* att_b2;
+  const float* pred_w1;
+  const float* pred_b1;
+  const float* pred_w2;
+  const float* pred_b2;
+  int32_t hidden;
+} NrlDknClickParams;
+
+typedef struct NrlDknClickGrads {
+  float* att_w1;
+  float* att_b1;
+  float* att_w2;
+  float* att_b2;
+  float* pred_w1;
+  float* pred_b1;
+  float* pred_w2;
+  float* pred_b2;
+} NrlDknClickGrads;
+
+size_t nrl_dkn_click_workspace_bytes(int64_t batch, int32_t max_cand, int32_t dim, int32_t hidden);
+int nrl_dkn_click_fwd(const NrlDknClickParams* p, const float* hist, const int64_t* hist_offsets, int32_t max_hist,
+                      const float* cand, const int64_t* cand_offsets, int64_t batch, int32_t max_cand, int32_t dim,
+                      float* scores, float* user, void* stream);
+int nrl_dkn_click_bwd(const NrlDknClickParams* p, const NrlDknClickGrads* g, const float* hist, const int64_t* hist_offsets,
+                      int32_t max_hist, const float* cand, const int64_t* cand_offsets, int64_t batch, int32_t max_cand,
+                      int32_t dim, const float* user, const float* d_scores, float* d_hist, float* d_cand, void* ws,
+                      size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

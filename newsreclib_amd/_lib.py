@@ -62,6 +62,30 @@ class NrlNpaQueryGrads(ctypes.Structure):
                 ("news_proj_bias", c_void_p), ("news_att_weight", c_void_p), ("news_att_bias", c_void_p)]
 
 
+class NrlDknParams(ctypes.Structure):
+    _fields_ = [("word_table", c_void_p), ("entity_table", c_void_p), ("context_table", c_void_p),
+                ("transform_matrix", c_void_p), ("transform_bias", c_void_p), ("conv_image", c_void_p * 4),
+                ("conv_bias", c_void_p * 4), ("windows", c_int32 * 4), ("num_windows", c_int32), ("word_dim", c_int32),
+                ("entity_dim", c_int32), ("num_filters", c_int32)]
+
+
+class NrlDknGrads(ctypes.Structure):
+    _fields_ = [("word_table", c_void_p), ("entity_table", c_void_p), ("context_table", c_void_p),
+                ("transform_matrix", c_void_p), ("transform_bias", c_void_p), ("conv_weight", c_void_p * 4),
+                ("conv_bias", c_void_p * 4)]
+
+
+class NrlDknClickParams(ctypes.Structure):
+    _fields_ = [("att_w1", c_void_p), ("att_b1", c_void_p), ("att_w2", c_void_p), ("att_b2", c_void_p),
+                ("pred_w1", c_void_p), ("pred_b1", c_void_p), ("pred_w2", c_void_p), ("pred_b2", c_void_p),
+                ("hidden", c_int32)]
+
+
+class NrlDknClickGrads(ctypes.Structure):
+    _fields_ = [("att_w1", c_void_p), ("att_b1", c_void_p), ("att_w2", c_void_p), ("att_b2", c_void_p),
+                ("pred_w1", c_void_p), ("pred_b1", c_void_p), ("pred_w2", c_void_p), ("pred_b2", c_void_p)]
+
+
 class NrlGruParams(ctypes.Structure):
     _fields_ = [("weight_ih", c_void_p), ("weight_hh", c_void_p), ("bias_ih", c_void_p), ("bias_hh", c_void_p),
                 ("input_dim", c_int32), ("hidden_dim", c_int32)]
@@ -182,6 +206,18 @@ SIGNATURES = {
                                                       c_void_p]),
     "nrl_personalized_user_attention_bwd": (c_int32, [c_void_p, c_void_p, c_int64, c_int32, c_int32, c_void_p, c_void_p,
                                                       c_void_p, c_void_p, c_void_p]),
+    "nrl_dkn_encoder_workspace_bytes": (c_size_t, [POINTER(NrlDknParams), c_int64, c_int32]),
+    "nrl_dkn_encoder_fwd": (c_int32, [POINTER(NrlDknParams), c_void_p, c_void_p, c_int64, c_int32, c_void_p, c_void_p,
+                                      c_void_p, c_size_t, c_void_p]),
+    "nrl_dkn_encoder_bwd": (c_int32, [POINTER(NrlDknParams), POINTER(NrlDknGrads), c_void_p, c_void_p, c_void_p,
+                                      c_void_p, c_int64, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,
+                                      c_void_p]),
+    "nrl_dkn_click_workspace_bytes": (c_size_t, [c_int64, c_int32, c_int32, c_int32]),
+    "nrl_dkn_click_fwd": (c_int32, [POINTER(NrlDknClickParams), c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_int64,
+                                    c_int32, c_int32, c_void_p, c_void_p, c_void_p]),
+    "nrl_dkn_click_bwd": (c_int32, [POINTER(NrlDknClickParams), POINTER(NrlDknClickGrads), c_void_p, c_void_p, c_int32,
+                                    c_void_p, c_void_p, c_int64, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p,
+                                    c_void_p, c_size_t, c_void_p]),
     "nrl_embedding_rows_fwd": (c_int32, [c_void_p, c_void_p, c_int64, c_int32, c_double, c_uint64, c_uint32,
                                          c_void_p, c_void_p]),
     "nrl_embedding_rows_bwd": (c_int32, [c_void_p, c_void_p, c_int64, c_int32, c_double, c_uint64, c_uint32,

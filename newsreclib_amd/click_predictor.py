@@ -16,6 +16,24 @@ class DotProduct(nn.Module):
         return ops.DotScoresFn.apply(user_vec.squeeze(1), cand)
 
 
+class DNNPredictor(nn.Module):
+    """DKN click predictor (reference click_predictor.py:14-45): ``Linear(input_dim, hidden) -> ReLU -> Linear(hidden, 1)`` on
+    ``[cand, user]``.  Holds the parameters under the reference's keys; DKN runs it fused with its user encoder
+    (``ops_dkn.DknClickFn``)."""
+
+    def __init__(self, input_dim: int, hidden_dim: int) -> None:
+        super().__init__()
+        if not isinstance(input_dim, int):
+            raise ValueError(f"Expected keyword argument `input_dim` to be an `int` but got {input_dim}")
+        if not isinstance(hidden_dim, int):
+            raise ValueError(f"Expected keyword argument `hidden_dim` to be an `int` but got {hidden_dim}")
+        self.dnn = nn.Sequential(nn.Linear(input_dim, hidden_dim), nn.ReLU(), nn.Linear(hidden_dim, 1))
+
+    def params(self):
+        """(w1, b1, w2, b2) as the kernels read them."""
+        return self.dnn[0].weight, self.dnn[0].bias, self.dnn[2].weight, self.dnn[2].bias
+
+
 class CrossEntropyLoss(nn.Module):
     """``torch.nn.CrossEntropyLoss()`` for float (probability) targets as used at
     nrms_module.py:287-288, fused with its gradient."""

@@ -507,6 +507,61 @@ static int gemm_wgrad(const float* dy, int I, const float* x, int J, float* dW, 
   return launch_gemm<NRL_TILE_W>(a, b, epi, I, J + 1, M, wgrad_splits(I, J + 1, M, 64, 160), st);
 }
 
+// (the convolution GEMM helpers below are shared by the CNN text encoders (nrl_api_lstur.hip) and DKN (nrl_dkn.hip))
+// ---- conv weight planes for the bf16x3 dgrad: plane[d][t'*F + f] = Wc[f][(W-1-t')*D + d] ------
+static __global__ void split_conv_weight_t_kernel(const float* __restrict__ w, int F, int D, int W, int Kp,
+                                           uint16_t* __restrict__ hi) {
+  const int64_t total = (int64_t)D * Kp;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total;
+       i += (int64_t)gridDim.x * blockDim.x) {
+    const int d = (int)(i / Kp), k = (int)(i % Kp);
+    float v = 0.f;
+    if (k < W * F) {
+      const int tr = k / F, f = k - tr * F;
+      v = w[((int64_t)f * W + (W - 1 - tr)) * D + d];
+    }
+    const __bf16 h = (__bf16)v;
+    const int64_t pos = split_pos(d, k, 2 * Kp);  // interleaved (hi | lo) k-tiles, see KCSplit
+    hi[pos] = __builtin_bit_cast(unsigned short, h);
+    hi[pos + 32] = __builtin_bit_cast(unsigned short, (__bf16)(v - (float)h));
+  }
+}
+
+// C = epi(A B) with A any k-contiguous fp32 accessor and B given both as fp32 k-major accessor (f32
+// engine) and as pre-split planes [N][Kp] (bf16x3 engine)
+template <class AOp, class BRc, class Epi>
+static int gemm_any(const AOp& a, const BRc& b_rc, const uint16_t* hi, const uint16_t* lo, int64_t ldp,
+                    const Epi& epi, int64_t M, int N, int K, hipStream_t st, const RpImage* rp = nullptr) {
+  if (cur_engine() == ENGINE_BF16X3) {
+    if (rp != nullptr && rp->img != nullptr) return rp_dispatch(a, *rp, epi, M, N, K, st);
+    const KCSplit b{hi, lo, ldp, N};
+    return launch_gemm_bf16x3_dma<X3_DMA_TILE>(a, b, epi, M, N, K, st);
+  }
+  return launch_gemm<NRL_TILE>(a, b_rc, epi, M, N, K, 1, st);
+}
+
+// dW (I, J) += A^T B, db (I) += colsum(A) with B any k-major accessor carrying the ones column
+template <class BOp>
+static int gemm_wgrad_any(const float* dy, int I, const BOp& b, int J, float* dW, float* db, int64_t M,
+                          hipStream_t st) {
+  const RCPlain a{dy, I, I, 0};
+  const EpiAtomicWB epi{dW, J, db, J};
+  if (cur_engine() == ENGINE_BF16X3) {
+    auto splits = [&](int bm) {
+      const int64_t tiles = ceil_div(I, bm) * ceil_div(J + 1, 160);
+      int64_t sp = ceil_div(M, 1664);
+      if (sp * tiles < 512) sp = ceil_div(512, tiles);
+      const int64_t max_s = ceil_div(M, 256);
+      return (int)(sp > max_s ? max_s : (sp < 1 ? 1 : sp));
+    };
+    // (the TRANSPOSED product (J + 1) x I on the wave-specialised kernel, so that its 256-row tiles cover the wide side
+    //  of the 300 x 900 convolution, measured slower: 1.03 vs 0.95 ms per launch, LSTUR step 9.7 vs 9.5 ms)
+    if (opt(O_X3_DMA)) return launch_gemm_bf16x3_dma_tn<2, 2, 2, 5, 2>(a, b, epi, I, J + 1, M, splits(64), st);
+    return launch_gemm_bf16x3<X3_TILE_W>(a, b, epi, I, J + 1, M, splits(64), st);
+  }
+  return launch_gemm<NRL_TILE_W>(a, b, epi, I, J + 1, M, wgrad_splits(I, J + 1, M, 64, 160), st);
+}
+
 static int block_fwd_tail(const NrlBlockParams* P, const BlockShape& s, const BlockWs& w, const BlockPlanes& bp,
                           Dropout drop2, float* out, hipStream_t st);
 

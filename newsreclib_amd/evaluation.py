@@ -95,6 +95,8 @@ class NewsVectorCache:
         self.module.eval()
         enc = self.module.news_encoder
         names = [k for k in self.table.attrs if k in TEXT_ATTRS or k in ("category", "subcategory")]
+        # encoders that read entity ids (DKN's KCNN) declare them; every other encoder's call stays as it was
+        names += [k for k in getattr(enc, "entity_attrs", ()) if k in self.table.attrs and k not in names]
         out = []
         import contextlib
         with contextlib.ExitStack() as stack:

@@ -260,6 +260,78 @@ class CNNPersAtt(nn.Module):
                                           bufs if any(b is not None for b in bufs) else None, order)
 
 
+class KCNN(nn.Module):
+    """DKN's knowledge-aware CNN (reference news.py:186-299) as one HIP pipeline (``nrl_dkn_encoder_fwd``/``_bwd``): word,
+    entity and (``use_context``) context lookups, the shared ``tanh(E T + b)`` transform of the entity channels, one
+    ``Conv2d(C, F, (W, D))`` per window without padding, ReLU, max over time, concat.  Same sub-modules and state-dict keys
+    as the reference.  Each convolution weight is read by the kernels as an (F, W, C, D) image, the K order of the windowed
+    GEMM; the images are a side buffer rebuilt whenever a weight changes (address, version counter, tensor identity)."""
+
+    entity_attrs = ("title_entities",)       # (evaluation.NewsVectorCache passes these through)
+
+    def __init__(self, pretrained_text_embeddings: torch.Tensor, pretrained_entity_embeddings: torch.Tensor,
+                 pretrained_context_embeddings: Optional[torch.Tensor], use_context: bool, text_embed_dim: int,
+                 entity_embed_dim: int, num_filters: int, window_sizes: List[int]) -> None:
+        super().__init__()
+        window_sizes = [int(x) for x in window_sizes]
+        if not 1 <= len(window_sizes) <= 4 or len(set(window_sizes)) != len(window_sizes) or min(window_sizes) < 1:
+            raise NotImplementedError("the DKN kernels take 1 to 4 distinct positive window sizes")
+        if num_filters % 4 != 0 or text_embed_dim % 4 != 0 or entity_embed_dim % 4 != 0:
+            raise NotImplementedError("num_filters, text_embed_dim and entity_embed_dim must be multiples of 4")
+        if text_embed_dim > 512:
+            raise NotImplementedError("text_embed_dim must be at most 512")
+        self.window_sizes = window_sizes
+        self.text_embedding_layer = nn.Embedding.from_pretrained(
+            torch.as_tensor(pretrained_text_embeddings, dtype=torch.float32), freeze=False, padding_idx=0)
+        self.entity_embedding_layer = nn.Embedding.from_pretrained(
+            torch.as_tensor(pretrained_entity_embeddings, dtype=torch.float32), freeze=False, padding_idx=0)
+        self.use_context = use_context
+        if use_context:
+            assert isinstance(pretrained_context_embeddings, torch.Tensor)
+            self.context_embedding_layer = nn.Embedding.from_pretrained(
+                torch.as_tensor(pretrained_context_embeddings, dtype=torch.float32), freeze=False, padding_idx=0)
+        self.transform_matrix = nn.Parameter(torch.empty(entity_embed_dim, text_embed_dim).uniform_(-0.1, 0.1))
+        self.transform_bias = nn.Parameter(torch.empty(text_embed_dim).uniform_(-0.1, 0.1))
+        self.conv_filters = nn.ModuleDict({str(x): nn.Conv2d(3 if use_context else 2, num_filters, (x, text_embed_dim))
+                                           for x in window_sizes})
+        self._images: Dict[int, torch.Tensor] = {}
+        self._image_keys: Dict[int, tuple] = {}
+
+    def conv_images(self) -> List[torch.Tensor]:
+        """(F, W, C, D) images of the convolution weights, rebuilt when a weight changed since the last call."""
+        out = []
+        for x in self.window_sizes:
+            w = self.conv_filters[str(x)].weight
+            key = (w.data_ptr(), w._version, tuple(w.shape), ops_blocks.tensor_serial(w), str(w.device))
+            img = self._images.get(x)
+            if img is None or self._image_keys.get(x) != key:
+                img = w.detach().permute(0, 2, 1, 3).contiguous()
+                self._images[x], self._image_keys[x] = img, key
+            out.append(img)
+        return out
+
+    def forward(self, news: Dict[str, torch.Tensor], seed: Optional[int] = None,
+                order: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """news["title"], news["title_entities"] (N, L) -> (N, len(window_sizes) * num_filters).  (No dropout: ``seed``
+        is accepted for the shared call signature and ignored.)"""
+        from . import ops_dkn
+        text, ents = news["title"], news["title_entities"]
+        L = text.shape[-1]
+        if max(self.window_sizes) > L:
+            raise NotImplementedError(f"window {max(self.window_sizes)} is longer than the title ({L} tokens)")
+        if L > 255:
+            raise NotImplementedError("titles longer than 255 tokens (the max-over-time argmax is one byte)")
+        convs = [t for x in self.window_sizes for t in (self.conv_filters[str(x)].weight, self.conv_filters[str(x)].bias)]
+        ctx_t = self.context_embedding_layer.weight if self.use_context else None
+        params = [self.text_embedding_layer.weight, self.entity_embedding_layer.weight] + \
+            ([ctx_t] if ctx_t is not None else []) + [self.transform_matrix, self.transform_bias] + convs
+        bufs = tuple(getattr(t, "main_grad", None) for t in params)
+        return ops_dkn.DknEncoderFn.apply(text, ents, order, tuple(self.window_sizes),
+                                          self.conv_images(), bufs if any(b is not None for b in bufs) else None,
+                                          self.text_embedding_layer.weight, self.entity_embedding_layer.weight, ctx_t,
+                                          self.transform_matrix, self.transform_bias, *convs)
+
+
 class LinearEncoder(nn.Module):
     """Category encoder (reference category.py:9-80) for the configuration the recommenders in scope use
     (LSTUR, lstur_module.py:173-183): a trainable ``nn.Embedding(padding_idx=0)`` lookup, no dropout, no

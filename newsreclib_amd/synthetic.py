@@ -118,3 +118,24 @@ def add_lstur_fields(batch: Dict, vocab: int, n_categ: int = 19, n_users: int = 
     uidx[rng.random(B) < 0.15] = 0
     batch["user_idx"] = torch.as_tensor(uidx).to(dev)
     return batch
+
+
+def add_dkn_fields(batch: Dict, n_entities: int = 30_000, seed: int = 7, max_per_title: int = 3) -> Dict:
+    """DKN inputs (dkn_module.py, news.py:262-266): ``title_entities`` (n_news, L) beside every ``title``, as
+    ``input_pipeline`` pads them.  Each title carries 0..max_per_title linked entities in its leading real-token slots
+    (uniform over [1, n_entities)), the rest 0 -- the padding / no-entity id.  n_entities = 30,000 stands for the order of
+    magnitude of MIND's small entity vocabulary (no dataset is on hand to count it exactly)."""
+    rng = np.random.default_rng(seed)
+    out = dict(batch)
+    for side in ("x_hist", "x_cand"):
+        title = batch[side]["title"]
+        ids = title.cpu().numpy() if torch.is_tensor(title) else np.asarray(title)
+        n, L = ids.shape
+        real = (ids != 0).sum(axis=1)
+        k = np.minimum(rng.integers(0, max_per_title + 1, n), real)
+        ents = rng.integers(1, n_entities, size=(n, L)).astype(np.int64)
+        ents[np.arange(L)[None, :] >= k[:, None]] = 0
+        t = torch.from_numpy(ents)
+        out[side] = dict(batch[side])
+        out[side]["title_entities"] = t.to(title.device) if torch.is_tensor(title) else t
+    return out

@@ -1,0 +1,166 @@
+"""CPU restatement of the reference DKN forward / loss (test infrastructure, beside the frozen ``oracle`` package).
+
+``DKNModule.forward`` (dkn_module.py:207-240): ``KCNN`` (news.py:255-299: word / entity / context lookups, the shared
+``tanh(E T + b)`` transform, one unpadded ``Conv2d(C, F, (W, D))`` per window, ReLU, max over time, concat) on history and
+candidates; early fusion: the candidate-aware ``UserEncoder`` (user/dkn.py:59-107, softmax with ``finfo.min`` at padded
+history slots, weights zeroed for padded candidates) and ``DNNPredictor`` (click_predictor.py:40-45) with padded
+candidates' scores set to 0; late fusion: mean of the true history and dot product.  CE loss.  No dropout anywhere.
+Pinned by tests/golden/make_golden_dkn.py."""
+from __future__ import annotations
+
+from typing import Dict, List
+
+import torch
+import torch.nn.functional as F
+
+from oracle.nrms_oracle import ce_loss, to_dense_batch
+
+PRE = "news_encoder."
+WORD = PRE + "text_embedding_layer.weight"
+ENT = PRE + "entity_embedding_layer.weight"
+CTX = PRE + "context_embedding_layer.weight"
+TM = PRE + "transform_matrix"
+TB = PRE + "transform_bias"
+UE = "user_encoder.dnn."
+CP = "click_predictor.dnn."
+
+
+def conv_key(x: int, what: str) -> str:
+    return f"{PRE}conv_filters.{x}.{what}"
+
+
+def make_dkn_params(vocab: int, n_ent: int, D: int, Ed: int, F_: int, windows: List[int], Hd: int,
+                    use_context: bool = True, late_fusion: bool = False, seed: int = 0) -> Dict[str, torch.Tensor]:
+    g = torch.Generator().manual_seed(seed)
+    C = 3 if use_context else 2
+
+    def rnd(*shape, scale):
+        return (torch.randn(*shape, generator=g) * scale).float()
+
+    ent = rnd(n_ent, Ed, scale=0.5)
+    p = {WORD: rnd(vocab, D, scale=0.3), ENT: ent}
+    if use_context:
+        p[CTX] = ent.clone()                 # loaded from the entity file (dkn_module.py:117-122)
+    p[TM] = rnd(Ed, D, scale=Ed ** -0.5)
+    p[TB] = rnd(D, scale=0.05)
+    for x in windows:
+        p[conv_key(x, "weight")] = rnd(F_, C, x, D, scale=(C * x * D) ** -0.5)
+        p[conv_key(x, "bias")] = rnd(F_, scale=0.05)
+    if not late_fusion:
+        dim = len(windows) * F_
+        p.update({UE + "0.weight": rnd(Hd, 2 * dim, scale=(2 * dim) ** -0.5), UE + "0.bias": rnd(Hd, scale=0.05),
+                  UE + "1.weight": rnd(1, Hd, scale=Hd ** -0.5), UE + "1.bias": rnd(1, scale=0.05),
+                  CP + "0.weight": rnd(Hd, 2 * dim, scale=(2 * dim) ** -0.5), CP + "0.bias": rnd(Hd, scale=0.05),
+                  CP + "2.weight": rnd(1, Hd, scale=Hd ** -0.5), CP + "2.bias": rnd(1, scale=0.05)})
+    return p
+
+
+def kcnn(ids, ents, params, windows):
+    x = params[WORD][ids]
+    chans = [x, torch.tanh(params[ENT][ents] @ params[TM] + params[TB])]
+    if CTX in params:
+        chans.append(torch.tanh(params[CTX][ents] @ params[TM] + params[TB]))
+    stack = torch.stack(chans, dim=1)                                  # (N, C, L, D)
+    pooled = []
+    for x_ in windows:
+        c = F.conv2d(stack, params[conv_key(x_, "weight")], params[conv_key(x_, "bias")]).squeeze(3)
+        pooled.append(torch.relu(c).max(dim=-1)[0])
+    return torch.cat(pooled, dim=1)
+
+
+def user_attention(hist, cand, mask_h, mask_c, params):
+    """user/dkn.py:59-107: (B, H, dim), (B, C, dim) -> (B, C, dim)."""
+    Hn, Cn = hist.shape[1], cand.shape[1]
+    pair = torch.cat([cand.unsqueeze(2).expand(-1, -1, Hn, -1), hist.unsqueeze(1).expand(-1, Cn, -1, -1)], dim=-1)
+    s = (pair @ params[UE + "0.weight"].t() + params[UE + "0.bias"]) @ params[UE + "1.weight"].t() + params[UE + "1.bias"]
+    s = s.squeeze(-1)
+    s = torch.where(mask_h.unsqueeze(1).expand(-1, Cn, -1), s, torch.tensor(torch.finfo(s.dtype).min))
+    w = torch.softmax(s, dim=-1)
+    w = torch.where(mask_c.unsqueeze(-1).expand(-1, -1, Hn), w, torch.tensor(0.0))
+    return torch.bmm(w, hist)
+
+
+def dnn_predictor(user, cand, params):
+    h = torch.relu(torch.cat([cand, user], dim=-1) @ params[CP + "0.weight"].t() + params[CP + "0.bias"])
+    return (h @ params[CP + "2.weight"].t() + params[CP + "2.bias"]).squeeze(-1)
+
+
+def dkn_forward(batch, params, windows, late_fusion: bool = False) -> dict:
+    B = int(batch.get("batch_size", int(batch["batch_hist"].max()) + 1))
+    xh, xc = batch["x_hist"], batch["x_cand"]
+    hist_vec = kcnn(xh["title"], xh["title_entities"], params, windows)
+    cand_vec = kcnn(xc["title"], xc["title_entities"], params, windows)
+    hist_dense, mask_h = to_dense_batch(hist_vec, batch["batch_hist"], B)
+    cand_dense, mask_c = to_dense_batch(cand_vec, batch["batch_cand"], B)
+    if not late_fusion:
+        user = user_attention(hist_dense, cand_dense, mask_h, mask_c, params)
+        scores = torch.where(mask_c, dnn_predictor(user, cand_dense, params), torch.tensor(0.0))
+    else:
+        user = hist_dense.sum(dim=1) / mask_h.sum(dim=1, keepdim=True)
+        scores = torch.einsum("bd,bcd->bc", user, cand_dense)
+    y_true, _ = to_dense_batch(batch["labels"], batch["batch_cand"], B)
+    return dict(hist_vec=hist_vec, cand_vec=cand_vec, user_vec=user, scores=scores, y_true=y_true,
+                loss=ce_loss(scores, y_true))
+
+
+def loss_and_grads(batch, params, windows, late_fusion=False):
+    leaves = {k: v.clone().requires_grad_(True) for k, v in params.items()}
+    out = dkn_forward(batch, leaves, windows, late_fusion=late_fusion)
+    grads = torch.autograd.grad(out["loss"], list(leaves.values()), allow_unused=True)
+    g = {k: (gr if gr is not None else torch.zeros_like(leaves[k])) for k, gr in zip(leaves, grads)}
+    for k in (WORD, ENT, CTX):                                          # padding_idx = 0
+        if k in g:
+            g[k][0] = 0.0
+    return out, g
+
+
+# ---- fixtures (tests/golden/dkn_*.npz) --------------------------------------------------------------------------------
+DKN_CASES = ["dkn_tiny_train", "dkn_tiny_eval", "dkn_tiny_late_fusion", "dkn_tiny_no_context", "dkn_tie", "dkn16_train"]
+MODULE_KEYS = ("vocab", "n_ent", "D", "Ed", "F", "Hd")
+
+
+def golden_cfg(g, prefix=""):
+    cfg = {k: int(g[prefix + "cfg_" + k]) for k in MODULE_KEYS}
+    cfg["windows"] = [int(x) for x in g[prefix + "cfg_windows"]]
+    cfg["param_seed"] = int(g[prefix + "cfg_param_seed"])
+    cfg["use_context"] = bool(g[prefix + "cfg_use_context"])
+    cfg["late_fusion"] = bool(g[prefix + "cfg_late_fusion"])
+    return cfg
+
+
+def golden_params(cfg):
+    return make_dkn_params(cfg["vocab"], cfg["n_ent"], cfg["D"], cfg["Ed"], cfg["F"], cfg["windows"], cfg["Hd"],
+                           use_context=cfg["use_context"], late_fusion=cfg["late_fusion"], seed=cfg["param_seed"])
+
+
+def golden_batch(g, prefix="", device="cpu"):
+    t = lambda a: torch.as_tensor(a).to(device)  # noqa: E731
+    B = int(g[prefix + "in_batch_size"])
+    return {"batch_hist": t(g[prefix + "in_batch_hist"]), "batch_cand": t(g[prefix + "in_batch_cand"]),
+            "x_hist": {"title": t(g[prefix + "in_title_hist"]), "title_entities": t(g[prefix + "in_ent_hist"])},
+            "x_cand": {"title": t(g[prefix + "in_title_cand"]), "title_entities": t(g[prefix + "in_ent_cand"])},
+            "labels": t(g[prefix + "in_labels"]), "user_idx": torch.arange(B).to(device),
+            "user_ids": (torch.arange(B) + 1).to(device), "batch_size": B}
+
+
+def module_kwargs(cfg, **overrides):
+    kw = dict(outputs={"train": ["preds", "targets", "cand_news_size"], "val": ["preds", "targets", "cand_news_size"],
+                       "test": ["preds", "targets", "cand_news_size"]},
+              dual_loss_training=False, dual_loss_coef=None, loss="cross_entropy_loss", late_fusion=cfg["late_fusion"],
+              temperature=None, pretrained_word_embeddings_path=None, text_embed_dim=cfg["D"],
+              use_context=cfg["use_context"], pretrained_entity_embeddings_path=None, entity_embed_dim=cfg["Ed"],
+              num_filters=cfg["F"], window_sizes=list(cfg["windows"]), hidden_dim_dnn=cfg["Hd"], top_k_list=[5],
+              num_categ_classes=18, num_sent_classes=3, save_recs=False, recs_fpath=None, optimizer=None, scheduler=None)
+    kw.update(overrides)
+    return kw
+
+
+def build_module(cfg, params, device="cuda", **overrides):
+    """DKNModule (the product) loaded from a reference-keyed state dict."""
+    from newsreclib_amd.dkn_module import DKNModule
+    kw = module_kwargs(cfg, pretrained_word_embeddings=params[WORD], pretrained_entity_embeddings=params[ENT])
+    kw.update(overrides)
+    mod = DKNModule(**kw)
+    res = mod.load_state_dict(params, strict=True)
+    assert not res.missing_keys and not res.unexpected_keys
+    return mod.to(device)

@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""Times the LSTUR (BASELINE config 5), NAML (--model naml) or NPA (--model npa: title only, 45,215 users) train step on one GPU: B users x 50 clicks, title 30 + abstract 50
+"""Times the LSTUR (BASELINE config 5), NAML (--model naml) NPA (--model npa: title only, 45,215 users) or DKN
+(--model dkn: title + title entities over 30,000 entities, 4 windows x 100 filters) train step on one GPU: B users x 50 clicks, title 30 + abstract 50
 tokens, CNN 300 filters x window 3, GRU 700.  Prints ms/step and impressions/s; with --breakdown also the
 per-kernel time from torch.profiler-free HIP events around the module's stages."""
 import argparse
@@ -19,7 +20,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--vocab", type=int, default=70000)
     ap.add_argument("--engine", default="bf16x3")
-    ap.add_argument("--model", default="lstur", choices=["lstur", "naml", "cen", "mins", "npa"])
+    ap.add_argument("--model", default="lstur", choices=["lstur", "naml", "cen", "mins", "npa", "dkn"])
     args = ap.parse_args()
     from functools import partial
 
@@ -81,9 +82,21 @@ def main():
             word_pref_query_dim=200, news_pref_query_dim=200, dropout_probability=0.2, top_k_list=[5, 10],
             num_categ_classes=18, num_sent_classes=3, save_recs=False, recs_fpath=None,
             optimizer=partial(torch.optim.Adam, lr=1e-4), scheduler=None, pretrained_embeddings=emb).cuda()
+    if args.model == "dkn":    # configs/model/dkn.yaml (use_context, windows 1-4 x 100 filters, entities 100-d)
+        from newsreclib_amd.dkn_module import DKNModule
+        mod = DKNModule(
+            outputs={"train": [], "val": [], "test": []}, dual_loss_training=False, dual_loss_coef=None,
+            loss="cross_entropy_loss", late_fusion=False, temperature=None, pretrained_word_embeddings_path=None,
+            text_embed_dim=300, use_context=True, pretrained_entity_embeddings_path=None, entity_embed_dim=100,
+            num_filters=100, window_sizes=[1, 2, 3, 4], hidden_dim_dnn=16, top_k_list=[5, 10], num_categ_classes=18,
+            num_sent_classes=3, save_recs=False, recs_fpath=None, optimizer=partial(torch.optim.Adam, lr=1e-4),
+            scheduler=None, pretrained_word_embeddings=emb, pretrained_entity_embeddings=torch.randn(30000, 100) * 0.3).cuda()
     trainer = NRMSTrainer(mod, lr=1e-4)
     batch = add_lstur_fields(make_batch(args.batch, vocab=args.vocab, mode="fixed", seed=1, device="cuda"), args.vocab,
                              19, 45215, 50, seed=2)
+    if args.model == "dkn":
+        from newsreclib_amd.synthetic import add_dkn_fields
+        batch = add_dkn_fields(batch, n_entities=30000, seed=3)
     batch = prepare_batch(batch)
     for _ in range(args.warmup):
         trainer.step(batch)
