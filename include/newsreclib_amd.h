@@ -775,6 +775,59 @@ int nrl_dkn_click_bwd(const NrlDknClickParams* p, const NrlDknClickGrads* g, con
                       int32_t dim, const float* user, const float* d_scores, float* d_hist, float* d_cand, void* ws,
                       size_t ws_bytes, void* stream);
 
+/* ---- CAUM (caum_module.py:326-360, user/caum.py:81-125): candidate-aware user encoder, head-padded self-attention ------
+ * nrl_caum_attn_*: attention over a packed (rows, 3 * heads * head_dim) q|k|v buffer -> o (rows, heads * head_dim), for every
+ * (outer, head) group over `seq` positions; seq_first: row = s * outer + n (nn.MultiheadAttention, batch_first=False), else
+ * row = n * seq + s.  lse (outer * heads, seq) is written by the forward and read by the backward; scale 0 = 1/sqrt(head_dim).
+ * head_dim in {16, 20, 32, 48, 64}: a module with another head dim pads its projections per head (news_encoder.MHSAAddAtt).
+ * dqkv is fully written. */
+int nrl_caum_attn_fwd(const float* qkv, float* o, float* lse, int64_t outer, int64_t seq, int32_t heads, int32_t head_dim,
+                      int32_t seq_first, float scale, void* stream);
+int nrl_caum_attn_bwd(const float* qkv, const float* o, const float* d_o, const float* lse, float* dqkv, int64_t outer,
+                      int64_t seq, int32_t heads, int32_t head_dim, int32_t seq_first, float scale, void* stream);
+/* y[k] = x[k] * mask(seed, stream_id, p)[k] (the nrl_dropout_mask spec, scaled by 1/(1-p)); also the backward. */
+int nrl_caum_dropout(const float* x, float* y, int64_t n, double p, uint64_t seed, uint32_t stream_id, void* stream);
+/* The user encoder over every candidate slot at once: rows r = (b, i, t), b < B users, i < C slots, t < H = max_hist.
+ * Dropout streams of slot i: stream_base + 3i -> dropout1 of the candidate over (B, D); + 3i + 1 -> dropout2 of the history
+ * over (B, H, D); + 3i + 2 -> dropout3 of [cnn, self] over (B, H, F + U); row-major flat indices.
+ * expand: h (B, H, D), c (B, C, D) -> hd (B, C, H, D), cd (B, C, D); the backward sums the slots in order. */
+int nrl_caum_expand_fwd(const float* h, const float* c, int64_t B, int32_t C, int32_t H, int32_t D, double p, uint64_t seed,
+                        uint32_t stream_base, float* hd, float* cd, void* stream);
+int nrl_caum_expand_bwd(const float* d_hd, const float* d_cd, int64_t B, int32_t C, int32_t H, int32_t D, double p,
+                        uint64_t seed, uint32_t stream_base, float* d_h, float* d_c, void* stream);
+/* combine: P (B * hist_slots * H, 3F + U) = history rows x [linear1 left | centre | right blocks ; linear2 history block]
+ * (+ biases), Q (B * C, F + U) = candidate rows x [linear1 candidate block ; linear2 candidate block] ->
+ *   cnn (R, F) = P[t-1, left] + P[t, centre] + P[t+1, right] + Q[cnn]  (circular in t over the dense, zero-padded history)
+ *   s   (R, U) = P[t, linear2] + Q[linear2]
+ * hist_slots = C (training: per-slot dropped-out history) or 1 (evaluation: one history for every slot).  _bwd writes
+ * d_P and d_Q in a fixed order. */
+int nrl_caum_combine_fwd(const float* P, const float* Q, int64_t B, int32_t C, int32_t H, int32_t F, int32_t U,
+                         int32_t hist_slots, float* cnn, float* s, void* stream);
+int nrl_caum_combine_bwd(const float* d_cnn, const float* d_s, int64_t B, int32_t C, int32_t H, int32_t F, int32_t U,
+                         int32_t hist_slots, float* d_P, float* d_Q, void* stream);
+/* z (R, F + U) = dropout3([cnn, a]); the backward splits d_z back under the same mask. */
+int nrl_caum_concat_dropout_fwd(const float* cnn, const float* a, int64_t B, int32_t C, int32_t H, int32_t F, int32_t U,
+                                double p, uint64_t seed, uint32_t stream_base, float* z, void* stream);
+int nrl_caum_concat_dropout_bwd(const float* d_z, int64_t B, int32_t C, int32_t H, int32_t F, int32_t U, double p,
+                                uint64_t seed, uint32_t stream_base, float* d_cnn, float* d_a, void* stream);
+/* z (groups * rows_per_group, N) = tanh(a + g[row / rows_per_group]); _bwd writes d_a and d_g (the sum over the group). */
+int nrl_caum_group_tanh_fwd(const float* a, const float* g, int64_t groups, int32_t rows_per_group, int32_t N, float* z,
+                            void* stream);
+int nrl_caum_group_tanh_bwd(const float* d_z, const float* z, int64_t groups, int32_t rows_per_group, int32_t N, float* d_a,
+                            float* d_g, void* stream);
+/* DenseAttention's last layer (w3 (N2), b3 (1)) on z2 (R, N2), softmax over the H slots (no mask), user (B * C, U) =
+ * sum_t alpha_t x_t for x (R, U), scores (B, C) = cd . user, 0 where slot0 + i >= the impression's candidate count
+ * (cand_offsets (B + 1)).  alpha (R) and user are kept for the backward.  _bwd writes d_z2, d_x, d_cd and ADDS d_w3, d_b3
+ * (fixed-order reduction).  H <= 8192. */
+int nrl_caum_score_fwd(const float* z2, const float* w3, const float* b3, const float* x, const float* cd,
+                       const int64_t* cand_offsets, int64_t B, int32_t C, int32_t slot0, int32_t H, int32_t N2, int32_t U,
+                       float* scores, float* alpha, float* user, void* stream);
+size_t nrl_caum_score_workspace_bytes(int64_t B, int32_t C, int32_t H, int32_t N2);
+int nrl_caum_score_bwd(const float* d_scores, const float* z2, const float* w3, const float* x, const float* cd,
+                       const float* alpha, const float* user, const int64_t* cand_offsets, int64_t B, int32_t C,
+                       int32_t slot0, int32_t H, int32_t N2, int32_t U, float* d_z2, float* d_x, float* d_cd, float* d_w3,
+                       float* d_b3, void* ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

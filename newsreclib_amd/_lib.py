@@ -218,6 +218,31 @@ SIGNATURES = {
     "nrl_dkn_click_bwd": (c_int32, [POINTER(NrlDknClickParams), POINTER(NrlDknClickGrads), c_void_p, c_void_p, c_int32,
                                     c_void_p, c_void_p, c_int64, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p,
                                     c_void_p, c_size_t, c_void_p]),
+    "nrl_caum_attn_fwd": (c_int32, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int32, c_int32, c_int32, c_float,
+                                    c_void_p]),
+    "nrl_caum_attn_bwd": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int32, c_int32,
+                                    c_int32, c_float, c_void_p]),
+    "nrl_caum_dropout": (c_int32, [c_void_p, c_void_p, c_int64, c_double, c_uint64, c_uint32, c_void_p]),
+    "nrl_caum_expand_fwd": (c_int32, [c_void_p, c_void_p, c_int64, c_int32, c_int32, c_int32, c_double, c_uint64, c_uint32,
+                                      c_void_p, c_void_p, c_void_p]),
+    "nrl_caum_expand_bwd": (c_int32, [c_void_p, c_void_p, c_int64, c_int32, c_int32, c_int32, c_double, c_uint64, c_uint32,
+                                      c_void_p, c_void_p, c_void_p]),
+    "nrl_caum_combine_fwd": (c_int32, [c_void_p, c_void_p, c_int64, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p,
+                                       c_void_p, c_void_p]),
+    "nrl_caum_combine_bwd": (c_int32, [c_void_p, c_void_p, c_int64, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p,
+                                       c_void_p, c_void_p]),
+    "nrl_caum_concat_dropout_fwd": (c_int32, [c_void_p, c_void_p, c_int64, c_int32, c_int32, c_int32, c_int32, c_double,
+                                              c_uint64, c_uint32, c_void_p, c_void_p]),
+    "nrl_caum_concat_dropout_bwd": (c_int32, [c_void_p, c_int64, c_int32, c_int32, c_int32, c_int32, c_double, c_uint64,
+                                              c_uint32, c_void_p, c_void_p, c_void_p]),
+    "nrl_caum_group_tanh_fwd": (c_int32, [c_void_p, c_void_p, c_int64, c_int32, c_int32, c_void_p, c_void_p]),
+    "nrl_caum_group_tanh_bwd": (c_int32, [c_void_p, c_void_p, c_int64, c_int32, c_int32, c_void_p, c_void_p, c_void_p]),
+    "nrl_caum_score_fwd": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_int32,
+                                     c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "nrl_caum_score_workspace_bytes": (c_size_t, [c_int64, c_int32, c_int32, c_int32]),
+    "nrl_caum_score_bwd": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64,
+                                     c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p,
+                                     c_void_p, c_void_p, c_size_t, c_void_p]),
     "nrl_embedding_rows_fwd": (c_int32, [c_void_p, c_void_p, c_int64, c_int32, c_double, c_uint64, c_uint32,
                                          c_void_p, c_void_p]),
     "nrl_embedding_rows_bwd": (c_int32, [c_void_p, c_void_p, c_int64, c_int32, c_double, c_uint64, c_uint32,

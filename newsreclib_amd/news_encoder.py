@@ -13,12 +13,15 @@ from typing import Dict, List, Optional
 import torch
 import torch.nn as nn
 
-from . import _lib, ops, ops_blocks, ops_lstur
+from . import _lib, ops, ops_blocks, ops_caum, ops_lstur
 from .attention import AdditiveAttention
 
 # dropout stream pair of each text attribute (fixed by NAME: the reference iterates its text encoders
 # in Python-set order, which must not change which random numbers an attribute sees)
 TEXT_STREAMS = {"title": 0, "abstract": 2, "text": 0}
+# ... and of the category encoders with dropout and the entity encoders (CAUM)
+CATEG_STREAMS = {"category": 4, "subcategory": 5}
+ENTITY_STREAMS = {"title_entities": 6, "abstract_entities": 8, "entities": 6}
 
 
 def _draw_seed() -> int:
@@ -53,6 +56,8 @@ class MHSAAddAtt(nn.Module):
         # table gradient is complete, before the weight-gradient GEMMs (trainer.NRMSTrainer starts its all-reduce there)
         self._tt_buf = self._tt_key = self._tt_seen_key = None       # token q|k|v table of evaluation forwards (below)
         self._tt_seen, self._tt_pinned = 0, False
+        # head dims the fused pipeline is not built for (CAUM: 300 / 20 = 15, 100 / 20 = 5) run the head-padded path below
+        self.padded_heads = embed_dim % num_heads != 0 or embed_dim // num_heads not in ops_caum.HEAD_DIMS
 
     def _params(self):
         mha, att = self.multihead_attention, self.additive_attention
@@ -133,11 +138,28 @@ class MHSAAddAtt(nn.Module):
         MHSAAddAtt.TOKEN_TABLE_USES["forwards"] += 1
         return ops.news_encoder_fwd_table(text, self._tt_buf, V, params[1:], self.num_heads)
 
+    def _padded_forward(self, text: torch.Tensor, p: float, seed: int, stream0: int) -> torch.Tensor:
+        """The same pipeline for head dims the fused kernels lack, with the attention in a space padded per head
+        (``ops_caum.padded_attention``: only the projections are padded, never the embedding table).  Dropout streams:
+        ``stream0`` on the embedded tokens (N, L, D), ``stream0 + 1`` on the attention output (N, L, D)."""
+        N, L = text.shape
+        w = self.embedding_layer.weight
+        D = w.shape[1]
+        x = ops_blocks.EmbeddingFn.apply(text.reshape(-1), w, 0, _grad_bufs((w,)))                # (N * L, D)
+        x = ops_caum.dropout(x, p, seed, stream0)
+        y = ops_caum.padded_attention(x, self.multihead_attention, self.num_heads, N, L, seq_first=False)
+        y = ops_caum.dropout(y, p, seed, stream0 + 1)
+        att = self.additive_attention
+        ap = (att.linear.weight, att.linear.bias, att.query)
+        return ops_blocks.AdditiveAttentionFn.apply(y.view(N, L, D), *ap, _grad_bufs(ap))
+
     def forward(self, text: torch.Tensor, seed: Optional[int] = None,
                 order: Optional[torch.Tensor] = None, stream0: int = 0) -> torch.Tensor:
         p = float(self.dropout.p) if self.training else 0.0
         if p > 0.0 and seed is None:
             seed = _draw_seed()
+        if self.padded_heads:
+            return self._padded_forward(text, p, seed or 0, stream0)
         params = self._params()
         if not self.training and not torch.is_grad_enabled():
             out = self._forward_from_token_table(text, params)
@@ -333,16 +355,16 @@ class KCNN(nn.Module):
 
 
 class LinearEncoder(nn.Module):
-    """Category encoder (reference category.py:9-80) for the configuration the recommenders in scope use
-    (LSTUR, lstur_module.py:173-183): a trainable ``nn.Embedding(padding_idx=0)`` lookup, no dropout, no
-    linear transform."""
+    """Category encoder (reference category.py:9-80): a trainable ``nn.Embedding(padding_idx=0)`` lookup, optionally
+    element dropout on the embedded row (CAUM, caum_module.py:195-205; ``forward``'s ``stream``) and ``relu(linear(.))``."""
 
     def __init__(self, pretrained_embeddings: Optional[torch.Tensor], from_pretrained: bool,
                  freeze_pretrained_emb: bool, num_categories: int, embed_dim: Optional[int], use_dropout: bool,
                  dropout_probability: Optional[float], linear_transform: bool, output_dim: Optional[int]) -> None:
         super().__init__()
-        if use_dropout:
-            raise NotImplementedError("newsreclib_amd.LinearEncoder covers use_dropout=False (LSTUR, NAML)")
+        if use_dropout and not isinstance(dropout_probability, float):
+            raise ValueError(
+                f"Expected keyword argument `dropout_probability` to be a `float` but got {dropout_probability}")
         if from_pretrained:
             assert isinstance(pretrained_embeddings, torch.Tensor)
             self.embedding_layer = nn.Embedding.from_pretrained(
@@ -351,13 +373,18 @@ class LinearEncoder(nn.Module):
             assert isinstance(embed_dim, int) and embed_dim > 0
             self.embedding_layer = nn.Embedding(num_embeddings=num_categories, embedding_dim=embed_dim, padding_idx=0)
         self.use_dropout, self.linear_transform = use_dropout, linear_transform
+        if self.use_dropout:
+            self.dropout = nn.Dropout(p=dropout_probability)        # holds p; the kernel draws the mask
         if self.linear_transform:
             assert isinstance(output_dim, int)
             self.linear = nn.Linear(in_features=self.embedding_layer.weight.shape[1], out_features=output_dim)
 
-    def forward(self, category: torch.Tensor) -> torch.Tensor:
+    def forward(self, category: torch.Tensor, seed: Optional[int] = None, stream: int = CATEG_STREAMS["category"]
+                ) -> torch.Tensor:
         w = self.embedding_layer.weight
         vec = ops_lstur.EmbeddingRowsFn.apply(category, w, 0.0, 0, 0, _grad_bufs((w,)))
+        if self.use_dropout and self.training and self.dropout.p > 0.0:      # category.py:75-76, mask over (N, dim)
+            vec = ops_caum.dropout(vec, float(self.dropout.p), _draw_seed() if seed is None else seed, stream)
         if self.linear_transform:                                   # F.relu(self.linear(x)), category.py:78-80
             lp = (self.linear.weight, self.linear.bias)
             vec = ops_blocks.LinearActFn.apply(vec, *lp, "relu", _grad_bufs(lp))
@@ -868,9 +895,9 @@ class NewsEncoder(nn.Module):
 
     Built configurations: NRMS (one text attribute -> that encoder's output unchanged, news.py:159-160),
     LSTUR (ONE text encoder registered under every text attribute, a category encoder,
-    ``combine_type="concat"``, news.py:69-79,128,181) and NAML (``combine_type="add_att"``: additive
-    attention over the stacked view vectors, news.py:118-121,164-165).  Entity encoders and the ``linear``
-    combine layer belong to recommenders that are out of this build's scope (they raise).
+    ``combine_type="concat"``, news.py:69-79,128,181), NAML (``combine_type="add_att"``: additive
+    attention over the stacked view vectors, news.py:118-121,164-165) and CAUM (an entity encoder over
+    ``title_entities``, ``combine_type="linear"``: ``nn.Linear`` over [text, category, entity], news.py:96-125,166-178).
 
     Text-vector order: the reference fills its ``ModuleDict`` from a Python ``set`` (news.py:72-77), so the
     title/abstract order of the concatenation depends on the process's string-hash seed.  Here it is
@@ -885,11 +912,9 @@ class NewsEncoder(nn.Module):
         super().__init__()
         assert len(dataset_attributes) > 0
         self.concatenate_inputs = concatenate_inputs
-        if entity_encoder is not None:
-            raise NotImplementedError("newsreclib_amd.NewsEncoder: entity encoders are not built")
-        if combine_vectors and combine_type not in ("concat", "add_att"):
-            raise NotImplementedError("newsreclib_amd.NewsEncoder: combine_type must be 'concat' or 'add_att' "
-                                      f"(got {combine_type!r})")
+        if combine_vectors and combine_type not in ("concat", "add_att", "linear"):
+            raise ValueError("Expected keyword argument `combine_type` to be in [`add_att`, `linear`, `concat`] but got "
+                             f"{combine_type}.")
         self.encode_text = self.encode_category = self.encode_entity = False
         if ("title" in attributes2encode) or ("abstract" in attributes2encode):
             assert isinstance(text_encoder, nn.Module)
@@ -904,8 +929,18 @@ class NewsEncoder(nn.Module):
             names = [a for a in attributes2encode if a in dataset_attributes and a in ("category", "subcategory")]
             self.category_encoders = nn.ModuleDict({name: category_encoder for name in names})
             self.encode_category = True
+        if ("title_entities" in attributes2encode) or ("abstract_entities" in attributes2encode):   # news.py:96-111
+            assert isinstance(entity_encoder, nn.Module)
+            if not concatenate_inputs:
+                names = [a for a in attributes2encode
+                         if a in dataset_attributes and a in ("title_entities", "abstract_entities")]
+                self.entity_encoders = nn.ModuleDict({name: entity_encoder for name in names})
+            else:
+                self.entity_encoders = nn.ModuleDict({"entities": entity_encoder})
+            self.encode_entity = True
         n_vec = (len(self.text_encoders) if self.encode_text else 0) + \
-            (len(self.category_encoders) if self.encode_category else 0)
+            (len(self.category_encoders) if self.encode_category else 0) + \
+            (len(self.entity_encoders) if self.encode_entity else 0)
         if n_vec == 0:
             raise ValueError("no news attribute to encode")
         if n_vec > 1 and not combine_vectors:
@@ -916,6 +951,15 @@ class NewsEncoder(nn.Module):
                 assert isinstance(input_dim, int) and input_dim > 0
                 assert isinstance(query_dim, int) and query_dim > 0
                 self.combine_layer = AdditiveAttention(input_dim=input_dim, query_dim=query_dim)
+            elif combine_type == "linear":                          # news.py:122-125
+                assert isinstance(input_dim, int) and input_dim > 0
+                assert isinstance(output_dim, int) and output_dim > 0
+                self.combine_layer = nn.Linear(in_features=input_dim, out_features=output_dim)
+
+    @property
+    def entity_attrs(self):
+        """Entity-id inputs this encoder reads (``evaluation.NewsVectorCache`` passes them through)."""
+        return tuple(self.entity_encoders.keys()) if self.encode_entity else ()
 
     def share_plm_bodies(self, *news_dicts) -> int:
         """Before several ``forward`` calls of one step (history news, candidate news): every PLM text encoder runs its transformer
@@ -951,9 +995,20 @@ class NewsEncoder(nn.Module):
                     kw["stream0"] = TEXT_STREAMS[name] + stream_base
                 vectors.append(encoder(news[name], **kw))
         if self.encode_category:
-            vectors += [encoder(news[name]) for name, encoder in self.category_encoders.items()]
+            for name, encoder in self.category_encoders.items():
+                if getattr(encoder, "use_dropout", False):
+                    vectors.append(encoder(news[name], seed=seed, stream=CATEG_STREAMS[name] + stream_base))
+                else:
+                    vectors.append(encoder(news[name]))
+        if self.encode_entity:                               # news.py:149-152: after text and category
+            for name, encoder in self.entity_encoders.items():
+                vectors.append(encoder(news[name], seed=seed, stream0=ENTITY_STREAMS[name] + stream_base))
         if len(vectors) == 1:
             return vectors[0]
         if self.combine_type == "add_att":                   # news.py:164-165: attention over the stacked views
             return self.combine_layer(torch.stack(vectors, dim=1))
+        if self.combine_type == "linear":                    # news.py:166-178: Linear over [text, category, entity]
+            lin = self.combine_layer
+            lp = (lin.weight, lin.bias)
+            return ops_blocks.LinearFn.apply(torch.cat(vectors, dim=1), *lp, _grad_bufs(lp))
         return torch.cat(vectors, dim=1)                     # news.py:128

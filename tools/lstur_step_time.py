@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
-"""Times the LSTUR (BASELINE config 5), NAML (--model naml) NPA (--model npa: title only, 45,215 users) or DKN
-(--model dkn: title + title entities over 30,000 entities, 4 windows x 100 filters) train step on one GPU: B users x 50 clicks, title 30 + abstract 50
+"""Times the LSTUR (BASELINE config 5), NAML (--model naml) NPA (--model npa: title only, 45,215 users), DKN
+(--model dkn: title + title entities over 30,000 entities, 4 windows x 100 filters) or CAUM (--model caum: title, category
+and title entities at the caum.yaml widths) train step on one GPU: B users x 50 clicks, title 30 + abstract 50
 tokens, CNN 300 filters x window 3, GRU 700.  Prints ms/step and impressions/s; with --breakdown also the
 per-kernel time from torch.profiler-free HIP events around the module's stages."""
 import argparse
@@ -20,7 +21,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--vocab", type=int, default=70000)
     ap.add_argument("--engine", default="bf16x3")
-    ap.add_argument("--model", default="lstur", choices=["lstur", "naml", "cen", "mins", "npa", "dkn"])
+    ap.add_argument("--model", default="lstur", choices=["lstur", "naml", "cen", "mins", "npa", "dkn", "caum"])
     args = ap.parse_args()
     from functools import partial
 
@@ -91,10 +92,23 @@ def main():
             num_filters=100, window_sizes=[1, 2, 3, 4], hidden_dim_dnn=16, top_k_list=[5, 10], num_categ_classes=18,
             num_sent_classes=3, save_recs=False, recs_fpath=None, optimizer=partial(torch.optim.Adam, lr=1e-4),
             scheduler=None, pretrained_word_embeddings=emb, pretrained_entity_embeddings=torch.randn(30000, 100) * 0.3).cuda()
+    if args.model == "caum":   # configs/model/caum.yaml: title 300 / 20 heads, category 100, title entities 100 / 20 heads
+        from newsreclib_amd.caum_module import CAUMModule
+        mod = CAUMModule(
+            dataset_attributes=["title", "abstract", "category", "title_entities"],
+            attributes2encode=["title", "category", "title_entities"], outputs={"train": [], "val": [], "test": []},
+            dual_loss_training=False, dual_loss_coef=None, loss="cross_entropy_loss", late_fusion=False, temperature=None,
+            use_plm=False, pretrained_word_embeddings_path=None, plm_model=None, frozen_layers=None, text_embed_dim=300,
+            categ_embed_dim=100, use_entities=True, pretrained_entity_embeddings_path=None, entity_embed_dim=100,
+            entity_num_heads=20, text_num_heads=20, news_embed_dim=400, query_dim=200, dropout_probability=0.2,
+            user_vector_dim=400, num_filters=400, dense_att_hidden_dim1=400, dense_att_hidden_dim2=256, top_k_list=[5, 10],
+            num_categ_classes=18, num_sent_classes=3, save_recs=False, recs_fpath=None,
+            optimizer=partial(torch.optim.Adam, lr=1e-4), scheduler=None, pretrained_word_embeddings=emb,
+            pretrained_entity_embeddings=torch.randn(30000, 100) * 0.3).cuda()
     trainer = NRMSTrainer(mod, lr=1e-4)
     batch = add_lstur_fields(make_batch(args.batch, vocab=args.vocab, mode="fixed", seed=1, device="cuda"), args.vocab,
                              19, 45215, 50, seed=2)
-    if args.model == "dkn":
+    if args.model in ("dkn", "caum"):
         from newsreclib_amd.synthetic import add_dkn_fields
         batch = add_dkn_fields(batch, n_entities=30000, seed=3)
     batch = prepare_batch(batch)
