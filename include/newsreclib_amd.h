@@ -828,6 +828,56 @@ int nrl_caum_score_bwd(const float* d_scores, const float* z2, const float* w3, 
                        int32_t slot0, int32_t H, int32_t N2, int32_t U, float* d_z2, float* d_x, float* d_cd, float* d_w3,
                        float* d_b3, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- MINER (miner_module.py:258-323,398-406, layers/attention.py:93-166): poly attention, category bias, scores, ------------
+ * disagreement loss.  History / candidate rows are FLAT (n_hist / n_cand rows) with int64 offsets (B + 1) and sorted int64
+ * assignment vectors; every feature width is a multiple of 4.  No float atomics in these entries: what they reduce (context
+ * codes, the two bias-free projection weights through nrl_miner_wgrad, the category sums, the loss) is bit-reproducible; the
+ * GEMM engines' own weight gradients (reduce_dim, the transformer body) keep their split-K atomics.
+ *
+ * nrl_miner_slab_sum: out[j] = scale * sum_s slabs[s * n + j], s in order. */
+int nrl_miner_tanh_grad(const float* d_c, const float* c, int64_t n, float* d_pre, void* stream);   /* d_c * (1 - c^2) */
+/* d_w (N, K) = G^T X for G (R, N), X (R, K): slabs of 64 rows, then the slabs added in order. */
+size_t nrl_miner_wgrad_workspace_bytes(int64_t R, int32_t N, int32_t K);
+int nrl_miner_wgrad(const float* G, const float* X, int64_t R, int32_t N, int32_t K, float* d_w, void* ws, size_t ws_bytes,
+                    void* stream);
+int nrl_miner_slab_sum(const float* slabs, int64_t num_slabs, int64_t n, float scale, float* out, void* stream);
+/* partial[g] = sum over k != l of cos(x[g, k], x[g, l]) for x (groups, R, D), rows divided by (norm + eps).  _bwd: d_x of
+ * d_loss[0] * scale * sum_g partial[g] (d_loss: one float on the device). */
+int nrl_miner_cos_fwd(const float* x, int64_t groups, int32_t R, int32_t D, float eps, float* partial, void* stream);
+int nrl_miner_cos_bwd(const float* x, int64_t groups, int32_t R, int32_t D, float eps, const float* d_loss, float scale,
+                      float* d_x, void* stream);
+/* bias[t] = hh_t . (S_all - S_own[user(t)]) / n_cand over unit-normalised (no epsilon) category rows hc (n_hist, Dc),
+ * cc (n_cand, Dc): the mean over ALL candidates of the batch of the cosine, the user's own candidates zeroed.  The workspace
+ * of _fwd is handed to _bwd unchanged. */
+size_t nrl_miner_categ_bias_workspace_bytes(int64_t B, int64_t n_hist, int64_t n_cand, int32_t Dc);
+int nrl_miner_categ_bias_fwd(const float* hc, const float* cc, const int64_t* batch_hist, const int64_t* cand_off, int64_t B,
+                             int64_t n_hist, int64_t n_cand, int32_t Dc, float* bias, void* ws, size_t ws_bytes,
+                             void* stream);
+int nrl_miner_categ_bias_bwd(const float* d_bias, const float* hc, const float* cc, const int64_t* hist_off,
+                             const int64_t* batch_cand, const float* bias, int64_t B, int64_t n_hist, int64_t n_cand,
+                             int32_t Dc, float* d_hc, float* d_cc, void* ws, size_t ws_bytes, void* stream);
+/* user_vector (B, K, D) = softmax over max_hist positions of (P codes^T + bias)^T times E, for E (n_hist, D),
+ * P (n_hist, Cd) = tanh(E W^T), codes (K, Cd), bias (n_hist) or NULL.  The max_hist - n_b padded positions of user b take
+ * part with logit 1e-30 and a zero embedding (closed-form denominator term).  A (B, K, max_hist) is kept for _bwd, which
+ * writes d_E, d_P, d_codes and d_bias (NULL without bias); workspace: the per-user slabs of d_codes. */
+size_t nrl_miner_poly_workspace_bytes(int64_t B, int32_t K, int32_t Cd);
+int nrl_miner_poly_fwd(const float* E, const float* P, const float* codes, const float* bias, const int64_t* hist_off,
+                       int64_t B, int32_t max_hist, int32_t D, int32_t Cd, int32_t K, float* user_vector, float* A,
+                       void* stream);
+int nrl_miner_poly_bwd(const float* d_user_vector, const float* E, const float* P, const float* codes, const float* A,
+                       const int64_t* hist_off, int64_t B, int32_t max_hist, int32_t D, int32_t Cd, int32_t K, float* d_E,
+                       float* d_P, float* d_codes, float* d_bias, void* ws, size_t ws_bytes, void* stream);
+/* scores (B, max_cand), 0 at padded slots, from cand (n_cand, D) and user_vector (B, K, D), K <= 255.  mode 0: max over K
+ * (argmax (n_cand) bytes kept, lowest index on ties), 1: mean, 2: softmax_K(cand . gelu(Z)) weighted sum with Z (B, K, D) the
+ * target-aware projection (G = gelu(Z), S, W (n_cand, K) kept).  G / S / W / argmax may be NULL when no backward follows. */
+int nrl_miner_score_fwd(const float* cand, const float* user_vector, const float* Z, const int64_t* cand_off, int64_t B,
+                        int32_t max_cand, int32_t D, int32_t K, int32_t mode, float* scores, float* G, float* S, float* W,
+                        uint8_t* argmax, void* stream);
+int nrl_miner_score_bwd(const float* d_scores, const float* scores, const float* cand, const float* user_vector,
+                        const float* Z, const float* G, const float* S, const float* W, const uint8_t* argmax,
+                        const int64_t* cand_off, int64_t B, int32_t max_cand, int32_t D, int32_t K, int32_t mode,
+                        float* d_cand, float* d_user_vector, float* d_Z, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -243,6 +243,27 @@ SIGNATURES = {
     "nrl_caum_score_bwd": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64,
                                      c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p,
                                      c_void_p, c_void_p, c_size_t, c_void_p]),
+    "nrl_miner_tanh_grad": (c_int32, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p]),
+    "nrl_miner_wgrad_workspace_bytes": (c_size_t, [c_int64, c_int32, c_int32]),
+    "nrl_miner_wgrad": (c_int32, [c_void_p, c_void_p, c_int64, c_int32, c_int32, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "nrl_miner_slab_sum": (c_int32, [c_void_p, c_int64, c_int64, c_float, c_void_p, c_void_p]),
+    "nrl_miner_cos_fwd": (c_int32, [c_void_p, c_int64, c_int32, c_int32, c_float, c_void_p, c_void_p]),
+    "nrl_miner_cos_bwd": (c_int32, [c_void_p, c_int64, c_int32, c_int32, c_float, c_void_p, c_float, c_void_p, c_void_p]),
+    "nrl_miner_categ_bias_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int64, c_int32]),
+    "nrl_miner_categ_bias_fwd": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int32,
+                                           c_void_p, c_void_p, c_size_t, c_void_p]),
+    "nrl_miner_categ_bias_bwd": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64,
+                                           c_int64, c_int32, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "nrl_miner_poly_workspace_bytes": (c_size_t, [c_int64, c_int32, c_int32]),
+    "nrl_miner_poly_fwd": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_int32, c_int32,
+                                     c_int32, c_void_p, c_void_p, c_void_p]),
+    "nrl_miner_poly_bwd": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_int32,
+                                     c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "nrl_miner_score_fwd": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_int32, c_int32, c_int32,
+                                      c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "nrl_miner_score_bwd": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                      c_void_p, c_void_p, c_int64, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p,
+                                      c_void_p, c_void_p]),
     "nrl_embedding_rows_fwd": (c_int32, [c_void_p, c_void_p, c_int64, c_int32, c_double, c_uint64, c_uint32,
                                          c_void_p, c_void_p]),
     "nrl_embedding_rows_bwd": (c_int32, [c_void_p, c_void_p, c_int64, c_int32, c_double, c_uint64, c_uint32,

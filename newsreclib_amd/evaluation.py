@@ -31,22 +31,28 @@ TEXT_ATTRS = ("title", "abstract")
 ASPECT_ATTRS = ("category", "subcategory", "sentiment")
 
 
+def _map_rows(v, fn):
+    """fn over a news attribute: a tensor, or the dict of tensors of a PLM's tokenised text."""
+    return {k: fn(t) for k, t in v.items()} if isinstance(v, dict) else fn(v)
+
+
 class DeviceNewsTable:
     """attrs: name -> (num_news, ...) tensor (token ids (num_news, L) int64 for text attributes, (num_news,)
-    int64 for category / sentiment ...).  Row 0 may be a padding news; indices are plain row numbers."""
+    int64 for category / sentiment ...) or, for a PLM's tokenised text, a dict of such tensors (``input_ids``,
+    ``attention_mask``).  Row 0 may be a padding news; indices are plain row numbers."""
 
     def __init__(self, attrs: Dict[str, torch.Tensor], device="cuda"):
         if not attrs:
             raise ValueError("DeviceNewsTable needs at least one news attribute")
-        n = {int(v.shape[0]) for v in attrs.values()}
+        n = {int(t.shape[0]) for v in attrs.values() for t in (v.values() if isinstance(v, dict) else (v,))}
         if len(n) != 1:
             raise ValueError(f"all news attributes must have the same number of rows, got {sorted(n)}")
         self.num_news = n.pop()
-        self.attrs = {k: v.to(device).contiguous() for k, v in attrs.items()}
+        self.attrs = {k: _map_rows(v, lambda t: t.to(device).contiguous()) for k, v in attrs.items()}
         self.device = torch.device(device)
 
     def gather(self, idx: torch.Tensor) -> Dict[str, torch.Tensor]:
-        return {k: v.index_select(0, idx) for k, v in self.attrs.items()}
+        return {k: _map_rows(v, lambda t: t.index_select(0, idx)) for k, v in self.attrs.items()}
 
     def build_batch(self, hist_idx: torch.Tensor, hist_sizes: torch.Tensor, cand_idx: torch.Tensor,
                     cand_sizes: torch.Tensor, labels: torch.Tensor, user_idx: Optional[torch.Tensor] = None,
@@ -88,12 +94,15 @@ class NewsVectorCache:
         if getattr(self.module, "user_dependent_news_vectors", False):
             raise NotImplementedError("this recommender's news vectors depend on the user (NPA's personalized attention, "
                                       "text.py:385-390): they cannot be cached; evaluate with the module's own forward")
-        if getattr(getattr(self.module, "hparams", None), "use_plm", False):
+        enc = self.module.news_encoder
+        text_encoders = list((getattr(enc, "text_encoders", {}) or {}).values())
+        # (a PLM text encoder with the CLS head -- use_mhsa == False, MINER -- encodes every news on its own and says so)
+        if getattr(getattr(self.module, "hparams", None), "use_plm", False) and \
+                not (text_encoders and all(getattr(t, "news_independent", False) for t in text_encoders)):
             raise NotImplementedError("the PLM text encoder attends across the news of one call (text.py:92-96): "
                                       "a news vector is not a function of the news alone and cannot be cached")
         was_training = self.module.training
         self.module.eval()
-        enc = self.module.news_encoder
         names = [k for k in self.table.attrs if k in TEXT_ATTRS or k in ("category", "subcategory")]
         # encoders that read entity ids (DKN's KCNN) declare them; every other encoder's call stays as it was
         names += [k for k in getattr(enc, "entity_attrs", ()) if k in self.table.attrs and k not in names]
@@ -107,7 +116,7 @@ class NewsVectorCache:
                     stack.enter_context(te.token_table())
             for lo in range(0, self.table.num_news, self.chunk):
                 hi = min(lo + self.chunk, self.table.num_news)
-                out.append(enc({k: self.table.attrs[k][lo:hi] for k in names}))
+                out.append(enc({k: _map_rows(self.table.attrs[k], lambda t: t[lo:hi]) for k in names}))
         self.vectors = torch.cat(out, dim=0)
         self.module.train(was_training)
         return self.vectors
@@ -137,6 +146,10 @@ class NewsVectorCache:
         dev = self.table.device
         hv = ops.embedding_gather(self.vectors, hist_idx.to(dev).reshape(-1, 1)).reshape(-1, self.vectors.shape[1])
         cv = ops.embedding_gather(self.vectors, cand_idx.to(dev).reshape(-1, 1)).reshape(-1, self.vectors.shape[1])
+        # a scorer that reads news attributes beside the vectors (MINER's category bias) declares them
+        for name in getattr(self.module, "score_news_attrs", ()):
+            meta["x_hist"][name] = self.table.attrs[name].index_select(0, hist_idx.to(dev))
+            meta["x_cand"][name] = self.table.attrs[name].index_select(0, cand_idx.to(dev))
         was_training = self.module.training
         self.module.eval()
         out = self.module.score_news_vectors(hv, cv, meta)

@@ -733,7 +733,8 @@ def register_body_attention() -> bool:
 class PLM(nn.Module):
     """Text encoder over a pretrained language model, mirroring the reference ``PLM`` (text.py:15-109)
     for the NRMS configuration ``use_mhsa=True, apply_reduce_dim=False``: transformer body -> dropout
-    -> multi-head self-attention -> dropout -> additive attention.
+    -> multi-head self-attention -> dropout -> additive attention; and for the CLS head ``use_mhsa=False`` (MINER):
+    transformer body -> CLS row (-> ``reduce_dim`` -> dropout with ``apply_reduce_dim``).
 
     The transformer body is HF ``AutoModel`` running on PyTorch-ROCm (hipBLASLt / SDPA; SURVEY.md build
     plan step 8); everything after ``last_hidden_state`` is ONE call into the HIP library
@@ -751,8 +752,9 @@ class PLM(nn.Module):
         if not isinstance(dropout_probability, float):
             raise ValueError(
                 f"Expected keyword argument `dropout_probability` to be a `float` but got {dropout_probability}")
-        if not use_mhsa or apply_reduce_dim:
-            raise NotImplementedError("newsreclib_amd.PLM covers use_mhsa=True, apply_reduce_dim=False (NRMS)")
+        if use_mhsa and apply_reduce_dim:
+            raise NotImplementedError("newsreclib_amd.PLM covers use_mhsa=True, apply_reduce_dim=False (NRMS) and the CLS head "
+                                      "use_mhsa=False (MINER)")
         from transformers import AutoModel
         self.use_mhsa, self.apply_reduce_dim = use_mhsa, apply_reduce_dim
         self.plm_model = AutoModel.from_pretrained(plm_model)
@@ -795,6 +797,13 @@ class PLM(nn.Module):
             for layer in (frozen_layers or []):
                 if "layer." + str(layer) + "." in name:
                     param.requires_grad = False
+        if not use_mhsa:
+            # the CLS head (text.py:102-107): no attention modules, so the state-dict keys are the reference's
+            if apply_reduce_dim:
+                assert isinstance(reduced_embed_dim, int) and reduced_embed_dim > 0
+                self.reduce_dim = nn.Linear(in_features=embed_dim, out_features=reduced_embed_dim)
+                self.dropout = nn.Dropout(p=dropout_probability)        # holds p; the kernel draws the mask
+            return
         assert isinstance(num_heads, int) and num_heads > 0
         self.multihead_attention = nn.MultiheadAttention(embed_dim=embed_dim, num_heads=num_heads)
         self.additive_attention = AdditiveAttention(input_dim=embed_dim, query_dim=query_dim)
@@ -869,6 +878,24 @@ class PLM(nn.Module):
             shared = True
         return shared
 
+    @property
+    def news_independent(self) -> bool:
+        """Whether a news vector depends on the news alone (the CLS head; the MHSA tail attends across the news of a call)."""
+        return not self.use_mhsa
+
+    def _cls_head(self, hidden: torch.Tensor, seed: Optional[int], stream0: int) -> torch.Tensor:
+        """``use_mhsa=False`` (text.py:102-107): the CLS row, then ``reduce_dim`` on the GEMM engine and element dropout under
+        stream ``stream0`` over (N, reduced_embed_dim).  The news vector depends on the news alone."""
+        vec = hidden[:, 0, :].contiguous()
+        if not self.apply_reduce_dim:
+            return vec
+        lp = (self.reduce_dim.weight, self.reduce_dim.bias)
+        vec = ops_blocks.LinearFn.apply(vec, *lp, _grad_bufs(lp))
+        p = float(self.dropout.p) if self.training else 0.0
+        if p > 0.0:
+            vec = ops_caum.dropout(vec, p, _draw_seed() if seed is None else seed, stream0)
+        return vec
+
     def forward(self, text: Dict[str, torch.Tensor], seed: Optional[int] = None, order=None,
                 stream0: int = 0) -> torch.Tensor:
         hidden = None
@@ -881,6 +908,8 @@ class PLM(nn.Module):
                     break
         if hidden is None:
             hidden = self.plm_model(**text)[0]                      # (N, L, D)
+        if not self.use_mhsa:
+            return self._cls_head(hidden, seed, stream0)
         p = float(self.dropout.p) if self.training else 0.0
         if p > 0.0 and seed is None:
             seed = _draw_seed()

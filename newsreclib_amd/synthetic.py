@@ -139,3 +139,23 @@ def add_dkn_fields(batch: Dict, n_entities: int = 30_000, seed: int = 7, max_per
         out[side] = dict(batch[side])
         out[side]["title_entities"] = t.to(title.device) if torch.is_tensor(title) else t
     return out
+
+
+def add_plm_fields(batch: Dict, vocab_size: int = 50265, pad_id: int = 1, seed: int = 11, L: int = 30) -> Dict:
+    """PLM-style ``title`` inputs (``rec_dataset.py:180-190``: the tokenizer's ``input_ids`` / ``attention_mask`` dict) on both
+    sides of a batch whose ``title`` is a plain id tensor (or absent); a ``title`` that already is a dict is kept.  Every news
+    gets 3..L real tokens (ids uniform over [3, vocab_size): 0-2 are roberta's special tokens), the rest ``pad_id`` under
+    mask 0."""
+    rng = np.random.default_rng(seed)
+    out = dict(batch)
+    for side, key in (("x_hist", "batch_hist"), ("x_cand", "batch_cand")):
+        if isinstance(batch[side].get("title"), dict):
+            continue
+        n, dev = int(batch[key].shape[0]), batch[key].device
+        ids = rng.integers(3, vocab_size, (n, L))
+        lens = rng.integers(3, L + 1, n)
+        m = (np.arange(L)[None, :] < lens[:, None]).astype(np.int64)
+        out[side] = dict(batch[side])
+        out[side]["title"] = {"input_ids": torch.from_numpy(np.where(m == 1, ids, pad_id)).to(dev),
+                              "attention_mask": torch.from_numpy(m).to(dev)}
+    return out

@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
 """Times the LSTUR (BASELINE config 5), NAML (--model naml) NPA (--model npa: title only, 45,215 users), DKN
 (--model dkn: title + title entities over 30,000 entities, 4 windows x 100 filters) or CAUM (--model caum: title, category
-and title entities at the caum.yaml widths) train step on one GPU: B users x 50 clicks, title 30 + abstract 50
+and title entities at the caum.yaml widths), MINER (--model miner: BASELINE configs[3] shape -- roberta-base-shaped random
+body from tests/helpers.make_roberta, L = 96, layers 0-7 frozen, run it with --batch 8 -- at the miner.yaml widths) or, for the
+same-box comparison with it, NRMS-PLM (--model nrms_plm: configs[3] itself) train step on one GPU: B users x 50 clicks, title 30 + abstract 50
 tokens, CNN 300 filters x window 3, GRU 700.  Prints ms/step and impressions/s; with --breakdown also the
 per-kernel time from torch.profiler-free HIP events around the module's stages."""
 import argparse
@@ -21,7 +23,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--vocab", type=int, default=70000)
     ap.add_argument("--engine", default="bf16x3")
-    ap.add_argument("--model", default="lstur", choices=["lstur", "naml", "cen", "mins", "npa", "dkn", "caum"])
+    ap.add_argument("--model", default="lstur", choices=["lstur", "naml", "cen", "mins", "npa", "dkn", "caum", "miner", "nrms_plm"])
     args = ap.parse_args()
     from functools import partial
 
@@ -32,6 +34,8 @@ def main():
     from newsreclib_amd.trainer import NRMSTrainer
     _lib.set_gemm_engine(args.engine)
     torch.manual_seed(0)
+    if args.model in ("miner", "nrms_plm"):
+        return plm_step(args)
     emb = torch.randn(args.vocab, 300) * 0.3
     mod = LSTURModule(
         dataset_attributes=["title", "abstract", "category"], attributes2encode=["title", "abstract", "category"],
@@ -122,6 +126,53 @@ def main():
     dt = (time.perf_counter() - t0) / args.steps
     print(f"{args.model} B={args.batch} engine={args.engine}: {dt * 1e3:.3f} ms/step, {args.batch / dt:.1f} impressions/s, "
           f"loss={float(loss):.4f}")
+
+
+def plm_step(args):
+    """MINER / NRMS-PLM at the BASELINE configs[3] shape: B users x 50 clicks + 5 candidates, titles of 96 tokens."""
+    import statistics
+    import tempfile
+    from functools import partial
+
+    from newsreclib_amd.nrms_module import prepare_batch
+    from newsreclib_amd.synthetic import make_batch
+    from newsreclib_amd.trainer import NRMSTrainer
+    from tests.helpers import PLM_FULL_CFG, make_roberta
+    path = make_roberta(tempfile.mkdtemp(), PLM_FULL_CFG, 41, 0.02)
+    common = dict(dataset_attributes=["title", "abstract", "category"], attributes2encode=["title"],
+                  outputs={"train": [], "val": [], "test": []}, dual_loss_training=False, dual_loss_coef=None,
+                  loss="cross_entropy_loss", late_fusion=False, temperature=None, use_plm=True, plm_model=path,
+                  frozen_layers=list(range(8)), dropout_probability=0.2, top_k_list=[5, 10], num_categ_classes=18,
+                  num_sent_classes=3, save_recs=False, recs_fpath=None, optimizer=partial(torch.optim.Adam, lr=1e-5),
+                  scheduler=None)
+    if args.model == "miner":      # configs/model/miner.yaml
+        from newsreclib_amd.miner_module import MINERModule
+        mod = MINERModule(apply_reduce_dim=True, text_embed_dim=768, news_embed_dim=256, use_categ_bias=True,
+                          pretrained_categ_embeddings_path=None, num_context_codes=32, context_code_dim=200,
+                          score_type="weighted", pretrained_categ_embeddings=torch.randn(19, 300) * 0.3, **common).cuda()
+    else:
+        from newsreclib_amd.nrms_module import NRMSModule
+        mod = NRMSModule(pretrained_embeddings_path=None, embed_dim=768, num_heads=16, query_dim=200, **common).cuda()
+    trainer = NRMSTrainer(mod, lr=1e-5)
+    b = make_batch(args.batch, vocab=50000, mode="fixed", seed=1, L=96, device="cuda")
+    rng = torch.Generator().manual_seed(2)
+    for part in ("x_hist", "x_cand"):          # tokenizer-style inputs (rec_dataset.py:180-190)
+        ids = b[part]["title"].clamp_min(3)
+        b[part]["title"] = {"input_ids": ids, "attention_mask": torch.ones_like(ids)}
+        b[part]["category"] = torch.randint(1, 19, (ids.shape[0],), generator=rng).cuda()
+    batch = prepare_batch(b)
+    for _ in range(args.warmup):
+        trainer.step(batch)
+    times = []
+    for _ in range(args.steps):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        loss = trainer.step(batch)
+        torch.cuda.synchronize()
+        times.append((time.perf_counter() - t0) * 1e3)
+    med = statistics.median(times)
+    print(f"{args.model} B={args.batch} engine={args.engine}: median {med:.2f} ms/step [min {min(times):.2f}, max {max(times):.2f}] "
+          f"over {args.steps} steps, {args.batch / med * 1e3:.1f} impressions/s, loss={float(loss):.4f}")
 
 
 if __name__ == "__main__":
