@@ -878,6 +878,49 @@ int nrl_miner_score_bwd(const float* d_scores, const float* scores, const float*
                         const int64_t* cand_off, int64_t B, int32_t max_cand, int32_t D, int32_t K, int32_t mode,
                         float* d_cand, float* d_user_vector, float* d_Z, void* stream);
 
+/* ---- SentiDebias (fair_rec/senti_debias_module.py:164-263,406-411,475-530; encoders/news/aspect.py) -------------------------
+ * The head around the NRMS encoders.  T (S, D) = tanh(E W^T + b) is the sentiment encoder evaluated on its S = num_sent_classes + 1
+ * ids (S <= 8): every sentiment vector is a row of it.  ids: int64 sentiment ids of the flat news rows, history rows first
+ * (n_hist of N); offsets: int64 (B + 1); D and the hidden width are multiples of 4.  No float atomics: row reductions are written
+ * as one slab per 64 rows (nrl_sd_num_slabs(rows) of them) which the caller adds in order with nrl_miner_slab_sum.
+ *
+ * nrl_sd_rowcos_*: out2 = [mean over history rows, mean over candidate rows] of news_r . T[id_r] / (1e-8 + |news_r| |T[id_r]|);
+ *   partial: 2 * nrl_sd_num_slabs(N) floats of scratch.  _bwd: d_out2 (2) on the device -> d_news (N, D) overwritten (NULL: skipped)
+ *   and slabs of S * D floats for d_T (NULL: skipped).
+ * nrl_sd_hist_*: out (B, H, D): T[id] at the real slots of each user's history, ZERO at padded slots; _bwd: slabs (per 64 slots) of d_T.
+ * nrl_sd_late_fwd: frac (B, S) = class counts / history size, u (B, D) = frac T (late fusion); its gradient is nrl_sd_bt_matmul.
+ * nrl_sd_bt_matmul: out (S, D) = W^T X for W (B, S), X (B, D), users added in order.
+ * nrl_sd_scores_*: out (B, C) = free_scores + (u . T[id of candidate c]) at real slots; P (B, S) = u T^T kept (may be NULL).
+ *   _bwd: d_out (B, C) -> dP (B, S), d_u (B, D) = dP T; d_T = nrl_sd_bt_matmul(dP, u); d_free_scores = d_out.
+ * nrl_sd_disc_tail_*: hidden (N, Hd) = tanh(linear1(news)), w2 (O, Hd), b2 (O), O <= 8: out2 = the two side means of
+ *   -log_softmax(hidden w2^T + b2) at column id - 1, id 0 wrapping to column O - 1 (:409); rows with id > O contribute nothing
+ *   (the host raises before).  _bwd: d_pre (N, Hd) = d_hidden (1 - hidden^2) overwritten; slabs of nrl_sd_disc_slab_width(Hd, O)
+ *   floats: O * Hd of d_w2, then O of d_b2, then padding (NULL: weight gradients skipped).  d_pre is always written: linear1's
+ *   weight gradient needs it as much as the activation gradient does.
+ * Edge cases: a side without rows (n_hist == 0 or n_hist == N) gives 0 for its mean where the reference's empty mean is NaN;
+ * nrl_sd_late_fwd divides by the history size, so a user without history gives NaN rows, as the reference does. */
+int64_t nrl_sd_num_slabs(int64_t rows);
+int32_t nrl_sd_disc_slab_width(int32_t Hd, int32_t O);
+int nrl_sd_rowcos_fwd(const float* news, const int64_t* ids, const float* T, int64_t N, int64_t n_hist, int32_t D, int32_t S,
+                      float* partial, float* out2, void* stream);
+int nrl_sd_rowcos_bwd(const float* news, const int64_t* ids, const float* T, const float* d_out2, int64_t N, int64_t n_hist,
+                      int32_t D, int32_t S, float* d_news, float* slabs, void* stream);
+int nrl_sd_hist_fwd(const int64_t* ids, const int64_t* hist_off, const float* T, int64_t B, int32_t H, int32_t D, int32_t S,
+                    int64_t n_ids, float* out, void* stream);
+int nrl_sd_hist_bwd(const float* d_out, const int64_t* ids, const int64_t* hist_off, int64_t B, int32_t H, int32_t D, int32_t S,
+                    int64_t n_ids, float* slabs, void* stream);
+int nrl_sd_late_fwd(const int64_t* ids, const int64_t* hist_off, const float* T, int64_t B, int32_t D, int32_t S, int64_t n_ids,
+                    float* frac, float* u, void* stream);
+int nrl_sd_bt_matmul(const float* W, const float* X, int64_t B, int32_t S, int32_t D, float* out, void* stream);
+int nrl_sd_scores_fwd(const float* u, const float* T, const int64_t* ids, const int64_t* cand_off, const float* free_scores,
+                      int64_t B, int32_t C, int32_t D, int32_t S, int64_t n_ids, float* P, float* out, void* stream);
+int nrl_sd_scores_bwd(const float* d_out, const float* T, const int64_t* ids, const int64_t* cand_off, int64_t B, int32_t C,
+                      int32_t D, int32_t S, int64_t n_ids, float* dP, float* d_u, void* stream);
+int nrl_sd_disc_tail_fwd(const float* hidden, const float* w2, const float* b2, const int64_t* ids, int64_t N, int64_t n_hist,
+                         int32_t Hd, int32_t O, float* partial, float* out2, void* stream);
+int nrl_sd_disc_tail_bwd(const float* hidden, const float* w2, const float* b2, const int64_t* ids, const float* d_out2, int64_t N,
+                         int64_t n_hist, int32_t Hd, int32_t O, float* d_pre, float* slabs, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -264,6 +264,23 @@ SIGNATURES = {
     "nrl_miner_score_bwd": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                       c_void_p, c_void_p, c_int64, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p,
                                       c_void_p, c_void_p]),
+    "nrl_sd_num_slabs": (c_int64, [c_int64]),
+    "nrl_sd_disc_slab_width": (c_int32, [c_int32, c_int32]),
+    "nrl_sd_rowcos_fwd": (c_int32, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int32, c_int32, c_void_p, c_void_p, c_void_p]),
+    "nrl_sd_rowcos_bwd": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int32, c_int32, c_void_p, c_void_p,
+                                    c_void_p]),
+    "nrl_sd_hist_fwd": (c_int32, [c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_int32, c_int32, c_int64, c_void_p, c_void_p]),
+    "nrl_sd_hist_bwd": (c_int32, [c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_int32, c_int32, c_int64, c_void_p, c_void_p]),
+    "nrl_sd_late_fwd": (c_int32, [c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_int32, c_int64, c_void_p, c_void_p, c_void_p]),
+    "nrl_sd_bt_matmul": (c_int32, [c_void_p, c_void_p, c_int64, c_int32, c_int32, c_void_p, c_void_p]),
+    "nrl_sd_scores_fwd": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_int32, c_int32, c_int64,
+                                    c_void_p, c_void_p, c_void_p]),
+    "nrl_sd_scores_bwd": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_int32, c_int32, c_int64, c_void_p,
+                                    c_void_p, c_void_p]),
+    "nrl_sd_disc_tail_fwd": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int32, c_int32, c_void_p,
+                                       c_void_p, c_void_p]),
+    "nrl_sd_disc_tail_bwd": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int32, c_int32,
+                                       c_void_p, c_void_p, c_void_p]),
     "nrl_embedding_rows_fwd": (c_int32, [c_void_p, c_void_p, c_int64, c_int32, c_double, c_uint64, c_uint32,
                                          c_void_p, c_void_p]),
     "nrl_embedding_rows_bwd": (c_int32, [c_void_p, c_void_p, c_int64, c_int32, c_double, c_uint64, c_uint32,

@@ -1220,3 +1220,47 @@ class NRMSTrainer:
         scale = r._timed(r.finish)
         r._step_measured()
         return scale
+
+
+class _FlatOptimizer:
+    """What ``SentiDebiasModule.training_step`` needs of an optimizer (``param_groups`` / ``step`` / ``zero_grad``) over one
+    ``FlatParams`` + ``FusedAdam`` pair."""
+
+    def __init__(self, flat: FlatParams, adam: FusedAdam):
+        self.flat, self.adam = flat, adam
+        self.param_groups = [{"params": flat.params}]
+
+    def step(self) -> None:
+        for p in self.flat.params:           # gradients autograd handed back (the head) join the ones the kernels wrote in place
+            if p.grad is not None:
+                p.main_grad.add_(p.grad)
+                p.grad = None
+        self.adam.step(zero_grad=True)       # (announces the parameter write: FusedAdam.begin_step)
+
+    def zero_grad(self, set_to_none: bool = True) -> None:
+        for p in self.flat.params:           # (the flat gradient was cleared by the step)
+            p.grad = None
+
+
+class SentiDebiasTrainer:
+    """The two-optimizer train step of ``senti_debias_module.SentiDebiasModule`` (senti_debias_module.py:475-530) under this
+    library's flat Adam: one ``FlatParams`` + ``FusedAdam`` pair for the generator and one for the discriminator, installed as the
+    module's ``optimizers()``.  Learning rates default to configs/model/senti_debias.yaml:66-74.  Single GPU."""
+
+    def __init__(self, module, lr_generator: float = 1e-5, lr_discriminator: float = 2e-5, betas=(0.9, 0.999), eps: float = 1e-8):
+        if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+            raise NotImplementedError("SentiDebiasTrainer: the two-optimizer step has no data-parallel gradient exchange")
+        self.module = module
+        self.flat_g, self.flat_d = FlatParams(module.generator.parameters()), FlatParams(module.discriminator.parameters())
+        self.opt_g, self.opt_d = FusedAdam(self.flat_g, lr_generator, betas, eps), FusedAdam(self.flat_d, lr_discriminator, betas, eps)
+        self.optimizers = [_FlatOptimizer(self.flat_g, self.opt_g), _FlatOptimizer(self.flat_d, self.opt_d)]
+        module.install_optimizers(self.optimizers)
+
+    def step(self, batch: Dict):
+        """One train step -> (g_loss, d_loss), detached device scalars."""
+        if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+            raise NotImplementedError("SentiDebiasTrainer: the two-optimizer step has no data-parallel gradient exchange")
+        if not self.module.training:
+            self.module.train()
+        g_loss, d_loss, _, _ = self.module.adversarial_step(batch)
+        return g_loss, d_loss

@@ -23,7 +23,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--vocab", type=int, default=70000)
     ap.add_argument("--engine", default="bf16x3")
-    ap.add_argument("--model", default="lstur", choices=["lstur", "naml", "cen", "mins", "npa", "dkn", "caum", "miner", "nrms_plm"])
+    ap.add_argument("--model", default="lstur", choices=["lstur", "naml", "cen", "mins", "npa", "dkn", "caum", "miner", "nrms_plm", "sentidebias", "nrms"])
     args = ap.parse_args()
     from functools import partial
 
@@ -36,6 +36,8 @@ def main():
     torch.manual_seed(0)
     if args.model in ("miner", "nrms_plm"):
         return plm_step(args)
+    if args.model in ("sentidebias", "nrms"):
+        return senti_step(args)
     emb = torch.randn(args.vocab, 300) * 0.3
     mod = LSTURModule(
         dataset_attributes=["title", "abstract", "category"], attributes2encode=["title", "abstract", "category"],
@@ -126,6 +128,59 @@ def main():
     dt = (time.perf_counter() - t0) / args.steps
     print(f"{args.model} B={args.batch} engine={args.engine}: {dt * 1e3:.3f} ms/step, {args.batch / dt:.1f} impressions/s, "
           f"loss={float(loss):.4f}")
+
+
+def senti_step(args):
+    """--model sentidebias: the two-optimizer SentiDebias step (configs/model/senti_debias.yaml: title, 300 / 15 heads / 200,
+    discriminator 300-256-3) under ``SentiDebiasTrainer``; --model nrms: the NRMS step of the same shape under ``NRMSTrainer``,
+    the same-box yardstick.  Median of per-step event times."""
+    from functools import partial
+
+    from newsreclib_amd.nrms_module import NRMSModule
+    from newsreclib_amd.senti_debias_module import Discriminator, Generator, SentiDebiasModule, SentimentEncoder
+    from newsreclib_amd.synthetic import make_batch
+    from newsreclib_amd.trainer import NRMSTrainer, SentiDebiasTrainer
+    emb = torch.randn(args.vocab, 300) * 0.3
+    batch = make_batch(args.batch, vocab=args.vocab, mode="fixed", seed=1, device="cuda")
+    g = torch.Generator().manual_seed(5)
+    for part in ("x_hist", "x_cand"):
+        batch[part]["sentiment"] = torch.randint(0, 4, (batch[part]["title"].shape[0],), generator=g).cuda()
+    outputs = {"train": [], "val": [], "test": []}
+    if args.model == "nrms":
+        mod = NRMSModule(dataset_attributes=["title", "abstract", "category"], attributes2encode=["title"], outputs=outputs,
+                         dual_loss_training=False, dual_loss_coef=None, loss="cross_entropy_loss", late_fusion=False,
+                         temperature=None, use_plm=False, pretrained_embeddings_path=None, plm_model=None, frozen_layers=None,
+                         embed_dim=300, num_heads=15, query_dim=200, dropout_probability=0.2, top_k_list=[5, 10],
+                         num_categ_classes=18, num_sent_classes=3, save_recs=False, recs_fpath=None,
+                         optimizer=partial(torch.optim.Adam, lr=1e-4), scheduler=None, pretrained_embeddings=emb).cuda()
+        trainer = NRMSTrainer(mod, lr=1e-4)
+    else:
+        gen = Generator(dataset_attributes=["title", "abstract", "category", "sentiment"], attributes2encode=["title"],
+                        late_fusion=False, use_plm=False, pretrained_embeddings_path=None, plm_model=None, frozen_layers=None,
+                        embed_dim=300, num_heads=15, query_dim=200, dropout_probability=0.2,
+                        sentiment_encoder=SentimentEncoder(3, 256, 300), pretrained_embeddings=emb)
+        mod = SentiDebiasModule(outputs=outputs, generator=gen, discriminator=Discriminator(300, 256, 3), top_k_list=[5, 10],
+                                num_categ_classes=18, num_sent_classes=3, save_recs=False, recs_fpath=None, optimizer=None,
+                                alpha_coefficient=0.15, beta_coefficient=10.0,
+                                optimizer_generator=partial(torch.optim.Adam, lr=1e-5),
+                                optimizer_discriminator=partial(torch.optim.Adam, lr=2e-5), scheduler=None).cuda()
+        trainer = SentiDebiasTrainer(mod)
+    batch = mod._prepare(batch)
+    for _ in range(args.warmup):
+        trainer.step(batch)
+    times = []
+    for _ in range(args.steps):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        loss = trainer.step(batch)
+        b.record()
+        torch.cuda.synchronize()
+        times.append(a.elapsed_time(b))
+    times.sort()
+    med = times[len(times) // 2]
+    loss = loss if torch.is_tensor(loss) else loss[0]
+    print(f"{args.model} B={args.batch} engine={args.engine}: median {med:.3f} ms/step [min {times[0]:.3f}, max {times[-1]:.3f}] "
+          f"over {len(times)} steps, loss={float(loss):.4f}")
 
 
 def plm_step(args):
