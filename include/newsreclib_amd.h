@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define NRL_ABI_VERSION 16
+#define NRL_ABI_VERSION 17
 
 #define NRL_OK 0
 #define NRL_E_INVALID (-1)   /* bad argument (shape / alignment / null) */
@@ -920,6 +920,27 @@ int nrl_sd_disc_tail_fwd(const float* hidden, const float* w2, const float* b2, 
                          int32_t Hd, int32_t O, float* partial, float* out2, void* stream);
 int nrl_sd_disc_tail_bwd(const float* hidden, const float* w2, const float* b2, const int64_t* ids, const float* d_out2, int64_t N,
                          int64_t n_hist, int32_t Hd, int32_t O, float* d_pre, float* slabs, void* stream);
+
+/* ---- MANNeR (fair_rec/manner_a_module.py:151-176, manner_module.py:152-204) ---------------------------------------------------
+ * nrl_supcon_embed_fwd_bwd: pytorch-metric-learning 2.2.0 SupConLoss(temperature, DotProductSimilarity(normalize_embeddings=False))
+ *   of embeddings E (N, D) with int64 labels (N), AvgNonZeroReducer, loss (1) and dE (N, D) = grad_scale * d loss / d E in one call.
+ *   Pairs: positives = same label off the diagonal, negatives = different label; the log-sum-exp runs over everything off the
+ *   diagonal; rows without a positive (or with a row loss <= 0) are dropped by the reducer.  The loss is exactly 0 with dE = 0 when
+ *   the batch has no positive pair or no negative pair.  S = E E^T and dE = (dS + dS^T) E run on the exact-fp32 MFMA GEMM whatever
+ *   nrl_set_gemm_engine says (a few MFLOP; the scores go through exp()).  1 <= N <= 1024, D a multiple of 4 up to 1024; workspace nrl_supcon_embed_workspace_bytes(N, D),
+ *   256-byte aligned.  No atomics: two calls on the same input give the same bits.
+ * nrl_manner_scores: out (B, max_cand) = sum_t weights[t] * zscore_b(mean(tables[t][hist of b]) . tables[t][cand of b]) for k in
+ *   {1, 2, 3} news-vector tables (V, D); `tables` (k device pointers) and `weights` (k floats) are HOST arrays read during the call.
+ *   hist_idx / cand_idx: int64 news rows concatenated over the impressions, *_offsets: int64 (B + 1).  The z-score uses the mean
+ *   and the UNBIASED standard deviation of the impression's own candidates, without an epsilon: an impression with one candidate,
+ *   with zero score variance or with an empty history gives a non-finite row, as the reference does.  Padded slots are written 0;
+ *   indices outside [0, V) are clamped.  D a multiple of 4 up to 1024, max_cand <= 2048.  Forward only. */
+size_t nrl_supcon_embed_workspace_bytes(int64_t N, int32_t D);
+int nrl_supcon_embed_fwd_bwd(const float* E, const int64_t* labels, int64_t N, int32_t D, float temperature, float grad_scale,
+                             float* loss, float* dE, void* ws, size_t ws_bytes, void* stream);
+int nrl_manner_scores(const float* const* tables, const float* weights, int32_t k, int64_t V, const int64_t* hist_idx,
+                      const int64_t* hist_offsets, const int64_t* cand_idx, const int64_t* cand_offsets, int64_t B,
+                      int32_t max_cand, int32_t D, float* out, void* stream);
 
 #ifdef __cplusplus
 }

@@ -11,7 +11,7 @@ from ctypes import POINTER, c_char_p, c_double, c_float, c_int32, c_int64, c_siz
 
 _PKG = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_PKG, "libnewsreclib_amd.so")
-ABI_VERSION = 16
+ABI_VERSION = 17
 
 
 class NrlBlockParams(ctypes.Structure):
@@ -281,6 +281,11 @@ SIGNATURES = {
                                        c_void_p, c_void_p]),
     "nrl_sd_disc_tail_bwd": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int32, c_int32,
                                        c_void_p, c_void_p, c_void_p]),
+    "nrl_supcon_embed_workspace_bytes": (c_size_t, [c_int64, c_int32]),
+    "nrl_supcon_embed_fwd_bwd": (c_int32, [c_void_p, c_void_p, c_int64, c_int32, c_float, c_float, c_void_p, c_void_p, c_void_p,
+                                           c_size_t, c_void_p]),
+    "nrl_manner_scores": (c_int32, [POINTER(c_void_p), POINTER(c_float), c_int32, c_int64, c_void_p, c_void_p, c_void_p, c_void_p,
+                                    c_int64, c_int32, c_int32, c_void_p, c_void_p]),
     "nrl_embedding_rows_fwd": (c_int32, [c_void_p, c_void_p, c_int64, c_int32, c_double, c_uint64, c_uint32,
                                          c_void_p, c_void_p]),
     "nrl_embedding_rows_bwd": (c_int32, [c_void_p, c_void_p, c_int64, c_int32, c_double, c_uint64, c_uint32,

@@ -179,6 +179,61 @@ class NewsVectorCache:
                 meta["user_ids"], cand_idx.to(dev))
 
 
+class MannerVectorCache:
+    """Encode-once evaluation of ``manner_module.MANNERModule``: one ``NewsVectorCache`` per loaded sub-model over the same
+    ``DeviceNewsTable``; ``scores`` is one ``nrl_manner_scores`` launch that gathers straight from the (up to three) tables.
+    ``model_step`` returns the 11-tuple ``evaluate_impressions`` consumes, with a zero tensor in the loss slot (MANNeR has no
+    loss).  The sub-models' encoders read the concatenated ``text`` input, which ``NewsVectorCache.build`` passes through because
+    ``NewsEncoder.entity_attrs`` lists it beside ``entities`` under ``concatenate_inputs`` (that property is the cache's list of
+    inputs to hand over besides title / abstract / category, entity ids or not).
+
+    ``hist_sizes`` / ``cand_sizes`` are HOST tensors, as ``evaluate_impressions`` builds them: the width of the score matrix is
+    their maximum, read on the host (a device tensor there costs one read-back per batch), so it covers every impression."""
+
+    def __init__(self, module, table: DeviceNewsTable, chunk: int = 16384):
+        self.module, self.table = module, table
+        pairs = module.submodels()
+        self.weights = [w for _, w in pairs]
+        self.caches = [NewsVectorCache(m, table, chunk) for m, _ in pairs]
+        self.vectors = None
+
+    @torch.no_grad()
+    def build(self):
+        self.vectors = [c.build() for c in self.caches]
+        return self.vectors
+
+    @torch.no_grad()
+    def scores(self, hist_idx: torch.Tensor, hist_sizes: torch.Tensor, cand_idx: torch.Tensor, cand_sizes: torch.Tensor,
+               user_idx: Optional[torch.Tensor] = None) -> torch.Tensor:
+        from .ops_manner import manner_scores
+        if self.vectors is None:
+            self.build()
+        dev = self.table.device
+        max_cand = int(cand_sizes.max())                       # the true largest count: no impression is truncated
+        zero = torch.zeros(1, dtype=torch.int64, device=dev)
+        hist_off = torch.cat([zero, torch.cumsum(hist_sizes.to(dev).long(), 0)])
+        cand_off = torch.cat([zero, torch.cumsum(cand_sizes.to(dev).long(), 0)])
+        return manner_scores(self.vectors, self.weights, hist_idx.to(dev).long(), hist_off, cand_idx.to(dev).long(), cand_off,
+                             max_cand)
+
+    @torch.no_grad()
+    def model_step(self, hist_idx, hist_sizes, cand_idx, cand_sizes, labels, user_idx=None, user_ids=None):
+        if self.vectors is None:
+            self.build()
+        dev = self.table.device
+        meta = self.caches[0]._meta(hist_sizes, cand_sizes, labels, user_idx, user_ids)
+        scores = self.scores(hist_idx, hist_sizes, cand_idx, cand_sizes, user_idx)
+        preds = scores.reshape(-1)[meta["cand_flat_idx"]]
+        empty = torch.empty(0, dtype=torch.int64, device=dev)
+
+        def attr(idx, name):
+            return self.table.attrs[name].index_select(0, idx.to(dev)) if name in self.table.attrs else empty
+
+        return (scores.new_zeros(()), preds, meta["labels"], meta["cand_sizes"], meta["hist_sizes"], attr(cand_idx, "category"),
+                attr(cand_idx, "sentiment"), attr(hist_idx, "category"), attr(hist_idx, "sentiment"), meta["user_ids"],
+                cand_idx.to(dev))
+
+
 def evaluate_impressions(cache: NewsVectorCache, impressions: Sequence[Dict], batch_size: int = 512,
                          top_k_list: Sequence[int] = (5, 10), num_categ_classes: Optional[int] = None,
                          num_sent_classes: Optional[int] = None) -> Dict[str, float]:

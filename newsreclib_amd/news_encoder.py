@@ -987,8 +987,12 @@ class NewsEncoder(nn.Module):
 
     @property
     def entity_attrs(self):
-        """Entity-id inputs this encoder reads (``evaluation.NewsVectorCache`` passes them through)."""
-        return tuple(self.entity_encoders.keys()) if self.encode_entity else ()
+        """Entity-id inputs this encoder reads (``evaluation.NewsVectorCache`` passes them through); with
+        ``concatenate_inputs`` (MANNeR) also the concatenated ``text`` input, which is not one of the per-attribute texts."""
+        ents = tuple(self.entity_encoders.keys()) if self.encode_entity else ()
+        if self.concatenate_inputs and self.encode_text:
+            return ("text",) + ents
+        return ents
 
     def share_plm_bodies(self, *news_dicts) -> int:
         """Before several ``forward`` calls of one step (history news, candidate news): every PLM text encoder runs its transformer

@@ -159,3 +159,24 @@ def add_plm_fields(batch: Dict, vocab_size: int = 50265, pad_id: int = 1, seed: 
         out[side]["title"] = {"input_ids": torch.from_numpy(np.where(m == 1, ids, pad_id)).to(dev),
                               "attention_mask": torch.from_numpy(m).to(dev)}
     return out
+
+
+def make_news_batch(n_classes: int, samples_per_class: int, vocab_size: int = 50265, n_entities: int = 30_000, L: int = 96,
+                    L_entities: int = 10, pad_id: int = 1, seed: int = 21, use_entities: bool = True) -> Dict:
+    """A ``NewsBatch`` as the A-Module reads it (manner_a_module.py:159-176): ``news["text"]`` = the tokenised concatenation of title
+    and abstract (``input_ids`` / ``attention_mask``, 3..L real tokens per news), ``news["entities"]`` = the concatenated title +
+    abstract entity ids (0 = none), and int64 aspect ``labels`` with ``samples_per_class`` news of each of ``n_classes`` classes in
+    shuffled order (the reference's MPerClassSampler batch: 17 x 5 = 85 at the configured shape)."""
+    rng = np.random.default_rng(seed)
+    n = int(n_classes) * int(samples_per_class)
+    ids = rng.integers(3, vocab_size, (n, L))
+    lens = rng.integers(3, L + 1, n)
+    m = (np.arange(L)[None, :] < lens[:, None]).astype(np.int64)
+    news = {"text": {"input_ids": torch.from_numpy(np.where(m == 1, ids, pad_id)), "attention_mask": torch.from_numpy(m)}}
+    if use_entities:
+        k = rng.integers(0, L_entities + 1, n)
+        ents = rng.integers(1, n_entities, (n, L_entities)).astype(np.int64)
+        ents[np.arange(L_entities)[None, :] >= k[:, None]] = 0
+        news["entities"] = torch.from_numpy(ents)
+    labels = np.repeat(np.arange(n_classes, dtype=np.int64), samples_per_class)
+    return {"news": news, "labels": torch.from_numpy(rng.permutation(labels))}
