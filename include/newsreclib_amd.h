@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define NRL_ABI_VERSION 17
+#define NRL_ABI_VERSION 18
 
 #define NRL_OK 0
 #define NRL_E_INVALID (-1)   /* bad argument (shape / alignment / null) */
@@ -627,6 +627,15 @@ int nrl_npa_encoder_bwd(const NrlCnnParams* p, const NrlCnnGrads* g, float* d_em
                         uint64_t seed, uint32_t stream0, const float* d_out, float* d_queries, void* ws, size_t ws_bytes,
                         void* stream);
 
+/* Encode-once evaluation, step 1: the eval-mode conv feature maps c = relu(conv(emb[ids]) + b) (text.py:377-383 with dropout
+ * off) of n_news rows, fp32, written straight into the caller's buffer out (n_news, L, F) -- a slice of a preallocated
+ * (num_news, L, F) table.  The same lookup and convolution stages as nrl_npa_encoder_fwd under the current engine, so a cached
+ * map has the bits the forward computes for that news.  `p` as for nrl_npa_encoder_fwd; out must be 16-byte aligned. */
+size_t nrl_npa_conv_features_workspace_bytes(int64_t n_news, int32_t seq_len, int32_t embed_dim, int32_t num_filters,
+                                             int32_t window);
+int nrl_npa_conv_features(const NrlCnnParams* p, const float* emb_table, int64_t vocab, const int64_t* ids, int64_t n_news,
+                          int32_t seq_len, float* out, void* ws, size_t ws_bytes, void* stream);
+
 /* Every per-user query of an NPA step in one launch.  Field <-> reference state_dict key:
  *   user_table        user_projection.user_embed                                                   (num_users, U)
  *   text_proj_*       news_encoder.text_query_projection.preference_query_projection.{weight,bias}   (Pw, U), (Pw)
@@ -686,6 +695,26 @@ int nrl_personalized_user_attention_fwd(const float* hist, const int64_t* hist_o
 int nrl_personalized_user_attention_bwd(const float* hist, const int64_t* hist_offsets, int64_t batch, int32_t max_hist,
                                         int32_t dim, const float* queries, const float* d_out, float* d_hist,
                                         float* d_queries, void* stream);
+
+/* Encode-once evaluation, step 2: NPAModule.forward in eval mode for a batch of impressions given by news-index lists, read
+ * from the cached table (num_news, L, F) of nrl_npa_conv_features.  Plain fp32 vector code, the same under every engine.
+ *   hist_idx (n_hist) / cand_idx (n_cand) int64 rows of the table; impression b owns [hist_offsets[b], hist_offsets[b+1]) and
+ *   [cand_offsets[b], cand_offsets[b+1]) (batch + 1 int64 each).  An index outside [0, num_news) stands for an all-zero feature
+ *   map (it pools to a zero vector) and is never dereferenced.
+ *   q_hist, q_cand (batch, F): the tanh'd text queries of the two CNNPersAtt calls; q_news (batch, F): the user encoder's news
+ *   query, or NULL for late fusion.
+ * Per impression: every history row is pooled with q_hist[b] (softmax over ALL L tokens); the pooled rows are attended with
+ * q_news[b], the softmax also counting max_hist - n_b zero rows of score 0 as nrl_personalized_user_attention_fwd does (late
+ * fusion: their mean); every candidate row is pooled with q_cand[b] and dotted with the user vector.
+ * WRITES user_vectors (batch, F) and scores (batch, max_cand), slots j >= n_cand_b exactly 0.  An empty history gives a zero
+ * user vector.  Two launches: user vectors (one workgroup per impression, the waves' online-softmax states merged through
+ * LDS), then one wave per candidate row of the whole batch.  Each table row is read once; no atomics; a fixed summation order.
+ * F % 4 == 0, F <= 1024; max_hist / max_cand: the largest counts of the batch (longer lists are cut there). */
+int nrl_npa_cached_scores(const float* table, int64_t num_news, int32_t seq_len, int32_t num_filters, const int64_t* hist_idx,
+                          int64_t n_hist, const int64_t* hist_offsets, const int64_t* cand_idx, int64_t n_cand,
+                          const int64_t* cand_offsets, int64_t batch, const float* q_hist, const float* q_cand,
+                          const float* q_news, int32_t max_hist, int32_t max_cand, float* user_vectors, float* scores,
+                          void* stream);
 
 /* ---- DKN (dkn_module.py:207-240): knowledge-aware CNN news encoder + candidate-aware user attention -------------------
  * Field <-> reference state_dict key (news_encoder.*):

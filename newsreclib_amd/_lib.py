@@ -11,7 +11,7 @@ from ctypes import POINTER, c_char_p, c_double, c_float, c_int32, c_int64, c_siz
 
 _PKG = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_PKG, "libnewsreclib_amd.so")
-ABI_VERSION = 17
+ABI_VERSION = 18
 
 
 class NrlBlockParams(ctypes.Structure):
@@ -196,6 +196,12 @@ SIGNATURES = {
     "nrl_npa_encoder_bwd": (c_int32, [POINTER(NrlCnnParams), POINTER(NrlCnnGrads), c_void_p, c_int64, c_void_p,
                                       c_void_p, c_int64, c_int32, c_void_p, c_void_p, c_void_p, c_int64, c_double,
                                       c_uint64, c_uint32, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "nrl_npa_conv_features_workspace_bytes": (c_size_t, [c_int64, c_int32, c_int32, c_int32, c_int32]),
+    "nrl_npa_conv_features": (c_int32, [POINTER(NrlCnnParams), c_void_p, c_int64, c_void_p, c_int64, c_int32, c_void_p,
+                                        c_void_p, c_size_t, c_void_p]),
+    "nrl_npa_cached_scores": (c_int32, [c_void_p, c_int64, c_int32, c_int32, c_void_p, c_int64, c_void_p, c_void_p, c_int64,
+                                        c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_void_p,
+                                        c_void_p, c_void_p]),
     "nrl_npa_user_queries_workspace_bytes": (c_size_t, [POINTER(NrlNpaQueryParams), c_int64]),
     "nrl_npa_user_queries_fwd": (c_int32, [POINTER(NrlNpaQueryParams), c_void_p, c_int64, c_double, c_uint64, c_uint32,
                                            c_void_p, c_void_p, c_void_p]),

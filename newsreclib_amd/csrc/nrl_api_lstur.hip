@@ -727,6 +727,35 @@ static int npa_check(const NrlCnnParams* p, int64_t n_news, int L, const float* 
 
 static size_t npa_ws_floats(const CnnShape& s) { return cnn_ws_floats(s) + align_up((size_t)s.N * s.F, 64); }
 
+// x = dropout(emb[ids]); c_out (M, F) = dropout(relu(conv(x) + b)) under the current engine: the lookup and convolution stages of
+// nrl_npa_encoder_fwd and nrl_npa_conv_features (which passes its caller's buffer as c_out and no dropout).
+static int npa_conv_stage(const NrlCnnParams* p, const CnnShape& s, const CnnWs& w, const float* emb_table, const int64_t* ids,
+                          const Dropout& drop1, const Dropout& drop2, float* c_out, hipStream_t st) {
+  const int KD = s.W * s.D;
+  SplitWeight sc = planes_view(w.planes_conv, s.F, KD);
+  CnnRp rp;
+  NRL_TRY(cnn_rp_images(p, s, w, true, &rp, st));
+  if (cur_engine() == ENGINE_BF16X3 && !rp.on) NRL_TRY(split_weight(p->conv_weight, s.F, KD, w.planes_conv, &sc, st));
+  // x = dropout(emb[ids]); c = dropout(relu(conv(x) + b))             (text.py:377-383), as nrl_cnn_encoder_fwd
+  const EpiLinear epi_c{c_out, s.F, p->conv_bias, 2, drop2, s.F};
+  if (cnn_x_planes_on(s) && rp.on && w.xpl != nullptr) {
+    const int ncb_x = cnn_ncb_x(s), nrb = 2 * cnn_conv_kt(s);
+    NRL_TRY(launch_embedding_rows_planes(emb_table, ids, s.N, s.L, s.D, ncb_x, nrb, drop1, w.xpl, st));
+    NRL_TRY(rp_dispatch(KCWindowPlanes{w.xpl, s.M, s.L, nrb, ncb_x, s.W, s.pad}, rp.conv_f, epi_c, s.M, s.F,
+                        s.W * 16 * ncb_x, st));
+  } else {
+    NRL_TRY(embedding_rows_fwd(emb_table, ids, s.M, s.D, drop1, 0, w.x, st));
+    const KCWindow a{w.x, s.M, s.D, s.L, s.W, s.pad};
+    if (cur_engine() == ENGINE_BF16X3) {
+      NRL_TRY(gemm_any(a, KCPlain{p->conv_weight, KD, s.F}, sc.hi, sc.lo, sc.ld, epi_c, s.M, s.F, KD, st,
+                       rp.on ? &rp.conv_f : nullptr));
+    } else {
+      NRL_TRY(launch_gemm<NRL_TILE>(a, KCPlain{p->conv_weight, KD, s.F}, epi_c, s.M, s.F, KD, 1, st));
+    }
+  }
+  return NRL_OK;
+}
+
 extern "C" {
 
 size_t nrl_npa_encoder_workspace_bytes(int64_t n_news, int32_t seq_len, int32_t embed_dim, int32_t num_filters,
@@ -749,30 +778,33 @@ int nrl_npa_encoder_fwd(const NrlCnnParams* p, const float* emb_table, int64_t v
   NRL_TRY(cnn_carve(ws, ws_bytes, s, &w));
   hipStream_t st = (hipStream_t)stream;
   const Dropout drop1 = make_dropout(p_drop, seed, stream0), drop2 = make_dropout(p_drop, seed, stream0 + 1);
-  const int KD = s.W * s.D;
-  SplitWeight sc = planes_view(w.planes_conv, s.F, KD);
-  CnnRp rp;
-  NRL_TRY(cnn_rp_images(p, s, w, true, &rp, st));
-  if (cur_engine() == ENGINE_BF16X3 && !rp.on) NRL_TRY(split_weight(p->conv_weight, s.F, KD, w.planes_conv, &sc, st));
-  // x = dropout(emb[ids]); c = dropout(relu(conv(x) + b))             (text.py:377-383), as nrl_cnn_encoder_fwd
-  const EpiLinear epi_c{w.c, s.F, p->conv_bias, 2, drop2, s.F};
-  if (cnn_x_planes_on(s) && rp.on && w.xpl != nullptr) {
-    const int ncb_x = cnn_ncb_x(s), nrb = 2 * cnn_conv_kt(s);
-    NRL_TRY(launch_embedding_rows_planes(emb_table, ids, s.N, s.L, s.D, ncb_x, nrb, drop1, w.xpl, st));
-    NRL_TRY(rp_dispatch(KCWindowPlanes{w.xpl, s.M, s.L, nrb, ncb_x, s.W, s.pad}, rp.conv_f, epi_c, s.M, s.F,
-                        s.W * 16 * ncb_x, st));
-  } else {
-    NRL_TRY(embedding_rows_fwd(emb_table, ids, s.M, s.D, drop1, 0, w.x, st));
-    const KCWindow a{w.x, s.M, s.D, s.L, s.W, s.pad};
-    if (cur_engine() == ENGINE_BF16X3) {
-      NRL_TRY(gemm_any(a, KCPlain{p->conv_weight, KD, s.F}, sc.hi, sc.lo, sc.ld, epi_c, s.M, s.F, KD, st,
-                       rp.on ? &rp.conv_f : nullptr));
-    } else {
-      NRL_TRY(launch_gemm<NRL_TILE>(a, KCPlain{p->conv_weight, KD, s.F}, epi_c, s.M, s.F, KD, 1, st));
-    }
-  }
+  NRL_TRY(npa_conv_stage(p, s, w, emb_table, ids, drop1, drop2, w.c, st));
   // w = softmax_t(queries[owner[n]] . c_t); out = sum_t w_t c_t     (attention.py:244-259)
   return npa_pool_fwd(w.c, queries, owner, n_queries, s.N, s.L, s.F, save_for_backward != 0 ? w.w : nullptr, out, st);
+}
+
+size_t nrl_npa_conv_features_workspace_bytes(int64_t n_news, int32_t seq_len, int32_t embed_dim, int32_t num_filters,
+                                             int32_t window) {
+  return cnn_ws_floats(npa_shape(n_news, seq_len, embed_dim, num_filters, window)) * sizeof(float);
+}
+
+// c = relu(conv(emb[ids]) + b) (text.py:377-383 in eval mode) straight into the caller's (n_news, L, F) buffer
+int nrl_npa_conv_features(const NrlCnnParams* p, const float* emb_table, int64_t vocab, const int64_t* ids, int64_t n_news,
+                          int32_t seq_len, float* out, void* ws, size_t ws_bytes, void* stream) {
+  (void)vocab;
+  NRL_REQUIRE(p != nullptr && p->conv_weight && p->conv_bias && emb_table && ids && out, "npa_conv_features: null argument");
+  NRL_REQUIRE(p->embed_dim > 0 && p->embed_dim % 4 == 0, "embed_dim must be a positive multiple of 4");
+  NRL_REQUIRE(p->num_filters > 0 && p->num_filters % 4 == 0, "num_filters must be a positive multiple of 4");
+  NRL_REQUIRE(p->window >= 1 && p->window <= 7 && p->window % 2 == 1, "window must be odd and <= 7");
+  NRL_REQUIRE(n_news >= 0 && seq_len > 0, "bad news batch shape");
+  NRL_REQUIRE((((uintptr_t)p->conv_weight | (uintptr_t)out) & 15) == 0, "weights and output must be 16-byte aligned");
+  const CnnShape s = npa_shape(n_news, seq_len, p->embed_dim, p->num_filters, p->window);
+  NRL_REQUIRE(s.M * (int64_t)(s.D > s.F ? s.D : s.F) < (1LL << 32), "row index space is 32-bit: encode the table in chunks");
+  if (s.M == 0) return NRL_OK;
+  CnnWs w;
+  NRL_TRY(cnn_carve(ws, ws_bytes, s, &w));
+  const Dropout none = make_dropout(0.0, 0, 0);
+  return npa_conv_stage(p, s, w, emb_table, ids, none, none, out, (hipStream_t)stream);
 }
 
 int nrl_npa_encoder_bwd(const NrlCnnParams* p, const NrlCnnGrads* g, float* d_emb_table, int64_t vocab, const int64_t* ids,

@@ -3,6 +3,7 @@
 //   npa_query_grad        segmented sum of the per-row query gradients onto the users' query rows (no float atomics)
 //   nrl_npa_user_queries  every per-user query: user embedding -> dropout -> (Linear -> ReLU -> dropout -> Linear -> tanh)
 //   nrl_personalized_user_attention  the user encoder (user/npa.py) over the ragged history, zero-padded to max_hist
+//   nrl_npa_cached_scores  eval-mode scores of whole impressions from the cached conv features (encode-once evaluation)
 #include <math.h>
 
 #include "nrl_kernels.h"
@@ -498,6 +499,203 @@ __global__ __launch_bounds__(NPA_THREADS) void npa_user_att_bwd_kernel(const flo
   }
 }
 
+// ---- encode-once evaluation: scores from the cached conv features ----------------------------------------------------------
+// table (num_news, L, F) holds c = relu(conv(E[ids]) + b) of every news (nrl_npa_conv_features).  A WAVE pools one news row at a
+// time: the F columns as float4 chunks over its lanes (CH per lane), an online softmax over all L tokens with the next token's
+// loads issued before the current one is used.  Each table row is read once; every sum has a fixed order (no atomics).
+constexpr int NPA_USER_WAVES = 8;     // 50 history rows over 8 waves; 2 workgroups of <= 33 KB LDS per CU keep 16 waves loading
+
+// feat: the (L, F) feature map of the news, or null (index outside the table: an all-zero map, which pools to zero)
+template <int CH>
+__device__ __forceinline__ void npa_cached_pool(const float* __restrict__ feat, const float4 (&q)[CH], int L, int F, int lane,
+                                                float4 (&out)[CH]) {
+  const int F4 = F >> 2;
+#pragma unroll
+  for (int k = 0; k < CH; ++k) out[k] = make_float4(0.f, 0.f, 0.f, 0.f);
+  if (feat == nullptr) return;
+  float4 cur[CH], nxt[CH];
+#pragma unroll
+  for (int k = 0; k < CH; ++k) {
+    const int j = lane + 64 * k;
+    cur[k] = j < F4 ? reinterpret_cast<const float4*>(feat)[j] : make_float4(0.f, 0.f, 0.f, 0.f);
+    nxt[k] = cur[k];
+  }
+  float m = -INFINITY, l = 0.f;
+  for (int t = 0; t < L; ++t) {
+    if (t + 1 < L) {
+      const float4* row = reinterpret_cast<const float4*>(feat + (int64_t)(t + 1) * F);
+#pragma unroll
+      for (int k = 0; k < CH; ++k) {
+        const int j = lane + 64 * k;
+        nxt[k] = j < F4 ? row[j] : make_float4(0.f, 0.f, 0.f, 0.f);
+      }
+    }
+    float part = 0.f;
+#pragma unroll
+    for (int k = 0; k < CH; ++k) part += q[k].x * cur[k].x + q[k].y * cur[k].y + q[k].z * cur[k].z + q[k].w * cur[k].w;
+    const float s = wave_sum(part);
+    const float m_new = fmaxf(m, s);
+    const float a = __expf(m - m_new), p = __expf(s - m_new);
+    l = l * a + p;
+#pragma unroll
+    for (int k = 0; k < CH; ++k) {
+      out[k].x = out[k].x * a + p * cur[k].x;
+      out[k].y = out[k].y * a + p * cur[k].y;
+      out[k].z = out[k].z * a + p * cur[k].z;
+      out[k].w = out[k].w * a + p * cur[k].w;
+      cur[k] = nxt[k];
+    }
+    m = m_new;
+  }
+  const float inv = 1.f / l;
+#pragma unroll
+  for (int k = 0; k < CH; ++k) { out[k].x *= inv; out[k].y *= inv; out[k].z *= inv; out[k].w *= inv; }
+}
+
+struct NpaCachedArgs {
+  const float* table;
+  int64_t num_news;
+  const int64_t *hist_idx, *hist_off, *cand_idx, *cand_off;
+  int64_t n_hist, n_cand, B;
+  const float *q_hist, *q_cand, *q_news;   // q_news null: late fusion
+  int L, F, max_hist, max_cand;
+  float* user;     // (B, F)
+  float* scores;   // (B, max_cand)
+};
+
+__device__ __forceinline__ int64_t npa_clamp(int64_t v, int64_t lo, int64_t hi) { return v < lo ? lo : (v > hi ? hi : v); }
+
+template <int CH>
+__device__ __forceinline__ void npa_load_q(const float* __restrict__ q, int F, int lane, float4 (&out)[CH]) {
+#pragma unroll
+  for (int k = 0; k < CH; ++k) {
+    const int j = lane + 64 * k;
+    out[k] = j < (F >> 2) ? reinterpret_cast<const float4*>(q)[j] : make_float4(0.f, 0.f, 0.f, 0.f);
+  }
+}
+
+// User vectors: one workgroup per impression b.  Wave w pools history rows w, w + 8, ... with q_hist[b] and folds each pooled
+// row v_i into its own online state of the history attention (s_i = q_news[b] . v_i; running max, sum, weighted sum), or into a
+// plain sum under late fusion.  The eight states meet in LDS; the softmax also counts max_hist - n_b virtual zero rows of
+// score 0 (the to_dense_batch rows of the reference).  No (n_hist, F) intermediate leaves the chip.  The workgroup also clears
+// the padded score slots of its impression.
+template <int CH>
+__global__ __launch_bounds__(64 * NPA_USER_WAVES) void npa_cached_user_kernel(NpaCachedArgs a) {
+  extern __shared__ float sm[];                 // m[8] | l[8] | acc[8][F]
+  float* m_w = sm;
+  float* l_w = sm + NPA_USER_WAVES;
+  float* acc_w = l_w + NPA_USER_WAVES;
+  const int64_t b = blockIdx.x;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int F = a.F, F4 = F >> 2;
+  const int64_t r0 = npa_clamp(a.hist_off[b], 0, a.n_hist);
+  const int64_t nr = npa_clamp(a.hist_off[b + 1], r0, a.n_hist) - r0;
+  const int n = (int)(nr < a.max_hist ? nr : a.max_hist);
+  const bool early = a.q_news != nullptr;
+  float4 q[CH], qn[CH], acc[CH], v[CH];
+  npa_load_q<CH>(a.q_hist + b * F, F, lane, q);
+  if (early) npa_load_q<CH>(a.q_news + b * F, F, lane, qn);
+#pragma unroll
+  for (int k = 0; k < CH; ++k) acc[k] = make_float4(0.f, 0.f, 0.f, 0.f);
+  float m = -INFINITY, l = 0.f;
+  for (int i = wave; i < n; i += NPA_USER_WAVES) {
+    const int64_t idx = a.hist_idx[r0 + i];
+    const float* feat = (idx >= 0 && idx < a.num_news) ? a.table + idx * (int64_t)a.L * F : nullptr;
+    npa_cached_pool<CH>(feat, q, a.L, F, lane, v);
+    float wgt = 1.f, keep = 1.f;
+    if (early) {
+      float part = 0.f;
+#pragma unroll
+      for (int k = 0; k < CH; ++k) part += qn[k].x * v[k].x + qn[k].y * v[k].y + qn[k].z * v[k].z + qn[k].w * v[k].w;
+      const float s = wave_sum(part);
+      const float m_new = fmaxf(m, s);
+      keep = expf(m - m_new);
+      wgt = expf(s - m_new);
+      m = m_new;
+    }
+    l = l * keep + wgt;
+#pragma unroll
+    for (int k = 0; k < CH; ++k) {
+      acc[k].x = acc[k].x * keep + wgt * v[k].x;
+      acc[k].y = acc[k].y * keep + wgt * v[k].y;
+      acc[k].z = acc[k].z * keep + wgt * v[k].z;
+      acc[k].w = acc[k].w * keep + wgt * v[k].w;
+    }
+  }
+  if (lane == 0) { m_w[wave] = m; l_w[wave] = l; }
+#pragma unroll
+  for (int k = 0; k < CH; ++k) {
+    const int j = lane + 64 * k;
+    if (j < F4) reinterpret_cast<float4*>(acc_w + wave * F)[j] = acc[k];
+  }
+  __syncthreads();
+  float sc[NPA_USER_WAVES], den = 0.f;
+  if (early) {
+    const int pad = a.max_hist - n;
+    float mx = pad > 0 ? 0.f : -INFINITY;
+#pragma unroll
+    for (int i = 0; i < NPA_USER_WAVES; ++i) mx = fmaxf(mx, m_w[i]);
+#pragma unroll
+    for (int i = 0; i < NPA_USER_WAVES; ++i) { sc[i] = l_w[i] > 0.f ? expf(m_w[i] - mx) : 0.f; den += sc[i] * l_w[i]; }
+    if (pad > 0) den += pad * expf(-mx);
+  } else {
+#pragma unroll
+    for (int i = 0; i < NPA_USER_WAVES; ++i) { sc[i] = l_w[i] > 0.f ? 1.f : 0.f; den += l_w[i]; }   // den = n_b: the mean
+  }
+  const float inv = den > 0.f ? 1.f / den : 0.f;
+  for (int f = threadIdx.x; f < F; f += 64 * NPA_USER_WAVES) {
+    float r = 0.f;
+#pragma unroll
+    for (int i = 0; i < NPA_USER_WAVES; ++i) r += sc[i] * acc_w[i * F + f];
+    a.user[b * F + f] = r * inv;
+  }
+  const int64_t c0 = npa_clamp(a.cand_off[b], 0, a.n_cand);
+  const int64_t nc = npa_clamp(a.cand_off[b + 1], c0, a.n_cand) - c0;
+  for (int64_t j = nc + threadIdx.x; j < a.max_cand; j += 64 * NPA_USER_WAVES) a.scores[b * a.max_cand + j] = 0.f;
+}
+
+// Candidate scores: the waves of the grid spread flat over ALL candidate rows of the batch (a 300-candidate impression is 300
+// waves, not one workgroup's tail).  Wave r finds its impression by bisection of cand_off, pools its row with q_cand[b] and dots
+// it with user[b].
+template <int CH>
+__global__ __launch_bounds__(NPA_THREADS) void npa_cached_cand_kernel(NpaCachedArgs a) {
+  const int lane = threadIdx.x & 63;
+  const int64_t r = (int64_t)blockIdx.x * NPA_WAVES + (threadIdx.x >> 6);
+  if (r >= a.n_cand) return;
+  int64_t lo = 0, hi = a.B;                     // the last b with cand_off[b] <= r
+  while (hi - lo > 1) {
+    const int64_t mid = (lo + hi) >> 1;
+    if (a.cand_off[mid] <= r) lo = mid; else hi = mid;
+  }
+  const int64_t b = lo;
+  const int64_t j = r - a.cand_off[b];
+  if (j < 0 || j >= a.max_cand || r >= a.cand_off[b + 1]) return;
+  const int F = a.F;
+  float4 q[CH], u[CH], v[CH];
+  npa_load_q<CH>(a.q_cand + b * F, F, lane, q);
+  const int64_t idx = a.cand_idx[r];
+  const float* feat = (idx >= 0 && idx < a.num_news) ? a.table + idx * (int64_t)a.L * F : nullptr;
+  npa_cached_pool<CH>(feat, q, a.L, F, lane, v);
+  npa_load_q<CH>(a.user + b * F, F, lane, u);
+  float part = 0.f;
+#pragma unroll
+  for (int k = 0; k < CH; ++k) part += u[k].x * v[k].x + u[k].y * v[k].y + u[k].z * v[k].z + u[k].w * v[k].w;
+  const float s = wave_sum(part);
+  if (lane == 0) a.scores[b * a.max_cand + j] = s;
+}
+
+template <int CH>
+static int npa_cached_launch(const NpaCachedArgs& a, hipStream_t st) {
+  const size_t lds = (size_t)(2 * NPA_USER_WAVES + NPA_USER_WAVES * a.F) * sizeof(float);
+  hipLaunchKernelGGL(npa_cached_user_kernel<CH>, dim3((unsigned)a.B), dim3(64 * NPA_USER_WAVES), lds, st, a);
+  NRL_LAUNCH_CHECK();
+  if (a.n_cand > 0) {
+    hipLaunchKernelGGL(npa_cached_cand_kernel<CH>, dim3((unsigned)ceil_div(a.n_cand, NPA_WAVES)), dim3(NPA_THREADS), 0, st, a);
+    NRL_LAUNCH_CHECK();
+  }
+  return NRL_OK;
+}
+
 static int npa_query_args(const NrlNpaQueryParams* p, const int64_t* user_idx, int64_t B, double p_drop, uint64_t seed,
                           uint32_t stream0, NpaQueryArgs* a, int* nheads) {
   NRL_REQUIRE(p != nullptr && p->user_table && p->text_proj_weight && p->text_proj_bias && p->text_att_weight &&
@@ -602,6 +800,38 @@ int nrl_npa_user_queries_bwd(const NrlNpaQueryParams* p, const NrlNpaQueryGrads*
   hipLaunchKernelGGL(npa_user_table_grad_kernel, dim3((unsigned)batch), dim3(64), 0, st, a, nheads, w, g->user_table);
   NRL_LAUNCH_CHECK();
   return NRL_OK;
+}
+
+int nrl_npa_cached_scores(const float* table, int64_t num_news, int32_t seq_len, int32_t num_filters, const int64_t* hist_idx,
+                          int64_t n_hist, const int64_t* hist_offsets, const int64_t* cand_idx, int64_t n_cand,
+                          const int64_t* cand_offsets, int64_t batch, const float* q_hist, const float* q_cand,
+                          const float* q_news, int32_t max_hist, int32_t max_cand, float* user_vectors, float* scores,
+                          void* stream) {
+  NRL_REQUIRE(table && hist_offsets && cand_offsets && q_hist && q_cand && user_vectors && scores,
+              "npa_cached_scores: null argument");
+  NRL_REQUIRE((hist_idx || n_hist == 0) && (cand_idx || n_cand == 0), "npa_cached_scores: null index list");
+  NRL_REQUIRE(num_news >= 0 && seq_len > 0 && n_hist >= 0 && n_cand >= 0 && batch >= 0 && max_hist >= 0 && max_cand >= 0,
+              "npa_cached_scores: bad dimensions");
+  NRL_REQUIRE(num_filters > 0 && num_filters % 4 == 0 && npa_ch(num_filters) <= NPA_MAX_CH,
+              "npa_cached_scores: num_filters must be a multiple of 4, <= 1024");
+  NRL_REQUIRE((((uintptr_t)table | (uintptr_t)q_hist | (uintptr_t)q_cand | (uintptr_t)q_news | (uintptr_t)user_vectors) & 15) == 0,
+              "npa_cached_scores: table, queries and user vectors must be 16-byte aligned");
+  NRL_REQUIRE(batch < (1LL << 31) && ceil_div(n_cand, NPA_WAVES) < (1LL << 31), "npa_cached_scores: batch too large");
+  if (batch == 0) return NRL_OK;
+  NpaCachedArgs a;
+  a.table = table; a.num_news = num_news;
+  a.hist_idx = hist_idx; a.hist_off = hist_offsets; a.cand_idx = cand_idx; a.cand_off = cand_offsets;
+  a.n_hist = n_hist; a.n_cand = n_cand; a.B = batch;
+  a.q_hist = q_hist; a.q_cand = q_cand; a.q_news = q_news;
+  a.L = seq_len; a.F = num_filters; a.max_hist = max_hist; a.max_cand = max_cand;
+  a.user = user_vectors; a.scores = scores;
+  hipStream_t st = (hipStream_t)stream;
+  switch (npa_ch(num_filters)) {
+    case 1: return npa_cached_launch<1>(a, st);
+    case 2: return npa_cached_launch<2>(a, st);
+    case 3: return npa_cached_launch<3>(a, st);
+    default: return npa_cached_launch<4>(a, st);
+  }
 }
 
 int nrl_personalized_user_attention_fwd(const float* hist, const int64_t* hist_offsets, int64_t batch, int32_t max_hist,

@@ -15,6 +15,9 @@ pandas ``.loc`` + per-row ``F.pad`` on the host.  Here
   (``score_news_vectors``).  The seq-first user-attention quirk still couples the users of a batch, exactly
   as in the uncached forward, so scores match the uncached path for the same batch composition.
 
+* ``NpaFeatureCache`` is the NPA form: its news vectors depend on the user, so it caches the conv feature maps (the part that
+  does not) and scores from them with ``nrl_npa_cached_scores``.
+
 Everything runs through the same C-ABI kernels; nothing here is a second implementation of the model.
 """
 from __future__ import annotations
@@ -93,7 +96,8 @@ class NewsVectorCache:
         """news vectors (num_news, D) of the whole table, in chunks (the encoder workspace is O(rows))."""
         if getattr(self.module, "user_dependent_news_vectors", False):
             raise NotImplementedError("this recommender's news vectors depend on the user (NPA's personalized attention, "
-                                      "text.py:385-390): they cannot be cached; evaluate with the module's own forward")
+                                      "text.py:385-390): they cannot be cached; NpaFeatureCache caches what does not "
+                                      "(the conv feature maps) and scores from it")
         enc = self.module.news_encoder
         text_encoders = list((getattr(enc, "text_encoders", {}) or {}).values())
         # (a PLM text encoder with the CLS head -- use_mhsa == False, MINER -- encodes every news on its own and says so)
@@ -230,6 +234,91 @@ class MannerVectorCache:
             return self.table.attrs[name].index_select(0, idx.to(dev)) if name in self.table.attrs else empty
 
         return (scores.new_zeros(()), preds, meta["labels"], meta["cand_sizes"], meta["hist_sizes"], attr(cand_idx, "category"),
+                attr(cand_idx, "sentiment"), attr(hist_idx, "category"), attr(hist_idx, "sentiment"), meta["user_ids"],
+                cand_idx.to(dev))
+
+
+class NpaFeatureCache:
+    """Encode-once evaluation of ``npa_module.NPAModule``.  An NPA news vector depends on the user, but in eval mode only through the
+    pooling: the conv feature maps ``c = relu(cnn(embedding(title)))`` (L, F) depend on the news alone.  ``build`` runs the lookup and
+    the convolution over the table once into ``features`` (num_news, L, F) fp32 (65 k news x 30 x 400: 3.1 GB); ``scores`` is the
+    per-user queries (``NpaUserQueriesFn`` at p = 0, as the forward) plus ``nrl_npa_cached_scores``, which pools the history and
+    candidate maps straight from the table with each user's queries, attends over the pooled history (counting the zero rows up to
+    the batch's longest history, as the forward) and takes the dot products.
+
+    A SNAPSHOT of the weights at ``build()``: after they change, call ``build()`` again (nothing is keyed on them).  The feature maps
+    carry the bits of the GEMM engine they were built under (``engine``); the scorer itself is engine-independent.
+    ``hist_sizes`` / ``cand_sizes`` are HOST tensors, as ``evaluate_impressions`` builds them: their maxima are read on the host."""
+
+    def __init__(self, module, table: DeviceNewsTable, chunk: int = 16384):
+        from .npa_module import NPAModule
+        if not isinstance(module, NPAModule):
+            raise TypeError(f"NpaFeatureCache caches the conv feature maps of an NPAModule, got {type(module).__name__}; "
+                            "every other recommender is served by NewsVectorCache")
+        self.module, self.table, self.chunk = module, table, int(chunk)
+        self.features: Optional[torch.Tensor] = None
+        self.engine: Optional[str] = None
+
+    _meta = NewsVectorCache._meta
+
+    @torch.no_grad()
+    def build(self) -> torch.Tensor:
+        """conv feature maps (num_news, L, F) of the whole table: one allocation, filled chunk by chunk in place."""
+        from . import _lib
+        enc = self.module.news_encoder
+        title = self.table.attrs["title"]
+        was_training = self.module.training
+        self.module.eval()
+        try:
+            feats = torch.empty((self.table.num_news, title.shape[1], enc.cnn.out_channels), dtype=torch.float32,
+                                device=self.table.device)
+            for lo in range(0, self.table.num_news, self.chunk):
+                hi = min(lo + self.chunk, self.table.num_news)
+                enc.conv_features(title[lo:hi], out=feats[lo:hi])
+        finally:
+            self.module.train(was_training)
+        self.features, self.engine = feats, _lib.get_gemm_engine()
+        return feats
+
+    @torch.no_grad()
+    def scores(self, hist_idx: torch.Tensor, hist_sizes: torch.Tensor, cand_idx: torch.Tensor, cand_sizes: torch.Tensor,
+               user_idx: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """(B, max_cand) click scores of a batch of impressions given by news-index lists; ``user_idx`` (B) is required."""
+        from .ops_npa import npa_cached_scores
+        if user_idx is None:
+            raise ValueError("NpaFeatureCache.scores needs user_idx: NPA's attention queries come from the user embedding")
+        if self.features is None:
+            self.build()
+        dev = self.table.device
+        max_hist = int(hist_sizes.max()) if hist_sizes.numel() else 0      # host tensors: no read-back
+        max_cand = int(cand_sizes.max()) if cand_sizes.numel() else 0
+        zero = torch.zeros(1, dtype=torch.int64, device=dev)
+        hist_off = torch.cat([zero, torch.cumsum(hist_sizes.to(dev).long(), 0)])
+        cand_off = torch.cat([zero, torch.cumsum(cand_sizes.to(dev).long(), 0)])
+        B = int(hist_sizes.numel())
+        text_q, q_news = self.module.user_queries(user_idx.to(dev).long())      # p = 0: the forward's eval-mode queries
+        q_hist, q_cand = text_q[:B], text_q[B:]
+        return npa_cached_scores(self.features, hist_idx.to(dev).long(), hist_off, cand_idx.to(dev).long(), cand_off, q_hist,
+                                 q_cand, q_news, max_hist, max_cand)
+
+    @torch.no_grad()
+    def model_step(self, hist_idx, hist_sizes, cand_idx, cand_sizes, labels, user_idx=None, user_ids=None):
+        """The 11-tuple of ``NewsVectorCache.model_step`` (loss from ``module._loss``), so ``evaluate_impressions`` applies."""
+        if user_idx is None:
+            raise ValueError("NpaFeatureCache.model_step needs user_idx: NPA's attention queries come from the user embedding")
+        dev = self.table.device
+        scores = self.scores(hist_idx, hist_sizes, cand_idx, cand_sizes, user_idx)
+        meta = self._meta(hist_sizes, cand_sizes, labels, user_idx, user_ids)
+        y_true = dense_rows(meta["labels"], meta["batch_cand"], meta["batch_size"], meta["max_cand"], meta["cand_offsets"],
+                            meta["cand_flat_idx"])
+        loss = self.module._loss(scores, y_true.float(), meta)
+        preds = scores.reshape(-1)[meta["cand_flat_idx"]]
+        empty = torch.empty(0, dtype=torch.int64, device=dev)
+
+        def attr(idx, name):
+            return self.table.attrs[name].index_select(0, idx.to(dev)) if name in self.table.attrs else empty
+
+        return (loss, preds, meta["labels"], meta["cand_sizes"], meta["hist_sizes"], attr(cand_idx, "category"),
                 attr(cand_idx, "sentiment"), attr(hist_idx, "category"), attr(hist_idx, "sentiment"), meta["user_ids"],
                 cand_idx.to(dev))
 

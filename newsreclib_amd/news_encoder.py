@@ -281,6 +281,14 @@ class CNNPersAtt(nn.Module):
         return ops_npa.NpaEncoderFn.apply(text, emb, w_c, self.cnn.bias, queries, owner, offsets, p, seed or 0, stream0,
                                           bufs if any(b is not None for b in bufs) else None, order)
 
+    @torch.no_grad()
+    def conv_features(self, text: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """text (N, L) -> the eval-mode conv feature maps ``relu(cnn(embedding(text)))`` (N, L, F): everything of this encoder
+        that depends on the news alone (no dropout, whatever ``self.training`` says).  ``out``: an (N, L, F) buffer to fill,
+        e.g. a slice of the table ``evaluation.NpaFeatureCache`` keeps."""
+        from . import ops_npa
+        return ops_npa.npa_conv_features(text, self.embedding_layer.weight, self.cnn.weight, self.cnn.bias, out=out)
+
 
 class KCNN(nn.Module):
     """DKN's knowledge-aware CNN (reference news.py:186-299) as one HIP pipeline (``nrl_dkn_encoder_fwd``/``_bwd``): word,

@@ -7,8 +7,11 @@ Same 22 constructor keyword arguments (npa_module.py:77-100), sub-module attribu
 ``user_encoder`` (NPA ``UserEncoder``, early fusion only), ``click_predictor`` (``DotProduct``).
 
 A news vector depends on the user it is encoded for (the text query is personalized), so there is no
-``score_news_vectors`` and ``evaluation.NewsVectorCache`` refuses this module: the forward under ``torch.no_grad()`` is
-its evaluation path.  Differences from the reference: history and candidate rows are encoded in one call (their two text
+``score_news_vectors`` and ``evaluation.NewsVectorCache`` refuses this module.  In eval mode only the pooling is
+personalized, though: the conv feature maps ``relu(cnn(embedding(title)))`` depend on the news alone, and
+``evaluation.NpaFeatureCache`` (``feature_cache(table)``) keeps them for the whole corpus and scores impressions from them
+with one fused kernel pair -- the encode-once evaluation path.  The forward under ``torch.no_grad()`` computes the same
+scores from token ids.  Differences from the reference: history and candidate rows are encoded in one call (their two text
 queries keep two dropout draws); at batch size 1 the reference's ``.squeeze()`` (attention.py:257) drops the batch axis and
 its ``bmm`` fails, while this module returns the (1, C) scores."""
 from __future__ import annotations
@@ -28,7 +31,7 @@ from .user_encoder_npa import UserEncoder
 
 
 class NPAModule(AbstractRecommender):
-    user_dependent_news_vectors = True       # (evaluation.NewsVectorCache refuses to cache them)
+    user_dependent_news_vectors = True       # (evaluation.NewsVectorCache refuses to cache them: NpaFeatureCache)
 
     def __init__(
         self,
@@ -78,8 +81,27 @@ class NPAModule(AbstractRecommender):
         self.click_predictor = DotProduct()
         self._init_step_outputs(outputs)
 
+    def feature_cache(self, table, chunk: int = 16384):
+        """The encode-once evaluation cache of this module over a ``evaluation.DeviceNewsTable`` (a snapshot of the present
+        weights: call its ``build()`` again after they change)."""
+        from .evaluation import NpaFeatureCache
+        return NpaFeatureCache(self, table, chunk)
+
     def _prepare(self, batch: Dict) -> Dict:
         return prepare_batch(batch, self.news_encoder.embedding_layer.weight.shape[0])
+
+    def user_queries(self, user_idx: torch.Tensor, p: float = 0.0, seed: Optional[int] = None):
+        """Projected users (once), the text query of both encoder calls and the user encoder's news query in one launch:
+        -> (text queries (2B, F): rows [history; candidates], news queries (B, F) or None under late fusion)."""
+        enc = self.news_encoder
+        news_head = None if self.hparams.late_fusion else query_head(self.user_encoder.news_query_projection,
+                                                                      self.user_encoder.personalized_attention)
+        params = (self.user_projection.user_embed,) + query_head(enc.text_query_projection, enc.personalized_attention) \
+            + (news_head or (None,) * 4)
+        bufs = tuple(getattr(t, "main_grad", None) if t is not None else None for t in params)
+        queries = ops_npa.NpaUserQueriesFn.apply(user_idx, *params, p, seed or 0, ops_npa.QUERY_STREAM0,
+                                                 bufs if any(b is not None for b in bufs) else None)
+        return (queries, None) if news_head is None else queries
 
     # -- reference: npa_module.py:208-252 -------------------------------------------------------------
     def forward(self, batch: Dict, seed: Optional[int] = None) -> torch.Tensor:
@@ -89,15 +111,7 @@ class NPAModule(AbstractRecommender):
             seed = _draw_seed()                       # one draw per step; streams separate the dropouts
         p = float(self.news_encoder.dropout.p) if self.training else 0.0
         enc = self.news_encoder
-        # projected users (once), the text query of both encoder calls and the user encoder's news query: one launch
-        news_head = None if self.hparams.late_fusion else query_head(self.user_encoder.news_query_projection,
-                                                                      self.user_encoder.personalized_attention)
-        params = (self.user_projection.user_embed,) + query_head(enc.text_query_projection, enc.personalized_attention) \
-            + (news_head or (None,) * 4)
-        bufs = tuple(getattr(t, "main_grad", None) if t is not None else None for t in params)
-        queries = ops_npa.NpaUserQueriesFn.apply(batch["user_idx"], *params, p, seed or 0, ops_npa.QUERY_STREAM0,
-                                                 bufs if any(b is not None for b in bufs) else None)
-        text_q, news_q = (queries, None) if news_head is None else queries
+        text_q, news_q = self.user_queries(batch["user_idx"], p, seed)
         # history rows attend with query row batch_hist[n], candidate rows with B + batch_cand[n]
         n_hist = batch["batch_hist"].shape[0]
         owner = torch.cat([batch["batch_hist"], batch["batch_cand"] + B]).to(torch.int32)

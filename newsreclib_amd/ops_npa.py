@@ -192,3 +192,80 @@ class PersonalizedUserAttentionFn(GradAwareFunction):
                                                            d_q.data_ptr(), _stream()),
                    "nrl_personalized_user_attention_bwd")
         return d_hist, None, None, d_q
+
+
+MAX_FILTERS = 1024      # the pooling kernels keep a row's F columns as float4 chunks over one wave: F % 4 == 0, F <= 1024
+
+
+def _conv_weight_image(w_c: torch.Tensor) -> torch.Tensor:
+    """``nn.Conv1d.weight`` (F, D, W) or the kernels' (F, 1, W, D) image -> the (F, 1, W, D) image."""
+    if w_c.dim() == 3:
+        return w_c.permute(0, 2, 1).contiguous().unsqueeze(1)
+    return w_c
+
+
+@torch.no_grad()
+def npa_conv_features(ids: torch.Tensor, emb: torch.Tensor, w_c: torch.Tensor, b_c: torch.Tensor,
+                      out: torch.Tensor = None) -> torch.Tensor:
+    """The eval-mode conv feature maps ``relu(conv1d(emb[ids]) + b)`` of ``CNNPersAtt`` (text.py:377-383, dropout off):
+    ids (N, L) -> (N, L, F) fp32, the same lookup and convolution launches as ``NpaEncoderFn`` under the current engine.
+    ``out``: a contiguous (N, L, F) buffer to fill (a slice of a preallocated table), else one is allocated."""
+    lib = _lib.load()
+    ids = _chk(ids, torch.int64, "ids")
+    emb, w_c, b_c = [_chk(t, torch.float32, n) for t, n in zip((emb, _conv_weight_image(w_c), b_c),
+                                                              ("embedding", "cnn.weight", "cnn.bias"))]
+    if ids.dim() != 2:
+        raise ValueError("newsreclib_amd: token ids must be (num_news, num_tokens)")
+    N, L = ids.shape
+    V, D = emb.shape
+    if w_c.dim() != 4 or w_c.shape[1] != 1 or w_c.shape[3] != D:
+        raise ValueError("newsreclib_amd: cnn.weight must be (num_filters, 1, window, embed_dim)")
+    F_, _, W, _ = w_c.shape
+    if b_c.shape != (F_,):
+        raise ValueError("newsreclib_amd: inconsistent NPA encoder shapes")
+    if out is None:
+        out = torch.empty((N, L, F_), dtype=torch.float32, device=ids.device)
+    else:
+        if not out.is_cuda or out.dtype != torch.float32 or out.shape != (N, L, F_) or not out.is_contiguous():
+            raise ValueError(f"newsreclib_amd: `out` must be a contiguous float32 GPU tensor of shape {(N, L, F_)}")
+    cp = NrlCnnParams(w_c.data_ptr(), b_c.data_ptr(), None, None, None, D, F_, W, 16)
+    ws = torch.empty(max(lib.nrl_npa_conv_features_workspace_bytes(N, L, D, F_, W), 256), dtype=torch.uint8,
+                     device=ids.device)
+    _lib.check(lib.nrl_npa_conv_features(ctypes.byref(cp), emb.data_ptr(), V, ids.data_ptr(), N, L, out.data_ptr(),
+                                         ws.data_ptr(), ws.numel(), _stream()), "nrl_npa_conv_features")
+    return out
+
+
+@torch.no_grad()
+def npa_cached_scores(table: torch.Tensor, hist_idx: torch.Tensor, hist_offsets: torch.Tensor, cand_idx: torch.Tensor,
+                      cand_offsets: torch.Tensor, q_hist: torch.Tensor, q_cand: torch.Tensor, q_news, max_hist: int,
+                      max_cand: int, return_user_vectors: bool = False):
+    """``NPAModule.forward`` in eval mode from the cached feature table (num_news, L, F) of ``npa_conv_features``:
+    hist_idx / cand_idx flat int64 table rows, hist_offsets / cand_offsets (B + 1) int64, q_hist / q_cand (B, F) the tanh'd
+    text queries, q_news (B, F) the news query or None (late fusion), max_hist / max_cand the batch maxima (plain ints).
+    -> scores (B, max_cand), 0 at padded slots [, user vectors (B, F)].  An index outside the table reads as an all-zero
+    feature map."""
+    lib = _lib.load()
+    table = _chk(table, torch.float32, "feature table")
+    hist_idx, cand_idx = _chk(hist_idx, torch.int64, "hist_idx"), _chk(cand_idx, torch.int64, "cand_idx")
+    hist_offsets, cand_offsets = _chk(hist_offsets, torch.int64, "hist_offsets"), _chk(cand_offsets, torch.int64, "cand_offsets")
+    q_hist, q_cand = _chk(q_hist, torch.float32, "q_hist"), _chk(q_cand, torch.float32, "q_cand")
+    if q_news is not None:
+        q_news = _chk(q_news, torch.float32, "q_news")
+    if table.dim() != 3:
+        raise ValueError("newsreclib_amd: the feature table must be (num_news, num_tokens, num_filters)")
+    V, L, F_ = table.shape
+    if F_ % 4 or not 4 <= F_ <= MAX_FILTERS:
+        raise ValueError(f"newsreclib_amd: num_filters must be a multiple of 4 up to {MAX_FILTERS}, got {F_}")
+    B = int(hist_offsets.numel()) - 1
+    if B < 0 or hist_idx.dim() != 1 or cand_idx.dim() != 1 or cand_offsets.shape != (B + 1,) or q_hist.shape != (B, F_) or \
+            q_cand.shape != (B, F_) or (q_news is not None and q_news.shape != (B, F_)) or int(max_hist) < 0 or int(max_cand) < 0:
+        raise ValueError("newsreclib_amd: inconsistent cached-score shapes")
+    scores = torch.empty((B, int(max_cand)), dtype=torch.float32, device=table.device)
+    user = torch.empty((B, F_), dtype=torch.float32, device=table.device)
+    _lib.check(lib.nrl_npa_cached_scores(table.data_ptr(), V, L, F_, hist_idx.data_ptr(), hist_idx.numel(),
+                                         hist_offsets.data_ptr(), cand_idx.data_ptr(), cand_idx.numel(),
+                                         cand_offsets.data_ptr(), B, q_hist.data_ptr(), q_cand.data_ptr(),
+                                         q_news.data_ptr() if q_news is not None else None, int(max_hist), int(max_cand),
+                                         user.data_ptr(), scores.data_ptr(), _stream()), "nrl_npa_cached_scores")
+    return (scores, user) if return_user_vectors else scores
