@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define NRL_ABI_VERSION 18
+#define NRL_ABI_VERSION 19
 
 #define NRL_OK 0
 #define NRL_E_INVALID (-1)   /* bad argument (shape / alignment / null) */
@@ -970,6 +970,42 @@ int nrl_supcon_embed_fwd_bwd(const float* E, const int64_t* labels, int64_t N, i
 int nrl_manner_scores(const float* const* tables, const float* weights, int32_t k, int64_t V, const int64_t* hist_idx,
                       const int64_t* hist_offsets, const int64_t* cand_idx, const int64_t* cand_offsets, int64_t B,
                       int32_t max_cand, int32_t D, float* out, void* stream);
+
+/* ---- streaming evaluation metrics (ABI v19).  Replaces: the torchmetrics objects wired at nrms_module.py:182-195 and computed at
+ * :456-493 (RetrievalMRR, RetrievalNormalizedDCG, Diversity, Personalization -- the AUROC stays a global sort on the host side),
+ * metrics/functional.py:8-127 (diversity, personalization, generalized_jaccard) and the per-query grouping with
+ * empty_target_action="neg" of metrics/base.py:137-182.
+ * nrl_impression_metrics: one batch of B ragged impressions.  preds / targets: N fp32, cand_offsets: (B + 1) int64.  n_aspects in
+ *   {0, 1, 2}; aspect a has cand_aspects_a (N int64), hist_aspects_a (n_hist int64) and num_classes_a in [2, 1024]; hist_offsets
+ *   (B + 1) int64 is shared by the aspects (all four may be null when n_aspects == 0).  top_k: n_k <= 4 values in [1, 1024], a HOST
+ *   array read during the call.
+ *   rank (N int32, nullable): 0-based position of every candidate in its impression's ranking, score descending, ties by ascending
+ *     position (a stable descending sort; NaN sorts first, -0 == +0).  Candidates of a flagged impression get -1.
+ *   rows (B, n_cols fp32, nullable), n_cols = 1 + n_k + 2 * n_k * n_aspects: rr | ndcg@k ... | per aspect: div@k ... then pers@k ...
+ *     rr = 1 / (1 + rank of the best-ranked candidate with target > 0), 0 without one; ndcg: gain = target, discount
+ *     1 / log2(pos + 2), ideal = the k largest targets, 0 when the ideal is 0, k > C uses all C; div = entropy of the aspect
+ *     distribution of the top k / log(num_classes); pers = sum(min) / sum(max) of the top-k aspect counts against the history
+ *     aspect counts; both 0 when every candidate aspect id of the impression is 0; pers = 0 for an empty history.
+ *   sums (n_cols doubles) and count (one int64), nullable together: this call ADDS the column sums of its rows and the number of
+ *     unflagged impressions.  The rows are reduced in a fixed order (a tree inside fixed 4096-row parts, a tree over the parts,
+ *     one plain add per column): no floating-point atomics, the same inputs give the same bits.
+ *   status (one int32, required): the kernel ORs NRL_METRICS_E_* into it.  A flagged impression writes zero rows, contributes
+ *     nothing to sums / count, and is never indexed outside the buffers.
+ *   Workspace: nrl_impression_metrics_workspace_bytes, 256-byte aligned.  B == 0 returns success without a launch.  Sizes beyond
+ *   the limits above return NRL_E_INVALID.  No host synchronisation. */
+#define NRL_METRICS_MAX_CAND 4096
+#define NRL_METRICS_MAX_CLASSES 1024
+#define NRL_METRICS_MAX_K 1024
+#define NRL_METRICS_MAX_NK 4
+#define NRL_METRICS_E_TOO_LONG 1 /* an impression has more than NRL_METRICS_MAX_CAND candidates */
+#define NRL_METRICS_E_ASPECT 2   /* an aspect id is negative or >= num_classes */
+#define NRL_METRICS_E_OFFSETS 4  /* an offset vector decreases or leaves [0, N] / [0, n_hist] */
+size_t nrl_impression_metrics_workspace_bytes(int64_t N, int64_t B, int32_t n_aspects, int32_t n_k);
+int nrl_impression_metrics(const float* preds, const float* targets, const int64_t* cand_offsets, int64_t N, int64_t B,
+                           int32_t n_aspects, const int64_t* cand_aspects0, const int64_t* hist_aspects0, int32_t num_classes0,
+                           const int64_t* cand_aspects1, const int64_t* hist_aspects1, int32_t num_classes1,
+                           const int64_t* hist_offsets, int64_t n_hist, const int32_t* top_k, int32_t n_k, int32_t* rank,
+                           float* rows, double* sums, int64_t* count, int32_t* status, void* ws, size_t ws_bytes, void* stream);
 
 #ifdef __cplusplus
 }

@@ -11,7 +11,7 @@ from ctypes import POINTER, c_char_p, c_double, c_float, c_int32, c_int64, c_siz
 
 _PKG = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_PKG, "libnewsreclib_amd.so")
-ABI_VERSION = 18
+ABI_VERSION = 19
 
 
 class NrlBlockParams(ctypes.Structure):
@@ -292,6 +292,10 @@ SIGNATURES = {
                                            c_size_t, c_void_p]),
     "nrl_manner_scores": (c_int32, [POINTER(c_void_p), POINTER(c_float), c_int32, c_int64, c_void_p, c_void_p, c_void_p, c_void_p,
                                     c_int64, c_int32, c_int32, c_void_p, c_void_p]),
+    "nrl_impression_metrics_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int32, c_int32]),
+    "nrl_impression_metrics": (c_int32, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int32, c_void_p, c_void_p, c_int32,
+                                         c_void_p, c_void_p, c_int32, c_void_p, c_int64, POINTER(c_int32), c_int32, c_void_p,
+                                         c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "nrl_embedding_rows_fwd": (c_int32, [c_void_p, c_void_p, c_int64, c_int32, c_double, c_uint64, c_uint32,
                                          c_void_p, c_void_p]),
     "nrl_embedding_rows_bwd": (c_int32, [c_void_p, c_void_p, c_int64, c_int32, c_double, c_uint64, c_uint32,

@@ -14,10 +14,21 @@ import torch.distributed as dist
 from ._lightning import LightningModuleBase
 from . import ops
 from .dense_batch import dense_rows
-from .metrics import aspect_metrics, ranking_metrics
+from .metrics import StreamingMetrics, aspect_metrics, ranking_metrics
+
+
+STEP_OUTPUT_NAMES = ("loss", "preds", "targets", "cand_news_size", "hist_news_size", "target_categories", "target_sentiments",
+                     "hist_categories", "hist_sentiments", "user_ids", "cand_news_ids")
+_RECS_OUTPUTS = ("user_ids", "cand_news_ids", "preds", "cand_news_size")
 
 
 class AbstractRecommender(LightningModuleBase):
+    # Opt-in (a class attribute, not a constructor keyword: the reference's constructor signatures are kept): validation / test
+    # steps feed a ``metrics.StreamingMetrics`` (``nrl_impression_metrics`` into an epoch accumulator) and the epoch end logs from
+    # it, instead of keeping every step output for the torch metrics.  Single process only: the cross-rank reduction of the
+    # accumulator is not built.
+    device_metrics = False
+
     def _init_step_outputs(self, outputs: Dict) -> None:
         self.step_outputs = {stage: {key: [] for key in keys} for stage, keys in outputs.items()}
         self.training_step_outputs = {key: [] for key in self.step_outputs.get("train", {})}
@@ -132,15 +143,44 @@ class AbstractRecommender(LightningModuleBase):
         return loss
 
     def validation_step(self, batch: Dict, batch_idx: int):
+        if self.device_metrics:
+            return self._device_metrics_step("val", self.val_step_outputs, self.model_step(batch))
         loss, preds, targets, cand_news_size, *_ = self.model_step(batch)
         self._track("val", loss)
         self.val_step_outputs = self._collect_step_outputs(self.val_step_outputs, locals())
 
     def test_step(self, batch: Dict, batch_idx: int):
+        if self.device_metrics:
+            return self._device_metrics_step("test", self.test_step_outputs, self.model_step(batch))
         (loss, preds, targets, cand_news_size, hist_news_size, target_categories, target_sentiments,
          hist_categories, hist_sentiments, user_ids, cand_news_ids) = self.model_step(batch)
         self._track("test", loss)
         self.test_step_outputs = self._collect_step_outputs(self.test_step_outputs, locals())
+
+    # -- device_metrics = True: the step outputs go into an epoch accumulator instead of the output lists --------
+    def _stream_metrics(self, stage: str, outputs: Dict[str, list]) -> StreamingMetrics:
+        if self._world() > 1:
+            raise NotImplementedError("device_metrics = True runs in a single process: the cross-rank reduction of the metric "
+                                      "accumulator is not built; leave the attribute False under data parallelism")
+        streams = self.__dict__.setdefault("_stream_metrics_by_stage", {})
+        if stage not in streams:
+            # the same switches as the torch path: an aspect is computed when the stage's configured outputs list its columns
+            def ncls(asp, attr):
+                wanted = all(k in outputs for k in (f"target_{asp}", f"hist_{asp}", "hist_news_size"))
+                return getattr(self, attr, None) if wanted else None
+            streams[stage] = StreamingMetrics(self.hparams.top_k_list, ncls("categories", "num_categ_classes"),
+                                              ncls("sentiments", "num_sent_classes"))
+        return streams[stage]
+
+    def _device_metrics_step(self, stage: str, outputs: Dict[str, list], step: Tuple) -> None:
+        self._track(stage, step[0])
+        if all(k in outputs for k in ("preds", "targets", "cand_news_size")):
+            self._stream_metrics(stage, outputs).update(step)
+        if stage == "test" and getattr(self.hparams, "save_recs", False):      # the recommendation file is written from these
+            named = dict(zip(STEP_OUTPUT_NAMES, step))
+            for k in _RECS_OUTPUTS:
+                if k in outputs:
+                    outputs[k].append(named[k])
 
     # -- data-parallel epoch ends: every rank sees every rank's step outputs -------------------------
     @staticmethod
@@ -172,7 +212,13 @@ class AbstractRecommender(LightningModuleBase):
             logs[f"{stage}/loss"] = float(s[0]) / s[1]
         local_outputs = outputs
         outputs = self._gather_outputs(outputs)
-        if outputs.get("preds") and outputs.get("targets") and outputs.get("cand_news_size"):
+        stream = self.__dict__.get("_stream_metrics_by_stage", {}).get(stage) if self.device_metrics else None
+        if stream is not None:
+            if self._world() > 1:
+                raise NotImplementedError("device_metrics = True runs in a single process")
+            logs.update({f"{stage}/{k}": v for k, v in stream.compute().items()})
+            stream.reset()
+        elif outputs.get("preds") and outputs.get("targets") and outputs.get("cand_news_size"):
             m = ranking_metrics(torch.cat(outputs["preds"]), torch.cat(outputs["targets"]),
                                 torch.cat(outputs["cand_news_size"]), self.hparams.top_k_list)
             logs.update({f"{stage}/{k}": v for k, v in m.items()})

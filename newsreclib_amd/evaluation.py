@@ -325,19 +325,32 @@ class NpaFeatureCache:
 
 def evaluate_impressions(cache: NewsVectorCache, impressions: Sequence[Dict], batch_size: int = 512,
                          top_k_list: Sequence[int] = (5, 10), num_categ_classes: Optional[int] = None,
-                         num_sent_classes: Optional[int] = None) -> Dict[str, float]:
+                         num_sent_classes: Optional[int] = None, device_metrics: bool = False) -> Dict[str, float]:
     """Scores a list of impressions ({"hist": idx tensor, "cand": idx tensor, "labels": tensor[, "user_idx"]})
-    in batches and returns the epoch-end metrics of ``on_test_epoch_end`` (nrms_module.py:456-493)."""
-    from .metrics import aspect_metrics, ranking_metrics
+    in batches and returns the epoch-end metrics of ``on_test_epoch_end`` (nrms_module.py:456-493).
+    ``device_metrics=True`` feeds every batch to a ``metrics.StreamingMetrics`` (``nrl_impression_metrics`` into an epoch
+    accumulator) instead of keeping the step outputs for the torch metrics; the returned dict has the same keys."""
+    from .metrics import StreamingMetrics, aspect_metrics, ranking_metrics
     outs = []
+    stream = StreamingMetrics(top_k_list, num_categ_classes, num_sent_classes) if device_metrics else None
+    loss_sum, steps = 0.0, 0
     for lo in range(0, len(impressions), batch_size):
         chunk = impressions[lo:lo + batch_size]
         hs = torch.tensor([len(i["hist"]) for i in chunk])
         cs = torch.tensor([len(i["cand"]) for i in chunk])
         uidx = torch.stack([torch.as_tensor(i["user_idx"]) for i in chunk]) if "user_idx" in chunk[0] else None
-        outs.append(cache.model_step(torch.cat([torch.as_tensor(i["hist"]) for i in chunk]), hs,
-                                     torch.cat([torch.as_tensor(i["cand"]) for i in chunk]), cs,
-                                     torch.cat([torch.as_tensor(i["labels"]).float() for i in chunk]), uidx))
+        out = cache.model_step(torch.cat([torch.as_tensor(i["hist"]) for i in chunk]), hs,
+                               torch.cat([torch.as_tensor(i["cand"]) for i in chunk]), cs,
+                               torch.cat([torch.as_tensor(i["labels"]).float() for i in chunk]), uidx)
+        if stream is not None:
+            stream.update(out)
+            loss_sum, steps = loss_sum + out[0].detach().double(), steps + 1      # stays on the device until the end
+        else:
+            outs.append(out)
+    if stream is not None:
+        logs = {"loss": float(loss_sum) / max(1, steps)}
+        logs.update(stream.compute() or {"mrr": 0.0, **{f"ndcg@{k}": 0.0 for k in top_k_list}, "auc": 0.0})
+        return logs
     cat = lambda j: torch.cat([o[j] for o in outs])  # noqa: E731
     logs = {"loss": float(sum(float(o[0]) for o in outs) / max(1, len(outs)))}
     logs.update(ranking_metrics(cat(1), cat(2), cat(3), top_k_list))

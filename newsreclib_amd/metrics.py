@@ -2,8 +2,13 @@
 
 The reference wires torchmetrics ``AUROC``/``RetrievalMRR``/``RetrievalNormalizedDCG`` grouped by an
 ``indexes`` vector (nrms_module.py:182-195,380-396).  These run once per epoch, outside the timed
-step, on small vectors; they are host-side bookkeeping in plain torch, vectorised over queries."""
-from typing import Dict, Sequence
+step, on small vectors; they are host-side bookkeeping in plain torch, vectorised over queries.
+
+``impression_metrics`` / ``StreamingMetrics`` are the opt-in device-side form (``nrl_impression_metrics``): one small kernel
+per batch computes the per-impression values from the ragged outputs and adds them into an O(1) epoch accumulator, so the
+epoch end needs neither the concatenated step outputs (beyond the two flat vectors of the global AUC) nor the dense
+(impressions, longest impression) tensors and their sorts.  ``ranking_metrics`` / ``aspect_metrics`` stay the default."""
+from typing import Dict, Optional, Sequence, Tuple
 
 import torch
 
@@ -15,6 +20,23 @@ def _dense(preds, targets, sizes):
     t = targets.new_zeros((B, C))
     p[mask], t[mask] = preds, targets
     return p, t, mask
+
+
+def _global_auc(preds: torch.Tensor, targets: torch.Tensor) -> float:
+    """global AUROC over all (score, label) pairs, as torchmetrics' binary AUROC without indexes"""
+    pos, neg = preds[targets > 0], preds[targets <= 0]
+    if pos.numel() and neg.numel():
+        allv = torch.cat([pos, neg])
+        r = torch.empty(allv.shape, dtype=torch.float64, device=allv.device)
+        srt, idx = torch.sort(allv)
+        # average ranks for ties; rank sums in float64 (an epoch holds millions of pairs: float32 ranks stop being integers at 2^24)
+        uniq, inv, cnt = torch.unique_consecutive(srt, return_inverse=True, return_counts=True)
+        ends = torch.cumsum(cnt, 0).double()
+        avg_rank = ends - (cnt.double() - 1) / 2
+        r[idx] = avg_rank[inv]
+        auc = (r[: pos.numel()].sum() - pos.numel() * (pos.numel() + 1) / 2) / (float(pos.numel()) * neg.numel())
+        return float(auc)
+    return 0.0
 
 
 def ranking_metrics(preds: torch.Tensor, targets: torch.Tensor, cand_news_size: torch.Tensor,
@@ -39,21 +61,7 @@ def ranking_metrics(preds: torch.Tensor, targets: torch.Tensor, cand_news_size: 
         idcg = (ideal[:, :k] * disc[:, :k]).sum(1)
         ndcg = torch.where(idcg > 0, dcg / idcg.clamp_min(1e-12), torch.zeros_like(dcg))
         out[f"ndcg@{k}"] = float(ndcg.mean()) if ndcg.numel() else 0.0      # 0 for impressions without a positive
-    # global AUROC over all (score, label) pairs, as torchmetrics' binary AUROC without indexes
-    pos, neg = preds[targets > 0], preds[targets <= 0]
-    if pos.numel() and neg.numel():
-        allv = torch.cat([pos, neg])
-        r = torch.empty(allv.shape, dtype=torch.float64, device=allv.device)
-        srt, idx = torch.sort(allv)
-        # average ranks for ties; rank sums in float64 (an epoch holds millions of pairs: float32 ranks stop being integers at 2^24)
-        uniq, inv, cnt = torch.unique_consecutive(srt, return_inverse=True, return_counts=True)
-        ends = torch.cumsum(cnt, 0).double()
-        avg_rank = ends - (cnt.double() - 1) / 2
-        r[idx] = avg_rank[inv]
-        auc = (r[: pos.numel()].sum() - pos.numel() * (pos.numel() + 1) / 2) / (float(pos.numel()) * neg.numel())
-        out["auc"] = float(auc)
-    else:
-        out["auc"] = 0.0
+    out["auc"] = _global_auc(preds, targets)
     return out
 
 
@@ -100,3 +108,128 @@ def aspect_metrics(preds: torch.Tensor, cand_aspects: torch.Tensor, hist_aspects
         out[f"{prefix}_div@{k}"] = float(div.mean()) if B else 0.0
         out[f"{prefix}_pers@{k}"] = float(pers.mean()) if B else 0.0
     return out
+
+
+# ---- device-side streaming form ------------------------------------------------------------------
+def _offsets(sizes: torch.Tensor, device) -> torch.Tensor:
+    """(B + 1) int64 prefix sums of the per-impression sizes, on the device, without a read-back."""
+    sizes = sizes.to(device).long()
+    off = torch.zeros(sizes.numel() + 1, dtype=torch.int64, device=device)
+    torch.cumsum(sizes, 0, out=off[1:])
+    return off
+
+
+def impression_metrics(preds: torch.Tensor, targets: torch.Tensor, cand_news_size: torch.Tensor,
+                       top_k_list: Sequence[int] = (5, 10), aspects: Optional[Dict[str, Tuple]] = None,
+                       hist_news_size: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
+    """Per-impression values of ``ranking_metrics`` / ``aspect_metrics`` as (B,) device tensors under the same key names (the
+    reciprocal rank under "mrr"), plus "rank": the 0-based position of every candidate in its impression's stable descending
+    ranking, and "status": the kernel's one-word error mask (``ops.METRICS_FLAGS``; 0 = every impression was taken), which the
+    caller reads when it wants to.  ``aspects``: prefix -> (cand_aspects, hist_aspects, num_classes), at most two, with
+    ``hist_news_size``.  GPU tensors only; nothing here synchronises with the host."""
+    from . import ops
+    aspects = aspects or {}
+    dev = preds.device
+    if aspects and hist_news_size is None:
+        raise ValueError("impression_metrics: aspects need hist_news_size")
+    rank, rows, status = ops.impression_metrics(
+        preds.float(), targets.float(), _offsets(cand_news_size, dev), top_k_list,
+        [(ca.to(dev).long(), ha.to(dev).long(), ncls) for ca, ha, ncls in aspects.values()],
+        _offsets(hist_news_size, dev) if aspects else None)
+    out = {name: rows[:, j] for j, name in enumerate(ops.metrics_columns(top_k_list, list(aspects)))}
+    out["rank"], out["status"] = rank, status
+    return out
+
+
+class StreamingMetrics:
+    """Epoch metrics without the epoch's step outputs: ``update`` takes the tuple ``model_step`` / ``*Cache.model_step`` returns
+    and launches ``nrl_impression_metrics`` into a float64 accumulator (one sum per metric column, an impression count and a status
+    word, all on the device); ``compute`` returns the dict of ``ranking_metrics`` + ``aspect_metrics(prefix="categ")`` +
+    ``aspect_metrics(prefix="sent")``.  Only the flat ``preds`` / ``targets`` are kept, for the global AUC (a sort over all pairs).
+    ``update`` performs no device-to-host transfer; ``compute`` reads the status word first and raises ``ValueError`` when the
+    kernel refused an impression.  An aspect is computed when its class count was given and the step outputs carry its ids; the
+    set of aspects is fixed by the first ``update``."""
+
+    def __init__(self, top_k_list: Sequence[int] = (5, 10), num_categ_classes: Optional[int] = None,
+                 num_sent_classes: Optional[int] = None):
+        self.top_k_list = tuple(int(k) for k in top_k_list)
+        self.num_classes = {"categ": num_categ_classes, "sent": num_sent_classes}
+        self.reset()
+
+    def reset(self) -> None:
+        self.prefixes: Optional[Tuple[str, ...]] = None
+        self.sums = self.count = self.status = None
+        self._preds, self._targets = [], []
+        self._hist_ids = 0                        # history aspect ids seen (a shape, known on the host)
+
+    def _alloc(self, prefixes, device) -> None:
+        from . import ops
+        self.prefixes = tuple(prefixes)
+        self.columns = ops.metrics_columns(self.top_k_list, self.prefixes)
+        self.sums = torch.zeros(len(self.columns), dtype=torch.float64, device=device)
+        self.count = torch.zeros(1, dtype=torch.int64, device=device)
+        self.status = torch.zeros(1, dtype=torch.int32, device=device)
+
+    def update(self, step_output: Sequence) -> None:
+        from . import ops
+        (_, preds, targets, cand_news_size, hist_news_size, target_categories, target_sentiments, hist_categories,
+         hist_sentiments, *_) = step_output
+        if not preds.is_cuda:
+            raise RuntimeError(f"newsreclib_amd: StreamingMetrics.update needs GPU step outputs (got {preds.device}); there is no "
+                               "CPU path -- metrics.ranking_metrics / aspect_metrics serve host tensors")
+        dev = preds.device
+        given = {"categ": (target_categories, hist_categories), "sent": (target_sentiments, hist_sentiments)}
+        prefixes = tuple(p for p in ("categ", "sent") if self.num_classes[p] and given[p][0].numel())
+        if self.prefixes is None:
+            self._alloc(prefixes, dev)
+        elif prefixes != self.prefixes:
+            raise ValueError(f"StreamingMetrics.update: this step carries the aspects {prefixes}, the accumulator was started with "
+                             f"{self.prefixes}")
+        preds, targets = preds.detach(), targets.detach()
+        aspects = [(given[p][0].to(dev).long(), given[p][1].to(dev).long(), self.num_classes[p]) for p in prefixes]
+        ops.impression_metrics(preds.float(), targets.float(), _offsets(cand_news_size, dev), self.top_k_list, aspects,
+                               _offsets(hist_news_size, dev) if aspects else None, status=self.status, sums=self.sums,
+                               count=self.count, want_rank=False, want_rows=False)
+        self._preds.append(preds)
+        self._targets.append(targets)
+        if aspects:
+            self._hist_ids += int(aspects[0][1].numel())
+
+    def merge(self, other: "StreamingMetrics") -> "StreamingMetrics":
+        """Adds another accumulator of the same configuration (say, a second evaluation stream over other impressions)."""
+        if other.top_k_list != self.top_k_list or other.num_classes != self.num_classes:
+            raise ValueError("StreamingMetrics.merge: the two accumulators were configured differently")
+        if other.prefixes is None:
+            return self
+        if self.prefixes is None:
+            self._alloc(other.prefixes, other.sums.device)
+        elif other.prefixes != self.prefixes:
+            raise ValueError(f"StreamingMetrics.merge: aspects {other.prefixes} against {self.prefixes}")
+        self.sums += other.sums.to(self.sums.device)
+        self.count += other.count.to(self.sums.device)
+        self.status |= other.status.to(self.sums.device)
+        self._preds += other._preds
+        self._targets += other._targets
+        self._hist_ids += other._hist_ids
+        return self
+
+    def compute(self) -> Dict[str, float]:
+        from . import ops
+        if self.prefixes is None:
+            return {}
+        flags = int(self.status)                   # the one read of the status word
+        if flags:
+            raise ValueError("StreamingMetrics: the metrics kernel refused input: " +
+                             "; ".join(msg for bit, msg in ops.METRICS_FLAGS.items() if flags & bit))
+        n = int(self.count)
+        mean = (self.sums / max(n, 1)).tolist()
+        vals = dict(zip(self.columns, mean))
+        out = {"mrr": vals["mrr"]}
+        out.update({f"ndcg@{k}": vals[f"ndcg@{k}"] for k in self.top_k_list})
+        out["auc"] = _global_auc(torch.cat(self._preds), torch.cat(self._targets)) if self._preds else 0.0
+        for p in self.prefixes:
+            if self._hist_ids:                     # (an epoch without any history id has no aspect metrics, as the torch path)
+                for k in self.top_k_list:
+                    out[f"{p}_div@{k}"] = vals[f"{p}_div@{k}"]
+                    out[f"{p}_pers@{k}"] = vals[f"{p}_pers@{k}"]
+        return out

@@ -628,3 +628,79 @@ def offsets_from_sorted_batch(batch: torch.Tensor, batch_size: int) -> torch.Ten
     off = torch.zeros(batch_size + 1, dtype=torch.int64, device=batch.device)
     torch.cumsum(counts, 0, out=off[1:])
     return off
+
+
+# ---- streaming evaluation metrics (nrl_metrics.hip) -----------------------------------------------
+METRICS_MAX_CAND, METRICS_MAX_CLASSES, METRICS_MAX_K, METRICS_MAX_NK = 4096, 1024, 1024, 4
+METRICS_FLAGS = {1: f"an impression has more than {METRICS_MAX_CAND} candidates",
+                 2: "an aspect id is negative or >= num_classes",
+                 4: "an offset vector is not non-decreasing inside its buffer"}
+
+
+def metrics_columns(top_k: Sequence[int], prefixes: Sequence[str] = ()) -> list:
+    """Column names of the rows / sums of ``impression_metrics`` (the key names of ``metrics.ranking_metrics`` /
+    ``metrics.aspect_metrics``; the per-impression reciprocal rank stands under "mrr")."""
+    cols = ["mrr"] + [f"ndcg@{k}" for k in top_k]
+    for p in prefixes:
+        cols += [f"{p}_div@{k}" for k in top_k] + [f"{p}_pers@{k}" for k in top_k]
+    return cols
+
+
+def impression_metrics(preds: torch.Tensor, targets: torch.Tensor, cand_offsets: torch.Tensor, top_k: Sequence[int],
+                       aspects: Sequence[Tuple[torch.Tensor, torch.Tensor, int]] = (), hist_offsets: Optional[torch.Tensor] = None,
+                       status: Optional[torch.Tensor] = None, sums: Optional[torch.Tensor] = None,
+                       count: Optional[torch.Tensor] = None, want_rank: bool = True, want_rows: bool = True):
+    """``nrl_impression_metrics`` over one batch of ragged impressions -> (rank (N) int32 | None, rows (B, cols) fp32 | None, status).
+    ``aspects``: up to two (cand_aspects (N) int64, hist_aspects (n_hist) int64, num_classes) sharing ``hist_offsets`` (B + 1).
+    ``sums`` (cols float64) / ``count`` (1 int64) are accumulated into; ``status`` (1 int32) is OR-ed into (``METRICS_FLAGS``) and
+    must be read by the caller -- nothing here synchronises with the host."""
+    lib = _lib.load()
+    preds, targets = _chk(preds, torch.float32, "preds"), _chk(targets, torch.float32, "targets")
+    cand_offsets = _chk(cand_offsets, torch.int64, "cand_offsets")
+    N, B = int(preds.numel()), int(cand_offsets.numel()) - 1
+    top_k = [int(k) for k in top_k]
+    if targets.numel() != N or B < 0 or preds.dim() != 1:
+        raise ValueError("newsreclib_amd: flat preds / targets of one length and cand_offsets of B + 1 entries expected")
+    if len(top_k) > METRICS_MAX_NK or any(not 1 <= k <= METRICS_MAX_K for k in top_k):
+        raise ValueError(f"newsreclib_amd: at most {METRICS_MAX_NK} top_k values, each in [1, {METRICS_MAX_K}]; got {top_k}")
+    if len(aspects) > 2:
+        raise ValueError("newsreclib_amd: at most two aspects per call")
+    asp, n_hist = [], 0
+    if aspects:
+        if hist_offsets is None:
+            raise ValueError("newsreclib_amd: aspects need hist_offsets")
+        hist_offsets = _chk(hist_offsets, torch.int64, "hist_offsets")
+        if hist_offsets.numel() != B + 1:
+            raise ValueError("newsreclib_amd: hist_offsets must have B + 1 entries")
+        n_hist = int(aspects[0][1].numel())
+        for ca, ha, ncls in aspects:
+            ca, ha = _chk(ca, torch.int64, "cand_aspects"), _chk(ha, torch.int64, "hist_aspects")
+            if ca.numel() != N or ha.numel() != n_hist or not 2 <= int(ncls) <= METRICS_MAX_CLASSES:
+                raise ValueError(f"newsreclib_amd: every aspect needs N candidate ids, one history length and 2 <= num_classes <= "
+                                 f"{METRICS_MAX_CLASSES}; got {ca.numel()} / {ha.numel()} ids, num_classes {ncls}")
+            asp.append((ca, ha, int(ncls)))
+    dev = preds.device
+    cols = 1 + len(top_k) * (1 + 2 * len(asp))
+    if status is None:
+        status = torch.zeros(1, dtype=torch.int32, device=dev)
+    status = _chk(status, torch.int32, "status")
+    if (sums is None) != (count is None):
+        raise ValueError("newsreclib_amd: sums and count go together")
+    if sums is not None:
+        sums, count = _chk(sums, torch.float64, "sums"), _chk(count, torch.int64, "count")
+        if sums.numel() != cols or count.numel() != 1:
+            raise ValueError(f"newsreclib_amd: sums must have {cols} entries and count one")
+    rank = torch.empty(N, dtype=torch.int32, device=dev) if want_rank else None
+    rows = torch.zeros((B, cols), dtype=torch.float32, device=dev) if want_rows else None
+    if B == 0:
+        return rank, rows, status
+    ws = torch.empty(max(lib.nrl_impression_metrics_workspace_bytes(N, B, len(asp), len(top_k)), 256), dtype=torch.uint8, device=dev)
+    ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
+    a0 = asp[0] if len(asp) > 0 else (None, None, 0)
+    a1 = asp[1] if len(asp) > 1 else (None, None, 0)
+    ks = (ctypes.c_int32 * max(len(top_k), 1))(*top_k)
+    _lib.check(lib.nrl_impression_metrics(preds.data_ptr(), targets.data_ptr(), cand_offsets.data_ptr(), N, B, len(asp),
+                                          ptr(a0[0]), ptr(a0[1]), a0[2], ptr(a1[0]), ptr(a1[1]), a1[2], ptr(hist_offsets) if asp else None,
+                                          n_hist, ks, len(top_k), ptr(rank), ptr(rows), ptr(sums), ptr(count), status.data_ptr(),
+                                          ws.data_ptr(), ws.numel(), _stream()), "nrl_impression_metrics")
+    return rank, rows, status
