@@ -1007,6 +1007,36 @@ int nrl_impression_metrics(const float* preds, const float* targets, const int64
                            const int64_t* hist_offsets, int64_t n_hist, const int32_t* top_k, int32_t n_k, int32_t* rank,
                            float* rows, double* sums, int64_t* count, int32_t* status, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- full-catalogue top-k recommendation (symbols added to ABI v19; nothing of the reference is replaced: it can only re-rank the
+ * candidates an impression lists).
+ * nrl_topk_scores: for each of B users the k rows of `table` with the highest dot product with the user's vector, without ever
+ *   writing the (B, V) score matrix.  user_vec (B, D) and table (V, D): fp32, row-major, device.  D a multiple of 4 up to 1024,
+ *   k in [1, NRL_TOPK_MAX_K], V < 2^31, B < 2^31.
+ *   excl_idx (int64) / excl_off ((B + 1) int64), nullable together: a ragged per-user list of table rows that are never returned
+ *     for that user (the history): user b owns excl_idx[excl_off[b] .. excl_off[b + 1]).  Duplicates, empty lists and any length
+ *     are fine.  excl_off[B] is the length of excl_idx and is trusted as such; every other offset is validated against it.
+ *   eligible (V uint8, nullable): 0 = the row is never returned for anyone (a padding row, stale news).
+ *   slices: 0 = the library chooses how many pieces of V are scanned in parallel per tile of 64 users; > 0 forces that count
+ *     (clamped to the number of 128-row table tiles).  The result does not depend on it.
+ *   out_idx (B, k) int64 / out_score (B, k) fp32: score descending, equal scores by ascending table row (-0 == +0); when fewer
+ *     than k rows qualify the tail is -1 / -inf.
+ *   status (one int32, required): the kernels OR NRL_TOPK_E_* into it.
+ *   Arithmetic: every score is the exact-fp32 MFMA dot product accumulated over D in one fixed order, whatever the GEMM engine
+ *     setting: the bits of score(u, v) do not depend on B, V, k, slices or the grid, and the selection is a pure function of those
+ *     bits and the row numbers.  No floating-point atomics, no allocation, no host synchronisation.
+ *   Workspace: nrl_topk_scores_workspace_bytes (callable without a device; B * slices * k * 8 bytes rounded up to 256, never
+ *     O(B * V)), 256-byte aligned.  B == 0 returns success without a launch; V == 0 fills the output with -1 / -inf.  Sizes outside
+ *     the limits above return NRL_E_INVALID, a short workspace NRL_E_WORKSPACE. */
+#define NRL_TOPK_MAX_K 128
+#define NRL_TOPK_MAX_D 1024
+#define NRL_TOPK_E_EXCLUDE 1 /* an exclusion index is outside [0, V): that entry is ignored */
+#define NRL_TOPK_E_OFFSETS 2 /* excl_off decreases or leaves [0, excl_off[B]]: that user's row is all -1 / -inf */
+#define NRL_TOPK_E_NAN 4     /* a NaN score of an eligible, not excluded row: the row is left out for that user */
+size_t nrl_topk_scores_workspace_bytes(int64_t B, int64_t V, int32_t D, int32_t k, int32_t slices);
+int nrl_topk_scores(const float* user_vec, const float* table, int64_t B, int64_t V, int32_t D, int32_t k, const int64_t* excl_idx,
+                    const int64_t* excl_off, const uint8_t* eligible, int32_t slices, int64_t* out_idx, float* out_score,
+                    int32_t* status, void* ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

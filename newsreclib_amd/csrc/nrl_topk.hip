@@ -1,0 +1,441 @@
+// Full-catalogue top-k recommendation: for B user vectors and a (V, D) news-vector table, the k table rows of highest dot product
+// per user, leaving out a ragged per-user exclusion list (the history) and the rows an `eligible` mask removes.  The (B, V) score
+// matrix is never written: every workgroup keeps k entries per user while its slice of the table streams past once.
+//
+//   tk_scores_kernel   256 threads, one workgroup per (tile of TK_BU = 64 users, slice of V).  Per table tile of TK_BV = 128 rows:
+//       * scores = exact-fp32 MFMA (v_mfma_f32_16x16x4_f32) over LDS tiles of both operands (k-major, double-buffered, register-
+//         staged global loads as nrl_gemm.h).  Every score is ONE accumulator chain over k = 0, 4, 8, ... from +0, zero-filled up to
+//         the next multiple of TK_BK: its bits are a function of the two rows and D alone, whatever B, V, k, the slicing or the
+//         GEMM engine setting (which this unit does not read);
+//       * the 64 x 128 scores go to LDS; each wave scans its 16 users: a lane owns two columns, builds the 64-bit entry
+//         (order-preserving score key << 32 | ~row: larger = better, so equal scores rank by ascending row, and 0 = empty slot) of
+//         the columns that are inside V and eligible, and compares it with the user's current k-th entry.  Nearly always no lane
+//         survives and the user costs a few instructions;
+//       * when lanes survive, the user's exclusion list (its first TK_XCAP entries cached in LDS, longer lists read from global
+//         memory) clears the bits of excluded rows that fall inside this tile, the user's list is loaded into registers (entry p in
+//         lane p & 63) and the survivors are inserted one by one with ballots and lane shifts.  The top k of a set under a strict
+//         total order does not depend on the insertion order, so the result is a pure function of the score bits and the rows.
+//   tk_merge_kernel    one wave per user: validates the user's offsets and exclusion indices (status flags), merges the `slices`
+//       partial lists with the same insertion and writes (row, score) or (-1, -inf).
+// No float atomics, no allocation, no host read-back; the workspace holds the partial lists, O(B * slices * k).
+#include <math.h>
+
+#include "nrl_common.h"
+
+namespace nrl {
+
+using tk_f32x4 = __attribute__((ext_vector_type(4))) float;
+
+constexpr int TK_THREADS = 256;
+constexpr int TK_BU = 64;                      // users per workgroup: 2 waves x 2 MFMA blocks
+constexpr int TK_BV = 128;                     // table rows per tile: 2 waves x 4 MFMA blocks
+constexpr int TK_BK = 16;
+constexpr int TK_LDA = TK_BU + 16;             // == 16 (mod 32): conflict-free fragment reads (nrl_gemm.h LdsLd)
+constexpr int TK_LDB = TK_BV + 16;
+constexpr int TK_SCLD = TK_BV + 4;             // score tile: 4 rows apart = 16 banks apart for the accumulator stores
+constexpr int TK_XCAP = 64;                    // exclusion entries per user cached in LDS
+constexpr int TK_USERS_PER_WAVE = TK_BU / 4;
+constexpr int TK_TARGET_BLOCKS = 512;          // two resident workgroups on each of the 256 CUs
+static_assert(2 * TK_BK * (TK_LDA + TK_LDB) <= TK_BU * TK_SCLD, "the operand tiles live inside the score tile");
+constexpr size_t TK_LDS_FIXED = (size_t)(TK_BU * TK_SCLD + TK_BU * TK_XCAP) * 4 + TK_BU * 8 + TK_BU * 4 + TK_BV;
+
+struct TkArgs {
+  const float* user;
+  const float* table;
+  int64_t B;
+  int32_t V, D, k;
+  const int64_t* excl_idx;
+  const int64_t* excl_off;
+  const uint8_t* eligible;
+  int32_t slices, tiles_per_slice;
+  unsigned long long* partial;                 // (B, slices, k) entries
+  int64_t* out_idx;
+  float* out_score;
+  int32_t* status;
+};
+
+// order-preserving key of a score (nrl_metrics.hip mt_key): a > b <=> key(a) > key(b), -0 == +0, NaN = 0xFFFFFFFF above +inf
+__device__ __forceinline__ uint32_t tk_key(float s) {
+  if (s != s) return 0xFFFFFFFFu;
+  if (s == 0.f) s = 0.f;
+  const uint32_t b = __float_as_uint(s);
+  return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+}
+__device__ __forceinline__ float tk_unkey(uint32_t key) {
+  return __uint_as_float((key & 0x80000000u) ? (key ^ 0x80000000u) : ~key);
+}
+__device__ __forceinline__ unsigned long long tk_entry(float s, uint32_t v) {
+  return ((unsigned long long)tk_key(s) << 32) | (uint32_t)~v;
+}
+
+__device__ __forceinline__ unsigned long long tk_shfl(unsigned long long x, int src) {
+  const uint32_t lo = (uint32_t)__shfl((int)(uint32_t)x, src, 64), hi = (uint32_t)__shfl((int)(uint32_t)(x >> 32), src, 64);
+  return ((unsigned long long)hi << 32) | lo;
+}
+__device__ __forceinline__ unsigned long long tk_shfl_up1(unsigned long long x) {
+  const uint32_t lo = (uint32_t)__shfl_up((int)(uint32_t)x, 1, 64), hi = (uint32_t)__shfl_up((int)(uint32_t)(x >> 32), 1, 64);
+  return ((unsigned long long)hi << 32) | lo;
+}
+
+// A descending list of up to 128 entries held by one wave: position p in lane p & 63 of e0 (p < 64) or e1.  Positions from k on
+// hold what fell off the end (all below the k-th entry) and are never read.
+struct TkList {
+  unsigned long long e0, e1;
+  __device__ __forceinline__ unsigned long long kth(int k) const { return tk_shfl(k <= 64 ? e0 : e1, (k - 1) & 63); }
+  // nk (wave-uniform) is above the k-th entry and differs from every entry
+  __device__ __forceinline__ void insert(unsigned long long nk, int lane, bool two) {
+    const bool g0 = e0 > nk;
+    int pos = __popcll(__ballot(g0));
+    const unsigned long long up0 = tk_shfl_up1(e0);
+    if (two) {
+      const bool g1 = e1 > nk;
+      pos += __popcll(__ballot(g1));
+      unsigned long long up1 = tk_shfl_up1(e1);
+      const unsigned long long last0 = tk_shfl(e0, 63);
+      if (lane == 0) up1 = last0;
+      e1 = g1 ? e1 : (lane + 64 == pos ? nk : up1);
+    }
+    e0 = g0 ? e0 : (lane == pos ? nk : up0);
+  }
+  // inserts the lanes' entries c whose bit is set in m, as long as they stay above the k-th entry; NaN scores are only reported
+  __device__ __forceinline__ bool take(unsigned long long c, unsigned long long m, int k, int lane, bool& nan) {
+    bool changed = false;
+    unsigned long long thr = kth(k);
+    while (m) {
+      const int b = __ffsll((long long)m) - 1;
+      m &= m - 1;
+      const unsigned long long nk = tk_shfl(c, b);
+      if (nk <= thr) continue;
+      if ((uint32_t)(nk >> 32) == 0xFFFFFFFFu) {
+        nan = true;
+        continue;
+      }
+      insert(nk, lane, k > 64);
+      thr = kth(k);
+      m &= __ballot(c > thr);
+      changed = true;
+    }
+    return changed;
+  }
+};
+
+__device__ __forceinline__ void tk_wave_sync() {        // one wave: LDS operations complete in order, the compiler must keep it
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// a user's exclusion range: false when the offsets decrease or leave [0, excl_off[B]]
+__device__ __forceinline__ bool tk_excl_range(const TkArgs& A, int64_t u, int64_t& s, int64_t& n) {
+  s = 0;
+  n = 0;
+  if (!A.excl_off) return true;
+  const int64_t a = A.excl_off[u], b = A.excl_off[u + 1], end = A.excl_off[A.B];
+  if (a < 0 || b < a || b > end) return false;
+  s = a;
+  n = A.excl_idx ? b - a : 0;
+  return true;
+}
+
+__global__ __launch_bounds__(TK_THREADS) void tk_scores_kernel(TkArgs A) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char tk_smem[];
+  float* const sc = reinterpret_cast<float*>(tk_smem);                       // [TK_BU][TK_SCLD]; before the scores exist it holds
+  float* const As = sc;                                                      // [2][TK_BK][TK_LDA] and
+  float* const Bs = As + 2 * TK_BK * TK_LDA;                                 // [2][TK_BK][TK_LDB], the operand tiles
+  int32_t* const xl = reinterpret_cast<int32_t*>(sc + TK_BU * TK_SCLD);      // [TK_BU][TK_XCAP] cached exclusion rows (-1: none)
+  int64_t* const xs = reinterpret_cast<int64_t*>(xl + TK_BU * TK_XCAP);      // [TK_BU] start of the user's exclusion list
+  int32_t* const xn = reinterpret_cast<int32_t*>(xs + TK_BU);                // [TK_BU] its length (0: none, or bad offsets)
+  uint8_t* const el = reinterpret_cast<uint8_t*>(xn + TK_BU);                // [TK_BV] column inside V and eligible
+  unsigned long long* const lists = reinterpret_cast<unsigned long long*>(el + TK_BV);      // [TK_BU][k]
+
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int wm = wave >> 1, wn = wave & 1;
+  const int l15 = lane & 15, g = lane >> 4;
+  const int k = A.k, D = A.D, V = A.V;
+  // the slice is the fast index: the workgroups resident together share their table slice across the user tiles
+  const int sl = (int)(blockIdx.x % (unsigned)A.slices);
+  const int64_t u0 = (int64_t)(blockIdx.x / (unsigned)A.slices) * TK_BU;
+  const int v_begin = sl * A.tiles_per_slice * TK_BV;                        // < V < 2^31
+  const int64_t v_stop = (int64_t)v_begin + (int64_t)A.tiles_per_slice * TK_BV;
+  const int v_end = v_stop < V ? (int)v_stop : V;
+  const int nvt = (v_end - v_begin + TK_BV - 1) / TK_BV;
+  const int nkt = (D + TK_BK - 1) / TK_BK;
+
+  for (int i = tid; i < TK_BU * k; i += TK_THREADS) lists[i] = 0ull;
+  if (tid < TK_BU) {
+    int64_t s = 0, n = 0;
+    if (u0 + tid < A.B && !tk_excl_range(A, u0 + tid, s, n)) n = 0;         // the merge kernel flags and blanks such a user
+    xs[tid] = s;
+    xn[tid] = (int32_t)(n < 0x7FFFFFFF ? n : 0x7FFFFFFF);
+  }
+  __syncthreads();
+  for (int i = tid; i < TK_BU * TK_XCAP; i += TK_THREADS) {
+    const int ul = i / TK_XCAP, j = i % TK_XCAP;
+    int32_t x = -1;
+    if (j < xn[ul]) {
+      const int64_t r = A.excl_idx[xs[ul] + j];
+      if (r >= 0 && r < V) x = (int32_t)r;
+    }
+    xl[i] = x;
+  }
+
+  // staging assignment: one float4 of the user tile and two of the table tile per thread and k-tile
+  const int srow = tid >> 2, skc = (tid & 3) * 4;
+  const int64_t ua = u0 + srow < A.B ? u0 + srow : A.B - 1;
+  const bool ua_ok = u0 + srow < A.B;
+  const float* const pa = A.user + ua * D;
+  bool nan = false;
+
+  for (int vt = 0; vt < nvt; ++vt) {
+    const int v0 = v_begin + vt * TK_BV;
+    const float* pb[2];
+    bool vb_ok[2];
+#pragma unroll
+    for (int c = 0; c < 2; ++c) {
+      const int64_t v = (int64_t)v0 + srow + c * 64;
+      vb_ok[c] = v < V;
+      pb[c] = A.table + (int64_t)(vb_ok[c] ? v : V - 1) * D;
+    }
+    if (tid < TK_BV) {
+      const int64_t v = (int64_t)v0 + tid;
+      el[tid] = (v < V && (!A.eligible || A.eligible[v])) ? 1 : 0;
+    }
+    float4 ra, rb[2];
+    auto load_tiles = [&](int k0) {                  // unconditional loads from clamped addresses; masked when staged
+      const int kk = k0 + skc < D ? k0 + skc : D - 4;
+      ra = *reinterpret_cast<const float4*>(pa + kk);
+#pragma unroll
+      for (int c = 0; c < 2; ++c) rb[c] = *reinterpret_cast<const float4*>(pb[c] + kk);
+    };
+    auto store_tiles = [&](int buf, int k0) {
+      const bool kok = k0 + skc < D;
+      float* as = As + buf * TK_BK * TK_LDA;
+      float* bs = Bs + buf * TK_BK * TK_LDB;
+      const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
+      const float4 a = (kok && ua_ok) ? ra : z;
+      as[(skc + 0) * TK_LDA + srow] = a.x;
+      as[(skc + 1) * TK_LDA + srow] = a.y;
+      as[(skc + 2) * TK_LDA + srow] = a.z;
+      as[(skc + 3) * TK_LDA + srow] = a.w;
+#pragma unroll
+      for (int c = 0; c < 2; ++c) {
+        const float4 b = (kok && vb_ok[c]) ? rb[c] : z;
+        const int row = srow + c * 64;
+        bs[(skc + 0) * TK_LDB + row] = b.x;
+        bs[(skc + 1) * TK_LDB + row] = b.y;
+        bs[(skc + 2) * TK_LDB + row] = b.z;
+        bs[(skc + 3) * TK_LDB + row] = b.w;
+      }
+    };
+
+    tk_f32x4 acc[2][4];
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+      for (int j = 0; j < 4; ++j) acc[i][j] = tk_f32x4{0.f, 0.f, 0.f, 0.f};
+
+    load_tiles(0);
+    store_tiles(0, 0);
+    __syncthreads();
+    for (int kt = 0; kt < nkt; ++kt) {
+      const int buf = kt & 1;
+      if (kt + 1 < nkt) load_tiles((kt + 1) * TK_BK);
+      const float* as = As + buf * TK_BK * TK_LDA + wm * 32 + l15;
+      const float* bs = Bs + buf * TK_BK * TK_LDB + wn * 64 + l15;
+#pragma unroll
+      for (int ks = 0; ks < TK_BK / 4; ++ks) {
+        float a[2], b[4];
+#pragma unroll
+        for (int i = 0; i < 2; ++i) a[i] = as[(4 * ks + g) * TK_LDA + i * 16];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) b[j] = bs[(4 * ks + g) * TK_LDB + j * 16];
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+          for (int j = 0; j < 4; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[i], b[j], acc[i][j], 0, 0, 0);
+      }
+      if (kt + 1 < nkt) store_tiles(buf ^ 1, (kt + 1) * TK_BK);
+      __syncthreads();
+    }
+
+    // accumulators -> score tile: the lane holds user 4g + r, column l15 of every 16 x 16 block
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) sc[(wm * 32 + i * 16 + 4 * g + r) * TK_SCLD + wn * 64 + j * 16 + l15] = acc[i][j][r];
+    __syncthreads();
+
+    // selection: wave w owns users 16 w ... 16 w + 15 of the tile and their lists
+    const bool e_0 = el[lane] != 0, e_1 = el[64 + lane] != 0;
+    for (int uu = 0; uu < TK_USERS_PER_WAVE; ++uu) {
+      const int ul = wave * TK_USERS_PER_WAVE + uu;
+      if (u0 + ul >= A.B) break;
+      unsigned long long* L = lists + ul * k;
+      const unsigned long long thr = L[k - 1];
+      const unsigned long long c0 = e_0 ? tk_entry(sc[ul * TK_SCLD + lane], (uint32_t)v0 + lane) : 0ull;
+      const unsigned long long c1 = e_1 ? tk_entry(sc[ul * TK_SCLD + 64 + lane], (uint32_t)v0 + 64 + lane) : 0ull;
+      unsigned long long m0 = __ballot(c0 > thr), m1 = __ballot(c1 > thr);
+      if (!(m0 | m1)) continue;
+      const int n = xn[ul];
+      for (int base = 0; base < n; base += 64) {       // excluded rows inside this tile lose their bit
+        const int i = base + lane;
+        int64_t x = -1;
+        if (i < n) x = i < TK_XCAP ? (int64_t)xl[ul * TK_XCAP + i] : A.excl_idx[xs[ul] + i];
+        const int64_t rel64 = x - v0;
+        const bool inr = x >= 0 && rel64 >= 0 && rel64 < TK_BV;
+        const int rel = inr ? (int)rel64 : 0;
+        unsigned long long hit = __ballot(inr);
+        while (hit) {
+          const int b = __ffsll((long long)hit) - 1;
+          hit &= hit - 1;
+          const int r = __shfl(rel, b, 64);
+          if (r < 64)
+            m0 &= ~(1ull << r);
+          else
+            m1 &= ~(1ull << (r - 64));
+        }
+      }
+      if (!(m0 | m1)) continue;
+      TkList S;
+      S.e0 = lane < k ? L[lane] : 0ull;
+      S.e1 = lane + 64 < k ? L[lane + 64] : 0ull;
+      bool changed = S.take(c0, m0, k, lane, nan);
+      changed |= S.take(c1, m1 & __ballot(c1 > S.kth(k)), k, lane, nan);
+      if (changed) {
+        if (lane < k) L[lane] = S.e0;
+        if (lane + 64 < k) L[lane + 64] = S.e1;
+        tk_wave_sync();
+      }
+    }
+    __syncthreads();                                  // the score tile and `el` are free for the next tile's operands
+  }
+
+  if (nan && lane == 0) atomicOr(A.status, NRL_TOPK_E_NAN);
+  tk_wave_sync();
+  for (int uu = 0; uu < TK_USERS_PER_WAVE; ++uu) {
+    const int ul = wave * TK_USERS_PER_WAVE + uu;
+    if (u0 + ul >= A.B) break;
+    unsigned long long* P = A.partial + ((u0 + ul) * A.slices + sl) * k;
+    for (int p = lane; p < k; p += 64) P[p] = lists[ul * k + p];
+  }
+}
+
+// one wave per user: status flags, merge of the user's partial lists, output
+__global__ __launch_bounds__(64) void tk_merge_kernel(TkArgs A) {
+  const int64_t u = blockIdx.x;
+  const int lane = threadIdx.x, k = A.k;
+  int64_t s, n;
+  const bool ok = tk_excl_range(A, u, s, n);
+  TkList S;
+  S.e0 = S.e1 = 0ull;
+  if (!ok) {
+    if (lane == 0) atomicOr(A.status, NRL_TOPK_E_OFFSETS);
+  } else {
+    int bad = 0;
+    for (int64_t i = lane; i < n; i += 64) {
+      const int64_t x = A.excl_idx[s + i];
+      bad |= (x < 0 || x >= A.V);
+    }
+    if (__ballot(bad) && lane == 0) atomicOr(A.status, NRL_TOPK_E_EXCLUDE);
+    const unsigned long long* P = A.partial + u * A.slices * k;
+    const int64_t total = (int64_t)A.slices * k;
+    bool nan = false;
+    for (int64_t base = 0; base < total; base += 64) {
+      const unsigned long long c = base + lane < total ? P[base + lane] : 0ull;
+      const unsigned long long m = __ballot(c > S.kth(k));
+      if (m) S.take(c, m, k, lane, nan);
+    }
+  }
+  for (int p = lane; p < k; p += 64) {
+    const unsigned long long e = p < 64 ? S.e0 : S.e1;
+    A.out_idx[u * k + p] = e ? (int64_t)(uint32_t)~(uint32_t)e : -1;
+    A.out_score[u * k + p] = e ? tk_unkey((uint32_t)(e >> 32)) : -INFINITY;
+  }
+}
+
+static bool tk_shape_ok(int64_t B, int64_t V, int32_t D, int32_t k) {
+  return B >= 0 && V >= 0 && V < ((int64_t)1 << 31) && D > 0 && D % 4 == 0 && D <= NRL_TOPK_MAX_D && k >= 1 && k <= NRL_TOPK_MAX_K;
+}
+
+// how many pieces of V run in parallel per user tile (`lists`: what the workspace is sized for) and the table tiles of each
+static void tk_plan(int64_t B, int64_t V, int32_t slices, int64_t& lists, int64_t& used, int64_t& tiles_per_slice) {
+  const int64_t nvt = ceil_div(V, TK_BV), ut = ceil_div(B, TK_BU);
+  int64_t want = slices > 0 ? slices : ceil_div(TK_TARGET_BLOCKS, ut > 0 ? ut : 1);
+  if (want > nvt) want = nvt;
+  if (want < 1) want = 1;
+  lists = want;
+  tiles_per_slice = nvt > 0 ? ceil_div(nvt, want) : 1;
+  used = nvt > 0 ? ceil_div(nvt, tiles_per_slice) : 0;
+}
+
+}  // namespace nrl
+
+using namespace nrl;
+
+extern "C" {
+
+size_t nrl_topk_scores_workspace_bytes(int64_t B, int64_t V, int32_t D, int32_t k, int32_t slices) {
+  if (!tk_shape_ok(B, V, D, k) || slices < 0) return 256;
+  int64_t lists, used, tps;
+  tk_plan(B, V, slices, lists, used, tps);
+  const size_t bytes = (size_t)B * (size_t)lists * (size_t)k * sizeof(unsigned long long);
+  return align_up(bytes > 0 ? bytes : 1, 256);
+}
+
+int nrl_topk_scores(const float* user_vec, const float* table, int64_t B, int64_t V, int32_t D, int32_t k, const int64_t* excl_idx,
+                    const int64_t* excl_off, const uint8_t* eligible, int32_t slices, int64_t* out_idx, float* out_score,
+                    int32_t* status, void* ws, size_t ws_bytes, void* stream) {
+  NRL_REQUIRE(B >= 0 && V >= 0 && D >= 0 && slices >= 0, "topk_scores: negative size");
+  NRL_REQUIRE(k >= 1 && k <= NRL_TOPK_MAX_K, "topk_scores: k in [1, %d] (got %d)", NRL_TOPK_MAX_K, k);
+  NRL_REQUIRE(D > 0 && D % 4 == 0 && D <= NRL_TOPK_MAX_D, "topk_scores: D a multiple of 4 in [4, %d] (got %d)", NRL_TOPK_MAX_D, D);
+  NRL_REQUIRE(V < ((int64_t)1 << 31), "topk_scores: at most 2^31 - 1 table rows (got %lld)", (long long)V);
+  NRL_REQUIRE(B < ((int64_t)1 << 31), "topk_scores: at most 2^31 - 1 users per call (got %lld)", (long long)B);
+  NRL_REQUIRE(status, "topk_scores: the status word is required");
+  NRL_REQUIRE((excl_idx == nullptr) == (excl_off == nullptr) || excl_off, "topk_scores: excl_idx without excl_off");
+  if (B == 0) return NRL_OK;
+  NRL_REQUIRE(out_idx && out_score && user_vec && (V == 0 || table), "topk_scores: null argument");
+  NRL_REQUIRE(ws && ((uintptr_t)ws & 255) == 0, "topk_scores: workspace null or not 256-byte aligned");
+  const size_t need = nrl_topk_scores_workspace_bytes(B, V, D, k, slices);
+  if (ws_bytes < need) {
+    set_error("workspace too small: %zu < %zu bytes", ws_bytes, need);
+    return NRL_E_WORKSPACE;
+  }
+  int64_t lists, used, tps;
+  tk_plan(B, V, slices, lists, used, tps);
+  const int64_t blocks = ceil_div(B, TK_BU) * used;
+  NRL_REQUIRE(blocks < ((int64_t)1 << 31), "topk_scores: grid too large (%lld workgroups)", (long long)blocks);
+
+  TkArgs A;
+  A.user = user_vec;
+  A.table = table;
+  A.B = B;
+  A.V = (int32_t)V;
+  A.D = D;
+  A.k = k;
+  A.excl_idx = excl_idx;
+  A.excl_off = excl_off;
+  A.eligible = eligible;
+  A.slices = (int32_t)used;
+  A.tiles_per_slice = (int32_t)tps;
+  A.partial = (unsigned long long*)ws;
+  A.out_idx = out_idx;
+  A.out_score = out_score;
+  A.status = status;
+  hipStream_t st = (hipStream_t)stream;
+  if (used > 0) {
+    const size_t smem = TK_LDS_FIXED + (size_t)TK_BU * k * sizeof(unsigned long long);      // 50 KB + 512 B per k: two workgroups per CU up to k = 60
+    // more than 64 KB of dynamic LDS (k > 28) needs the attribute; it belongs to the current device, so it is set per call
+    if (smem > 64 * 1024)
+      NRL_HIP(hipFuncSetAttribute((const void*)tk_scores_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    tk_scores_kernel<<<(unsigned)blocks, TK_THREADS, smem, st>>>(A);
+    NRL_LAUNCH_CHECK();
+  }
+  tk_merge_kernel<<<(unsigned)B, 64, 0, st>>>(A);
+  NRL_LAUNCH_CHECK();
+  return NRL_OK;
+}
+
+}  // extern "C"

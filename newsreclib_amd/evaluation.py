@@ -160,6 +160,56 @@ class NewsVectorCache:
         self.module.train(was_training)
         return out
 
+    def _user_meta(self, hist_sizes: torch.Tensor, user_idx: Optional[torch.Tensor]) -> Dict:
+        """The history half of ``_meta`` from HOST sizes: maxima and offsets are computed on the host and copied over, so nothing
+        is read back from the device (``_meta`` reads the longest list back)."""
+        dev = self.table.device
+        hs = hist_sizes.detach().cpu().long()               # (a device tensor here costs the one read-back this avoids)
+        B = int(hs.numel())
+        ar = torch.arange(B, device=dev)
+
+        def up(t):                                          # host -> device through pinned memory: the host does not wait
+            return t if t.is_cuda else t.pin_memory().to(dev, non_blocking=True)
+
+        both = up(torch.cat([hs, torch.zeros(1, dtype=torch.int64), torch.cumsum(hs, 0)]))
+        return {
+            "batch_size": B, "hist_sizes": both[:B], "batch_hist": torch.repeat_interleave(ar, both[:B], output_size=int(hs.sum())),
+            "hist_offsets": both[B:], "max_hist": int(hs.max()) if B else 0, "min_hist": int(hs.min()) if B else 0,
+            "user_idx": up(user_idx) if user_idx is not None else ar.clone(),
+        }
+
+    @torch.no_grad()
+    def recommend(self, hist_idx: torch.Tensor, hist_sizes: torch.Tensor, k: int, user_idx: Optional[torch.Tensor] = None,
+                  exclude_history: bool = True, eligible: Optional[torch.Tensor] = None):
+        """The ``k`` news of the WHOLE table each user scores highest -> (news_idx (B, k) int64, scores (B, k) fp32, status):
+        the module's ``user_vectors`` over the gathered history vectors (eval mode, restored afterwards), then
+        ``ops.topk_scores`` against the cached table with the history as the exclusion list (``exclude_history``) and
+        ``eligible`` (num_news, uint8 / bool: 0 = never recommended, e.g. the padding row 0).  Slots beyond the rows that
+        qualify hold ``-1`` / ``-inf``; ``status`` (``ops.TOPK_FLAGS``) stays on the device.  ``hist_idx`` is a GPU tensor (the
+        library has no CPU path), ``hist_sizes`` a HOST tensor as ``evaluate_impressions`` builds it: nothing is read back."""
+        if not getattr(self.module, "dot_product_scorer", False):
+            raise NotImplementedError(
+                f"{type(self.module).__name__} does not score a news by one dot product with a candidate-independent user vector "
+                "(no `dot_product_scorer`): its user representation or its predictor depends on the candidate (MINER's "
+                "poly-attention scores, CAUM's candidate-aware encoder, DKN's attention + DNN, SentiDebias' generator), so "
+                "the whole table cannot be ranked by one GEMM + top-k")
+        if not hist_idx.is_cuda:
+            raise RuntimeError(f"newsreclib_amd: `hist_idx` must live on the GPU (got {hist_idx.device}); there is no CPU path")
+        if self.vectors is None:
+            self.build()
+        dev = self.table.device
+        hist_idx = hist_idx.to(dev).long()
+        meta = self._user_meta(hist_sizes, user_idx)
+        hv = ops.embedding_gather(self.vectors, hist_idx.reshape(-1, 1)).reshape(-1, self.vectors.shape[1])
+        was_training = self.module.training
+        self.module.eval()
+        try:
+            user = self.module.user_vectors(hv, meta)
+        finally:
+            self.module.train(was_training)
+        excl = (hist_idx, meta["hist_offsets"]) if exclude_history else (None, None)
+        return ops.topk_scores(user, self.vectors, k, excl[0], excl[1], eligible.to(dev) if eligible is not None else None)
+
     @torch.no_grad()
     def model_step(self, hist_idx, hist_sizes, cand_idx, cand_sizes, labels, user_idx=None, user_ids=None):
         """The tuple ``model_step`` returns (loss, preds, targets, cand_news_size, hist_news_size, aspects ...)
@@ -219,6 +269,11 @@ class MannerVectorCache:
         cand_off = torch.cat([zero, torch.cumsum(cand_sizes.to(dev).long(), 0)])
         return manner_scores(self.vectors, self.weights, hist_idx.to(dev).long(), hist_off, cand_idx.to(dev).long(), cand_off,
                              max_cand)
+
+    def recommend(self, *args, **kwargs):
+        raise NotImplementedError("MANNeR z-scores every sub-model's scores within an impression's own candidate list "
+                                  "(manner_module.py: the ensemble of standardised scores): without a candidate list there is no "
+                                  "score to rank the whole table by; recommend from one sub-model's NewsVectorCache instead")
 
     @torch.no_grad()
     def model_step(self, hist_idx, hist_sizes, cand_idx, cand_sizes, labels, user_idx=None, user_ids=None):
@@ -301,6 +356,11 @@ class NpaFeatureCache:
         return npa_cached_scores(self.features, hist_idx.to(dev).long(), hist_off, cand_idx.to(dev).long(), cand_off, q_hist,
                                  q_cand, q_news, max_hist, max_cand)
 
+    def recommend(self, *args, **kwargs):
+        raise NotImplementedError("NPA's news vectors depend on the user (personalized attention pooling, text.py:385-390): there "
+                                  "is no (V, D) table to rank with one user vector, so the whole catalogue cannot be scored by "
+                                  "one GEMM + top-k")
+
     @torch.no_grad()
     def model_step(self, hist_idx, hist_sizes, cand_idx, cand_sizes, labels, user_idx=None, user_ids=None):
         """The 11-tuple of ``NewsVectorCache.model_step`` (loss from ``module._loss``), so ``evaluate_impressions`` applies."""
@@ -358,3 +418,40 @@ def evaluate_impressions(cache: NewsVectorCache, impressions: Sequence[Dict], ba
         if ncls and cat(tj).numel() and cat(hj).numel():
             logs.update(aspect_metrics(cat(1), cat(tj), cat(hj), cat(3), cat(4), ncls, top_k_list, prefix=name))
     return logs
+
+
+def format_recommendations(user_ids: Sequence, news_idx: torch.Tensor, scores: torch.Tensor,
+                           news_ids: Optional[torch.Tensor] = None) -> Dict[str, Dict[str, float]]:
+    """Host tensors (B, k) of ``recommend`` -> the reference's recommendation dictionary ``{"U<user id>": {"N<news id>": score}}``
+    (``AbstractRecommender._get_recommendations``; ``_save_recommendations`` writes it unchanged).  ``news_ids`` (num_news) maps
+    a table row to its news id, the row number stands in without it; slots with index ``-1`` are left out."""
+    out: Dict[str, Dict[str, float]] = {}
+    for uid, rows, vals in zip(user_ids, news_idx.tolist(), scores.tolist()):
+        out["U" + str(int(uid))] = {"N" + str(int(news_ids[r]) if news_ids is not None else r): float(v)
+                                    for r, v in zip(rows, vals) if r >= 0}
+    return out
+
+
+def recommend_users(cache: NewsVectorCache, users: Sequence[Dict], k: int, batch_size: int = 512,
+                    eligible: Optional[torch.Tensor] = None) -> Dict[str, Dict[str, float]]:
+    """``cache.recommend`` over a list of users ({"hist": idx tensor[, "user_idx", "user_id"]}) in batches -> the recommendation
+    dictionary of ``format_recommendations``.  ``user_id`` defaults to the user's position in the list + 1 (as ``build_batch``);
+    news ids come from the table's ``news_ids`` column when it has one.  One device-to-host copy per batch, at its end; a status
+    flag of the batch (``ops.TOPK_FLAGS``: each is handled by the kernel) is passed on as a warning."""
+    dev = cache.table.device
+    news_ids = cache.table.attrs["news_ids"].cpu() if "news_ids" in cache.table.attrs else None
+    out: Dict[str, Dict[str, float]] = {}
+    for lo in range(0, len(users), batch_size):
+        chunk = users[lo:lo + batch_size]
+        hs = torch.tensor([len(u["hist"]) for u in chunk])
+        hist = torch.cat([torch.as_tensor(u["hist"]).long() for u in chunk]).to(dev)
+        uidx = torch.stack([torch.as_tensor(u["user_idx"]) for u in chunk]) if "user_idx" in chunk[0] else None
+        idx, score, status = cache.recommend(hist, hs, k, user_idx=uidx, eligible=eligible)
+        packed = torch.cat([idx.double(), score.double(), status.double().expand(idx.shape[0], 1)], dim=1).cpu()      # the one copy
+        word = int(packed[0, -1]) if packed.shape[0] else 0
+        if word:                                            # the kernel has dealt with each of these; the caller should know
+            import warnings
+            warnings.warn("recommend_users: " + "; ".join(msg for bit, msg in ops.TOPK_FLAGS.items() if word & bit))
+        ids = [int(u["user_id"]) if "user_id" in u else lo + j + 1 for j, u in enumerate(chunk)]
+        out.update(format_recommendations(ids, packed[:, :k].long(), packed[:, k:2 * k].float(), news_ids))
+    return out

@@ -23,6 +23,8 @@ from .user_encoder_lstur import UserEncoder
 
 
 class LSTURModule(AbstractRecommender):
+    dot_product_scorer = True                # score = user_vectors(...) . news vector (evaluation.NewsVectorCache.recommend)
+
     def __init__(
         self,
         dataset_attributes: List[str],
@@ -112,15 +114,20 @@ class LSTURModule(AbstractRecommender):
                            seed: Optional[int] = None) -> torch.Tensor:
         """lstur_module.py:280-303 from already-encoded news rows (see ``evaluation.NewsVectorCache``)."""
         B = batch["batch_size"]
-        hist_news_vector_agg = dense_rows(hist_news_vector, batch["batch_hist"], B,
-                                                 batch["max_hist"], batch["hist_offsets"])
+        user_vector = self.user_vectors(hist_news_vector, batch, seed=seed)
         cand_news_vector_agg = dense_rows(cand_news_vector, batch["batch_cand"], B,
                                                  batch["max_cand"], batch["cand_offsets"])
-        hist_size = batch["hist_sizes"]               # == mask_hist row sums (lstur_module.py:287-290)
-        if not self.hparams.late_fusion:
-            user_vector = self.user_encoder(batch["user_idx"], hist_news_vector_agg, hist_size, seed=seed,
-                                            min_hist_size=batch["min_hist"])
-        else:                                         # lstur_module.py:295-296
-            user_vector = ops.HistMeanFn.apply(hist_news_vector_agg, batch["hist_offsets"])
         scores = self.click_predictor(user_vector.unsqueeze(dim=1), cand_news_vector_agg.permute(0, 2, 1))
         return scores
+
+    def user_vectors(self, hist_news_vector: torch.Tensor, batch: Dict, seed: Optional[int] = None) -> torch.Tensor:
+        """The candidate-independent half of ``score_news_vectors``: dense history rows, then the user encoder (or the history
+        mean under late fusion) -> (B, D).  The score of any news is one dot product with it (``dot_product_scorer``), which is
+        what ``evaluation.NewsVectorCache.recommend`` ranks the whole table by."""
+        hist_news_vector_agg = dense_rows(hist_news_vector, batch["batch_hist"], batch["batch_size"],
+                                                 batch["max_hist"], batch["hist_offsets"])
+        hist_size = batch["hist_sizes"]               # == mask_hist row sums (lstur_module.py:287-290)
+        if not self.hparams.late_fusion:
+            return self.user_encoder(batch["user_idx"], hist_news_vector_agg, hist_size, seed=seed,
+                                     min_hist_size=batch["min_hist"])
+        return ops.HistMeanFn.apply(hist_news_vector_agg, batch["hist_offsets"])      # lstur_module.py:295-296

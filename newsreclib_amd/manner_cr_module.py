@@ -66,6 +66,8 @@ def load_module_from_checkpoint(cls, checkpoint_path: str, map_location="cpu", s
 
 
 class CRModule(AbstractRecommender):
+    dot_product_scorer = True                # score = user_vectors(...) . news vector (evaluation.NewsVectorCache.recommend)
+
     def __init__(
         self,
         dataset_attributes: List[str],
@@ -130,10 +132,16 @@ class CRModule(AbstractRecommender):
     def score_news_vectors(self, hist_news_vector: torch.Tensor, cand_news_vector: torch.Tensor, batch: Dict) -> torch.Tensor:
         """manner_cr_module.py:232-254 from already-encoded news rows (``evaluation.NewsVectorCache``)."""
         B = batch["batch_size"]
-        hist_agg = dense_rows(hist_news_vector, batch["batch_hist"], B, batch["max_hist"], batch["hist_offsets"], max_is_exact=True)
+        user_vector = self.user_vectors(hist_news_vector, batch)
         cand_agg = dense_rows(cand_news_vector, batch["batch_cand"], B, batch["max_cand"], batch["cand_offsets"], max_is_exact=True)
-        if not self.hparams.late_fusion:
-            user_vector = self.user_encoder(hist_agg)
-        else:
-            user_vector = ops.HistMeanFn.apply(hist_agg, batch["hist_offsets"])
         return self.click_predictor(user_vector.unsqueeze(dim=1), cand_agg.permute(0, 2, 1))
+
+    def user_vectors(self, hist_news_vector: torch.Tensor, batch: Dict) -> torch.Tensor:
+        """The candidate-independent half of ``score_news_vectors``: dense history rows, then the user encoder (or the history
+        mean under late fusion) -> (B, D).  The score of any news is one dot product with it (``dot_product_scorer``), which is
+        what ``evaluation.NewsVectorCache.recommend`` ranks the whole table by."""
+        hist_agg = dense_rows(hist_news_vector, batch["batch_hist"], batch["batch_size"], batch["max_hist"], batch["hist_offsets"],
+                              max_is_exact=True)
+        if not self.hparams.late_fusion:
+            return self.user_encoder(hist_agg)
+        return ops.HistMeanFn.apply(hist_agg, batch["hist_offsets"])

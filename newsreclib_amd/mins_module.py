@@ -21,6 +21,8 @@ from .user_encoder_mins import UserEncoder
 
 
 class MINSModule(AbstractRecommender):
+    dot_product_scorer = True                # score = user_vectors(...) . news vector (evaluation.NewsVectorCache.recommend)
+
     def __init__(
         self,
         dataset_attributes: List[str],
@@ -97,14 +99,19 @@ class MINSModule(AbstractRecommender):
     def score_news_vectors(self, hist_news_vector: torch.Tensor, cand_news_vector: torch.Tensor,
                            batch: Dict) -> torch.Tensor:
         B = batch["batch_size"]
-        hist_news_vector_agg = dense_rows(hist_news_vector, batch["batch_hist"], B,
-                                                 batch["max_hist"], batch["hist_offsets"])
+        user_vector = self.user_vectors(hist_news_vector, batch)
         cand_news_vector_agg = dense_rows(cand_news_vector, batch["batch_cand"], B,
                                                  batch["max_cand"], batch["cand_offsets"])
+        return self.click_predictor(user_vector.unsqueeze(dim=1), cand_news_vector_agg.permute(0, 2, 1))
+
+    def user_vectors(self, hist_news_vector: torch.Tensor, batch: Dict) -> torch.Tensor:
+        """The candidate-independent half of ``score_news_vectors``: dense history rows, then the user encoder (or the history
+        mean under late fusion) -> (B, D).  The score of any news is one dot product with it (``dot_product_scorer``), which is
+        what ``evaluation.NewsVectorCache.recommend`` ranks the whole table by."""
+        hist_news_vector_agg = dense_rows(hist_news_vector, batch["batch_hist"], batch["batch_size"],
+                                                 batch["max_hist"], batch["hist_offsets"])
         if not self.hparams.late_fusion:
             if batch["min_hist"] < 1:
                 raise RuntimeError("Length of all samples has to be greater than 0")   # pack_padded_sequence's check
-            user_vector = self.user_encoder(hist_news_vector_agg, batch["hist_sizes"])
-        else:
-            user_vector = ops.HistMeanFn.apply(hist_news_vector_agg, batch["hist_offsets"])
-        return self.click_predictor(user_vector.unsqueeze(dim=1), cand_news_vector_agg.permute(0, 2, 1))
+            return self.user_encoder(hist_news_vector_agg, batch["hist_sizes"])
+        return ops.HistMeanFn.apply(hist_news_vector_agg, batch["hist_offsets"])

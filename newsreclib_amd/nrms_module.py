@@ -101,6 +101,8 @@ def prepare_batch(batch: Dict, vocab: Optional[int] = None, need_order: Optional
 
 
 class NRMSModule(AbstractRecommender):
+    dot_product_scorer = True                # score = user_vectors(...) . news vector (evaluation.NewsVectorCache.recommend)
+
     def __init__(
         self,
         dataset_attributes: List[str],
@@ -193,13 +195,19 @@ class NRMSModule(AbstractRecommender):
         """nrms_module.py:233-253 from already-encoded news rows (also the entry of the evaluation path that
         encodes every unique news once, ``evaluation.NewsVectorCache``)."""
         B = batch["batch_size"]
-        hist_news_vector_agg = dense_rows(hist_news_vector, batch["batch_hist"], B,
-                                          batch["max_hist"], batch["hist_offsets"], max_is_exact=True)
+        user_vector = self.user_vectors(hist_news_vector, batch)
         cand_news_vector_agg = dense_rows(cand_news_vector, batch["batch_cand"], B,
                                           batch["max_cand"], batch["cand_offsets"], max_is_exact=True)
-        if not self.hparams.late_fusion:
-            user_vector = self.user_encoder(hist_news_vector_agg)
-        else:  # aggregate embeddings of clicked news (nrms_module.py:243-248)
-            user_vector = ops.HistMeanFn.apply(hist_news_vector_agg, batch["hist_offsets"])
         scores = self.click_predictor(user_vector.unsqueeze(dim=1), cand_news_vector_agg.permute(0, 2, 1))
         return scores
+
+    def user_vectors(self, hist_news_vector: torch.Tensor, batch: Dict) -> torch.Tensor:
+        """The candidate-independent half of ``score_news_vectors``: dense history rows, then the user encoder (or the history
+        mean under late fusion) -> (B, D).  The score of any news is one dot product with it (``dot_product_scorer``), which is
+        what ``evaluation.NewsVectorCache.recommend`` ranks the whole table by."""
+        hist_news_vector_agg = dense_rows(hist_news_vector, batch["batch_hist"], batch["batch_size"],
+                                          batch["max_hist"], batch["hist_offsets"], max_is_exact=True)
+        if not self.hparams.late_fusion:
+            return self.user_encoder(hist_news_vector_agg)
+        # aggregate embeddings of clicked news (nrms_module.py:243-248)
+        return ops.HistMeanFn.apply(hist_news_vector_agg, batch["hist_offsets"])

@@ -704,3 +704,50 @@ def impression_metrics(preds: torch.Tensor, targets: torch.Tensor, cand_offsets:
                                           n_hist, ks, len(top_k), ptr(rank), ptr(rows), ptr(sums), ptr(count), status.data_ptr(),
                                           ws.data_ptr(), ws.numel(), _stream()), "nrl_impression_metrics")
     return rank, rows, status
+
+
+# ---- full-catalogue top-k recommendation (nrl_topk.hip) ------------------------------------------------------------------------
+TOPK_MAX_K, TOPK_MAX_D = 128, 1024
+TOPK_FLAGS = {1: "an exclusion index is outside [0, V) (ignored)",
+              2: "excl_off decreases or leaves its range (that user's row is all -1 / -inf)",
+              4: "a NaN score of an eligible, not excluded row (that row is left out for that user)"}
+
+
+def topk_scores(user_vec: torch.Tensor, table: torch.Tensor, k: int, excl_idx: Optional[torch.Tensor] = None,
+                excl_off: Optional[torch.Tensor] = None, eligible: Optional[torch.Tensor] = None, slices: int = 0):
+    """``nrl_topk_scores``: for each row of ``user_vec`` (B, D) the ``k`` rows of ``table`` (V, D) of highest dot product ->
+    (idx (B, k) int64, score (B, k) fp32, status (1) int32), score descending, equal scores by ascending row, ``-1`` / ``-inf``
+    where fewer than ``k`` rows qualify.  ``excl_idx`` (int64) / ``excl_off`` (B + 1 int64): ragged per-user rows that are never
+    returned (the history); ``eligible`` (V uint8 or bool): 0 = never returned for anyone.  The (B, V) score matrix is never
+    materialised.  ``status`` (``TOPK_FLAGS``) stays on the device and must be read by the caller -- nothing here synchronises
+    with the host."""
+    lib = _lib.load()
+    user_vec, table = _chk(user_vec, torch.float32, "user_vec"), _chk(table, torch.float32, "table")
+    if user_vec.dim() != 2 or table.dim() != 2 or user_vec.shape[1] != table.shape[1]:
+        raise ValueError(f"newsreclib_amd: user_vec (B, D) and table (V, D) expected, got {tuple(user_vec.shape)} and "
+                         f"{tuple(table.shape)}")
+    B, D, V, k = int(user_vec.shape[0]), int(user_vec.shape[1]), int(table.shape[0]), int(k)
+    if (excl_idx is None) != (excl_off is None):
+        raise ValueError("newsreclib_amd: excl_idx and excl_off go together")
+    if excl_idx is not None:
+        excl_idx, excl_off = _chk(excl_idx, torch.int64, "excl_idx"), _chk(excl_off, torch.int64, "excl_off")
+        if excl_off.numel() != B + 1:
+            raise ValueError("newsreclib_amd: excl_off must have B + 1 entries")
+        # the kernel trusts excl_off[B] as the length of excl_idx: an offset beyond the list is turned into one it rejects
+        excl_off = torch.where(excl_off > excl_idx.numel(), torch.full_like(excl_off, -1), excl_off)
+    if eligible is not None:
+        if eligible.dtype == torch.bool and eligible.is_cuda:
+            eligible = eligible.to(torch.uint8)
+        eligible = _chk(eligible, torch.uint8, "eligible")
+        if eligible.numel() != V:
+            raise ValueError("newsreclib_amd: eligible must have one entry per table row")
+    dev = user_vec.device
+    idx = torch.empty((B, max(k, 0)), dtype=torch.int64, device=dev)
+    score = torch.empty((B, max(k, 0)), dtype=torch.float32, device=dev)
+    status = torch.zeros(1, dtype=torch.int32, device=dev)
+    ws = torch.empty(max(lib.nrl_topk_scores_workspace_bytes(B, V, D, k, int(slices)), 256), dtype=torch.uint8, device=dev)
+    ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
+    _lib.check(lib.nrl_topk_scores(user_vec.data_ptr(), table.data_ptr(), B, V, D, k, ptr(excl_idx), ptr(excl_off), ptr(eligible),
+                                   int(slices), idx.data_ptr(), score.data_ptr(), status.data_ptr(), ws.data_ptr(), ws.numel(),
+                                   _stream()), "nrl_topk_scores")
+    return idx, score, status
