@@ -4,6 +4,7 @@
 lstur_module.py:308-410 -- identical apart from the class name)."""
 from __future__ import annotations
 
+import contextlib
 import json
 from typing import Any, Dict, List, Tuple
 
@@ -15,6 +16,7 @@ from ._lightning import LightningModuleBase
 from . import ops
 from .dense_batch import dense_rows
 from .metrics import StreamingMetrics, aspect_metrics, ranking_metrics
+from .news_encoder import token_tables
 
 
 STEP_OUTPUT_NAMES = ("loss", "preds", "targets", "cand_news_size", "hist_news_size", "target_categories", "target_sentiments",
@@ -274,21 +276,13 @@ class AbstractRecommender(LightningModuleBase):
     # -- evaluation epochs (nrms_module.py:398-535) run under frozen weights: every ``MHSAAddAtt`` text encoder serves its forwards
     #    from ONE per-token q|k|v table for the length of the epoch (news_encoder.MHSAAddAtt.token_table; results torch.equal) ----
     def _token_tables(self, enter: bool) -> None:
-        import contextlib
         stack = getattr(self, "_tt_stack", None)
         if stack is not None:
             stack.close()
             self._tt_stack = None
-        if not enter:
-            return
-        stack = contextlib.ExitStack()
-        seen = set()
-        enc = getattr(self, "news_encoder", None)
-        for te in (getattr(enc, "text_encoders", {}) or {}).values():
-            if hasattr(te, "token_table") and id(te) not in seen:
-                seen.add(id(te))
-                stack.enter_context(te.token_table())
-        self._tt_stack = stack
+        if enter:
+            self._tt_stack = contextlib.ExitStack()
+            self._tt_stack.enter_context(token_tables(getattr(self, "news_encoder", None)))
 
     def on_validation_epoch_start(self) -> None:
         self._token_tables(True)

@@ -22,16 +22,36 @@ Everything runs through the same C-ABI kernels; nothing here is a second impleme
 """
 from __future__ import annotations
 
+import contextlib
 from typing import Dict, Optional, Sequence
 
 import torch
 
 from . import ops
 from .dense_batch import dense_rows
+from .news_encoder import token_tables
 from .nrms_module import prepare_batch
 
 TEXT_ATTRS = ("title", "abstract")
 ASPECT_ATTRS = ("category", "subcategory", "sentiment")
+
+
+@contextlib.contextmanager
+def eval_mode(module):
+    """``module`` in eval mode for the scope, back in the mode it was in afterwards -- also when the scope raises (a module left
+    in eval mode trains on without dropout and nothing reports it)."""
+    was_training = module.training
+    module.eval()
+    try:
+        yield module
+    finally:
+        module.train(was_training)
+
+
+def ragged_offsets(sizes: torch.Tensor, device) -> torch.Tensor:
+    """(B) list lengths -> (B + 1) int64 start offsets on ``device``."""
+    sizes = sizes.to(device).long()
+    return torch.cat([sizes.new_zeros(1), torch.cumsum(sizes, 0)])
 
 
 def _map_rows(v, fn):
@@ -83,7 +103,53 @@ class DeviceNewsTable:
         return batch
 
 
-class NewsVectorCache:
+class _ImpressionCache:
+    """What the encode-once caches share: the batch metadata of a list of impressions given by news indices, and the
+    ``model_step`` tuple over the cache's own ``scores`` (``self.module`` / ``self.table`` are the subclass's)."""
+    user_idx_reason: Optional[str] = None       # why ``model_step`` cannot do without ``user_idx``, where it cannot (NPA)
+
+    def _meta(self, hist_sizes, cand_sizes, labels, user_idx, user_ids) -> Dict:
+        dev = self.table.device
+        hist_sizes, cand_sizes = hist_sizes.to(dev).long(), cand_sizes.to(dev).long()
+        B = int(hist_sizes.numel())
+        ar = torch.arange(B, device=dev)
+        meta = {
+            "x_hist": {}, "x_cand": {},
+            "batch_hist": torch.repeat_interleave(ar, hist_sizes), "batch_cand": torch.repeat_interleave(ar, cand_sizes),
+            "labels": labels.to(dev).float() if labels is not None else None,
+            "user_idx": user_idx.to(dev) if user_idx is not None else ar.clone(),
+            "user_ids": user_ids.to(dev) if user_ids is not None else ar + 1,
+            "batch_size": B,
+        }
+        return prepare_batch(meta)
+
+    def _step_loss(self, scores: torch.Tensor, meta: Dict) -> torch.Tensor:
+        y_true = dense_rows(meta["labels"], meta["batch_cand"], meta["batch_size"], meta["max_cand"], meta["cand_offsets"],
+                            meta["cand_flat_idx"])
+        return self.module._loss(scores, y_true.float(), meta)
+
+    @torch.no_grad()
+    def model_step(self, hist_idx, hist_sizes, cand_idx, cand_sizes, labels, user_idx=None, user_ids=None):
+        """The tuple ``model_step`` returns (loss, preds, targets, cand_news_size, hist_news_size, aspects ...)
+        for a batch given by index lists; feeds ``test_step`` / the epoch-end metrics unchanged."""
+        if user_idx is None and self.user_idx_reason:
+            raise ValueError(f"{type(self).__name__}.model_step needs user_idx: {self.user_idx_reason}")
+        dev = self.table.device
+        scores = self.scores(hist_idx, hist_sizes, cand_idx, cand_sizes, user_idx)      # (builds the cache at its first use)
+        meta = self._meta(hist_sizes, cand_sizes, labels, user_idx, user_ids)
+        loss = self._step_loss(scores, meta)
+        preds = scores.reshape(-1)[meta["cand_flat_idx"]]
+        empty = torch.empty(0, dtype=torch.int64, device=dev)
+
+        def attr(idx, name):
+            return self.table.attrs[name].index_select(0, idx.to(dev)) if name in self.table.attrs else empty
+
+        return (loss, preds, meta["labels"], meta["cand_sizes"], meta["hist_sizes"], attr(cand_idx, "category"),
+                attr(cand_idx, "sentiment"), attr(hist_idx, "category"), attr(hist_idx, "sentiment"),
+                meta["user_ids"], cand_idx.to(dev))
+
+
+class NewsVectorCache(_ImpressionCache):
     """Encode-once evaluation of a drop-in recommender (any of the module mirrors: NRMS, LSTUR, NAML, TANR,
     CenNewsRec, MINS -- whatever exposes ``news_encoder`` and ``score_news_vectors``)."""
 
@@ -105,40 +171,18 @@ class NewsVectorCache:
                 not (text_encoders and all(getattr(t, "news_independent", False) for t in text_encoders)):
             raise NotImplementedError("the PLM text encoder attends across the news of one call (text.py:92-96): "
                                       "a news vector is not a function of the news alone and cannot be cached")
-        was_training = self.module.training
-        self.module.eval()
         names = [k for k in self.table.attrs if k in TEXT_ATTRS or k in ("category", "subcategory")]
         # encoders that read entity ids (DKN's KCNN) declare them; every other encoder's call stays as it was
         names += [k for k in getattr(enc, "entity_attrs", ()) if k in self.table.attrs and k not in names]
         out = []
-        import contextlib
-        with contextlib.ExitStack() as stack:
-            # one pass over the whole corpus under frozen weights: MHSAAddAtt text encoders run their in-projection once per
-            # VOCABULARY id instead of once per token position (news_encoder.MHSAAddAtt.token_table; same bits)
-            for te in {id(t): t for t in (getattr(enc, "text_encoders", {}) or {}).values()}.values():
-                if hasattr(te, "token_table"):
-                    stack.enter_context(te.token_table())
+        # one pass over the whole corpus under frozen weights: MHSAAddAtt text encoders run their in-projection once per
+        # VOCABULARY id instead of once per token position (news_encoder.MHSAAddAtt.token_table; same bits)
+        with eval_mode(self.module), token_tables(enc):
             for lo in range(0, self.table.num_news, self.chunk):
                 hi = min(lo + self.chunk, self.table.num_news)
                 out.append(enc({k: _map_rows(self.table.attrs[k], lambda t: t[lo:hi]) for k in names}))
         self.vectors = torch.cat(out, dim=0)
-        self.module.train(was_training)
         return self.vectors
-
-    def _meta(self, hist_sizes, cand_sizes, labels, user_idx, user_ids) -> Dict:
-        dev = self.table.device
-        hist_sizes, cand_sizes = hist_sizes.to(dev).long(), cand_sizes.to(dev).long()
-        B = int(hist_sizes.numel())
-        ar = torch.arange(B, device=dev)
-        meta = {
-            "x_hist": {}, "x_cand": {},
-            "batch_hist": torch.repeat_interleave(ar, hist_sizes), "batch_cand": torch.repeat_interleave(ar, cand_sizes),
-            "labels": labels.to(dev).float() if labels is not None else None,
-            "user_idx": user_idx.to(dev) if user_idx is not None else ar.clone(),
-            "user_ids": user_ids.to(dev) if user_ids is not None else ar + 1,
-            "batch_size": B,
-        }
-        return prepare_batch(meta)
 
     @torch.no_grad()
     def scores(self, hist_idx: torch.Tensor, hist_sizes: torch.Tensor, cand_idx: torch.Tensor,
@@ -154,11 +198,8 @@ class NewsVectorCache:
         for name in getattr(self.module, "score_news_attrs", ()):
             meta["x_hist"][name] = self.table.attrs[name].index_select(0, hist_idx.to(dev))
             meta["x_cand"][name] = self.table.attrs[name].index_select(0, cand_idx.to(dev))
-        was_training = self.module.training
-        self.module.eval()
-        out = self.module.score_news_vectors(hv, cv, meta)
-        self.module.train(was_training)
-        return out
+        with eval_mode(self.module):
+            return self.module.score_news_vectors(hv, cv, meta)
 
     def _user_meta(self, hist_sizes: torch.Tensor, user_idx: Optional[torch.Tensor]) -> Dict:
         """The history half of ``_meta`` from HOST sizes: maxima and offsets are computed on the host and copied over, so nothing
@@ -201,39 +242,13 @@ class NewsVectorCache:
         hist_idx = hist_idx.to(dev).long()
         meta = self._user_meta(hist_sizes, user_idx)
         hv = ops.embedding_gather(self.vectors, hist_idx.reshape(-1, 1)).reshape(-1, self.vectors.shape[1])
-        was_training = self.module.training
-        self.module.eval()
-        try:
+        with eval_mode(self.module):
             user = self.module.user_vectors(hv, meta)
-        finally:
-            self.module.train(was_training)
         excl = (hist_idx, meta["hist_offsets"]) if exclude_history else (None, None)
         return ops.topk_scores(user, self.vectors, k, excl[0], excl[1], eligible.to(dev) if eligible is not None else None)
 
-    @torch.no_grad()
-    def model_step(self, hist_idx, hist_sizes, cand_idx, cand_sizes, labels, user_idx=None, user_ids=None):
-        """The tuple ``model_step`` returns (loss, preds, targets, cand_news_size, hist_news_size, aspects ...)
-        for a batch given by index lists; feeds ``test_step`` / the epoch-end metrics unchanged."""
-        if self.vectors is None:
-            self.build()
-        dev = self.table.device
-        meta = self._meta(hist_sizes, cand_sizes, labels, user_idx, user_ids)
-        scores = self.scores(hist_idx, hist_sizes, cand_idx, cand_sizes, user_idx)
-        y_true = dense_rows(meta["labels"], meta["batch_cand"], meta["batch_size"], meta["max_cand"],
-                                   meta["cand_offsets"], meta["cand_flat_idx"])
-        loss = self.module._loss(scores, y_true.float(), meta)
-        preds = scores.reshape(-1)[meta["cand_flat_idx"]]
-        empty = torch.empty(0, dtype=torch.int64, device=dev)
 
-        def attr(idx, name):
-            return self.table.attrs[name].index_select(0, idx.to(dev)) if name in self.table.attrs else empty
-
-        return (loss, preds, meta["labels"], meta["cand_sizes"], meta["hist_sizes"], attr(cand_idx, "category"),
-                attr(cand_idx, "sentiment"), attr(hist_idx, "category"), attr(hist_idx, "sentiment"),
-                meta["user_ids"], cand_idx.to(dev))
-
-
-class MannerVectorCache:
+class MannerVectorCache(_ImpressionCache):
     """Encode-once evaluation of ``manner_module.MANNERModule``: one ``NewsVectorCache`` per loaded sub-model over the same
     ``DeviceNewsTable``; ``scores`` is one ``nrl_manner_scores`` launch that gathers straight from the (up to three) tables.
     ``model_step`` returns the 11-tuple ``evaluate_impressions`` consumes, with a zero tensor in the loss slot (MANNeR has no
@@ -264,36 +279,20 @@ class MannerVectorCache:
             self.build()
         dev = self.table.device
         max_cand = int(cand_sizes.max())                       # the true largest count: no impression is truncated
-        zero = torch.zeros(1, dtype=torch.int64, device=dev)
-        hist_off = torch.cat([zero, torch.cumsum(hist_sizes.to(dev).long(), 0)])
-        cand_off = torch.cat([zero, torch.cumsum(cand_sizes.to(dev).long(), 0)])
+        hist_off, cand_off = ragged_offsets(hist_sizes, dev), ragged_offsets(cand_sizes, dev)
         return manner_scores(self.vectors, self.weights, hist_idx.to(dev).long(), hist_off, cand_idx.to(dev).long(), cand_off,
                              max_cand)
+
+    def _step_loss(self, scores: torch.Tensor, meta: Dict) -> torch.Tensor:
+        return scores.new_zeros(())                            # MANNeR has no loss
 
     def recommend(self, *args, **kwargs):
         raise NotImplementedError("MANNeR z-scores every sub-model's scores within an impression's own candidate list "
                                   "(manner_module.py: the ensemble of standardised scores): without a candidate list there is no "
                                   "score to rank the whole table by; recommend from one sub-model's NewsVectorCache instead")
 
-    @torch.no_grad()
-    def model_step(self, hist_idx, hist_sizes, cand_idx, cand_sizes, labels, user_idx=None, user_ids=None):
-        if self.vectors is None:
-            self.build()
-        dev = self.table.device
-        meta = self.caches[0]._meta(hist_sizes, cand_sizes, labels, user_idx, user_ids)
-        scores = self.scores(hist_idx, hist_sizes, cand_idx, cand_sizes, user_idx)
-        preds = scores.reshape(-1)[meta["cand_flat_idx"]]
-        empty = torch.empty(0, dtype=torch.int64, device=dev)
 
-        def attr(idx, name):
-            return self.table.attrs[name].index_select(0, idx.to(dev)) if name in self.table.attrs else empty
-
-        return (scores.new_zeros(()), preds, meta["labels"], meta["cand_sizes"], meta["hist_sizes"], attr(cand_idx, "category"),
-                attr(cand_idx, "sentiment"), attr(hist_idx, "category"), attr(hist_idx, "sentiment"), meta["user_ids"],
-                cand_idx.to(dev))
-
-
-class NpaFeatureCache:
+class NpaFeatureCache(_ImpressionCache):
     """Encode-once evaluation of ``npa_module.NPAModule``.  An NPA news vector depends on the user, but in eval mode only through the
     pooling: the conv feature maps ``c = relu(cnn(embedding(title)))`` (L, F) depend on the news alone.  ``build`` runs the lookup and
     the convolution over the table once into ``features`` (num_news, L, F) fp32 (65 k news x 30 x 400: 3.1 GB); ``scores`` is the
@@ -304,6 +303,7 @@ class NpaFeatureCache:
     A SNAPSHOT of the weights at ``build()``: after they change, call ``build()`` again (nothing is keyed on them).  The feature maps
     carry the bits of the GEMM engine they were built under (``engine``); the scorer itself is engine-independent.
     ``hist_sizes`` / ``cand_sizes`` are HOST tensors, as ``evaluate_impressions`` builds them: their maxima are read on the host."""
+    user_idx_reason = "NPA's attention queries come from the user embedding"
 
     def __init__(self, module, table: DeviceNewsTable, chunk: int = 16384):
         from .npa_module import NPAModule
@@ -314,24 +314,18 @@ class NpaFeatureCache:
         self.features: Optional[torch.Tensor] = None
         self.engine: Optional[str] = None
 
-    _meta = NewsVectorCache._meta
-
     @torch.no_grad()
     def build(self) -> torch.Tensor:
         """conv feature maps (num_news, L, F) of the whole table: one allocation, filled chunk by chunk in place."""
         from . import _lib
         enc = self.module.news_encoder
         title = self.table.attrs["title"]
-        was_training = self.module.training
-        self.module.eval()
-        try:
+        with eval_mode(self.module):
             feats = torch.empty((self.table.num_news, title.shape[1], enc.cnn.out_channels), dtype=torch.float32,
                                 device=self.table.device)
             for lo in range(0, self.table.num_news, self.chunk):
                 hi = min(lo + self.chunk, self.table.num_news)
                 enc.conv_features(title[lo:hi], out=feats[lo:hi])
-        finally:
-            self.module.train(was_training)
         self.features, self.engine = feats, _lib.get_gemm_engine()
         return feats
 
@@ -341,15 +335,13 @@ class NpaFeatureCache:
         """(B, max_cand) click scores of a batch of impressions given by news-index lists; ``user_idx`` (B) is required."""
         from .ops_npa import npa_cached_scores
         if user_idx is None:
-            raise ValueError("NpaFeatureCache.scores needs user_idx: NPA's attention queries come from the user embedding")
+            raise ValueError(f"NpaFeatureCache.scores needs user_idx: {self.user_idx_reason}")
         if self.features is None:
             self.build()
         dev = self.table.device
         max_hist = int(hist_sizes.max()) if hist_sizes.numel() else 0      # host tensors: no read-back
         max_cand = int(cand_sizes.max()) if cand_sizes.numel() else 0
-        zero = torch.zeros(1, dtype=torch.int64, device=dev)
-        hist_off = torch.cat([zero, torch.cumsum(hist_sizes.to(dev).long(), 0)])
-        cand_off = torch.cat([zero, torch.cumsum(cand_sizes.to(dev).long(), 0)])
+        hist_off, cand_off = ragged_offsets(hist_sizes, dev), ragged_offsets(cand_sizes, dev)
         B = int(hist_sizes.numel())
         text_q, q_news = self.module.user_queries(user_idx.to(dev).long())      # p = 0: the forward's eval-mode queries
         q_hist, q_cand = text_q[:B], text_q[B:]
@@ -360,27 +352,6 @@ class NpaFeatureCache:
         raise NotImplementedError("NPA's news vectors depend on the user (personalized attention pooling, text.py:385-390): there "
                                   "is no (V, D) table to rank with one user vector, so the whole catalogue cannot be scored by "
                                   "one GEMM + top-k")
-
-    @torch.no_grad()
-    def model_step(self, hist_idx, hist_sizes, cand_idx, cand_sizes, labels, user_idx=None, user_ids=None):
-        """The 11-tuple of ``NewsVectorCache.model_step`` (loss from ``module._loss``), so ``evaluate_impressions`` applies."""
-        if user_idx is None:
-            raise ValueError("NpaFeatureCache.model_step needs user_idx: NPA's attention queries come from the user embedding")
-        dev = self.table.device
-        scores = self.scores(hist_idx, hist_sizes, cand_idx, cand_sizes, user_idx)
-        meta = self._meta(hist_sizes, cand_sizes, labels, user_idx, user_ids)
-        y_true = dense_rows(meta["labels"], meta["batch_cand"], meta["batch_size"], meta["max_cand"], meta["cand_offsets"],
-                            meta["cand_flat_idx"])
-        loss = self.module._loss(scores, y_true.float(), meta)
-        preds = scores.reshape(-1)[meta["cand_flat_idx"]]
-        empty = torch.empty(0, dtype=torch.int64, device=dev)
-
-        def attr(idx, name):
-            return self.table.attrs[name].index_select(0, idx.to(dev)) if name in self.table.attrs else empty
-
-        return (loss, preds, meta["labels"], meta["cand_sizes"], meta["hist_sizes"], attr(cand_idx, "category"),
-                attr(cand_idx, "sentiment"), attr(hist_idx, "category"), attr(hist_idx, "sentiment"), meta["user_ids"],
-                cand_idx.to(dev))
 
 
 def evaluate_impressions(cache: NewsVectorCache, impressions: Sequence[Dict], batch_size: int = 512,

@@ -24,12 +24,10 @@ from typing import Any, Dict, List, Optional
 
 import torch
 
-from . import ops
-from .abstract_recommender import AbstractRecommender
+from .batch_layout import prepare_batch
 from .click_predictor import DotProduct
-from .dense_batch import dense_rows
+from .dot_product_recommender import DotProductRecommender
 from .news_encoder import PLM, MHSAAddAtt, NewsEncoder, _draw_seed
-from .nrms_module import prepare_batch
 from .user_encoder import UserEncoder
 
 
@@ -65,8 +63,8 @@ def load_module_from_checkpoint(cls, checkpoint_path: str, map_location="cpu", s
     return module
 
 
-class CRModule(AbstractRecommender):
-    dot_product_scorer = True                # score = user_vectors(...) . news vector (evaluation.NewsVectorCache.recommend)
+class CRModule(DotProductRecommender):
+    dense_max_is_exact = True
 
     def __init__(
         self,
@@ -129,19 +127,5 @@ class CRModule(AbstractRecommender):
         cand_vec = self.news_encoder(batch["x_cand"], seed=seed, stream_base=4)
         return self.score_news_vectors(hist_vec, cand_vec, batch)
 
-    def score_news_vectors(self, hist_news_vector: torch.Tensor, cand_news_vector: torch.Tensor, batch: Dict) -> torch.Tensor:
-        """manner_cr_module.py:232-254 from already-encoded news rows (``evaluation.NewsVectorCache``)."""
-        B = batch["batch_size"]
-        user_vector = self.user_vectors(hist_news_vector, batch)
-        cand_agg = dense_rows(cand_news_vector, batch["batch_cand"], B, batch["max_cand"], batch["cand_offsets"], max_is_exact=True)
-        return self.click_predictor(user_vector.unsqueeze(dim=1), cand_agg.permute(0, 2, 1))
-
-    def user_vectors(self, hist_news_vector: torch.Tensor, batch: Dict) -> torch.Tensor:
-        """The candidate-independent half of ``score_news_vectors``: dense history rows, then the user encoder (or the history
-        mean under late fusion) -> (B, D).  The score of any news is one dot product with it (``dot_product_scorer``), which is
-        what ``evaluation.NewsVectorCache.recommend`` ranks the whole table by."""
-        hist_agg = dense_rows(hist_news_vector, batch["batch_hist"], batch["batch_size"], batch["max_hist"], batch["hist_offsets"],
-                              max_is_exact=True)
-        if not self.hparams.late_fusion:
-            return self.user_encoder(hist_agg)
-        return ops.HistMeanFn.apply(hist_agg, batch["hist_offsets"])
+    def _encode_user(self, hist_dense: torch.Tensor, batch: Dict, seed: Optional[int]) -> torch.Tensor:
+        return self.user_encoder(hist_dense)

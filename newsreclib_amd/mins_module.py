@@ -11,18 +11,13 @@ from typing import Any, Dict, List, Optional
 
 import torch
 
-from . import ops
-from .abstract_recommender import AbstractRecommender
 from .click_predictor import DotProduct
-from .dense_batch import dense_rows
-from .news_encoder import LinearEncoder, MHSAAddAtt, NewsEncoder, _draw_seed
-from .nrms_module import prepare_batch, text_vocab
+from .dot_product_recommender import DotProductRecommender
+from .news_encoder import LinearEncoder, MHSAAddAtt, NewsEncoder
 from .user_encoder_mins import UserEncoder
 
 
-class MINSModule(AbstractRecommender):
-    dot_product_scorer = True                # score = user_vectors(...) . news vector (evaluation.NewsVectorCache.recommend)
-
+class MINSModule(DotProductRecommender):
     def __init__(
         self,
         dataset_attributes: List[str],
@@ -85,33 +80,7 @@ class MINSModule(AbstractRecommender):
         self.click_predictor = DotProduct()
         self._init_step_outputs(outputs)
 
-    def _prepare(self, batch: Dict) -> Dict:
-        return prepare_batch(batch, text_vocab(self))
-
-    # -- reference: mins_module.py:250-279 -------------------------------------------------------------
-    def forward(self, batch: Dict, seed: Optional[int] = None) -> torch.Tensor:
-        batch = prepare_batch(batch, text_vocab(self))
-        if self.training and seed is None:
-            seed = _draw_seed()
-        hist_vec, cand_vec = self._encode_news(batch, seed)
-        return self.score_news_vectors(hist_vec, cand_vec, batch)
-
-    def score_news_vectors(self, hist_news_vector: torch.Tensor, cand_news_vector: torch.Tensor,
-                           batch: Dict) -> torch.Tensor:
-        B = batch["batch_size"]
-        user_vector = self.user_vectors(hist_news_vector, batch)
-        cand_news_vector_agg = dense_rows(cand_news_vector, batch["batch_cand"], B,
-                                                 batch["max_cand"], batch["cand_offsets"])
-        return self.click_predictor(user_vector.unsqueeze(dim=1), cand_news_vector_agg.permute(0, 2, 1))
-
-    def user_vectors(self, hist_news_vector: torch.Tensor, batch: Dict) -> torch.Tensor:
-        """The candidate-independent half of ``score_news_vectors``: dense history rows, then the user encoder (or the history
-        mean under late fusion) -> (B, D).  The score of any news is one dot product with it (``dot_product_scorer``), which is
-        what ``evaluation.NewsVectorCache.recommend`` ranks the whole table by."""
-        hist_news_vector_agg = dense_rows(hist_news_vector, batch["batch_hist"], batch["batch_size"],
-                                                 batch["max_hist"], batch["hist_offsets"])
-        if not self.hparams.late_fusion:
-            if batch["min_hist"] < 1:
-                raise RuntimeError("Length of all samples has to be greater than 0")   # pack_padded_sequence's check
-            return self.user_encoder(hist_news_vector_agg, batch["hist_sizes"])
-        return ops.HistMeanFn.apply(hist_news_vector_agg, batch["hist_offsets"])
+    def _encode_user(self, hist_dense: torch.Tensor, batch: Dict, seed: Optional[int]) -> torch.Tensor:
+        if batch["min_hist"] < 1:
+            raise RuntimeError("Length of all samples has to be greater than 0")   # pack_padded_sequence's check
+        return self.user_encoder(hist_dense, batch["hist_sizes"])

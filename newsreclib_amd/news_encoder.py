@@ -7,6 +7,7 @@ for the NRMS configuration (one text attribute) and the LSTUR one (shared text e
 abstract, category embedding, ``combine_type="concat"``).  Constructor signatures, attribute names
 and ``state_dict`` keys are the reference's.
 """
+import contextlib
 import os
 from typing import Dict, List, Optional
 
@@ -27,6 +28,17 @@ ENTITY_STREAMS = {"title_entities": 6, "abstract_entities": 8, "entities": 6}
 def _draw_seed() -> int:
     # host-side draw from torch's CPU generator (no device sync); reproducible under torch.manual_seed
     return int(torch.empty((), dtype=torch.int64).random_(0, 2 ** 62))
+
+
+@contextlib.contextmanager
+def token_tables(news_encoder):
+    """Scope of frozen weights (an evaluation epoch, one pass over the corpus): enters ``token_table()`` of every distinct text
+    encoder of ``news_encoder`` that has one (an encoder shared by title and abstract once)."""
+    encoders = {id(te): te for te in (getattr(news_encoder, "text_encoders", None) or {}).values() if hasattr(te, "token_table")}
+    with contextlib.ExitStack() as stack:
+        for te in encoders.values():
+            stack.enter_context(te.token_table())
+        yield
 
 
 def _grad_bufs(params):
@@ -88,8 +100,6 @@ class MHSAAddAtt(nn.Module):
     def token_table(self):
         """Context manager: forwards inside (eval mode, no grad) run from ONE table built at the first of them; the table is
         dropped when the outermost scope ends."""
-        import contextlib
-
         @contextlib.contextmanager
         def scope():
             prev = self._tt_pinned

@@ -13,18 +13,14 @@ from typing import Any, Dict, List, Optional
 import torch
 import torch.nn as nn
 
-from . import ops, ops_blocks
-from .abstract_recommender import AbstractRecommender
+from . import ops_blocks
 from .click_predictor import CrossEntropyLoss, DotProduct
-from .dense_batch import dense_rows
-from .news_encoder import CNNAddAtt, NewsEncoder, _draw_seed
-from .nrms_module import prepare_batch, text_vocab
+from .dot_product_recommender import DotProductRecommender
+from .news_encoder import CNNAddAtt, NewsEncoder
 from .user_encoder_naml import UserEncoder
 
 
-class TANRModule(AbstractRecommender):
-    dot_product_scorer = True                # score = user_vectors(...) . news vector (evaluation.NewsVectorCache.recommend)
-
+class TANRModule(DotProductRecommender):
     def __init__(
         self,
         dataset_attributes: List[str],
@@ -85,18 +81,11 @@ class TANRModule(AbstractRecommender):
         self.click_predictor = DotProduct()
         self._init_step_outputs(outputs)
 
-    def _prepare(self, batch: Dict) -> Dict:
-        return prepare_batch(batch, text_vocab(self))
-
     # -- reference: tanr_module.py:258-286 -------------------------------------------------------------
     def forward(self, batch: Dict, seed: Optional[int] = None):
-        batch = prepare_batch(batch, text_vocab(self))
-        if self.training and seed is None:
-            seed = _draw_seed()
-        hist_vec, cand_vec = self._encode_news(batch, seed)
+        scores, hist_vec, cand_vec = self._encode_and_score(batch, seed)
         n_hist = hist_vec.shape[0]
         news_vector = torch.cat((hist_vec, cand_vec), dim=0)              # rows: [history; candidates]
-        scores = self.score_news_vectors(hist_vec, cand_vec, batch)
         # topic scores of every encoded news.  The reference orders the rows [candidates; history]
         # (tanr_module.py:284); the loss is a mean over rows, so the order only matters for the returned tensor.
         w, b = self.topic_predictor.weight, self.topic_predictor.bias
@@ -108,25 +97,8 @@ class TANRModule(AbstractRecommender):
         topic_scores = torch.cat((topic_all[n_hist:], topic_all[:n_hist]), dim=0)
         return scores, topic_scores
 
-    def score_news_vectors(self, hist_news_vector: torch.Tensor, cand_news_vector: torch.Tensor,
-                           batch: Dict) -> torch.Tensor:
-        """User encoding + click scores from already-encoded news (tanr_module.py:262-282; also the entry of the
-        encode-once evaluation path, evaluation.NewsVectorCache)."""
-        B = batch["batch_size"]
-        user_vector = self.user_vectors(hist_news_vector, batch)
-        cand_news_vector_agg = dense_rows(cand_news_vector, batch["batch_cand"], B,
-                                                 batch["max_cand"], batch["cand_offsets"])
-        return self.click_predictor(user_vector.unsqueeze(dim=1), cand_news_vector_agg.permute(0, 2, 1))
-
-    def user_vectors(self, hist_news_vector: torch.Tensor, batch: Dict) -> torch.Tensor:
-        """The candidate-independent half of ``score_news_vectors``: dense history rows, then the user encoder (or the history
-        mean under late fusion) -> (B, D).  The score of any news is one dot product with it (``dot_product_scorer``), which is
-        what ``evaluation.NewsVectorCache.recommend`` ranks the whole table by."""
-        hist_news_vector_agg = dense_rows(hist_news_vector, batch["batch_hist"], batch["batch_size"],
-                                                 batch["max_hist"], batch["hist_offsets"])
-        if not self.hparams.late_fusion:
-            return self.user_encoder(hist_news_vector_agg)
-        return ops.HistMeanFn.apply(hist_news_vector_agg, batch["hist_offsets"])
+    def _encode_user(self, hist_dense: torch.Tensor, batch: Dict, seed: Optional[int]) -> torch.Tensor:
+        return self.user_encoder(hist_dense)
 
     # -- reference: tanr_module.py:361-367 -------------------------------------------------------------
     def _aux_loss(self, batch: Dict, topic_scores: torch.Tensor) -> torch.Tensor:

@@ -397,3 +397,121 @@ def test_token_table_under_inference_mode(monkeypatch):
         b = enc(ids)
     assert uses["built"] == b0 + 2
     assert torch.equal(a, plain) and torch.equal(b, plain)
+
+
+# ---- the shared skeletons: DotProductRecommender, the impression-cache base, eval_mode, token_tables ---------------------------------
+# One shape for the four tests: a table of 13 news (token lengths and widths of test_gpu_topk._tiny), 3 users.
+_RESHAPES_FULL_ROWS = ("nrms", "sentirec", "manner_cr")         # dense_max_is_exact: NRMS (SentiRec inherits it) and the CR-Module
+
+
+def _small_batch(full=False):
+    """(hist idx, hist sizes, cand idx, cand sizes, labels): histories of 1, 2 and 4 news and candidate lists of 2, 3 and 1; ``full``:
+    3 x 2 histories and 3 x 2 candidates, so N == B * max on both sides."""
+    hs, cs = ((2, 2, 2), (2, 2, 2)) if full else ((1, 2, 4), (2, 3, 1))
+    g = torch.Generator().manual_seed(5)
+    hist, cand = torch.randint(1, 13, (sum(hs),), generator=g), torch.randint(1, 13, (sum(cs),), generator=g)
+    labels = torch.cat([(torch.arange(c) == 0).float() for c in cs])
+    return hist, torch.tensor(hs), cand, torch.tensor(cs), labels
+
+
+def _small_cache(model, tmp_path=None):
+    from newsreclib_amd.evaluation import DeviceNewsTable, NewsVectorCache
+    from tests.test_gpu_topk import _tiny
+    mod, table = _tiny(model, tmp_path=tmp_path, n_news=13)
+    table = table if isinstance(table, DeviceNewsTable) else DeviceNewsTable(table)
+    assert table.num_news == 13
+    return mod, NewsVectorCache(mod, table)
+
+
+def _raise(message):
+    def fn(*args, **kwargs):
+        raise RuntimeError(message)
+    return fn
+
+
+@pytest.mark.parametrize("training", [True, False])
+def test_an_exception_inside_the_cache_leaves_the_module_in_its_mode(training, monkeypatch):
+    """Host-side RuntimeErrors from a patched scorer / news encoder: ``scores`` and ``build`` put the module back into the mode it
+    was in (a module left in eval mode would train on without dropout), and the token-table scope is closed."""
+    from newsreclib_amd.evaluation import NewsVectorCache
+    mod, cache = _small_cache("nrms")
+    mod.train(training)
+    cache.build()
+    assert mod.training is training
+    hist, hs, cand, cs, _ = _small_batch()
+    monkeypatch.setattr(mod, "score_news_vectors", _raise("the scorer failed"))
+    with pytest.raises(RuntimeError, match="the scorer failed"):
+        cache.scores(hist, hs, cand, cs)
+    assert mod.training is training
+    monkeypatch.setattr(mod.news_encoder, "forward", _raise("the encoder failed"))
+    with pytest.raises(RuntimeError, match="the encoder failed"):
+        NewsVectorCache(mod, cache.table).build()
+    assert mod.training is training
+    te = mod.news_encoder.text_encoders["title"]
+    assert not te._tt_pinned and te._tt_buf is None
+
+
+@pytest.mark.parametrize("late", [False, True])
+@pytest.mark.parametrize("model", ["nrms", "lstur_ini", "naml", "tanr", "cen", "mins", "sentirec", "manner_cr"])
+def test_both_dense_paths_of_every_dot_product_family(model, late, tmp_path, monkeypatch):
+    """``score_news_vectors`` == click predictor over ``user_vectors`` and the dense candidates, bit for bit, on a ragged batch and
+    on a full one.  The full batch is a reshape (no dense-batch launch) where the family sets ``dense_max_is_exact`` and two
+    launches (history, candidates) everywhere else: the launches are counted, so a flag shared across families shows."""
+    from newsreclib_amd import ops
+    from newsreclib_amd.dense_batch import dense_rows
+    mod, cache = _small_cache(model, tmp_path)
+    mod.hparams.late_fusion = late                               # (the user encoder, where one was built, is then unused)
+    assert type(mod).dense_max_is_exact is (model in _RESHAPES_FULL_ROWS)
+    vec = cache.build()
+    launches = []
+    apply = ops.ToDenseBatchFn.apply
+    monkeypatch.setattr(ops.ToDenseBatchFn, "apply", lambda *a: (launches.append(1), apply(*a))[1])
+    for full in (False, True):
+        hist, hs, cand, cs, _ = _small_batch(full)
+        meta = cache._meta(hs, cs, None, None, None)
+        hv = ops.embedding_gather(vec, hist.cuda().reshape(-1, 1)).reshape(-1, vec.shape[1])
+        cv = ops.embedding_gather(vec, cand.cuda().reshape(-1, 1)).reshape(-1, vec.shape[1])
+        with torch.no_grad():
+            del launches[:]
+            want = mod.score_news_vectors(hv, cv, meta)
+            assert len(launches) == (0 if full and model in _RESHAPES_FULL_ROWS else 2), (full, len(launches))
+            user = mod.user_vectors(hv, meta)
+            cand_agg = dense_rows(cv, meta["batch_cand"], 3, meta["max_cand"], meta["cand_offsets"])      # always the kernel
+            got = mod.click_predictor(user.unsqueeze(dim=1), cand_agg.permute(0, 2, 1))
+        assert want.shape == (3, int(cs.max())) and user.shape == (3, vec.shape[1])
+        assert torch.equal(got, want), full
+
+
+def test_manner_cache_model_step_has_a_zero_loss_and_the_gathered_scores(tmp_path):
+    """(The third impression lists one candidate: its z-score is 0 / 0 = NaN, as in the reference, so the scores are compared as
+    bit patterns.)"""
+    from newsreclib_amd.evaluation import MannerVectorCache
+    from tests.test_gpu_manner import _ensemble, _modules, _table_and_impressions
+    cache = MannerVectorCache(_ensemble(*_modules(tmp_path)), _table_and_impressions(13)[0])
+    hist, hs, cand, cs, labels = _small_batch()
+    out = cache.model_step(hist, hs, cand, cs, labels)
+    assert len(out) == 11 and out[0].shape == () and float(out[0]) == 0.0
+    scores = cache.scores(hist, hs, cand, cs)
+    meta = cache._meta(hs, cs, labels, None, None)
+    assert scores.shape == (3, 3) and bool(torch.isfinite(out[1][:5]).all())
+    assert torch.equal(out[1].view(torch.int32), scores.reshape(-1)[meta["cand_flat_idx"]].view(torch.int32))
+    assert torch.equal(out[2].cpu(), labels) and torch.equal(out[3].cpu(), cs) and torch.equal(out[4].cpu(), hs)
+    assert torch.equal(out[10].cpu(), cand)
+
+
+def test_a_shared_text_encoder_enters_its_token_table_once(monkeypatch):
+    """MINS registers ONE ``MHSAAddAtt`` under title and abstract: ``NewsVectorCache.build`` and the epoch hooks (both through
+    ``news_encoder.token_tables``) enter its ``token_table()`` once each, and leave it."""
+    mod, cache = _small_cache("mins")
+    encoders = mod.news_encoder.text_encoders
+    te = encoders["title"]
+    assert encoders["abstract"] is te
+    entered = []
+    token_table = te.token_table
+    monkeypatch.setattr(te, "token_table", lambda: (entered.append(1), token_table())[1])
+    cache.build()
+    assert len(entered) == 1 and not te._tt_pinned
+    mod.on_validation_epoch_start()
+    assert len(entered) == 2 and te._tt_pinned
+    mod.on_validation_epoch_end()
+    assert len(entered) == 2 and not te._tt_pinned

@@ -300,12 +300,12 @@ def test_topk_scores_does_not_synchronise_with_the_host():
 
 
 # ---- 8. wiring -----------------------------------------------------------------------------------------------------------------------------
-def _tiny(model, late_fusion=False, tmp_path=None):
+def _tiny(model, late_fusion=False, tmp_path=None, n_news=None):
     """(module in eval mode, table attributes or a DeviceNewsTable) from the synthetic builders of the existing GPU tests."""
     from tests import helpers as H
     from tests.test_gpu_eval import _table
     rng = np.random.default_rng(11)
-    n_news, vocab = 50, 120
+    n_news, manner_news, vocab = n_news or 50, n_news or 40, 120      # (the MANNeR table builder's own default is 40)
     if model == "sentirec":
         from oracle import sentirec_oracle as SO
         g = H.load_golden("sentirec_tiny_eval")
@@ -319,7 +319,7 @@ def _tiny(model, late_fusion=False, tmp_path=None):
         torch.manual_seed(11)
         mod = CRModule(**cr_kwargs(H.make_tiny_roberta(str(tmp_path)), late_fusion=late_fusion),
                        pretrained_entity_embeddings=entity_table(1)).to("cuda").eval()
-        return mod, _table_and_impressions()[0]
+        return mod, _table_and_impressions(manner_news)[0]
     attrs = _table(rng, n_news, vocab, L=12, n_categ=7)
     attrs["abstract"] = _table(rng, n_news, vocab, L=20)["title"]
     if model == "nrms":

@@ -99,6 +99,62 @@ def test_dot_product_scorers_are_marked():
         assert cls.dot_product_scorer is True and callable(cls.user_vectors), cls
 
 
+def test_dot_product_families_share_one_scoring_skeleton():
+    """The eight families take ``user_vectors`` / ``score_news_vectors`` from the one base class, no module file defines either
+    name, and the reshape of full rows (``dense_max_is_exact``) stays with NRMS, SentiRec and the CR-Module."""
+    import sys
+
+    from newsreclib_amd.cen_news_rec_module import CenNewsRecModule
+    from newsreclib_amd.dot_product_recommender import DotProductRecommender
+    from newsreclib_amd.lstur_module import LSTURModule
+    from newsreclib_amd.manner_cr_module import CRModule
+    from newsreclib_amd.mins_module import MINSModule
+    from newsreclib_amd.naml_module import NAMLModule
+    from newsreclib_amd.nrms_module import NRMSModule, attach_layout, prepare_batch, text_vocab
+    from newsreclib_amd.sentirec_module import SentiRecModule
+    from newsreclib_amd.tanr_module import TANRModule
+    assert callable(attach_layout) and callable(prepare_batch) and callable(text_vocab)
+    exact = (NRMSModule, SentiRecModule, CRModule)
+    for cls in (NRMSModule, LSTURModule, NAMLModule, TANRModule, CenNewsRecModule, MINSModule, SentiRecModule, CRModule):
+        assert issubclass(cls, DotProductRecommender), cls
+        assert cls.user_vectors is DotProductRecommender.user_vectors, cls
+        assert cls.score_news_vectors is DotProductRecommender.score_news_vectors, cls
+        assert cls._encode_user is not DotProductRecommender._encode_user, cls
+        assert cls.dense_max_is_exact is (cls in exact), cls
+        source = open(sys.modules[cls.__module__].__file__).read()
+        assert not re.search(r"def\s+(user_vectors|score_news_vectors)\b", source), cls.__module__
+
+
+def test_eval_mode_restores_the_mode_when_the_scope_raises():
+    from newsreclib_amd.evaluation import eval_mode
+    m = torch.nn.Linear(2, 2)
+    for training in (True, False):
+        m.train(training)
+        with pytest.raises(RuntimeError, match="inside"):
+            with eval_mode(m):
+                assert m.training is False
+                raise RuntimeError("inside")
+        assert m.training is training
+        with eval_mode(m):
+            assert m.training is False
+        assert m.training is training
+
+
+def test_the_three_caches_share_one_model_step():
+    from newsreclib_amd import evaluation as E
+    from newsreclib_amd.npa_module import NPAModule
+    caches = (E.NewsVectorCache, E.MannerVectorCache, E.NpaFeatureCache)
+    base = [c for c in E.NewsVectorCache.__mro__ if "model_step" in vars(c)]
+    assert len(base) == 1 and base[0] not in caches
+    for cls in caches:
+        assert issubclass(cls, base[0]) and cls.model_step is base[0].model_step and cls._meta is base[0]._meta, cls
+    # before any device work: the module is not initialised, there is no table and the arguments are host tensors
+    cache = E.NpaFeatureCache(object.__new__(NPAModule), None)
+    idx, sizes = torch.tensor([1, 2, 3]), torch.tensor([2, 1])
+    with pytest.raises(ValueError, match="NpaFeatureCache.model_step needs user_idx: NPA's attention queries come from the user embedding"):
+        cache.model_step(idx, sizes, idx, sizes, torch.zeros(3), user_idx=None)
+
+
 @pytest.mark.parametrize("family", ["miner", "caum", "dkn", "sentidebias", "npa", "manner"])
 def test_recommend_is_refused_where_the_score_is_no_single_dot_product(family):
     """Before any device work: the modules are not even initialised and the arguments are host tensors."""
