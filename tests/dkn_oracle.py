@@ -55,17 +55,18 @@ def make_dkn_params(vocab: int, n_ent: int, D: int, Ed: int, F_: int, windows: L
     return p
 
 
-def kcnn(ids, ents, params, windows):
+def kcnn_conv(ids, ents, params, windows):
+    """The pre-ReLU convolution maps (N, F, L - W + 1), one per window."""
     x = params[WORD][ids]
     chans = [x, torch.tanh(params[ENT][ents] @ params[TM] + params[TB])]
     if CTX in params:
         chans.append(torch.tanh(params[CTX][ents] @ params[TM] + params[TB]))
     stack = torch.stack(chans, dim=1)                                  # (N, C, L, D)
-    pooled = []
-    for x_ in windows:
-        c = F.conv2d(stack, params[conv_key(x_, "weight")], params[conv_key(x_, "bias")]).squeeze(3)
-        pooled.append(torch.relu(c).max(dim=-1)[0])
-    return torch.cat(pooled, dim=1)
+    return [F.conv2d(stack, params[conv_key(x_, "weight")], params[conv_key(x_, "bias")]).squeeze(3) for x_ in windows]
+
+
+def kcnn(ids, ents, params, windows):
+    return torch.cat([torch.relu(c).max(dim=-1)[0] for c in kcnn_conv(ids, ents, params, windows)], dim=1)
 
 
 def user_attention(hist, cand, mask_h, mask_c, params):
@@ -74,9 +75,9 @@ def user_attention(hist, cand, mask_h, mask_c, params):
     pair = torch.cat([cand.unsqueeze(2).expand(-1, -1, Hn, -1), hist.unsqueeze(1).expand(-1, Cn, -1, -1)], dim=-1)
     s = (pair @ params[UE + "0.weight"].t() + params[UE + "0.bias"]) @ params[UE + "1.weight"].t() + params[UE + "1.bias"]
     s = s.squeeze(-1)
-    s = torch.where(mask_h.unsqueeze(1).expand(-1, Cn, -1), s, torch.tensor(torch.finfo(s.dtype).min))
+    s = torch.where(mask_h.unsqueeze(1).expand(-1, Cn, -1), s, torch.tensor(torch.finfo(s.dtype).min, dtype=s.dtype))
     w = torch.softmax(s, dim=-1)
-    w = torch.where(mask_c.unsqueeze(-1).expand(-1, -1, Hn), w, torch.tensor(0.0))
+    w = torch.where(mask_c.unsqueeze(-1).expand(-1, -1, Hn), w, torch.tensor(0.0, dtype=w.dtype))
     return torch.bmm(w, hist)
 
 

@@ -50,17 +50,17 @@ def make_npa_params(vocab: int, num_users: int, D: int = 300, U: int = 50, F_: i
 def _query(u, params, proj, att, mask):
     h = torch.relu(u @ params[proj + "weight"].t() + params[proj + "bias"])
     if mask is not None:
-        h = h * mask
+        h = h * mask.to(h.dtype)
     return torch.tanh(h @ params[att + "weight"].t() + params[att + "bias"])
 
 
 def _conv_features(ids, params, m1, m2):
     x = params[PRE + "embedding_layer.weight"][ids]
     if m1 is not None:
-        x = x * m1
+        x = x * m1.to(x.dtype)
     c = torch.relu(F.conv1d(x.permute(0, 2, 1), params[PRE + "cnn.weight"], params[PRE + "cnn.bias"], padding=1))
     c = c.permute(0, 2, 1)                                           # (N, L, F)
-    return c * m2 if m2 is not None else c
+    return c * m2.to(c.dtype) if m2 is not None else c
 
 
 def _pers_att(keys, q):
@@ -87,7 +87,7 @@ def npa_forward(batch, params, p_drop: float = 0.0, seed: int = 0, late_fusion: 
             m["qn"] = dropout_multiplier(seed, 5, p_drop, (B, params[NEWS_PROJ + "weight"].shape[0]))
     u = table[batch["user_idx"]]
     if m["u"] is not None:
-        u = u * m["u"]
+        u = u * m["u"].to(u.dtype)
     q_hist = _query(u, params, TEXT_PROJ, TEXT_ATT, m["qh"])
     q_cand = _query(u, params, TEXT_PROJ, TEXT_ATT, m["qc"])
     c = _conv_features(torch.cat([ids_h, ids_c]), params, m["x"], m["c"])

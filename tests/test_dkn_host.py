@@ -92,3 +92,31 @@ def test_add_dkn_fields_pads_after_leading_entities():
         assert bool((e[t == 0] == 0).all())
         nz = (e != 0).int()
         assert bool((nz[:, 1:] <= nz[:, :-1]).all())           # leading entities, then zeros
+
+
+# ---- input generators of the op-level shape sweep (tests/sweep_inputs.py, run on the GPU by test_gpu_npa_dkn_sweep.py) ------
+def test_sweep_dkn_fragile_share_is_within_the_cap_for_every_seed():
+    """The float64 oracle alone: at most 2 % of a case's pooled outputs have a top-two gap or a |max| below 10x either
+    engine's forward tolerance; the L = 255 case holds a maximum at the last valid position of every window."""
+    from tests import sweep_inputs as S
+    for i, case in enumerate(S.DKN_ENCODER_CASES):
+        for engine in S.TOL:
+            ref = S.cached("dkn_encoder", i, "float64", engine)
+            assert float(ref["fragile"].float().mean()) <= S.FRAGILE_CAP, (case["name"], engine)
+        if case["last"]:
+            F_ = case["F"]
+            for j, w in enumerate(case["windows"]):
+                assert int(ref["argmax"][0, j * F_]) == case["L"] - w == (254, 251)[j]
+                assert not bool(ref["fragile"][0, j * F_]) and float(ref["out"][0, j * F_]) > 0
+
+
+def test_sweep_dkn_click_gates_are_clear_of_zero():
+    """No pre-activation of the predictor's ReLU is within 1e-4 of zero (fp32 rounding there is ~1e-6): the gate decides
+    the same in fp32 and float64.  Every case has an empty history, whose user vector is exactly zero."""
+    from tests import sweep_inputs as S
+    assert {c["Hd"] for c in S.DKN_CLICK_CASES} >= {1, 16, 64} and {c["dim"] for c in S.DKN_CLICK_CASES} >= {4, 32, 400, 1024}
+    for i, case in enumerate(S.DKN_CLICK_CASES):
+        ref = S.cached("dkn_click", i, "float64")
+        assert ref["min_pre"] >= 1e-4, (case["name"], ref["min_pre"])
+        assert bool(torch.isfinite(ref["scores"]).all())
+        assert bool((ref["user"][case["hist"].index(0)] == 0).all())
