@@ -77,6 +77,44 @@ def ensemble_scores(tables, weights, hist, cand) -> list:
     return total
 
 
+# ---- inputs of the kernel checks (tests/test_gpu_manner.py, tests/sweep_inputs_sd_manner.py) --------------------------------------
+def supcon_case(N, D, classes, T, seed=0, singleton=False):
+    """Embeddings scaled so that the float64 row losses are exactly 0 or >= 1e-3 (the reducer's `> 0` test cannot flip within
+    tolerance): seeds counted up from `seed + 1`, first hit.  ``singleton``: the last row gets a class of its own."""
+    for s in range(seed + 1, seed + 50):
+        g = torch.Generator().manual_seed(s)
+        E = torch.randn(N, D, generator=g) * (0.6 * (T ** 0.5) / D ** 0.25)
+        labels = torch.randint(0, classes, (N,), generator=g)
+        if N <= classes * 2:
+            labels = torch.arange(N) % classes
+        if singleton:
+            labels[N - 1] = classes
+        rows = supcon_rows(E.double(), labels, T)
+        if rows is not None and bool(((rows == 0) | (rows >= 1e-3)).all()) and bool((rows > 0).any()):
+            return E, labels
+    raise AssertionError("no seed satisfies the row-loss condition")
+
+
+def random_tables(k, V, D, seed):
+    """Unit-scale random news vectors.  Every multi-candidate impression must have std >= 1e-2 max|score| in every sub-model
+    (asserted by the caller), else the z-score amplifies rounding."""
+    g = torch.Generator().manual_seed(seed)
+    return [torch.randn(V, D, generator=g) / D ** 0.5 for _ in range(k)]
+
+
+def min_std_ratio(tables, hist, cand, skip=()):
+    """min over the sub-models and the impressions with several candidates (those in ``skip`` left out) of
+    std / max|score| of the float64 raw scores."""
+    worst = float("inf")
+    for t in tables:
+        t = t.double()
+        for b, (h, c) in enumerate(zip(hist, cand)):
+            if len(c) > 1 and b not in skip:
+                s = t[c] @ (t[h].sum(0) / len(h))
+                worst = min(worst, float(torch.std(s)) / float(s.abs().max()))
+    return worst
+
+
 # ---- fixtures shared by tests/golden/make_golden_manner.py and the tests ----------------------------------------------------------
 TINY = dict(T=96, De=96, H=6, Q=32, n_ent=40, frozen=(0,))          # tests.helpers.make_tiny_roberta's width; heads of 16
 NE = "news_encoder."

@@ -1,6 +1,7 @@
 """Input generators and float64 / float32 CPU references of the NPA / DKN op-level shape sweep
 (tests/test_gpu_npa_dkn_sweep.py); their properties are asserted on the host in tests/test_npa_host.py and
-tests/test_dkn_host.py.  Plain module: no fixtures, no GPU.
+tests/test_dkn_host.py, and the ``Report`` helper every sweep file prints and asserts through (the SentiDebias / MANNeR
+generators are in tests/sweep_inputs_sd_manner.py).  Plain module: no fixtures, no GPU.
 
 Two constructions make a ReLU or arg-max decision the same in fp32 and in float64 ("Shape sweeps against
 float64"):
@@ -59,6 +60,49 @@ def _offsets(counts):
 
 def _leaf(t, dtype):
     return t.to(dtype).clone().requires_grad_(True)
+
+
+# ---- the printed comparison of every sweep file (tests/test_gpu_npa_dkn_sweep.py, tests/test_gpu_sd_manner_sweep.py) ----------
+class Report:
+    """Prints every figure of a case, then asserts them all."""
+
+    def __init__(self, family, case, engine):
+        self.tag, self.engine, self.bad = f"{family}/{case}", engine, []
+        self.ftol, self.gtol = TOL[engine]
+
+    def _line(self, what, got, want, want32, tol):
+        got = got.detach().cpu().double()
+        err = float((got - want).abs().max()) if want.numel() else 0.0
+        e32 = float((want32.double() - want).abs().max()) if want.numel() else 0.0
+        ok = err <= tol and bool(torch.isfinite(got).all())
+        print(f"SWEEP {self.tag} {self.engine} {what}: kernel {err:.3e} oracle32 {e32:.3e} tol {tol:.3e}" + ("" if ok else " FAIL"))
+        if not ok:
+            self.bad.append((what, err, tol))
+
+    def fwd(self, what, got, want, want32):
+        self._line(what, got, want, want32, 5 * self.ftol)
+
+    def grad(self, what, got, want, want32):
+        self._line(what, got, want, want32, self.gtol * max(1.0, float(want.abs().max()) if want.numel() else 0.0))
+
+    def bound(self, what, got, want, want32, tol, rel=False):
+        """A bound set at the configured shape, carried to a wider one: the larger of the project's number (times
+        max(1, |want|_max) when ``rel``) and 4x the float32 CPU oracle's own error against float64 at this case."""
+        scale = max(1.0, float(want.abs().max()) if want.numel() else 0.0) if rel else 1.0
+        e32 = float((want32.double() - want).abs().max()) if want.numel() else 0.0
+        self._line(what, got, want, want32, max(tol * scale, 4 * e32))
+
+    def within(self, what, got, want, want32, tol):
+        """A bound the caller derived from the float32 oracle's error alone."""
+        self._line(what, got, want, want32, tol)
+
+    def check(self, what, ok):
+        if not ok:
+            print(f"SWEEP {self.tag} {self.engine} {what}: FAIL")
+            self.bad.append((what,))
+
+    def done(self):
+        assert not self.bad, (self.tag, self.engine, self.bad)
 
 
 # ---- NPA text encoder -------------------------------------------------------------------------------------------------------

@@ -25,19 +25,7 @@ def engine(request):
     _lib.set_gemm_engine(prev)
 
 
-def _supcon_case(N, D, classes, T, seed=0):
-    """Embeddings scaled so that the float64 row losses are exactly 0 or >= 1e-3 (the reducer's `> 0` test cannot flip within
-    tolerance): seeds counted up from `seed + 1`, first hit."""
-    for s in range(seed + 1, seed + 50):
-        g = torch.Generator().manual_seed(s)
-        E = torch.randn(N, D, generator=g) * (0.6 * (T ** 0.5) / D ** 0.25)
-        labels = torch.randint(0, classes, (N,), generator=g)
-        if N <= classes * 2:
-            labels = torch.arange(N) % classes
-        rows = MO.supcon_rows(E.double(), labels, T)
-        if rows is not None and bool(((rows == 0) | (rows >= 1e-3)).all()) and bool((rows > 0).any()):
-            return E, labels
-    raise AssertionError("no seed satisfies the row-loss condition")
+_supcon_case = MO.supcon_case
 
 
 def _err(a, ref):
@@ -131,22 +119,14 @@ def _flat(hist, cand, hs, cs):
             torch.cat([z, torch.cumsum(cs, 0)]).to(DEV))
 
 
-def _tables(k, V, D, seed):
-    """Unit-scale random news vectors.  Every multi-candidate impression must have std >= 1e-2 max|score| in every sub-model
-    (asserted by the caller), else the z-score amplifies rounding."""
-    g = torch.Generator().manual_seed(seed)
-    return [torch.randn(V, D, generator=g) / D ** 0.5 for _ in range(k)]
+_tables = MO.random_tables
 
 
 def _check_scores(tables, weights, hist, cand, hs, cs):
     from newsreclib_amd.ops_manner import manner_scores
     ref = MO.ensemble_scores([t.double() for t in tables], weights, hist, cand)
     f32 = MO.ensemble_scores(tables, weights, hist, cand)
-    for t in tables:
-        for h, c in zip(hist, cand):
-            if len(c) > 1:
-                s = t.double()[c] @ (t.double()[h].sum(0) / len(h))
-                assert float(torch.std(s)) >= 1e-2 * float(s.abs().max())
+    assert MO.min_std_ratio(tables, hist, cand) >= 1e-2
     e32 = max(float((a.double() - b).abs().max()) for a, b in zip(f32, ref) if len(b) > 1)
     bound = 4 * e32
     out = manner_scores([t.to(DEV) for t in tables], weights, *_flat(hist, cand, hs, cs), int(cs.max())).cpu()

@@ -8,12 +8,13 @@ The inputs come from tests/sweep_inputs.py, which makes every ReLU / arg-max dec
 gate inputs for NPA, the fragile-output mask for DKN; their properties are asserted on the host in test_npa_host.py and
 test_dkn_host.py).  Tolerances are the project's own, as test_gpu_shapes.py: forward 5 ftol, gradients
 gtol max(1, |want|_max), against float64.  Every comparison prints a ``SWEEP`` line with the kernel's error and the float32
-CPU oracle's error at the same case (tools/npa_dkn_sweep_errors.py collects them into profiles/npa_dkn_sweep_errors.txt)."""
+CPU oracle's error at the same case (tools/sweep_errors.py collects them into profiles/npa_dkn_sweep_errors.txt)."""
 import pytest
 import torch
 
 from tests import dkn_oracle as DO
 from tests import sweep_inputs as S
+from tests.sweep_inputs import Report
 
 pytestmark = pytest.mark.gpu
 
@@ -25,37 +26,6 @@ def engine(request):
     _lib.set_gemm_engine(request.param)
     yield request.param
     _lib.set_gemm_engine(prev)
-
-
-class Report:
-    """Prints every figure of a case, then asserts them all."""
-
-    def __init__(self, family, case, engine):
-        self.tag, self.engine, self.bad = f"{family}/{case}", engine, []
-        self.ftol, self.gtol = S.TOL[engine]
-
-    def _line(self, what, got, want, want32, tol):
-        got = got.detach().cpu().double()
-        err = float((got - want).abs().max()) if want.numel() else 0.0
-        e32 = float((want32.double() - want).abs().max()) if want.numel() else 0.0
-        ok = err <= tol and bool(torch.isfinite(got).all())
-        print(f"SWEEP {self.tag} {self.engine} {what}: kernel {err:.3e} oracle32 {e32:.3e} tol {tol:.3e}" + ("" if ok else " FAIL"))
-        if not ok:
-            self.bad.append((what, err, tol))
-
-    def fwd(self, what, got, want, want32):
-        self._line(what, got, want, want32, 5 * self.ftol)
-
-    def grad(self, what, got, want, want32):
-        self._line(what, got, want, want32, self.gtol * max(1.0, float(want.abs().max()) if want.numel() else 0.0))
-
-    def check(self, what, ok):
-        if not ok:
-            print(f"SWEEP {self.tag} {self.engine} {what}: FAIL")
-            self.bad.append((what,))
-
-    def done(self):
-        assert not self.bad, (self.tag, self.engine, self.bad)
 
 
 def _ids(cases):
