@@ -33,6 +33,8 @@ extern "C" {
 #define NRL_E_INVALID (-1)   /* bad argument (shape / alignment / null) */
 #define NRL_E_WORKSPACE (-2) /* workspace too small */
 #define NRL_E_HIP (-3)       /* a HIP runtime call failed */
+/* Every entry point that takes a workspace reports a short one the same way: NRL_E_WORKSPACE with the message
+ * "workspace too small: <given> < <needed> bytes", before anything is launched; a null or misaligned one is NRL_E_INVALID. */
 
 /* One "multi-head self-attention + additive attention" block.  Field <-> reference state_dict key
  * (prefix `news_encoder.text_encoders.title.` or `user_encoder.`):

@@ -171,8 +171,7 @@ int nrl_dropout_mask(uint8_t* keep, int64_t n_elems, double p, uint64_t seed, ui
 
 size_t nrl_news_encoder_workspace_bytes(int64_t n_news, int32_t seq_len, int32_t embed_dim,
                                         int32_t num_heads, int32_t query_dim) {
-  return block_ws_floats(n_news * seq_len, embed_dim, query_dim, num_heads, true, news_pad_rows(n_news, seq_len, embed_dim, num_heads)) *
-         sizeof(float);
+  return block_ws_bytes(n_news * seq_len, embed_dim, query_dim, num_heads, true, news_pad_rows(n_news, seq_len, embed_dim, num_heads));
 }
 
 int nrl_news_encoder_fwd(const NrlBlockParams* p, const float* emb_table, int64_t vocab,
@@ -312,13 +311,18 @@ int nrl_token_table_build(const NrlBlockParams* p, const float* emb_table, int64
 }
 
 // workspace of the table forward: the `o` planes + the short-first news list of the pad-row sharing
-static size_t table_fwd_planes_bytes(int64_t n_news, int L, int heads) {
+struct TableFwdWs {
+  unsigned char* o_planes;
+  int32_t* hdr;
+};
+static void table_fwd_layout(Arena& a, int64_t n_news, int L, int heads, TableFwdWs* w) {
   const int64_t M = n_news * L;
-  return align_up((size_t)((M + 31) / 32 * 32) * (size_t)(heads + (heads + 3) / 4) * 16 * sizeof(float), 256);
+  w->o_planes = a.take<unsigned char>((size_t)((M + 31) / 32 * 32) * (size_t)(heads + (heads + 3) / 4) * 16 * sizeof(float));
+  w->hdr = a.take<int32_t>((size_t)(n_news + 2));
 }
 size_t nrl_news_encoder_fwd_table_workspace_bytes(int64_t n_news, int32_t seq_len, int32_t num_heads) {
   if (n_news <= 0 || seq_len <= 0 || num_heads <= 0) return 0;
-  return table_fwd_planes_bytes(n_news, seq_len, num_heads) + align_up((size_t)(n_news + 2) * sizeof(int32_t), 256);
+  return measure_workspace<TableFwdWs>([&](Arena& a, auto* w) { table_fwd_layout(a, n_news, seq_len, num_heads, w); });
 }
 
 int nrl_news_encoder_fwd_table(const NrlBlockParams* p, const void* table, size_t table_bytes, int64_t vocab,
@@ -335,17 +339,13 @@ int nrl_news_encoder_fwd_table(const NrlBlockParams* p, const void* table, size_
   const size_t need_t = nrl_token_table_bytes(vocab, D, heads, Q);
   NRL_REQUIRE(need_t > 0 && table_bytes >= need_t, "news_encoder_fwd_table: not a table of this vocabulary / geometry");
   NRL_REQUIRE(n_news * (int64_t)seq_len < (1LL << 31), "news_encoder_fwd_table: too many token rows for one call");
-  NRL_REQUIRE(ws != nullptr && ((uintptr_t)ws & 255) == 0, "workspace must be 256-byte aligned");
-  const size_t need_w = nrl_news_encoder_fwd_table_workspace_bytes(n_news, seq_len, heads);
-  if (ws_bytes < need_w) {
-    set_error("workspace too small: %zu < %zu bytes", ws_bytes, need_w);
-    return NRL_E_WORKSPACE;
-  }
+  TableFwdWs w;
+  NRL_TRY(carve_workspace(ws, ws_bytes, [&](Arena& a) { table_fwd_layout(a, n_news, seq_len, heads, &w); }));
   hipStream_t st = (hipStream_t)stream;
   const TokenTable t = token_table_layout(vocab, D, heads);
   const unsigned char* base = static_cast<const unsigned char*>(table);
-  unsigned char* o_planes = static_cast<unsigned char*>(ws);
-  int32_t* hdr = reinterpret_cast<int32_t*>(o_planes + table_fwd_planes_bytes(n_news, seq_len, heads));
+  unsigned char* const o_planes = w.o_planes;
+  int32_t* const hdr = w.hdr;
   NewsTabArgs a;
   a.tab = reinterpret_cast<const float*>(base + t.qkv); a.ids = ids; a.n_news = n_news; a.vocab = vocab; a.L = seq_len;
   a.heads = heads; a.scale = 1.0f / sqrtf((float)(D / heads)); a.o_planes = o_planes;
@@ -462,7 +462,7 @@ int nrl_news_encoder_bwd(const NrlBlockParams* p, const NrlBlockGrads* g, const 
 
 size_t nrl_user_encoder_workspace_bytes(int64_t batch, int64_t hist_len, int32_t embed_dim,
                                         int32_t num_heads, int32_t query_dim) {
-  return block_ws_floats(batch * hist_len, embed_dim, query_dim, num_heads, true) * sizeof(float);
+  return block_ws_bytes(batch * hist_len, embed_dim, query_dim, num_heads, true);
 }
 
 int nrl_user_encoder_fwd(const NrlBlockParams* p, const float* hist, int64_t batch, int64_t hist_len,
@@ -630,15 +630,25 @@ int nrl_embedding_gather(const float* table, const int64_t* ids, int64_t n_ids, 
   return embedding_gather(table, ids, n_ids, dim, out, (hipStream_t)stream);
 }
 
+// workspace of the nrl_linear_* family, one region: bf16 planes of W and W^T (tiled kernels), or the panel images of the forward
+// (n columns over k) / the activation gradient (k columns over n), whichever is larger
+static void linear_layout(Arena& a, int n, int k, uint16_t** img) {
+  size_t e = split_weight_elems(n, k);
+  if (lin_image_elems(n, k) > e) e = lin_image_elems(n, k);
+  if (lin_image_elems(k, n) > e) e = lin_image_elems(k, n);
+  *img = a.take<uint16_t>(e);
+}
+
 // nn.Linear + exact GELU (a BERT-family feed-forward block's first half, ABI v14): h = a W^T + bias (saved), g = gelu(h)
 int nrl_linear_gelu_fwd_img(const float* a, const float* w, const float* bias, int64_t m, int32_t n, int32_t k, float* h, float* g,
                             void* ws, size_t ws_bytes, int32_t image_ready, void* stream) {
   NRL_REQUIRE(a && w && bias && h && g && m >= 0 && n > 0 && k > 0 && k % 4 == 0 && n % 4 == 0, "linear_gelu_fwd: bad arguments");
   NRL_REQUIRE((((uintptr_t)a | (uintptr_t)w | (uintptr_t)h | (uintptr_t)g | (uintptr_t)bias) & 15) == 0, "linear_gelu_fwd: 16-byte alignment");
   NRL_REQUIRE(cur_engine() == ENGINE_BF16X3 && lin_panels_on(n), "linear_gelu_fwd: bf16x3 engine and n >= 256 (nrl_linear_gelu_supported)");
-  NRL_REQUIRE(ws != nullptr && ((uintptr_t)ws & 255) == 0 && ws_bytes >= nrl_linear_workspace_bytes(n, k), "linear_gelu_fwd: workspace");
+  uint16_t* img;
+  NRL_TRY(carve_workspace(ws, ws_bytes, [&](Arena& ar) { linear_layout(ar, n, k, &img); }));
   if (m == 0) return NRL_OK;
-  return linear_panels(a, w, k, 1, n, k, EpiLinearGelu{h, g, n, bias}, m, (uint16_t*)ws, (hipStream_t)stream, image_ready == 0);
+  return linear_panels(a, w, k, 1, n, k, EpiLinearGelu{h, g, n, bias}, m, img, (hipStream_t)stream, image_ready == 0);
 }
 
 // activation gradient of a projection whose INPUT was g = gelu(pre): d_pre (m, k) = (d_c W) * gelu'(pre) in the epilogue
@@ -647,9 +657,10 @@ int nrl_linear_dgrad_gelu_img(const float* w, const float* d_c, const float* pre
   NRL_REQUIRE(w && d_c && pre && d_pre && m >= 0 && n > 0 && k > 0 && k % 4 == 0 && n % 4 == 0, "linear_dgrad_gelu: bad arguments");
   NRL_REQUIRE((((uintptr_t)w | (uintptr_t)d_c | (uintptr_t)pre | (uintptr_t)d_pre) & 15) == 0, "linear_dgrad_gelu: 16-byte alignment");
   NRL_REQUIRE(cur_engine() == ENGINE_BF16X3 && lin_panels_on(k), "linear_dgrad_gelu: bf16x3 engine and k >= 256 (nrl_linear_gelu_supported)");
-  NRL_REQUIRE(ws != nullptr && ((uintptr_t)ws & 255) == 0 && ws_bytes >= nrl_linear_workspace_bytes(n, k), "linear_dgrad_gelu: workspace");
+  uint16_t* img;
+  NRL_TRY(carve_workspace(ws, ws_bytes, [&](Arena& ar) { linear_layout(ar, n, k, &img); }));
   if (m == 0) return NRL_OK;
-  return linear_panels(d_c, w, 1, k, k, n, EpiGeluBwd{d_pre, k, pre}, m, (uint16_t*)ws, (hipStream_t)stream, image_ready == 0);
+  return linear_panels(d_c, w, 1, k, k, n, EpiGeluBwd{d_pre, k, pre}, m, img, (hipStream_t)stream, image_ready == 0);
 }
 
 // ---- three projections of one input (query / key / value of a transformer layer) as one GEMM each way, ABI v15 -----------
@@ -660,10 +671,14 @@ static inline bool lin3_ok(int n, int k) {
          3 * lin_panels(n) <= RP_MAX_JOBS && 3 * lin_panels(k) <= RP_MAX_JOBS;
 }
 int32_t nrl_linear3_supported(int32_t n, int32_t k) { return (n > 0 && k > 0 && lin3_ok(n, k)) ? 1 : 0; }
-size_t nrl_linear3_workspace_bytes(int32_t n, int32_t k) {
+// one region: the forward image or the backward image, whichever is larger
+static void linear3_layout(Arena& a, int n, int k, uint16_t** img) {
   size_t e = lin_image_elems(3 * n, k);
   if (lin_image_elems(k, 3 * n) > e) e = lin_image_elems(k, 3 * n);
-  return align_up(e * sizeof(uint16_t), 256);
+  *img = a.take<uint16_t>(e);
+}
+size_t nrl_linear3_workspace_bytes(int32_t n, int32_t k) {
+  return measure_workspace<uint16_t*>([&](Arena& a, auto* w) { linear3_layout(a, n, k, w); });
 }
 
 int nrl_linear3_fwd_img(const float* a, const float* w0, const float* w1, const float* w2, const float* b0, const float* b1,
@@ -673,12 +688,12 @@ int nrl_linear3_fwd_img(const float* a, const float* w0, const float* w1, const 
   NRL_REQUIRE(lin3_ok(n, k), "linear3_fwd: bf16x3 engine, n and k multiples of 256, at most 12 panels (nrl_linear3_supported)");
   NRL_REQUIRE((((uintptr_t)a | (uintptr_t)w0 | (uintptr_t)w1 | (uintptr_t)w2 | (uintptr_t)b0 | (uintptr_t)b1 | (uintptr_t)b2 | (uintptr_t)c) & 15) == 0,
               "linear3_fwd: 16-byte alignment");
-  NRL_REQUIRE(ws != nullptr && ((uintptr_t)ws & 255) == 0 && ws_bytes >= nrl_linear3_workspace_bytes(n, k), "linear3_fwd: workspace");
+  uint16_t* img;
+  NRL_TRY(carve_workspace(ws, ws_bytes, [&](Arena& ar) { linear3_layout(ar, n, k, &img); }));
   if (m == 0) return NRL_OK;
   hipStream_t st = (hipStream_t)stream;
   const int pp = lin_panels(n), P = 3 * pp, kb = rp_kblocks(k, false), pw = 16 * LIN_PANEL_BLOCKS;
   const size_t pe = rp_image_elems(LIN_PANEL_BLOCKS, kb);
-  uint16_t* img = (uint16_t*)ws;
   if (image_ready == 0) {
     const float* w[3] = {w0, w1, w2};
     RpImageJobs jobs;
@@ -699,12 +714,12 @@ int nrl_linear3_dgrad_img(const float* d_c, const float* w0, const float* w1, co
   NRL_REQUIRE(lin3_ok(n, k), "linear3_dgrad: bf16x3 engine, n and k multiples of 256, at most 12 panels (nrl_linear3_supported)");
   NRL_REQUIRE((((uintptr_t)d_c | (uintptr_t)w0 | (uintptr_t)w1 | (uintptr_t)w2 | (uintptr_t)add | (uintptr_t)d_a) & 15) == 0,
               "linear3_dgrad: 16-byte alignment");
-  NRL_REQUIRE(ws != nullptr && ((uintptr_t)ws & 255) == 0 && ws_bytes >= nrl_linear3_workspace_bytes(n, k), "linear3_dgrad: workspace");
+  uint16_t* img;
+  NRL_TRY(carve_workspace(ws, ws_bytes, [&](Arena& ar) { linear3_layout(ar, n, k, &img); }));
   if (m == 0) return NRL_OK;
   hipStream_t st = (hipStream_t)stream;
   const int P = lin_panels(k), kbp = n / 32, kb = 3 * kbp, pw = 16 * LIN_PANEL_BLOCKS;
   const size_t pe = rp_image_elems(LIN_PANEL_BLOCKS, kb), part = rp_image_elems(LIN_PANEL_BLOCKS, kbp);
-  uint16_t* img = (uint16_t*)ws;
   if (image_ready == 0) {
     const float* w[3] = {w0, w1, w2};
     RpImageJobs jobs;
@@ -727,9 +742,10 @@ int nrl_linear_dgrad_add_img(const float* d_c, const float* w, int64_t m, int32_
   NRL_REQUIRE(d_c && w && add && d_a && m >= 0 && n > 0 && k > 0 && k % 4 == 0 && n % 4 == 0, "linear_dgrad_add: bad arguments");
   NRL_REQUIRE((((uintptr_t)d_c | (uintptr_t)w | (uintptr_t)add | (uintptr_t)d_a) & 15) == 0, "linear_dgrad_add: 16-byte alignment");
   NRL_REQUIRE(cur_engine() == ENGINE_BF16X3 && lin_panels_on(k), "linear_dgrad_add: bf16x3 engine and k >= 256 (nrl_linear_gelu_supported)");
-  NRL_REQUIRE(ws != nullptr && ((uintptr_t)ws & 255) == 0 && ws_bytes >= nrl_linear_workspace_bytes(n, k), "linear_dgrad_add: workspace");
+  uint16_t* img;
+  NRL_TRY(carve_workspace(ws, ws_bytes, [&](Arena& ar) { linear_layout(ar, n, k, &img); }));
   if (m == 0) return NRL_OK;
-  return linear_panels(d_c, w, 1, k, k, n, EpiAddStore{d_a, k, add}, m, (uint16_t*)ws, (hipStream_t)stream, image_ready == 0);
+  return linear_panels(d_c, w, 1, k, k, n, EpiAddStore{d_a, k, add}, m, img, (hipStream_t)stream, image_ready == 0);
 }
 
 int32_t nrl_linear_gelu_supported(int32_t n_wide) { return (cur_engine() == ENGINE_BF16X3 && lin_panels_on(n_wide)) ? 1 : 0; }
@@ -741,12 +757,7 @@ int nrl_embedding_grad(const float* d_out, const int64_t* ids, const int64_t* so
 }
 
 size_t nrl_linear_workspace_bytes(int32_t n, int32_t k) {
-  // bf16 planes of W and W^T (tiled kernels), or the panel images of the forward (n columns over k) / the activation
-  // gradient (k columns over n), whichever is larger
-  size_t e = split_weight_elems(n, k);
-  if (lin_image_elems(n, k) > e) e = lin_image_elems(n, k);
-  if (lin_image_elems(k, n) > e) e = lin_image_elems(k, n);
-  return align_up(e * sizeof(uint16_t), 256);
+  return measure_workspace<uint16_t*>([&](Arena& a, auto* w) { linear_layout(a, n, k, w); });
 }
 
 int nrl_linear_fwd(const float* a, const float* w, const float* bias, int64_t m, int32_t n, int32_t k,
@@ -762,15 +773,12 @@ int nrl_linear_fwd_img(const float* a, const float* w, const float* bias, int64_
   const EpiLinear epi{c, n, bias, 0, make_dropout(0.0, 0, 0), n};
   if (ws == nullptr || cur_engine() != ENGINE_BF16X3)
     return launch_gemm<NRL_TILE>(KCPlain{a, k, m}, KCPlain{w, k, n}, epi, m, n, k, 1, st);
-  NRL_REQUIRE(((uintptr_t)ws & 255) == 0, "workspace must be 256-byte aligned");
-  if (ws_bytes < nrl_linear_workspace_bytes(n, k)) {
-    set_error("workspace too small: %zu < %zu bytes", ws_bytes, nrl_linear_workspace_bytes(n, k));
-    return NRL_E_WORKSPACE;
-  }
+  uint16_t* img;
+  NRL_TRY(carve_workspace(ws, ws_bytes, [&](Arena& ar) { linear_layout(ar, n, k, &img); }));
   if (m == 0) return NRL_OK;
-  if (lin_panels_on(n)) return linear_panels(a, w, k, 1, n, k, epi, m, (uint16_t*)ws, st, image_ready == 0);   // element (n, k) = W[n][k]
+  if (lin_panels_on(n)) return linear_panels(a, w, k, 1, n, k, epi, m, img, st, image_ready == 0);   // element (n, k) = W[n][k]
   SplitWeight sw;
-  NRL_TRY(split_weight(w, n, k, (uint16_t*)ws, &sw, st));
+  NRL_TRY(split_weight(w, n, k, img, &sw, st));
   return gemm_fwd(KCPlain{a, k, m}, w, sw, epi, m, n, k, n <= 224, st);
 }
 
@@ -793,15 +801,12 @@ int nrl_linear_bwd_img(const float* a, const float* w, const float* d_c, int64_t
   if (d_a != nullptr) {
     SplitWeight sw{};
     if (cur_engine() == ENGINE_BF16X3) {
-      NRL_REQUIRE(ws != nullptr && ((uintptr_t)ws & 255) == 0, "workspace must be 256-byte aligned");
-      if (ws_bytes < nrl_linear_workspace_bytes(n, k)) {
-        set_error("workspace too small: %zu < %zu bytes", ws_bytes, nrl_linear_workspace_bytes(n, k));
-        return NRL_E_WORKSPACE;
-      }
+      uint16_t* img;
+      NRL_TRY(carve_workspace(ws, ws_bytes, [&](Arena& ar) { linear_layout(ar, n, k, &img); }));
       if (lin_panels_on(k)) {        // d_a columns j over the reduction i: element = W[i][j]
-        NRL_TRY(linear_panels(d_c, w, 1, k, k, n, EpiStore{d_a, k}, m, (uint16_t*)ws, st, image_ready == 0));
+        NRL_TRY(linear_panels(d_c, w, 1, k, k, n, EpiStore{d_a, k}, m, img, st, image_ready == 0));
       } else {
-        NRL_TRY(split_weight(w, n, k, (uint16_t*)ws, &sw, st));
+        NRL_TRY(split_weight(w, n, k, img, &sw, st));
         NRL_TRY(gemm_dgrad(d_c, w, sw, EpiStore{d_a, k}, m, n, k, st));
       }
     } else {

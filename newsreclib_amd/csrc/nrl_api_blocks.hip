@@ -10,23 +10,10 @@ struct AddAttWs {
   uint16_t* planes;
 };
 
-static size_t addatt_ws_floats(int64_t M, int D, int Q) {
-  auto al = [](size_t n) { return align_up(n, 64); };
-  return al((size_t)M * Q) + al((size_t)M) + al((split_weight_elems(Q, D) + 1) / 2);
-}
-
-static int addatt_carve(void* ws, size_t ws_bytes, int64_t M, int D, int Q, AddAttWs* o) {
-  NRL_REQUIRE(ws != nullptr && ((uintptr_t)ws & 255) == 0, "workspace must be 256-byte aligned");
-  if (ws_bytes < addatt_ws_floats(M, D, Q) * sizeof(float)) {
-    set_error("workspace too small: %zu < %zu bytes", ws_bytes, addatt_ws_floats(M, D, Q) * sizeof(float));
-    return NRL_E_WORKSPACE;
-  }
-  float* p = (float*)ws;
-  auto take = [&](size_t n) { float* r = p; p += align_up(n, 64); return r; };
-  o->t = take((size_t)M * Q);
-  o->w = take((size_t)M);
-  o->planes = reinterpret_cast<uint16_t*>(take((split_weight_elems(Q, D) + 1) / 2));
-  return NRL_OK;
+static void addatt_layout(Arena& a, int64_t M, int D, int Q, AddAttWs* o) {
+  o->t = a.take<float>((size_t)M * Q);
+  o->w = a.take<float>((size_t)M);
+  o->planes = a.take<uint16_t>(split_weight_elems(Q, D));
 }
 
 static int addatt_check(const NrlAddAttParams* p, int64_t groups, int64_t len) {
@@ -63,26 +50,23 @@ struct MhaWs {
 
 static size_t mha_plane_elems(int D) { return split_weight_elems(3 * D, D) + split_weight_elems(D, D); }
 
-static size_t mha_ws_floats(int64_t M, int D, int heads) {
-  auto al = [](size_t n) { return align_up(n, 64); };
-  return 2 * al((size_t)M * 3 * D) + 2 * al((size_t)M * D) + al((size_t)M * heads) + al((mha_plane_elems(D) + 1) / 2);
+static void mha_layout(Arena& a, int64_t M, int D, int heads, MhaWs* o) {
+  o->qkv = a.take<float>((size_t)M * 3 * D);
+  o->dqkv = a.take<float>((size_t)M * 3 * D);
+  o->o = a.take<float>((size_t)M * D);
+  o->d_o = a.take<float>((size_t)M * D);
+  o->lse = a.take<float>((size_t)M * heads);
+  o->planes = a.take<uint16_t>(mha_plane_elems(D));
 }
 
-static int mha_carve(void* ws, size_t ws_bytes, int64_t M, int D, int heads, MhaWs* o) {
-  NRL_REQUIRE(ws != nullptr && ((uintptr_t)ws & 255) == 0, "workspace must be 256-byte aligned");
-  if (ws_bytes < mha_ws_floats(M, D, heads) * sizeof(float)) {
-    set_error("workspace too small: %zu < %zu bytes", ws_bytes, mha_ws_floats(M, D, heads) * sizeof(float));
-    return NRL_E_WORKSPACE;
-  }
-  float* p = (float*)ws;
-  auto take = [&](size_t n) { float* r = p; p += align_up(n, 64); return r; };
-  o->qkv = take((size_t)M * 3 * D);
-  o->dqkv = take((size_t)M * 3 * D);
-  o->o = take((size_t)M * D);
-  o->d_o = take((size_t)M * D);
-  o->lse = take((size_t)M * heads);
-  o->planes = reinterpret_cast<uint16_t*>(take((mha_plane_elems(D) + 1) / 2));
-  return NRL_OK;
+// nn.Linear + activation: the weight's planes (filled by the forward), d_pre of the backward
+struct LinearActWs {
+  uint16_t* planes;
+  float* d_pre;
+};
+static void linear_act_layout(Arena& a, int64_t m, int n, int k, LinearActWs* o) {
+  o->planes = a.take<uint16_t>(split_weight_elems(n, k));
+  o->d_pre = a.take<float>((size_t)m * n);
 }
 
 static int mha_check(const NrlMhaParams* p, int64_t S, int64_t Bt) {
@@ -132,7 +116,7 @@ using namespace nrl;
 extern "C" {
 
 size_t nrl_additive_attention_workspace_bytes(int64_t groups, int64_t len, int32_t dim, int32_t query_dim) {
-  return addatt_ws_floats(groups * len, dim, query_dim) * sizeof(float);
+  return measure_workspace<AddAttWs>([&](Arena& a, auto* w) { addatt_layout(a, groups * len, dim, query_dim, w); });
 }
 
 int nrl_additive_attention_fwd(const NrlAddAttParams* p, const float* y, int64_t groups, int64_t len,
@@ -144,7 +128,7 @@ int nrl_additive_attention_fwd(const NrlAddAttParams* p, const float* y, int64_t
   const int D = p->dim, Q = p->query_dim;
   const int64_t M = groups * len;
   AddAttWs w;
-  NRL_TRY(addatt_carve(ws, ws_bytes, M, D, Q, &w));
+  NRL_TRY(carve_workspace(ws, ws_bytes, [&](Arena& a) { addatt_layout(a, M, D, Q, &w); }));
   hipStream_t st = (hipStream_t)stream;
   SplitWeight sa = split_weight_view(w.planes, Q, D);
   if (cur_engine() == ENGINE_BF16X3) NRL_TRY(split_weight(p->att_weight, Q, D, w.planes, &sa, st));
@@ -165,7 +149,7 @@ int nrl_additive_attention_bwd(const NrlAddAttParams* p, const NrlAddAttGrads* g
   const int D = p->dim, Q = p->query_dim;
   const int64_t M = groups * len;
   AddAttWs w;
-  NRL_TRY(addatt_carve(ws, ws_bytes, M, D, Q, &w));
+  NRL_TRY(carve_workspace(ws, ws_bytes, [&](Arena& a) { addatt_layout(a, M, D, Q, &w); }));
   hipStream_t st = (hipStream_t)stream;
   const SplitWeight sa = split_weight_view(w.planes, Q, D);   // filled by the forward
   NRL_TRY(pool_bwd_pre(d_out, y, w.w, w.t, p->att_query, g->att_query, groups, (int)len, Q, D, st));
@@ -177,8 +161,7 @@ int nrl_additive_attention_bwd(const NrlAddAttParams* p, const NrlAddAttGrads* g
 }
 
 size_t nrl_linear_act_workspace_bytes(int64_t m, int32_t n, int32_t k) {
-  (void)k;
-  return align_up(split_weight_elems(n, k) * sizeof(uint16_t), 256) + align_up((size_t)m * n * sizeof(float), 256);
+  return measure_workspace<LinearActWs>([&](Arena& a, auto* w) { linear_act_layout(a, m, n, k, w); });
 }
 
 int nrl_linear_act_fwd(const float* a, const float* w, const float* bias, int64_t m, int32_t n, int32_t k,
@@ -186,16 +169,13 @@ int nrl_linear_act_fwd(const float* a, const float* w, const float* bias, int64_
   NRL_REQUIRE(a && w && c && m >= 0 && n > 0 && k > 0 && k % 4 == 0 && n % 4 == 0,
               "linear_act_fwd: bad arguments (n, k multiples of 4)");
   NRL_REQUIRE(act >= 0 && act <= 2, "linear_act: act must be 0 (none), 1 (tanh) or 2 (relu)");
-  NRL_REQUIRE((((uintptr_t)a | (uintptr_t)w) & 15) == 0 && ws != nullptr && ((uintptr_t)ws & 255) == 0,
-              "linear_act_fwd: operands / workspace misaligned");
-  if (ws_bytes < nrl_linear_act_workspace_bytes(m, n, k)) {
-    set_error("workspace too small: %zu < %zu bytes", ws_bytes, nrl_linear_act_workspace_bytes(m, n, k));
-    return NRL_E_WORKSPACE;
-  }
+  NRL_REQUIRE((((uintptr_t)a | (uintptr_t)w) & 15) == 0, "linear_act_fwd: operands misaligned");
+  LinearActWs lw;
+  NRL_TRY(carve_workspace(ws, ws_bytes, [&](Arena& ar) { linear_act_layout(ar, m, n, k, &lw); }));
   if (m == 0) return NRL_OK;
   hipStream_t st = (hipStream_t)stream;
-  SplitWeight sw = split_weight_view((uint16_t*)ws, n, k);
-  if (cur_engine() == ENGINE_BF16X3) NRL_TRY(split_weight(w, n, k, (uint16_t*)ws, &sw, st));
+  SplitWeight sw = split_weight_view(lw.planes, n, k);
+  if (cur_engine() == ENGINE_BF16X3) NRL_TRY(split_weight(w, n, k, lw.planes, &sw, st));
   return gemm_fwd(KCPlain{a, k, m}, w, sw, EpiLinear{c, n, bias, act, make_dropout(0.0, 0, 0), n}, m, n, k, n <= 224,
                   st);
 }
@@ -206,15 +186,12 @@ int nrl_linear_act_bwd(const float* a, const float* w, const float* c, const flo
   NRL_REQUIRE(a && w && c && d_c && d_w && m >= 0 && n > 0 && k > 0 && k % 4 == 0 && n % 4 == 0,
               "linear_act_bwd: bad arguments");
   NRL_REQUIRE(act >= 0 && act <= 2, "linear_act: act must be 0 (none), 1 (tanh) or 2 (relu)");
-  NRL_REQUIRE(ws != nullptr && ((uintptr_t)ws & 255) == 0, "workspace must be 256-byte aligned");
-  if (ws_bytes < nrl_linear_act_workspace_bytes(m, n, k)) {
-    set_error("workspace too small: %zu < %zu bytes", ws_bytes, nrl_linear_act_workspace_bytes(m, n, k));
-    return NRL_E_WORKSPACE;
-  }
+  LinearActWs lw;
+  NRL_TRY(carve_workspace(ws, ws_bytes, [&](Arena& ar) { linear_act_layout(ar, m, n, k, &lw); }));
   if (m == 0) return NRL_OK;
   hipStream_t st = (hipStream_t)stream;
-  const SplitWeight sw = split_weight_view((uint16_t*)ws, n, k);   // filled by the forward
-  float* d_pre = reinterpret_cast<float*>((unsigned char*)ws + align_up(split_weight_elems(n, k) * sizeof(uint16_t), 256));
+  const SplitWeight sw = split_weight_view(lw.planes, n, k);   // filled by the forward
+  float* const d_pre = lw.d_pre;
   const int64_t n4 = m * n / 4;
   hipLaunchKernelGGL(act_grad_kernel, dim3((unsigned)((n4 + 255) / 256 < 65535 * 16 ? (n4 + 255) / 256 : 65535 * 16)),
                      dim3(256), 0, st, (const float4*)d_c, (const float4*)c, n4, act, (float4*)d_pre);
@@ -227,7 +204,7 @@ int nrl_linear_act_bwd(const float* a, const float* w, const float* c, const flo
 // ---- nn.MultiheadAttention(x, x, x) (batch_first=False) on its own: MINS user encoder, user/mins.py:55-57 ----
 size_t nrl_mha_workspace_bytes(int64_t seq, int64_t batch, int32_t embed_dim, int32_t num_heads) {
   if (seq <= 0 || batch <= 0 || embed_dim <= 0 || num_heads <= 0) return 0;
-  return mha_ws_floats(seq * batch, embed_dim, num_heads) * sizeof(float);
+  return measure_workspace<MhaWs>([&](Arena& a, auto* w) { mha_layout(a, seq * batch, embed_dim, num_heads, w); });
 }
 
 int nrl_mha_fwd(const NrlMhaParams* p, const float* x, int64_t seq, int64_t batch, int32_t save_for_backward,
@@ -239,7 +216,7 @@ int nrl_mha_fwd(const NrlMhaParams* p, const float* x, int64_t seq, int64_t batc
   const int D = p->embed_dim;
   const int64_t M = seq * batch;
   MhaWs w;
-  NRL_TRY(mha_carve(ws, ws_bytes, M, D, p->num_heads, &w));
+  NRL_TRY(carve_workspace(ws, ws_bytes, [&](Arena& a) { mha_layout(a, M, D, p->num_heads, &w); }));
   SplitWeight in, outp;
   NRL_TRY(mha_planes(p, w, cur_engine() == ENGINE_BF16X3, &in, &outp, st));
   const Dropout nodrop = make_dropout(0.0, 0, 0);
@@ -261,7 +238,7 @@ int nrl_mha_bwd(const NrlMhaParams* p, const NrlMhaGrads* g, const float* x, int
   const int D = p->embed_dim;
   const int64_t M = seq * batch;
   MhaWs w;
-  NRL_TRY(mha_carve(ws, ws_bytes, M, D, p->num_heads, &w));
+  NRL_TRY(carve_workspace(ws, ws_bytes, [&](Arena& a) { mha_layout(a, M, D, p->num_heads, &w); }));
   SplitWeight in, outp;
   NRL_TRY(mha_planes(p, w, false, &in, &outp, st));
   const Dropout nodrop = make_dropout(0.0, 0, 0);

@@ -241,49 +241,32 @@ static size_t od_elems(int64_t M, int D, int heads, int64_t pad_rows) {
   return planes > rows ? planes : rows;
 }
 
-static size_t block_ws_floats(int64_t M, int D, int Q, int heads, bool with_x, int64_t pad_rows = 0) {
-  auto al = [](size_t n) { return align_up(n, 64); };
-  size_t n = 0;
-  if (with_x) n += al(x_elems(M, D, pad_rows));
-  n += al(qkv_elems(M, D, heads, pad_rows)) * 2;  // qkv, dqkv
-  n += al(od_elems(M, D, heads, pad_rows)) * 2 + al((size_t)M * D) * 2;      // o, dy | y, d_o (later dx)
-  if (pad_rows > 0 && D == heads * 20)                                       // y planes, d_pre planes
-    n += al((size_t)((M + 31) / 32 * 32) * ((D + 16) / 16) * 16) + al((size_t)((M + 31) / 32 * 32) * ((Q + 15) / 16) * 16);
-  n += al((size_t)M * Q);          // t / d_pre
-  n += al((size_t)M);              // w
-  n += al((size_t)M * heads);      // lse
-  n += al((plane_elems(D, Q) + 1) / 2);  // bf16 weight planes
-  n += al((block_rp_elems(D, Q) + 1) / 2);
-  return n;
-}
-
-static int carve_ws(void* ws, size_t ws_bytes, const BlockShape& s, bool with_x, BlockWs* out) {
-  NRL_REQUIRE(ws != nullptr && ((uintptr_t)ws & 255) == 0, "workspace must be 256-byte aligned");
-  if (ws_bytes < block_ws_floats(s.M, s.D, s.Q, s.heads, with_x, s.pad_rows) * sizeof(float)) {
-    set_error("workspace too small: %zu < %zu bytes", ws_bytes,
-              block_ws_floats(s.M, s.D, s.Q, s.heads, with_x, s.pad_rows) * sizeof(float));
-    return NRL_E_WORKSPACE;
-  }
-  float* p = (float*)ws;
-  auto take = [&](size_t n) { float* r = p; p += align_up(n, 64); return r; };
-  out->x = with_x ? take(x_elems(s.M, s.D, s.pad_rows)) : nullptr;
-  out->qkv = take(qkv_elems(s.M, s.D, s.heads, s.pad_rows));
-  out->dqkv = take(qkv_elems(s.M, s.D, s.heads, s.pad_rows));
-  out->o = take(od_elems(s.M, s.D, s.heads, s.pad_rows));
-  out->y = take((size_t)s.M * s.D);
-  out->dy = take(od_elems(s.M, s.D, s.heads, s.pad_rows));
+// the block's workspace; `x` only for the entries that build their own input rows (with_x)
+static void block_layout(Arena& a, int64_t M, int D, int Q, int heads, bool with_x, int64_t pad_rows, BlockWs* out) {
+  const size_t rows32 = (size_t)((M + 31) / 32 * 32);
+  out->x = with_x ? a.take<float>(x_elems(M, D, pad_rows)) : nullptr;
+  out->qkv = a.take<float>(qkv_elems(M, D, heads, pad_rows));
+  out->dqkv = a.take<float>(qkv_elems(M, D, heads, pad_rows));
+  out->o = a.take<float>(od_elems(M, D, heads, pad_rows));
+  out->y = a.take<float>((size_t)M * D);
+  out->dy = a.take<float>(od_elems(M, D, heads, pad_rows));
   out->yp = out->tp = nullptr;
-  if (s.pad_rows > 0 && s.D == s.heads * 20) {
-    out->yp = take((size_t)((s.M + 31) / 32 * 32) * ((s.D + 16) / 16) * 16);
-    out->tp = take((size_t)((s.M + 31) / 32 * 32) * ((s.Q + 15) / 16) * 16);
+  if (pad_rows > 0 && D == heads * 20) {          // y planes, d_pre planes
+    out->yp = a.take<float>(rows32 * ((D + 16) / 16) * 16);
+    out->tp = a.take<float>(rows32 * ((Q + 15) / 16) * 16);
   }
-  out->d_o = take((size_t)s.M * s.D);
-  out->t = take((size_t)s.M * s.Q);
-  out->w = take((size_t)s.M);
-  out->lse = take((size_t)s.M * s.heads);
-  out->planes = reinterpret_cast<uint16_t*>(take((plane_elems(s.D, s.Q) + 1) / 2));
-  out->rp = reinterpret_cast<uint16_t*>(take((block_rp_elems(s.D, s.Q) + 1) / 2));
-  return NRL_OK;
+  out->d_o = a.take<float>((size_t)M * D);        // (later dx)
+  out->t = a.take<float>((size_t)M * Q);          // t / d_pre
+  out->w = a.take<float>((size_t)M);
+  out->lse = a.take<float>((size_t)M * heads);
+  out->planes = a.take<uint16_t>(plane_elems(D, Q));
+  out->rp = a.take<uint16_t>(block_rp_elems(D, Q));
+}
+static size_t block_ws_bytes(int64_t M, int D, int Q, int heads, bool with_x, int64_t pad_rows = 0) {
+  return measure_workspace<BlockWs>([&](Arena& a, auto* w) { block_layout(a, M, D, Q, heads, with_x, pad_rows, w); });
+}
+static int carve_ws(void* ws, size_t ws_bytes, const BlockShape& s, bool with_x, BlockWs* out) {
+  return carve_workspace(ws, ws_bytes, [&](Arena& a) { block_layout(a, s.M, s.D, s.Q, s.heads, with_x, s.pad_rows, out); });
 }
 
 static int check_params(const NrlBlockParams* p) {

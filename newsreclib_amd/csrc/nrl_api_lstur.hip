@@ -132,59 +132,34 @@ static int cnn_rp_images(const NrlCnnParams* p, const CnnShape& s, const CnnWs& 
 
 static size_t conv_t_plane_elems(int D, int F, int W) { return (size_t)2 * D * ((W * F + 31) / 32 * 32); }
 
-static size_t cnn_ws_floats(const CnnShape& s) {
-  auto al = [](size_t n) { return align_up(n, 64); };
+// (the dense buffers carry W rows of slack on both sides, nrl_conv.h; dx needs none, kept symmetric)
+static void cnn_layout(Arena& a, const CnnShape& s, CnnWs* o) {
   const size_t slack_x = (size_t)s.W * s.D, slack_c = (size_t)s.W * s.F;
-  size_t n = 0;
-  n += al((size_t)s.M * s.D + 2 * slack_x) * 2;  // x, dx (dx needs no slack; kept symmetric)
-  n += al((size_t)s.M * s.F + 2 * slack_c) * 2;  // c, dc
-  n += al((size_t)s.M * s.Q);                    // t / d_pre
-  n += al((size_t)s.M);                          // w
-  n += al((split_weight_elems(s.F, s.W * s.D) + 1) / 2);
-  n += al((split_weight_elems(s.Q, s.F) + 1) / 2);
-  n += al((conv_t_plane_elems(s.D, s.F, s.W) + 1) / 2);
-  n += al((cnn_rp_elems(s) + 1) / 2);
-  if (cnn_conv_planes_ok(s)) {
-    n += al(planes_from_rows_bytes(s.N, cnn_ncb_x(s), 2 * cnn_conv_kt(s)) / 4) + al(planes_from_rows_bytes(s.N, cnn_ncb_dc(s), 2 * cnn_conv_kt(s)) / 4);
-    n += al(wgrad_planes_conv_scratch_floats(5, 2, cnn_ncb_dc(s), cnn_ncb_x(s), cnn_conv_planes_splits()));
-    if ((s.F & 15) == 12 && s.F <= 304 && s.Q <= 224)      // (sized by shape alone: the switches are read per call)
-      n += al(cnn_row_planes_bytes(s.M, cnn_ncb_c(s)) / 4) + al(cnn_row_planes_bytes(s.M, cnn_ncb_q(s)) / 4);
-  }
-  return n;
-}
-
-static int cnn_carve(void* ws, size_t ws_bytes, const CnnShape& s, CnnWs* o) {
-  NRL_REQUIRE(ws != nullptr && ((uintptr_t)ws & 255) == 0, "workspace must be 256-byte aligned");
-  if (ws_bytes < cnn_ws_floats(s) * sizeof(float)) {
-    set_error("workspace too small: %zu < %zu bytes", ws_bytes, cnn_ws_floats(s) * sizeof(float));
-    return NRL_E_WORKSPACE;
-  }
-  float* p = (float*)ws;
-  auto take = [&](size_t n) { float* r = p; p += align_up(n, 64); return r; };
-  const size_t slack_x = (size_t)s.W * s.D, slack_c = (size_t)s.W * s.F;
-  o->x = take((size_t)s.M * s.D + 2 * slack_x) + slack_x;
-  o->dx = take((size_t)s.M * s.D + 2 * slack_x) + slack_x;
-  o->c = take((size_t)s.M * s.F + 2 * slack_c) + slack_c;
-  o->dc = take((size_t)s.M * s.F + 2 * slack_c) + slack_c;
-  o->t = take((size_t)s.M * s.Q);
-  o->w = take((size_t)s.M);
-  o->planes_conv = reinterpret_cast<uint16_t*>(take((split_weight_elems(s.F, s.W * s.D) + 1) / 2));
-  o->planes_att = reinterpret_cast<uint16_t*>(take((split_weight_elems(s.Q, s.F) + 1) / 2));
-  o->planes_conv_t = reinterpret_cast<uint16_t*>(take((conv_t_plane_elems(s.D, s.F, s.W) + 1) / 2));
-  o->rp = reinterpret_cast<uint16_t*>(take((cnn_rp_elems(s) + 1) / 2));
+  o->x = a.take_after<float>(slack_x, (size_t)s.M * s.D + 2 * slack_x);
+  o->dx = a.take_after<float>(slack_x, (size_t)s.M * s.D + 2 * slack_x);
+  o->c = a.take_after<float>(slack_c, (size_t)s.M * s.F + 2 * slack_c);
+  o->dc = a.take_after<float>(slack_c, (size_t)s.M * s.F + 2 * slack_c);
+  o->t = a.take<float>((size_t)s.M * s.Q);       // t / d_pre
+  o->w = a.take<float>((size_t)s.M);
+  o->planes_conv = a.take<uint16_t>(split_weight_elems(s.F, s.W * s.D));
+  o->planes_att = a.take<uint16_t>(split_weight_elems(s.Q, s.F));
+  o->planes_conv_t = a.take<uint16_t>(conv_t_plane_elems(s.D, s.F, s.W));
+  o->rp = a.take<uint16_t>(cnn_rp_elems(s));
   o->xpl = o->dpl = nullptr;
   o->wsc = nullptr;
   o->cpl = o->tpl = nullptr;
   if (cnn_conv_planes_ok(s)) {
-    o->xpl = reinterpret_cast<unsigned char*>(take(planes_from_rows_bytes(s.N, cnn_ncb_x(s), 2 * cnn_conv_kt(s)) / 4));
-    o->dpl = reinterpret_cast<unsigned char*>(take(planes_from_rows_bytes(s.N, cnn_ncb_dc(s), 2 * cnn_conv_kt(s)) / 4));
-    o->wsc = take(wgrad_planes_conv_scratch_floats(5, 2, cnn_ncb_dc(s), cnn_ncb_x(s), cnn_conv_planes_splits()));
-    if ((s.F & 15) == 12 && s.F <= 304 && s.Q <= 224) {
-      o->cpl = reinterpret_cast<unsigned char*>(take(cnn_row_planes_bytes(s.M, cnn_ncb_c(s)) / 4));
-      o->tpl = reinterpret_cast<unsigned char*>(take(cnn_row_planes_bytes(s.M, cnn_ncb_q(s)) / 4));
+    o->xpl = a.take<unsigned char>(planes_from_rows_bytes(s.N, cnn_ncb_x(s), 2 * cnn_conv_kt(s)));
+    o->dpl = a.take<unsigned char>(planes_from_rows_bytes(s.N, cnn_ncb_dc(s), 2 * cnn_conv_kt(s)));
+    o->wsc = a.take<float>(wgrad_planes_conv_scratch_floats(5, 2, cnn_ncb_dc(s), cnn_ncb_x(s), cnn_conv_planes_splits()));
+    if ((s.F & 15) == 12 && s.F <= 304 && s.Q <= 224) {    // (present by shape alone: the switches are read per call)
+      o->cpl = a.take<unsigned char>(cnn_row_planes_bytes(s.M, cnn_ncb_c(s)));
+      o->tpl = a.take<unsigned char>(cnn_row_planes_bytes(s.M, cnn_ncb_q(s)));
     }
   }
-  return NRL_OK;
+}
+static size_t cnn_ws_bytes(const CnnShape& s) {
+  return measure_workspace<CnnWs>([&](Arena& a, auto* w) { cnn_layout(a, s, w); });
 }
 
 static int cnn_check(const NrlCnnParams* p, int64_t n_news, int L, CnnShape* s) {
@@ -255,41 +230,18 @@ struct GruWs {
   uint16_t *planes_ih, *planes_hh;
 };
 
-static size_t gru_ws_floats(const GruShape& s) {
-  auto al = [](size_t n) { return align_up(n, 64); };
+static void gru_layout(Arena& a, const GruShape& s, GruWs* o) {
   const size_t TB = (size_t)s.T * s.B;
-  size_t n = 0;
-  n += al(TB * s.Din) * 2;               // x_tm, dx_tm
-  n += al(TB * 3 * s.Hd) * 2;            // g (gi -> gates -> dgi), dgh
-  n += al((size_t)s.B * 3 * s.Hd);       // gh of the current step
-  n += al(TB * s.Hd);                    // ghn
-  n += al((TB + s.B) * s.Hd);            // hs[0..T]
-  n += al((size_t)s.B * s.Hd);           // dh
-  n += al((split_weight_elems(3 * s.Hd, s.Din) + 1) / 2);
-  n += al((split_weight_elems(3 * s.Hd, s.Hd) + 1) / 2);
-  return n;
-}
-
-static int gru_carve(void* ws, size_t ws_bytes, const GruShape& s, GruWs* o) {
-  NRL_REQUIRE(ws != nullptr && ((uintptr_t)ws & 255) == 0, "workspace must be 256-byte aligned");
-  if (ws_bytes < gru_ws_floats(s) * sizeof(float)) {
-    set_error("workspace too small: %zu < %zu bytes", ws_bytes, gru_ws_floats(s) * sizeof(float));
-    return NRL_E_WORKSPACE;
-  }
-  float* p = (float*)ws;
-  auto take = [&](size_t n) { float* r = p; p += align_up(n, 64); return r; };
-  const size_t TB = (size_t)s.T * s.B;
-  o->x_tm = take(TB * s.Din);
-  o->dx_tm = take(TB * s.Din);
-  o->g = take(TB * 3 * s.Hd);
-  o->dgh = take(TB * 3 * s.Hd);
-  o->gh = take((size_t)s.B * 3 * s.Hd);
-  o->ghn = take(TB * s.Hd);
-  o->hs = take((TB + s.B) * s.Hd);
-  o->dh = take((size_t)s.B * s.Hd);
-  o->planes_ih = reinterpret_cast<uint16_t*>(take((split_weight_elems(3 * s.Hd, s.Din) + 1) / 2));
-  o->planes_hh = reinterpret_cast<uint16_t*>(take((split_weight_elems(3 * s.Hd, s.Hd) + 1) / 2));
-  return NRL_OK;
+  o->x_tm = a.take<float>(TB * s.Din);
+  o->dx_tm = a.take<float>(TB * s.Din);
+  o->g = a.take<float>(TB * 3 * s.Hd);            // gi -> gates -> dgi
+  o->dgh = a.take<float>(TB * 3 * s.Hd);
+  o->gh = a.take<float>((size_t)s.B * 3 * s.Hd);  // gh of the current step
+  o->ghn = a.take<float>(TB * s.Hd);
+  o->hs = a.take<float>((TB + s.B) * s.Hd);       // hs[0..T]
+  o->dh = a.take<float>((size_t)s.B * s.Hd);
+  o->planes_ih = a.take<uint16_t>(split_weight_elems(3 * s.Hd, s.Din));
+  o->planes_hh = a.take<uint16_t>(split_weight_elems(3 * s.Hd, s.Hd));
 }
 
 static int gru_check(const NrlGruParams* p, int64_t B, int64_t T, GruShape* s) {
@@ -356,7 +308,7 @@ size_t nrl_cnn_encoder_workspace_bytes(int64_t n_news, int32_t seq_len, int32_t 
   CnnShape s;
   s.N = n_news; s.L = seq_len; s.M = n_news * seq_len; s.D = embed_dim; s.F = num_filters; s.W = window;
   s.Q = query_dim; s.pad = (window - 1) / 2;
-  return cnn_ws_floats(s) * sizeof(float);
+  return cnn_ws_bytes(s);
 }
 
 int nrl_cnn_encoder_fwd(const NrlCnnParams* p, const float* emb_table, int64_t vocab, const int64_t* ids,
@@ -369,7 +321,7 @@ int nrl_cnn_encoder_fwd(const NrlCnnParams* p, const float* emb_table, int64_t v
   NRL_REQUIRE(p_drop >= 0.0 && p_drop < 1.0, "p_drop must be in [0, 1)");
   if (s.M == 0) return NRL_OK;
   CnnWs w;
-  NRL_TRY(cnn_carve(ws, ws_bytes, s, &w));
+  NRL_TRY(carve_workspace(ws, ws_bytes, [&](Arena& a) { cnn_layout(a, s, &w); }));
   hipStream_t st = (hipStream_t)stream;
   const Dropout drop1 = make_dropout(p_drop, seed, stream0), drop2 = make_dropout(p_drop, seed, stream0 + 1);
   const Dropout nodrop = make_dropout(0.0, 0, 0);
@@ -434,7 +386,7 @@ int nrl_cnn_encoder_bwd(const NrlCnnParams* p, const NrlCnnGrads* g, float* d_em
   NRL_REQUIRE(d_emb_table && ids && d_out, "cnn_encoder_bwd: null argument");
   if (s.M == 0) return NRL_OK;
   CnnWs w;
-  NRL_TRY(cnn_carve(ws, ws_bytes, s, &w));
+  NRL_TRY(carve_workspace(ws, ws_bytes, [&](Arena& a) { cnn_layout(a, s, &w); }));
   hipStream_t st = (hipStream_t)stream;
   const Dropout drop1 = make_dropout(p_drop, seed, stream0), drop2 = make_dropout(p_drop, seed, stream0 + 1);
   const SplitWeight sa = planes_view(w.planes_att, s.Q, s.F);
@@ -477,12 +429,19 @@ int nrl_cnn_encoder_bwd(const NrlCnnParams* p, const NrlCnnGrads* g, float* d_em
 }
 
 // ---- CNN + multi-head self-attention + additive attention text encoder (CenNewsRec) ----------------------
+// one arena: the CNN's regions, then the block's (whose padded fragment-block planes belong to the fused NRMS news path only:
+// pad_rows = 0)
+static void cnn_mhsa_layout(Arena& a, const CnnShape& s, int heads, CnnWs* cw, BlockWs* bw) {
+  cnn_layout(a, s, cw);
+  block_layout(a, s.M, s.F, s.Q, heads, false, 0, bw);
+}
 size_t nrl_cnn_mhsa_encoder_workspace_bytes(int64_t n_news, int32_t seq_len, int32_t embed_dim, int32_t num_filters,
                                             int32_t window, int32_t num_heads, int32_t query_dim) {
   CnnShape s;
   s.N = n_news; s.L = seq_len; s.M = n_news * seq_len; s.D = embed_dim; s.F = num_filters; s.W = window;
   s.Q = query_dim; s.pad = (window - 1) / 2;
-  return (cnn_ws_floats(s) + align_up(block_ws_floats(s.M, num_filters, query_dim, num_heads, false), 64)) * sizeof(float);
+  BlockWs bw;
+  return measure_workspace<CnnWs>([&](Arena& a, auto* cw) { cnn_mhsa_layout(a, s, num_heads, cw, &bw); });
 }
 
 static int cnn_mhsa_carve(const NrlCnnParams* cp, const NrlBlockParams* bp, int64_t n_news, int L, void* ws,
@@ -498,16 +457,8 @@ static int cnn_mhsa_carve(const NrlCnnParams* cp, const NrlBlockParams* bp, int6
   cs->Q = bp->query_dim; cs->pad = (cp->window - 1) / 2;
   NRL_REQUIRE(cs->M * (int64_t)(cs->D > cs->F ? cs->D : cs->F) < (1LL << 32), "dropout index space is 32-bit");
   *bs = news_shape(bp, n_news, L);
-  bs->pad_rows = 0;   // (the padded fragment-block planes belong to the fused NRMS news path only)
-  const size_t cnn_bytes = cnn_ws_floats(*cs) * sizeof(float);
-  NRL_REQUIRE(ws != nullptr && ((uintptr_t)ws & 255) == 0, "workspace must be 256-byte aligned");
-  if (ws_bytes < cnn_bytes + block_ws_floats(cs->M, cs->F, cs->Q, bp->num_heads, false) * sizeof(float)) {
-    set_error("workspace too small: %zu bytes", ws_bytes);
-    return NRL_E_WORKSPACE;
-  }
-  NRL_TRY(cnn_carve(ws, cnn_bytes, *cs, cw));
-  NRL_TRY(carve_ws((unsigned char*)ws + cnn_bytes, ws_bytes - cnn_bytes, *bs, false, bw));
-  return NRL_OK;
+  bs->pad_rows = 0;
+  return carve_workspace(ws, ws_bytes, [&](Arena& a) { cnn_mhsa_layout(a, *cs, bp->num_heads, cw, bw); });
 }
 
 int nrl_cnn_mhsa_encoder_fwd(const NrlCnnParams* cp, const NrlBlockParams* bp, const float* emb_table, int64_t vocab,
@@ -609,8 +560,8 @@ int nrl_embedding_rows_bwd(const float* d_out, const int64_t* ids, int64_t n_ids
 }
 
 size_t nrl_gru_workspace_bytes(int64_t batch, int64_t max_len, int32_t input_dim, int32_t hidden_dim) {
-  GruShape s{batch, max_len, input_dim, hidden_dim};
-  return gru_ws_floats(s) * sizeof(float);
+  const GruShape s{batch, max_len, input_dim, hidden_dim};
+  return measure_workspace<GruWs>([&](Arena& a, auto* w) { gru_layout(a, s, w); });
 }
 
 int nrl_gru_fwd(const NrlGruParams* p, const float* hist, const int64_t* lengths, const float* h0, int64_t batch,
@@ -620,7 +571,7 @@ int nrl_gru_fwd(const NrlGruParams* p, const float* hist, const int64_t* lengths
   NRL_TRY(gru_check(p, batch, max_len, &s));
   NRL_REQUIRE(hist && lengths && out, "gru_fwd: null argument");
   GruWs w;
-  NRL_TRY(gru_carve(ws, ws_bytes, s, &w));
+  NRL_TRY(carve_workspace(ws, ws_bytes, [&](Arena& a) { gru_layout(a, s, &w); }));
   hipStream_t st = (hipStream_t)stream;
   const int Hd = s.Hd, Din = s.Din;
   const int64_t B = s.B, T = s.T;
@@ -677,7 +628,7 @@ int nrl_gru_bwd(const NrlGruParams* p, const NrlGruGrads* g, const float* hist, 
   NRL_REQUIRE(g && g->weight_ih && g->weight_hh && g->bias_ih && g->bias_hh, "null GRU gradient pointer");
   NRL_REQUIRE(lengths && d_out && d_hist, "gru_bwd: null argument");
   GruWs w;
-  NRL_TRY(gru_carve(ws, ws_bytes, s, &w));
+  NRL_TRY(carve_workspace(ws, ws_bytes, [&](Arena& a) { gru_layout(a, s, &w); }));
   hipStream_t st = (hipStream_t)stream;
   const int Hd = s.Hd, Din = s.Din;
   const int64_t B = s.B, T = s.T;
@@ -725,7 +676,11 @@ static int npa_check(const NrlCnnParams* p, int64_t n_news, int L, const float* 
   return NRL_OK;
 }
 
-static size_t npa_ws_floats(const CnnShape& s) { return cnn_ws_floats(s) + align_up((size_t)s.N * s.F, 64); }
+// NPA = the CNN workspace + the per-row query gradients of the backward
+static void npa_layout(Arena& a, const CnnShape& s, CnnWs* w, float** dq) {
+  cnn_layout(a, s, w);
+  *dq = a.take<float>((size_t)s.N * s.F);
+}
 
 // x = dropout(emb[ids]); c_out (M, F) = dropout(relu(conv(x) + b)) under the current engine: the lookup and convolution stages of
 // nrl_npa_encoder_fwd and nrl_npa_conv_features (which passes its caller's buffer as c_out and no dropout).
@@ -760,7 +715,9 @@ extern "C" {
 
 size_t nrl_npa_encoder_workspace_bytes(int64_t n_news, int32_t seq_len, int32_t embed_dim, int32_t num_filters,
                                        int32_t window) {
-  return npa_ws_floats(npa_shape(n_news, seq_len, embed_dim, num_filters, window)) * sizeof(float);
+  float* dq;
+  return measure_workspace<CnnWs>(
+      [&](Arena& a, auto* w) { npa_layout(a, npa_shape(n_news, seq_len, embed_dim, num_filters, window), w, &dq); });
 }
 
 int nrl_npa_encoder_fwd(const NrlCnnParams* p, const float* emb_table, int64_t vocab, const int64_t* ids, int64_t n_news,
@@ -773,9 +730,9 @@ int nrl_npa_encoder_fwd(const NrlCnnParams* p, const float* emb_table, int64_t v
   NRL_REQUIRE(emb_table && ids && out, "npa_encoder_fwd: null argument");
   NRL_REQUIRE(p_drop >= 0.0 && p_drop < 1.0, "p_drop must be in [0, 1)");
   if (s.M == 0) return NRL_OK;
-  NRL_REQUIRE(ws_bytes >= npa_ws_floats(s) * sizeof(float), "npa_encoder_fwd: workspace too small");
   CnnWs w;
-  NRL_TRY(cnn_carve(ws, ws_bytes, s, &w));
+  float* dq;
+  NRL_TRY(carve_workspace(ws, ws_bytes, [&](Arena& a) { npa_layout(a, s, &w, &dq); }));
   hipStream_t st = (hipStream_t)stream;
   const Dropout drop1 = make_dropout(p_drop, seed, stream0), drop2 = make_dropout(p_drop, seed, stream0 + 1);
   NRL_TRY(npa_conv_stage(p, s, w, emb_table, ids, drop1, drop2, w.c, st));
@@ -785,7 +742,7 @@ int nrl_npa_encoder_fwd(const NrlCnnParams* p, const float* emb_table, int64_t v
 
 size_t nrl_npa_conv_features_workspace_bytes(int64_t n_news, int32_t seq_len, int32_t embed_dim, int32_t num_filters,
                                              int32_t window) {
-  return cnn_ws_floats(npa_shape(n_news, seq_len, embed_dim, num_filters, window)) * sizeof(float);
+  return cnn_ws_bytes(npa_shape(n_news, seq_len, embed_dim, num_filters, window));
 }
 
 // c = relu(conv(emb[ids]) + b) (text.py:377-383 in eval mode) straight into the caller's (n_news, L, F) buffer
@@ -802,7 +759,7 @@ int nrl_npa_conv_features(const NrlCnnParams* p, const float* emb_table, int64_t
   NRL_REQUIRE(s.M * (int64_t)(s.D > s.F ? s.D : s.F) < (1LL << 32), "row index space is 32-bit: encode the table in chunks");
   if (s.M == 0) return NRL_OK;
   CnnWs w;
-  NRL_TRY(cnn_carve(ws, ws_bytes, s, &w));
+  NRL_TRY(carve_workspace(ws, ws_bytes, [&](Arena& a) { cnn_layout(a, s, &w); }));
   const Dropout none = make_dropout(0.0, 0, 0);
   return npa_conv_stage(p, s, w, emb_table, ids, none, none, out, (hipStream_t)stream);
 }
@@ -822,10 +779,9 @@ int nrl_npa_encoder_bwd(const NrlCnnParams* p, const NrlCnnGrads* g, float* d_em
     if (n_queries > 0) NRL_HIP(hipMemsetAsync(d_queries, 0, (size_t)n_queries * s.F * sizeof(float), st));
     return NRL_OK;
   }
-  NRL_REQUIRE(ws_bytes >= npa_ws_floats(s) * sizeof(float), "npa_encoder_bwd: workspace too small");
   CnnWs w;
-  NRL_TRY(cnn_carve(ws, ws_bytes, s, &w));
-  float* dq = reinterpret_cast<float*>(ws) + cnn_ws_floats(s);
+  float* dq;
+  NRL_TRY(carve_workspace(ws, ws_bytes, [&](Arena& a) { npa_layout(a, s, &w, &dq); }));
   const Dropout drop1 = make_dropout(p_drop, seed, stream0), drop2 = make_dropout(p_drop, seed, stream0 + 1);
   CnnRp rp;
   NRL_TRY(cnn_rp_images(p, s, w, false, &rp, st));        // built by the forward; weights unchanged since

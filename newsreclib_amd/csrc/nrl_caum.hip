@@ -509,25 +509,34 @@ int nrl_caum_score_fwd(const float* z2, const float* w3, const float* b3, const 
   return NRL_OK;
 }
 
+// score backward: d_logit per (impression, slot, history row) | the column-sum partials of every row chunk, packed floats
+struct CaumScoreWs {
+  float *d_logit, *part;
+};
+static void caum_score_layout(Arena& a, int64_t B, int C, int H, int N2, CaumScoreWs* w) {
+  const int64_t R = B * C * H;
+  w->d_logit = a.take<float>((size_t)R, sizeof(float));
+  w->part = a.take<float>((size_t)(ceil_div(R, CAUM_RED_ROWS) * (int64_t)(N2 + 1)), sizeof(float));
+}
+
 size_t nrl_caum_score_workspace_bytes(int64_t B, int32_t C, int32_t H, int32_t N2) {
   if (B <= 0 || C <= 0 || H <= 0 || N2 <= 0) return 0;
-  const int64_t R = B * C * H;
-  return (size_t)(R + ceil_div(R, CAUM_RED_ROWS) * (int64_t)(N2 + 1)) * sizeof(float);
+  return measure_workspace<CaumScoreWs>([&](Arena& a, auto* w) { caum_score_layout(a, B, C, H, N2, w); });
 }
 
 int nrl_caum_score_bwd(const float* d_scores, const float* z2, const float* w3, const float* x, const float* cd,
                        const float* alpha, const float* user, const int64_t* cand_offsets, int64_t B, int32_t C,
                        int32_t slot0, int32_t H, int32_t N2, int32_t U, float* d_z2, float* d_x, float* d_cd, float* d_w3,
                        float* d_b3, void* ws, size_t ws_bytes, void* stream) {
-  NRL_REQUIRE(d_scores && z2 && w3 && x && cd && alpha && user && cand_offsets && d_z2 && d_x && d_cd && d_w3 && d_b3 && ws,
+  NRL_REQUIRE(d_scores && z2 && w3 && x && cd && alpha && user && cand_offsets && d_z2 && d_x && d_cd && d_w3 && d_b3,
               "caum_score_bwd: null pointer");
   NRL_REQUIRE(B > 0 && C > 0 && slot0 >= 0 && H > 0 && H <= 8192 && N2 > 0 && U > 0,
               "caum_score_bwd: bad dimensions (max_hist <= 8192)");
-  NRL_REQUIRE(ws_bytes >= nrl_caum_score_workspace_bytes(B, C, H, N2), "caum_score_bwd: workspace too small");
+  CaumScoreWs w;
+  NRL_TRY(carve_workspace(ws, ws_bytes, [&](Arena& a) { caum_score_layout(a, B, C, H, N2, &w); }));
   hipStream_t st = (hipStream_t)stream;
   const int64_t R = B * C * H, chunks = ceil_div(R, CAUM_RED_ROWS);
-  float* d_logit = (float*)ws;
-  float* part = d_logit + R;
+  float *const d_logit = w.d_logit, *const part = w.part;
   const size_t lds = H * sizeof(float);
   hipLaunchKernelGGL(caum_score_bwd_kernel, dim3((unsigned)(B * C)), dim3(CAUM_THREADS), lds, st, d_scores, w3, x, cd, alpha,
                      user, cand_offsets, C, slot0, H, N2, U, d_z2, d_x, d_cd, d_logit);

@@ -5,6 +5,7 @@
 #include <stdio.h>
 
 #include "../../include/newsreclib_amd.h"
+#include "nrl_arena.h"
 
 namespace nrl {
 
@@ -35,6 +36,32 @@ void set_error(const char* fmt, ...);
     int rc__ = (expr);           \
     if (rc__ != NRL_OK) return rc__; \
   } while (0)
+
+// ---- workspaces (nrl_arena.h) --------------------------------------------------------------------
+// The one workspace check of every entry point.  `layout(Arena&)` names the regions; it runs once measuring and, when the
+// caller's buffer holds that many bytes, once more carving.  Null / misaligned: NRL_E_INVALID; short: NRL_E_WORKSPACE.
+template <class Layout>
+static inline int carve_workspace(void* ws, size_t ws_bytes, Layout&& layout) {
+  NRL_REQUIRE(ws != nullptr && ((uintptr_t)ws & 255) == 0, "workspace must be 256-byte aligned");
+  Arena need;
+  layout(need);
+  if (ws_bytes < need.bytes()) {
+    set_error("workspace too small: %zu < %zu bytes", ws_bytes, need.bytes());
+    return NRL_E_WORKSPACE;
+  }
+  Arena a(ws);
+  layout(a);
+  return NRL_OK;
+}
+
+// the `*_workspace_bytes` side: the same layout on a measuring arena, its pointers thrown away
+template <class Ws, class Layout>
+static inline size_t measure_workspace(Layout&& layout) {
+  Arena a;
+  Ws w;
+  layout(a, &w);
+  return a.bytes();
+}
 
 // ---- dropout keep mask (normative statement in oracle/nrms_oracle.py) -------------------------
 __host__ __device__ __forceinline__ uint32_t lowbias32(uint32_t x) {

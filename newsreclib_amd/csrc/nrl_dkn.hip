@@ -240,33 +240,27 @@ static size_t dkn_plane_elems(const DknShape& s) {
 }
 
 // forward: x | c | e | planes | planes_t;  backward adds dxw | de | wimg | part (the forward's x must survive; c and e are reused)
-static size_t dkn_ws_bytes(const DknShape& s) {
-  auto al = [](size_t n) { return align_up(n, 64); };
-  const int64_t slack = s.Wmax;
-  size_t f = al((size_t)(s.M + 2 * slack) * s.inner) + al((size_t)(s.M + 2 * slack) * s.F) + al((size_t)s.M * s.Ed) +
-             al((size_t)s.M * s.D) + al((size_t)s.M * (s.inner - s.D)) + al((size_t)s.F * s.Wmax * s.inner) +
-             al(dkn_part_floats(s));
-  f += 2 * al((dkn_plane_elems(s) + 1) / 2);
-  return f * sizeof(float);
+static void dkn_layout(Arena& a, const DknShape& s, DknWs* w) {
+  const size_t slack = (size_t)s.Wmax;
+  w->x = a.take_after<float>(slack * s.inner, (size_t)(s.M + 2 * slack) * s.inner);
+  w->c = a.take_after<float>(slack * s.F, (size_t)(s.M + 2 * slack) * s.F);
+  w->e = a.take<float>((size_t)s.M * s.Ed);
+  w->dxw = a.take<float>((size_t)s.M * s.D);
+  w->de = a.take<float>((size_t)s.M * (s.inner - s.D));
+  w->wimg = a.take<float>((size_t)s.F * s.Wmax * s.inner);
+  w->part = a.take<float>(dkn_part_floats(s));
+  w->planes = a.take<uint16_t>(dkn_plane_elems(s));
+  w->planes_t = a.take<uint16_t>(dkn_plane_elems(s));
 }
 
-static int dkn_carve(void* ws, size_t ws_bytes, const DknShape& s, DknWs* w) {
-  NRL_REQUIRE(ws != nullptr && ((uintptr_t)ws & 255) == 0, "workspace must be 256-byte aligned");
-  NRL_REQUIRE(ws_bytes >= dkn_ws_bytes(s), "dkn encoder: workspace too small");
-  float* p = reinterpret_cast<float*>(ws);
-  auto take = [&](size_t n) { float* r = p; p += align_up(n, 64); return r; };
-  const int64_t slack = s.Wmax;
-  w->x = take((size_t)(s.M + 2 * slack) * s.inner) + slack * s.inner;
-  w->c = take((size_t)(s.M + 2 * slack) * s.F) + slack * s.F;
-  w->e = take((size_t)s.M * s.Ed);
-  w->dxw = take((size_t)s.M * s.D);
-  w->de = take((size_t)s.M * (s.inner - s.D));
-  w->wimg = take((size_t)s.F * s.Wmax * s.inner);
-  w->part = take(dkn_part_floats(s));
-  const size_t pe = (dkn_plane_elems(s) + 1) / 2;
-  w->planes = reinterpret_cast<uint16_t*>(take(pe));
-  w->planes_t = reinterpret_cast<uint16_t*>(take(pe));
-  return NRL_OK;
+// click backward: d(user vector) rows + their column sum in row `batch` | dz | hr, packed floats
+struct DknClickWs {
+  float *dv, *dz, *hr;
+};
+static void dkn_click_layout(Arena& a, int64_t batch, int max_cand, int dim, int hidden, DknClickWs* w) {
+  w->dv = a.take<float>((size_t)((batch + 1) * (int64_t)dim), sizeof(float));
+  w->dz = a.take<float>((size_t)(batch * (int64_t)max_cand * hidden), sizeof(float));
+  w->hr = a.take<float>((size_t)(batch * (int64_t)max_cand * hidden), sizeof(float));
 }
 
 static int dkn_check(const NrlDknParams* p, int64_t n_news, int L, DknShape* s) {
@@ -301,7 +295,7 @@ extern "C" {
 size_t nrl_dkn_encoder_workspace_bytes(const NrlDknParams* p, int64_t n_news, int32_t seq_len) {
   DknShape s;
   if (dkn_check(p, n_news, seq_len, &s) != NRL_OK) return 0;
-  return dkn_ws_bytes(s);
+  return measure_workspace<DknWs>([&](Arena& a, auto* w) { dkn_layout(a, s, w); });
 }
 
 int nrl_dkn_encoder_fwd(const NrlDknParams* p, const int64_t* ids, const int64_t* entity_ids, int64_t n_news,
@@ -311,7 +305,7 @@ int nrl_dkn_encoder_fwd(const NrlDknParams* p, const int64_t* ids, const int64_t
   NRL_REQUIRE(ids && entity_ids && out && argmax, "dkn encoder fwd: null argument");
   if (s.M == 0) return NRL_OK;
   DknWs w;
-  NRL_TRY(dkn_carve(ws, ws_bytes, s, &w));
+  NRL_TRY(carve_workspace(ws, ws_bytes, [&](Arena& a) { dkn_layout(a, s, &w); }));
   hipStream_t st = (hipStream_t)stream;
   const Dropout nodrop = make_dropout(0.0, 0, 0);
   // X = [word rows | tanh(E[ids] T + b) | tanh(C[ids] T + b)]   (news.py:271-291)
@@ -354,7 +348,7 @@ int nrl_dkn_encoder_bwd(const NrlDknParams* p, const NrlDknGrads* g, const int64
   for (int i = 0; i < s.nw; ++i) NRL_REQUIRE(g->conv_weight[i] && g->conv_bias[i], "dkn encoder bwd: null conv gradient");
   if (s.M == 0) return NRL_OK;
   DknWs w;
-  NRL_TRY(dkn_carve(ws, ws_bytes, s, &w));
+  NRL_TRY(carve_workspace(ws, ws_bytes, [&](Arena& a) { dkn_layout(a, s, &w); }));
   hipStream_t st = (hipStream_t)stream;
   const Dropout nodrop = make_dropout(0.0, 0, 0);
   const int64_t ldo = (int64_t)s.nw * s.F;
@@ -711,7 +705,7 @@ static int dkn_click_check(const NrlDknClickParams* p, int64_t B, int max_hist, 
 extern "C" {
 
 size_t nrl_dkn_click_workspace_bytes(int64_t batch, int32_t max_cand, int32_t dim, int32_t hidden) {
-  return (size_t)((batch + 1) * (int64_t)dim + 2 * batch * (int64_t)max_cand * hidden) * sizeof(float);
+  return measure_workspace<DknClickWs>([&](Arena& a, auto* w) { dkn_click_layout(a, batch, max_cand, dim, hidden, w); });
 }
 
 int nrl_dkn_click_fwd(const NrlDknClickParams* p, const float* hist, const int64_t* hist_offsets, int32_t max_hist,
@@ -735,12 +729,10 @@ int nrl_dkn_click_bwd(const NrlDknClickParams* p, const NrlDknClickGrads* g, con
               "dkn click bwd: null gradient");
   NRL_REQUIRE(hist_offsets && cand_offsets && user && d_scores && d_hist && d_cand, "dkn click bwd: null argument");
   if (batch == 0) return NRL_OK;
-  NRL_REQUIRE(ws != nullptr && ws_bytes >= nrl_dkn_click_workspace_bytes(batch, max_cand, dim, p->hidden),
-              "dkn click bwd: workspace too small");
+  DknClickWs w;
+  NRL_TRY(carve_workspace(ws, ws_bytes, [&](Arena& a) { dkn_click_layout(a, batch, max_cand, dim, p->hidden, &w); }));
   hipStream_t st = (hipStream_t)stream;
-  float* dv = reinterpret_cast<float*>(ws);
-  float* dz = dv + (batch + 1) * dim;      // (row `batch` of dv: its column sum)
-  float* hr = dz + batch * (int64_t)max_cand * p->hidden;
+  float *const dv = w.dv, *const dz = w.dz, *const hr = w.hr;
   hipLaunchKernelGGL(dkn_click_bwd_kernel, dim3((unsigned)batch), dim3(DKN_THREADS), 0, st, *p, hist, hist_offsets, cand,
                      cand_offsets, max_cand, dim, d_scores, d_hist, d_cand, dv, dz, hr);
   NRL_LAUNCH_CHECK();

@@ -248,42 +248,43 @@ using namespace nrl;
 
 extern "C" {
 
-static size_t mn_gemm_ws(int64_t Np, int32_t D) { return align_up(nrl_linear_workspace_bytes((int32_t)Np, D), 256); }
+// workspace of the two nrl_linear_* calls | E padded to Np rows | S | G | row stats | per-chunk dE (more than one column chunk only)
+struct SupconWs {
+  unsigned char* gemm;
+  size_t gemm_bytes;
+  float *Epad, *S, *G, *stats, *part;
+};
+static void supcon_layout(Arena& a, int64_t N, int32_t D, SupconWs* w) {
+  const int64_t Np = (N + 3) & ~(int64_t)3;
+  const int64_t chunks = ceil_div(Np, MN_KCHUNK);
+  w->gemm_bytes = Arena::round_up(nrl_linear_workspace_bytes((int32_t)Np, D), 256);
+  w->gemm = a.take<unsigned char>(w->gemm_bytes);
+  w->Epad = a.take<float>((size_t)Np * D);
+  w->S = a.take<float>((size_t)N * Np);
+  w->G = a.take<float>((size_t)N * Np);
+  w->stats = a.take<float>((size_t)3 * N);
+  w->part = chunks > 1 ? a.take<float>((size_t)chunks * N * D) : nullptr;
+}
 
 size_t nrl_supcon_embed_workspace_bytes(int64_t N, int32_t D) {
   if (N <= 0 || D <= 0) return 256;
-  const int64_t Np = (N + 3) & ~(int64_t)3;
-  const int64_t chunks = ceil_div(Np, MN_KCHUNK);
-  return mn_gemm_ws(Np, D) + align_up((size_t)Np * D * sizeof(float), 256) + 2 * align_up((size_t)N * Np * sizeof(float), 256) +
-         align_up((size_t)3 * N * sizeof(float), 256) + (chunks > 1 ? align_up((size_t)chunks * N * D * sizeof(float), 256) : 0);
+  return measure_workspace<SupconWs>([&](Arena& a, auto* w) { supcon_layout(a, N, D, w); });
 }
 
 int nrl_supcon_embed_fwd_bwd(const float* E, const int64_t* labels, int64_t N, int32_t D, float temperature, float grad_scale,
                              float* loss, float* dE, void* ws, size_t ws_bytes, void* stream) {
-  NRL_REQUIRE(E && labels && loss && dE && ws, "supcon_embed: null argument");
+  NRL_REQUIRE(E && labels && loss && dE, "supcon_embed: null argument");
   NRL_REQUIRE(N >= 1 && N <= MN_MAX_N, "supcon_embed: 1 <= N <= %d anchors (got %lld)", MN_MAX_N, (long long)N);
   NRL_REQUIRE(D >= 4 && D <= MN_MAX_D && D % 4 == 0, "supcon_embed: D a multiple of 4 up to %d (got %d)", MN_MAX_D, D);
   NRL_REQUIRE(temperature > 0.f, "supcon_embed: temperature must be positive");
-  NRL_REQUIRE((((uintptr_t)E | (uintptr_t)dE) & 15) == 0 && ((uintptr_t)ws & 255) == 0, "supcon_embed: E / dE 16-byte, workspace 256-byte aligned");
-  if (ws_bytes < nrl_supcon_embed_workspace_bytes(N, D)) {
-    set_error("workspace too small: %zu < %zu bytes", ws_bytes, nrl_supcon_embed_workspace_bytes(N, D));
-    return NRL_E_WORKSPACE;
-  }
+  NRL_REQUIRE((((uintptr_t)E | (uintptr_t)dE) & 15) == 0, "supcon_embed: E / dE must be 16-byte aligned");
+  SupconWs w;
+  NRL_TRY(carve_workspace(ws, ws_bytes, [&](Arena& a) { supcon_layout(a, N, D, &w); }));
   hipStream_t st = (hipStream_t)stream;
   const EngineScope exact(1);          // 1 = exact fp32 for the two nrl_linear_* calls below, whatever the process default
   const int64_t Np = (N + 3) & ~(int64_t)3;
-  char* p = (char*)ws;
-  void* gemm_ws = p;
-  p += mn_gemm_ws(Np, D);
-  float* Epad = (float*)p;
-  p += align_up((size_t)Np * D * sizeof(float), 256);
-  float* S = (float*)p;
-  p += align_up((size_t)N * Np * sizeof(float), 256);
-  float* G = (float*)p;
-  p += align_up((size_t)N * Np * sizeof(float), 256);
-  float* stats = (float*)p;
-  p += align_up((size_t)3 * N * sizeof(float), 256);
-  float* part = (float*)p;
+  void* const gemm_ws = w.gemm;
+  float *const Epad = w.Epad, *const S = w.S, *const G = w.G, *const stats = w.stats, *const part = w.part;
   const int chunks = (int)ceil_div(Np, MN_KCHUNK);
   const float* Ew = E;
   if (Np != N) {
@@ -294,7 +295,7 @@ int nrl_supcon_embed_fwd_bwd(const float* E, const int64_t* labels, int64_t N, i
   }
   const float inv_t = 1.0f / temperature;
   const unsigned blocks = (unsigned)ceil_div(N, MN_WAVES);
-  NRL_TRY(nrl_linear_fwd(E, Ew, nullptr, N, (int32_t)Np, D, S, gemm_ws, mn_gemm_ws(Np, D), stream));      // S (N, Np) = E [E; 0]^T
+  NRL_TRY(nrl_linear_fwd(E, Ew, nullptr, N, (int32_t)Np, D, S, gemm_ws, w.gemm_bytes, stream));      // S (N, Np) = E [E; 0]^T
   mn_row_stats_kernel<<<blocks, MN_THREADS, 0, st>>>(S, labels, (int)N, (int)Np, inv_t, stats);
   NRL_LAUNCH_CHECK();
   mn_pair_grad_kernel<<<blocks, MN_THREADS, 0, st>>>(S, G, labels, (int)N, (int)Np, inv_t, grad_scale, stats, loss);
@@ -304,7 +305,7 @@ int nrl_supcon_embed_fwd_bwd(const float* E, const int64_t* labels, int64_t N, i
     const int64_t c0 = (int64_t)c * MN_KCHUNK;
     const int32_t wc = (int32_t)(Np - c0 < MN_KCHUNK ? Np - c0 : MN_KCHUNK);
     float* dst = chunks == 1 ? dE : part + (int64_t)c * N * D;
-    NRL_TRY(nrl_linear_bwd(nullptr, Ew + c0 * D, G + N * c0, N, wc, D, dst, nullptr, nullptr, gemm_ws, mn_gemm_ws(Np, D), stream));
+    NRL_TRY(nrl_linear_bwd(nullptr, Ew + c0 * D, G + N * c0, N, wc, D, dst, nullptr, nullptr, gemm_ws, w.gemm_bytes, stream));
   }
   if (chunks > 1) {
     const int64_t n4 = N * (int64_t)(D / 4);

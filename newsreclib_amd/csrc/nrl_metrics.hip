@@ -393,12 +393,23 @@ using namespace nrl;
 
 extern "C" {
 
+// ranks and rows when the caller keeps none | the per-impression valid flags | the reduction's per-part sums (+ count)
+struct MtWs {
+  int32_t *rank, *valid;
+  float* rows;
+  double* partial;
+};
+static void mt_layout(Arena& a, int64_t N, int64_t B, int n_aspects, int n_k, MtWs* w) {
+  const int cols = mt_cols(n_aspects, n_k);
+  w->rank = a.take<int32_t>((size_t)(N > 0 ? N : 1));
+  w->rows = a.take<float>((size_t)B * cols);
+  w->valid = a.take<int32_t>((size_t)B);
+  w->partial = a.take<double>((size_t)ceil_div(B, MT_PART_ROWS) * (cols + 1));
+}
+
 size_t nrl_impression_metrics_workspace_bytes(int64_t N, int64_t B, int32_t n_aspects, int32_t n_k) {
   if (N < 0 || B <= 0 || n_aspects < 0 || n_aspects > 2 || n_k < 0 || n_k > MT_MAX_K) return 256;
-  const int cols = mt_cols(n_aspects, n_k);
-  const int64_t parts = ceil_div(B, MT_PART_ROWS);
-  return align_up((size_t)(N > 0 ? N : 1) * sizeof(int32_t), 256) + align_up((size_t)B * cols * sizeof(float), 256) +
-         align_up((size_t)B * sizeof(int32_t), 256) + align_up((size_t)parts * (cols + 1) * sizeof(double), 256);
+  return measure_workspace<MtWs>([&](Arena& a, auto* w) { mt_layout(a, N, B, n_aspects, n_k, w); });
 }
 
 int nrl_impression_metrics(const float* preds, const float* targets, const int64_t* cand_offsets, int64_t N, int64_t B,
@@ -428,22 +439,13 @@ int nrl_impression_metrics(const float* preds, const float* targets, const int64
     NRL_REQUIRE((N == 0 || ca[a]) && (n_hist == 0 || ha[a]) && hist_offsets, "impression_metrics: aspect %d: null argument", a);
     nc_max = ncs[a] > nc_max ? ncs[a] : nc_max;
   }
-  NRL_REQUIRE(ws && ((uintptr_t)ws & 255) == 0, "impression_metrics: workspace null or not 256-byte aligned");
-  const size_t need = nrl_impression_metrics_workspace_bytes(N, B, n_aspects, n_k);
-  if (ws_bytes < need) {
-    set_error("workspace too small: %zu < %zu bytes", ws_bytes, need);
-    return NRL_E_WORKSPACE;
-  }
+  MtWs w;
+  NRL_TRY(carve_workspace(ws, ws_bytes, [&](Arena& ar) { mt_layout(ar, N, B, n_aspects, n_k, &w); }));
   const int cols = mt_cols(n_aspects, n_k);
   const int64_t parts = ceil_div(B, MT_PART_ROWS);
-  char* p = (char*)ws;
-  int32_t* rank_ws = (int32_t*)p;
-  p += align_up((size_t)(N > 0 ? N : 1) * sizeof(int32_t), 256);
-  float* rows_ws = (float*)p;
-  p += align_up((size_t)B * cols * sizeof(float), 256);
-  int32_t* valid = (int32_t*)p;
-  p += align_up((size_t)B * sizeof(int32_t), 256);
-  double* partial = (double*)p;
+  int32_t *const rank_ws = w.rank, *const valid = w.valid;
+  float* const rows_ws = w.rows;
+  double* const partial = w.partial;
 
   MtArgs A;
   A.preds = preds;

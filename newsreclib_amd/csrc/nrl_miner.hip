@@ -195,18 +195,17 @@ __global__ __launch_bounds__(MN_THREADS) void miner_cos_bwd_kernel(const float* 
 struct CbWs {
   float *rn_h, *rn_c, *s_own, *s_all, *q_own, *q_all;
 };
-static size_t cb_ws_floats(int64_t B, int64_t n_hist, int64_t n_cand, int32_t Dc) {
-  return align_up((size_t)n_hist, 4) + align_up((size_t)n_cand, 4) + 2 * ((size_t)B * Dc + Dc);
+static void cb_layout(Arena& a, int64_t B, int64_t n_hist, int64_t n_cand, int32_t Dc, CbWs* w) {
+  w->rn_h = a.take<float>((size_t)n_hist, 4 * sizeof(float));
+  w->rn_c = a.take<float>((size_t)n_cand, 4 * sizeof(float));
+  w->s_own = a.take<float>((size_t)B * Dc, sizeof(float));
+  w->s_all = a.take<float>((size_t)Dc, sizeof(float));
+  w->q_own = a.take<float>((size_t)B * Dc, sizeof(float));
+  w->q_all = a.take<float>((size_t)Dc, sizeof(float));
 }
-static CbWs cb_ws(float* ws, int64_t B, int64_t n_hist, int64_t n_cand, int32_t Dc) {
-  CbWs w;
-  w.rn_h = ws;
-  w.rn_c = w.rn_h + align_up((size_t)n_hist, 4);
-  w.s_own = w.rn_c + align_up((size_t)n_cand, 4);
-  w.s_all = w.s_own + (size_t)B * Dc;
-  w.q_own = w.s_all + Dc;
-  w.q_all = w.q_own + (size_t)B * Dc;
-  return w;
+// the slab workspaces: per-chunk partial weight gradients (wgrad) / per-user code gradients (poly backward), summed by mn_slab_sum
+static void mn_slabs_layout(Arena& a, int64_t num_slabs, int64_t n, float** slabs) {
+  *slabs = a.take<float>((size_t)num_slabs * (size_t)n, sizeof(float));
 }
 
 // one workgroup per user: 1 / |c| of its candidate rows, then s_own[b] = sum of its unit rows (row order)
@@ -642,32 +641,34 @@ int nrl_miner_tanh_grad(const float* d_c, const float* c, int64_t n, float* d_pr
 }
 
 size_t nrl_miner_wgrad_workspace_bytes(int64_t R, int32_t N, int32_t K) {
-  return (size_t)ceil_div(R > 0 ? R : 1, MN_WG_ROWS) * N * K * sizeof(float);
+  const int64_t chunks = ceil_div(R > 0 ? R : 1, MN_WG_ROWS);
+  return measure_workspace<float*>([&](Arena& a, auto* w) { mn_slabs_layout(a, chunks, (int64_t)N * K, w); });
 }
 
 int nrl_miner_wgrad(const float* G, const float* X, int64_t R, int32_t N, int32_t K, float* d_w, void* ws, size_t ws_bytes,
                     void* stream) {
-  NRL_REQUIRE(G && X && d_w && ws && R > 0 && N > 0 && K > 0 && K % 4 == 0, "nrl_miner_wgrad: bad arguments (K %% 4 == 0)");
-  NRL_REQUIRE(ws_bytes >= nrl_miner_wgrad_workspace_bytes(R, N, K), "nrl_miner_wgrad: workspace");
-  hipStream_t st = (hipStream_t)stream;
+  NRL_REQUIRE(G && X && d_w && R > 0 && N > 0 && K > 0 && K % 4 == 0, "nrl_miner_wgrad: bad arguments (K %% 4 == 0)");
   const int64_t chunks = ceil_div(R, MN_WG_ROWS);
-  miner_wgrad_kernel<<<dim3((unsigned)chunks, (unsigned)ceil_div(N, MN_WG_TN)), MN_THREADS, 0, st>>>(G, X, R, N, K, (float*)ws);
+  float* slabs;
+  NRL_TRY(carve_workspace(ws, ws_bytes, [&](Arena& a) { mn_slabs_layout(a, chunks, (int64_t)N * K, &slabs); }));
+  hipStream_t st = (hipStream_t)stream;
+  miner_wgrad_kernel<<<dim3((unsigned)chunks, (unsigned)ceil_div(N, MN_WG_TN)), MN_THREADS, 0, st>>>(G, X, R, N, K, slabs);
   NRL_LAUNCH_CHECK();
-  return mn_slab_sum((const float*)ws, chunks, (int64_t)N * K, 1.f, d_w, st);
+  return mn_slab_sum(slabs, chunks, (int64_t)N * K, 1.f, d_w, st);
 }
 
 size_t nrl_miner_categ_bias_workspace_bytes(int64_t B, int64_t n_hist, int64_t n_cand, int32_t Dc) {
-  return cb_ws_floats(B, n_hist, n_cand, Dc) * sizeof(float);
+  return measure_workspace<CbWs>([&](Arena& a, auto* w) { cb_layout(a, B, n_hist, n_cand, Dc, w); });
 }
 
 int nrl_miner_categ_bias_fwd(const float* hc, const float* cc, const int64_t* batch_hist, const int64_t* cand_off, int64_t B,
                              int64_t n_hist, int64_t n_cand, int32_t Dc, float* bias, void* ws, size_t ws_bytes,
                              void* stream) {
-  NRL_REQUIRE(hc && cc && batch_hist && cand_off && bias && ws, "nrl_miner_categ_bias_fwd: null argument");
+  NRL_REQUIRE(hc && cc && batch_hist && cand_off && bias, "nrl_miner_categ_bias_fwd: null argument");
   NRL_REQUIRE(B > 0 && n_hist > 0 && n_cand > 0 && Dc > 0 && Dc % 4 == 0, "nrl_miner_categ_bias_fwd: bad shape (Dc %% 4 == 0)");
-  NRL_REQUIRE(ws_bytes >= nrl_miner_categ_bias_workspace_bytes(B, n_hist, n_cand, Dc), "nrl_miner_categ_bias_fwd: workspace");
+  CbWs w;
+  NRL_TRY(carve_workspace(ws, ws_bytes, [&](Arena& a) { cb_layout(a, B, n_hist, n_cand, Dc, &w); }));
   hipStream_t st = (hipStream_t)stream;
-  const CbWs w = cb_ws((float*)ws, B, n_hist, n_cand, Dc);
   miner_cb_cand_kernel<<<(unsigned)B, MN_THREADS, 0, st>>>(cc, cand_off, Dc, w.rn_c, w.s_own);
   NRL_LAUNCH_CHECK();
   NRL_TRY(mn_slab_sum(w.s_own, B, Dc, 1.f, w.s_all, st));
@@ -681,12 +682,11 @@ int nrl_miner_categ_bias_fwd(const float* hc, const float* cc, const int64_t* ba
 int nrl_miner_categ_bias_bwd(const float* d_bias, const float* hc, const float* cc, const int64_t* hist_off,
                              const int64_t* batch_cand, const float* bias, int64_t B, int64_t n_hist, int64_t n_cand,
                              int32_t Dc, float* d_hc, float* d_cc, void* ws, size_t ws_bytes, void* stream) {
-  NRL_REQUIRE(d_bias && hc && cc && hist_off && batch_cand && bias && d_hc && d_cc && ws,
-              "nrl_miner_categ_bias_bwd: null argument");
+  NRL_REQUIRE(d_bias && hc && cc && hist_off && batch_cand && bias && d_hc && d_cc, "nrl_miner_categ_bias_bwd: null argument");
   NRL_REQUIRE(B > 0 && n_hist > 0 && n_cand > 0 && Dc > 0 && Dc % 4 == 0, "nrl_miner_categ_bias_bwd: bad shape");
-  NRL_REQUIRE(ws_bytes >= nrl_miner_categ_bias_workspace_bytes(B, n_hist, n_cand, Dc), "nrl_miner_categ_bias_bwd: workspace");
+  CbWs w;
+  NRL_TRY(carve_workspace(ws, ws_bytes, [&](Arena& a) { cb_layout(a, B, n_hist, n_cand, Dc, &w); }));
   hipStream_t st = (hipStream_t)stream;
-  const CbWs w = cb_ws((float*)ws, B, n_hist, n_cand, Dc);
   miner_cb_bwd_hist_kernel<<<(unsigned)B, MN_THREADS, 0, st>>>(d_bias, hc, hist_off, Dc, 1.f / (float)n_cand, bias, w.rn_h,
                                                               w.s_own, w.s_all, w.q_own, d_hc);
   NRL_LAUNCH_CHECK();
@@ -697,7 +697,9 @@ int nrl_miner_categ_bias_bwd(const float* d_bias, const float* hc, const float* 
   return NRL_OK;
 }
 
-size_t nrl_miner_poly_workspace_bytes(int64_t B, int32_t K, int32_t Cd) { return (size_t)B * K * Cd * sizeof(float); }
+size_t nrl_miner_poly_workspace_bytes(int64_t B, int32_t K, int32_t Cd) {
+  return measure_workspace<float*>([&](Arena& a, auto* w) { mn_slabs_layout(a, B, (int64_t)K * Cd, w); });
+}
 
 int nrl_miner_poly_fwd(const float* E, const float* P, const float* codes, const float* bias, const int64_t* hist_off,
                        int64_t B, int32_t max_hist, int32_t D, int32_t Cd, int32_t K, float* user_vector, float* A,
@@ -719,18 +721,19 @@ int nrl_miner_poly_fwd(const float* E, const float* P, const float* codes, const
 int nrl_miner_poly_bwd(const float* d_user_vector, const float* E, const float* P, const float* codes, const float* A,
                        const int64_t* hist_off, int64_t B, int32_t max_hist, int32_t D, int32_t Cd, int32_t K, float* d_E,
                        float* d_P, float* d_codes, float* d_bias, void* ws, size_t ws_bytes, void* stream) {
-  NRL_REQUIRE(d_user_vector && E && P && codes && A && hist_off && d_E && d_P && d_codes && ws,
+  NRL_REQUIRE(d_user_vector && E && P && codes && A && hist_off && d_E && d_P && d_codes,
               "nrl_miner_poly_bwd: null argument");
   NRL_REQUIRE(B > 0 && max_hist > 0 && K > 0 && D > 0 && Cd > 0 && D % 4 == 0 && Cd % 4 == 0, "nrl_miner_poly_bwd: bad shape");
-  NRL_REQUIRE(ws_bytes >= nrl_miner_poly_workspace_bytes(B, K, Cd), "nrl_miner_poly_bwd: workspace");
+  float* slabs;
+  NRL_TRY(carve_workspace(ws, ws_bytes, [&](Arena& a) { mn_slabs_layout(a, B, (int64_t)K * Cd, &slabs); }));
   const size_t lds = 2 * (size_t)K * max_hist * sizeof(float);
   static bool raised = false;
   NRL_TRY(mn_set_lds(reinterpret_cast<const void*>(&miner_poly_bwd_kernel), lds, "nrl_miner_poly_bwd", &raised));
   hipStream_t st = (hipStream_t)stream;
   miner_poly_bwd_kernel<<<(unsigned)B, MN_THREADS, lds, st>>>(d_user_vector, E, P, codes, A, hist_off, max_hist, D, Cd, K, d_E,
-                                                            d_P, d_bias, (float*)ws);
+                                                            d_P, d_bias, slabs);
   NRL_LAUNCH_CHECK();
-  return mn_slab_sum((const float*)ws, B, (int64_t)K * Cd, 1.f, d_codes, st);
+  return mn_slab_sum(slabs, B, (int64_t)K * Cd, 1.f, d_codes, st);
 }
 
 int nrl_miner_score_fwd(const float* cand, const float* user_vector, const float* Z, const int64_t* cand_off, int64_t B,

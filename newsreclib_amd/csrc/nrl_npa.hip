@@ -725,9 +725,13 @@ static int npa_pmax(const NrlNpaQueryParams* p) {
   return p->news_proj_weight != nullptr && p->news_query_dim > p->text_query_dim ? p->news_query_dim : p->text_query_dim;
 }
 
-static size_t npa_query_ws_floats(int64_t B, int U, int Pmax, int F) {
-  return align_up((size_t)3 * B * F, 64) + 2 * align_up((size_t)3 * B * Pmax, 64) + align_up((size_t)3 * B * U, 64) +
-         align_up((size_t)B * U, 64);
+static void npa_query_layout(Arena& a, int64_t B, int U, int Pmax, int F, NpaQueryWs* w) {
+  w->Pmax = Pmax;
+  w->ga = a.take<float>((size_t)3 * B * F);
+  w->gt = a.take<float>((size_t)3 * B * Pmax);
+  w->h = a.take<float>((size_t)3 * B * Pmax);
+  w->du = a.take<float>((size_t)3 * B * U);
+  w->u = a.take<float>((size_t)B * U);
 }
 
 }  // namespace nrl
@@ -738,7 +742,8 @@ extern "C" {
 
 size_t nrl_npa_user_queries_workspace_bytes(const NrlNpaQueryParams* p, int64_t batch) {
   if (p == nullptr) return 0;
-  return npa_query_ws_floats(batch, p->user_dim, npa_pmax(p), p->num_filters) * sizeof(float);
+  return measure_workspace<NpaQueryWs>(
+      [&](Arena& a, auto* w) { npa_query_layout(a, batch, p->user_dim, npa_pmax(p), p->num_filters, w); });
 }
 
 int nrl_npa_user_queries_fwd(const NrlNpaQueryParams* p, const int64_t* user_idx, int64_t batch, double p_drop,
@@ -768,20 +773,8 @@ int nrl_npa_user_queries_bwd(const NrlNpaQueryParams* p, const NrlNpaQueryGrads*
   NRL_REQUIRE(d_text_queries != nullptr && (nheads == 2 || d_news_queries != nullptr), "npa user queries: null d_queries");
   if (batch == 0) return NRL_OK;
   const int Pmax = npa_pmax(p);
-  const size_t need = npa_query_ws_floats(batch, a.U, Pmax, a.F) * sizeof(float);
-  NRL_REQUIRE(ws != nullptr && ((uintptr_t)ws & 255) == 0, "workspace must be 256-byte aligned");
-  if (ws_bytes < need) {
-    set_error("workspace too small: %zu < %zu bytes", ws_bytes, need);
-    return NRL_E_WORKSPACE;
-  }
-  float* f = (float*)ws;
   NpaQueryWs w;
-  w.Pmax = Pmax;
-  w.ga = f; f += align_up((size_t)3 * batch * a.F, 64);
-  w.gt = f; f += align_up((size_t)3 * batch * Pmax, 64);
-  w.h = f; f += align_up((size_t)3 * batch * Pmax, 64);
-  w.du = f; f += align_up((size_t)3 * batch * a.U, 64);
-  w.u = f;
+  NRL_TRY(carve_workspace(ws, ws_bytes, [&](Arena& ar) { npa_query_layout(ar, batch, a.U, Pmax, a.F, &w); }));
   hipStream_t st = (hipStream_t)stream;
   const size_t lds = (size_t)(a.U + 3 * Pmax + a.F) * sizeof(float);
   hipLaunchKernelGGL(npa_user_queries_bwd_rows_kernel, dim3((unsigned)batch, nheads), dim3(NPA_THREADS), lds, st, a,

@@ -149,9 +149,17 @@ using namespace nrl;
 
 extern "C" {
 
+struct SortWs {
+  int *hist, *rank, *totals;
+};
+static void sort_layout(Arena& a, int64_t n, int64_t vocab, SortWs* w) {
+  w->hist = a.take<int>((size_t)(vocab > 0 ? vocab : 1));
+  w->rank = a.take<int>((size_t)(n > 0 ? n : 1));
+  w->totals = a.take<int>(1024);   // block totals
+}
+
 size_t nrl_sort_positions_workspace_bytes(int64_t n, int64_t vocab) {
-  return align_up((size_t)(vocab > 0 ? vocab : 1) * sizeof(int), 256) + align_up((size_t)(n > 0 ? n : 1) * sizeof(int), 256) +
-         4096;  // + block totals
+  return measure_workspace<SortWs>([&](Arena& a, auto* w) { sort_layout(a, n, vocab, w); });
 }
 
 int nrl_sort_positions(const int64_t* ids, int64_t n, int64_t vocab, int64_t* order, void* ws, size_t ws_bytes,
@@ -164,15 +172,10 @@ int nrl_sort_positions(const int64_t* ids, int64_t n, int64_t vocab, int64_t* or
     return NRL_OK;
   }
   NRL_REQUIRE(ids && order, "sort_positions: null argument");
-  NRL_REQUIRE(ws != nullptr && ((uintptr_t)ws & 255) == 0, "workspace must be 256-byte aligned");
-  if (ws_bytes < nrl_sort_positions_workspace_bytes(n, vocab)) {
-    set_error("workspace too small: %zu bytes", ws_bytes);
-    return NRL_E_WORKSPACE;
-  }
+  SortWs w;
+  NRL_TRY(carve_workspace(ws, ws_bytes, [&](Arena& a) { sort_layout(a, n, vocab, &w); }));
   hipStream_t st = (hipStream_t)stream;
-  int* hist = (int*)ws;
-  int* rank = (int*)((unsigned char*)ws + align_up((size_t)vocab * sizeof(int), 256));
-  int* totals = (int*)((unsigned char*)rank + align_up((size_t)n * sizeof(int), 256));
+  int *const hist = w.hist, *const rank = w.rank, *const totals = w.totals;
   const int sblocks = (int)ceil_div(vocab, 1024);
   NRL_HIP(hipMemsetAsync(hist, 0, (size_t)vocab * sizeof(int), st));
   const unsigned blocks = (unsigned)ceil_div(n, CS_BLOCK);

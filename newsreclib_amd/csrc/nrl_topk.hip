@@ -377,12 +377,17 @@ using namespace nrl;
 
 extern "C" {
 
-size_t nrl_topk_scores_workspace_bytes(int64_t B, int64_t V, int32_t D, int32_t k, int32_t slices) {
-  if (!tk_shape_ok(B, V, D, k) || slices < 0) return 256;
+// k packed (score, index) keys per (user, slice list); never empty
+static void tk_layout(Arena& a, int64_t B, int64_t V, int32_t k, int32_t slices, unsigned long long** partial) {
   int64_t lists, used, tps;
   tk_plan(B, V, slices, lists, used, tps);
-  const size_t bytes = (size_t)B * (size_t)lists * (size_t)k * sizeof(unsigned long long);
-  return align_up(bytes > 0 ? bytes : 1, 256);
+  const size_t keys = (size_t)B * (size_t)lists * (size_t)k;
+  *partial = a.take<unsigned long long>(keys > 0 ? keys : 1);
+}
+
+size_t nrl_topk_scores_workspace_bytes(int64_t B, int64_t V, int32_t D, int32_t k, int32_t slices) {
+  if (!tk_shape_ok(B, V, D, k) || slices < 0) return 256;
+  return measure_workspace<unsigned long long*>([&](Arena& a, auto* w) { tk_layout(a, B, V, k, slices, w); });
 }
 
 int nrl_topk_scores(const float* user_vec, const float* table, int64_t B, int64_t V, int32_t D, int32_t k, const int64_t* excl_idx,
@@ -397,12 +402,8 @@ int nrl_topk_scores(const float* user_vec, const float* table, int64_t B, int64_
   NRL_REQUIRE((excl_idx == nullptr) == (excl_off == nullptr) || excl_off, "topk_scores: excl_idx without excl_off");
   if (B == 0) return NRL_OK;
   NRL_REQUIRE(out_idx && out_score && user_vec && (V == 0 || table), "topk_scores: null argument");
-  NRL_REQUIRE(ws && ((uintptr_t)ws & 255) == 0, "topk_scores: workspace null or not 256-byte aligned");
-  const size_t need = nrl_topk_scores_workspace_bytes(B, V, D, k, slices);
-  if (ws_bytes < need) {
-    set_error("workspace too small: %zu < %zu bytes", ws_bytes, need);
-    return NRL_E_WORKSPACE;
-  }
+  unsigned long long* partial;
+  NRL_TRY(carve_workspace(ws, ws_bytes, [&](Arena& a) { tk_layout(a, B, V, k, slices, &partial); }));
   int64_t lists, used, tps;
   tk_plan(B, V, slices, lists, used, tps);
   const int64_t blocks = ceil_div(B, TK_BU) * used;
@@ -420,7 +421,7 @@ int nrl_topk_scores(const float* user_vec, const float* table, int64_t B, int64_
   A.eligible = eligible;
   A.slices = (int32_t)used;
   A.tiles_per_slice = (int32_t)tps;
-  A.partial = (unsigned long long*)ws;
+  A.partial = partial;
   A.out_idx = out_idx;
   A.out_score = out_score;
   A.status = status;

@@ -33,6 +33,12 @@ def _stream() -> int:
     return torch.cuda.current_stream().cuda_stream
 
 
+def workspace(nbytes: int, device) -> torch.Tensor:
+    """The one place a native workspace is allocated: a uint8 buffer of at least 256 bytes (never empty, so never a null pointer).
+    The wrappers of the sibling modules call it as ``ops.workspace`` so that replacing this attribute reaches every call."""
+    return torch.empty(max(int(nbytes), 256), dtype=torch.uint8, device=device)
+
+
 def _chk(t: torch.Tensor, dtype, name: str) -> torch.Tensor:
     if not t.is_cuda:
         raise RuntimeError(f"newsreclib_amd: `{name}` must live on the GPU (got {t.device}); "
@@ -151,7 +157,7 @@ class NewsEncoderFn(GradAwareFunction):
         bp = _block_params(params[1:], heads, engine, options)
         save = saving(ctx)
         ws_bytes = lib.nrl_news_encoder_workspace_bytes(N, L, D, heads, bp.query_dim)
-        ws = torch.empty(max(ws_bytes, 256), dtype=torch.uint8, device=ids.device)
+        ws = workspace(ws_bytes, ids.device)
         out = torch.empty((N, D), dtype=torch.float32, device=ids.device)
         _lib.check(lib.nrl_news_encoder_fwd(ctypes.byref(bp), emb.data_ptr(), V, ids.data_ptr(), N, L,
                                             float(p_drop), int(seed), int(stream0), int(save),
@@ -241,7 +247,7 @@ class UserEncoderFn(GradAwareFunction):
             raise ValueError("newsreclib_amd: hist feature dim does not match the encoder")
         save = saving(ctx)
         ws_bytes = lib.nrl_user_encoder_workspace_bytes(B, H, D, heads, bp.query_dim)
-        ws = torch.empty(max(ws_bytes, 256), dtype=torch.uint8, device=hist.device)
+        ws = workspace(ws_bytes, hist.device)
         out = torch.empty((B, D), dtype=torch.float32, device=hist.device)
         _lib.check(lib.nrl_user_encoder_fwd(ctypes.byref(bp), hist.data_ptr(), B, H, float(p_drop), int(seed),
                                             int(stream0), int(bool(input_dropout)), int(save), out.data_ptr(),
@@ -488,8 +494,7 @@ def news_encoder_fwd_table(ids: torch.Tensor, table: torch.Tensor, vocab: int, p
     params = [_chk(t.detach(), torch.float32, "parameter") for t in params]
     bp = _block_params(params, heads, _lib.engine_code(), _lib.options_word())
     out = torch.empty((N, bp.embed_dim), dtype=torch.float32, device=ids.device)
-    ws = torch.empty(max(int(lib.nrl_news_encoder_fwd_table_workspace_bytes(N, L, int(heads))), 256), dtype=torch.uint8,
-                     device=ids.device)
+    ws = workspace(lib.nrl_news_encoder_fwd_table_workspace_bytes(N, L, int(heads)), ids.device)
     _lib.check(lib.nrl_news_encoder_fwd_table(ctypes.byref(bp), table.data_ptr(), table.numel(), int(vocab), ids.data_ptr(), N, L,
                                               out.data_ptr(), ws.data_ptr(), ws.numel(), _stream()), "nrl_news_encoder_fwd_table")
     return out
@@ -512,7 +517,7 @@ def linear(a: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None
     N = w.shape[0]
     c = torch.empty((M, N), dtype=torch.float32, device=a.device)
     b = _chk(bias, torch.float32, "bias").data_ptr() if bias is not None else None
-    ws = torch.empty(max(lib.nrl_linear_workspace_bytes(N, K), 256), dtype=torch.uint8, device=a.device)
+    ws = workspace(lib.nrl_linear_workspace_bytes(N, K), a.device)
     _lib.check(lib.nrl_linear_fwd(a.data_ptr(), w.data_ptr(), b, M, N, K, c.data_ptr(), ws.data_ptr(), ws.numel(),
                                   _stream()), "nrl_linear_fwd")
     return c
@@ -577,8 +582,7 @@ def sort_positions(ids: torch.Tensor, vocab: Optional[int] = None) -> torch.Tens
         return torch.cat([torch.argsort(flat, stable=True), (flat == 0).sum().reshape(1)])
     lib = _lib.load()
     order = torch.empty(n + 1, dtype=torch.int64, device=flat.device)
-    ws = torch.empty(max(lib.nrl_sort_positions_workspace_bytes(n, int(vocab)), 256), dtype=torch.uint8,
-                     device=flat.device)
+    ws = workspace(lib.nrl_sort_positions_workspace_bytes(n, int(vocab)), flat.device)
     _lib.check(lib.nrl_sort_positions(flat.data_ptr(), n, int(vocab), order.data_ptr(), ws.data_ptr(), ws.numel(),
                                       _stream()), "nrl_sort_positions")
     return order
@@ -694,7 +698,7 @@ def impression_metrics(preds: torch.Tensor, targets: torch.Tensor, cand_offsets:
     rows = torch.zeros((B, cols), dtype=torch.float32, device=dev) if want_rows else None
     if B == 0:
         return rank, rows, status
-    ws = torch.empty(max(lib.nrl_impression_metrics_workspace_bytes(N, B, len(asp), len(top_k)), 256), dtype=torch.uint8, device=dev)
+    ws = workspace(lib.nrl_impression_metrics_workspace_bytes(N, B, len(asp), len(top_k)), dev)
     ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
     a0 = asp[0] if len(asp) > 0 else (None, None, 0)
     a1 = asp[1] if len(asp) > 1 else (None, None, 0)
@@ -745,7 +749,7 @@ def topk_scores(user_vec: torch.Tensor, table: torch.Tensor, k: int, excl_idx: O
     idx = torch.empty((B, max(k, 0)), dtype=torch.int64, device=dev)
     score = torch.empty((B, max(k, 0)), dtype=torch.float32, device=dev)
     status = torch.zeros(1, dtype=torch.int32, device=dev)
-    ws = torch.empty(max(lib.nrl_topk_scores_workspace_bytes(B, V, D, k, int(slices)), 256), dtype=torch.uint8, device=dev)
+    ws = workspace(lib.nrl_topk_scores_workspace_bytes(B, V, D, k, int(slices)), dev)
     ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
     _lib.check(lib.nrl_topk_scores(user_vec.data_ptr(), table.data_ptr(), B, V, D, k, ptr(excl_idx), ptr(excl_off), ptr(eligible),
                                    int(slices), idx.data_ptr(), score.data_ptr(), status.data_ptr(), ws.data_ptr(), ws.numel(),

@@ -10,7 +10,7 @@ import weakref
 import torch
 from torch.optim.optimizer import register_optimizer_step_post_hook
 
-from . import _lib
+from . import _lib, ops
 from ._lib import NrlAddAttGrads, NrlAddAttParams
 from .ops import GradAwareFunction, _chk, _grad_targets, _stream, saving
 
@@ -32,8 +32,7 @@ class AdditiveAttentionFn(GradAwareFunction):
         if params[0].shape != (Q, D) or params[1].shape != (Q,) or params[2].shape != (Q,):
             raise ValueError("newsreclib_amd: inconsistent additive-attention parameter shapes")
         ap = NrlAddAttParams(*[p.data_ptr() for p in params], D, Q)
-        ws = torch.empty(max(lib.nrl_additive_attention_workspace_bytes(G, S, D, Q), 256), dtype=torch.uint8,
-                         device=y.device)
+        ws = ops.workspace(lib.nrl_additive_attention_workspace_bytes(G, S, D, Q), y.device)
         out = torch.empty((G, D), dtype=torch.float32, device=y.device)
         save = saving(ctx)
         _lib.check(lib.nrl_additive_attention_fwd(ctypes.byref(ap), y.data_ptr(), G, S, int(save), out.data_ptr(),
@@ -75,7 +74,7 @@ class LinearActFn(GradAwareFunction):
         M, K = a.shape
         N = w.shape[0]
         code = ACT[act]
-        ws = torch.empty(max(lib.nrl_linear_act_workspace_bytes(M, N, K), 256), dtype=torch.uint8, device=a.device)
+        ws = ops.workspace(lib.nrl_linear_act_workspace_bytes(M, N, K), a.device)
         c = torch.empty((M, N), dtype=torch.float32, device=a.device)
         _lib.check(lib.nrl_linear_act_fwd(a.data_ptr(), w.data_ptr(), bias.data_ptr(), M, N, K, code, c.data_ptr(),
                                           ws.data_ptr(), ws.numel(), _stream()), "nrl_linear_act_fwd")
@@ -122,7 +121,7 @@ class LinearFn(GradAwareFunction):
         # `images` (FrozenImages, a frozen weight only): the matrix-core images of the weight kept across calls
         ws, ready, key = images.buffer("fwd", w, lib, a.device) if images is not None else (None, 0, None)
         if ws is None:
-            ws = torch.empty(max(lib.nrl_linear_workspace_bytes(N, K), 256), dtype=torch.uint8, device=a.device)
+            ws = ops.workspace(lib.nrl_linear_workspace_bytes(N, K), a.device)
         c = torch.empty((M, N), dtype=torch.float32, device=a.device)
         _lib.check(lib.nrl_linear_fwd_img(a2.data_ptr(), w.data_ptr(), bias.data_ptr(), M, N, K, c.data_ptr(), ws.data_ptr(),
                                           ws.numel(), ready, _stream()), "nrl_linear_fwd")
@@ -153,7 +152,7 @@ class LinearFn(GradAwareFunction):
         d_a = torch.empty((M, K), dtype=torch.float32, device=d_c.device) if need_a else None
         ws, ready, key = ctx.images.buffer("bwd", w, lib, d_c.device) if ctx.images is not None else (None, 0, None)
         if ws is None:
-            ws = torch.empty(max(lib.nrl_linear_workspace_bytes(N, K), 256), dtype=torch.uint8, device=d_c.device)
+            ws = ops.workspace(lib.nrl_linear_workspace_bytes(N, K), d_c.device)
         _lib.check(lib.nrl_linear_bwd_img(a2.data_ptr() if need_w else None, w.data_ptr(), d_c.data_ptr(), M, N, K,
                                           d_a.data_ptr() if need_a else None, dw, db, ws.data_ptr(), ws.numel(), ready,
                                           _stream()), "nrl_linear_bwd")
@@ -167,7 +166,7 @@ def _image_ws(images, which, w, lib, device):
     ws, ready, key = images.buffer(which, w, lib, device) if images is not None else (None, 0, None)
     if ws is None:
         N, K = w.shape
-        ws = torch.empty(max(lib.nrl_linear_workspace_bytes(N, K), 256), dtype=torch.uint8, device=device)
+        ws = ops.workspace(lib.nrl_linear_workspace_bytes(N, K), device)
     return ws, ready, key
 
 
@@ -229,7 +228,7 @@ class FfnFn(GradAwareFunction):
         if need_w2:
             bufs, r = _grad_targets([w2, b2], gb[2:4] if gb is not None else None)
             rets[2:4] = r
-            ws = torch.empty(256, dtype=torch.uint8, device=dev)          # (weight gradient only: no image)
+            ws = ops.workspace(0, dev)          # (weight gradient only: no image)
             _lib.check(lib.nrl_linear_bwd_img(g.data_ptr(), w2.data_ptr(), d_y.data_ptr(), M, N2, K2, None, bufs[0].data_ptr(),
                                               bufs[1].data_ptr(), ws.data_ptr(), ws.numel(), 0, _stream()), "nrl_linear_bwd")
         d_x = None
@@ -262,7 +261,6 @@ class EmbeddingFn(GradAwareFunction):
 
     @staticmethod
     def forward(ctx, ids, weight, padding_idx, grad_bufs):
-        from . import ops
         ids = _chk(ids, torch.int64, "ids")
         weight = _chk(weight, torch.float32, "embedding weight")
         out = ops.embedding_gather(weight, ids)
@@ -273,7 +271,6 @@ class EmbeddingFn(GradAwareFunction):
 
     @staticmethod
     def backward(ctx, d_out):
-        from . import ops
         lib = _lib.load()
         (ids,) = ctx.saved_tensors
         V, D = ctx.shape
@@ -411,7 +408,7 @@ def _glue_bwd(lib, d_y, z, stats, gamma, p_drop, seed, dg, db):
 def _wgrad_only(lib, a2, w, d_c, M, dw, db, dev):
     """d_w += d_c^T a, d_bias += colsum(d_c) of one nn.Linear (no activation gradient, no image)."""
     N, K = w.shape
-    ws = torch.empty(256, dtype=torch.uint8, device=dev)
+    ws = ops.workspace(0, dev)
     _lib.check(lib.nrl_linear_bwd_img(a2.data_ptr(), w.data_ptr(), d_c.data_ptr(), M, N, K, None, dw.data_ptr(), db.data_ptr(),
                                       ws.data_ptr(), ws.numel(), 0, _stream()), "nrl_linear_bwd")
 
@@ -452,7 +449,7 @@ class AttnBlockFn(GradAwareFunction):
         nbytes = lib.nrl_linear3_workspace_bytes(n, K)
         ws, ready, key = images_qkv.buffer_multi("fwd", (wq, wk, wv), nbytes, dev) if images_qkv is not None else (None, 0, None)
         if ws is None:
-            ws = torch.empty(max(nbytes, 256), dtype=torch.uint8, device=dev)
+            ws = ops.workspace(nbytes, dev)
         _lib.check(lib.nrl_linear3_fwd_img(x2.data_ptr(), wq.data_ptr(), wk.data_ptr(), wv.data_ptr(), bq.data_ptr(), bk.data_ptr(),
                                            bv.data_ptr(), M, n, K, qkv.data_ptr(), ws.data_ptr(), ws.numel(), ready, _stream()),
                    "nrl_linear3_fwd")
@@ -530,7 +527,7 @@ class AttnBlockFn(GradAwareFunction):
             nbytes = lib.nrl_linear3_workspace_bytes(n, K)
             ws, ready, key = images_qkv.buffer_multi("bwd", (wq, wk, wv), nbytes, dev) if images_qkv is not None else (None, 0, None)
             if ws is None:
-                ws = torch.empty(max(nbytes, 256), dtype=torch.uint8, device=dev)
+                ws = ops.workspace(nbytes, dev)
             _lib.check(lib.nrl_linear3_dgrad_img(dqkv.data_ptr(), wq.data_ptr(), wk.data_ptr(), wv.data_ptr(), M, n, K, d_res.data_ptr(),
                                                  d_x.data_ptr(), ws.data_ptr(), ws.numel(), ready, _stream()), "nrl_linear3_dgrad")
             if key is not None:
@@ -767,7 +764,7 @@ class FrozenImages:
         buf = self._buf.get(which)
         if buf is None or buf.device != device:
             N, K = w.shape
-            buf = self._buf[which] = torch.empty(max(lib.nrl_linear_workspace_bytes(N, K), 256), dtype=torch.uint8, device=device)
+            buf = self._buf[which] = ops.workspace(lib.nrl_linear_workspace_bytes(N, K), device)
             self._key[which] = None
         ready = 1 if self._key.get(which) == key else 0
         if not ready:
@@ -785,7 +782,7 @@ class FrozenImages:
                _lib.options_word(), str(device), _IMAGE_GENERATION[0], _STEP_GENERATION[0] if self._allow_trainable else 0)
         buf = self._buf.get(which)
         if buf is None or buf.device != device or buf.numel() < nbytes:
-            buf = self._buf[which] = torch.empty(max(int(nbytes), 256), dtype=torch.uint8, device=device)
+            buf = self._buf[which] = ops.workspace(nbytes, device)
             self._key[which] = None
         ready = 1 if self._key.get(which) == key else 0
         if not ready:
@@ -816,7 +813,7 @@ class MhaFn(GradAwareFunction):
             raise ValueError("newsreclib_amd: inconsistent attention parameter shapes")
         engine = _lib.engine_code()
         mp = NrlMhaParams(*[p.data_ptr() for p in params], D, int(heads), float(scale or 0.0), engine)
-        ws = torch.empty(max(lib.nrl_mha_workspace_bytes(S, Bt, D, int(heads)), 256), dtype=torch.uint8, device=x.device)
+        ws = ops.workspace(lib.nrl_mha_workspace_bytes(S, Bt, D, int(heads)), x.device)
         out = torch.empty_like(x)
         save = saving(ctx)
         _lib.check(lib.nrl_mha_fwd(ctypes.byref(mp), x.data_ptr(), S, Bt, int(save), out.data_ptr(), ws.data_ptr(),

@@ -8,7 +8,7 @@ from __future__ import annotations
 
 import torch
 
-from . import _lib
+from . import _lib, ops
 from .ops import GradAwareFunction, _chk, _grad_targets, _stream, saving
 
 USER_STREAM_BASE = 16
@@ -230,7 +230,7 @@ class ScoreFn(GradAwareFunction):
         d_scores = _chk(d_scores, torch.float32, "d_scores")
         bufs, rets = _grad_targets([w3, b3], ctx.grad_bufs)
         d_z2, d_x, d_cd = torch.empty_like(z2), torch.empty_like(x), torch.empty_like(cd)
-        ws = torch.empty((max(lib.nrl_caum_score_workspace_bytes(B, C, H, N2), 256),), dtype=torch.uint8, device=z2.device)
+        ws = ops.workspace(lib.nrl_caum_score_workspace_bytes(B, C, H, N2), z2.device)
         _check(lib.nrl_caum_score_bwd(d_scores.data_ptr(), z2.data_ptr(), w3.data_ptr(), x.data_ptr(), cd.data_ptr(),
                                       alpha.data_ptr(), user.data_ptr(), offs.data_ptr(), B, C, slot0, H, N2, U,
                                       d_z2.data_ptr(), d_x.data_ptr(), d_cd.data_ptr(), bufs[0].data_ptr(), bufs[1].data_ptr(),

@@ -8,7 +8,7 @@ from typing import Optional, Sequence
 
 import torch
 
-from . import _lib
+from . import _lib, ops
 from ._lib import NrlDknClickGrads, NrlDknClickParams, NrlDknGrads, NrlDknParams
 from .ops import GradAwareFunction, _chk, _grad_targets, _stream, order_event, saving, wait_order
 from .ops import sort_positions as _sort_positions
@@ -51,7 +51,7 @@ class DknEncoderFn(GradAwareFunction):
         nbytes = lib.nrl_dkn_encoder_workspace_bytes(ctypes.byref(p), N, L)
         if nbytes == 0:
             raise ValueError("newsreclib_amd: unsupported DKN encoder shapes")
-        ws = torch.empty(max(nbytes, 256), dtype=torch.uint8, device=ids.device)
+        ws = ops.workspace(nbytes, ids.device)
         F_ = biases[0].shape[0]
         out = torch.empty((N, len(windows) * F_), dtype=torch.float32, device=ids.device)
         am = torch.empty((N, len(windows) * F_), dtype=torch.uint8, device=ids.device)
@@ -149,8 +149,7 @@ class DknClickFn(GradAwareFunction):
         bufs, rets = _grad_targets(att + pred, None)
         g = NrlDknClickGrads(*[t.data_ptr() for t in bufs])
         d_hist, d_cand = torch.empty_like(hist), torch.empty_like(cand)
-        ws = torch.empty(max(lib.nrl_dkn_click_workspace_bytes(B, max_cand, dim, att[0].shape[0]), 256), dtype=torch.uint8,
-                         device=cand.device)
+        ws = ops.workspace(lib.nrl_dkn_click_workspace_bytes(B, max_cand, dim, att[0].shape[0]), cand.device)
         p = _click_params(att, pred)
         _lib.check(lib.nrl_dkn_click_bwd(ctypes.byref(p), ctypes.byref(g), hist.data_ptr(), hist_offsets.data_ptr(),
                                          max_hist, cand.data_ptr(), cand_offsets.data_ptr(), B, max_cand, dim,

@@ -8,7 +8,7 @@ from typing import Sequence
 
 import torch
 
-from . import _lib
+from . import _lib, ops
 from ._lib import NrlCnnGrads, NrlCnnParams, NrlGruGrads, NrlGruParams
 from .ops import GradAwareFunction, _chk, _grad_targets, _stream, saving
 from .ops import sort_positions as _sort_positions
@@ -43,7 +43,7 @@ class CnnEncoderFn(GradAwareFunction):
         cp = _cnn_params(params[1:], D)
         save = saving(ctx)
         ws_bytes = lib.nrl_cnn_encoder_workspace_bytes(N, L, D, cp.num_filters, cp.window, cp.query_dim)
-        ws = torch.empty(max(ws_bytes, 256), dtype=torch.uint8, device=ids.device)
+        ws = ops.workspace(ws_bytes, ids.device)
         out = torch.empty((N, cp.num_filters), dtype=torch.float32, device=ids.device)
         _lib.check(lib.nrl_cnn_encoder_fwd(ctypes.byref(cp), emb.data_ptr(), V, ids.data_ptr(), N, L, float(p_drop),
                                            int(seed), int(stream0), int(save), out.data_ptr(), ws.data_ptr(),
@@ -140,7 +140,7 @@ class GruFn(GradAwareFunction):
                 raise ValueError("newsreclib_amd: h0 must be (batch, hidden_dim)")
         gp = NrlGruParams(*[p.data_ptr() for p in params], Din, Hd)
         ws_bytes = lib.nrl_gru_workspace_bytes(B, T, Din, Hd)
-        ws = torch.empty(max(ws_bytes, 256), dtype=torch.uint8, device=hist.device)
+        ws = ops.workspace(ws_bytes, hist.device)
         out = torch.empty((B, Hd), dtype=torch.float32, device=hist.device)
         save = saving(ctx)
         _lib.check(lib.nrl_gru_fwd(ctypes.byref(gp), hist.data_ptr(), lengths.data_ptr(),
@@ -195,8 +195,7 @@ class CnnMhsaEncoderFn(GradAwareFunction):
         bp = _block_params(params[3:], heads, engine, options)
         cp = NrlCnnParams(w_c.data_ptr(), b_c.data_ptr(), None, None, None, D, F_, W, bp.query_dim)
         save = saving(ctx)
-        ws = torch.empty(max(lib.nrl_cnn_mhsa_encoder_workspace_bytes(N, L, D, F_, W, heads, bp.query_dim), 256),
-                         dtype=torch.uint8, device=ids.device)
+        ws = ops.workspace(lib.nrl_cnn_mhsa_encoder_workspace_bytes(N, L, D, F_, W, heads, bp.query_dim), ids.device)
         out = torch.empty((N, F_), dtype=torch.float32, device=ids.device)
         _lib.check(lib.nrl_cnn_mhsa_encoder_fwd(ctypes.byref(cp), ctypes.byref(bp), emb.data_ptr(), V, ids.data_ptr(), N,
                                                 L, float(p_drop), int(seed), int(stream0), int(save), out.data_ptr(),

@@ -13,7 +13,7 @@ from typing import Optional, Sequence
 
 import torch
 
-from . import _lib
+from . import _lib, ops
 from .ops import GradAwareFunction, _chk, _stream
 
 MAX_ANCHORS = 1024
@@ -35,7 +35,7 @@ def supcon_embed_fwd_bwd(embeddings: torch.Tensor, labels: torch.Tensor, tempera
                          f"multiple of 4 up to {MAX_DIM}; got ({N}, {D})")
     loss = torch.empty((), dtype=torch.float32, device=E.device)
     d_E = torch.empty_like(E)
-    ws = torch.empty(max(lib.nrl_supcon_embed_workspace_bytes(N, D), 256), dtype=torch.uint8, device=E.device)
+    ws = ops.workspace(lib.nrl_supcon_embed_workspace_bytes(N, D), E.device)
     _lib.check(lib.nrl_supcon_embed_fwd_bwd(E.data_ptr(), labels.data_ptr(), N, D, float(temperature), float(grad_scale),
                                             loss.data_ptr(), d_E.data_ptr(), ws.data_ptr(), ws.numel(), _stream()),
                "nrl_supcon_embed_fwd_bwd")

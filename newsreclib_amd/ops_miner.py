@@ -12,7 +12,7 @@ from __future__ import annotations
 
 import torch
 
-from . import _lib
+from . import _lib, ops
 from .ops import GradAwareFunction, _chk, _stream, saving
 
 STREAM_BASE = 0x4D49
@@ -48,11 +48,11 @@ class BiasFreeLinearFn(GradAwareFunction):
         zeros = torch.zeros((N,), dtype=torch.float32, device=x.device)
         c = _f32((M, N), x)
         if act == "tanh":
-            ws = torch.empty(max(lib.nrl_linear_act_workspace_bytes(M, N, K), 256), dtype=torch.uint8, device=x.device)
+            ws = ops.workspace(lib.nrl_linear_act_workspace_bytes(M, N, K), x.device)
             _check(lib.nrl_linear_act_fwd(x.data_ptr(), w.data_ptr(), zeros.data_ptr(), M, N, K, 1, c.data_ptr(), ws.data_ptr(),
                                           ws.numel(), _stream()), "nrl_linear_act_fwd")
         else:
-            ws = torch.empty(max(lib.nrl_linear_workspace_bytes(N, K), 256), dtype=torch.uint8, device=x.device)
+            ws = ops.workspace(lib.nrl_linear_workspace_bytes(N, K), x.device)
             _check(lib.nrl_linear_fwd_img(x.data_ptr(), w.data_ptr(), zeros.data_ptr(), M, N, K, c.data_ptr(), ws.data_ptr(),
                                           ws.numel(), 0, _stream()), "nrl_linear_fwd")
         if saving(ctx):
@@ -75,12 +75,12 @@ class BiasFreeLinearFn(GradAwareFunction):
         d_x = d_w = None
         if ctx.needs_input_grad[0]:
             d_x = torch.empty_like(x)
-            ws = torch.empty(max(lib.nrl_linear_workspace_bytes(N, K), 256), dtype=torch.uint8, device=x.device)
+            ws = ops.workspace(lib.nrl_linear_workspace_bytes(N, K), x.device)
             _check(lib.nrl_linear_bwd_img(None, w.data_ptr(), d_pre.data_ptr(), M, N, K, d_x.data_ptr(), None, None,
                                           ws.data_ptr(), ws.numel(), 0, _stream()), "nrl_linear_bwd")
         if ctx.needs_input_grad[1]:
             d_w = torch.empty_like(w)
-            ws = torch.empty(max(lib.nrl_miner_wgrad_workspace_bytes(M, N, K), 256), dtype=torch.uint8, device=x.device)
+            ws = ops.workspace(lib.nrl_miner_wgrad_workspace_bytes(M, N, K), x.device)
             _check(lib.nrl_miner_wgrad(d_pre.data_ptr(), x.data_ptr(), M, N, K, d_w.data_ptr(), ws.data_ptr(), ws.numel(),
                                        _stream()), "nrl_miner_wgrad")
         return d_x, d_w, None
@@ -101,8 +101,7 @@ class CategBiasFn(GradAwareFunction):
         nc = cc.shape[0]
         if cc.shape[1] != Dc or bh.shape[0] != nh or bc.shape[0] != nc or ho.numel() != B + 1 or co.numel() != B + 1:
             raise ValueError("newsreclib_amd: inconsistent MINER category-bias shapes")
-        ws = torch.empty((max(lib.nrl_miner_categ_bias_workspace_bytes(B, nh, nc, Dc), 256),), dtype=torch.uint8,
-                         device=hc.device)
+        ws = ops.workspace(lib.nrl_miner_categ_bias_workspace_bytes(B, nh, nc, Dc), hc.device)
         bias = _f32((nh,), hc)
         _check(lib.nrl_miner_categ_bias_fwd(hc.data_ptr(), cc.data_ptr(), bh.data_ptr(), co.data_ptr(), B, nh, nc, Dc,
                                             bias.data_ptr(), ws.data_ptr(), ws.numel(), _stream()), "nrl_miner_categ_bias_fwd")
@@ -158,7 +157,7 @@ class PolyFn(GradAwareFunction):
         d_uv = _chk(d_uv, torch.float32, "d_user_vector")
         d_E, d_P, d_codes = torch.empty_like(E), torch.empty_like(P), torch.empty_like(codes)
         d_bias = _f32((E.shape[0],), E) if ctx.has_bias else None
-        ws = torch.empty((max(lib.nrl_miner_poly_workspace_bytes(B, K, Cd), 256),), dtype=torch.uint8, device=E.device)
+        ws = ops.workspace(lib.nrl_miner_poly_workspace_bytes(B, K, Cd), E.device)
         _check(lib.nrl_miner_poly_bwd(d_uv.data_ptr(), E.data_ptr(), P.data_ptr(), codes.data_ptr(), A.data_ptr(), ho.data_ptr(),
                                       *ctx.cfg, d_E.data_ptr(), d_P.data_ptr(), d_codes.data_ptr(),
                                       d_bias.data_ptr() if d_bias is not None else None, ws.data_ptr(), ws.numel(), _stream()),

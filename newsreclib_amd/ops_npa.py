@@ -7,7 +7,7 @@ import ctypes
 
 import torch
 
-from . import _lib
+from . import _lib, ops
 from ._lib import NrlCnnGrads, NrlCnnParams, NrlNpaQueryGrads, NrlNpaQueryParams
 from .ops import GradAwareFunction, _chk, _grad_targets, _stream, saving
 from .ops import sort_positions as _sort_positions
@@ -42,8 +42,7 @@ class NpaEncoderFn(GradAwareFunction):
             raise ValueError("newsreclib_amd: inconsistent NPA encoder shapes")
         cp = NrlCnnParams(w_c.data_ptr(), b_c.data_ptr(), None, None, None, D, F_, W, 16)
         save = saving(ctx)
-        ws = torch.empty(max(lib.nrl_npa_encoder_workspace_bytes(N, L, D, F_, W), 256), dtype=torch.uint8,
-                         device=ids.device)
+        ws = ops.workspace(lib.nrl_npa_encoder_workspace_bytes(N, L, D, F_, W), ids.device)
         out = torch.empty((N, F_), dtype=torch.float32, device=ids.device)
         _lib.check(lib.nrl_npa_encoder_fwd(ctypes.byref(cp), emb.data_ptr(), V, ids.data_ptr(), N, L, queries.data_ptr(),
                                            owner.data_ptr(), nq, float(p_drop), int(seed), int(stream0), int(save),
@@ -147,8 +146,7 @@ class NpaUserQueriesFn(GradAwareFunction):
         if news is not None:
             d_news = _chk(d_news.contiguous() if d_news is not None else torch.zeros((B, F_), device=table.device),
                           torch.float32, "d_news_queries")
-        ws = torch.empty(max(lib.nrl_npa_user_queries_workspace_bytes(ctypes.byref(qp), B), 256), dtype=torch.uint8,
-                         device=table.device)
+        ws = ops.workspace(lib.nrl_npa_user_queries_workspace_bytes(ctypes.byref(qp), B), table.device)
         _lib.check(lib.nrl_npa_user_queries_bwd(ctypes.byref(qp), ctypes.byref(qg), user_idx.data_ptr(), B, p_drop, seed,
                                                 stream0, d_text.data_ptr(),
                                                 d_news.data_ptr() if news is not None else None, ws.data_ptr(),
@@ -229,8 +227,7 @@ def npa_conv_features(ids: torch.Tensor, emb: torch.Tensor, w_c: torch.Tensor, b
         if not out.is_cuda or out.dtype != torch.float32 or out.shape != (N, L, F_) or not out.is_contiguous():
             raise ValueError(f"newsreclib_amd: `out` must be a contiguous float32 GPU tensor of shape {(N, L, F_)}")
     cp = NrlCnnParams(w_c.data_ptr(), b_c.data_ptr(), None, None, None, D, F_, W, 16)
-    ws = torch.empty(max(lib.nrl_npa_conv_features_workspace_bytes(N, L, D, F_, W), 256), dtype=torch.uint8,
-                     device=ids.device)
+    ws = ops.workspace(lib.nrl_npa_conv_features_workspace_bytes(N, L, D, F_, W), ids.device)
     _lib.check(lib.nrl_npa_conv_features(ctypes.byref(cp), emb.data_ptr(), V, ids.data_ptr(), N, L, out.data_ptr(),
                                          ws.data_ptr(), ws.numel(), _stream()), "nrl_npa_conv_features")
     return out

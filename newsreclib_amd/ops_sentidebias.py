@@ -9,7 +9,7 @@ from __future__ import annotations
 
 import torch
 
-from . import _lib
+from . import _lib, ops
 from .ops import GradAwareFunction, _chk, _stream, saving
 
 MAX_CLASSES = 8
@@ -204,7 +204,7 @@ class DiscriminatorLossFn(GradAwareFunction):
             raise ValueError("newsreclib_amd: inconsistent SentiDebias discriminator shapes")
         if O > MAX_CLASSES:
             raise NotImplementedError(f"newsreclib_amd: the discriminator tail takes at most {MAX_CLASSES} outputs")
-        ws = torch.empty(max(lib.nrl_linear_act_workspace_bytes(N, Hd, D), 256), dtype=torch.uint8, device=news.device)
+        ws = ops.workspace(lib.nrl_linear_act_workspace_bytes(N, Hd, D), news.device)
         h = _f32((N, Hd), news)
         _lib.check(lib.nrl_linear_act_fwd(news.data_ptr(), w1.data_ptr(), b1.data_ptr(), N, Hd, D, 1, h.data_ptr(), ws.data_ptr(),
                                           ws.numel(), _stream()), "nrl_linear_act_fwd")
@@ -242,7 +242,7 @@ class DiscriminatorLossFn(GradAwareFunction):
                 d_x = torch.empty_like(news)
             if need_1:                                   # (the engine ADDS its weight gradients)
                 d_w1, d_b1 = torch.zeros_like(w1), torch.zeros((Hd,), dtype=torch.float32, device=news.device)
-            ws = torch.empty(max(lib.nrl_linear_workspace_bytes(Hd, D), 256), dtype=torch.uint8, device=news.device)
+            ws = ops.workspace(lib.nrl_linear_workspace_bytes(Hd, D), news.device)
             ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
             _lib.check(lib.nrl_linear_bwd_img(news.data_ptr(), w1.data_ptr(), d_pre.data_ptr(), N, Hd, D, ptr(d_x), ptr(d_w1),
                                               ptr(d_b1), ws.data_ptr(), ws.numel(), 0, _stream()), "nrl_linear_bwd")
