@@ -1039,6 +1039,34 @@ int nrl_topk_scores(const float* user_vec, const float* table, int64_t B, int64_
                     const int64_t* excl_off, const uint8_t* eligible, int32_t slices, int64_t* out_idx, float* out_score,
                     int32_t* status, void* ws, size_t ws_bytes, void* stream);
 
+/* nrl_topk_interest_scores: the same ranking where a user is K interest vectors and the score of a table row is an aggregate over
+ *   them (MINER, miner_module.py:298-308 and attention.py:162-166 with the candidate list replaced by the table).  interests
+ *   (B, K, D), gate (B, K, D; required by mode 2, ignored otherwise) and table (V, D): fp32, row-major, device.  B counts users.
+ *   With s_j = interests[u, j, :] . table[v, :] the score of (u, v) is
+ *     mode 0 (max):      max_j s_j;
+ *     mode 1 (mean):     (s_0 + s_1 + ... + s_{K-1}) / K, summed in fp32 in ascending j, then one fp32 division;
+ *     mode 2 (weighted): with l_j = gate[u, j, :] . table[v, :], m = max_j l_j and e_j = expf(l_j - m):
+ *                        (sum_j e_j s_j) / (sum_j e_j), both sums in fp32 in ascending j.  gate is gelu(user_vector Wt^T): it is
+ *                        formed before the call and does not depend on the table row.
+ *   K in [1, NRL_TOPK_MAX_INTERESTS]; D, k, V, B, excl_idx / excl_off, eligible, slices, out_idx / out_score and status as for
+ *   nrl_topk_scores (slices 0: the count is chosen per tile of floor(64 / K) users).  A NaN aggregate (any NaN s_j or l_j, or
+ *   inf - inf) of an eligible, not excluded row sets NRL_TOPK_E_NAN and the row is left out for that user.
+ *   Arithmetic: every s_j and l_j is the one exact-fp32 MFMA accumulator chain of nrl_topk_scores and the aggregation order is
+ *     fixed, so the bits of a user's score for a row depend on the user's K rows, the table row, D, K and the mode alone, not on B,
+ *     V, k, slices, the grid or the GEMM engine setting; at K == 1 every mode returns the bits of nrl_topk_scores.  Neither the
+ *     (B, V) nor the (B * K, V) matrix is written.  No floating-point atomics, no allocation, no host synchronisation.
+ *   Workspace: there is no size function of its own.  nrl_topk_scores_workspace_bytes(B, V, D, k, slices) with B in users always
+ *     suffices: the entry keeps B * lists * k * 8 bytes, where lists = min(slices, tiles) for slices > 0 and otherwise
+ *     ceil(512 / ceil(B / floor(64 / K))) clamped to [1, tiles], which is never above the count that function sizes for
+ *     (floor(64 / K) <= 64).  The entry carves with its own count and refuses a shorter buffer with NRL_E_WORKSPACE before any
+ *     launch.  B == 0 returns success without a launch; V == 0 fills the output with -1 / -inf.  Sizes or a mode outside the
+ *     limits, and mode 2 without gate, return NRL_E_INVALID. */
+#define NRL_TOPK_MAX_INTERESTS 64
+int nrl_topk_interest_scores(const float* interests, const float* gate, const float* table, int64_t B, int32_t K, int64_t V, int32_t D,
+                             int32_t k, int32_t mode, const int64_t* excl_idx, const int64_t* excl_off, const uint8_t* eligible,
+                             int32_t slices, int64_t* out_idx, float* out_score, int32_t* status, void* ws, size_t ws_bytes,
+                             void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -356,13 +356,291 @@ __global__ __launch_bounds__(64) void tk_merge_kernel(TkArgs A) {
   }
 }
 
+// ---- multi-interest scores (MINER) ---------------------------------------------------------------------------------------------
+// A user is K interest rows; a table row's score is an aggregate of the K dot products (ops_miner.SCORE_MODES: 0 max, 1 mean,
+// 2 softmax-weighted by the K gate logits).  tki_scores_kernel is tk_scores_kernel with the (B * K, D) interest rows as the A
+// operand: the 64 rows of a workgroup hold Ut = 64 / K whole users (rows from Ut * K on are zero and belong to nobody), and once
+// the 64 x 128 tile of s_j is in LDS the K rows of every user are reduced per column, in ascending j, into the user's first row.
+// From there the scan, the exclusion and the insertion are those of tk_scores_kernel over Ut users, and tk_merge_kernel finishes.
+// GATE (mode 2) runs the gate rows as a second A operand against the SAME staged table tile into a second score tile.
+struct TkiArgs : TkArgs {                      // `user` is the interests; B counts users
+  const float* gate;
+  int32_t K, Ut, mode;
+};
+
+constexpr size_t tki_lds_bytes(bool gate, int Ut, int k) {
+  return (size_t)(gate ? 2 : 1) * TK_BU * TK_SCLD * 4 + (size_t)Ut * k * 8 + (size_t)Ut * 8 + (size_t)Ut * TK_XCAP * 4 + (size_t)Ut * 4 +
+         TK_BV;
+}
+static_assert(2 * TK_BK * (2 * TK_LDA + TK_LDB) <= 2 * TK_BU * TK_SCLD, "with a gate the three operand tiles live inside the two score tiles");
+static_assert(tki_lds_bytes(true, TK_BU, NRL_TOPK_MAX_K) <= 160 * 1024, "the largest layout fits the dynamic LDS the launch may request");
+
+// the aggregate of one user's K scores of one column (stride TK_SCLD apart); lg: the gate logits of the same positions
+template <bool GATE>
+__device__ __forceinline__ float tki_aggregate(const float* s, const float* lg, int K, int mode) {
+  if constexpr (GATE) {
+    float m = lg[0];
+    for (int j = 1; j < K; ++j) m = fmaxf(m, lg[j * TK_SCLD]);
+    float num = 0.f, den = 0.f;
+    for (int j = 0; j < K; ++j) {              // a NaN logit, or inf - inf, makes e (and the score) NaN
+      const float e = expf(__fsub_rn(lg[j * TK_SCLD], m));
+      const float es = __fmul_rn(e, s[j * TK_SCLD]);
+      num = j ? __fadd_rn(num, es) : es;
+      den = j ? __fadd_rn(den, e) : e;
+    }
+    return num / den;
+  }
+  float a = s[0];
+  if (mode == 0) {
+    bool bad = a != a;
+    for (int j = 1; j < K; ++j) {
+      const float x = s[j * TK_SCLD];
+      bad |= x != x;
+      a = fmaxf(a, x);
+    }
+    return bad ? __uint_as_float(0x7FC00000u) : a;
+  }
+  for (int j = 1; j < K; ++j) a = __fadd_rn(a, s[j * TK_SCLD]);
+  return a / (float)K;
+}
+
+template <bool GATE>
+__global__ __launch_bounds__(TK_THREADS) void tki_scores_kernel(TkiArgs A) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char tk_smem[];
+  const int K = A.K, Ut = A.Ut;
+  float* const sc = reinterpret_cast<float*>(tk_smem);                       // [TK_BU][TK_SCLD] the s_j; with a gate
+  float* const lg = sc + TK_BU * TK_SCLD;                                    // [TK_BU][TK_SCLD] the l_j follow.  Before they exist:
+  float* const As = sc;                                                      // [2][TK_BK][TK_LDA] interest rows,
+  float* const Gs = As + 2 * TK_BK * TK_LDA;                                 // [2][TK_BK][TK_LDA] gate rows (GATE only) and
+  float* const Bs = Gs + (GATE ? 2 * TK_BK * TK_LDA : 0);                    // [2][TK_BK][TK_LDB] table rows
+  unsigned long long* const lists = reinterpret_cast<unsigned long long*>(sc + (GATE ? 2 : 1) * TK_BU * TK_SCLD);      // [Ut][k]
+  int64_t* const xs = reinterpret_cast<int64_t*>(lists + Ut * A.k);          // [Ut] start of the user's exclusion list
+  int32_t* const xl = reinterpret_cast<int32_t*>(xs + Ut);                   // [Ut][TK_XCAP] cached exclusion rows (-1: none)
+  int32_t* const xn = xl + Ut * TK_XCAP;                                     // [Ut] its length (0: none, or bad offsets)
+  uint8_t* const el = reinterpret_cast<uint8_t*>(xn + Ut);                   // [TK_BV] column inside V and eligible
+
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int wm = wave >> 1, wn = wave & 1;
+  const int l15 = lane & 15, g = lane >> 4;
+  const int k = A.k, D = A.D, V = A.V;
+  const int sl = (int)(blockIdx.x % (unsigned)A.slices);
+  const int64_t u0 = (int64_t)(blockIdx.x / (unsigned)A.slices) * Ut;        // first user of the tile
+  const int nu = A.B - u0 < Ut ? (int)(A.B - u0) : Ut;                       // its users (>= 1)
+  const int v_begin = sl * A.tiles_per_slice * TK_BV;
+  const int64_t v_stop = (int64_t)v_begin + (int64_t)A.tiles_per_slice * TK_BV;
+  const int v_end = v_stop < V ? (int)v_stop : V;
+  const int nvt = (v_end - v_begin + TK_BV - 1) / TK_BV;
+  const int nkt = (D + TK_BK - 1) / TK_BK;
+
+  for (int i = tid; i < Ut * k; i += TK_THREADS) lists[i] = 0ull;
+  if (tid < Ut) {
+    int64_t s = 0, n = 0;
+    if (tid < nu && !tk_excl_range(A, u0 + tid, s, n)) n = 0;                // the merge kernel flags and blanks such a user
+    xs[tid] = s;
+    xn[tid] = (int32_t)(n < 0x7FFFFFFF ? n : 0x7FFFFFFF);
+  }
+  __syncthreads();
+  for (int i = tid; i < Ut * TK_XCAP; i += TK_THREADS) {
+    const int ul = i / TK_XCAP, j = i % TK_XCAP;
+    int32_t x = -1;
+    if (j < xn[ul]) {
+      const int64_t r = A.excl_idx[xs[ul] + j];
+      if (r >= 0 && r < V) x = (int32_t)r;
+    }
+    xl[i] = x;
+  }
+
+  // staging: tile row r is interest row u0 * K + r of the (B * K, D) matrix while r < nu * K, zero from there on
+  const int srow = tid >> 2, skc = (tid & 3) * 4;
+  const bool ua_ok = srow < nu * K;
+  const int64_t ua = ua_ok ? u0 * K + srow : 0;
+  const float* const pa = A.user + ua * D;
+  const float* const pg = GATE ? A.gate + ua * D : nullptr;
+  bool nan = false;
+
+  for (int vt = 0; vt < nvt; ++vt) {
+    const int v0 = v_begin + vt * TK_BV;
+    const float* pb[2];
+    bool vb_ok[2];
+#pragma unroll
+    for (int c = 0; c < 2; ++c) {
+      const int64_t v = (int64_t)v0 + srow + c * 64;
+      vb_ok[c] = v < V;
+      pb[c] = A.table + (int64_t)(vb_ok[c] ? v : V - 1) * D;
+    }
+    if (tid < TK_BV) {
+      const int64_t v = (int64_t)v0 + tid;
+      el[tid] = (v < V && (!A.eligible || A.eligible[v])) ? 1 : 0;
+    }
+    float4 ra, rg, rb[2];
+    auto load_tiles = [&](int k0) {                  // unconditional loads from clamped addresses; masked when staged
+      const int kk = k0 + skc < D ? k0 + skc : D - 4;
+      ra = *reinterpret_cast<const float4*>(pa + kk);
+      if constexpr (GATE) rg = *reinterpret_cast<const float4*>(pg + kk);
+#pragma unroll
+      for (int c = 0; c < 2; ++c) rb[c] = *reinterpret_cast<const float4*>(pb[c] + kk);
+    };
+    auto store_tiles = [&](int buf, int k0) {
+      const bool kok = k0 + skc < D;
+      float* as = As + buf * TK_BK * TK_LDA;
+      float* bs = Bs + buf * TK_BK * TK_LDB;
+      const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
+      const float4 a = (kok && ua_ok) ? ra : z;
+      as[(skc + 0) * TK_LDA + srow] = a.x;
+      as[(skc + 1) * TK_LDA + srow] = a.y;
+      as[(skc + 2) * TK_LDA + srow] = a.z;
+      as[(skc + 3) * TK_LDA + srow] = a.w;
+      if constexpr (GATE) {
+        float* gs = Gs + buf * TK_BK * TK_LDA;
+        const float4 q = (kok && ua_ok) ? rg : z;
+        gs[(skc + 0) * TK_LDA + srow] = q.x;
+        gs[(skc + 1) * TK_LDA + srow] = q.y;
+        gs[(skc + 2) * TK_LDA + srow] = q.z;
+        gs[(skc + 3) * TK_LDA + srow] = q.w;
+      }
+#pragma unroll
+      for (int c = 0; c < 2; ++c) {
+        const float4 b = (kok && vb_ok[c]) ? rb[c] : z;
+        const int row = srow + c * 64;
+        bs[(skc + 0) * TK_LDB + row] = b.x;
+        bs[(skc + 1) * TK_LDB + row] = b.y;
+        bs[(skc + 2) * TK_LDB + row] = b.z;
+        bs[(skc + 3) * TK_LDB + row] = b.w;
+      }
+    };
+
+    tk_f32x4 acc[2][4], gac[2][4];
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        acc[i][j] = tk_f32x4{0.f, 0.f, 0.f, 0.f};
+        if constexpr (GATE) gac[i][j] = tk_f32x4{0.f, 0.f, 0.f, 0.f};
+      }
+
+    load_tiles(0);
+    store_tiles(0, 0);
+    __syncthreads();
+    for (int kt = 0; kt < nkt; ++kt) {
+      const int buf = kt & 1;
+      if (kt + 1 < nkt) load_tiles((kt + 1) * TK_BK);
+      const float* as = As + buf * TK_BK * TK_LDA + wm * 32 + l15;
+      const float* gs = Gs + buf * TK_BK * TK_LDA + wm * 32 + l15;
+      const float* bs = Bs + buf * TK_BK * TK_LDB + wn * 64 + l15;
+#pragma unroll
+      for (int ks = 0; ks < TK_BK / 4; ++ks) {
+        float a[2], q[2], b[4];
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+          a[i] = as[(4 * ks + g) * TK_LDA + i * 16];
+          if constexpr (GATE) q[i] = gs[(4 * ks + g) * TK_LDA + i * 16];
+        }
+#pragma unroll
+        for (int j = 0; j < 4; ++j) b[j] = bs[(4 * ks + g) * TK_LDB + j * 16];
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+          for (int j = 0; j < 4; ++j) {
+            acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[i], b[j], acc[i][j], 0, 0, 0);
+            if constexpr (GATE) gac[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(q[i], b[j], gac[i][j], 0, 0, 0);
+          }
+      }
+      if (kt + 1 < nkt) store_tiles(buf ^ 1, (kt + 1) * TK_BK);
+      __syncthreads();
+    }
+
+    // accumulators -> score tile(s): the lane holds tile row 4g + r, column l15 of every 16 x 16 block
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int at = (wm * 32 + i * 16 + 4 * g + r) * TK_SCLD + wn * 64 + j * 16 + l15;
+          sc[at] = acc[i][j][r];
+          if constexpr (GATE) lg[at] = gac[i][j][r];
+        }
+    __syncthreads();
+
+    // aggregation: the K rows of user ul, one column per thread, into the user's first row (nobody else reads or writes them)
+    for (int i = tid; i < nu * TK_BV; i += TK_THREADS) {
+      const int at = (i / TK_BV) * K * TK_SCLD + (i % TK_BV);
+      sc[at] = tki_aggregate<GATE>(sc + at, lg + at, K, A.mode);
+    }
+    __syncthreads();
+
+    // selection: wave w owns users w, w + 4, ... of the tile and their lists
+    const bool e_0 = el[lane] != 0, e_1 = el[64 + lane] != 0;
+    for (int ul = wave; ul < nu; ul += 4) {
+      const float* row = sc + ul * K * TK_SCLD;
+      unsigned long long* L = lists + ul * k;
+      const unsigned long long thr = L[k - 1];
+      const unsigned long long c0 = e_0 ? tk_entry(row[lane], (uint32_t)v0 + lane) : 0ull;
+      const unsigned long long c1 = e_1 ? tk_entry(row[64 + lane], (uint32_t)v0 + 64 + lane) : 0ull;
+      unsigned long long m0 = __ballot(c0 > thr), m1 = __ballot(c1 > thr);
+      if (!(m0 | m1)) continue;
+      const int n = xn[ul];
+      for (int base = 0; base < n; base += 64) {       // excluded rows inside this tile lose their bit
+        const int i = base + lane;
+        int64_t x = -1;
+        if (i < n) x = i < TK_XCAP ? (int64_t)xl[ul * TK_XCAP + i] : A.excl_idx[xs[ul] + i];
+        const int64_t rel64 = x - v0;
+        const bool inr = x >= 0 && rel64 >= 0 && rel64 < TK_BV;
+        const int rel = inr ? (int)rel64 : 0;
+        unsigned long long hit = __ballot(inr);
+        while (hit) {
+          const int b = __ffsll((long long)hit) - 1;
+          hit &= hit - 1;
+          const int r = __shfl(rel, b, 64);
+          if (r < 64)
+            m0 &= ~(1ull << r);
+          else
+            m1 &= ~(1ull << (r - 64));
+        }
+      }
+      if (!(m0 | m1)) continue;
+      TkList S;
+      S.e0 = lane < k ? L[lane] : 0ull;
+      S.e1 = lane + 64 < k ? L[lane + 64] : 0ull;
+      bool changed = S.take(c0, m0, k, lane, nan);
+      changed |= S.take(c1, m1 & __ballot(c1 > S.kth(k)), k, lane, nan);
+      if (changed) {
+        if (lane < k) L[lane] = S.e0;
+        if (lane + 64 < k) L[lane + 64] = S.e1;
+        tk_wave_sync();
+      }
+    }
+    __syncthreads();                                  // the score tiles and `el` are free for the next tile's operands
+  }
+
+  if (nan && lane == 0) atomicOr(A.status, NRL_TOPK_E_NAN);
+  tk_wave_sync();
+  for (int ul = wave; ul < nu; ul += 4) {
+    unsigned long long* P = A.partial + ((u0 + ul) * A.slices + sl) * k;
+    for (int p = lane; p < k; p += 64) P[p] = lists[ul * k + p];
+  }
+}
+
+template <bool GATE>
+static int tki_launch(const TkiArgs& A, int64_t blocks, hipStream_t st) {
+  const size_t smem = tki_lds_bytes(GATE, A.Ut, A.k);
+  // more than 64 KB of dynamic LDS needs the attribute; it belongs to the current device, so it is set per call
+  if (smem > 64 * 1024)
+    NRL_HIP(hipFuncSetAttribute((const void*)tki_scores_kernel<GATE>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+  tki_scores_kernel<GATE><<<(unsigned)blocks, TK_THREADS, smem, st>>>(A);
+  NRL_LAUNCH_CHECK();
+  return NRL_OK;
+}
+
 static bool tk_shape_ok(int64_t B, int64_t V, int32_t D, int32_t k) {
   return B >= 0 && V >= 0 && V < ((int64_t)1 << 31) && D > 0 && D % 4 == 0 && D <= NRL_TOPK_MAX_D && k >= 1 && k <= NRL_TOPK_MAX_K;
 }
 
 // how many pieces of V run in parallel per user tile (`lists`: what the workspace is sized for) and the table tiles of each
-static void tk_plan(int64_t B, int64_t V, int32_t slices, int64_t& lists, int64_t& used, int64_t& tiles_per_slice) {
-  const int64_t nvt = ceil_div(V, TK_BV), ut = ceil_div(B, TK_BU);
+// (`bu` users per workgroup: TK_BU, or the whole users of a multi-interest tile)
+static void tk_plan(int64_t B, int64_t V, int32_t slices, int64_t bu, int64_t& lists, int64_t& used, int64_t& tiles_per_slice) {
+  const int64_t nvt = ceil_div(V, TK_BV), ut = ceil_div(B, bu);
   int64_t want = slices > 0 ? slices : ceil_div(TK_TARGET_BLOCKS, ut > 0 ? ut : 1);
   if (want > nvt) want = nvt;
   if (want < 1) want = 1;
@@ -378,16 +656,16 @@ using namespace nrl;
 extern "C" {
 
 // k packed (score, index) keys per (user, slice list); never empty
-static void tk_layout(Arena& a, int64_t B, int64_t V, int32_t k, int32_t slices, unsigned long long** partial) {
+static void tk_layout(Arena& a, int64_t B, int64_t V, int32_t k, int32_t slices, int64_t bu, unsigned long long** partial) {
   int64_t lists, used, tps;
-  tk_plan(B, V, slices, lists, used, tps);
+  tk_plan(B, V, slices, bu, lists, used, tps);
   const size_t keys = (size_t)B * (size_t)lists * (size_t)k;
   *partial = a.take<unsigned long long>(keys > 0 ? keys : 1);
 }
 
 size_t nrl_topk_scores_workspace_bytes(int64_t B, int64_t V, int32_t D, int32_t k, int32_t slices) {
   if (!tk_shape_ok(B, V, D, k) || slices < 0) return 256;
-  return measure_workspace<unsigned long long*>([&](Arena& a, auto* w) { tk_layout(a, B, V, k, slices, w); });
+  return measure_workspace<unsigned long long*>([&](Arena& a, auto* w) { tk_layout(a, B, V, k, slices, TK_BU, w); });
 }
 
 int nrl_topk_scores(const float* user_vec, const float* table, int64_t B, int64_t V, int32_t D, int32_t k, const int64_t* excl_idx,
@@ -403,9 +681,9 @@ int nrl_topk_scores(const float* user_vec, const float* table, int64_t B, int64_
   if (B == 0) return NRL_OK;
   NRL_REQUIRE(out_idx && out_score && user_vec && (V == 0 || table), "topk_scores: null argument");
   unsigned long long* partial;
-  NRL_TRY(carve_workspace(ws, ws_bytes, [&](Arena& a) { tk_layout(a, B, V, k, slices, &partial); }));
+  NRL_TRY(carve_workspace(ws, ws_bytes, [&](Arena& a) { tk_layout(a, B, V, k, slices, TK_BU, &partial); }));
   int64_t lists, used, tps;
-  tk_plan(B, V, slices, lists, used, tps);
+  tk_plan(B, V, slices, TK_BU, lists, used, tps);
   const int64_t blocks = ceil_div(B, TK_BU) * used;
   NRL_REQUIRE(blocks < ((int64_t)1 << 31), "topk_scores: grid too large (%lld workgroups)", (long long)blocks);
 
@@ -435,6 +713,58 @@ int nrl_topk_scores(const float* user_vec, const float* table, int64_t B, int64_
     NRL_LAUNCH_CHECK();
   }
   tk_merge_kernel<<<(unsigned)B, 64, 0, st>>>(A);
+  NRL_LAUNCH_CHECK();
+  return NRL_OK;
+}
+
+int nrl_topk_interest_scores(const float* interests, const float* gate, const float* table, int64_t B, int32_t K, int64_t V, int32_t D,
+                             int32_t k, int32_t mode, const int64_t* excl_idx, const int64_t* excl_off, const uint8_t* eligible,
+                             int32_t slices, int64_t* out_idx, float* out_score, int32_t* status, void* ws, size_t ws_bytes,
+                             void* stream) {
+  NRL_REQUIRE(B >= 0 && V >= 0 && D >= 0 && slices >= 0, "topk_interest_scores: negative size");
+  NRL_REQUIRE(K >= 1 && K <= NRL_TOPK_MAX_INTERESTS, "topk_interest_scores: K in [1, %d] (got %d)", NRL_TOPK_MAX_INTERESTS, K);
+  NRL_REQUIRE(mode >= 0 && mode <= 2, "topk_interest_scores: mode 0 (max), 1 (mean) or 2 (weighted) (got %d)", mode);
+  NRL_REQUIRE(mode != 2 || gate, "topk_interest_scores: mode 2 (weighted) needs the gate rows");
+  NRL_REQUIRE(k >= 1 && k <= NRL_TOPK_MAX_K, "topk_interest_scores: k in [1, %d] (got %d)", NRL_TOPK_MAX_K, k);
+  NRL_REQUIRE(D > 0 && D % 4 == 0 && D <= NRL_TOPK_MAX_D, "topk_interest_scores: D a multiple of 4 in [4, %d] (got %d)", NRL_TOPK_MAX_D, D);
+  NRL_REQUIRE(V < ((int64_t)1 << 31), "topk_interest_scores: at most 2^31 - 1 table rows (got %lld)", (long long)V);
+  NRL_REQUIRE(B < ((int64_t)1 << 31), "topk_interest_scores: at most 2^31 - 1 users per call (got %lld)", (long long)B);
+  NRL_REQUIRE((excl_idx == nullptr) == (excl_off == nullptr) || excl_off, "topk_interest_scores: excl_idx without excl_off");
+  if (B == 0) return NRL_OK;
+  // the lists of this entry's own plan: never more than nrl_topk_scores_workspace_bytes(B, V, D, k, slices) holds (Ut <= TK_BU)
+  const int32_t Ut = TK_BU / K;
+  unsigned long long* partial;
+  NRL_TRY(carve_workspace(ws, ws_bytes, [&](Arena& a) { tk_layout(a, B, V, k, slices, Ut, &partial); }));
+  NRL_REQUIRE(status, "topk_interest_scores: the status word is required");
+  NRL_REQUIRE(out_idx && out_score && interests && (V == 0 || table), "topk_interest_scores: null argument");
+  int64_t lists, used, tps;
+  tk_plan(B, V, slices, Ut, lists, used, tps);
+  const int64_t blocks = ceil_div(B, Ut) * used;
+  NRL_REQUIRE(blocks < ((int64_t)1 << 31), "topk_interest_scores: grid too large (%lld workgroups)", (long long)blocks);
+
+  TkiArgs A;
+  A.user = interests;
+  A.gate = mode == 2 ? gate : nullptr;
+  A.table = table;
+  A.B = B;
+  A.V = (int32_t)V;
+  A.D = D;
+  A.k = k;
+  A.K = K;
+  A.Ut = Ut;
+  A.mode = mode;
+  A.excl_idx = excl_idx;
+  A.excl_off = excl_off;
+  A.eligible = eligible;
+  A.slices = (int32_t)used;
+  A.tiles_per_slice = (int32_t)tps;
+  A.partial = partial;
+  A.out_idx = out_idx;
+  A.out_score = out_score;
+  A.status = status;
+  hipStream_t st = (hipStream_t)stream;
+  if (used > 0) NRL_TRY(mode == 2 ? tki_launch<true>(A, blocks, st) : tki_launch<false>(A, blocks, st));
+  tk_merge_kernel<<<(unsigned)B, 64, 0, st>>>(static_cast<const TkArgs&>(A));
   NRL_LAUNCH_CHECK();
   return NRL_OK;
 }

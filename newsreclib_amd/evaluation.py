@@ -248,6 +248,36 @@ class NewsVectorCache(_ImpressionCache):
         return ops.topk_scores(user, self.vectors, k, excl[0], excl[1], eligible.to(dev) if eligible is not None else None)
 
 
+    @torch.no_grad()
+    def recommend_interests(self, hist_idx: torch.Tensor, hist_sizes: torch.Tensor, k: int, user_idx: Optional[torch.Tensor] = None,
+                            exclude_history: bool = True, eligible: Optional[torch.Tensor] = None,
+                            bias: Optional[torch.Tensor] = None):
+        """``recommend`` for a module whose score is an aggregate over K candidate-independent interest vectors
+        (``multi_interest_scorer``: MINER) -> (news_idx (B, k) int64, scores (B, k) fp32, status): the module's
+        ``user_interests`` over the gathered history vectors (eval mode, restored afterwards; ``max_hist`` is the batch's longest
+        history, as ``scores`` uses), then ``ops.topk_interest_scores`` with the module's ``interest_score_mode`` against the
+        cached table.  Same contract as ``recommend``: ``hist_idx`` on the GPU, ``hist_sizes`` on the host, nothing read back.
+        MINER's category bias needs the batch's candidate lists and is left out (``MINERModule.user_interests``); ``bias``
+        (n_hist) passes a per-history-row bias of the caller's own."""
+        if not getattr(self.module, "multi_interest_scorer", False):
+            raise NotImplementedError(
+                f"{type(self.module).__name__} has no candidate-independent interest vectors (no `multi_interest_scorer`); a "
+                "module that scores by one dot product with a user vector (`dot_product_scorer`) is served by `recommend`")
+        if not hist_idx.is_cuda:
+            raise RuntimeError(f"newsreclib_amd: `hist_idx` must live on the GPU (got {hist_idx.device}); there is no CPU path")
+        if self.vectors is None:
+            self.build()
+        dev = self.table.device
+        hist_idx = hist_idx.to(dev).long()
+        meta = self._user_meta(hist_sizes, user_idx)
+        hv = ops.embedding_gather(self.vectors, hist_idx.reshape(-1, 1)).reshape(-1, self.vectors.shape[1])
+        with eval_mode(self.module):
+            interests, gate = self.module.user_interests(hv, meta, bias=bias.to(dev) if bias is not None else None)
+        excl = (hist_idx, meta["hist_offsets"]) if exclude_history else (None, None)
+        return ops.topk_interest_scores(interests, self.vectors, k, self.module.interest_score_mode, gate, excl[0], excl[1],
+                                        eligible.to(dev) if eligible is not None else None)
+
+
 class MannerVectorCache(_ImpressionCache):
     """Encode-once evaluation of ``manner_module.MANNERModule``: one ``NewsVectorCache`` per loaded sub-model over the same
     ``DeviceNewsTable``; ``scores`` is one ``nrl_manner_scores`` launch that gathers straight from the (up to three) tables.
@@ -405,8 +435,8 @@ def format_recommendations(user_ids: Sequence, news_idx: torch.Tensor, scores: t
 
 def recommend_users(cache: NewsVectorCache, users: Sequence[Dict], k: int, batch_size: int = 512,
                     eligible: Optional[torch.Tensor] = None) -> Dict[str, Dict[str, float]]:
-    """``cache.recommend`` over a list of users ({"hist": idx tensor[, "user_idx", "user_id"]}) in batches -> the recommendation
-    dictionary of ``format_recommendations``.  ``user_id`` defaults to the user's position in the list + 1 (as ``build_batch``);
+    """``cache.recommend`` (``cache.recommend_interests`` where the cache's module is a ``multi_interest_scorer``) over a list of
+    users ({"hist": idx tensor[, "user_idx", "user_id"]}) in batches -> the recommendation dictionary of ``format_recommendations``.  ``user_id`` defaults to the user's position in the list + 1 (as ``build_batch``);
     news ids come from the table's ``news_ids`` column when it has one.  One device-to-host copy per batch, at its end; a status
     flag of the batch (``ops.TOPK_FLAGS``: each is handled by the kernel) is passed on as a warning."""
     dev = cache.table.device
@@ -417,7 +447,8 @@ def recommend_users(cache: NewsVectorCache, users: Sequence[Dict], k: int, batch
         hs = torch.tensor([len(u["hist"]) for u in chunk])
         hist = torch.cat([torch.as_tensor(u["hist"]).long() for u in chunk]).to(dev)
         uidx = torch.stack([torch.as_tensor(u["user_idx"]) for u in chunk]) if "user_idx" in chunk[0] else None
-        idx, score, status = cache.recommend(hist, hs, k, user_idx=uidx, eligible=eligible)
+        rank = cache.recommend_interests if getattr(cache.module, "multi_interest_scorer", False) else cache.recommend
+        idx, score, status = rank(hist, hs, k, user_idx=uidx, eligible=eligible)
         packed = torch.cat([idx.double(), score.double(), status.double().expand(idx.shape[0], 1)], dim=1).cpu()      # the one copy
         word = int(packed[0, -1]) if packed.shape[0] else 0
         if word:                                            # the kernel has dealt with each of these; the caller should know

@@ -40,6 +40,10 @@ from .user_encoder_miner import TargetAwareAttention
 
 
 class MINERModule(AbstractRecommender):
+    # score = an aggregate over K candidate-independent interest vectors (``user_interests``): no single dot product, so not a
+    # ``dot_product_scorer``; ``evaluation.NewsVectorCache.recommend_interests`` ranks the whole table by it
+    multi_interest_scorer = True
+
     def __init__(
         self,
         dataset_attributes: List[str],
@@ -154,6 +158,35 @@ class MINERModule(AbstractRecommender):
             scores = ops_miner.ScoreFn.apply(cand_news_vector, user_vector, None, batch["cand_offsets"], B,
                                              batch["max_cand"], hp.score_type)
         return (scores, user_vector) if with_aux else scores
+
+    @property
+    def interest_score_mode(self) -> str:
+        """The aggregate over the interest vectors of ``user_interests`` (``ops_miner.SCORE_MODES``): ``score_type``, or "mean"
+        over the one history mean under late fusion."""
+        return "mean" if self.hparams.late_fusion else self.hparams.score_type
+
+    def user_interests(self, hist_news_vector: torch.Tensor, batch: Dict, bias: Optional[torch.Tensor] = None):
+        """The candidate-independent half of ``score_news_vectors`` -> (interests (B, K, D), gate (B, K, D) or None); the score
+        of any news is their aggregate ``interest_score_mode`` (``ops.topk_interest_scores``).  Early fusion: the
+        poly-attention user vectors and, for ``score_type="weighted"``, ``gate = gelu(user_vector Wt^T)`` with the projection
+        formed as ``TargetAwareAttention.forward`` forms it.  Late fusion: the history mean as the one interest (K = 1), no gate.
+
+        The category bias of the reference is a mean over the candidate rows OF THE BATCH, each user's own candidates counted
+        as 0 (miner_module.py:275-285, ``ops_miner.CategBiasFn``): a function of the batch's candidate lists, and 0 for a user
+        whose candidates are all their own.  There are no candidate lists here, so the poly attention runs with ``bias=None``
+        whatever ``use_categ_bias`` says; ``bias`` (n_hist) takes a per-history-row bias from a caller who has one."""
+        hp = self.hparams
+        B = batch["batch_size"]
+        if hp.late_fusion:
+            hist_agg = dense_rows(hist_news_vector, batch["batch_hist"], B, batch["max_hist"], batch["hist_offsets"])
+            return ops.HistMeanFn.apply(hist_agg, batch["hist_offsets"]).unsqueeze(dim=1), None
+        user_vector = self.user_encoder(hist_news_vector, batch["hist_offsets"], B, batch["max_hist"], bias=bias)
+        gate = None
+        if hp.score_type == "weighted":
+            K, D = user_vector.shape[1], user_vector.shape[2]
+            z = ops_miner.BiasFreeLinearFn.apply(user_vector.reshape(B * K, D), self.target_aware_attn.linear.weight, None)
+            gate = torch.nn.functional.gelu(z).view(B, K, D)
+        return user_vector, gate
 
     # -- reference: miner_module.py:398-406 -----------------------------------------------------------
     def _aux_loss(self, batch: Dict, user_vector: torch.Tensor) -> torch.Tensor:

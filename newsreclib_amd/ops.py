@@ -755,3 +755,63 @@ def topk_scores(user_vec: torch.Tensor, table: torch.Tensor, k: int, excl_idx: O
                                    int(slices), idx.data_ptr(), score.data_ptr(), status.data_ptr(), ws.data_ptr(), ws.numel(),
                                    _stream()), "nrl_topk_scores")
     return idx, score, status
+
+
+TOPK_MAX_INTERESTS = 64
+
+
+def topk_interest_scores(interests: torch.Tensor, table: torch.Tensor, k: int, mode: str, gate: Optional[torch.Tensor] = None,
+                         excl_idx: Optional[torch.Tensor] = None, excl_off: Optional[torch.Tensor] = None,
+                         eligible: Optional[torch.Tensor] = None, slices: int = 0):
+    """``nrl_topk_interest_scores``: ``topk_scores`` where a user is ``K`` interest vectors -- ``interests`` (B, K, D) -- and a
+    table row's score is their aggregate ``mode`` (``ops_miner.SCORE_MODES``): "max" ``max_j s_j``, "mean" ``sum_j s_j / K``,
+    "weighted" ``sum_j softmax_j(l)_j s_j`` with ``s_j = interests[u, j] . table[v]`` and ``l_j = gate[u, j] . table[v]``
+    (``gate`` (B, K, D) = gelu(user_vector Wt^T), required by "weighted" alone).  -> (idx (B, k) int64, score (B, k) fp32,
+    status (1) int32) with the ordering, exclusion, eligibility and status flags of ``topk_scores``; neither the (B, V) nor the
+    (B K, V) matrix is materialised.  The workspace is sized by ``nrl_topk_scores_workspace_bytes`` with B in users, which always
+    suffices.  Nothing here synchronises with the host."""
+    from .ops_miner import SCORE_MODES
+    lib = _lib.load()
+    interests, table = _chk(interests, torch.float32, "interests"), _chk(table, torch.float32, "table")
+    if interests.dim() != 3 or table.dim() != 2 or interests.shape[2] != table.shape[1]:
+        raise ValueError(f"newsreclib_amd: interests (B, K, D) and table (V, D) expected, got {tuple(interests.shape)} and "
+                         f"{tuple(table.shape)}")
+    if mode not in SCORE_MODES:
+        raise ValueError(f"newsreclib_amd: mode must be one of {sorted(SCORE_MODES)} (got {mode!r})")
+    B, K, D, V, k = int(interests.shape[0]), int(interests.shape[1]), int(interests.shape[2]), int(table.shape[0]), int(k)
+    if K > TOPK_MAX_INTERESTS:
+        raise NotImplementedError(f"newsreclib_amd: topk_interest_scores takes at most {TOPK_MAX_INTERESTS} interest vectors per "
+                                  f"user (got {K})")
+    if mode == "weighted":
+        if gate is None:
+            raise ValueError("newsreclib_amd: mode 'weighted' needs `gate` (B, K, D) = gelu(user_vector Wt^T)")
+        gate = _chk(gate, torch.float32, "gate")
+        if gate.shape != interests.shape:
+            raise ValueError(f"newsreclib_amd: gate must have the shape of interests, got {tuple(gate.shape)}")
+    else:
+        gate = None
+    if (excl_idx is None) != (excl_off is None):
+        raise ValueError("newsreclib_amd: excl_idx and excl_off go together")
+    if excl_idx is not None:
+        excl_idx, excl_off = _chk(excl_idx, torch.int64, "excl_idx"), _chk(excl_off, torch.int64, "excl_off")
+        if excl_off.numel() != B + 1:
+            raise ValueError("newsreclib_amd: excl_off must have B + 1 entries")
+        # the kernel trusts excl_off[B] as the length of excl_idx: an offset beyond the list is turned into one it rejects
+        excl_off = torch.where(excl_off > excl_idx.numel(), torch.full_like(excl_off, -1), excl_off)
+    if eligible is not None:
+        if eligible.dtype == torch.bool and eligible.is_cuda:
+            eligible = eligible.to(torch.uint8)
+        eligible = _chk(eligible, torch.uint8, "eligible")
+        if eligible.numel() != V:
+            raise ValueError("newsreclib_amd: eligible must have one entry per table row")
+    dev = interests.device
+    idx = torch.empty((B, max(k, 0)), dtype=torch.int64, device=dev)
+    score = torch.empty((B, max(k, 0)), dtype=torch.float32, device=dev)
+    status = torch.zeros(1, dtype=torch.int32, device=dev)
+    ws = workspace(lib.nrl_topk_scores_workspace_bytes(B, V, D, k, int(slices)), dev)
+    ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
+    _lib.check(lib.nrl_topk_interest_scores(interests.data_ptr(), ptr(gate), table.data_ptr(), B, K, V, D, k, SCORE_MODES[mode],
+                                            ptr(excl_idx), ptr(excl_off), ptr(eligible), int(slices), idx.data_ptr(),
+                                            score.data_ptr(), status.data_ptr(), ws.data_ptr(), ws.numel(), _stream()),
+               "nrl_topk_interest_scores")
+    return idx, score, status
