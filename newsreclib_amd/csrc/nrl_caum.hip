@@ -24,11 +24,7 @@ struct SlotDrop {
   uint32_t stream_base;
   uint32_t thresh;
   float scale;
-  __device__ __forceinline__ uint32_t key(uint32_t stream) const {   // == dropout_key(seed, stream)
-    uint32_t s = lowbias32(stream + 0x9E3779B9u);
-    s = lowbias32((uint32_t)(seed >> 32) ^ s);
-    return lowbias32((uint32_t)(seed & 0xFFFFFFFFu) ^ s);
-  }
+  __device__ __forceinline__ uint32_t key(uint32_t stream) const { return dropout_key(seed, stream); }
   __device__ __forceinline__ float mult(uint32_t k, uint32_t flat_idx) const {
     return lowbias32(flat_idx * 0x9E3779B1u + k) >= thresh ? scale : 0.0f;
   }
@@ -232,17 +228,6 @@ __global__ void caum_group_tanh_bwd_kernel(const float* __restrict__ d_z, const 
 }
 
 // ---- DenseAttention layer 3 + softmax over max_hist + weighted sum + score, one workgroup per (b, i) ----------------------
-__device__ float block_sum(float v, float* red) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  v = wave_sum(v);
-  __syncthreads();
-  if (lane == 0) red[wave] = v;
-  __syncthreads();
-  float s = 0.f;
-  for (int w = 0; w < CAUM_THREADS / 64; ++w) s += red[w];
-  return s;
-}
-
 // slot i of the call is candidate slot slot0 + i of the impression (evaluation runs the slots in chunks)
 __global__ __launch_bounds__(CAUM_THREADS) void caum_score_fwd_kernel(
     const float* __restrict__ z2, const float* __restrict__ w3, const float* __restrict__ b3, const float* __restrict__ x,
@@ -283,7 +268,7 @@ __global__ __launch_bounds__(CAUM_THREADS) void caum_score_fwd_kernel(
     user[g * U + u] = acc;
     part += acc * cd[g * U + u];
   }
-  const float s = block_sum(part, red);
+  const float s = block_sum<CAUM_THREADS / 64>(part, red);
   if (threadIdx.x == 0) scores[g] = valid ? s : 0.f;
 }
 

@@ -73,7 +73,7 @@ __host__ __device__ __forceinline__ uint32_t lowbias32(uint32_t x) {
   return x;
 }
 
-inline uint32_t dropout_key(uint64_t seed, uint32_t stream) {
+__host__ __device__ __forceinline__ uint32_t dropout_key(uint64_t seed, uint32_t stream) {
   uint32_t s = lowbias32(stream + 0x9E3779B9u);
   s = lowbias32((uint32_t)(seed >> 32) ^ s);
   s = lowbias32((uint32_t)(seed & 0xFFFFFFFFu) ^ s);
@@ -112,6 +112,52 @@ __device__ __forceinline__ float wave_max(float v) {
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) v = fmaxf(v, __shfl_xor(v, off, 64));
   return v;
+}
+
+// Reductions over a workgroup of WAVES waves in a fixed order (xor tree within a wave, then the waves in order); every thread
+// gets the result.  `red` holds WAVES floats of LDS; the leading barrier lets it be reused by the next call.  The sum starts
+// from +0: a block of all -0 gives +0.
+template <int WAVES>
+__device__ __forceinline__ float block_sum(float v, float* red) {
+  v = wave_sum(v);
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  float s = 0.f;
+#pragma unroll
+  for (int w = 0; w < WAVES; ++w) s += red[w];
+  return s;
+}
+template <int WAVES>
+__device__ __forceinline__ float block_max(float v, float* red) {
+  v = wave_max(v);
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  float s = red[0];
+#pragma unroll
+  for (int w = 1; w < WAVES; ++w) s = fmaxf(s, red[w]);
+  return s;
+}
+
+// dot4 keeps this expression order: contraction sees the same tree everywhere
+__device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
+__device__ __forceinline__ void st4(float* p, float4 v) { *reinterpret_cast<float4*>(p) = v; }
+__device__ __forceinline__ float dot4(float4 a, float4 b) { return a.x * b.x + a.y * b.y + a.z * b.z + a.w * b.w; }
+
+// order-preserving key of a score: a > b  <=>  key(a) > key(b); -0 == +0, NaN = 0xFFFFFFFF above +inf
+__device__ __forceinline__ uint32_t score_key(float s) {
+  if (s != s) return 0xFFFFFFFFu;
+  if (s == 0.f) s = 0.f;
+  const uint32_t b = __float_as_uint(s);
+  return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+}
+
+// one wave: its LDS operations complete in order, the compiler must not move them across
+__device__ __forceinline__ void wave_lds_sync() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
 static inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }

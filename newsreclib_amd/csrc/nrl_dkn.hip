@@ -420,38 +420,6 @@ constexpr int DKN_MAX_DIM = 1024;
 constexpr int DKN_MAX_HID = 64;
 constexpr int DKN_WAVES = DKN_THREADS / 64;
 
-__device__ __forceinline__ float dkn_wave_sum(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
-// fixed-order block reduction of one value per thread (deterministic); every thread gets the result
-__device__ __forceinline__ float dkn_block_sum(float v, float* red) {
-  v = dkn_wave_sum(v);
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  __syncthreads();
-  if (lane == 0) red[wave] = v;
-  __syncthreads();
-  float s = 0.f;
-#pragma unroll
-  for (int i = 0; i < DKN_WAVES; ++i) s += red[i];
-  return s;
-}
-
-__device__ __forceinline__ float dkn_block_max(float v, float* red) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  __syncthreads();
-  if (lane == 0) red[wave] = v;
-  __syncthreads();
-  float s = red[0];
-#pragma unroll
-  for (int i = 1; i < DKN_WAVES; ++i) s = fmaxf(s, red[i]);
-  return s;
-}
-
 // The attention DNN is affine (Linear -> Linear, user/dkn.py:42-45): its score of (cand j, hist i) is
 // w2 . (W1[:, :dim] c_j + W1[:, dim:] h_i + b1) + b2 = v . h_i + (a term constant over i), which the softmax cancels.
 // So one attention per impression, s_i = v . h_i with v = W1[:, dim:]^T w2, serves every valid candidate; the gradients
@@ -482,20 +450,20 @@ __device__ int dkn_attend(const NrlDknClickParams& p, const float* hist, const i
     const float* h = hist + (h0 + i) * dim;
     float acc = 0.f;
     for (int d = lane; d < dim; d += 64) acc = fmaf(sm.v[d], h[d], acc);
-    acc = dkn_wave_sum(acc);
+    acc = wave_sum(acc);
     if (lane == 0) sm.s[i] = acc;
   }
   __syncthreads();
   float mx = -INFINITY;
   for (int i = threadIdx.x; i < nb; i += DKN_THREADS) mx = fmaxf(mx, sm.s[i]);
-  mx = dkn_block_max(mx, sm.red);
+  mx = block_max<DKN_WAVES>(mx, sm.red);
   float part = 0.f;
   for (int i = threadIdx.x; i < nb; i += DKN_THREADS) {
     const float e = expf(sm.s[i] - mx);
     sm.a[i] = e;
     part += e;
   }
-  const float tot = dkn_block_sum(part, sm.red);
+  const float tot = block_sum<DKN_WAVES>(part, sm.red);
   const float inv = nb > 0 ? 1.0f / tot : 0.f;
   for (int i = threadIdx.x; i < nb; i += DKN_THREADS) sm.a[i] *= inv;
   __syncthreads();
@@ -515,7 +483,7 @@ __device__ void dkn_pred_pre(const NrlDknClickParams& p, const float* c, int dim
     const float* w = p.pred_w1 + (int64_t)k * 2 * dim;
     float acc = 0.f;
     for (int d = lane; d < dim; d += 64) acc = fmaf(w[d], c[d], fmaf(w[dim + d], sm.u[d], acc));
-    acc = dkn_wave_sum(acc);
+    acc = wave_sum(acc);
     if (lane == 0) sm.pre[k] = acc + p.pred_b1[k];
   }
   __syncthreads();
@@ -610,13 +578,13 @@ __global__ __launch_bounds__(DKN_THREADS) void dkn_click_bwd_kernel(NrlDknClickP
     const float* h = hist + (h0 + i) * dim;
     float acc = 0.f;
     for (int d = lane; d < dim; d += 64) acc = fmaf(sm.u[d], h[d], acc);
-    acc = dkn_wave_sum(acc);
+    acc = wave_sum(acc);
     if (lane == 0) sm.s[i] = acc;
   }
   __syncthreads();
   float part = 0.f;
   for (int i = threadIdx.x; i < nb; i += DKN_THREADS) part += sm.a[i] * sm.s[i];
-  const float rho = dkn_block_sum(part, sm.red);
+  const float rho = block_sum<DKN_WAVES>(part, sm.red);
   for (int i = threadIdx.x; i < nb; i += DKN_THREADS) sm.s[i] = sm.a[i] * (sm.s[i] - rho);
   __syncthreads();
   for (int d = threadIdx.x; d < dim; d += DKN_THREADS) {

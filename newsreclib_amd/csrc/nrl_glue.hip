@@ -18,12 +18,6 @@ namespace nrl {
 
 constexpr int NG_MAXV = 8;          // float4 slots per lane: dim <= 8 * 256 = 2048
 
-__device__ __forceinline__ float ng_wave_sum(float v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
-
 struct GlueArgs {
   const float* x;        // fwd: dense output (rows, dim);   bwd: dy
   const float* res;      // fwd: residual (rows, dim);        bwd: z (saved pre-norm sum)
@@ -66,7 +60,7 @@ __global__ void __launch_bounds__(256) glue_ln_fwd_kernel(const GlueArgs A) {
     }
   }
   const float inv = 1.0f / (float)dim;
-  const float mean = ng_wave_sum(sum) * inv;
+  const float mean = wave_sum(sum) * inv;
   float sq = 0.f;
 #pragma unroll
   for (int i = 0; i < NV; ++i) {
@@ -76,7 +70,7 @@ __global__ void __launch_bounds__(256) glue_ln_fwd_kernel(const GlueArgs A) {
       sq += (a * a + b * b) + (cc * cc + d * d);
     }
   }
-  const float rstd = rsqrtf(ng_wave_sum(sq) * inv + A.eps);
+  const float rstd = rsqrtf(wave_sum(sq) * inv + A.eps);
   float* yr = A.y + row * dim;
 #pragma unroll
   for (int i = 0; i < NV; ++i) {
@@ -169,7 +163,7 @@ __global__ void __launch_bounds__(WAVES * 64) glue_ln_bwd_kernel(const GlueArgs 
         }
       }
     }
-    const float c1 = ng_wave_sum(s1) * inv, c2 = ng_wave_sum(s2) * inv;
+    const float c1 = wave_sum(s1) * inv, c2 = wave_sum(s2) * inv;
 #pragma unroll
     for (int i = 0; i < NV; ++i) {
       const int c = 4 * (lane + 64 * i);

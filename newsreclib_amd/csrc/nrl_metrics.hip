@@ -52,23 +52,12 @@ struct MtArgs {
   int32_t* status;
 };
 
-// order-preserving key of a score: a > b  <=>  key(a) > key(b); NaN above everything, -0 == +0
-__device__ __forceinline__ uint32_t mt_key(float s) {
-  if (s != s) return 0xFFFFFFFFu;
-  if (s == 0.f) s = 0.f;
-  const uint32_t b = __float_as_uint(s);
-  return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
-
 template <bool BLOCK>
 __device__ __forceinline__ void mt_sync() {
-  if (BLOCK) {
+  if (BLOCK)
     __syncthreads();
-  } else {                    // one wave: LDS operations complete in order, the compiler must not move them across
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-  }
+  else
+    wave_lds_sync();
 }
 
 __device__ __forceinline__ int mt_wave_sum_i(int v) {
@@ -88,6 +77,7 @@ __device__ __forceinline__ int mt_wave_or_i(int v) {
 }
 
 // group-wide reductions, identical in every thread of the group; the workgroup form adds the waves in wave order
+// (not block_sum: no leading +0, so four waves of -0 give -0 here)
 template <bool BLOCK>
 __device__ __forceinline__ float mt_sum_f(float v, float* red) {
   v = wave_sum(v);
@@ -208,16 +198,16 @@ __device__ __forceinline__ void mt_impression(const MtArgs& A, int64_t b, int t,
       const int i = base + o * G + t;
       const bool act = i < C;
       tv[o] = act ? A.targets[c0 + i] : 0.f;
-      ks[o] = act ? mt_key(A.preds[c0 + i]) : 0u;
-      kt[o] = mt_key(tv[o]);
+      ks[o] = act ? score_key(A.preds[c0 + i]) : 0u;
+      kt[o] = score_key(tv[o]);
       cs[o] = ct[o] = 0;
     }
     for (int tb = 0; tb < C; tb += TILE) {
       const int n = min(TILE, C - tb);
       mt_sync<BLOCK>();                   // the previous tile is no longer read
       for (int j = t; j < n; j += G) {
-        skey[j] = mt_key(A.preds[c0 + tb + j]);
-        tkey[j] = mt_key(A.targets[c0 + tb + j]);
+        skey[j] = score_key(A.preds[c0 + tb + j]);
+        tkey[j] = score_key(A.targets[c0 + tb + j]);
       }
       mt_sync<BLOCK>();
       for (int j = 0; j < n; ++j) {

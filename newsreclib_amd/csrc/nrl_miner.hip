@@ -25,9 +25,6 @@ constexpr size_t MN_LDS_MAX = 160 * 1024;      // LDS of one gfx950 workgroup
 constexpr int MN_CT = 32;                      // candidates per tile of the score backward
 constexpr float MN_FILL = 1e-30f;              // attention.py:117: masked_fill_(~mask, 1e-30), NOT -inf
 
-__device__ __forceinline__ float4 mn_ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
-__device__ __forceinline__ void mn_st4(float* p, float4 v) { *reinterpret_cast<float4*>(p) = v; }
-__device__ __forceinline__ float mn_dot4(float4 a, float4 b) { return a.x * b.x + a.y * b.y + a.z * b.z + a.w * b.w; }
 __device__ __forceinline__ float4 mn_sub4(float4 a, float4 b) { return make_float4(a.x - b.x, a.y - b.y, a.z - b.z, a.w - b.w); }
 __device__ __forceinline__ void mn_fma4(float4& acc, float s, float4 v) {
   acc.x += s * v.x;
@@ -38,18 +35,6 @@ __device__ __forceinline__ void mn_fma4(float4& acc, float s, float4 v) {
 __device__ __forceinline__ float mn_gelu(float z) { return 0.5f * z * (1.f + erff(z * 0.70710678118654752f)); }
 __device__ __forceinline__ float mn_gelu_grad(float z) {
   return 0.5f * (1.f + erff(z * 0.70710678118654752f)) + z * 0.39894228040143268f * expf(-0.5f * z * z);
-}
-
-// sum over the workgroup in a fixed order (xor tree within a wave, then the waves in order); every thread gets the result
-__device__ __forceinline__ float mn_block_sum(float v, float* red) {
-  v = wave_sum(v);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  float s = 0.f;
-#pragma unroll
-  for (int w = 0; w < MN_WAVES; ++w) s += red[w];
-  return s;
 }
 
 // every kernel here may take up to the whole LDS of a workgroup: the attribute is raised once per kernel, not per launch
@@ -85,8 +70,8 @@ __global__ __launch_bounds__(MN_THREADS) void miner_wgrad_kernel(const float* __
     if (n >= N) break;
     float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
 #pragma unroll 8
-    for (int64_t r = r0; r < r1; ++r) mn_fma4(acc, G[r * N + n], mn_ld4(X + r * K + 4 * k4));
-    mn_st4(slab + ((int64_t)blockIdx.x * N + n) * K + 4 * k4, acc);
+    for (int64_t r = r0; r < r1; ++r) mn_fma4(acc, G[r * N + n], ld4(X + r * K + 4 * k4));
+    st4(slab + ((int64_t)blockIdx.x * N + n) * K + 4 * k4, acc);
   }
 }
 
@@ -117,8 +102,8 @@ __device__ __forceinline__ void mn_cos_rowsum(const float* __restrict__ x, int R
   for (int k = wave; k < R; k += MN_WAVES) {
     float acc = 0.f;
     for (int d4 = lane; d4 < D4; d4 += 64) {
-      const float4 v = mn_ld4(x + (int64_t)k * D + 4 * d4);
-      acc += mn_dot4(v, v);
+      const float4 v = ld4(x + (int64_t)k * D + 4 * d4);
+      acc += dot4(v, v);
     }
     acc = wave_sum(acc);
     const float r = 1.f / (sqrtf(acc) + eps);
@@ -130,8 +115,8 @@ __device__ __forceinline__ void mn_cos_rowsum(const float* __restrict__ x, int R
   __syncthreads();
   for (int d4 = threadIdx.x; d4 < D4; d4 += MN_THREADS) {
     float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
-    for (int k = 0; k < R; ++k) mn_fma4(acc, sR[k], mn_ld4(x + (int64_t)k * D + 4 * d4));
-    mn_st4(sS + 4 * d4, acc);
+    for (int k = 0; k < R; ++k) mn_fma4(acc, sR[k], ld4(x + (int64_t)k * D + 4 * d4));
+    st4(sS + 4 * d4, acc);
   }
   __syncthreads();
 }
@@ -147,8 +132,8 @@ __global__ __launch_bounds__(MN_THREADS) void miner_cos_fwd_kernel(const float* 
   mn_cos_rowsum(x, R, D, eps, sS, sR, sumsq);
   float ss = 0.f;
   for (int d = threadIdx.x; d < D; d += MN_THREADS) ss += sS[d] * sS[d];
-  const float total = mn_block_sum(ss, red);
-  const float diag = mn_block_sum(sumsq, red);
+  const float total = block_sum<MN_WAVES>(ss, red);
+  const float diag = block_sum<MN_WAVES>(sumsq, red);
   if (threadIdx.x == 0) partial[blockIdx.x] = total - diag;
 }
 
@@ -168,9 +153,9 @@ __global__ __launch_bounds__(MN_THREADS) void miner_cos_bwd_kernel(const float* 
   for (int k = wave; k < R; k += MN_WAVES) {
     float sx = 0.f, xx = 0.f;
     for (int d4 = lane; d4 < D4; d4 += 64) {
-      const float4 v = mn_ld4(x + (int64_t)k * D + 4 * d4);
-      sx += mn_dot4(v, mn_ld4(sS + 4 * d4));
-      xx += mn_dot4(v, v);
+      const float4 v = ld4(x + (int64_t)k * D + 4 * d4);
+      sx += dot4(v, ld4(sS + 4 * d4));
+      xx += dot4(v, v);
     }
     sx = wave_sum(sx);
     xx = wave_sum(xx);
@@ -179,13 +164,13 @@ __global__ __launch_bounds__(MN_THREADS) void miner_cos_bwd_kernel(const float* 
     const float vx = 2.f * (sx - r * xx);                       // v_k . x_k, v_k = 2 (S - xh_k)
     const float coef = nrm > 0.f ? vx * r * r / nrm : 0.f;      // (the norm's subgradient at 0 is 0, as in autograd)
     for (int d4 = lane; d4 < D4; d4 += 64) {
-      const float4 v = mn_ld4(x + (int64_t)k * D + 4 * d4), s = mn_ld4(sS + 4 * d4);
+      const float4 v = ld4(x + (int64_t)k * D + 4 * d4), s = ld4(sS + 4 * d4);
       float4 o;
       o.x = c * (2.f * (s.x - v.x * r) * r - v.x * coef);
       o.y = c * (2.f * (s.y - v.y * r) * r - v.y * coef);
       o.z = c * (2.f * (s.z - v.z * r) * r - v.z * coef);
       o.w = c * (2.f * (s.w - v.w * r) * r - v.w * coef);
-      mn_st4(dx + (int64_t)k * D + 4 * d4, o);
+      st4(dx + (int64_t)k * D + 4 * d4, o);
     }
   }
 }
@@ -217,8 +202,8 @@ __global__ __launch_bounds__(MN_THREADS) void miner_cb_cand_kernel(const float* 
   for (int64_t c = c0 + wave; c < c1; c += MN_WAVES) {
     float acc = 0.f;
     for (int d4 = lane; d4 < D4; d4 += 64) {
-      const float4 v = mn_ld4(cc + c * Dc + 4 * d4);
-      acc += mn_dot4(v, v);
+      const float4 v = ld4(cc + c * Dc + 4 * d4);
+      acc += dot4(v, v);
     }
     acc = wave_sum(acc);
     if (lane == 0) rn_c[c] = 1.f / sqrtf(acc);           // no epsilon (torchmetrics' cosine): a zero row gives NaN there too
@@ -226,8 +211,8 @@ __global__ __launch_bounds__(MN_THREADS) void miner_cb_cand_kernel(const float* 
   __syncthreads();
   for (int d4 = threadIdx.x; d4 < D4; d4 += MN_THREADS) {
     float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
-    for (int64_t c = c0; c < c1; ++c) mn_fma4(acc, rn_c[c], mn_ld4(cc + c * Dc + 4 * d4));
-    mn_st4(s_own + (int64_t)b * Dc + 4 * d4, acc);
+    for (int64_t c = c0; c < c1; ++c) mn_fma4(acc, rn_c[c], ld4(cc + c * Dc + 4 * d4));
+    st4(s_own + (int64_t)b * Dc + 4 * d4, acc);
   }
 }
 
@@ -243,9 +228,9 @@ __global__ __launch_bounds__(MN_THREADS) void miner_cb_hist_kernel(const float* 
   const float* so = s_own + batch_hist[t] * Dc;
   float ss = 0.f, dv = 0.f;
   for (int d4 = lane; d4 < D4; d4 += 64) {
-    const float4 h = mn_ld4(hc + t * Dc + 4 * d4);
-    ss += mn_dot4(h, h);
-    dv += mn_dot4(h, mn_sub4(mn_ld4(s_all + 4 * d4), mn_ld4(so + 4 * d4)));
+    const float4 h = ld4(hc + t * Dc + 4 * d4);
+    ss += dot4(h, h);
+    dv += dot4(h, mn_sub4(ld4(s_all + 4 * d4), ld4(so + 4 * d4)));
   }
   ss = wave_sum(ss);
   dv = wave_sum(dv);
@@ -264,10 +249,10 @@ __global__ __launch_bounds__(MN_THREADS) void miner_cb_bwd_hist_kernel(
   const int b = blockIdx.x, D4 = Dc >> 2;
   const int64_t t0 = hist_off[b], t1 = hist_off[b + 1];
   for (int d4 = threadIdx.x; d4 < D4; d4 += MN_THREADS) {
-    const float4 V = mn_sub4(mn_ld4(s_all + 4 * d4), mn_ld4(s_own + (int64_t)b * Dc + 4 * d4));
+    const float4 V = mn_sub4(ld4(s_all + 4 * d4), ld4(s_own + (int64_t)b * Dc + 4 * d4));
     float4 q = make_float4(0.f, 0.f, 0.f, 0.f);
     for (int64_t t = t0; t < t1; ++t) {
-      const float4 h = mn_ld4(hc + t * Dc + 4 * d4);
+      const float4 h = ld4(hc + t * Dc + 4 * d4);
       const float rn = rn_h[t], g = d_bias[t] * inv_n, hd = d_bias[t] * bias[t] * rn;      // hd: (hh . d_hh) / |h|
       mn_fma4(q, g * rn, h);
       float4 dh;
@@ -275,9 +260,9 @@ __global__ __launch_bounds__(MN_THREADS) void miner_cb_bwd_hist_kernel(
       dh.y = rn * (g * V.y - h.y * hd);
       dh.z = rn * (g * V.z - h.z * hd);
       dh.w = rn * (g * V.w - h.w * hd);
-      mn_st4(d_hc + t * Dc + 4 * d4, dh);
+      st4(d_hc + t * Dc + 4 * d4, dh);
     }
-    mn_st4(q_own + (int64_t)b * Dc + 4 * d4, q);
+    st4(q_own + (int64_t)b * Dc + 4 * d4, q);
   }
 }
 
@@ -295,16 +280,16 @@ __global__ __launch_bounds__(MN_THREADS) void miner_cb_bwd_cand_kernel(const flo
   const float rn = rn_c[c];
   float cd = 0.f;
   for (int d4 = lane; d4 < D4; d4 += 64)
-    cd += mn_dot4(mn_ld4(cc + c * Dc + 4 * d4), mn_sub4(mn_ld4(q_all + 4 * d4), mn_ld4(qo + 4 * d4)));
+    cd += dot4(ld4(cc + c * Dc + 4 * d4), mn_sub4(ld4(q_all + 4 * d4), ld4(qo + 4 * d4)));
   cd = wave_sum(cd) * rn * rn;                                                            // (ch . d_ch) / |c|
   for (int d4 = lane; d4 < D4; d4 += 64) {
-    const float4 v = mn_ld4(cc + c * Dc + 4 * d4), q = mn_sub4(mn_ld4(q_all + 4 * d4), mn_ld4(qo + 4 * d4));
+    const float4 v = ld4(cc + c * Dc + 4 * d4), q = mn_sub4(ld4(q_all + 4 * d4), ld4(qo + 4 * d4));
     float4 d;
     d.x = rn * (q.x - v.x * cd);
     d.y = rn * (q.y - v.y * cd);
     d.z = rn * (q.z - v.z * cd);
     d.w = rn * (q.w - v.w * cd);
-    mn_st4(d_cc + c * Dc + 4 * d4, d);
+    st4(d_cc + c * Dc + 4 * d4, d);
   }
 }
 
@@ -324,14 +309,14 @@ __global__ __launch_bounds__(MN_THREADS) void miner_poly_fwd_kernel(
   const int n = min((int)(hist_off[b + 1] - r0), Hs);
   const float* Eb = E + r0 * D;
   if (tile_in_lds)
-    for (int i = threadIdx.x; i < n * D4; i += MN_THREADS) mn_st4(sE + 4 * i, mn_ld4(Eb + 4 * (int64_t)i));
+    for (int i = threadIdx.x; i < n * D4; i += MN_THREADS) st4(sE + 4 * i, ld4(Eb + 4 * (int64_t)i));
   // logits[k][t] = P[t] . codes[k] + bias[t]
   for (int idx = threadIdx.x; idx < K * n; idx += MN_THREADS) {
     const int k = idx / n, t = idx - k * n;
     const float* p = P + (r0 + t) * Cd;
     const float* q = codes + (int64_t)k * Cd;
     float acc = 0.f;
-    for (int c4 = 0; c4 < C4; ++c4) acc += mn_dot4(mn_ld4(p + 4 * c4), mn_ld4(q + 4 * c4));
+    for (int c4 = 0; c4 < C4; ++c4) acc += dot4(ld4(p + 4 * c4), ld4(q + 4 * c4));
     sA[k * Hs + t] = acc + (bias ? bias[r0 + t] : 0.f);
   }
   __syncthreads();
@@ -357,8 +342,8 @@ __global__ __launch_bounds__(MN_THREADS) void miner_poly_fwd_kernel(
   for (int idx = threadIdx.x; idx < K * D4; idx += MN_THREADS) {
     const int k = idx / D4, d4 = idx - k * D4;
     float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
-    for (int t = 0; t < n; ++t) mn_fma4(acc, sA[k * Hs + t], mn_ld4(Et + (int64_t)t * D + 4 * d4));
-    mn_st4(uv + ((int64_t)b * K + k) * D + 4 * d4, acc);
+    for (int t = 0; t < n; ++t) mn_fma4(acc, sA[k * Hs + t], ld4(Et + (int64_t)t * D + 4 * d4));
+    st4(uv + ((int64_t)b * K + k) * D + 4 * d4, acc);
   }
 }
 
@@ -380,7 +365,7 @@ __global__ __launch_bounds__(MN_THREADS) void miner_poly_bwd_kernel(
     const float* e = E + (r0 + t) * D;
     const float* g = du + (int64_t)k * D;
     float acc = 0.f;
-    for (int d4 = 0; d4 < D4; ++d4) acc += mn_dot4(mn_ld4(e + 4 * d4), mn_ld4(g + 4 * d4));
+    for (int d4 = 0; d4 < D4; ++d4) acc += dot4(ld4(e + 4 * d4), ld4(g + 4 * d4));
     sL[k * Hs + t] = acc;                                          // d_A[k][t]; 0 at the padded rows (zero embeddings)
   }
   __syncthreads();
@@ -400,20 +385,20 @@ __global__ __launch_bounds__(MN_THREADS) void miner_poly_bwd_kernel(
   for (int idx = threadIdx.x; idx < n * D4; idx += MN_THREADS) {
     const int t = idx / D4, d4 = idx - t * D4;
     float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
-    for (int k = 0; k < K; ++k) mn_fma4(acc, sA[k * Hs + t], mn_ld4(du + (int64_t)k * D + 4 * d4));
-    mn_st4(d_E + (r0 + t) * D + 4 * d4, acc);
+    for (int k = 0; k < K; ++k) mn_fma4(acc, sA[k * Hs + t], ld4(du + (int64_t)k * D + 4 * d4));
+    st4(d_E + (r0 + t) * D + 4 * d4, acc);
   }
   for (int idx = threadIdx.x; idx < n * C4; idx += MN_THREADS) {
     const int t = idx / C4, c4 = idx - t * C4;
     float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
-    for (int k = 0; k < K; ++k) mn_fma4(acc, sL[k * Hs + t], mn_ld4(codes + (int64_t)k * Cd + 4 * c4));
-    mn_st4(d_P + (r0 + t) * Cd + 4 * c4, acc);
+    for (int k = 0; k < K; ++k) mn_fma4(acc, sL[k * Hs + t], ld4(codes + (int64_t)k * Cd + 4 * c4));
+    st4(d_P + (r0 + t) * Cd + 4 * c4, acc);
   }
   for (int idx = threadIdx.x; idx < K * C4; idx += MN_THREADS) {
     const int k = idx / C4, c4 = idx - k * C4;
     float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
-    for (int t = 0; t < n; ++t) mn_fma4(acc, sL[k * Hs + t], mn_ld4(P + (r0 + t) * Cd + 4 * c4));
-    mn_st4(slab + ((int64_t)b * K + k) * Cd + 4 * c4, acc);
+    for (int t = 0; t < n; ++t) mn_fma4(acc, sL[k * Hs + t], ld4(P + (r0 + t) * Cd + 4 * c4));
+    st4(slab + ((int64_t)b * K + k) * Cd + 4 * c4, acc);
   }
 }
 
@@ -449,7 +434,7 @@ __global__ __launch_bounds__(MN_THREADS) void miner_score_fwd_kernel(
     const int j = j0 + wave;
     __syncthreads();
     if (j < nc)
-      for (int d4 = lane; d4 < D4; d4 += 64) mn_st4(myC + 4 * d4, mn_ld4(cand + (c0 + j) * D + 4 * d4));
+      for (int d4 = lane; d4 < D4; d4 += 64) st4(myC + 4 * d4, ld4(cand + (c0 + j) * D + 4 * d4));
     __syncthreads();
     if (j >= nc) continue;
     float s[4] = {0.f, 0.f, 0.f, 0.f}, t[4] = {0.f, 0.f, 0.f, 0.f};
@@ -566,34 +551,34 @@ __global__ __launch_bounds__(MN_THREADS) void miner_score_bwd_kernel(
       const int j = idx / D4, d4 = idx - j * D4;
       float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
       for (int k = 0; k < K; ++k) {
-        mn_fma4(acc, sdS[j * K + k], mn_ld4(ub + (int64_t)k * D + 4 * d4));
-        if (mode == 2) mn_fma4(acc, sdT[j * K + k], mn_ld4(gb + (int64_t)k * D + 4 * d4));
+        mn_fma4(acc, sdS[j * K + k], ld4(ub + (int64_t)k * D + 4 * d4));
+        if (mode == 2) mn_fma4(acc, sdT[j * K + k], ld4(gb + (int64_t)k * D + 4 * d4));
       }
-      mn_st4(d_cand + (c0 + j0 + j) * D + 4 * d4, acc);
+      st4(d_cand + (c0 + j0 + j) * D + 4 * d4, acc);
     }
     const bool last = tile == tiles - 1;
     for (int idx = threadIdx.x; idx < K * D4; idx += MN_THREADS) {
       const int k = idx / D4, d4 = idx - k * D4;
       float4 au = make_float4(0.f, 0.f, 0.f, 0.f), az = au;
       if (tile > 0) {
-        au = mn_ld4(dub + (int64_t)k * D + 4 * d4);
-        if (mode == 2) az = mn_ld4(dzb + (int64_t)k * D + 4 * d4);
+        au = ld4(dub + (int64_t)k * D + 4 * d4);
+        if (mode == 2) az = ld4(dzb + (int64_t)k * D + 4 * d4);
       }
       for (int j = 0; j < ct; ++j) {
-        const float4 c = mn_ld4(cand + (c0 + j0 + j) * D + 4 * d4);
+        const float4 c = ld4(cand + (c0 + j0 + j) * D + 4 * d4);
         mn_fma4(au, sdS[j * K + k], c);
         if (mode == 2) mn_fma4(az, sdT[j * K + k], c);
       }
-      mn_st4(dub + (int64_t)k * D + 4 * d4, au);
+      st4(dub + (int64_t)k * D + 4 * d4, au);
       if (mode == 2) {
         if (last) {
-          const float4 z = mn_ld4(Z + ((int64_t)b * K + k) * D + 4 * d4);
+          const float4 z = ld4(Z + ((int64_t)b * K + k) * D + 4 * d4);
           az.x *= mn_gelu_grad(z.x);
           az.y *= mn_gelu_grad(z.y);
           az.z *= mn_gelu_grad(z.z);
           az.w *= mn_gelu_grad(z.w);
         }
-        mn_st4(dzb + (int64_t)k * D + 4 * d4, az);
+        st4(dzb + (int64_t)k * D + 4 * d4, az);
       }
     }
   }

@@ -27,9 +27,6 @@ constexpr float SD_EPS = 1e-8f;      // senti_debias_module.py:212,223,235
 
 // floats of one discriminator slab: O * Hd (d_W2) | O (d_b2), padded to 4 so that every wave's bins stay 16-byte aligned
 __host__ __device__ __forceinline__ int sd_disc_width(int Hd, int O) { return (O * Hd + O + 3) & ~3; }
-__device__ __forceinline__ float4 sd_ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
-__device__ __forceinline__ void sd_st4(float* p, float4 v) { *reinterpret_cast<float4*>(p) = v; }
-__device__ __forceinline__ float sd_dot4(float4 a, float4 b) { return a.x * b.x + a.y * b.y + a.z * b.z + a.w * b.w; }
 
 // the per-wave bins of a workgroup added in wave order into its slab
 __device__ __forceinline__ void sd_bins_to_slab(const float* bins, int n, float* __restrict__ slab) {
@@ -75,10 +72,10 @@ struct SdCos {
 __device__ __forceinline__ SdCos sd_cos_terms(const float* __restrict__ a, const float* __restrict__ b, int D4, int lane) {
   SdCos c = {0.f, 0.f, 0.f};
   for (int d4 = lane; d4 < D4; d4 += 64) {
-    const float4 x = sd_ld4(a + 4 * d4), y = sd_ld4(b + 4 * d4);
-    c.dot += sd_dot4(x, y);
-    c.aa += sd_dot4(x, x);
-    c.bb += sd_dot4(y, y);
+    const float4 x = ld4(a + 4 * d4), y = ld4(b + 4 * d4);
+    c.dot += dot4(x, y);
+    c.aa += dot4(x, x);
+    c.bb += dot4(y, y);
   }
   c.dot = wave_sum(c.dot);
   c.aa = wave_sum(c.aa);
@@ -131,17 +128,17 @@ __global__ __launch_bounds__(SD_THREADS) void sd_rowcos_bwd_kernel(const float* 
     const float qb = nb > 0.f ? g * c.dot * na / (nb * den * den) : 0.f;
     float* wb = bins + wave * SDn + (ok ? id : 0) * D;
     for (int d4 = lane; d4 < D4; d4 += 64) {
-      const float4 x = sd_ld4(a + 4 * d4), y = sd_ld4(b + 4 * d4);
+      const float4 x = ld4(a + 4 * d4), y = ld4(b + 4 * d4);
       if (d_news != nullptr)
-        sd_st4(d_news + r * D + 4 * d4,
+        st4(d_news + r * D + 4 * d4,
                make_float4(lin * y.x - qa * x.x, lin * y.y - qa * x.y, lin * y.z - qa * x.z, lin * y.w - qa * x.w));
       if (slab != nullptr && ok) {
-        float4 t = sd_ld4(wb + 4 * d4);
+        float4 t = ld4(wb + 4 * d4);
         t.x += lin * x.x - qb * y.x;
         t.y += lin * x.y - qb * y.y;
         t.z += lin * x.z - qb * y.z;
         t.w += lin * x.w - qb * y.w;
-        sd_st4(wb + 4 * d4, t);
+        st4(wb + 4 * d4, t);
       }
     }
   }
@@ -162,7 +159,7 @@ __global__ __launch_bounds__(SD_THREADS) void sd_hist_fwd_kernel(const int64_t* 
     if (h < n && o + h < n_ids) id = ids[o + h];
     const bool ok = id >= 0 && id < S;
     for (int d4 = lane; d4 < D4; d4 += 64)
-      sd_st4(out + s * D + 4 * d4, ok ? sd_ld4(T + id * D + 4 * d4) : make_float4(0.f, 0.f, 0.f, 0.f));
+      st4(out + s * D + 4 * d4, ok ? ld4(T + id * D + 4 * d4) : make_float4(0.f, 0.f, 0.f, 0.f));
   }
 }
 
@@ -184,13 +181,13 @@ __global__ __launch_bounds__(SD_THREADS) void sd_hist_bwd_kernel(const float* __
     if (id < 0 || id >= S) continue;
     float* wb = bins + wave * SDn + id * D;
     for (int d4 = lane; d4 < D4; d4 += 64) {
-      const float4 g = sd_ld4(d_out + s * D + 4 * d4);
-      float4 t = sd_ld4(wb + 4 * d4);
+      const float4 g = ld4(d_out + s * D + 4 * d4);
+      float4 t = ld4(wb + 4 * d4);
       t.x += g.x;
       t.y += g.y;
       t.z += g.z;
       t.w += g.w;
-      sd_st4(wb + 4 * d4, t);
+      st4(wb + 4 * d4, t);
     }
   }
   sd_bins_to_slab(bins, SDn, slab + (int64_t)blockIdx.x * SDn);
@@ -223,13 +220,13 @@ __global__ __launch_bounds__(SD_THREADS) void sd_late_fwd_kernel(const int64_t* 
 #pragma unroll
     for (int c = 0; c < SD_MAXC; ++c)
       if (c < S) {
-        const float4 t = sd_ld4(T + c * D + 4 * d4);
+        const float4 t = ld4(T + c * D + 4 * d4);
         acc.x += cnt[c] * t.x;
         acc.y += cnt[c] * t.y;
         acc.z += cnt[c] * t.z;
         acc.w += cnt[c] * t.w;
       }
-    sd_st4(u + b * D + 4 * d4, acc);
+    st4(u + b * D + 4 * d4, acc);
   }
 }
 
@@ -243,13 +240,13 @@ __global__ void sd_bt_matmul_kernel(const float* __restrict__ W, const float* __
   float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
   for (int64_t b = 0; b < B; ++b) {
     const float w = W[b * S + s];
-    const float4 x = sd_ld4(X + b * D + 4 * d4);
+    const float4 x = ld4(X + b * D + 4 * d4);
     acc.x += w * x.x;
     acc.y += w * x.y;
     acc.z += w * x.z;
     acc.w += w * x.w;
   }
-  sd_st4(out + (int64_t)s * D + 4 * d4, acc);
+  st4(out + (int64_t)s * D + 4 * d4, acc);
 }
 
 // ---- bias-aware scores (one wave per user) -----------------------------------------------------------------------------------
@@ -266,7 +263,7 @@ __global__ __launch_bounds__(SD_THREADS) void sd_scores_fwd_kernel(const float* 
   for (int c = 0; c < SD_MAXC; ++c) {
     float acc = 0.f;
     if (c < S)
-      for (int d4 = lane; d4 < D4; d4 += 64) acc += sd_dot4(sd_ld4(u + b * D + 4 * d4), sd_ld4(T + c * D + 4 * d4));
+      for (int d4 = lane; d4 < D4; d4 += 64) acc += dot4(ld4(u + b * D + 4 * d4), ld4(T + c * D + 4 * d4));
     p[c] = wave_sum(acc);
     if (lane == 0 && c < S && P != nullptr) P[b * S + c] = p[c];
   }
@@ -310,13 +307,13 @@ __global__ __launch_bounds__(SD_THREADS) void sd_scores_bwd_kernel(const float* 
 #pragma unroll
     for (int c = 0; c < SD_MAXC; ++c)
       if (c < S) {
-        const float4 t = sd_ld4(T + c * D + 4 * d4);
+        const float4 t = ld4(T + c * D + 4 * d4);
         g.x += acc[c] * t.x;
         g.y += acc[c] * t.y;
         g.z += acc[c] * t.z;
         g.w += acc[c] * t.w;
       }
-    sd_st4(d_u + b * D + 4 * d4, g);
+    st4(d_u + b * D + 4 * d4, g);
   }
 }
 
@@ -336,7 +333,7 @@ __device__ __forceinline__ SdLogits sd_logits(const float* __restrict__ h, const
   for (int o = 0; o < SD_MAXC; ++o) {
     float acc = 0.f;
     if (o < O)
-      for (int d4 = lane; d4 < Hd4; d4 += 64) acc += sd_dot4(sd_ld4(h + 4 * d4), sd_ld4(W2 + o * Hd + 4 * d4));
+      for (int d4 = lane; d4 < Hd4; d4 += 64) acc += dot4(ld4(h + 4 * d4), ld4(W2 + o * Hd + 4 * d4));
     acc = wave_sum(acc);
     r.l[o] = o < O ? acc + b2[o] : -INFINITY;
     mx = fmaxf(mx, r.l[o]);
@@ -393,26 +390,26 @@ __global__ __launch_bounds__(SD_THREADS) void sd_disc_tail_bwd_kernel(const floa
 #pragma unroll
     for (int o = 0; o < SD_MAXC; ++o) dl[o] = o < O ? gr * (expf(g.l[o] - g.lse) - (o == g.target ? 1.f : 0.f)) : 0.f;
     for (int d4 = lane; d4 < Hd4; d4 += 64) {
-      const float4 x = sd_ld4(h + 4 * d4);
+      const float4 x = ld4(h + 4 * d4);
       float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
 #pragma unroll
       for (int o = 0; o < SD_MAXC; ++o)
         if (o < O) {
-          const float4 w = sd_ld4(W2 + o * Hd + 4 * d4);
+          const float4 w = ld4(W2 + o * Hd + 4 * d4);
           acc.x += dl[o] * w.x;
           acc.y += dl[o] * w.y;
           acc.z += dl[o] * w.z;
           acc.w += dl[o] * w.w;
           if (slab != nullptr) {
-            float4 t = sd_ld4(wb + o * Hd + 4 * d4);
+            float4 t = ld4(wb + o * Hd + 4 * d4);
             t.x += dl[o] * x.x;
             t.y += dl[o] * x.y;
             t.z += dl[o] * x.z;
             t.w += dl[o] * x.w;
-            sd_st4(wb + o * Hd + 4 * d4, t);
+            st4(wb + o * Hd + 4 * d4, t);
           }
         }
-      sd_st4(d_pre + r * Hd + 4 * d4, make_float4(acc.x * (1.f - x.x * x.x), acc.y * (1.f - x.y * x.y),
+      st4(d_pre + r * Hd + 4 * d4, make_float4(acc.x * (1.f - x.x * x.x), acc.y * (1.f - x.y * x.y),
                                                   acc.z * (1.f - x.z * x.z), acc.w * (1.f - x.w * x.w)));
     }
     if (slab != nullptr && lane == 0) {

@@ -15,8 +15,11 @@
 //         memory) clears the bits of excluded rows that fall inside this tile, the user's list is loaded into registers (entry p in
 //         lane p & 63) and the survivors are inserted one by one with ballots and lane shifts.  The top k of a set under a strict
 //         total order does not depend on the insertion order, so the result is a pure function of the score bits and the rows.
+//   tki_scores_kernel  the same stages over the K interest rows of a user, with an aggregation between the tile and the scan.
 //   tk_merge_kernel    one wave per user: validates the user's offsets and exclusion indices (status flags), merges the `slices`
 //       partial lists with the same insertion and writes (row, score) or (-1, -inf).
+// The stages (exclusion cache, eligibility, tile product, per-user selection, flush) are written once, as inlined device functions
+// of pointers and counts; a scores kernel owns its LDS layout and its wave-to-user mapping and calls them.
 // No float atomics, no allocation, no host read-back; the workspace holds the partial lists, O(B * slices * k).
 #include <math.h>
 
@@ -36,8 +39,17 @@ constexpr int TK_SCLD = TK_BV + 4;             // score tile: 4 rows apart = 16 
 constexpr int TK_XCAP = 64;                    // exclusion entries per user cached in LDS
 constexpr int TK_USERS_PER_WAVE = TK_BU / 4;
 constexpr int TK_TARGET_BLOCKS = 512;          // two resident workgroups on each of the 256 CUs
+
+// dynamic LDS of a scores kernel: `tiles` score tiles (2 with a gate), and per user of the workgroup a list of k entries and the
+// exclusion cache (start, length, TK_XCAP rows); then the eligibility bytes.  64 users, one tile: 50 KB + 512 B per k, so two
+// workgroups per CU up to k = 60 and more than 64 KB from k = 29 on.
+constexpr size_t tk_lds_bytes(int tiles, int users, int k) {
+  return (size_t)tiles * TK_BU * TK_SCLD * 4 + (size_t)users * k * 8 + (size_t)users * 8 + (size_t)users * TK_XCAP * 4 + (size_t)users * 4 +
+         TK_BV;
+}
 static_assert(2 * TK_BK * (TK_LDA + TK_LDB) <= TK_BU * TK_SCLD, "the operand tiles live inside the score tile");
-constexpr size_t TK_LDS_FIXED = (size_t)(TK_BU * TK_SCLD + TK_BU * TK_XCAP) * 4 + TK_BU * 8 + TK_BU * 4 + TK_BV;
+static_assert(2 * TK_BK * (2 * TK_LDA + TK_LDB) <= 2 * TK_BU * TK_SCLD, "with a gate the three operand tiles live inside the two score tiles");
+static_assert(tk_lds_bytes(2, TK_BU, NRL_TOPK_MAX_K) <= 160 * 1024, "the largest layout fits the dynamic LDS the launch may request");
 
 struct TkArgs {
   const float* user;
@@ -54,18 +66,11 @@ struct TkArgs {
   int32_t* status;
 };
 
-// order-preserving key of a score (nrl_metrics.hip mt_key): a > b <=> key(a) > key(b), -0 == +0, NaN = 0xFFFFFFFF above +inf
-__device__ __forceinline__ uint32_t tk_key(float s) {
-  if (s != s) return 0xFFFFFFFFu;
-  if (s == 0.f) s = 0.f;
-  const uint32_t b = __float_as_uint(s);
-  return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
-__device__ __forceinline__ float tk_unkey(uint32_t key) {
+__device__ __forceinline__ float tk_unkey(uint32_t key) {      // the score of a score_key
   return __uint_as_float((key & 0x80000000u) ? (key ^ 0x80000000u) : ~key);
 }
 __device__ __forceinline__ unsigned long long tk_entry(float s, uint32_t v) {
-  return ((unsigned long long)tk_key(s) << 32) | (uint32_t)~v;
+  return ((unsigned long long)score_key(s) << 32) | (uint32_t)~v;
 }
 
 __device__ __forceinline__ unsigned long long tk_shfl(unsigned long long x, int src) {
@@ -119,12 +124,6 @@ struct TkList {
   }
 };
 
-__device__ __forceinline__ void tk_wave_sync() {        // one wave: LDS operations complete in order, the compiler must keep it
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
 // a user's exclusion range: false when the offsets decrease or leave [0, excl_off[B]]
 __device__ __forceinline__ bool tk_excl_range(const TkArgs& A, int64_t u, int64_t& s, int64_t& n) {
   s = 0;
@@ -137,190 +136,236 @@ __device__ __forceinline__ bool tk_excl_range(const TkArgs& A, int64_t u, int64_
   return true;
 }
 
-__global__ __launch_bounds__(TK_THREADS) void tk_scores_kernel(TkArgs A) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char tk_smem[];
-  float* const sc = reinterpret_cast<float*>(tk_smem);                       // [TK_BU][TK_SCLD]; before the scores exist it holds
-  float* const As = sc;                                                      // [2][TK_BK][TK_LDA] and
-  float* const Bs = As + 2 * TK_BK * TK_LDA;                                 // [2][TK_BK][TK_LDB], the operand tiles
-  int32_t* const xl = reinterpret_cast<int32_t*>(sc + TK_BU * TK_SCLD);      // [TK_BU][TK_XCAP] cached exclusion rows (-1: none)
-  int64_t* const xs = reinterpret_cast<int64_t*>(xl + TK_BU * TK_XCAP);      // [TK_BU] start of the user's exclusion list
-  int32_t* const xn = reinterpret_cast<int32_t*>(xs + TK_BU);                // [TK_BU] its length (0: none, or bad offsets)
-  uint8_t* const el = reinterpret_cast<uint8_t*>(xn + TK_BU);                // [TK_BV] column inside V and eligible
-  unsigned long long* const lists = reinterpret_cast<unsigned long long*>(el + TK_BV);      // [TK_BU][k]
-
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int wm = wave >> 1, wn = wave & 1;
-  const int l15 = lane & 15, g = lane >> 4;
-  const int k = A.k, D = A.D, V = A.V;
-  // the slice is the fast index: the workgroups resident together share their table slice across the user tiles
-  const int sl = (int)(blockIdx.x % (unsigned)A.slices);
-  const int64_t u0 = (int64_t)(blockIdx.x / (unsigned)A.slices) * TK_BU;
-  const int v_begin = sl * A.tiles_per_slice * TK_BV;                        // < V < 2^31
-  const int64_t v_stop = (int64_t)v_begin + (int64_t)A.tiles_per_slice * TK_BV;
-  const int v_end = v_stop < V ? (int)v_stop : V;
-  const int nvt = (v_end - v_begin + TK_BV - 1) / TK_BV;
-  const int nkt = (D + TK_BK - 1) / TK_BK;
-
-  for (int i = tid; i < TK_BU * k; i += TK_THREADS) lists[i] = 0ull;
-  if (tid < TK_BU) {
+// ---- the stages of a scores kernel ---------------------------------------------------------------------------------------------
+// Exclusion cache of a tile of `slots` users of which the first `nu`, from user u0 on, exist: xs[slots] the start of the user's
+// exclusion list, xn[slots] its length (0: none, or bad offsets), xl[slots][TK_XCAP] its first rows (-1: none, or outside V).
+__device__ __forceinline__ void tk_cache_exclusions(const TkArgs& A, int64_t u0, int nu, int slots, int64_t* xs, int32_t* xn,
+                                                    int32_t* xl) {
+  const int tid = threadIdx.x;
+  if (tid < slots) {
     int64_t s = 0, n = 0;
-    if (u0 + tid < A.B && !tk_excl_range(A, u0 + tid, s, n)) n = 0;         // the merge kernel flags and blanks such a user
+    if (tid < nu && !tk_excl_range(A, u0 + tid, s, n)) n = 0;                // the merge kernel flags and blanks such a user
     xs[tid] = s;
     xn[tid] = (int32_t)(n < 0x7FFFFFFF ? n : 0x7FFFFFFF);
   }
   __syncthreads();
-  for (int i = tid; i < TK_BU * TK_XCAP; i += TK_THREADS) {
+  for (int i = tid; i < slots * TK_XCAP; i += TK_THREADS) {
     const int ul = i / TK_XCAP, j = i % TK_XCAP;
     int32_t x = -1;
     if (j < xn[ul]) {
       const int64_t r = A.excl_idx[xs[ul] + j];
-      if (r >= 0 && r < V) x = (int32_t)r;
+      if (r >= 0 && r < A.V) x = (int32_t)r;
     }
     xl[i] = x;
   }
+}
 
-  // staging assignment: one float4 of the user tile and two of the table tile per thread and k-tile
+// el[TK_BV]: column v0 + c of the table tile is inside V and eligible
+__device__ __forceinline__ void tk_fill_eligible(const uint8_t* eligible, int v0, int V, uint8_t* el) {
+  const int tid = threadIdx.x;
+  if (tid < TK_BV) {
+    const int64_t v = (int64_t)v0 + tid;
+    el[tid] = (v < V && (!eligible || eligible[v])) ? 1 : 0;
+  }
+}
+
+// The 64 x 128 products of NA row operands (pa[a]: this thread's staging row, tid >> 2, of operand a; zero when !ua_ok) with table
+// rows v0 ... v0 + 127, into NA score tiles [TK_BU][TK_SCLD] from `sc` on.  Until the scores exist the same LDS holds the operand
+// tiles, NA x [2][TK_BK][TK_LDA] and then [2][TK_BK][TK_LDB], all staged against ONE pass over the table tile.  Ends with the
+// tiles written and the workgroup synchronised.
+template <int NA>
+__device__ __forceinline__ void tk_tile_product(const float* const (&pa)[NA], bool ua_ok, const float* table, int v0, int V, int D,
+                                                float* sc) {
+  float* const As = sc;
+  float* const Bs = As + NA * 2 * TK_BK * TK_LDA;
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int wm = wave >> 1, wn = wave & 1;
+  const int l15 = lane & 15, g = lane >> 4;
+  // staging assignment: one float4 of every row-operand tile and two of the table tile per thread and k-tile
   const int srow = tid >> 2, skc = (tid & 3) * 4;
-  const int64_t ua = u0 + srow < A.B ? u0 + srow : A.B - 1;
-  const bool ua_ok = u0 + srow < A.B;
-  const float* const pa = A.user + ua * D;
+  const int nkt = (D + TK_BK - 1) / TK_BK;
+  const float* pb[2];
+  bool vb_ok[2];
+#pragma unroll
+  for (int c = 0; c < 2; ++c) {
+    const int64_t v = (int64_t)v0 + srow + c * 64;
+    vb_ok[c] = v < V;
+    pb[c] = table + (int64_t)(vb_ok[c] ? v : V - 1) * D;
+  }
+  float4 ra[NA], rb[2];
+  auto load_tiles = [&](int k0) {                    // unconditional loads from clamped addresses; masked when staged
+    const int kk = k0 + skc < D ? k0 + skc : D - 4;
+#pragma unroll
+    for (int a = 0; a < NA; ++a) ra[a] = ld4(pa[a] + kk);
+#pragma unroll
+    for (int c = 0; c < 2; ++c) rb[c] = ld4(pb[c] + kk);
+  };
+  auto store_tiles = [&](int buf, int k0) {
+    const bool kok = k0 + skc < D;
+    const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+    for (int a = 0; a < NA; ++a) {
+      float* as = As + (2 * a + buf) * TK_BK * TK_LDA;
+      const float4 x = (kok && ua_ok) ? ra[a] : z;
+      as[(skc + 0) * TK_LDA + srow] = x.x;
+      as[(skc + 1) * TK_LDA + srow] = x.y;
+      as[(skc + 2) * TK_LDA + srow] = x.z;
+      as[(skc + 3) * TK_LDA + srow] = x.w;
+    }
+    float* bs = Bs + buf * TK_BK * TK_LDB;
+#pragma unroll
+    for (int c = 0; c < 2; ++c) {
+      const float4 b = (kok && vb_ok[c]) ? rb[c] : z;
+      const int row = srow + c * 64;
+      bs[(skc + 0) * TK_LDB + row] = b.x;
+      bs[(skc + 1) * TK_LDB + row] = b.y;
+      bs[(skc + 2) * TK_LDB + row] = b.z;
+      bs[(skc + 3) * TK_LDB + row] = b.w;
+    }
+  };
+
+  tk_f32x4 acc[NA][2][4];
+#pragma unroll
+  for (int a = 0; a < NA; ++a)
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+      for (int j = 0; j < 4; ++j) acc[a][i][j] = tk_f32x4{0.f, 0.f, 0.f, 0.f};
+
+  load_tiles(0);
+  store_tiles(0, 0);
+  __syncthreads();
+  for (int kt = 0; kt < nkt; ++kt) {
+    const int buf = kt & 1;
+    if (kt + 1 < nkt) load_tiles((kt + 1) * TK_BK);
+    const float* bs = Bs + buf * TK_BK * TK_LDB + wn * 64 + l15;
+#pragma unroll
+    for (int ks = 0; ks < TK_BK / 4; ++ks) {
+      float x[NA][2], b[4];
+#pragma unroll
+      for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int a = 0; a < NA; ++a) x[a][i] = As[(2 * a + buf) * TK_BK * TK_LDA + wm * 32 + l15 + (4 * ks + g) * TK_LDA + i * 16];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) b[j] = bs[(4 * ks + g) * TK_LDB + j * 16];
+#pragma unroll
+      for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+#pragma unroll
+          for (int a = 0; a < NA; ++a) acc[a][i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(x[a][i], b[j], acc[a][i][j], 0, 0, 0);
+    }
+    if (kt + 1 < nkt) store_tiles(buf ^ 1, (kt + 1) * TK_BK);
+    __syncthreads();
+  }
+
+  // accumulators -> score tiles: the lane holds tile row 4g + r, column l15 of every 16 x 16 block
+#pragma unroll
+  for (int i = 0; i < 2; ++i)
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+#pragma unroll
+      for (int r = 0; r < 4; ++r)
+#pragma unroll
+        for (int a = 0; a < NA; ++a)
+          sc[a * TK_BU * TK_SCLD + (wm * 32 + i * 16 + 4 * g + r) * TK_SCLD + wn * 64 + j * 16 + l15] = acc[a][i][j][r];
+  __syncthreads();
+}
+
+// One user against one table tile, by one wave: `row` the user's 128 scores, L its list of k entries, xn / xs / xl its entries of
+// the exclusion cache, e_0 / e_1 the lane's eligibility of columns lane and 64 + lane.
+__device__ __forceinline__ void tk_select_user(const float* row, unsigned long long* L, const int32_t* xn, const int64_t* xs,
+                                               const int32_t* xl, const int64_t* excl_idx, int v0, bool e_0, bool e_1, int k, int lane,
+                                               bool& nan) {
+  const unsigned long long thr = L[k - 1];
+  const unsigned long long c0 = e_0 ? tk_entry(row[lane], (uint32_t)v0 + lane) : 0ull;
+  const unsigned long long c1 = e_1 ? tk_entry(row[64 + lane], (uint32_t)v0 + 64 + lane) : 0ull;
+  unsigned long long m0 = __ballot(c0 > thr), m1 = __ballot(c1 > thr);
+  if (!(m0 | m1)) return;
+  const int n = *xn;
+  for (int base = 0; base < n; base += 64) {         // excluded rows inside this tile lose their bit
+    const int i = base + lane;
+    int64_t x = -1;
+    if (i < n) x = i < TK_XCAP ? (int64_t)xl[i] : excl_idx[*xs + i];
+    const int64_t rel64 = x - v0;
+    const bool inr = x >= 0 && rel64 >= 0 && rel64 < TK_BV;
+    const int rel = inr ? (int)rel64 : 0;
+    unsigned long long hit = __ballot(inr);
+    while (hit) {
+      const int b = __ffsll((long long)hit) - 1;
+      hit &= hit - 1;
+      const int r = __shfl(rel, b, 64);
+      if (r < 64)
+        m0 &= ~(1ull << r);
+      else
+        m1 &= ~(1ull << (r - 64));
+    }
+  }
+  if (!(m0 | m1)) return;
+  TkList S;
+  S.e0 = lane < k ? L[lane] : 0ull;
+  S.e1 = lane + 64 < k ? L[lane + 64] : 0ull;
+  bool changed = S.take(c0, m0, k, lane, nan);
+  changed |= S.take(c1, m1 & __ballot(c1 > S.kth(k)), k, lane, nan);
+  if (changed) {
+    if (lane < k) L[lane] = S.e0;
+    if (lane + 64 < k) L[lane + 64] = S.e1;
+    wave_lds_sync();
+  }
+}
+
+// a user's k entries, by the wave that owns them, to its slot of `partial`
+__device__ __forceinline__ void tk_flush_user(const unsigned long long* L, unsigned long long* P, int k, int lane) {
+  for (int p = lane; p < k; p += 64) P[p] = L[p];
+}
+
+__global__ __launch_bounds__(TK_THREADS) void tk_scores_kernel(TkArgs A) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char tk_smem[];
+  float* const sc = reinterpret_cast<float*>(tk_smem);                       // [TK_BU][TK_SCLD]
+  int32_t* const xl = reinterpret_cast<int32_t*>(sc + TK_BU * TK_SCLD);      // [TK_BU][TK_XCAP]
+  int64_t* const xs = reinterpret_cast<int64_t*>(xl + TK_BU * TK_XCAP);      // [TK_BU]
+  int32_t* const xn = reinterpret_cast<int32_t*>(xs + TK_BU);                // [TK_BU]
+  uint8_t* const el = reinterpret_cast<uint8_t*>(xn + TK_BU);                // [TK_BV]
+  unsigned long long* const lists = reinterpret_cast<unsigned long long*>(el + TK_BV);      // [TK_BU][k]
+
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int k = A.k, V = A.V;
+  // the slice is the fast index: the workgroups resident together share their table slice across the user tiles
+  const int sl = (int)(blockIdx.x % (unsigned)A.slices);
+  const int64_t u0 = (int64_t)(blockIdx.x / (unsigned)A.slices) * TK_BU;
+  const int nu = A.B - u0 < TK_BU ? (int)(A.B - u0) : TK_BU;                 // the tile's users (>= 1)
+  const int v_begin = sl * A.tiles_per_slice * TK_BV;                        // < V < 2^31
+  const int64_t v_stop = (int64_t)v_begin + (int64_t)A.tiles_per_slice * TK_BV;
+  const int v_end = v_stop < V ? (int)v_stop : V;
+  const int nvt = (v_end - v_begin + TK_BV - 1) / TK_BV;
+
+  for (int i = tid; i < TK_BU * k; i += TK_THREADS) lists[i] = 0ull;
+  tk_cache_exclusions(A, u0, nu, TK_BU, xs, xn, xl);
+
+  // wave w owns users 16 w ... 16 w + 15 of the tile and their lists
+  const int ul_begin = wave * TK_USERS_PER_WAVE, ul_end = ul_begin + TK_USERS_PER_WAVE < nu ? ul_begin + TK_USERS_PER_WAVE : nu;
+  // staging: tile row r is user u0 + r, zero past the last user
+  const int srow = tid >> 2;
+  const bool ua_ok = srow < nu;
+  const float* const pa[1] = {A.user + (ua_ok ? u0 + srow : A.B - 1) * A.D};
   bool nan = false;
 
   for (int vt = 0; vt < nvt; ++vt) {
     const int v0 = v_begin + vt * TK_BV;
-    const float* pb[2];
-    bool vb_ok[2];
-#pragma unroll
-    for (int c = 0; c < 2; ++c) {
-      const int64_t v = (int64_t)v0 + srow + c * 64;
-      vb_ok[c] = v < V;
-      pb[c] = A.table + (int64_t)(vb_ok[c] ? v : V - 1) * D;
-    }
-    if (tid < TK_BV) {
-      const int64_t v = (int64_t)v0 + tid;
-      el[tid] = (v < V && (!A.eligible || A.eligible[v])) ? 1 : 0;
-    }
-    float4 ra, rb[2];
-    auto load_tiles = [&](int k0) {                  // unconditional loads from clamped addresses; masked when staged
-      const int kk = k0 + skc < D ? k0 + skc : D - 4;
-      ra = *reinterpret_cast<const float4*>(pa + kk);
-#pragma unroll
-      for (int c = 0; c < 2; ++c) rb[c] = *reinterpret_cast<const float4*>(pb[c] + kk);
-    };
-    auto store_tiles = [&](int buf, int k0) {
-      const bool kok = k0 + skc < D;
-      float* as = As + buf * TK_BK * TK_LDA;
-      float* bs = Bs + buf * TK_BK * TK_LDB;
-      const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
-      const float4 a = (kok && ua_ok) ? ra : z;
-      as[(skc + 0) * TK_LDA + srow] = a.x;
-      as[(skc + 1) * TK_LDA + srow] = a.y;
-      as[(skc + 2) * TK_LDA + srow] = a.z;
-      as[(skc + 3) * TK_LDA + srow] = a.w;
-#pragma unroll
-      for (int c = 0; c < 2; ++c) {
-        const float4 b = (kok && vb_ok[c]) ? rb[c] : z;
-        const int row = srow + c * 64;
-        bs[(skc + 0) * TK_LDB + row] = b.x;
-        bs[(skc + 1) * TK_LDB + row] = b.y;
-        bs[(skc + 2) * TK_LDB + row] = b.z;
-        bs[(skc + 3) * TK_LDB + row] = b.w;
-      }
-    };
+    tk_fill_eligible(A.eligible, v0, V, el);
+    tk_tile_product<1>(pa, ua_ok, A.table, v0, V, A.D, sc);
 
-    tk_f32x4 acc[2][4];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-      for (int j = 0; j < 4; ++j) acc[i][j] = tk_f32x4{0.f, 0.f, 0.f, 0.f};
-
-    load_tiles(0);
-    store_tiles(0, 0);
-    __syncthreads();
-    for (int kt = 0; kt < nkt; ++kt) {
-      const int buf = kt & 1;
-      if (kt + 1 < nkt) load_tiles((kt + 1) * TK_BK);
-      const float* as = As + buf * TK_BK * TK_LDA + wm * 32 + l15;
-      const float* bs = Bs + buf * TK_BK * TK_LDB + wn * 64 + l15;
-#pragma unroll
-      for (int ks = 0; ks < TK_BK / 4; ++ks) {
-        float a[2], b[4];
-#pragma unroll
-        for (int i = 0; i < 2; ++i) a[i] = as[(4 * ks + g) * TK_LDA + i * 16];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) b[j] = bs[(4 * ks + g) * TK_LDB + j * 16];
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-          for (int j = 0; j < 4; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[i], b[j], acc[i][j], 0, 0, 0);
-      }
-      if (kt + 1 < nkt) store_tiles(buf ^ 1, (kt + 1) * TK_BK);
-      __syncthreads();
-    }
-
-    // accumulators -> score tile: the lane holds user 4g + r, column l15 of every 16 x 16 block
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-      for (int j = 0; j < 4; ++j)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) sc[(wm * 32 + i * 16 + 4 * g + r) * TK_SCLD + wn * 64 + j * 16 + l15] = acc[i][j][r];
-    __syncthreads();
-
-    // selection: wave w owns users 16 w ... 16 w + 15 of the tile and their lists
     const bool e_0 = el[lane] != 0, e_1 = el[64 + lane] != 0;
-    for (int uu = 0; uu < TK_USERS_PER_WAVE; ++uu) {
-      const int ul = wave * TK_USERS_PER_WAVE + uu;
-      if (u0 + ul >= A.B) break;
-      unsigned long long* L = lists + ul * k;
-      const unsigned long long thr = L[k - 1];
-      const unsigned long long c0 = e_0 ? tk_entry(sc[ul * TK_SCLD + lane], (uint32_t)v0 + lane) : 0ull;
-      const unsigned long long c1 = e_1 ? tk_entry(sc[ul * TK_SCLD + 64 + lane], (uint32_t)v0 + 64 + lane) : 0ull;
-      unsigned long long m0 = __ballot(c0 > thr), m1 = __ballot(c1 > thr);
-      if (!(m0 | m1)) continue;
-      const int n = xn[ul];
-      for (int base = 0; base < n; base += 64) {       // excluded rows inside this tile lose their bit
-        const int i = base + lane;
-        int64_t x = -1;
-        if (i < n) x = i < TK_XCAP ? (int64_t)xl[ul * TK_XCAP + i] : A.excl_idx[xs[ul] + i];
-        const int64_t rel64 = x - v0;
-        const bool inr = x >= 0 && rel64 >= 0 && rel64 < TK_BV;
-        const int rel = inr ? (int)rel64 : 0;
-        unsigned long long hit = __ballot(inr);
-        while (hit) {
-          const int b = __ffsll((long long)hit) - 1;
-          hit &= hit - 1;
-          const int r = __shfl(rel, b, 64);
-          if (r < 64)
-            m0 &= ~(1ull << r);
-          else
-            m1 &= ~(1ull << (r - 64));
-        }
-      }
-      if (!(m0 | m1)) continue;
-      TkList S;
-      S.e0 = lane < k ? L[lane] : 0ull;
-      S.e1 = lane + 64 < k ? L[lane + 64] : 0ull;
-      bool changed = S.take(c0, m0, k, lane, nan);
-      changed |= S.take(c1, m1 & __ballot(c1 > S.kth(k)), k, lane, nan);
-      if (changed) {
-        if (lane < k) L[lane] = S.e0;
-        if (lane + 64 < k) L[lane + 64] = S.e1;
-        tk_wave_sync();
-      }
-    }
+    for (int ul = ul_begin; ul < ul_end; ++ul)
+      tk_select_user(sc + ul * TK_SCLD, lists + ul * k, xn + ul, xs + ul, xl + ul * TK_XCAP, A.excl_idx, v0, e_0, e_1, k, lane, nan);
     __syncthreads();                                  // the score tile and `el` are free for the next tile's operands
   }
 
   if (nan && lane == 0) atomicOr(A.status, NRL_TOPK_E_NAN);
-  tk_wave_sync();
-  for (int uu = 0; uu < TK_USERS_PER_WAVE; ++uu) {
-    const int ul = wave * TK_USERS_PER_WAVE + uu;
-    if (u0 + ul >= A.B) break;
-    unsigned long long* P = A.partial + ((u0 + ul) * A.slices + sl) * k;
-    for (int p = lane; p < k; p += 64) P[p] = lists[ul * k + p];
-  }
+  wave_lds_sync();
+  for (int ul = ul_begin; ul < ul_end; ++ul) tk_flush_user(lists + ul * k, A.partial + ((u0 + ul) * A.slices + sl) * k, k, lane);
 }
 
 // one wave per user: status flags, merge of the user's partial lists, output
@@ -358,22 +403,15 @@ __global__ __launch_bounds__(64) void tk_merge_kernel(TkArgs A) {
 
 // ---- multi-interest scores (MINER) ---------------------------------------------------------------------------------------------
 // A user is K interest rows; a table row's score is an aggregate of the K dot products (ops_miner.SCORE_MODES: 0 max, 1 mean,
-// 2 softmax-weighted by the K gate logits).  tki_scores_kernel is tk_scores_kernel with the (B * K, D) interest rows as the A
-// operand: the 64 rows of a workgroup hold Ut = 64 / K whole users (rows from Ut * K on are zero and belong to nobody), and once
-// the 64 x 128 tile of s_j is in LDS the K rows of every user are reduced per column, in ascending j, into the user's first row.
-// From there the scan, the exclusion and the insertion are those of tk_scores_kernel over Ut users, and tk_merge_kernel finishes.
-// GATE (mode 2) runs the gate rows as a second A operand against the SAME staged table tile into a second score tile.
+// 2 softmax-weighted by the K gate logits).  The row operand of the tile product is the (B * K, D) interest matrix: the 64 rows of
+// a workgroup hold Ut = 64 / K whole users (rows from Ut * K on are zero and belong to nobody), and once the 64 x 128 tile of s_j
+// is in LDS the K rows of every user are reduced per column, in ascending j, into the user's first row: the one stage that is
+// this kernel's own.  The scan, the exclusion and the insertion then run over Ut users, and tk_merge_kernel finishes.
+// GATE (mode 2) runs the gate rows as a second row operand against the SAME staged table tile into a second score tile.
 struct TkiArgs : TkArgs {                      // `user` is the interests; B counts users
   const float* gate;
   int32_t K, Ut, mode;
 };
-
-constexpr size_t tki_lds_bytes(bool gate, int Ut, int k) {
-  return (size_t)(gate ? 2 : 1) * TK_BU * TK_SCLD * 4 + (size_t)Ut * k * 8 + (size_t)Ut * 8 + (size_t)Ut * TK_XCAP * 4 + (size_t)Ut * 4 +
-         TK_BV;
-}
-static_assert(2 * TK_BK * (2 * TK_LDA + TK_LDB) <= 2 * TK_BU * TK_SCLD, "with a gate the three operand tiles live inside the two score tiles");
-static_assert(tki_lds_bytes(true, TK_BU, NRL_TOPK_MAX_K) <= 160 * 1024, "the largest layout fits the dynamic LDS the launch may request");
 
 // the aggregate of one user's K scores of one column (stride TK_SCLD apart); lg: the gate logits of the same positions
 template <bool GATE>
@@ -407,23 +445,19 @@ __device__ __forceinline__ float tki_aggregate(const float* s, const float* lg, 
 template <bool GATE>
 __global__ __launch_bounds__(TK_THREADS) void tki_scores_kernel(TkiArgs A) {
   extern __shared__ __attribute__((aligned(16))) unsigned char tk_smem[];
+  constexpr int NA = GATE ? 2 : 1;
   const int K = A.K, Ut = A.Ut;
   float* const sc = reinterpret_cast<float*>(tk_smem);                       // [TK_BU][TK_SCLD] the s_j; with a gate
-  float* const lg = sc + TK_BU * TK_SCLD;                                    // [TK_BU][TK_SCLD] the l_j follow.  Before they exist:
-  float* const As = sc;                                                      // [2][TK_BK][TK_LDA] interest rows,
-  float* const Gs = As + 2 * TK_BK * TK_LDA;                                 // [2][TK_BK][TK_LDA] gate rows (GATE only) and
-  float* const Bs = Gs + (GATE ? 2 * TK_BK * TK_LDA : 0);                    // [2][TK_BK][TK_LDB] table rows
-  unsigned long long* const lists = reinterpret_cast<unsigned long long*>(sc + (GATE ? 2 : 1) * TK_BU * TK_SCLD);      // [Ut][k]
-  int64_t* const xs = reinterpret_cast<int64_t*>(lists + Ut * A.k);          // [Ut] start of the user's exclusion list
-  int32_t* const xl = reinterpret_cast<int32_t*>(xs + Ut);                   // [Ut][TK_XCAP] cached exclusion rows (-1: none)
-  int32_t* const xn = xl + Ut * TK_XCAP;                                     // [Ut] its length (0: none, or bad offsets)
-  uint8_t* const el = reinterpret_cast<uint8_t*>(xn + Ut);                   // [TK_BV] column inside V and eligible
+  float* const lg = sc + TK_BU * TK_SCLD;                                    // [TK_BU][TK_SCLD] the l_j follow
+  unsigned long long* const lists = reinterpret_cast<unsigned long long*>(sc + NA * TK_BU * TK_SCLD);      // [Ut][k]
+  int64_t* const xs = reinterpret_cast<int64_t*>(lists + Ut * A.k);          // [Ut]
+  int32_t* const xl = reinterpret_cast<int32_t*>(xs + Ut);                   // [Ut][TK_XCAP]
+  int32_t* const xn = xl + Ut * TK_XCAP;                                     // [Ut]
+  uint8_t* const el = reinterpret_cast<uint8_t*>(xn + Ut);                   // [TK_BV]
 
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int wm = wave >> 1, wn = wave & 1;
-  const int l15 = lane & 15, g = lane >> 4;
-  const int k = A.k, D = A.D, V = A.V;
+  const int k = A.k, V = A.V;
   const int sl = (int)(blockIdx.x % (unsigned)A.slices);
   const int64_t u0 = (int64_t)(blockIdx.x / (unsigned)A.slices) * Ut;        // first user of the tile
   const int nu = A.B - u0 < Ut ? (int)(A.B - u0) : Ut;                       // its users (>= 1)
@@ -431,137 +465,23 @@ __global__ __launch_bounds__(TK_THREADS) void tki_scores_kernel(TkiArgs A) {
   const int64_t v_stop = (int64_t)v_begin + (int64_t)A.tiles_per_slice * TK_BV;
   const int v_end = v_stop < V ? (int)v_stop : V;
   const int nvt = (v_end - v_begin + TK_BV - 1) / TK_BV;
-  const int nkt = (D + TK_BK - 1) / TK_BK;
 
   for (int i = tid; i < Ut * k; i += TK_THREADS) lists[i] = 0ull;
-  if (tid < Ut) {
-    int64_t s = 0, n = 0;
-    if (tid < nu && !tk_excl_range(A, u0 + tid, s, n)) n = 0;                // the merge kernel flags and blanks such a user
-    xs[tid] = s;
-    xn[tid] = (int32_t)(n < 0x7FFFFFFF ? n : 0x7FFFFFFF);
-  }
-  __syncthreads();
-  for (int i = tid; i < Ut * TK_XCAP; i += TK_THREADS) {
-    const int ul = i / TK_XCAP, j = i % TK_XCAP;
-    int32_t x = -1;
-    if (j < xn[ul]) {
-      const int64_t r = A.excl_idx[xs[ul] + j];
-      if (r >= 0 && r < V) x = (int32_t)r;
-    }
-    xl[i] = x;
-  }
+  tk_cache_exclusions(A, u0, nu, Ut, xs, xn, xl);
 
   // staging: tile row r is interest row u0 * K + r of the (B * K, D) matrix while r < nu * K, zero from there on
-  const int srow = tid >> 2, skc = (tid & 3) * 4;
+  const int srow = tid >> 2;
   const bool ua_ok = srow < nu * K;
   const int64_t ua = ua_ok ? u0 * K + srow : 0;
-  const float* const pa = A.user + ua * D;
-  const float* const pg = GATE ? A.gate + ua * D : nullptr;
+  const float* pa[NA];
+  pa[0] = A.user + ua * A.D;
+  if constexpr (GATE) pa[1] = A.gate + ua * A.D;
   bool nan = false;
 
   for (int vt = 0; vt < nvt; ++vt) {
     const int v0 = v_begin + vt * TK_BV;
-    const float* pb[2];
-    bool vb_ok[2];
-#pragma unroll
-    for (int c = 0; c < 2; ++c) {
-      const int64_t v = (int64_t)v0 + srow + c * 64;
-      vb_ok[c] = v < V;
-      pb[c] = A.table + (int64_t)(vb_ok[c] ? v : V - 1) * D;
-    }
-    if (tid < TK_BV) {
-      const int64_t v = (int64_t)v0 + tid;
-      el[tid] = (v < V && (!A.eligible || A.eligible[v])) ? 1 : 0;
-    }
-    float4 ra, rg, rb[2];
-    auto load_tiles = [&](int k0) {                  // unconditional loads from clamped addresses; masked when staged
-      const int kk = k0 + skc < D ? k0 + skc : D - 4;
-      ra = *reinterpret_cast<const float4*>(pa + kk);
-      if constexpr (GATE) rg = *reinterpret_cast<const float4*>(pg + kk);
-#pragma unroll
-      for (int c = 0; c < 2; ++c) rb[c] = *reinterpret_cast<const float4*>(pb[c] + kk);
-    };
-    auto store_tiles = [&](int buf, int k0) {
-      const bool kok = k0 + skc < D;
-      float* as = As + buf * TK_BK * TK_LDA;
-      float* bs = Bs + buf * TK_BK * TK_LDB;
-      const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
-      const float4 a = (kok && ua_ok) ? ra : z;
-      as[(skc + 0) * TK_LDA + srow] = a.x;
-      as[(skc + 1) * TK_LDA + srow] = a.y;
-      as[(skc + 2) * TK_LDA + srow] = a.z;
-      as[(skc + 3) * TK_LDA + srow] = a.w;
-      if constexpr (GATE) {
-        float* gs = Gs + buf * TK_BK * TK_LDA;
-        const float4 q = (kok && ua_ok) ? rg : z;
-        gs[(skc + 0) * TK_LDA + srow] = q.x;
-        gs[(skc + 1) * TK_LDA + srow] = q.y;
-        gs[(skc + 2) * TK_LDA + srow] = q.z;
-        gs[(skc + 3) * TK_LDA + srow] = q.w;
-      }
-#pragma unroll
-      for (int c = 0; c < 2; ++c) {
-        const float4 b = (kok && vb_ok[c]) ? rb[c] : z;
-        const int row = srow + c * 64;
-        bs[(skc + 0) * TK_LDB + row] = b.x;
-        bs[(skc + 1) * TK_LDB + row] = b.y;
-        bs[(skc + 2) * TK_LDB + row] = b.z;
-        bs[(skc + 3) * TK_LDB + row] = b.w;
-      }
-    };
-
-    tk_f32x4 acc[2][4], gac[2][4];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        acc[i][j] = tk_f32x4{0.f, 0.f, 0.f, 0.f};
-        if constexpr (GATE) gac[i][j] = tk_f32x4{0.f, 0.f, 0.f, 0.f};
-      }
-
-    load_tiles(0);
-    store_tiles(0, 0);
-    __syncthreads();
-    for (int kt = 0; kt < nkt; ++kt) {
-      const int buf = kt & 1;
-      if (kt + 1 < nkt) load_tiles((kt + 1) * TK_BK);
-      const float* as = As + buf * TK_BK * TK_LDA + wm * 32 + l15;
-      const float* gs = Gs + buf * TK_BK * TK_LDA + wm * 32 + l15;
-      const float* bs = Bs + buf * TK_BK * TK_LDB + wn * 64 + l15;
-#pragma unroll
-      for (int ks = 0; ks < TK_BK / 4; ++ks) {
-        float a[2], q[2], b[4];
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-          a[i] = as[(4 * ks + g) * TK_LDA + i * 16];
-          if constexpr (GATE) q[i] = gs[(4 * ks + g) * TK_LDA + i * 16];
-        }
-#pragma unroll
-        for (int j = 0; j < 4; ++j) b[j] = bs[(4 * ks + g) * TK_LDB + j * 16];
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-          for (int j = 0; j < 4; ++j) {
-            acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[i], b[j], acc[i][j], 0, 0, 0);
-            if constexpr (GATE) gac[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(q[i], b[j], gac[i][j], 0, 0, 0);
-          }
-      }
-      if (kt + 1 < nkt) store_tiles(buf ^ 1, (kt + 1) * TK_BK);
-      __syncthreads();
-    }
-
-    // accumulators -> score tile(s): the lane holds tile row 4g + r, column l15 of every 16 x 16 block
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-      for (int j = 0; j < 4; ++j)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const int at = (wm * 32 + i * 16 + 4 * g + r) * TK_SCLD + wn * 64 + j * 16 + l15;
-          sc[at] = acc[i][j][r];
-          if constexpr (GATE) lg[at] = gac[i][j][r];
-        }
-    __syncthreads();
+    tk_fill_eligible(A.eligible, v0, V, el);
+    tk_tile_product<NA>(pa, ua_ok, A.table, v0, V, A.D, sc);
 
     // aggregation: the K rows of user ul, one column per thread, into the user's first row (nobody else reads or writes them)
     for (int i = tid; i < nu * TK_BV; i += TK_THREADS) {
@@ -572,65 +492,14 @@ __global__ __launch_bounds__(TK_THREADS) void tki_scores_kernel(TkiArgs A) {
 
     // selection: wave w owns users w, w + 4, ... of the tile and their lists
     const bool e_0 = el[lane] != 0, e_1 = el[64 + lane] != 0;
-    for (int ul = wave; ul < nu; ul += 4) {
-      const float* row = sc + ul * K * TK_SCLD;
-      unsigned long long* L = lists + ul * k;
-      const unsigned long long thr = L[k - 1];
-      const unsigned long long c0 = e_0 ? tk_entry(row[lane], (uint32_t)v0 + lane) : 0ull;
-      const unsigned long long c1 = e_1 ? tk_entry(row[64 + lane], (uint32_t)v0 + 64 + lane) : 0ull;
-      unsigned long long m0 = __ballot(c0 > thr), m1 = __ballot(c1 > thr);
-      if (!(m0 | m1)) continue;
-      const int n = xn[ul];
-      for (int base = 0; base < n; base += 64) {       // excluded rows inside this tile lose their bit
-        const int i = base + lane;
-        int64_t x = -1;
-        if (i < n) x = i < TK_XCAP ? (int64_t)xl[ul * TK_XCAP + i] : A.excl_idx[xs[ul] + i];
-        const int64_t rel64 = x - v0;
-        const bool inr = x >= 0 && rel64 >= 0 && rel64 < TK_BV;
-        const int rel = inr ? (int)rel64 : 0;
-        unsigned long long hit = __ballot(inr);
-        while (hit) {
-          const int b = __ffsll((long long)hit) - 1;
-          hit &= hit - 1;
-          const int r = __shfl(rel, b, 64);
-          if (r < 64)
-            m0 &= ~(1ull << r);
-          else
-            m1 &= ~(1ull << (r - 64));
-        }
-      }
-      if (!(m0 | m1)) continue;
-      TkList S;
-      S.e0 = lane < k ? L[lane] : 0ull;
-      S.e1 = lane + 64 < k ? L[lane + 64] : 0ull;
-      bool changed = S.take(c0, m0, k, lane, nan);
-      changed |= S.take(c1, m1 & __ballot(c1 > S.kth(k)), k, lane, nan);
-      if (changed) {
-        if (lane < k) L[lane] = S.e0;
-        if (lane + 64 < k) L[lane + 64] = S.e1;
-        tk_wave_sync();
-      }
-    }
+    for (int ul = wave; ul < nu; ul += 4)
+      tk_select_user(sc + ul * K * TK_SCLD, lists + ul * k, xn + ul, xs + ul, xl + ul * TK_XCAP, A.excl_idx, v0, e_0, e_1, k, lane, nan);
     __syncthreads();                                  // the score tiles and `el` are free for the next tile's operands
   }
 
   if (nan && lane == 0) atomicOr(A.status, NRL_TOPK_E_NAN);
-  tk_wave_sync();
-  for (int ul = wave; ul < nu; ul += 4) {
-    unsigned long long* P = A.partial + ((u0 + ul) * A.slices + sl) * k;
-    for (int p = lane; p < k; p += 64) P[p] = lists[ul * k + p];
-  }
-}
-
-template <bool GATE>
-static int tki_launch(const TkiArgs& A, int64_t blocks, hipStream_t st) {
-  const size_t smem = tki_lds_bytes(GATE, A.Ut, A.k);
-  // more than 64 KB of dynamic LDS needs the attribute; it belongs to the current device, so it is set per call
-  if (smem > 64 * 1024)
-    NRL_HIP(hipFuncSetAttribute((const void*)tki_scores_kernel<GATE>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-  tki_scores_kernel<GATE><<<(unsigned)blocks, TK_THREADS, smem, st>>>(A);
-  NRL_LAUNCH_CHECK();
-  return NRL_OK;
+  wave_lds_sync();
+  for (int ul = wave; ul < nu; ul += 4) tk_flush_user(lists + ul * k, A.partial + ((u0 + ul) * A.slices + sl) * k, k, lane);
 }
 
 static bool tk_shape_ok(int64_t B, int64_t V, int32_t D, int32_t k) {
@@ -647,6 +516,45 @@ static void tk_plan(int64_t B, int64_t V, int32_t slices, int64_t bu, int64_t& l
   lists = want;
   tiles_per_slice = nvt > 0 ? ceil_div(nvt, want) : 1;
   used = nvt > 0 ? ceil_div(nvt, tiles_per_slice) : 0;
+}
+
+// the checks both entries make, in this order; `who` is the entry's name in the message
+static int tk_check(const char* who, int64_t B, int64_t V, int32_t D, int32_t k, const int64_t* excl_idx, const int64_t* excl_off) {
+  NRL_REQUIRE(k >= 1 && k <= NRL_TOPK_MAX_K, "%s: k in [1, %d] (got %d)", who, NRL_TOPK_MAX_K, k);
+  NRL_REQUIRE(D > 0 && D % 4 == 0 && D <= NRL_TOPK_MAX_D, "%s: D a multiple of 4 in [4, %d] (got %d)", who, NRL_TOPK_MAX_D, D);
+  NRL_REQUIRE(V < ((int64_t)1 << 31), "%s: at most 2^31 - 1 table rows (got %lld)", who, (long long)V);
+  NRL_REQUIRE(B < ((int64_t)1 << 31), "%s: at most 2^31 - 1 users per call (got %lld)", who, (long long)B);
+  NRL_REQUIRE((excl_idx == nullptr) == (excl_off == nullptr) || excl_off, "%s: excl_idx without excl_off", who);
+  return NRL_OK;
+}
+
+// the arguments every kernel of the unit reads, in the order of TkArgs; the launcher sets the two slice fields
+static TkArgs tk_args(const float* user, const float* table, int64_t B, int64_t V, int32_t D, int32_t k, const int64_t* excl_idx,
+                      const int64_t* excl_off, const uint8_t* eligible, unsigned long long* partial, int64_t* out_idx,
+                      float* out_score, int32_t* status) {
+  return TkArgs{user, table, B, (int32_t)V, D, k, excl_idx, excl_off, eligible, 0, 0, partial, out_idx, out_score, status};
+}
+
+// plans the slices, runs `kernel` (`tiles` score tiles, `bu` users per workgroup) over them and then the merge
+template <class Args>
+static int tk_launch(const char* who, void (*kernel)(Args), Args& A, int32_t slices, int tiles, int bu, void* stream) {
+  int64_t lists, used, tps;
+  tk_plan(A.B, A.V, slices, bu, lists, used, tps);
+  const int64_t blocks = ceil_div(A.B, bu) * used;
+  NRL_REQUIRE(blocks < ((int64_t)1 << 31), "%s: grid too large (%lld workgroups)", who, (long long)blocks);
+  A.slices = (int32_t)used;
+  A.tiles_per_slice = (int32_t)tps;
+  hipStream_t st = (hipStream_t)stream;
+  if (used > 0) {
+    const size_t smem = tk_lds_bytes(tiles, bu, A.k);
+    // more than 64 KB of dynamic LDS needs the attribute; it belongs to the current device, so it is set per call
+    if (smem > 64 * 1024) NRL_HIP(hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    kernel<<<(unsigned)blocks, TK_THREADS, smem, st>>>(A);
+    NRL_LAUNCH_CHECK();
+  }
+  tk_merge_kernel<<<(unsigned)A.B, 64, 0, st>>>(static_cast<const TkArgs&>(A));
+  NRL_LAUNCH_CHECK();
+  return NRL_OK;
 }
 
 }  // namespace nrl
@@ -672,49 +580,14 @@ int nrl_topk_scores(const float* user_vec, const float* table, int64_t B, int64_
                     const int64_t* excl_off, const uint8_t* eligible, int32_t slices, int64_t* out_idx, float* out_score,
                     int32_t* status, void* ws, size_t ws_bytes, void* stream) {
   NRL_REQUIRE(B >= 0 && V >= 0 && D >= 0 && slices >= 0, "topk_scores: negative size");
-  NRL_REQUIRE(k >= 1 && k <= NRL_TOPK_MAX_K, "topk_scores: k in [1, %d] (got %d)", NRL_TOPK_MAX_K, k);
-  NRL_REQUIRE(D > 0 && D % 4 == 0 && D <= NRL_TOPK_MAX_D, "topk_scores: D a multiple of 4 in [4, %d] (got %d)", NRL_TOPK_MAX_D, D);
-  NRL_REQUIRE(V < ((int64_t)1 << 31), "topk_scores: at most 2^31 - 1 table rows (got %lld)", (long long)V);
-  NRL_REQUIRE(B < ((int64_t)1 << 31), "topk_scores: at most 2^31 - 1 users per call (got %lld)", (long long)B);
+  NRL_TRY(tk_check("topk_scores", B, V, D, k, excl_idx, excl_off));
   NRL_REQUIRE(status, "topk_scores: the status word is required");
-  NRL_REQUIRE((excl_idx == nullptr) == (excl_off == nullptr) || excl_off, "topk_scores: excl_idx without excl_off");
   if (B == 0) return NRL_OK;
   NRL_REQUIRE(out_idx && out_score && user_vec && (V == 0 || table), "topk_scores: null argument");
   unsigned long long* partial;
   NRL_TRY(carve_workspace(ws, ws_bytes, [&](Arena& a) { tk_layout(a, B, V, k, slices, TK_BU, &partial); }));
-  int64_t lists, used, tps;
-  tk_plan(B, V, slices, TK_BU, lists, used, tps);
-  const int64_t blocks = ceil_div(B, TK_BU) * used;
-  NRL_REQUIRE(blocks < ((int64_t)1 << 31), "topk_scores: grid too large (%lld workgroups)", (long long)blocks);
-
-  TkArgs A;
-  A.user = user_vec;
-  A.table = table;
-  A.B = B;
-  A.V = (int32_t)V;
-  A.D = D;
-  A.k = k;
-  A.excl_idx = excl_idx;
-  A.excl_off = excl_off;
-  A.eligible = eligible;
-  A.slices = (int32_t)used;
-  A.tiles_per_slice = (int32_t)tps;
-  A.partial = partial;
-  A.out_idx = out_idx;
-  A.out_score = out_score;
-  A.status = status;
-  hipStream_t st = (hipStream_t)stream;
-  if (used > 0) {
-    const size_t smem = TK_LDS_FIXED + (size_t)TK_BU * k * sizeof(unsigned long long);      // 50 KB + 512 B per k: two workgroups per CU up to k = 60
-    // more than 64 KB of dynamic LDS (k > 28) needs the attribute; it belongs to the current device, so it is set per call
-    if (smem > 64 * 1024)
-      NRL_HIP(hipFuncSetAttribute((const void*)tk_scores_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    tk_scores_kernel<<<(unsigned)blocks, TK_THREADS, smem, st>>>(A);
-    NRL_LAUNCH_CHECK();
-  }
-  tk_merge_kernel<<<(unsigned)B, 64, 0, st>>>(A);
-  NRL_LAUNCH_CHECK();
-  return NRL_OK;
+  TkArgs A = tk_args(user_vec, table, B, V, D, k, excl_idx, excl_off, eligible, partial, out_idx, out_score, status);
+  return tk_launch("topk_scores", tk_scores_kernel, A, slices, 1, TK_BU, stream);
 }
 
 int nrl_topk_interest_scores(const float* interests, const float* gate, const float* table, int64_t B, int32_t K, int64_t V, int32_t D,
@@ -725,11 +598,7 @@ int nrl_topk_interest_scores(const float* interests, const float* gate, const fl
   NRL_REQUIRE(K >= 1 && K <= NRL_TOPK_MAX_INTERESTS, "topk_interest_scores: K in [1, %d] (got %d)", NRL_TOPK_MAX_INTERESTS, K);
   NRL_REQUIRE(mode >= 0 && mode <= 2, "topk_interest_scores: mode 0 (max), 1 (mean) or 2 (weighted) (got %d)", mode);
   NRL_REQUIRE(mode != 2 || gate, "topk_interest_scores: mode 2 (weighted) needs the gate rows");
-  NRL_REQUIRE(k >= 1 && k <= NRL_TOPK_MAX_K, "topk_interest_scores: k in [1, %d] (got %d)", NRL_TOPK_MAX_K, k);
-  NRL_REQUIRE(D > 0 && D % 4 == 0 && D <= NRL_TOPK_MAX_D, "topk_interest_scores: D a multiple of 4 in [4, %d] (got %d)", NRL_TOPK_MAX_D, D);
-  NRL_REQUIRE(V < ((int64_t)1 << 31), "topk_interest_scores: at most 2^31 - 1 table rows (got %lld)", (long long)V);
-  NRL_REQUIRE(B < ((int64_t)1 << 31), "topk_interest_scores: at most 2^31 - 1 users per call (got %lld)", (long long)B);
-  NRL_REQUIRE((excl_idx == nullptr) == (excl_off == nullptr) || excl_off, "topk_interest_scores: excl_idx without excl_off");
+  NRL_TRY(tk_check("topk_interest_scores", B, V, D, k, excl_idx, excl_off));
   if (B == 0) return NRL_OK;
   // the lists of this entry's own plan: never more than nrl_topk_scores_workspace_bytes(B, V, D, k, slices) holds (Ut <= TK_BU)
   const int32_t Ut = TK_BU / K;
@@ -737,36 +606,14 @@ int nrl_topk_interest_scores(const float* interests, const float* gate, const fl
   NRL_TRY(carve_workspace(ws, ws_bytes, [&](Arena& a) { tk_layout(a, B, V, k, slices, Ut, &partial); }));
   NRL_REQUIRE(status, "topk_interest_scores: the status word is required");
   NRL_REQUIRE(out_idx && out_score && interests && (V == 0 || table), "topk_interest_scores: null argument");
-  int64_t lists, used, tps;
-  tk_plan(B, V, slices, Ut, lists, used, tps);
-  const int64_t blocks = ceil_div(B, Ut) * used;
-  NRL_REQUIRE(blocks < ((int64_t)1 << 31), "topk_interest_scores: grid too large (%lld workgroups)", (long long)blocks);
-
   TkiArgs A;
-  A.user = interests;
+  static_cast<TkArgs&>(A) = tk_args(interests, table, B, V, D, k, excl_idx, excl_off, eligible, partial, out_idx, out_score, status);
   A.gate = mode == 2 ? gate : nullptr;
-  A.table = table;
-  A.B = B;
-  A.V = (int32_t)V;
-  A.D = D;
-  A.k = k;
   A.K = K;
   A.Ut = Ut;
   A.mode = mode;
-  A.excl_idx = excl_idx;
-  A.excl_off = excl_off;
-  A.eligible = eligible;
-  A.slices = (int32_t)used;
-  A.tiles_per_slice = (int32_t)tps;
-  A.partial = partial;
-  A.out_idx = out_idx;
-  A.out_score = out_score;
-  A.status = status;
-  hipStream_t st = (hipStream_t)stream;
-  if (used > 0) NRL_TRY(mode == 2 ? tki_launch<true>(A, blocks, st) : tki_launch<false>(A, blocks, st));
-  tk_merge_kernel<<<(unsigned)B, 64, 0, st>>>(static_cast<const TkArgs&>(A));
-  NRL_LAUNCH_CHECK();
-  return NRL_OK;
+  return mode == 2 ? tk_launch("topk_interest_scores", tki_scores_kernel<true>, A, slices, 2, Ut, stream)
+                   : tk_launch("topk_interest_scores", tki_scores_kernel<false>, A, slices, 1, Ut, stream);
 }
 
 }  // extern "C"
