@@ -1067,6 +1067,46 @@ int nrl_topk_interest_scores(const float* interests, const float* gate, const fl
                              int32_t slices, int64_t* out_idx, float* out_score, int32_t* status, void* ws, size_t ws_bytes,
                              void* stream);
 
+/* nrl_topk_ensemble_scores: the same ranking by MANNeR's ensemble of standardised scores (manner_module.py:175-186 with the
+ *   candidate list replaced by the table).  T in [1, NRL_TOPK_MAX_MODELS] sub-models, each a user matrix users[t] (B, D) and a table
+ *   tables[t] (V, D), all of one shape, fp32, row-major, device, and a weight weights[t]; `users`, `tables` (T device pointers each)
+ *   and `weights` (T floats) are HOST arrays read during the call, as nrl_manner_scores takes its tables.
+ *   Population: P_u = { v in [0, V) : eligible[v] != 0 and v not on the exclusion list of u } -- the candidate list of a
+ *     full-catalogue recommendation is every row the user may be recommended.  The exclusion list counts as a set.
+ *   Raw score: s_t[u, v] = users[t][u] . tables[t][v], the bits of nrl_topk_scores.
+ *   Statistics: mu_t[u] the mean and sd_t[u] the UNBIASED standard deviation (divisor n - 1, as torch.std and nrl_manner_scores)
+ *     of s_t[u, v] over the v in P_u whose s_t is not NaN.  out_stats (B, T, 2) receives (mu, sd).
+ *   Score: z[u, v] = w_0 ((s_0 - mu_0) / sd_0) + w_1 (...) + w_2 (...), in ascending t, every operation rounded to fp32 on its own
+ *     (no contraction): a pure function of the raw-score bits and the user's statistics.  No epsilon is added anywhere.
+ *   Ranking: the k rows of P_u of largest z, descending, equal z by ascending row, -1 / -inf where fewer rows qualify; D, k, V, B,
+ *     excl_idx / excl_off, eligible, slices, out_idx / out_score as for nrl_topk_scores.
+ *   status: NRL_TOPK_E_EXCLUDE and NRL_TOPK_E_OFFSETS as for nrl_topk_scores.  A NaN raw score of a row of P_u sets NRL_TOPK_E_NAN,
+ *     stays out of that table's statistics (its n is smaller) and the row is left out for that user.  NRL_TOPK_E_STATS: some
+ *     sd_t[u] is zero, NaN, infinite or undefined (fewer than two usable scores): that user's row is all -1 / -inf and the other
+ *     users are untouched -- where nrl_manner_scores returns NaN or inf this entry refuses the user and says so.
+ *   Invariance: the statistics are reduced in an order planned from V alone.  With nvt = ceil(V / 128) table tiles, a chunk is
+ *     ceil(nvt / NRL_TOPK_STAT_CHUNKS) consecutive tiles (at most NRL_TOPK_STAT_CHUNKS chunks, none empty).  Per tile: the masked
+ *     count, the sum by the fixed wave reduction, the tile mean, then M2 = sum (s - mean)^2 in a second pass.  Tiles are folded into
+ *     the chunk's (n, mean, M2) in ascending order by the pairwise update d = mean_b - mean_a, mean = mean_a + d n_b / n,
+ *     M2 = M2_a + M2_b + d d n_a n_b / n (an empty side is skipped), and the chunks in ascending order the same way.  So the bits
+ *     of mu, sd and of every returned score and row depend on the user's T rows, the tables, eligible, the exclusion set and V
+ *     alone: not on B, the user's position in the batch, k, slices, the grid, the GEMM engine setting or the run.  Neither a (B, V)
+ *     matrix nor anything of that order is written.  No floating-point atomics, no allocation, no host synchronisation.
+ *   moments: caller-provided device scratch of B * NRL_TOPK_STAT_CHUNKS * T * 3 floats (the chunks' n, mean, M2), overwritten.
+ *   Workspace: there is no size function of its own: the partial lists are those of nrl_topk_scores, so
+ *     nrl_topk_scores_workspace_bytes(B, V, D, k, slices) is exactly this entry's requirement; a shorter buffer is refused with
+ *     NRL_E_WORKSPACE before any launch.  B == 0 returns success without a launch; V == 0 gives NRL_TOPK_E_STATS and -1 / -inf.
+ *     T or sizes outside the limits and a null users[t], tables[t], out_stats, moments or status return NRL_E_INVALID. */
+#define NRL_TOPK_E_STATS 8 /* a user's scores of some table cannot be standardised: that user's row is all -1 / -inf */
+#define NRL_TOPK_MAX_MODELS 3
+#define NRL_TOPK_STAT_CHUNKS 64
+int nrl_topk_ensemble_scores(const float* const* users, const float* const* tables, const float* weights, int32_t T,
+                             int64_t B, int64_t V, int32_t D, int32_t k, const int64_t* excl_idx, const int64_t* excl_off,
+                             const uint8_t* eligible, int32_t slices, int64_t* out_idx, float* out_score,
+                             float* out_stats /* (B, T, 2): mean, sd */,
+                             float* moments   /* (B, NRL_TOPK_STAT_CHUNKS, T, 3) caller-provided scratch */,
+                             int32_t* status, void* ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

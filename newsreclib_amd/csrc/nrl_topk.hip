@@ -16,6 +16,8 @@
 //         lane p & 63) and the survivors are inserted one by one with ballots and lane shifts.  The top k of a set under a strict
 //         total order does not depend on the insertion order, so the result is a pure function of the score bits and the rows.
 //   tki_scores_kernel  the same stages over the K interest rows of a user, with an aggregation between the tile and the scan.
+//   tke_*_kernel       the z-scored ensemble of up to three tables (MANNeR): a statistics pass, then the same stages over a second
+//       score tile that collects the weighted z-scores.
 //   tk_merge_kernel    one wave per user: validates the user's offsets and exclusion indices (status flags), merges the `slices`
 //       partial lists with the same insertion and writes (row, score) or (-1, -inf).
 // The stages (exclusion cache, eligibility, tile product, per-user selection, flush) are written once, as inlined device functions
@@ -49,7 +51,9 @@ constexpr size_t tk_lds_bytes(int tiles, int users, int k) {
 }
 static_assert(2 * TK_BK * (TK_LDA + TK_LDB) <= TK_BU * TK_SCLD, "the operand tiles live inside the score tile");
 static_assert(2 * TK_BK * (2 * TK_LDA + TK_LDB) <= 2 * TK_BU * TK_SCLD, "with a gate the three operand tiles live inside the two score tiles");
-static_assert(tk_lds_bytes(2, TK_BU, NRL_TOPK_MAX_K) <= 160 * 1024, "the largest layout fits the dynamic LDS the launch may request");
+constexpr size_t TKE_STATS_LDS = (size_t)TK_BU * NRL_TOPK_MAX_MODELS * 2 * 4;      // the ensemble kernel's (mean, sd) per user and table
+static_assert(tk_lds_bytes(2, TK_BU, NRL_TOPK_MAX_K) + TKE_STATS_LDS <= 160 * 1024,
+              "the largest layout fits the dynamic LDS the launch may request");
 
 struct TkArgs {
   const float* user;
@@ -273,16 +277,10 @@ __device__ __forceinline__ void tk_tile_product(const float* const (&pa)[NA], bo
   __syncthreads();
 }
 
-// One user against one table tile, by one wave: `row` the user's 128 scores, L its list of k entries, xn / xs / xl its entries of
-// the exclusion cache, e_0 / e_1 the lane's eligibility of columns lane and 64 + lane.
-__device__ __forceinline__ void tk_select_user(const float* row, unsigned long long* L, const int32_t* xn, const int64_t* xs,
-                                               const int32_t* xl, const int64_t* excl_idx, int v0, bool e_0, bool e_1, int k, int lane,
-                                               bool& nan) {
-  const unsigned long long thr = L[k - 1];
-  const unsigned long long c0 = e_0 ? tk_entry(row[lane], (uint32_t)v0 + lane) : 0ull;
-  const unsigned long long c1 = e_1 ? tk_entry(row[64 + lane], (uint32_t)v0 + 64 + lane) : 0ull;
-  unsigned long long m0 = __ballot(c0 > thr), m1 = __ballot(c1 > thr);
-  if (!(m0 | m1)) return;
+// The bits of m0 (columns 0 ... 63 of the table tile at v0) and m1 (64 ... 127) of the rows on one user's exclusion list are cleared,
+// by one wave: xn / xs / xl the user's entries of the exclusion cache, longer lists read on from global memory.
+__device__ __forceinline__ void tk_clear_excluded(const int32_t* xn, const int64_t* xs, const int32_t* xl, const int64_t* excl_idx,
+                                                  int v0, int lane, unsigned long long& m0, unsigned long long& m1) {
   const int n = *xn;
   for (int base = 0; base < n; base += 64) {         // excluded rows inside this tile lose their bit
     const int i = base + lane;
@@ -302,6 +300,19 @@ __device__ __forceinline__ void tk_select_user(const float* row, unsigned long l
         m1 &= ~(1ull << (r - 64));
     }
   }
+}
+
+// One user against one table tile, by one wave: `row` the user's 128 scores, L its list of k entries, xn / xs / xl its entries of
+// the exclusion cache, e_0 / e_1 the lane's eligibility of columns lane and 64 + lane.
+__device__ __forceinline__ void tk_select_user(const float* row, unsigned long long* L, const int32_t* xn, const int64_t* xs,
+                                               const int32_t* xl, const int64_t* excl_idx, int v0, bool e_0, bool e_1, int k, int lane,
+                                               bool& nan) {
+  const unsigned long long thr = L[k - 1];
+  const unsigned long long c0 = e_0 ? tk_entry(row[lane], (uint32_t)v0 + lane) : 0ull;
+  const unsigned long long c1 = e_1 ? tk_entry(row[64 + lane], (uint32_t)v0 + 64 + lane) : 0ull;
+  unsigned long long m0 = __ballot(c0 > thr), m1 = __ballot(c1 > thr);
+  if (!(m0 | m1)) return;
+  tk_clear_excluded(xn, xs, xl, excl_idx, v0, lane, m0, m1);
   if (!(m0 | m1)) return;
   TkList S;
   S.e0 = lane < k ? L[lane] : 0ull;
@@ -502,6 +513,222 @@ __global__ __launch_bounds__(TK_THREADS) void tki_scores_kernel(TkiArgs A) {
   for (int ul = wave; ul < nu; ul += 4) tk_flush_user(lists + ul * k, A.partial + ((u0 + ul) * A.slices + sl) * k, k, lane);
 }
 
+// ---- z-scored ensemble scores (MANNeR) ------------------------------------------------------------------------------------------
+// T <= 3 sub-models, each a (B, D) user matrix and a (V, D) table.  The score of (u, v) is sum_t w_t (s_t - mu_t[u]) / sd_t[u], where
+// mu_t / sd_t are the mean and the unbiased standard deviation of s_t[u, .] over the user's population (eligible, inside V, not
+// excluded, not NaN).  Two passes over the tables:
+//   tke_stats_kernel   one workgroup per (tile of 64 users, statistics chunk): per t and table tile the tile product, then per user
+//       the tile's (n, mean, M2) over the population, folded into the chunk's running moments by the pairwise update;
+//   tke_finish_kernel  one wave per user folds the chunks in ascending order, writes (mean, sd), flags what cannot be standardised;
+//   tke_scores_kernel  tk_scores_kernel with a second score tile that collects the weighted z-scores of the T products.
+// The chunks depend on V alone (never on B or `slices`), so a user's statistics are a function of its rows, the tables, the mask,
+// its exclusion set and V.
+struct TkeArgs : TkArgs {                      // `user` / `table` are those of sub-model 0
+  const float* users[NRL_TOPK_MAX_MODELS];
+  const float* tables[NRL_TOPK_MAX_MODELS];
+  float w[NRL_TOPK_MAX_MODELS];
+  int32_t T, chunks, tiles_per_chunk;
+  float* out_stats;                            // (B, T, 2): mean, sd
+  float* moments;                              // (B, NRL_TOPK_STAT_CHUNKS, T, 3): n (int32 bits), mean, M2
+};
+
+__device__ __forceinline__ const float* tke_pick(const float* const (&p)[NRL_TOPK_MAX_MODELS], int t) {
+  return t == 0 ? p[0] : (t == 1 ? p[1] : p[2]);
+}
+
+// (n, mean, M2) of b folded into a (Chan et al.); both sides non-empty
+__device__ __forceinline__ void tke_fold(int& n, float& mean, float& m2, int nb, float mb, float m2b) {
+  const int na = n;
+  n = na + nb;
+  const float d = __fsub_rn(mb, mean);
+  mean = __fadd_rn(mean, __fdiv_rn(__fmul_rn(d, (float)nb), (float)n));
+  m2 = __fadd_rn(__fadd_rn(m2, m2b), __fdiv_rn(__fmul_rn(__fmul_rn(__fmul_rn(d, d), (float)na), (float)nb), (float)n));
+}
+
+__global__ __launch_bounds__(TK_THREADS) void tke_stats_kernel(TkeArgs A) {
+  __shared__ __attribute__((aligned(16))) float sc[TK_BU * TK_SCLD];
+  __shared__ int32_t xl[TK_BU * TK_XCAP];
+  __shared__ int64_t xs[TK_BU];
+  __shared__ int32_t xn[TK_BU];
+  __shared__ uint8_t el[TK_BV];
+  __shared__ int32_t mn[TK_BU * NRL_TOPK_MAX_MODELS];
+  __shared__ float mm[TK_BU * NRL_TOPK_MAX_MODELS], m2[TK_BU * NRL_TOPK_MAX_MODELS];
+
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int V = A.V, T = A.T;
+  const int ch = (int)(blockIdx.x % (unsigned)A.chunks);
+  const int64_t u0 = (int64_t)(blockIdx.x / (unsigned)A.chunks) * TK_BU;
+  const int nu = A.B - u0 < TK_BU ? (int)(A.B - u0) : TK_BU;
+  const int v_begin = ch * A.tiles_per_chunk * TK_BV;
+  const int64_t v_stop = (int64_t)v_begin + (int64_t)A.tiles_per_chunk * TK_BV;
+  const int v_end = v_stop < V ? (int)v_stop : V;
+  const int nvt = (v_end - v_begin + TK_BV - 1) / TK_BV;
+
+  for (int i = tid; i < TK_BU * NRL_TOPK_MAX_MODELS; i += TK_THREADS) {
+    mn[i] = 0;
+    mm[i] = 0.f;
+    m2[i] = 0.f;
+  }
+  tk_cache_exclusions(A, u0, nu, TK_BU, xs, xn, xl);
+
+  const int ul_begin = wave * TK_USERS_PER_WAVE, ul_end = ul_begin + TK_USERS_PER_WAVE < nu ? ul_begin + TK_USERS_PER_WAVE : nu;
+  const int srow = tid >> 2;
+  const bool ua_ok = srow < nu;
+  bool nan = false;
+
+  for (int t = 0; t < T; ++t) {
+    const float* const pa[1] = {tke_pick(A.users, t) + (ua_ok ? u0 + srow : A.B - 1) * A.D};
+    const float* const table = tke_pick(A.tables, t);
+    for (int vt = 0; vt < nvt; ++vt) {
+      const int v0 = v_begin + vt * TK_BV;
+      tk_fill_eligible(A.eligible, v0, V, el);
+      tk_tile_product<1>(pa, ua_ok, table, v0, V, A.D, sc);
+
+      const bool e_0 = el[lane] != 0, e_1 = el[64 + lane] != 0;
+      for (int ul = ul_begin; ul < ul_end; ++ul) {
+        unsigned long long m0 = __ballot(e_0), m1 = __ballot(e_1);
+        tk_clear_excluded(xn + ul, xs + ul, xl + ul * TK_XCAP, A.excl_idx, v0, lane, m0, m1);
+        const float x0 = sc[ul * TK_SCLD + lane], x1 = sc[ul * TK_SCLD + 64 + lane];
+        bool b0 = (m0 >> lane) & 1, b1 = (m1 >> lane) & 1;
+        if (__ballot((b0 && x0 != x0) || (b1 && x1 != x1))) nan = true;
+        b0 = b0 && x0 == x0;
+        b1 = b1 && x1 == x1;
+        const int nb = __popcll(__ballot(b0)) + __popcll(__ballot(b1));
+        if (nb == 0) continue;
+        const float mb = __fdiv_rn(wave_sum(__fadd_rn(b0 ? x0 : 0.f, b1 ? x1 : 0.f)), (float)nb);
+        const float d0 = b0 ? __fsub_rn(x0, mb) : 0.f, d1 = b1 ? __fsub_rn(x1, mb) : 0.f;
+        const float m2b = wave_sum(__fadd_rn(__fmul_rn(d0, d0), __fmul_rn(d1, d1)));
+        const int at = ul * NRL_TOPK_MAX_MODELS + t;
+        int n = mn[at];
+        float mean = mm[at], M2 = m2[at];
+        if (n == 0) {
+          n = nb;
+          mean = mb;
+          M2 = m2b;
+        } else {
+          tke_fold(n, mean, M2, nb, mb, m2b);
+        }
+        if (lane == 0) {
+          mn[at] = n;
+          mm[at] = mean;
+          m2[at] = M2;
+        }
+      }
+      __syncthreads();                                // the score tile and `el` are free for the next tile's operands
+    }
+  }
+
+  if (nan && lane == 0) atomicOr(A.status, NRL_TOPK_E_NAN);
+  for (int i = tid; i < nu * T; i += TK_THREADS) {
+    const int ul = i / T, t = i % T, at = ul * NRL_TOPK_MAX_MODELS + t;
+    float* const o = A.moments + (((u0 + ul) * NRL_TOPK_STAT_CHUNKS + ch) * T + t) * 3;
+    o[0] = __int_as_float(mn[at]);
+    o[1] = mm[at];
+    o[2] = m2[at];
+  }
+}
+
+// a user's statistics can standardise: every sd positive and finite
+__device__ __forceinline__ bool tke_sd_ok(float sd) { return sd > 0.f && sd < INFINITY; }
+
+__global__ __launch_bounds__(64) void tke_finish_kernel(TkeArgs A) {
+  const int64_t u = blockIdx.x;
+  const int lane = threadIdx.x, T = A.T;
+  bool bad = false;
+  if (lane < T) {
+    int n = 0;
+    float mean = 0.f, M2 = 0.f;
+    for (int c = 0; c < A.chunks; ++c) {
+      const float* const m = A.moments + ((u * NRL_TOPK_STAT_CHUNKS + c) * T + lane) * 3;
+      const int nb = __float_as_int(m[0]);
+      if (nb == 0) continue;
+      if (n == 0) {
+        n = nb;
+        mean = m[1];
+        M2 = m[2];
+      } else {
+        tke_fold(n, mean, M2, nb, m[1], m[2]);
+      }
+    }
+    const float nanv = __uint_as_float(0x7FC00000u);
+    const float sd = n >= 2 ? __fsqrt_rn(__fdiv_rn(M2, (float)(n - 1))) : nanv;
+    A.out_stats[(u * T + lane) * 2] = n ? mean : nanv;
+    A.out_stats[(u * T + lane) * 2 + 1] = sd;
+    bad = !tke_sd_ok(sd);
+  }
+  if (__ballot(bad) && lane == 0) atomicOr(A.status, NRL_TOPK_E_STATS);
+}
+
+__global__ __launch_bounds__(TK_THREADS) void tke_scores_kernel(TkeArgs A) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char tk_smem[];
+  float* const sc = reinterpret_cast<float*>(tk_smem);                       // [TK_BU][TK_SCLD] the raw scores of one table
+  float* const zs = sc + TK_BU * TK_SCLD;                                    // [TK_BU][TK_SCLD] the ensemble scores
+  int32_t* const xl = reinterpret_cast<int32_t*>(zs + TK_BU * TK_SCLD);      // [TK_BU][TK_XCAP]
+  int64_t* const xs = reinterpret_cast<int64_t*>(xl + TK_BU * TK_XCAP);      // [TK_BU]
+  int32_t* const xn = reinterpret_cast<int32_t*>(xs + TK_BU);                // [TK_BU]
+  uint8_t* const el = reinterpret_cast<uint8_t*>(xn + TK_BU);                // [TK_BV]
+  unsigned long long* const lists = reinterpret_cast<unsigned long long*>(el + TK_BV);      // [TK_BU][k]
+  float* const st = reinterpret_cast<float*>(lists + TK_BU * A.k);           // [TK_BU][T][2] mean, sd; sd 0: the user is refused
+
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int k = A.k, V = A.V, T = A.T;
+  const int sl = (int)(blockIdx.x % (unsigned)A.slices);
+  const int64_t u0 = (int64_t)(blockIdx.x / (unsigned)A.slices) * TK_BU;
+  const int nu = A.B - u0 < TK_BU ? (int)(A.B - u0) : TK_BU;
+  const int v_begin = sl * A.tiles_per_slice * TK_BV;
+  const int64_t v_stop = (int64_t)v_begin + (int64_t)A.tiles_per_slice * TK_BV;
+  const int v_end = v_stop < V ? (int)v_stop : V;
+  const int nvt = (v_end - v_begin + TK_BV - 1) / TK_BV;
+
+  for (int i = tid; i < TK_BU * k; i += TK_THREADS) lists[i] = 0ull;
+  if (tid < TK_BU) {                                  // a refused user (and a slot without one) is marked by sd = 0 in its first entry
+    bool ok = tid < nu;
+    for (int t = 0; t < T; ++t) {
+      const float mean = ok ? A.out_stats[((u0 + tid) * T + t) * 2] : 0.f, sd = ok ? A.out_stats[((u0 + tid) * T + t) * 2 + 1] : 1.f;
+      st[(tid * T + t) * 2] = mean;
+      st[(tid * T + t) * 2 + 1] = sd;
+      ok = ok && tke_sd_ok(sd);
+    }
+    if (!ok) st[tid * T * 2 + 1] = 0.f;
+  }
+  tk_cache_exclusions(A, u0, nu, TK_BU, xs, xn, xl);   // (its barrier also publishes `lists` and `st`)
+
+  const int ul_begin = wave * TK_USERS_PER_WAVE, ul_end = ul_begin + TK_USERS_PER_WAVE < nu ? ul_begin + TK_USERS_PER_WAVE : nu;
+  const int srow = tid >> 2;
+  const bool ua_ok = srow < nu;
+  bool nan = false;
+
+  for (int vt = 0; vt < nvt; ++vt) {
+    const int v0 = v_begin + vt * TK_BV;
+    tk_fill_eligible(A.eligible, v0, V, el);
+    for (int t = 0; t < T; ++t) {
+      const float* const pa[1] = {tke_pick(A.users, t) + (ua_ok ? u0 + srow : A.B - 1) * A.D};
+      tk_tile_product<1>(pa, ua_ok, tke_pick(A.tables, t), v0, V, A.D, sc);
+      const float w = t == 0 ? A.w[0] : (t == 1 ? A.w[1] : A.w[2]);
+      for (int i = tid; i < TK_BU * TK_BV; i += TK_THREADS) {
+        const int ul = i / TK_BV, at = ul * TK_SCLD + (i % TK_BV);
+        const float* const s2 = st + (ul * T + t) * 2;
+        const float z = __fmul_rn(w, __fdiv_rn(__fsub_rn(sc[at], s2[0]), s2[1]));
+        zs[at] = t ? __fadd_rn(zs[at], z) : z;
+      }
+      __syncthreads();                                // the ensemble tile is complete; tile 0 is free for the next operands
+    }
+
+    const bool e_0 = el[lane] != 0, e_1 = el[64 + lane] != 0;
+    for (int ul = ul_begin; ul < ul_end; ++ul) {
+      if (st[ul * T * 2 + 1] == 0.f) continue;        // refused: the lists stay empty and the merge writes -1 / -inf
+      tk_select_user(zs + ul * TK_SCLD, lists + ul * k, xn + ul, xs + ul, xl + ul * TK_XCAP, A.excl_idx, v0, e_0, e_1, k, lane, nan);
+    }
+    __syncthreads();                                  // the ensemble tile and `el` are free for the next tile
+  }
+
+  if (nan && lane == 0) atomicOr(A.status, NRL_TOPK_E_NAN);
+  wave_lds_sync();
+  for (int ul = ul_begin; ul < ul_end; ++ul) tk_flush_user(lists + ul * k, A.partial + ((u0 + ul) * A.slices + sl) * k, k, lane);
+}
+
 static bool tk_shape_ok(int64_t B, int64_t V, int32_t D, int32_t k) {
   return B >= 0 && V >= 0 && V < ((int64_t)1 << 31) && D > 0 && D % 4 == 0 && D <= NRL_TOPK_MAX_D && k >= 1 && k <= NRL_TOPK_MAX_K;
 }
@@ -535,9 +762,11 @@ static TkArgs tk_args(const float* user, const float* table, int64_t B, int64_t 
   return TkArgs{user, table, B, (int32_t)V, D, k, excl_idx, excl_off, eligible, 0, 0, partial, out_idx, out_score, status};
 }
 
-// plans the slices, runs `kernel` (`tiles` score tiles, `bu` users per workgroup) over them and then the merge
+// plans the slices, runs `kernel` (`tiles` score tiles, `bu` users per workgroup, `extra_lds` bytes of its own after the layout of
+// tk_lds_bytes) over them and then the merge
 template <class Args>
-static int tk_launch(const char* who, void (*kernel)(Args), Args& A, int32_t slices, int tiles, int bu, void* stream) {
+static int tk_launch(const char* who, void (*kernel)(Args), Args& A, int32_t slices, int tiles, int bu, void* stream,
+                     size_t extra_lds = 0) {
   int64_t lists, used, tps;
   tk_plan(A.B, A.V, slices, bu, lists, used, tps);
   const int64_t blocks = ceil_div(A.B, bu) * used;
@@ -546,7 +775,7 @@ static int tk_launch(const char* who, void (*kernel)(Args), Args& A, int32_t sli
   A.tiles_per_slice = (int32_t)tps;
   hipStream_t st = (hipStream_t)stream;
   if (used > 0) {
-    const size_t smem = tk_lds_bytes(tiles, bu, A.k);
+    const size_t smem = tk_lds_bytes(tiles, bu, A.k) + extra_lds;
     // more than 64 KB of dynamic LDS needs the attribute; it belongs to the current device, so it is set per call
     if (smem > 64 * 1024) NRL_HIP(hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     kernel<<<(unsigned)blocks, TK_THREADS, smem, st>>>(A);
@@ -614,6 +843,48 @@ int nrl_topk_interest_scores(const float* interests, const float* gate, const fl
   A.mode = mode;
   return mode == 2 ? tk_launch("topk_interest_scores", tki_scores_kernel<true>, A, slices, 2, Ut, stream)
                    : tk_launch("topk_interest_scores", tki_scores_kernel<false>, A, slices, 1, Ut, stream);
+}
+
+int nrl_topk_ensemble_scores(const float* const* users, const float* const* tables, const float* weights, int32_t T, int64_t B,
+                             int64_t V, int32_t D, int32_t k, const int64_t* excl_idx, const int64_t* excl_off,
+                             const uint8_t* eligible, int32_t slices, int64_t* out_idx, float* out_score, float* out_stats,
+                             float* moments, int32_t* status, void* ws, size_t ws_bytes, void* stream) {
+  NRL_REQUIRE(B >= 0 && V >= 0 && D >= 0 && slices >= 0, "topk_ensemble_scores: negative size");
+  NRL_REQUIRE(T >= 1 && T <= NRL_TOPK_MAX_MODELS, "topk_ensemble_scores: T in [1, %d] sub-models (got %d)", NRL_TOPK_MAX_MODELS, T);
+  NRL_TRY(tk_check("topk_ensemble_scores", B, V, D, k, excl_idx, excl_off));
+  NRL_REQUIRE(users && tables && weights, "topk_ensemble_scores: null users / tables / weights array");
+  for (int t = 0; t < T; ++t)
+    NRL_REQUIRE(users[t] && (V == 0 || tables[t]), "topk_ensemble_scores: null user matrix or table of sub-model %d", t);
+  NRL_REQUIRE(status, "topk_ensemble_scores: the status word is required");
+  NRL_REQUIRE(out_stats && moments, "topk_ensemble_scores: out_stats and the moments scratch are required");
+  if (B == 0) return NRL_OK;
+  NRL_REQUIRE(out_idx && out_score, "topk_ensemble_scores: null argument");
+  unsigned long long* partial;
+  NRL_TRY(carve_workspace(ws, ws_bytes, [&](Arena& a) { tk_layout(a, B, V, k, slices, TK_BU, &partial); }));
+  TkeArgs A;
+  static_cast<TkArgs&>(A) = tk_args(users[0], tables[0], B, V, D, k, excl_idx, excl_off, eligible, partial, out_idx, out_score, status);
+  for (int t = 0; t < NRL_TOPK_MAX_MODELS; ++t) {
+    A.users[t] = users[t < T ? t : 0];
+    A.tables[t] = tables[t < T ? t : 0];
+    A.w[t] = t < T ? weights[t] : 0.f;
+  }
+  A.T = T;
+  A.out_stats = out_stats;
+  A.moments = moments;
+  // the statistics chunks: a function of V alone, so that the order of every reduction is
+  const int64_t nvt = ceil_div(V, TK_BV);
+  A.tiles_per_chunk = (int32_t)(nvt > 0 ? ceil_div(nvt, NRL_TOPK_STAT_CHUNKS) : 1);
+  A.chunks = (int32_t)(nvt > 0 ? ceil_div(nvt, A.tiles_per_chunk) : 0);
+  const int64_t blocks = ceil_div(B, TK_BU) * A.chunks;
+  NRL_REQUIRE(blocks < ((int64_t)1 << 31), "topk_ensemble_scores: grid too large (%lld workgroups)", (long long)blocks);
+  hipStream_t st = (hipStream_t)stream;
+  if (blocks > 0) {
+    tke_stats_kernel<<<(unsigned)blocks, TK_THREADS, 0, st>>>(A);
+    NRL_LAUNCH_CHECK();
+  }
+  tke_finish_kernel<<<(unsigned)B, 64, 0, st>>>(A);
+  NRL_LAUNCH_CHECK();
+  return tk_launch("topk_ensemble_scores", tke_scores_kernel, A, slices, 2, TK_BU, stream, (size_t)TK_BU * T * 2 * 4);
 }
 
 }  // extern "C"

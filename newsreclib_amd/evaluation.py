@@ -319,7 +319,36 @@ class MannerVectorCache(_ImpressionCache):
     def recommend(self, *args, **kwargs):
         raise NotImplementedError("MANNeR z-scores every sub-model's scores within an impression's own candidate list "
                                   "(manner_module.py: the ensemble of standardised scores): without a candidate list there is no "
-                                  "score to rank the whole table by; recommend from one sub-model's NewsVectorCache instead")
+                                  "score to rank the whole table by; recommend from one sub-model's NewsVectorCache instead, or "
+                                  "name the population: `recommend_ensemble` z-scores over every row a user may be recommended")
+
+    @torch.no_grad()
+    def recommend_ensemble(self, hist_idx: torch.Tensor, hist_sizes: torch.Tensor, k: int, user_idx: Optional[torch.Tensor] = None,
+                           exclude_history: bool = True, eligible: Optional[torch.Tensor] = None, return_stats: bool = False):
+        """The ``k`` news of the WHOLE table each user's ensemble score ranks highest -> (news_idx (B, k) int64, scores (B, k)
+        fp32, status[, stats (B, T, 2): mean, sd]).  The candidate list of a user is its population: every eligible row that is
+        not in its history (``exclude_history``); each sub-model's scores are z-scored over it and the weighted sum is what
+        ``scores`` returns for that candidate list (``ops.topk_ensemble_scores``).  Per sub-model the user vector is the mean of
+        the gathered history rows of that sub-model's table, as in ``scores``; an empty history gives a NaN vector and that user
+        is refused through ``status`` (``ops.TOPK_FLAGS``), as is any user whose scores cannot be standardised.  Same contract as
+        ``NewsVectorCache.recommend``: ``hist_idx`` on the GPU, ``hist_sizes`` on the host, nothing read back."""
+        from .dense_batch import dense_rows
+        if not hist_idx.is_cuda:
+            raise RuntimeError(f"newsreclib_amd: `hist_idx` must live on the GPU (got {hist_idx.device}); there is no CPU path")
+        if self.vectors is None:
+            self.build()
+        dev = self.table.device
+        hist_idx = hist_idx.to(dev).long()
+        meta = self.caches[0]._user_meta(hist_sizes, user_idx)
+        users = []
+        for vec in self.vectors:
+            hv = ops.embedding_gather(vec, hist_idx.reshape(-1, 1)).reshape(-1, vec.shape[1])
+            dense = dense_rows(hv, meta["batch_hist"], meta["batch_size"], meta["max_hist"], meta["hist_offsets"])
+            users.append(ops.HistMeanFn.apply(dense, meta["hist_offsets"]))
+        excl = (hist_idx, meta["hist_offsets"]) if exclude_history else (None, None)
+        idx, score, status, stats = ops.topk_ensemble_scores(users, self.vectors, self.weights, k, excl[0], excl[1],
+                                                             eligible.to(dev) if eligible is not None else None)
+        return (idx, score, status, stats) if return_stats else (idx, score, status)
 
 
 class NpaFeatureCache(_ImpressionCache):
@@ -435,7 +464,8 @@ def format_recommendations(user_ids: Sequence, news_idx: torch.Tensor, scores: t
 
 def recommend_users(cache: NewsVectorCache, users: Sequence[Dict], k: int, batch_size: int = 512,
                     eligible: Optional[torch.Tensor] = None) -> Dict[str, Dict[str, float]]:
-    """``cache.recommend`` (``cache.recommend_interests`` where the cache's module is a ``multi_interest_scorer``) over a list of
+    """``cache.recommend`` (``cache.recommend_interests`` where the cache's module is a ``multi_interest_scorer``,
+    ``cache.recommend_ensemble`` where the cache has one: ``MannerVectorCache``) over a list of
     users ({"hist": idx tensor[, "user_idx", "user_id"]}) in batches -> the recommendation dictionary of ``format_recommendations``.  ``user_id`` defaults to the user's position in the list + 1 (as ``build_batch``);
     news ids come from the table's ``news_ids`` column when it has one.  One device-to-host copy per batch, at its end; a status
     flag of the batch (``ops.TOPK_FLAGS``: each is handled by the kernel) is passed on as a warning."""
@@ -448,6 +478,7 @@ def recommend_users(cache: NewsVectorCache, users: Sequence[Dict], k: int, batch
         hist = torch.cat([torch.as_tensor(u["hist"]).long() for u in chunk]).to(dev)
         uidx = torch.stack([torch.as_tensor(u["user_idx"]) for u in chunk]) if "user_idx" in chunk[0] else None
         rank = cache.recommend_interests if getattr(cache.module, "multi_interest_scorer", False) else cache.recommend
+        rank = getattr(cache, "recommend_ensemble", rank)
         idx, score, status = rank(hist, hs, k, user_idx=uidx, eligible=eligible)
         packed = torch.cat([idx.double(), score.double(), status.double().expand(idx.shape[0], 1)], dim=1).cpu()      # the one copy
         word = int(packed[0, -1]) if packed.shape[0] else 0

@@ -714,7 +714,28 @@ def impression_metrics(preds: torch.Tensor, targets: torch.Tensor, cand_offsets:
 TOPK_MAX_K, TOPK_MAX_D = 128, 1024
 TOPK_FLAGS = {1: "an exclusion index is outside [0, V) (ignored)",
               2: "excl_off decreases or leaves its range (that user's row is all -1 / -inf)",
-              4: "a NaN score of an eligible, not excluded row (that row is left out for that user)"}
+              4: "a NaN score of an eligible, not excluded row (that row is left out for that user)",
+              8: "a user's scores of some table cannot be standardised: zero, non-finite or undefined standard deviation (that "
+                 "user's row is all -1 / -inf)"}
+
+
+def _topk_masks(excl_idx, excl_off, eligible, B: int, V: int):
+    """The exclusion lists and the eligibility mask as every top-k entry takes them, checked."""
+    if (excl_idx is None) != (excl_off is None):
+        raise ValueError("newsreclib_amd: excl_idx and excl_off go together")
+    if excl_idx is not None:
+        excl_idx, excl_off = _chk(excl_idx, torch.int64, "excl_idx"), _chk(excl_off, torch.int64, "excl_off")
+        if excl_off.numel() != B + 1:
+            raise ValueError("newsreclib_amd: excl_off must have B + 1 entries")
+        # the kernel trusts excl_off[B] as the length of excl_idx: an offset beyond the list is turned into one it rejects
+        excl_off = torch.where(excl_off > excl_idx.numel(), torch.full_like(excl_off, -1), excl_off)
+    if eligible is not None:
+        if eligible.dtype == torch.bool and eligible.is_cuda:
+            eligible = eligible.to(torch.uint8)
+        eligible = _chk(eligible, torch.uint8, "eligible")
+        if eligible.numel() != V:
+            raise ValueError("newsreclib_amd: eligible must have one entry per table row")
+    return excl_idx, excl_off, eligible
 
 
 def topk_scores(user_vec: torch.Tensor, table: torch.Tensor, k: int, excl_idx: Optional[torch.Tensor] = None,
@@ -731,20 +752,7 @@ def topk_scores(user_vec: torch.Tensor, table: torch.Tensor, k: int, excl_idx: O
         raise ValueError(f"newsreclib_amd: user_vec (B, D) and table (V, D) expected, got {tuple(user_vec.shape)} and "
                          f"{tuple(table.shape)}")
     B, D, V, k = int(user_vec.shape[0]), int(user_vec.shape[1]), int(table.shape[0]), int(k)
-    if (excl_idx is None) != (excl_off is None):
-        raise ValueError("newsreclib_amd: excl_idx and excl_off go together")
-    if excl_idx is not None:
-        excl_idx, excl_off = _chk(excl_idx, torch.int64, "excl_idx"), _chk(excl_off, torch.int64, "excl_off")
-        if excl_off.numel() != B + 1:
-            raise ValueError("newsreclib_amd: excl_off must have B + 1 entries")
-        # the kernel trusts excl_off[B] as the length of excl_idx: an offset beyond the list is turned into one it rejects
-        excl_off = torch.where(excl_off > excl_idx.numel(), torch.full_like(excl_off, -1), excl_off)
-    if eligible is not None:
-        if eligible.dtype == torch.bool and eligible.is_cuda:
-            eligible = eligible.to(torch.uint8)
-        eligible = _chk(eligible, torch.uint8, "eligible")
-        if eligible.numel() != V:
-            raise ValueError("newsreclib_amd: eligible must have one entry per table row")
+    excl_idx, excl_off, eligible = _topk_masks(excl_idx, excl_off, eligible, B, V)
     dev = user_vec.device
     idx = torch.empty((B, max(k, 0)), dtype=torch.int64, device=dev)
     score = torch.empty((B, max(k, 0)), dtype=torch.float32, device=dev)
@@ -790,20 +798,7 @@ def topk_interest_scores(interests: torch.Tensor, table: torch.Tensor, k: int, m
             raise ValueError(f"newsreclib_amd: gate must have the shape of interests, got {tuple(gate.shape)}")
     else:
         gate = None
-    if (excl_idx is None) != (excl_off is None):
-        raise ValueError("newsreclib_amd: excl_idx and excl_off go together")
-    if excl_idx is not None:
-        excl_idx, excl_off = _chk(excl_idx, torch.int64, "excl_idx"), _chk(excl_off, torch.int64, "excl_off")
-        if excl_off.numel() != B + 1:
-            raise ValueError("newsreclib_amd: excl_off must have B + 1 entries")
-        # the kernel trusts excl_off[B] as the length of excl_idx: an offset beyond the list is turned into one it rejects
-        excl_off = torch.where(excl_off > excl_idx.numel(), torch.full_like(excl_off, -1), excl_off)
-    if eligible is not None:
-        if eligible.dtype == torch.bool and eligible.is_cuda:
-            eligible = eligible.to(torch.uint8)
-        eligible = _chk(eligible, torch.uint8, "eligible")
-        if eligible.numel() != V:
-            raise ValueError("newsreclib_amd: eligible must have one entry per table row")
+    excl_idx, excl_off, eligible = _topk_masks(excl_idx, excl_off, eligible, B, V)
     dev = interests.device
     idx = torch.empty((B, max(k, 0)), dtype=torch.int64, device=dev)
     score = torch.empty((B, max(k, 0)), dtype=torch.float32, device=dev)
@@ -815,3 +810,47 @@ def topk_interest_scores(interests: torch.Tensor, table: torch.Tensor, k: int, m
                                             score.data_ptr(), status.data_ptr(), ws.data_ptr(), ws.numel(), _stream()),
                "nrl_topk_interest_scores")
     return idx, score, status
+
+
+TOPK_MAX_MODELS, TOPK_STAT_CHUNKS = 3, 64
+
+
+def topk_ensemble_scores(users: Sequence[torch.Tensor], tables: Sequence[torch.Tensor], weights: Sequence[float], k: int,
+                         excl_idx: Optional[torch.Tensor] = None, excl_off: Optional[torch.Tensor] = None,
+                         eligible: Optional[torch.Tensor] = None, slices: int = 0):
+    """``nrl_topk_ensemble_scores``: ``topk_scores`` by MANNeR's ensemble of standardised scores.  ``users[t]`` (B, D),
+    ``tables[t]`` (V, D) and ``weights[t]`` for T in {1, 2, 3} sub-models; the score of a table row is
+    ``sum_t weights[t] * (s_t - mu_t) / sd_t`` with ``s_t = users[t][u] . tables[t][v]`` and ``mu_t`` / ``sd_t`` the mean and the
+    unbiased standard deviation of ``s_t`` over the user's population: the eligible rows that are not on its exclusion list.
+    -> (idx (B, k) int64, score (B, k) fp32, status (1) int32, stats (B, T, 2) fp32: mean, sd) with the ordering, exclusion,
+    eligibility and status flags of ``topk_scores`` and one flag more (``TOPK_FLAGS[8]``): a user whose scores cannot be
+    standardised gets ``-1`` / ``-inf``.  No (B, V) matrix is materialised; nothing here synchronises with the host."""
+    lib = _lib.load()
+    users, tables = list(users), list(tables)
+    T = len(tables)
+    if not 1 <= T <= TOPK_MAX_MODELS or len(users) != T or len(weights) != T:
+        raise ValueError(f"newsreclib_amd: 1 to {TOPK_MAX_MODELS} sub-models with one user matrix, one table and one weight each "
+                         f"(got {len(users)}, {T} and {len(weights)})")
+    if users[0].dim() != 2 or tables[0].dim() != 2 or users[0].shape[1] != tables[0].shape[1] or \
+            any(u.shape != users[0].shape for u in users) or any(t.shape != tables[0].shape for t in tables):
+        raise ValueError(f"newsreclib_amd: users (B, D) and tables (V, D) of one shape each expected, got "
+                         f"{[tuple(u.shape) for u in users]} and {[tuple(t.shape) for t in tables]}")
+    users = [_chk(u, torch.float32, "users") for u in users]
+    tables = [_chk(t, torch.float32, "tables") for t in tables]
+    B, D, V, k = int(users[0].shape[0]), int(users[0].shape[1]), int(tables[0].shape[0]), int(k)
+    excl_idx, excl_off, eligible = _topk_masks(excl_idx, excl_off, eligible, B, V)
+    dev = users[0].device
+    idx = torch.empty((B, max(k, 0)), dtype=torch.int64, device=dev)
+    score = torch.empty((B, max(k, 0)), dtype=torch.float32, device=dev)
+    stats = torch.empty((B, T, 2), dtype=torch.float32, device=dev)
+    moments = torch.empty((B, TOPK_STAT_CHUNKS, T, 3), dtype=torch.float32, device=dev)
+    status = torch.zeros(1, dtype=torch.int32, device=dev)
+    ws = workspace(lib.nrl_topk_scores_workspace_bytes(B, V, D, k, int(slices)), dev)
+    ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
+    uptr = (ctypes.c_void_p * T)(*[u.data_ptr() for u in users])
+    tptr = (ctypes.c_void_p * T)(*[t.data_ptr() for t in tables])
+    wts = (ctypes.c_float * T)(*[float(w) for w in weights])
+    _lib.check(lib.nrl_topk_ensemble_scores(uptr, tptr, wts, T, B, V, D, k, ptr(excl_idx), ptr(excl_off), ptr(eligible), int(slices),
+                                            idx.data_ptr(), score.data_ptr(), stats.data_ptr(), moments.data_ptr(),
+                                            status.data_ptr(), ws.data_ptr(), ws.numel(), _stream()), "nrl_topk_ensemble_scores")
+    return idx, score, status, stats
