@@ -805,6 +805,19 @@ int nrl_dkn_click_bwd(const NrlDknClickParams* p, const NrlDknClickGrads* g, con
                       int32_t max_hist, const float* cand, const int64_t* cand_offsets, int64_t batch, int32_t max_cand,
                       int32_t dim, const float* user, const float* d_scores, float* d_hist, float* d_cand, void* ws,
                       size_t ws_bytes, void* stream);
+/* The click predictor factored for a full-catalogue ranking (symbols added to ABI v19): its first layer splits by columns,
+ * pred_w1 = [Wc | Wu], so pre[b, v, j] = P[v, j] + q[b, j] and nrl_topk_relu_scores ranks the whole table without the (B, V, dim)
+ * work.  Neither entry needs a workspace; limits and messages are those of nrl_dkn_click_fwd.
+ * nrl_dkn_user_query: one workgroup per user.  user (B, dim): the user vector, the bits nrl_dkn_click_fwd writes for the same
+ *   history (the same attention code); q (B, Hd): q[b, j] = (sum_d pred_w1[j, dim + d] user[b, d]) + pred_b1[j].  An empty
+ *   history gives user = 0 and q = pred_b1.
+ * nrl_dkn_cand_project: out (N, Hd): out[n, j] = sum_d pred_w1[j, d] rows[n, d], no bias; rows (N, dim) fp32, N < 2^31; plain fp32
+ *   fmaf code, once per table.
+ * Every output element is one reduction whose order is fixed by dim alone: its bits do not depend on B, N, the grid or the
+ * GEMM engine setting. */
+int nrl_dkn_user_query(const NrlDknClickParams* p, const float* hist, const int64_t* hist_offsets, int32_t max_hist, int64_t B,
+                       int32_t dim, float* user, float* q, void* stream);
+int nrl_dkn_cand_project(const NrlDknClickParams* p, const float* rows, int64_t N, int32_t dim, float* out, void* stream);
 
 /* ---- CAUM (caum_module.py:326-360, user/caum.py:81-125): candidate-aware user encoder, head-padded self-attention ------
  * nrl_caum_attn_*: attention over a packed (rows, 3 * heads * head_dim) q|k|v buffer -> o (rows, heads * head_dim), for every
@@ -1106,6 +1119,30 @@ int nrl_topk_ensemble_scores(const float* const* users, const float* const* tabl
                              float* out_stats /* (B, T, 2): mean, sd */,
                              float* moments   /* (B, NRL_TOPK_STAT_CHUNKS, T, 3) caller-provided scratch */,
                              int32_t* status, void* ws, size_t ws_bytes, void* stream);
+
+/* nrl_topk_relu_scores: the same ranking by DKN's DNN click predictor (click_predictor.py:14-45: Linear(2 dim, Hd) -> ReLU ->
+ *   Linear(Hd, 1) on [cand; user]) with the candidate list replaced by the table.  The first layer splits by columns,
+ *   pred_w1 = [Wc | Wu], so with q (B, Hd) = user Wu^T + b1 (nrl_dkn_user_query) and proj (V, Hd) = table Wc^T
+ *   (nrl_dkn_cand_project), both fp32, row-major, device:
+ *     score(u, v) = b2 + sum_j w2[j] relu(proj[v, j] + q[u, j]).
+ *   w2 (Hd) and b2 (one float) are DEVICE pointers (the module's parameters: nothing is read back).  Hd in
+ *   [1, NRL_TOPK_MAX_HIDDEN], any value (no multiple-of-4 requirement); k, V, B, excl_idx / excl_off, eligible, slices,
+ *   out_idx / out_score and status as for nrl_topk_scores.
+ *   Arithmetic, fixed: x = proj[v, j] + q[u, j] (one fp32 addition); h_j = x < 0 ? 0 : x, so a NaN x stays NaN (unlike the
+ *     fmaxf of nrl_dkn_click_fwd, which turns it into 0); s = b2, then s = fmaf(w2[j], h_j, s) for j = 0 ... Hd - 1: the order of
+ *     nrl_dkn_click_fwd's last stage.  The bits of score(u, v) depend on q[u], proj[v], w2, b2 and Hd alone: not on B, V, k,
+ *     slices, the grid or the GEMM engine setting (which this entry does not read).  A NaN score of an eligible, not excluded
+ *     row sets NRL_TOPK_E_NAN and the row is left out for that user.  Plain vector loads / stores and LDS; no floating-point
+ *     atomics, no allocation, no host synchronisation; neither (B, V) nor (B, V, Hd) is written.
+ *   Workspace: there is no size function of its own: the partial lists are those of nrl_topk_scores, so
+ *     nrl_topk_scores_workspace_bytes(B, V, 4, k, slices) -- D = 4 stands in, the size does not depend on D and Hd need not be
+ *     a D that function accepts -- is exactly this entry's requirement; a shorter buffer is refused with NRL_E_WORKSPACE before
+ *     any launch.  B == 0 returns success without a launch; V == 0 fills the output with -1 / -inf.  Sizes outside the limits and
+ *     a null status, w2 or b2 return NRL_E_INVALID. */
+#define NRL_TOPK_MAX_HIDDEN 64
+int nrl_topk_relu_scores(const float* q, const float* proj, const float* w2, const float* b2, int64_t B, int64_t V, int32_t Hd,
+                         int32_t k, const int64_t* excl_idx, const int64_t* excl_off, const uint8_t* eligible, int32_t slices,
+                         int64_t* out_idx, float* out_score, int32_t* status, void* ws, size_t ws_bytes, void* stream);
 
 #ifdef __cplusplus
 }

@@ -224,6 +224,9 @@ SIGNATURES = {
     "nrl_dkn_click_bwd": (c_int32, [POINTER(NrlDknClickParams), POINTER(NrlDknClickGrads), c_void_p, c_void_p, c_int32,
                                     c_void_p, c_void_p, c_int64, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p,
                                     c_void_p, c_size_t, c_void_p]),
+    "nrl_dkn_user_query": (c_int32, [POINTER(NrlDknClickParams), c_void_p, c_void_p, c_int32, c_int64, c_int32, c_void_p,
+                                     c_void_p, c_void_p]),
+    "nrl_dkn_cand_project": (c_int32, [POINTER(NrlDknClickParams), c_void_p, c_int64, c_int32, c_void_p, c_void_p]),
     "nrl_caum_attn_fwd": (c_int32, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int32, c_int32, c_int32, c_float,
                                     c_void_p]),
     "nrl_caum_attn_bwd": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int32, c_int32,
@@ -305,6 +308,8 @@ SIGNATURES = {
     "nrl_topk_ensemble_scores": (c_int32, [POINTER(c_void_p), POINTER(c_void_p), POINTER(c_float), c_int32, c_int64, c_int64, c_int32,
                                            c_int32, c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p,
                                            c_void_p, c_void_p, c_size_t, c_void_p]),
+    "nrl_topk_relu_scores": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int32, c_int32, c_void_p,
+                                       c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "nrl_embedding_rows_fwd": (c_int32, [c_void_p, c_void_p, c_int64, c_int32, c_double, c_uint64, c_uint32,
                                          c_void_p, c_void_p]),
     "nrl_embedding_rows_bwd": (c_int32, [c_void_p, c_void_p, c_int64, c_int32, c_double, c_uint64, c_uint32,

@@ -7,6 +7,8 @@
 //   nrl_dkn_click_*    one workgroup per impression: the user attention over its ragged history, the user vector, the
 //                      predictor and the score mask; backward without float atomics (a fixed-order reduction over the
 //                      batch for the parameter gradients)
+//   nrl_dkn_user_query / nrl_dkn_cand_project  the two halves of the predictor's first layer, split by columns of pred_w1: the
+//                      user's q = Wu u + b1 and the catalogue's P = rows Wc^T, for nrl_topk_relu_scores (nrl_topk.hip)
 #include <math.h>
 
 #include "nrl_api_internal.h"
@@ -659,6 +661,72 @@ __global__ __launch_bounds__(DKN_THREADS) void dkn_click_param_grad_kernel(
   }
 }
 
+// ---- the factored click predictor: pre[j] = P[v, j] + q[b, j] with pred_w1 = [Wc | Wu] (full-catalogue top-k, nrl_topk.hip) ------
+// One workgroup per user: the user vector of dkn_attend (the bits dkn_click_fwd_kernel writes) and
+// q[b, j] = (sum_d Wu[j, d] u[d]) + b1[j], every j one wave's lane-strided fmaf chain and wave_sum: the order depends on dim alone.
+__global__ __launch_bounds__(DKN_THREADS) void dkn_user_query_kernel(NrlDknClickParams p, const float* __restrict__ hist,
+                                                                     const int64_t* __restrict__ hoff, int dim,
+                                                                     float* __restrict__ user, float* __restrict__ q) {
+  __shared__ DknSmem sm;
+  const int64_t b = blockIdx.x;
+  dkn_attend(p, hist, hoff, b, dim, sm);
+  for (int d = threadIdx.x; d < dim; d += DKN_THREADS) user[b * dim + d] = sm.u[d];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  for (int j = wave; j < p.hidden; j += DKN_WAVES) {
+    const float* w = p.pred_w1 + (int64_t)j * 2 * dim + dim;
+    float acc = 0.f;
+    for (int d = lane; d < dim; d += 64) acc = fmaf(w[d], sm.u[d], acc);
+    acc = wave_sum(acc);
+    if (lane == 0) q[b * p.hidden + j] = acc + p.pred_b1[j];
+  }
+}
+
+// out[n, j] = sum_d Wc[j, d] rows[n, d]: one thread per (row, NJ values of j), one fmaf chain over d = 0, 1, ... from +0 each, so
+// the bits of an output depend on its row, Wc[j] and dim alone.  A workgroup owns DKN_PROJ_ROWS rows; chunks of DKN_PROJ_DK
+// columns of the rows and of Wc pass through LDS (row stride DK + 1: the 64 lanes of a wave read 64 rows at one column from 64
+// different banks; a wave's j is uniform, so Wc is read as a broadcast).
+constexpr int DKN_PROJ_ROWS = 64;
+constexpr int DKN_PROJ_DK = 32;
+constexpr int DKN_PROJ_LD = DKN_PROJ_DK + 1;
+
+template <int NJ>
+__global__ __launch_bounds__(DKN_THREADS) void dkn_cand_project_kernel(const float* __restrict__ w1, int Hd,
+                                                                       const float* __restrict__ rows, int64_t N, int dim,
+                                                                       float* __restrict__ out) {
+  __shared__ float xs[DKN_PROJ_ROWS * DKN_PROJ_LD];
+  __shared__ float ws[DKN_MAX_HID * DKN_PROJ_LD];
+  const int tid = threadIdx.x, r = tid & 63;
+  const int jg = __builtin_amdgcn_readfirstlane(tid >> 6);           // this wave's j are jg, jg + 4, ...
+  const int64_t n0 = (int64_t)blockIdx.x * DKN_PROJ_ROWS;
+  float acc[NJ];
+#pragma unroll
+  for (int i = 0; i < NJ; ++i) acc[i] = 0.f;
+  for (int d0 = 0; d0 < dim; d0 += DKN_PROJ_DK) {
+    const int nd = min(DKN_PROJ_DK, dim - d0);
+    for (int i = tid; i < DKN_PROJ_ROWS * DKN_PROJ_DK; i += DKN_THREADS) {
+      const int rr = i / DKN_PROJ_DK, c = i % DKN_PROJ_DK;
+      xs[rr * DKN_PROJ_LD + c] = (n0 + rr < N && c < nd) ? rows[(n0 + rr) * dim + d0 + c] : 0.f;
+    }
+    for (int i = tid; i < Hd * DKN_PROJ_DK; i += DKN_THREADS) {
+      const int j = i / DKN_PROJ_DK, c = i % DKN_PROJ_DK;
+      ws[j * DKN_PROJ_LD + c] = c < nd ? w1[(int64_t)j * 2 * dim + d0 + c] : 0.f;
+    }
+    __syncthreads();
+    for (int c = 0; c < nd; ++c) {
+      const float x = xs[r * DKN_PROJ_LD + c];
+#pragma unroll
+      for (int i = 0; i < NJ; ++i)
+        if (jg + 4 * i < Hd) acc[i] = fmaf(ws[(jg + 4 * i) * DKN_PROJ_LD + c], x, acc[i]);
+    }
+    __syncthreads();
+  }
+  if (n0 + r < N) {
+#pragma unroll
+    for (int i = 0; i < NJ; ++i)
+      if (jg + 4 * i < Hd) out[(n0 + r) * Hd + jg + 4 * i] = acc[i];
+  }
+}
+
 static int dkn_click_check(const NrlDknClickParams* p, int64_t B, int max_hist, int max_cand, int dim) {
   NRL_REQUIRE(p && p->att_w1 && p->att_w2 && p->pred_w1 && p->pred_b1 && p->pred_w2 && p->pred_b2, "dkn click: null parameter");
   NRL_REQUIRE(p->hidden >= 1 && p->hidden <= DKN_MAX_HID, "dkn click: hidden_dim_dnn must be in [1, 64]");
@@ -684,6 +752,34 @@ int nrl_dkn_click_fwd(const NrlDknClickParams* p, const float* hist, const int64
   if (batch == 0) return NRL_OK;
   hipLaunchKernelGGL(dkn_click_fwd_kernel, dim3((unsigned)batch), dim3(DKN_THREADS), 0, (hipStream_t)stream, *p, hist,
                      hist_offsets, cand, cand_offsets, max_cand, dim, scores, user);
+  NRL_LAUNCH_CHECK();
+  return NRL_OK;
+}
+
+int nrl_dkn_user_query(const NrlDknClickParams* p, const float* hist, const int64_t* hist_offsets, int32_t max_hist, int64_t B,
+                       int32_t dim, float* user, float* q, void* stream) {
+  NRL_TRY(dkn_click_check(p, B, max_hist, 0, dim));
+  NRL_REQUIRE(hist_offsets && user && q, "dkn user query: null hist_offsets, user or q");
+  if (B == 0) return NRL_OK;
+  hipLaunchKernelGGL(dkn_user_query_kernel, dim3((unsigned)B), dim3(DKN_THREADS), 0, (hipStream_t)stream, *p, hist, hist_offsets,
+                     dim, user, q);
+  NRL_LAUNCH_CHECK();
+  return NRL_OK;
+}
+
+int nrl_dkn_cand_project(const NrlDknClickParams* p, const float* rows, int64_t N, int32_t dim, float* out, void* stream) {
+  NRL_TRY(dkn_click_check(p, 0, 0, 0, dim));
+  NRL_REQUIRE(N >= 0 && N < ((int64_t)1 << 31), "dkn cand project: N in [0, 2^31) rows (got %lld)", (long long)N);
+  if (N == 0) return NRL_OK;
+  NRL_REQUIRE(rows && out, "dkn cand project: null rows or out");
+  const dim3 grid((unsigned)ceil_div(N, DKN_PROJ_ROWS)), block(DKN_THREADS);
+  hipStream_t st = (hipStream_t)stream;
+  if (p->hidden <= 16)
+    hipLaunchKernelGGL(dkn_cand_project_kernel<4>, grid, block, 0, st, p->pred_w1, p->hidden, rows, N, dim, out);
+  else if (p->hidden <= 32)
+    hipLaunchKernelGGL(dkn_cand_project_kernel<8>, grid, block, 0, st, p->pred_w1, p->hidden, rows, N, dim, out);
+  else
+    hipLaunchKernelGGL(dkn_cand_project_kernel<16>, grid, block, 0, st, p->pred_w1, p->hidden, rows, N, dim, out);
   NRL_LAUNCH_CHECK();
   return NRL_OK;
 }

@@ -18,6 +18,8 @@
 //   tki_scores_kernel  the same stages over the K interest rows of a user, with an aggregation between the tile and the scan.
 //   tke_*_kernel       the z-scored ensemble of up to three tables (MANNeR): a statistics pass, then the same stages over a second
 //       score tile that collects the weighted z-scores.
+//   tkr_scores_kernel  DKN's factored DNN predictor: the tile is b2 + sum_j w2[j] relu(proj[v, j] + q[u, j]) in plain fp32 vector
+//       code instead of a product; the other stages unchanged.
 //   tk_merge_kernel    one wave per user: validates the user's offsets and exclusion indices (status flags), merges the `slices`
 //       partial lists with the same insertion and writes (row, score) or (-1, -inf).
 // The stages (exclusion cache, eligibility, tile product, per-user selection, flush) are written once, as inlined device functions
@@ -729,6 +731,140 @@ __global__ __launch_bounds__(TK_THREADS) void tke_scores_kernel(TkeArgs A) {
   for (int ul = ul_begin; ul < ul_end; ++ul) tk_flush_user(lists + ul * k, A.partial + ((u0 + ul) * A.slices + sl) * k, k, lane);
 }
 
+// ---- factored DNN scores (DKN) ---------------------------------------------------------------------------------------------------
+// DKN's click predictor Linear(2 dim, Hd) -> ReLU -> Linear(Hd, 1) on [cand; user] with its first layer split by columns:
+// score(u, v) = b2 + sum_j w2[j] relu(proj[v, j] + q[u, j]), proj (V, Hd) the catalogue's share and q (B, Hd) the user's with the
+// bias (nrl_dkn_cand_project / nrl_dkn_user_query).  tk_scores_kernel with another tile producer: no GEMM, B V Hd add / select / fma.
+//   * q of the workgroup's 64 users and w2 are staged once (row stride Hd rounded up to 4: a wave reads one user's q as 16-byte
+//     broadcasts); per table tile the 128 proj rows, contiguous in memory, are staged into the LDS of the score tile with the
+//     odd row stride Hd | 1: lane l reads rows l and 64 + l at the same j, 32 lanes of a ds_read_b32 group then hit 32 banks;
+//   * wave w produces the scores of its own users 16 w ... 16 w + 15 (the ones it selects for): a lane holds 16 x 2 chains
+//     s = b2; s = fmaf(w2[j], h_j, s) in ascending j, h_j = x < 0 ? 0 : x (a NaN x stays NaN), x = proj[v, j] + q[u, j];
+//   * the proj tile is dead once every chain is complete; the scores overwrite it and the selection runs as everywhere.
+struct TkrArgs : TkArgs {                      // `user` is q, `table` is proj, D is Hd
+  const float* w2;
+  const float* b2;
+};
+
+constexpr int tkr_ldp(int Hd) { return Hd | 1; }
+constexpr int tkr_ldq(int Hd) { return (Hd + 3) & ~3; }
+constexpr size_t tkr_extra_lds(int Hd) { return (size_t)(TK_BU + 1) * tkr_ldq(Hd) * 4; }      // q rows, then w2
+static_assert(TK_BV * tkr_ldp(NRL_TOPK_MAX_HIDDEN) <= TK_BU * TK_SCLD, "the proj tile lives inside the score tile");
+static_assert(tk_lds_bytes(1, TK_BU, NRL_TOPK_MAX_K) + tkr_extra_lds(NRL_TOPK_MAX_HIDDEN) <= 160 * 1024 &&
+                  tk_lds_bytes(1, TK_BU, 1) % 16 == 0 && (TK_BU * 8) % 16 == 0,
+              "the largest layout fits, and the q rows that follow the lists are 16-byte aligned for every k");
+
+__device__ __forceinline__ float tkr_step(float w, float p, float q, float s) {
+  const float x = __fadd_rn(p, q);
+  return fmaf(w, x < 0.f ? 0.f : x, s);
+}
+
+__global__ __launch_bounds__(TK_THREADS) void tkr_scores_kernel(TkrArgs A) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char tk_smem[];
+  float* const sc = reinterpret_cast<float*>(tk_smem);                       // [TK_BU][TK_SCLD]; before: proj tile [TK_BV][ldp]
+  int32_t* const xl = reinterpret_cast<int32_t*>(sc + TK_BU * TK_SCLD);      // [TK_BU][TK_XCAP]
+  int64_t* const xs = reinterpret_cast<int64_t*>(xl + TK_BU * TK_XCAP);      // [TK_BU]
+  int32_t* const xn = reinterpret_cast<int32_t*>(xs + TK_BU);                // [TK_BU]
+  uint8_t* const el = reinterpret_cast<uint8_t*>(xn + TK_BU);                // [TK_BV]
+  unsigned long long* const lists = reinterpret_cast<unsigned long long*>(el + TK_BV);      // [TK_BU][k]
+  const int Hd = A.D, ldp = tkr_ldp(Hd), ldq = tkr_ldq(Hd);
+  float* const qs = reinterpret_cast<float*>(lists + TK_BU * A.k);           // [TK_BU][ldq], zero past Hd and past the last user
+  float* const w2s = qs + TK_BU * ldq;                                       // [ldq]
+
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int k = A.k, V = A.V;
+  const int sl = (int)(blockIdx.x % (unsigned)A.slices);
+  const int64_t u0 = (int64_t)(blockIdx.x / (unsigned)A.slices) * TK_BU;
+  const int nu = A.B - u0 < TK_BU ? (int)(A.B - u0) : TK_BU;
+  const int v_begin = sl * A.tiles_per_slice * TK_BV;
+  const int64_t v_stop = (int64_t)v_begin + (int64_t)A.tiles_per_slice * TK_BV;
+  const int v_end = v_stop < V ? (int)v_stop : V;
+  const int nvt = (v_end - v_begin + TK_BV - 1) / TK_BV;
+
+  for (int i = tid; i < TK_BU * k; i += TK_THREADS) lists[i] = 0ull;
+  for (int i = tid; i < TK_BU * ldq; i += TK_THREADS) {
+    const int ul = i / ldq, j = i - ul * ldq;
+    qs[i] = (ul < nu && j < Hd) ? A.user[(u0 + ul) * Hd + j] : 0.f;
+  }
+  for (int i = tid; i < ldq; i += TK_THREADS) w2s[i] = i < Hd ? A.w2[i] : 0.f;
+  const float b2 = A.b2[0];
+  tk_cache_exclusions(A, u0, nu, TK_BU, xs, xn, xl);
+
+  const int ul_begin = wave * TK_USERS_PER_WAVE, ul_end = ul_begin + TK_USERS_PER_WAVE < nu ? ul_begin + TK_USERS_PER_WAVE : nu;
+  // staging walk: element e = tid, tid + 256, ... of the tile is column e % Hd of tile row e / Hd
+  const int row0 = tid / Hd, col0 = tid - row0 * Hd, drow = TK_THREADS / Hd, dcol = TK_THREADS - drow * Hd;
+  const float* const p0 = sc + lane * ldp;                                   // this lane's two proj rows
+  const float* const p1 = sc + (64 + lane) * ldp;
+  const float* const qw = qs + ul_begin * ldq;                               // this wave's 16 q rows
+  bool nan = false;
+
+  for (int vt = 0; vt < nvt; ++vt) {
+    const int v0 = v_begin + vt * TK_BV;
+    tk_fill_eligible(A.eligible, v0, V, el);
+    {
+      const float* const src = A.table + (int64_t)v0 * Hd;                   // the tile's rows are contiguous
+      const int inside = (V - v0 < TK_BV ? V - v0 : TK_BV) * Hd;             // rows from V on are zero (and not eligible)
+      int row = row0, col = col0;
+      for (int e = tid; e < TK_BV * Hd; e += TK_THREADS) {
+        sc[row * ldp + col] = e < inside ? src[e] : 0.f;
+        row += drow;
+        col += dcol;
+        if (col >= Hd) {
+          col -= Hd;
+          ++row;
+        }
+      }
+    }
+    __syncthreads();
+
+    float acc[TK_USERS_PER_WAVE][2];
+#pragma unroll
+    for (int u = 0; u < TK_USERS_PER_WAVE; ++u) acc[u][0] = acc[u][1] = b2;
+    int j = 0;
+    for (; j + 4 <= Hd; j += 4) {
+      const float a0[4] = {p0[j], p0[j + 1], p0[j + 2], p0[j + 3]}, a1[4] = {p1[j], p1[j + 1], p1[j + 2], p1[j + 3]};
+      const float4 w = *reinterpret_cast<const float4*>(w2s + j);
+      const float wj[4] = {w.x, w.y, w.z, w.w};
+#pragma unroll
+      for (int u = 0; u < TK_USERS_PER_WAVE; ++u) {
+        const float4 q4 = *reinterpret_cast<const float4*>(qw + u * ldq + j);
+        const float qj[4] = {q4.x, q4.y, q4.z, q4.w};
+#pragma unroll
+        for (int t = 0; t < 4; ++t) {
+          acc[u][0] = tkr_step(wj[t], a0[t], qj[t], acc[u][0]);
+          acc[u][1] = tkr_step(wj[t], a1[t], qj[t], acc[u][1]);
+        }
+      }
+    }
+    for (; j < Hd; ++j) {
+      const float a0 = p0[j], a1 = p1[j], w = w2s[j];
+#pragma unroll
+      for (int u = 0; u < TK_USERS_PER_WAVE; ++u) {
+        const float q = qw[u * ldq + j];
+        acc[u][0] = tkr_step(w, a0, q, acc[u][0]);
+        acc[u][1] = tkr_step(w, a1, q, acc[u][1]);
+      }
+    }
+    __syncthreads();                                  // every chain is complete: the proj tile gives way to the scores
+#pragma unroll
+    for (int u = 0; u < TK_USERS_PER_WAVE; ++u) {
+      sc[(ul_begin + u) * TK_SCLD + lane] = acc[u][0];
+      sc[(ul_begin + u) * TK_SCLD + 64 + lane] = acc[u][1];
+    }
+    __syncthreads();
+
+    const bool e_0 = el[lane] != 0, e_1 = el[64 + lane] != 0;
+    for (int ul = ul_begin; ul < ul_end; ++ul)
+      tk_select_user(sc + ul * TK_SCLD, lists + ul * k, xn + ul, xs + ul, xl + ul * TK_XCAP, A.excl_idx, v0, e_0, e_1, k, lane, nan);
+    __syncthreads();                                  // the score tile and `el` are free for the next proj tile
+  }
+
+  if (nan && lane == 0) atomicOr(A.status, NRL_TOPK_E_NAN);
+  wave_lds_sync();
+  for (int ul = ul_begin; ul < ul_end; ++ul) tk_flush_user(lists + ul * k, A.partial + ((u0 + ul) * A.slices + sl) * k, k, lane);
+}
+
 static bool tk_shape_ok(int64_t B, int64_t V, int32_t D, int32_t k) {
   return B >= 0 && V >= 0 && V < ((int64_t)1 << 31) && D > 0 && D % 4 == 0 && D <= NRL_TOPK_MAX_D && k >= 1 && k <= NRL_TOPK_MAX_K;
 }
@@ -843,6 +979,26 @@ int nrl_topk_interest_scores(const float* interests, const float* gate, const fl
   A.mode = mode;
   return mode == 2 ? tk_launch("topk_interest_scores", tki_scores_kernel<true>, A, slices, 2, Ut, stream)
                    : tk_launch("topk_interest_scores", tki_scores_kernel<false>, A, slices, 1, Ut, stream);
+}
+
+int nrl_topk_relu_scores(const float* q, const float* proj, const float* w2, const float* b2, int64_t B, int64_t V, int32_t Hd,
+                         int32_t k, const int64_t* excl_idx, const int64_t* excl_off, const uint8_t* eligible, int32_t slices,
+                         int64_t* out_idx, float* out_score, int32_t* status, void* ws, size_t ws_bytes, void* stream) {
+  NRL_REQUIRE(B >= 0 && V >= 0 && slices >= 0, "topk_relu_scores: negative size");
+  NRL_REQUIRE(Hd >= 1 && Hd <= NRL_TOPK_MAX_HIDDEN, "topk_relu_scores: Hd in [1, %d] (got %d)", NRL_TOPK_MAX_HIDDEN, Hd);
+  NRL_TRY(tk_check("topk_relu_scores", B, V, 4, k, excl_idx, excl_off));      // (no D here: Hd is checked above)
+  NRL_REQUIRE(status, "topk_relu_scores: the status word is required");
+  NRL_REQUIRE(w2, "topk_relu_scores: w2 is required");
+  NRL_REQUIRE(b2, "topk_relu_scores: b2 is required (a device pointer)");
+  if (B == 0) return NRL_OK;
+  NRL_REQUIRE(out_idx && out_score && q && (V == 0 || proj), "topk_relu_scores: null argument");
+  unsigned long long* partial;
+  NRL_TRY(carve_workspace(ws, ws_bytes, [&](Arena& a) { tk_layout(a, B, V, k, slices, TK_BU, &partial); }));
+  TkrArgs A;
+  static_cast<TkArgs&>(A) = tk_args(q, proj, B, V, Hd, k, excl_idx, excl_off, eligible, partial, out_idx, out_score, status);
+  A.w2 = w2;
+  A.b2 = b2;
+  return tk_launch("topk_relu_scores", tkr_scores_kernel, A, slices, 1, TK_BU, stream, tkr_extra_lds(Hd));
 }
 
 int nrl_topk_ensemble_scores(const float* const* users, const float* const* tables, const float* weights, int32_t T, int64_t B,

@@ -31,6 +31,11 @@ from .user_encoder_dkn import UserEncoder
 
 
 class DKNModule(AbstractRecommender):
+    # the DNN click predictor's first layer splits by columns into a news half and a user half, and the user vector does not depend
+    # on the candidate (the affine attention DNN): ``evaluation.NewsVectorCache.recommend_dnn`` ranks the whole table by it.  The
+    # score is still no single dot product, so there is no ``dot_product_scorer`` and ``recommend`` refuses
+    dnn_predictor_scorer = True
+
     def __init__(
         self,
         outputs: Dict[str, List[str]],
@@ -118,3 +123,14 @@ class DKNModule(AbstractRecommender):
         cand_agg = dense_rows(cand_news_vector, batch["batch_cand"], B, batch["max_cand"], batch["cand_offsets"])
         user_vector = ops.HistMeanFn.apply(hist_agg, batch["hist_offsets"])          # :226-232, the true history size
         return self.click_predictor(user_vector.unsqueeze(dim=1), cand_agg.permute(0, 2, 1))
+
+    def user_queries(self, hist_news_vector: torch.Tensor, meta: Dict):
+        """Early fusion, from the gathered history rows and the history half of the batch metadata (``hist_offsets``,
+        ``max_hist``) -> (user (B, dim), q (B, Hd)): the candidate-independent user vector -- the one ``score_news_vectors``
+        computes -- and ``q = user Wu^T + b1``, the user's share of the click predictor's first layer
+        (``click_predictor.dnn.0.weight = [Wc | Wu]``).  The score of a news vector ``c`` is then
+        ``b2 + w2 . relu(c Wc^T + q)``.  DKN has no dropout: eval and train semantics are the same.  No gradient."""
+        if self.hparams.late_fusion:
+            raise NotImplementedError("DKN under late fusion has no DNN predictor: its score is the dot product with the history mean")
+        return ops_dkn.dkn_user_query(hist_news_vector, meta["hist_offsets"], meta["max_hist"], self.user_encoder.params(),
+                                      self.click_predictor.params())

@@ -156,10 +156,12 @@ class NewsVectorCache(_ImpressionCache):
     def __init__(self, module, table: DeviceNewsTable, chunk: int = 16384):
         self.module, self.table, self.chunk = module, table, int(chunk)
         self.vectors: Optional[torch.Tensor] = None
+        self.projection: Optional[torch.Tensor] = None      # (num_news, Hd): ``recommend_dnn``'s share of the table, built lazily
 
     @torch.no_grad()
     def build(self) -> torch.Tensor:
         """news vectors (num_news, D) of the whole table, in chunks (the encoder workspace is O(rows))."""
+        self.projection = None
         if getattr(self.module, "user_dependent_news_vectors", False):
             raise NotImplementedError("this recommender's news vectors depend on the user (NPA's personalized attention, "
                                       "text.py:385-390): they cannot be cached; NpaFeatureCache caches what does not "
@@ -232,8 +234,9 @@ class NewsVectorCache(_ImpressionCache):
             raise NotImplementedError(
                 f"{type(self.module).__name__} does not score a news by one dot product with a candidate-independent user vector "
                 "(no `dot_product_scorer`): its user representation or its predictor depends on the candidate (MINER's "
-                "poly-attention scores, CAUM's candidate-aware encoder, DKN's attention + DNN, SentiDebias' generator), so "
-                "the whole table cannot be ranked by one GEMM + top-k")
+                "poly-attention scores, CAUM's candidate-aware encoder, DKN's DNN predictor, SentiDebias' generator), so "
+                "the whole table cannot be ranked by one GEMM + top-k; MINER is served by `recommend_interests`, DKN (whose "
+                "user vector does not depend on the candidate and whose DNN factors) by `recommend_dnn`")
         if not hist_idx.is_cuda:
             raise RuntimeError(f"newsreclib_amd: `hist_idx` must live on the GPU (got {hist_idx.device}); there is no CPU path")
         if self.vectors is None:
@@ -276,6 +279,45 @@ class NewsVectorCache(_ImpressionCache):
         excl = (hist_idx, meta["hist_offsets"]) if exclude_history else (None, None)
         return ops.topk_interest_scores(interests, self.vectors, k, self.module.interest_score_mode, gate, excl[0], excl[1],
                                         eligible.to(dev) if eligible is not None else None)
+
+    @torch.no_grad()
+    def recommend_dnn(self, hist_idx: torch.Tensor, hist_sizes: torch.Tensor, k: int, user_idx: Optional[torch.Tensor] = None,
+                      exclude_history: bool = True, eligible: Optional[torch.Tensor] = None):
+        """``recommend`` for a module that scores ``[news; user]`` with a DNN whose first layer splits by columns and whose user
+        vector does not depend on the candidate (``dnn_predictor_scorer``: DKN) -> (news_idx (B, k) int64, scores (B, k) fp32,
+        status).  Early fusion: the module's ``user_queries`` over the gathered history vectors gives every user's share ``q`` of
+        the first layer, and ``ops.topk_relu_scores`` ranks ``b2 + w2 . relu(P[v] + q[u])`` against ``projection``
+        ``P = vectors Wc^T`` (num_news, Hd).  ``P`` is built from ``vectors`` at the first call and dropped by ``build()``; like
+        ``vectors`` it is a SNAPSHOT of the weights at that moment: after they change, call ``build()`` again (nothing is keyed on
+        them).  ``w2``, ``b2`` and the user half are read from the module at every call.  Late fusion (a dot product with the
+        history mean): ``ops.topk_scores`` against ``vectors``.  Same contract as ``recommend``: ``hist_idx`` on the GPU,
+        ``hist_sizes`` on the host, nothing read back."""
+        if not getattr(self.module, "dnn_predictor_scorer", False):
+            raise NotImplementedError(
+                f"{type(self.module).__name__} has no DNN click predictor over a candidate-independent user vector (no "
+                "`dnn_predictor_scorer`); a module that scores by one dot product with a user vector (`dot_product_scorer`) is "
+                "served by `recommend`, one with interest vectors (`multi_interest_scorer`) by `recommend_interests`")
+        if not hist_idx.is_cuda:
+            raise RuntimeError(f"newsreclib_amd: `hist_idx` must live on the GPU (got {hist_idx.device}); there is no CPU path")
+        if self.vectors is None:
+            self.build()
+        dev = self.table.device
+        hist_idx = hist_idx.to(dev).long()
+        meta = self._user_meta(hist_sizes, user_idx)
+        hv = ops.embedding_gather(self.vectors, hist_idx.reshape(-1, 1)).reshape(-1, self.vectors.shape[1])
+        excl = (hist_idx, meta["hist_offsets"]) if exclude_history else (None, None)
+        eligible = eligible.to(dev) if eligible is not None else None
+        if self.module.hparams.late_fusion:
+            dense = dense_rows(hv, meta["batch_hist"], meta["batch_size"], meta["max_hist"], meta["hist_offsets"])
+            user = ops.HistMeanFn.apply(dense, meta["hist_offsets"])
+            return ops.topk_scores(user, self.vectors, k, excl[0], excl[1], eligible)
+        from . import ops_dkn
+        pred = self.module.click_predictor.params()
+        if self.projection is None:
+            self.projection = ops_dkn.dkn_cand_project(self.vectors, pred)
+        with eval_mode(self.module):
+            _, q = self.module.user_queries(hv, meta)
+        return ops.topk_relu_scores(q, self.projection, pred[2], pred[3], k, excl[0], excl[1], eligible)
 
 
 class MannerVectorCache(_ImpressionCache):
@@ -465,6 +507,7 @@ def format_recommendations(user_ids: Sequence, news_idx: torch.Tensor, scores: t
 def recommend_users(cache: NewsVectorCache, users: Sequence[Dict], k: int, batch_size: int = 512,
                     eligible: Optional[torch.Tensor] = None) -> Dict[str, Dict[str, float]]:
     """``cache.recommend`` (``cache.recommend_interests`` where the cache's module is a ``multi_interest_scorer``,
+    ``cache.recommend_dnn`` where it is a ``dnn_predictor_scorer``,
     ``cache.recommend_ensemble`` where the cache has one: ``MannerVectorCache``) over a list of
     users ({"hist": idx tensor[, "user_idx", "user_id"]}) in batches -> the recommendation dictionary of ``format_recommendations``.  ``user_id`` defaults to the user's position in the list + 1 (as ``build_batch``);
     news ids come from the table's ``news_ids`` column when it has one.  One device-to-host copy per batch, at its end; a status
@@ -477,7 +520,8 @@ def recommend_users(cache: NewsVectorCache, users: Sequence[Dict], k: int, batch
         hs = torch.tensor([len(u["hist"]) for u in chunk])
         hist = torch.cat([torch.as_tensor(u["hist"]).long() for u in chunk]).to(dev)
         uidx = torch.stack([torch.as_tensor(u["user_idx"]) for u in chunk]) if "user_idx" in chunk[0] else None
-        rank = cache.recommend_interests if getattr(cache.module, "multi_interest_scorer", False) else cache.recommend
+        rank = cache.recommend_interests if getattr(cache.module, "multi_interest_scorer", False) else \
+            cache.recommend_dnn if getattr(cache.module, "dnn_predictor_scorer", False) else cache.recommend
         rank = getattr(cache, "recommend_ensemble", rank)
         idx, score, status = rank(hist, hs, k, user_idx=uidx, eligible=eligible)
         packed = torch.cat([idx.double(), score.double(), status.double().expand(idx.shape[0], 1)], dim=1).cpu()      # the one copy

@@ -854,3 +854,38 @@ def topk_ensemble_scores(users: Sequence[torch.Tensor], tables: Sequence[torch.T
                                             idx.data_ptr(), score.data_ptr(), stats.data_ptr(), moments.data_ptr(),
                                             status.data_ptr(), ws.data_ptr(), ws.numel(), _stream()), "nrl_topk_ensemble_scores")
     return idx, score, status, stats
+
+
+TOPK_MAX_HIDDEN = 64
+
+
+def topk_relu_scores(q: torch.Tensor, proj: torch.Tensor, w2: torch.Tensor, b2: torch.Tensor, k: int,
+                     excl_idx: Optional[torch.Tensor] = None, excl_off: Optional[torch.Tensor] = None,
+                     eligible: Optional[torch.Tensor] = None, slices: int = 0):
+    """``nrl_topk_relu_scores``: ``topk_scores`` by DKN's DNN click predictor with its first layer split by columns: the score of
+    table row ``v`` for user ``u`` is ``b2 + sum_j w2[j] * relu(proj[v, j] + q[u, j])`` with ``q`` (B, Hd) the user's share and the
+    bias (``ops_dkn.dkn_user_query``) and ``proj`` (V, Hd) the table's (``ops_dkn.dkn_cand_project``); ``w2`` (Hd values) and
+    ``b2`` (one value) are the second layer's parameters, on the device.  Hd in [1, 64].  -> (idx (B, k) int64, score (B, k)
+    fp32, status (1) int32) with the ordering, exclusion, eligibility and status flags of ``topk_scores``; neither the (B, V) nor
+    the (B, V, Hd) array is materialised.  The workspace is sized by ``nrl_topk_scores_workspace_bytes(B, V, 4, k, slices)``: the
+    partial lists are those of ``topk_scores``, whose size does not depend on D.  Nothing here synchronises with the host."""
+    lib = _lib.load()
+    if q.dim() != 2 or proj.dim() != 2 or q.shape[1] != proj.shape[1] or w2.numel() != q.shape[1] or b2.numel() != 1:
+        raise ValueError(f"newsreclib_amd: q (B, Hd), proj (V, Hd), w2 (Hd) and b2 (1) expected, got {tuple(q.shape)}, "
+                         f"{tuple(proj.shape)}, {tuple(w2.shape)} and {tuple(b2.shape)}")
+    q, proj = _chk(q, torch.float32, "q"), _chk(proj, torch.float32, "proj")
+    w2, b2 = _chk(w2, torch.float32, "w2"), _chk(b2, torch.float32, "b2")
+    B, Hd, V, k = int(q.shape[0]), int(q.shape[1]), int(proj.shape[0]), int(k)
+    if not 1 <= Hd <= TOPK_MAX_HIDDEN:
+        raise NotImplementedError(f"newsreclib_amd: topk_relu_scores takes a hidden width in [1, {TOPK_MAX_HIDDEN}] (got {Hd})")
+    excl_idx, excl_off, eligible = _topk_masks(excl_idx, excl_off, eligible, B, V)
+    dev = q.device
+    idx = torch.empty((B, max(k, 0)), dtype=torch.int64, device=dev)
+    score = torch.empty((B, max(k, 0)), dtype=torch.float32, device=dev)
+    status = torch.zeros(1, dtype=torch.int32, device=dev)
+    ws = workspace(lib.nrl_topk_scores_workspace_bytes(B, V, 4, k, int(slices)), dev)
+    ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
+    _lib.check(lib.nrl_topk_relu_scores(q.data_ptr(), proj.data_ptr(), w2.data_ptr(), b2.data_ptr(), B, V, Hd, k, ptr(excl_idx),
+                                        ptr(excl_off), ptr(eligible), int(slices), idx.data_ptr(), score.data_ptr(),
+                                        status.data_ptr(), ws.data_ptr(), ws.numel(), _stream()), "nrl_topk_relu_scores")
+    return idx, score, status

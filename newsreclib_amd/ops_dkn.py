@@ -156,3 +156,52 @@ class DknClickFn(GradAwareFunction):
                                          user.data_ptr(), d_scores.data_ptr(), d_hist.data_ptr(), d_cand.data_ptr(),
                                          ws.data_ptr(), ws.numel(), _stream()), "nrl_dkn_click_bwd")
         return (d_hist, None, None, d_cand, None, None, *rets)
+
+
+# ---- the click predictor factored for a full-catalogue ranking (ops.topk_relu_scores) -------------------------------------------
+def _pred_params(pred: Sequence[torch.Tensor], dim: int):
+    pred = [_chk(t, torch.float32, "click_predictor.dnn") for t in pred]
+    Hd = pred[0].shape[0]
+    if pred[0].shape != (Hd, 2 * dim) or pred[1].numel() != Hd or pred[2].numel() != Hd or pred[3].numel() != 1:
+        raise ValueError("newsreclib_amd: inconsistent DKN click-predictor shapes")
+    return pred, int(Hd)
+
+
+def dkn_user_query(hist: torch.Tensor, hist_offsets: torch.Tensor, max_hist: int, att: Sequence[torch.Tensor],
+                   pred: Sequence[torch.Tensor]):
+    """``nrl_dkn_user_query``: hist (n_hist, dim) with hist_offsets (B + 1) -> (user (B, dim), q (B, Hd)).  ``user`` is the DKN
+    user vector, the bits ``DknClickFn`` computes for the same histories; ``q = user Wu^T + b1`` is the user's share of the click
+    predictor's first layer (``pred[0] = [Wc | Wu]``).  An empty history gives ``user = 0`` and ``q = b1``.  No gradient."""
+    lib = _lib.load()
+    hist = _chk(hist, torch.float32, "hist_news_vector")
+    hist_offsets = _chk(hist_offsets, torch.int64, "hist_offsets")
+    if hist.dim() != 2 or hist_offsets.dim() != 1 or hist_offsets.numel() < 1:
+        raise ValueError("newsreclib_amd: hist (n_hist, dim) and hist_offsets (B + 1) expected")
+    B, dim = int(hist_offsets.numel()) - 1, int(hist.shape[1])
+    att = [_chk(t, torch.float32, "user_encoder.dnn") for t in att]
+    pred, Hd = _pred_params(pred, dim)
+    if att[0].shape != (Hd, 2 * dim) or att[2].numel() != Hd:
+        raise ValueError("newsreclib_amd: inconsistent DKN user-encoder / click-predictor shapes")
+    user = torch.empty((B, dim), dtype=torch.float32, device=hist.device)
+    q = torch.empty((B, Hd), dtype=torch.float32, device=hist.device)
+    p = _click_params(att, pred)
+    _lib.check(lib.nrl_dkn_user_query(ctypes.byref(p), hist.data_ptr(), hist_offsets.data_ptr(), int(max_hist), B, dim,
+                                      user.data_ptr(), q.data_ptr(), _stream()), "nrl_dkn_user_query")
+    return user, q
+
+
+def dkn_cand_project(rows: torch.Tensor, pred: Sequence[torch.Tensor]) -> torch.Tensor:
+    """``nrl_dkn_cand_project``: rows (N, dim) -> (N, Hd) = rows Wc^T, the news' share of the click predictor's first layer
+    (``pred[0] = [Wc | Wu]``), without the bias.  A row's result does not depend on the other rows.  No gradient."""
+    lib = _lib.load()
+    rows = _chk(rows, torch.float32, "rows")
+    if rows.dim() != 2:
+        raise ValueError("newsreclib_amd: rows (N, dim) expected")
+    N, dim = int(rows.shape[0]), int(rows.shape[1])
+    pred, Hd = _pred_params(pred, dim)
+    out = torch.empty((N, Hd), dtype=torch.float32, device=rows.device)
+    # (the attention half of the parameter struct is not read by this entry: the predictor's own tensors stand in)
+    p = _click_params(pred, pred)
+    _lib.check(lib.nrl_dkn_cand_project(ctypes.byref(p), rows.data_ptr(), N, dim, out.data_ptr(), _stream()),
+               "nrl_dkn_cand_project")
+    return out

@@ -1,0 +1,471 @@
+"""Full-catalogue top-k by DKN's factored DNN click predictor (``nrl_dkn_user_query`` / ``nrl_dkn_cand_project`` /
+``nrl_topk_relu_scores``, ``ops.topk_relu_scores``, ``NewsVectorCache.recommend_dnn``).
+
+Expected values are computed on the CPU in float64 (tests/topk_dnn_ref.py).  Small-integer ``q``, ``proj``, ``w2``, ``b2`` in
+[-4, 4] make every operation exact (|score| <= 4 + 64 * 4 * 8), so those cases compare with ``torch.equal``.  Real-valued cases
+use the derived bound of that module and its floor form: the gap between a user's k-th and (k + 1)-th score can be below the
+bound, so row sets are never compared with float64."""
+import ctypes
+import functools
+
+import numpy as np
+import pytest
+import torch
+
+from tests import topk_dnn_ref as R
+
+pytestmark = pytest.mark.gpu
+
+E_EXCLUDE, E_OFFSETS, E_NAN = 1, 2, 4
+
+
+@pytest.fixture(autouse=True, params=["f32", "bf16x3"])
+def engine(request):
+    from newsreclib_amd import _lib
+    prev = _lib.get_gemm_engine()
+    _lib.set_gemm_engine(request.param)
+    yield request.param
+    _lib.set_gemm_engine(prev)
+
+
+@functools.lru_cache(maxsize=None)
+def _int_case(seed, B, V, Hd):
+    """(q, proj, w2, b2, float64 scores); shared, never modified."""
+    g = torch.Generator().manual_seed(seed)
+    r = lambda *shape: torch.randint(-4, 5, shape, generator=g).float()  # noqa: E731
+    q, proj, w2, b2 = r(B, Hd), r(V, Hd), r(1, Hd), r(1)
+    return q, proj, w2, b2, R.relu_scores64(q, proj, w2, b2)
+
+
+def _ragged(lists):
+    off = torch.tensor([0] + [len(x) for x in lists]).cumsum(0)
+    idx = torch.tensor([v for x in lists for v in x], dtype=torch.int64)
+    return idx, off
+
+
+def _run(q, proj, w2, b2, k, excl=None, eligible=None, slices=0, off=None):
+    from newsreclib_amd import ops
+    ei = eo = None
+    if excl is not None:
+        ei, eo = _ragged(excl)
+        ei, eo = ei.cuda(), (off if off is not None else eo).cuda()
+    idx, score, status = ops.topk_relu_scores(q.cuda(), proj.cuda(), w2.cuda(), b2.cuda(), k, ei, eo,
+                                              eligible.cuda() if eligible is not None else None, slices)
+    return idx.cpu(), score.cpu(), int(status)
+
+
+# ---- 1. exact, with ties --------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("k", [1, 10, 128])
+@pytest.mark.parametrize("Hd", [1, 3, 16, 50, 64])
+def test_exact_with_ties(Hd, k):
+    """Three user tiles (the last of 2 users), eight table tiles (the last of 104 rows), every slicing."""
+    q, proj, w2, b2, s = _int_case(100 + Hd, 130, 1000, Hd)
+    want_idx, want_score = R.ranking(s, k)
+    for slices in (0, 1, 2, 7):
+        idx, score, status = _run(q, proj, w2, b2, k, slices=slices)
+        assert status == 0, slices
+        assert torch.equal(idx, want_idx), slices
+        assert torch.equal(score, want_score), slices
+
+
+@pytest.mark.parametrize("slices", [0, 2])
+def test_all_equal_scores_return_the_first_rows(slices):
+    q, proj, w2, b2 = torch.ones(3, 6), torch.ones(300, 6) * 2, torch.ones(1, 6), torch.tensor([-1.0])
+    idx, score, status = _run(q, proj, w2, b2, 16, slices=slices)
+    assert status == 0
+    assert torch.equal(idx, torch.arange(16).expand(3, 16))
+    assert torch.equal(score, torch.full((3, 16), 17.0))
+
+
+def test_fewer_rows_than_k_and_an_empty_table():
+    q, proj, w2, b2, s = _int_case(7, 3, 5, 16)
+    idx, score, status = _run(q, proj, w2, b2, 8)
+    want_idx, want_score = R.ranking(s, 8)
+    assert status == 0 and torch.equal(idx, want_idx) and torch.equal(score, want_score)
+    assert bool((idx[:, 5:] == -1).all()) and bool((score[:, 5:] == float("-inf")).all()) and bool((idx[:, :5] >= 0).all())
+    idx, score, status = _run(q, proj[:0], w2, b2, 8)
+    assert status == 0 and bool((idx == -1).all()) and bool((score == float("-inf")).all())
+
+
+# ---- 2. exclusion and eligibility --------------------------------------------------------------------------------------------------
+def _excl_case():
+    B, V, Hd, k = 5, 40, 12, 16
+    q, proj, w2, b2, s = _int_case(91, B, V, Hd)
+    eligible = torch.ones(V, dtype=torch.uint8)
+    eligible[[0, 7, 8, 31]] = 0
+    first = R.ranking(R.mask(s, None, eligible), k)[0][:, 0]           # every user's would-be first place
+    everything = [v for v in range(V) if eligible[v]]
+    excl = [[], [3, 3, 9, 3, 9], [int(first[2]), 5], everything, [int(first[4])] * 3 + [39, 1]]
+    return (q, proj, w2, b2), s, k, excl, eligible
+
+
+@pytest.mark.parametrize("slices", [0, 1])
+def test_exclusion_and_eligibility(slices):
+    ops_in, s, k, excl, eligible = _excl_case()
+    idx, score, status = _run(*ops_in, k, excl, eligible, slices)
+    want_idx, want_score = R.ranking(R.mask(s, excl, eligible), k)
+    assert status == 0
+    assert torch.equal(idx, want_idx) and torch.equal(score, want_score)
+    assert torch.equal(idx[3], torch.full((k,), -1)) and bool(torch.isinf(score[3]).all())
+    for b in range(len(excl)):
+        got = set(idx[b].tolist()) - {-1}
+        assert not (got & set(excl[b])) and not (got & {0, 7, 8, 31})
+
+
+def test_exclusion_list_longer_than_the_cached_part():
+    """Lists beyond the 64 entries a workgroup caches are read from global memory: 150 entries and duplicates, several tiles."""
+    B, V, Hd, k = 3, 700, 7, 20
+    q, proj, w2, b2, s = _int_case(5, B, V, Hd)
+    g = torch.Generator().manual_seed(3)
+    best = R.ranking(s, 150)[0][2].tolist()
+    excl = [torch.randperm(V, generator=g)[:150].tolist(), [], best + best[:40]]
+    idx, score, status = _run(q, proj, w2, b2, k, excl, slices=3)
+    want_idx, want_score = R.ranking(R.mask(s, excl), k)
+    assert status == 0 and torch.equal(idx, want_idx) and torch.equal(score, want_score)
+
+
+# ---- 3. status word ----------------------------------------------------------------------------------------------------------------
+def test_status_bad_exclusion_index_is_ignored():
+    ops_in, s, k, excl, eligible = _excl_case()
+    bad = [list(x) for x in excl]
+    bad[1] = [-1] + bad[1]
+    bad[2] = bad[2] + [s.shape[1]]
+    idx, score, status = _run(*ops_in, k, bad, eligible)
+    want_idx, want_score = R.ranking(R.mask(s, excl, eligible), k)
+    assert status == E_EXCLUDE
+    assert torch.equal(idx, want_idx) and torch.equal(score, want_score)
+
+
+def test_status_decreasing_offsets_blank_that_user_alone():
+    q, proj, w2, b2, s = _int_case(17, 4, 40, 12)
+    k, flat = 6, list(range(12))
+    off = torch.tensor([0, 5, 3, 8, 12])                    # user 1 runs backwards
+    idx, score, status = _run(q, proj, w2, b2, k, [flat], off=off)
+    assert status == E_OFFSETS
+    want_idx, want_score = R.ranking(R.mask(s, [flat[0:5], [], flat[3:8], flat[8:12]]), k)
+    for b in (0, 2, 3):
+        assert torch.equal(idx[b], want_idx[b]) and torch.equal(score[b], want_score[b])
+    assert torch.equal(idx[1], torch.full((k,), -1)) and bool((score[1] == float("-inf")).all())
+
+
+def test_status_offsets_beyond_the_list():
+    q, proj, w2, b2, s = _int_case(18, 3, 40, 12)
+    k = 6
+    idx, score, status = _run(q, proj, w2, b2, k, [list(range(6))], off=torch.tensor([0, 2, 9, 6]))
+    assert status == E_OFFSETS
+    want_idx, _ = R.ranking(R.mask(s, [[0, 1], [], []]), k)
+    assert torch.equal(idx[0], want_idx[0])
+    assert torch.equal(idx[1:], torch.full((2, k), -1))
+
+
+def test_status_nan_row_is_left_out():
+    """A NaN in one proj row passes through x < 0 ? 0 : x (fmaxf would hide it): flagged, and the row is left out."""
+    q, proj, w2, b2, s = _int_case(23, 5, 300, 12)
+    k = 9
+    w2 = w2.abs() + 1                                       # every w2[j] != 0, so the NaN reaches every user's score
+    s = R.relu_scores64(q, proj, w2, b2)
+    clean_idx, clean_score, status = _run(q, proj, w2, b2, k, slices=2)
+    assert status == 0 and torch.equal(clean_idx, R.ranking(s, k)[0])
+    nan_row = int(clean_idx[0, 0])                          # a row that would be returned
+    pn = proj.clone()
+    pn[nan_row, 3] = float("nan")
+    idx, score, status = _run(q, pn, w2, b2, k, slices=2)
+    assert status == E_NAN
+    assert not bool((idx == nan_row).any())
+    elig = torch.ones(300, dtype=torch.uint8)
+    elig[nan_row] = 0
+    want_idx, want_score = R.ranking(R.mask(s, None, elig), k)          # every other position unchanged
+    assert torch.equal(idx, want_idx) and torch.equal(score, want_score)
+    # not eligible: nobody is told
+    idx, score, status = _run(q, pn, w2, b2, k, eligible=elig, slices=2)
+    assert status == 0 and torch.equal(idx, want_idx) and torch.equal(score, want_score)
+
+
+# ---- 4. real values against float64, through the chain -----------------------------------------------------------------------------
+def test_real_values_against_float64():
+    """dkn_cand_project + dkn_user_query + topk_relu_scores from random history rows and weights; the float64 reference and the
+    bound start from the fp32 user vectors the chain itself reports (compared bit for bit with the click kernel's below)."""
+    from newsreclib_amd import ops, ops_dkn
+    c, k = R.real_case(), R.REAL["k"]
+    att, pred = [t.cuda() for t in c["att"]], [t.cuda() for t in c["pred"]]
+    proj = ops_dkn.dkn_cand_project(c["table"].cuda(), pred)
+    user, q = ops_dkn.dkn_user_query(c["hist"].cuda(), c["off"].cuda(), int(c["sizes"].max()), att, pred)
+    ei, eo = _ragged(c["excl"])
+    idx, score, status = ops.topk_relu_scores(q, proj, pred[2], pred[3], k, ei.cuda(), eo.cuda())
+    assert int(status) == 0
+    user = user.cpu()
+    assert bool((user[3] == 0).all()) and torch.equal(q[3].cpu(), c["pred"][1])          # the empty history: u = 0, q = b1
+    raw, bound = R.scores64(user, c["table"], c["pred"])
+    R.check_floor(idx.cpu(), score.cpu(), raw, bound, R.mask(raw, c["excl"]), c["excl"], k)
+
+
+# ---- 5. the user vector is the click kernel's -------------------------------------------------------------------------------------
+def _click_fwd_user(hist, off, max_hist, att, pred):
+    """``user`` of nrl_dkn_click_fwd for the same histories (one candidate row per impression)."""
+    from newsreclib_amd import _lib, ops_dkn
+    from newsreclib_amd.ops import _stream
+    lib = _lib.load()
+    B, dim = off.numel() - 1, hist.shape[1]
+    cand = torch.zeros(B, dim, device="cuda")
+    coff = torch.arange(B + 1, device="cuda")
+    scores, user = torch.empty(B, 1, device="cuda"), torch.empty(B, dim, device="cuda")
+    p = ops_dkn._click_params(att, pred)
+    _lib.check(lib.nrl_dkn_click_fwd(ctypes.byref(p), hist.data_ptr(), off.data_ptr(), max_hist, cand.data_ptr(), coff.data_ptr(), B, 1,
+                                     dim, scores.data_ptr(), user.data_ptr(), _stream()), "nrl_dkn_click_fwd")
+    return user
+
+
+@pytest.mark.parametrize("dim,Hd,sizes", [(24, 16, [3, 0, 1, 7, 2]), (400, 16, [50, 1, 0, 13]), (37, 5, [1, 1, 0, 1]), (1024, 64, [2, 9])])
+def test_user_output_is_the_click_forwards(dim, Hd, sizes):
+    """Ragged histories with an empty one; max_hist = 1; the widest rows."""
+    from newsreclib_amd import ops_dkn
+    g = torch.Generator().manual_seed(dim + Hd)
+    att, pred = R.make_weights(g, dim, Hd)
+    att, pred = [t.cuda() for t in att], [t.cuda() for t in pred]
+    hist = torch.randn(sum(sizes), dim, generator=g).cuda()
+    off = torch.tensor([0] + sizes).cumsum(0).cuda()
+    user, q = ops_dkn.dkn_user_query(hist, off, max(sizes), att, pred)
+    assert torch.equal(user, _click_fwd_user(hist, off, max(sizes), att, pred))
+    if 0 in sizes:
+        empty = sizes.index(0)
+        assert bool((user[empty] == 0).all()) and torch.equal(q[empty], pred[1])
+    # q against float64 from the fp32 user vector: one dot product of length dim and the bias
+    w1, b1 = pred[0].double().cpu(), pred[1].double().cpu()
+    u64 = user.double().cpu()
+    want = u64 @ w1[:, dim:].T + b1
+    bound = (dim + 1) * R.EPS * (u64.abs() @ w1[:, dim:].abs().T + b1.abs())
+    assert bool(((q.double().cpu() - want).abs() <= bound).all())
+
+
+# ---- 6. invariance and determinism ---------------------------------------------------------------------------------------------------
+def test_invariance_and_determinism():
+    """Bit-equal rows and scores whatever the slicing, the batch (all 130 users one at a time), the GEMM engine setting (both are
+    set here, inside the one test, on top of the fixture's) and on a second run; a row slice of dkn_cand_project equals the slice
+    of the full result."""
+    from newsreclib_amd import _lib, ops, ops_dkn
+    B, V, dim, Hd, k = 130, 1000, 100, 13, 10
+    g = torch.Generator().manual_seed(31)
+    att, pred = R.make_weights(g, dim, Hd)
+    att, pred = [t.cuda() for t in att], [t.cuda() for t in pred]
+    table = torch.randn(V, dim, generator=g).cuda()
+    sizes = torch.randint(0, 6, (B,), generator=g)
+    hist = torch.randn(int(sizes.sum()), dim, generator=g).cuda()
+    off = torch.cat([torch.zeros(1, dtype=torch.int64), torch.cumsum(sizes, 0)]).cuda()
+    bits = lambda t: t.view(torch.int32)  # noqa: E731
+
+    def chain():
+        proj = ops_dkn.dkn_cand_project(table, pred)
+        user, q = ops_dkn.dkn_user_query(hist, off, 5, att, pred)
+        return proj, user, q
+
+    proj, user, q = chain()
+    for lo, hi in ((0, 1), (63, 65), (129, 700), (999, 1000), (0, 0)):
+        assert torch.equal(bits(ops_dkn.dkn_cand_project(table[lo:hi], pred)), bits(proj[lo:hi])), (lo, hi)
+    base_idx, base_score, _ = ops.topk_relu_scores(q, proj, pred[2], pred[3], k)
+    for slices in (1, 2, 7, 0):
+        idx, score, status = ops.topk_relu_scores(q, proj, pred[2], pred[3], k, slices=slices)
+        assert int(status) == 0
+        assert torch.equal(idx, base_idx) and torch.equal(bits(score), bits(base_score)), slices
+    singles = [ops.topk_relu_scores(q[b:b + 1], proj, pred[2], pred[3], k) for b in range(B)]
+    assert all(int(s[2]) == 0 for s in singles)
+    assert torch.equal(torch.cat([s[0] for s in singles]), base_idx)
+    assert torch.equal(bits(torch.cat([s[1] for s in singles])), bits(base_score))
+    one_user, one_q = ops_dkn.dkn_user_query(hist[int(off[7]):int(off[8])], off[7:9] - off[7], 5, att, pred)
+    assert torch.equal(bits(one_user), bits(user[7:8])) and torch.equal(bits(one_q), bits(q[7:8]))
+    prev = _lib.get_gemm_engine()
+    try:
+        for name in ("f32", "bf16x3"):
+            _lib.set_gemm_engine(name)
+            p2, u2, q2 = chain()
+            assert torch.equal(bits(p2), bits(proj)) and torch.equal(bits(u2), bits(user)) and torch.equal(bits(q2), bits(q)), name
+            idx, score, _ = ops.topk_relu_scores(q2, p2, pred[2], pred[3], k)
+            assert torch.equal(idx, base_idx) and torch.equal(bits(score), bits(base_score)), name
+    finally:
+        _lib.set_gemm_engine(prev)
+
+
+# ---- 7. memory -------------------------------------------------------------------------------------------------------------------------
+def test_peak_memory_is_far_below_the_hidden_activations():
+    from newsreclib_amd import ops
+    B, V, Hd, k = 512, 65536, 16, 10
+    g = torch.Generator().manual_seed(2)
+    q, proj = torch.randn(B, Hd, generator=g).cuda(), torch.randn(V, Hd, generator=g).cuda()
+    w2, b2 = torch.randn(1, Hd, generator=g).cuda(), torch.randn(1, generator=g).cuda()
+    ops.topk_relu_scores(q[:2], proj[:256], w2, b2, k)      # library loaded, kernels resident
+    torch.cuda.synchronize()
+    torch.cuda.reset_peak_memory_stats()
+    live = torch.cuda.memory_allocated()
+    out = ops.topk_relu_scores(q, proj, w2, b2, k)
+    torch.cuda.synchronize()
+    peak = torch.cuda.max_memory_allocated() - live
+    print(f"peak above the inputs: {peak} bytes; (B, V, Hd) activations: {B * V * Hd * 4} bytes")
+    assert peak < B * V * Hd * 4 / 100
+    assert int(out[2]) == 0 and bool((out[0] >= 0).all())
+
+
+# ---- 8. no read-back ---------------------------------------------------------------------------------------------------------------------
+def _sync_debug_honoured():
+    try:
+        float(torch.ones(1, device="cuda").sum())
+    except RuntimeError:
+        return True
+    return False
+
+
+def test_topk_relu_scores_does_not_synchronise_with_the_host():
+    from newsreclib_amd import ops
+    q, proj, w2, b2, _ = _int_case(3, 5, 200, 12)
+    q, proj, w2, b2 = q.cuda(), proj.cuda(), w2.cuda(), b2.cuda()
+    ei, eo = _ragged([[1, 2], [], [5], [7, 7], []])
+    ei, eo, elig = ei.cuda(), eo.cuda(), torch.ones(200, dtype=torch.uint8).cuda()
+    torch.cuda.synchronize()
+    torch.cuda.set_sync_debug_mode("error")
+    try:
+        if not _sync_debug_honoured():
+            pytest.skip("this torch build does not raise on synchronising calls under set_sync_debug_mode('error')")
+        idx, score, status = ops.topk_relu_scores(q, proj, w2, b2, 4, ei, eo, elig)
+    finally:
+        torch.cuda.set_sync_debug_mode("default")
+    assert int(status) == 0 and idx.shape == (5, 4)
+
+
+# ---- 9. wiring -----------------------------------------------------------------------------------------------------------------------------
+def _tiny(late_fusion=False, n_news=50, Hd=6):
+    """(DKNModule in eval mode, table attributes) from the synthetic builders of the DKN tests: dim = 24."""
+    from tests import dkn_oracle as DO
+    cfg = dict(vocab=120, n_ent=30, D=16, Ed=8, F=8, Hd=Hd, windows=[1, 2, 3], use_context=True, late_fusion=late_fusion)
+    params = DO.make_dkn_params(cfg["vocab"], cfg["n_ent"], cfg["D"], cfg["Ed"], cfg["F"], cfg["windows"], Hd,
+                                use_context=True, late_fusion=late_fusion, seed=8)
+    rng = np.random.default_rng(11)
+    attrs = {"title": torch.from_numpy(rng.integers(1, cfg["vocab"], (n_news, 12))),
+             "title_entities": torch.from_numpy(rng.integers(0, cfg["n_ent"], (n_news, 12)))}
+    return DO.build_module(cfg, params).eval(), attrs
+
+
+def _hist_batch(n_news, B=6, seed=3):
+    rng = np.random.default_rng(seed)
+    sizes = rng.integers(1, 9, B)
+    hist = [torch.from_numpy(rng.choice(np.arange(1, n_news), int(n), replace=False)) for n in sizes]
+    return hist, torch.cat(hist), torch.tensor([len(h) for h in hist])
+
+
+def _click_bound(user, vec, pred):
+    """float64 score (B, V) of the UNFACTORED predictor from fp32 user / news vectors and the fp32 bound of nrl_dkn_click_fwd:
+    every pre[j] one dot product of length 2 dim and the bias, then the same chain."""
+    dim = vec.shape[1]
+    w1, b1, w2, b2 = [t.double() for t in pred]
+    Hd, w2 = w1.shape[0], w2.reshape(-1)
+    user, vec = user.double(), vec.double()
+    score, bound = torch.empty(user.shape[0], vec.shape[0], dtype=torch.float64), torch.empty(user.shape[0], vec.shape[0], dtype=torch.float64)
+    for b in range(user.shape[0]):
+        x = torch.cat([vec, user[b].expand(vec.shape[0], dim)], dim=1)
+        pre = x @ w1.T + b1
+        e_pre = (2 * dim + 1) * R.EPS * (x.abs() @ w1.abs().T + b1.abs())
+        h = torch.relu(pre)
+        score[b] = h @ w2 + b2
+        bound[b] = e_pre @ w2.abs() + (Hd + 1) * R.EPS * (h @ w2.abs() + b2.abs())
+    return score, bound
+
+
+def test_recommend_dnn_against_the_cache_scores():
+    """Early fusion: the factored ranking against ``cache.scores`` (the unfactored nrl_dkn_click_fwd) over the whole small table."""
+    from newsreclib_amd import ops
+    from newsreclib_amd.evaluation import DeviceNewsTable, NewsVectorCache, recommend_users
+    mod, attrs = _tiny()
+    mod.train()
+    cache = NewsVectorCache(mod, DeviceNewsTable(attrs), chunk=32)
+    V, B, k = 50, 6, 10
+    lists, hist, hs = _hist_batch(V)
+    with pytest.raises(NotImplementedError, match="dot product"):
+        cache.recommend(hist.cuda(), hs, k)
+    idx, score, status = cache.recommend_dnn(hist.cuda(), hs, k)
+    assert mod.training                                          # the mode is restored
+    assert int(status) == 0 and idx.shape == (B, k)
+    assert cache.projection is not None and cache.projection.shape == (V, 6)
+    full = cache.scores(hist, hs, torch.arange(V).repeat(B), torch.full((B,), V)).double().cpu()      # (B, V), unfactored
+    idx, score = idx.cpu(), score.cpu()
+    vec = cache.vectors
+    with torch.no_grad():
+        user, _ = mod.user_queries(ops.embedding_gather(vec, hist.cuda().reshape(-1, 1)).reshape(-1, vec.shape[1]),
+                                   cache._user_meta(hs, None))
+    pred = [t.detach().cpu() for t in mod.click_predictor.params()]
+    s_f, b_f = R.scores64(user.cpu(), vec.cpu(), pred)
+    s_u, b_u = _click_bound(user.cpu(), vec.cpu(), pred)
+    assert float((s_f - s_u).abs().max()) < 1e-12                # the same function, factored or not
+    assert bool(((full - s_u).abs() <= b_u).all())               # the unfactored side is inside its own bound
+    bound = b_f + b_u
+    for b in range(B):
+        rows = idx[b]
+        assert bool((rows >= 0).all()) and not (set(rows.tolist()) & set(lists[b].tolist()))
+        assert bool(((score[b].double() - s_f[b, rows]).abs() <= b_f[b, rows]).all())
+        assert bool(((score[b].double() - full[b, rows]).abs() <= bound[b, rows]).all())
+        assert bool((score[b][1:] <= score[b][:-1]).all())
+        rest = torch.ones(V, dtype=torch.bool)
+        rest[rows] = False
+        rest[lists[b]] = False
+        assert bool((full[b][rest] <= full[b, rows].min() + 2 * bound[b][rest]).all())
+    # without the exclusion the history may appear
+    idx2, _, _ = cache.recommend_dnn(hist.cuda(), hs, V, exclude_history=False)
+    assert all(set(idx2[b].tolist()) == set(range(V)) for b in range(B))
+    # build() drops the projection; it is rebuilt to the same bits
+    old = cache.projection
+    cache.build()
+    assert cache.projection is None
+    idx3, score3, _ = cache.recommend_dnn(hist.cuda(), hs, k)
+    assert torch.equal(cache.projection, old) and torch.equal(idx3.cpu(), idx) and torch.equal(score3.cpu(), score)
+    users = [{"hist": lists[b], "user_id": 100 + b} for b in range(B)]
+    for batch_size in (4, 8):                                    # two batches (the second partial), one batch
+        recs = recommend_users(cache, users, k, batch_size=batch_size)
+        assert list(recs) == [f"U{100 + b}" for b in range(B)]
+        # (a DKN user does not depend on the other users of the batch)
+        assert all(list(recs[f"U{100 + b}"]) == [f"N{int(i)}" for i in idx[b]] for b in range(B))
+        assert list(recs["U100"].values()) == [float(v) for v in score[0]]
+
+
+def test_recommend_dnn_under_late_fusion_is_the_dot_product_ranking():
+    from newsreclib_amd.evaluation import DeviceNewsTable, NewsVectorCache, recommend_users
+    mod, attrs = _tiny(late_fusion=True)
+    cache = NewsVectorCache(mod, DeviceNewsTable(attrs), chunk=32)
+    V, B, k = 50, 6, 10
+    lists, hist, hs = _hist_batch(V)
+    idx, score, status = cache.recommend_dnn(hist.cuda(), hs, k)
+    assert int(status) == 0 and cache.projection is None
+    full = cache.scores(hist, hs, torch.arange(V).repeat(B), torch.full((B,), V)).double().cpu()
+    idx, score = idx.cpu(), score.cpu()
+    vec = cache.vectors.cpu()
+    user = torch.stack([vec[h].double().mean(0) for h in lists])
+    # both sides: one fp32 mean over the history (n + 1 roundings) and one fp32 dot product of length dim
+    n = torch.tensor([len(h) for h in lists]).double().reshape(-1, 1)
+    side = (vec.shape[1] + n + 1) * R.EPS * (torch.stack([vec[h].double().abs().mean(0) for h in lists]) @ vec.double().abs().T)
+    raw = user @ vec.double().T
+    for b in range(B):
+        rows = idx[b]
+        assert bool((rows >= 0).all()) and not (set(rows.tolist()) & set(lists[b].tolist()))
+        assert bool(((score[b].double() - raw[b, rows]).abs() <= side[b, rows]).all())
+        assert bool(((score[b].double() - full[b, rows]).abs() <= 2 * side[b, rows]).all())
+        rest = torch.ones(V, dtype=torch.bool)
+        rest[rows] = False
+        rest[lists[b]] = False
+        assert bool((full[b][rest] <= full[b, rows].min() + 4 * side[b][rest]).all())
+    recs = recommend_users(cache, [{"hist": lists[b]} for b in range(B)], k)
+    assert all(list(recs[f"U{b + 1}"]) == [f"N{int(i)}" for i in idx[b]] for b in range(B))
+    with pytest.raises(NotImplementedError, match="dot product"):
+        cache.recommend(hist.cuda(), hs, k)
+
+
+def test_recommend_dnn_does_not_synchronise_with_the_host():
+    from newsreclib_amd.evaluation import DeviceNewsTable, NewsVectorCache
+    mod, attrs = _tiny()
+    cache = NewsVectorCache(mod, DeviceNewsTable(attrs), chunk=32)
+    cache.build()
+    _, hist, hs = _hist_batch(50)
+    hist = hist.cuda()                                           # the sizes stay on the host, as evaluate_impressions builds them
+    torch.cuda.synchronize()
+    torch.cuda.set_sync_debug_mode("error")
+    try:
+        if not _sync_debug_honoured():
+            pytest.skip("this torch build does not raise on synchronising calls under set_sync_debug_mode('error')")
+        idx, score, status = cache.recommend_dnn(hist, hs, 5)      # (the first call: the projection is built inside)
+    finally:
+        torch.cuda.set_sync_debug_mode("default")
+    assert int(status) == 0 and idx.shape == (6, 5)
