@@ -1144,6 +1144,32 @@ int nrl_topk_relu_scores(const float* q, const float* proj, const float* w2, con
                          int32_t k, const int64_t* excl_idx, const int64_t* excl_off, const uint8_t* eligible, int32_t slices,
                          int64_t* out_idx, float* out_score, int32_t* status, void* ws, size_t ws_bytes, void* stream);
 
+/* nrl_topk_pooled_scores: the same ranking by NPA's eval-mode score (text.py:385-390 and user/npa.py with the candidate list
+ *   replaced by the table), from the cached conv feature maps `features` (V, L, F) of nrl_npa_conv_features: with
+ *     a[u, v, t] = features[v, t, :] . q[u]          q (B, F): the users' tanh'd candidate-side text queries
+ *     s[u, v, t] = features[v, t, :] . user[u]       user (B, F): the user vectors (nrl_npa_cached_scores reports them)
+ *     score(u, v) = sum_t softmax_t(a[u, v, :])[t] s[u, v, t],
+ *   the dot product of user[u] with the news vector pooled by the user's own attention; the softmax runs over all L tokens with no
+ *   mask, as nrl_npa_cached_scores pools.  All three fp32, row-major, device, 16-byte aligned; V * L * F is addressed in int64.
+ *   L in [1, NRL_TOPK_MAX_TOKENS]; F a multiple of 4 in [4, NRL_TOPK_MAX_D]; k, V, B, excl_idx / excl_off, eligible, slices,
+ *   out_idx / out_score and status as for nrl_topk_scores.
+ *   Arithmetic, fixed: each a and s is the one exact-fp32 MFMA accumulator chain of nrl_topk_scores over F; the tokens are folded
+ *     in ascending t into an online softmax, m' = fmaxf(m, a); r = exp(m - m'); p = exp(a - m'); l = fmaf(l, r, p);
+ *     o = fmaf(o, r, p * s) from m = -inf, l = o = 0 (exp: the fast device exponential nrl_npa_cached_scores pools with), then one
+ *     fp32 division o / l.  The bits of score(u, v) depend on q[u], user[u], the (L, F) map of v, L and F alone: not on B, V, k,
+ *     slices, the user's place in the batch, the grid or the GEMM engine setting (which this entry does not read).  A NaN anywhere
+ *     in the map (through p: fmaxf alone would drop a NaN logit) and inf - inf make the score NaN; a NaN score of an eligible, not
+ *     excluded row sets NRL_TOPK_E_NAN and the row is left out for that user.  Neither (B, V, L) nor (B, V, F) is written.  No
+ *     floating-point atomics, no allocation, no host synchronisation.
+ *   Workspace: there is no size function of its own: the partial lists are those of nrl_topk_scores, so
+ *     nrl_topk_scores_workspace_bytes(B, V, 4, k, slices) is exactly this entry's requirement; a shorter buffer is refused with
+ *     NRL_E_WORKSPACE before any launch.  B == 0 returns success without a launch; V == 0 fills the output with -1 / -inf.  Sizes
+ *     outside the limits and a null status, q, user or features return NRL_E_INVALID. */
+#define NRL_TOPK_MAX_TOKENS 128
+int nrl_topk_pooled_scores(const float* q, const float* user, const float* features, int64_t B, int64_t V, int32_t L, int32_t F,
+                           int32_t k, const int64_t* excl_idx, const int64_t* excl_off, const uint8_t* eligible, int32_t slices,
+                           int64_t* out_idx, float* out_score, int32_t* status, void* ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -20,6 +20,8 @@
 //       score tile that collects the weighted z-scores.
 //   tkr_scores_kernel  DKN's factored DNN predictor: the tile is b2 + sum_j w2[j] relu(proj[v, j] + q[u, j]) in plain fp32 vector
 //       code instead of a product; the other stages unchanged.
+//   tkp_scores_kernel  NPA's personalized pooling: per token of the cached feature maps a two-operand tile product kept in
+//       registers and folded into an online softmax per (user, row); the other stages unchanged.
 //   tk_merge_kernel    one wave per user: validates the user's offsets and exclusion indices (status flags), merges the `slices`
 //       partial lists with the same insertion and writes (row, score) or (-1, -inf).
 // The stages (exclusion cache, eligibility, tile product, per-user selection, flush) are written once, as inlined device functions
@@ -175,14 +177,15 @@ __device__ __forceinline__ void tk_fill_eligible(const uint8_t* eligible, int v0
   }
 }
 
-// The 64 x 128 products of NA row operands (pa[a]: this thread's staging row, tid >> 2, of operand a; zero when !ua_ok) with table
-// rows v0 ... v0 + 127, into NA score tiles [TK_BU][TK_SCLD] from `sc` on.  Until the scores exist the same LDS holds the operand
-// tiles, NA x [2][TK_BK][TK_LDA] and then [2][TK_BK][TK_LDB], all staged against ONE pass over the table tile.  Ends with the
-// tiles written and the workgroup synchronised.
+// The 64 x 128 products of NA row operands (pa[a]: this thread's staging row, tid >> 2, of operand a; zero when !ua_ok) with the
+// table rows v0 ... v0 + 127, `ldt` floats apart and D deep (ldt > D: a table whose rows are one token of a (V, L, F) map), left in
+// `acc`: the lane holds tile row wm * 32 + i * 16 + 4 g + r, column wn * 64 + j * 16 + l15 in acc[a][i][j][r].  `lds` holds the
+// operand tiles, NA x [2][TK_BK][TK_LDA] and then [2][TK_BK][TK_LDB], all staged against ONE pass over the table tile.  Ends with
+// the workgroup synchronised: `lds` is free.
 template <int NA>
-__device__ __forceinline__ void tk_tile_product(const float* const (&pa)[NA], bool ua_ok, const float* table, int v0, int V, int D,
-                                                float* sc) {
-  float* const As = sc;
+__device__ __forceinline__ void tk_tile_accumulate(const float* const (&pa)[NA], bool ua_ok, const float* table, int64_t ldt, int v0,
+                                                   int V, int D, float* lds, tk_f32x4 (&acc)[NA][2][4]) {
+  float* const As = lds;
   float* const Bs = As + NA * 2 * TK_BK * TK_LDA;
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -197,7 +200,7 @@ __device__ __forceinline__ void tk_tile_product(const float* const (&pa)[NA], bo
   for (int c = 0; c < 2; ++c) {
     const int64_t v = (int64_t)v0 + srow + c * 64;
     vb_ok[c] = v < V;
-    pb[c] = table + (int64_t)(vb_ok[c] ? v : V - 1) * D;
+    pb[c] = table + (int64_t)(vb_ok[c] ? v : V - 1) * ldt;
   }
   float4 ra[NA], rb[2];
   auto load_tiles = [&](int k0) {                    // unconditional loads from clamped addresses; masked when staged
@@ -231,7 +234,6 @@ __device__ __forceinline__ void tk_tile_product(const float* const (&pa)[NA], bo
     }
   };
 
-  tk_f32x4 acc[NA][2][4];
 #pragma unroll
   for (int a = 0; a < NA; ++a)
 #pragma unroll
@@ -265,17 +267,30 @@ __device__ __forceinline__ void tk_tile_product(const float* const (&pa)[NA], bo
     if (kt + 1 < nkt) store_tiles(buf ^ 1, (kt + 1) * TK_BK);
     __syncthreads();
   }
+}
 
-  // accumulators -> score tiles: the lane holds tile row 4g + r, column l15 of every 16 x 16 block
+// one operand's fragments of tk_tile_accumulate -> a score tile [TK_BU][TK_SCLD]
+__device__ __forceinline__ void tk_store_fragments(const tk_f32x4 (&x)[2][4], float* tile) {
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int wm = wave >> 1, wn = wave & 1, l15 = lane & 15, g = lane >> 4;
 #pragma unroll
   for (int i = 0; i < 2; ++i)
 #pragma unroll
     for (int j = 0; j < 4; ++j)
 #pragma unroll
-      for (int r = 0; r < 4; ++r)
+      for (int r = 0; r < 4; ++r) tile[(wm * 32 + i * 16 + 4 * g + r) * TK_SCLD + wn * 64 + j * 16 + l15] = x[i][j][r];
+}
+
+// The products of tk_tile_accumulate over a (V, D) table into NA score tiles [TK_BU][TK_SCLD] from `sc` on: until the scores exist
+// the same LDS holds the operand tiles.  Ends with the tiles written and the workgroup synchronised.
+template <int NA>
+__device__ __forceinline__ void tk_tile_product(const float* const (&pa)[NA], bool ua_ok, const float* table, int v0, int V, int D,
+                                                float* sc) {
+  tk_f32x4 acc[NA][2][4];
+  tk_tile_accumulate<NA>(pa, ua_ok, table, D, v0, V, D, sc, acc);
 #pragma unroll
-        for (int a = 0; a < NA; ++a)
-          sc[a * TK_BU * TK_SCLD + (wm * 32 + i * 16 + 4 * g + r) * TK_SCLD + wn * 64 + j * 16 + l15] = acc[a][i][j][r];
+  for (int a = 0; a < NA; ++a) tk_store_fragments(acc[a], sc + a * TK_BU * TK_SCLD);
   __syncthreads();
 }
 
@@ -865,6 +880,110 @@ __global__ __launch_bounds__(TK_THREADS) void tkr_scores_kernel(TkrArgs A) {
   for (int ul = ul_begin; ul < ul_end; ++ul) tk_flush_user(lists + ul * k, A.partial + ((u0 + ul) * A.slices + sl) * k, k, lane);
 }
 
+// ---- personalized-pooling scores (NPA) --------------------------------------------------------------------------------------------
+// NPA's eval-mode score from the cached conv feature maps c (V, L, F): with a[u, v, t] = c[v, t] . q[u] (q the user's tanh'd text
+// query) and s[u, v, t] = c[v, t] . user[u], score(u, v) = sum_t softmax_t(a[u, v, :])[t] s[u, v, t]: the dot product of the user
+// vector with the news vector pooled by the user's own attention, without forming the pooled vector.  tk_scores_kernel with
+// another tile producer:
+//   * tokens t = 0 ... L - 1 in ascending order; per token ONE pass of tk_tile_accumulate<2> with the row operands q and user over
+//     the table rows features + (v L + t) F (row stride L F, depth F), so a and s of a position come out of the same staged tile;
+//   * the two accumulator fragments stay in registers, 32 (u, v) positions per thread, and are folded into an online-softmax
+//     state (m, l, o) per position: m' = max(m, a); r = exp(m - m'); p = exp(a - m'); l = l r + p; o = o r + p s, with the
+//     exponential of npa_cached_pool.  A NaN logit leaves m alone (fmaxf) and makes p, hence l and o, NaN; so does inf - inf;
+//   * after the last token o / l goes to the score tile and the selection runs as everywhere.
+// LDS: the three operand tiles (38 KB) take the place of the one score tile (33 KB) of tk_lds_bytes(1, ...), so two workgroups
+// fit a CU up to k = 50; (B, V, L) is never written.  Registers: 32 positions x (2 accumulators + 3 state) and the staging; the
+// second launch bound holds the compiler to two waves per SIMD (231 VGPRs, no scratch; without it 269 and one wave: a quarter slower).
+struct TkpArgs : TkArgs {                      // `user` is q, `table` the feature maps, D is F
+  const float* uvec;
+  int32_t L;
+};
+
+constexpr int TKP_OPERAND_FLOATS = 2 * TK_BK * (2 * TK_LDA + TK_LDB);
+constexpr size_t TKP_EXTRA_LDS = (size_t)(TKP_OPERAND_FLOATS - TK_BU * TK_SCLD) * 4;
+static_assert(TKP_OPERAND_FLOATS >= TK_BU * TK_SCLD && TKP_EXTRA_LDS % 16 == 0, "the score tile lives inside the operand tiles");
+static_assert(tk_lds_bytes(1, TK_BU, NRL_TOPK_MAX_K) + TKP_EXTRA_LDS <= 160 * 1024, "the largest layout fits");
+
+__global__ __launch_bounds__(TK_THREADS, 2) void tkp_scores_kernel(TkpArgs A) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char tk_smem[];
+  float* const sc = reinterpret_cast<float*>(tk_smem);                       // operand tiles; afterwards [TK_BU][TK_SCLD] scores
+  int32_t* const xl = reinterpret_cast<int32_t*>(sc + TKP_OPERAND_FLOATS);   // [TK_BU][TK_XCAP]
+  int64_t* const xs = reinterpret_cast<int64_t*>(xl + TK_BU * TK_XCAP);      // [TK_BU]
+  int32_t* const xn = reinterpret_cast<int32_t*>(xs + TK_BU);                // [TK_BU]
+  uint8_t* const el = reinterpret_cast<uint8_t*>(xn + TK_BU);                // [TK_BV]
+  unsigned long long* const lists = reinterpret_cast<unsigned long long*>(el + TK_BV);      // [TK_BU][k]
+
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int k = A.k, V = A.V, L = A.L, F = A.D;
+  const int sl = (int)(blockIdx.x % (unsigned)A.slices);
+  const int64_t u0 = (int64_t)(blockIdx.x / (unsigned)A.slices) * TK_BU;
+  const int nu = A.B - u0 < TK_BU ? (int)(A.B - u0) : TK_BU;
+  const int v_begin = sl * A.tiles_per_slice * TK_BV;
+  const int64_t v_stop = (int64_t)v_begin + (int64_t)A.tiles_per_slice * TK_BV;
+  const int v_end = v_stop < V ? (int)v_stop : V;
+  const int nvt = (v_end - v_begin + TK_BV - 1) / TK_BV;
+
+  for (int i = tid; i < TK_BU * k; i += TK_THREADS) lists[i] = 0ull;
+  tk_cache_exclusions(A, u0, nu, TK_BU, xs, xn, xl);
+
+  const int ul_begin = wave * TK_USERS_PER_WAVE, ul_end = ul_begin + TK_USERS_PER_WAVE < nu ? ul_begin + TK_USERS_PER_WAVE : nu;
+  const int srow = tid >> 2;
+  const bool ua_ok = srow < nu;
+  const int64_t ua = (ua_ok ? u0 + srow : A.B - 1) * F;
+  const float* const pa[2] = {A.user + ua, A.uvec + ua};
+  const int64_t ldt = (int64_t)L * F;
+  bool nan = false;
+
+  for (int vt = 0; vt < nvt; ++vt) {
+    const int v0 = v_begin + vt * TK_BV;
+    tk_fill_eligible(A.eligible, v0, V, el);
+
+    tk_f32x4 m[2][4], l[2][4], o[2][4];
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        m[i][j] = tk_f32x4{-INFINITY, -INFINITY, -INFINITY, -INFINITY};
+        l[i][j] = o[i][j] = tk_f32x4{0.f, 0.f, 0.f, 0.f};
+      }
+    for (int t = 0; t < L; ++t) {
+      tk_f32x4 acc[2][2][4];                          // [0]: the logits a, [1]: the values s
+      tk_tile_accumulate<2>(pa, ua_ok, A.table + (int64_t)t * F, ldt, v0, V, F, sc, acc);
+#pragma unroll
+      for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            const float a = acc[0][i][j][r], mo = m[i][j][r];
+            const float mn = fmaxf(mo, a);            // a NaN logit leaves the maximum alone and arrives through p
+            const float keep = __expf(mo - mn), p = __expf(a - mn);
+            l[i][j][r] = fmaf(l[i][j][r], keep, p);
+            o[i][j][r] = fmaf(o[i][j][r], keep, __fmul_rn(p, acc[1][i][j][r]));
+            m[i][j][r] = mn;
+          }
+    }
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) o[i][j][r] = __fdiv_rn(o[i][j][r], l[i][j][r]);
+    tk_store_fragments(o, sc);                        // (the last pass ended synchronised: the operand tiles are dead)
+    __syncthreads();
+
+    const bool e_0 = el[lane] != 0, e_1 = el[64 + lane] != 0;
+    for (int ul = ul_begin; ul < ul_end; ++ul)
+      tk_select_user(sc + ul * TK_SCLD, lists + ul * k, xn + ul, xs + ul, xl + ul * TK_XCAP, A.excl_idx, v0, e_0, e_1, k, lane, nan);
+    __syncthreads();                                  // the score tile and `el` are free for the next tile's operands
+  }
+
+  if (nan && lane == 0) atomicOr(A.status, NRL_TOPK_E_NAN);
+  wave_lds_sync();
+  for (int ul = ul_begin; ul < ul_end; ++ul) tk_flush_user(lists + ul * k, A.partial + ((u0 + ul) * A.slices + sl) * k, k, lane);
+}
+
 static bool tk_shape_ok(int64_t B, int64_t V, int32_t D, int32_t k) {
   return B >= 0 && V >= 0 && V < ((int64_t)1 << 31) && D > 0 && D % 4 == 0 && D <= NRL_TOPK_MAX_D && k >= 1 && k <= NRL_TOPK_MAX_K;
 }
@@ -999,6 +1118,28 @@ int nrl_topk_relu_scores(const float* q, const float* proj, const float* w2, con
   A.w2 = w2;
   A.b2 = b2;
   return tk_launch("topk_relu_scores", tkr_scores_kernel, A, slices, 1, TK_BU, stream, tkr_extra_lds(Hd));
+}
+
+int nrl_topk_pooled_scores(const float* q, const float* user, const float* features, int64_t B, int64_t V, int32_t L, int32_t F,
+                           int32_t k, const int64_t* excl_idx, const int64_t* excl_off, const uint8_t* eligible, int32_t slices,
+                           int64_t* out_idx, float* out_score, int32_t* status, void* ws, size_t ws_bytes, void* stream) {
+  NRL_REQUIRE(B >= 0 && V >= 0 && slices >= 0, "topk_pooled_scores: negative size");
+  NRL_REQUIRE(L >= 1 && L <= NRL_TOPK_MAX_TOKENS, "topk_pooled_scores: L in [1, %d] tokens (got %d)", NRL_TOPK_MAX_TOKENS, L);
+  NRL_REQUIRE(F >= 4 && F % 4 == 0 && F <= NRL_TOPK_MAX_D, "topk_pooled_scores: F a multiple of 4 in [4, %d] (got %d)",
+              NRL_TOPK_MAX_D, F);
+  NRL_TRY(tk_check("topk_pooled_scores", B, V, 4, k, excl_idx, excl_off));    // (no D here: F is checked above)
+  NRL_REQUIRE(status, "topk_pooled_scores: the status word is required");
+  if (B == 0) return NRL_OK;
+  NRL_REQUIRE(out_idx && out_score && q && user && (V == 0 || features), "topk_pooled_scores: null argument");
+  NRL_REQUIRE((((uintptr_t)q | (uintptr_t)user | (uintptr_t)features) & 15) == 0,
+              "topk_pooled_scores: q, user and features must be 16-byte aligned");
+  unsigned long long* partial;
+  NRL_TRY(carve_workspace(ws, ws_bytes, [&](Arena& a) { tk_layout(a, B, V, k, slices, TK_BU, &partial); }));
+  TkpArgs A;
+  static_cast<TkArgs&>(A) = tk_args(q, features, B, V, F, k, excl_idx, excl_off, eligible, partial, out_idx, out_score, status);
+  A.uvec = user;
+  A.L = L;
+  return tk_launch("topk_pooled_scores", tkp_scores_kernel, A, slices, 1, TK_BU, stream, TKP_EXTRA_LDS);
 }
 
 int nrl_topk_ensemble_scores(const float* const* users, const float* const* tables, const float* weights, int32_t T, int64_t B,

@@ -452,7 +452,47 @@ class NpaFeatureCache(_ImpressionCache):
     def recommend(self, *args, **kwargs):
         raise NotImplementedError("NPA's news vectors depend on the user (personalized attention pooling, text.py:385-390): there "
                                   "is no (V, D) table to rank with one user vector, so the whole catalogue cannot be scored by "
-                                  "one GEMM + top-k")
+                                  "one GEMM + top-k; `recommend_pooled` ranks it from the cached feature maps (two GEMMs and a "
+                                  "softmax over the tokens per user and news, fused)")
+
+    @torch.no_grad()
+    def recommend_pooled(self, hist_idx: torch.Tensor, hist_sizes: torch.Tensor, k: int, user_idx: Optional[torch.Tensor] = None,
+                         exclude_history: bool = True, eligible: Optional[torch.Tensor] = None):
+        """The ``k`` news of the WHOLE table each user scores highest -> (news_idx (B, k) int64, scores (B, k) fp32, status), by
+        the score ``scores`` gives a candidate: the user vector dotted with the news' feature map pooled by the user's
+        candidate-side text query (``ops.topk_pooled_scores``: neither the pooled vectors nor a (B, V, L) array is formed).  The
+        queries come from ``module.user_queries(user_idx)`` (required: ``user_idx_reason``); the user vectors are the ones
+        ``scores`` computes for the same batch, bit for bit -- ``npa_cached_scores`` over the history with an empty candidate
+        list: history rows pooled with the history-side query, then the personalized attention, or the mean under late fusion
+        (the same ranking kernel either way).  Under early fusion that attention counts ``max_hist - n`` virtual zero rows,
+        ``max_hist`` the longest history OF THE BATCH (the model's own ``to_dense_batch`` quirk): a user's vector, hence its
+        ranking, depends on the batch it is in exactly as in ``scores``.  Same contract as ``NewsVectorCache.recommend``:
+        ``hist_idx`` on the GPU, ``hist_sizes`` on the host, nothing read back; the features are built at the first use."""
+        from .ops_npa import npa_cached_scores
+        if user_idx is None:
+            raise ValueError(f"NpaFeatureCache.recommend_pooled needs user_idx: {self.user_idx_reason}")
+        if not hist_idx.is_cuda:
+            raise RuntimeError(f"newsreclib_amd: `hist_idx` must live on the GPU (got {hist_idx.device}); there is no CPU path")
+        if self.features is None:
+            self.build()
+        dev = self.table.device
+        hist_idx = hist_idx.to(dev).long()
+        hs = hist_sizes.detach().cpu().long()               # host sizes: the maximum and the offsets cost no read-back
+        B = int(hs.numel())
+        max_hist = int(hs.max()) if B else 0
+        off = torch.cat([torch.zeros(1, dtype=torch.int64), torch.cumsum(hs, 0)])
+        hist_off = off.pin_memory().to(dev, non_blocking=True)
+        user_idx = user_idx if user_idx.is_cuda else user_idx.pin_memory().to(dev, non_blocking=True)
+        with eval_mode(self.module):
+            text_q, q_news = self.module.user_queries(user_idx.to(dev).long())      # p = 0, as ``scores``
+        q_hist, q_cand = text_q[:B], text_q[B:]
+        no_cand = torch.empty(0, dtype=torch.int64, device=dev)
+        # (the scorer wants a score buffer: one padded slot per user, no candidate rows)
+        _, user = npa_cached_scores(self.features, hist_idx, hist_off, no_cand, torch.zeros(B + 1, dtype=torch.int64, device=dev),
+                                    q_hist, q_cand, q_news, max_hist, 1, return_user_vectors=True)
+        excl = (hist_idx, hist_off) if exclude_history else (None, None)
+        return ops.topk_pooled_scores(q_cand, user, self.features, k, excl[0], excl[1],
+                                      eligible.to(dev) if eligible is not None else None)
 
 
 def evaluate_impressions(cache: NewsVectorCache, impressions: Sequence[Dict], batch_size: int = 512,
@@ -507,7 +547,8 @@ def format_recommendations(user_ids: Sequence, news_idx: torch.Tensor, scores: t
 def recommend_users(cache: NewsVectorCache, users: Sequence[Dict], k: int, batch_size: int = 512,
                     eligible: Optional[torch.Tensor] = None) -> Dict[str, Dict[str, float]]:
     """``cache.recommend`` (``cache.recommend_interests`` where the cache's module is a ``multi_interest_scorer``,
-    ``cache.recommend_dnn`` where it is a ``dnn_predictor_scorer``,
+    ``cache.recommend_dnn`` where it is a ``dnn_predictor_scorer``, ``cache.recommend_pooled`` where it is a
+    ``personalized_pooling_scorer``: ``NpaFeatureCache``, whose users need ``user_idx``,
     ``cache.recommend_ensemble`` where the cache has one: ``MannerVectorCache``) over a list of
     users ({"hist": idx tensor[, "user_idx", "user_id"]}) in batches -> the recommendation dictionary of ``format_recommendations``.  ``user_id`` defaults to the user's position in the list + 1 (as ``build_batch``);
     news ids come from the table's ``news_ids`` column when it has one.  One device-to-host copy per batch, at its end; a status
@@ -521,7 +562,8 @@ def recommend_users(cache: NewsVectorCache, users: Sequence[Dict], k: int, batch
         hist = torch.cat([torch.as_tensor(u["hist"]).long() for u in chunk]).to(dev)
         uidx = torch.stack([torch.as_tensor(u["user_idx"]) for u in chunk]) if "user_idx" in chunk[0] else None
         rank = cache.recommend_interests if getattr(cache.module, "multi_interest_scorer", False) else \
-            cache.recommend_dnn if getattr(cache.module, "dnn_predictor_scorer", False) else cache.recommend
+            cache.recommend_dnn if getattr(cache.module, "dnn_predictor_scorer", False) else \
+            cache.recommend_pooled if getattr(cache.module, "personalized_pooling_scorer", False) else cache.recommend
         rank = getattr(cache, "recommend_ensemble", rank)
         idx, score, status = rank(hist, hs, k, user_idx=uidx, eligible=eligible)
         packed = torch.cat([idx.double(), score.double(), status.double().expand(idx.shape[0], 1)], dim=1).cpu()      # the one copy

@@ -32,6 +32,10 @@ from .user_encoder_npa import UserEncoder
 
 class NPAModule(AbstractRecommender):
     user_dependent_news_vectors = True       # (evaluation.NewsVectorCache refuses to cache them: NpaFeatureCache)
+    # in eval mode the news vector depends on the user only through the attention pooling of the cached conv feature maps, and the
+    # score is a dot product with a candidate-independent user vector: ``evaluation.NpaFeatureCache.recommend_pooled`` ranks the
+    # whole table by it.  There is still no (V, D) table, so there is no ``dot_product_scorer``
+    personalized_pooling_scorer = True
 
     def __init__(
         self,

@@ -889,3 +889,38 @@ def topk_relu_scores(q: torch.Tensor, proj: torch.Tensor, w2: torch.Tensor, b2: 
                                         ptr(excl_off), ptr(eligible), int(slices), idx.data_ptr(), score.data_ptr(),
                                         status.data_ptr(), ws.data_ptr(), ws.numel(), _stream()), "nrl_topk_relu_scores")
     return idx, score, status
+
+
+TOPK_MAX_TOKENS = 128
+
+
+def topk_pooled_scores(q: torch.Tensor, user: torch.Tensor, features: torch.Tensor, k: int,
+                       excl_idx: Optional[torch.Tensor] = None, excl_off: Optional[torch.Tensor] = None,
+                       eligible: Optional[torch.Tensor] = None, slices: int = 0):
+    """``nrl_topk_pooled_scores``: ``topk_scores`` by NPA's eval-mode score from the cached conv feature maps ``features``
+    (V, L, F) (``ops_npa.npa_conv_features``): the score of table row ``v`` for user ``u`` is
+    ``sum_t softmax_t(features[v] @ q[u])[t] * (features[v] @ user[u])[t]`` -- the user vector ``user`` (B, F) dotted with the news
+    vector pooled by the user's own text query ``q`` (B, F), the softmax over all L tokens.  L in [1, 128], F a multiple of 4 up to
+    1024.  -> (idx (B, k) int64, score (B, k) fp32, status (1) int32) with the ordering, exclusion, eligibility and status flags of
+    ``topk_scores``; neither a (B, V, L) nor the (B, V, F) array is materialised.  The workspace is sized by
+    ``nrl_topk_scores_workspace_bytes(B, V, 4, k, slices)``: the partial lists are those of ``topk_scores``.  Nothing here
+    synchronises with the host."""
+    lib = _lib.load()
+    if q.dim() != 2 or features.dim() != 3 or user.shape != q.shape or q.shape[1] != features.shape[2]:
+        raise ValueError(f"newsreclib_amd: q (B, F), user (B, F) and features (V, L, F) expected, got {tuple(q.shape)}, "
+                         f"{tuple(user.shape)} and {tuple(features.shape)}")
+    q, user, features = _chk(q, torch.float32, "q"), _chk(user, torch.float32, "user"), _chk(features, torch.float32, "features")
+    B, F_, V, L, k = int(q.shape[0]), int(q.shape[1]), int(features.shape[0]), int(features.shape[1]), int(k)
+    if not 1 <= L <= TOPK_MAX_TOKENS:
+        raise NotImplementedError(f"newsreclib_amd: topk_pooled_scores takes feature maps of 1 to {TOPK_MAX_TOKENS} tokens (got {L})")
+    excl_idx, excl_off, eligible = _topk_masks(excl_idx, excl_off, eligible, B, V)
+    dev = q.device
+    idx = torch.empty((B, max(k, 0)), dtype=torch.int64, device=dev)
+    score = torch.empty((B, max(k, 0)), dtype=torch.float32, device=dev)
+    status = torch.zeros(1, dtype=torch.int32, device=dev)
+    ws = workspace(lib.nrl_topk_scores_workspace_bytes(B, V, 4, k, int(slices)), dev)
+    ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
+    _lib.check(lib.nrl_topk_pooled_scores(q.data_ptr(), user.data_ptr(), features.data_ptr(), B, V, L, F_, k, ptr(excl_idx),
+                                          ptr(excl_off), ptr(eligible), int(slices), idx.data_ptr(), score.data_ptr(),
+                                          status.data_ptr(), ws.data_ptr(), ws.numel(), _stream()), "nrl_topk_pooled_scores")
+    return idx, score, status
