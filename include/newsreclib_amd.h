@@ -1170,6 +1170,47 @@ int nrl_topk_pooled_scores(const float* q, const float* user, const float* featu
                            int32_t k, const int64_t* excl_idx, const int64_t* excl_off, const uint8_t* eligible, int32_t slices,
                            int64_t* out_idx, float* out_score, int32_t* status, void* ws, size_t ws_bytes, void* stream);
 
+/* nrl_catalogue_ranks: where held-out rows (the clicks of a test split) land when a user is ranked against the whole table: the
+ *   evaluation counterpart of nrl_topk_scores, with its scores, its order and its masks, again without the (B, V) matrix.
+ *   user_vec, table, B, V, D, excl_idx / excl_off (and the trust in excl_off[B]), eligible, slices and the flags
+ *   NRL_TOPK_E_EXCLUDE / NRL_TOPK_E_OFFSETS / NRL_TOPK_E_NAN as for nrl_topk_scores; duplicates and empty exclusion lists are
+ *   fine and a duplicate exclusion entry removes its row once.
+ *   Population: P_u = { v in [0, V) : eligible[v] != 0, v not on u's exclusion list, score(u, v) not NaN }.
+ *     out_ranked[u] = |P_u| (0 for a user NRL_TOPK_E_OFFSETS refuses).
+ *   Order: that of nrl_topk_scores: entry = score_key(score) << 32 | ~row, larger is better, so equal scores rank by ascending
+ *     row and -0 equals +0.
+ *   Targets: tgt_idx (n_targets int64) / tgt_off ((B + 1) int64; nullable only with n_targets == 0 and a null tgt_idx), a ragged
+ *     per-user list laid out like the exclusion list: user b owns the slots tgt_off[b] .. tgt_off[b + 1].
+ *     out_rank[j] = 1 + the number of rows of P_u whose entry is strictly above target j's entry; 0 when the target row is not
+ *     itself in P_u (outside [0, V), ineligible, on the exclusion list or NaN-scored).  out_score[j] is the target's score, -inf
+ *     when the rank is 0.  Other targets of the same user are ordinary rows; the same row listed twice gets the same rank twice.
+ *   Bit identity: a score's bits are a function of the two rows and D alone (see nrl_topk_scores: one accumulator chain of the
+ *     exact-fp32 MFMA, whatever the place of the rows in a tile); the target scores are computed by that same tile product over
+ *     the gathered target rows, so out_score[j] has the bits nrl_topk_scores returns for that (user, row) and for every
+ *     k <= NRL_TOPK_MAX_K: out_rank[j] = r <= k if and only if out_idx[u, r - 1] == tgt_idx[j].
+ *   NRL_RANK_E_TARGETS: a user whose tgt_off decreases or leaves [0, n_targets], or who owns more than NRL_RANK_MAX_TARGETS
+ *     slots, has ranks 0 and scores -inf; the other users are untouched and out_ranked is written for every user.  (Ranges can
+ *     overlap only where the offsets decrease somewhere; a slot two sound ranges claim belongs to the later user, and a slot
+ *     nobody owns holds 0 / -inf.)  NRL_RANK_E_TARGET_ROW: a target index outside [0, V): its rank is 0.
+ *   Determinism: the counts are integers and the scores single chains: nothing depends on B, the batch split, slices, the grid or
+ *     the GEMM engine setting.  No floating-point atomics, no allocation, no host synchronisation.
+ *   Workspace: nrl_catalogue_ranks_workspace_size (callable without a device; named _size because the set of *_workspace_bytes
+ *     functions is the one tests/data/workspace_sizes.json pins -- this one has its own table,
+ *     tests/data/catalogue_rank_workspace_sizes.json): the gathered rows n_targets * D * 4, and
+ *     (B + n_targets) * slices * 4 of per-slice counts, each region rounded up to 256; never O(B * V).  B == 0 returns success
+ *     without a launch; V == 0 gives ranks 0 and out_ranked 0; n_targets == 0 still fills out_ranked.  Sizes outside the limits
+ *     of nrl_topk_scores, n_targets >= 2^31, a null status and tgt_idx without tgt_off return NRL_E_INVALID, a short workspace
+ *     NRL_E_WORKSPACE, all before any launch. */
+#define NRL_RANK_MAX_TARGETS 32
+#define NRL_RANK_E_TARGETS 16     /* tgt_off decreases / leaves [0, n_targets], or a user owns more than NRL_RANK_MAX_TARGETS */
+#define NRL_RANK_E_TARGET_ROW 32  /* a target index outside [0, V): its rank is 0 */
+size_t nrl_catalogue_ranks_workspace_size(int64_t B, int64_t V, int32_t D, int64_t n_targets, int32_t slices);
+int nrl_catalogue_ranks(const float* user_vec, const float* table, int64_t B, int64_t V, int32_t D,
+                        const int64_t* tgt_idx, const int64_t* tgt_off, int64_t n_targets,
+                        const int64_t* excl_idx, const int64_t* excl_off, const uint8_t* eligible, int32_t slices,
+                        int32_t* out_rank /* n_targets */, float* out_score /* n_targets */, int32_t* out_ranked /* B */,
+                        int32_t* status, void* ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -22,6 +22,7 @@
 //       code instead of a product; the other stages unchanged.
 //   tkp_scores_kernel  NPA's personalized pooling: per token of the cached feature maps a two-operand tile product kept in
 //       registers and folded into an online softmax per (user, row); the other stages unchanged.
+//   tkc_*_kernel       the rank of held-out rows: the same walk with a consumer that counts instead of selects.
 //   tk_merge_kernel    one wave per user: validates the user's offsets and exclusion indices (status flags), merges the `slices`
 //       partial lists with the same insertion and writes (row, score) or (-1, -inf).
 // The stages (exclusion cache, eligibility, tile product, per-user selection, flush) are written once, as inlined device functions
@@ -984,6 +985,224 @@ __global__ __launch_bounds__(TK_THREADS, 2) void tkp_scores_kernel(TkpArgs A) {
   for (int ul = ul_begin; ul < ul_end; ++ul) tk_flush_user(lists + ul * k, A.partial + ((u0 + ul) * A.slices + sl) * k, k, lane);
 }
 
+// ---- full-catalogue rank of held-out rows ------------------------------------------------------------------------------------------
+// The consumer that counts instead of selects: for a ragged per-user list of target rows (the held-out clicks), 1 + the number of
+// rows of the user's population (eligible, inside V, not excluded, not NaN) whose entry is above the target's, and the population.
+//   tkc_init_kernel     one wave per target slot: blanks the slot's outputs and owner and gathers the target's table row into a
+//       (n_targets, D) workspace table (zeros for a row outside V);
+//   tkc_owner_kernel    one thread per user: a user whose target range is sound claims its slots (ranges can overlap only where the
+//       offsets decrease somewhere; the later user then owns the slot);
+//   tkc_target_kernel   one workgroup per 64 slots: the tile product of the owners' user rows (row operand, by pointer) with the
+//       gathered rows; slot j's score is the tile's diagonal -- the bits tk_scores_kernel computes for that (user, row);
+//   tkc_count_kernel    tk_scores_kernel's walk with another consumer: per (user, table tile) the entries, the exclusion sweep, the
+//       NaN drop, then popc of the survivors into the user's population counter and, per target, popc of `entry > target entry`;
+//   tkc_finish_kernel   one wave per user: status flags, the sum over the slices, each target's validity, the outputs.
+// Counts are integers: nothing depends on the order of any sum.
+struct TkcArgs : TkArgs {                      // k, partial and out_idx are unused
+  const int64_t* tgt_idx;
+  const int64_t* tgt_off;
+  int64_t n_targets;
+  float* gathered;                             // (n_targets, D)
+  float* tscore;                               // (n_targets)
+  int32_t* owner;                              // (n_targets): the user that owns the slot, -1 none
+  int32_t* pcnt;                               // (B, slices) population per slice
+  int32_t* tcnt;                               // (n_targets, slices) rows above the target per slice
+  int32_t* out_rank;
+  int32_t* out_ranked;
+};
+
+constexpr int TKC_T = NRL_RANK_MAX_TARGETS;
+constexpr int TKC_CLD = TKC_T + 1;             // a user's counters: one per target, then the population
+// dynamic LDS of tkc_count_kernel: score tile, exclusion cache, eligibility, then target entries, counters, target ranges
+constexpr size_t TKC_LDS = tk_lds_bytes(1, TK_BU, 0) + (size_t)TK_BU * TKC_T * 8 + (size_t)TK_BU * TKC_CLD * 4 + (size_t)TK_BU * 12;
+static_assert(2 * TKC_LDS <= 160 * 1024, "two workgroups of the count kernel fit a CU");
+static_assert(tk_lds_bytes(1, TK_BU, 0) % 8 == 0, "the target entries that follow the eligibility bytes are 8-byte aligned");
+
+// a user's target range: false when the offsets decrease, leave [0, n_targets] or span more than TKC_T slots
+__device__ __forceinline__ bool tkc_tgt_range(const TkcArgs& A, int64_t u, int64_t& s, int& n) {
+  s = 0;
+  n = 0;
+  if (!A.tgt_off) return true;
+  const int64_t a = A.tgt_off[u], b = A.tgt_off[u + 1];
+  if (a < 0 || b < a || b > A.n_targets || b - a > TKC_T) return false;
+  s = a;
+  n = (int)(b - a);
+  return true;
+}
+
+__global__ __launch_bounds__(64) void tkc_init_kernel(TkcArgs A) {
+  const int64_t j = blockIdx.x;
+  const int lane = threadIdx.x;
+  const int64_t row = A.tgt_idx[j];
+  const bool ok = row >= 0 && row < A.V;
+  if (lane == 0) {
+    A.owner[j] = -1;
+    A.out_rank[j] = 0;
+    A.out_score[j] = -INFINITY;
+  }
+  const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
+  for (int c = lane * 4; c < A.D; c += 256) st4(A.gathered + j * A.D + c, ok ? ld4(A.table + row * A.D + c) : z);
+}
+
+__global__ __launch_bounds__(256) void tkc_owner_kernel(TkcArgs A) {
+  const int64_t u = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (u >= A.B) return;
+  int64_t s;
+  int n;
+  if (!tkc_tgt_range(A, u, s, n)) return;
+  for (int t = 0; t < n; ++t) atomicMax(A.owner + s + t, (int32_t)u);
+}
+
+__global__ __launch_bounds__(TK_THREADS) void tkc_target_kernel(TkcArgs A) {
+  __shared__ __attribute__((aligned(16))) float sc[TK_BU * TK_SCLD];
+  const int tid = threadIdx.x;
+  const int64_t j0 = (int64_t)blockIdx.x * TK_BU;
+  // staging: tile row r is the user row of the owner of slot j0 + r, zero where nobody owns it; the table tile starts at the
+  // gathered row j0, so slot j0 + r is column r
+  const int srow = tid >> 2;
+  const int own = j0 + srow < A.n_targets ? A.owner[j0 + srow] : -1;
+  const bool ua_ok = own >= 0;
+  const float* const pa[1] = {A.user + (int64_t)(ua_ok ? own : 0) * A.D};
+  tk_tile_product<1>(pa, ua_ok, A.gathered, (int)j0, (int)A.n_targets, A.D, sc);
+  if (tid < TK_BU && j0 + tid < A.n_targets) A.tscore[j0 + tid] = sc[tid * TK_SCLD + tid];
+}
+
+__global__ __launch_bounds__(TK_THREADS) void tkc_count_kernel(TkcArgs A) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char tk_smem[];
+  float* const sc = reinterpret_cast<float*>(tk_smem);                       // [TK_BU][TK_SCLD]
+  int32_t* const xl = reinterpret_cast<int32_t*>(sc + TK_BU * TK_SCLD);      // [TK_BU][TK_XCAP]
+  int64_t* const xs = reinterpret_cast<int64_t*>(xl + TK_BU * TK_XCAP);      // [TK_BU]
+  int32_t* const xn = reinterpret_cast<int32_t*>(xs + TK_BU);                // [TK_BU]
+  uint8_t* const el = reinterpret_cast<uint8_t*>(xn + TK_BU);                // [TK_BV]
+  unsigned long long* const te = reinterpret_cast<unsigned long long*>(el + TK_BV);      // [TK_BU][TKC_T] target entries
+  int64_t* const ts = reinterpret_cast<int64_t*>(te + TK_BU * TKC_T);        // [TK_BU] first target slot
+  int32_t* const cnt = reinterpret_cast<int32_t*>(ts + TK_BU);               // [TK_BU][TKC_CLD]
+  int32_t* const tn = cnt + TK_BU * TKC_CLD;                                 // [TK_BU] target slots (0: none, or a bad range)
+
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int V = A.V;
+  const int sl = (int)(blockIdx.x % (unsigned)A.slices);
+  const int64_t u0 = (int64_t)(blockIdx.x / (unsigned)A.slices) * TK_BU;
+  const int nu = A.B - u0 < TK_BU ? (int)(A.B - u0) : TK_BU;
+  const int v_begin = sl * A.tiles_per_slice * TK_BV;
+  const int64_t v_stop = (int64_t)v_begin + (int64_t)A.tiles_per_slice * TK_BV;
+  const int v_end = v_stop < V ? (int)v_stop : V;
+  const int nvt = (v_end - v_begin + TK_BV - 1) / TK_BV;
+
+  for (int i = tid; i < TK_BU * TKC_CLD; i += TK_THREADS) cnt[i] = 0;
+  if (tid < TK_BU) {
+    int64_t s = 0;
+    int n = 0;
+    if (tid < nu && !tkc_tgt_range(A, u0 + tid, s, n)) n = 0;                // the finish kernel flags and blanks such a user
+    ts[tid] = s;
+    tn[tid] = n;
+  }
+  tk_cache_exclusions(A, u0, nu, TK_BU, xs, xn, xl);   // (its barrier also publishes `cnt`, `ts` and `tn`)
+  // a slot's entry; ~0 (above every entry: it counts nothing) where the user does not own the slot or the row is outside V
+  for (int i = tid; i < TK_BU * TKC_T; i += TK_THREADS) {
+    const int ul = i / TKC_T, t = i % TKC_T;
+    unsigned long long e = ~0ull;
+    if (t < tn[ul]) {
+      const int64_t j = ts[ul] + t, row = A.tgt_idx[j];
+      if (A.owner[j] == (int32_t)(u0 + ul) && row >= 0 && row < V) e = tk_entry(A.tscore[j], (uint32_t)row);
+    }
+    te[i] = e;
+  }
+  __syncthreads();
+
+  const int ul_begin = wave * TK_USERS_PER_WAVE, ul_end = ul_begin + TK_USERS_PER_WAVE < nu ? ul_begin + TK_USERS_PER_WAVE : nu;
+  const int srow = tid >> 2;
+  const bool ua_ok = srow < nu;
+  const float* const pa[1] = {A.user + (ua_ok ? u0 + srow : A.B - 1) * A.D};
+  bool nan = false;
+
+  for (int vt = 0; vt < nvt; ++vt) {
+    const int v0 = v_begin + vt * TK_BV;
+    tk_fill_eligible(A.eligible, v0, V, el);
+    tk_tile_product<1>(pa, ua_ok, A.table, v0, V, A.D, sc);
+
+    const bool e_0 = el[lane] != 0, e_1 = el[64 + lane] != 0;
+    for (int ul = ul_begin; ul < ul_end; ++ul) {
+      const float* const row = sc + ul * TK_SCLD;
+      unsigned long long c0 = e_0 ? tk_entry(row[lane], (uint32_t)v0 + lane) : 0ull;
+      unsigned long long c1 = e_1 ? tk_entry(row[64 + lane], (uint32_t)v0 + 64 + lane) : 0ull;
+      unsigned long long m0 = __ballot(e_0), m1 = __ballot(e_1);
+      tk_clear_excluded(xn + ul, xs + ul, xl + ul * TK_XCAP, A.excl_idx, v0, lane, m0, m1);
+      const unsigned long long n0 = m0 & __ballot((uint32_t)(c0 >> 32) == 0xFFFFFFFFu), n1 = m1 & __ballot((uint32_t)(c1 >> 32) == 0xFFFFFFFFu);
+      if (n0 | n1) nan = true;                        // a NaN score of a row of the population: flagged and left out
+      m0 &= ~n0;
+      m1 &= ~n1;
+      if (!((m0 >> lane) & 1)) c0 = 0ull;
+      if (!((m1 >> lane) & 1)) c1 = 0ull;
+      // lane t collects target t's count, lane TKC_T the population; one LDS update per user and tile
+      int add = lane == TKC_T ? __popcll(m0) + __popcll(m1) : 0;
+      const int nt = tn[ul];
+      for (int t = 0; t < nt; ++t) {
+        const unsigned long long e = te[ul * TKC_T + t];      // wave-uniform
+        const int above = __popcll(__ballot(c0 > e)) + __popcll(__ballot(c1 > e));
+        if (lane == t) add = above;
+      }
+      if (lane < nt || lane == TKC_T) cnt[ul * TKC_CLD + lane] += add;
+    }
+    __syncthreads();                                  // the score tile and `el` are free for the next tile's operands
+  }
+
+  if (nan && lane == 0) atomicOr(A.status, NRL_TOPK_E_NAN);
+  wave_lds_sync();
+  for (int ul = ul_begin; ul < ul_end; ++ul) {
+    if (lane == TKC_T) A.pcnt[(u0 + ul) * A.slices + sl] = cnt[ul * TKC_CLD + TKC_T];
+    if (lane < tn[ul] && te[ul * TKC_T + lane] != ~0ull) A.tcnt[(ts[ul] + lane) * A.slices + sl] = cnt[ul * TKC_CLD + lane];
+  }
+}
+
+__device__ __forceinline__ int tkc_wave_sum(int v) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+  return v;
+}
+
+__global__ __launch_bounds__(64) void tkc_finish_kernel(TkcArgs A) {
+  const int64_t u = blockIdx.x;
+  const int lane = threadIdx.x;
+  int64_t xs, xn, ts;
+  int nt;
+  const bool excl_ok = tk_excl_range(A, u, xs, xn);
+  const bool tgt_ok = tkc_tgt_range(A, u, ts, nt);
+  if (lane == 0 && !excl_ok) atomicOr(A.status, NRL_TOPK_E_OFFSETS);
+  if (lane == 0 && !tgt_ok) atomicOr(A.status, NRL_RANK_E_TARGETS);
+  int pop = 0;
+  for (int s = lane; s < A.slices; s += 64) pop += A.pcnt[u * A.slices + s];
+  pop = tkc_wave_sum(pop);
+  if (lane == 0) A.out_ranked[u] = excl_ok ? pop : 0;
+  if (!excl_ok) return;                               // (the slots it owns keep rank 0 / -inf)
+
+  // lane t < nt: target slot ts + t, when this user owns it
+  const bool mine = lane < nt && A.owner[ts + lane] == (int32_t)u;
+  const int64_t row = mine ? A.tgt_idx[ts + lane] : -1;
+  const bool inside = row >= 0 && row < A.V;
+  if (__ballot(mine && !inside) && lane == 0) atomicOr(A.status, NRL_RANK_E_TARGET_ROW);
+  bool excluded = false;
+  int bad = 0;
+  for (int64_t base = 0; base < xn; base += 64) {
+    const int64_t x = base + lane < xn ? A.excl_idx[xs + base + lane] : -1;
+    bad |= base + lane < xn && (x < 0 || x >= A.V);
+    for (int t = 0; t < nt; ++t) {
+      const int64_t rt = ((int64_t)__shfl((int)(row >> 32), t, 64) << 32) | (uint32_t)__shfl((int)(uint32_t)row, t, 64);
+      const bool hit = __ballot(x >= 0 && x == rt) != 0ull;
+      if (lane == t) excluded |= hit;
+    }
+  }
+  if (__ballot(bad) && lane == 0) atomicOr(A.status, NRL_TOPK_E_EXCLUDE);
+  if (!mine || !inside || excluded || (A.eligible && !A.eligible[row])) return;
+  const float s = A.tscore[ts + lane];
+  if (s != s) return;
+  int above = 0;
+  for (int i = 0; i < A.slices; ++i) above += A.tcnt[(ts + lane) * A.slices + i];
+  A.out_rank[ts + lane] = 1 + above;
+  A.out_score[ts + lane] = tk_unkey(score_key(s));    // (-0 comes back as +0, as from tk_merge_kernel)
+}
+
 static bool tk_shape_ok(int64_t B, int64_t V, int32_t D, int32_t k) {
   return B >= 0 && V >= 0 && V < ((int64_t)1 << 31) && D > 0 && D % 4 == 0 && D <= NRL_TOPK_MAX_D && k >= 1 && k <= NRL_TOPK_MAX_K;
 }
@@ -1072,6 +1291,81 @@ int nrl_topk_scores(const float* user_vec, const float* table, int64_t B, int64_
   NRL_TRY(carve_workspace(ws, ws_bytes, [&](Arena& a) { tk_layout(a, B, V, k, slices, TK_BU, &partial); }));
   TkArgs A = tk_args(user_vec, table, B, V, D, k, excl_idx, excl_off, eligible, partial, out_idx, out_score, status);
   return tk_launch("topk_scores", tk_scores_kernel, A, slices, 1, TK_BU, stream);
+}
+
+// the workspace of nrl_catalogue_ranks: the gathered target rows and their scores and owners, then the per-slice counts
+struct TkcWs {
+  float *gathered, *tscore;
+  int32_t *owner, *pcnt, *tcnt;
+};
+static void tkc_layout(Arena& a, int64_t B, int64_t V, int32_t D, int64_t n_targets, int32_t slices, TkcWs* w) {
+  int64_t lists, used, tps;
+  tk_plan(B, V, slices, TK_BU, lists, used, tps);
+  const size_t n = (size_t)n_targets;
+  w->gathered = a.take<float>(n * (size_t)D > 0 ? n * (size_t)D : 1);
+  w->tscore = a.take<float>(n > 0 ? n : 1);
+  w->owner = a.take<int32_t>(n > 0 ? n : 1);
+  w->pcnt = a.take<int32_t>((size_t)B * (size_t)lists > 0 ? (size_t)B * (size_t)lists : 1);
+  w->tcnt = a.take<int32_t>(n * (size_t)lists > 0 ? n * (size_t)lists : 1);
+}
+
+size_t nrl_catalogue_ranks_workspace_size(int64_t B, int64_t V, int32_t D, int64_t n_targets, int32_t slices) {
+  if (!tk_shape_ok(B, V, D, 1) || slices < 0 || n_targets < 0 || n_targets >= ((int64_t)1 << 31)) return 256;
+  return measure_workspace<TkcWs>([&](Arena& a, auto* w) { tkc_layout(a, B, V, D, n_targets, slices, w); });
+}
+
+int nrl_catalogue_ranks(const float* user_vec, const float* table, int64_t B, int64_t V, int32_t D, const int64_t* tgt_idx,
+                        const int64_t* tgt_off, int64_t n_targets, const int64_t* excl_idx, const int64_t* excl_off,
+                        const uint8_t* eligible, int32_t slices, int32_t* out_rank, float* out_score, int32_t* out_ranked,
+                        int32_t* status, void* ws, size_t ws_bytes, void* stream) {
+  NRL_REQUIRE(B >= 0 && V >= 0 && D >= 0 && slices >= 0 && n_targets >= 0, "catalogue_ranks: negative size");
+  NRL_TRY(tk_check("catalogue_ranks", B, V, D, 1, excl_idx, excl_off));
+  NRL_REQUIRE(n_targets < ((int64_t)1 << 31), "catalogue_ranks: at most 2^31 - 1 targets per call (got %lld)", (long long)n_targets);
+  NRL_REQUIRE(tgt_off || (!tgt_idx && n_targets == 0), "catalogue_ranks: tgt_idx without tgt_off");
+  NRL_REQUIRE(status, "catalogue_ranks: the status word is required");
+  if (B == 0) return NRL_OK;
+  NRL_REQUIRE(out_ranked && user_vec && (V == 0 || table) && (n_targets == 0 || (tgt_idx && out_rank && out_score)),
+              "catalogue_ranks: null argument");
+  TkcWs w;
+  NRL_TRY(carve_workspace(ws, ws_bytes, [&](Arena& a) { tkc_layout(a, B, V, D, n_targets, slices, &w); }));
+  int64_t lists, used, tps;
+  tk_plan(B, V, slices, TK_BU, lists, used, tps);
+  const int64_t blocks = ceil_div(B, TK_BU) * used;
+  NRL_REQUIRE(blocks < ((int64_t)1 << 31), "catalogue_ranks: grid too large (%lld workgroups)", (long long)blocks);
+  TkcArgs A;
+  static_cast<TkArgs&>(A) = tk_args(user_vec, table, B, V, D, 1, excl_idx, excl_off, eligible, nullptr, nullptr, out_score, status);
+  A.slices = (int32_t)used;
+  A.tiles_per_slice = (int32_t)tps;
+  A.tgt_idx = tgt_idx;
+  A.tgt_off = tgt_off;
+  A.n_targets = n_targets;
+  A.gathered = w.gathered;
+  A.tscore = w.tscore;
+  A.owner = w.owner;
+  A.pcnt = w.pcnt;
+  A.tcnt = w.tcnt;
+  A.out_rank = out_rank;
+  A.out_ranked = out_ranked;
+  hipStream_t st = (hipStream_t)stream;
+  if (n_targets > 0) {
+    tkc_init_kernel<<<(unsigned)n_targets, 64, 0, st>>>(A);
+    NRL_LAUNCH_CHECK();
+    tkc_owner_kernel<<<(unsigned)ceil_div(B, 256), 256, 0, st>>>(A);
+    NRL_LAUNCH_CHECK();
+    if (V > 0) {
+      tkc_target_kernel<<<(unsigned)ceil_div(n_targets, TK_BU), TK_THREADS, 0, st>>>(A);
+      NRL_LAUNCH_CHECK();
+    }
+  }
+  if (used > 0) {
+    // more than 64 KB of dynamic LDS needs the attribute; it belongs to the current device, so it is set per call
+    NRL_HIP(hipFuncSetAttribute((const void*)tkc_count_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    tkc_count_kernel<<<(unsigned)blocks, TK_THREADS, TKC_LDS, st>>>(A);
+    NRL_LAUNCH_CHECK();
+  }
+  tkc_finish_kernel<<<(unsigned)B, 64, 0, st>>>(A);
+  NRL_LAUNCH_CHECK();
+  return NRL_OK;
 }
 
 int nrl_topk_interest_scores(const float* interests, const float* gate, const float* table, int64_t B, int32_t K, int64_t V, int32_t D,

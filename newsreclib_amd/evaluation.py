@@ -252,6 +252,45 @@ class NewsVectorCache(_ImpressionCache):
 
 
     @torch.no_grad()
+    def rank_clicks(self, hist_idx: torch.Tensor, hist_sizes: torch.Tensor, click_idx: torch.Tensor, click_sizes: torch.Tensor,
+                    user_idx: Optional[torch.Tensor] = None, exclude_history: bool = True,
+                    eligible: Optional[torch.Tensor] = None):
+        """Where each user's held-out clicks land when the user is ranked against the WHOLE table -> (rank int32 (n_clicks),
+        score fp32 (n_clicks), ranked int32 (B), status): ``recommend``'s user vectors, scores, order, exclusion of the history
+        and ``eligible``, with ``ops.catalogue_ranks`` counting where ``recommend`` selects.  ``rank`` is the click's 1-based
+        place among the ``ranked[b]`` news the user could be recommended, 0 when the click is not one of them (in the history,
+        ineligible, outside the table); ``rank <= k`` exactly when the click is slot ``rank - 1`` of ``recommend(k)``.  At most
+        ``ops.RANK_MAX_TARGETS`` clicks per user (``ValueError`` otherwise, from the host sizes).  Same contract as ``recommend``:
+        ``hist_idx`` and ``click_idx`` on the GPU, ``hist_sizes`` and ``click_sizes`` on the host, nothing read back; ``status``
+        (``ops.RANK_FLAGS``) stays on the device.  ``metrics.full_rank_metrics`` turns the result into MRR / nDCG@k / recall@k."""
+        if not getattr(self.module, "dot_product_scorer", False):
+            raise NotImplementedError(
+                f"{type(self.module).__name__} does not score a news by one dot product with a candidate-independent user vector "
+                "(no `dot_product_scorer`): only the dot-product families are served by `rank_clicks` so far; the count stage is "
+                "not yet wired under the MINER, DKN and NPA scorers")
+        if not hist_idx.is_cuda or not click_idx.is_cuda:
+            raise RuntimeError(f"newsreclib_amd: `hist_idx` and `click_idx` must live on the GPU (got {hist_idx.device} and "
+                               f"{click_idx.device}); there is no CPU path")
+        cs = click_sizes.detach().cpu().long()              # host sizes: the limit and the offsets cost no read-back
+        if cs.numel() != int(hist_sizes.numel()):
+            raise ValueError("newsreclib_amd: hist_sizes and click_sizes must have one entry per user")
+        if cs.numel() and int(cs.max()) > ops.RANK_MAX_TARGETS:
+            raise ValueError(f"newsreclib_amd: rank_clicks takes at most {ops.RANK_MAX_TARGETS} clicks per user "
+                             f"(got {int(cs.max())})")
+        if self.vectors is None:
+            self.build()
+        dev = self.table.device
+        hist_idx, click_idx = hist_idx.to(dev).long(), click_idx.to(dev).long()
+        meta = self._user_meta(hist_sizes, user_idx)
+        click_off = torch.cat([torch.zeros(1, dtype=torch.int64), torch.cumsum(cs, 0)]).pin_memory().to(dev, non_blocking=True)
+        hv = ops.embedding_gather(self.vectors, hist_idx.reshape(-1, 1)).reshape(-1, self.vectors.shape[1])
+        with eval_mode(self.module):
+            user = self.module.user_vectors(hv, meta)
+        excl = (hist_idx, meta["hist_offsets"]) if exclude_history else (None, None)
+        return ops.catalogue_ranks(user, self.vectors, click_idx, click_off, excl[0], excl[1],
+                                   eligible.to(dev) if eligible is not None else None)
+
+    @torch.no_grad()
     def recommend_interests(self, hist_idx: torch.Tensor, hist_sizes: torch.Tensor, k: int, user_idx: Optional[torch.Tensor] = None,
                             exclude_history: bool = True, eligible: Optional[torch.Tensor] = None,
                             bias: Optional[torch.Tensor] = None):
@@ -364,6 +403,11 @@ class MannerVectorCache(_ImpressionCache):
                                   "score to rank the whole table by; recommend from one sub-model's NewsVectorCache instead, or "
                                   "name the population: `recommend_ensemble` z-scores over every row a user may be recommended")
 
+    def rank_clicks(self, *args, **kwargs):
+        raise NotImplementedError("only the dot-product families are served by `rank_clicks` so far (NewsVectorCache over a "
+                                  "`dot_product_scorer` module): MANNeR's ensemble of standardised scores is not yet counted; "
+                                  "rank the clicks with one sub-model's NewsVectorCache instead")
+
     @torch.no_grad()
     def recommend_ensemble(self, hist_idx: torch.Tensor, hist_sizes: torch.Tensor, k: int, user_idx: Optional[torch.Tensor] = None,
                            exclude_history: bool = True, eligible: Optional[torch.Tensor] = None, return_stats: bool = False):
@@ -454,6 +498,10 @@ class NpaFeatureCache(_ImpressionCache):
                                   "is no (V, D) table to rank with one user vector, so the whole catalogue cannot be scored by "
                                   "one GEMM + top-k; `recommend_pooled` ranks it from the cached feature maps (two GEMMs and a "
                                   "softmax over the tokens per user and news, fused)")
+
+    def rank_clicks(self, *args, **kwargs):
+        raise NotImplementedError("only the dot-product families are served by `rank_clicks` so far (NewsVectorCache over a "
+                                  "`dot_product_scorer` module): NPA's personalized-pooling score is not yet counted")
 
     @torch.no_grad()
     def recommend_pooled(self, hist_idx: torch.Tensor, hist_sizes: torch.Tensor, k: int, user_idx: Optional[torch.Tensor] = None,
@@ -574,3 +622,41 @@ def recommend_users(cache: NewsVectorCache, users: Sequence[Dict], k: int, batch
         ids = [int(u["user_id"]) if "user_id" in u else lo + j + 1 for j, u in enumerate(chunk)]
         out.update(format_recommendations(ids, packed[:, :k].long(), packed[:, k:2 * k].float(), news_ids))
     return out
+
+
+def evaluate_full_rank(cache: NewsVectorCache, users: Sequence[Dict], top_k_list: Sequence[int] = (5, 10), batch_size: int = 512,
+                       eligible: Optional[torch.Tensor] = None) -> Dict[str, float]:
+    """Full-catalogue ranking metrics of held-out clicks: ``cache.rank_clicks`` over a list of users ({"hist": idx tensor,
+    "clicks": idx tensor[, "user_idx"]}), batched as ``recommend_users`` batches them, then ``metrics.full_rank_metrics``
+    (``mrr``, ``ndcg@k``, ``recall@k``, ``hit@k``, ``auc_user``; every click is ranked against every news the user could be
+    recommended, not against an impression's candidates).  The ranks, the click counts and the populations of all batches stay
+    on the device; one device-to-host copy at the end.  The OR of the batches' status words (``ops.RANK_FLAGS``: each flag is
+    handled by the kernel) is passed on as one warning."""
+    from .metrics import full_rank_metrics
+    dev = cache.table.device
+    ranks, sizes, pops, words = [], [], [], []
+    for lo in range(0, len(users), batch_size):
+        chunk = users[lo:lo + batch_size]
+        hs = torch.tensor([len(u["hist"]) for u in chunk])
+        cs = torch.tensor([len(u["clicks"]) for u in chunk])
+        hist = torch.cat([torch.as_tensor(u["hist"]).long() for u in chunk]).to(dev)
+        clicks = torch.cat([torch.as_tensor(u["clicks"]).long() for u in chunk]).to(dev)
+        uidx = torch.stack([torch.as_tensor(u["user_idx"]) for u in chunk]) if "user_idx" in chunk[0] else None
+        rank, _, ranked, status = cache.rank_clicks(hist, hs, clicks, cs, user_idx=uidx, eligible=eligible)
+        ranks.append(rank)
+        sizes.append(cs.pin_memory().to(dev, non_blocking=True))
+        pops.append(ranked)
+        words.append(status)
+    if not ranks:
+        return full_rank_metrics(torch.zeros(0, dtype=torch.int32), torch.zeros(0, dtype=torch.int64),
+                                 torch.zeros(0, dtype=torch.int32), top_k_list)
+    word = words[0]
+    for w in words[1:]:
+        word = torch.bitwise_or(word, w)
+    n, B = sum(int(r.numel()) for r in ranks), sum(int(p.numel()) for p in pops)
+    packed = torch.cat([torch.cat(ranks).long(), torch.cat(sizes).long(), torch.cat(pops).long(), word.reshape(1).long()]).cpu()
+    word = int(packed[-1])
+    if word:                                                # the kernel has dealt with each of these; the caller should know
+        import warnings
+        warnings.warn("evaluate_full_rank: " + "; ".join(msg for bit, msg in ops.RANK_FLAGS.items() if word & bit))
+    return full_rank_metrics(packed[:n], packed[n:n + B], packed[n + B:n + 2 * B], top_k_list)

@@ -65,6 +65,60 @@ def ranking_metrics(preds: torch.Tensor, targets: torch.Tensor, cand_news_size: 
     return out
 
 
+def full_rank_metrics(rank: torch.Tensor, click_sizes: torch.Tensor, ranked: torch.Tensor,
+                      top_k_list: Sequence[int] = (5, 10)) -> Dict[str, float]:
+    """Full-catalogue ranking metrics from ranks alone (``ops.catalogue_ranks`` / ``NewsVectorCache.rank_clicks``): ``rank``
+    (n_clicks) the 1-based place of every held-out click among the news its user could be recommended, 0 = the click is not one
+    of them and does not count; ``click_sizes`` (B) the clicks per user, in order; ``ranked`` (B) the size N of each user's
+    population.  Plain torch on whatever device the inputs share, in float64.  With r_1 < ... < r_P a user's valid ranks:
+
+    * ``mrr``       1 / r_1;
+    * ``ndcg@k``    sum_{r_j <= k} 1 / log2(r_j + 1)  /  sum_{j <= min(P, k)} 1 / log2(j + 1);
+    * ``recall@k``  #{r_j <= k} / P;   ``hit@k``  [r_1 <= k];
+    * ``auc_user``  1 - sum_j (r_j - j) / (P (N - P)): the share of (click, other news) pairs ranked the right way round.  The
+      ranks come with ties already BROKEN by row (equal scores rank by ascending row), not averaged as ``_global_auc`` does.
+
+    Each is the mean over users; a user without a valid click counts 0 and stays in the mean (``ranking_metrics``' convention,
+    torchmetrics' ``empty_target_action="neg"``), and so does, for ``auc_user``, a user with N = P.  ``mrr`` and ``ndcg@k`` equal
+    ``ranking_metrics`` run on one impression per user whose candidate list is the user's whole population in ascending row
+    order."""
+    dev = rank.device
+    sizes, N = click_sizes.to(dev).long(), ranked.to(dev).double()
+    B = int(sizes.numel())
+    keys = ["mrr"] + [f"{m}@{k}" for k in top_k_list for m in ("ndcg", "recall", "hit")] + ["auc_user"]
+    if B == 0:
+        return {k: 0.0 for k in keys}
+    C = max(int(sizes.max()), 1)
+    off = torch.cumsum(sizes, 0) - sizes
+    user = torch.repeat_interleave(torch.arange(B, device=dev), sizes, output_size=int(rank.numel()))
+    col = torch.arange(rank.numel(), device=dev) - off[user]
+    big = torch.iinfo(torch.int64).max
+    dense = torch.full((B, C), big, dtype=torch.int64, device=dev)
+    r = rank.long()
+    dense[user, col] = torch.where(r > 0, r, torch.full_like(r, big))
+    dense = torch.sort(dense, dim=1).values                 # r_1 <= r_2 <= ..., the clicks that do not count at the end
+    valid = dense < big
+    P = valid.sum(1).double()
+    has = P > 0
+    rd = torch.where(valid, dense, torch.ones_like(dense)).double()
+    zero = torch.zeros(B, dtype=torch.float64, device=dev)
+    out = {"mrr": float(torch.where(has, 1.0 / rd[:, 0], zero).mean())}
+    gain = torch.where(valid, 1.0 / torch.log2(rd + 1.0), torch.zeros_like(rd))
+    ideal = torch.cumsum(1.0 / torch.log2(torch.arange(1, C + 1, device=dev, dtype=torch.float64) + 1.0), 0)
+    for k in top_k_list:
+        inside = valid & (dense <= k)
+        dcg = (gain * inside).sum(1)
+        idcg = ideal[(torch.minimum(P, torch.full_like(P, min(int(k), C))).long() - 1).clamp_min(0)]
+        out[f"ndcg@{k}"] = float(torch.where(has, dcg / idcg, zero).mean())
+        out[f"recall@{k}"] = float(torch.where(has, inside.sum(1).double() / P.clamp_min(1.0), zero).mean())
+        out[f"hit@{k}"] = float((has & (dense[:, 0] <= k)).double().mean())
+    j = torch.arange(1, C + 1, device=dev, dtype=torch.float64)[None, :]
+    wrong = torch.where(valid, rd - j, torch.zeros_like(rd)).sum(1)
+    pairs = P * (N - P)
+    out["auc_user"] = float(torch.where(has & (pairs > 0), 1.0 - wrong / pairs.clamp_min(1.0), zero).mean())
+    return out
+
+
 def aspect_metrics(preds: torch.Tensor, cand_aspects: torch.Tensor, hist_aspects: torch.Tensor,
                    cand_news_size: torch.Tensor, hist_news_size: torch.Tensor, num_classes: int,
                    top_k_list: Sequence[int] = (5, 10), prefix: str = "categ") -> Dict[str, float]:

@@ -765,6 +765,53 @@ def topk_scores(user_vec: torch.Tensor, table: torch.Tensor, k: int, excl_idx: O
     return idx, score, status
 
 
+RANK_MAX_TARGETS = 32
+# the status word of ``catalogue_ranks``: the flags of ``topk_scores`` it shares, in its own words, and its two own bits
+RANK_FLAGS = {1: TOPK_FLAGS[1],
+              2: "excl_off decreases or leaves its range (that user's ranks and population are 0)",
+              4: "a NaN score of an eligible, not excluded row (that row is left out of that user's population)",
+              16: "tgt_off decreases or leaves its range, or a user owns more than 32 targets (that user's ranks are 0)",
+              32: "a target index is outside [0, V) (its rank is 0)"}
+
+
+def catalogue_ranks(user_vec: torch.Tensor, table: torch.Tensor, tgt_idx: torch.Tensor, tgt_off: torch.Tensor,
+                    excl_idx: Optional[torch.Tensor] = None, excl_off: Optional[torch.Tensor] = None,
+                    eligible: Optional[torch.Tensor] = None, slices: int = 0):
+    """``nrl_catalogue_ranks``: where the held-out rows ``tgt_idx`` (int64) / ``tgt_off`` (B + 1 int64, ragged per user, at most
+    ``RANK_MAX_TARGETS`` per user) land when each row of ``user_vec`` (B, D) is ranked against the whole ``table`` (V, D) ->
+    (rank int32 (n_tgt), score fp32 (n_tgt), ranked int32 (B), status (1) int32).  ``rank`` is 1 + the number of rows of the
+    user's population (eligible, not excluded, not NaN-scored) that ``topk_scores`` orders above the target, 0 when the target
+    is not itself in the population (its ``score`` is then ``-inf``); ``ranked`` is the size of the population.  Scores, order,
+    ``excl_idx`` / ``excl_off`` and ``eligible`` are those of ``topk_scores``, bit for bit: ``rank <= k`` exactly when the target is
+    slot ``rank - 1`` of the user's top-k list.  The (B, V) score matrix is never materialised.  ``status`` (``RANK_FLAGS``)
+    stays on the device -- nothing here synchronises with the host."""
+    lib = _lib.load()
+    user_vec, table = _chk(user_vec, torch.float32, "user_vec"), _chk(table, torch.float32, "table")
+    if user_vec.dim() != 2 or table.dim() != 2 or user_vec.shape[1] != table.shape[1]:
+        raise ValueError(f"newsreclib_amd: user_vec (B, D) and table (V, D) expected, got {tuple(user_vec.shape)} and "
+                         f"{tuple(table.shape)}")
+    B, D, V = int(user_vec.shape[0]), int(user_vec.shape[1]), int(table.shape[0])
+    tgt_idx, tgt_off = _chk(tgt_idx, torch.int64, "tgt_idx"), _chk(tgt_off, torch.int64, "tgt_off")
+    if tgt_off.numel() != B + 1:
+        raise ValueError("newsreclib_amd: tgt_off must have B + 1 entries")
+    n_tgt = int(tgt_idx.numel())
+    # (the kernel validates the offsets against n_tgt itself; as for excl_off, one beyond the list is turned into one it rejects)
+    tgt_off = torch.where(tgt_off > n_tgt, torch.full_like(tgt_off, -1), tgt_off)
+    excl_idx, excl_off, eligible = _topk_masks(excl_idx, excl_off, eligible, B, V)
+    dev = user_vec.device
+    rank = torch.empty(n_tgt, dtype=torch.int32, device=dev)
+    score = torch.empty(n_tgt, dtype=torch.float32, device=dev)
+    ranked = torch.empty(B, dtype=torch.int32, device=dev)
+    status = torch.zeros(1, dtype=torch.int32, device=dev)
+    ws = workspace(lib.nrl_catalogue_ranks_workspace_size(B, V, D, n_tgt, int(slices)), dev)
+    ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
+    _lib.check(lib.nrl_catalogue_ranks(user_vec.data_ptr(), table.data_ptr(), B, V, D, tgt_idx.data_ptr(), tgt_off.data_ptr(), n_tgt,
+                                       ptr(excl_idx), ptr(excl_off), ptr(eligible), int(slices), rank.data_ptr(), score.data_ptr(),
+                                       ranked.data_ptr(), status.data_ptr(), ws.data_ptr(), ws.numel(), _stream()),
+               "nrl_catalogue_ranks")
+    return rank, score, ranked, status
+
+
 TOPK_MAX_INTERESTS = 64
 
 
