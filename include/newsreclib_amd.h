@@ -1211,6 +1211,40 @@ int nrl_catalogue_ranks(const float* user_vec, const float* table, int64_t B, in
                         int32_t* out_rank /* n_targets */, float* out_score /* n_targets */, int32_t* out_ranked /* B */,
                         int32_t* status, void* ws, size_t ws_bytes, void* stream);
 
+/* nrl_catalogue_interest_ranks / nrl_catalogue_relu_ranks / nrl_catalogue_pooled_ranks: nrl_catalogue_ranks under the scores of
+ *   nrl_topk_interest_scores (MINER: interests (B, K, D), gate (B, K, D) or null, mode 0 max / 1 mean / 2 weighted), of
+ *   nrl_topk_relu_scores (DKN: q (B, Hd), proj (V, Hd), w2 (Hd), b2 (1), all on the device) and of nrl_topk_pooled_scores (NPA:
+ *   q (B, F), user (B, F), features (V, L, F), 16-byte aligned).  Population, order, targets, ownership of slots, flags, blanking rules,
+ *   determinism and outputs are those of nrl_catalogue_ranks; shape limits are those of the matching nrl_topk_* call (k aside)
+ *   plus NRL_RANK_MAX_TARGETS.
+ *   Bit identity: the count walk runs the tile producer of the matching scores kernel (the same device functions), and the target
+ *     scores are computed by the same chain -- MINER: the tile product of the owners' K interest (and gate) rows with the gathered
+ *     target rows, then the same aggregate; DKN: the chain s = b2; s = fma(w2[j], relu(proj[row, j] + q[u, j]), s) in ascending
+ *     j, read in place; NPA: the per-token tile products of the owners' (q, user) rows with the targets' feature maps, read in
+ *     place through tgt_idx (nothing is gathered: a map is L F floats), tokens ascending, the same online softmax.  So out_score[j] has the bits the matching nrl_topk_* call returns for that (user, row), and for every
+ *     k <= NRL_TOPK_MAX_K: out_rank[j] = r <= k if and only if out_idx[u, r - 1] == tgt_idx[j].  K = 1 (modes 0 and 1) is
+ *     nrl_catalogue_ranks bit for bit.  A NaN in a user's interests, gate, q or user vector makes that user's scores NaN: its population is
+ *     empty, its ranks are 0 and NRL_TOPK_E_NAN is set; the other users are unchanged.
+ *   Workspace: nrl_catalogue_ranks_workspace_size(B, V, D, n_targets, slices) with B in users for the interests (its layout for
+ *     64 / K users per workgroup never needs more), nrl_catalogue_ranks_workspace_size(B, V, 4, n_targets, slices) for the DNN
+ *     and the pooling scorer (nothing is gathered: O(n_targets + (B + n_targets) slices), whatever L and F).  B == 0, V == 0, n_targets == 0 and the refusals (NRL_E_INVALID, NRL_E_WORKSPACE, before any
+ *     launch) as for nrl_catalogue_ranks. */
+int nrl_catalogue_interest_ranks(const float* interests, const float* gate, const float* table, int64_t B, int32_t K, int64_t V,
+                                 int32_t D, int32_t mode, const int64_t* tgt_idx, const int64_t* tgt_off, int64_t n_targets,
+                                 const int64_t* excl_idx, const int64_t* excl_off, const uint8_t* eligible, int32_t slices,
+                                 int32_t* out_rank /* n_targets */, float* out_score /* n_targets */, int32_t* out_ranked /* B */,
+                                 int32_t* status, void* ws, size_t ws_bytes, void* stream);
+int nrl_catalogue_relu_ranks(const float* q, const float* proj, const float* w2, const float* b2, int64_t B, int64_t V, int32_t Hd,
+                             const int64_t* tgt_idx, const int64_t* tgt_off, int64_t n_targets, const int64_t* excl_idx,
+                             const int64_t* excl_off, const uint8_t* eligible, int32_t slices, int32_t* out_rank /* n_targets */,
+                             float* out_score /* n_targets */, int32_t* out_ranked /* B */, int32_t* status, void* ws,
+                             size_t ws_bytes, void* stream);
+int nrl_catalogue_pooled_ranks(const float* q, const float* user, const float* features, int64_t B, int64_t V, int32_t L, int32_t F,
+                               const int64_t* tgt_idx, const int64_t* tgt_off, int64_t n_targets, const int64_t* excl_idx,
+                               const int64_t* excl_off, const uint8_t* eligible, int32_t slices, int32_t* out_rank /* n_targets */,
+                               float* out_score /* n_targets */, int32_t* out_ranked /* B */, int32_t* status, void* ws,
+                               size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -22,7 +22,8 @@
 //       code instead of a product; the other stages unchanged.
 //   tkp_scores_kernel  NPA's personalized pooling: per token of the cached feature maps a two-operand tile product kept in
 //       registers and folded into an online softmax per (user, row); the other stages unchanged.
-//   tkc_*_kernel       the rank of held-out rows: the same walk with a consumer that counts instead of selects.
+//   tkc_*_kernel       the rank of held-out rows: the same walk with a consumer that counts instead of selects;
+//   tkic_* / tkrc_* / tkpc_*  that consumer under the tile producers of tki_ / tkr_ / tkp_scores_kernel.
 //   tk_merge_kernel    one wave per user: validates the user's offsets and exclusion indices (status flags), merges the `slices`
 //       partial lists with the same insertion and writes (row, score) or (-1, -inf).
 // The stages (exclusion cache, eligibility, tile product, per-user selection, flush) are written once, as inlined device functions
@@ -183,9 +184,13 @@ __device__ __forceinline__ void tk_fill_eligible(const uint8_t* eligible, int v0
 // `acc`: the lane holds tile row wm * 32 + i * 16 + 4 g + r, column wn * 64 + j * 16 + l15 in acc[a][i][j][r].  `lds` holds the
 // operand tiles, NA x [2][TK_BK][TK_LDA] and then [2][TK_BK][TK_LDB], all staged against ONE pass over the table tile.  Ends with
 // the workgroup synchronised: `lds` is free.
-template <int NA>
+// ROWS: tile column c is not table row v0 + c but table row rows[v0 + c] (v0 + c < V, the length of `rows`), read in place at
+// table + rows[v0 + c] * ldt, and a zero row where that index is outside [0, table_rows): the products of a gathered table
+// without the gather.
+template <int NA, bool ROWS = false>
 __device__ __forceinline__ void tk_tile_accumulate(const float* const (&pa)[NA], bool ua_ok, const float* table, int64_t ldt, int v0,
-                                                   int V, int D, float* lds, tk_f32x4 (&acc)[NA][2][4]) {
+                                                   int V, int D, float* lds, tk_f32x4 (&acc)[NA][2][4],
+                                                   const int64_t* rows = nullptr, int64_t table_rows = 0) {
   float* const As = lds;
   float* const Bs = As + NA * 2 * TK_BK * TK_LDA;
   const int tid = threadIdx.x, lane = tid & 63;
@@ -200,8 +205,14 @@ __device__ __forceinline__ void tk_tile_accumulate(const float* const (&pa)[NA],
 #pragma unroll
   for (int c = 0; c < 2; ++c) {
     const int64_t v = (int64_t)v0 + srow + c * 64;
-    vb_ok[c] = v < V;
-    pb[c] = table + (int64_t)(vb_ok[c] ? v : V - 1) * ldt;
+    if constexpr (ROWS) {
+      const int64_t r = v < V ? rows[v] : -1;
+      vb_ok[c] = r >= 0 && r < table_rows;
+      pb[c] = table + (vb_ok[c] ? r : 0) * ldt;
+    } else {
+      vb_ok[c] = v < V;
+      pb[c] = table + (int64_t)(vb_ok[c] ? v : V - 1) * ldt;
+    }
   }
   float4 ra[NA], rb[2];
   auto load_tiles = [&](int k0) {                    // unconditional loads from clamped addresses; masked when staged
@@ -471,13 +482,27 @@ __device__ __forceinline__ float tki_aggregate(const float* s, const float* lg, 
   return a / (float)K;
 }
 
+// The tile producer of the multi-interest kernels (scores and count): the products of the staged interest (and gate) rows with the
+// table tile at v0 into the score tile(s) from `sc` on, then the aggregation: the K rows of each of the tile's `nu` users, one column
+// per thread, into the user's first row (nobody else reads or writes them).  Ends with the workgroup synchronised.
+template <bool GATE>
+__device__ __forceinline__ void tki_tile(const float* const (&pa)[GATE ? 2 : 1], bool ua_ok, const float* table, int v0, int V, int D,
+                                         float* sc, int nu, int K, int mode) {
+  const float* const lg = sc + TK_BU * TK_SCLD;
+  tk_tile_product<GATE ? 2 : 1>(pa, ua_ok, table, v0, V, D, sc);
+  for (int i = threadIdx.x; i < nu * TK_BV; i += TK_THREADS) {
+    const int at = (i / TK_BV) * K * TK_SCLD + (i % TK_BV);
+    sc[at] = tki_aggregate<GATE>(sc + at, lg + at, K, mode);
+  }
+  __syncthreads();
+}
+
 template <bool GATE>
 __global__ __launch_bounds__(TK_THREADS) void tki_scores_kernel(TkiArgs A) {
   extern __shared__ __attribute__((aligned(16))) unsigned char tk_smem[];
   constexpr int NA = GATE ? 2 : 1;
   const int K = A.K, Ut = A.Ut;
-  float* const sc = reinterpret_cast<float*>(tk_smem);                       // [TK_BU][TK_SCLD] the s_j; with a gate
-  float* const lg = sc + TK_BU * TK_SCLD;                                    // [TK_BU][TK_SCLD] the l_j follow
+  float* const sc = reinterpret_cast<float*>(tk_smem);                       // [TK_BU][TK_SCLD] the s_j; with a gate the l_j follow
   unsigned long long* const lists = reinterpret_cast<unsigned long long*>(sc + NA * TK_BU * TK_SCLD);      // [Ut][k]
   int64_t* const xs = reinterpret_cast<int64_t*>(lists + Ut * A.k);          // [Ut]
   int32_t* const xl = reinterpret_cast<int32_t*>(xs + Ut);                   // [Ut][TK_XCAP]
@@ -510,14 +535,7 @@ __global__ __launch_bounds__(TK_THREADS) void tki_scores_kernel(TkiArgs A) {
   for (int vt = 0; vt < nvt; ++vt) {
     const int v0 = v_begin + vt * TK_BV;
     tk_fill_eligible(A.eligible, v0, V, el);
-    tk_tile_product<NA>(pa, ua_ok, A.table, v0, V, A.D, sc);
-
-    // aggregation: the K rows of user ul, one column per thread, into the user's first row (nobody else reads or writes them)
-    for (int i = tid; i < nu * TK_BV; i += TK_THREADS) {
-      const int at = (i / TK_BV) * K * TK_SCLD + (i % TK_BV);
-      sc[at] = tki_aggregate<GATE>(sc + at, lg + at, K, A.mode);
-    }
-    __syncthreads();
+    tki_tile<GATE>(pa, ua_ok, A.table, v0, V, A.D, sc, nu, K, A.mode);
 
     // selection: wave w owns users w, w + 4, ... of the tile and their lists
     const bool e_0 = el[lane] != 0, e_1 = el[64 + lane] != 0;
@@ -775,6 +793,91 @@ __device__ __forceinline__ float tkr_step(float w, float p, float q, float s) {
   return fmaf(w, x < 0.f ? 0.f : x, s);
 }
 
+// The tile producer of the DNN count kernel, in three pieces.  It is tkr_scores_kernel's producer, DUPLICATED rather than shared:
+// with the scores kernel calling these functions the compiler scheduled its chains differently and the whole call measured
+// 2 - 5 % slower at B = 512, V = 65,536 (profiles/topk_scores_refactor_before_after.txt), so that kernel keeps its own text.  The
+// two must stay the same chain, line for line: tests/test_gpu_catalogue_rank_scorers.py::test_consistency_with_topk_on_real_values
+// compares the score bits of the two.
+// q of the tile's `nu` users from u0 on and w2 into LDS: qs[TK_BU][ldq], zero past Hd and past the last user, then w2s[ldq]
+__device__ __forceinline__ void tkr_stage_users(const float* q, const float* w2, int64_t u0, int nu, int Hd, float* qs, float* w2s) {
+  const int tid = threadIdx.x, ldq = tkr_ldq(Hd);
+  for (int i = tid; i < TK_BU * ldq; i += TK_THREADS) {
+    const int ul = i / ldq, j = i - ul * ldq;
+    qs[i] = (ul < nu && j < Hd) ? q[(u0 + ul) * Hd + j] : 0.f;
+  }
+  for (int i = tid; i < ldq; i += TK_THREADS) w2s[i] = i < Hd ? w2[i] : 0.f;
+}
+
+// a thread's staging walk over a proj tile: element e = tid, tid + 256, ... of the tile is column e % Hd of tile row e / Hd
+struct TkrWalk {
+  int row0, col0, drow, dcol;
+};
+__device__ __forceinline__ TkrWalk tkr_walk(int Hd) {
+  const int tid = threadIdx.x, row0 = tid / Hd, drow = TK_THREADS / Hd;
+  return TkrWalk{row0, tid - row0 * Hd, drow, TK_THREADS - drow * Hd};
+}
+
+// The scores of the wave's 16 users (tile rows ul_begin ...; `qw` their q rows) for the 128 proj rows from v0 on, left in the score
+// tile `sc`, which holds the staged proj tile until every chain is complete.  Ends with the workgroup synchronised.
+__device__ __forceinline__ void tkr_tile(const float* table, int v0, int V, int Hd, const TkrWalk& W, float* sc, const float* qw,
+                                         const float* w2s, float b2, int ul_begin) {
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int ldp = tkr_ldp(Hd), ldq = tkr_ldq(Hd);
+  const float* const p0 = sc + lane * ldp;                                   // this lane's two proj rows
+  const float* const p1 = sc + (64 + lane) * ldp;
+  {
+    const float* const src = table + (int64_t)v0 * Hd;                       // the tile's rows are contiguous
+    const int inside = (V - v0 < TK_BV ? V - v0 : TK_BV) * Hd;               // rows from V on are zero (and not eligible)
+    int row = W.row0, col = W.col0;
+    for (int e = tid; e < TK_BV * Hd; e += TK_THREADS) {
+      sc[row * ldp + col] = e < inside ? src[e] : 0.f;
+      row += W.drow;
+      col += W.dcol;
+      if (col >= Hd) {
+        col -= Hd;
+        ++row;
+      }
+    }
+  }
+  __syncthreads();
+
+  float acc[TK_USERS_PER_WAVE][2];
+#pragma unroll
+  for (int u = 0; u < TK_USERS_PER_WAVE; ++u) acc[u][0] = acc[u][1] = b2;
+  int j = 0;
+  for (; j + 4 <= Hd; j += 4) {
+    const float a0[4] = {p0[j], p0[j + 1], p0[j + 2], p0[j + 3]}, a1[4] = {p1[j], p1[j + 1], p1[j + 2], p1[j + 3]};
+    const float4 w = *reinterpret_cast<const float4*>(w2s + j);
+    const float wj[4] = {w.x, w.y, w.z, w.w};
+#pragma unroll
+    for (int u = 0; u < TK_USERS_PER_WAVE; ++u) {
+      const float4 q4 = *reinterpret_cast<const float4*>(qw + u * ldq + j);
+      const float qj[4] = {q4.x, q4.y, q4.z, q4.w};
+#pragma unroll
+      for (int t = 0; t < 4; ++t) {
+        acc[u][0] = tkr_step(wj[t], a0[t], qj[t], acc[u][0]);
+        acc[u][1] = tkr_step(wj[t], a1[t], qj[t], acc[u][1]);
+      }
+    }
+  }
+  for (; j < Hd; ++j) {
+    const float a0 = p0[j], a1 = p1[j], w = w2s[j];
+#pragma unroll
+    for (int u = 0; u < TK_USERS_PER_WAVE; ++u) {
+      const float q = qw[u * ldq + j];
+      acc[u][0] = tkr_step(w, a0, q, acc[u][0]);
+      acc[u][1] = tkr_step(w, a1, q, acc[u][1]);
+    }
+  }
+  __syncthreads();                                    // every chain is complete: the proj tile gives way to the scores
+#pragma unroll
+  for (int u = 0; u < TK_USERS_PER_WAVE; ++u) {
+    sc[(ul_begin + u) * TK_SCLD + lane] = acc[u][0];
+    sc[(ul_begin + u) * TK_SCLD + 64 + lane] = acc[u][1];
+  }
+  __syncthreads();
+}
+
 __global__ __launch_bounds__(TK_THREADS) void tkr_scores_kernel(TkrArgs A) {
   extern __shared__ __attribute__((aligned(16))) unsigned char tk_smem[];
   float* const sc = reinterpret_cast<float*>(tk_smem);                       // [TK_BU][TK_SCLD]; before: proj tile [TK_BV][ldp]
@@ -905,6 +1008,48 @@ constexpr size_t TKP_EXTRA_LDS = (size_t)(TKP_OPERAND_FLOATS - TK_BU * TK_SCLD) 
 static_assert(TKP_OPERAND_FLOATS >= TK_BU * TK_SCLD && TKP_EXTRA_LDS % 16 == 0, "the score tile lives inside the operand tiles");
 static_assert(tk_lds_bytes(1, TK_BU, NRL_TOPK_MAX_K) + TKP_EXTRA_LDS <= 160 * 1024, "the largest layout fits");
 
+// The tile producer of the pooling kernels (scores, count and target): per token one pass of tk_tile_accumulate<2> with the row
+// operands q (pa[0]) and user (pa[1]) over the feature maps, folded into the online softmax in registers; o / l is left in the
+// score tile `sc`, which holds the operand tiles until then.  ROWS / rows / table_rows as for tk_tile_accumulate.  Ends with the
+// workgroup synchronised.
+template <bool ROWS>
+__device__ __forceinline__ void tkp_tile(const float* const (&pa)[2], bool ua_ok, const float* table, int64_t ldt, int v0, int V, int L,
+                                         int F, float* sc, const int64_t* rows = nullptr, int64_t table_rows = 0) {
+  tk_f32x4 m[2][4], l[2][4], o[2][4];
+#pragma unroll
+  for (int i = 0; i < 2; ++i)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      m[i][j] = tk_f32x4{-INFINITY, -INFINITY, -INFINITY, -INFINITY};
+      l[i][j] = o[i][j] = tk_f32x4{0.f, 0.f, 0.f, 0.f};
+    }
+  for (int t = 0; t < L; ++t) {
+    tk_f32x4 acc[2][2][4];                          // [0]: the logits a, [1]: the values s
+    tk_tile_accumulate<2, ROWS>(pa, ua_ok, table + (int64_t)t * F, ldt, v0, V, F, sc, acc, rows, table_rows);
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const float a = acc[0][i][j][r], mo = m[i][j][r];
+          const float mn = fmaxf(mo, a);            // a NaN logit leaves the maximum alone and arrives through p
+          const float keep = __expf(mo - mn), p = __expf(a - mn);
+          l[i][j][r] = fmaf(l[i][j][r], keep, p);
+          o[i][j][r] = fmaf(o[i][j][r], keep, __fmul_rn(p, acc[1][i][j][r]));
+          m[i][j][r] = mn;
+        }
+  }
+#pragma unroll
+  for (int i = 0; i < 2; ++i)
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) o[i][j][r] = __fdiv_rn(o[i][j][r], l[i][j][r]);
+  tk_store_fragments(o, sc);                        // (the last pass ended synchronised: the operand tiles are dead)
+  __syncthreads();
+}
+
 __global__ __launch_bounds__(TK_THREADS, 2) void tkp_scores_kernel(TkpArgs A) {
   extern __shared__ __attribute__((aligned(16))) unsigned char tk_smem[];
   float* const sc = reinterpret_cast<float*>(tk_smem);                       // operand tiles; afterwards [TK_BU][TK_SCLD] scores
@@ -939,40 +1084,7 @@ __global__ __launch_bounds__(TK_THREADS, 2) void tkp_scores_kernel(TkpArgs A) {
   for (int vt = 0; vt < nvt; ++vt) {
     const int v0 = v_begin + vt * TK_BV;
     tk_fill_eligible(A.eligible, v0, V, el);
-
-    tk_f32x4 m[2][4], l[2][4], o[2][4];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        m[i][j] = tk_f32x4{-INFINITY, -INFINITY, -INFINITY, -INFINITY};
-        l[i][j] = o[i][j] = tk_f32x4{0.f, 0.f, 0.f, 0.f};
-      }
-    for (int t = 0; t < L; ++t) {
-      tk_f32x4 acc[2][2][4];                          // [0]: the logits a, [1]: the values s
-      tk_tile_accumulate<2>(pa, ua_ok, A.table + (int64_t)t * F, ldt, v0, V, F, sc, acc);
-#pragma unroll
-      for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-#pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            const float a = acc[0][i][j][r], mo = m[i][j][r];
-            const float mn = fmaxf(mo, a);            // a NaN logit leaves the maximum alone and arrives through p
-            const float keep = __expf(mo - mn), p = __expf(a - mn);
-            l[i][j][r] = fmaf(l[i][j][r], keep, p);
-            o[i][j][r] = fmaf(o[i][j][r], keep, __fmul_rn(p, acc[1][i][j][r]));
-            m[i][j][r] = mn;
-          }
-    }
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-      for (int j = 0; j < 4; ++j)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) o[i][j][r] = __fdiv_rn(o[i][j][r], l[i][j][r]);
-    tk_store_fragments(o, sc);                        // (the last pass ended synchronised: the operand tiles are dead)
-    __syncthreads();
+    tkp_tile<false>(pa, ua_ok, A.table, ldt, v0, V, L, F, sc);
 
     const bool e_0 = el[lane] != 0, e_1 = el[64 + lane] != 0;
     for (int ul = ul_begin; ul < ul_end; ++ul)
@@ -1013,10 +1125,38 @@ struct TkcArgs : TkArgs {                      // k, partial and out_idx are unu
 
 constexpr int TKC_T = NRL_RANK_MAX_TARGETS;
 constexpr int TKC_CLD = TKC_T + 1;             // a user's counters: one per target, then the population
-// dynamic LDS of tkc_count_kernel: score tile, exclusion cache, eligibility, then target entries, counters, target ranges
-constexpr size_t TKC_LDS = tk_lds_bytes(1, TK_BU, 0) + (size_t)TK_BU * TKC_T * 8 + (size_t)TK_BU * TKC_CLD * 4 + (size_t)TK_BU * 12;
+
+// The LDS a count kernel keeps beside its score tiles, for a tile of `slots` users (TK_BU, or the whole users of a multi-interest
+// tile): the exclusion cache and the eligibility bytes of the scores kernels, then what the counting consumer owns.  8-byte
+// members first, so any `slots` keeps every member aligned; `p` is 8-byte aligned.
+struct TkcLds {
+  unsigned long long* te;                      // [slots][TKC_T] target entries
+  int64_t* xs;                                 // [slots] exclusion cache: start
+  int64_t* ts;                                 // [slots] first target slot
+  int32_t* xl;                                 // [slots][TK_XCAP] exclusion cache: first rows
+  int32_t* xn;                                 // [slots] exclusion cache: length
+  int32_t* cnt;                                // [slots][TKC_CLD] counters
+  int32_t* tn;                                 // [slots] target slots (0: none, or a bad range)
+  uint8_t* el;                                 // [TK_BV]
+  __device__ __forceinline__ TkcLds(unsigned char* p, int slots) {
+    te = reinterpret_cast<unsigned long long*>(p);
+    xs = reinterpret_cast<int64_t*>(te + slots * TKC_T);
+    ts = xs + slots;
+    xl = reinterpret_cast<int32_t*>(ts + slots);
+    xn = xl + slots * TK_XCAP;
+    cnt = xn + slots;
+    tn = cnt + slots * TKC_CLD;
+    el = reinterpret_cast<uint8_t*>(tn + slots);
+  }
+};
+constexpr size_t tkc_lds_bytes(int slots) {
+  return (size_t)slots * (TKC_T * 8 + 8 + 8 + TK_XCAP * 4 + 4 + TKC_CLD * 4 + 4) + TK_BV;
+}
+constexpr size_t TKC_TILE_BYTES = (size_t)TK_BU * TK_SCLD * 4;
+// dynamic LDS of tkc_count_kernel: score tile, then the layout above (33 KB + 41.9 KB)
+constexpr size_t TKC_LDS = TKC_TILE_BYTES + tkc_lds_bytes(TK_BU);
 static_assert(2 * TKC_LDS <= 160 * 1024, "two workgroups of the count kernel fit a CU");
-static_assert(tk_lds_bytes(1, TK_BU, 0) % 8 == 0, "the target entries that follow the eligibility bytes are 8-byte aligned");
+static_assert(TKC_TILE_BYTES % 16 == 0, "what follows the score tiles is 16-byte aligned");
 
 // a user's target range: false when the offsets decrease, leave [0, n_targets] or span more than TKC_T slots
 __device__ __forceinline__ bool tkc_tgt_range(const TkcArgs& A, int64_t u, int64_t& s, int& n) {
@@ -1030,6 +1170,73 @@ __device__ __forceinline__ bool tkc_tgt_range(const TkcArgs& A, int64_t u, int64
   return true;
 }
 
+// ---- the counting consumer: what a count kernel runs where a scores kernel runs tk_select_user / tk_flush_user -------------------
+// Prologue, by the workgroup, for the tile's `nu` users from u0 on: zero counters, target ranges, the exclusion cache, and every
+// slot's entry -- ~0 (above every entry: it counts nothing) where the user does not own the slot or the row is outside V.  Ends
+// with the workgroup synchronised.
+__device__ __forceinline__ void tkc_prologue(const TkcArgs& A, int64_t u0, int nu, int slots, const TkcLds& S) {
+  const int tid = threadIdx.x;
+  for (int i = tid; i < slots * TKC_CLD; i += TK_THREADS) S.cnt[i] = 0;
+  if (tid < slots) {
+    int64_t s = 0;
+    int n = 0;
+    if (tid < nu && !tkc_tgt_range(A, u0 + tid, s, n)) n = 0;                // the finish kernel flags and blanks such a user
+    S.ts[tid] = s;
+    S.tn[tid] = n;
+  }
+  tk_cache_exclusions(A, u0, nu, slots, S.xs, S.xn, S.xl);                   // (its barrier also publishes `cnt`, `ts` and `tn`)
+  for (int i = tid; i < slots * TKC_T; i += TK_THREADS) {
+    const int ul = i / TKC_T, t = i % TKC_T;
+    unsigned long long e = ~0ull;
+    if (t < S.tn[ul]) {
+      const int64_t j = S.ts[ul] + t, row = A.tgt_idx[j];
+      if (A.owner[j] == (int32_t)(u0 + ul) && row >= 0 && row < A.V) e = tk_entry(A.tscore[j], (uint32_t)row);
+    }
+    S.te[i] = e;
+  }
+  __syncthreads();
+}
+
+// One user (slot `ul` of the tile) against one table tile, by the wave that owns the user: `row` the user's 128 scores, e_0 / e_1
+// the lane's eligibility of columns lane and 64 + lane.  Entries, the exclusion sweep, the NaN drop (flagged), then popc of the
+// survivors into the population counter and, per target, popc of `entry > target entry`: one LDS update per user and tile.
+__device__ __forceinline__ void tkc_count_user(const float* row, const TkcLds& S, int ul, const int64_t* excl_idx, int v0, bool e_0,
+                                               bool e_1, int lane, bool& nan) {
+  unsigned long long c0 = e_0 ? tk_entry(row[lane], (uint32_t)v0 + lane) : 0ull;
+  unsigned long long c1 = e_1 ? tk_entry(row[64 + lane], (uint32_t)v0 + 64 + lane) : 0ull;
+  unsigned long long m0 = __ballot(e_0), m1 = __ballot(e_1);
+  tk_clear_excluded(S.xn + ul, S.xs + ul, S.xl + ul * TK_XCAP, excl_idx, v0, lane, m0, m1);
+  const unsigned long long n0 = m0 & __ballot((uint32_t)(c0 >> 32) == 0xFFFFFFFFu), n1 = m1 & __ballot((uint32_t)(c1 >> 32) == 0xFFFFFFFFu);
+  if (n0 | n1) nan = true;                            // a NaN score of a row of the population: flagged and left out
+  m0 &= ~n0;
+  m1 &= ~n1;
+  if (!((m0 >> lane) & 1)) c0 = 0ull;
+  if (!((m1 >> lane) & 1)) c1 = 0ull;
+  // lane t collects target t's count, lane TKC_T the population
+  int add = lane == TKC_T ? __popcll(m0) + __popcll(m1) : 0;
+  const int nt = S.tn[ul];
+  for (int t = 0; t < nt; ++t) {
+    const unsigned long long e = S.te[ul * TKC_T + t];        // wave-uniform
+    const int above = __popcll(__ballot(c0 > e)) + __popcll(__ballot(c1 > e));
+    if (lane == t) add = above;
+  }
+  if (lane < nt || lane == TKC_T) S.cnt[ul * TKC_CLD + lane] += add;
+}
+
+// Epilogue of user u (slot `ul` of the tile) by the wave that owns it: the slice's population and the counts of the slots it owns
+__device__ __forceinline__ void tkc_flush_user(const TkcArgs& A, const TkcLds& S, int ul, int64_t u, int sl, int lane) {
+  if (lane == TKC_T) A.pcnt[u * A.slices + sl] = S.cnt[ul * TKC_CLD + TKC_T];
+  if (lane < S.tn[ul] && S.te[ul * TKC_T + lane] != ~0ull) A.tcnt[(S.ts[ul] + lane) * A.slices + sl] = S.cnt[ul * TKC_CLD + lane];
+}
+
+// the slice of table tiles of a workgroup of a count (or scores) walk: first row and number of tiles
+__device__ __forceinline__ void tkc_slice(const TkArgs& A, int sl, int& v_begin, int& nvt) {
+  v_begin = sl * A.tiles_per_slice * TK_BV;
+  const int64_t v_stop = (int64_t)v_begin + (int64_t)A.tiles_per_slice * TK_BV;
+  const int v_end = v_stop < A.V ? (int)v_stop : A.V;
+  nvt = (v_end - v_begin + TK_BV - 1) / TK_BV;
+}
+
 __global__ __launch_bounds__(64) void tkc_init_kernel(TkcArgs A) {
   const int64_t j = blockIdx.x;
   const int lane = threadIdx.x;
@@ -1040,6 +1247,7 @@ __global__ __launch_bounds__(64) void tkc_init_kernel(TkcArgs A) {
     A.out_rank[j] = 0;
     A.out_score[j] = -INFINITY;
   }
+  if (!A.gathered) return;                            // (a scorer whose target scores read the table in place)
   const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
   for (int c = lane * 4; c < A.D; c += 256) st4(A.gathered + j * A.D + c, ok ? ld4(A.table + row * A.D + c) : z);
 }
@@ -1070,14 +1278,7 @@ __global__ __launch_bounds__(TK_THREADS) void tkc_target_kernel(TkcArgs A) {
 __global__ __launch_bounds__(TK_THREADS) void tkc_count_kernel(TkcArgs A) {
   extern __shared__ __attribute__((aligned(16))) unsigned char tk_smem[];
   float* const sc = reinterpret_cast<float*>(tk_smem);                       // [TK_BU][TK_SCLD]
-  int32_t* const xl = reinterpret_cast<int32_t*>(sc + TK_BU * TK_SCLD);      // [TK_BU][TK_XCAP]
-  int64_t* const xs = reinterpret_cast<int64_t*>(xl + TK_BU * TK_XCAP);      // [TK_BU]
-  int32_t* const xn = reinterpret_cast<int32_t*>(xs + TK_BU);                // [TK_BU]
-  uint8_t* const el = reinterpret_cast<uint8_t*>(xn + TK_BU);                // [TK_BV]
-  unsigned long long* const te = reinterpret_cast<unsigned long long*>(el + TK_BV);      // [TK_BU][TKC_T] target entries
-  int64_t* const ts = reinterpret_cast<int64_t*>(te + TK_BU * TKC_T);        // [TK_BU] first target slot
-  int32_t* const cnt = reinterpret_cast<int32_t*>(ts + TK_BU);               // [TK_BU][TKC_CLD]
-  int32_t* const tn = cnt + TK_BU * TKC_CLD;                                 // [TK_BU] target slots (0: none, or a bad range)
+  const TkcLds S(tk_smem + TKC_TILE_BYTES, TK_BU);
 
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -1085,31 +1286,10 @@ __global__ __launch_bounds__(TK_THREADS) void tkc_count_kernel(TkcArgs A) {
   const int sl = (int)(blockIdx.x % (unsigned)A.slices);
   const int64_t u0 = (int64_t)(blockIdx.x / (unsigned)A.slices) * TK_BU;
   const int nu = A.B - u0 < TK_BU ? (int)(A.B - u0) : TK_BU;
-  const int v_begin = sl * A.tiles_per_slice * TK_BV;
-  const int64_t v_stop = (int64_t)v_begin + (int64_t)A.tiles_per_slice * TK_BV;
-  const int v_end = v_stop < V ? (int)v_stop : V;
-  const int nvt = (v_end - v_begin + TK_BV - 1) / TK_BV;
+  int v_begin, nvt;
+  tkc_slice(A, sl, v_begin, nvt);
 
-  for (int i = tid; i < TK_BU * TKC_CLD; i += TK_THREADS) cnt[i] = 0;
-  if (tid < TK_BU) {
-    int64_t s = 0;
-    int n = 0;
-    if (tid < nu && !tkc_tgt_range(A, u0 + tid, s, n)) n = 0;                // the finish kernel flags and blanks such a user
-    ts[tid] = s;
-    tn[tid] = n;
-  }
-  tk_cache_exclusions(A, u0, nu, TK_BU, xs, xn, xl);   // (its barrier also publishes `cnt`, `ts` and `tn`)
-  // a slot's entry; ~0 (above every entry: it counts nothing) where the user does not own the slot or the row is outside V
-  for (int i = tid; i < TK_BU * TKC_T; i += TK_THREADS) {
-    const int ul = i / TKC_T, t = i % TKC_T;
-    unsigned long long e = ~0ull;
-    if (t < tn[ul]) {
-      const int64_t j = ts[ul] + t, row = A.tgt_idx[j];
-      if (A.owner[j] == (int32_t)(u0 + ul) && row >= 0 && row < V) e = tk_entry(A.tscore[j], (uint32_t)row);
-    }
-    te[i] = e;
-  }
-  __syncthreads();
+  tkc_prologue(A, u0, nu, TK_BU, S);
 
   const int ul_begin = wave * TK_USERS_PER_WAVE, ul_end = ul_begin + TK_USERS_PER_WAVE < nu ? ul_begin + TK_USERS_PER_WAVE : nu;
   const int srow = tid >> 2;
@@ -1119,41 +1299,230 @@ __global__ __launch_bounds__(TK_THREADS) void tkc_count_kernel(TkcArgs A) {
 
   for (int vt = 0; vt < nvt; ++vt) {
     const int v0 = v_begin + vt * TK_BV;
-    tk_fill_eligible(A.eligible, v0, V, el);
+    tk_fill_eligible(A.eligible, v0, V, S.el);
     tk_tile_product<1>(pa, ua_ok, A.table, v0, V, A.D, sc);
 
-    const bool e_0 = el[lane] != 0, e_1 = el[64 + lane] != 0;
-    for (int ul = ul_begin; ul < ul_end; ++ul) {
-      const float* const row = sc + ul * TK_SCLD;
-      unsigned long long c0 = e_0 ? tk_entry(row[lane], (uint32_t)v0 + lane) : 0ull;
-      unsigned long long c1 = e_1 ? tk_entry(row[64 + lane], (uint32_t)v0 + 64 + lane) : 0ull;
-      unsigned long long m0 = __ballot(e_0), m1 = __ballot(e_1);
-      tk_clear_excluded(xn + ul, xs + ul, xl + ul * TK_XCAP, A.excl_idx, v0, lane, m0, m1);
-      const unsigned long long n0 = m0 & __ballot((uint32_t)(c0 >> 32) == 0xFFFFFFFFu), n1 = m1 & __ballot((uint32_t)(c1 >> 32) == 0xFFFFFFFFu);
-      if (n0 | n1) nan = true;                        // a NaN score of a row of the population: flagged and left out
-      m0 &= ~n0;
-      m1 &= ~n1;
-      if (!((m0 >> lane) & 1)) c0 = 0ull;
-      if (!((m1 >> lane) & 1)) c1 = 0ull;
-      // lane t collects target t's count, lane TKC_T the population; one LDS update per user and tile
-      int add = lane == TKC_T ? __popcll(m0) + __popcll(m1) : 0;
-      const int nt = tn[ul];
-      for (int t = 0; t < nt; ++t) {
-        const unsigned long long e = te[ul * TKC_T + t];      // wave-uniform
-        const int above = __popcll(__ballot(c0 > e)) + __popcll(__ballot(c1 > e));
-        if (lane == t) add = above;
-      }
-      if (lane < nt || lane == TKC_T) cnt[ul * TKC_CLD + lane] += add;
-    }
+    const bool e_0 = S.el[lane] != 0, e_1 = S.el[64 + lane] != 0;
+    for (int ul = ul_begin; ul < ul_end; ++ul) tkc_count_user(sc + ul * TK_SCLD, S, ul, A.excl_idx, v0, e_0, e_1, lane, nan);
     __syncthreads();                                  // the score tile and `el` are free for the next tile's operands
   }
 
   if (nan && lane == 0) atomicOr(A.status, NRL_TOPK_E_NAN);
   wave_lds_sync();
-  for (int ul = ul_begin; ul < ul_end; ++ul) {
-    if (lane == TKC_T) A.pcnt[(u0 + ul) * A.slices + sl] = cnt[ul * TKC_CLD + TKC_T];
-    if (lane < tn[ul] && te[ul * TKC_T + lane] != ~0ull) A.tcnt[(ts[ul] + lane) * A.slices + sl] = cnt[ul * TKC_CLD + lane];
+  for (int ul = ul_begin; ul < ul_end; ++ul) tkc_flush_user(A, S, ul, u0 + ul, sl, lane);
+}
+
+// ---- the count walk under the other scorers ------------------------------------------------------------------------------------------
+// Each is the walk of its scores kernel -- the same tile producer, device function for device function, so a score's bits cannot
+// differ between the top-k list and the rank -- with the counting consumer, and a target kernel that computes the slots' scores by
+// the same chain.
+
+// MINER: tki_scores_kernel's walk.  A workgroup holds Ut = 64 / K users, so the consumer's arrays are [Ut][...].
+struct TkicArgs : TkcArgs {                    // `user` is the interests; B counts users
+  const float* gate;
+  int32_t K, Ut, mode;
+};
+constexpr size_t tkic_lds_bytes(bool gate, int Ut) { return (gate ? 2 : 1) * TKC_TILE_BYTES + tkc_lds_bytes(Ut); }
+static_assert(2 * tkic_lds_bytes(false, TK_BU) <= 160 * 1024, "max / mean: two workgroups of the interest count kernel fit a CU");
+static_assert(tkic_lds_bytes(true, TK_BU) <= 160 * 1024, "weighted: the second score tile leaves room for one workgroup per CU");
+
+// One workgroup per Ut slots from j0 on: tile rows i K ... i K + K - 1 are the K interest (and gate) rows of the owner of slot
+// j0 + i, the table tile is the gathered target rows from j0 on, so slot j0 + i's K products are column i of those rows; the
+// aggregate over them is the score tki_scores_kernel computes for that (user, row).  K = 1: tkc_target_kernel.
+template <bool GATE>
+__global__ __launch_bounds__(TK_THREADS) void tkic_target_kernel(TkicArgs A) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char tk_smem[];
+  constexpr int NA = GATE ? 2 : 1;
+  float* const sc = reinterpret_cast<float*>(tk_smem);                       // [TK_BU][TK_SCLD] the s_j; with a gate the l_j follow
+  const float* const lg = sc + TK_BU * TK_SCLD;
+  const int tid = threadIdx.x, K = A.K, Ut = A.Ut;
+  const int64_t j0 = (int64_t)blockIdx.x * Ut;
+  const int srow = tid >> 2, i = srow / K;
+  const int own = (i < Ut && j0 + i < A.n_targets) ? A.owner[j0 + i] : -1;
+  const bool ua_ok = own >= 0;
+  const int64_t ua = ua_ok ? (int64_t)own * K + (srow - i * K) : 0;
+  const float* pa[NA];
+  pa[0] = A.user + ua * A.D;
+  if constexpr (GATE) pa[1] = A.gate + ua * A.D;
+  tk_tile_product<NA>(pa, ua_ok, A.gathered, (int)j0, (int)A.n_targets, A.D, sc);
+  if (tid < Ut && j0 + tid < A.n_targets) {
+    const int at = tid * K * TK_SCLD + tid;
+    A.tscore[j0 + tid] = tki_aggregate<GATE>(sc + at, lg + at, K, A.mode);
   }
+}
+
+template <bool GATE>
+__global__ __launch_bounds__(TK_THREADS) void tkic_count_kernel(TkicArgs A) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char tk_smem[];
+  constexpr int NA = GATE ? 2 : 1;
+  const int K = A.K, Ut = A.Ut;
+  float* const sc = reinterpret_cast<float*>(tk_smem);                       // [TK_BU][TK_SCLD] the s_j; with a gate the l_j follow
+  const TkcLds S(tk_smem + NA * TKC_TILE_BYTES, Ut);
+
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int V = A.V;
+  const int sl = (int)(blockIdx.x % (unsigned)A.slices);
+  const int64_t u0 = (int64_t)(blockIdx.x / (unsigned)A.slices) * Ut;        // first user of the tile
+  const int nu = A.B - u0 < Ut ? (int)(A.B - u0) : Ut;                       // its users (>= 1)
+  int v_begin, nvt;
+  tkc_slice(A, sl, v_begin, nvt);
+
+  tkc_prologue(A, u0, nu, Ut, S);
+
+  // staging: tile row r is interest row u0 * K + r of the (B * K, D) matrix while r < nu * K, zero from there on
+  const int srow = tid >> 2;
+  const bool ua_ok = srow < nu * K;
+  const int64_t ua = ua_ok ? u0 * K + srow : 0;
+  const float* pa[NA];
+  pa[0] = A.user + ua * A.D;
+  if constexpr (GATE) pa[1] = A.gate + ua * A.D;
+  bool nan = false;
+
+  for (int vt = 0; vt < nvt; ++vt) {
+    const int v0 = v_begin + vt * TK_BV;
+    tk_fill_eligible(A.eligible, v0, V, S.el);
+    tki_tile<GATE>(pa, ua_ok, A.table, v0, V, A.D, sc, nu, K, A.mode);
+
+    // wave w owns users w, w + 4, ... of the tile and their counters
+    const bool e_0 = S.el[lane] != 0, e_1 = S.el[64 + lane] != 0;
+    for (int ul = wave; ul < nu; ul += 4) tkc_count_user(sc + ul * K * TK_SCLD, S, ul, A.excl_idx, v0, e_0, e_1, lane, nan);
+    __syncthreads();                                  // the score tiles and `el` are free for the next tile's operands
+  }
+
+  if (nan && lane == 0) atomicOr(A.status, NRL_TOPK_E_NAN);
+  wave_lds_sync();
+  for (int ul = wave; ul < nu; ul += 4) tkc_flush_user(A, S, ul, u0 + ul, sl, lane);
+}
+
+// DKN: tkr_scores_kernel's walk (over the duplicate of its producer above).  The q rows and w2 follow the score tile (16-byte aligned), then the consumer's arrays.
+struct TkrcArgs : TkcArgs {                    // `user` is q, `table` is proj, D is Hd
+  const float* w2;
+  const float* b2;
+};
+constexpr size_t tkrc_lds_bytes(int Hd) { return TKC_TILE_BYTES + tkr_extra_lds(Hd) + tkc_lds_bytes(TK_BU); }
+static_assert(tkr_extra_lds(NRL_TOPK_MAX_HIDDEN) % 16 == 0 && tkrc_lds_bytes(NRL_TOPK_MAX_HIDDEN) <= 160 * 1024 &&
+                  2 * tkrc_lds_bytes(20) <= 160 * 1024,
+              "the largest layout fits (91.1 KB at Hd = 64: one workgroup per CU); two workgroups fit a CU up to Hd = 20");
+
+// one thread per slot: the chain of tkr_tile for (owner, target row), read in place -- no gather, no tile
+__global__ __launch_bounds__(256) void tkrc_target_kernel(TkrcArgs A) {
+  const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (j >= A.n_targets) return;
+  const int own = A.owner[j], Hd = A.D;
+  const int64_t row = A.tgt_idx[j];
+  float s = 0.f;
+  if (own >= 0 && row >= 0 && row < A.V) {
+    const float* const p = A.table + row * Hd;
+    const float* const q = A.user + (int64_t)own * Hd;
+    s = A.b2[0];
+    for (int c = 0; c < Hd; ++c) s = tkr_step(A.w2[c], p[c], q[c], s);
+  }
+  A.tscore[j] = s;
+}
+
+__global__ __launch_bounds__(TK_THREADS) void tkrc_count_kernel(TkrcArgs A) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char tk_smem[];
+  float* const sc = reinterpret_cast<float*>(tk_smem);                       // [TK_BU][TK_SCLD]; before: proj tile [TK_BV][ldp]
+  const int Hd = A.D;
+  float* const qs = sc + TK_BU * TK_SCLD;                                    // [TK_BU][ldq], zero past Hd and past the last user
+  float* const w2s = qs + TK_BU * tkr_ldq(Hd);                               // [ldq]
+  const TkcLds S(tk_smem + TKC_TILE_BYTES + tkr_extra_lds(Hd), TK_BU);
+
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int V = A.V;
+  const int sl = (int)(blockIdx.x % (unsigned)A.slices);
+  const int64_t u0 = (int64_t)(blockIdx.x / (unsigned)A.slices) * TK_BU;
+  const int nu = A.B - u0 < TK_BU ? (int)(A.B - u0) : TK_BU;
+  int v_begin, nvt;
+  tkc_slice(A, sl, v_begin, nvt);
+
+  tkr_stage_users(A.user, A.w2, u0, nu, Hd, qs, w2s);
+  const float b2 = A.b2[0];
+  tkc_prologue(A, u0, nu, TK_BU, S);                  // (its barriers also publish `qs` and `w2s`)
+
+  const int ul_begin = wave * TK_USERS_PER_WAVE, ul_end = ul_begin + TK_USERS_PER_WAVE < nu ? ul_begin + TK_USERS_PER_WAVE : nu;
+  const TkrWalk W = tkr_walk(Hd);
+  bool nan = false;
+
+  for (int vt = 0; vt < nvt; ++vt) {
+    const int v0 = v_begin + vt * TK_BV;
+    tk_fill_eligible(A.eligible, v0, V, S.el);
+    tkr_tile(A.table, v0, V, Hd, W, sc, qs + ul_begin * tkr_ldq(Hd), w2s, b2, ul_begin);
+
+    const bool e_0 = S.el[lane] != 0, e_1 = S.el[64 + lane] != 0;
+    for (int ul = ul_begin; ul < ul_end; ++ul) tkc_count_user(sc + ul * TK_SCLD, S, ul, A.excl_idx, v0, e_0, e_1, lane, nan);
+    __syncthreads();                                  // the score tile and `el` are free for the next proj tile
+  }
+
+  if (nan && lane == 0) atomicOr(A.status, NRL_TOPK_E_NAN);
+  wave_lds_sync();
+  for (int ul = ul_begin; ul < ul_end; ++ul) tkc_flush_user(A, S, ul, u0 + ul, sl, lane);
+}
+
+// NPA: tkp_scores_kernel's walk.  The operand tiles (38 KB) and the consumer's arrays (41.9 KB) are 79.9 KB: two workgroups fit a
+// CU with all NRL_RANK_MAX_TARGETS targets.
+struct TkpcArgs : TkcArgs {                    // `user` is q, `table` the feature maps, D is F
+  const float* uvec;
+  int32_t L;
+};
+constexpr size_t TKPC_LDS = (size_t)TKP_OPERAND_FLOATS * 4 + tkc_lds_bytes(TK_BU);
+static_assert(((size_t)TKP_OPERAND_FLOATS * 4) % 16 == 0 && 2 * TKPC_LDS <= 160 * 1024,
+              "two workgroups of the pooled count kernel fit a CU (under 80 KB each)");
+
+// One workgroup per 64 slots from j0 on: tile row r is (q, user) of the owner of slot j0 + r, tile column c the feature map of
+// target row tgt_idx[j0 + c], read in place (nothing is gathered: a map is L F floats); slot j0 + r's score is the diagonal.
+__global__ __launch_bounds__(TK_THREADS, 2) void tkpc_target_kernel(TkpcArgs A) {
+  __shared__ __attribute__((aligned(16))) float sc[TKP_OPERAND_FLOATS];
+  const int tid = threadIdx.x, F = A.D;
+  const int64_t j0 = (int64_t)blockIdx.x * TK_BU;
+  const int srow = tid >> 2;
+  const int own = j0 + srow < A.n_targets ? A.owner[j0 + srow] : -1;
+  const bool ua_ok = own >= 0;
+  const int64_t ua = (int64_t)(ua_ok ? own : 0) * F;
+  const float* const pa[2] = {A.user + ua, A.uvec + ua};
+  tkp_tile<true>(pa, ua_ok, A.table, (int64_t)A.L * F, (int)j0, (int)A.n_targets, A.L, F, sc, A.tgt_idx, A.V);
+  if (tid < TK_BU && j0 + tid < A.n_targets) A.tscore[j0 + tid] = sc[tid * TK_SCLD + tid];
+}
+
+__global__ __launch_bounds__(TK_THREADS, 2) void tkpc_count_kernel(TkpcArgs A) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char tk_smem[];
+  float* const sc = reinterpret_cast<float*>(tk_smem);                       // operand tiles; afterwards [TK_BU][TK_SCLD] scores
+  const TkcLds S(tk_smem + (size_t)TKP_OPERAND_FLOATS * 4, TK_BU);
+
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int V = A.V, L = A.L, F = A.D;
+  const int sl = (int)(blockIdx.x % (unsigned)A.slices);
+  const int64_t u0 = (int64_t)(blockIdx.x / (unsigned)A.slices) * TK_BU;
+  const int nu = A.B - u0 < TK_BU ? (int)(A.B - u0) : TK_BU;
+  int v_begin, nvt;
+  tkc_slice(A, sl, v_begin, nvt);
+
+  tkc_prologue(A, u0, nu, TK_BU, S);
+
+  const int ul_begin = wave * TK_USERS_PER_WAVE, ul_end = ul_begin + TK_USERS_PER_WAVE < nu ? ul_begin + TK_USERS_PER_WAVE : nu;
+  const int srow = tid >> 2;
+  const bool ua_ok = srow < nu;
+  const int64_t ua = (ua_ok ? u0 + srow : A.B - 1) * F;
+  const float* const pa[2] = {A.user + ua, A.uvec + ua};
+  const int64_t ldt = (int64_t)L * F;
+  bool nan = false;
+
+  for (int vt = 0; vt < nvt; ++vt) {
+    const int v0 = v_begin + vt * TK_BV;
+    tk_fill_eligible(A.eligible, v0, V, S.el);
+    tkp_tile<false>(pa, ua_ok, A.table, ldt, v0, V, L, F, sc);
+
+    const bool e_0 = S.el[lane] != 0, e_1 = S.el[64 + lane] != 0;
+    for (int ul = ul_begin; ul < ul_end; ++ul) tkc_count_user(sc + ul * TK_SCLD, S, ul, A.excl_idx, v0, e_0, e_1, lane, nan);
+    __syncthreads();                                  // the score tile and `el` are free for the next tile's operands
+  }
+
+  if (nan && lane == 0) atomicOr(A.status, NRL_TOPK_E_NAN);
+  wave_lds_sync();
+  for (int ul = ul_begin; ul < ul_end; ++ul) tkc_flush_user(A, S, ul, u0 + ul, sl, lane);
 }
 
 __device__ __forceinline__ int tkc_wave_sum(int v) {
@@ -1260,6 +1629,29 @@ static int tk_launch(const char* who, void (*kernel)(Args), Args& A, int32_t sli
   return NRL_OK;
 }
 
+// The launches of a rank entry: slots and owners, `target` (the entry's target kernel: a callable that launches it), the count
+// kernel with `smem` bytes of dynamic LDS over `blocks` workgroups, the finish.
+template <class Args, class Target>
+static int tkc_launch(void (*count)(Args), Args& A, int64_t blocks, size_t smem, void* stream, Target target) {
+  hipStream_t st = (hipStream_t)stream;
+  if (A.n_targets > 0) {
+    tkc_init_kernel<<<(unsigned)A.n_targets, 64, 0, st>>>(static_cast<const TkcArgs&>(A));
+    NRL_LAUNCH_CHECK();
+    tkc_owner_kernel<<<(unsigned)ceil_div(A.B, 256), 256, 0, st>>>(static_cast<const TkcArgs&>(A));
+    NRL_LAUNCH_CHECK();
+    if (A.V > 0) NRL_TRY(target(st));
+  }
+  if (blocks > 0) {
+    // more than 64 KB of dynamic LDS needs the attribute; it belongs to the current device, so it is set per call
+    NRL_HIP(hipFuncSetAttribute((const void*)count, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    count<<<(unsigned)blocks, TK_THREADS, smem, st>>>(A);
+    NRL_LAUNCH_CHECK();
+  }
+  tkc_finish_kernel<<<(unsigned)A.B, 64, 0, st>>>(static_cast<const TkcArgs&>(A));
+  NRL_LAUNCH_CHECK();
+  return NRL_OK;
+}
+
 }  // namespace nrl
 
 using namespace nrl;
@@ -1298,9 +1690,9 @@ struct TkcWs {
   float *gathered, *tscore;
   int32_t *owner, *pcnt, *tcnt;
 };
-static void tkc_layout(Arena& a, int64_t B, int64_t V, int32_t D, int64_t n_targets, int32_t slices, TkcWs* w) {
+static void tkc_layout(Arena& a, int64_t B, int64_t V, int32_t D, int64_t n_targets, int32_t slices, int64_t bu, TkcWs* w) {
   int64_t lists, used, tps;
-  tk_plan(B, V, slices, TK_BU, lists, used, tps);
+  tk_plan(B, V, slices, bu, lists, used, tps);
   const size_t n = (size_t)n_targets;
   w->gathered = a.take<float>(n * (size_t)D > 0 ? n * (size_t)D : 1);
   w->tscore = a.take<float>(n > 0 ? n : 1);
@@ -1311,7 +1703,44 @@ static void tkc_layout(Arena& a, int64_t B, int64_t V, int32_t D, int64_t n_targ
 
 size_t nrl_catalogue_ranks_workspace_size(int64_t B, int64_t V, int32_t D, int64_t n_targets, int32_t slices) {
   if (!tk_shape_ok(B, V, D, 1) || slices < 0 || n_targets < 0 || n_targets >= ((int64_t)1 << 31)) return 256;
-  return measure_workspace<TkcWs>([&](Arena& a, auto* w) { tkc_layout(a, B, V, D, n_targets, slices, w); });
+  return measure_workspace<TkcWs>([&](Arena& a, auto* w) { tkc_layout(a, B, V, D, n_targets, slices, TK_BU, w); });
+}
+
+// the checks every rank entry makes after its own shape checks, in this order; `who` is the entry's name in the message
+static int tkc_check(const char* who, int64_t n_targets, const int64_t* tgt_idx, const int64_t* tgt_off, const int32_t* status) {
+  NRL_REQUIRE(n_targets < ((int64_t)1 << 31), "%s: at most 2^31 - 1 targets per call (got %lld)", who, (long long)n_targets);
+  NRL_REQUIRE(tgt_off || (!tgt_idx && n_targets == 0), "%s: tgt_idx without tgt_off", who);
+  NRL_REQUIRE(status, "%s: the status word is required", who);
+  return NRL_OK;
+}
+
+// Carves the workspace (D floats per gathered target row), plans the slices for `bu` users per workgroup and fills the arguments
+// every kernel of a rank entry reads; `gather`: the target kernel reads gathered rows.
+static int tkc_prepare(const char* who, TkcArgs& A, const float* user, const float* table, int64_t B, int64_t V, int32_t D,
+                       int32_t ws_D, bool gather, const int64_t* tgt_idx, const int64_t* tgt_off, int64_t n_targets,
+                       const int64_t* excl_idx, const int64_t* excl_off, const uint8_t* eligible, int32_t slices, int64_t bu,
+                       int32_t* out_rank, float* out_score, int32_t* out_ranked, int32_t* status, void* ws, size_t ws_bytes,
+                       int64_t* blocks) {
+  TkcWs w;
+  NRL_TRY(carve_workspace(ws, ws_bytes, [&](Arena& a) { tkc_layout(a, B, V, ws_D, n_targets, slices, bu, &w); }));
+  int64_t lists, used, tps;
+  tk_plan(B, V, slices, bu, lists, used, tps);
+  *blocks = ceil_div(B, bu) * used;
+  NRL_REQUIRE(*blocks < ((int64_t)1 << 31), "%s: grid too large (%lld workgroups)", who, (long long)*blocks);
+  static_cast<TkArgs&>(A) = tk_args(user, table, B, V, D, 1, excl_idx, excl_off, eligible, nullptr, nullptr, out_score, status);
+  A.slices = (int32_t)used;
+  A.tiles_per_slice = (int32_t)tps;
+  A.tgt_idx = tgt_idx;
+  A.tgt_off = tgt_off;
+  A.n_targets = n_targets;
+  A.gathered = gather ? w.gathered : nullptr;
+  A.tscore = w.tscore;
+  A.owner = w.owner;
+  A.pcnt = w.pcnt;
+  A.tcnt = w.tcnt;
+  A.out_rank = out_rank;
+  A.out_ranked = out_ranked;
+  return NRL_OK;
 }
 
 int nrl_catalogue_ranks(const float* user_vec, const float* table, int64_t B, int64_t V, int32_t D, const int64_t* tgt_idx,
@@ -1320,52 +1749,114 @@ int nrl_catalogue_ranks(const float* user_vec, const float* table, int64_t B, in
                         int32_t* status, void* ws, size_t ws_bytes, void* stream) {
   NRL_REQUIRE(B >= 0 && V >= 0 && D >= 0 && slices >= 0 && n_targets >= 0, "catalogue_ranks: negative size");
   NRL_TRY(tk_check("catalogue_ranks", B, V, D, 1, excl_idx, excl_off));
-  NRL_REQUIRE(n_targets < ((int64_t)1 << 31), "catalogue_ranks: at most 2^31 - 1 targets per call (got %lld)", (long long)n_targets);
-  NRL_REQUIRE(tgt_off || (!tgt_idx && n_targets == 0), "catalogue_ranks: tgt_idx without tgt_off");
-  NRL_REQUIRE(status, "catalogue_ranks: the status word is required");
+  NRL_TRY(tkc_check("catalogue_ranks", n_targets, tgt_idx, tgt_off, status));
   if (B == 0) return NRL_OK;
   NRL_REQUIRE(out_ranked && user_vec && (V == 0 || table) && (n_targets == 0 || (tgt_idx && out_rank && out_score)),
               "catalogue_ranks: null argument");
-  TkcWs w;
-  NRL_TRY(carve_workspace(ws, ws_bytes, [&](Arena& a) { tkc_layout(a, B, V, D, n_targets, slices, &w); }));
-  int64_t lists, used, tps;
-  tk_plan(B, V, slices, TK_BU, lists, used, tps);
-  const int64_t blocks = ceil_div(B, TK_BU) * used;
-  NRL_REQUIRE(blocks < ((int64_t)1 << 31), "catalogue_ranks: grid too large (%lld workgroups)", (long long)blocks);
   TkcArgs A;
-  static_cast<TkArgs&>(A) = tk_args(user_vec, table, B, V, D, 1, excl_idx, excl_off, eligible, nullptr, nullptr, out_score, status);
-  A.slices = (int32_t)used;
-  A.tiles_per_slice = (int32_t)tps;
-  A.tgt_idx = tgt_idx;
-  A.tgt_off = tgt_off;
-  A.n_targets = n_targets;
-  A.gathered = w.gathered;
-  A.tscore = w.tscore;
-  A.owner = w.owner;
-  A.pcnt = w.pcnt;
-  A.tcnt = w.tcnt;
-  A.out_rank = out_rank;
-  A.out_ranked = out_ranked;
-  hipStream_t st = (hipStream_t)stream;
-  if (n_targets > 0) {
-    tkc_init_kernel<<<(unsigned)n_targets, 64, 0, st>>>(A);
+  int64_t blocks;
+  NRL_TRY(tkc_prepare("catalogue_ranks", A, user_vec, table, B, V, D, D, true, tgt_idx, tgt_off, n_targets, excl_idx, excl_off,
+                      eligible, slices, TK_BU, out_rank, out_score, out_ranked, status, ws, ws_bytes, &blocks));
+  return tkc_launch(tkc_count_kernel, A, blocks, TKC_LDS, stream, [&](hipStream_t st) {
+    tkc_target_kernel<<<(unsigned)ceil_div(n_targets, TK_BU), TK_THREADS, 0, st>>>(A);
     NRL_LAUNCH_CHECK();
-    tkc_owner_kernel<<<(unsigned)ceil_div(B, 256), 256, 0, st>>>(A);
-    NRL_LAUNCH_CHECK();
-    if (V > 0) {
-      tkc_target_kernel<<<(unsigned)ceil_div(n_targets, TK_BU), TK_THREADS, 0, st>>>(A);
+    return NRL_OK;
+  });
+}
+
+int nrl_catalogue_interest_ranks(const float* interests, const float* gate, const float* table, int64_t B, int32_t K, int64_t V,
+                                 int32_t D, int32_t mode, const int64_t* tgt_idx, const int64_t* tgt_off, int64_t n_targets,
+                                 const int64_t* excl_idx, const int64_t* excl_off, const uint8_t* eligible, int32_t slices,
+                                 int32_t* out_rank, float* out_score, int32_t* out_ranked, int32_t* status, void* ws,
+                                 size_t ws_bytes, void* stream) {
+  NRL_REQUIRE(B >= 0 && V >= 0 && D >= 0 && slices >= 0 && n_targets >= 0, "catalogue_interest_ranks: negative size");
+  NRL_REQUIRE(K >= 1 && K <= NRL_TOPK_MAX_INTERESTS, "catalogue_interest_ranks: K in [1, %d] (got %d)", NRL_TOPK_MAX_INTERESTS, K);
+  NRL_REQUIRE(mode >= 0 && mode <= 2, "catalogue_interest_ranks: mode 0 (max), 1 (mean) or 2 (weighted) (got %d)", mode);
+  NRL_REQUIRE(mode != 2 || gate, "catalogue_interest_ranks: mode 2 (weighted) needs the gate rows");
+  NRL_TRY(tk_check("catalogue_interest_ranks", B, V, D, 1, excl_idx, excl_off));
+  NRL_TRY(tkc_check("catalogue_interest_ranks", n_targets, tgt_idx, tgt_off, status));
+  if (B == 0) return NRL_OK;
+  NRL_REQUIRE(out_ranked && interests && (V == 0 || table) && (n_targets == 0 || (tgt_idx && out_rank && out_score)),
+              "catalogue_interest_ranks: null argument");
+  // the slices of this entry's own plan: never more than nrl_catalogue_ranks_workspace_size(B, V, D, ...) holds (Ut <= TK_BU)
+  const int32_t Ut = TK_BU / K;
+  TkicArgs A;
+  int64_t blocks;
+  NRL_TRY(tkc_prepare("catalogue_interest_ranks", A, interests, table, B, V, D, D, true, tgt_idx, tgt_off, n_targets, excl_idx,
+                      excl_off, eligible, slices, Ut, out_rank, out_score, out_ranked, status, ws, ws_bytes, &blocks));
+  A.gate = mode == 2 ? gate : nullptr;
+  A.K = K;
+  A.Ut = Ut;
+  A.mode = mode;
+  const unsigned tgrid = (unsigned)ceil_div(n_targets, Ut);
+  if (mode == 2)
+    return tkc_launch(tkic_count_kernel<true>, A, blocks, tkic_lds_bytes(true, Ut), stream, [&](hipStream_t st) {
+      NRL_HIP(hipFuncSetAttribute((const void*)tkic_target_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+      tkic_target_kernel<true><<<tgrid, TK_THREADS, 2 * TKC_TILE_BYTES, st>>>(A);
       NRL_LAUNCH_CHECK();
-    }
-  }
-  if (used > 0) {
-    // more than 64 KB of dynamic LDS needs the attribute; it belongs to the current device, so it is set per call
-    NRL_HIP(hipFuncSetAttribute((const void*)tkc_count_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    tkc_count_kernel<<<(unsigned)blocks, TK_THREADS, TKC_LDS, st>>>(A);
+      return NRL_OK;
+    });
+  return tkc_launch(tkic_count_kernel<false>, A, blocks, tkic_lds_bytes(false, Ut), stream, [&](hipStream_t st) {
+    tkic_target_kernel<false><<<tgrid, TK_THREADS, TKC_TILE_BYTES, st>>>(A);
     NRL_LAUNCH_CHECK();
-  }
-  tkc_finish_kernel<<<(unsigned)B, 64, 0, st>>>(A);
-  NRL_LAUNCH_CHECK();
-  return NRL_OK;
+    return NRL_OK;
+  });
+}
+
+int nrl_catalogue_relu_ranks(const float* q, const float* proj, const float* w2, const float* b2, int64_t B, int64_t V, int32_t Hd,
+                             const int64_t* tgt_idx, const int64_t* tgt_off, int64_t n_targets, const int64_t* excl_idx,
+                             const int64_t* excl_off, const uint8_t* eligible, int32_t slices, int32_t* out_rank, float* out_score,
+                             int32_t* out_ranked, int32_t* status, void* ws, size_t ws_bytes, void* stream) {
+  NRL_REQUIRE(B >= 0 && V >= 0 && slices >= 0 && n_targets >= 0, "catalogue_relu_ranks: negative size");
+  NRL_REQUIRE(Hd >= 1 && Hd <= NRL_TOPK_MAX_HIDDEN, "catalogue_relu_ranks: Hd in [1, %d] (got %d)", NRL_TOPK_MAX_HIDDEN, Hd);
+  NRL_TRY(tk_check("catalogue_relu_ranks", B, V, 4, 1, excl_idx, excl_off));   // (no D here: Hd is checked above)
+  NRL_TRY(tkc_check("catalogue_relu_ranks", n_targets, tgt_idx, tgt_off, status));
+  NRL_REQUIRE(w2, "catalogue_relu_ranks: w2 is required");
+  NRL_REQUIRE(b2, "catalogue_relu_ranks: b2 is required (a device pointer)");
+  if (B == 0) return NRL_OK;
+  NRL_REQUIRE(out_ranked && q && (V == 0 || proj) && (n_targets == 0 || (tgt_idx && out_rank && out_score)),
+              "catalogue_relu_ranks: null argument");
+  // the layout of nrl_catalogue_ranks_workspace_size(B, V, 4, ...): nothing is gathered, the target kernel reads proj in place
+  TkrcArgs A;
+  int64_t blocks;
+  NRL_TRY(tkc_prepare("catalogue_relu_ranks", A, q, proj, B, V, Hd, 4, false, tgt_idx, tgt_off, n_targets, excl_idx, excl_off,
+                      eligible, slices, TK_BU, out_rank, out_score, out_ranked, status, ws, ws_bytes, &blocks));
+  A.w2 = w2;
+  A.b2 = b2;
+  return tkc_launch(tkrc_count_kernel, A, blocks, tkrc_lds_bytes(Hd), stream, [&](hipStream_t st) {
+    tkrc_target_kernel<<<(unsigned)ceil_div(n_targets, 256), 256, 0, st>>>(A);
+    NRL_LAUNCH_CHECK();
+    return NRL_OK;
+  });
+}
+
+int nrl_catalogue_pooled_ranks(const float* q, const float* user, const float* features, int64_t B, int64_t V, int32_t L, int32_t F,
+                               const int64_t* tgt_idx, const int64_t* tgt_off, int64_t n_targets, const int64_t* excl_idx,
+                               const int64_t* excl_off, const uint8_t* eligible, int32_t slices, int32_t* out_rank, float* out_score,
+                               int32_t* out_ranked, int32_t* status, void* ws, size_t ws_bytes, void* stream) {
+  NRL_REQUIRE(B >= 0 && V >= 0 && slices >= 0 && n_targets >= 0, "catalogue_pooled_ranks: negative size");
+  NRL_REQUIRE(L >= 1 && L <= NRL_TOPK_MAX_TOKENS, "catalogue_pooled_ranks: L in [1, %d] tokens (got %d)", NRL_TOPK_MAX_TOKENS, L);
+  NRL_REQUIRE(F >= 4 && F % 4 == 0 && F <= NRL_TOPK_MAX_D, "catalogue_pooled_ranks: F a multiple of 4 in [4, %d] (got %d)",
+              NRL_TOPK_MAX_D, F);
+  NRL_TRY(tk_check("catalogue_pooled_ranks", B, V, 4, 1, excl_idx, excl_off));  // (no D here: F is checked above)
+  NRL_TRY(tkc_check("catalogue_pooled_ranks", n_targets, tgt_idx, tgt_off, status));
+  if (B == 0) return NRL_OK;
+  NRL_REQUIRE(out_ranked && q && user && (V == 0 || features) && (n_targets == 0 || (tgt_idx && out_rank && out_score)),
+              "catalogue_pooled_ranks: null argument");
+  NRL_REQUIRE((((uintptr_t)q | (uintptr_t)user | (uintptr_t)features) & 15) == 0,
+              "catalogue_pooled_ranks: q, user and features must be 16-byte aligned");
+  // the layout of nrl_catalogue_ranks_workspace_size(B, V, 4, ...): nothing is gathered, the target kernel reads the maps in place
+  TkpcArgs A;
+  int64_t blocks;
+  NRL_TRY(tkc_prepare("catalogue_pooled_ranks", A, q, features, B, V, F, 4, false, tgt_idx, tgt_off, n_targets, excl_idx, excl_off,
+                      eligible, slices, TK_BU, out_rank, out_score, out_ranked, status, ws, ws_bytes, &blocks));
+  A.uvec = user;
+  A.L = L;
+  return tkc_launch(tkpc_count_kernel, A, blocks, TKPC_LDS, stream, [&](hipStream_t st) {
+    tkpc_target_kernel<<<(unsigned)ceil_div(n_targets, TK_BU), TK_THREADS, 0, st>>>(A);
+    NRL_LAUNCH_CHECK();
+    return NRL_OK;
+  });
 }
 
 int nrl_topk_interest_scores(const float* interests, const float* gate, const float* table, int64_t B, int32_t K, int64_t V, int32_t D,

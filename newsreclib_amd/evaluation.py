@@ -149,6 +149,24 @@ class _ImpressionCache:
                 meta["user_ids"], cand_idx.to(dev))
 
 
+def _click_sizes(who: str, hist_idx, hist_sizes, click_idx, click_sizes) -> torch.Tensor:
+    """The checks ``rank_clicks`` makes on the click side, for ``who``: the limit from the HOST sizes (``ValueError``) and both
+    index lists on the GPU -> the sizes as a host int64 tensor; nothing is read back."""
+    cs = click_sizes.detach().cpu().long()                  # host sizes: the limit and the offsets cost no read-back
+    if cs.numel() != int(hist_sizes.numel()):
+        raise ValueError("newsreclib_amd: hist_sizes and click_sizes must have one entry per user")
+    if cs.numel() and int(cs.max()) > ops.RANK_MAX_TARGETS:
+        raise ValueError(f"newsreclib_amd: {who} takes at most {ops.RANK_MAX_TARGETS} clicks per user (got {int(cs.max())})")
+    if not hist_idx.is_cuda or not click_idx.is_cuda:
+        raise RuntimeError(f"newsreclib_amd: `hist_idx` and `click_idx` must live on the GPU (got {hist_idx.device} and "
+                           f"{click_idx.device}); there is no CPU path")
+    return cs
+
+
+def _click_offsets(cs: torch.Tensor, dev) -> torch.Tensor:
+    return torch.cat([torch.zeros(1, dtype=torch.int64), torch.cumsum(cs, 0)]).pin_memory().to(dev, non_blocking=True)
+
+
 class NewsVectorCache(_ImpressionCache):
     """Encode-once evaluation of a drop-in recommender (any of the module mirrors: NRMS, LSTUR, NAML, TANR,
     CenNewsRec, MINS -- whatever exposes ``news_encoder`` and ``score_news_vectors``)."""
@@ -358,6 +376,68 @@ class NewsVectorCache(_ImpressionCache):
             _, q = self.module.user_queries(hv, meta)
         return ops.topk_relu_scores(q, self.projection, pred[2], pred[3], k, excl[0], excl[1], eligible)
 
+    @torch.no_grad()
+    def rank_clicks_interests(self, hist_idx: torch.Tensor, hist_sizes: torch.Tensor, click_idx: torch.Tensor,
+                              click_sizes: torch.Tensor, user_idx: Optional[torch.Tensor] = None, exclude_history: bool = True,
+                              eligible: Optional[torch.Tensor] = None, bias: Optional[torch.Tensor] = None):
+        """``rank_clicks`` for a ``multi_interest_scorer`` module (MINER) -> (rank int32 (n_clicks), score fp32 (n_clicks), ranked
+        int32 (B), status): ``recommend_interests``' interests, gate, ``interest_score_mode``, scores, order, exclusion of the
+        history and ``eligible``, with ``ops.catalogue_interest_ranks`` counting where ``recommend_interests`` selects: ``rank <=
+        k`` exactly when the click is slot ``rank - 1`` of ``recommend_interests(k)``.  The click side is that of ``rank_clicks``
+        (host ``click_sizes``, at most ``ops.RANK_MAX_TARGETS`` a user, nothing read back)."""
+        if not getattr(self.module, "multi_interest_scorer", False):
+            raise NotImplementedError(
+                f"{type(self.module).__name__} has no candidate-independent interest vectors (no `multi_interest_scorer`); a "
+                "module that scores by one dot product with a user vector (`dot_product_scorer`) is served by `rank_clicks`")
+        cs = _click_sizes("rank_clicks_interests", hist_idx, hist_sizes, click_idx, click_sizes)
+        if self.vectors is None:
+            self.build()
+        dev = self.table.device
+        hist_idx, click_idx, click_off = hist_idx.to(dev).long(), click_idx.to(dev).long(), _click_offsets(cs, dev)
+        meta = self._user_meta(hist_sizes, user_idx)
+        hv = ops.embedding_gather(self.vectors, hist_idx.reshape(-1, 1)).reshape(-1, self.vectors.shape[1])
+        with eval_mode(self.module):
+            interests, gate = self.module.user_interests(hv, meta, bias=bias.to(dev) if bias is not None else None)
+        excl = (hist_idx, meta["hist_offsets"]) if exclude_history else (None, None)
+        return ops.catalogue_interest_ranks(interests, self.vectors, click_idx, click_off, self.module.interest_score_mode, gate,
+                                            excl[0], excl[1], eligible.to(dev) if eligible is not None else None)
+
+    @torch.no_grad()
+    def rank_clicks_dnn(self, hist_idx: torch.Tensor, hist_sizes: torch.Tensor, click_idx: torch.Tensor, click_sizes: torch.Tensor,
+                        user_idx: Optional[torch.Tensor] = None, exclude_history: bool = True,
+                        eligible: Optional[torch.Tensor] = None):
+        """``rank_clicks`` for a ``dnn_predictor_scorer`` module (DKN) -> (rank int32 (n_clicks), score fp32 (n_clicks), ranked
+        int32 (B), status): ``recommend_dnn``'s user side (``user_queries`` and the cached ``projection`` under early fusion, the
+        history mean under late fusion), scores, order, exclusion of the history and ``eligible``, with
+        ``ops.catalogue_relu_ranks`` (late fusion: ``ops.catalogue_ranks``) counting where ``recommend_dnn`` selects: ``rank <= k``
+        exactly when the click is slot ``rank - 1`` of ``recommend_dnn(k)``.  The click side is that of ``rank_clicks`` (host
+        ``click_sizes``, at most ``ops.RANK_MAX_TARGETS`` a user, nothing read back)."""
+        if not getattr(self.module, "dnn_predictor_scorer", False):
+            raise NotImplementedError(
+                f"{type(self.module).__name__} has no DNN click predictor over a candidate-independent user vector (no "
+                "`dnn_predictor_scorer`); a module that scores by one dot product with a user vector (`dot_product_scorer`) is "
+                "served by `rank_clicks`, one with interest vectors (`multi_interest_scorer`) by `rank_clicks_interests`")
+        cs = _click_sizes("rank_clicks_dnn", hist_idx, hist_sizes, click_idx, click_sizes)
+        if self.vectors is None:
+            self.build()
+        dev = self.table.device
+        hist_idx, click_idx, click_off = hist_idx.to(dev).long(), click_idx.to(dev).long(), _click_offsets(cs, dev)
+        meta = self._user_meta(hist_sizes, user_idx)
+        hv = ops.embedding_gather(self.vectors, hist_idx.reshape(-1, 1)).reshape(-1, self.vectors.shape[1])
+        excl = (hist_idx, meta["hist_offsets"]) if exclude_history else (None, None)
+        eligible = eligible.to(dev) if eligible is not None else None
+        if self.module.hparams.late_fusion:
+            dense = dense_rows(hv, meta["batch_hist"], meta["batch_size"], meta["max_hist"], meta["hist_offsets"])
+            user = ops.HistMeanFn.apply(dense, meta["hist_offsets"])
+            return ops.catalogue_ranks(user, self.vectors, click_idx, click_off, excl[0], excl[1], eligible)
+        from . import ops_dkn
+        pred = self.module.click_predictor.params()
+        if self.projection is None:
+            self.projection = ops_dkn.dkn_cand_project(self.vectors, pred)
+        with eval_mode(self.module):
+            _, q = self.module.user_queries(hv, meta)
+        return ops.catalogue_relu_ranks(q, self.projection, pred[2], pred[3], click_idx, click_off, excl[0], excl[1], eligible)
+
 
 class MannerVectorCache(_ImpressionCache):
     """Encode-once evaluation of ``manner_module.MANNERModule``: one ``NewsVectorCache`` per loaded sub-model over the same
@@ -501,7 +581,8 @@ class NpaFeatureCache(_ImpressionCache):
 
     def rank_clicks(self, *args, **kwargs):
         raise NotImplementedError("only the dot-product families are served by `rank_clicks` so far (NewsVectorCache over a "
-                                  "`dot_product_scorer` module): NPA's personalized-pooling score is not yet counted")
+                                  "`dot_product_scorer` module): NPA's personalized-pooling score is counted by "
+                                  "`rank_clicks_pooled`")
 
     @torch.no_grad()
     def recommend_pooled(self, hist_idx: torch.Tensor, hist_sizes: torch.Tensor, k: int, user_idx: Optional[torch.Tensor] = None,
@@ -516,11 +597,18 @@ class NpaFeatureCache(_ImpressionCache):
         ``max_hist`` the longest history OF THE BATCH (the model's own ``to_dense_batch`` quirk): a user's vector, hence its
         ranking, depends on the batch it is in exactly as in ``scores``.  Same contract as ``NewsVectorCache.recommend``:
         ``hist_idx`` on the GPU, ``hist_sizes`` on the host, nothing read back; the features are built at the first use."""
-        from .ops_npa import npa_cached_scores
         if user_idx is None:
             raise ValueError(f"NpaFeatureCache.recommend_pooled needs user_idx: {self.user_idx_reason}")
         if not hist_idx.is_cuda:
             raise RuntimeError(f"newsreclib_amd: `hist_idx` must live on the GPU (got {hist_idx.device}); there is no CPU path")
+        hist_idx, hist_off, q_cand, user = self._pooled_user_side(hist_idx, hist_sizes, user_idx)
+        excl = (hist_idx, hist_off) if exclude_history else (None, None)
+        return ops.topk_pooled_scores(q_cand, user, self.features, k, excl[0], excl[1],
+                                      eligible.to(self.table.device) if eligible is not None else None)
+
+    def _pooled_user_side(self, hist_idx: torch.Tensor, hist_sizes: torch.Tensor, user_idx: torch.Tensor):
+        """The user side ``recommend_pooled`` documents -> (hist_idx, hist_off, q_cand, user) on the device, nothing read back."""
+        from .ops_npa import npa_cached_scores
         if self.features is None:
             self.build()
         dev = self.table.device
@@ -538,9 +626,25 @@ class NpaFeatureCache(_ImpressionCache):
         # (the scorer wants a score buffer: one padded slot per user, no candidate rows)
         _, user = npa_cached_scores(self.features, hist_idx, hist_off, no_cand, torch.zeros(B + 1, dtype=torch.int64, device=dev),
                                     q_hist, q_cand, q_news, max_hist, 1, return_user_vectors=True)
+        return hist_idx, hist_off, q_cand, user
+
+    @torch.no_grad()
+    def rank_clicks_pooled(self, hist_idx: torch.Tensor, hist_sizes: torch.Tensor, click_idx: torch.Tensor, click_sizes: torch.Tensor,
+                           user_idx: Optional[torch.Tensor] = None, exclude_history: bool = True,
+                           eligible: Optional[torch.Tensor] = None):
+        """``NewsVectorCache.rank_clicks`` by the score of ``recommend_pooled`` -> (rank int32 (n_clicks), score fp32 (n_clicks),
+        ranked int32 (B), status): ``recommend_pooled``'s queries and user vectors (``user_idx`` required; the ``max_hist`` quirk
+        included), scores, order, exclusion of the history and ``eligible``, with ``ops.catalogue_pooled_ranks`` counting where
+        ``recommend_pooled`` selects: ``rank <= k`` exactly when the click is slot ``rank - 1`` of ``recommend_pooled(k)``.  The
+        click side is that of ``rank_clicks`` (host ``click_sizes``, at most ``ops.RANK_MAX_TARGETS`` a user, nothing read back)."""
+        if user_idx is None:
+            raise ValueError(f"NpaFeatureCache.rank_clicks_pooled needs user_idx: {self.user_idx_reason}")
+        cs = _click_sizes("rank_clicks_pooled", hist_idx, hist_sizes, click_idx, click_sizes)
+        hist_idx, hist_off, q_cand, user = self._pooled_user_side(hist_idx, hist_sizes, user_idx)
+        dev = self.table.device
         excl = (hist_idx, hist_off) if exclude_history else (None, None)
-        return ops.topk_pooled_scores(q_cand, user, self.features, k, excl[0], excl[1],
-                                      eligible.to(dev) if eligible is not None else None)
+        return ops.catalogue_pooled_ranks(q_cand, user, self.features, click_idx.to(dev).long(), _click_offsets(cs, dev), excl[0],
+                                          excl[1], eligible.to(dev) if eligible is not None else None)
 
 
 def evaluate_impressions(cache: NewsVectorCache, impressions: Sequence[Dict], batch_size: int = 512,
@@ -626,7 +730,10 @@ def recommend_users(cache: NewsVectorCache, users: Sequence[Dict], k: int, batch
 
 def evaluate_full_rank(cache: NewsVectorCache, users: Sequence[Dict], top_k_list: Sequence[int] = (5, 10), batch_size: int = 512,
                        eligible: Optional[torch.Tensor] = None) -> Dict[str, float]:
-    """Full-catalogue ranking metrics of held-out clicks: ``cache.rank_clicks`` over a list of users ({"hist": idx tensor,
+    """Full-catalogue ranking metrics of held-out clicks: ``cache.rank_clicks`` (``cache.rank_clicks_interests`` where the cache's
+    module is a ``multi_interest_scorer``, ``cache.rank_clicks_dnn`` where it is a ``dnn_predictor_scorer``,
+    ``cache.rank_clicks_pooled`` where it is a ``personalized_pooling_scorer``, as ``recommend_users`` picks ``recommend_*``;
+    MANNeR's ensemble is not counted yet and ``MannerVectorCache.rank_clicks`` says so) over a list of users ({"hist": idx tensor,
     "clicks": idx tensor[, "user_idx"]}), batched as ``recommend_users`` batches them, then ``metrics.full_rank_metrics``
     (``mrr``, ``ndcg@k``, ``recall@k``, ``hit@k``, ``auc_user``; every click is ranked against every news the user could be
     recommended, not against an impression's candidates).  The ranks, the click counts and the populations of all batches stay
@@ -642,7 +749,10 @@ def evaluate_full_rank(cache: NewsVectorCache, users: Sequence[Dict], top_k_list
         hist = torch.cat([torch.as_tensor(u["hist"]).long() for u in chunk]).to(dev)
         clicks = torch.cat([torch.as_tensor(u["clicks"]).long() for u in chunk]).to(dev)
         uidx = torch.stack([torch.as_tensor(u["user_idx"]) for u in chunk]) if "user_idx" in chunk[0] else None
-        rank, _, ranked, status = cache.rank_clicks(hist, hs, clicks, cs, user_idx=uidx, eligible=eligible)
+        rank_clicks = cache.rank_clicks_interests if getattr(cache.module, "multi_interest_scorer", False) else \
+            cache.rank_clicks_dnn if getattr(cache.module, "dnn_predictor_scorer", False) else \
+            cache.rank_clicks_pooled if getattr(cache.module, "personalized_pooling_scorer", False) else cache.rank_clicks
+        rank, _, ranked, status = rank_clicks(hist, hs, clicks, cs, user_idx=uidx, eligible=eligible)
         ranks.append(rank)
         sizes.append(cs.pin_memory().to(dev, non_blocking=True))
         pops.append(ranked)

@@ -938,6 +938,91 @@ def topk_relu_scores(q: torch.Tensor, proj: torch.Tensor, w2: torch.Tensor, b2: 
     return idx, score, status
 
 
+def _rank_targets(tgt_idx, tgt_off, B: int):
+    """The target lists as every rank entry takes them, checked (``catalogue_ranks`` documents them)."""
+    tgt_idx, tgt_off = _chk(tgt_idx, torch.int64, "tgt_idx"), _chk(tgt_off, torch.int64, "tgt_off")
+    if tgt_off.numel() != B + 1:
+        raise ValueError("newsreclib_amd: tgt_off must have B + 1 entries")
+    n_tgt = int(tgt_idx.numel())
+    # (the kernel validates the offsets against n_tgt itself; as for excl_off, one beyond the list is turned into one it rejects)
+    return tgt_idx, torch.where(tgt_off > n_tgt, torch.full_like(tgt_off, -1), tgt_off), n_tgt
+
+
+def _rank_outputs(n_tgt: int, B: int, dev):
+    return (torch.empty(n_tgt, dtype=torch.int32, device=dev), torch.empty(n_tgt, dtype=torch.float32, device=dev),
+            torch.empty(B, dtype=torch.int32, device=dev), torch.zeros(1, dtype=torch.int32, device=dev))
+
+
+def catalogue_interest_ranks(interests: torch.Tensor, table: torch.Tensor, tgt_idx: torch.Tensor, tgt_off: torch.Tensor, mode: str,
+                             gate: Optional[torch.Tensor] = None, excl_idx: Optional[torch.Tensor] = None,
+                             excl_off: Optional[torch.Tensor] = None, eligible: Optional[torch.Tensor] = None, slices: int = 0):
+    """``nrl_catalogue_interest_ranks``: ``catalogue_ranks`` by the scores of ``topk_interest_scores`` -- ``interests`` (B, K, D),
+    ``mode`` "max" / "mean" / "weighted" (``gate`` (B, K, D), required by "weighted" alone) -> (rank int32 (n_tgt), score fp32
+    (n_tgt), ranked int32 (B), status (1) int32) with the targets, population, order, masks and flags (``RANK_FLAGS``) of
+    ``catalogue_ranks`` and the score bits of ``topk_interest_scores``: ``rank <= k`` exactly when the target is slot ``rank - 1``
+    of that call's list.  Neither the (B, V) nor the (B K, V) matrix is materialised; nothing here synchronises with the host."""
+    from .ops_miner import SCORE_MODES
+    lib = _lib.load()
+    interests, table = _chk(interests, torch.float32, "interests"), _chk(table, torch.float32, "table")
+    if interests.dim() != 3 or table.dim() != 2 or interests.shape[2] != table.shape[1]:
+        raise ValueError(f"newsreclib_amd: interests (B, K, D) and table (V, D) expected, got {tuple(interests.shape)} and "
+                         f"{tuple(table.shape)}")
+    if mode not in SCORE_MODES:
+        raise ValueError(f"newsreclib_amd: mode must be one of {sorted(SCORE_MODES)} (got {mode!r})")
+    B, K, D, V = int(interests.shape[0]), int(interests.shape[1]), int(interests.shape[2]), int(table.shape[0])
+    if K > TOPK_MAX_INTERESTS:
+        raise NotImplementedError(f"newsreclib_amd: catalogue_interest_ranks takes at most {TOPK_MAX_INTERESTS} interest vectors "
+                                  f"per user (got {K})")
+    if mode == "weighted":
+        if gate is None:
+            raise ValueError("newsreclib_amd: mode 'weighted' needs `gate` (B, K, D) = gelu(user_vector Wt^T)")
+        gate = _chk(gate, torch.float32, "gate")
+        if gate.shape != interests.shape:
+            raise ValueError(f"newsreclib_amd: gate must have the shape of interests, got {tuple(gate.shape)}")
+    else:
+        gate = None
+    tgt_idx, tgt_off, n_tgt = _rank_targets(tgt_idx, tgt_off, B)
+    excl_idx, excl_off, eligible = _topk_masks(excl_idx, excl_off, eligible, B, V)
+    rank, score, ranked, status = _rank_outputs(n_tgt, B, interests.device)
+    ws = workspace(lib.nrl_catalogue_ranks_workspace_size(B, V, D, n_tgt, int(slices)), interests.device)
+    ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
+    _lib.check(lib.nrl_catalogue_interest_ranks(interests.data_ptr(), ptr(gate), table.data_ptr(), B, K, V, D, SCORE_MODES[mode],
+                                                tgt_idx.data_ptr(), tgt_off.data_ptr(), n_tgt, ptr(excl_idx), ptr(excl_off),
+                                                ptr(eligible), int(slices), rank.data_ptr(), score.data_ptr(), ranked.data_ptr(),
+                                                status.data_ptr(), ws.data_ptr(), ws.numel(), _stream()),
+               "nrl_catalogue_interest_ranks")
+    return rank, score, ranked, status
+
+
+def catalogue_relu_ranks(q: torch.Tensor, proj: torch.Tensor, w2: torch.Tensor, b2: torch.Tensor, tgt_idx: torch.Tensor,
+                         tgt_off: torch.Tensor, excl_idx: Optional[torch.Tensor] = None, excl_off: Optional[torch.Tensor] = None,
+                         eligible: Optional[torch.Tensor] = None, slices: int = 0):
+    """``nrl_catalogue_relu_ranks``: ``catalogue_ranks`` by the scores of ``topk_relu_scores`` -- ``q`` (B, Hd), ``proj`` (V, Hd),
+    ``w2`` (Hd values), ``b2`` (one value), Hd in [1, 64] -> (rank int32 (n_tgt), score fp32 (n_tgt), ranked int32 (B), status (1)
+    int32) with the targets, population, order, masks and flags (``RANK_FLAGS``) of ``catalogue_ranks`` and the score bits of
+    ``topk_relu_scores``: ``rank <= k`` exactly when the target is slot ``rank - 1`` of that call's list.  Neither the (B, V) nor
+    the (B, V, Hd) array is materialised; nothing here synchronises with the host."""
+    lib = _lib.load()
+    if q.dim() != 2 or proj.dim() != 2 or q.shape[1] != proj.shape[1] or w2.numel() != q.shape[1] or b2.numel() != 1:
+        raise ValueError(f"newsreclib_amd: q (B, Hd), proj (V, Hd), w2 (Hd) and b2 (1) expected, got {tuple(q.shape)}, "
+                         f"{tuple(proj.shape)}, {tuple(w2.shape)} and {tuple(b2.shape)}")
+    q, proj = _chk(q, torch.float32, "q"), _chk(proj, torch.float32, "proj")
+    w2, b2 = _chk(w2, torch.float32, "w2"), _chk(b2, torch.float32, "b2")
+    B, Hd, V = int(q.shape[0]), int(q.shape[1]), int(proj.shape[0])
+    if not 1 <= Hd <= TOPK_MAX_HIDDEN:
+        raise NotImplementedError(f"newsreclib_amd: catalogue_relu_ranks takes a hidden width in [1, {TOPK_MAX_HIDDEN}] (got {Hd})")
+    tgt_idx, tgt_off, n_tgt = _rank_targets(tgt_idx, tgt_off, B)
+    excl_idx, excl_off, eligible = _topk_masks(excl_idx, excl_off, eligible, B, V)
+    rank, score, ranked, status = _rank_outputs(n_tgt, B, q.device)
+    ws = workspace(lib.nrl_catalogue_ranks_workspace_size(B, V, 4, n_tgt, int(slices)), q.device)
+    ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
+    _lib.check(lib.nrl_catalogue_relu_ranks(q.data_ptr(), proj.data_ptr(), w2.data_ptr(), b2.data_ptr(), B, V, Hd, tgt_idx.data_ptr(),
+                                            tgt_off.data_ptr(), n_tgt, ptr(excl_idx), ptr(excl_off), ptr(eligible), int(slices),
+                                            rank.data_ptr(), score.data_ptr(), ranked.data_ptr(), status.data_ptr(), ws.data_ptr(),
+                                            ws.numel(), _stream()), "nrl_catalogue_relu_ranks")
+    return rank, score, ranked, status
+
+
 TOPK_MAX_TOKENS = 128
 
 
@@ -971,3 +1056,33 @@ def topk_pooled_scores(q: torch.Tensor, user: torch.Tensor, features: torch.Tens
                                           ptr(excl_off), ptr(eligible), int(slices), idx.data_ptr(), score.data_ptr(),
                                           status.data_ptr(), ws.data_ptr(), ws.numel(), _stream()), "nrl_topk_pooled_scores")
     return idx, score, status
+
+
+def catalogue_pooled_ranks(q: torch.Tensor, user: torch.Tensor, features: torch.Tensor, tgt_idx: torch.Tensor, tgt_off: torch.Tensor,
+                           excl_idx: Optional[torch.Tensor] = None, excl_off: Optional[torch.Tensor] = None,
+                           eligible: Optional[torch.Tensor] = None, slices: int = 0):
+    """``nrl_catalogue_pooled_ranks``: ``catalogue_ranks`` by the scores of ``topk_pooled_scores`` -- ``q`` (B, F), ``user`` (B, F),
+    ``features`` (V, L, F), L in [1, 128], F a multiple of 4 up to 1024 -> (rank int32 (n_tgt), score fp32 (n_tgt), ranked int32
+    (B), status (1) int32) with the targets, population, order, masks and flags (``RANK_FLAGS``) of ``catalogue_ranks`` and the
+    score bits of ``topk_pooled_scores``: ``rank <= k`` exactly when the target is slot ``rank - 1`` of that call's list.  The
+    targets' feature maps are read in place: no (B, V), (B, V, L) or (n_tgt, L, F) array is materialised; nothing here
+    synchronises with the host."""
+    lib = _lib.load()
+    if q.dim() != 2 or features.dim() != 3 or user.shape != q.shape or q.shape[1] != features.shape[2]:
+        raise ValueError(f"newsreclib_amd: q (B, F), user (B, F) and features (V, L, F) expected, got {tuple(q.shape)}, "
+                         f"{tuple(user.shape)} and {tuple(features.shape)}")
+    q, user, features = _chk(q, torch.float32, "q"), _chk(user, torch.float32, "user"), _chk(features, torch.float32, "features")
+    B, F_, V, L = int(q.shape[0]), int(q.shape[1]), int(features.shape[0]), int(features.shape[1])
+    if not 1 <= L <= TOPK_MAX_TOKENS:
+        raise NotImplementedError(f"newsreclib_amd: catalogue_pooled_ranks takes feature maps of 1 to {TOPK_MAX_TOKENS} tokens "
+                                  f"(got {L})")
+    tgt_idx, tgt_off, n_tgt = _rank_targets(tgt_idx, tgt_off, B)
+    excl_idx, excl_off, eligible = _topk_masks(excl_idx, excl_off, eligible, B, V)
+    rank, score, ranked, status = _rank_outputs(n_tgt, B, q.device)
+    ws = workspace(lib.nrl_catalogue_ranks_workspace_size(B, V, 4, n_tgt, int(slices)), q.device)
+    ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
+    _lib.check(lib.nrl_catalogue_pooled_ranks(q.data_ptr(), user.data_ptr(), features.data_ptr(), B, V, L, F_, tgt_idx.data_ptr(),
+                                              tgt_off.data_ptr(), n_tgt, ptr(excl_idx), ptr(excl_off), ptr(eligible), int(slices),
+                                              rank.data_ptr(), score.data_ptr(), ranked.data_ptr(), status.data_ptr(), ws.data_ptr(),
+                                              ws.numel(), _stream()), "nrl_catalogue_pooled_ranks")
+    return rank, score, ranked, status
