@@ -1245,6 +1245,41 @@ int nrl_catalogue_pooled_ranks(const float* q, const float* user, const float* f
                                float* out_score /* n_targets */, int32_t* out_ranked /* B */, int32_t* status, void* ws,
                                size_t ws_bytes, void* stream);
 
+/* nrl_catalogue_ensemble_ranks: nrl_catalogue_ranks under the scores of nrl_topk_ensemble_scores (MANNeR): the evaluation
+ *   counterpart of that entry, again without a (B, V) matrix.
+ *   users, tables, weights (HOST arrays of T device pointers / T floats, read during the call), T, B, V, D, the raw scores, the
+ *     statistics, the score z, the invariance statement, out_stats (B, T, 2), the caller-provided `moments` scratch
+ *     (B * NRL_TOPK_STAT_CHUNKS * T * 3 floats, overwritten) and NRL_TOPK_E_STATS as for nrl_topk_ensemble_scores: the statistics
+ *     pass is that entry's, launched over the same chunk plan from V, so out_stats has its bits.
+ *   Population (P_u as for nrl_topk_ensemble_scores, less the rows whose z is NaN), order, targets, ownership of slots,
+ *     out_rank / out_score / out_ranked, NRL_TOPK_E_EXCLUDE / NRL_TOPK_E_OFFSETS / NRL_TOPK_E_NAN, NRL_RANK_E_TARGETS and
+ *     NRL_RANK_E_TARGET_ROW as for nrl_catalogue_ranks.
+ *   NRL_TOPK_E_STATS: a user whose scores of some table cannot be standardised has ranks 0, scores -inf and out_ranked 0; its
+ *     out_stats row says why.  The other users are untouched.
+ *   Bit identity: the count walk runs the tile producer of the ensemble scores kernel (the same device function), and a target's
+ *     score is computed by the same chain: per sub-model in ascending t the tile product of the owner's row of users[t] with the
+ *     gathered target row of tables[t], folded as w_t ((s - mu_t) / sd_t) by the same rounded operations in the same order.  So
+ *     out_score[j] has the bits nrl_topk_ensemble_scores returns for that (user, row), and for every k <= NRL_TOPK_MAX_K:
+ *     out_rank[j] = r <= k if and only if out_idx[u, r - 1] == tgt_idx[j].
+ *   Determinism: the statistics as above, the counts integers: nothing depends on B, the user's place in the batch, slices, the
+ *     grid, the GEMM engine setting or the run.  No floating-point atomics, no allocation, no host synchronisation.
+ *   Workspace: nrl_catalogue_ensemble_ranks_workspace_size (callable without a device; its table is
+ *     tests/data/catalogue_ensemble_rank_workspace_sizes.json): the layout of nrl_catalogue_ranks with T gathered blocks,
+ *     T * n_targets * D * 4, and (B + n_targets) * slices * 4 of per-slice counts, each region rounded up to 256; never O(B * V).
+ *     B == 0 returns success without a launch; V == 0 gives ranks 0, out_ranked 0 and NRL_TOPK_E_STATS; n_targets == 0 still
+ *     fills out_ranked and out_stats.  Negative sizes, T outside [1, NRL_TOPK_MAX_MODELS], sizes outside the limits of
+ *     nrl_topk_scores, n_targets >= 2^31, a null status, tgt_idx without tgt_off, a null users / tables / weights array or
+ *     users[t] / tables[t], a null out_stats or moments return NRL_E_INVALID, a short workspace NRL_E_WORKSPACE, all before any
+ *     launch. */
+size_t nrl_catalogue_ensemble_ranks_workspace_size(int32_t T, int64_t B, int64_t V, int32_t D, int64_t n_targets, int32_t slices);
+int nrl_catalogue_ensemble_ranks(const float* const* users, const float* const* tables, const float* weights, int32_t T,
+                                 int64_t B, int64_t V, int32_t D, const int64_t* tgt_idx, const int64_t* tgt_off,
+                                 int64_t n_targets, const int64_t* excl_idx, const int64_t* excl_off, const uint8_t* eligible,
+                                 int32_t slices, int32_t* out_rank /* n_targets */, float* out_score /* n_targets */,
+                                 int32_t* out_ranked /* B */, float* out_stats /* (B, T, 2): mean, sd */,
+                                 float* moments /* (B, NRL_TOPK_STAT_CHUNKS, T, 3) caller-provided scratch */,
+                                 int32_t* status, void* ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

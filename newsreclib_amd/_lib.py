@@ -324,6 +324,11 @@ SIGNATURES = {
     "nrl_catalogue_pooled_ranks": (c_int32, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int32, c_int32, c_void_p, c_void_p,
                                              c_int64, c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p,
                                              c_void_p, c_size_t, c_void_p]),
+    "nrl_catalogue_ensemble_ranks_workspace_size": (c_size_t, [c_int32, c_int64, c_int64, c_int32, c_int64, c_int32]),
+    "nrl_catalogue_ensemble_ranks": (c_int32, [POINTER(c_void_p), POINTER(c_void_p), POINTER(c_float), c_int32, c_int64, c_int64,
+                                               c_int32, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int32,
+                                               c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,
+                                               c_void_p]),
     "nrl_embedding_rows_fwd": (c_int32, [c_void_p, c_void_p, c_int64, c_int32, c_double, c_uint64, c_uint32,
                                          c_void_p, c_void_p]),
     "nrl_embedding_rows_bwd": (c_int32, [c_void_p, c_void_p, c_int64, c_int32, c_double, c_uint64, c_uint32,

@@ -23,7 +23,7 @@
 //   tkp_scores_kernel  NPA's personalized pooling: per token of the cached feature maps a two-operand tile product kept in
 //       registers and folded into an online softmax per (user, row); the other stages unchanged.
 //   tkc_*_kernel       the rank of held-out rows: the same walk with a consumer that counts instead of selects;
-//   tkic_* / tkrc_* / tkpc_*  that consumer under the tile producers of tki_ / tkr_ / tkp_scores_kernel.
+//   tkic_* / tkrc_* / tkpc_* / tkec_*  that consumer under the tile producers of tki_ / tkr_ / tkp_ / tke_scores_kernel.
 //   tk_merge_kernel    one wave per user: validates the user's offsets and exclusion indices (status flags), merges the `slices`
 //       partial lists with the same insertion and writes (row, score) or (-1, -inf).
 // The stages (exclusion cache, eligibility, tile product, per-user selection, flush) are written once, as inlined device functions
@@ -696,6 +696,53 @@ __global__ __launch_bounds__(64) void tke_finish_kernel(TkeArgs A) {
   if (__ballot(bad) && lane == 0) atomicOr(A.status, NRL_TOPK_E_STATS);
 }
 
+// One sub-model's share w ((s - mean) / sd) of an ensemble score, folded into `acc` (the first share starts the sum): every
+// operation rounded to fp32 on its own.  Written once for the tile and for the target kernel, with contraction switched off: the
+// __f*_rn intrinsics are plain operators, and where the product feeds the sum directly the compiler would otherwise fuse the two
+// into an fma in one kernel and not in the other, one ulp apart.
+__device__ __forceinline__ float tke_fold_z(float acc, bool first, float w, float s, float mean, float sd) {
+#pragma clang fp contract(off)
+  const float z = w * ((s - mean) / sd);
+  return first ? z : acc + z;
+}
+
+// The tile producer of the ensemble kernels (scores and count): per sub-model t in ascending order the product of the staged rows
+// `urow` of users[t] with the tile of tables[t] at v0 into `sc`, folded into the ensemble tile `zs` as w_t (s - mu_t) / sd_t with
+// the workgroup's statistics st[TK_BU][T][2], one rounded operation at a time.  Ends with `zs` complete, `sc` free and the
+// workgroup synchronised.
+__device__ __forceinline__ void tke_tile(const float* const (&users)[NRL_TOPK_MAX_MODELS], const float* const (&tables)[NRL_TOPK_MAX_MODELS],
+                                         const float (&wt)[NRL_TOPK_MAX_MODELS], int T, int64_t urow, bool ua_ok, int v0, int V, int D,
+                                         float* sc, float* zs, const float* st) {
+  const int tid = threadIdx.x;
+  for (int t = 0; t < T; ++t) {
+    const float* const pa[1] = {tke_pick(users, t) + urow * D};
+    tk_tile_product<1>(pa, ua_ok, tke_pick(tables, t), v0, V, D, sc);
+    const float w = t == 0 ? wt[0] : (t == 1 ? wt[1] : wt[2]);
+    for (int i = tid; i < TK_BU * TK_BV; i += TK_THREADS) {
+      const int ul = i / TK_BV, at = ul * TK_SCLD + (i % TK_BV);
+      const float* const s2 = st + (ul * T + t) * 2;
+      zs[at] = tke_fold_z(t ? zs[at] : 0.f, t == 0, w, sc[at], s2[0], s2[1]);
+    }
+    __syncthreads();                                  // the ensemble tile is complete; tile 0 is free for the next operands
+  }
+}
+
+// The workgroup's copy st[TK_BU][T][2] of the (mean, sd) of its `nu` users from u0 on; a refused user (and a slot without one) is
+// marked by sd = 0 in its first entry.  The caller's next barrier publishes it.
+__device__ __forceinline__ void tke_stage_stats(const float* out_stats, int64_t u0, int nu, int T, float* st) {
+  const int tid = threadIdx.x;
+  if (tid < TK_BU) {
+    bool ok = tid < nu;
+    for (int t = 0; t < T; ++t) {
+      const float mean = ok ? out_stats[((u0 + tid) * T + t) * 2] : 0.f, sd = ok ? out_stats[((u0 + tid) * T + t) * 2 + 1] : 1.f;
+      st[(tid * T + t) * 2] = mean;
+      st[(tid * T + t) * 2 + 1] = sd;
+      ok = ok && tke_sd_ok(sd);
+    }
+    if (!ok) st[tid * T * 2 + 1] = 0.f;
+  }
+}
+
 __global__ __launch_bounds__(TK_THREADS) void tke_scores_kernel(TkeArgs A) {
   extern __shared__ __attribute__((aligned(16))) unsigned char tk_smem[];
   float* const sc = reinterpret_cast<float*>(tk_smem);                       // [TK_BU][TK_SCLD] the raw scores of one table
@@ -719,38 +766,19 @@ __global__ __launch_bounds__(TK_THREADS) void tke_scores_kernel(TkeArgs A) {
   const int nvt = (v_end - v_begin + TK_BV - 1) / TK_BV;
 
   for (int i = tid; i < TK_BU * k; i += TK_THREADS) lists[i] = 0ull;
-  if (tid < TK_BU) {                                  // a refused user (and a slot without one) is marked by sd = 0 in its first entry
-    bool ok = tid < nu;
-    for (int t = 0; t < T; ++t) {
-      const float mean = ok ? A.out_stats[((u0 + tid) * T + t) * 2] : 0.f, sd = ok ? A.out_stats[((u0 + tid) * T + t) * 2 + 1] : 1.f;
-      st[(tid * T + t) * 2] = mean;
-      st[(tid * T + t) * 2 + 1] = sd;
-      ok = ok && tke_sd_ok(sd);
-    }
-    if (!ok) st[tid * T * 2 + 1] = 0.f;
-  }
+  tke_stage_stats(A.out_stats, u0, nu, T, st);
   tk_cache_exclusions(A, u0, nu, TK_BU, xs, xn, xl);   // (its barrier also publishes `lists` and `st`)
 
   const int ul_begin = wave * TK_USERS_PER_WAVE, ul_end = ul_begin + TK_USERS_PER_WAVE < nu ? ul_begin + TK_USERS_PER_WAVE : nu;
   const int srow = tid >> 2;
   const bool ua_ok = srow < nu;
+  const int64_t urow = ua_ok ? u0 + srow : A.B - 1;   // staging: tile row r is user u0 + r of every sub-model, zero past the last
   bool nan = false;
 
   for (int vt = 0; vt < nvt; ++vt) {
     const int v0 = v_begin + vt * TK_BV;
     tk_fill_eligible(A.eligible, v0, V, el);
-    for (int t = 0; t < T; ++t) {
-      const float* const pa[1] = {tke_pick(A.users, t) + (ua_ok ? u0 + srow : A.B - 1) * A.D};
-      tk_tile_product<1>(pa, ua_ok, tke_pick(A.tables, t), v0, V, A.D, sc);
-      const float w = t == 0 ? A.w[0] : (t == 1 ? A.w[1] : A.w[2]);
-      for (int i = tid; i < TK_BU * TK_BV; i += TK_THREADS) {
-        const int ul = i / TK_BV, at = ul * TK_SCLD + (i % TK_BV);
-        const float* const s2 = st + (ul * T + t) * 2;
-        const float z = __fmul_rn(w, __fdiv_rn(__fsub_rn(sc[at], s2[0]), s2[1]));
-        zs[at] = t ? __fadd_rn(zs[at], z) : z;
-      }
-      __syncthreads();                                // the ensemble tile is complete; tile 0 is free for the next operands
-    }
+    tke_tile(A.users, A.tables, A.w, T, urow, ua_ok, v0, V, A.D, sc, zs, st);
 
     const bool e_0 = el[lane] != 0, e_1 = el[64 + lane] != 0;
     for (int ul = ul_begin; ul < ul_end; ++ul) {
@@ -1525,6 +1553,105 @@ __global__ __launch_bounds__(TK_THREADS, 2) void tkpc_count_kernel(TkpcArgs A) {
   for (int ul = ul_begin; ul < ul_end; ++ul) tkc_flush_user(A, S, ul, u0 + ul, sl, lane);
 }
 
+// MANNeR: tke_scores_kernel's walk.  The statistics pass runs first, as for the top-k; the raw tile, the ensemble tile and the
+// workgroup's statistics (67.5 KB) and the consumer's arrays (41.9 KB) are 109.4 KB: one workgroup per CU.
+struct TkecArgs : TkcArgs {                    // `user` / `table` are those of sub-model 0; the ensemble fields of TkeArgs
+  const float* users[NRL_TOPK_MAX_MODELS];
+  const float* tables[NRL_TOPK_MAX_MODELS];
+  float w[NRL_TOPK_MAX_MODELS];
+  int32_t T;
+  const float* stats;                          // (B, T, 2): mean, sd, as tke_finish_kernel left them
+};
+constexpr size_t TKEC_LDS = 2 * TKC_TILE_BYTES + TKE_STATS_LDS + tkc_lds_bytes(TK_BU);
+static_assert((2 * TKC_TILE_BYTES + TKE_STATS_LDS) % 16 == 0 && TKEC_LDS <= 160 * 1024,
+              "the two score tiles and the statistics leave room for one workgroup per CU");
+
+// one wave per target slot: the target's rows of tables 1 ... T - 1 into blocks 1 ... T - 1 of the (T, n_targets, D) gathered
+// workspace (tkc_init_kernel filled block 0 from table 0); zeros for a row outside V
+__global__ __launch_bounds__(64) void tkec_gather_kernel(TkecArgs A) {
+  const int64_t j = blockIdx.x;
+  const int lane = threadIdx.x, t = 1 + (int)blockIdx.y;
+  const int64_t row = A.tgt_idx[j];
+  const bool ok = row >= 0 && row < A.V;
+  const float* const table = tke_pick(A.tables, t);
+  float* const dst = A.gathered + ((int64_t)t * A.n_targets + j) * A.D;
+  const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
+  for (int c = lane * 4; c < A.D; c += 256) st4(dst + c, ok ? ld4(table + row * A.D + c) : z);
+}
+
+// One workgroup per 64 slots from j0 on, as tkc_target_kernel: per sub-model the tile product of the owners' rows of users[t] with
+// the gathered rows of tables[t]; the diagonal is the raw score tke_scores_kernel computes for that (user, row), folded with the
+// owner's statistics by the same operations in the same order.  NaN where the owner's statistics cannot standardise: the finish
+// kernel leaves such a slot at rank 0 / -inf.
+__global__ __launch_bounds__(TK_THREADS) void tkec_target_kernel(TkecArgs A) {
+  __shared__ __attribute__((aligned(16))) float sc[TK_BU * TK_SCLD];
+  const int tid = threadIdx.x, T = A.T;
+  const int64_t j0 = (int64_t)blockIdx.x * TK_BU;
+  const int srow = tid >> 2;
+  const int own = j0 + srow < A.n_targets ? A.owner[j0 + srow] : -1;
+  const bool ua_ok = own >= 0;
+  // thread i < 64 folds slot j0 + i (its own staging row is another slot's: the owner is read again)
+  const bool mine = tid < TK_BU && j0 + tid < A.n_targets;
+  const int jown = mine ? A.owner[j0 + tid] : -1;
+  bool ok = true;
+  float zsum = 0.f;
+  for (int t = 0; t < T; ++t) {
+    const float* const pa[1] = {tke_pick(A.users, t) + (int64_t)(ua_ok ? own : 0) * A.D};
+    tk_tile_product<1>(pa, ua_ok, A.gathered + (int64_t)t * A.n_targets * A.D, (int)j0, (int)A.n_targets, A.D, sc);
+    if (jown >= 0) {
+      const float mean = A.stats[((int64_t)jown * T + t) * 2], sd = A.stats[((int64_t)jown * T + t) * 2 + 1];
+      const float w = t == 0 ? A.w[0] : (t == 1 ? A.w[1] : A.w[2]);
+      zsum = tke_fold_z(zsum, t == 0, w, sc[tid * TK_SCLD + tid], mean, sd);
+      ok = ok && tke_sd_ok(sd);
+    }
+    __syncthreads();                                  // the diagonal is read; the tile is free for the next operands
+  }
+  if (mine) A.tscore[j0 + tid] = ok ? zsum : __uint_as_float(0x7FC00000u);
+}
+
+__global__ __launch_bounds__(TK_THREADS) void tkec_count_kernel(TkecArgs A) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char tk_smem[];
+  float* const sc = reinterpret_cast<float*>(tk_smem);                       // [TK_BU][TK_SCLD] the raw scores of one table
+  float* const zs = sc + TK_BU * TK_SCLD;                                    // [TK_BU][TK_SCLD] the ensemble scores
+  float* const st = zs + TK_BU * TK_SCLD;                                    // [TK_BU][T][2] mean, sd; sd 0: the user is refused
+  const TkcLds S(tk_smem + 2 * TKC_TILE_BYTES + TKE_STATS_LDS, TK_BU);
+
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int V = A.V, T = A.T;
+  const int sl = (int)(blockIdx.x % (unsigned)A.slices);
+  const int64_t u0 = (int64_t)(blockIdx.x / (unsigned)A.slices) * TK_BU;
+  const int nu = A.B - u0 < TK_BU ? (int)(A.B - u0) : TK_BU;
+  int v_begin, nvt;
+  tkc_slice(A, sl, v_begin, nvt);
+
+  tke_stage_stats(A.stats, u0, nu, T, st);
+  tkc_prologue(A, u0, nu, TK_BU, S);                  // (its barriers also publish `st`)
+
+  const int ul_begin = wave * TK_USERS_PER_WAVE, ul_end = ul_begin + TK_USERS_PER_WAVE < nu ? ul_begin + TK_USERS_PER_WAVE : nu;
+  const int srow = tid >> 2;
+  const bool ua_ok = srow < nu;
+  const int64_t urow = ua_ok ? u0 + srow : A.B - 1;
+  bool nan = false;
+
+  for (int vt = 0; vt < nvt; ++vt) {
+    const int v0 = v_begin + vt * TK_BV;
+    tk_fill_eligible(A.eligible, v0, V, S.el);
+    tke_tile(A.users, A.tables, A.w, T, urow, ua_ok, v0, V, A.D, sc, zs, st);
+
+    const bool e_0 = S.el[lane] != 0, e_1 = S.el[64 + lane] != 0;
+    for (int ul = ul_begin; ul < ul_end; ++ul) {
+      if (st[ul * T * 2 + 1] == 0.f) continue;        // refused: the counters stay 0, so the population comes out 0
+      tkc_count_user(zs + ul * TK_SCLD, S, ul, A.excl_idx, v0, e_0, e_1, lane, nan);
+    }
+    __syncthreads();                                  // the ensemble tile and `el` are free for the next tile
+  }
+
+  if (nan && lane == 0) atomicOr(A.status, NRL_TOPK_E_NAN);
+  wave_lds_sync();
+  for (int ul = ul_begin; ul < ul_end; ++ul) tkc_flush_user(A, S, ul, u0 + ul, sl, lane);
+}
+
 __device__ __forceinline__ int tkc_wave_sum(int v) {
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
@@ -1927,6 +2054,32 @@ int nrl_topk_pooled_scores(const float* q, const float* user, const float* featu
   return tk_launch("topk_pooled_scores", tkp_scores_kernel, A, slices, 1, TK_BU, stream, TKP_EXTRA_LDS);
 }
 
+// The checks both ensemble entries make after the shape checks, in this order; `who` is the entry's name in the message
+static int tke_check(const char* who, const float* const* users, const float* const* tables, const float* weights, int32_t T,
+                     int64_t V) {
+  NRL_REQUIRE(users && tables && weights, "%s: null users / tables / weights array", who);
+  for (int t = 0; t < T; ++t) NRL_REQUIRE(users[t] && (V == 0 || tables[t]), "%s: null user matrix or table of sub-model %d", who, t);
+  return NRL_OK;
+}
+
+// The statistics pass of both ensemble entries: plans the chunks and runs tke_stats_kernel and tke_finish_kernel over them
+static int tke_statistics(const char* who, TkeArgs& A, void* stream) {
+  // the statistics chunks: a function of V alone, so that the order of every reduction is
+  const int64_t nvt = ceil_div((int64_t)A.V, TK_BV);
+  A.tiles_per_chunk = (int32_t)(nvt > 0 ? ceil_div(nvt, NRL_TOPK_STAT_CHUNKS) : 1);
+  A.chunks = (int32_t)(nvt > 0 ? ceil_div(nvt, A.tiles_per_chunk) : 0);
+  const int64_t blocks = ceil_div(A.B, TK_BU) * A.chunks;
+  NRL_REQUIRE(blocks < ((int64_t)1 << 31), "%s: grid too large (%lld workgroups)", who, (long long)blocks);
+  hipStream_t st = (hipStream_t)stream;
+  if (blocks > 0) {
+    tke_stats_kernel<<<(unsigned)blocks, TK_THREADS, 0, st>>>(A);
+    NRL_LAUNCH_CHECK();
+  }
+  tke_finish_kernel<<<(unsigned)A.B, 64, 0, st>>>(A);
+  NRL_LAUNCH_CHECK();
+  return NRL_OK;
+}
+
 int nrl_topk_ensemble_scores(const float* const* users, const float* const* tables, const float* weights, int32_t T, int64_t B,
                              int64_t V, int32_t D, int32_t k, const int64_t* excl_idx, const int64_t* excl_off,
                              const uint8_t* eligible, int32_t slices, int64_t* out_idx, float* out_score, float* out_stats,
@@ -1934,9 +2087,7 @@ int nrl_topk_ensemble_scores(const float* const* users, const float* const* tabl
   NRL_REQUIRE(B >= 0 && V >= 0 && D >= 0 && slices >= 0, "topk_ensemble_scores: negative size");
   NRL_REQUIRE(T >= 1 && T <= NRL_TOPK_MAX_MODELS, "topk_ensemble_scores: T in [1, %d] sub-models (got %d)", NRL_TOPK_MAX_MODELS, T);
   NRL_TRY(tk_check("topk_ensemble_scores", B, V, D, k, excl_idx, excl_off));
-  NRL_REQUIRE(users && tables && weights, "topk_ensemble_scores: null users / tables / weights array");
-  for (int t = 0; t < T; ++t)
-    NRL_REQUIRE(users[t] && (V == 0 || tables[t]), "topk_ensemble_scores: null user matrix or table of sub-model %d", t);
+  NRL_TRY(tke_check("topk_ensemble_scores", users, tables, weights, T, V));
   NRL_REQUIRE(status, "topk_ensemble_scores: the status word is required");
   NRL_REQUIRE(out_stats && moments, "topk_ensemble_scores: out_stats and the moments scratch are required");
   if (B == 0) return NRL_OK;
@@ -1953,20 +2104,54 @@ int nrl_topk_ensemble_scores(const float* const* users, const float* const* tabl
   A.T = T;
   A.out_stats = out_stats;
   A.moments = moments;
-  // the statistics chunks: a function of V alone, so that the order of every reduction is
-  const int64_t nvt = ceil_div(V, TK_BV);
-  A.tiles_per_chunk = (int32_t)(nvt > 0 ? ceil_div(nvt, NRL_TOPK_STAT_CHUNKS) : 1);
-  A.chunks = (int32_t)(nvt > 0 ? ceil_div(nvt, A.tiles_per_chunk) : 0);
-  const int64_t blocks = ceil_div(B, TK_BU) * A.chunks;
-  NRL_REQUIRE(blocks < ((int64_t)1 << 31), "topk_ensemble_scores: grid too large (%lld workgroups)", (long long)blocks);
-  hipStream_t st = (hipStream_t)stream;
-  if (blocks > 0) {
-    tke_stats_kernel<<<(unsigned)blocks, TK_THREADS, 0, st>>>(A);
-    NRL_LAUNCH_CHECK();
-  }
-  tke_finish_kernel<<<(unsigned)B, 64, 0, st>>>(A);
-  NRL_LAUNCH_CHECK();
+  NRL_TRY(tke_statistics("topk_ensemble_scores", A, stream));
   return tk_launch("topk_ensemble_scores", tke_scores_kernel, A, slices, 2, TK_BU, stream, (size_t)TK_BU * T * 2 * 4);
+}
+
+size_t nrl_catalogue_ensemble_ranks_workspace_size(int32_t T, int64_t B, int64_t V, int32_t D, int64_t n_targets, int32_t slices) {
+  if (!tk_shape_ok(B, V, D, 1) || T < 1 || T > NRL_TOPK_MAX_MODELS || slices < 0 || n_targets < 0 || n_targets >= ((int64_t)1 << 31))
+    return 256;
+  return measure_workspace<TkcWs>([&](Arena& a, auto* w) { tkc_layout(a, B, V, T * D, n_targets, slices, TK_BU, w); });
+}
+
+int nrl_catalogue_ensemble_ranks(const float* const* users, const float* const* tables, const float* weights, int32_t T, int64_t B,
+                                 int64_t V, int32_t D, const int64_t* tgt_idx, const int64_t* tgt_off, int64_t n_targets,
+                                 const int64_t* excl_idx, const int64_t* excl_off, const uint8_t* eligible, int32_t slices,
+                                 int32_t* out_rank, float* out_score, int32_t* out_ranked, float* out_stats, float* moments,
+                                 int32_t* status, void* ws, size_t ws_bytes, void* stream) {
+  NRL_REQUIRE(B >= 0 && V >= 0 && D >= 0 && slices >= 0 && n_targets >= 0, "catalogue_ensemble_ranks: negative size");
+  NRL_REQUIRE(T >= 1 && T <= NRL_TOPK_MAX_MODELS, "catalogue_ensemble_ranks: T in [1, %d] sub-models (got %d)", NRL_TOPK_MAX_MODELS, T);
+  NRL_TRY(tk_check("catalogue_ensemble_ranks", B, V, D, 1, excl_idx, excl_off));
+  NRL_TRY(tkc_check("catalogue_ensemble_ranks", n_targets, tgt_idx, tgt_off, status));
+  NRL_TRY(tke_check("catalogue_ensemble_ranks", users, tables, weights, T, V));
+  NRL_REQUIRE(out_stats && moments, "catalogue_ensemble_ranks: out_stats and the moments scratch are required");
+  if (B == 0) return NRL_OK;
+  NRL_REQUIRE(out_ranked && (n_targets == 0 || (tgt_idx && out_rank && out_score)), "catalogue_ensemble_ranks: null argument");
+  // the layout of nrl_catalogue_ranks with T gathered blocks: (T, n_targets, D)
+  TkecArgs A;
+  int64_t blocks;
+  NRL_TRY(tkc_prepare("catalogue_ensemble_ranks", A, users[0], tables[0], B, V, D, T * D, true, tgt_idx, tgt_off, n_targets, excl_idx,
+                      excl_off, eligible, slices, TK_BU, out_rank, out_score, out_ranked, status, ws, ws_bytes, &blocks));
+  TkeArgs E;                                          // what the statistics kernels read: the fields of nrl_topk_ensemble_scores
+  static_cast<TkArgs&>(E) = static_cast<const TkArgs&>(A);
+  for (int t = 0; t < NRL_TOPK_MAX_MODELS; ++t) {
+    A.users[t] = E.users[t] = users[t < T ? t : 0];
+    A.tables[t] = E.tables[t] = tables[t < T ? t : 0];
+    A.w[t] = E.w[t] = t < T ? weights[t] : 0.f;
+  }
+  A.T = E.T = T;
+  A.stats = E.out_stats = out_stats;
+  E.moments = moments;
+  NRL_TRY(tke_statistics("catalogue_ensemble_ranks", E, stream));
+  return tkc_launch(tkec_count_kernel, A, blocks, TKEC_LDS, stream, [&](hipStream_t st) {
+    if (T > 1) {
+      tkec_gather_kernel<<<dim3((unsigned)n_targets, (unsigned)(T - 1)), 64, 0, st>>>(A);
+      NRL_LAUNCH_CHECK();
+    }
+    tkec_target_kernel<<<(unsigned)ceil_div(n_targets, TK_BU), TK_THREADS, 0, st>>>(A);
+    NRL_LAUNCH_CHECK();
+    return NRL_OK;
+  });
 }
 
 }  // extern "C"

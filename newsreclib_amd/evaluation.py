@@ -443,7 +443,8 @@ class MannerVectorCache(_ImpressionCache):
     """Encode-once evaluation of ``manner_module.MANNERModule``: one ``NewsVectorCache`` per loaded sub-model over the same
     ``DeviceNewsTable``; ``scores`` is one ``nrl_manner_scores`` launch that gathers straight from the (up to three) tables.
     ``model_step`` returns the 11-tuple ``evaluate_impressions`` consumes, with a zero tensor in the loss slot (MANNeR has no
-    loss).  The sub-models' encoders read the concatenated ``text`` input, which ``NewsVectorCache.build`` passes through because
+    loss).  ``recommend_ensemble`` / ``rank_clicks_ensemble`` rank the whole table by the ensemble z-scored over the user's
+    population (top-k and the rank of held-out clicks; ``recommend`` / ``rank_clicks`` refuse and say why).  The sub-models' encoders read the concatenated ``text`` input, which ``NewsVectorCache.build`` passes through because
     ``NewsEncoder.entity_attrs`` lists it beside ``entities`` under ``concatenate_inputs`` (that property is the cache's list of
     inputs to hand over besides title / abstract / category, entity ids or not).
 
@@ -485,8 +486,10 @@ class MannerVectorCache(_ImpressionCache):
 
     def rank_clicks(self, *args, **kwargs):
         raise NotImplementedError("only the dot-product families are served by `rank_clicks` so far (NewsVectorCache over a "
-                                  "`dot_product_scorer` module): MANNeR's ensemble of standardised scores is not yet counted; "
-                                  "rank the clicks with one sub-model's NewsVectorCache instead")
+                                  "`dot_product_scorer` module): MANNeR z-scores every sub-model's scores within a candidate list, "
+                                  "and without a named population there is no z-score to rank a click by; rank the clicks with "
+                                  "one sub-model's NewsVectorCache instead, or name the population: `rank_clicks_ensemble` "
+                                  "z-scores over every row a user may be recommended, as `recommend_ensemble` does")
 
     @torch.no_grad()
     def recommend_ensemble(self, hist_idx: torch.Tensor, hist_sizes: torch.Tensor, k: int, user_idx: Optional[torch.Tensor] = None,
@@ -498,23 +501,51 @@ class MannerVectorCache(_ImpressionCache):
         the gathered history rows of that sub-model's table, as in ``scores``; an empty history gives a NaN vector and that user
         is refused through ``status`` (``ops.TOPK_FLAGS``), as is any user whose scores cannot be standardised.  Same contract as
         ``NewsVectorCache.recommend``: ``hist_idx`` on the GPU, ``hist_sizes`` on the host, nothing read back."""
-        from .dense_batch import dense_rows
         if not hist_idx.is_cuda:
             raise RuntimeError(f"newsreclib_amd: `hist_idx` must live on the GPU (got {hist_idx.device}); there is no CPU path")
+        hist_idx, users, excl = self._ensemble_users(hist_idx, hist_sizes, user_idx, exclude_history)
+        idx, score, status, stats = ops.topk_ensemble_scores(users, self.vectors, self.weights, k, excl[0], excl[1],
+                                                             eligible.to(self.table.device) if eligible is not None else None)
+        return (idx, score, status, stats) if return_stats else (idx, score, status)
+
+    def _ensemble_users(self, hist_idx: torch.Tensor, hist_sizes: torch.Tensor, user_idx: Optional[torch.Tensor],
+                        exclude_history: bool):
+        """The user side of ``recommend_ensemble`` and ``rank_clicks_ensemble`` -> (hist_idx on the device, the user matrix of every
+        sub-model: the mean of the gathered history rows of its table, the exclusion lists (idx, offsets) or (None, None)).
+        Builds the tables when they are missing; nothing is read back."""
+        from .dense_batch import dense_rows
         if self.vectors is None:
             self.build()
-        dev = self.table.device
-        hist_idx = hist_idx.to(dev).long()
+        hist_idx = hist_idx.to(self.table.device).long()
         meta = self.caches[0]._user_meta(hist_sizes, user_idx)
         users = []
         for vec in self.vectors:
             hv = ops.embedding_gather(vec, hist_idx.reshape(-1, 1)).reshape(-1, vec.shape[1])
             dense = dense_rows(hv, meta["batch_hist"], meta["batch_size"], meta["max_hist"], meta["hist_offsets"])
             users.append(ops.HistMeanFn.apply(dense, meta["hist_offsets"]))
-        excl = (hist_idx, meta["hist_offsets"]) if exclude_history else (None, None)
-        idx, score, status, stats = ops.topk_ensemble_scores(users, self.vectors, self.weights, k, excl[0], excl[1],
-                                                             eligible.to(dev) if eligible is not None else None)
-        return (idx, score, status, stats) if return_stats else (idx, score, status)
+        return hist_idx, users, ((hist_idx, meta["hist_offsets"]) if exclude_history else (None, None))
+
+    @torch.no_grad()
+    def rank_clicks_ensemble(self, hist_idx: torch.Tensor, hist_sizes: torch.Tensor, click_idx: torch.Tensor,
+                             click_sizes: torch.Tensor, user_idx: Optional[torch.Tensor] = None, exclude_history: bool = True,
+                             eligible: Optional[torch.Tensor] = None, return_stats: bool = False):
+        """Where each user's held-out clicks land when the user's ensemble score ranks the WHOLE table -> (rank int32 (n_clicks),
+        score fp32 (n_clicks), ranked int32 (B), status[, stats (B, T, 2): mean, sd]): ``recommend_ensemble``'s user vectors,
+        population, statistics, scores, order, exclusion of the history and ``eligible``, with ``ops.catalogue_ensemble_ranks``
+        counting where ``recommend_ensemble`` selects: ``rank <= k`` exactly when the click is slot ``rank - 1`` of
+        ``recommend_ensemble(k)``.  ``rank`` is 0 when the click is not in the user's population, and for every click of a user
+        ``recommend_ensemble`` refuses (``status``: ``ops.ENSEMBLE_RANK_FLAGS``; its ``ranked`` is 0 too).  The z-score is taken
+        over the user's whole population, not over an impression's candidates: it is the number ``recommend_ensemble`` ranks
+        by, not the one ``scores`` returns for an impression.  Same contract as ``NewsVectorCache.rank_clicks``: ``hist_idx``
+        and ``click_idx`` on the GPU, ``hist_sizes`` and ``click_sizes`` on the host, at most ``ops.RANK_MAX_TARGETS`` clicks a
+        user (``ValueError`` otherwise), nothing read back."""
+        cs = _click_sizes("rank_clicks_ensemble", hist_idx, hist_sizes, click_idx, click_sizes)
+        hist_idx, users, excl = self._ensemble_users(hist_idx, hist_sizes, user_idx, exclude_history)
+        dev = self.table.device
+        rank, score, ranked, status, stats = ops.catalogue_ensemble_ranks(
+            users, self.vectors, self.weights, click_idx.to(dev).long(), _click_offsets(cs, dev), excl[0], excl[1],
+            eligible.to(dev) if eligible is not None else None)
+        return (rank, score, ranked, status, stats) if return_stats else (rank, score, ranked, status)
 
 
 class NpaFeatureCache(_ImpressionCache):
@@ -729,17 +760,27 @@ def recommend_users(cache: NewsVectorCache, users: Sequence[Dict], k: int, batch
 
 
 def evaluate_full_rank(cache: NewsVectorCache, users: Sequence[Dict], top_k_list: Sequence[int] = (5, 10), batch_size: int = 512,
-                       eligible: Optional[torch.Tensor] = None) -> Dict[str, float]:
+                       eligible: Optional[torch.Tensor] = None, ensemble: bool = False) -> Dict[str, float]:
     """Full-catalogue ranking metrics of held-out clicks: ``cache.rank_clicks`` (``cache.rank_clicks_interests`` where the cache's
     module is a ``multi_interest_scorer``, ``cache.rank_clicks_dnn`` where it is a ``dnn_predictor_scorer``,
-    ``cache.rank_clicks_pooled`` where it is a ``personalized_pooling_scorer``, as ``recommend_users`` picks ``recommend_*``;
-    MANNeR's ensemble is not counted yet and ``MannerVectorCache.rank_clicks`` says so) over a list of users ({"hist": idx tensor,
+    ``cache.rank_clicks_pooled`` where it is a ``personalized_pooling_scorer``, as ``recommend_users`` picks ``recommend_*``)
+    over a list of users ({"hist": idx tensor,
     "clicks": idx tensor[, "user_idx"]}), batched as ``recommend_users`` batches them, then ``metrics.full_rank_metrics``
     (``mrr``, ``ndcg@k``, ``recall@k``, ``hit@k``, ``auc_user``; every click is ranked against every news the user could be
     recommended, not against an impression's candidates).  The ranks, the click counts and the populations of all batches stay
     on the device; one device-to-host copy at the end.  The OR of the batches' status words (``ops.RANK_FLAGS``: each flag is
-    handled by the kernel) is passed on as one warning."""
+    handled by the kernel) is passed on as one warning.
+
+    ``ensemble=True`` ranks by MANNeR's ensemble instead: ``cache.rank_clicks_ensemble`` (``MannerVectorCache``; ``TypeError`` for
+    a cache without one), the warning worded from ``ops.ENSEMBLE_RANK_FLAGS``.  It is opt-in, where ``recommend_users`` picks
+    ``recommend_ensemble`` by itself, because the z-score over the whole catalogue is a different number from the z-score over an
+    impression's candidates that MANNeR's ``scores`` returns: the default must not silently change what ``rank_clicks`` means for
+    MANNeR, so without the flag ``MannerVectorCache.rank_clicks`` keeps refusing and says where to go."""
     from .metrics import full_rank_metrics
+    if ensemble and not callable(getattr(cache, "rank_clicks_ensemble", None)):
+        raise TypeError(f"evaluate_full_rank(ensemble=True) needs a cache with `rank_clicks_ensemble` (MannerVectorCache), got "
+                        f"{type(cache).__name__}")
+    flags = ops.ENSEMBLE_RANK_FLAGS if ensemble else ops.RANK_FLAGS
     dev = cache.table.device
     ranks, sizes, pops, words = [], [], [], []
     for lo in range(0, len(users), batch_size):
@@ -752,6 +793,8 @@ def evaluate_full_rank(cache: NewsVectorCache, users: Sequence[Dict], top_k_list
         rank_clicks = cache.rank_clicks_interests if getattr(cache.module, "multi_interest_scorer", False) else \
             cache.rank_clicks_dnn if getattr(cache.module, "dnn_predictor_scorer", False) else \
             cache.rank_clicks_pooled if getattr(cache.module, "personalized_pooling_scorer", False) else cache.rank_clicks
+        if ensemble:
+            rank_clicks = cache.rank_clicks_ensemble
         rank, _, ranked, status = rank_clicks(hist, hs, clicks, cs, user_idx=uidx, eligible=eligible)
         ranks.append(rank)
         sizes.append(cs.pin_memory().to(dev, non_blocking=True))
@@ -768,5 +811,5 @@ def evaluate_full_rank(cache: NewsVectorCache, users: Sequence[Dict], top_k_list
     word = int(packed[-1])
     if word:                                                # the kernel has dealt with each of these; the caller should know
         import warnings
-        warnings.warn("evaluate_full_rank: " + "; ".join(msg for bit, msg in ops.RANK_FLAGS.items() if word & bit))
+        warnings.warn("evaluate_full_rank: " + "; ".join(msg for bit, msg in flags.items() if word & bit))
     return full_rank_metrics(packed[:n], packed[n:n + B], packed[n + B:n + 2 * B], top_k_list)

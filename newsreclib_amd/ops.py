@@ -903,6 +903,54 @@ def topk_ensemble_scores(users: Sequence[torch.Tensor], tables: Sequence[torch.T
     return idx, score, status, stats
 
 
+# the status word of ``catalogue_ensemble_ranks``: the flags of ``catalogue_ranks`` and, worded for ranks, the one of the ensemble
+ENSEMBLE_RANK_FLAGS = {**RANK_FLAGS,
+                       8: "a user's scores of some table cannot be standardised: zero, non-finite or undefined standard deviation "
+                          "(that user's ranks and population are 0)"}
+
+
+def catalogue_ensemble_ranks(users: Sequence[torch.Tensor], tables: Sequence[torch.Tensor], weights: Sequence[float],
+                             tgt_idx: torch.Tensor, tgt_off: torch.Tensor, excl_idx: Optional[torch.Tensor] = None,
+                             excl_off: Optional[torch.Tensor] = None, eligible: Optional[torch.Tensor] = None, slices: int = 0):
+    """``nrl_catalogue_ensemble_ranks``: ``catalogue_ranks`` by the scores of ``topk_ensemble_scores`` -- ``users[t]`` (B, D),
+    ``tables[t]`` (V, D) and ``weights[t]`` for T in {1, 2, 3} sub-models -> (rank int32 (n_tgt), score fp32 (n_tgt), ranked int32
+    (B), status (1) int32, stats (B, T, 2) fp32: mean, sd) with the targets, population, order and masks of ``catalogue_ranks`` and
+    the statistics and score bits of ``topk_ensemble_scores``: ``rank <= k`` exactly when the target is slot ``rank - 1`` of that
+    call's list.  ``status`` (``ENSEMBLE_RANK_FLAGS``): the flags of ``catalogue_ranks`` and one more -- a user whose scores cannot
+    be standardised has ranks 0, scores ``-inf`` and ``ranked`` 0.  No (B, V) matrix is materialised; nothing here synchronises
+    with the host."""
+    lib = _lib.load()
+    users, tables = list(users), list(tables)
+    T = len(tables)
+    if not 1 <= T <= TOPK_MAX_MODELS or len(users) != T or len(weights) != T:
+        raise ValueError(f"newsreclib_amd: 1 to {TOPK_MAX_MODELS} sub-models with one user matrix, one table and one weight each "
+                         f"(got {len(users)}, {T} and {len(weights)})")
+    if users[0].dim() != 2 or tables[0].dim() != 2 or users[0].shape[1] != tables[0].shape[1] or \
+            any(u.shape != users[0].shape for u in users) or any(t.shape != tables[0].shape for t in tables):
+        raise ValueError(f"newsreclib_amd: users (B, D) and tables (V, D) of one shape each expected, got "
+                         f"{[tuple(u.shape) for u in users]} and {[tuple(t.shape) for t in tables]}")
+    users = [_chk(u, torch.float32, "users") for u in users]
+    tables = [_chk(t, torch.float32, "tables") for t in tables]
+    B, D, V = int(users[0].shape[0]), int(users[0].shape[1]), int(tables[0].shape[0])
+    tgt_idx, tgt_off, n_tgt = _rank_targets(tgt_idx, tgt_off, B)
+    excl_idx, excl_off, eligible = _topk_masks(excl_idx, excl_off, eligible, B, V)
+    dev = users[0].device
+    rank, score, ranked, status = _rank_outputs(n_tgt, B, dev)
+    stats = torch.empty((B, T, 2), dtype=torch.float32, device=dev)
+    moments = torch.empty((B, TOPK_STAT_CHUNKS, T, 3), dtype=torch.float32, device=dev)
+    ws = workspace(lib.nrl_catalogue_ensemble_ranks_workspace_size(T, B, V, D, n_tgt, int(slices)), dev)
+    ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
+    uptr = (ctypes.c_void_p * T)(*[u.data_ptr() for u in users])
+    tptr = (ctypes.c_void_p * T)(*[t.data_ptr() for t in tables])
+    wts = (ctypes.c_float * T)(*[float(w) for w in weights])
+    _lib.check(lib.nrl_catalogue_ensemble_ranks(uptr, tptr, wts, T, B, V, D, tgt_idx.data_ptr(), tgt_off.data_ptr(), n_tgt,
+                                                ptr(excl_idx), ptr(excl_off), ptr(eligible), int(slices), rank.data_ptr(),
+                                                score.data_ptr(), ranked.data_ptr(), stats.data_ptr(), moments.data_ptr(),
+                                                status.data_ptr(), ws.data_ptr(), ws.numel(), _stream()),
+               "nrl_catalogue_ensemble_ranks")
+    return rank, score, ranked, status, stats
+
+
 TOPK_MAX_HIDDEN = 64
 
 
