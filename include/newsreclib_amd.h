@@ -871,6 +871,22 @@ int nrl_caum_score_bwd(const float* d_scores, const float* z2, const float* w3, 
                        const float* alpha, const float* user, const int64_t* cand_offsets, int64_t B, int32_t C,
                        int32_t slot0, int32_t H, int32_t N2, int32_t U, float* d_z2, float* d_x, float* d_cd, float* d_w3,
                        float* d_b3, void* ws, size_t ws_bytes, void* stream);
+/* Factored evaluation (no dropout): the q|k|v row of (user b, slot i, position t) is qkv_h[b * H + t] + qkv_c[cand_offsets[b] + i]
+ * (rows of 3 * heads * head_dim), qkv_h alone where user b has no slot i.  nrl_caum_eval_attn runs the across-users attention
+ * (keys: all B users) for the queries [j0, j1) of the slot-major pair list: pair_row (n) = flat candidate row, pair_user (n) = its
+ * user, ordered by (slot, user).  slot_tab (entries, 4) int32 = {slot, first pair, pair count, first work item} of every slot the
+ * range touches, a slot taking ceil(pair count / 64) * H * heads work items; n_items = their total (< 2^31).
+ * o ((j1 - j0) * H, heads * head_dim), row (j - j0) * H + t.  Every index taken from cand_offsets, the pair list or the table
+ * is range-checked on the device: a violation ORs 1 into *status (int32, never cleared here) and that pair's rows are zeros.
+ * Exact-fp32 matrix cores under either engine; no workspace, no float atomics, nothing read back.
+ * nrl_caum_eval_add: x[(jj, t)] = y[(jj, t)] + xh[pair_user[j0 + jj] * H + t] + xc[j0 + jj] over pairs * H rows of U floats
+ * (U % 4 == 0; x may be y; xc (n, U) in pair-list order); a user index out of range: zeros and status |= 1. */
+int nrl_caum_eval_attn(const float* qkv_h, const float* qkv_c, const int64_t* cand_offsets, const int64_t* pair_row,
+                       const int64_t* pair_user, const int32_t* slot_tab, int32_t entries, int64_t n_items, int64_t B, int32_t H,
+                       int64_t n, int64_t j0, int64_t j1, int32_t heads, int32_t head_dim, float scale, float* o,
+                       int32_t* status, void* stream);
+int nrl_caum_eval_add(const float* y, const float* xh, const float* xc, const int64_t* pair_user, int64_t n, int64_t j0,
+                      int64_t pairs, int64_t B, int32_t H, int32_t U, float* x, int32_t* status, void* stream);
 
 /* ---- MINER (miner_module.py:258-323,398-406, layers/attention.py:93-166): poly attention, category bias, scores, ------------
  * disagreement loss.  History / candidate rows are FLAT (n_hist / n_cand rows) with int64 offsets (B + 1) and sorted int64

@@ -252,6 +252,11 @@ SIGNATURES = {
     "nrl_caum_score_bwd": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64,
                                      c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p,
                                      c_void_p, c_void_p, c_size_t, c_void_p]),
+    "nrl_caum_eval_attn": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int64, c_int64,
+                                     c_int32, c_int64, c_int64, c_int64, c_int32, c_int32, c_float, c_void_p, c_void_p,
+                                     c_void_p]),
+    "nrl_caum_eval_add": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int64, c_int32,
+                                    c_int32, c_void_p, c_void_p, c_void_p]),
     "nrl_miner_tanh_grad": (c_int32, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p]),
     "nrl_miner_wgrad_workspace_bytes": (c_size_t, [c_int64, c_int32, c_int32]),
     "nrl_miner_wgrad": (c_int32, [c_void_p, c_void_p, c_int64, c_int32, c_int32, c_void_p, c_void_p, c_size_t, c_void_p]),

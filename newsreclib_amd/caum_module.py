@@ -11,7 +11,9 @@ category, a second ``MHSAAddAtt`` over ``title_entities``, ``combine_type="linea
 Differences from the reference: history and candidates are encoded in one news-encoder call (dropout streams:
 ``ops_caum``); the user encoder runs every candidate slot in one pass instead of a Python loop over the slots
 (``user_encoder_caum``), reassociating its first layers (equal within rounding).  A news vector depends on the news alone,
-so ``evaluation.NewsVectorCache`` applies (``score_news_vectors``)."""
+so ``evaluation.NewsVectorCache`` applies (``score_news_vectors``).  ``factored_eval = True`` (class or instance attribute)
+switches the evaluation-mode user encoder to its factored form, whose cost follows the real candidate lists instead of the
+padded (B, max_cand) block; inference only, and the status word of its last call is kept in ``factored_status``."""
 from __future__ import annotations
 
 from typing import Any, Dict, List, Optional
@@ -29,6 +31,11 @@ from .user_encoder_caum import UserEncoder
 
 
 class CAUMModule(AbstractRecommender):
+    # True: in evaluation mode with early fusion, ``score_news_vectors`` scores the real (user, candidate) pairs only
+    # (``UserEncoder.score_ragged``: same dense (B, max_cand) result within rounding, no work on padded slots).  Training mode
+    # and late fusion ignore it.  False (default): the path below, unchanged.
+    factored_eval = False
+
     def __init__(
         self,
         dataset_attributes: List[str],
@@ -146,6 +153,11 @@ class CAUMModule(AbstractRecommender):
         """caum_module.py:333-358 from already-encoded news rows (see ``evaluation.NewsVectorCache``)."""
         B = batch["batch_size"]
         hist_agg = dense_rows(hist_news_vector, batch["batch_hist"], B, batch["max_hist"], batch["hist_offsets"])
+        if self.factored_eval and not self.training and not self.hparams.late_fusion:
+            flat, self.factored_status = self.user_encoder.score_ragged(hist_agg, cand_news_vector, batch["cand_offsets"])
+            dense = flat.new_zeros(B * batch["max_cand"])
+            dense[batch["cand_flat_idx"]] = flat            # padded slots stay exactly 0
+            return dense.view(B, batch["max_cand"])
         cand_agg = dense_rows(cand_news_vector, batch["batch_cand"], B, batch["max_cand"], batch["cand_offsets"])
         if not self.hparams.late_fusion:
             return self.user_encoder(hist_agg, cand_agg, batch["cand_offsets"], seed=seed or 0)

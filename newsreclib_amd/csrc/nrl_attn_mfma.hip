@@ -191,6 +191,191 @@ int attn_fwd_mfma(const float* qkv, float* o, float* lse, const AttnGeom& G, hip
 }
 
 // ---------------------------------------------------------------------------------------------------
+// CAUM factored evaluation (user_encoder_caum.UserEncoder.score_ragged): attn_fwd_mfma_kernel over q|k|v rows that exist only as
+// two addends.  Without dropout linear2 and the in-projection are linear, so the q|k|v row of (user b, slot i, position t) is
+// qkv_h[(b, t)] + qkv_c[cand_offsets[b] + i] -- and qkv_h[(b, t)] alone where user b has fewer than i + 1 candidates (the
+// reference's zero candidate; that user still is a KEY of the slot's attention).  The sum is formed while the K / V tiles are
+// staged into LDS and while the query registers are loaded; the (slot, position, user) rows are never written.
+// Work item = (slot, position t, 64 queries among the slot's REAL pairs, head): the queries come from the slot-major pair list,
+// the keys are all B users.  Item order within a slot-table entry: t, query tile, head -- the items of one (slot, t) are
+// consecutive and, under fa_item, land on one XCD, whose L2 then serves their re-reads of the same B key rows.
+// Every index read from cand_offsets / the pair list / the slot table is range-checked before it addresses anything; a
+// violation ORs 1 into *status (an integer atomic) and the pair's output rows are zeros.
+// ---------------------------------------------------------------------------------------------------
+template <int DH>
+__global__ void __launch_bounds__(256) caum_eval_attn_kernel(const CaumEvalArgs P) {
+  constexpr int DHP = DH + 4, KS = DH / 4, DB = (DH + 15) / 16;
+  __shared__ __attribute__((aligned(16))) float Ks[FA_BK * DHP];
+  __shared__ __attribute__((aligned(16))) float Vs[FA_BK * DHP];
+
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int l15 = lane & 15, g = lane >> 4;
+  const int64_t item = fa_item(P.n_items);
+  if (item < 0) return;
+  // slot-table entry of the item: the last one whose first item is <= item
+  int e = -1;
+  for (int lo = 0, hi = P.entries - 1; lo <= hi;) {
+    const int mid = (lo + hi) >> 1;
+    if ((int64_t)P.slot_tab[4 * mid + 3] <= item) { e = mid; lo = mid + 1; } else { hi = mid - 1; }
+  }
+  if (e < 0) return;
+  const int slot = P.slot_tab[4 * e];
+  const int64_t qb = (int64_t)P.slot_tab[4 * e + 1], qc = (int64_t)P.slot_tab[4 * e + 2];
+  const int64_t local = item - (int64_t)P.slot_tab[4 * e + 3];
+  if (slot < 0 || qc <= 0 || qb < P.j0 || qb + qc > P.j1) {       // (uniform over the workgroup: the table is read alike)
+    if (tid == 0) atomicOr(P.status, 1);
+    return;
+  }
+  const int q_tiles = (int)((qc + FA_BQ - 1) / FA_BQ);
+  const int64_t per_t = (int64_t)q_tiles * P.heads;
+  const int64_t t64 = local / per_t;
+  if (t64 >= P.H) return;                   // past the entry's items (a table that disagrees with n_items): nothing to do
+  const int t = (int)t64;
+  const int qt = (int)((local - t64 * per_t) / P.heads);
+  const int head = (int)((local - t64 * per_t) % P.heads);
+  const int B = P.B, D = P.D;
+  const int64_t pitch = 3 * (int64_t)D;
+  const int64_t jw = qb + (int64_t)qt * FA_BQ + wave * 16;        // first pair of this wave
+  const int64_t jend = qb + qc;
+  const bool wave_has_query = jw < jend;                          // (uniform over the wave)
+
+  // B operand of the score product: (qh + qc)[query l15][d = 4 s + g] * scale; a pair that fails its checks takes q = 0
+  float qreg[KS];
+  bool q_ok;
+  {
+    const bool in = jw + l15 < jend;
+    const int64_t j = in ? jw + l15 : jend - 1;
+    const int64_t p = P.pair_row[j], b = P.pair_user[j];
+    q_ok = p >= 0 && p < P.n && b >= 0 && b < B;
+    if (q_ok) {
+      const int64_t lo = P.cand_offsets[b], hi = P.cand_offsets[b + 1];
+      q_ok = lo >= 0 && lo <= hi && hi <= P.n && p == lo + slot && p < hi;
+    }
+    if (!q_ok && in && g == 0) atomicOr(P.status, 1);
+    const float* hrow = P.qkv_h + ((q_ok ? b : 0) * P.H + t) * pitch + head * DH;
+    const float* crow = P.qkv_c + (q_ok ? p : 0) * pitch + head * DH;
+#pragma unroll
+    for (int s = 0; s < KS; ++s) qreg[s] = q_ok ? (hrow[4 * s + g] + crow[4 * s + g]) * P.scale : 0.f;
+  }
+
+  f32x4 oacc[DB];
+#pragma unroll
+  for (int db = 0; db < DB; ++db) oacc[db] = f32x4{0.f, 0.f, 0.f, 0.f};
+  float m = -INFINITY, l = 0.f;
+
+  for (int k0 = 0; k0 < B; k0 += FA_BK) {
+    __syncthreads();
+    // stage K and V of key users k0 .. k0 + 63 (past B: clamped, masked below): history row + the user's candidate row of this slot
+    constexpr int C4 = DH / 4;
+    for (int idx = tid; idx < FA_BK * C4; idx += 256) {
+      const int row = idx / C4, c4 = idx - row * C4;
+      const int64_t kr = k0 + row < B ? k0 + row : B - 1;
+      const int64_t lo = P.cand_offsets[kr], hi = P.cand_offsets[kr + 1];
+      const bool offs_ok = lo >= 0 && lo <= hi && hi <= P.n;
+      if (!offs_ok && c4 == 0) atomicOr(P.status, 1);
+      const float* src = P.qkv_h + (kr * P.H + t) * pitch + head * DH + 4 * c4;
+      float4 kv = *reinterpret_cast<const float4*>(src + D);
+      float4 vv = *reinterpret_cast<const float4*>(src + 2 * D);
+      if (offs_ok && (int64_t)slot < hi - lo) {
+        const float* csrc = P.qkv_c + (lo + slot) * pitch + head * DH + 4 * c4;
+        const float4 kc = *reinterpret_cast<const float4*>(csrc + D);
+        const float4 vc = *reinterpret_cast<const float4*>(csrc + 2 * D);
+        kv.x += kc.x; kv.y += kc.y; kv.z += kc.z; kv.w += kc.w;
+        vv.x += vc.x; vv.y += vc.y; vv.z += vc.z; vv.w += vc.w;
+      }
+      *reinterpret_cast<float4*>(Ks + row * DHP + 4 * c4) = kv;
+      *reinterpret_cast<float4*>(Vs + row * DHP + 4 * c4) = vv;
+    }
+    __syncthreads();
+
+    // ---- from here on: attn_fwd_mfma_kernel's block step (transposed scores, online softmax, O += P V) with S = B.
+    // A wave without a query (the tile of a slot's last few pairs) only helps staging (3.43 -> 3.28 ms a launch at the README
+    // shape; rotating the strip of queries over the waves so that such tiles load different SIMDs: no measurable gain, not kept).
+    if (!wave_has_query) continue;
+    f32x4 st[4];
+#pragma unroll
+    for (int kb = 0; kb < 4; ++kb) {
+      f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
+      const float* krow = Ks + (16 * kb + l15) * DHP + g;
+#pragma unroll
+      for (int s = 0; s < KS; ++s) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(krow[4 * s], qreg[s], acc, 0, 0, 0);
+      st[kb] = acc;
+    }
+    float mloc = -INFINITY;
+#pragma unroll
+    for (int kb = 0; kb < 4; ++kb)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int key = k0 + 16 * kb + 4 * g + r;
+        const float v = key < B ? st[kb][r] : -INFINITY;
+        st[kb][r] = v;
+        mloc = fmaxf(mloc, v);
+      }
+    mloc = fmaxf(mloc, __shfl_xor(mloc, 16, 64));
+    mloc = fmaxf(mloc, __shfl_xor(mloc, 32, 64));
+    const float m_new = fmaxf(m, mloc);
+    const float alpha = expf(m - m_new);
+    float lsum = 0.f;
+#pragma unroll
+    for (int kb = 0; kb < 4; ++kb)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const float p = expf(st[kb][r] - m_new);
+        st[kb][r] = p;
+        lsum += p;
+      }
+    l = l * alpha + lsum;
+    m = m_new;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const float a_r = __shfl(alpha, 4 * g + r, 64);
+#pragma unroll
+      for (int db = 0; db < DB; ++db) oacc[db][r] *= a_r;
+    }
+#pragma unroll
+    for (int kb = 0; kb < 4; ++kb)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const float* vrow = Vs + (16 * kb + 4 * g + r) * DHP;
+#pragma unroll
+        for (int db = 0; db < DB; ++db) {
+          const int d = 16 * db + l15;
+          const float b = (DH % 16 == 0 || d < DH) ? vrow[d < DH ? d : 0] : 0.f;
+          oacc[db] = __builtin_amdgcn_mfma_f32_16x16x4f32(st[kb][r], b, oacc[db], 0, 0, 0);
+        }
+      }
+  }
+
+  // ---- finish: normalise and store the compact rows ((pair - j0) * H + t); zeros for a pair that failed its checks
+  l += __shfl_xor(l, 16, 64);
+  l += __shfl_xor(l, 32, 64);
+  const float inv = q_ok ? 1.0f / l : 0.f;
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    const float inv_r = __shfl(inv, 4 * g + r, 64);
+    const int64_t j = jw + 4 * g + r;
+    if (j < jend) {
+      float* orow = P.o + ((j - P.j0) * P.H + t) * (int64_t)D + head * DH;
+#pragma unroll
+      for (int db = 0; db < DB; ++db) {
+        const int d = 16 * db + l15;
+        if (DH % 16 == 0 || d < DH) orow[d] = oacc[db][r] * inv_r;
+      }
+    }
+  }
+}
+
+int caum_eval_attn(const CaumEvalArgs& a, hipStream_t stream) {
+  if (a.n_items == 0) return NRL_OK;
+  NRL_REQUIRE(a.n_items < (1LL << 31), "caum_eval_attn: grid too large");
+  NRL_FA_DISPATCH(a.dh, {
+    hipLaunchKernelGGL((caum_eval_attn_kernel<DH>), dim3(fa_grid(a.n_items)), dim3(256), 0, stream, a);
+  });
+  NRL_LAUNCH_CHECK();
+  return NRL_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------
 // Backward, two kernels (no atomics): (B) one workgroup per 64 QUERIES -> dQ, streaming keys; (A) one workgroup
 // per 64 KEYS -> dK, dV, streaming queries.  Both recompute the scores from the saved log-sum-exp:
 //   P = exp(S - lse[q]),  dP = dO V^T,  dS = P o (dP - delta[q]),  delta[q] = <dO[q], O[q]>

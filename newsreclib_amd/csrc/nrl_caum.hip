@@ -331,6 +331,31 @@ __global__ void caum_colsum_final_kernel(const float* __restrict__ part, int64_t
   }
 }
 
+// ---- factored evaluation: x[(jj, t)] = y[(jj, t)] + Xh[(user of pair j0 + jj, t)] + Xc[j0 + jj] over the compact rows ------
+// (y may be x: every element is read and written by the same thread.)  A user index out of range: zeros, status |= 1.
+__global__ void caum_eval_add_kernel(const float* y, const float* __restrict__ xh, const float* __restrict__ xc,
+                                     const int64_t* __restrict__ pair_user, int64_t j0, int64_t pairs, int B, int H, int U4,
+                                     float* x, int32_t* __restrict__ status) {
+  const int64_t n = pairs * H * U4;
+  for (int64_t k = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; k < n; k += (int64_t)gridDim.x * blockDim.x) {
+    const int u = (int)(k % U4);
+    const int64_t r = k / U4;
+    const int t = (int)(r % H);
+    const int64_t jj = r / H;
+    const int64_t b = pair_user[j0 + jj];
+    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (b >= 0 && b < B) {
+      const float4 a = reinterpret_cast<const float4*>(y)[k];
+      const float4 h = reinterpret_cast<const float4*>(xh)[(b * H + t) * U4 + u];
+      const float4 c = reinterpret_cast<const float4*>(xc)[(j0 + jj) * U4 + u];
+      v = make_float4(a.x + h.x + c.x, a.y + h.y + c.y, a.z + h.z + c.z, a.w + h.w + c.w);
+    } else if (u == 0 && t == 0) {
+      atomicOr(status, 1);
+    }
+    reinterpret_cast<float4*>(x)[k] = v;
+  }
+}
+
 static AttnGeom caum_geom(int64_t outer, int64_t seq, int heads, int dh, int seq_first, float scale) {
   AttnGeom g;
   const int D = heads * dh;
@@ -529,6 +554,39 @@ int nrl_caum_score_bwd(const float* d_scores, const float* z2, const float* w3, 
   hipLaunchKernelGGL(caum_colsum_partial_kernel, dim3((unsigned)chunks), dim3(CAUM_THREADS), 0, st, z2, d_logit, R, N2, part);
   NRL_LAUNCH_CHECK();
   hipLaunchKernelGGL(caum_colsum_final_kernel, dim3(1), dim3(CAUM_THREADS), 0, st, part, chunks, N2, d_w3, d_b3);
+  NRL_LAUNCH_CHECK();
+  return NRL_OK;
+}
+
+int nrl_caum_eval_attn(const float* qkv_h, const float* qkv_c, const int64_t* cand_offsets, const int64_t* pair_row,
+                       const int64_t* pair_user, const int32_t* slot_tab, int32_t entries, int64_t n_items, int64_t B, int32_t H,
+                       int64_t n, int64_t j0, int64_t j1, int32_t heads, int32_t head_dim, float scale, float* o,
+                       int32_t* status, void* stream) {
+  NRL_REQUIRE(qkv_h && qkv_c && cand_offsets && pair_row && pair_user && slot_tab && o && status,
+              "caum_eval_attn: null pointer");
+  NRL_REQUIRE((((uintptr_t)qkv_h | (uintptr_t)qkv_c | (uintptr_t)o) & 15) == 0, "caum_eval_attn: rows must be 16-byte aligned");
+  NRL_REQUIRE(B > 0 && B < (1LL << 31) && H > 0 && heads > 0 && n > 0 && entries > 0 && n_items >= 0 && scale > 0.f,
+              "caum_eval_attn: bad dimensions");
+  NRL_REQUIRE(0 <= j0 && j0 < j1 && j1 <= n, "caum_eval_attn: the pair range must lie inside the pair list");
+  NRL_REQUIRE(attn_head_dim_supported(head_dim), "caum_eval_attn: head dim %d unsupported (16, 20, 32, 48, 64)", head_dim);
+  CaumEvalArgs a;
+  a.qkv_h = qkv_h; a.qkv_c = qkv_c; a.cand_offsets = cand_offsets; a.pair_row = pair_row; a.pair_user = pair_user;
+  a.slot_tab = slot_tab; a.o = o; a.status = status;
+  a.n = n; a.j0 = j0; a.j1 = j1; a.n_items = n_items;
+  a.B = (int)B; a.H = H; a.heads = heads; a.D = heads * head_dim; a.dh = head_dim; a.entries = entries;
+  a.scale = scale;
+  return caum_eval_attn(a, (hipStream_t)stream);
+}
+
+int nrl_caum_eval_add(const float* y, const float* xh, const float* xc, const int64_t* pair_user, int64_t n, int64_t j0,
+                      int64_t pairs, int64_t B, int32_t H, int32_t U, float* x, int32_t* status, void* stream) {
+  NRL_REQUIRE(y && xh && xc && pair_user && x && status, "caum_eval_add: null pointer");
+  NRL_REQUIRE(j0 >= 0 && pairs > 0 && pairs <= n - j0 && B > 0 && B < (1LL << 31) && H > 0 && U > 0 && U % 4 == 0,
+              "caum_eval_add: bad dimensions (U a multiple of 4)");
+  NRL_REQUIRE((((uintptr_t)y | (uintptr_t)xh | (uintptr_t)xc | (uintptr_t)x) & 15) == 0,
+              "caum_eval_add: rows must be 16-byte aligned");
+  hipLaunchKernelGGL(caum_eval_add_kernel, dim3(grid_for(pairs * H * (U / 4))), dim3(CAUM_THREADS), 0, (hipStream_t)stream, y,
+                     xh, xc, pair_user, j0, pairs, (int)B, H, U / 4, x, status);
   NRL_LAUNCH_CHECK();
   return NRL_OK;
 }

@@ -40,6 +40,23 @@ int attn_fwd_x3_proj(const float* x, int64_t x_outer, int64_t x_seq, const uint1
 int attn_bwd(const float* qkv, const float* o, const float* d_o, const float* lse, float* dqkv,
              const AttnGeom& G, hipStream_t stream);
 
+// CAUM factored evaluation (nrl_attn_mfma.hip): the across-users attention of every REAL (user, candidate slot) pair with q|k|v
+// rows that are sums of a history-side row qkv_h[(b, t)] and a candidate-side row qkv_c[cand_offsets[b] + slot] (the history
+// row alone for a key user without that slot).  Queries are the entries [j0, j1) of the slot-major pair list (pair_row = the
+// flat candidate row, pair_user = its user); slot_tab (entries, 4) = {slot, first pair, pair count, first work item} of every
+// slot the range touches.  o ((j1 - j0) * H, D) compact, zeros for a pair whose indices fail their range checks (status |= 1).
+struct CaumEvalArgs {
+  const float *qkv_h, *qkv_c;
+  const int64_t *cand_offsets, *pair_row, *pair_user;
+  const int32_t* slot_tab;
+  float* o;
+  int32_t* status;
+  int64_t n, j0, j1, n_items;
+  int B, H, heads, D, dh, entries;
+  float scale;
+};
+int caum_eval_attn(const CaumEvalArgs& a, hipStream_t stream);
+
 // additive attention tail (attention.py:37-40): a = t . q_a; w = softmax_S(a); out = sum w y.
 // rows of group g are [g*S, (g+1)*S).  w (M) is saved for backward.
 int pool_fwd(const float* t, const float* q_a, const float* y, int64_t groups, int S, int Q, int D,

@@ -265,6 +265,85 @@ def padded_attention_params(mha, heads: int):
     return w_in_p, b_in_p, w_o_p, dhp, scale
 
 
+EVAL_QUERY_TILE = 64                      # queries per work item of ``nrl_caum_eval_attn``
+STATUS_BAD_INDEX = 1                      # set by the kernels: an offset / pair-list entry failed its range check
+STATUS_BAD_OFFSETS = 2                    # set by ``score_ragged``: the candidate sizes do not add up to the candidate rows
+
+
+def plan_pair_chunks(slot_counts, H: int, row_budget: int):
+    """The factored evaluation's passes over the slot-major pair list (slot 0's pairs, then slot 1's ...; ``slot_counts[i]`` =
+    users with more than i candidates): -> [(j0, j1)] contiguous, disjoint, covering every pair once, each with
+    ``(j1 - j0) * H <= row_budget`` -- except that a chunk always holds at least one pair.  A chunk takes whole slots while
+    they fit and ends inside a slot only where that slot alone exceeds what is left of an empty chunk."""
+    per = max(1, int(row_budget) // max(1, int(H)))
+    chunks, j0, j = [], 0, 0
+    for cnt in (int(c) for c in slot_counts):
+        while cnt > 0:
+            room = per - (j - j0)
+            if cnt <= room:
+                j, cnt = j + cnt, 0
+            elif j > j0:                  # the slot does not fit behind what the chunk holds: close the chunk
+                chunks.append((j0, j))
+                j0 = j
+            else:                         # an empty chunk and a slot larger than the budget: split the slot
+                chunks.append((j0, j0 + per))
+                j0 = j = j0 + per
+                cnt -= per
+    if j > j0:
+        chunks.append((j0, j))
+    return chunks
+
+
+def pair_chunk_table(slot_counts, j0: int, j1: int, H: int, heads: int):
+    """-> (rows [slot, first pair, pair count, first work item], work items) of the pair range [j0, j1): what
+    ``nrl_caum_eval_attn`` takes as ``slot_tab`` / ``n_items``."""
+    rows, items, start = [], 0, 0
+    for slot, cnt in enumerate(int(c) for c in slot_counts):
+        lo, hi = max(start, j0), min(start + cnt, j1)
+        if lo < hi:
+            rows.append([slot, lo, hi - lo, items])
+            items += -(-(hi - lo) // EVAL_QUERY_TILE) * H * heads
+        start += cnt
+    return rows, items
+
+
+def caum_eval_attn(qkv_h, qkv_c, cand_offsets, pair_row, pair_user, slot_tab, n_items: int, B: int, H: int, j0: int, j1: int,
+                   heads: int, dh: int, scale: float, status):
+    """``nrl_caum_eval_attn``: qkv_h (B * H, 3 * heads * dh), qkv_c (n, 3 * heads * dh) in flat candidate order -> the attention
+    output ((j1 - j0) * H, heads * dh) of the pairs [j0, j1) of the slot-major pair list (``pair_row`` / ``pair_user`` int64 (n),
+    ``slot_tab`` int32 (entries, 4): ``pair_chunk_table``).  ``status`` int32 (1): bit 0 is ORed in when an index fails its
+    range check on the device (that pair's rows are zeros)."""
+    lib = _lib.load()
+    qkv_h, qkv_c = _chk(qkv_h, torch.float32, "qkv_h"), _chk(qkv_c, torch.float32, "qkv_c")
+    offs, pair_row = _chk(cand_offsets, torch.int64, "cand_offsets"), _chk(pair_row, torch.int64, "pair_row")
+    pair_user, slot_tab = _chk(pair_user, torch.int64, "pair_user"), _chk(slot_tab, torch.int32, "slot_tab")
+    status = _chk(status, torch.int32, "status")
+    n, W = qkv_c.shape[0], 3 * heads * dh
+    if qkv_h.shape != (B * H, W) or qkv_c.shape != (n, W) or offs.numel() != B + 1 or pair_row.numel() != n or \
+            pair_user.numel() != n or slot_tab.dim() != 2 or slot_tab.shape[1] != 4 or status.numel() != 1 or \
+            not status.is_contiguous():
+        raise ValueError("newsreclib_amd: inconsistent CAUM factored-attention shapes")
+    o = torch.empty(((j1 - j0) * H, heads * dh), dtype=torch.float32, device=qkv_h.device)
+    _check(lib.nrl_caum_eval_attn(qkv_h.data_ptr(), qkv_c.data_ptr(), offs.data_ptr(), pair_row.data_ptr(),
+                                  pair_user.data_ptr(), slot_tab.data_ptr(), slot_tab.shape[0], int(n_items), B, H, n, int(j0),
+                                  int(j1), heads, dh, float(scale), o.data_ptr(), status.data_ptr(), _stream()),
+           "nrl_caum_eval_attn")
+    return o
+
+
+def caum_eval_add_(y, xh, xc, pair_user, j0: int, B: int, H: int, status):
+    """In place: y ((pairs) * H, U) += xh[(user of pair j0 + jj) * H + t] + xc[j0 + jj] (``nrl_caum_eval_add``)."""
+    lib = _lib.load()
+    U = y.shape[1]
+    pairs = y.shape[0] // H
+    if not y.is_contiguous() or y.shape[0] != pairs * H or xh.shape != (B * H, U) or xc.shape != (pair_user.numel(), U):
+        raise ValueError("newsreclib_amd: inconsistent CAUM factored-add shapes")
+    xh, xc = _chk(xh, torch.float32, "xh"), _chk(xc, torch.float32, "xc")
+    _check(lib.nrl_caum_eval_add(y.data_ptr(), xh.data_ptr(), xc.data_ptr(), pair_user.data_ptr(), pair_user.numel(), int(j0),
+                                 pairs, B, H, U, y.data_ptr(), status.data_ptr(), _stream()), "nrl_caum_eval_add")
+    return y
+
+
 def padded_attention(x, mha, heads: int, outer: int, seq: int, seq_first: bool):
     """``mha(x, x, x)[0]`` on rows x (outer * seq, D) laid out as ``AttnFn`` describes, at any head dim the padding reaches:
     in-projection and out-projection on the GEMM engines (``LinearFn``), the attention on ``nrl_caum_attn_*``."""
