@@ -1,34 +1,39 @@
-// Full-catalogue top-k recommendation: for B user vectors and a (V, D) news-vector table, the k table rows of highest dot product
-// per user, leaving out a ragged per-user exclusion list (the history) and the rows an `eligible` mask removes.  The (B, V) score
-// matrix is never written: every workgroup keeps k entries per user while its slice of the table streams past once.
+// Full-catalogue ranking: for B users and a table of V news, either the k rows each user scores highest (nrl_topk_*) or where a
+// ragged per-user list of held-out rows lands among all of them (nrl_catalogue_*_ranks), leaving out a ragged per-user exclusion
+// list (the history) and the rows an `eligible` mask removes.  The (B, V) score matrix is never written: every workgroup walks its
+// slice of the table once, tile by tile, and keeps per user only what its consumer needs.
 //
-//   tk_scores_kernel   256 threads, one workgroup per (tile of TK_BU = 64 users, slice of V).  Per table tile of TK_BV = 128 rows:
-//       * scores = exact-fp32 MFMA (v_mfma_f32_16x16x4_f32) over LDS tiles of both operands (k-major, double-buffered, register-
-//         staged global loads as nrl_gemm.h).  Every score is ONE accumulator chain over k = 0, 4, 8, ... from +0, zero-filled up to
-//         the next multiple of TK_BK: its bits are a function of the two rows and D alone, whatever B, V, k, the slicing or the
-//         GEMM engine setting (which this unit does not read);
-//       * the 64 x 128 scores go to LDS; each wave scans its 16 users: a lane owns two columns, builds the 64-bit entry
-//         (order-preserving score key << 32 | ~row: larger = better, so equal scores rank by ascending row, and 0 = empty slot) of
-//         the columns that are inside V and eligible, and compares it with the user's current k-th entry.  Nearly always no lane
-//         survives and the user costs a few instructions;
-//       * when lanes survive, the user's exclusion list (its first TK_XCAP entries cached in LDS, longer lists read from global
-//         memory) clears the bits of excluded rows that fall inside this tile, the user's list is loaded into registers (entry p in
-//         lane p & 63) and the survivors are inserted one by one with ballots and lane shifts.  The top k of a set under a strict
-//         total order does not depend on the insertion order, so the result is a pure function of the score bits and the rows.
-//   tki_scores_kernel  the same stages over the K interest rows of a user, with an aggregation between the tile and the scan.
-//   tke_*_kernel       the z-scored ensemble of up to three tables (MANNeR): a statistics pass, then the same stages over a second
-//       score tile that collects the weighted z-scores.
-//   tkr_scores_kernel  DKN's factored DNN predictor: the tile is b2 + sum_j w2[j] relu(proj[v, j] + q[u, j]) in plain fp32 vector
-//       code instead of a product; the other stages unchanged.
-//   tkp_scores_kernel  NPA's personalized pooling: per token of the cached feature maps a two-operand tile product kept in
-//       registers and folded into an online softmax per (user, row); the other stages unchanged.
-//   tkc_*_kernel       the rank of held-out rows: the same walk with a consumer that counts instead of selects;
-//   tkic_* / tkrc_* / tkpc_* / tkec_*  that consumer under the tile producers of tki_ / tkr_ / tkp_ / tke_scores_kernel.
+// ONE WALK (tk_walk), five tile producers, two consumers; nine of the ten walk kernels are its instantiations and nothing else
+// (tkr_scores_kernel keeps its own text, for its speed: see there):
+//                      plain dot product   MINER interests      MANNeR ensemble     DKN factored DNN    NPA pooling
+//   producer           TkDot               TkiProducer<GATE>    TkeProducer         TkrProducer         TkpProducer
+//   TkSelect (top-k)   tk_scores_kernel    tki_scores_kernel    tke_scores_kernel   tkr_scores_kernel   tkp_scores_kernel
+//   TkCount  (rank)    tkc_count_kernel    tkic_count_kernel    tkec_count_kernel   tkrc_count_kernel   tkpc_count_kernel
+// 256 threads, one workgroup per (slice of V, tile of users).  Per table tile of TK_BV = 128 rows:
+//   * the PRODUCER leaves the tile's scores in LDS.  TkDot: exact-fp32 MFMA (v_mfma_f32_16x16x4_f32) over LDS tiles of both
+//     operands (k-major, double-buffered, register-staged global loads as nrl_gemm.h); every score is ONE accumulator chain over
+//     k = 0, 4, 8, ... from +0, zero-filled up to the next multiple of TK_BK: its bits are a function of the two rows and D alone,
+//     whatever B, V, k, the slicing or the GEMM engine setting (which this unit does not read).  The others: that product over the
+//     K interest rows of a user with an aggregation behind it; over up to three tables into a tile of weighted z-scores (after a
+//     statistics pass, tke_stats_kernel / tke_finish_kernel); b2 + sum_j w2[j] relu(proj[v, j] + q[u, j]) in plain fp32 vector
+//     code; per token a two-operand product folded into an online softmax in registers.  Each section below says how;
+//   * the CONSUMER sees one user's 128 scores at a time, by the wave that serves the user: a lane owns two columns and builds the
+//     64-bit entry (order-preserving score key << 32 | ~row: larger = better, so equal scores rank by ascending row, and 0 = empty
+//     slot) of the columns that are inside V and eligible.  TkSelect compares it with the user's current k-th entry; nearly always
+//     no lane survives and the user costs a few instructions.  When lanes survive, the user's exclusion list (its first TK_XCAP
+//     entries cached in LDS, longer lists read from global memory) clears the bits of excluded rows inside this tile, the user's
+//     list is loaded into registers (entry p in lane p & 63) and the survivors are inserted one by one with ballots and lane
+//     shifts.  The top k of a set under a strict total order does not depend on the insertion order, so the result is a pure
+//     function of the score bits and the rows.  TkCount counts the entries above each target's entry, and the population.
+// A producer does not know its consumer, so a score has the same bits in the list and in the rank; what a rank entry computes
+// outside the walk -- the targets' own scores, one *_target_kernel per scorer -- runs the same chain on the same operands.
 //   tk_merge_kernel    one wave per user: validates the user's offsets and exclusion indices (status flags), merges the `slices`
-//       partial lists with the same insertion and writes (row, score) or (-1, -inf).
-// The stages (exclusion cache, eligibility, tile product, per-user selection, flush) are written once, as inlined device functions
-// of pointers and counts; a scores kernel owns its LDS layout and its wave-to-user mapping and calls them.
-// No float atomics, no allocation, no host read-back; the workspace holds the partial lists, O(B * slices * k).
+//       partial lists with the same insertion and writes (row, score) or (-1, -inf);
+//   tkc_finish_kernel  one wave per user: the same flags, the sum of the slices' counts, each target's validity, the outputs.
+// The stages (exclusion cache, eligibility, tile product, per-user selection or count, flush) are inlined device functions of
+// pointers and counts; the producers and consumers are structs of pointers into LDS that call them.  On the host each scorer's
+// own checks and fields are one function each, shared by its two entries.
+// No float atomics, no allocation, no host read-back; the workspace holds the partial lists, O(B * slices * k), or the counts.
 #include <math.h>
 
 #include "nrl_common.h"
@@ -48,9 +53,9 @@ constexpr int TK_XCAP = 64;                    // exclusion entries per user cac
 constexpr int TK_USERS_PER_WAVE = TK_BU / 4;
 constexpr int TK_TARGET_BLOCKS = 512;          // two resident workgroups on each of the 256 CUs
 
-// dynamic LDS of a scores kernel: `tiles` score tiles (2 with a gate), and per user of the workgroup a list of k entries and the
-// exclusion cache (start, length, TK_XCAP rows); then the eligibility bytes.  64 users, one tile: 50 KB + 512 B per k, so two
-// workgroups per CU up to k = 60 and more than 64 KB from k = 29 on.
+// dynamic LDS of a scores kernel: `tiles` score tiles (2 with a gate), and what TkSelect carves behind the producer's share: per
+// user of the workgroup a list of k entries and the exclusion cache (start, TK_XCAP rows, length); then the eligibility bytes.
+// 64 users, one tile: 50 KB + 512 B per k, so two workgroups per CU up to k = 60 and more than 64 KB from k = 29 on.
 constexpr size_t tk_lds_bytes(int tiles, int users, int k) {
   return (size_t)tiles * TK_BU * TK_SCLD * 4 + (size_t)users * k * 8 + (size_t)users * 8 + (size_t)users * TK_XCAP * 4 + (size_t)users * 4 +
          TK_BV;
@@ -75,6 +80,9 @@ struct TkArgs {
   float* out_score;
   int32_t* status;
 };
+// the arguments of a kernel that serves one scorer: a consumer's base (TkArgs, or TkcArgs for the rank) and the scorer's own fields
+template <class Base, class Fields>
+struct TkWith : Base, Fields {};
 
 __device__ __forceinline__ float tk_unkey(uint32_t key) {      // the score of a score_key
   return __uint_as_float((key & 0x80000000u) ? (key ^ 0x80000000u) : ~key);
@@ -360,52 +368,133 @@ __device__ __forceinline__ void tk_flush_user(const unsigned long long* L, unsig
   for (int p = lane; p < k; p += 64) P[p] = L[p];
 }
 
-__global__ __launch_bounds__(TK_THREADS) void tk_scores_kernel(TkArgs A) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char tk_smem[];
-  float* const sc = reinterpret_cast<float*>(tk_smem);                       // [TK_BU][TK_SCLD]
-  int32_t* const xl = reinterpret_cast<int32_t*>(sc + TK_BU * TK_SCLD);      // [TK_BU][TK_XCAP]
-  int64_t* const xs = reinterpret_cast<int64_t*>(xl + TK_BU * TK_XCAP);      // [TK_BU]
-  int32_t* const xn = reinterpret_cast<int32_t*>(xs + TK_BU);                // [TK_BU]
-  uint8_t* const el = reinterpret_cast<uint8_t*>(xn + TK_BU);                // [TK_BV]
-  unsigned long long* const lists = reinterpret_cast<unsigned long long*>(el + TK_BV);      // [TK_BU][k]
+// ---- the walk: one skeleton for every (tile producer, consumer) pair ---------------------------------------------------------------
+// A workgroup serves one (slice of V, tile of users) and walks the slice's table tiles once.  What differs between the walk
+// kernels is chosen at compile time by two types and never branched on at run time (tkr_scores_kernel alone is written out):
+//   the PRODUCER (one per scorer) owns the score tile(s) at the front of the dynamic LDS and whatever else of the scorer's lives in
+//     LDS, contiguously; `rest` is the first byte after that.  slots(): the users of a tile.  stage(A, u0, nu): before the walk, its
+//     operands (per-thread row pointers, or rows staged in LDS: the consumer's prologue publishes them).  tile(A, v0, nu): the
+//     scores of the tile's users for table rows v0 ... v0 + 127, workgroup synchronised at the end.  row(ul): user ul's 128 scores.
+//     skip(ul): the user takes no part.  first / end / STEP: which users of the tile a wave serves (TkBlocked or TkStrided);
+//   the CONSUMER (TkSelect, TkCount) carves its arrays from `rest` on, 8-byte members first so that any slots() keeps every member
+//     aligned.  `el`: the eligibility bytes.  prologue(A, u0, nu, slots): by the workgroup, ends with its arrays published except
+//     for what only the first tile's barriers need to publish.  user(row, ul, ...): one user against one table tile, by the wave
+//     that serves the user.  flush(A, ul, u, sl, lane): the user's result for slice sl, by the same wave.
+// Both consumers therefore see the same score bits: there is one producer per scorer, and it does not know who consumes.
 
+// the slice of table tiles of a workgroup: first row and number of tiles
+__device__ __forceinline__ void tk_slice(const TkArgs& A, int sl, int& v_begin, int& nvt) {
+  v_begin = sl * A.tiles_per_slice * TK_BV;                                  // < V < 2^31
+  const int64_t v_stop = (int64_t)v_begin + (int64_t)A.tiles_per_slice * TK_BV;
+  const int v_end = v_stop < A.V ? (int)v_stop : A.V;
+  nvt = (v_end - v_begin + TK_BV - 1) / TK_BV;
+}
+
+// wave w serves users 16 w ... 16 w + 15 of the tile
+struct TkBlocked {
+  static constexpr int STEP = 1;
+  __device__ __forceinline__ static int first(int wave) { return wave * TK_USERS_PER_WAVE; }
+  __device__ __forceinline__ static int end(int wave, int nu) {
+    return first(wave) + TK_USERS_PER_WAVE < nu ? first(wave) + TK_USERS_PER_WAVE : nu;
+  }
+};
+// wave w serves users w, w + 4, ... of the tile
+struct TkStrided {
+  static constexpr int STEP = 4;
+  __device__ __forceinline__ static int first(int wave) { return wave; }
+  __device__ __forceinline__ static int end(int, int nu) { return nu; }
+};
+
+template <class Args, class Producer, class Consumer>
+__device__ __forceinline__ void tk_walk(const Args& A, Producer& P, Consumer& C) {
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int k = A.k, V = A.V;
+  const int slots = P.slots();
   // the slice is the fast index: the workgroups resident together share their table slice across the user tiles
   const int sl = (int)(blockIdx.x % (unsigned)A.slices);
-  const int64_t u0 = (int64_t)(blockIdx.x / (unsigned)A.slices) * TK_BU;
-  const int nu = A.B - u0 < TK_BU ? (int)(A.B - u0) : TK_BU;                 // the tile's users (>= 1)
-  const int v_begin = sl * A.tiles_per_slice * TK_BV;                        // < V < 2^31
-  const int64_t v_stop = (int64_t)v_begin + (int64_t)A.tiles_per_slice * TK_BV;
-  const int v_end = v_stop < V ? (int)v_stop : V;
-  const int nvt = (v_end - v_begin + TK_BV - 1) / TK_BV;
+  const int64_t u0 = (int64_t)(blockIdx.x / (unsigned)A.slices) * slots;     // first user of the tile
+  const int nu = A.B - u0 < slots ? (int)(A.B - u0) : slots;                 // its users (>= 1)
+  int v_begin, nvt;
+  tk_slice(A, sl, v_begin, nvt);
 
-  for (int i = tid; i < TK_BU * k; i += TK_THREADS) lists[i] = 0ull;
-  tk_cache_exclusions(A, u0, nu, TK_BU, xs, xn, xl);
-
-  // wave w owns users 16 w ... 16 w + 15 of the tile and their lists
-  const int ul_begin = wave * TK_USERS_PER_WAVE, ul_end = ul_begin + TK_USERS_PER_WAVE < nu ? ul_begin + TK_USERS_PER_WAVE : nu;
-  // staging: tile row r is user u0 + r, zero past the last user
-  const int srow = tid >> 2;
-  const bool ua_ok = srow < nu;
-  const float* const pa[1] = {A.user + (ua_ok ? u0 + srow : A.B - 1) * A.D};
+  P.stage(A, u0, nu);
+  C.prologue(A, u0, nu, slots);                       // (its barriers also publish what the producer staged in LDS)
+  const int ul_begin = Producer::first(wave), ul_end = Producer::end(wave, nu);
   bool nan = false;
 
   for (int vt = 0; vt < nvt; ++vt) {
     const int v0 = v_begin + vt * TK_BV;
-    tk_fill_eligible(A.eligible, v0, V, el);
-    tk_tile_product<1>(pa, ua_ok, A.table, v0, V, A.D, sc);
+    tk_fill_eligible(A.eligible, v0, A.V, C.el);
+    P.tile(A, v0, nu);
 
-    const bool e_0 = el[lane] != 0, e_1 = el[64 + lane] != 0;
-    for (int ul = ul_begin; ul < ul_end; ++ul)
-      tk_select_user(sc + ul * TK_SCLD, lists + ul * k, xn + ul, xs + ul, xl + ul * TK_XCAP, A.excl_idx, v0, e_0, e_1, k, lane, nan);
-    __syncthreads();                                  // the score tile and `el` are free for the next tile's operands
+    const bool e_0 = C.el[lane] != 0, e_1 = C.el[64 + lane] != 0;
+    for (int ul = ul_begin; ul < ul_end; ul += Producer::STEP) {
+      if (P.skip(ul)) continue;
+      C.user(P.row(ul), ul, A.excl_idx, v0, e_0, e_1, lane, nan);
+    }
+    __syncthreads();                                  // the score tiles and `el` are free for the next tile's operands
   }
 
   if (nan && lane == 0) atomicOr(A.status, NRL_TOPK_E_NAN);
   wave_lds_sync();
-  for (int ul = ul_begin; ul < ul_end; ++ul) tk_flush_user(lists + ul * k, A.partial + ((u0 + ul) * A.slices + sl) * k, k, lane);
+  for (int ul = ul_begin; ul < ul_end; ul += Producer::STEP) C.flush(A, ul, u0 + ul, sl, lane);
+}
+
+constexpr size_t TK_TILE_BYTES = (size_t)TK_BU * TK_SCLD * 4;
+static_assert(TK_TILE_BYTES % 16 == 0, "what follows the score tiles is 16-byte aligned");
+
+// The selecting consumer: per user of the tile a list of k entries, kept while the slice streams past, and the exclusion cache.
+struct TkSelect {
+  unsigned long long* lists;                   // [slots][k]
+  int64_t* xs;                                 // [slots] exclusion cache: start
+  int32_t* xl;                                 // [slots][TK_XCAP] exclusion cache: first rows
+  int32_t* xn;                                 // [slots] exclusion cache: length
+  uint8_t* el;                                 // [TK_BV]
+  int k;
+  __device__ __forceinline__ TkSelect(unsigned char* p, int slots, int k_) : k(k_) {
+    lists = reinterpret_cast<unsigned long long*>(p);
+    xs = reinterpret_cast<int64_t*>(lists + slots * k);
+    xl = reinterpret_cast<int32_t*>(xs + slots);
+    xn = xl + slots * TK_XCAP;
+    el = reinterpret_cast<uint8_t*>(xn + slots);
+  }
+  __device__ __forceinline__ void prologue(const TkArgs& A, int64_t u0, int nu, int slots) const {
+    for (int i = threadIdx.x; i < slots * k; i += TK_THREADS) lists[i] = 0ull;
+    tk_cache_exclusions(A, u0, nu, slots, xs, xn, xl);                       // (its barrier also publishes `lists`)
+  }
+  __device__ __forceinline__ void user(const float* row, int ul, const int64_t* excl_idx, int v0, bool e_0, bool e_1, int lane,
+                                       bool& nan) const {
+    tk_select_user(row, lists + ul * k, xn + ul, xs + ul, xl + ul * TK_XCAP, excl_idx, v0, e_0, e_1, k, lane, nan);
+  }
+  __device__ __forceinline__ void flush(const TkArgs& A, int ul, int64_t u, int sl, int lane) const {
+    tk_flush_user(lists + ul * k, A.partial + (u * A.slices + sl) * k, k, lane);
+  }
+};
+static_assert(tk_lds_bytes(0, 1, 1) == 8 + 8 + TK_XCAP * 4 + 4 + TK_BV, "tk_lds_bytes counts the members of TkSelect");
+
+// The producer of the plain dot product: tile row r is user u0 + r, zero past the last user.
+struct TkDot : TkBlocked {
+  float* sc;                                   // [TK_BU][TK_SCLD]; until the scores exist, the operand tiles
+  unsigned char* rest;
+  const float* pa[1];
+  bool ua_ok;
+  __device__ __forceinline__ explicit TkDot(unsigned char* p) : sc(reinterpret_cast<float*>(p)), rest(p + TK_TILE_BYTES) {}
+  __device__ __forceinline__ int slots() const { return TK_BU; }
+  __device__ __forceinline__ void stage(const TkArgs& A, int64_t u0, int nu) {
+    const int srow = threadIdx.x >> 2;
+    ua_ok = srow < nu;
+    pa[0] = A.user + (ua_ok ? u0 + srow : A.B - 1) * A.D;
+  }
+  __device__ __forceinline__ void tile(const TkArgs& A, int v0, int) const { tk_tile_product<1>(pa, ua_ok, A.table, v0, A.V, A.D, sc); }
+  __device__ __forceinline__ const float* row(int ul) const { return sc + ul * TK_SCLD; }
+  __device__ __forceinline__ bool skip(int) const { return false; }
+};
+
+__global__ __launch_bounds__(TK_THREADS) void tk_scores_kernel(TkArgs A) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char tk_smem[];
+  TkDot P(tk_smem);
+  TkSelect C(P.rest, TK_BU, A.k);
+  tk_walk(A, P, C);
 }
 
 // one wave per user: status flags, merge of the user's partial lists, output
@@ -448,7 +537,7 @@ __global__ __launch_bounds__(64) void tk_merge_kernel(TkArgs A) {
 // is in LDS the K rows of every user are reduced per column, in ascending j, into the user's first row: the one stage that is
 // this kernel's own.  The scan, the exclusion and the insertion then run over Ut users, and tk_merge_kernel finishes.
 // GATE (mode 2) runs the gate rows as a second row operand against the SAME staged table tile into a second score tile.
-struct TkiArgs : TkArgs {                      // `user` is the interests; B counts users
+struct TkiFields {                             // beside them `user` is the interests and B counts users
   const float* gate;
   int32_t K, Ut, mode;
 };
@@ -497,56 +586,39 @@ __device__ __forceinline__ void tki_tile(const float* const (&pa)[GATE ? 2 : 1],
   __syncthreads();
 }
 
+// The producer of the multi-interest kernels: tile row r is interest row u0 * K + r of the (B * K, D) matrix while r < nu * K, zero
+// from there on; a user's scores are in the first of its K rows.
 template <bool GATE>
-__global__ __launch_bounds__(TK_THREADS) void tki_scores_kernel(TkiArgs A) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char tk_smem[];
-  constexpr int NA = GATE ? 2 : 1;
-  const int K = A.K, Ut = A.Ut;
-  float* const sc = reinterpret_cast<float*>(tk_smem);                       // [TK_BU][TK_SCLD] the s_j; with a gate the l_j follow
-  unsigned long long* const lists = reinterpret_cast<unsigned long long*>(sc + NA * TK_BU * TK_SCLD);      // [Ut][k]
-  int64_t* const xs = reinterpret_cast<int64_t*>(lists + Ut * A.k);          // [Ut]
-  int32_t* const xl = reinterpret_cast<int32_t*>(xs + Ut);                   // [Ut][TK_XCAP]
-  int32_t* const xn = xl + Ut * TK_XCAP;                                     // [Ut]
-  uint8_t* const el = reinterpret_cast<uint8_t*>(xn + Ut);                   // [TK_BV]
-
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int k = A.k, V = A.V;
-  const int sl = (int)(blockIdx.x % (unsigned)A.slices);
-  const int64_t u0 = (int64_t)(blockIdx.x / (unsigned)A.slices) * Ut;        // first user of the tile
-  const int nu = A.B - u0 < Ut ? (int)(A.B - u0) : Ut;                       // its users (>= 1)
-  const int v_begin = sl * A.tiles_per_slice * TK_BV;
-  const int64_t v_stop = (int64_t)v_begin + (int64_t)A.tiles_per_slice * TK_BV;
-  const int v_end = v_stop < V ? (int)v_stop : V;
-  const int nvt = (v_end - v_begin + TK_BV - 1) / TK_BV;
-
-  for (int i = tid; i < Ut * k; i += TK_THREADS) lists[i] = 0ull;
-  tk_cache_exclusions(A, u0, nu, Ut, xs, xn, xl);
-
-  // staging: tile row r is interest row u0 * K + r of the (B * K, D) matrix while r < nu * K, zero from there on
-  const int srow = tid >> 2;
-  const bool ua_ok = srow < nu * K;
-  const int64_t ua = ua_ok ? u0 * K + srow : 0;
+struct TkiProducer : TkStrided {
+  static constexpr int NA = GATE ? 2 : 1;
+  float* sc;                                   // [TK_BU][TK_SCLD] the s_j; with a gate the l_j follow
+  unsigned char* rest;
+  const TkiFields& F;
   const float* pa[NA];
-  pa[0] = A.user + ua * A.D;
-  if constexpr (GATE) pa[1] = A.gate + ua * A.D;
-  bool nan = false;
-
-  for (int vt = 0; vt < nvt; ++vt) {
-    const int v0 = v_begin + vt * TK_BV;
-    tk_fill_eligible(A.eligible, v0, V, el);
-    tki_tile<GATE>(pa, ua_ok, A.table, v0, V, A.D, sc, nu, K, A.mode);
-
-    // selection: wave w owns users w, w + 4, ... of the tile and their lists
-    const bool e_0 = el[lane] != 0, e_1 = el[64 + lane] != 0;
-    for (int ul = wave; ul < nu; ul += 4)
-      tk_select_user(sc + ul * K * TK_SCLD, lists + ul * k, xn + ul, xs + ul, xl + ul * TK_XCAP, A.excl_idx, v0, e_0, e_1, k, lane, nan);
-    __syncthreads();                                  // the score tiles and `el` are free for the next tile's operands
+  bool ua_ok;
+  __device__ __forceinline__ TkiProducer(unsigned char* p, const TkiFields& f)
+      : sc(reinterpret_cast<float*>(p)), rest(p + NA * TK_TILE_BYTES), F(f) {}
+  __device__ __forceinline__ int slots() const { return F.Ut; }
+  __device__ __forceinline__ void stage(const TkArgs& A, int64_t u0, int nu) {
+    const int srow = threadIdx.x >> 2;
+    ua_ok = srow < nu * F.K;
+    const int64_t ua = ua_ok ? u0 * F.K + srow : 0;
+    pa[0] = A.user + ua * A.D;
+    if constexpr (GATE) pa[1] = F.gate + ua * A.D;
   }
+  __device__ __forceinline__ void tile(const TkArgs& A, int v0, int nu) const {
+    tki_tile<GATE>(pa, ua_ok, A.table, v0, A.V, A.D, sc, nu, F.K, F.mode);
+  }
+  __device__ __forceinline__ const float* row(int ul) const { return sc + ul * F.K * TK_SCLD; }
+  __device__ __forceinline__ bool skip(int) const { return false; }
+};
 
-  if (nan && lane == 0) atomicOr(A.status, NRL_TOPK_E_NAN);
-  wave_lds_sync();
-  for (int ul = wave; ul < nu; ul += 4) tk_flush_user(lists + ul * k, A.partial + ((u0 + ul) * A.slices + sl) * k, k, lane);
+template <bool GATE>
+__global__ __launch_bounds__(TK_THREADS) void tki_scores_kernel(TkWith<TkArgs, TkiFields> A) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char tk_smem[];
+  TkiProducer<GATE> P(tk_smem, A);
+  TkSelect C(P.rest, A.Ut, A.k);
+  tk_walk(A, P, C);
 }
 
 // ---- z-scored ensemble scores (MANNeR) ------------------------------------------------------------------------------------------
@@ -559,7 +631,7 @@ __global__ __launch_bounds__(TK_THREADS) void tki_scores_kernel(TkiArgs A) {
 //   tke_scores_kernel  tk_scores_kernel with a second score tile that collects the weighted z-scores of the T products.
 // The chunks depend on V alone (never on B or `slices`), so a user's statistics are a function of its rows, the tables, the mask,
 // its exclusion set and V.
-struct TkeArgs : TkArgs {                      // `user` / `table` are those of sub-model 0
+struct TkeFields {                             // beside them `user` / `table` are those of sub-model 0
   const float* users[NRL_TOPK_MAX_MODELS];
   const float* tables[NRL_TOPK_MAX_MODELS];
   float w[NRL_TOPK_MAX_MODELS];
@@ -581,7 +653,7 @@ __device__ __forceinline__ void tke_fold(int& n, float& mean, float& m2, int nb,
   m2 = __fadd_rn(__fadd_rn(m2, m2b), __fdiv_rn(__fmul_rn(__fmul_rn(__fmul_rn(d, d), (float)na), (float)nb), (float)n));
 }
 
-__global__ __launch_bounds__(TK_THREADS) void tke_stats_kernel(TkeArgs A) {
+__global__ __launch_bounds__(TK_THREADS) void tke_stats_kernel(TkWith<TkArgs, TkeFields> A) {
   __shared__ __attribute__((aligned(16))) float sc[TK_BU * TK_SCLD];
   __shared__ int32_t xl[TK_BU * TK_XCAP];
   __shared__ int64_t xs[TK_BU];
@@ -668,7 +740,7 @@ __global__ __launch_bounds__(TK_THREADS) void tke_stats_kernel(TkeArgs A) {
 // a user's statistics can standardise: every sd positive and finite
 __device__ __forceinline__ bool tke_sd_ok(float sd) { return sd > 0.f && sd < INFINITY; }
 
-__global__ __launch_bounds__(64) void tke_finish_kernel(TkeArgs A) {
+__global__ __launch_bounds__(64) void tke_finish_kernel(TkWith<TkArgs, TkeFields> A) {
   const int64_t u = blockIdx.x;
   const int lane = threadIdx.x, T = A.T;
   bool bad = false;
@@ -743,54 +815,39 @@ __device__ __forceinline__ void tke_stage_stats(const float* out_stats, int64_t 
   }
 }
 
-__global__ __launch_bounds__(TK_THREADS) void tke_scores_kernel(TkeArgs A) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char tk_smem[];
-  float* const sc = reinterpret_cast<float*>(tk_smem);                       // [TK_BU][TK_SCLD] the raw scores of one table
-  float* const zs = sc + TK_BU * TK_SCLD;                                    // [TK_BU][TK_SCLD] the ensemble scores
-  int32_t* const xl = reinterpret_cast<int32_t*>(zs + TK_BU * TK_SCLD);      // [TK_BU][TK_XCAP]
-  int64_t* const xs = reinterpret_cast<int64_t*>(xl + TK_BU * TK_XCAP);      // [TK_BU]
-  int32_t* const xn = reinterpret_cast<int32_t*>(xs + TK_BU);                // [TK_BU]
-  uint8_t* const el = reinterpret_cast<uint8_t*>(xn + TK_BU);                // [TK_BV]
-  unsigned long long* const lists = reinterpret_cast<unsigned long long*>(el + TK_BV);      // [TK_BU][k]
-  float* const st = reinterpret_cast<float*>(lists + TK_BU * A.k);           // [TK_BU][T][2] mean, sd; sd 0: the user is refused
-
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int k = A.k, V = A.V, T = A.T;
-  const int sl = (int)(blockIdx.x % (unsigned)A.slices);
-  const int64_t u0 = (int64_t)(blockIdx.x / (unsigned)A.slices) * TK_BU;
-  const int nu = A.B - u0 < TK_BU ? (int)(A.B - u0) : TK_BU;
-  const int v_begin = sl * A.tiles_per_slice * TK_BV;
-  const int64_t v_stop = (int64_t)v_begin + (int64_t)A.tiles_per_slice * TK_BV;
-  const int v_end = v_stop < V ? (int)v_stop : V;
-  const int nvt = (v_end - v_begin + TK_BV - 1) / TK_BV;
-
-  for (int i = tid; i < TK_BU * k; i += TK_THREADS) lists[i] = 0ull;
-  tke_stage_stats(A.out_stats, u0, nu, T, st);
-  tk_cache_exclusions(A, u0, nu, TK_BU, xs, xn, xl);   // (its barrier also publishes `lists` and `st`)
-
-  const int ul_begin = wave * TK_USERS_PER_WAVE, ul_end = ul_begin + TK_USERS_PER_WAVE < nu ? ul_begin + TK_USERS_PER_WAVE : nu;
-  const int srow = tid >> 2;
-  const bool ua_ok = srow < nu;
-  const int64_t urow = ua_ok ? u0 + srow : A.B - 1;   // staging: tile row r is user u0 + r of every sub-model, zero past the last
-  bool nan = false;
-
-  for (int vt = 0; vt < nvt; ++vt) {
-    const int v0 = v_begin + vt * TK_BV;
-    tk_fill_eligible(A.eligible, v0, V, el);
-    tke_tile(A.users, A.tables, A.w, T, urow, ua_ok, v0, V, A.D, sc, zs, st);
-
-    const bool e_0 = el[lane] != 0, e_1 = el[64 + lane] != 0;
-    for (int ul = ul_begin; ul < ul_end; ++ul) {
-      if (st[ul * T * 2 + 1] == 0.f) continue;        // refused: the lists stay empty and the merge writes -1 / -inf
-      tk_select_user(zs + ul * TK_SCLD, lists + ul * k, xn + ul, xs + ul, xl + ul * TK_XCAP, A.excl_idx, v0, e_0, e_1, k, lane, nan);
-    }
-    __syncthreads();                                  // the ensemble tile and `el` are free for the next tile
+// The producer of the ensemble kernels: tile row r is user u0 + r of every sub-model, zero past the last; the raw tile, the ensemble
+// tile a user's scores are read from, then the workgroup's statistics.  A user whose statistics cannot standardise is skipped: its
+// list stays empty and the merge writes -1 / -inf; its counters stay 0, so the population comes out 0.
+struct TkeProducer : TkBlocked {
+  float* sc;                                   // [TK_BU][TK_SCLD] the raw scores of one table
+  float* zs;                                   // [TK_BU][TK_SCLD] the ensemble scores
+  float* st;                                   // [TK_BU][T][2] mean, sd; sd 0: the user is refused
+  unsigned char* rest;
+  const TkeFields& E;
+  int64_t urow;
+  bool ua_ok;
+  __device__ __forceinline__ TkeProducer(unsigned char* p, const TkeFields& e)
+      : sc(reinterpret_cast<float*>(p)), zs(sc + TK_BU * TK_SCLD), st(zs + TK_BU * TK_SCLD),
+        rest(p + 2 * TK_TILE_BYTES + (size_t)TK_BU * e.T * 2 * 4), E(e) {}
+  __device__ __forceinline__ int slots() const { return TK_BU; }
+  __device__ __forceinline__ void stage(const TkArgs& A, int64_t u0, int nu) {
+    tke_stage_stats(E.out_stats, u0, nu, E.T, st);
+    const int srow = threadIdx.x >> 2;
+    ua_ok = srow < nu;
+    urow = ua_ok ? u0 + srow : A.B - 1;
   }
+  __device__ __forceinline__ void tile(const TkArgs& A, int v0, int) const {
+    tke_tile(E.users, E.tables, E.w, E.T, urow, ua_ok, v0, A.V, A.D, sc, zs, st);
+  }
+  __device__ __forceinline__ const float* row(int ul) const { return zs + ul * TK_SCLD; }
+  __device__ __forceinline__ bool skip(int ul) const { return st[ul * E.T * 2 + 1] == 0.f; }
+};
 
-  if (nan && lane == 0) atomicOr(A.status, NRL_TOPK_E_NAN);
-  wave_lds_sync();
-  for (int ul = ul_begin; ul < ul_end; ++ul) tk_flush_user(lists + ul * k, A.partial + ((u0 + ul) * A.slices + sl) * k, k, lane);
+__global__ __launch_bounds__(TK_THREADS) void tke_scores_kernel(TkWith<TkArgs, TkeFields> A) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char tk_smem[];
+  TkeProducer P(tk_smem, A);
+  TkSelect C(P.rest, TK_BU, A.k);
+  tk_walk(A, P, C);
 }
 
 // ---- factored DNN scores (DKN) ---------------------------------------------------------------------------------------------------
@@ -803,7 +860,7 @@ __global__ __launch_bounds__(TK_THREADS) void tke_scores_kernel(TkeArgs A) {
 //   * wave w produces the scores of its own users 16 w ... 16 w + 15 (the ones it selects for): a lane holds 16 x 2 chains
 //     s = b2; s = fmaf(w2[j], h_j, s) in ascending j, h_j = x < 0 ? 0 : x (a NaN x stays NaN), x = proj[v, j] + q[u, j];
 //   * the proj tile is dead once every chain is complete; the scores overwrite it and the selection runs as everywhere.
-struct TkrArgs : TkArgs {                      // `user` is q, `table` is proj, D is Hd
+struct TkrFields {                             // beside them `user` is q, `table` is proj, D is Hd
   const float* w2;
   const float* b2;
 };
@@ -813,19 +870,16 @@ constexpr int tkr_ldq(int Hd) { return (Hd + 3) & ~3; }
 constexpr size_t tkr_extra_lds(int Hd) { return (size_t)(TK_BU + 1) * tkr_ldq(Hd) * 4; }      // q rows, then w2
 static_assert(TK_BV * tkr_ldp(NRL_TOPK_MAX_HIDDEN) <= TK_BU * TK_SCLD, "the proj tile lives inside the score tile");
 static_assert(tk_lds_bytes(1, TK_BU, NRL_TOPK_MAX_K) + tkr_extra_lds(NRL_TOPK_MAX_HIDDEN) <= 160 * 1024 &&
-                  tk_lds_bytes(1, TK_BU, 1) % 16 == 0 && (TK_BU * 8) % 16 == 0,
-              "the largest layout fits, and the q rows that follow the lists are 16-byte aligned for every k");
+                  tkr_extra_lds(1) % 16 == 0 && tkr_extra_lds(NRL_TOPK_MAX_HIDDEN) % 16 == 0,
+              "the largest layout fits; under the walk the q rows follow the score tile (16-byte aligned) and, whole float4s,"
+              " keep the consumer's arrays aligned");
 
 __device__ __forceinline__ float tkr_step(float w, float p, float q, float s) {
   const float x = __fadd_rn(p, q);
   return fmaf(w, x < 0.f ? 0.f : x, s);
 }
 
-// The tile producer of the DNN count kernel, in three pieces.  It is tkr_scores_kernel's producer, DUPLICATED rather than shared:
-// with the scores kernel calling these functions the compiler scheduled its chains differently and the whole call measured
-// 2 - 5 % slower at B = 512, V = 65,536 (profiles/topk_scores_refactor_before_after.txt), so that kernel keeps its own text.  The
-// two must stay the same chain, line for line: tests/test_gpu_catalogue_rank_scorers.py::test_consistency_with_topk_on_real_values
-// compares the score bits of the two.
+// The tile producer of the DNN count kernel, in three pieces (tkr_scores_kernel has its own copy: below).
 // q of the tile's `nu` users from u0 on and w2 into LDS: qs[TK_BU][ldq], zero past Hd and past the last user, then w2s[ldq]
 __device__ __forceinline__ void tkr_stage_users(const float* q, const float* w2, int64_t u0, int nu, int Hd, float* qs, float* w2s) {
   const int tid = threadIdx.x, ldq = tkr_ldq(Hd);
@@ -906,7 +960,46 @@ __device__ __forceinline__ void tkr_tile(const float* table, int v0, int V, int 
   __syncthreads();
 }
 
-__global__ __launch_bounds__(TK_THREADS) void tkr_scores_kernel(TkrArgs A) {
+// The producer of the DNN count kernel: the score tile, then the q rows of the tile's users and w2.  Blocked mapping, and it needs
+// it: a wave computes the scores of the users it serves.
+struct TkrProducer : TkBlocked {
+  float* sc;                                   // [TK_BU][TK_SCLD]; before: proj tile [TK_BV][ldp]
+  float* qs;                                   // [TK_BU][ldq], zero past Hd and past the last user
+  float* w2s;                                  // [ldq]
+  unsigned char* rest;
+  const TkrFields& F;
+  TkrWalk W;
+  const float* qw;                             // the q rows of the users this wave serves, the first of which is ul_begin
+  int ul_begin;
+  float b2;
+  __device__ __forceinline__ TkrProducer(unsigned char* p, const TkrFields& f, int Hd)
+      : sc(reinterpret_cast<float*>(p)), qs(sc + TK_BU * TK_SCLD), w2s(qs + TK_BU * tkr_ldq(Hd)),
+        rest(p + TK_TILE_BYTES + tkr_extra_lds(Hd)), F(f) {}
+  __device__ __forceinline__ int slots() const { return TK_BU; }
+  __device__ __forceinline__ void stage(const TkArgs& A, int64_t u0, int nu) {
+    tkr_stage_users(A.user, F.w2, u0, nu, A.D, qs, w2s);
+    b2 = F.b2[0];
+    W = tkr_walk(A.D);
+    ul_begin = first(__builtin_amdgcn_readfirstlane(threadIdx.x >> 6));
+    qw = qs + ul_begin * tkr_ldq(A.D);
+  }
+  __device__ __forceinline__ void tile(const TkArgs& A, int v0, int) const {
+    tkr_tile(A.table, v0, A.V, A.D, W, sc, qw, w2s, b2, ul_begin);
+  }
+  __device__ __forceinline__ const float* row(int ul) const { return sc + ul * TK_SCLD; }
+  __device__ __forceinline__ bool skip(int) const { return false; }
+};
+
+// tkr_scores_kernel is the one walk kernel that is NOT an instantiation of tk_walk: it keeps its own text -- the skeleton, the slice
+// range and DKN's tile producer inline -- and compiles to the instructions it always had.  DUPLICATED rather than shared: with this
+// kernel going through TkrProducer (tkr_stage_users / tkr_walk / tkr_tile) the compiler scheduled its scalar code differently and
+// the whole call measured 3 - 8 % slower at B = 512, V = 65,536, Hd = 16, as it had when the producer was first factored out
+// (profiles/topk_walk_refactor_before_after.txt, profiles/topk_scores_refactor_before_after.txt).  Its LDS order is the earlier
+// one too: lists after `el`, then q and w2 (tk_lds_bytes(1, TK_BU, 1) and TK_BU * 8 are multiples of 16, so the q rows are
+// 16-byte aligned for every k).  The chain must stay that of tkr_tile, line for line:
+// tests/test_gpu_catalogue_rank_scorers.py::test_consistency_with_topk_on_real_values compares the score bits of the two.
+static_assert(tk_lds_bytes(1, TK_BU, 1) % 16 == 0 && (TK_BU * 8) % 16 == 0, "tkr_scores_kernel's q rows follow its lists, 16-byte aligned");
+__global__ __launch_bounds__(TK_THREADS) void tkr_scores_kernel(TkWith<TkArgs, TkrFields> A) {
   extern __shared__ __attribute__((aligned(16))) unsigned char tk_smem[];
   float* const sc = reinterpret_cast<float*>(tk_smem);                       // [TK_BU][TK_SCLD]; before: proj tile [TK_BV][ldp]
   int32_t* const xl = reinterpret_cast<int32_t*>(sc + TK_BU * TK_SCLD);      // [TK_BU][TK_XCAP]
@@ -1026,7 +1119,7 @@ __global__ __launch_bounds__(TK_THREADS) void tkr_scores_kernel(TkrArgs A) {
 // LDS: the three operand tiles (38 KB) take the place of the one score tile (33 KB) of tk_lds_bytes(1, ...), so two workgroups
 // fit a CU up to k = 50; (B, V, L) is never written.  Registers: 32 positions x (2 accumulators + 3 state) and the staging; the
 // second launch bound holds the compiler to two waves per SIMD (231 VGPRs, no scratch; without it 269 and one wave: a quarter slower).
-struct TkpArgs : TkArgs {                      // `user` is q, `table` the feature maps, D is F
+struct TkpFields {                             // beside them `user` is q, `table` the feature maps, D is F
   const float* uvec;
   int32_t L;
 };
@@ -1078,51 +1171,36 @@ __device__ __forceinline__ void tkp_tile(const float* const (&pa)[2], bool ua_ok
   __syncthreads();
 }
 
-__global__ __launch_bounds__(TK_THREADS, 2) void tkp_scores_kernel(TkpArgs A) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char tk_smem[];
-  float* const sc = reinterpret_cast<float*>(tk_smem);                       // operand tiles; afterwards [TK_BU][TK_SCLD] scores
-  int32_t* const xl = reinterpret_cast<int32_t*>(sc + TKP_OPERAND_FLOATS);   // [TK_BU][TK_XCAP]
-  int64_t* const xs = reinterpret_cast<int64_t*>(xl + TK_BU * TK_XCAP);      // [TK_BU]
-  int32_t* const xn = reinterpret_cast<int32_t*>(xs + TK_BU);                // [TK_BU]
-  uint8_t* const el = reinterpret_cast<uint8_t*>(xn + TK_BU);                // [TK_BV]
-  unsigned long long* const lists = reinterpret_cast<unsigned long long*>(el + TK_BV);      // [TK_BU][k]
-
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int k = A.k, V = A.V, L = A.L, F = A.D;
-  const int sl = (int)(blockIdx.x % (unsigned)A.slices);
-  const int64_t u0 = (int64_t)(blockIdx.x / (unsigned)A.slices) * TK_BU;
-  const int nu = A.B - u0 < TK_BU ? (int)(A.B - u0) : TK_BU;
-  const int v_begin = sl * A.tiles_per_slice * TK_BV;
-  const int64_t v_stop = (int64_t)v_begin + (int64_t)A.tiles_per_slice * TK_BV;
-  const int v_end = v_stop < V ? (int)v_stop : V;
-  const int nvt = (v_end - v_begin + TK_BV - 1) / TK_BV;
-
-  for (int i = tid; i < TK_BU * k; i += TK_THREADS) lists[i] = 0ull;
-  tk_cache_exclusions(A, u0, nu, TK_BU, xs, xn, xl);
-
-  const int ul_begin = wave * TK_USERS_PER_WAVE, ul_end = ul_begin + TK_USERS_PER_WAVE < nu ? ul_begin + TK_USERS_PER_WAVE : nu;
-  const int srow = tid >> 2;
-  const bool ua_ok = srow < nu;
-  const int64_t ua = (ua_ok ? u0 + srow : A.B - 1) * F;
-  const float* const pa[2] = {A.user + ua, A.uvec + ua};
-  const int64_t ldt = (int64_t)L * F;
-  bool nan = false;
-
-  for (int vt = 0; vt < nvt; ++vt) {
-    const int v0 = v_begin + vt * TK_BV;
-    tk_fill_eligible(A.eligible, v0, V, el);
-    tkp_tile<false>(pa, ua_ok, A.table, ldt, v0, V, L, F, sc);
-
-    const bool e_0 = el[lane] != 0, e_1 = el[64 + lane] != 0;
-    for (int ul = ul_begin; ul < ul_end; ++ul)
-      tk_select_user(sc + ul * TK_SCLD, lists + ul * k, xn + ul, xs + ul, xl + ul * TK_XCAP, A.excl_idx, v0, e_0, e_1, k, lane, nan);
-    __syncthreads();                                  // the score tile and `el` are free for the next tile's operands
+// The producer of the pooling kernels: tile row r is (q, user) of user u0 + r, zero past the last user; the three operand tiles,
+// of which the score tile takes the place once the last token is folded.
+struct TkpProducer : TkBlocked {
+  float* sc;                                   // operand tiles; afterwards [TK_BU][TK_SCLD] scores
+  unsigned char* rest;
+  const TkpFields& F;
+  const float* pa[2];
+  bool ua_ok;
+  __device__ __forceinline__ TkpProducer(unsigned char* p, const TkpFields& f)
+      : sc(reinterpret_cast<float*>(p)), rest(p + (size_t)TKP_OPERAND_FLOATS * 4), F(f) {}
+  __device__ __forceinline__ int slots() const { return TK_BU; }
+  __device__ __forceinline__ void stage(const TkArgs& A, int64_t u0, int nu) {
+    const int srow = threadIdx.x >> 2;
+    ua_ok = srow < nu;
+    const int64_t ua = (ua_ok ? u0 + srow : A.B - 1) * A.D;
+    pa[0] = A.user + ua;
+    pa[1] = F.uvec + ua;
   }
+  __device__ __forceinline__ void tile(const TkArgs& A, int v0, int) const {
+    tkp_tile<false>(pa, ua_ok, A.table, (int64_t)F.L * A.D, v0, A.V, F.L, A.D, sc);
+  }
+  __device__ __forceinline__ const float* row(int ul) const { return sc + ul * TK_SCLD; }
+  __device__ __forceinline__ bool skip(int) const { return false; }
+};
 
-  if (nan && lane == 0) atomicOr(A.status, NRL_TOPK_E_NAN);
-  wave_lds_sync();
-  for (int ul = ul_begin; ul < ul_end; ++ul) tk_flush_user(lists + ul * k, A.partial + ((u0 + ul) * A.slices + sl) * k, k, lane);
+__global__ __launch_bounds__(TK_THREADS, 2) void tkp_scores_kernel(TkWith<TkArgs, TkpFields> A) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char tk_smem[];
+  TkpProducer P(tk_smem, A);
+  TkSelect C(P.rest, TK_BU, A.k);
+  tk_walk(A, P, C);
 }
 
 // ---- full-catalogue rank of held-out rows ------------------------------------------------------------------------------------------
@@ -1180,11 +1258,9 @@ struct TkcLds {
 constexpr size_t tkc_lds_bytes(int slots) {
   return (size_t)slots * (TKC_T * 8 + 8 + 8 + TK_XCAP * 4 + 4 + TKC_CLD * 4 + 4) + TK_BV;
 }
-constexpr size_t TKC_TILE_BYTES = (size_t)TK_BU * TK_SCLD * 4;
 // dynamic LDS of tkc_count_kernel: score tile, then the layout above (33 KB + 41.9 KB)
-constexpr size_t TKC_LDS = TKC_TILE_BYTES + tkc_lds_bytes(TK_BU);
+constexpr size_t TKC_LDS = TK_TILE_BYTES + tkc_lds_bytes(TK_BU);
 static_assert(2 * TKC_LDS <= 160 * 1024, "two workgroups of the count kernel fit a CU");
-static_assert(TKC_TILE_BYTES % 16 == 0, "what follows the score tiles is 16-byte aligned");
 
 // a user's target range: false when the offsets decrease, leave [0, n_targets] or span more than TKC_T slots
 __device__ __forceinline__ bool tkc_tgt_range(const TkcArgs& A, int64_t u, int64_t& s, int& n) {
@@ -1257,13 +1333,20 @@ __device__ __forceinline__ void tkc_flush_user(const TkcArgs& A, const TkcLds& S
   if (lane < S.tn[ul] && S.te[ul * TKC_T + lane] != ~0ull) A.tcnt[(S.ts[ul] + lane) * A.slices + sl] = S.cnt[ul * TKC_CLD + lane];
 }
 
-// the slice of table tiles of a workgroup of a count (or scores) walk: first row and number of tiles
-__device__ __forceinline__ void tkc_slice(const TkArgs& A, int sl, int& v_begin, int& nvt) {
-  v_begin = sl * A.tiles_per_slice * TK_BV;
-  const int64_t v_stop = (int64_t)v_begin + (int64_t)A.tiles_per_slice * TK_BV;
-  const int v_end = v_stop < A.V ? (int)v_stop : A.V;
-  nvt = (v_end - v_begin + TK_BV - 1) / TK_BV;
-}
+// the counting consumer of the walk
+struct TkCount {
+  const TkcLds S;
+  uint8_t* el;
+  __device__ __forceinline__ TkCount(unsigned char* p, int slots) : S(p, slots), el(S.el) {}
+  __device__ __forceinline__ void prologue(const TkcArgs& A, int64_t u0, int nu, int slots) const { tkc_prologue(A, u0, nu, slots, S); }
+  __device__ __forceinline__ void user(const float* row, int ul, const int64_t* excl_idx, int v0, bool e_0, bool e_1, int lane,
+                                       bool& nan) const {
+    tkc_count_user(row, S, ul, excl_idx, v0, e_0, e_1, lane, nan);
+  }
+  __device__ __forceinline__ void flush(const TkcArgs& A, int ul, int64_t u, int sl, int lane) const {
+    tkc_flush_user(A, S, ul, u, sl, lane);
+  }
+};
 
 __global__ __launch_bounds__(64) void tkc_init_kernel(TkcArgs A) {
   const int64_t j = blockIdx.x;
@@ -1305,52 +1388,17 @@ __global__ __launch_bounds__(TK_THREADS) void tkc_target_kernel(TkcArgs A) {
 
 __global__ __launch_bounds__(TK_THREADS) void tkc_count_kernel(TkcArgs A) {
   extern __shared__ __attribute__((aligned(16))) unsigned char tk_smem[];
-  float* const sc = reinterpret_cast<float*>(tk_smem);                       // [TK_BU][TK_SCLD]
-  const TkcLds S(tk_smem + TKC_TILE_BYTES, TK_BU);
-
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int V = A.V;
-  const int sl = (int)(blockIdx.x % (unsigned)A.slices);
-  const int64_t u0 = (int64_t)(blockIdx.x / (unsigned)A.slices) * TK_BU;
-  const int nu = A.B - u0 < TK_BU ? (int)(A.B - u0) : TK_BU;
-  int v_begin, nvt;
-  tkc_slice(A, sl, v_begin, nvt);
-
-  tkc_prologue(A, u0, nu, TK_BU, S);
-
-  const int ul_begin = wave * TK_USERS_PER_WAVE, ul_end = ul_begin + TK_USERS_PER_WAVE < nu ? ul_begin + TK_USERS_PER_WAVE : nu;
-  const int srow = tid >> 2;
-  const bool ua_ok = srow < nu;
-  const float* const pa[1] = {A.user + (ua_ok ? u0 + srow : A.B - 1) * A.D};
-  bool nan = false;
-
-  for (int vt = 0; vt < nvt; ++vt) {
-    const int v0 = v_begin + vt * TK_BV;
-    tk_fill_eligible(A.eligible, v0, V, S.el);
-    tk_tile_product<1>(pa, ua_ok, A.table, v0, V, A.D, sc);
-
-    const bool e_0 = S.el[lane] != 0, e_1 = S.el[64 + lane] != 0;
-    for (int ul = ul_begin; ul < ul_end; ++ul) tkc_count_user(sc + ul * TK_SCLD, S, ul, A.excl_idx, v0, e_0, e_1, lane, nan);
-    __syncthreads();                                  // the score tile and `el` are free for the next tile's operands
-  }
-
-  if (nan && lane == 0) atomicOr(A.status, NRL_TOPK_E_NAN);
-  wave_lds_sync();
-  for (int ul = ul_begin; ul < ul_end; ++ul) tkc_flush_user(A, S, ul, u0 + ul, sl, lane);
+  TkDot P(tk_smem);
+  TkCount C(P.rest, TK_BU);
+  tk_walk(A, P, C);
 }
 
 // ---- the count walk under the other scorers ------------------------------------------------------------------------------------------
-// Each is the walk of its scores kernel -- the same tile producer, device function for device function, so a score's bits cannot
-// differ between the top-k list and the rank -- with the counting consumer, and a target kernel that computes the slots' scores by
-// the same chain.
+// Each is the walk under its scorer's producer -- the one its scores kernel runs, so a score's bits cannot differ between the
+// top-k list and the rank -- with the counting consumer, and a target kernel that computes the slots' scores by the same chain.
 
-// MINER: tki_scores_kernel's walk.  A workgroup holds Ut = 64 / K users, so the consumer's arrays are [Ut][...].
-struct TkicArgs : TkcArgs {                    // `user` is the interests; B counts users
-  const float* gate;
-  int32_t K, Ut, mode;
-};
-constexpr size_t tkic_lds_bytes(bool gate, int Ut) { return (gate ? 2 : 1) * TKC_TILE_BYTES + tkc_lds_bytes(Ut); }
+// MINER.  A workgroup holds Ut = 64 / K users, so the consumer's arrays are [Ut][...].
+constexpr size_t tkic_lds_bytes(bool gate, int Ut) { return (gate ? 2 : 1) * TK_TILE_BYTES + tkc_lds_bytes(Ut); }
 static_assert(2 * tkic_lds_bytes(false, TK_BU) <= 160 * 1024, "max / mean: two workgroups of the interest count kernel fit a CU");
 static_assert(tkic_lds_bytes(true, TK_BU) <= 160 * 1024, "weighted: the second score tile leaves room for one workgroup per CU");
 
@@ -1358,7 +1406,7 @@ static_assert(tkic_lds_bytes(true, TK_BU) <= 160 * 1024, "weighted: the second s
 // j0 + i, the table tile is the gathered target rows from j0 on, so slot j0 + i's K products are column i of those rows; the
 // aggregate over them is the score tki_scores_kernel computes for that (user, row).  K = 1: tkc_target_kernel.
 template <bool GATE>
-__global__ __launch_bounds__(TK_THREADS) void tkic_target_kernel(TkicArgs A) {
+__global__ __launch_bounds__(TK_THREADS) void tkic_target_kernel(TkWith<TkcArgs, TkiFields> A) {
   extern __shared__ __attribute__((aligned(16))) unsigned char tk_smem[];
   constexpr int NA = GATE ? 2 : 1;
   float* const sc = reinterpret_cast<float*>(tk_smem);                       // [TK_BU][TK_SCLD] the s_j; with a gate the l_j follow
@@ -1380,61 +1428,20 @@ __global__ __launch_bounds__(TK_THREADS) void tkic_target_kernel(TkicArgs A) {
 }
 
 template <bool GATE>
-__global__ __launch_bounds__(TK_THREADS) void tkic_count_kernel(TkicArgs A) {
+__global__ __launch_bounds__(TK_THREADS) void tkic_count_kernel(TkWith<TkcArgs, TkiFields> A) {
   extern __shared__ __attribute__((aligned(16))) unsigned char tk_smem[];
-  constexpr int NA = GATE ? 2 : 1;
-  const int K = A.K, Ut = A.Ut;
-  float* const sc = reinterpret_cast<float*>(tk_smem);                       // [TK_BU][TK_SCLD] the s_j; with a gate the l_j follow
-  const TkcLds S(tk_smem + NA * TKC_TILE_BYTES, Ut);
-
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int V = A.V;
-  const int sl = (int)(blockIdx.x % (unsigned)A.slices);
-  const int64_t u0 = (int64_t)(blockIdx.x / (unsigned)A.slices) * Ut;        // first user of the tile
-  const int nu = A.B - u0 < Ut ? (int)(A.B - u0) : Ut;                       // its users (>= 1)
-  int v_begin, nvt;
-  tkc_slice(A, sl, v_begin, nvt);
-
-  tkc_prologue(A, u0, nu, Ut, S);
-
-  // staging: tile row r is interest row u0 * K + r of the (B * K, D) matrix while r < nu * K, zero from there on
-  const int srow = tid >> 2;
-  const bool ua_ok = srow < nu * K;
-  const int64_t ua = ua_ok ? u0 * K + srow : 0;
-  const float* pa[NA];
-  pa[0] = A.user + ua * A.D;
-  if constexpr (GATE) pa[1] = A.gate + ua * A.D;
-  bool nan = false;
-
-  for (int vt = 0; vt < nvt; ++vt) {
-    const int v0 = v_begin + vt * TK_BV;
-    tk_fill_eligible(A.eligible, v0, V, S.el);
-    tki_tile<GATE>(pa, ua_ok, A.table, v0, V, A.D, sc, nu, K, A.mode);
-
-    // wave w owns users w, w + 4, ... of the tile and their counters
-    const bool e_0 = S.el[lane] != 0, e_1 = S.el[64 + lane] != 0;
-    for (int ul = wave; ul < nu; ul += 4) tkc_count_user(sc + ul * K * TK_SCLD, S, ul, A.excl_idx, v0, e_0, e_1, lane, nan);
-    __syncthreads();                                  // the score tiles and `el` are free for the next tile's operands
-  }
-
-  if (nan && lane == 0) atomicOr(A.status, NRL_TOPK_E_NAN);
-  wave_lds_sync();
-  for (int ul = wave; ul < nu; ul += 4) tkc_flush_user(A, S, ul, u0 + ul, sl, lane);
+  TkiProducer<GATE> P(tk_smem, A);
+  TkCount C(P.rest, A.Ut);
+  tk_walk(A, P, C);
 }
 
-// DKN: tkr_scores_kernel's walk (over the duplicate of its producer above).  The q rows and w2 follow the score tile (16-byte aligned), then the consumer's arrays.
-struct TkrcArgs : TkcArgs {                    // `user` is q, `table` is proj, D is Hd
-  const float* w2;
-  const float* b2;
-};
-constexpr size_t tkrc_lds_bytes(int Hd) { return TKC_TILE_BYTES + tkr_extra_lds(Hd) + tkc_lds_bytes(TK_BU); }
-static_assert(tkr_extra_lds(NRL_TOPK_MAX_HIDDEN) % 16 == 0 && tkrc_lds_bytes(NRL_TOPK_MAX_HIDDEN) <= 160 * 1024 &&
-                  2 * tkrc_lds_bytes(20) <= 160 * 1024,
+// DKN.  The q rows and w2 follow the score tile (16-byte aligned), then the consumer's arrays.
+constexpr size_t tkrc_lds_bytes(int Hd) { return TK_TILE_BYTES + tkr_extra_lds(Hd) + tkc_lds_bytes(TK_BU); }
+static_assert(tkrc_lds_bytes(NRL_TOPK_MAX_HIDDEN) <= 160 * 1024 && 2 * tkrc_lds_bytes(20) <= 160 * 1024,
               "the largest layout fits (91.1 KB at Hd = 64: one workgroup per CU); two workgroups fit a CU up to Hd = 20");
 
 // one thread per slot: the chain of tkr_tile for (owner, target row), read in place -- no gather, no tile
-__global__ __launch_bounds__(256) void tkrc_target_kernel(TkrcArgs A) {
+__global__ __launch_bounds__(256) void tkrc_target_kernel(TkWith<TkcArgs, TkrFields> A) {
   const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (j >= A.n_targets) return;
   const int own = A.owner[j], Hd = A.D;
@@ -1449,59 +1456,22 @@ __global__ __launch_bounds__(256) void tkrc_target_kernel(TkrcArgs A) {
   A.tscore[j] = s;
 }
 
-__global__ __launch_bounds__(TK_THREADS) void tkrc_count_kernel(TkrcArgs A) {
+__global__ __launch_bounds__(TK_THREADS) void tkrc_count_kernel(TkWith<TkcArgs, TkrFields> A) {
   extern __shared__ __attribute__((aligned(16))) unsigned char tk_smem[];
-  float* const sc = reinterpret_cast<float*>(tk_smem);                       // [TK_BU][TK_SCLD]; before: proj tile [TK_BV][ldp]
-  const int Hd = A.D;
-  float* const qs = sc + TK_BU * TK_SCLD;                                    // [TK_BU][ldq], zero past Hd and past the last user
-  float* const w2s = qs + TK_BU * tkr_ldq(Hd);                               // [ldq]
-  const TkcLds S(tk_smem + TKC_TILE_BYTES + tkr_extra_lds(Hd), TK_BU);
-
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int V = A.V;
-  const int sl = (int)(blockIdx.x % (unsigned)A.slices);
-  const int64_t u0 = (int64_t)(blockIdx.x / (unsigned)A.slices) * TK_BU;
-  const int nu = A.B - u0 < TK_BU ? (int)(A.B - u0) : TK_BU;
-  int v_begin, nvt;
-  tkc_slice(A, sl, v_begin, nvt);
-
-  tkr_stage_users(A.user, A.w2, u0, nu, Hd, qs, w2s);
-  const float b2 = A.b2[0];
-  tkc_prologue(A, u0, nu, TK_BU, S);                  // (its barriers also publish `qs` and `w2s`)
-
-  const int ul_begin = wave * TK_USERS_PER_WAVE, ul_end = ul_begin + TK_USERS_PER_WAVE < nu ? ul_begin + TK_USERS_PER_WAVE : nu;
-  const TkrWalk W = tkr_walk(Hd);
-  bool nan = false;
-
-  for (int vt = 0; vt < nvt; ++vt) {
-    const int v0 = v_begin + vt * TK_BV;
-    tk_fill_eligible(A.eligible, v0, V, S.el);
-    tkr_tile(A.table, v0, V, Hd, W, sc, qs + ul_begin * tkr_ldq(Hd), w2s, b2, ul_begin);
-
-    const bool e_0 = S.el[lane] != 0, e_1 = S.el[64 + lane] != 0;
-    for (int ul = ul_begin; ul < ul_end; ++ul) tkc_count_user(sc + ul * TK_SCLD, S, ul, A.excl_idx, v0, e_0, e_1, lane, nan);
-    __syncthreads();                                  // the score tile and `el` are free for the next proj tile
-  }
-
-  if (nan && lane == 0) atomicOr(A.status, NRL_TOPK_E_NAN);
-  wave_lds_sync();
-  for (int ul = ul_begin; ul < ul_end; ++ul) tkc_flush_user(A, S, ul, u0 + ul, sl, lane);
+  TkrProducer P(tk_smem, A, A.D);
+  TkCount C(P.rest, TK_BU);
+  tk_walk(A, P, C);
 }
 
-// NPA: tkp_scores_kernel's walk.  The operand tiles (38 KB) and the consumer's arrays (41.9 KB) are 79.9 KB: two workgroups fit a
-// CU with all NRL_RANK_MAX_TARGETS targets.
-struct TkpcArgs : TkcArgs {                    // `user` is q, `table` the feature maps, D is F
-  const float* uvec;
-  int32_t L;
-};
+// NPA.  The operand tiles (38 KB) and the consumer's arrays (41.9 KB) are 79.9 KB: two workgroups fit a CU with all
+// NRL_RANK_MAX_TARGETS targets.
 constexpr size_t TKPC_LDS = (size_t)TKP_OPERAND_FLOATS * 4 + tkc_lds_bytes(TK_BU);
 static_assert(((size_t)TKP_OPERAND_FLOATS * 4) % 16 == 0 && 2 * TKPC_LDS <= 160 * 1024,
               "two workgroups of the pooled count kernel fit a CU (under 80 KB each)");
 
 // One workgroup per 64 slots from j0 on: tile row r is (q, user) of the owner of slot j0 + r, tile column c the feature map of
 // target row tgt_idx[j0 + c], read in place (nothing is gathered: a map is L F floats); slot j0 + r's score is the diagonal.
-__global__ __launch_bounds__(TK_THREADS, 2) void tkpc_target_kernel(TkpcArgs A) {
+__global__ __launch_bounds__(TK_THREADS, 2) void tkpc_target_kernel(TkWith<TkcArgs, TkpFields> A) {
   __shared__ __attribute__((aligned(16))) float sc[TKP_OPERAND_FLOATS];
   const int tid = threadIdx.x, F = A.D;
   const int64_t j0 = (int64_t)blockIdx.x * TK_BU;
@@ -1514,61 +1484,22 @@ __global__ __launch_bounds__(TK_THREADS, 2) void tkpc_target_kernel(TkpcArgs A) 
   if (tid < TK_BU && j0 + tid < A.n_targets) A.tscore[j0 + tid] = sc[tid * TK_SCLD + tid];
 }
 
-__global__ __launch_bounds__(TK_THREADS, 2) void tkpc_count_kernel(TkpcArgs A) {
+__global__ __launch_bounds__(TK_THREADS, 2) void tkpc_count_kernel(TkWith<TkcArgs, TkpFields> A) {
   extern __shared__ __attribute__((aligned(16))) unsigned char tk_smem[];
-  float* const sc = reinterpret_cast<float*>(tk_smem);                       // operand tiles; afterwards [TK_BU][TK_SCLD] scores
-  const TkcLds S(tk_smem + (size_t)TKP_OPERAND_FLOATS * 4, TK_BU);
-
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int V = A.V, L = A.L, F = A.D;
-  const int sl = (int)(blockIdx.x % (unsigned)A.slices);
-  const int64_t u0 = (int64_t)(blockIdx.x / (unsigned)A.slices) * TK_BU;
-  const int nu = A.B - u0 < TK_BU ? (int)(A.B - u0) : TK_BU;
-  int v_begin, nvt;
-  tkc_slice(A, sl, v_begin, nvt);
-
-  tkc_prologue(A, u0, nu, TK_BU, S);
-
-  const int ul_begin = wave * TK_USERS_PER_WAVE, ul_end = ul_begin + TK_USERS_PER_WAVE < nu ? ul_begin + TK_USERS_PER_WAVE : nu;
-  const int srow = tid >> 2;
-  const bool ua_ok = srow < nu;
-  const int64_t ua = (ua_ok ? u0 + srow : A.B - 1) * F;
-  const float* const pa[2] = {A.user + ua, A.uvec + ua};
-  const int64_t ldt = (int64_t)L * F;
-  bool nan = false;
-
-  for (int vt = 0; vt < nvt; ++vt) {
-    const int v0 = v_begin + vt * TK_BV;
-    tk_fill_eligible(A.eligible, v0, V, S.el);
-    tkp_tile<false>(pa, ua_ok, A.table, ldt, v0, V, L, F, sc);
-
-    const bool e_0 = S.el[lane] != 0, e_1 = S.el[64 + lane] != 0;
-    for (int ul = ul_begin; ul < ul_end; ++ul) tkc_count_user(sc + ul * TK_SCLD, S, ul, A.excl_idx, v0, e_0, e_1, lane, nan);
-    __syncthreads();                                  // the score tile and `el` are free for the next tile's operands
-  }
-
-  if (nan && lane == 0) atomicOr(A.status, NRL_TOPK_E_NAN);
-  wave_lds_sync();
-  for (int ul = ul_begin; ul < ul_end; ++ul) tkc_flush_user(A, S, ul, u0 + ul, sl, lane);
+  TkpProducer P(tk_smem, A);
+  TkCount C(P.rest, TK_BU);
+  tk_walk(A, P, C);
 }
 
-// MANNeR: tke_scores_kernel's walk.  The statistics pass runs first, as for the top-k; the raw tile, the ensemble tile and the
-// workgroup's statistics (67.5 KB) and the consumer's arrays (41.9 KB) are 109.4 KB: one workgroup per CU.
-struct TkecArgs : TkcArgs {                    // `user` / `table` are those of sub-model 0; the ensemble fields of TkeArgs
-  const float* users[NRL_TOPK_MAX_MODELS];
-  const float* tables[NRL_TOPK_MAX_MODELS];
-  float w[NRL_TOPK_MAX_MODELS];
-  int32_t T;
-  const float* stats;                          // (B, T, 2): mean, sd, as tke_finish_kernel left them
-};
-constexpr size_t TKEC_LDS = 2 * TKC_TILE_BYTES + TKE_STATS_LDS + tkc_lds_bytes(TK_BU);
-static_assert((2 * TKC_TILE_BYTES + TKE_STATS_LDS) % 16 == 0 && TKEC_LDS <= 160 * 1024,
+// MANNeR.  The statistics pass runs first, as for the top-k; the raw tile, the ensemble tile and the workgroup's statistics
+// (67.5 KB) and the consumer's arrays (41.9 KB) are 109.4 KB: one workgroup per CU.
+constexpr size_t TKEC_LDS = 2 * TK_TILE_BYTES + TKE_STATS_LDS + tkc_lds_bytes(TK_BU);
+static_assert((2 * TK_TILE_BYTES + TKE_STATS_LDS) % 16 == 0 && TKEC_LDS <= 160 * 1024,
               "the two score tiles and the statistics leave room for one workgroup per CU");
 
 // one wave per target slot: the target's rows of tables 1 ... T - 1 into blocks 1 ... T - 1 of the (T, n_targets, D) gathered
 // workspace (tkc_init_kernel filled block 0 from table 0); zeros for a row outside V
-__global__ __launch_bounds__(64) void tkec_gather_kernel(TkecArgs A) {
+__global__ __launch_bounds__(64) void tkec_gather_kernel(TkWith<TkcArgs, TkeFields> A) {
   const int64_t j = blockIdx.x;
   const int lane = threadIdx.x, t = 1 + (int)blockIdx.y;
   const int64_t row = A.tgt_idx[j];
@@ -1583,7 +1514,7 @@ __global__ __launch_bounds__(64) void tkec_gather_kernel(TkecArgs A) {
 // the gathered rows of tables[t]; the diagonal is the raw score tke_scores_kernel computes for that (user, row), folded with the
 // owner's statistics by the same operations in the same order.  NaN where the owner's statistics cannot standardise: the finish
 // kernel leaves such a slot at rank 0 / -inf.
-__global__ __launch_bounds__(TK_THREADS) void tkec_target_kernel(TkecArgs A) {
+__global__ __launch_bounds__(TK_THREADS) void tkec_target_kernel(TkWith<TkcArgs, TkeFields> A) {
   __shared__ __attribute__((aligned(16))) float sc[TK_BU * TK_SCLD];
   const int tid = threadIdx.x, T = A.T;
   const int64_t j0 = (int64_t)blockIdx.x * TK_BU;
@@ -1599,7 +1530,7 @@ __global__ __launch_bounds__(TK_THREADS) void tkec_target_kernel(TkecArgs A) {
     const float* const pa[1] = {tke_pick(A.users, t) + (int64_t)(ua_ok ? own : 0) * A.D};
     tk_tile_product<1>(pa, ua_ok, A.gathered + (int64_t)t * A.n_targets * A.D, (int)j0, (int)A.n_targets, A.D, sc);
     if (jown >= 0) {
-      const float mean = A.stats[((int64_t)jown * T + t) * 2], sd = A.stats[((int64_t)jown * T + t) * 2 + 1];
+      const float mean = A.out_stats[((int64_t)jown * T + t) * 2], sd = A.out_stats[((int64_t)jown * T + t) * 2 + 1];
       const float w = t == 0 ? A.w[0] : (t == 1 ? A.w[1] : A.w[2]);
       zsum = tke_fold_z(zsum, t == 0, w, sc[tid * TK_SCLD + tid], mean, sd);
       ok = ok && tke_sd_ok(sd);
@@ -1609,47 +1540,11 @@ __global__ __launch_bounds__(TK_THREADS) void tkec_target_kernel(TkecArgs A) {
   if (mine) A.tscore[j0 + tid] = ok ? zsum : __uint_as_float(0x7FC00000u);
 }
 
-__global__ __launch_bounds__(TK_THREADS) void tkec_count_kernel(TkecArgs A) {
+__global__ __launch_bounds__(TK_THREADS) void tkec_count_kernel(TkWith<TkcArgs, TkeFields> A) {
   extern __shared__ __attribute__((aligned(16))) unsigned char tk_smem[];
-  float* const sc = reinterpret_cast<float*>(tk_smem);                       // [TK_BU][TK_SCLD] the raw scores of one table
-  float* const zs = sc + TK_BU * TK_SCLD;                                    // [TK_BU][TK_SCLD] the ensemble scores
-  float* const st = zs + TK_BU * TK_SCLD;                                    // [TK_BU][T][2] mean, sd; sd 0: the user is refused
-  const TkcLds S(tk_smem + 2 * TKC_TILE_BYTES + TKE_STATS_LDS, TK_BU);
-
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int V = A.V, T = A.T;
-  const int sl = (int)(blockIdx.x % (unsigned)A.slices);
-  const int64_t u0 = (int64_t)(blockIdx.x / (unsigned)A.slices) * TK_BU;
-  const int nu = A.B - u0 < TK_BU ? (int)(A.B - u0) : TK_BU;
-  int v_begin, nvt;
-  tkc_slice(A, sl, v_begin, nvt);
-
-  tke_stage_stats(A.stats, u0, nu, T, st);
-  tkc_prologue(A, u0, nu, TK_BU, S);                  // (its barriers also publish `st`)
-
-  const int ul_begin = wave * TK_USERS_PER_WAVE, ul_end = ul_begin + TK_USERS_PER_WAVE < nu ? ul_begin + TK_USERS_PER_WAVE : nu;
-  const int srow = tid >> 2;
-  const bool ua_ok = srow < nu;
-  const int64_t urow = ua_ok ? u0 + srow : A.B - 1;
-  bool nan = false;
-
-  for (int vt = 0; vt < nvt; ++vt) {
-    const int v0 = v_begin + vt * TK_BV;
-    tk_fill_eligible(A.eligible, v0, V, S.el);
-    tke_tile(A.users, A.tables, A.w, T, urow, ua_ok, v0, V, A.D, sc, zs, st);
-
-    const bool e_0 = S.el[lane] != 0, e_1 = S.el[64 + lane] != 0;
-    for (int ul = ul_begin; ul < ul_end; ++ul) {
-      if (st[ul * T * 2 + 1] == 0.f) continue;        // refused: the counters stay 0, so the population comes out 0
-      tkc_count_user(zs + ul * TK_SCLD, S, ul, A.excl_idx, v0, e_0, e_1, lane, nan);
-    }
-    __syncthreads();                                  // the ensemble tile and `el` are free for the next tile
-  }
-
-  if (nan && lane == 0) atomicOr(A.status, NRL_TOPK_E_NAN);
-  wave_lds_sync();
-  for (int ul = ul_begin; ul < ul_end; ++ul) tkc_flush_user(A, S, ul, u0 + ul, sl, lane);
+  TkeProducer P(tk_smem, A);
+  TkCount C(P.rest, TK_BU);
+  tk_walk(A, P, C);
 }
 
 __device__ __forceinline__ int tkc_wave_sum(int v) {
@@ -1891,43 +1786,100 @@ int nrl_catalogue_ranks(const float* user_vec, const float* table, int64_t B, in
   });
 }
 
+// ---- the other scorers: each one's own checks and its fields, written once for its two entries ------------------------------------
+// The order in which an entry's checks fire is part of its contract (a caller sees the first that fails), and a scorer's checks do
+// not all sit together in it: those of its sizes come before tk_check, those of its operands after.  Hence up to two functions
+// per scorer; `who` is the entry's name in the message.
+
+// MINER
+static int tki_check(const char* who, int32_t K, int32_t mode, const float* gate) {
+  NRL_REQUIRE(K >= 1 && K <= NRL_TOPK_MAX_INTERESTS, "%s: K in [1, %d] (got %d)", who, NRL_TOPK_MAX_INTERESTS, K);
+  NRL_REQUIRE(mode >= 0 && mode <= 2, "%s: mode 0 (max), 1 (mean) or 2 (weighted) (got %d)", who, mode);
+  NRL_REQUIRE(mode != 2 || gate, "%s: mode 2 (weighted) needs the gate rows", who);
+  return NRL_OK;
+}
+// Ut = TK_BU / K users per workgroup: the plan of these entries is their own, and never needs more lists (or counts) than the
+// workspace of the plain entries holds for the same sizes (Ut <= TK_BU)
+static TkiFields tki_fields(const float* gate, int32_t K, int32_t mode) { return TkiFields{mode == 2 ? gate : nullptr, K, TK_BU / K, mode}; }
+
+int nrl_topk_interest_scores(const float* interests, const float* gate, const float* table, int64_t B, int32_t K, int64_t V, int32_t D,
+                             int32_t k, int32_t mode, const int64_t* excl_idx, const int64_t* excl_off, const uint8_t* eligible,
+                             int32_t slices, int64_t* out_idx, float* out_score, int32_t* status, void* ws, size_t ws_bytes,
+                             void* stream) {
+  NRL_REQUIRE(B >= 0 && V >= 0 && D >= 0 && slices >= 0, "topk_interest_scores: negative size");
+  NRL_TRY(tki_check("topk_interest_scores", K, mode, gate));
+  NRL_TRY(tk_check("topk_interest_scores", B, V, D, k, excl_idx, excl_off));
+  if (B == 0) return NRL_OK;
+  TkWith<TkArgs, TkiFields> A;
+  static_cast<TkiFields&>(A) = tki_fields(gate, K, mode);
+  unsigned long long* partial;
+  NRL_TRY(carve_workspace(ws, ws_bytes, [&](Arena& a) { tk_layout(a, B, V, k, slices, A.Ut, &partial); }));
+  NRL_REQUIRE(status, "topk_interest_scores: the status word is required");
+  NRL_REQUIRE(out_idx && out_score && interests && (V == 0 || table), "topk_interest_scores: null argument");
+  static_cast<TkArgs&>(A) = tk_args(interests, table, B, V, D, k, excl_idx, excl_off, eligible, partial, out_idx, out_score, status);
+  return mode == 2 ? tk_launch("topk_interest_scores", tki_scores_kernel<true>, A, slices, 2, A.Ut, stream)
+                   : tk_launch("topk_interest_scores", tki_scores_kernel<false>, A, slices, 1, A.Ut, stream);
+}
+
 int nrl_catalogue_interest_ranks(const float* interests, const float* gate, const float* table, int64_t B, int32_t K, int64_t V,
                                  int32_t D, int32_t mode, const int64_t* tgt_idx, const int64_t* tgt_off, int64_t n_targets,
                                  const int64_t* excl_idx, const int64_t* excl_off, const uint8_t* eligible, int32_t slices,
                                  int32_t* out_rank, float* out_score, int32_t* out_ranked, int32_t* status, void* ws,
                                  size_t ws_bytes, void* stream) {
   NRL_REQUIRE(B >= 0 && V >= 0 && D >= 0 && slices >= 0 && n_targets >= 0, "catalogue_interest_ranks: negative size");
-  NRL_REQUIRE(K >= 1 && K <= NRL_TOPK_MAX_INTERESTS, "catalogue_interest_ranks: K in [1, %d] (got %d)", NRL_TOPK_MAX_INTERESTS, K);
-  NRL_REQUIRE(mode >= 0 && mode <= 2, "catalogue_interest_ranks: mode 0 (max), 1 (mean) or 2 (weighted) (got %d)", mode);
-  NRL_REQUIRE(mode != 2 || gate, "catalogue_interest_ranks: mode 2 (weighted) needs the gate rows");
+  NRL_TRY(tki_check("catalogue_interest_ranks", K, mode, gate));
   NRL_TRY(tk_check("catalogue_interest_ranks", B, V, D, 1, excl_idx, excl_off));
   NRL_TRY(tkc_check("catalogue_interest_ranks", n_targets, tgt_idx, tgt_off, status));
   if (B == 0) return NRL_OK;
   NRL_REQUIRE(out_ranked && interests && (V == 0 || table) && (n_targets == 0 || (tgt_idx && out_rank && out_score)),
               "catalogue_interest_ranks: null argument");
-  // the slices of this entry's own plan: never more than nrl_catalogue_ranks_workspace_size(B, V, D, ...) holds (Ut <= TK_BU)
-  const int32_t Ut = TK_BU / K;
-  TkicArgs A;
+  TkWith<TkcArgs, TkiFields> A;
+  static_cast<TkiFields&>(A) = tki_fields(gate, K, mode);
   int64_t blocks;
   NRL_TRY(tkc_prepare("catalogue_interest_ranks", A, interests, table, B, V, D, D, true, tgt_idx, tgt_off, n_targets, excl_idx,
-                      excl_off, eligible, slices, Ut, out_rank, out_score, out_ranked, status, ws, ws_bytes, &blocks));
-  A.gate = mode == 2 ? gate : nullptr;
-  A.K = K;
-  A.Ut = Ut;
-  A.mode = mode;
-  const unsigned tgrid = (unsigned)ceil_div(n_targets, Ut);
+                      excl_off, eligible, slices, A.Ut, out_rank, out_score, out_ranked, status, ws, ws_bytes, &blocks));
+  const unsigned tgrid = (unsigned)ceil_div(n_targets, A.Ut);
   if (mode == 2)
-    return tkc_launch(tkic_count_kernel<true>, A, blocks, tkic_lds_bytes(true, Ut), stream, [&](hipStream_t st) {
+    return tkc_launch(tkic_count_kernel<true>, A, blocks, tkic_lds_bytes(true, A.Ut), stream, [&](hipStream_t st) {
       NRL_HIP(hipFuncSetAttribute((const void*)tkic_target_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-      tkic_target_kernel<true><<<tgrid, TK_THREADS, 2 * TKC_TILE_BYTES, st>>>(A);
+      tkic_target_kernel<true><<<tgrid, TK_THREADS, 2 * TK_TILE_BYTES, st>>>(A);
       NRL_LAUNCH_CHECK();
       return NRL_OK;
     });
-  return tkc_launch(tkic_count_kernel<false>, A, blocks, tkic_lds_bytes(false, Ut), stream, [&](hipStream_t st) {
-    tkic_target_kernel<false><<<tgrid, TK_THREADS, TKC_TILE_BYTES, st>>>(A);
+  return tkc_launch(tkic_count_kernel<false>, A, blocks, tkic_lds_bytes(false, A.Ut), stream, [&](hipStream_t st) {
+    tkic_target_kernel<false><<<tgrid, TK_THREADS, TK_TILE_BYTES, st>>>(A);
     NRL_LAUNCH_CHECK();
     return NRL_OK;
   });
+}
+
+// DKN (no D in its tk_check: Hd takes its place and has its own bounds)
+static int tkr_check_sizes(const char* who, int32_t Hd) {
+  NRL_REQUIRE(Hd >= 1 && Hd <= NRL_TOPK_MAX_HIDDEN, "%s: Hd in [1, %d] (got %d)", who, NRL_TOPK_MAX_HIDDEN, Hd);
+  return NRL_OK;
+}
+static int tkr_check_operands(const char* who, const float* w2, const float* b2) {
+  NRL_REQUIRE(w2, "%s: w2 is required", who);
+  NRL_REQUIRE(b2, "%s: b2 is required (a device pointer)", who);
+  return NRL_OK;
+}
+
+int nrl_topk_relu_scores(const float* q, const float* proj, const float* w2, const float* b2, int64_t B, int64_t V, int32_t Hd,
+                         int32_t k, const int64_t* excl_idx, const int64_t* excl_off, const uint8_t* eligible, int32_t slices,
+                         int64_t* out_idx, float* out_score, int32_t* status, void* ws, size_t ws_bytes, void* stream) {
+  NRL_REQUIRE(B >= 0 && V >= 0 && slices >= 0, "topk_relu_scores: negative size");
+  NRL_TRY(tkr_check_sizes("topk_relu_scores", Hd));
+  NRL_TRY(tk_check("topk_relu_scores", B, V, 4, k, excl_idx, excl_off));
+  NRL_REQUIRE(status, "topk_relu_scores: the status word is required");
+  NRL_TRY(tkr_check_operands("topk_relu_scores", w2, b2));
+  if (B == 0) return NRL_OK;
+  NRL_REQUIRE(out_idx && out_score && q && (V == 0 || proj), "topk_relu_scores: null argument");
+  unsigned long long* partial;
+  NRL_TRY(carve_workspace(ws, ws_bytes, [&](Arena& a) { tk_layout(a, B, V, k, slices, TK_BU, &partial); }));
+  TkWith<TkArgs, TkrFields> A;
+  static_cast<TkArgs&>(A) = tk_args(q, proj, B, V, Hd, k, excl_idx, excl_off, eligible, partial, out_idx, out_score, status);
+  static_cast<TkrFields&>(A) = TkrFields{w2, b2};
+  return tk_launch("topk_relu_scores", tkr_scores_kernel, A, slices, 1, TK_BU, stream, tkr_extra_lds(Hd));
 }
 
 int nrl_catalogue_relu_ranks(const float* q, const float* proj, const float* w2, const float* b2, int64_t B, int64_t V, int32_t Hd,
@@ -1935,21 +1887,19 @@ int nrl_catalogue_relu_ranks(const float* q, const float* proj, const float* w2,
                              const int64_t* excl_off, const uint8_t* eligible, int32_t slices, int32_t* out_rank, float* out_score,
                              int32_t* out_ranked, int32_t* status, void* ws, size_t ws_bytes, void* stream) {
   NRL_REQUIRE(B >= 0 && V >= 0 && slices >= 0 && n_targets >= 0, "catalogue_relu_ranks: negative size");
-  NRL_REQUIRE(Hd >= 1 && Hd <= NRL_TOPK_MAX_HIDDEN, "catalogue_relu_ranks: Hd in [1, %d] (got %d)", NRL_TOPK_MAX_HIDDEN, Hd);
-  NRL_TRY(tk_check("catalogue_relu_ranks", B, V, 4, 1, excl_idx, excl_off));   // (no D here: Hd is checked above)
+  NRL_TRY(tkr_check_sizes("catalogue_relu_ranks", Hd));
+  NRL_TRY(tk_check("catalogue_relu_ranks", B, V, 4, 1, excl_idx, excl_off));
   NRL_TRY(tkc_check("catalogue_relu_ranks", n_targets, tgt_idx, tgt_off, status));
-  NRL_REQUIRE(w2, "catalogue_relu_ranks: w2 is required");
-  NRL_REQUIRE(b2, "catalogue_relu_ranks: b2 is required (a device pointer)");
+  NRL_TRY(tkr_check_operands("catalogue_relu_ranks", w2, b2));
   if (B == 0) return NRL_OK;
   NRL_REQUIRE(out_ranked && q && (V == 0 || proj) && (n_targets == 0 || (tgt_idx && out_rank && out_score)),
               "catalogue_relu_ranks: null argument");
   // the layout of nrl_catalogue_ranks_workspace_size(B, V, 4, ...): nothing is gathered, the target kernel reads proj in place
-  TkrcArgs A;
+  TkWith<TkcArgs, TkrFields> A;
   int64_t blocks;
   NRL_TRY(tkc_prepare("catalogue_relu_ranks", A, q, proj, B, V, Hd, 4, false, tgt_idx, tgt_off, n_targets, excl_idx, excl_off,
                       eligible, slices, TK_BU, out_rank, out_score, out_ranked, status, ws, ws_bytes, &blocks));
-  A.w2 = w2;
-  A.b2 = b2;
+  static_cast<TkrFields&>(A) = TkrFields{w2, b2};
   return tkc_launch(tkrc_count_kernel, A, blocks, tkrc_lds_bytes(Hd), stream, [&](hipStream_t st) {
     tkrc_target_kernel<<<(unsigned)ceil_div(n_targets, 256), 256, 0, st>>>(A);
     NRL_LAUNCH_CHECK();
@@ -1957,28 +1907,53 @@ int nrl_catalogue_relu_ranks(const float* q, const float* proj, const float* w2,
   });
 }
 
+// NPA (no D in its tk_check: F takes its place and has its own bounds)
+static int tkp_check_sizes(const char* who, int32_t L, int32_t F) {
+  NRL_REQUIRE(L >= 1 && L <= NRL_TOPK_MAX_TOKENS, "%s: L in [1, %d] tokens (got %d)", who, NRL_TOPK_MAX_TOKENS, L);
+  NRL_REQUIRE(F >= 4 && F % 4 == 0 && F <= NRL_TOPK_MAX_D, "%s: F a multiple of 4 in [4, %d] (got %d)", who, NRL_TOPK_MAX_D, F);
+  return NRL_OK;
+}
+static int tkp_check_operands(const char* who, const float* q, const float* user, const float* features) {
+  NRL_REQUIRE((((uintptr_t)q | (uintptr_t)user | (uintptr_t)features) & 15) == 0, "%s: q, user and features must be 16-byte aligned", who);
+  return NRL_OK;
+}
+
+int nrl_topk_pooled_scores(const float* q, const float* user, const float* features, int64_t B, int64_t V, int32_t L, int32_t F,
+                           int32_t k, const int64_t* excl_idx, const int64_t* excl_off, const uint8_t* eligible, int32_t slices,
+                           int64_t* out_idx, float* out_score, int32_t* status, void* ws, size_t ws_bytes, void* stream) {
+  NRL_REQUIRE(B >= 0 && V >= 0 && slices >= 0, "topk_pooled_scores: negative size");
+  NRL_TRY(tkp_check_sizes("topk_pooled_scores", L, F));
+  NRL_TRY(tk_check("topk_pooled_scores", B, V, 4, k, excl_idx, excl_off));
+  NRL_REQUIRE(status, "topk_pooled_scores: the status word is required");
+  if (B == 0) return NRL_OK;
+  NRL_REQUIRE(out_idx && out_score && q && user && (V == 0 || features), "topk_pooled_scores: null argument");
+  NRL_TRY(tkp_check_operands("topk_pooled_scores", q, user, features));
+  unsigned long long* partial;
+  NRL_TRY(carve_workspace(ws, ws_bytes, [&](Arena& a) { tk_layout(a, B, V, k, slices, TK_BU, &partial); }));
+  TkWith<TkArgs, TkpFields> A;
+  static_cast<TkArgs&>(A) = tk_args(q, features, B, V, F, k, excl_idx, excl_off, eligible, partial, out_idx, out_score, status);
+  static_cast<TkpFields&>(A) = TkpFields{user, L};
+  return tk_launch("topk_pooled_scores", tkp_scores_kernel, A, slices, 1, TK_BU, stream, TKP_EXTRA_LDS);
+}
+
 int nrl_catalogue_pooled_ranks(const float* q, const float* user, const float* features, int64_t B, int64_t V, int32_t L, int32_t F,
                                const int64_t* tgt_idx, const int64_t* tgt_off, int64_t n_targets, const int64_t* excl_idx,
                                const int64_t* excl_off, const uint8_t* eligible, int32_t slices, int32_t* out_rank, float* out_score,
                                int32_t* out_ranked, int32_t* status, void* ws, size_t ws_bytes, void* stream) {
   NRL_REQUIRE(B >= 0 && V >= 0 && slices >= 0 && n_targets >= 0, "catalogue_pooled_ranks: negative size");
-  NRL_REQUIRE(L >= 1 && L <= NRL_TOPK_MAX_TOKENS, "catalogue_pooled_ranks: L in [1, %d] tokens (got %d)", NRL_TOPK_MAX_TOKENS, L);
-  NRL_REQUIRE(F >= 4 && F % 4 == 0 && F <= NRL_TOPK_MAX_D, "catalogue_pooled_ranks: F a multiple of 4 in [4, %d] (got %d)",
-              NRL_TOPK_MAX_D, F);
-  NRL_TRY(tk_check("catalogue_pooled_ranks", B, V, 4, 1, excl_idx, excl_off));  // (no D here: F is checked above)
+  NRL_TRY(tkp_check_sizes("catalogue_pooled_ranks", L, F));
+  NRL_TRY(tk_check("catalogue_pooled_ranks", B, V, 4, 1, excl_idx, excl_off));
   NRL_TRY(tkc_check("catalogue_pooled_ranks", n_targets, tgt_idx, tgt_off, status));
   if (B == 0) return NRL_OK;
   NRL_REQUIRE(out_ranked && q && user && (V == 0 || features) && (n_targets == 0 || (tgt_idx && out_rank && out_score)),
               "catalogue_pooled_ranks: null argument");
-  NRL_REQUIRE((((uintptr_t)q | (uintptr_t)user | (uintptr_t)features) & 15) == 0,
-              "catalogue_pooled_ranks: q, user and features must be 16-byte aligned");
+  NRL_TRY(tkp_check_operands("catalogue_pooled_ranks", q, user, features));
   // the layout of nrl_catalogue_ranks_workspace_size(B, V, 4, ...): nothing is gathered, the target kernel reads the maps in place
-  TkpcArgs A;
+  TkWith<TkcArgs, TkpFields> A;
   int64_t blocks;
   NRL_TRY(tkc_prepare("catalogue_pooled_ranks", A, q, features, B, V, F, 4, false, tgt_idx, tgt_off, n_targets, excl_idx, excl_off,
                       eligible, slices, TK_BU, out_rank, out_score, out_ranked, status, ws, ws_bytes, &blocks));
-  A.uvec = user;
-  A.L = L;
+  static_cast<TkpFields&>(A) = TkpFields{user, L};
   return tkc_launch(tkpc_count_kernel, A, blocks, TKPC_LDS, stream, [&](hipStream_t st) {
     tkpc_target_kernel<<<(unsigned)ceil_div(n_targets, TK_BU), TK_THREADS, 0, st>>>(A);
     NRL_LAUNCH_CHECK();
@@ -1986,90 +1961,47 @@ int nrl_catalogue_pooled_ranks(const float* q, const float* user, const float* f
   });
 }
 
-int nrl_topk_interest_scores(const float* interests, const float* gate, const float* table, int64_t B, int32_t K, int64_t V, int32_t D,
-                             int32_t k, int32_t mode, const int64_t* excl_idx, const int64_t* excl_off, const uint8_t* eligible,
-                             int32_t slices, int64_t* out_idx, float* out_score, int32_t* status, void* ws, size_t ws_bytes,
-                             void* stream) {
-  NRL_REQUIRE(B >= 0 && V >= 0 && D >= 0 && slices >= 0, "topk_interest_scores: negative size");
-  NRL_REQUIRE(K >= 1 && K <= NRL_TOPK_MAX_INTERESTS, "topk_interest_scores: K in [1, %d] (got %d)", NRL_TOPK_MAX_INTERESTS, K);
-  NRL_REQUIRE(mode >= 0 && mode <= 2, "topk_interest_scores: mode 0 (max), 1 (mean) or 2 (weighted) (got %d)", mode);
-  NRL_REQUIRE(mode != 2 || gate, "topk_interest_scores: mode 2 (weighted) needs the gate rows");
-  NRL_TRY(tk_check("topk_interest_scores", B, V, D, k, excl_idx, excl_off));
-  if (B == 0) return NRL_OK;
-  // the lists of this entry's own plan: never more than nrl_topk_scores_workspace_bytes(B, V, D, k, slices) holds (Ut <= TK_BU)
-  const int32_t Ut = TK_BU / K;
-  unsigned long long* partial;
-  NRL_TRY(carve_workspace(ws, ws_bytes, [&](Arena& a) { tk_layout(a, B, V, k, slices, Ut, &partial); }));
-  NRL_REQUIRE(status, "topk_interest_scores: the status word is required");
-  NRL_REQUIRE(out_idx && out_score && interests && (V == 0 || table), "topk_interest_scores: null argument");
-  TkiArgs A;
-  static_cast<TkArgs&>(A) = tk_args(interests, table, B, V, D, k, excl_idx, excl_off, eligible, partial, out_idx, out_score, status);
-  A.gate = mode == 2 ? gate : nullptr;
-  A.K = K;
-  A.Ut = Ut;
-  A.mode = mode;
-  return mode == 2 ? tk_launch("topk_interest_scores", tki_scores_kernel<true>, A, slices, 2, Ut, stream)
-                   : tk_launch("topk_interest_scores", tki_scores_kernel<false>, A, slices, 1, Ut, stream);
+// MANNeR
+static int tke_check_sizes(const char* who, int32_t T) {
+  NRL_REQUIRE(T >= 1 && T <= NRL_TOPK_MAX_MODELS, "%s: T in [1, %d] sub-models (got %d)", who, NRL_TOPK_MAX_MODELS, T);
+  return NRL_OK;
 }
-
-int nrl_topk_relu_scores(const float* q, const float* proj, const float* w2, const float* b2, int64_t B, int64_t V, int32_t Hd,
-                         int32_t k, const int64_t* excl_idx, const int64_t* excl_off, const uint8_t* eligible, int32_t slices,
-                         int64_t* out_idx, float* out_score, int32_t* status, void* ws, size_t ws_bytes, void* stream) {
-  NRL_REQUIRE(B >= 0 && V >= 0 && slices >= 0, "topk_relu_scores: negative size");
-  NRL_REQUIRE(Hd >= 1 && Hd <= NRL_TOPK_MAX_HIDDEN, "topk_relu_scores: Hd in [1, %d] (got %d)", NRL_TOPK_MAX_HIDDEN, Hd);
-  NRL_TRY(tk_check("topk_relu_scores", B, V, 4, k, excl_idx, excl_off));      // (no D here: Hd is checked above)
-  NRL_REQUIRE(status, "topk_relu_scores: the status word is required");
-  NRL_REQUIRE(w2, "topk_relu_scores: w2 is required");
-  NRL_REQUIRE(b2, "topk_relu_scores: b2 is required (a device pointer)");
-  if (B == 0) return NRL_OK;
-  NRL_REQUIRE(out_idx && out_score && q && (V == 0 || proj), "topk_relu_scores: null argument");
-  unsigned long long* partial;
-  NRL_TRY(carve_workspace(ws, ws_bytes, [&](Arena& a) { tk_layout(a, B, V, k, slices, TK_BU, &partial); }));
-  TkrArgs A;
-  static_cast<TkArgs&>(A) = tk_args(q, proj, B, V, Hd, k, excl_idx, excl_off, eligible, partial, out_idx, out_score, status);
-  A.w2 = w2;
-  A.b2 = b2;
-  return tk_launch("topk_relu_scores", tkr_scores_kernel, A, slices, 1, TK_BU, stream, tkr_extra_lds(Hd));
-}
-
-int nrl_topk_pooled_scores(const float* q, const float* user, const float* features, int64_t B, int64_t V, int32_t L, int32_t F,
-                           int32_t k, const int64_t* excl_idx, const int64_t* excl_off, const uint8_t* eligible, int32_t slices,
-                           int64_t* out_idx, float* out_score, int32_t* status, void* ws, size_t ws_bytes, void* stream) {
-  NRL_REQUIRE(B >= 0 && V >= 0 && slices >= 0, "topk_pooled_scores: negative size");
-  NRL_REQUIRE(L >= 1 && L <= NRL_TOPK_MAX_TOKENS, "topk_pooled_scores: L in [1, %d] tokens (got %d)", NRL_TOPK_MAX_TOKENS, L);
-  NRL_REQUIRE(F >= 4 && F % 4 == 0 && F <= NRL_TOPK_MAX_D, "topk_pooled_scores: F a multiple of 4 in [4, %d] (got %d)",
-              NRL_TOPK_MAX_D, F);
-  NRL_TRY(tk_check("topk_pooled_scores", B, V, 4, k, excl_idx, excl_off));    // (no D here: F is checked above)
-  NRL_REQUIRE(status, "topk_pooled_scores: the status word is required");
-  if (B == 0) return NRL_OK;
-  NRL_REQUIRE(out_idx && out_score && q && user && (V == 0 || features), "topk_pooled_scores: null argument");
-  NRL_REQUIRE((((uintptr_t)q | (uintptr_t)user | (uintptr_t)features) & 15) == 0,
-              "topk_pooled_scores: q, user and features must be 16-byte aligned");
-  unsigned long long* partial;
-  NRL_TRY(carve_workspace(ws, ws_bytes, [&](Arena& a) { tk_layout(a, B, V, k, slices, TK_BU, &partial); }));
-  TkpArgs A;
-  static_cast<TkArgs&>(A) = tk_args(q, features, B, V, F, k, excl_idx, excl_off, eligible, partial, out_idx, out_score, status);
-  A.uvec = user;
-  A.L = L;
-  return tk_launch("topk_pooled_scores", tkp_scores_kernel, A, slices, 1, TK_BU, stream, TKP_EXTRA_LDS);
-}
-
-// The checks both ensemble entries make after the shape checks, in this order; `who` is the entry's name in the message
-static int tke_check(const char* who, const float* const* users, const float* const* tables, const float* weights, int32_t T,
-                     int64_t V) {
+static int tke_check_operands(const char* who, const float* const* users, const float* const* tables, const float* weights, int32_t T,
+                              int64_t V) {
   NRL_REQUIRE(users && tables && weights, "%s: null users / tables / weights array", who);
   for (int t = 0; t < T; ++t) NRL_REQUIRE(users[t] && (V == 0 || tables[t]), "%s: null user matrix or table of sub-model %d", who, t);
   return NRL_OK;
 }
+static int tke_check_stats(const char* who, const float* out_stats, const float* moments) {
+  NRL_REQUIRE(out_stats && moments, "%s: out_stats and the moments scratch are required", who);
+  return NRL_OK;
+}
+// (the statistics pass sets the two chunk fields)
+static TkeFields tke_fields(const float* const* users, const float* const* tables, const float* weights, int32_t T, float* out_stats,
+                            float* moments) {
+  TkeFields E;
+  for (int t = 0; t < NRL_TOPK_MAX_MODELS; ++t) {
+    E.users[t] = users[t < T ? t : 0];
+    E.tables[t] = tables[t < T ? t : 0];
+    E.w[t] = t < T ? weights[t] : 0.f;
+  }
+  E.T = T;
+  E.chunks = E.tiles_per_chunk = 0;
+  E.out_stats = out_stats;
+  E.moments = moments;
+  return E;
+}
 
-// The statistics pass of both ensemble entries: plans the chunks and runs tke_stats_kernel and tke_finish_kernel over them
-static int tke_statistics(const char* who, TkeArgs& A, void* stream) {
+// The statistics pass of both ensemble entries: plans the chunks (into E, which the entry's walk kernel is then handed) and runs
+// tke_stats_kernel and tke_finish_kernel over them
+static int tke_statistics(const char* who, const TkArgs& base, TkeFields& E, void* stream) {
   // the statistics chunks: a function of V alone, so that the order of every reduction is
-  const int64_t nvt = ceil_div((int64_t)A.V, TK_BV);
-  A.tiles_per_chunk = (int32_t)(nvt > 0 ? ceil_div(nvt, NRL_TOPK_STAT_CHUNKS) : 1);
-  A.chunks = (int32_t)(nvt > 0 ? ceil_div(nvt, A.tiles_per_chunk) : 0);
-  const int64_t blocks = ceil_div(A.B, TK_BU) * A.chunks;
+  const int64_t nvt = ceil_div((int64_t)base.V, TK_BV);
+  E.tiles_per_chunk = (int32_t)(nvt > 0 ? ceil_div(nvt, NRL_TOPK_STAT_CHUNKS) : 1);
+  E.chunks = (int32_t)(nvt > 0 ? ceil_div(nvt, E.tiles_per_chunk) : 0);
+  const int64_t blocks = ceil_div(base.B, TK_BU) * E.chunks;
   NRL_REQUIRE(blocks < ((int64_t)1 << 31), "%s: grid too large (%lld workgroups)", who, (long long)blocks);
+  const TkWith<TkArgs, TkeFields> A{base, E};
   hipStream_t st = (hipStream_t)stream;
   if (blocks > 0) {
     tke_stats_kernel<<<(unsigned)blocks, TK_THREADS, 0, st>>>(A);
@@ -2085,26 +2017,19 @@ int nrl_topk_ensemble_scores(const float* const* users, const float* const* tabl
                              const uint8_t* eligible, int32_t slices, int64_t* out_idx, float* out_score, float* out_stats,
                              float* moments, int32_t* status, void* ws, size_t ws_bytes, void* stream) {
   NRL_REQUIRE(B >= 0 && V >= 0 && D >= 0 && slices >= 0, "topk_ensemble_scores: negative size");
-  NRL_REQUIRE(T >= 1 && T <= NRL_TOPK_MAX_MODELS, "topk_ensemble_scores: T in [1, %d] sub-models (got %d)", NRL_TOPK_MAX_MODELS, T);
+  NRL_TRY(tke_check_sizes("topk_ensemble_scores", T));
   NRL_TRY(tk_check("topk_ensemble_scores", B, V, D, k, excl_idx, excl_off));
-  NRL_TRY(tke_check("topk_ensemble_scores", users, tables, weights, T, V));
+  NRL_TRY(tke_check_operands("topk_ensemble_scores", users, tables, weights, T, V));
   NRL_REQUIRE(status, "topk_ensemble_scores: the status word is required");
-  NRL_REQUIRE(out_stats && moments, "topk_ensemble_scores: out_stats and the moments scratch are required");
+  NRL_TRY(tke_check_stats("topk_ensemble_scores", out_stats, moments));
   if (B == 0) return NRL_OK;
   NRL_REQUIRE(out_idx && out_score, "topk_ensemble_scores: null argument");
   unsigned long long* partial;
   NRL_TRY(carve_workspace(ws, ws_bytes, [&](Arena& a) { tk_layout(a, B, V, k, slices, TK_BU, &partial); }));
-  TkeArgs A;
+  TkWith<TkArgs, TkeFields> A;
   static_cast<TkArgs&>(A) = tk_args(users[0], tables[0], B, V, D, k, excl_idx, excl_off, eligible, partial, out_idx, out_score, status);
-  for (int t = 0; t < NRL_TOPK_MAX_MODELS; ++t) {
-    A.users[t] = users[t < T ? t : 0];
-    A.tables[t] = tables[t < T ? t : 0];
-    A.w[t] = t < T ? weights[t] : 0.f;
-  }
-  A.T = T;
-  A.out_stats = out_stats;
-  A.moments = moments;
-  NRL_TRY(tke_statistics("topk_ensemble_scores", A, stream));
+  static_cast<TkeFields&>(A) = tke_fields(users, tables, weights, T, out_stats, moments);
+  NRL_TRY(tke_statistics("topk_ensemble_scores", A, A, stream));
   return tk_launch("topk_ensemble_scores", tke_scores_kernel, A, slices, 2, TK_BU, stream, (size_t)TK_BU * T * 2 * 4);
 }
 
@@ -2120,29 +2045,20 @@ int nrl_catalogue_ensemble_ranks(const float* const* users, const float* const* 
                                  int32_t* out_rank, float* out_score, int32_t* out_ranked, float* out_stats, float* moments,
                                  int32_t* status, void* ws, size_t ws_bytes, void* stream) {
   NRL_REQUIRE(B >= 0 && V >= 0 && D >= 0 && slices >= 0 && n_targets >= 0, "catalogue_ensemble_ranks: negative size");
-  NRL_REQUIRE(T >= 1 && T <= NRL_TOPK_MAX_MODELS, "catalogue_ensemble_ranks: T in [1, %d] sub-models (got %d)", NRL_TOPK_MAX_MODELS, T);
+  NRL_TRY(tke_check_sizes("catalogue_ensemble_ranks", T));
   NRL_TRY(tk_check("catalogue_ensemble_ranks", B, V, D, 1, excl_idx, excl_off));
   NRL_TRY(tkc_check("catalogue_ensemble_ranks", n_targets, tgt_idx, tgt_off, status));
-  NRL_TRY(tke_check("catalogue_ensemble_ranks", users, tables, weights, T, V));
-  NRL_REQUIRE(out_stats && moments, "catalogue_ensemble_ranks: out_stats and the moments scratch are required");
+  NRL_TRY(tke_check_operands("catalogue_ensemble_ranks", users, tables, weights, T, V));
+  NRL_TRY(tke_check_stats("catalogue_ensemble_ranks", out_stats, moments));
   if (B == 0) return NRL_OK;
   NRL_REQUIRE(out_ranked && (n_targets == 0 || (tgt_idx && out_rank && out_score)), "catalogue_ensemble_ranks: null argument");
   // the layout of nrl_catalogue_ranks with T gathered blocks: (T, n_targets, D)
-  TkecArgs A;
+  TkWith<TkcArgs, TkeFields> A;
   int64_t blocks;
   NRL_TRY(tkc_prepare("catalogue_ensemble_ranks", A, users[0], tables[0], B, V, D, T * D, true, tgt_idx, tgt_off, n_targets, excl_idx,
                       excl_off, eligible, slices, TK_BU, out_rank, out_score, out_ranked, status, ws, ws_bytes, &blocks));
-  TkeArgs E;                                          // what the statistics kernels read: the fields of nrl_topk_ensemble_scores
-  static_cast<TkArgs&>(E) = static_cast<const TkArgs&>(A);
-  for (int t = 0; t < NRL_TOPK_MAX_MODELS; ++t) {
-    A.users[t] = E.users[t] = users[t < T ? t : 0];
-    A.tables[t] = E.tables[t] = tables[t < T ? t : 0];
-    A.w[t] = E.w[t] = t < T ? weights[t] : 0.f;
-  }
-  A.T = E.T = T;
-  A.stats = E.out_stats = out_stats;
-  E.moments = moments;
-  NRL_TRY(tke_statistics("catalogue_ensemble_ranks", E, stream));
+  static_cast<TkeFields&>(A) = tke_fields(users, tables, weights, T, out_stats, moments);
+  NRL_TRY(tke_statistics("catalogue_ensemble_ranks", A, A, stream));
   return tkc_launch(tkec_count_kernel, A, blocks, TKEC_LDS, stream, [&](hipStream_t st) {
     if (T > 1) {
       tkec_gather_kernel<<<dim3((unsigned)n_targets, (unsigned)(T - 1)), 64, 0, st>>>(A);

@@ -167,6 +167,21 @@ def _click_offsets(cs: torch.Tensor, dev) -> torch.Tensor:
     return torch.cat([torch.zeros(1, dtype=torch.int64), torch.cumsum(cs, 0)]).pin_memory().to(dev, non_blocking=True)
 
 
+def _catalogue_side(who: str, cache, hist_idx, hist_sizes, eligible, clicks):
+    """The caller's side of a whole-table method ``who``, checked and moved to the device of ``cache``'s table (which is not
+    touched before every check has passed).  ``clicks`` None (a ``recommend*``): ``hist_idx`` must live on the GPU; ``clicks``
+    (click_idx, click_sizes) (a ``rank_clicks*``): the checks of ``_click_sizes`` -> (hist_idx int64, eligible or None, the click
+    lists as ``ops.catalogue_*ranks`` take them: (click_idx, click_off), or ())."""
+    if clicks is None:
+        if not hist_idx.is_cuda:
+            raise RuntimeError(f"newsreclib_amd: `hist_idx` must live on the GPU (got {hist_idx.device}); there is no CPU path")
+    else:
+        cs = _click_sizes(who, hist_idx, hist_sizes, *clicks)
+    dev = cache.table.device
+    targets = () if clicks is None else (clicks[0].to(dev).long(), _click_offsets(cs, dev))
+    return hist_idx.to(dev).long(), eligible.to(dev) if eligible is not None else None, targets
+
+
 class NewsVectorCache(_ImpressionCache):
     """Encode-once evaluation of a drop-in recommender (any of the module mirrors: NRMS, LSTUR, NAML, TANR,
     CenNewsRec, MINS -- whatever exposes ``news_encoder`` and ``score_news_vectors``)."""
@@ -239,6 +254,75 @@ class NewsVectorCache(_ImpressionCache):
             "user_idx": up(user_idx) if user_idx is not None else ar.clone(),
         }
 
+    # ---- ranking the whole table: each scorer's user side, written once for its `recommend*` and its `rank_clicks*` ----
+    def _history(self, who: str, hist_idx, hist_sizes, user_idx, exclude_history: bool, eligible, clicks):
+        """What every whole-table method ``who`` does before its scorer's own user side: the caller's side of the call checked
+        and on the device (``_catalogue_side``), the table built when it is missing -> (the gathered history vectors, the
+        history meta, the click lists ``_catalogue_side`` returns, the (excl_idx, excl_off, eligible) every ``ops`` entry ends
+        with)."""
+        hist_idx, eligible, targets = _catalogue_side(who, self, hist_idx, hist_sizes, eligible, clicks)
+        if self.vectors is None:
+            self.build()
+        meta = self._user_meta(hist_sizes, user_idx)
+        hv = ops.embedding_gather(self.vectors, hist_idx.reshape(-1, 1)).reshape(-1, self.vectors.shape[1])
+        excl = (hist_idx, meta["hist_offsets"]) if exclude_history else (None, None)
+        return hv, meta, targets, (*excl, eligible)
+
+    def _dot_users(self, verb: str, *side):
+        """The user side of ``recommend`` / ``rank_clicks`` (``verb``): the refusal, then the module's ``user_vectors`` (eval mode)
+        -> (user (B, D), click lists, (excl_idx, excl_off, eligible))."""
+        if not getattr(self.module, "dot_product_scorer", False):
+            raise NotImplementedError(
+                f"{type(self.module).__name__} does not score a news by one dot product with a candidate-independent user vector "
+                "(no `dot_product_scorer`): " + {
+                    "recommend":
+                        "its user representation or its predictor depends on the candidate (MINER's "
+                        "poly-attention scores, CAUM's candidate-aware encoder, DKN's DNN predictor, SentiDebias' generator), so "
+                        "the whole table cannot be ranked by one GEMM + top-k; MINER is served by `recommend_interests`, DKN (whose "
+                        "user vector does not depend on the candidate and whose DNN factors) by `recommend_dnn`",
+                    "rank_clicks":
+                        "only the dot-product families are served by `rank_clicks`; MINER is served by `rank_clicks_interests`, "
+                        "DKN (whose user vector does not depend on the candidate and whose DNN factors) by `rank_clicks_dnn`",
+                }[verb])
+        hv, meta, targets, tail = self._history(verb, *side)
+        with eval_mode(self.module):
+            user = self.module.user_vectors(hv, meta)
+        return user, targets, tail
+
+    def _interest_users(self, verb: str, bias, *side):
+        """The user side of ``recommend_interests`` / ``rank_clicks_interests``: the refusal, then the module's ``user_interests``
+        (eval mode) -> (interests, gate, click lists, (excl_idx, excl_off, eligible))."""
+        if not getattr(self.module, "multi_interest_scorer", False):
+            raise NotImplementedError(
+                f"{type(self.module).__name__} has no candidate-independent interest vectors (no `multi_interest_scorer`); a "
+                f"module that scores by one dot product with a user vector (`dot_product_scorer`) is served by `{verb}`")
+        hv, meta, targets, tail = self._history(verb + "_interests", *side)
+        with eval_mode(self.module):
+            interests, gate = self.module.user_interests(hv, meta, bias=bias.to(self.table.device) if bias is not None else None)
+        return interests, gate, targets, tail
+
+    def _dnn_users(self, verb: str, *side):
+        """The user side of ``recommend_dnn`` / ``rank_clicks_dnn``: the refusal, then under late fusion the history mean against
+        ``vectors``, under early fusion the module's ``user_queries`` (eval mode) against ``projection``, built when it is missing
+        -> (late fusion?, the scorer's leading ``ops`` arguments: (user, vectors) or (q, projection, w2, b2), click lists,
+        (excl_idx, excl_off, eligible))."""
+        if not getattr(self.module, "dnn_predictor_scorer", False):
+            raise NotImplementedError(
+                f"{type(self.module).__name__} has no DNN click predictor over a candidate-independent user vector (no "
+                "`dnn_predictor_scorer`); a module that scores by one dot product with a user vector (`dot_product_scorer`) is "
+                f"served by `{verb}`, one with interest vectors (`multi_interest_scorer`) by `{verb}_interests`")
+        hv, meta, targets, tail = self._history(verb + "_dnn", *side)
+        if self.module.hparams.late_fusion:
+            dense = dense_rows(hv, meta["batch_hist"], meta["batch_size"], meta["max_hist"], meta["hist_offsets"])
+            return True, (ops.HistMeanFn.apply(dense, meta["hist_offsets"]), self.vectors), targets, tail
+        from . import ops_dkn
+        pred = self.module.click_predictor.params()
+        if self.projection is None:
+            self.projection = ops_dkn.dkn_cand_project(self.vectors, pred)
+        with eval_mode(self.module):
+            _, q = self.module.user_queries(hv, meta)
+        return False, (q, self.projection, pred[2], pred[3]), targets, tail
+
     @torch.no_grad()
     def recommend(self, hist_idx: torch.Tensor, hist_sizes: torch.Tensor, k: int, user_idx: Optional[torch.Tensor] = None,
                   exclude_history: bool = True, eligible: Optional[torch.Tensor] = None):
@@ -248,26 +332,8 @@ class NewsVectorCache(_ImpressionCache):
         ``eligible`` (num_news, uint8 / bool: 0 = never recommended, e.g. the padding row 0).  Slots beyond the rows that
         qualify hold ``-1`` / ``-inf``; ``status`` (``ops.TOPK_FLAGS``) stays on the device.  ``hist_idx`` is a GPU tensor (the
         library has no CPU path), ``hist_sizes`` a HOST tensor as ``evaluate_impressions`` builds it: nothing is read back."""
-        if not getattr(self.module, "dot_product_scorer", False):
-            raise NotImplementedError(
-                f"{type(self.module).__name__} does not score a news by one dot product with a candidate-independent user vector "
-                "(no `dot_product_scorer`): its user representation or its predictor depends on the candidate (MINER's "
-                "poly-attention scores, CAUM's candidate-aware encoder, DKN's DNN predictor, SentiDebias' generator), so "
-                "the whole table cannot be ranked by one GEMM + top-k; MINER is served by `recommend_interests`, DKN (whose "
-                "user vector does not depend on the candidate and whose DNN factors) by `recommend_dnn`")
-        if not hist_idx.is_cuda:
-            raise RuntimeError(f"newsreclib_amd: `hist_idx` must live on the GPU (got {hist_idx.device}); there is no CPU path")
-        if self.vectors is None:
-            self.build()
-        dev = self.table.device
-        hist_idx = hist_idx.to(dev).long()
-        meta = self._user_meta(hist_sizes, user_idx)
-        hv = ops.embedding_gather(self.vectors, hist_idx.reshape(-1, 1)).reshape(-1, self.vectors.shape[1])
-        with eval_mode(self.module):
-            user = self.module.user_vectors(hv, meta)
-        excl = (hist_idx, meta["hist_offsets"]) if exclude_history else (None, None)
-        return ops.topk_scores(user, self.vectors, k, excl[0], excl[1], eligible.to(dev) if eligible is not None else None)
-
+        user, _, tail = self._dot_users("recommend", hist_idx, hist_sizes, user_idx, exclude_history, eligible, None)
+        return ops.topk_scores(user, self.vectors, k, *tail)
 
     @torch.no_grad()
     def rank_clicks(self, hist_idx: torch.Tensor, hist_sizes: torch.Tensor, click_idx: torch.Tensor, click_sizes: torch.Tensor,
@@ -281,32 +347,9 @@ class NewsVectorCache(_ImpressionCache):
         ``ops.RANK_MAX_TARGETS`` clicks per user (``ValueError`` otherwise, from the host sizes).  Same contract as ``recommend``:
         ``hist_idx`` and ``click_idx`` on the GPU, ``hist_sizes`` and ``click_sizes`` on the host, nothing read back; ``status``
         (``ops.RANK_FLAGS``) stays on the device.  ``metrics.full_rank_metrics`` turns the result into MRR / nDCG@k / recall@k."""
-        if not getattr(self.module, "dot_product_scorer", False):
-            raise NotImplementedError(
-                f"{type(self.module).__name__} does not score a news by one dot product with a candidate-independent user vector "
-                "(no `dot_product_scorer`): only the dot-product families are served by `rank_clicks` so far; the count stage is "
-                "not yet wired under the MINER, DKN and NPA scorers")
-        if not hist_idx.is_cuda or not click_idx.is_cuda:
-            raise RuntimeError(f"newsreclib_amd: `hist_idx` and `click_idx` must live on the GPU (got {hist_idx.device} and "
-                               f"{click_idx.device}); there is no CPU path")
-        cs = click_sizes.detach().cpu().long()              # host sizes: the limit and the offsets cost no read-back
-        if cs.numel() != int(hist_sizes.numel()):
-            raise ValueError("newsreclib_amd: hist_sizes and click_sizes must have one entry per user")
-        if cs.numel() and int(cs.max()) > ops.RANK_MAX_TARGETS:
-            raise ValueError(f"newsreclib_amd: rank_clicks takes at most {ops.RANK_MAX_TARGETS} clicks per user "
-                             f"(got {int(cs.max())})")
-        if self.vectors is None:
-            self.build()
-        dev = self.table.device
-        hist_idx, click_idx = hist_idx.to(dev).long(), click_idx.to(dev).long()
-        meta = self._user_meta(hist_sizes, user_idx)
-        click_off = torch.cat([torch.zeros(1, dtype=torch.int64), torch.cumsum(cs, 0)]).pin_memory().to(dev, non_blocking=True)
-        hv = ops.embedding_gather(self.vectors, hist_idx.reshape(-1, 1)).reshape(-1, self.vectors.shape[1])
-        with eval_mode(self.module):
-            user = self.module.user_vectors(hv, meta)
-        excl = (hist_idx, meta["hist_offsets"]) if exclude_history else (None, None)
-        return ops.catalogue_ranks(user, self.vectors, click_idx, click_off, excl[0], excl[1],
-                                   eligible.to(dev) if eligible is not None else None)
+        user, targets, tail = self._dot_users("rank_clicks",
+                                              hist_idx, hist_sizes, user_idx, exclude_history, eligible, (click_idx, click_sizes))
+        return ops.catalogue_ranks(user, self.vectors, *targets, *tail)
 
     @torch.no_grad()
     def recommend_interests(self, hist_idx: torch.Tensor, hist_sizes: torch.Tensor, k: int, user_idx: Optional[torch.Tensor] = None,
@@ -319,23 +362,9 @@ class NewsVectorCache(_ImpressionCache):
         cached table.  Same contract as ``recommend``: ``hist_idx`` on the GPU, ``hist_sizes`` on the host, nothing read back.
         MINER's category bias needs the batch's candidate lists and is left out (``MINERModule.user_interests``); ``bias``
         (n_hist) passes a per-history-row bias of the caller's own."""
-        if not getattr(self.module, "multi_interest_scorer", False):
-            raise NotImplementedError(
-                f"{type(self.module).__name__} has no candidate-independent interest vectors (no `multi_interest_scorer`); a "
-                "module that scores by one dot product with a user vector (`dot_product_scorer`) is served by `recommend`")
-        if not hist_idx.is_cuda:
-            raise RuntimeError(f"newsreclib_amd: `hist_idx` must live on the GPU (got {hist_idx.device}); there is no CPU path")
-        if self.vectors is None:
-            self.build()
-        dev = self.table.device
-        hist_idx = hist_idx.to(dev).long()
-        meta = self._user_meta(hist_sizes, user_idx)
-        hv = ops.embedding_gather(self.vectors, hist_idx.reshape(-1, 1)).reshape(-1, self.vectors.shape[1])
-        with eval_mode(self.module):
-            interests, gate = self.module.user_interests(hv, meta, bias=bias.to(dev) if bias is not None else None)
-        excl = (hist_idx, meta["hist_offsets"]) if exclude_history else (None, None)
-        return ops.topk_interest_scores(interests, self.vectors, k, self.module.interest_score_mode, gate, excl[0], excl[1],
-                                        eligible.to(dev) if eligible is not None else None)
+        interests, gate, _, tail = self._interest_users("recommend", bias,
+                                                        hist_idx, hist_sizes, user_idx, exclude_history, eligible, None)
+        return ops.topk_interest_scores(interests, self.vectors, k, self.module.interest_score_mode, gate, *tail)
 
     @torch.no_grad()
     def recommend_dnn(self, hist_idx: torch.Tensor, hist_sizes: torch.Tensor, k: int, user_idx: Optional[torch.Tensor] = None,
@@ -349,32 +378,8 @@ class NewsVectorCache(_ImpressionCache):
         them).  ``w2``, ``b2`` and the user half are read from the module at every call.  Late fusion (a dot product with the
         history mean): ``ops.topk_scores`` against ``vectors``.  Same contract as ``recommend``: ``hist_idx`` on the GPU,
         ``hist_sizes`` on the host, nothing read back."""
-        if not getattr(self.module, "dnn_predictor_scorer", False):
-            raise NotImplementedError(
-                f"{type(self.module).__name__} has no DNN click predictor over a candidate-independent user vector (no "
-                "`dnn_predictor_scorer`); a module that scores by one dot product with a user vector (`dot_product_scorer`) is "
-                "served by `recommend`, one with interest vectors (`multi_interest_scorer`) by `recommend_interests`")
-        if not hist_idx.is_cuda:
-            raise RuntimeError(f"newsreclib_amd: `hist_idx` must live on the GPU (got {hist_idx.device}); there is no CPU path")
-        if self.vectors is None:
-            self.build()
-        dev = self.table.device
-        hist_idx = hist_idx.to(dev).long()
-        meta = self._user_meta(hist_sizes, user_idx)
-        hv = ops.embedding_gather(self.vectors, hist_idx.reshape(-1, 1)).reshape(-1, self.vectors.shape[1])
-        excl = (hist_idx, meta["hist_offsets"]) if exclude_history else (None, None)
-        eligible = eligible.to(dev) if eligible is not None else None
-        if self.module.hparams.late_fusion:
-            dense = dense_rows(hv, meta["batch_hist"], meta["batch_size"], meta["max_hist"], meta["hist_offsets"])
-            user = ops.HistMeanFn.apply(dense, meta["hist_offsets"])
-            return ops.topk_scores(user, self.vectors, k, excl[0], excl[1], eligible)
-        from . import ops_dkn
-        pred = self.module.click_predictor.params()
-        if self.projection is None:
-            self.projection = ops_dkn.dkn_cand_project(self.vectors, pred)
-        with eval_mode(self.module):
-            _, q = self.module.user_queries(hv, meta)
-        return ops.topk_relu_scores(q, self.projection, pred[2], pred[3], k, excl[0], excl[1], eligible)
+        late, scorer, _, tail = self._dnn_users("recommend", hist_idx, hist_sizes, user_idx, exclude_history, eligible, None)
+        return (ops.topk_scores if late else ops.topk_relu_scores)(*scorer, k, *tail)
 
     @torch.no_grad()
     def rank_clicks_interests(self, hist_idx: torch.Tensor, hist_sizes: torch.Tensor, click_idx: torch.Tensor,
@@ -385,22 +390,9 @@ class NewsVectorCache(_ImpressionCache):
         history and ``eligible``, with ``ops.catalogue_interest_ranks`` counting where ``recommend_interests`` selects: ``rank <=
         k`` exactly when the click is slot ``rank - 1`` of ``recommend_interests(k)``.  The click side is that of ``rank_clicks``
         (host ``click_sizes``, at most ``ops.RANK_MAX_TARGETS`` a user, nothing read back)."""
-        if not getattr(self.module, "multi_interest_scorer", False):
-            raise NotImplementedError(
-                f"{type(self.module).__name__} has no candidate-independent interest vectors (no `multi_interest_scorer`); a "
-                "module that scores by one dot product with a user vector (`dot_product_scorer`) is served by `rank_clicks`")
-        cs = _click_sizes("rank_clicks_interests", hist_idx, hist_sizes, click_idx, click_sizes)
-        if self.vectors is None:
-            self.build()
-        dev = self.table.device
-        hist_idx, click_idx, click_off = hist_idx.to(dev).long(), click_idx.to(dev).long(), _click_offsets(cs, dev)
-        meta = self._user_meta(hist_sizes, user_idx)
-        hv = ops.embedding_gather(self.vectors, hist_idx.reshape(-1, 1)).reshape(-1, self.vectors.shape[1])
-        with eval_mode(self.module):
-            interests, gate = self.module.user_interests(hv, meta, bias=bias.to(dev) if bias is not None else None)
-        excl = (hist_idx, meta["hist_offsets"]) if exclude_history else (None, None)
-        return ops.catalogue_interest_ranks(interests, self.vectors, click_idx, click_off, self.module.interest_score_mode, gate,
-                                            excl[0], excl[1], eligible.to(dev) if eligible is not None else None)
+        interests, gate, targets, tail = self._interest_users(
+            "rank_clicks", bias, hist_idx, hist_sizes, user_idx, exclude_history, eligible, (click_idx, click_sizes))
+        return ops.catalogue_interest_ranks(interests, self.vectors, *targets, self.module.interest_score_mode, gate, *tail)
 
     @torch.no_grad()
     def rank_clicks_dnn(self, hist_idx: torch.Tensor, hist_sizes: torch.Tensor, click_idx: torch.Tensor, click_sizes: torch.Tensor,
@@ -412,31 +404,9 @@ class NewsVectorCache(_ImpressionCache):
         ``ops.catalogue_relu_ranks`` (late fusion: ``ops.catalogue_ranks``) counting where ``recommend_dnn`` selects: ``rank <= k``
         exactly when the click is slot ``rank - 1`` of ``recommend_dnn(k)``.  The click side is that of ``rank_clicks`` (host
         ``click_sizes``, at most ``ops.RANK_MAX_TARGETS`` a user, nothing read back)."""
-        if not getattr(self.module, "dnn_predictor_scorer", False):
-            raise NotImplementedError(
-                f"{type(self.module).__name__} has no DNN click predictor over a candidate-independent user vector (no "
-                "`dnn_predictor_scorer`); a module that scores by one dot product with a user vector (`dot_product_scorer`) is "
-                "served by `rank_clicks`, one with interest vectors (`multi_interest_scorer`) by `rank_clicks_interests`")
-        cs = _click_sizes("rank_clicks_dnn", hist_idx, hist_sizes, click_idx, click_sizes)
-        if self.vectors is None:
-            self.build()
-        dev = self.table.device
-        hist_idx, click_idx, click_off = hist_idx.to(dev).long(), click_idx.to(dev).long(), _click_offsets(cs, dev)
-        meta = self._user_meta(hist_sizes, user_idx)
-        hv = ops.embedding_gather(self.vectors, hist_idx.reshape(-1, 1)).reshape(-1, self.vectors.shape[1])
-        excl = (hist_idx, meta["hist_offsets"]) if exclude_history else (None, None)
-        eligible = eligible.to(dev) if eligible is not None else None
-        if self.module.hparams.late_fusion:
-            dense = dense_rows(hv, meta["batch_hist"], meta["batch_size"], meta["max_hist"], meta["hist_offsets"])
-            user = ops.HistMeanFn.apply(dense, meta["hist_offsets"])
-            return ops.catalogue_ranks(user, self.vectors, click_idx, click_off, excl[0], excl[1], eligible)
-        from . import ops_dkn
-        pred = self.module.click_predictor.params()
-        if self.projection is None:
-            self.projection = ops_dkn.dkn_cand_project(self.vectors, pred)
-        with eval_mode(self.module):
-            _, q = self.module.user_queries(hv, meta)
-        return ops.catalogue_relu_ranks(q, self.projection, pred[2], pred[3], click_idx, click_off, excl[0], excl[1], eligible)
+        late, scorer, targets, tail = self._dnn_users("rank_clicks",
+                                                      hist_idx, hist_sizes, user_idx, exclude_history, eligible, (click_idx, click_sizes))
+        return (ops.catalogue_ranks if late else ops.catalogue_relu_ranks)(*scorer, *targets, *tail)
 
 
 class MannerVectorCache(_ImpressionCache):
@@ -501,29 +471,27 @@ class MannerVectorCache(_ImpressionCache):
         the gathered history rows of that sub-model's table, as in ``scores``; an empty history gives a NaN vector and that user
         is refused through ``status`` (``ops.TOPK_FLAGS``), as is any user whose scores cannot be standardised.  Same contract as
         ``NewsVectorCache.recommend``: ``hist_idx`` on the GPU, ``hist_sizes`` on the host, nothing read back."""
-        if not hist_idx.is_cuda:
-            raise RuntimeError(f"newsreclib_amd: `hist_idx` must live on the GPU (got {hist_idx.device}); there is no CPU path")
-        hist_idx, users, excl = self._ensemble_users(hist_idx, hist_sizes, user_idx, exclude_history)
-        idx, score, status, stats = ops.topk_ensemble_scores(users, self.vectors, self.weights, k, excl[0], excl[1],
-                                                             eligible.to(self.table.device) if eligible is not None else None)
+        users, _, tail = self._ensemble_users("recommend_ensemble", hist_idx, hist_sizes, user_idx, exclude_history, eligible, None)
+        idx, score, status, stats = ops.topk_ensemble_scores(users, self.vectors, self.weights, k, *tail)
         return (idx, score, status, stats) if return_stats else (idx, score, status)
 
-    def _ensemble_users(self, hist_idx: torch.Tensor, hist_sizes: torch.Tensor, user_idx: Optional[torch.Tensor],
-                        exclude_history: bool):
-        """The user side of ``recommend_ensemble`` and ``rank_clicks_ensemble`` -> (hist_idx on the device, the user matrix of every
-        sub-model: the mean of the gathered history rows of its table, the exclusion lists (idx, offsets) or (None, None)).
-        Builds the tables when they are missing; nothing is read back."""
+    def _ensemble_users(self, who: str, hist_idx, hist_sizes, user_idx, exclude_history: bool, eligible, clicks):
+        """The user side of ``recommend_ensemble`` and ``rank_clicks_ensemble`` (``who``): the caller's side of the call checked and
+        on the device (``_catalogue_side``) -> (the user matrix of every sub-model: the mean of the gathered history rows of its
+        table, the click lists, (excl_idx, excl_off, eligible)).  Builds the tables when they are missing; nothing is read
+        back."""
         from .dense_batch import dense_rows
+        hist_idx, eligible, targets = _catalogue_side(who, self, hist_idx, hist_sizes, eligible, clicks)
         if self.vectors is None:
             self.build()
-        hist_idx = hist_idx.to(self.table.device).long()
         meta = self.caches[0]._user_meta(hist_sizes, user_idx)
         users = []
         for vec in self.vectors:
             hv = ops.embedding_gather(vec, hist_idx.reshape(-1, 1)).reshape(-1, vec.shape[1])
             dense = dense_rows(hv, meta["batch_hist"], meta["batch_size"], meta["max_hist"], meta["hist_offsets"])
             users.append(ops.HistMeanFn.apply(dense, meta["hist_offsets"]))
-        return hist_idx, users, ((hist_idx, meta["hist_offsets"]) if exclude_history else (None, None))
+        excl = (hist_idx, meta["hist_offsets"]) if exclude_history else (None, None)
+        return users, targets, (*excl, eligible)
 
     @torch.no_grad()
     def rank_clicks_ensemble(self, hist_idx: torch.Tensor, hist_sizes: torch.Tensor, click_idx: torch.Tensor,
@@ -539,12 +507,9 @@ class MannerVectorCache(_ImpressionCache):
         by, not the one ``scores`` returns for an impression.  Same contract as ``NewsVectorCache.rank_clicks``: ``hist_idx``
         and ``click_idx`` on the GPU, ``hist_sizes`` and ``click_sizes`` on the host, at most ``ops.RANK_MAX_TARGETS`` clicks a
         user (``ValueError`` otherwise), nothing read back."""
-        cs = _click_sizes("rank_clicks_ensemble", hist_idx, hist_sizes, click_idx, click_sizes)
-        hist_idx, users, excl = self._ensemble_users(hist_idx, hist_sizes, user_idx, exclude_history)
-        dev = self.table.device
-        rank, score, ranked, status, stats = ops.catalogue_ensemble_ranks(
-            users, self.vectors, self.weights, click_idx.to(dev).long(), _click_offsets(cs, dev), excl[0], excl[1],
-            eligible.to(dev) if eligible is not None else None)
+        users, targets, tail = self._ensemble_users("rank_clicks_ensemble",
+                                                    hist_idx, hist_sizes, user_idx, exclude_history, eligible, (click_idx, click_sizes))
+        rank, score, ranked, status, stats = ops.catalogue_ensemble_ranks(users, self.vectors, self.weights, *targets, *tail)
         return (rank, score, ranked, status, stats) if return_stats else (rank, score, ranked, status)
 
 
@@ -628,27 +593,25 @@ class NpaFeatureCache(_ImpressionCache):
         ``max_hist`` the longest history OF THE BATCH (the model's own ``to_dense_batch`` quirk): a user's vector, hence its
         ranking, depends on the batch it is in exactly as in ``scores``.  Same contract as ``NewsVectorCache.recommend``:
         ``hist_idx`` on the GPU, ``hist_sizes`` on the host, nothing read back; the features are built at the first use."""
-        if user_idx is None:
-            raise ValueError(f"NpaFeatureCache.recommend_pooled needs user_idx: {self.user_idx_reason}")
-        if not hist_idx.is_cuda:
-            raise RuntimeError(f"newsreclib_amd: `hist_idx` must live on the GPU (got {hist_idx.device}); there is no CPU path")
-        hist_idx, hist_off, q_cand, user = self._pooled_user_side(hist_idx, hist_sizes, user_idx)
-        excl = (hist_idx, hist_off) if exclude_history else (None, None)
-        return ops.topk_pooled_scores(q_cand, user, self.features, k, excl[0], excl[1],
-                                      eligible.to(self.table.device) if eligible is not None else None)
+        scorer, _, tail = self._pooled_user_side("recommend_pooled",
+                                                 hist_idx, hist_sizes, user_idx, exclude_history, eligible, None)
+        return ops.topk_pooled_scores(*scorer, self.features, k, *tail)
 
-    def _pooled_user_side(self, hist_idx: torch.Tensor, hist_sizes: torch.Tensor, user_idx: torch.Tensor):
-        """The user side ``recommend_pooled`` documents -> (hist_idx, hist_off, q_cand, user) on the device, nothing read back."""
+    def _pooled_user_side(self, who: str, hist_idx, hist_sizes, user_idx, exclude_history: bool, eligible, clicks):
+        """The user side ``recommend_pooled`` documents, for it and for ``rank_clicks_pooled`` (``who``): ``user_idx`` required, the
+        caller's side of the call checked and on the device (``_catalogue_side``) -> ((q_cand, user), the click lists,
+        (excl_idx, excl_off, eligible)); nothing read back."""
         from .ops_npa import npa_cached_scores
+        if user_idx is None:
+            raise ValueError(f"NpaFeatureCache.{who} needs user_idx: {self.user_idx_reason}")
+        hist_idx, eligible, targets = _catalogue_side(who, self, hist_idx, hist_sizes, eligible, clicks)
         if self.features is None:
             self.build()
         dev = self.table.device
-        hist_idx = hist_idx.to(dev).long()
         hs = hist_sizes.detach().cpu().long()               # host sizes: the maximum and the offsets cost no read-back
         B = int(hs.numel())
         max_hist = int(hs.max()) if B else 0
-        off = torch.cat([torch.zeros(1, dtype=torch.int64), torch.cumsum(hs, 0)])
-        hist_off = off.pin_memory().to(dev, non_blocking=True)
+        hist_off = _click_offsets(hs, dev)
         user_idx = user_idx if user_idx.is_cuda else user_idx.pin_memory().to(dev, non_blocking=True)
         with eval_mode(self.module):
             text_q, q_news = self.module.user_queries(user_idx.to(dev).long())      # p = 0, as ``scores``
@@ -657,7 +620,8 @@ class NpaFeatureCache(_ImpressionCache):
         # (the scorer wants a score buffer: one padded slot per user, no candidate rows)
         _, user = npa_cached_scores(self.features, hist_idx, hist_off, no_cand, torch.zeros(B + 1, dtype=torch.int64, device=dev),
                                     q_hist, q_cand, q_news, max_hist, 1, return_user_vectors=True)
-        return hist_idx, hist_off, q_cand, user
+        excl = (hist_idx, hist_off) if exclude_history else (None, None)
+        return (q_cand, user), targets, (*excl, eligible)
 
     @torch.no_grad()
     def rank_clicks_pooled(self, hist_idx: torch.Tensor, hist_sizes: torch.Tensor, click_idx: torch.Tensor, click_sizes: torch.Tensor,
@@ -668,14 +632,9 @@ class NpaFeatureCache(_ImpressionCache):
         included), scores, order, exclusion of the history and ``eligible``, with ``ops.catalogue_pooled_ranks`` counting where
         ``recommend_pooled`` selects: ``rank <= k`` exactly when the click is slot ``rank - 1`` of ``recommend_pooled(k)``.  The
         click side is that of ``rank_clicks`` (host ``click_sizes``, at most ``ops.RANK_MAX_TARGETS`` a user, nothing read back)."""
-        if user_idx is None:
-            raise ValueError(f"NpaFeatureCache.rank_clicks_pooled needs user_idx: {self.user_idx_reason}")
-        cs = _click_sizes("rank_clicks_pooled", hist_idx, hist_sizes, click_idx, click_sizes)
-        hist_idx, hist_off, q_cand, user = self._pooled_user_side(hist_idx, hist_sizes, user_idx)
-        dev = self.table.device
-        excl = (hist_idx, hist_off) if exclude_history else (None, None)
-        return ops.catalogue_pooled_ranks(q_cand, user, self.features, click_idx.to(dev).long(), _click_offsets(cs, dev), excl[0],
-                                          excl[1], eligible.to(dev) if eligible is not None else None)
+        scorer, targets, tail = self._pooled_user_side("rank_clicks_pooled",
+                                                       hist_idx, hist_sizes, user_idx, exclude_history, eligible, (click_idx, click_sizes))
+        return ops.catalogue_pooled_ranks(*scorer, self.features, *targets, *tail)
 
 
 def evaluate_impressions(cache: NewsVectorCache, impressions: Sequence[Dict], batch_size: int = 512,

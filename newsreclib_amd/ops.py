@@ -12,7 +12,7 @@ from __future__ import annotations
 
 import ctypes
 import os
-from typing import Optional, Sequence, Tuple
+from typing import NamedTuple, Optional, Sequence, Tuple
 
 import torch
 
@@ -738,6 +738,81 @@ def _topk_masks(excl_idx, excl_off, eligible, B: int, V: int):
     return excl_idx, excl_off, eligible
 
 
+def _ptr(t):
+    """An optional tensor as a native entry takes it."""
+    return t.data_ptr() if t is not None else None
+
+
+def _topk_outputs(B: int, k: int, dev):
+    return (torch.empty((B, max(k, 0)), dtype=torch.int64, device=dev), torch.empty((B, max(k, 0)), dtype=torch.float32, device=dev),
+            torch.zeros(1, dtype=torch.int32, device=dev))
+
+
+def _rank_targets(tgt_idx, tgt_off, B: int):
+    """The target lists as every rank entry takes them, checked (``catalogue_ranks`` documents them)."""
+    tgt_idx, tgt_off = _chk(tgt_idx, torch.int64, "tgt_idx"), _chk(tgt_off, torch.int64, "tgt_off")
+    if tgt_off.numel() != B + 1:
+        raise ValueError("newsreclib_amd: tgt_off must have B + 1 entries")
+    n_tgt = int(tgt_idx.numel())
+    # (the kernel validates the offsets against n_tgt itself; as for excl_off, one beyond the list is turned into one it rejects)
+    return tgt_idx, torch.where(tgt_off > n_tgt, torch.full_like(tgt_off, -1), tgt_off), n_tgt
+
+
+def _rank_outputs(n_tgt: int, B: int, dev):
+    return (torch.empty(n_tgt, dtype=torch.int32, device=dev), torch.empty(n_tgt, dtype=torch.float32, device=dev),
+            torch.empty(B, dtype=torch.int32, device=dev), torch.zeros(1, dtype=torch.int32, device=dev))
+
+
+class _Scorer(NamedTuple):
+    """A scorer's inputs, checked once for its top-k wrapper and its rank wrapper: the sizes, the D its workspace is sized with and
+    its own arguments of the native call, those before ``k`` / the targets (``lead``) and those after (``trail``); ``keep`` holds
+    what the pointers among them point into."""
+    B: int
+    V: int
+    D: int
+    dev: torch.device
+    lead: tuple
+    trail: tuple
+    keep: tuple
+
+
+def _run_topk(entry: str, s: _Scorer, k: int, excl_idx, excl_off, eligible, slices: int, extra=()):
+    """The top-k entry ``entry`` under scorer ``s``; ``extra``: the outputs of its own between ``score`` and ``status``."""
+    lib = _lib.load()
+    k = int(k)
+    excl_idx, excl_off, eligible = _topk_masks(excl_idx, excl_off, eligible, s.B, s.V)
+    idx, score, status = _topk_outputs(s.B, k, s.dev)
+    ws = workspace(lib.nrl_topk_scores_workspace_bytes(s.B, s.V, s.D, k, int(slices)), s.dev)
+    _lib.check(getattr(lib, entry)(*s.lead, k, *s.trail, _ptr(excl_idx), _ptr(excl_off), _ptr(eligible), int(slices), idx.data_ptr(),
+                                   score.data_ptr(), *(t.data_ptr() for t in extra), status.data_ptr(), ws.data_ptr(), ws.numel(),
+                                   _stream()), entry)
+    return idx, score, status
+
+
+def _run_ranks(entry: str, s: _Scorer, tgt_idx, tgt_off, excl_idx, excl_off, eligible, slices: int, extra=(), ws_lead=()):
+    """The rank entry ``entry`` under scorer ``s``; ``extra``: the outputs of its own between ``ranked`` and ``status``; ``ws_lead``
+    (with it the entry has a workspace function of its own): that function's arguments before B."""
+    lib = _lib.load()
+    tgt_idx, tgt_off, n_tgt = _rank_targets(tgt_idx, tgt_off, s.B)
+    excl_idx, excl_off, eligible = _topk_masks(excl_idx, excl_off, eligible, s.B, s.V)
+    rank, score, ranked, status = _rank_outputs(n_tgt, s.B, s.dev)
+    ws_size = getattr(lib, entry + "_workspace_size") if ws_lead else lib.nrl_catalogue_ranks_workspace_size
+    ws = workspace(ws_size(*ws_lead, s.B, s.V, s.D, n_tgt, int(slices)), s.dev)
+    _lib.check(getattr(lib, entry)(*s.lead, *s.trail, tgt_idx.data_ptr(), tgt_off.data_ptr(), n_tgt, _ptr(excl_idx), _ptr(excl_off),
+                                   _ptr(eligible), int(slices), rank.data_ptr(), score.data_ptr(), ranked.data_ptr(),
+                                   *(t.data_ptr() for t in extra), status.data_ptr(), ws.data_ptr(), ws.numel(), _stream()), entry)
+    return rank, score, ranked, status
+
+
+def _dot_scorer(user_vec, table) -> _Scorer:
+    user_vec, table = _chk(user_vec, torch.float32, "user_vec"), _chk(table, torch.float32, "table")
+    if user_vec.dim() != 2 or table.dim() != 2 or user_vec.shape[1] != table.shape[1]:
+        raise ValueError(f"newsreclib_amd: user_vec (B, D) and table (V, D) expected, got {tuple(user_vec.shape)} and "
+                         f"{tuple(table.shape)}")
+    B, D, V = int(user_vec.shape[0]), int(user_vec.shape[1]), int(table.shape[0])
+    return _Scorer(B, V, D, user_vec.device, (user_vec.data_ptr(), table.data_ptr(), B, V, D), (), (user_vec, table))
+
+
 def topk_scores(user_vec: torch.Tensor, table: torch.Tensor, k: int, excl_idx: Optional[torch.Tensor] = None,
                 excl_off: Optional[torch.Tensor] = None, eligible: Optional[torch.Tensor] = None, slices: int = 0):
     """``nrl_topk_scores``: for each row of ``user_vec`` (B, D) the ``k`` rows of ``table`` (V, D) of highest dot product ->
@@ -746,23 +821,7 @@ def topk_scores(user_vec: torch.Tensor, table: torch.Tensor, k: int, excl_idx: O
     returned (the history); ``eligible`` (V uint8 or bool): 0 = never returned for anyone.  The (B, V) score matrix is never
     materialised.  ``status`` (``TOPK_FLAGS``) stays on the device and must be read by the caller -- nothing here synchronises
     with the host."""
-    lib = _lib.load()
-    user_vec, table = _chk(user_vec, torch.float32, "user_vec"), _chk(table, torch.float32, "table")
-    if user_vec.dim() != 2 or table.dim() != 2 or user_vec.shape[1] != table.shape[1]:
-        raise ValueError(f"newsreclib_amd: user_vec (B, D) and table (V, D) expected, got {tuple(user_vec.shape)} and "
-                         f"{tuple(table.shape)}")
-    B, D, V, k = int(user_vec.shape[0]), int(user_vec.shape[1]), int(table.shape[0]), int(k)
-    excl_idx, excl_off, eligible = _topk_masks(excl_idx, excl_off, eligible, B, V)
-    dev = user_vec.device
-    idx = torch.empty((B, max(k, 0)), dtype=torch.int64, device=dev)
-    score = torch.empty((B, max(k, 0)), dtype=torch.float32, device=dev)
-    status = torch.zeros(1, dtype=torch.int32, device=dev)
-    ws = workspace(lib.nrl_topk_scores_workspace_bytes(B, V, D, k, int(slices)), dev)
-    ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
-    _lib.check(lib.nrl_topk_scores(user_vec.data_ptr(), table.data_ptr(), B, V, D, k, ptr(excl_idx), ptr(excl_off), ptr(eligible),
-                                   int(slices), idx.data_ptr(), score.data_ptr(), status.data_ptr(), ws.data_ptr(), ws.numel(),
-                                   _stream()), "nrl_topk_scores")
-    return idx, score, status
+    return _run_topk("nrl_topk_scores", _dot_scorer(user_vec, table), k, excl_idx, excl_off, eligible, slices)
 
 
 RANK_MAX_TARGETS = 32
@@ -785,34 +844,33 @@ def catalogue_ranks(user_vec: torch.Tensor, table: torch.Tensor, tgt_idx: torch.
     ``excl_idx`` / ``excl_off`` and ``eligible`` are those of ``topk_scores``, bit for bit: ``rank <= k`` exactly when the target is
     slot ``rank - 1`` of the user's top-k list.  The (B, V) score matrix is never materialised.  ``status`` (``RANK_FLAGS``)
     stays on the device -- nothing here synchronises with the host."""
-    lib = _lib.load()
-    user_vec, table = _chk(user_vec, torch.float32, "user_vec"), _chk(table, torch.float32, "table")
-    if user_vec.dim() != 2 or table.dim() != 2 or user_vec.shape[1] != table.shape[1]:
-        raise ValueError(f"newsreclib_amd: user_vec (B, D) and table (V, D) expected, got {tuple(user_vec.shape)} and "
-                         f"{tuple(table.shape)}")
-    B, D, V = int(user_vec.shape[0]), int(user_vec.shape[1]), int(table.shape[0])
-    tgt_idx, tgt_off = _chk(tgt_idx, torch.int64, "tgt_idx"), _chk(tgt_off, torch.int64, "tgt_off")
-    if tgt_off.numel() != B + 1:
-        raise ValueError("newsreclib_amd: tgt_off must have B + 1 entries")
-    n_tgt = int(tgt_idx.numel())
-    # (the kernel validates the offsets against n_tgt itself; as for excl_off, one beyond the list is turned into one it rejects)
-    tgt_off = torch.where(tgt_off > n_tgt, torch.full_like(tgt_off, -1), tgt_off)
-    excl_idx, excl_off, eligible = _topk_masks(excl_idx, excl_off, eligible, B, V)
-    dev = user_vec.device
-    rank = torch.empty(n_tgt, dtype=torch.int32, device=dev)
-    score = torch.empty(n_tgt, dtype=torch.float32, device=dev)
-    ranked = torch.empty(B, dtype=torch.int32, device=dev)
-    status = torch.zeros(1, dtype=torch.int32, device=dev)
-    ws = workspace(lib.nrl_catalogue_ranks_workspace_size(B, V, D, n_tgt, int(slices)), dev)
-    ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
-    _lib.check(lib.nrl_catalogue_ranks(user_vec.data_ptr(), table.data_ptr(), B, V, D, tgt_idx.data_ptr(), tgt_off.data_ptr(), n_tgt,
-                                       ptr(excl_idx), ptr(excl_off), ptr(eligible), int(slices), rank.data_ptr(), score.data_ptr(),
-                                       ranked.data_ptr(), status.data_ptr(), ws.data_ptr(), ws.numel(), _stream()),
-               "nrl_catalogue_ranks")
-    return rank, score, ranked, status
+    return _run_ranks("nrl_catalogue_ranks", _dot_scorer(user_vec, table), tgt_idx, tgt_off, excl_idx, excl_off, eligible, slices)
 
 
 TOPK_MAX_INTERESTS = 64
+
+
+def _interest_scorer(who: str, interests, table, mode, gate) -> _Scorer:
+    from .ops_miner import SCORE_MODES
+    interests, table = _chk(interests, torch.float32, "interests"), _chk(table, torch.float32, "table")
+    if interests.dim() != 3 or table.dim() != 2 or interests.shape[2] != table.shape[1]:
+        raise ValueError(f"newsreclib_amd: interests (B, K, D) and table (V, D) expected, got {tuple(interests.shape)} and "
+                         f"{tuple(table.shape)}")
+    if mode not in SCORE_MODES:
+        raise ValueError(f"newsreclib_amd: mode must be one of {sorted(SCORE_MODES)} (got {mode!r})")
+    B, K, D, V = int(interests.shape[0]), int(interests.shape[1]), int(interests.shape[2]), int(table.shape[0])
+    if K > TOPK_MAX_INTERESTS:
+        raise NotImplementedError(f"newsreclib_amd: {who} takes at most {TOPK_MAX_INTERESTS} interest vectors per user (got {K})")
+    if mode == "weighted":
+        if gate is None:
+            raise ValueError("newsreclib_amd: mode 'weighted' needs `gate` (B, K, D) = gelu(user_vector Wt^T)")
+        gate = _chk(gate, torch.float32, "gate")
+        if gate.shape != interests.shape:
+            raise ValueError(f"newsreclib_amd: gate must have the shape of interests, got {tuple(gate.shape)}")
+    else:
+        gate = None
+    return _Scorer(B, V, D, interests.device, (interests.data_ptr(), _ptr(gate), table.data_ptr(), B, K, V, D), (SCORE_MODES[mode],),
+                   (interests, gate, table))
 
 
 def topk_interest_scores(interests: torch.Tensor, table: torch.Tensor, k: int, mode: str, gate: Optional[torch.Tensor] = None,
@@ -825,41 +883,45 @@ def topk_interest_scores(interests: torch.Tensor, table: torch.Tensor, k: int, m
     status (1) int32) with the ordering, exclusion, eligibility and status flags of ``topk_scores``; neither the (B, V) nor the
     (B K, V) matrix is materialised.  The workspace is sized by ``nrl_topk_scores_workspace_bytes`` with B in users, which always
     suffices.  Nothing here synchronises with the host."""
-    from .ops_miner import SCORE_MODES
-    lib = _lib.load()
-    interests, table = _chk(interests, torch.float32, "interests"), _chk(table, torch.float32, "table")
-    if interests.dim() != 3 or table.dim() != 2 or interests.shape[2] != table.shape[1]:
-        raise ValueError(f"newsreclib_amd: interests (B, K, D) and table (V, D) expected, got {tuple(interests.shape)} and "
-                         f"{tuple(table.shape)}")
-    if mode not in SCORE_MODES:
-        raise ValueError(f"newsreclib_amd: mode must be one of {sorted(SCORE_MODES)} (got {mode!r})")
-    B, K, D, V, k = int(interests.shape[0]), int(interests.shape[1]), int(interests.shape[2]), int(table.shape[0]), int(k)
-    if K > TOPK_MAX_INTERESTS:
-        raise NotImplementedError(f"newsreclib_amd: topk_interest_scores takes at most {TOPK_MAX_INTERESTS} interest vectors per "
-                                  f"user (got {K})")
-    if mode == "weighted":
-        if gate is None:
-            raise ValueError("newsreclib_amd: mode 'weighted' needs `gate` (B, K, D) = gelu(user_vector Wt^T)")
-        gate = _chk(gate, torch.float32, "gate")
-        if gate.shape != interests.shape:
-            raise ValueError(f"newsreclib_amd: gate must have the shape of interests, got {tuple(gate.shape)}")
-    else:
-        gate = None
-    excl_idx, excl_off, eligible = _topk_masks(excl_idx, excl_off, eligible, B, V)
-    dev = interests.device
-    idx = torch.empty((B, max(k, 0)), dtype=torch.int64, device=dev)
-    score = torch.empty((B, max(k, 0)), dtype=torch.float32, device=dev)
-    status = torch.zeros(1, dtype=torch.int32, device=dev)
-    ws = workspace(lib.nrl_topk_scores_workspace_bytes(B, V, D, k, int(slices)), dev)
-    ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
-    _lib.check(lib.nrl_topk_interest_scores(interests.data_ptr(), ptr(gate), table.data_ptr(), B, K, V, D, k, SCORE_MODES[mode],
-                                            ptr(excl_idx), ptr(excl_off), ptr(eligible), int(slices), idx.data_ptr(),
-                                            score.data_ptr(), status.data_ptr(), ws.data_ptr(), ws.numel(), _stream()),
-               "nrl_topk_interest_scores")
-    return idx, score, status
+    s = _interest_scorer("topk_interest_scores", interests, table, mode, gate)
+    return _run_topk("nrl_topk_interest_scores", s, k, excl_idx, excl_off, eligible, slices)
+
+
+def catalogue_interest_ranks(interests: torch.Tensor, table: torch.Tensor, tgt_idx: torch.Tensor, tgt_off: torch.Tensor, mode: str,
+                             gate: Optional[torch.Tensor] = None, excl_idx: Optional[torch.Tensor] = None,
+                             excl_off: Optional[torch.Tensor] = None, eligible: Optional[torch.Tensor] = None, slices: int = 0):
+    """``nrl_catalogue_interest_ranks``: ``catalogue_ranks`` by the scores of ``topk_interest_scores`` -- ``interests`` (B, K, D),
+    ``mode`` "max" / "mean" / "weighted" (``gate`` (B, K, D), required by "weighted" alone) -> (rank int32 (n_tgt), score fp32
+    (n_tgt), ranked int32 (B), status (1) int32) with the targets, population, order, masks and flags (``RANK_FLAGS``) of
+    ``catalogue_ranks`` and the score bits of ``topk_interest_scores``: ``rank <= k`` exactly when the target is slot ``rank - 1``
+    of that call's list.  Neither the (B, V) nor the (B K, V) matrix is materialised; nothing here synchronises with the host."""
+    s = _interest_scorer("catalogue_interest_ranks", interests, table, mode, gate)
+    return _run_ranks("nrl_catalogue_interest_ranks", s, tgt_idx, tgt_off, excl_idx, excl_off, eligible, slices)
 
 
 TOPK_MAX_MODELS, TOPK_STAT_CHUNKS = 3, 64
+
+
+def _ensemble_scorer(users, tables, weights):
+    """-> the scorer and the two outputs of its own: stats (B, T, 2) and the moments scratch."""
+    users, tables = list(users), list(tables)
+    T = len(tables)
+    if not 1 <= T <= TOPK_MAX_MODELS or len(users) != T or len(weights) != T:
+        raise ValueError(f"newsreclib_amd: 1 to {TOPK_MAX_MODELS} sub-models with one user matrix, one table and one weight each "
+                         f"(got {len(users)}, {T} and {len(weights)})")
+    if users[0].dim() != 2 or tables[0].dim() != 2 or users[0].shape[1] != tables[0].shape[1] or \
+            any(u.shape != users[0].shape for u in users) or any(t.shape != tables[0].shape for t in tables):
+        raise ValueError(f"newsreclib_amd: users (B, D) and tables (V, D) of one shape each expected, got "
+                         f"{[tuple(u.shape) for u in users]} and {[tuple(t.shape) for t in tables]}")
+    users = [_chk(u, torch.float32, "users") for u in users]
+    tables = [_chk(t, torch.float32, "tables") for t in tables]
+    B, D, V, dev = int(users[0].shape[0]), int(users[0].shape[1]), int(tables[0].shape[0]), users[0].device
+    uptr = (ctypes.c_void_p * T)(*[u.data_ptr() for u in users])
+    tptr = (ctypes.c_void_p * T)(*[t.data_ptr() for t in tables])
+    wts = (ctypes.c_float * T)(*[float(w) for w in weights])
+    stats = torch.empty((B, T, 2), dtype=torch.float32, device=dev)
+    moments = torch.empty((B, TOPK_STAT_CHUNKS, T, 3), dtype=torch.float32, device=dev)
+    return _Scorer(B, V, D, dev, (uptr, tptr, wts, T, B, V, D), (), (users, tables)), stats, moments
 
 
 def topk_ensemble_scores(users: Sequence[torch.Tensor], tables: Sequence[torch.Tensor], weights: Sequence[float], k: int,
@@ -872,35 +934,8 @@ def topk_ensemble_scores(users: Sequence[torch.Tensor], tables: Sequence[torch.T
     -> (idx (B, k) int64, score (B, k) fp32, status (1) int32, stats (B, T, 2) fp32: mean, sd) with the ordering, exclusion,
     eligibility and status flags of ``topk_scores`` and one flag more (``TOPK_FLAGS[8]``): a user whose scores cannot be
     standardised gets ``-1`` / ``-inf``.  No (B, V) matrix is materialised; nothing here synchronises with the host."""
-    lib = _lib.load()
-    users, tables = list(users), list(tables)
-    T = len(tables)
-    if not 1 <= T <= TOPK_MAX_MODELS or len(users) != T or len(weights) != T:
-        raise ValueError(f"newsreclib_amd: 1 to {TOPK_MAX_MODELS} sub-models with one user matrix, one table and one weight each "
-                         f"(got {len(users)}, {T} and {len(weights)})")
-    if users[0].dim() != 2 or tables[0].dim() != 2 or users[0].shape[1] != tables[0].shape[1] or \
-            any(u.shape != users[0].shape for u in users) or any(t.shape != tables[0].shape for t in tables):
-        raise ValueError(f"newsreclib_amd: users (B, D) and tables (V, D) of one shape each expected, got "
-                         f"{[tuple(u.shape) for u in users]} and {[tuple(t.shape) for t in tables]}")
-    users = [_chk(u, torch.float32, "users") for u in users]
-    tables = [_chk(t, torch.float32, "tables") for t in tables]
-    B, D, V, k = int(users[0].shape[0]), int(users[0].shape[1]), int(tables[0].shape[0]), int(k)
-    excl_idx, excl_off, eligible = _topk_masks(excl_idx, excl_off, eligible, B, V)
-    dev = users[0].device
-    idx = torch.empty((B, max(k, 0)), dtype=torch.int64, device=dev)
-    score = torch.empty((B, max(k, 0)), dtype=torch.float32, device=dev)
-    stats = torch.empty((B, T, 2), dtype=torch.float32, device=dev)
-    moments = torch.empty((B, TOPK_STAT_CHUNKS, T, 3), dtype=torch.float32, device=dev)
-    status = torch.zeros(1, dtype=torch.int32, device=dev)
-    ws = workspace(lib.nrl_topk_scores_workspace_bytes(B, V, D, k, int(slices)), dev)
-    ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
-    uptr = (ctypes.c_void_p * T)(*[u.data_ptr() for u in users])
-    tptr = (ctypes.c_void_p * T)(*[t.data_ptr() for t in tables])
-    wts = (ctypes.c_float * T)(*[float(w) for w in weights])
-    _lib.check(lib.nrl_topk_ensemble_scores(uptr, tptr, wts, T, B, V, D, k, ptr(excl_idx), ptr(excl_off), ptr(eligible), int(slices),
-                                            idx.data_ptr(), score.data_ptr(), stats.data_ptr(), moments.data_ptr(),
-                                            status.data_ptr(), ws.data_ptr(), ws.numel(), _stream()), "nrl_topk_ensemble_scores")
-    return idx, score, status, stats
+    s, stats, moments = _ensemble_scorer(users, tables, weights)
+    return (*_run_topk("nrl_topk_ensemble_scores", s, k, excl_idx, excl_off, eligible, slices, extra=(stats, moments)), stats)
 
 
 # the status word of ``catalogue_ensemble_ranks``: the flags of ``catalogue_ranks`` and, worded for ranks, the one of the ensemble
@@ -919,39 +954,25 @@ def catalogue_ensemble_ranks(users: Sequence[torch.Tensor], tables: Sequence[tor
     call's list.  ``status`` (``ENSEMBLE_RANK_FLAGS``): the flags of ``catalogue_ranks`` and one more -- a user whose scores cannot
     be standardised has ranks 0, scores ``-inf`` and ``ranked`` 0.  No (B, V) matrix is materialised; nothing here synchronises
     with the host."""
-    lib = _lib.load()
-    users, tables = list(users), list(tables)
-    T = len(tables)
-    if not 1 <= T <= TOPK_MAX_MODELS or len(users) != T or len(weights) != T:
-        raise ValueError(f"newsreclib_amd: 1 to {TOPK_MAX_MODELS} sub-models with one user matrix, one table and one weight each "
-                         f"(got {len(users)}, {T} and {len(weights)})")
-    if users[0].dim() != 2 or tables[0].dim() != 2 or users[0].shape[1] != tables[0].shape[1] or \
-            any(u.shape != users[0].shape for u in users) or any(t.shape != tables[0].shape for t in tables):
-        raise ValueError(f"newsreclib_amd: users (B, D) and tables (V, D) of one shape each expected, got "
-                         f"{[tuple(u.shape) for u in users]} and {[tuple(t.shape) for t in tables]}")
-    users = [_chk(u, torch.float32, "users") for u in users]
-    tables = [_chk(t, torch.float32, "tables") for t in tables]
-    B, D, V = int(users[0].shape[0]), int(users[0].shape[1]), int(tables[0].shape[0])
-    tgt_idx, tgt_off, n_tgt = _rank_targets(tgt_idx, tgt_off, B)
-    excl_idx, excl_off, eligible = _topk_masks(excl_idx, excl_off, eligible, B, V)
-    dev = users[0].device
-    rank, score, ranked, status = _rank_outputs(n_tgt, B, dev)
-    stats = torch.empty((B, T, 2), dtype=torch.float32, device=dev)
-    moments = torch.empty((B, TOPK_STAT_CHUNKS, T, 3), dtype=torch.float32, device=dev)
-    ws = workspace(lib.nrl_catalogue_ensemble_ranks_workspace_size(T, B, V, D, n_tgt, int(slices)), dev)
-    ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
-    uptr = (ctypes.c_void_p * T)(*[u.data_ptr() for u in users])
-    tptr = (ctypes.c_void_p * T)(*[t.data_ptr() for t in tables])
-    wts = (ctypes.c_float * T)(*[float(w) for w in weights])
-    _lib.check(lib.nrl_catalogue_ensemble_ranks(uptr, tptr, wts, T, B, V, D, tgt_idx.data_ptr(), tgt_off.data_ptr(), n_tgt,
-                                                ptr(excl_idx), ptr(excl_off), ptr(eligible), int(slices), rank.data_ptr(),
-                                                score.data_ptr(), ranked.data_ptr(), stats.data_ptr(), moments.data_ptr(),
-                                                status.data_ptr(), ws.data_ptr(), ws.numel(), _stream()),
-               "nrl_catalogue_ensemble_ranks")
-    return rank, score, ranked, status, stats
+    s, stats, moments = _ensemble_scorer(users, tables, weights)
+    return (*_run_ranks("nrl_catalogue_ensemble_ranks", s, tgt_idx, tgt_off, excl_idx, excl_off, eligible, slices,
+                        extra=(stats, moments), ws_lead=(stats.shape[1],)), stats)
 
 
 TOPK_MAX_HIDDEN = 64
+
+
+def _relu_scorer(who: str, q, proj, w2, b2) -> _Scorer:
+    """(D = 4 sizes the workspace: the partial lists and the counts do not depend on it, and nothing is gathered)"""
+    if q.dim() != 2 or proj.dim() != 2 or q.shape[1] != proj.shape[1] or w2.numel() != q.shape[1] or b2.numel() != 1:
+        raise ValueError(f"newsreclib_amd: q (B, Hd), proj (V, Hd), w2 (Hd) and b2 (1) expected, got {tuple(q.shape)}, "
+                         f"{tuple(proj.shape)}, {tuple(w2.shape)} and {tuple(b2.shape)}")
+    q, proj = _chk(q, torch.float32, "q"), _chk(proj, torch.float32, "proj")
+    w2, b2 = _chk(w2, torch.float32, "w2"), _chk(b2, torch.float32, "b2")
+    B, Hd, V = int(q.shape[0]), int(q.shape[1]), int(proj.shape[0])
+    if not 1 <= Hd <= TOPK_MAX_HIDDEN:
+        raise NotImplementedError(f"newsreclib_amd: {who} takes a hidden width in [1, {TOPK_MAX_HIDDEN}] (got {Hd})")
+    return _Scorer(B, V, 4, q.device, (q.data_ptr(), proj.data_ptr(), w2.data_ptr(), b2.data_ptr(), B, V, Hd), (), (q, proj, w2, b2))
 
 
 def topk_relu_scores(q: torch.Tensor, proj: torch.Tensor, w2: torch.Tensor, b2: torch.Tensor, k: int,
@@ -964,82 +985,8 @@ def topk_relu_scores(q: torch.Tensor, proj: torch.Tensor, w2: torch.Tensor, b2: 
     fp32, status (1) int32) with the ordering, exclusion, eligibility and status flags of ``topk_scores``; neither the (B, V) nor
     the (B, V, Hd) array is materialised.  The workspace is sized by ``nrl_topk_scores_workspace_bytes(B, V, 4, k, slices)``: the
     partial lists are those of ``topk_scores``, whose size does not depend on D.  Nothing here synchronises with the host."""
-    lib = _lib.load()
-    if q.dim() != 2 or proj.dim() != 2 or q.shape[1] != proj.shape[1] or w2.numel() != q.shape[1] or b2.numel() != 1:
-        raise ValueError(f"newsreclib_amd: q (B, Hd), proj (V, Hd), w2 (Hd) and b2 (1) expected, got {tuple(q.shape)}, "
-                         f"{tuple(proj.shape)}, {tuple(w2.shape)} and {tuple(b2.shape)}")
-    q, proj = _chk(q, torch.float32, "q"), _chk(proj, torch.float32, "proj")
-    w2, b2 = _chk(w2, torch.float32, "w2"), _chk(b2, torch.float32, "b2")
-    B, Hd, V, k = int(q.shape[0]), int(q.shape[1]), int(proj.shape[0]), int(k)
-    if not 1 <= Hd <= TOPK_MAX_HIDDEN:
-        raise NotImplementedError(f"newsreclib_amd: topk_relu_scores takes a hidden width in [1, {TOPK_MAX_HIDDEN}] (got {Hd})")
-    excl_idx, excl_off, eligible = _topk_masks(excl_idx, excl_off, eligible, B, V)
-    dev = q.device
-    idx = torch.empty((B, max(k, 0)), dtype=torch.int64, device=dev)
-    score = torch.empty((B, max(k, 0)), dtype=torch.float32, device=dev)
-    status = torch.zeros(1, dtype=torch.int32, device=dev)
-    ws = workspace(lib.nrl_topk_scores_workspace_bytes(B, V, 4, k, int(slices)), dev)
-    ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
-    _lib.check(lib.nrl_topk_relu_scores(q.data_ptr(), proj.data_ptr(), w2.data_ptr(), b2.data_ptr(), B, V, Hd, k, ptr(excl_idx),
-                                        ptr(excl_off), ptr(eligible), int(slices), idx.data_ptr(), score.data_ptr(),
-                                        status.data_ptr(), ws.data_ptr(), ws.numel(), _stream()), "nrl_topk_relu_scores")
-    return idx, score, status
-
-
-def _rank_targets(tgt_idx, tgt_off, B: int):
-    """The target lists as every rank entry takes them, checked (``catalogue_ranks`` documents them)."""
-    tgt_idx, tgt_off = _chk(tgt_idx, torch.int64, "tgt_idx"), _chk(tgt_off, torch.int64, "tgt_off")
-    if tgt_off.numel() != B + 1:
-        raise ValueError("newsreclib_amd: tgt_off must have B + 1 entries")
-    n_tgt = int(tgt_idx.numel())
-    # (the kernel validates the offsets against n_tgt itself; as for excl_off, one beyond the list is turned into one it rejects)
-    return tgt_idx, torch.where(tgt_off > n_tgt, torch.full_like(tgt_off, -1), tgt_off), n_tgt
-
-
-def _rank_outputs(n_tgt: int, B: int, dev):
-    return (torch.empty(n_tgt, dtype=torch.int32, device=dev), torch.empty(n_tgt, dtype=torch.float32, device=dev),
-            torch.empty(B, dtype=torch.int32, device=dev), torch.zeros(1, dtype=torch.int32, device=dev))
-
-
-def catalogue_interest_ranks(interests: torch.Tensor, table: torch.Tensor, tgt_idx: torch.Tensor, tgt_off: torch.Tensor, mode: str,
-                             gate: Optional[torch.Tensor] = None, excl_idx: Optional[torch.Tensor] = None,
-                             excl_off: Optional[torch.Tensor] = None, eligible: Optional[torch.Tensor] = None, slices: int = 0):
-    """``nrl_catalogue_interest_ranks``: ``catalogue_ranks`` by the scores of ``topk_interest_scores`` -- ``interests`` (B, K, D),
-    ``mode`` "max" / "mean" / "weighted" (``gate`` (B, K, D), required by "weighted" alone) -> (rank int32 (n_tgt), score fp32
-    (n_tgt), ranked int32 (B), status (1) int32) with the targets, population, order, masks and flags (``RANK_FLAGS``) of
-    ``catalogue_ranks`` and the score bits of ``topk_interest_scores``: ``rank <= k`` exactly when the target is slot ``rank - 1``
-    of that call's list.  Neither the (B, V) nor the (B K, V) matrix is materialised; nothing here synchronises with the host."""
-    from .ops_miner import SCORE_MODES
-    lib = _lib.load()
-    interests, table = _chk(interests, torch.float32, "interests"), _chk(table, torch.float32, "table")
-    if interests.dim() != 3 or table.dim() != 2 or interests.shape[2] != table.shape[1]:
-        raise ValueError(f"newsreclib_amd: interests (B, K, D) and table (V, D) expected, got {tuple(interests.shape)} and "
-                         f"{tuple(table.shape)}")
-    if mode not in SCORE_MODES:
-        raise ValueError(f"newsreclib_amd: mode must be one of {sorted(SCORE_MODES)} (got {mode!r})")
-    B, K, D, V = int(interests.shape[0]), int(interests.shape[1]), int(interests.shape[2]), int(table.shape[0])
-    if K > TOPK_MAX_INTERESTS:
-        raise NotImplementedError(f"newsreclib_amd: catalogue_interest_ranks takes at most {TOPK_MAX_INTERESTS} interest vectors "
-                                  f"per user (got {K})")
-    if mode == "weighted":
-        if gate is None:
-            raise ValueError("newsreclib_amd: mode 'weighted' needs `gate` (B, K, D) = gelu(user_vector Wt^T)")
-        gate = _chk(gate, torch.float32, "gate")
-        if gate.shape != interests.shape:
-            raise ValueError(f"newsreclib_amd: gate must have the shape of interests, got {tuple(gate.shape)}")
-    else:
-        gate = None
-    tgt_idx, tgt_off, n_tgt = _rank_targets(tgt_idx, tgt_off, B)
-    excl_idx, excl_off, eligible = _topk_masks(excl_idx, excl_off, eligible, B, V)
-    rank, score, ranked, status = _rank_outputs(n_tgt, B, interests.device)
-    ws = workspace(lib.nrl_catalogue_ranks_workspace_size(B, V, D, n_tgt, int(slices)), interests.device)
-    ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
-    _lib.check(lib.nrl_catalogue_interest_ranks(interests.data_ptr(), ptr(gate), table.data_ptr(), B, K, V, D, SCORE_MODES[mode],
-                                                tgt_idx.data_ptr(), tgt_off.data_ptr(), n_tgt, ptr(excl_idx), ptr(excl_off),
-                                                ptr(eligible), int(slices), rank.data_ptr(), score.data_ptr(), ranked.data_ptr(),
-                                                status.data_ptr(), ws.data_ptr(), ws.numel(), _stream()),
-               "nrl_catalogue_interest_ranks")
-    return rank, score, ranked, status
+    s = _relu_scorer("topk_relu_scores", q, proj, w2, b2)
+    return _run_topk("nrl_topk_relu_scores", s, k, excl_idx, excl_off, eligible, slices)
 
 
 def catalogue_relu_ranks(q: torch.Tensor, proj: torch.Tensor, w2: torch.Tensor, b2: torch.Tensor, tgt_idx: torch.Tensor,
@@ -1050,28 +997,23 @@ def catalogue_relu_ranks(q: torch.Tensor, proj: torch.Tensor, w2: torch.Tensor, 
     int32) with the targets, population, order, masks and flags (``RANK_FLAGS``) of ``catalogue_ranks`` and the score bits of
     ``topk_relu_scores``: ``rank <= k`` exactly when the target is slot ``rank - 1`` of that call's list.  Neither the (B, V) nor
     the (B, V, Hd) array is materialised; nothing here synchronises with the host."""
-    lib = _lib.load()
-    if q.dim() != 2 or proj.dim() != 2 or q.shape[1] != proj.shape[1] or w2.numel() != q.shape[1] or b2.numel() != 1:
-        raise ValueError(f"newsreclib_amd: q (B, Hd), proj (V, Hd), w2 (Hd) and b2 (1) expected, got {tuple(q.shape)}, "
-                         f"{tuple(proj.shape)}, {tuple(w2.shape)} and {tuple(b2.shape)}")
-    q, proj = _chk(q, torch.float32, "q"), _chk(proj, torch.float32, "proj")
-    w2, b2 = _chk(w2, torch.float32, "w2"), _chk(b2, torch.float32, "b2")
-    B, Hd, V = int(q.shape[0]), int(q.shape[1]), int(proj.shape[0])
-    if not 1 <= Hd <= TOPK_MAX_HIDDEN:
-        raise NotImplementedError(f"newsreclib_amd: catalogue_relu_ranks takes a hidden width in [1, {TOPK_MAX_HIDDEN}] (got {Hd})")
-    tgt_idx, tgt_off, n_tgt = _rank_targets(tgt_idx, tgt_off, B)
-    excl_idx, excl_off, eligible = _topk_masks(excl_idx, excl_off, eligible, B, V)
-    rank, score, ranked, status = _rank_outputs(n_tgt, B, q.device)
-    ws = workspace(lib.nrl_catalogue_ranks_workspace_size(B, V, 4, n_tgt, int(slices)), q.device)
-    ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
-    _lib.check(lib.nrl_catalogue_relu_ranks(q.data_ptr(), proj.data_ptr(), w2.data_ptr(), b2.data_ptr(), B, V, Hd, tgt_idx.data_ptr(),
-                                            tgt_off.data_ptr(), n_tgt, ptr(excl_idx), ptr(excl_off), ptr(eligible), int(slices),
-                                            rank.data_ptr(), score.data_ptr(), ranked.data_ptr(), status.data_ptr(), ws.data_ptr(),
-                                            ws.numel(), _stream()), "nrl_catalogue_relu_ranks")
-    return rank, score, ranked, status
+    s = _relu_scorer("catalogue_relu_ranks", q, proj, w2, b2)
+    return _run_ranks("nrl_catalogue_relu_ranks", s, tgt_idx, tgt_off, excl_idx, excl_off, eligible, slices)
 
 
 TOPK_MAX_TOKENS = 128
+
+
+def _pooled_scorer(who: str, q, user, features) -> _Scorer:
+    """(D = 4 sizes the workspace, as for ``_relu_scorer``: the targets' feature maps are read in place)"""
+    if q.dim() != 2 or features.dim() != 3 or user.shape != q.shape or q.shape[1] != features.shape[2]:
+        raise ValueError(f"newsreclib_amd: q (B, F), user (B, F) and features (V, L, F) expected, got {tuple(q.shape)}, "
+                         f"{tuple(user.shape)} and {tuple(features.shape)}")
+    q, user, features = _chk(q, torch.float32, "q"), _chk(user, torch.float32, "user"), _chk(features, torch.float32, "features")
+    B, F_, V, L = int(q.shape[0]), int(q.shape[1]), int(features.shape[0]), int(features.shape[1])
+    if not 1 <= L <= TOPK_MAX_TOKENS:
+        raise NotImplementedError(f"newsreclib_amd: {who} takes feature maps of 1 to {TOPK_MAX_TOKENS} tokens (got {L})")
+    return _Scorer(B, V, 4, q.device, (q.data_ptr(), user.data_ptr(), features.data_ptr(), B, V, L, F_), (), (q, user, features))
 
 
 def topk_pooled_scores(q: torch.Tensor, user: torch.Tensor, features: torch.Tensor, k: int,
@@ -1085,25 +1027,8 @@ def topk_pooled_scores(q: torch.Tensor, user: torch.Tensor, features: torch.Tens
     ``topk_scores``; neither a (B, V, L) nor the (B, V, F) array is materialised.  The workspace is sized by
     ``nrl_topk_scores_workspace_bytes(B, V, 4, k, slices)``: the partial lists are those of ``topk_scores``.  Nothing here
     synchronises with the host."""
-    lib = _lib.load()
-    if q.dim() != 2 or features.dim() != 3 or user.shape != q.shape or q.shape[1] != features.shape[2]:
-        raise ValueError(f"newsreclib_amd: q (B, F), user (B, F) and features (V, L, F) expected, got {tuple(q.shape)}, "
-                         f"{tuple(user.shape)} and {tuple(features.shape)}")
-    q, user, features = _chk(q, torch.float32, "q"), _chk(user, torch.float32, "user"), _chk(features, torch.float32, "features")
-    B, F_, V, L, k = int(q.shape[0]), int(q.shape[1]), int(features.shape[0]), int(features.shape[1]), int(k)
-    if not 1 <= L <= TOPK_MAX_TOKENS:
-        raise NotImplementedError(f"newsreclib_amd: topk_pooled_scores takes feature maps of 1 to {TOPK_MAX_TOKENS} tokens (got {L})")
-    excl_idx, excl_off, eligible = _topk_masks(excl_idx, excl_off, eligible, B, V)
-    dev = q.device
-    idx = torch.empty((B, max(k, 0)), dtype=torch.int64, device=dev)
-    score = torch.empty((B, max(k, 0)), dtype=torch.float32, device=dev)
-    status = torch.zeros(1, dtype=torch.int32, device=dev)
-    ws = workspace(lib.nrl_topk_scores_workspace_bytes(B, V, 4, k, int(slices)), dev)
-    ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
-    _lib.check(lib.nrl_topk_pooled_scores(q.data_ptr(), user.data_ptr(), features.data_ptr(), B, V, L, F_, k, ptr(excl_idx),
-                                          ptr(excl_off), ptr(eligible), int(slices), idx.data_ptr(), score.data_ptr(),
-                                          status.data_ptr(), ws.data_ptr(), ws.numel(), _stream()), "nrl_topk_pooled_scores")
-    return idx, score, status
+    s = _pooled_scorer("topk_pooled_scores", q, user, features)
+    return _run_topk("nrl_topk_pooled_scores", s, k, excl_idx, excl_off, eligible, slices)
 
 
 def catalogue_pooled_ranks(q: torch.Tensor, user: torch.Tensor, features: torch.Tensor, tgt_idx: torch.Tensor, tgt_off: torch.Tensor,
@@ -1115,22 +1040,5 @@ def catalogue_pooled_ranks(q: torch.Tensor, user: torch.Tensor, features: torch.
     score bits of ``topk_pooled_scores``: ``rank <= k`` exactly when the target is slot ``rank - 1`` of that call's list.  The
     targets' feature maps are read in place: no (B, V), (B, V, L) or (n_tgt, L, F) array is materialised; nothing here
     synchronises with the host."""
-    lib = _lib.load()
-    if q.dim() != 2 or features.dim() != 3 or user.shape != q.shape or q.shape[1] != features.shape[2]:
-        raise ValueError(f"newsreclib_amd: q (B, F), user (B, F) and features (V, L, F) expected, got {tuple(q.shape)}, "
-                         f"{tuple(user.shape)} and {tuple(features.shape)}")
-    q, user, features = _chk(q, torch.float32, "q"), _chk(user, torch.float32, "user"), _chk(features, torch.float32, "features")
-    B, F_, V, L = int(q.shape[0]), int(q.shape[1]), int(features.shape[0]), int(features.shape[1])
-    if not 1 <= L <= TOPK_MAX_TOKENS:
-        raise NotImplementedError(f"newsreclib_amd: catalogue_pooled_ranks takes feature maps of 1 to {TOPK_MAX_TOKENS} tokens "
-                                  f"(got {L})")
-    tgt_idx, tgt_off, n_tgt = _rank_targets(tgt_idx, tgt_off, B)
-    excl_idx, excl_off, eligible = _topk_masks(excl_idx, excl_off, eligible, B, V)
-    rank, score, ranked, status = _rank_outputs(n_tgt, B, q.device)
-    ws = workspace(lib.nrl_catalogue_ranks_workspace_size(B, V, 4, n_tgt, int(slices)), q.device)
-    ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
-    _lib.check(lib.nrl_catalogue_pooled_ranks(q.data_ptr(), user.data_ptr(), features.data_ptr(), B, V, L, F_, tgt_idx.data_ptr(),
-                                              tgt_off.data_ptr(), n_tgt, ptr(excl_idx), ptr(excl_off), ptr(eligible), int(slices),
-                                              rank.data_ptr(), score.data_ptr(), ranked.data_ptr(), status.data_ptr(), ws.data_ptr(),
-                                              ws.numel(), _stream()), "nrl_catalogue_pooled_ranks")
-    return rank, score, ranked, status
+    s = _pooled_scorer("catalogue_pooled_ranks", q, user, features)
+    return _run_ranks("nrl_catalogue_pooled_ranks", s, tgt_idx, tgt_off, excl_idx, excl_off, eligible, slices)
