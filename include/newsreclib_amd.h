@@ -1136,6 +1136,37 @@ int nrl_topk_ensemble_scores(const float* const* users, const float* const* tabl
                              float* moments   /* (B, NRL_TOPK_STAT_CHUNKS, T, 3) caller-provided scratch */,
                              int32_t* status, void* ws, size_t ws_bytes, void* stream);
 
+/* nrl_topk_scores_capped / nrl_topk_ensemble_scores_capped: nrl_topk_scores / nrl_topk_ensemble_scores under a diversity
+ *   constraint on the list itself: the k best rows of a user with at most max_per_class of any one class.  Every argument of the
+ *   uncapped entry keeps its meaning; two are added behind k:
+ *   row_class (V int32, device): the class of every table row (a category, a subcategory, a sentiment class).  Every int32 value
+ *     is a class of its own; rows with equal values share a cap.
+ *   max_per_class: m >= 1.
+ *   Selection: of the rows of user u that are inside V, eligible, not on u's exclusion list and not NaN-scored, ordered by the
+ *     family's strict total order (score descending, equal scores by ascending row, -0 == +0), a row is taken if and only if fewer
+ *     than m rows of its class have been taken before it; the first k taken are returned.  The tail is -1 / -inf when fewer
+ *     qualify, which now also happens when sum_c min(m, n_c) < k.  Excluded, ineligible and NaN rows never count toward a cap.
+ *     That list is the top k of the union of the classes' top-m sets: a pure function of the score bits, the row numbers and the
+ *     class ids, whatever B, slices, the grid or the GEMM engine setting.  With m >= k the result is the uncapped entry's, bit
+ *     for bit.  The ensemble's statistics are those of the uncapped entry: the population does not know the cap.
+ *   k in [1, NRL_TOPK_CAP_MAX_K]: a capped list lives in one register per lane.  status: the flags of the uncapped entry, no new one.
+ *   Workspace: that of the uncapped entry, nrl_topk_scores_workspace_bytes(B, V, D, k, slices): the classes are re-read from
+ *     row_class when a list is loaded and are stored nowhere.  No (B, V) matrix, no floating-point atomics, no allocation, no host
+ *     synchronisation.
+ *   Checks: those of the uncapped entry in their order, then k > NRL_TOPK_CAP_MAX_K, a null row_class (with V > 0) or
+ *     max_per_class < 1 return NRL_E_INVALID.  B == 0 and V == 0 as in the uncapped entries. */
+#define NRL_TOPK_CAP_MAX_K 64
+int nrl_topk_scores_capped(const float* user_vec, const float* table, int64_t B, int64_t V, int32_t D, int32_t k,
+                           const int32_t* row_class, int32_t max_per_class, const int64_t* excl_idx, const int64_t* excl_off,
+                           const uint8_t* eligible, int32_t slices, int64_t* out_idx, float* out_score, int32_t* status, void* ws,
+                           size_t ws_bytes, void* stream);
+int nrl_topk_ensemble_scores_capped(const float* const* users, const float* const* tables, const float* weights, int32_t T,
+                                    int64_t B, int64_t V, int32_t D, int32_t k, const int32_t* row_class, int32_t max_per_class,
+                                    const int64_t* excl_idx, const int64_t* excl_off, const uint8_t* eligible, int32_t slices,
+                                    int64_t* out_idx, float* out_score, float* out_stats /* (B, T, 2): mean, sd */,
+                                    float* moments /* (B, NRL_TOPK_STAT_CHUNKS, T, 3) caller-provided scratch */,
+                                    int32_t* status, void* ws, size_t ws_bytes, void* stream);
+
 /* nrl_topk_relu_scores: the same ranking by DKN's DNN click predictor (click_predictor.py:14-45: Linear(2 dim, Hd) -> ReLU ->
  *   Linear(Hd, 1) on [cand; user]) with the candidate list replaced by the table.  The first layer splits by columns,
  *   pred_w1 = [Wc | Wu], so with q (B, Hd) = user Wu^T + b1 (nrl_dkn_user_query) and proj (V, Hd) = table Wc^T

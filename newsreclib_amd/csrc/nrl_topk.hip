@@ -3,12 +3,14 @@
 // list (the history) and the rows an `eligible` mask removes.  The (B, V) score matrix is never written: every workgroup walks its
 // slice of the table once, tile by tile, and keeps per user only what its consumer needs.
 //
-// ONE WALK (tk_walk), five tile producers, two consumers; nine of the ten walk kernels are its instantiations and nothing else
-// (tkr_scores_kernel keeps its own text, for its speed: see there):
+// ONE WALK (tk_walk), five tile producers, three consumers; eleven of the twelve walk kernels are its instantiations and nothing
+// else (tkr_scores_kernel keeps its own text, for its speed: see there):
 //                      plain dot product   MINER interests      MANNeR ensemble     DKN factored DNN    NPA pooling
 //   producer           TkDot               TkiProducer<GATE>    TkeProducer         TkrProducer         TkpProducer
 //   TkSelect (top-k)   tk_scores_kernel    tki_scores_kernel    tke_scores_kernel   tkr_scores_kernel   tkp_scores_kernel
 //   TkCount  (rank)    tkc_count_kernel    tkic_count_kernel    tkec_count_kernel   tkrc_count_kernel   tkpc_count_kernel
+//   TkSelectCapped     tkcap_scores_kernel -                    tkecap_scores_kernel -                  -
+//     (top-k, at most m rows per class; k <= 64; merged by tk_merge_capped_kernel)
 // 256 threads, one workgroup per (slice of V, tile of users).  Per table tile of TK_BV = 128 rows:
 //   * the PRODUCER leaves the tile's scores in LDS.  TkDot: exact-fp32 MFMA (v_mfma_f32_16x16x4_f32) over LDS tiles of both
 //     operands (k-major, double-buffered, register-staged global loads as nrl_gemm.h); every score is ONE accumulator chain over
@@ -530,6 +532,150 @@ __global__ __launch_bounds__(64) void tk_merge_kernel(TkArgs A) {
   }
 }
 
+// ---- class-capped selection: the k best rows with at most m of any one class ----------------------------------------------------------
+// Every table row has a class (row_class[v], any int32) and a user's list takes a row, walking the family's order from the best
+// row down, only while fewer than m rows of its class are in it.  That list is the top k of the union of the classes' own top-m
+// sets, so like the plain top-k it does not depend on the order in which the rows are seen: TkSelectCapped streams the tiles
+// past it and tk_merge_capped_kernel merges the slices' lists by the same insertion (a row of the global answer has, class by
+// class, no more better-ranked rivals inside its slice than it has globally, so it is in its slice's answer).
+//   * TkCapList: one descending list of up to NRL_TOPK_CAP_MAX_K = 64 entries, position p in lane p, every entry with the class
+//     of its row beside it (`tag`; an empty slot, entry 0, has no class; positions from k on hold what fell off and are masked out
+//     of every count).  A candidate x of class c above the k-th entry: with g the class-c entries better than x, g >= m drops x;
+//     otherwise, when the list already holds m entries of class c, the worst of them (position w) leaves and x enters at its
+//     place pos <= w; otherwise x enters and the last entry falls off (w = 63).  Both are ONE lane-select: positions below pos
+//     and above w keep their entry, pos takes x, the positions between take their upper neighbour;
+//   * the tags are not stored: the lists in LDS, the partial lists and so the workspace and the LDS layout are those of TkSelect,
+//     and a list's tags are re-read from row_class[row] when it is loaded into registers (V * 4 bytes, resident in L2);
+//   * the threshold pruning is TkSelect's (a candidate not above the k-th entry is dropped first), against the capped list's
+//     k-th entry, which is lower: more lanes survive the ballot and are then dropped by their class, one at a time.
+// With m >= k no class ever fills up before the list does and every step is TkList's: the bits of the uncapped entry.
+struct TkCapFields {
+  const int32_t* row_class;                    // (V) the class of every table row
+  int32_t m;                                   // the rows of one class a list may hold
+};
+
+struct TkCapList {
+  unsigned long long e;
+  int32_t tag;
+  __device__ __forceinline__ unsigned long long kth(int k) const { return tk_shfl(e, k - 1); }
+  // nk (wave-uniform, of class c) is above the k-th entry and differs from every entry; false: its class is full of better rows
+  __device__ __forceinline__ bool insert(unsigned long long nk, int32_t c, int k, int m, int lane) {
+    const bool g = e > nk;                             // (false in the empty slots and from k on: those are below the k-th)
+    const bool same = lane < k && e != 0ull && tag == c;
+    if (__popcll(__ballot(same && g)) >= m) return false;
+    const unsigned long long held = __ballot(same);
+    const int pos = __popcll(__ballot(g));
+    const int w = __popcll(held) >= m ? 63 - __clzll((long long)held) : 63;
+    const unsigned long long up = tk_shfl_up1(e);
+    const int32_t tup = __shfl_up(tag, 1, 64);
+    const bool keep = lane < pos || lane > w;
+    e = keep ? e : (lane == pos ? nk : up);
+    tag = keep ? tag : (lane == pos ? c : tup);
+    return true;
+  }
+  // TkList::take over entries c with classes t
+  __device__ __forceinline__ bool take(unsigned long long c, int32_t t, unsigned long long msk, int k, int m, int lane, bool& nan) {
+    bool changed = false;
+    unsigned long long thr = kth(k);
+    while (msk) {
+      const int b = __ffsll((long long)msk) - 1;
+      msk &= msk - 1;
+      const unsigned long long nk = tk_shfl(c, b);
+      if (nk <= thr) continue;
+      if ((uint32_t)(nk >> 32) == 0xFFFFFFFFu) {
+        nan = true;
+        continue;
+      }
+      if (!insert(nk, __shfl(t, b, 64), k, m, lane)) continue;
+      thr = kth(k);
+      msk &= __ballot(c > thr);
+      changed = true;
+    }
+    return changed;
+  }
+  // the list of k <= 64 entries at L, its tags read from row_class
+  __device__ __forceinline__ void load(const unsigned long long* L, const int32_t* row_class, int k, int lane) {
+    e = lane < k ? L[lane] : 0ull;
+    tag = e ? row_class[(uint32_t)~(uint32_t)e] : 0;
+  }
+};
+
+// tk_select_user under the cap
+__device__ __forceinline__ void tk_select_user_capped(const float* row, unsigned long long* L, const int32_t* xn, const int64_t* xs,
+                                                      const int32_t* xl, const int64_t* excl_idx, const int32_t* row_class, int v0,
+                                                      bool e_0, bool e_1, int k, int m, int lane, bool& nan) {
+  const unsigned long long thr = L[k - 1];
+  const unsigned long long c0 = e_0 ? tk_entry(row[lane], (uint32_t)v0 + lane) : 0ull;
+  const unsigned long long c1 = e_1 ? tk_entry(row[64 + lane], (uint32_t)v0 + 64 + lane) : 0ull;
+  unsigned long long m0 = __ballot(c0 > thr), m1 = __ballot(c1 > thr);
+  if (!(m0 | m1)) return;
+  tk_clear_excluded(xn, xs, xl, excl_idx, v0, lane, m0, m1);
+  if (!(m0 | m1)) return;
+  const int32_t t0 = ((m0 >> lane) & 1) ? row_class[(int64_t)v0 + lane] : 0;           // (a set bit: the column is inside V)
+  const int32_t t1 = ((m1 >> lane) & 1) ? row_class[(int64_t)v0 + 64 + lane] : 0;
+  TkCapList S;
+  S.load(L, row_class, k, lane);
+  bool changed = S.take(c0, t0, m0, k, m, lane, nan);
+  changed |= S.take(c1, t1, m1 & __ballot(c1 > S.kth(k)), k, m, lane, nan);
+  if (changed) {
+    if (lane < k) L[lane] = S.e;
+    wave_lds_sync();
+  }
+}
+
+// The capped selecting consumer: TkSelect's arrays, prologue and flush; only what a user does with a tile differs.
+struct TkSelectCapped : TkSelect {
+  TkCapFields F;
+  __device__ __forceinline__ TkSelectCapped(unsigned char* p, int slots, int k_, const TkCapFields& f) : TkSelect(p, slots, k_), F(f) {}
+  __device__ __forceinline__ void user(const float* row, int ul, const int64_t* excl_idx, int v0, bool e_0, bool e_1, int lane,
+                                       bool& nan) const {
+    tk_select_user_capped(row, lists + ul * k, xn + ul, xs + ul, xl + ul * TK_XCAP, excl_idx, F.row_class, v0, e_0, e_1, k, F.m, lane,
+                          nan);
+  }
+};
+
+__global__ __launch_bounds__(TK_THREADS) void tkcap_scores_kernel(TkWith<TkArgs, TkCapFields> A) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char tk_smem[];
+  TkDot P(tk_smem);
+  TkSelectCapped C(P.rest, TK_BU, A.k, A);
+  tk_walk(A, P, C);
+}
+
+// tk_merge_kernel under the cap (k <= 64): the same flags, the slices' lists merged by the capped insertion
+__global__ __launch_bounds__(64) void tk_merge_capped_kernel(TkWith<TkArgs, TkCapFields> A) {
+  const int64_t u = blockIdx.x;
+  const int lane = threadIdx.x, k = A.k;
+  int64_t s, n;
+  const bool ok = tk_excl_range(A, u, s, n);
+  TkCapList S;
+  S.e = 0ull;
+  S.tag = 0;
+  if (!ok) {
+    if (lane == 0) atomicOr(A.status, NRL_TOPK_E_OFFSETS);
+  } else {
+    int bad = 0;
+    for (int64_t i = lane; i < n; i += 64) {
+      const int64_t x = A.excl_idx[s + i];
+      bad |= (x < 0 || x >= A.V);
+    }
+    if (__ballot(bad) && lane == 0) atomicOr(A.status, NRL_TOPK_E_EXCLUDE);
+    const unsigned long long* P = A.partial + u * A.slices * k;
+    const int64_t total = (int64_t)A.slices * k;
+    bool nan = false;
+    for (int64_t base = 0; base < total; base += 64) {
+      const unsigned long long c = base + lane < total ? P[base + lane] : 0ull;
+      const unsigned long long msk = __ballot(c > S.kth(k));
+      if (!msk) continue;
+      const int32_t t = ((msk >> lane) & 1) ? A.row_class[(uint32_t)~(uint32_t)c] : 0;
+      S.take(c, t, msk, k, A.m, lane, nan);
+    }
+  }
+  if (lane < k) {
+    A.out_idx[u * k + lane] = S.e ? (int64_t)(uint32_t)~(uint32_t)S.e : -1;
+    A.out_score[u * k + lane] = S.e ? tk_unkey((uint32_t)(S.e >> 32)) : -INFINITY;
+  }
+}
+
 // ---- multi-interest scores (MINER) ---------------------------------------------------------------------------------------------
 // A user is K interest rows; a table row's score is an aggregate of the K dot products (ops_miner.SCORE_MODES: 0 max, 1 mean,
 // 2 softmax-weighted by the K gate logits).  The row operand of the tile product is the (B * K, D) interest matrix: the 64 rows of
@@ -847,6 +993,13 @@ __global__ __launch_bounds__(TK_THREADS) void tke_scores_kernel(TkWith<TkArgs, T
   extern __shared__ __attribute__((aligned(16))) unsigned char tk_smem[];
   TkeProducer P(tk_smem, A);
   TkSelect C(P.rest, TK_BU, A.k);
+  tk_walk(A, P, C);
+}
+
+__global__ __launch_bounds__(TK_THREADS) void tkecap_scores_kernel(TkWith<TkWith<TkArgs, TkeFields>, TkCapFields> A) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char tk_smem[];
+  TkeProducer P(tk_smem, A);
+  TkSelectCapped C(P.rest, TK_BU, A.k, A);
   tk_walk(A, P, C);
 }
 
@@ -1627,11 +1780,36 @@ static TkArgs tk_args(const float* user, const float* table, int64_t B, int64_t 
   return TkArgs{user, table, B, (int32_t)V, D, k, excl_idx, excl_off, eligible, 0, 0, partial, out_idx, out_score, status};
 }
 
+// the merge that follows a scores kernel: the plain one, or the one under a class cap
+struct TkMerge {
+  int operator()(const TkArgs& A, hipStream_t st) const {
+    tk_merge_kernel<<<(unsigned)A.B, 64, 0, st>>>(A);
+    NRL_LAUNCH_CHECK();
+    return NRL_OK;
+  }
+};
+struct TkMergeCapped {
+  TkCapFields F;
+  int operator()(const TkArgs& A, hipStream_t st) const {
+    tk_merge_capped_kernel<<<(unsigned)A.B, 64, 0, st>>>(TkWith<TkArgs, TkCapFields>{A, F});
+    NRL_LAUNCH_CHECK();
+    return NRL_OK;
+  }
+};
+
+// the checks of a capped entry, after those of the entry it caps
+static int tk_cap_check(const char* who, int64_t V, int32_t k, const int32_t* row_class, int32_t max_per_class) {
+  NRL_REQUIRE(k <= NRL_TOPK_CAP_MAX_K, "%s: k in [1, %d] under a class cap (got %d)", who, NRL_TOPK_CAP_MAX_K, k);
+  NRL_REQUIRE(row_class || V == 0, "%s: row_class is required", who);
+  NRL_REQUIRE(max_per_class >= 1, "%s: max_per_class >= 1 (got %d)", who, max_per_class);
+  return NRL_OK;
+}
+
 // plans the slices, runs `kernel` (`tiles` score tiles, `bu` users per workgroup, `extra_lds` bytes of its own after the layout of
 // tk_lds_bytes) over them and then the merge
-template <class Args>
+template <class Args, class Merge = TkMerge>
 static int tk_launch(const char* who, void (*kernel)(Args), Args& A, int32_t slices, int tiles, int bu, void* stream,
-                     size_t extra_lds = 0) {
+                     size_t extra_lds = 0, Merge merge = Merge{}) {
   int64_t lists, used, tps;
   tk_plan(A.B, A.V, slices, bu, lists, used, tps);
   const int64_t blocks = ceil_div(A.B, bu) * used;
@@ -1646,9 +1824,7 @@ static int tk_launch(const char* who, void (*kernel)(Args), Args& A, int32_t sli
     kernel<<<(unsigned)blocks, TK_THREADS, smem, st>>>(A);
     NRL_LAUNCH_CHECK();
   }
-  tk_merge_kernel<<<(unsigned)A.B, 64, 0, st>>>(static_cast<const TkArgs&>(A));
-  NRL_LAUNCH_CHECK();
-  return NRL_OK;
+  return merge(A, st);
 }
 
 // The launches of a rank entry: slots and owners, `target` (the entry's target kernel: a callable that launches it), the count
@@ -1693,18 +1869,39 @@ size_t nrl_topk_scores_workspace_bytes(int64_t B, int64_t V, int32_t D, int32_t 
   return measure_workspace<unsigned long long*>([&](Arena& a, auto* w) { tk_layout(a, B, V, k, slices, TK_BU, w); });
 }
 
-int nrl_topk_scores(const float* user_vec, const float* table, int64_t B, int64_t V, int32_t D, int32_t k, const int64_t* excl_idx,
-                    const int64_t* excl_off, const uint8_t* eligible, int32_t slices, int64_t* out_idx, float* out_score,
-                    int32_t* status, void* ws, size_t ws_bytes, void* stream) {
-  NRL_REQUIRE(B >= 0 && V >= 0 && D >= 0 && slices >= 0, "topk_scores: negative size");
-  NRL_TRY(tk_check("topk_scores", B, V, D, k, excl_idx, excl_off));
-  NRL_REQUIRE(status, "topk_scores: the status word is required");
+// nrl_topk_scores (`cap` null) and nrl_topk_scores_capped: one sequence of checks, one layout; the cap picks the kernels
+static int tk_scores_entry(const char* who, const float* user_vec, const float* table, int64_t B, int64_t V, int32_t D, int32_t k,
+                           const TkCapFields* cap, const int64_t* excl_idx, const int64_t* excl_off, const uint8_t* eligible,
+                           int32_t slices, int64_t* out_idx, float* out_score, int32_t* status, void* ws, size_t ws_bytes,
+                           void* stream) {
+  NRL_REQUIRE(B >= 0 && V >= 0 && D >= 0 && slices >= 0, "%s: negative size", who);
+  NRL_TRY(tk_check(who, B, V, D, k, excl_idx, excl_off));
+  NRL_REQUIRE(status, "%s: the status word is required", who);
+  if (cap) NRL_TRY(tk_cap_check(who, V, k, cap->row_class, cap->m));
   if (B == 0) return NRL_OK;
-  NRL_REQUIRE(out_idx && out_score && user_vec && (V == 0 || table), "topk_scores: null argument");
+  NRL_REQUIRE(out_idx && out_score && user_vec && (V == 0 || table), "%s: null argument", who);
   unsigned long long* partial;
   NRL_TRY(carve_workspace(ws, ws_bytes, [&](Arena& a) { tk_layout(a, B, V, k, slices, TK_BU, &partial); }));
   TkArgs A = tk_args(user_vec, table, B, V, D, k, excl_idx, excl_off, eligible, partial, out_idx, out_score, status);
-  return tk_launch("topk_scores", tk_scores_kernel, A, slices, 1, TK_BU, stream);
+  if (!cap) return tk_launch(who, tk_scores_kernel, A, slices, 1, TK_BU, stream);
+  TkWith<TkArgs, TkCapFields> C{A, *cap};
+  return tk_launch(who, tkcap_scores_kernel, C, slices, 1, TK_BU, stream, 0, TkMergeCapped{*cap});
+}
+
+int nrl_topk_scores(const float* user_vec, const float* table, int64_t B, int64_t V, int32_t D, int32_t k, const int64_t* excl_idx,
+                    const int64_t* excl_off, const uint8_t* eligible, int32_t slices, int64_t* out_idx, float* out_score,
+                    int32_t* status, void* ws, size_t ws_bytes, void* stream) {
+  return tk_scores_entry("topk_scores", user_vec, table, B, V, D, k, nullptr, excl_idx, excl_off, eligible, slices, out_idx, out_score,
+                         status, ws, ws_bytes, stream);
+}
+
+int nrl_topk_scores_capped(const float* user_vec, const float* table, int64_t B, int64_t V, int32_t D, int32_t k,
+                           const int32_t* row_class, int32_t max_per_class, const int64_t* excl_idx, const int64_t* excl_off,
+                           const uint8_t* eligible, int32_t slices, int64_t* out_idx, float* out_score, int32_t* status, void* ws,
+                           size_t ws_bytes, void* stream) {
+  const TkCapFields cap{row_class, max_per_class};
+  return tk_scores_entry("topk_scores_capped", user_vec, table, B, V, D, k, &cap, excl_idx, excl_off, eligible, slices, out_idx,
+                         out_score, status, ws, ws_bytes, stream);
 }
 
 // the workspace of nrl_catalogue_ranks: the gathered target rows and their scores and owners, then the per-slice counts
@@ -2012,25 +2209,48 @@ static int tke_statistics(const char* who, const TkArgs& base, TkeFields& E, voi
   return NRL_OK;
 }
 
-int nrl_topk_ensemble_scores(const float* const* users, const float* const* tables, const float* weights, int32_t T, int64_t B,
-                             int64_t V, int32_t D, int32_t k, const int64_t* excl_idx, const int64_t* excl_off,
-                             const uint8_t* eligible, int32_t slices, int64_t* out_idx, float* out_score, float* out_stats,
-                             float* moments, int32_t* status, void* ws, size_t ws_bytes, void* stream) {
-  NRL_REQUIRE(B >= 0 && V >= 0 && D >= 0 && slices >= 0, "topk_ensemble_scores: negative size");
-  NRL_TRY(tke_check_sizes("topk_ensemble_scores", T));
-  NRL_TRY(tk_check("topk_ensemble_scores", B, V, D, k, excl_idx, excl_off));
-  NRL_TRY(tke_check_operands("topk_ensemble_scores", users, tables, weights, T, V));
-  NRL_REQUIRE(status, "topk_ensemble_scores: the status word is required");
-  NRL_TRY(tke_check_stats("topk_ensemble_scores", out_stats, moments));
+// nrl_topk_ensemble_scores (`cap` null) and nrl_topk_ensemble_scores_capped: the statistics pass does not know the cap
+static int tke_scores_entry(const char* who, const float* const* users, const float* const* tables, const float* weights, int32_t T,
+                            int64_t B, int64_t V, int32_t D, int32_t k, const TkCapFields* cap, const int64_t* excl_idx,
+                            const int64_t* excl_off, const uint8_t* eligible, int32_t slices, int64_t* out_idx, float* out_score,
+                            float* out_stats, float* moments, int32_t* status, void* ws, size_t ws_bytes, void* stream) {
+  NRL_REQUIRE(B >= 0 && V >= 0 && D >= 0 && slices >= 0, "%s: negative size", who);
+  NRL_TRY(tke_check_sizes(who, T));
+  NRL_TRY(tk_check(who, B, V, D, k, excl_idx, excl_off));
+  NRL_TRY(tke_check_operands(who, users, tables, weights, T, V));
+  NRL_REQUIRE(status, "%s: the status word is required", who);
+  NRL_TRY(tke_check_stats(who, out_stats, moments));
+  if (cap) NRL_TRY(tk_cap_check(who, V, k, cap->row_class, cap->m));
   if (B == 0) return NRL_OK;
-  NRL_REQUIRE(out_idx && out_score, "topk_ensemble_scores: null argument");
+  NRL_REQUIRE(out_idx && out_score, "%s: null argument", who);
   unsigned long long* partial;
   NRL_TRY(carve_workspace(ws, ws_bytes, [&](Arena& a) { tk_layout(a, B, V, k, slices, TK_BU, &partial); }));
   TkWith<TkArgs, TkeFields> A;
   static_cast<TkArgs&>(A) = tk_args(users[0], tables[0], B, V, D, k, excl_idx, excl_off, eligible, partial, out_idx, out_score, status);
   static_cast<TkeFields&>(A) = tke_fields(users, tables, weights, T, out_stats, moments);
-  NRL_TRY(tke_statistics("topk_ensemble_scores", A, A, stream));
-  return tk_launch("topk_ensemble_scores", tke_scores_kernel, A, slices, 2, TK_BU, stream, (size_t)TK_BU * T * 2 * 4);
+  NRL_TRY(tke_statistics(who, A, A, stream));
+  const size_t stats_lds = (size_t)TK_BU * T * 2 * 4;
+  if (!cap) return tk_launch(who, tke_scores_kernel, A, slices, 2, TK_BU, stream, stats_lds);
+  TkWith<TkWith<TkArgs, TkeFields>, TkCapFields> C{A, *cap};
+  return tk_launch(who, tkecap_scores_kernel, C, slices, 2, TK_BU, stream, stats_lds, TkMergeCapped{*cap});
+}
+
+int nrl_topk_ensemble_scores(const float* const* users, const float* const* tables, const float* weights, int32_t T, int64_t B,
+                             int64_t V, int32_t D, int32_t k, const int64_t* excl_idx, const int64_t* excl_off,
+                             const uint8_t* eligible, int32_t slices, int64_t* out_idx, float* out_score, float* out_stats,
+                             float* moments, int32_t* status, void* ws, size_t ws_bytes, void* stream) {
+  return tke_scores_entry("topk_ensemble_scores", users, tables, weights, T, B, V, D, k, nullptr, excl_idx, excl_off, eligible, slices,
+                          out_idx, out_score, out_stats, moments, status, ws, ws_bytes, stream);
+}
+
+int nrl_topk_ensemble_scores_capped(const float* const* users, const float* const* tables, const float* weights, int32_t T, int64_t B,
+                                    int64_t V, int32_t D, int32_t k, const int32_t* row_class, int32_t max_per_class,
+                                    const int64_t* excl_idx, const int64_t* excl_off, const uint8_t* eligible, int32_t slices,
+                                    int64_t* out_idx, float* out_score, float* out_stats, float* moments, int32_t* status, void* ws,
+                                    size_t ws_bytes, void* stream) {
+  const TkCapFields cap{row_class, max_per_class};
+  return tke_scores_entry("topk_ensemble_scores_capped", users, tables, weights, T, B, V, D, k, &cap, excl_idx, excl_off, eligible,
+                          slices, out_idx, out_score, out_stats, moments, status, ws, ws_bytes, stream);
 }
 
 size_t nrl_catalogue_ensemble_ranks_workspace_size(int32_t T, int64_t B, int64_t V, int32_t D, int64_t n_targets, int32_t slices) {

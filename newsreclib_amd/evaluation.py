@@ -23,7 +23,7 @@ Everything runs through the same C-ABI kernels; nothing here is a second impleme
 from __future__ import annotations
 
 import contextlib
-from typing import Dict, Optional, Sequence
+from typing import Dict, Optional, Sequence, Tuple
 
 import torch
 
@@ -182,6 +182,19 @@ def _catalogue_side(who: str, cache, hist_idx, hist_sizes, eligible, clicks):
     return hist_idx.to(dev).long(), eligible.to(dev) if eligible is not None else None, targets
 
 
+def _aspect_classes(cache, aspect: str) -> torch.Tensor:
+    """The class of every news under ``aspect`` as the capped top-k entries take it: ``cache.table.attrs[aspect]`` (one integer
+    per news: ``category``, ``subcategory``, ``sentiment``) as int32, converted once per aspect and kept on the cache."""
+    got = cache._row_class.get(aspect)
+    if got is None:
+        col = cache.table.attrs.get(aspect)
+        if not isinstance(col, torch.Tensor) or col.dim() != 1 or col.is_floating_point():
+            raise ValueError(f"newsreclib_amd: a class cap needs an integer news attribute with one value per news; the table has "
+                             f"no such `{aspect}`")
+        got = cache._row_class[aspect] = col.to(torch.int32)
+    return got
+
+
 class NewsVectorCache(_ImpressionCache):
     """Encode-once evaluation of a drop-in recommender (any of the module mirrors: NRMS, LSTUR, NAML, TANR,
     CenNewsRec, MINS -- whatever exposes ``news_encoder`` and ``score_news_vectors``)."""
@@ -190,6 +203,7 @@ class NewsVectorCache(_ImpressionCache):
         self.module, self.table, self.chunk = module, table, int(chunk)
         self.vectors: Optional[torch.Tensor] = None
         self.projection: Optional[torch.Tensor] = None      # (num_news, Hd): ``recommend_dnn``'s share of the table, built lazily
+        self._row_class: Dict[str, torch.Tensor] = {}       # aspect -> (num_news) int32: ``recommend_capped``'s classes
 
     @torch.no_grad()
     def build(self) -> torch.Tensor:
@@ -336,6 +350,19 @@ class NewsVectorCache(_ImpressionCache):
         return ops.topk_scores(user, self.vectors, k, *tail)
 
     @torch.no_grad()
+    def recommend_capped(self, hist_idx: torch.Tensor, hist_sizes: torch.Tensor, k: int, aspect: str, max_per_class: int,
+                         user_idx: Optional[torch.Tensor] = None, exclude_history: bool = True,
+                         eligible: Optional[torch.Tensor] = None):
+        """``recommend`` with a diversity constraint on the list itself: the ``k`` (at most ``ops.TOPK_CAP_MAX_K``) best news of
+        each user with at most ``max_per_class`` of any one class of ``aspect``, a news attribute of the table with one integer
+        per news (``category``, ``subcategory``, ``sentiment``) -> (news_idx (B, k) int64, scores (B, k) fp32, status).  The user
+        side, the scores, the order, the exclusion of the history, ``eligible`` and the refusals are ``recommend``'s;
+        ``ops.topk_scores_capped`` selects.  Slots beyond the rows that qualify hold ``-1`` / ``-inf``, which also happens when
+        the classes together admit fewer than ``k`` rows.  Nothing is read back."""
+        user, _, tail = self._dot_users("recommend", hist_idx, hist_sizes, user_idx, exclude_history, eligible, None)
+        return ops.topk_scores_capped(user, self.vectors, k, _aspect_classes(self, aspect), max_per_class, *tail)
+
+    @torch.no_grad()
     def rank_clicks(self, hist_idx: torch.Tensor, hist_sizes: torch.Tensor, click_idx: torch.Tensor, click_sizes: torch.Tensor,
                     user_idx: Optional[torch.Tensor] = None, exclude_history: bool = True,
                     eligible: Optional[torch.Tensor] = None):
@@ -427,6 +454,7 @@ class MannerVectorCache(_ImpressionCache):
         self.weights = [w for _, w in pairs]
         self.caches = [NewsVectorCache(m, table, chunk) for m, _ in pairs]
         self.vectors = None
+        self._row_class: Dict[str, torch.Tensor] = {}       # aspect -> (num_news) int32: ``recommend_ensemble_capped``'s classes
 
     @torch.no_grad()
     def build(self):
@@ -473,6 +501,19 @@ class MannerVectorCache(_ImpressionCache):
         ``NewsVectorCache.recommend``: ``hist_idx`` on the GPU, ``hist_sizes`` on the host, nothing read back."""
         users, _, tail = self._ensemble_users("recommend_ensemble", hist_idx, hist_sizes, user_idx, exclude_history, eligible, None)
         idx, score, status, stats = ops.topk_ensemble_scores(users, self.vectors, self.weights, k, *tail)
+        return (idx, score, status, stats) if return_stats else (idx, score, status)
+
+    @torch.no_grad()
+    def recommend_ensemble_capped(self, hist_idx: torch.Tensor, hist_sizes: torch.Tensor, k: int, aspect: str, max_per_class: int,
+                                  user_idx: Optional[torch.Tensor] = None, exclude_history: bool = True,
+                                  eligible: Optional[torch.Tensor] = None, return_stats: bool = False):
+        """``recommend_ensemble`` with at most ``max_per_class`` news of any one class of ``aspect`` in a user's list, as
+        ``NewsVectorCache.recommend_capped`` caps ``recommend``: the users, the population, the statistics and the scores are
+        ``recommend_ensemble``'s (the z-scores do not know the cap), ``ops.topk_ensemble_scores_capped`` selects."""
+        users, _, tail = self._ensemble_users("recommend_ensemble_capped", hist_idx, hist_sizes, user_idx, exclude_history, eligible,
+                                              None)
+        idx, score, status, stats = ops.topk_ensemble_scores_capped(users, self.vectors, self.weights, k,
+                                                                    _aspect_classes(self, aspect), max_per_class, *tail)
         return (idx, score, status, stats) if return_stats else (idx, score, status)
 
     def _ensemble_users(self, who: str, hist_idx, hist_sizes, user_idx, exclude_history: bool, eligible, clicks):
@@ -687,14 +728,25 @@ def format_recommendations(user_ids: Sequence, news_idx: torch.Tensor, scores: t
 
 
 def recommend_users(cache: NewsVectorCache, users: Sequence[Dict], k: int, batch_size: int = 512,
-                    eligible: Optional[torch.Tensor] = None) -> Dict[str, Dict[str, float]]:
+                    eligible: Optional[torch.Tensor] = None, cap: Optional[Tuple[str, int]] = None) -> Dict[str, Dict[str, float]]:
     """``cache.recommend`` (``cache.recommend_interests`` where the cache's module is a ``multi_interest_scorer``,
     ``cache.recommend_dnn`` where it is a ``dnn_predictor_scorer``, ``cache.recommend_pooled`` where it is a
     ``personalized_pooling_scorer``: ``NpaFeatureCache``, whose users need ``user_idx``,
     ``cache.recommend_ensemble`` where the cache has one: ``MannerVectorCache``) over a list of
     users ({"hist": idx tensor[, "user_idx", "user_id"]}) in batches -> the recommendation dictionary of ``format_recommendations``.  ``user_id`` defaults to the user's position in the list + 1 (as ``build_batch``);
     news ids come from the table's ``news_ids`` column when it has one.  One device-to-host copy per batch, at its end; a status
-    flag of the batch (``ops.TOPK_FLAGS``: each is handled by the kernel) is passed on as a warning."""
+    flag of the batch (``ops.TOPK_FLAGS``: each is handled by the kernel) is passed on as a warning.
+
+    ``cap`` = (aspect, max_per_class): at most that many news of any one class of the table's ``aspect`` column in a user's list
+    (``cache.recommend_ensemble_capped`` where the cache has one, else ``cache.recommend_capped``).  ``NotImplementedError`` for
+    the caches of the other scorers (MINER, DKN, NPA): their capped kernels do not exist yet."""
+    if cap is not None:
+        other = [a for a in ("multi_interest_scorer", "dnn_predictor_scorer", "personalized_pooling_scorer")
+                 if getattr(cache.module, a, False)]
+        if other:
+            raise NotImplementedError(f"recommend_users(cap=...) serves the dot-product families and MANNeR's ensemble; "
+                                      f"{type(cache.module).__name__} is a `{other[0]}`, whose capped top-k kernel does not exist yet")
+        aspect, max_per_class = cap
     dev = cache.table.device
     news_ids = cache.table.attrs["news_ids"].cpu() if "news_ids" in cache.table.attrs else None
     out: Dict[str, Dict[str, float]] = {}
@@ -707,6 +759,9 @@ def recommend_users(cache: NewsVectorCache, users: Sequence[Dict], k: int, batch
             cache.recommend_dnn if getattr(cache.module, "dnn_predictor_scorer", False) else \
             cache.recommend_pooled if getattr(cache.module, "personalized_pooling_scorer", False) else cache.recommend
         rank = getattr(cache, "recommend_ensemble", rank)
+        if cap is not None:
+            capped = getattr(cache, "recommend_ensemble_capped", None) or cache.recommend_capped
+            rank = lambda hist, hs, k, **kw: capped(hist, hs, k, aspect, max_per_class, **kw)  # noqa: E731
         idx, score, status = rank(hist, hs, k, user_idx=uidx, eligible=eligible)
         packed = torch.cat([idx.double(), score.double(), status.double().expand(idx.shape[0], 1)], dim=1).cpu()      # the one copy
         word = int(packed[0, -1]) if packed.shape[0] else 0

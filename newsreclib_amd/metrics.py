@@ -195,6 +195,34 @@ def impression_metrics(preds: torch.Tensor, targets: torch.Tensor, cand_news_siz
     return out
 
 
+def recommendation_aspect_metrics(idx: torch.Tensor, scores: torch.Tensor, row_class: torch.Tensor, hist_idx: torch.Tensor,
+                                  hist_off: torch.Tensor, num_classes: int, top_k_list: Sequence[int] = (5, 10),
+                                  prefix: str = "categ") -> Dict[str, float]:
+    """``{prefix}_div@k`` / ``{prefix}_pers@k`` of recommendation LISTS, mean over users: what a class cap
+    (``ops.topk_scores_capped``, ``NewsVectorCache.recommend_capped``) buys, in the terms of ``aspect_metrics``.  ``idx`` /
+    ``scores`` (B, k): the lists as ``ops.topk_*`` return them (a slot with ``idx < 0`` is empty and left out); ``row_class``
+    (V): the class of every news, in [0, num_classes); ``hist_idx`` / ``hist_off`` (B + 1): the ragged histories the
+    personalization compares with.  Each user's valid slots are ONE impression of ``impression_metrics`` (candidates: the list,
+    scores: its scores), so the values are those ``aspect_metrics`` gives the same lists.  GPU tensors; Python only: no kernel
+    of its own.  One read of the status word and of the means at the end (``ValueError`` when the kernel refused a list)."""
+    from . import ops
+    dev = idx.device
+    valid = idx >= 0
+    rows = idx[valid]
+    preds = scores.float()[valid]
+    row_class, hist_off = row_class.to(dev).long(), hist_off.to(dev).long()
+    out = impression_metrics(preds, torch.zeros_like(preds), valid.sum(1), top_k_list,
+                             {prefix: (row_class[rows], row_class[hist_idx.to(dev).long()], int(num_classes))},
+                             hist_off[1:] - hist_off[:-1])
+    flags = int(out["status"])
+    if flags:
+        raise ValueError("recommendation_aspect_metrics: the metrics kernel refused input: " +
+                         "; ".join(msg for bit, msg in ops.METRICS_FLAGS.items() if flags & bit))
+    keys = [f"{prefix}_{m}@{k}" for k in top_k_list for m in ("div", "pers")]
+    B = int(idx.shape[0])
+    return {key: float(out[key].double().mean()) if B else 0.0 for key in keys}
+
+
 class StreamingMetrics:
     """Epoch metrics without the epoch's step outputs: ``update`` takes the tuple ``model_step`` / ``*Cache.model_step`` returns
     and launches ``nrl_impression_metrics`` into a float64 accumulator (one sum per metric column, an impression count and a status

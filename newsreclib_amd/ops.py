@@ -824,6 +824,36 @@ def topk_scores(user_vec: torch.Tensor, table: torch.Tensor, k: int, excl_idx: O
     return _run_topk("nrl_topk_scores", _dot_scorer(user_vec, table), k, excl_idx, excl_off, eligible, slices)
 
 
+TOPK_CAP_MAX_K = 64
+
+
+def _capped(s: _Scorer, row_class: torch.Tensor, max_per_class: int) -> _Scorer:
+    """Scorer ``s`` with the class cap behind ``k``: ``row_class`` checked (one int32 per table row; int64 converted by one device
+    op); the native entry checks ``k`` and ``max_per_class`` before it launches anything."""
+    if row_class is None:
+        raise ValueError("newsreclib_amd: row_class (one class id per table row) is required")
+    if row_class.dtype == torch.int64 and row_class.is_cuda:
+        row_class = row_class.to(torch.int32)
+    row_class = _chk(row_class, torch.int32, "row_class")
+    if row_class.dim() != 1 or row_class.numel() != s.V:
+        raise ValueError(f"newsreclib_amd: row_class must have one entry per table row ({s.V}), got {tuple(row_class.shape)}")
+    m = max(min(int(max_per_class), 2 ** 31 - 1), 0)                          # (as an int32; anything below 1 is refused natively)
+    return s._replace(trail=(*s.trail, row_class.data_ptr(), m), keep=(*s.keep, row_class))
+
+
+def topk_scores_capped(user_vec: torch.Tensor, table: torch.Tensor, k: int, row_class: torch.Tensor, max_per_class: int,
+                       excl_idx: Optional[torch.Tensor] = None, excl_off: Optional[torch.Tensor] = None,
+                       eligible: Optional[torch.Tensor] = None, slices: int = 0):
+    """``nrl_topk_scores_capped``: ``topk_scores`` with at most ``max_per_class`` rows of any one class in a user's list.
+    ``row_class`` (V int32, or int64: converted by one device op) gives every table row its class (a category, a subcategory, a
+    sentiment class; any value is a class of its own).  Walking a user's rows that are eligible, not excluded and not NaN-scored
+    in ``topk_scores``' order, a row is taken while fewer than ``max_per_class`` rows of its class have been; the first ``k``
+    (at most ``TOPK_CAP_MAX_K``) are returned, ``-1`` / ``-inf`` beyond them.  Returns, flags and the rest of the arguments are
+    those of ``topk_scores``; with ``max_per_class >= k`` so are the bits.  Nothing here synchronises with the host."""
+    s = _capped(_dot_scorer(user_vec, table), row_class, max_per_class)
+    return _run_topk("nrl_topk_scores_capped", s, k, excl_idx, excl_off, eligible, slices)
+
+
 RANK_MAX_TARGETS = 32
 # the status word of ``catalogue_ranks``: the flags of ``topk_scores`` it shares, in its own words, and its two own bits
 RANK_FLAGS = {1: TOPK_FLAGS[1],
@@ -936,6 +966,17 @@ def topk_ensemble_scores(users: Sequence[torch.Tensor], tables: Sequence[torch.T
     standardised gets ``-1`` / ``-inf``.  No (B, V) matrix is materialised; nothing here synchronises with the host."""
     s, stats, moments = _ensemble_scorer(users, tables, weights)
     return (*_run_topk("nrl_topk_ensemble_scores", s, k, excl_idx, excl_off, eligible, slices, extra=(stats, moments)), stats)
+
+
+def topk_ensemble_scores_capped(users: Sequence[torch.Tensor], tables: Sequence[torch.Tensor], weights: Sequence[float], k: int,
+                                row_class: torch.Tensor, max_per_class: int, excl_idx: Optional[torch.Tensor] = None,
+                                excl_off: Optional[torch.Tensor] = None, eligible: Optional[torch.Tensor] = None, slices: int = 0):
+    """``nrl_topk_ensemble_scores_capped``: ``topk_ensemble_scores`` with at most ``max_per_class`` rows of any one class of
+    ``row_class`` in a user's list, as ``topk_scores_capped`` caps ``topk_scores``.  The statistics do not know the cap: they are
+    those of ``topk_ensemble_scores``, bit for bit, and so is every returned score.  -> (idx, score, status, stats) as there."""
+    s, stats, moments = _ensemble_scorer(users, tables, weights)
+    s = _capped(s, row_class, max_per_class)
+    return (*_run_topk("nrl_topk_ensemble_scores_capped", s, k, excl_idx, excl_off, eligible, slices, extra=(stats, moments)), stats)
 
 
 # the status word of ``catalogue_ensemble_ranks``: the flags of ``catalogue_ranks`` and, worded for ranks, the one of the ensemble
