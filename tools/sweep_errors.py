@@ -8,11 +8,12 @@ not assert it.
 pytest prints a test's progress character without a newline, so a test's first line arrives as ``.SWEEP ...``: lines are
 searched, not matched at their start, and the tool fails when it kept fewer lines than the run printed.
 
-    python tools/sweep_errors.py [--tests npa_dkn | sd_manner | tests/FILE.py] [--out FILE] [--log FILE] [--timeout SECONDS]
+    python tools/sweep_errors.py [--tests npa_dkn | sd_manner | caum_miner | tests/FILE.py] [--out FILE] [--log FILE]
+                                 [--timeout SECONDS]
 
 ``--tests npa_dkn`` (the default) runs tests/test_gpu_npa_dkn_sweep.py into profiles/npa_dkn_sweep_errors.txt,
-``--tests sd_manner`` tests/test_gpu_sd_manner_sweep.py into profiles/sd_manner_sweep_errors.txt; a path runs that file
-and needs ``--out``."""
+``--tests sd_manner`` tests/test_gpu_sd_manner_sweep.py into profiles/sd_manner_sweep_errors.txt, ``--tests caum_miner``
+tests/test_gpu_caum_miner_sweep.py into profiles/caum_miner_sweep_errors.txt; a path runs that file and needs ``--out``."""
 import argparse
 import os
 import re
@@ -23,13 +24,14 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SWEEPS = {
     "npa_dkn": ("tests/test_gpu_npa_dkn_sweep.py", "forward 5 ftol, gradients gtol max(1, |want|_max)"),
     "sd_manner": ("tests/test_gpu_sd_manner_sweep.py", "the larger of the project's bound and 4x oracle32; MANNeR: 4x oracle32, SupCon x3 under bf16x3"),
+    "caum_miner": ("tests/test_gpu_caum_miner_sweep.py", "forward 5 ftol, gradients gtol max(1, |want|_max); above a configured width the larger of that and 4x oracle32"),
 }
 LINE = re.compile(r"SWEEP (\S+) (\S+) (.+): kernel (\S+) oracle32 (\S+) tol (\S+)( FAIL)?$")
 
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--tests", default="npa_dkn", help="npa_dkn, sd_manner, or the path of a sweep file")
+    ap.add_argument("--tests", default="npa_dkn", help="npa_dkn, sd_manner, caum_miner, or the path of a sweep file")
     ap.add_argument("--out", help="the table (default: profiles/<tests>_sweep_errors.txt)")
     ap.add_argument("--log", help="also keep pytest's whole output here")
     ap.add_argument("--timeout", type=float, default=300.0, help="limit of the pytest run in seconds (it takes about 10)")
