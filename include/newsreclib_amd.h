@@ -1167,6 +1167,48 @@ int nrl_topk_ensemble_scores_capped(const float* const* users, const float* cons
                                     float* moments /* (B, NRL_TOPK_STAT_CHUNKS, T, 3) caller-provided scratch */,
                                     int32_t* status, void* ws, size_t ws_bytes, void* stream);
 
+/* nrl_topk_bias_scores / nrl_topk_bias_scores_capped / nrl_catalogue_bias_ranks: nrl_topk_scores / nrl_topk_scores_capped /
+ *   nrl_catalogue_ranks by a dot product plus a per-(user, class) additive term: the soft counterpart of the class cap (a user's
+ *   category-affinity prior, a sentiment penalty) and the combined score SentiDebias's generator is trained on,
+ *   u_free . n_v + (u_aware T^T)[u, sentiment(v)].  Every argument of the dot-product entry keeps its meaning; three are added
+ *   behind D:
+ *   bias (B, S) fp32, row-major, device: the term of user u and class c is bias[u * S + c].
+ *   row_class (V int32, device): the class of every table row, for the bias.
+ *   S in [1, NRL_TOPK_MAX_BIAS_CLASSES]: a workgroup keeps the bias rows of its 64 users in LDS.
+ *   Score: score(u, v) = fl32(dot(u, v) + bias[u, row_class[v]]): dot(u, v) is the value of nrl_topk_scores for that pair, the same
+ *     accumulator chain with the same bits, and the bias is added by ONE fp32 add behind the chain (never as a further k step).
+ *     So with an all +0 bias the rows are those of nrl_topk_scores and the scores compare equal, and a score's bits do not depend
+ *     on B, V, k, slices, the grid or the GEMM engine setting.
+ *   A class id outside [0, S), negative ids included: the row is scored with bias +0 and NRL_TOPK_E_CLASS is ORed into status
+ *     (for any such row inside V, eligible or not).  Nothing is read back and nothing is validated on the host.
+ *   Order, exclusion lists, eligible, -1 / -inf padding, slices, the other flags and the workspace
+ *     (nrl_topk_scores_workspace_bytes / nrl_catalogue_ranks_workspace_size) are those of the dot-product entries.  A NaN score
+ *     (a NaN bias, inf - inf) of an eligible, not excluded row sets NRL_TOPK_E_NAN and the row is left out for that user.
+ *   The capped entry adds cap_class (V int32) / max_per_class behind k as nrl_topk_scores_capped does: the cap's classes are an
+ *     array of their own (the cap may go by category while the bias goes by sentiment; the same pointer is fine).  With
+ *     max_per_class >= k it returns the bits of nrl_topk_bias_scores.
+ *   The rank entry: targets, population, out_rank / out_score / out_ranked and NRL_RANK_E_* as for nrl_catalogue_ranks; a target's
+ *     score is the same chain over the gathered row and the same single add, so out_score[j] has the bits nrl_topk_bias_scores
+ *     returns for that (user, row) and out_rank[j] = r <= k if and only if out_idx[u, r - 1] == tgt_idx[j].
+ *   Checks, in this order: those of the dot-product entry under this entry's name; S outside its range, a null bias or a null
+ *     row_class with V > 0; for the capped entry those of nrl_topk_scores_capped.  All return NRL_E_INVALID before any launch.
+ *     B == 0 returns success without a launch.  No floating-point atomics, no allocation, no host synchronisation. */
+#define NRL_TOPK_MAX_BIAS_CLASSES 64
+#define NRL_TOPK_E_CLASS 64 /* a class id outside [0, S): that row is scored with bias +0 */
+int nrl_topk_bias_scores(const float* user_vec, const float* table, int64_t B, int64_t V, int32_t D, const float* bias,
+                         const int32_t* row_class, int32_t S, int32_t k, const int64_t* excl_idx, const int64_t* excl_off,
+                         const uint8_t* eligible, int32_t slices, int64_t* out_idx, float* out_score, int32_t* status, void* ws,
+                         size_t ws_bytes, void* stream);
+int nrl_topk_bias_scores_capped(const float* user_vec, const float* table, int64_t B, int64_t V, int32_t D, const float* bias,
+                                const int32_t* row_class, int32_t S, int32_t k, const int32_t* cap_class, int32_t max_per_class,
+                                const int64_t* excl_idx, const int64_t* excl_off, const uint8_t* eligible, int32_t slices,
+                                int64_t* out_idx, float* out_score, int32_t* status, void* ws, size_t ws_bytes, void* stream);
+int nrl_catalogue_bias_ranks(const float* user_vec, const float* table, int64_t B, int64_t V, int32_t D, const float* bias,
+                             const int32_t* row_class, int32_t S, const int64_t* tgt_idx, const int64_t* tgt_off,
+                             int64_t n_targets, const int64_t* excl_idx, const int64_t* excl_off, const uint8_t* eligible,
+                             int32_t slices, int32_t* out_rank /* n_targets */, float* out_score /* n_targets */,
+                             int32_t* out_ranked /* B */, int32_t* status, void* ws, size_t ws_bytes, void* stream);
+
 /* nrl_topk_relu_scores: the same ranking by DKN's DNN click predictor (click_predictor.py:14-45: Linear(2 dim, Hd) -> ReLU ->
  *   Linear(Hd, 1) on [cand; user]) with the candidate list replaced by the table.  The first layer splits by columns,
  *   pred_w1 = [Wc | Wu], so with q (B, Hd) = user Wu^T + b1 (nrl_dkn_user_query) and proj (V, Hd) = table Wc^T

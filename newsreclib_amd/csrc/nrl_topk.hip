@@ -3,8 +3,9 @@
 // list (the history) and the rows an `eligible` mask removes.  The (B, V) score matrix is never written: every workgroup walks its
 // slice of the table once, tile by tile, and keeps per user only what its consumer needs.
 //
-// ONE WALK (tk_walk), five tile producers, three consumers; eleven of the twelve walk kernels are its instantiations and nothing
-// else (tkr_scores_kernel keeps its own text, for its speed: see there):
+// ONE WALK (tk_walk), six tile producers, three consumers; fourteen of the fifteen walk kernels are its instantiations and nothing
+// else (tkr_scores_kernel keeps its own text, for its speed: see there).  The sixth producer, TkBiasProducer (the dot product plus
+// a per-(user, class) bias: tkb_scores_kernel, tkbc_count_kernel, tkbcap_scores_kernel), is TkDot's column with one add behind it:
 //                      plain dot product   MINER interests      MANNeR ensemble     DKN factored DNN    NPA pooling
 //   producer           TkDot               TkiProducer<GATE>    TkeProducer         TkrProducer         TkpProducer
 //   TkSelect (top-k)   tk_scores_kernel    tki_scores_kernel    tke_scores_kernel   tkr_scores_kernel   tkp_scores_kernel
@@ -674,6 +675,103 @@ __global__ __launch_bounds__(64) void tk_merge_capped_kernel(TkWith<TkArgs, TkCa
     A.out_idx[u * k + lane] = S.e ? (int64_t)(uint32_t)~(uint32_t)S.e : -1;
     A.out_score[u * k + lane] = S.e ? tk_unkey((uint32_t)(S.e >> 32)) : -INFINITY;
   }
+}
+
+// ---- class-biased scores: the dot product plus a per-(user, class) additive term ------------------------------------------------------
+// score(u, v) = fl32(dot(u, v) + bias[u, c]), c = bias_class[v]: the accumulator chain of TkDot, bit for bit, and then ONE fp32 add
+// (never a further k step of the chain).  bias (B, S) fp32, S <= NRL_TOPK_MAX_BIAS_CLASSES; a class id outside [0, S) is scored
+// with bias +0 and sets NRL_TOPK_E_CLASS.  The soft counterpart of the class cap above, and SentiDebias's combined score.
+//   * the bias rows of the workgroup's 64 users are staged once, [TK_BU][ld] behind the score tile; column S of every row is +0 and
+//     is where a bad class id points, so the add has no branch;
+//   * per table tile the 128 class ids (already mapped into [0, S]) are staged behind them, and the add is done on the accumulator
+//     fragments before they are stored: no second pass over the tile and no further barrier.  A lane reads, per fragment register,
+//     bias[4 g + r][class of column l15]: within the 32 lanes a ds_read_b32 banks together that is two rows (g and g + 1) times up
+//     to 16 classes; equal classes are one address (a broadcast), and ld = 4 (mod 8) puts the two rows 16 banks apart, so up to
+//     16 classes never conflict and more can only where two columns' classes are 16 (other row) or 32 (same row) apart.
+struct TkbFields {
+  const float* bias;                           // (B, S)
+  const int32_t* bias_class;                   // (V) the class of every table row, for the bias
+  int32_t S;
+};
+
+constexpr int tkb_ld(int S) { return (S + 4) / 8 * 8 + 4; }                  // the smallest ld >= S + 1 with ld = 4 (mod 8)
+constexpr size_t tkb_extra_lds(int S) { return (size_t)TK_BU * tkb_ld(S) * 4 + TK_BV * 4; }
+static_assert(tkb_ld(1) == 4 && tkb_ld(3) == 4 && tkb_ld(4) == 12 && tkb_ld(19) == 20 && tkb_ld(NRL_TOPK_MAX_BIAS_CLASSES) == 68,
+              "room for the zero column, 16 banks between rows 4 apart");
+static_assert(tkb_extra_lds(1) % 16 == 0 && tkb_extra_lds(NRL_TOPK_MAX_BIAS_CLASSES) % 16 == 0 && (TK_BU * 8 * 4) % 16 == 0,
+              "what follows the bias rows and the class ids is 16-byte aligned, for every S");
+static_assert(tk_lds_bytes(1, TK_BU, NRL_TOPK_MAX_K) + tkb_extra_lds(NRL_TOPK_MAX_BIAS_CLASSES) <= 160 * 1024,
+              "the largest layout fits the dynamic LDS the launch may request");
+
+// the class of table row v as the add reads it: S (the zero column) for an id outside [0, S), which is flagged
+__device__ __forceinline__ int tkb_class(const TkbFields& F, int64_t v, bool& bad) {
+  const int32_t c = F.bias_class[v];
+  bad = c < 0 || c >= F.S;
+  return bad ? F.S : c;
+}
+
+// The producer of the class-biased kernels: TkDot's tile, every element with its (user, class) bias added once.
+struct TkBiasProducer : TkBlocked {
+  float* sc;                                   // [TK_BU][TK_SCLD]; until the scores exist, the operand tiles
+  float* bl;                                   // [TK_BU][ld] the users' bias rows; column S (and the rows past B) +0
+  int32_t* cl;                                 // [TK_BV] the tile's class ids in [0, S]
+  unsigned char* rest;
+  const TkbFields& F;
+  int ld;
+  const float* pa[1];
+  bool ua_ok;
+  __device__ __forceinline__ TkBiasProducer(unsigned char* p, const TkbFields& f)
+      : sc(reinterpret_cast<float*>(p)), bl(sc + TK_BU * TK_SCLD), cl(reinterpret_cast<int32_t*>(bl + TK_BU * tkb_ld(f.S))),
+        rest(p + TK_TILE_BYTES + tkb_extra_lds(f.S)), F(f), ld(tkb_ld(f.S)) {}
+  __device__ __forceinline__ int slots() const { return TK_BU; }
+  __device__ __forceinline__ void stage(const TkArgs& A, int64_t u0, int nu) {
+    const int srow = threadIdx.x >> 2;
+    ua_ok = srow < nu;
+    pa[0] = A.user + (ua_ok ? u0 + srow : A.B - 1) * A.D;
+    for (int i = threadIdx.x; i < TK_BU * ld; i += TK_THREADS) {             // (the consumer's prologue publishes the rows)
+      const int ul = i / ld, c = i % ld;
+      bl[i] = (ul < nu && c < F.S) ? F.bias[(u0 + ul) * F.S + c] : 0.f;
+    }
+  }
+  __device__ __forceinline__ void tile(const TkArgs& A, int v0, int) const {
+    const int tid = threadIdx.x, lane = tid & 63;
+    if (tid < TK_BV) {                                // (rows past V: any class, eligibility drops them)
+      const int64_t v = (int64_t)v0 + tid;
+      bool bad = false;
+      cl[tid] = v < A.V ? tkb_class(F, v, bad) : F.S;
+      if (__ballot(bad) && lane == 0) atomicOr(A.status, NRL_TOPK_E_CLASS);
+    }
+    tk_f32x4 acc[1][2][4];
+    tk_tile_accumulate<1>(pa, ua_ok, A.table, A.D, v0, A.V, A.D, sc, acc);   // (its barriers publish `cl`)
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int wm = wave >> 1, wn = wave & 1, l15 = lane & 15, g = lane >> 4;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const float* const b = bl + cl[wn * 64 + j * 16 + l15];
+#pragma unroll
+      for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) acc[0][i][j][r] = __fadd_rn(acc[0][i][j][r], b[(wm * 32 + i * 16 + 4 * g + r) * ld]);
+    }
+    tk_store_fragments(acc[0], sc);
+    __syncthreads();
+  }
+  __device__ __forceinline__ const float* row(int ul) const { return sc + ul * TK_SCLD; }
+  __device__ __forceinline__ bool skip(int) const { return false; }
+};
+
+__global__ __launch_bounds__(TK_THREADS) void tkb_scores_kernel(TkWith<TkArgs, TkbFields> A) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char tk_smem[];
+  TkBiasProducer P(tk_smem, A);
+  TkSelect C(P.rest, TK_BU, A.k);
+  tk_walk(A, P, C);
+}
+
+__global__ __launch_bounds__(TK_THREADS) void tkbcap_scores_kernel(TkWith<TkWith<TkArgs, TkbFields>, TkCapFields> A) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char tk_smem[];
+  TkBiasProducer P(tk_smem, A);
+  TkSelectCapped C(P.rest, TK_BU, A.k, A);
+  tk_walk(A, P, C);
 }
 
 // ---- multi-interest scores (MINER) ---------------------------------------------------------------------------------------------
@@ -1550,6 +1648,41 @@ __global__ __launch_bounds__(TK_THREADS) void tkc_count_kernel(TkcArgs A) {
 // Each is the walk under its scorer's producer -- the one its scores kernel runs, so a score's bits cannot differ between the
 // top-k list and the rank -- with the counting consumer, and a target kernel that computes the slots' scores by the same chain.
 
+// The class bias.  The score tile, the bias rows and class ids, then the consumer's arrays: 74.9 KB + 1.5 KB (S <= 3) ... 17.5 KB.
+static_assert(TKC_LDS + tkb_extra_lds(NRL_TOPK_MAX_BIAS_CLASSES) <= 160 * 1024, "the biased count kernel's largest layout fits");
+static_assert(2 * (TKC_LDS + tkb_extra_lds(8)) <= 160 * 1024, "up to 8 classes two workgroups of it fit a CU");
+
+// tkc_target_kernel, then the one add of the producer: slot j's score is the diagonal plus bias[owner, class of the target row]
+__global__ __launch_bounds__(TK_THREADS) void tkbc_target_kernel(TkWith<TkcArgs, TkbFields> A) {
+  __shared__ __attribute__((aligned(16))) float sc[TK_BU * TK_SCLD];
+  const int tid = threadIdx.x;
+  const int64_t j0 = (int64_t)blockIdx.x * TK_BU;
+  const int srow = tid >> 2;
+  const int own = j0 + srow < A.n_targets ? A.owner[j0 + srow] : -1;
+  const bool ua_ok = own >= 0;
+  const float* const pa[1] = {A.user + (int64_t)(ua_ok ? own : 0) * A.D};
+  tk_tile_product<1>(pa, ua_ok, A.gathered, (int)j0, (int)A.n_targets, A.D, sc);
+  if (tid < TK_BU && j0 + tid < A.n_targets) {
+    // (its own staging row is another slot's: the owner is read again.  The walk flags a bad class id of any row inside V.)
+    const int jown = A.owner[j0 + tid];
+    const int64_t row = A.tgt_idx[j0 + tid];
+    float b = 0.f;
+    if (jown >= 0 && row >= 0 && row < A.V) {
+      bool bad;
+      const int c = tkb_class(A, row, bad);
+      if (!bad) b = A.bias[(int64_t)jown * A.S + c];
+    }
+    A.tscore[j0 + tid] = __fadd_rn(sc[tid * TK_SCLD + tid], b);
+  }
+}
+
+__global__ __launch_bounds__(TK_THREADS) void tkbc_count_kernel(TkWith<TkcArgs, TkbFields> A) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char tk_smem[];
+  TkBiasProducer P(tk_smem, A);
+  TkCount C(P.rest, TK_BU);
+  tk_walk(A, P, C);
+}
+
 // MINER.  A workgroup holds Ut = 64 / K users, so the consumer's arrays are [Ut][...].
 constexpr size_t tkic_lds_bytes(bool gate, int Ut) { return (gate ? 2 : 1) * TK_TILE_BYTES + tkc_lds_bytes(Ut); }
 static_assert(2 * tkic_lds_bytes(false, TK_BU) <= 160 * 1024, "max / mean: two workgroups of the interest count kernel fit a CU");
@@ -2285,6 +2418,77 @@ int nrl_catalogue_ensemble_ranks(const float* const* users, const float* const* 
       NRL_LAUNCH_CHECK();
     }
     tkec_target_kernel<<<(unsigned)ceil_div(n_targets, TK_BU), TK_THREADS, 0, st>>>(A);
+    NRL_LAUNCH_CHECK();
+    return NRL_OK;
+  });
+}
+
+// The class bias: the dot product's entries with (bias, bias_class, S) behind D
+static int tkb_check(const char* who, const float* bias, const int32_t* bias_class, int32_t S, int64_t V) {
+  NRL_REQUIRE(S >= 1 && S <= NRL_TOPK_MAX_BIAS_CLASSES, "%s: S in [1, %d] (got %d)", who, NRL_TOPK_MAX_BIAS_CLASSES, S);
+  NRL_REQUIRE(bias, "%s: bias is required", who);
+  NRL_REQUIRE(bias_class || V == 0, "%s: row_class is required", who);
+  return NRL_OK;
+}
+
+// nrl_topk_bias_scores (`cap` null) and nrl_topk_bias_scores_capped: tk_scores_entry with the bias fields
+static int tkb_scores_entry(const char* who, const float* user_vec, const float* table, int64_t B, int64_t V, int32_t D,
+                            const TkbFields& bias, int32_t k, const TkCapFields* cap, const int64_t* excl_idx, const int64_t* excl_off,
+                            const uint8_t* eligible, int32_t slices, int64_t* out_idx, float* out_score, int32_t* status, void* ws,
+                            size_t ws_bytes, void* stream) {
+  NRL_REQUIRE(B >= 0 && V >= 0 && D >= 0 && slices >= 0, "%s: negative size", who);
+  NRL_TRY(tk_check(who, B, V, D, k, excl_idx, excl_off));
+  NRL_REQUIRE(status, "%s: the status word is required", who);
+  NRL_TRY(tkb_check(who, bias.bias, bias.bias_class, bias.S, V));
+  if (cap) NRL_TRY(tk_cap_check(who, V, k, cap->row_class, cap->m));
+  if (B == 0) return NRL_OK;
+  NRL_REQUIRE(out_idx && out_score && user_vec && (V == 0 || table), "%s: null argument", who);
+  unsigned long long* partial;
+  NRL_TRY(carve_workspace(ws, ws_bytes, [&](Arena& a) { tk_layout(a, B, V, k, slices, TK_BU, &partial); }));
+  TkWith<TkArgs, TkbFields> A;
+  static_cast<TkArgs&>(A) = tk_args(user_vec, table, B, V, D, k, excl_idx, excl_off, eligible, partial, out_idx, out_score, status);
+  static_cast<TkbFields&>(A) = bias;
+  if (!cap) return tk_launch(who, tkb_scores_kernel, A, slices, 1, TK_BU, stream, tkb_extra_lds(bias.S));
+  TkWith<TkWith<TkArgs, TkbFields>, TkCapFields> C{A, *cap};
+  return tk_launch(who, tkbcap_scores_kernel, C, slices, 1, TK_BU, stream, tkb_extra_lds(bias.S), TkMergeCapped{*cap});
+}
+
+int nrl_topk_bias_scores(const float* user_vec, const float* table, int64_t B, int64_t V, int32_t D, const float* bias,
+                         const int32_t* row_class, int32_t S, int32_t k, const int64_t* excl_idx, const int64_t* excl_off,
+                         const uint8_t* eligible, int32_t slices, int64_t* out_idx, float* out_score, int32_t* status, void* ws,
+                         size_t ws_bytes, void* stream) {
+  return tkb_scores_entry("topk_bias_scores", user_vec, table, B, V, D, TkbFields{bias, row_class, S}, k, nullptr, excl_idx, excl_off,
+                          eligible, slices, out_idx, out_score, status, ws, ws_bytes, stream);
+}
+
+int nrl_topk_bias_scores_capped(const float* user_vec, const float* table, int64_t B, int64_t V, int32_t D, const float* bias,
+                                const int32_t* row_class, int32_t S, int32_t k, const int32_t* cap_class, int32_t max_per_class,
+                                const int64_t* excl_idx, const int64_t* excl_off, const uint8_t* eligible, int32_t slices,
+                                int64_t* out_idx, float* out_score, int32_t* status, void* ws, size_t ws_bytes, void* stream) {
+  const TkCapFields cap{cap_class, max_per_class};
+  return tkb_scores_entry("topk_bias_scores_capped", user_vec, table, B, V, D, TkbFields{bias, row_class, S}, k, &cap, excl_idx,
+                          excl_off, eligible, slices, out_idx, out_score, status, ws, ws_bytes, stream);
+}
+
+int nrl_catalogue_bias_ranks(const float* user_vec, const float* table, int64_t B, int64_t V, int32_t D, const float* bias,
+                             const int32_t* row_class, int32_t S, const int64_t* tgt_idx, const int64_t* tgt_off, int64_t n_targets,
+                             const int64_t* excl_idx, const int64_t* excl_off, const uint8_t* eligible, int32_t slices,
+                             int32_t* out_rank, float* out_score, int32_t* out_ranked, int32_t* status, void* ws, size_t ws_bytes,
+                             void* stream) {
+  NRL_REQUIRE(B >= 0 && V >= 0 && D >= 0 && slices >= 0 && n_targets >= 0, "catalogue_bias_ranks: negative size");
+  NRL_TRY(tk_check("catalogue_bias_ranks", B, V, D, 1, excl_idx, excl_off));
+  NRL_TRY(tkc_check("catalogue_bias_ranks", n_targets, tgt_idx, tgt_off, status));
+  NRL_TRY(tkb_check("catalogue_bias_ranks", bias, row_class, S, V));
+  if (B == 0) return NRL_OK;
+  NRL_REQUIRE(out_ranked && user_vec && (V == 0 || table) && (n_targets == 0 || (tgt_idx && out_rank && out_score)),
+              "catalogue_bias_ranks: null argument");
+  TkWith<TkcArgs, TkbFields> A;
+  int64_t blocks;
+  NRL_TRY(tkc_prepare("catalogue_bias_ranks", A, user_vec, table, B, V, D, D, true, tgt_idx, tgt_off, n_targets, excl_idx, excl_off,
+                      eligible, slices, TK_BU, out_rank, out_score, out_ranked, status, ws, ws_bytes, &blocks));
+  static_cast<TkbFields&>(A) = TkbFields{bias, row_class, S};
+  return tkc_launch(tkbc_count_kernel, A, blocks, TKC_LDS + tkb_extra_lds(S), stream, [&](hipStream_t st) {
+    tkbc_target_kernel<<<(unsigned)ceil_div(n_targets, TK_BU), TK_THREADS, 0, st>>>(A);
     NRL_LAUNCH_CHECK();
     return NRL_OK;
   });

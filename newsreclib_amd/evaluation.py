@@ -303,6 +303,73 @@ class NewsVectorCache(_ImpressionCache):
             user = self.module.user_vectors(hv, meta)
         return user, targets, tail
 
+    def _biased_users(self, verb: str, combined: bool, aspect, bias, *side):
+        """The user side of ``recommend_biased`` / ``rank_clicks_biased``: the refusal, then either the module's
+        ``user_vectors_and_bias`` (a ``class_biased_scorer``: SentiDebias; the classes are its ``class_bias_aspect`` column of the
+        table, the history's classes gathered from the same column) or the module's ``user_vectors`` with the caller's ``aspect``
+        and ``bias`` (a ``dot_product_scorer``) -> (user (B, D), bias (B, S) or None: rank by the dot product alone, the classes
+        (num_news) int32 or None, click lists, (excl_idx, excl_off, eligible))."""
+        own = getattr(self.module, "class_biased_scorer", False)
+        if not own and not getattr(self.module, "dot_product_scorer", False):
+            raise NotImplementedError(
+                f"{type(self.module).__name__} scores a news neither by a dot product plus a per-class term of its own "
+                f"(`class_biased_scorer`: SentiDebias) nor by one dot product with a candidate-independent user vector "
+                f"(`dot_product_scorer`), to which `{verb}_biased` could add the caller's per-class `bias`")
+        if own and (aspect is not None or bias is not None):
+            raise ValueError(f"newsreclib_amd: {type(self.module).__name__} brings its own class bias (`combined=True`); `aspect` and "
+                             "`bias` are for a `dot_product_scorer` module")
+        if not own and (aspect is None or bias is None or combined):
+            raise ValueError(f"newsreclib_amd: {verb}_biased over a `dot_product_scorer` module needs `aspect` and `bias` (B, S), and "
+                             "has no `combined` score")
+        hv, meta, targets, tail = self._history(verb + "_biased", *side)
+        with eval_mode(self.module):
+            if not own:
+                return self.module.user_vectors(hv, meta), bias.to(self.table.device), _aspect_classes(self, aspect), targets, tail
+            if not combined:
+                return self.module.user_vectors_and_bias(hv, meta, None, False)[0], None, None, targets, tail
+            classes = _aspect_classes(self, self.module.class_bias_aspect)
+            hist_classes = self.table.attrs[self.module.class_bias_aspect].index_select(0, side[0].to(self.table.device).long())
+            user, own_bias = self.module.user_vectors_and_bias(hv, meta, hist_classes, True)
+        return user, own_bias, classes, targets, tail
+
+    @torch.no_grad()
+    def recommend_biased(self, hist_idx: torch.Tensor, hist_sizes: torch.Tensor, k: int, user_idx: Optional[torch.Tensor] = None,
+                         exclude_history: bool = True, eligible: Optional[torch.Tensor] = None, combined: bool = False,
+                         aspect: Optional[str] = None, bias: Optional[torch.Tensor] = None, cap: Optional[Tuple[str, int]] = None):
+        """``recommend`` by a dot product plus a per-(user, class) additive term -> (news_idx (B, k) int64, scores (B, k) fp32,
+        status).  Two uses.  A ``class_biased_scorer`` module (SentiDebias): ``combined=False`` (the default) ranks by the
+        bias-free score ``u_free . n_v`` through ``ops.topk_scores`` -- what the reference's test step ranks by; ``combined=True``
+        ranks by the score the generator is trained on, ``u_free . n_v + (u_aware T^T)[u, sentiment(v)]``, through
+        ``ops.topk_bias_scores`` with the table's ``class_bias_aspect`` column as the classes.  A ``dot_product_scorer`` module:
+        the caller passes ``aspect`` (an integer news attribute of the table) and ``bias`` (B, S), a boost or penalty per user
+        and class of its own (a category-affinity prior, a sentiment penalty); the user vectors are ``recommend``'s.
+        ``cap`` = (aspect, max_per_class) selects under ``recommend_capped``'s class cap as well (``k`` at most
+        ``ops.TOPK_CAP_MAX_K``); its aspect need not be the bias's.  Same contract as ``recommend``: ``hist_idx`` on the GPU,
+        ``hist_sizes`` on the host, nothing read back; ``status``: ``ops.TOPK_BIAS_FLAGS``."""
+        user, bias, classes, _, tail = self._biased_users("recommend", combined, aspect, bias,
+                                                          hist_idx, hist_sizes, user_idx, exclude_history, eligible, None)
+        capped = () if cap is None else (_aspect_classes(self, cap[0]), cap[1])
+        if bias is None:
+            return (ops.topk_scores_capped if capped else ops.topk_scores)(user, self.vectors, k, *capped, *tail)
+        return (ops.topk_bias_scores_capped if capped else ops.topk_bias_scores)(user, self.vectors, bias, classes, k, *capped, *tail)
+
+    @torch.no_grad()
+    def rank_clicks_biased(self, hist_idx: torch.Tensor, hist_sizes: torch.Tensor, click_idx: torch.Tensor,
+                           click_sizes: torch.Tensor, user_idx: Optional[torch.Tensor] = None, exclude_history: bool = True,
+                           eligible: Optional[torch.Tensor] = None, combined: bool = False, aspect: Optional[str] = None,
+                           bias: Optional[torch.Tensor] = None):
+        """``rank_clicks`` by ``recommend_biased``'s scores -> (rank int32 (n_clicks), score fp32 (n_clicks), ranked int32 (B),
+        status): its user side, ``combined`` / ``aspect`` / ``bias``, scores, order, exclusion of the history and ``eligible``,
+        with ``ops.catalogue_bias_ranks`` (the bias-free score: ``ops.catalogue_ranks``) counting where ``recommend_biased``
+        selects: ``rank <= k`` exactly when the click is slot ``rank - 1`` of ``recommend_biased(k)``.  The click side is that of
+        ``rank_clicks`` (host ``click_sizes``, at most ``ops.RANK_MAX_TARGETS`` a user, nothing read back); ``status``:
+        ``ops.RANK_BIAS_FLAGS``."""
+        user, bias, classes, targets, tail = self._biased_users(
+            "rank_clicks", combined, aspect, bias, hist_idx, hist_sizes, user_idx, exclude_history, eligible, (click_idx, click_sizes))
+        if bias is None:
+            return ops.catalogue_ranks(user, self.vectors, *targets, *tail)
+        return ops.catalogue_bias_ranks(user, self.vectors, bias, classes, *targets, *tail)
+
     def _interest_users(self, verb: str, bias, *side):
         """The user side of ``recommend_interests`` / ``rank_clicks_interests``: the refusal, then the module's ``user_interests``
         (eval mode) -> (interests, gate, click lists, (excl_idx, excl_off, eligible))."""
@@ -732,7 +799,8 @@ def recommend_users(cache: NewsVectorCache, users: Sequence[Dict], k: int, batch
     """``cache.recommend`` (``cache.recommend_interests`` where the cache's module is a ``multi_interest_scorer``,
     ``cache.recommend_dnn`` where it is a ``dnn_predictor_scorer``, ``cache.recommend_pooled`` where it is a
     ``personalized_pooling_scorer``: ``NpaFeatureCache``, whose users need ``user_idx``,
-    ``cache.recommend_ensemble`` where the cache has one: ``MannerVectorCache``) over a list of
+    ``cache.recommend_biased`` -- the bias-free score, its default -- where it is a ``class_biased_scorer``: SentiDebias, to which
+    ``cap`` is routed as well, ``cache.recommend_ensemble`` where the cache has one: ``MannerVectorCache``) over a list of
     users ({"hist": idx tensor[, "user_idx", "user_id"]}) in batches -> the recommendation dictionary of ``format_recommendations``.  ``user_id`` defaults to the user's position in the list + 1 (as ``build_batch``);
     news ids come from the table's ``news_ids`` column when it has one.  One device-to-host copy per batch, at its end; a status
     flag of the batch (``ops.TOPK_FLAGS``: each is handled by the kernel) is passed on as a warning.
@@ -759,7 +827,12 @@ def recommend_users(cache: NewsVectorCache, users: Sequence[Dict], k: int, batch
             cache.recommend_dnn if getattr(cache.module, "dnn_predictor_scorer", False) else \
             cache.recommend_pooled if getattr(cache.module, "personalized_pooling_scorer", False) else cache.recommend
         rank = getattr(cache, "recommend_ensemble", rank)
-        if cap is not None:
+        biased = getattr(cache.module, "class_biased_scorer", False)
+        if biased:
+            rank = cache.recommend_biased
+        if cap is not None and biased:
+            rank = lambda hist, hs, k, **kw: cache.recommend_biased(hist, hs, k, cap=(aspect, max_per_class), **kw)  # noqa: E731
+        elif cap is not None:
             capped = getattr(cache, "recommend_ensemble_capped", None) or cache.recommend_capped
             rank = lambda hist, hs, k, **kw: capped(hist, hs, k, aspect, max_per_class, **kw)  # noqa: E731
         idx, score, status = rank(hist, hs, k, user_idx=uidx, eligible=eligible)
@@ -767,7 +840,8 @@ def recommend_users(cache: NewsVectorCache, users: Sequence[Dict], k: int, batch
         word = int(packed[0, -1]) if packed.shape[0] else 0
         if word:                                            # the kernel has dealt with each of these; the caller should know
             import warnings
-            warnings.warn("recommend_users: " + "; ".join(msg for bit, msg in ops.TOPK_FLAGS.items() if word & bit))
+            flags = ops.TOPK_BIAS_FLAGS if biased else ops.TOPK_FLAGS
+            warnings.warn("recommend_users: " + "; ".join(msg for bit, msg in flags.items() if word & bit))
         ids = [int(u["user_id"]) if "user_id" in u else lo + j + 1 for j, u in enumerate(chunk)]
         out.update(format_recommendations(ids, packed[:, :k].long(), packed[:, k:2 * k].float(), news_ids))
     return out
@@ -777,7 +851,8 @@ def evaluate_full_rank(cache: NewsVectorCache, users: Sequence[Dict], top_k_list
                        eligible: Optional[torch.Tensor] = None, ensemble: bool = False) -> Dict[str, float]:
     """Full-catalogue ranking metrics of held-out clicks: ``cache.rank_clicks`` (``cache.rank_clicks_interests`` where the cache's
     module is a ``multi_interest_scorer``, ``cache.rank_clicks_dnn`` where it is a ``dnn_predictor_scorer``,
-    ``cache.rank_clicks_pooled`` where it is a ``personalized_pooling_scorer``, as ``recommend_users`` picks ``recommend_*``)
+    ``cache.rank_clicks_pooled`` where it is a ``personalized_pooling_scorer``, ``cache.rank_clicks_biased`` -- the bias-free score --
+    where it is a ``class_biased_scorer``, as ``recommend_users`` picks ``recommend_*``)
     over a list of users ({"hist": idx tensor,
     "clicks": idx tensor[, "user_idx"]}), batched as ``recommend_users`` batches them, then ``metrics.full_rank_metrics``
     (``mrr``, ``ndcg@k``, ``recall@k``, ``hit@k``, ``auc_user``; every click is ranked against every news the user could be
@@ -806,7 +881,8 @@ def evaluate_full_rank(cache: NewsVectorCache, users: Sequence[Dict], top_k_list
         uidx = torch.stack([torch.as_tensor(u["user_idx"]) for u in chunk]) if "user_idx" in chunk[0] else None
         rank_clicks = cache.rank_clicks_interests if getattr(cache.module, "multi_interest_scorer", False) else \
             cache.rank_clicks_dnn if getattr(cache.module, "dnn_predictor_scorer", False) else \
-            cache.rank_clicks_pooled if getattr(cache.module, "personalized_pooling_scorer", False) else cache.rank_clicks
+            cache.rank_clicks_pooled if getattr(cache.module, "personalized_pooling_scorer", False) else \
+            cache.rank_clicks_biased if getattr(cache.module, "class_biased_scorer", False) else cache.rank_clicks
         if ensemble:
             rank_clicks = cache.rank_clicks_ensemble
         rank, _, ranked, status = rank_clicks(hist, hs, clicks, cs, user_idx=uidx, eligible=eligible)

@@ -877,6 +877,67 @@ def catalogue_ranks(user_vec: torch.Tensor, table: torch.Tensor, tgt_idx: torch.
     return _run_ranks("nrl_catalogue_ranks", _dot_scorer(user_vec, table), tgt_idx, tgt_off, excl_idx, excl_off, eligible, slices)
 
 
+TOPK_MAX_BIAS_CLASSES = 64
+# the status words of the class-biased entries: the flags of ``topk_scores`` / ``catalogue_ranks`` and one more (bit 64).  They are
+# dictionaries of their own, as ``ENSEMBLE_RANK_FLAGS`` is: the key sets of ``TOPK_FLAGS`` and ``RANK_FLAGS`` are pinned.
+TOPK_BIAS_FLAGS = {**TOPK_FLAGS, 64: "a class id is outside [0, S) (that row is scored with bias 0)"}
+RANK_BIAS_FLAGS = {**RANK_FLAGS, 64: TOPK_BIAS_FLAGS[64]}
+
+
+def _bias_scorer(user_vec, table, bias, row_class) -> _Scorer:
+    """The dot-product scorer with ``(bias, row_class, S)`` behind ``D``: ``bias`` (B, S) fp32 and ``row_class`` checked (one int32
+    per table row; int64 converted by one device op).  The class ids themselves are checked on the device (``TOPK_BIAS_FLAGS[64]``)."""
+    s = _dot_scorer(user_vec, table)
+    if bias is None or row_class is None:
+        raise ValueError("newsreclib_amd: bias (B, S) and row_class (one class id per table row) are required")
+    bias = _chk(bias, torch.float32, "bias")
+    if bias.dim() != 2 or bias.shape[0] != s.B or bias.shape[1] < 1:
+        raise ValueError(f"newsreclib_amd: bias (B, S) with B = {s.B} and S >= 1 expected, got {tuple(bias.shape)}")
+    S = int(bias.shape[1])
+    if S > TOPK_MAX_BIAS_CLASSES:
+        raise NotImplementedError(f"newsreclib_amd: a class bias takes at most {TOPK_MAX_BIAS_CLASSES} classes (got {S})")
+    if row_class.dtype == torch.int64 and row_class.is_cuda:
+        row_class = row_class.to(torch.int32)
+    row_class = _chk(row_class, torch.int32, "row_class")
+    if row_class.dim() != 1 or row_class.numel() != s.V:
+        raise ValueError(f"newsreclib_amd: row_class must have one entry per table row ({s.V}), got {tuple(row_class.shape)}")
+    return s._replace(lead=(*s.lead, bias.data_ptr(), row_class.data_ptr(), S), keep=(*s.keep, bias, row_class))
+
+
+def topk_bias_scores(user_vec: torch.Tensor, table: torch.Tensor, bias: torch.Tensor, row_class: torch.Tensor, k: int,
+                     excl_idx: Optional[torch.Tensor] = None, excl_off: Optional[torch.Tensor] = None,
+                     eligible: Optional[torch.Tensor] = None, slices: int = 0):
+    """``nrl_topk_bias_scores``: ``topk_scores`` by ``user_vec[u] . table[v] + bias[u, row_class[v]]`` -- ``bias`` (B, S) fp32, a
+    per-user additive term per class (a category-affinity prior, a sentiment penalty, SentiDebias's ``u_aware T^T``), ``S`` at
+    most ``TOPK_MAX_BIAS_CLASSES``; ``row_class`` (V int32, or int64: converted by one device op).  The dot product has the bits
+    of ``topk_scores`` and the bias is one fp32 add behind it, so an all-zero bias returns ``topk_scores``' rows and scores.  A
+    class id outside [0, S) is scored with bias 0 and flagged (``TOPK_BIAS_FLAGS[64]``); a NaN sum is dropped and flagged as any NaN
+    score.  Returns, order, masks and the other flags (``TOPK_BIAS_FLAGS``) are those of ``topk_scores``.  Nothing here
+    synchronises with the host."""
+    return _run_topk("nrl_topk_bias_scores", _bias_scorer(user_vec, table, bias, row_class), k, excl_idx, excl_off, eligible, slices)
+
+
+def topk_bias_scores_capped(user_vec: torch.Tensor, table: torch.Tensor, bias: torch.Tensor, row_class: torch.Tensor, k: int,
+                            cap_class: torch.Tensor, max_per_class: int, excl_idx: Optional[torch.Tensor] = None,
+                            excl_off: Optional[torch.Tensor] = None, eligible: Optional[torch.Tensor] = None, slices: int = 0):
+    """``nrl_topk_bias_scores_capped``: ``topk_bias_scores`` with at most ``max_per_class`` rows of any one class of ``cap_class``
+    in a user's list, as ``topk_scores_capped`` caps ``topk_scores``.  ``cap_class`` (V) is an array of its own: the cap may go by
+    category while the bias goes by sentiment.  With ``max_per_class >= k`` the bits are those of ``topk_bias_scores``."""
+    s = _capped(_bias_scorer(user_vec, table, bias, row_class), cap_class, max_per_class)
+    return _run_topk("nrl_topk_bias_scores_capped", s, k, excl_idx, excl_off, eligible, slices)
+
+
+def catalogue_bias_ranks(user_vec: torch.Tensor, table: torch.Tensor, bias: torch.Tensor, row_class: torch.Tensor,
+                         tgt_idx: torch.Tensor, tgt_off: torch.Tensor, excl_idx: Optional[torch.Tensor] = None,
+                         excl_off: Optional[torch.Tensor] = None, eligible: Optional[torch.Tensor] = None, slices: int = 0):
+    """``nrl_catalogue_bias_ranks``: ``catalogue_ranks`` by the scores of ``topk_bias_scores`` -> (rank int32 (n_tgt), score fp32
+    (n_tgt), ranked int32 (B), status (1) int32) with the targets, population, order, masks and flags (``RANK_BIAS_FLAGS``) of
+    ``catalogue_ranks`` and the score bits of ``topk_bias_scores``: ``rank <= k`` exactly when the target is slot ``rank - 1`` of
+    that call's list.  Nothing here synchronises with the host."""
+    return _run_ranks("nrl_catalogue_bias_ranks", _bias_scorer(user_vec, table, bias, row_class), tgt_idx, tgt_off, excl_idx,
+                      excl_off, eligible, slices)
+
+
 TOPK_MAX_INTERESTS = 64
 
 

@@ -251,6 +251,32 @@ class SentiDebiasModule(AbstractRecommender):
         encode-once evaluation (``evaluation.NewsVectorCache``; the news vectors do not depend on the user)."""
         return self.generator.bias_free_scores(hist_news_vector, cand_news_vector, batch)
 
+    # Ranking the whole news table (``evaluation.NewsVectorCache.recommend_biased`` / ``rank_clicks_biased``).  The module has no
+    # ``dot_product_scorer``: its trained score is a dot product PLUS a term per (user, sentiment class), which the class-biased
+    # top-k entries of ``ops`` rank by; the classes are the table's ``class_bias_aspect`` column.
+    class_biased_scorer = True
+    class_bias_aspect = "sentiment"
+
+    def user_vectors_and_bias(self, hist_news_vector: torch.Tensor, meta: Dict, hist_classes: Optional[torch.Tensor],
+                              combined: bool) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+        """-> (u_free (B, D), bias (B, S) or None) from already-encoded history rows and the history meta of the cache
+        (``Generator.user_vectors``).  ``combined=False``: the bias-free score ``u_free . n_v`` alone, what ``model_step`` ranks
+        by; the sentiment half is not evaluated.  ``combined=True``: ``bias = u_aware T^T``, so that ``u_free . n_v + bias[u,
+        sentiment(v)]`` is the combined score ``Generator.forward_full`` trains on; ``hist_classes`` (n_hist) are the history
+        rows' sentiment ids.  The bias is ``CombinedScoresFn`` over a candidate list of the S classes per user and zero bias-free
+        scores: the very values the training-time score adds, each a function of its user and its class alone."""
+        gen = self.generator
+        if not combined:
+            return gen.user_vectors(hist_news_vector, meta, None)[0], None
+        batch = dict(meta)
+        batch["x_all"] = {"sentiment": hist_classes.reshape(-1).long()}
+        table = SD.sentiment_table(gen.sentiment_encoder)
+        free, aware = gen.user_vectors(hist_news_vector, batch, table)
+        B, S = free.shape[0], table.shape[0]
+        ids = torch.arange(S, device=free.device).repeat(B)
+        off = torch.arange(B + 1, device=free.device) * S
+        return free, SD.CombinedScoresFn.apply(free.new_zeros((B, S)), aware, table, ids, off)
+
     def forward(self, batch: Dict):
         return self.generator(batch)
 
