@@ -1209,6 +1209,42 @@ int nrl_catalogue_bias_ranks(const float* user_vec, const float* table, int64_t 
                              int32_t slices, int32_t* out_rank /* n_targets */, float* out_score /* n_targets */,
                              int32_t* out_ranked /* B */, int32_t* status, void* ws, size_t ws_bytes, void* stream);
 
+/* nrl_mmr_rerank (symbol added to ABI v19): greedy Maximal Marginal Relevance over a pool of table rows per user -- the (idx, score)
+ *   pair any nrl_topk_* entry returns -- trading relevance against similarity to what is already in the list.
+ *   Inputs: pool_idx (B, N) int64, -1 = an empty slot; pool_score (B, N) fp32; table (V, D) fp32; k, lambda (fp32), similarity
+ *     (0 = cosine, 1 = dot), normalize (0 / 1).
+ *   Limits: 1 <= k <= N <= NRL_MMR_MAX_POOL = 128; D as for nrl_topk_scores, a multiple of 4 in [4, 1024]; lambda in [0, 1].
+ *   Live slots: slot i of user u is live when its row is in [0, V) and its score is finite.  A row other than -1 outside [0, V) is
+ *     dead and ORs NRL_MMR_E_ROW (1) into status; a NaN or +-inf score in a slot with a valid row is dead and ORs NRL_TOPK_E_NAN
+ *     (4); a live slot whose own Gram diagonal is not finite is dead and ORs 4.  The pool need not be sorted.  Duplicate rows are
+ *     two slots with similarity 1 (cosine); the kernel does not handle them specially.
+ *   Gram matrix: G[i][j] is the exact-fp32 accumulator chain of nrl_topk_scores over the two table rows: it has the bits that entry
+ *     returns for that pair, a function of the two rows and D alone, and it is bit-symmetric.
+ *   Similarity: dot: sim[i][j] = G[i][j].  Cosine: sim[i][j] = fl(G[i][j] * fl(r_i * r_j)), r_i = fl(1 / fl(sqrt(G[i][i]))), and
+ *     r_i = 0 where G[i][i] == 0.  Every operation is one correctly rounded fp32 operation (the operations __fsqrt_rn, __fdiv_rn,
+ *     __fmul_rn, __fsub_rn name); nothing contracts to an fma.  A float32 numpy restatement reproduces the bits.
+ *   Relevance: normalize = 0: rel_i = score_i.  normalize = 1: rel_i = fl(fl(score_i - s_min) / fl(s_max - s_min)) over the user's
+ *     live slots (a -0 extreme counts as +0); all rel_i are +0 when s_max == s_min.
+ *   Greedy steps t = 0 ... k - 1, pen_i = +0 before anything is selected.  After selecting c: the first selection sets
+ *     pen_i = sim[c][i], every later one pen_i = max(pen_i, sim[c][i]) -- the true maximum, so it may be negative.
+ *     obj_i = fl(fl(lambda * rel_i) - fl(fl(1 - lambda) * pen_i)).  The step selects the live, unselected slot of largest obj;
+ *     equal obj (-0 == +0) goes to the lower slot; a NaN obj ranks below every number.
+ *   Outputs: out_idx (B, k) int64 the row; out_score (B, k) fp32 that slot's pool_score, bits unchanged; out_mmr (B, k) fp32 the
+ *     winning obj; -1 / -inf / -inf once the live slots run out.  status (one int32, required): integer atomicOr only.
+ *   Properties: the result for k is a prefix of the result for k' > k.  Nothing depends on B, on the user's place in the batch, on
+ *     the GEMM engine setting or on the run.  lambda = 1 with normalize = 0 returns the live slots in (score descending, slot
+ *     ascending) order: on a pool that came from nrl_topk_scores, that pool's first k entries bit for bit.  No float atomics, no
+ *     workspace, no allocation, no host synchronisation.
+ *   Checks, in this order, each NRL_E_INVALID before any launch: negative sizes; N outside [1, 128]; k outside [1, N]; D, V, B
+ *     outside the limits of nrl_topk_scores; lambda outside [0, 1] or NaN; similarity / normalize outside {0, 1}; a null status.
+ *     B == 0 returns success without a launch.  After that, null pointers among the rest return NRL_E_INVALID; table may be null
+ *     only when V == 0. */
+#define NRL_MMR_MAX_POOL 128
+#define NRL_MMR_E_ROW 1 /* a pool row other than -1 is outside [0, V): that slot is dead */
+int nrl_mmr_rerank(const int64_t* pool_idx, const float* pool_score, const float* table, int64_t B, int32_t N, int64_t V, int32_t D,
+                   int32_t k, float lambda, int32_t similarity, int32_t normalize, int64_t* out_idx, float* out_score,
+                   float* out_mmr, int32_t* status, void* stream);
+
 /* nrl_topk_relu_scores: the same ranking by DKN's DNN click predictor (click_predictor.py:14-45: Linear(2 dim, Hd) -> ReLU ->
  *   Linear(Hd, 1) on [cand; user]) with the candidate list replaced by the table.  The first layer splits by columns,
  *   pred_w1 = [Wc | Wu], so with q (B, Hd) = user Wu^T + b1 (nrl_dkn_user_query) and proj (V, Hd) = table Wc^T

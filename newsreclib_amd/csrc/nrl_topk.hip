@@ -37,6 +37,8 @@
 // pointers and counts; the producers and consumers are structs of pointers into LDS that call them.  On the host each scorer's
 // own checks and fields are one function each, shared by its two entries.
 // No float atomics, no allocation, no host read-back; the workspace holds the partial lists, O(B * slices * k), or the counts.
+// Behind the walk kernels, mmr_rerank_kernel (nrl_mmr_rerank) re-ranks a pool any of the top-k entries returned by greedy MMR: it is
+// no walk (one workgroup per user, the pool's Gram matrix by tk_tile_accumulate<1, true>, then k steps) and needs no workspace.
 #include <math.h>
 
 #include "nrl_common.h"
@@ -1880,6 +1882,204 @@ __global__ __launch_bounds__(64) void tkc_finish_kernel(TkcArgs A) {
   A.out_score[ts + lane] = tk_unkey(score_key(s));    // (-0 comes back as +0, as from tk_merge_kernel)
 }
 
+// ---- greedy MMR re-ranking of a pool (nrl_mmr_rerank) ------------------------------------------------------------------------------
+// One workgroup per user.  The pool's Gram matrix is ceil(N / 64) calls of tk_tile_accumulate<1, true>: the A rows are pool slots
+// 64 h ... 64 h + 63 read in place, the gathered B rows the whole pool, so G[i][j] is the chain of nrl_topk_scores over the two
+// table rows and bit-symmetric.  Each call stages its operands inside the tile it then writes; the two [TK_BU][TK_SCLD] tiles are
+// contiguous, so sim[i][j] is at i * TK_SCLD + j for every i.  Behind them:
+//   wk[2][4] u64    the waves' best entries of a step, double-buffered by the step's parity (one barrier a step)
+//   rows[128] i64   the slots' table rows;  scs[128] their scores;  rn[128] 1 / sqrt(G[i][i]);  objs[2][128] the slots' objectives
+// rel, pen and the live / selected flags of slot i live in the registers of thread i.  The greedy loop reads sim[c][i], the ROW of
+// the slot just selected: lane i reads word c * 132 + i, consecutive lanes consecutive banks, no conflict (the column, i * 132 + c,
+// would put lanes 8 apart on one bank).  Every scalar operation below is one correctly rounded fp32 operation and none contracts.
+constexpr int MMR_MAX_POOL = NRL_MMR_MAX_POOL;
+constexpr size_t MMR_SLOT_BYTES = 2 * 4 * 8 + (size_t)MMR_MAX_POOL * (8 + 4 + 4 + 2 * 4);
+constexpr size_t mmr_lds_bytes(int halves) { return (size_t)halves * TK_TILE_BYTES + MMR_SLOT_BYTES; }
+static_assert(MMR_MAX_POOL == TK_BV && MMR_MAX_POOL == 2 * TK_BU, "a pool is one tile of gathered rows and at most two tiles of A rows");
+static_assert(MMR_MAX_POOL <= TK_THREADS, "one thread per slot");
+static_assert(2 * mmr_lds_bytes(2) <= 160 * 1024, "two workgroups of the largest layout fit a CU");
+
+struct MmrArgs {
+  const int64_t* pool_idx;
+  const float* pool_score;
+  const float* table;
+  int32_t N, D, k;
+  int64_t V;
+  float lambda;
+  int32_t similarity, normalize;
+  int64_t* out_idx;
+  float* out_score;
+  float* out_mmr;
+  int32_t* status;
+};
+
+// plain fp32 operations that stay single: the unit is compiled with contraction on (__fsqrt_rn would be the approximate
+// v_sqrt_f32 here; sqrtf and the division are the correctly rounded expansions)
+__device__ __forceinline__ float mmr_mul(float a, float b) {
+#pragma clang fp contract(off)
+  return a * b;
+}
+__device__ __forceinline__ float mmr_sub(float a, float b) {
+#pragma clang fp contract(off)
+  return a - b;
+}
+__device__ __forceinline__ float mmr_div(float a, float b) {
+#pragma clang fp contract(off)
+  return a / b;
+}
+__device__ __forceinline__ unsigned long long mmr_wave_max(unsigned long long x, int lane) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    const unsigned long long y = tk_shfl(x, lane ^ off);
+    x = y > x ? y : x;
+  }
+  return x;
+}
+
+__global__ __launch_bounds__(TK_THREADS) void mmr_rerank_kernel(MmrArgs A) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char tk_smem[];
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int N = A.N, k = A.k;
+  const int halves = (N + TK_BU - 1) / TK_BU;
+  const int64_t u = blockIdx.x;
+  float* const sim = reinterpret_cast<float*>(tk_smem);
+  unsigned long long* const wk = reinterpret_cast<unsigned long long*>(tk_smem + (size_t)halves * TK_TILE_BYTES);
+  int64_t* const rows = reinterpret_cast<int64_t*>(wk + 8);
+  float* const scs = reinterpret_cast<float*>(rows + MMR_MAX_POOL);
+  float* const rn = scs + MMR_MAX_POOL;
+  float* const objs = rn + MMR_MAX_POOL;
+  const int64_t* const pool = A.pool_idx + u * N;
+
+  // the slots: thread i owns slot i
+  bool live = false;
+  float score = 0.f;
+  int flags = 0;
+  if (tid < MMR_MAX_POOL) {
+    int64_t row = -1;
+    if (tid < N) {
+      row = pool[tid];
+      score = A.pool_score[u * N + tid];
+    }
+    const bool row_ok = row >= 0 && row < A.V;
+    const bool fin = fabsf(score) < INFINITY;
+    if (row != -1 && !row_ok) flags |= NRL_MMR_E_ROW;
+    if (row_ok && !fin) flags |= NRL_TOPK_E_NAN;
+    live = row_ok && fin;
+    rows[tid] = live ? row : -1;
+    scs[tid] = score;
+    rn[tid] = 0.f;
+  }
+  __syncthreads();
+
+  // the Gram matrix
+  if (A.V > 0) {
+    for (int h = 0; h < halves; ++h) {
+      const int64_t ar = rows[h * TK_BU + (tid >> 2)];                        // (-1: an empty, bad or non-finite slot)
+      const bool ua_ok = ar >= 0;
+      const float* const pa[1] = {A.table + (ua_ok ? ar : 0) * A.D};
+      float* const tile = sim + h * TK_BU * TK_SCLD;
+      tk_f32x4 acc[1][2][4];
+      tk_tile_accumulate<1, true>(pa, ua_ok, A.table, A.D, 0, N, A.D, tile, acc, pool, A.V);
+      tk_store_fragments(acc[0], tile);
+      __syncthreads();
+    }
+  }
+
+  // the diagonal: a slot whose own product is not finite is dead; r
+  if (tid < N && live) {
+    const float g = sim[tid * TK_SCLD + tid];
+    if (!(fabsf(g) < INFINITY)) {
+      live = false;
+      flags |= NRL_TOPK_E_NAN;
+    } else {
+      rn[tid] = g == 0.f ? 0.f : mmr_div(1.f, __builtin_sqrtf(g));
+    }
+  }
+  {
+    int f = flags;
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) f |= __shfl_xor(f, off, 64);
+    if (f && lane == 0) atomicOr(A.status, f);
+  }
+  // relevance: the extremes of the live scores as keys (-0 counts as +0), through the waves' slots of wk
+  const uint32_t key = score_key(score);
+  if (A.normalize) {
+    uint32_t lo = live ? key : 0xFFFFFFFFu, hi = live ? key : 0u;
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+      const uint32_t l2 = (uint32_t)__shfl_xor((int)lo, off, 64), h2 = (uint32_t)__shfl_xor((int)hi, off, 64);
+      lo = l2 < lo ? l2 : lo;
+      hi = h2 > hi ? h2 : hi;
+    }
+    if (lane == 0) wk[wave] = ((unsigned long long)hi << 32) | lo;
+  }
+  __syncthreads();                                    // publishes rn and the extremes
+  float rel = score;
+  if (A.normalize) {
+    uint32_t lo = 0xFFFFFFFFu, hi = 0u;
+#pragma unroll
+    for (int w = 0; w < TK_THREADS / 64; ++w) {
+      const unsigned long long e = wk[w];
+      const uint32_t l2 = (uint32_t)e, h2 = (uint32_t)(e >> 32);
+      lo = l2 < lo ? l2 : lo;
+      hi = h2 > hi ? h2 : hi;
+    }
+    if (hi == lo || hi == 0u) {
+      rel = 0.f;
+    } else {
+      const float s_min = tk_unkey(lo), s_max = tk_unkey(hi);
+      rel = mmr_div(mmr_sub(score, s_min), mmr_sub(s_max, s_min));
+    }
+  }
+  if (A.similarity == 0) {
+    for (int e = tid; e < N * TK_BV; e += TK_THREADS) {
+      const int i = e / TK_BV, j = e % TK_BV;
+      float* const p = sim + i * TK_SCLD + j;
+      *p = mmr_mul(*p, mmr_mul(rn[i], rn[j]));
+    }
+  }
+  __syncthreads();                                    // sim is final; wk is free for the steps
+
+  const float lrel = mmr_mul(A.lambda, rel), om = mmr_sub(1.f, A.lambda);
+  float pen = 0.f;
+  bool sel = false;
+  int c = -1, t = 0;
+  for (; t < k; ++t) {
+    if (t > 0) {
+      const float s = tid < N ? sim[c * TK_SCLD + tid] : 0.f;
+      pen = t == 1 ? s : fmaxf(pen, s);
+    }
+    const float obj = mmr_sub(lrel, mmr_mul(om, pen));
+    unsigned long long e = 0ull;
+    if (live && !sel) e = obj != obj ? ((1ull << 32) | (uint32_t)~(uint32_t)tid) : tk_entry(obj, (uint32_t)tid);
+    e = mmr_wave_max(e, lane);
+    const int par = t & 1;
+    if (lane == 0) wk[par * 4 + wave] = e;
+    if (tid < MMR_MAX_POOL) objs[par * MMR_MAX_POOL + tid] = obj;
+    __syncthreads();
+    unsigned long long best = wk[par * 4];
+#pragma unroll
+    for (int w = 1; w < TK_THREADS / 64; ++w) {
+      const unsigned long long y = wk[par * 4 + w];
+      best = y > best ? y : best;
+    }
+    if (best == 0ull) break;                          // the live slots have run out (uniform)
+    c = (int)~(uint32_t)best;
+    if (tid == c) sel = true;
+    if (tid == 0) {
+      A.out_idx[u * k + t] = rows[c];
+      A.out_score[u * k + t] = scs[c];
+      A.out_mmr[u * k + t] = objs[par * MMR_MAX_POOL + c];
+    }
+  }
+  for (int p = t + tid; p < k; p += TK_THREADS) {
+    A.out_idx[u * k + p] = -1;
+    A.out_score[u * k + p] = -INFINITY;
+    A.out_mmr[u * k + p] = -INFINITY;
+  }
+}
+
 static bool tk_shape_ok(int64_t B, int64_t V, int32_t D, int32_t k) {
   return B >= 0 && V >= 0 && V < ((int64_t)1 << 31) && D > 0 && D % 4 == 0 && D <= NRL_TOPK_MAX_D && k >= 1 && k <= NRL_TOPK_MAX_K;
 }
@@ -2492,6 +2692,32 @@ int nrl_catalogue_bias_ranks(const float* user_vec, const float* table, int64_t 
     NRL_LAUNCH_CHECK();
     return NRL_OK;
   });
+}
+
+// ---- nrl_mmr_rerank (header: semantics) --------------------------------------------------------------------------------------------
+int nrl_mmr_rerank(const int64_t* pool_idx, const float* pool_score, const float* table, int64_t B, int32_t N, int64_t V, int32_t D,
+                   int32_t k, float lambda, int32_t similarity, int32_t normalize, int64_t* out_idx, float* out_score, float* out_mmr,
+                   int32_t* status, void* stream) {
+  NRL_REQUIRE(B >= 0 && N >= 0 && V >= 0 && D >= 0 && k >= 0, "mmr_rerank: negative size");
+  NRL_REQUIRE(N >= 1 && N <= NRL_MMR_MAX_POOL, "mmr_rerank: N in [1, %d] (got %d)", NRL_MMR_MAX_POOL, N);
+  NRL_REQUIRE(k >= 1 && k <= N, "mmr_rerank: k in [1, N = %d] (got %d)", N, k);
+  NRL_REQUIRE(D > 0 && D % 4 == 0 && D <= NRL_TOPK_MAX_D, "mmr_rerank: D a multiple of 4 in [4, %d] (got %d)", NRL_TOPK_MAX_D, D);
+  NRL_REQUIRE(V < ((int64_t)1 << 31), "mmr_rerank: at most 2^31 - 1 table rows (got %lld)", (long long)V);
+  NRL_REQUIRE(B < ((int64_t)1 << 31), "mmr_rerank: at most 2^31 - 1 users per call (got %lld)", (long long)B);
+  NRL_REQUIRE(lambda >= 0.f && lambda <= 1.f, "mmr_rerank: lambda in [0, 1] (got %g)", (double)lambda);
+  NRL_REQUIRE((similarity == 0 || similarity == 1) && (normalize == 0 || normalize == 1),
+              "mmr_rerank: similarity (0 cosine, 1 dot) and normalize in {0, 1} (got %d, %d)", similarity, normalize);
+  NRL_REQUIRE(status, "mmr_rerank: the status word is required");
+  if (B == 0) return NRL_OK;
+  NRL_REQUIRE(pool_idx && pool_score && out_idx && out_score && out_mmr && (V == 0 || table), "mmr_rerank: null argument");
+  const MmrArgs A{pool_idx, pool_score, table, N, D, k, V, lambda, similarity, normalize, out_idx, out_score, out_mmr, status};
+  const size_t smem = mmr_lds_bytes((N + TK_BU - 1) / TK_BU);
+  // more than 64 KB of dynamic LDS needs the attribute; it belongs to the current device, so it is set per call
+  if (smem > 64 * 1024)
+    NRL_HIP(hipFuncSetAttribute((const void*)mmr_rerank_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+  mmr_rerank_kernel<<<(unsigned)B, TK_THREADS, smem, (hipStream_t)stream>>>(A);
+  NRL_LAUNCH_CHECK();
+  return NRL_OK;
 }
 
 }  // extern "C"

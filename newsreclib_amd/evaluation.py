@@ -430,6 +430,17 @@ class NewsVectorCache(_ImpressionCache):
         return ops.topk_scores_capped(user, self.vectors, k, _aspect_classes(self, aspect), max_per_class, *tail)
 
     @torch.no_grad()
+    def rerank_diverse(self, pool_idx: torch.Tensor, pool_score: torch.Tensor, k: int, lam: float, similarity: str = "cosine",
+                       normalize: bool = True):
+        """Greedy MMR over a pool any ``recommend*`` of this cache returned (``pool_idx`` / ``pool_score`` (B, N), N at most
+        ``ops.MMR_MAX_POOL``) -> (news_idx (B, k) int64, scores (B, k) fp32: the pool's own, mmr (B, k) fp32, status:
+        ``ops.MMR_FLAGS``): ``ops.mmr_rerank`` against the cached news vectors, built when they are missing.  The similarity is
+        between news vectors, whatever scorer produced the pool.  Nothing is read back."""
+        if self.vectors is None:
+            self.build()
+        return ops.mmr_rerank(pool_idx, pool_score, self.vectors, k, lam, similarity, normalize)
+
+    @torch.no_grad()
     def rank_clicks(self, hist_idx: torch.Tensor, hist_sizes: torch.Tensor, click_idx: torch.Tensor, click_sizes: torch.Tensor,
                     user_idx: Optional[torch.Tensor] = None, exclude_history: bool = True,
                     eligible: Optional[torch.Tensor] = None):
@@ -583,6 +594,15 @@ class MannerVectorCache(_ImpressionCache):
                                                                     _aspect_classes(self, aspect), max_per_class, *tail)
         return (idx, score, status, stats) if return_stats else (idx, score, status)
 
+    @torch.no_grad()
+    def rerank_diverse(self, pool_idx: torch.Tensor, pool_score: torch.Tensor, k: int, lam: float, similarity: str = "cosine",
+                       normalize: bool = True, submodel: int = 0):
+        """``NewsVectorCache.rerank_diverse`` of a pool ``recommend_ensemble*`` returned, against the table of sub-model
+        ``submodel`` (the similarity between two news needs one vector space; the ensemble has one per sub-model)."""
+        if self.vectors is None:
+            self.build()
+        return ops.mmr_rerank(pool_idx, pool_score, self.vectors[submodel], k, lam, similarity, normalize)
+
     def _ensemble_users(self, who: str, hist_idx, hist_sizes, user_idx, exclude_history: bool, eligible, clicks):
         """The user side of ``recommend_ensemble`` and ``rank_clicks_ensemble`` (``who``): the caller's side of the call checked and
         on the device (``_catalogue_side``) -> (the user matrix of every sub-model: the mean of the gathered history rows of its
@@ -687,6 +707,11 @@ class NpaFeatureCache(_ImpressionCache):
         raise NotImplementedError("only the dot-product families are served by `rank_clicks` so far (NewsVectorCache over a "
                                   "`dot_product_scorer` module): NPA's personalized-pooling score is counted by "
                                   "`rank_clicks_pooled`")
+
+    def rerank_diverse(self, *args, **kwargs):
+        raise NotImplementedError("MMR trades relevance against the similarity of two news vectors, and an NPA news vector depends "
+                                  "on the user (personalized attention pooling, text.py:385-390): the cache holds feature maps, not "
+                                  "a (V, D) table of news vectors to take that similarity in")
 
     @torch.no_grad()
     def recommend_pooled(self, hist_idx: torch.Tensor, hist_sizes: torch.Tensor, k: int, user_idx: Optional[torch.Tensor] = None,
@@ -795,7 +820,8 @@ def format_recommendations(user_ids: Sequence, news_idx: torch.Tensor, scores: t
 
 
 def recommend_users(cache: NewsVectorCache, users: Sequence[Dict], k: int, batch_size: int = 512,
-                    eligible: Optional[torch.Tensor] = None, cap: Optional[Tuple[str, int]] = None) -> Dict[str, Dict[str, float]]:
+                    eligible: Optional[torch.Tensor] = None, cap: Optional[Tuple[str, int]] = None,
+                    diversify: Optional[Tuple[int, float]] = None) -> Dict[str, Dict[str, float]]:
     """``cache.recommend`` (``cache.recommend_interests`` where the cache's module is a ``multi_interest_scorer``,
     ``cache.recommend_dnn`` where it is a ``dnn_predictor_scorer``, ``cache.recommend_pooled`` where it is a
     ``personalized_pooling_scorer``: ``NpaFeatureCache``, whose users need ``user_idx``,
@@ -807,7 +833,19 @@ def recommend_users(cache: NewsVectorCache, users: Sequence[Dict], k: int, batch
 
     ``cap`` = (aspect, max_per_class): at most that many news of any one class of the table's ``aspect`` column in a user's list
     (``cache.recommend_ensemble_capped`` where the cache has one, else ``cache.recommend_capped``).  ``NotImplementedError`` for
-    the caches of the other scorers (MINER, DKN, NPA): their capped kernels do not exist yet."""
+    the caches of the other scorers (MINER, DKN, NPA): their capped kernels do not exist yet.
+
+    ``diversify`` = (pool, lam): the method picked above returns each user's ``pool`` best news (``k <= pool <=
+    ops.MMR_MAX_POOL``; under ``cap`` at most ``ops.TOPK_CAP_MAX_K``) and ``cache.rerank_diverse(idx, score, k, lam)`` -- greedy
+    MMR by the cosine of the cached news vectors, the relevance min-max scaled -- picks the ``k`` that are listed, in its order,
+    with the scores the scorer gave them.  Its status word (``ops.MMR_FLAGS``) is OR-ed into the batch's on the device, 16 bits
+    up, so there is still one device-to-host copy per batch.  ``None`` is the path without it, launch for launch."""
+    if diversify is not None:
+        pool, lam = int(diversify[0]), float(diversify[1])
+        if pool < k:
+            raise ValueError(f"recommend_users(diversify=(pool, lam)): the pool ({pool}) must hold at least k = {k} news")
+        if getattr(cache.module, "personalized_pooling_scorer", False):
+            cache.rerank_diverse()                          # (NpaFeatureCache: refuses and says why, before any device work)
     if cap is not None:
         other = [a for a in ("multi_interest_scorer", "dnn_predictor_scorer", "personalized_pooling_scorer")
                  if getattr(cache.module, a, False)]
@@ -835,13 +873,17 @@ def recommend_users(cache: NewsVectorCache, users: Sequence[Dict], k: int, batch
         elif cap is not None:
             capped = getattr(cache, "recommend_ensemble_capped", None) or cache.recommend_capped
             rank = lambda hist, hs, k, **kw: capped(hist, hs, k, aspect, max_per_class, **kw)  # noqa: E731
-        idx, score, status = rank(hist, hs, k, user_idx=uidx, eligible=eligible)
+        idx, score, status = rank(hist, hs, k if diversify is None else pool, user_idx=uidx, eligible=eligible)
+        if diversify is not None:
+            idx, score, _, mmr_status = cache.rerank_diverse(idx, score, k, lam)
+            status = status | (mmr_status << 16)
         packed = torch.cat([idx.double(), score.double(), status.double().expand(idx.shape[0], 1)], dim=1).cpu()      # the one copy
         word = int(packed[0, -1]) if packed.shape[0] else 0
         if word:                                            # the kernel has dealt with each of these; the caller should know
             import warnings
             flags = ops.TOPK_BIAS_FLAGS if biased else ops.TOPK_FLAGS
-            warnings.warn("recommend_users: " + "; ".join(msg for bit, msg in flags.items() if word & bit))
+            said = [msg for bit, msg in flags.items() if word & bit] + [msg for bit, msg in ops.MMR_FLAGS.items() if (word >> 16) & bit]
+            warnings.warn("recommend_users: " + "; ".join(said))
         ids = [int(u["user_id"]) if "user_id" in u else lo + j + 1 for j, u in enumerate(chunk)]
         out.update(format_recommendations(ids, packed[:, :k].long(), packed[:, k:2 * k].float(), news_ids))
     return out

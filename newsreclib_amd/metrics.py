@@ -223,6 +223,26 @@ def recommendation_aspect_metrics(idx: torch.Tensor, scores: torch.Tensor, row_c
     return {key: float(out[key].double().mean()) if B else 0.0 for key in keys}
 
 
+def intra_list_similarity(idx: torch.Tensor, table: torch.Tensor) -> float:
+    """The intra-list similarity of recommendation LISTS: per user the mean cosine over the pairs of distinct valid slots of its
+    list (``idx`` (B, k): rows of ``table`` (V, D); a slot with ``idx < 0`` is empty and left out; a zero vector has cosine 0 with
+    everything), then the mean over the users with at least two valid slots (0.0 when there is none).  Lower is more diverse: it
+    is what ``ops.mmr_rerank`` buys, as ``recommendation_aspect_metrics`` shows what a class cap buys.  Torch ops on the
+    tensors' device (a (B, k, D) gather and a (B, k, k) product); a metric, not a hot path; one read at the end."""
+    valid = idx >= 0
+    rows = table.float()[idx.clamp(min=0).long()]                               # (B, k, D)
+    norm = rows.norm(dim=2, keepdim=True)
+    unit = torch.where(norm > 0, rows / norm.clamp(min=torch.finfo(torch.float32).tiny), torch.zeros_like(rows))
+    unit = unit * valid.unsqueeze(2)
+    n = valid.sum(1).double()
+    gram = torch.bmm(unit, unit.transpose(1, 2)).double()
+    off_diagonal = gram.sum((1, 2)) - torch.diagonal(gram, dim1=1, dim2=2).sum(1)
+    users = n >= 2
+    if not bool(users.any()):
+        return 0.0
+    return float((off_diagonal[users] / (n[users] * (n[users] - 1))).mean())
+
+
 class StreamingMetrics:
     """Epoch metrics without the epoch's step outputs: ``update`` takes the tuple ``model_step`` / ``*Cache.model_step`` returns
     and launches ``nrl_impression_metrics`` into a float64 accumulator (one sum per metric column, an impression count and a status

@@ -938,6 +938,52 @@ def catalogue_bias_ranks(user_vec: torch.Tensor, table: torch.Tensor, bias: torc
                       excl_off, eligible, slices)
 
 
+# ---- greedy MMR re-ranking of a top-k pool (nrl_topk.hip: mmr_rerank_kernel) ------------------------------------------------------
+MMR_MAX_POOL = 128
+MMR_SIMILARITIES = {"cosine": 0, "dot": 1}
+# the status word of ``mmr_rerank``; a dictionary of its own: bit 1 means something else in ``TOPK_FLAGS``, whose key set is pinned
+MMR_FLAGS = {1: "a pool row other than -1 is outside [0, V) (that slot is dead)",
+             4: "a non-finite score, or a non-finite self-similarity, in a slot with a valid row (that slot is dead)"}
+
+
+def mmr_rerank(pool_idx: torch.Tensor, pool_score: torch.Tensor, table: torch.Tensor, k: int, lam: float,
+               similarity: str = "cosine", normalize: bool = True):
+    """``nrl_mmr_rerank``: greedy Maximal Marginal Relevance over a pool of table rows per user -> (idx (B, k) int64, score (B, k)
+    fp32, mmr (B, k) fp32, status (1) int32).  ``pool_idx`` (B, N) int64 (``-1``: an empty slot) and ``pool_score`` (B, N) fp32 are
+    what any ``topk_*`` wrapper returns, N at most ``MMR_MAX_POOL``; ``table`` (V, D) fp32 holds the news vectors.  Step by step
+    the live, unselected slot of largest ``lam * rel_i - (1 - lam) * max_{c selected} sim(c, i)`` is taken (ties: the lower slot);
+    ``similarity``: ``"cosine"`` or ``"dot"`` of the table rows, with the bits of ``topk_scores``' chain; ``normalize``: ``rel``
+    is the score min-max scaled over the user's live slots, else the score itself.  ``score`` is the slot's pool score unchanged,
+    ``mmr`` the objective it won with; ``-1`` / ``-inf`` / ``-inf`` once the live slots run out.  ``lam = 1`` without ``normalize``
+    returns the pool's first ``k`` entries.  The native header states every rounding.  ``status``: ``MMR_FLAGS``; it stays on the
+    device -- nothing here synchronises with the host."""
+    for t, dt, name in ((pool_idx, torch.int64, "pool_idx"), (pool_score, torch.float32, "pool_score"), (table, torch.float32, "table")):
+        if t.dtype != dt:
+            raise ValueError(f"newsreclib_amd: `{name}` must be {dt}, got {t.dtype}")
+    if pool_idx.dim() != 2 or pool_score.shape != pool_idx.shape or table.dim() != 2:
+        raise ValueError(f"newsreclib_amd: pool_idx (B, N), pool_score (B, N) and table (V, D) expected, got {tuple(pool_idx.shape)}, "
+                         f"{tuple(pool_score.shape)} and {tuple(table.shape)}")
+    if similarity not in MMR_SIMILARITIES:
+        raise ValueError(f"newsreclib_amd: similarity is one of {sorted(MMR_SIMILARITIES)}, got {similarity!r}")
+    B, N, V, D, k = int(pool_idx.shape[0]), int(pool_idx.shape[1]), int(table.shape[0]), int(table.shape[1]), int(k)
+    if N > MMR_MAX_POOL:
+        raise NotImplementedError(f"newsreclib_amd: mmr_rerank takes a pool of at most {MMR_MAX_POOL} slots (got {N})")
+    if not 1 <= k <= N:
+        raise ValueError(f"newsreclib_amd: k in [1, N = {N}] expected, got {k}")
+    if not 0.0 <= float(lam) <= 1.0:
+        raise ValueError(f"newsreclib_amd: lam in [0, 1] expected, got {lam}")
+    pool_idx, pool_score, table = _chk(pool_idx, torch.int64, "pool_idx"), _chk(pool_score, torch.float32, "pool_score"), \
+        _chk(table, torch.float32, "table")
+    lib = _lib.load()
+    dev = pool_idx.device
+    idx, score, status = _topk_outputs(B, k, dev)
+    mmr = torch.empty((B, k), dtype=torch.float32, device=dev)
+    _lib.check(lib.nrl_mmr_rerank(pool_idx.data_ptr(), pool_score.data_ptr(), table.data_ptr() if V else None, B, N, V, D, k,
+                                  float(lam), MMR_SIMILARITIES[similarity], int(bool(normalize)), idx.data_ptr(), score.data_ptr(),
+                                  mmr.data_ptr(), status.data_ptr(), _stream()), "nrl_mmr_rerank")
+    return idx, score, mmr, status
+
+
 TOPK_MAX_INTERESTS = 64
 
 
