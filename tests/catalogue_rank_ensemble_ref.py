@@ -7,19 +7,18 @@ Two references, both on the CPU:
   ascending t (torch on the CPU rounds every elementwise operation on its own), and the rank is counted in the order of the
   entry: higher z first, equal z by ascending row, -0 equal to +0.  Rows that are ineligible, excluded or NaN are outside the
   population; a user whose statistics cannot standardise (some sd not positive and finite) has ranks 0 and population 0.
-* ``rank_intervals``: the independent one, float64 (``topk_ensemble_ref.stats64``) under the derived tolerance of
-  ``test_gpu_topk_ensemble._ensemble64``: with ``tol`` the worst-case error of an fp32 ensemble score, a row v != t is certainly
-  above the target t when ``z64[v] - tol[v] > z64[t] + tol[t]`` and possibly above it when ``z64[v] + tol[v] >= z64[t] -
-  tol[t]``, so ``1 + #certain <= rank <= 1 + #possible``.  The tolerance grows with D (it is a worst case), so the intervals
-  are only sharp at small D; ``interval_case`` lists the inputs and tests/test_catalogue_rank_ensemble_host.py checks on the
-  reference alone that at least two thirds of them collapse to one point and none is wider than 2."""
+* ``catalogue_ref.rank_intervals``: the independent one, float64 under the derived tolerance of
+  ``topk_ensemble_ref.ensemble64``, the worst-case error of an fp32 ensemble score.  The tolerance grows with D (it is a worst
+  case), so the intervals are only sharp at small D; ``interval_case`` lists the inputs and
+  tests/test_catalogue_rank_ensemble_host.py checks on the reference alone that at least two thirds of them collapse to one
+  point and none is wider than 2."""
 import functools
 
 import torch
 
+from tests import catalogue_ref as C
 from tests import topk_ensemble_ref as R
 
-EPS = 2.0 ** -23
 WEIGHTS = (1.0, 0.2, -0.25)
 NEG_INF = float("-inf")
 INTERVAL_SHAPES = ((9, 300, 20), (9, 1000, 64))             # (B, V, D), D <= 64
@@ -41,53 +40,10 @@ def ensemble_from_bits(raw, stats, weights):
 
 def ranks_from_bits(raw, stats, weights, targets, excl=None, eligible=None):
     """rank int32 (n), score fp32 (n), ranked int32 (B): the exact reference of the module docstring."""
-    B, V = raw[0].shape
     z = ensemble_from_bits(raw, stats, weights)
-    pop = R.population(B, V, excl, eligible) & ~torch.isnan(z)
-    refused = ~sd_ok(stats[:, :, 1]).all(1)
-    pop[refused] = False
-    rows = torch.arange(V)
-    rank, score = [], []
-    for b, tl in enumerate(targets):
-        for t in tl:
-            if not 0 <= t < V or not bool(pop[b, t]):
-                rank.append(0)
-                score.append(NEG_INF)
-                continue
-            above = pop[b] & ((z[b] > z[b, t]) | ((z[b] == z[b, t]) & (rows < t)))
-            rank.append(1 + int(above.sum()))
-            score.append(float(z[b, t]))
-    return torch.tensor(rank, dtype=torch.int32), torch.tensor(score, dtype=torch.float32), pop.sum(1).to(torch.int32)
-
-
-def ensemble64(users, tables, weights, pop):
-    """float64 (B, V) ensemble scores over the population and their derived tolerance: ``test_gpu_topk_ensemble._ensemble64``."""
-    V = tables[0].shape[0]
-    agg, tol, mag = 0.0, 0.0, 0.0
-    for w, (s, bs, n, mean, sd) in zip(weights, R.stats64(users, tables, pop)):
-        dmu, dsd = R.stat_bounds(s, bs, n, sd, pop, V)
-        z = (s - mean[:, None]) / sd[:, None]
-        agg = agg + w * z
-        tol = tol + abs(w) * ((bs + dmu[:, None]) / sd[:, None] + z.abs() * (dsd / sd)[:, None])
-        mag = mag + (w * z).abs()
-    return agg, tol + 8 * EPS * mag
-
-
-def rank_intervals(agg, tol, pop, targets):
-    """Per target in the population (lo, hi) of the module docstring, None for a target outside it."""
-    V = agg.shape[1]
-    out = []
-    for b, tl in enumerate(targets):
-        for t in tl:
-            if not 0 <= t < V or not bool(pop[b, t]):
-                out.append(None)
-                continue
-            others = pop[b].clone()
-            others[t] = False
-            certain = others & (agg[b] - tol[b] > agg[b, t] + tol[b, t])
-            possible = others & (agg[b] + tol[b] >= agg[b, t] - tol[b, t])
-            out.append((1 + int(certain.sum()), 1 + int(possible.sum())))
-    return out
+    pop = C.population(z, excl, eligible)[0]
+    pop[~sd_ok(stats[:, :, 1]).all(1)] = False              # a refused user's population is empty
+    return C.ranks(z, pop, targets)
 
 
 @functools.lru_cache(maxsize=None)
@@ -98,9 +54,9 @@ def interval_case(B, V, D):
     g = torch.Generator().manual_seed(D)
     excl = tuple(tuple(torch.randint(0, V, (int(n),), generator=g).tolist()) for n in torch.randint(0, 10, (B,), generator=g))
     clicks = tuple(tuple(torch.randint(0, V, (int(n),), generator=g).tolist()) for n in torch.randint(1, 6, (B,), generator=g))
-    pop = R.population(B, V, excl)
-    agg, tol = ensemble64(users, tables, WEIGHTS, pop)
-    return users, tables, excl, clicks, pop, rank_intervals(agg, tol, pop, clicks)
+    pop = C.allowed(B, V, excl)
+    agg, tol = R.ensemble64(users, tables, WEIGHTS, pop)
+    return users, tables, excl, clicks, pop, C.rank_intervals(agg, tol, pop, clicks)
 
 
 def click_lists(seed, B, V, excl=None, eligible=None):

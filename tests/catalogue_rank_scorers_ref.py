@@ -4,9 +4,7 @@ test_gpu_catalogue_rank_scorers.py.
 
 Scores: ``interest_scores64`` (the aggregates of ``ops_miner.SCORE_MODES`` over ``s[b, j, v] = E64[b, j] . T64[v]``) and
 ``topk_dnn_ref.relu_scores64`` / ``topk_dnn_ref.scores64`` and ``topk_npa_ref.exact_case`` / ``topk_npa_ref.scores64`` with
-their derived bounds.  Masking and ranks are those of ``catalogue_rank_ref``: ineligible,
-excluded and NaN positions at ``-inf``, rank = 1 + the number of qualifying rows with a higher score or an equal score and a lower
-row.
+their derived bounds.  Population, ranks and rank intervals are those of ``tests/catalogue_ref.py``.
 
 Bounds of the MINER aggregates (derived, not measured), from the dot-product bound ``bs_j = D 2^-23 sum_i |e_ji| |t_i|`` of one fp32
 dot product of length D in any order (``bl_j`` likewise from the gate rows):
@@ -15,16 +13,12 @@ dot product of length D in any order (``bl_j`` likewise from the gate rows):
   mean      max_j bs_j + K 2^-23 max_j |s_j|             K - 1 additions and one division, 2^-24 relative each, rounded up
   weighted  max_j bs_j + (max_j s_j - min_j s_j) (expm1(2 max_j bl_j) + (K + 8) 2^-23) + K 2^-23 max_j |s_j|
             a convex combination moves by at most its spread times the relative change of its weights: logits off by bl_j change
-            the weight ratios by up to exp(2 bl); expf, the subtraction and the two sums add (K + 8) 2^-23.
-
-Rank interval of a target t of user b from float64 scores s and bounds e: a population row v can be on the other side of t in fp32
-only if ``|s[v] - s[t]| <= e[v] + e[t]``, so the fp32 rank lies in ``[lo, hi]`` with ``lo = 1 + #{v : s[v] - s[t] > e[v] + e[t]}``
-and ``hi = lo + #{v != t : |s[v] - s[t]| <= e[v] + e[t]}``."""
+            the weight ratios by up to exp(2 bl); expf, the subtraction and the two sums add (K + 8) 2^-23."""
 import functools
 
 import torch
 
-from tests import catalogue_rank_ref as C
+from tests import catalogue_ref as C
 from tests import topk_dnn_ref as DR
 from tests import topk_npa_ref as NR
 
@@ -36,7 +30,7 @@ def interest_scores64(E, T, mode, G=None):
     """float64 (B, V) aggregated scores of interests E (B, K, D) against T (V, D) and the derived fp32 bound (B, V)."""
     K, D = E.shape[1], E.shape[2]
     s = torch.einsum("bkd,vd->bkv", E.double(), T.double())
-    bs = D * EPS * torch.einsum("bkd,vd->bkv", E.double().abs(), T.double().abs())
+    bs = C.dot_bound(E.reshape(-1, D), T).reshape(E.shape[0], K, -1)
     if mode == "max":
         agg = s.max(dim=1)[0]
         agg[torch.isnan(s).any(dim=1)] = float("nan")           # (torch's max propagates NaN as well; spelled out)
@@ -44,39 +38,10 @@ def interest_scores64(E, T, mode, G=None):
     if mode == "mean":
         return s.sum(dim=1) / K, bs.max(dim=1)[0] + K * EPS * s.abs().max(dim=1)[0]
     lg = torch.einsum("bkd,vd->bkv", G.double(), T.double())
-    bl = D * EPS * torch.einsum("bkd,vd->bkv", G.double().abs(), T.double().abs())
+    bl = C.dot_bound(G.reshape(-1, D), T).reshape(E.shape[0], K, -1)
     agg = (torch.softmax(lg, dim=1) * s).sum(dim=1)
     spread = s.max(dim=1)[0] - s.min(dim=1)[0]
     return agg, bs.max(dim=1)[0] + spread * (torch.expm1(2 * bl.max(dim=1)[0]) + (K + 8) * EPS) + K * EPS * s.abs().max(dim=1)[0]
-
-
-def masked(s, excl=None, eligible=None):
-    """``topk_dnn_ref.mask`` with NaN scores at -inf as well (a copy)."""
-    s = DR.mask(s, excl, eligible)
-    s[torch.isnan(s)] = float("-inf")
-    return s
-
-
-def reference(s, targets, excl=None, eligible=None):
-    """(rank int32, score float32, ranked int32) of float64 scores ``s`` (B, V)."""
-    return C.ranks_from_scores(masked(s, excl, eligible), targets)
-
-
-def rank_intervals(s, bound, targets, excl=None, eligible=None):
-    """Per target in flat order ``(lo, hi)``, or None where the target is not in its user's population."""
-    m = masked(s, excl, eligible)
-    V = s.shape[1]
-    out = []
-    for b, tl in enumerate(targets):
-        ok = torch.isfinite(m[b])
-        for t in tl:
-            if not 0 <= t < V or not bool(ok[t]):
-                out.append(None)
-                continue
-            diff, margin = s[b] - s[b, t], bound[b] + bound[b, t]
-            lo = 1 + int((ok & (diff > margin)).sum())
-            out.append((lo, lo + int((ok & (diff.abs() <= margin)).sum()) - 1))      # (the target itself is always close)
-    return out
 
 
 # ---- the inputs both tiers use -----------------------------------------------------------------------------------------------------

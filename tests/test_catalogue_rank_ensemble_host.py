@@ -12,6 +12,7 @@ import pytest
 import torch
 
 from tests import catalogue_rank_ensemble_ref as ER
+from tests import catalogue_ref as C
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAMES = ("nrl_catalogue_ensemble_ranks_workspace_size", "nrl_catalogue_ensemble_ranks")
@@ -177,7 +178,7 @@ def test_exact_reference_against_a_stable_sort():
     rank, score, ranked = ER.ranks_from_bits(raw, stats, (1.0, -0.25), [list(range(V))] * B, excl, eligible)
     rank, score = rank.reshape(B, V), score.reshape(B, V)
     z = ER.ensemble_from_bits(raw, stats, (1.0, -0.25))
-    pop = ER.R.population(B, V, excl, eligible)
+    pop = C.allowed(B, V, excl, eligible)
     pop[:, 17] = False
     assert len(torch.unique(z[pop])) < 60                            # tie-heavy
     for b in range(B):

@@ -11,7 +11,7 @@ import numpy as np
 import pytest
 import torch
 
-from tests import catalogue_rank_ref as R
+from tests import catalogue_ref as C
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAMES = ("nrl_catalogue_ranks_workspace_size", "nrl_catalogue_ranks")
@@ -114,8 +114,9 @@ def test_reference_against_a_stable_sort():
     eligible = (torch.rand(V, generator=g) > 0.2).to(torch.uint8)
     excl = [torch.randint(0, V, (int(n),), generator=g).tolist() for n in (0, 3, 10, 1, 25, 7)]
     targets = [list(range(V)) for _ in range(B)]                     # every row of every user
-    rank, score, ranked = R.reference(U, T, targets, excl, eligible)
-    s = R.masked_scores(U, T, excl, eligible)
+    raw = U.double() @ T.double().T
+    rank, score, ranked = C.expected_ranks(raw, targets, excl, eligible)
+    s = C.masked(raw, C.population(raw, excl, eligible)[0])
     assert len(torch.unique(s)) < 12                                 # tie-heavy
     neg, order = torch.sort(-s, dim=1, stable=True)                  # score descending, equal scores by ascending row
     rank = rank.reshape(B, V)
@@ -125,7 +126,7 @@ def test_reference_against_a_stable_sort():
         assert torch.equal(rank[b, order[b, :n]], torch.arange(1, n + 1, dtype=torch.int32))
         assert bool((rank[b, order[b, n:]] == 0).all())
     assert bool((score.reshape(B, V)[rank == 0] == float("-inf")).all())
-    assert R.reference(U, T, [[-1, V], [], [], [], [], []])[0].tolist() == [0, 0]
+    assert C.expected_ranks(raw, [[-1, V], [], [], [], [], []])[0].tolist() == [0, 0]
 
 
 # ---- full_rank_metrics -----------------------------------------------------------------------------------------------------------
@@ -153,7 +154,7 @@ def test_full_rank_metrics_against_ranking_metrics_and_brute_force():
     from newsreclib_amd.metrics import full_rank_metrics, ranking_metrics
     s, clicks = _metric_case()
     B, V = s.shape
-    rank, _, ranked = R.ranks_from_scores(s, clicks)
+    rank, _, ranked = C.ranks(s, torch.isfinite(s), clicks)
     sizes = torch.tensor([len(c) for c in clicks])
     top_k = (1, 5, 10)
     got = full_rank_metrics(rank, sizes, ranked, top_k)

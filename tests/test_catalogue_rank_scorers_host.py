@@ -9,6 +9,7 @@ import subprocess
 import pytest
 import torch
 
+from tests import catalogue_ref as C
 from tests import catalogue_rank_scorers_ref as R
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -139,7 +140,8 @@ def test_python_entries_refuse_before_any_device_work():
             getattr(E.NewsVectorCache(object.__new__(NRMSModule), None), name)(hist, hs, torch.tensor([4]), torch.tensor([1, 0]))
 
 
-def _share_decided(intervals):
+def _share_decided(s, bound, targets, excl):
+    intervals = C.rank_intervals(s, bound, C.population(s, excl)[0], targets)
     valid = [iv for iv in intervals if iv is not None]
     return sum(lo == hi for lo, hi in valid) / len(valid), len(valid)
 
@@ -150,15 +152,15 @@ def test_the_rank_intervals_of_the_real_cases_are_not_vacuous():
     c = R.real_miner()
     for mode in R.MODES:
         s, bound = R.interest_scores64(c["E"], c["T"], mode, c["G"])
-        share, n = _share_decided(R.rank_intervals(s, bound, c["targets"], c["excl"]))
+        share, n = _share_decided(s, bound, c["targets"], c["excl"])
         print(f"MINER {mode}: lo == hi for {share:.3f} of {n} valid targets")
         assert n >= 20 and share >= 0.9, mode
     d = R.real_dkn()
-    share, n = _share_decided(R.rank_intervals(d["s"], d["bound"], d["targets"], d["excl"]))
+    share, n = _share_decided(d["s"], d["bound"], d["targets"], d["excl"])
     print(f"DKN: lo == hi for {share:.3f} of {n} valid targets")
     assert n >= 40 and share >= 0.9
     p = R.real_npa()
-    share, n = _share_decided(R.rank_intervals(p["s"], p["bound"], p["targets"], p["excl"]))
+    share, n = _share_decided(p["s"], p["bound"], p["targets"], p["excl"])
     print(f"NPA: lo == hi for {share:.3f} of {n} valid targets")
     assert n >= 20 and share >= 0.9
 

@@ -1,15 +1,15 @@
 """Full-catalogue rank of held-out clicks (``nrl_catalogue_ranks`` / ``ops.catalogue_ranks`` / ``NewsVectorCache.rank_clicks`` /
 ``evaluate_full_rank``).
 
-Expected values come from ``tests/catalogue_rank_ref.py`` (CPU, float64).  Integer-valued vectors in [-4, 4] make every fp32 dot
-product exact in any order (|s| <= 16 * 1024 < 2^24), so those cases compare with ``torch.equal``, ties included.  The
-real-valued case uses ``bound(u, v) = D * 2^-23 * sum_i |u_i| |v_i|``, the worst-case error of an fp32 dot product of length D
-(derived, as in ``test_gpu_topk.py``): a row can change sides of a target only if their float64 scores are closer than the sum of
-their two bounds."""
+Expected values come from ``tests/catalogue_ref.py`` (CPU, float64) over ``s = U64 @ T64.T``.  Integer-valued vectors in
+[-4, 4] make every fp32 dot product exact in any order (|s| <= 16 * 1024 < 2^24), so those cases compare with ``torch.equal``,
+ties included.  The real-valued case uses ``catalogue_ref.dot_bound``, the worst-case error of an fp32 dot product of length D
+(derived): a row can change sides of a target only if their float64 scores are closer than the sum of their two bounds."""
 import pytest
 import torch
 
-from tests import catalogue_rank_ref as R
+from tests import builders
+from tests import catalogue_ref as C
 
 pytestmark = pytest.mark.gpu
 
@@ -27,30 +27,25 @@ def engine(request):
     _lib.set_gemm_engine(prev)
 
 
-def _int_vectors(seed, B, V, D):
-    g = torch.Generator().manual_seed(seed)
-    return (torch.randint(-4, 5, (B, D), generator=g).float(), torch.randint(-4, 5, (V, D), generator=g).float())
+def _reference(U, T, targets, excl=None, eligible=None):
+    return C.expected_ranks(U.double() @ T.double().T, targets, excl, eligible)
 
 
 def _run(U, T, targets, excl=None, eligible=None, slices=0, tgt_off=None, excl_off=None):
     from newsreclib_amd import ops
-    ti, to = R.ragged(targets)
+    ti, to = C.ragged(targets)
     ei = eo = None
     if excl is not None:
-        ei, eo = R.ragged(excl)
+        ei, eo = C.ragged(excl)
         ei, eo = ei.cuda(), (excl_off if excl_off is not None else eo).cuda()
     rank, score, ranked, status = ops.catalogue_ranks(U.cuda(), T.cuda(), ti.cuda(), (tgt_off if tgt_off is not None else to).cuda(),
                                                       ei, eo, eligible.cuda() if eligible is not None else None, slices)
     return rank.cpu(), score.cpu(), ranked.cpu(), int(status)
 
 
-def _same(got, want):
-    return torch.equal(got[0], want[0]) and torch.equal(got[1], want[1]) and torch.equal(got[2], want[2])
-
-
 def _random_case(seed, B, V, D):
     """Targets (0 to 4 a user, a duplicate now and then), exclusion lists (0 to 9, duplicates allowed) and a mixed mask."""
-    U, T = _int_vectors(seed, B, V, D)
+    U, T = C.int_vectors(seed, B, V, D)
     g = torch.Generator().manual_seed(seed + 1)
     targets = [torch.randint(0, V, (int(n),), generator=g).tolist() for n in torch.randint(0, 5, (B,), generator=g)]
     targets[0] = targets[0] or [0]
@@ -64,25 +59,25 @@ def _random_case(seed, B, V, D):
 def test_exact_with_ties(B, V, D):
     U, T, targets, excl, eligible = _random_case(B * 7 + V + D, B, V, D)
     rank, score, ranked, status = _run(U, T, targets)
-    assert status == 0 and _same((rank, score, ranked), R.reference(U, T, targets))
+    assert status == 0 and C.same((rank, score, ranked), _reference(U, T, targets))
     assert bool((ranked == V).all())
     rank, score, ranked, status = _run(U, T, targets, excl, eligible)
-    assert status == 0 and _same((rank, score, ranked), R.reference(U, T, targets, excl, eligible))
+    assert status == 0 and C.same((rank, score, ranked), _reference(U, T, targets, excl, eligible))
 
 
 def test_slice_counts():
     """(70, 700, 36) has 6 table tiles: every slice count gives the reference."""
     U, T, targets, excl, eligible = _random_case(77, 70, 700, 36)
-    want = R.reference(U, T, targets, excl, eligible)
+    want = _reference(U, T, targets, excl, eligible)
     for slices in (0, 1, 2, 3, 4, 6):
         rank, score, ranked, status = _run(U, T, targets, excl, eligible, slices)
-        assert status == 0 and _same((rank, score, ranked), want), slices
+        assert status == 0 and C.same((rank, score, ranked), want), slices
 
 
 # ---- 2. target lists --------------------------------------------------------------------------------------------------------------
 def _target_case():
     B, V, D = 6, 300, 12
-    U, T = _int_vectors(41, B, V, D)
+    U, T = C.int_vectors(41, B, V, D)
     g = torch.Generator().manual_seed(42)
     eligible = torch.ones(V, dtype=torch.uint8)
     eligible[[7, 200]] = 0
@@ -95,8 +90,8 @@ def test_target_lists():
     """No targets, exactly 32, the same row twice, a target on the own exclusion list, an ineligible one, -1 and V."""
     U, T, targets, excl, eligible = _target_case()
     rank, score, ranked, status = _run(U, T, targets, excl, eligible, slices=2)
-    want = R.reference(U, T, targets, excl, eligible)
-    assert status == E_TARGET_ROW and _same((rank, score, ranked), want)
+    want = _reference(U, T, targets, excl, eligible)
+    assert status == E_TARGET_ROW and C.same((rank, score, ranked), want)
     r2 = rank[32:40].tolist()                                    # user 2: [17, 150, 17, 7, -1, V, 3, 299]
     assert r2[0] == r2[2] > 0 and r2[1] == r2[3] == r2[4] == r2[5] == r2[6] == 0 and r2[7] > 0
     assert bool((score[32:40][torch.tensor(r2) == 0] == NEG_INF).all())
@@ -106,7 +101,7 @@ def test_target_lists():
 def test_more_than_32_targets_blank_that_user_alone():
     U, T, targets, excl, eligible = _target_case()
     clean = [[t for t in tl if 0 <= t < T.shape[0]] for tl in targets]
-    want = R.reference(U, T, clean, excl, eligible)
+    want = _reference(U, T, clean, excl, eligible)
     over = [list(tl) for tl in clean]
     over[3] = list(range(33))
     rank, score, ranked, status = _run(U, T, over, excl, eligible)
@@ -122,18 +117,18 @@ def test_more_than_32_targets_blank_that_user_alone():
 
 def test_decreasing_target_offsets_blank_that_user_alone():
     B, V, D = 4, 40, 12
-    U, T = _int_vectors(17, B, V, D)
+    U, T = C.int_vectors(17, B, V, D)
     flat = [3, 9, 9, 0, 21, 39, 5, 6, 7]
     off = torch.tensor([0, 4, 9, 7, 7])                          # user 2 runs backwards; user 3 is empty
     from newsreclib_amd import ops
     rank, score, ranked, status = ops.catalogue_ranks(U.cuda(), T.cuda(), torch.tensor(flat).cuda(), off.cuda())
     assert int(status) == E_TARGETS
-    want = R.reference(U, T, [flat[0:4], flat[4:9], [], []])
-    assert _same((rank.cpu(), score.cpu(), ranked.cpu()), want)
+    want = _reference(U, T, [flat[0:4], flat[4:9], [], []])
+    assert C.same((rank.cpu(), score.cpu(), ranked.cpu()), want)
     # an offset beyond the list is rejected the same way
     rank, score, ranked, status = ops.catalogue_ranks(U.cuda(), T.cuda(), torch.tensor(flat).cuda(), torch.tensor([0, 4, 12, 9, 9]).cuda())
     assert int(status) == E_TARGETS
-    want = R.reference(U, T, [flat[0:4], [], [], []])
+    want = _reference(U, T, [flat[0:4], [], [], []])
     assert torch.equal(rank.cpu()[:4], want[0]) and bool((rank.cpu()[4:] == 0).all()) and torch.equal(ranked.cpu(), want[2])
 
 
@@ -141,14 +136,14 @@ def test_no_targets_still_counts_the_population():
     U, T, _, excl, eligible = _target_case()
     rank, score, ranked, status = _run(U, T, [[] for _ in range(6)], excl, eligible)
     assert status == 0 and rank.numel() == 0 and score.numel() == 0
-    assert torch.equal(ranked, R.reference(U, T, [[]] * 6, excl, eligible)[2])
+    assert torch.equal(ranked, _reference(U, T, [[]] * 6, excl, eligible)[2])
     assert ranked.tolist() == [298, 296, 296, 298, 298, 297]
 
 
 # ---- 3. masks -------------------------------------------------------------------------------------------------------------------------
 def _mask_case():
     B, V, D = 5, 700, 8
-    U, T = _int_vectors(5, B, V, D)
+    U, T = C.int_vectors(5, B, V, D)
     g = torch.Generator().manual_seed(3)
     long = torch.randperm(V, generator=g)[:70].tolist()          # beyond the 64 entries a workgroup caches
     excl = [[], [3, 3, 9, 3, 9, 650], long, [699, 0, 128, 127], long[:64] + long[:6]]
@@ -161,7 +156,7 @@ def test_exclusion_lists(slices):
     """Empty, with duplicates (a duplicate removes its row once), 70 entries (beyond the cached 64), at tile edges."""
     U, T, targets, excl = _mask_case()
     rank, score, ranked, status = _run(U, T, targets, excl, slices=slices)
-    assert status == 0 and _same((rank, score, ranked), R.reference(U, T, targets, excl))
+    assert status == 0 and C.same((rank, score, ranked), _reference(U, T, targets, excl))
     assert ranked.tolist() == [700, 697, 630, 696, 636]
 
 
@@ -171,20 +166,20 @@ def test_status_bad_exclusion_index_is_ignored():
     bad[1] = [-1] + bad[1]
     bad[3] = bad[3] + [T.shape[0]]
     rank, score, ranked, status = _run(U, T, targets, bad)
-    assert status == E_EXCLUDE and _same((rank, score, ranked), R.reference(U, T, targets, excl))
+    assert status == E_EXCLUDE and C.same((rank, score, ranked), _reference(U, T, targets, excl))
 
 
 def test_status_bad_exclusion_offsets_blank_that_user_alone():
     B, V, D = 4, 40, 12
-    U, T = _int_vectors(19, B, V, D)
+    U, T = C.int_vectors(19, B, V, D)
     excl_flat, targets = list(range(12)), [[20, 1], [30], [31, 4], [32]]
     off = torch.tensor([0, 5, 3, 8, 12])                         # user 1 runs backwards
     from newsreclib_amd import ops
-    ti, to = R.ragged(targets)
+    ti, to = C.ragged(targets)
     rank, score, ranked, status = ops.catalogue_ranks(U.cuda(), T.cuda(), ti.cuda(), to.cuda(), torch.tensor(excl_flat).cuda(), off.cuda())
     rank, score, ranked = rank.cpu(), score.cpu(), ranked.cpu()
     assert int(status) == E_OFFSETS
-    want = R.reference(U, T, targets, [excl_flat[0:5], [], excl_flat[3:8], excl_flat[8:12]])
+    want = _reference(U, T, targets, [excl_flat[0:5], [], excl_flat[3:8], excl_flat[8:12]])
     keep = torch.tensor([True, True, False, True, True, True])
     assert torch.equal(rank[keep], want[0][keep]) and torch.equal(score[keep], want[1][keep])
     assert int(rank[2]) == 0 and float(score[2]) == NEG_INF and int(ranked[1]) == 0
@@ -198,13 +193,13 @@ def test_eligibility():
     mixed = (torch.rand(V, generator=g) > 0.5).to(torch.uint8)
     for eligible in (None, mixed, mixed.bool()):
         rank, score, ranked, status = _run(U, T, targets, excl, eligible)
-        assert status == 0 and _same((rank, score, ranked), R.reference(U, T, targets, excl, eligible))
+        assert status == 0 and C.same((rank, score, ranked), _reference(U, T, targets, excl, eligible))
     rank, score, ranked, status = _run(U, T, targets, excl, torch.zeros(V, dtype=torch.uint8))
     assert status == 0 and not bool(rank.any()) and not bool(ranked.any()) and bool((score == NEG_INF).all())
 
 
 def test_empty_table():
-    U = _int_vectors(1, 3, 1, 8)[0]
+    U = C.int_vectors(1, 3, 1, 8)[0]
     rank, score, ranked, status = _run(U, torch.zeros(0, 8), [[0], [], [1, -1]])
     assert status == E_TARGET_ROW                                # every index is outside an empty table
     assert rank.tolist() == [0, 0, 0] and bool((score == NEG_INF).all()) and ranked.tolist() == [0, 0, 0]
@@ -212,7 +207,7 @@ def test_empty_table():
 
 def test_nan_row_is_left_out():
     B, V, D = 5, 300, 12
-    U, T = _int_vectors(23, B, V, D)
+    U, T = C.int_vectors(23, B, V, D)
     nan_row = 140
     targets = [[nan_row, 3], [5], [141, 139], [], [nan_row]]
     Tn = T.clone()
@@ -221,18 +216,14 @@ def test_nan_row_is_left_out():
     assert status == E_NAN
     elig = torch.ones(V, dtype=torch.uint8)
     elig[nan_row] = 0
-    assert _same((rank, score, ranked), R.reference(U, T, targets, eligible=elig))      # as if the row were not there
-    assert _same((rank, score, ranked), R.reference(U, Tn, targets))                   # (the reference drops NaN itself)
+    assert C.same((rank, score, ranked), _reference(U, T, targets, eligible=elig))      # as if the row were not there
+    assert C.same((rank, score, ranked), _reference(U, Tn, targets))                   # (the reference drops NaN itself)
     assert int(rank[0]) == 0 and int(rank[-1]) == 0 and bool((ranked == V - 1).all())
     # a NaN row nobody may be recommended is not reported
     assert _run(U, Tn, targets, eligible=elig)[3] == 0
 
 
 # ---- 4. consistency with topk_scores on real values ----------------------------------------------------------------------------------
-def _bound(U, T):
-    return U.shape[1] * 2.0 ** -23 * (U.double().abs() @ T.double().abs().T)
-
-
 _REAL_SEED = 36
 
 
@@ -260,8 +251,8 @@ def test_consistency_with_topk_scores_on_real_values(engine):
     assert status == 0 and bool((ranked == V).all()) and bool((rank >= 1).all())
     rank2, score2 = rank.reshape(B, 6), score.reshape(B, 6)
     assert rank2[:, 3:].tolist() == [[1, 64, 128]] * B
-    s64, bound = U.double() @ T.double().T, _bound(U, T)
-    ref = R.ranks_from_scores(s64, targets)[0].reshape(B, 6)
+    s64, bound = U.double() @ T.double().T, C.dot_bound(U, T)
+    ref = C.expected_ranks(s64, targets)[0].reshape(B, 6)
     worst_allow = worst_off = 0
     for b in range(B):
         for j, t in enumerate(targets[b]):
@@ -282,7 +273,7 @@ def test_consistency_with_topk_scores_on_real_values(engine):
     if engine == "f32":
         _F32[key] = (rank, score, ranked)
     elif key in _F32:
-        assert _same((rank, score.view(torch.int32), ranked), (_F32[key][0], _F32[key][1].view(torch.int32), _F32[key][2]))
+        assert C.same((rank, score.view(torch.int32), ranked), (_F32[key][0], _F32[key][1].view(torch.int32), _F32[key][2]))
 
 
 # ---- 5. invariance ----------------------------------------------------------------------------------------------------------------------
@@ -296,7 +287,7 @@ def test_invariance(engine):
     sizes = torch.randint(0, 5, (B,), generator=g)
     targets = [torch.randint(0, V, (int(n),), generator=g).tolist() for n in sizes]
     excl = [torch.randint(0, V, (int(n),), generator=g).tolist() for n in torch.randint(0, 30, (B,), generator=g)]
-    (ti, to), (ei, eo) = R.ragged(targets), R.ragged(excl)
+    (ti, to), (ei, eo) = C.ragged(targets), C.ragged(excl)
     ti, to, ei, eo = ti.cuda(), to.cuda(), ei.cuda(), eo.cuda()
 
     def bits(out):
@@ -306,14 +297,14 @@ def test_invariance(engine):
     assert int(base[3]) == 0
     for slices in (1, 2, 7):
         out = ops.catalogue_ranks(U, T, ti, to, ei, eo, slices=slices)
-        assert int(out[3]) == 0 and _same(bits(out), bits(base)), slices
+        assert int(out[3]) == 0 and C.same(bits(out), bits(base)), slices
     singles = []
     for b in range(B):
         t1, e1 = torch.tensor(targets[b], dtype=torch.int64).cuda(), torch.tensor(excl[b], dtype=torch.int64).cuda()
         singles.append(ops.catalogue_ranks(U[b:b + 1], T, t1, torch.tensor([0, len(targets[b])]).cuda(), e1,
                                            torch.tensor([0, len(excl[b])]).cuda()))
     assert all(int(s[3]) == 0 for s in singles)
-    assert _same(bits(tuple(torch.cat([s[i] for s in singles]) for i in range(3))), bits(base))
+    assert C.same(bits(tuple(torch.cat([s[i] for s in singles]) for i in range(3))), bits(base))
     if engine == "f32":
         _F32["invariance"] = tuple(x.cpu() for x in bits(base))
     else:
@@ -321,21 +312,20 @@ def test_invariance(engine):
             _lib.set_gemm_engine("f32")
             _F32["invariance"] = tuple(x.cpu() for x in bits(ops.catalogue_ranks(U, T, ti, to, ei, eo)))
             _lib.set_gemm_engine(engine)
-        assert _same(tuple(x.cpu() for x in bits(base)), _F32["invariance"])
+        assert C.same(tuple(x.cpu() for x in bits(base)), _F32["invariance"])
 
 
 # ---- 6. no read-back, memory ---------------------------------------------------------------------------------------------------------------
 def test_catalogue_ranks_does_not_synchronise_with_the_host():
     from newsreclib_amd import ops
-    from tests.test_gpu_topk import _sync_debug_honoured
-    U, T = _int_vectors(3, 5, 200, 12)
+    U, T = C.int_vectors(3, 5, 200, 12)
     U, T = U.cuda(), T.cuda()
-    (ti, to), (ei, eo) = R.ragged([[1, 2], [], [5], [7, 7], [199]]), R.ragged([[1], [], [5, 6], [], []])
+    (ti, to), (ei, eo) = C.ragged([[1, 2], [], [5], [7, 7], [199]]), C.ragged([[1], [], [5, 6], [], []])
     ti, to, ei, eo, elig = ti.cuda(), to.cuda(), ei.cuda(), eo.cuda(), torch.ones(200, dtype=torch.uint8).cuda()
     torch.cuda.synchronize()
     torch.cuda.set_sync_debug_mode("error")
     try:
-        if not _sync_debug_honoured():
+        if not C.sync_debug_honoured():
             pytest.skip("this torch build does not raise on synchronising calls under set_sync_debug_mode('error')")
         rank, score, ranked, status = ops.catalogue_ranks(U, T, ti, to, ei, eo, elig)
     finally:
@@ -365,10 +355,9 @@ def test_peak_memory_is_far_below_the_score_matrix():
 # ---- 7. cache level ---------------------------------------------------------------------------------------------------------------------------
 def _cache_case():
     from newsreclib_amd.evaluation import DeviceNewsTable, NewsVectorCache
-    from tests.test_gpu_topk import _hist_batch, _tiny
-    mod, attrs = _tiny("nrms")
+    mod, attrs = builders.tiny("nrms")
     cache = NewsVectorCache(mod, DeviceNewsTable(attrs), chunk=32)
-    lists, hist, hs, uidx = _hist_batch(50)
+    lists, hist, hs, uidx = builders.hist_batch(50)
     return mod, cache, lists, hist, hs, uidx
 
 

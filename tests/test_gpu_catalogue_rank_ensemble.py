@@ -9,7 +9,7 @@ Three references (tests/catalogue_rank_ensemble_ref.py):
   the order of the entry.  Every rank, population and score bit must be equal;
 * ``ops.topk_ensemble_scores``: ``rank = r <= k`` exactly when slot ``r - 1`` of that call is the click, with equal score bits and
   equal statistics bits;
-* float64 at D <= 64 under the derived tolerance of ``test_gpu_topk_ensemble._ensemble64``: each rank inside its interval (the
+* float64 at D <= 64 under the derived tolerance of ``topk_ensemble_ref.ensemble64``: each rank inside its interval (the
   host tier checks on the reference alone that the intervals are sharp on these inputs)."""
 import functools
 import warnings
@@ -17,9 +17,10 @@ import warnings
 import pytest
 import torch
 
+from tests import builders
 from tests import catalogue_rank_ensemble_ref as ER
+from tests import catalogue_ref as C
 from tests import topk_ensemble_ref as R
-from tests.test_gpu_topk import _ragged, _sync_debug_honoured
 
 pytestmark = pytest.mark.gpu
 
@@ -37,10 +38,6 @@ def engine(request):
     _lib.set_gemm_engine(prev)
 
 
-def _bits(x):
-    return x.view(torch.int32)
-
-
 def _int_case(seed, T, B, V, D):
     g = torch.Generator().manual_seed(seed)
     return ([torch.randint(-4, 5, (B, D), generator=g).float() for _ in range(T)],
@@ -49,10 +46,10 @@ def _int_case(seed, T, B, V, D):
 
 def _run(users, tables, weights, targets, excl=None, eligible=None, slices=0, tgt_off=None, excl_off=None):
     from newsreclib_amd import ops
-    ti, to = _ragged([list(x) for x in targets])
+    ti, to = C.ragged([list(x) for x in targets])
     ei = eo = None
     if excl is not None:
-        ei, eo = _ragged([list(x) for x in excl])
+        ei, eo = C.ragged([list(x) for x in excl])
         ei, eo = ei.cuda(), (excl_off if excl_off is not None else eo).cuda()
     rank, score, ranked, status, stats = ops.catalogue_ensemble_ranks(
         [u.cuda() for u in users], [t.cuda() for t in tables], list(weights), ti.cuda(), (tgt_off if tgt_off is not None else to).cuda(),
@@ -64,18 +61,18 @@ def _topk(users, tables, weights, k, excl=None, eligible=None, slices=0):
     from newsreclib_amd import ops
     ei = eo = None
     if excl is not None:
-        ei, eo = (t.cuda() for t in _ragged([list(x) for x in excl]))
+        ei, eo = (t.cuda() for t in C.ragged([list(x) for x in excl]))
     idx, score, status, stats = ops.topk_ensemble_scores([u.cuda() for u in users], [t.cuda() for t in tables], list(weights), k, ei, eo,
                                                          eligible.cuda() if eligible is not None else None, slices)
     return idx.cpu(), score.cpu(), int(status), stats.cpu()
 
 
 def _same_slots(a, b, slots):
-    return torch.equal(a[0][slots], b[0][slots]) and torch.equal(_bits(a[1][slots]), _bits(b[1][slots]))
+    return torch.equal(a[0][slots], b[0][slots]) and torch.equal(C.bits(a[1][slots]), C.bits(b[1][slots]))
 
 
 def _same_users(a, b, users):
-    return torch.equal(a[2][users], b[2][users]) and torch.equal(_bits(a[4][users]), _bits(b[4][users]))
+    return torch.equal(a[2][users], b[2][users]) and torch.equal(C.bits(a[4][users]), C.bits(b[4][users]))
 
 
 def _slots(targets, users):
@@ -140,7 +137,7 @@ def test_exact_ranks_from_the_librarys_own_bits(T, B, V, D, slices):
     want = ER.ranks_from_bits(raw, stats, WEIGHTS[:T], clicks, excl, eligible)
     assert torch.equal(ranked, want[2])
     assert torch.equal(rank, want[0])
-    assert torch.equal(_bits(score), _bits(want[1]))
+    assert torch.equal(C.bits(score), C.bits(want[1]))
     r0 = rank[:32].tolist()                                   # user 0: a duplicate, -1, V, an excluded row, an ineligible row
     assert r0[0] == r0[1] and r0[2] == r0[3] == 0
     if V >= 129:
@@ -148,7 +145,7 @@ def test_exact_ranks_from_the_librarys_own_bits(T, B, V, D, slices):
         if B > 1:                                             # rows 3 and 100 are copies: equal bits, adjacent ranks
             a, b = int(rank[32]), int(rank[33])
             if a and b:
-                assert b == a + 1 and torch.equal(_bits(score[32]), _bits(score[33]))
+                assert b == a + 1 and torch.equal(C.bits(score[32]), C.bits(score[33]))
 
 
 # ---- 2. agreement with the top-k ---------------------------------------------------------------------------------------------------
@@ -159,7 +156,7 @@ def _agrees_with_topk(rank, score, clicks, idx, top_score, k):
             r = int(rank[at])
             assert (1 <= r <= k) == bool((idx[b] == c).any()), (b, c, r, k)
             if 1 <= r <= k:
-                assert int(idx[b, r - 1]) == c and torch.equal(_bits(score[at]), _bits(top_score[b, r - 1])), (b, c, r, k)
+                assert int(idx[b, r - 1]) == c and torch.equal(C.bits(score[at]), C.bits(top_score[b, r - 1])), (b, c, r, k)
             at += 1
 
 
@@ -182,7 +179,7 @@ def test_agreement_with_the_topk(T, B, V, D):
         at += len(clicks[b])
         assert int(rank[at - 1]) == int(rank[at - 2]) == 0     # the excluded row and the ineligible row
     for k, (idx_k, score_k, status_k, stats_k) in tops.items():
-        assert status_k == 0 and torch.equal(_bits(stats_k), _bits(stats)), k
+        assert status_k == 0 and torch.equal(C.bits(stats_k), C.bits(stats)), k
         _agrees_with_topk(rank, score, clicks, idx_k, score_k, k)
 
 
@@ -199,7 +196,7 @@ def test_copies_of_one_row_rank_one_two_three_with_equal_bits():
     assert status == 0 and bool((ranked == V).all())
     assert rank.reshape(B, 3).tolist() == [[3, 1, 2]] * B
     s = score.reshape(B, 3)
-    assert torch.equal(_bits(s[:, 0]), _bits(s[:, 1])) and torch.equal(_bits(s[:, 0]), _bits(s[:, 2]))
+    assert torch.equal(C.bits(s[:, 0]), C.bits(s[:, 1])) and torch.equal(C.bits(s[:, 0]), C.bits(s[:, 2]))
 
 
 # ---- 3. float64, small D -----------------------------------------------------------------------------------------------------------
@@ -270,7 +267,7 @@ def test_status_nan_table_row_is_left_out_of_every_population():
     # NaN in one table alone: the row leaves that table's statistics and, its ensemble score being NaN, every population
     out = _run(users, [tables[0], tn[1]], WEIGHTS[:2], _STATUS_CLICKS, slices=2)
     assert out[3] == E_NAN and bool((out[2] == V - 1).all()) and out[0].tolist()[1] == 0
-    assert torch.equal(_bits(out[4][:, 1]), _bits(want[4][:, 1]))
+    assert torch.equal(C.bits(out[4][:, 1]), C.bits(want[4][:, 1]))
 
 
 def test_status_nan_in_one_users_vector_refuses_that_user_alone():
@@ -297,7 +294,7 @@ def test_status_decreasing_exclusion_offsets_refuse_that_user_alone():
     others = [0, 2, 3, 4]
     assert want[3] == 0 and torch.equal(out[2][others], want[2][others])
     assert _same_slots(out, want, _slots(_STATUS_CLICKS, others))
-    assert torch.equal(_bits(out[4][others]), _bits(want[4][others]))
+    assert torch.equal(C.bits(out[4][others]), C.bits(want[4][others]))
 
 
 def test_status_decreasing_target_offsets_refuse_that_user_alone():
@@ -309,8 +306,8 @@ def test_status_decreasing_target_offsets_refuse_that_user_alone():
     want = _run(users, tables, WEIGHTS[:2], [flat[0:4], flat[4:7], [], [], flat[7:9]])
     assert want[3] == 0
     # slots 4 .. 8 were claimed by users 1 and 4 (the later user owns 7 and 8); user 1 keeps 4, 5, 6
-    assert torch.equal(out[0], want[0]) and torch.equal(_bits(out[1]), _bits(want[1]))
-    assert torch.equal(out[2], want[2]) and torch.equal(_bits(out[4]), _bits(want[4]))
+    assert torch.equal(out[0], want[0]) and torch.equal(C.bits(out[1]), C.bits(want[1]))
+    assert torch.equal(out[2], want[2]) and torch.equal(C.bits(out[4]), C.bits(want[4]))
 
 
 def test_status_33_clicks_through_the_c_entry_refuse_that_user_alone():
@@ -322,10 +319,10 @@ def test_status_33_clicks_through_the_c_entry_refuse_that_user_alone():
     assert out[3] == E_TARGETS
     s3 = _slots(clicks, [3])
     assert bool((out[0][s3] == 0).all()) and bool((out[1][s3] == NEG_INF).all())
-    assert torch.equal(out[2], clean[2]) and torch.equal(_bits(out[4]), _bits(clean[4]))      # the population is still counted
+    assert torch.equal(out[2], clean[2]) and torch.equal(C.bits(out[4]), C.bits(clean[4]))      # the population is still counted
     others = [0, 1, 2, 4]
     a, b = _slots(clicks, others), _slots(_STATUS_CLICKS, others)
-    assert torch.equal(out[0][a], clean[0][b]) and torch.equal(_bits(out[1][a]), _bits(clean[1][b]))
+    assert torch.equal(out[0][a], clean[0][b]) and torch.equal(C.bits(out[1][a]), C.bits(clean[1][b]))
 
 
 def test_no_table_and_no_targets():
@@ -336,7 +333,7 @@ def test_no_table_and_no_targets():
     assert bool((out[1] == NEG_INF).all()) and bool(torch.isnan(out[4]).all())
     empty = _run(users, tables, WEIGHTS[:2], [[]] * 5)
     clean = _run(users, tables, WEIGHTS[:2], _STATUS_CLICKS)
-    assert empty[3] == 0 and empty[0].numel() == 0 and torch.equal(empty[2], clean[2]) and torch.equal(_bits(empty[4]), _bits(clean[4]))
+    assert empty[3] == 0 and empty[0].numel() == 0 and torch.equal(empty[2], clean[2]) and torch.equal(C.bits(empty[4]), C.bits(clean[4]))
 
 
 # ---- 5. invariance and determinism ---------------------------------------------------------------------------------------------------
@@ -352,8 +349,8 @@ def test_invariance_and_determinism(V):
     excl = [torch.randint(0, V, (int(n),), generator=g).tolist() for n in torch.randint(0, 80, (B,), generator=g)]
     clicks = [torch.randint(0, V, (int(n),), generator=g).tolist() for n in torch.randint(0, 6, (B,), generator=g)]
     clicks[0], clicks[64] = [1, 2, 3], [V - 2, 7]
-    ei, eo = (t.cuda() for t in _ragged(excl))
-    ti, to = (t.cuda() for t in _ragged(clicks))
+    ei, eo = (t.cuda() for t in C.ragged(excl))
+    ti, to = (t.cuda() for t in C.ragged(clicks))
     elig = torch.ones(V, dtype=torch.uint8)
     elig[[0, 500, V - 1]] = 0
     elig = elig.cuda()
@@ -363,8 +360,8 @@ def test_invariance_and_determinism(V):
 
     def same(out, name):
         assert int(out[3]) == 0, name
-        assert torch.equal(out[0], base[0]) and torch.equal(_bits(out[1]), _bits(base[1])), name
-        assert torch.equal(out[2], base[2]) and torch.equal(_bits(out[4]), _bits(base[4])), name
+        assert torch.equal(out[0], base[0]) and torch.equal(C.bits(out[1]), C.bits(base[1])), name
+        assert torch.equal(out[2], base[2]) and torch.equal(C.bits(out[4]), C.bits(base[4])), name
 
     base = run()
     assert int(base[3]) == 0 and bool((base[2] > V - 90).all())
@@ -372,7 +369,7 @@ def test_invariance_and_determinism(V):
         same(run(slices), slices)
     singles = []
     for b in range(B):
-        (xi, xo), (ci, co) = _ragged([excl[b]]), _ragged([clicks[b]])
+        (xi, xo), (ci, co) = C.ragged([excl[b]]), C.ragged([clicks[b]])
         singles.append(ops.catalogue_ensemble_ranks([u[b:b + 1] for u in users], tables, list(WEIGHTS), ci.cuda(), co.cuda(), xi.cuda(),
                                                     xo.cuda(), elig))
     same(tuple(torch.cat([s[i] for s in singles]) if i != 3 else sum(s[3] for s in singles) for i in range(5)), "one at a time")
@@ -389,10 +386,9 @@ def test_invariance_and_determinism(V):
 def test_rank_clicks_ensemble_against_recommend_ensemble(tmp_path):
     from newsreclib_amd.evaluation import MannerVectorCache, evaluate_full_rank
     from newsreclib_amd.metrics import full_rank_metrics
-    from tests.test_gpu_manner import _ensemble, _modules, _table_and_impressions
-    cr, ac, asent = _modules(tmp_path)
-    ens = _ensemble(cr, ac, asent)
-    table, imps = _table_and_impressions()
+    cr, ac, asent = builders.manner_modules(tmp_path)
+    ens = builders.manner_ensemble(cr, ac, asent)
+    table, imps = builders.manner_table_and_impressions()
     V, B, k = table.num_news, len(imps), 10
     cache = MannerVectorCache(ens, table)
     lists = [i["hist"] for i in imps]
@@ -413,7 +409,7 @@ def test_rank_clicks_ensemble_against_recommend_ensemble(tmp_path):
     ens.eval()
     assert int(status) == 0 and rank.shape == (int(cs.sum()),) and ranked.shape == (B,) and stats.shape == (B, 3, 2)
     assert len(cache.rank_clicks_ensemble(hist.cuda(), hs, click_idx.cuda(), cs, eligible=eligible)) == 4
-    assert torch.equal(_bits(stats.cpu()), _bits(top_stats.cpu()))
+    assert torch.equal(C.bits(stats.cpu()), C.bits(top_stats.cpu()))
     rank, score, ranked = rank.cpu(), score.cpu(), ranked.cpu()
     assert ranked.tolist() == [V - len(set(lists[b].tolist()) | {0}) for b in range(B)]    # all but the padding row and the history
     _agrees_with_topk(rank, score, clicks, idx, top_score, k)
@@ -461,7 +457,7 @@ def test_peak_memory_is_far_below_one_score_matrix():
     users, tables = [u.cuda() for u in users], [t.cuda() for t in tables]
     g = torch.Generator().manual_seed(5)
     clicks = [torch.randint(0, V, (int(n),), generator=g).tolist() for n in torch.randint(1, 6, (B,), generator=g)]
-    ti, to = (t.cuda() for t in _ragged(clicks))
+    ti, to = (t.cuda() for t in C.ragged(clicks))
     ops.catalogue_ensemble_ranks([u[:2] for u in users], [t[:256] for t in tables], list(WEIGHTS), ti[:1] * 0, to[:3] * 0)   # kernels resident
     torch.cuda.synchronize()
     torch.cuda.reset_peak_memory_stats()
@@ -478,13 +474,13 @@ def test_catalogue_ensemble_ranks_does_not_synchronise_with_the_host():
     from newsreclib_amd import ops
     users, tables = _int_case(3, 3, 5, 200, 12)
     users, tables = [u.cuda() for u in users], [t.cuda() for t in tables]
-    ei, eo = _ragged([[1, 2], [], [5], [7, 7], []])
-    ti, to = _ragged([[3], [4, 4], [], [199], [0, 1, 2]])
+    ei, eo = C.ragged([[1, 2], [], [5], [7, 7], []])
+    ti, to = C.ragged([[3], [4, 4], [], [199], [0, 1, 2]])
     ei, eo, ti, to, elig = ei.cuda(), eo.cuda(), ti.cuda(), to.cuda(), torch.ones(200, dtype=torch.bool).cuda()
     torch.cuda.synchronize()
     torch.cuda.set_sync_debug_mode("error")
     try:
-        if not _sync_debug_honoured():
+        if not C.sync_debug_honoured():
             pytest.skip("this torch build does not raise on synchronising calls under set_sync_debug_mode('error')")
         out = ops.catalogue_ensemble_ranks(users, tables, list(WEIGHTS), ti, to, ei, eo, elig)
     finally:

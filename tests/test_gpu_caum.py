@@ -6,6 +6,7 @@ import torch
 
 from oracle import losses_oracle as LO
 from oracle.nrms_oracle import to_dense_batch
+from tests import builders
 from tests import caum_oracle as CO
 from tests.helpers import batch_to, check_lstur_grads, load_golden, module_grads
 
@@ -19,10 +20,6 @@ def engine(request):
     _lib.set_gemm_engine(request.param)
     yield request.param
     _lib.set_gemm_engine(prev)
-
-
-def _tols(engine):
-    return (5e-5, 5e-4) if engine == "f32" else (1e-4, 1e-3)
 
 
 def _dense(preds, sizes, shape):
@@ -53,7 +50,7 @@ def test_caum_module_matches_reference_golden(name, engine, monkeypatch):
     mod.news_encoder.forward = lambda *a, **kw: seen.setdefault("news", enc_fwd(*a, **kw))
     batch = batch_to(CO.golden_batch(g), "cuda")
     loss, preds, targets, cand_news_size, *_ = mod.model_step(batch)
-    ftol, gtol = _tols(engine)
+    ftol, gtol = builders.head_tols(engine)
     ref = g["out_scores"]
     got = _dense(preds, cand_news_size, ref.shape)
     assert float(np.abs(got - ref).max()) <= 20 * ftol * max(1.0, float(np.abs(ref).max())), float(np.abs(got - ref).max())

@@ -6,6 +6,7 @@ import functools
 import pytest
 import torch
 
+from tests import builders
 from tests import caum_oracle as CO
 from tests.caum_factored_ref import factored_scores
 from tests.helpers import batch_to, load_golden
@@ -23,8 +24,7 @@ def engine(request):
 
 
 def _ftol(engine):
-    from tests.test_gpu_caum import _tols
-    return _tols(engine)[0]
+    return builders.head_tols(engine)[0]
 
 
 def _sizes(B, lo, hi):

@@ -6,29 +6,10 @@ import pytest
 import torch
 
 from oracle import nrms_oracle as O
+from tests import builders
 from tests.helpers import build_module
 
 pytestmark = pytest.mark.gpu
-
-
-def _impressions(rng, n_imp, n_news, max_hist=12, max_cand=40):
-    imps = []
-    for i in range(n_imp):
-        nh, nc = int(rng.integers(1, max_hist + 1)), int(rng.integers(2, max_cand + 1))
-        lab = np.zeros(nc, dtype=np.float32)
-        lab[rng.integers(0, nc)] = 1.0
-        imps.append({"hist": torch.from_numpy(rng.integers(1, n_news, nh)), "cand": torch.from_numpy(rng.integers(1, n_news, nc)),
-                     "labels": torch.from_numpy(lab), "user_idx": torch.tensor(i % 7)})
-    return imps
-
-
-def _table(rng, n_news, vocab, L=30, n_categ=19):
-    lens = rng.integers(3, L + 1, n_news)
-    ids = rng.integers(1, vocab, (n_news, L))
-    ids[np.arange(L)[None, :] >= lens[:, None]] = 0
-    ids[0] = 0
-    return {"title": torch.from_numpy(ids), "category": torch.from_numpy(rng.integers(1, n_categ, n_news)),
-            "sentiment": torch.from_numpy(rng.integers(1, 4, n_news))}
 
 
 @pytest.mark.parametrize("engine_name", ["f32", "bf16x3"])
@@ -42,11 +23,11 @@ def test_cached_scores_equal_uncached_forward_and_oracle(engine_name):
         vocab, n_news = 300, 157
         params = O.make_params(vocab, seed=8)
         mod = build_module(params).eval()
-        table = DeviceNewsTable(_table(rng, n_news, vocab))
+        table = DeviceNewsTable(builders.news_table(rng, n_news, vocab))
         cache = NewsVectorCache(mod, table, chunk=64)        # several chunks, last one partial
         vec = cache.build()
         assert vec.shape == (n_news, 300)
-        imps = _impressions(rng, 9, n_news)
+        imps = builders.impressions(rng, 9, n_news)
         hist = torch.cat([i["hist"] for i in imps])
         cand = torch.cat([i["cand"] for i in imps])
         hs = torch.tensor([len(i["hist"]) for i in imps])
@@ -82,9 +63,9 @@ def test_evaluate_impressions_metrics_and_full_impression_width():
     rng = np.random.default_rng(11)
     vocab, n_news = 400, 500
     mod = build_module(O.make_params(vocab, seed=2)).eval()
-    table = DeviceNewsTable(_table(rng, n_news, vocab))
+    table = DeviceNewsTable(builders.news_table(rng, n_news, vocab))
     cache = NewsVectorCache(mod, table)
-    imps = _impressions(rng, 40, n_news, max_hist=50, max_cand=300)
+    imps = builders.impressions(rng, 40, n_news, max_hist=50, max_cand=300)
     logs = evaluate_impressions(cache, imps, batch_size=16, num_categ_classes=19, num_sent_classes=4)
     for k in ("auc", "mrr", "ndcg@5", "ndcg@10", "categ_div@5", "categ_pers@10", "sent_div@10", "sent_pers@5", "loss"):
         assert k in logs and np.isfinite(logs[k]), k
@@ -114,11 +95,11 @@ def test_lstur_cached_scores_equal_uncached_forward():
     params = make_lstur_params(cfg["vocab"], cfg["n_categ"], cfg["n_users"], 48, 48, 3, 32, 16, seed=5)
     mod = build_lstur_module(cfg, params).eval()
     n_news = 90
-    attrs = _table(rng, n_news, cfg["vocab"], L=12, n_categ=7)
-    attrs["abstract"] = _table(rng, n_news, cfg["vocab"], L=20)["title"]
+    attrs = builders.news_table(rng, n_news, cfg["vocab"], L=12, n_categ=7)
+    attrs["abstract"] = builders.news_table(rng, n_news, cfg["vocab"], L=20)["title"]
     table = DeviceNewsTable(attrs)
     cache = NewsVectorCache(mod, table, chunk=32)
-    imps = _impressions(rng, 6, n_news, max_hist=8, max_cand=12)
+    imps = builders.impressions(rng, 6, n_news, max_hist=8, max_cand=12)
     hist, cand = torch.cat([i["hist"] for i in imps]), torch.cat([i["cand"] for i in imps])
     hs, cs = torch.tensor([len(i["hist"]) for i in imps]), torch.tensor([len(i["cand"]) for i in imps])
     uidx = torch.stack([i["user_idx"] for i in imps])
@@ -156,11 +137,11 @@ def test_sibling_models_cached_scores_equal_uncached_forward(model):
                    text_attrs=("title", "abstract"), text_order=("title", "abstract"), p_drop=0.2)
         mod = H.build_mins_module(cfg, make_mins_params(vocab, 7, 48, 32, 16, 4, seed=5))
     mod = mod.eval()
-    attrs = _table(rng, n_news, vocab, L=12, n_categ=7)
-    attrs["abstract"] = _table(rng, n_news, vocab, L=20)["title"]
+    attrs = builders.news_table(rng, n_news, vocab, L=12, n_categ=7)
+    attrs["abstract"] = builders.news_table(rng, n_news, vocab, L=20)["title"]
     table = DeviceNewsTable(attrs)
     cache = NewsVectorCache(mod, table, chunk=32)
-    imps = _impressions(rng, 6, n_news, max_hist=8, max_cand=12)
+    imps = builders.impressions(rng, 6, n_news, max_hist=8, max_cand=12)
     hist, cand = torch.cat([i["hist"] for i in imps]), torch.cat([i["cand"] for i in imps])
     hs, cs = torch.tensor([len(i["hist"]) for i in imps]), torch.tensor([len(i["cand"]) for i in imps])
     got = cache.scores(hist, hs, cand, cs)
@@ -335,7 +316,7 @@ def test_news_vector_cache_and_epoch_hooks_use_the_token_table():
     vocab, n_news = 900, 333
     params = O.make_params(vocab, seed=2)
     mod = build_module(params).eval()
-    table = DeviceNewsTable(_table(rng, n_news, vocab))
+    table = DeviceNewsTable(builders.news_table(rng, n_news, vocab))
     uses = MHSAAddAtt.TOKEN_TABLE_USES
     b0 = uses["built"]
     vec = NewsVectorCache(mod, table, chunk=100).build()
@@ -353,7 +334,7 @@ def test_news_vector_cache_and_epoch_hooks_use_the_token_table():
         te.token_table = orig
     assert torch.equal(vec, ref)
     # epoch hooks of the drop-in module
-    imps = _impressions(rng, 6, n_news)
+    imps = builders.impressions(rng, 6, n_news)
     hist, cand = torch.cat([i["hist"] for i in imps]), torch.cat([i["cand"] for i in imps])
     hs, cs = torch.tensor([len(i["hist"]) for i in imps]), torch.tensor([len(i["cand"]) for i in imps])
     batch = table.build_batch(hist, hs, cand, cs, torch.cat([i["labels"] for i in imps]))
@@ -416,8 +397,7 @@ def _small_batch(full=False):
 
 def _small_cache(model, tmp_path=None):
     from newsreclib_amd.evaluation import DeviceNewsTable, NewsVectorCache
-    from tests.test_gpu_topk import _tiny
-    mod, table = _tiny(model, tmp_path=tmp_path, n_news=13)
+    mod, table = builders.tiny(model, tmp_path=tmp_path, n_news=13)
     table = table if isinstance(table, DeviceNewsTable) else DeviceNewsTable(table)
     assert table.num_news == 13
     return mod, NewsVectorCache(mod, table)
@@ -486,8 +466,7 @@ def test_manner_cache_model_step_has_a_zero_loss_and_the_gathered_scores(tmp_pat
     """(The third impression lists one candidate: its z-score is 0 / 0 = NaN, as in the reference, so the scores are compared as
     bit patterns.)"""
     from newsreclib_amd.evaluation import MannerVectorCache
-    from tests.test_gpu_manner import _ensemble, _modules, _table_and_impressions
-    cache = MannerVectorCache(_ensemble(*_modules(tmp_path)), _table_and_impressions(13)[0])
+    cache = MannerVectorCache(builders.manner_ensemble(*builders.manner_modules(tmp_path)), builders.manner_table_and_impressions(13)[0])
     hist, hs, cand, cs, labels = _small_batch()
     out = cache.model_step(hist, hs, cand, cs, labels)
     assert len(out) == 11 and out[0].shape == () and float(out[0]) == 0.0

@@ -8,7 +8,7 @@ from newsreclib_amd import input_pipeline as IP
 from oracle import input_oracle as IO
 from oracle import nrms_oracle as O
 from tests.helpers import build_module
-from tests.test_input_pipeline import ATTRS, assert_batches_equal, make_frames
+from tests.builders import ATTRS, assert_batches_equal, make_frames
 
 pytestmark = pytest.mark.gpu
 

@@ -9,8 +9,9 @@ import pytest
 import torch
 
 from tests import manner_oracle as MO
+from tests.builders import (N_ENT, a_kwargs, cr_kwargs, entity_table, manner_ensemble, manner_modules, manner_news,
+                            manner_table_and_impressions)
 from tests.helpers import make_tiny_roberta
-from tests.test_manner_host import N_ENT, a_kwargs, cr_kwargs, entity_table
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
@@ -162,17 +163,13 @@ def test_manner_scores_mind_like(k):
 
 
 # ---- modules ----------------------------------------------------------------------------------------------------------------------
-def _news(n, L, seed, use_entities=True):
-    from newsreclib_amd.synthetic import make_news_batch
-    b = make_news_batch(n, 1, vocab_size=200, n_entities=N_ENT, L=L, seed=seed, use_entities=use_entities)["news"]
-    return {k: ({kk: vv.to(DEV) for kk, vv in v.items()} if isinstance(v, dict) else v.to(DEV)) for k, v in b.items()}
 
 
 def _rec_batch(hs, cs, seed=1):
     B = len(hs)
     g = torch.Generator().manual_seed(seed)
     labels = torch.cat([(torch.arange(c) == int(torch.randint(0, c, (1,), generator=g))).float() for c in cs])
-    batch = {"x_hist": _news(sum(hs), 12, seed), "x_cand": _news(sum(cs), 10, seed + 1),
+    batch = {"x_hist": manner_news(sum(hs), 12, seed), "x_cand": manner_news(sum(cs), 10, seed + 1),
              "batch_hist": torch.repeat_interleave(torch.arange(B), torch.tensor(hs)).to(DEV),
              "batch_cand": torch.repeat_interleave(torch.arange(B), torch.tensor(cs)).to(DEV),
              "labels": labels.to(DEV), "user_ids": (torch.arange(B) + 1).to(DEV), "user_idx": torch.arange(B).to(DEV),
@@ -183,32 +180,11 @@ def _rec_batch(hs, cs, seed=1):
     return batch
 
 
-def _modules(tmp_path):
-    from newsreclib_amd.manner_a_module import AModule
-    from newsreclib_amd.manner_cr_module import CRModule
-    plm = make_tiny_roberta(str(tmp_path))
-    torch.manual_seed(11)
-    cr = CRModule(**cr_kwargs(plm, late_fusion=True), pretrained_entity_embeddings=entity_table(1)).to(DEV).eval()
-    ac = AModule(**a_kwargs(plm), pretrained_entity_embeddings=entity_table(2)).to(DEV).eval()
-    asent = AModule(**a_kwargs(plm, use_entities=False)).to(DEV).eval()
-    with torch.no_grad():                                    # three different encoders (the same tiny body otherwise)
-        for i, m in enumerate((cr, ac, asent)):
-            for p in m.news_encoder.combine_layer.parameters():
-                p.copy_(torch.randn(p.shape, generator=torch.Generator().manual_seed(20 + i)).to(DEV) * 0.3)
-    return cr, ac, asent
-
-
-def _ensemble(cr, ac, asent, cw=0.2, sw=-0.25):
-    from newsreclib_amd.manner_module import MANNERModule
-    return MANNERModule.from_modules(cr, ac, asent, outputs={"test": ["preds", "targets", "cand_news_size"]}, categ_weight=cw,
-                                     sent_weight=sw, top_k_list=[5, 10], num_categ_classes=4, num_sent_classes=3).eval()
-
-
 def test_ensemble_forward_matches_the_loops(tmp_path, engine):
-    cr, ac, asent = _modules(tmp_path)
+    cr, ac, asent = manner_modules(tmp_path)
     hs, cs = [3, 1, 4], [4, 2, 5]
     batch = _rec_batch(hs, cs)
-    ens = _ensemble(cr, ac, asent)
+    ens = manner_ensemble(cr, ac, asent)
     with torch.no_grad():
         scores = ens(batch).cpu()
         tables = [torch.cat([m.news_encoder(batch["x_hist"]), m.news_encoder(batch["x_cand"])]).double().cpu() for m in (cr, ac, asent)]
@@ -221,34 +197,19 @@ def test_ensemble_forward_matches_the_loops(tmp_path, engine):
     assert float(scores[1, 2:].abs().max()) == 0.0
     out = ens.model_step(batch)
     assert len(out) == 10 and out[0].shape == (11,) and torch.equal(out[2].cpu(), torch.tensor(cs))
-    only_cr = _ensemble(cr, None, None, cw=0, sw=0)
+    only_cr = manner_ensemble(cr, None, None, cw=0, sw=0)
     with torch.no_grad():
         s1 = only_cr(batch).cpu()
     ref1 = MO.ensemble_scores(tables[:1], [1.0], hist, cand)
     assert all(torch.allclose(s1[b, :len(r)].double(), r, rtol=1e-4, atol=1e-4) for b, r in enumerate(ref1))
 
 
-def _table_and_impressions(n_news=40, seed=3):
-    from newsreclib_amd.evaluation import DeviceNewsTable
-    g = torch.Generator().manual_seed(seed)
-    news = _news(n_news, 12, seed)
-    attrs = dict(news, category=torch.randint(1, 5, (n_news,), generator=g), sentiment=torch.randint(1, 4, (n_news,), generator=g))
-    imps = []
-    for _ in range(9):
-        h, c = int(torch.randint(1, 6, (1,), generator=g)), int(torch.randint(2, 8, (1,), generator=g))
-        lab = torch.zeros(c)
-        lab[int(torch.randint(0, c, (1,), generator=g))] = 1.0
-        imps.append({"hist": torch.randint(0, n_news, (h,), generator=g), "cand": torch.randperm(n_news, generator=g)[:c],
-                     "labels": lab})
-    return DeviceNewsTable(attrs, device=DEV), imps
-
-
 def test_vector_cache_equals_forward_and_metrics(tmp_path, engine):
     from newsreclib_amd.evaluation import MannerVectorCache, NewsVectorCache, evaluate_impressions
     from newsreclib_amd.metrics import aspect_metrics, ranking_metrics
-    cr, ac, asent = _modules(tmp_path)
-    ens = _ensemble(cr, ac, asent)
-    table, imps = _table_and_impressions()
+    cr, ac, asent = manner_modules(tmp_path)
+    ens = manner_ensemble(cr, ac, asent)
+    table, imps = manner_table_and_impressions()
     cache = MannerVectorCache(ens, table)
     hs, cs = torch.tensor([len(i["hist"]) for i in imps]), torch.tensor([len(i["cand"]) for i in imps])
     hidx, cidx = torch.cat([i["hist"] for i in imps]), torch.cat([i["cand"] for i in imps])

@@ -7,7 +7,7 @@ import torch
 
 from tests import manner_oracle as MO
 from tests.helpers import check_grads_against_golden, load_golden, module_grads
-from tests.test_manner_host import a_kwargs, cr_kwargs
+from tests.builders import a_kwargs, cr_kwargs
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
@@ -54,8 +54,6 @@ def _a(tmp_path, param_seed, temperature, p):
     mod = AModule(**a_kwargs(MO.make_body(str(tmp_path)), temperature=temperature, p_drop=p),
                   pretrained_entity_embeddings=params[MO.ENT + "embedding_layer.weight"].clone())
     return _load(mod, params)
-
-
 
 
 @pytest.mark.parametrize("name", ["manner_cr_tiny_train", "manner_cr_tiny_late_fusion", "manner_cr_tiny_eval"])

@@ -13,6 +13,8 @@ import torch
 
 from oracle import metrics_oracle as MO
 
+from tests import builders
+
 pytestmark = pytest.mark.gpu
 
 TOL = 2e-5
@@ -333,12 +335,11 @@ def _eval_setup(n_imp=40):
     from newsreclib_amd.evaluation import DeviceNewsTable, NewsVectorCache
     from oracle import nrms_oracle as O
     from tests.helpers import build_module
-    from tests.test_gpu_eval import _impressions, _table
     rng = np.random.default_rng(11)
     vocab, n_news = 400, 500
     mod = build_module(O.make_params(vocab, seed=2)).eval()
-    table = DeviceNewsTable(_table(rng, n_news, vocab))
-    return mod, table, NewsVectorCache(mod, table), _impressions(rng, n_imp, n_news, max_hist=50, max_cand=300)
+    table = DeviceNewsTable(builders.news_table(rng, n_news, vocab))
+    return mod, table, NewsVectorCache(mod, table), builders.impressions(rng, n_imp, n_news, max_hist=50, max_cand=300)
 
 
 def test_evaluate_impressions_with_device_metrics_equals_the_default():

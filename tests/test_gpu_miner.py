@@ -12,6 +12,7 @@ import torch
 
 from oracle import losses_oracle as LO
 from oracle.nrms_oracle import to_dense_batch
+from tests import builders
 from tests import miner_oracle as MO
 from tests.helpers import batch_to, check_lstur_grads, load_golden, make_tiny_roberta, module_grads
 
@@ -25,10 +26,6 @@ def engine(request):
     _lib.set_gemm_engine(request.param)
     yield request.param
     _lib.set_gemm_engine(prev)
-
-
-def _tols(engine):
-    return (5e-5, 5e-4) if engine == "f32" else (1e-4, 1e-3)
 
 
 def _close(got, ref, atol, rtol):
@@ -46,24 +43,6 @@ def _dense(preds, sizes, shape):
     return dense
 
 
-def _golden_module(name, tmp_path, monkeypatch=None, **overrides):
-    g = load_golden(name)
-    cfg = MO.golden_cfg(g)
-    over = dict(text_embed_dim=96) if name == "miner_head_full" else {}          # (the head fixture never runs the body)
-    over.update(overrides)
-    params = MO.golden_params(cfg)
-    if name == "miner_head_full":
-        params = {k: v for k, v in params.items() if not k.startswith(MO.TXT)}
-        params.update({MO.TXT + "reduce_dim.weight": torch.zeros(cfg["Dn"], 96), MO.TXT + "reduce_dim.bias": torch.zeros(cfg["Dn"])})
-    mod = MO.build_module(cfg, params, MO.make_body(str(tmp_path), cfg), **over)
-    mod.train() if cfg["p_drop"] > 0 else mod.eval()
-    mod.news_encoder.text_encoders["title"].plm_model.eval()
-    if monkeypatch is not None:
-        from newsreclib_amd import miner_module
-        monkeypatch.setattr(miner_module, "_draw_seed", lambda: cfg["seed"])
-    return g, cfg, mod
-
-
 def _cpu_oracle(mod, cfg, tmp_path):
     """(body, params) on the CPU holding the module's CURRENT weights."""
     from transformers import AutoModel
@@ -79,7 +58,7 @@ def _cpu_oracle(mod, cfg, tmp_path):
 
 @pytest.mark.parametrize("name", MO.MINER_TINY_CASES)
 def test_miner_module_matches_reference_golden(name, engine, tmp_path, monkeypatch):
-    g, cfg, mod = _golden_module(name, tmp_path, monkeypatch)
+    g, cfg, mod = builders.miner_golden_module(name, tmp_path, monkeypatch)
     seen = {}
     fwd = mod.forward
     mod.forward = lambda *a, **kw: seen.setdefault("out", fwd(*a, **kw))
@@ -112,13 +91,13 @@ def test_miner_head_matches_reference_golden_at_config_widths(engine, tmp_path, 
     """User encoder, category bias, target-aware scorer and disagreement loss at the miner.yaml widths (D = 256, K = 32,
     Cd = 200, 200 candidates, histories 50 / 23 / 1 / 37), forward and every gradient."""
     from newsreclib_amd.nrms_module import prepare_batch
-    g, cfg, mod = _golden_module("miner_head_full", tmp_path, monkeypatch)
+    g, cfg, mod = builders.miner_golden_module("miner_head_full", tmp_path, monkeypatch)
     hist_vec, cand_vec, batch = _head_inputs(g, cfg)
     hv, cv = hist_vec.cuda().requires_grad_(True), cand_vec.cuda().requires_grad_(True)
     pb = prepare_batch(batch_to(batch, "cuda"))
     scores, uv = mod.score_news_vectors(hv, cv, pb, seed=cfg["seed"], with_aux=True)
     loss = mod._loss(scores, torch.from_numpy(g["out_y_true"]).cuda(), pb) + mod._aux_loss(pb, uv)
-    ftol, gtol = _tols(engine)
+    ftol, gtol = builders.head_tols(engine)
     stride = int(g["cfg_sample_stride"])
     print("head", engine, "scores err", float((scores.detach().cpu() - torch.from_numpy(g["out_scores"])).abs().max()),
           "loss", float(loss.detach()), float(g["out_loss"]))
@@ -159,7 +138,7 @@ def test_closed_form_padded_rows_equal_materialised_rows(max_hist, engine):
     P = LinearActFn.apply(dev[0], dev[1], torch.zeros(Cd, device="cuda"), "tanh", None)
     got = ops_miner.PolyFn.apply(dev[0], P, dev[2], dev[3], off, B, max_hist)
     (got * d_out.cuda()).sum().backward()
-    ftol, gtol = _tols(engine)
+    ftol, gtol = builders.head_tols(engine)
     _close(got, want.detach(), ftol, gtol)
     for a, b, name in zip(dev, (E, W, codes, bias), ("E", "W", "codes", "bias")):
         _close(a.grad, b.grad, 1e-5, gtol)
@@ -189,7 +168,7 @@ def test_scores_over_300_candidates_in_tiles(score_type, engine):
     got = ops_miner.ScoreFn.apply(c, u, z, off, B, 300, score_type)
     assert bool((got[1, 7:] == 0).all())
     (got * d_out.cuda()).sum().backward()
-    ftol, gtol = _tols(engine)
+    ftol, gtol = builders.head_tols(engine)
     _close(got, (want * mask).detach(), ftol, gtol)
     _close(c.grad, cand.grad, 1e-5, gtol)
     _close(u.grad, uv.grad, 1e-5, gtol)
@@ -198,7 +177,7 @@ def test_scores_over_300_candidates_in_tiles(score_type, engine):
 
 
 def test_miner_batch_of_one_and_full_histories(engine, tmp_path):
-    g, cfg, mod = _golden_module("miner_tiny_eval", tmp_path)
+    g, cfg, mod = builders.miner_golden_module("miner_tiny_eval", tmp_path)
     body, params = _cpu_oracle(mod, cfg, tmp_path)
     batch = MO.golden_batch(g)
     one = {"batch_hist": torch.zeros(5, dtype=torch.int64), "batch_cand": torch.zeros(7, dtype=torch.int64),
@@ -230,7 +209,7 @@ def test_miner_batch_of_one_and_full_histories(engine, tmp_path):
 
 def test_miner_padded_candidates_score_exactly_zero(engine, tmp_path):
     for name in ("miner_tiny_eval", "miner_tiny_max", "miner_tiny_mean", "miner_tiny_late_fusion"):
-        g, cfg, mod = _golden_module(name, tmp_path)
+        g, cfg, mod = builders.miner_golden_module(name, tmp_path)
         mod.eval()
         batch = MO.golden_batch(g)
         with torch.no_grad():
@@ -249,7 +228,7 @@ def test_miner_steps_are_bit_reproducible(engine, tmp_path, monkeypatch):
     engines' split-K weight gradients, the sorted-segment table gradient), which add partial sums atomically."""
     runs = []
     for _ in range(2):
-        g, cfg, mod = _golden_module("miner_tiny_train", tmp_path, monkeypatch)
+        g, cfg, mod = builders.miner_golden_module("miner_tiny_train", tmp_path, monkeypatch)
         loss = mod.model_step(batch_to(MO.golden_batch(g), "cuda"))[0]
         loss.backward()
         runs.append((loss.detach().cpu(), {k: v.detach().cpu().clone() for k, v in module_grads(mod).items()}))
@@ -289,7 +268,7 @@ def test_miner_dual_loss_step_matches_oracle(engine, tmp_path):
 
 
 def test_miner_frozen_body_layers_get_no_gradient(engine, tmp_path, monkeypatch):
-    g, cfg, mod = _golden_module("miner_tiny_train", tmp_path, monkeypatch)
+    g, cfg, mod = builders.miner_golden_module("miner_tiny_train", tmp_path, monkeypatch)
     mod.model_step(batch_to(MO.golden_batch(g), "cuda"))[0].backward()
     frozen = [(k, p) for k, p in mod.named_parameters() if any(f"layer.{i}." in k for i in MO.BODY_FROZEN)]
     assert frozen and all(not p.requires_grad and p.grad is None for _, p in frozen)
@@ -316,7 +295,7 @@ def test_miner_trainer_step_matches_oracle_adam_and_refreshes_images(engine, tmp
     each against the oracle at the module's CURRENT weights -- nothing derived from a weight (matrix-core images of the body's
     and the head's projections) may survive the optimizer's write."""
     from newsreclib_amd.trainer import NRMSTrainer
-    g, cfg, mod = _golden_module("miner_tiny_train", tmp_path, monkeypatch)
+    g, cfg, mod = builders.miner_golden_module("miner_tiny_train", tmp_path, monkeypatch)
     batch = MO.golden_batch(g)
     lr = 1e-4
     trainer = NRMSTrainer(mod, lr=lr)
@@ -346,26 +325,12 @@ def test_miner_trainer_step_matches_oracle_adam_and_refreshes_images(engine, tmp
         assert float((scores.cpu() - ref).abs().max()) <= 2e-4
 
 
-def _table_case(g):
-    """One table row per history / candidate row of the fixture, both sides padded to one length."""
-    batch = MO.golden_batch(g)
-    L = max(batch["x_hist"]["title"]["input_ids"].shape[1], batch["x_cand"]["title"]["input_ids"].shape[1])
-
-    def pad(t, value):
-        return torch.nn.functional.pad(t, (0, L - t.shape[1]), value=value)
-
-    title = {"input_ids": torch.cat([pad(batch["x_" + s]["title"]["input_ids"], 1) for s in ("hist", "cand")]),
-             "attention_mask": torch.cat([pad(batch["x_" + s]["title"]["attention_mask"], 0) for s in ("hist", "cand")])}
-    categ = torch.cat([batch["x_hist"]["category"], batch["x_cand"]["category"]])
-    return batch, title, categ
-
-
 @pytest.mark.parametrize("name", ["miner_tiny_eval", "miner_tiny_no_bias", "miner_tiny_late_fusion"])
 def test_miner_news_vector_cache_matches_forward(name, engine, tmp_path):
     from newsreclib_amd.evaluation import DeviceNewsTable, NewsVectorCache
-    g, cfg, mod = _golden_module(name, tmp_path)
+    g, cfg, mod = builders.miner_golden_module(name, tmp_path)
     mod.eval()
-    batch, title, categ = _table_case(g)
+    batch, title, categ = builders.miner_table_case(g)
     table = DeviceNewsTable({"title": title, "category": categ}, device="cuda")
     nh, nc, B = batch["batch_hist"].shape[0], batch["batch_cand"].shape[0], batch["batch_size"]
     hs, cs = torch.bincount(batch["batch_hist"], minlength=B), torch.bincount(batch["batch_cand"], minlength=B)
@@ -380,7 +345,7 @@ def test_miner_news_vector_cache_matches_forward(name, engine, tmp_path):
         want = mod(own)[0]
     mod.news_encoder.forward = enc
     assert torch.equal(cache.vectors, torch.cat(seen, dim=0))
-    ftol, gtol = _tols(engine)
+    ftol, gtol = builders.head_tols(engine)
     _close(got, want.cpu(), ftol, gtol)
     if cfg["p_drop"] == 0.0:          # (the other fixtures hold train-mode scores)
         assert float((got.cpu() - torch.from_numpy(g["out_scores"])).abs().max()) <= 2e-4

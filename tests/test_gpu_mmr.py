@@ -10,8 +10,9 @@ import numpy as np
 import pytest
 import torch
 
+from tests import builders
+from tests import catalogue_ref as C
 from tests import mmr_ref as R
-from tests.test_gpu_topk import _sync_debug_honoured
 
 pytestmark = pytest.mark.gpu
 
@@ -23,18 +24,6 @@ def engine(request):
     _lib.set_gemm_engine(request.param)
     yield request.param
     _lib.set_gemm_engine(prev)
-
-
-def _bits(x):
-    return x.contiguous().view(torch.int32)
-
-
-def _same(got, want):
-    """a GPU result against a numpy expectation: equal values, and for floats equal bits"""
-    got = got.cpu()
-    want = torch.from_numpy(np.ascontiguousarray(want))
-    assert got.shape == want.shape and got.dtype == want.dtype, (got.shape, want.shape, got.dtype, want.dtype)
-    return torch.equal(_bits(got), _bits(want)) if got.dtype == torch.float32 else torch.equal(got, want)
 
 
 def _rerank(idx, score, table, k, lam, similarity="cosine", normalize=True):
@@ -119,17 +108,17 @@ def test_exact_sweep_rows_scores_and_objective_bits(B, N, D):
         users = list(range(B)) if B * k <= 2000 else [0, 1, 2, 3, B - 2, B - 1]
         w_idx, w_score, w_mmr = _expected(B, N, D, users, k, lam, sim, norm)
         assert int(status) == want_flags, (k, lam, sim, norm, int(status))
-        assert _same(got_idx[users], w_idx), (k, lam, sim, norm)
-        assert _same(got_score[users], w_score) and _same(got_mmr[users], w_mmr), (k, lam, sim, norm)
+        assert C.same(got_idx[users], w_idx), (k, lam, sim, norm)
+        assert C.same(got_score[users], w_score) and C.same(got_mmr[users], w_mmr), (k, lam, sim, norm)
         if B >= 3:                                           # the all-empty user and the user with two live slots
             assert bool((got_idx[1] == -1).all()) and bool(torch.isneginf(got_score[1]).all()) and bool(torch.isneginf(got_mmr[1]).all())
             assert int((got_idx[2] >= 0).sum()) == min(k, 2)
         if B * k > 2000:                                     # every user: the list of k is a prefix-extension of the list of 5
             s_idx, s_score, s_mmr, _ = _rerank(idx, score, table, 5, lam, sim, norm)
-            assert torch.equal(s_idx, got_idx[:, :5]) and torch.equal(_bits(s_score), _bits(got_score[:, :5]))
-            assert torch.equal(_bits(s_mmr), _bits(got_mmr[:, :5]))
+            assert torch.equal(s_idx, got_idx[:, :5]) and torch.equal(C.bits(s_score), C.bits(got_score[:, :5]))
+            assert torch.equal(C.bits(s_mmr), C.bits(got_mmr[:, :5]))
             all5 = _expected(B, N, D, list(range(B)), 5, lam, sim, norm)
-            assert _same(s_idx, all5[0]) and _same(s_score, all5[1]) and _same(s_mmr, all5[2])
+            assert C.same(s_idx, all5[0]) and C.same(s_score, all5[1]) and C.same(s_mmr, all5[2])
 
 
 def test_a_duplicated_row_has_cosine_one_and_the_zero_row_cosine_zero():
@@ -162,7 +151,7 @@ def test_the_gram_matrix_has_the_bits_of_topk_scores(D):
     for u in range(B):
         pos = (all_idx[u] == got_idx[u, 1]).nonzero()
         assert pos.numel() == 1
-        assert torch.equal(_bits(got_mmr[u, 1:2]), _bits(-all_score[u, pos[0, 0]].reshape(1)))
+        assert torch.equal(C.bits(got_mmr[u, 1:2]), C.bits(-all_score[u, pos[0, 0]].reshape(1)))
         in_pool = torch.isin(all_idx[u], idx[u, 1:])
         assert float(all_score[u][in_pool].min()) == -float(got_mmr[u, 1])       # and it is the pool's smallest
 
@@ -227,28 +216,28 @@ def test_prefix_batch_composition_engine_and_lambda_one():
     table = table.cuda()
     full = ops.mmr_rerank(idx, score, table, K_GEN, 0.5)
     part = ops.mmr_rerank(idx, score, table, 5, 0.5)
-    assert all(torch.equal(_bits(p), _bits(f[:, :5])) for p, f in zip(part[:3], full[:3]))
+    assert all(torch.equal(C.bits(p), C.bits(f[:, :5])) for p, f in zip(part[:3], full[:3]))
     # a user alone, and inside a batch of 130 at another place
     big_idx, big_score = idx.repeat(4, 1)[:130].contiguous(), score.repeat(4, 1)[:130].contiguous()
     big = ops.mmr_rerank(big_idx, big_score, table, K_GEN, 0.5)
     alone = ops.mmr_rerank(idx[7:8].contiguous(), score[7:8].contiguous(), table, K_GEN, 0.5)
     for u in (7, 47, 87, 127):
-        assert all(torch.equal(_bits(a[0]), _bits(b[u])) for a, b in zip(alone[:3], big[:3]))
-    assert all(torch.equal(_bits(b[:B_GEN]), _bits(f)) for b, f in zip(big[:3], full[:3]))
+        assert all(torch.equal(C.bits(a[0]), C.bits(b[u])) for a, b in zip(alone[:3], big[:3]))
+    assert all(torch.equal(C.bits(b[:B_GEN]), C.bits(f)) for b, f in zip(big[:3], full[:3]))
     # the engine setting
     prev = _lib.get_gemm_engine()
     try:
         for name in ("f32", "bf16x3"):
             _lib.set_gemm_engine(name)
             again = ops.mmr_rerank(idx, score, table, K_GEN, 0.5)
-            assert all(torch.equal(_bits(a), _bits(f)) for a, f in zip(again[:3], full[:3])), name
+            assert all(torch.equal(C.bits(a), C.bits(f)) for a, f in zip(again[:3], full[:3])), name
     finally:
         _lib.set_gemm_engine(prev)
     # lambda = 1 without normalisation: the pool's first k entries, whatever the similarity
     for sim in ("cosine", "dot"):
         one = ops.mmr_rerank(idx, score, table, K_GEN, 1.0, sim, False)
-        assert int(one[3]) == 0 and torch.equal(one[0], idx[:, :K_GEN]) and torch.equal(_bits(one[1]), _bits(score[:, :K_GEN]))
-        assert torch.equal(_bits(one[2]), _bits(score[:, :K_GEN]))
+        assert int(one[3]) == 0 and torch.equal(one[0], idx[:, :K_GEN]) and torch.equal(C.bits(one[1]), C.bits(score[:, :K_GEN]))
+        assert torch.equal(C.bits(one[2]), C.bits(score[:, :K_GEN]))
 
 
 def test_bad_arguments_are_refused_before_any_launch():
@@ -279,7 +268,7 @@ def test_mmr_rerank_does_not_synchronise_with_the_host():
     torch.cuda.synchronize()
     torch.cuda.set_sync_debug_mode("error")
     try:
-        if not _sync_debug_honoured():
+        if not C.sync_debug_honoured():
             pytest.skip("this torch build does not raise on synchronising calls under set_sync_debug_mode('error')")
         out = ops.mmr_rerank(idx, score, table, 10, 0.5)
         short = ops.mmr_rerank(idx[:, :40].contiguous(), score[:, :40].contiguous(), table, 10, 0.7, "dot", False)
@@ -303,11 +292,10 @@ def test_recommend_users_diversifies_an_nrms_cache():
     from newsreclib_amd import ops
     from newsreclib_amd.evaluation import DeviceNewsTable, NewsVectorCache, NpaFeatureCache, recommend_users
     from newsreclib_amd.metrics import intra_list_similarity
-    from tests.test_gpu_topk import _hist_batch, _tiny
-    mod, attrs = _tiny("nrms", n_news=200)
+    mod, attrs = builders.tiny("nrms", n_news=200)
     cache = NewsVectorCache(mod, DeviceNewsTable(attrs), chunk=64)
     V, B, k = 200, 6, 10
-    lists, hist, hs, uidx = _hist_batch(V)
+    lists, hist, hs, uidx = builders.hist_batch(V)
     users = [{"hist": lists[b], "user_id": 100 + b} for b in range(B)]
     plain = recommend_users(cache, users, k, batch_size=B)
     assert recommend_users(cache, users, k, batch_size=B, diversify=None) == plain
@@ -316,7 +304,7 @@ def test_recommend_users_diversifies_an_nrms_cache():
     recs = recommend_users(cache, users, k, batch_size=B, diversify=(64, 0.5))
     by_hand = cache.rerank_diverse(pool_idx, pool_score, k, 0.5)
     want = ops.mmr_rerank(pool_idx, pool_score, cache.vectors, k, 0.5, "cosine", True)
-    assert int(by_hand[3]) == 0 and all(torch.equal(_bits(a), _bits(b)) for a, b in zip(by_hand[:3], want[:3]))
+    assert int(by_hand[3]) == 0 and all(torch.equal(C.bits(a), C.bits(b)) for a, b in zip(by_hand[:3], want[:3]))
     for b in range(B):
         assert list(recs[f"U{100 + b}"]) == [f"N{int(i)}" for i in by_hand[0][b]]
         assert list(recs[f"U{100 + b}"].values()) == [float(s) for s in by_hand[1][b]]
@@ -339,10 +327,9 @@ def test_recommend_users_diversifies_an_nrms_cache():
 def test_manner_reranks_against_either_sub_model(tmp_path):
     from newsreclib_amd import ops
     from newsreclib_amd.evaluation import MannerVectorCache, recommend_users
-    from tests.test_gpu_manner import _ensemble, _modules, _table_and_impressions
-    cr, ac, asent = _modules(tmp_path)
-    table, imps = _table_and_impressions()
-    cache = MannerVectorCache(_ensemble(cr, ac, asent), table)
+    cr, ac, asent = builders.manner_modules(tmp_path)
+    table, imps = builders.manner_table_and_impressions()
+    cache = MannerVectorCache(builders.manner_ensemble(cr, ac, asent), table)
     lists = [i["hist"] for i in imps]
     hs, hist = torch.tensor([len(x) for x in lists]), torch.cat(lists)
     B, k, pool = len(imps), 5, 16
@@ -351,7 +338,7 @@ def test_manner_reranks_against_either_sub_model(tmp_path):
     for s in (0, 1):
         got = cache.rerank_diverse(idx, score, k, 0.5, submodel=s)
         want = ops.mmr_rerank(idx, score, cache.vectors[s], k, 0.5)
-        assert int(got[3]) == 0 and all(torch.equal(_bits(a), _bits(b)) for a, b in zip(got[:3], want[:3]))
+        assert int(got[3]) == 0 and all(torch.equal(C.bits(a), C.bits(b)) for a, b in zip(got[:3], want[:3]))
     first = cache.rerank_diverse(idx, score, k, 0.5)
     users = [{"hist": lists[b], "user_id": 100 + b} for b in range(B)]
     recs = recommend_users(cache, users, k, batch_size=B + 3, diversify=(pool, 0.5))
@@ -360,8 +347,7 @@ def test_manner_reranks_against_either_sub_model(tmp_path):
 
 def test_a_miner_cache_is_diversified_like_any_other(tmp_path):
     from newsreclib_amd.evaluation import recommend_users
-    from tests.test_gpu_topk_interests import _miner_cache
-    mod, cfg, cache, hist, hs = _miner_cache("miner_tiny_no_bias", "max", tmp_path)
+    mod, cfg, cache, hist, hs = builders.miner_cache("miner_tiny_no_bias", "max", tmp_path)
     V, B = cache.table.num_news, int(hs.numel())
     pool = min(12, V - int(hs.max()))
     k = min(5, pool)

@@ -1,13 +1,14 @@
 """Full-catalogue top-k recommendation (``nrl_topk_scores`` / ``ops.topk_scores`` / ``NewsVectorCache.recommend``).
 
-Expected values are computed here on the CPU in float64: ``s = U64 @ T64.T``, ineligible and excluded positions at ``-inf``,
-``torch.sort(-s, stable=True)`` = score descending with equal scores by ascending row.  Integer-valued vectors in [-4, 4] make
-every fp32 dot product exact in any order (|s| <= 16 * 768 < 2^24), so those cases compare with ``torch.equal``.  Real-valued
-cases use ``bound(u, v) = D * 2^-23 * sum_i |u_i| |v_i|``, the worst-case error of an fp32 dot product of length D (derived, not
-measured)."""
-import numpy as np
+Expected values are computed on the CPU in float64: ``s = U64 @ T64.T`` under the population and the order of
+``tests/catalogue_ref.py`` (score descending, equal scores by ascending row).  Integer-valued vectors in [-4, 4] make every fp32
+dot product exact in any order (|s| <= 16 * 768 < 2^24), so those cases compare with ``torch.equal``.  Real-valued cases use
+``catalogue_ref.dot_bound``, the worst-case error of an fp32 dot product of length D (derived, not measured)."""
 import pytest
 import torch
+
+from tests import builders
+from tests import catalogue_ref as C
 
 pytestmark = pytest.mark.gpu
 
@@ -23,52 +24,16 @@ def engine(request):
     _lib.set_gemm_engine(prev)
 
 
-def _int_vectors(seed, B, V, D):
-    g = torch.Generator().manual_seed(seed)
-    return (torch.randint(-4, 5, (B, D), generator=g).float(), torch.randint(-4, 5, (V, D), generator=g).float())
-
-
-def _ragged(lists):
-    off = torch.tensor([0] + [len(x) for x in lists]).cumsum(0)
-    idx = torch.tensor([v for x in lists for v in x], dtype=torch.int64)
-    return idx, off
-
-
-def _masked_scores(U, T, excl=None, eligible=None):
-    """(B, V) float64 scores with the positions that may not be returned at -inf."""
-    s = U.double() @ T.double().T
-    V = T.shape[0]
-    if eligible is not None:
-        s[:, ~eligible.bool()] = float("-inf")
-    if excl is not None:
-        for b, rows in enumerate(excl):
-            rows = [r for r in rows if 0 <= r < V]
-            if rows:
-                s[b, torch.tensor(rows)] = float("-inf")
-    return s
-
-
 def _reference(U, T, k, excl=None, eligible=None):
     """idx (B, k) int64 and score (B, k) float32 of the exact cases; -1 / -inf where fewer than k rows qualify."""
-    s = _masked_scores(U, T, excl, eligible)
-    B, V = s.shape
-    neg, order = torch.sort(-s, dim=1, stable=True) if V else (s, torch.empty((B, 0), dtype=torch.int64))
-    idx = torch.full((B, k), -1, dtype=torch.int64)
-    score = torch.full((B, k), float("-inf"), dtype=torch.float32)
-    n = min(k, V)
-    if n:
-        val = -neg[:, :n]
-        keep = val > float("-inf")
-        idx[:, :n] = torch.where(keep, order[:, :n], torch.full_like(order[:, :n], -1))
-        score[:, :n] = torch.where(keep, val, torch.full_like(val, float("-inf"))).float()
-    return idx, score
+    return C.expected_topk(U.double() @ T.double().T, k, excl, eligible)
 
 
 def _run(U, T, k, excl=None, eligible=None, slices=0, off=None):
     from newsreclib_amd import ops
     ei = eo = None
     if excl is not None:
-        ei, eo = _ragged(excl)
+        ei, eo = C.ragged(excl)
         ei, eo = ei.cuda(), (off if off is not None else eo).cuda()
     idx, score, status = ops.topk_scores(U.cuda(), T.cuda(), k, ei, eo, eligible.cuda() if eligible is not None else None, slices)
     return idx.cpu(), score.cpu(), int(status)
@@ -82,7 +47,7 @@ _EXACT = [(130, 1000, 300, 128, 1), (130, 1000, 300, 128, 2), (130, 1000, 300, 1
 
 @pytest.mark.parametrize("B,V,D,k,slices", _EXACT)
 def test_exact_with_ties(B, V, D, k, slices):
-    U, T = _int_vectors(B * 7 + V + D + k, B, V, D)
+    U, T = C.int_vectors(B * 7 + V + D + k, B, V, D)
     idx, score, status = _run(U, T, k, slices=slices)
     want_idx, want_score = _reference(U, T, k)
     assert status == 0
@@ -102,7 +67,7 @@ def test_all_equal_scores_return_the_first_rows(slices):
 # ---- 2. exclusion and eligibility --------------------------------------------------------------------------------------------------
 def _excl_case():
     B, V, D, k = 5, 40, 12, 16
-    U, T = _int_vectors(91, B, V, D)
+    U, T = C.int_vectors(91, B, V, D)
     eligible = torch.ones(V, dtype=torch.uint8)
     eligible[[0, 7, 8, 31]] = 0
     first = _reference(U, T, k, eligible=eligible)[0][:, 0]           # every user's would-be first place
@@ -127,7 +92,7 @@ def test_exclusion_and_eligibility(slices):
 def test_exclusion_list_longer_than_the_cached_part():
     """Lists beyond the 64 entries a workgroup caches are read from global memory: 150 entries, several table tiles."""
     B, V, D, k = 3, 700, 8, 20
-    U, T = _int_vectors(5, B, V, D)
+    U, T = C.int_vectors(5, B, V, D)
     g = torch.Generator().manual_seed(3)
     excl = [torch.randperm(V, generator=g)[:150].tolist(), [], _reference(U, T, 150)[0][2].tolist()]
     idx, score, status = _run(U, T, k, excl, slices=3)
@@ -149,7 +114,7 @@ def test_status_bad_exclusion_index_is_ignored():
 
 def test_status_decreasing_offsets_blank_that_user_alone():
     B, V, D, k = 4, 40, 12, 6
-    U, T = _int_vectors(17, B, V, D)
+    U, T = C.int_vectors(17, B, V, D)
     flat = list(range(12))
     off = torch.tensor([0, 5, 3, 8, 12])                    # user 1 runs backwards
     from newsreclib_amd import ops
@@ -164,7 +129,7 @@ def test_status_decreasing_offsets_blank_that_user_alone():
 
 def test_status_offsets_beyond_the_list():
     B, V, D, k = 3, 40, 12, 6
-    U, T = _int_vectors(18, B, V, D)
+    U, T = C.int_vectors(18, B, V, D)
     from newsreclib_amd import ops
     idx, score, status = ops.topk_scores(U.cuda(), T.cuda(), k, torch.arange(6).cuda(), torch.tensor([0, 2, 9, 6]).cuda())
     assert int(status) == E_OFFSETS
@@ -175,7 +140,7 @@ def test_status_offsets_beyond_the_list():
 
 def test_status_nan_row_is_left_out():
     B, V, D, k = 5, 300, 12, 9
-    U, T = _int_vectors(23, B, V, D)
+    U, T = C.int_vectors(23, B, V, D)
     clean_idx, clean_score, status = _run(U, T, k, slices=2)
     assert status == 0
     nan_row = int(clean_idx[0, 0])                          # a row that would be returned
@@ -191,33 +156,6 @@ def test_status_nan_row_is_left_out():
 
 
 # ---- 4. real values against float64 -------------------------------------------------------------------------------------------------
-def _bound(U, T):
-    return U.shape[1] * 2.0 ** -23 * (U.double().abs() @ T.double().abs().T)
-
-
-def _check_real(U, T, idx, score, excl, k):
-    s = _masked_scores(U, T, excl)
-    raw = U.double() @ T.double().T
-    bound = _bound(U, T)
-    B, V = raw.shape
-    for b in range(B):
-        rows = idx[b]
-        assert bool((rows >= 0).all())
-        got = score[b].double()
-        err = (got - raw[b, rows]).abs()
-        print(f"user {b}: max |score - float64| = {float(err.max()):.3e}, bound >= {float(bound[b, rows].min()):.3e}")
-        assert bool((err <= bound[b, rows]).all())
-        assert bool((got[1:] <= got[:-1]).all())
-        tie = got[1:] == got[:-1]
-        assert bool((rows[1:][tie] > rows[:-1][tie]).all())
-        assert len(set(rows.tolist())) == k and not (set(rows.tolist()) & set(excl[b]))
-        rest = torch.ones(V, dtype=torch.bool)
-        rest[rows] = False
-        rest &= s[b] > float("-inf")
-        floor = raw[b, rows].min()
-        assert bool((s[b][rest] <= floor + 2 * bound[b][rest]).all())
-
-
 def test_real_values_against_float64():
     B, V, D, k = 37, 5000, 300, 10
     g = torch.Generator().manual_seed(12)
@@ -225,7 +163,8 @@ def test_real_values_against_float64():
     excl = [torch.randint(0, V, (int(n),), generator=g).tolist() for n in torch.randint(0, 51, (B,), generator=g)]
     idx, score, status = _run(U, T, k, excl)
     assert status == 0
-    _check_real(U, T, idx, score, excl, k)
+    raw = U.double() @ T.double().T
+    C.check_floor(idx, score, raw, C.dot_bound(U, T), C.population(raw, excl)[0], k)
 
 
 # ---- 5. invariance and determinism ---------------------------------------------------------------------------------------------------
@@ -274,24 +213,16 @@ def test_peak_memory_is_far_below_the_score_matrix():
 
 
 # ---- 7. no read-back ---------------------------------------------------------------------------------------------------------------------
-def _sync_debug_honoured():
-    try:
-        float(torch.ones(1, device="cuda").sum())
-    except RuntimeError:
-        return True
-    return False
-
-
 def test_topk_scores_does_not_synchronise_with_the_host():
     from newsreclib_amd import ops
-    U, T = _int_vectors(3, 5, 200, 12)
+    U, T = C.int_vectors(3, 5, 200, 12)
     U, T = U.cuda(), T.cuda()
-    ei, eo = _ragged([[1, 2], [], [5], [7, 7], []])
+    ei, eo = C.ragged([[1, 2], [], [5], [7, 7], []])
     ei, eo, elig = ei.cuda(), eo.cuda(), torch.ones(200, dtype=torch.uint8).cuda()
     torch.cuda.synchronize()
     torch.cuda.set_sync_debug_mode("error")
     try:
-        if not _sync_debug_honoured():
+        if not C.sync_debug_honoured():
             pytest.skip("this torch build does not raise on synchronising calls under set_sync_debug_mode('error')")
         idx, score, status = ops.topk_scores(U, T, 4, ei, eo, elig)
     finally:
@@ -300,65 +231,6 @@ def test_topk_scores_does_not_synchronise_with_the_host():
 
 
 # ---- 8. wiring -----------------------------------------------------------------------------------------------------------------------------
-def _tiny(model, late_fusion=False, tmp_path=None, n_news=None):
-    """(module in eval mode, table attributes or a DeviceNewsTable) from the synthetic builders of the existing GPU tests."""
-    from tests import helpers as H
-    from tests.test_gpu_eval import _table
-    rng = np.random.default_rng(11)
-    n_news, manner_news, vocab = n_news or 50, n_news or 40, 120      # (the MANNeR table builder's own default is 40)
-    if model == "sentirec":
-        from oracle import sentirec_oracle as SO
-        g = H.load_golden("sentirec_tiny_eval")
-        params = SO.make_sentirec_params(int(g["cfg_vocab"]), int(g["cfg_n_sent"]), seed=int(g["cfg_param_seed"]))
-        attrs = _table(rng, n_news, int(g["cfg_vocab"]), L=12, n_categ=7)
-        return H.build_sentirec_module(g, params).eval(), {"title": attrs["title"]}
-    if model == "manner_cr":
-        from newsreclib_amd.manner_cr_module import CRModule
-        from tests.test_gpu_manner import _table_and_impressions
-        from tests.test_manner_host import cr_kwargs, entity_table
-        torch.manual_seed(11)
-        mod = CRModule(**cr_kwargs(H.make_tiny_roberta(str(tmp_path)), late_fusion=late_fusion),
-                       pretrained_entity_embeddings=entity_table(1)).to("cuda").eval()
-        return mod, _table_and_impressions(manner_news)[0]
-    attrs = _table(rng, n_news, vocab, L=12, n_categ=7)
-    attrs["abstract"] = _table(rng, n_news, vocab, L=20)["title"]
-    if model == "nrms":
-        from oracle import nrms_oracle as O
-        mod = H.build_module(O.make_params(vocab, seed=8), late_fusion=late_fusion)
-        attrs = {k: v for k, v in attrs.items() if k != "abstract"}
-    elif model in ("lstur_ini", "lstur_con"):
-        from oracle.lstur_oracle import make_lstur_params
-        cfg = dict(vocab=vocab, n_categ=7, n_users=9, D=48, F=48, W=3, Q=32, categ_dim=16, text_attrs=("title", "abstract"),
-                   text_order=("title", "abstract"), method=model[-3:], p_drop=0.2, p_mask=0.5)
-        mod = H.build_lstur_module(cfg, make_lstur_params(vocab, 7, 9, 48, 48, 3, 32, 16, method=model[-3:], seed=5))
-    elif model == "naml":
-        from oracle.naml_oracle import make_naml_params
-        cfg = dict(vocab=vocab, n_categ=7, D=48, F=48, W=3, Q=32, categ_dim=16, text_attrs=("title", "abstract"),
-                   text_order=("title", "abstract"), p_drop=0.2)
-        mod = H.build_naml_module(cfg, make_naml_params(vocab, 7, 48, 48, 3, 32, 16, seed=5))
-    elif model == "tanr":
-        from oracle.tanr_oracle import make_tanr_params
-        cfg = dict(vocab=vocab, n_categ=7, D=48, F=48, W=3, Q=32, p_drop=0.2, coef=0.2)
-        mod = H.build_tanr_module(cfg, make_tanr_params(vocab, 7, 48, 48, 3, 32, seed=5))
-    elif model == "cen":
-        from oracle.cen_news_rec_oracle import make_cen_news_rec_params
-        cfg = dict(vocab=vocab, D=40, F=48, W=3, Q=32, heads=3, recent=3, p_drop=0.2, late_fusion=False)
-        mod = H.build_cen_module(cfg, make_cen_news_rec_params(vocab, 40, 48, 3, 32, seed=5))
-    elif model == "mins":
-        from oracle.mins_oracle import make_mins_params
-        cfg = dict(vocab=vocab, n_categ=7, D=48, Q=32, categ_dim=16, heads=3, channels=4,
-                   text_attrs=("title", "abstract"), text_order=("title", "abstract"), p_drop=0.2)
-        mod = H.build_mins_module(cfg, make_mins_params(vocab, 7, 48, 32, 16, 4, seed=5))
-    else:
-        raise AssertionError(model)
-    return mod.eval(), attrs
-
-
-def _hist_batch(n_news, B=6, seed=3, full=False):
-    rng = np.random.default_rng(seed)
-    sizes = np.full(B, 8) if full else rng.integers(1, 9, B)      # full: every history as long as the longest
-    hist = [torch.from_numpy(rng.choice(np.arange(1, n_news), int(n), replace=False)) for n in sizes]
-    return hist, torch.cat(hist), torch.tensor([len(h) for h in hist]), torch.arange(B) % 7
 
 
 @pytest.mark.parametrize("model,late", [("nrms", False), ("nrms", True), ("lstur_ini", False), ("lstur_con", False), ("naml", False),
@@ -370,14 +242,14 @@ def test_user_vectors_is_the_first_half_of_score_news_vectors(model, late, tmp_p
     from newsreclib_amd import ops
     from newsreclib_amd.dense_batch import dense_rows
     from newsreclib_amd.evaluation import DeviceNewsTable, NewsVectorCache
-    mod, table = _tiny(model, late, tmp_path)
+    mod, table = builders.tiny(model, late, tmp_path)
     assert type(mod).dot_product_scorer is True
     table = table if isinstance(table, DeviceNewsTable) else DeviceNewsTable(table)
     cache = NewsVectorCache(mod, table, chunk=32)
     vec = cache.build()
     V = table.num_news
     for full in (False, True):
-        _, hist, hs, uidx = _hist_batch(V, full=full)
+        _, hist, hs, uidx = builders.hist_batch(V, full=full)
         cand, cs = torch.arange(V).repeat(6), torch.full((6,), V)
         meta = cache._meta(hs, cs, None, uidx, None)
         hv = ops.embedding_gather(vec, hist.cuda().reshape(-1, 1)).reshape(-1, vec.shape[1])
@@ -394,11 +266,11 @@ def test_user_vectors_is_the_first_half_of_score_news_vectors(model, late, tmp_p
 @pytest.mark.parametrize("model", ["nrms", "lstur_ini"])
 def test_recommend_against_the_cache_scores(model):
     from newsreclib_amd.evaluation import DeviceNewsTable, NewsVectorCache, recommend_users
-    mod, attrs = _tiny(model)
+    mod, attrs = builders.tiny(model)
     mod.train()
     cache = NewsVectorCache(mod, DeviceNewsTable(attrs), chunk=32)
     V, B, k = 50, 6, 10
-    lists, hist, hs, uidx = _hist_batch(V)
+    lists, hist, hs, uidx = builders.hist_batch(V)
     idx, score, status = cache.recommend(hist.cuda(), hs, k, user_idx=uidx)
     assert mod.training                                          # the mode is restored
     assert int(status) == 0 and idx.shape == (B, k)
@@ -413,7 +285,7 @@ def test_recommend_against_the_cache_scores(model):
         user = mod.user_vectors(ops.embedding_gather(vec, hist.cuda().reshape(-1, 1)).reshape(-1, vec.shape[1]),
                                 cache._user_meta(hs, uidx))
         mod.train()
-    bound = _bound(user.cpu(), vec.cpu())
+    bound = C.dot_bound(user.cpu(), vec.cpu())
     for b in range(B):
         rows = idx[b]
         assert bool((rows >= 0).all()) and not (set(rows.tolist()) & set(lists[b].tolist()))
@@ -437,15 +309,15 @@ def test_recommend_against_the_cache_scores(model):
 
 def test_recommend_does_not_synchronise_with_the_host():
     from newsreclib_amd.evaluation import DeviceNewsTable, NewsVectorCache
-    mod, attrs = _tiny("nrms")
+    mod, attrs = builders.tiny("nrms")
     cache = NewsVectorCache(mod, DeviceNewsTable(attrs), chunk=32)
     cache.build()
-    _, hist, hs, _ = _hist_batch(50)
+    _, hist, hs, _ = builders.hist_batch(50)
     hist = hist.cuda()                                           # the sizes stay on the host, as evaluate_impressions builds them
     torch.cuda.synchronize()
     torch.cuda.set_sync_debug_mode("error")
     try:
-        if not _sync_debug_honoured():
+        if not C.sync_debug_honoured():
             pytest.skip("this torch build does not raise on synchronising calls under set_sync_debug_mode('error')")
         idx, score, status = cache.recommend(hist, hs, 5)
     finally:

@@ -1,18 +1,20 @@
 """Class-biased full-catalogue top-k and rank (``nrl_topk_bias_scores`` / ``nrl_topk_bias_scores_capped`` /
 ``nrl_catalogue_bias_ranks``, their ``ops`` wrappers, ``NewsVectorCache.recommend_biased`` / ``rank_clicks_biased``).
 
-Expected values come from the float64 restatement on the CPU (``tests/topk_bias_ref.py``).  The exact cases use entries that are
-multiples of 1/8 in [-2, 2] (vectors) and [-4, 4] (bias): every product is a multiple of 1/64, every partial sum stays below
-2^11 and so has at most 17 significant bits, and the one add of the bias is exact too -- fp32 and float64 must agree in rows
-AND score bits.  The real-valued cases compare against ``ops.topk_scores`` of the same call plus ONE torch fp32 add."""
+Expected values come from the float64 scores of ``tests/topk_bias_ref.py`` under the contract of ``tests/catalogue_ref.py``.
+The exact cases use entries that are multiples of 1/8 in [-2, 2] (vectors) and [-4, 4] (bias): every product is a multiple of
+1/64, every partial sum stays below 2^11 and so has at most 17 significant bits, and the one add of the bias is exact too --
+fp32 and float64 must agree in rows AND score bits.  The real-valued cases compare against ``ops.topk_scores`` of the same call plus ONE torch fp32 add."""
 import functools
 
 import numpy as np
 import pytest
 import torch
 
+from tests import builders
+from tests import catalogue_ref as C
 from tests import topk_bias_ref as R
-from tests.test_gpu_topk import _ragged, _sync_debug_honoured
+from tests import topk_capped_ref
 
 pytestmark = pytest.mark.gpu
 
@@ -29,18 +31,6 @@ def engine(request):
     _lib.set_gemm_engine(prev)
 
 
-def _bits(x):
-    return x.contiguous().view(torch.int32)
-
-
-def _same(got, want):
-    """a GPU result against a numpy expectation: equal values, and for floats equal bits"""
-    got = got.cpu()
-    want = torch.from_numpy(np.ascontiguousarray(want))
-    assert got.shape == want.shape and got.dtype == want.dtype, (got.shape, want.shape, got.dtype, want.dtype)
-    return torch.equal(_bits(got), _bits(want)) if got.dtype == torch.float32 else torch.equal(got, want)
-
-
 def _eighths(rng, shape, top):
     return (rng.integers(-8 * top, 8 * top + 1, shape) / 8.0).astype(np.float32)
 
@@ -48,7 +38,7 @@ def _eighths(rng, shape, top):
 def _masks(excl, eligible):
     ei = eo = None
     if excl is not None:
-        ei, eo = _ragged(excl)
+        ei, eo = C.ragged(excl)
         ei, eo = ei.cuda(), eo.cuda()
     return ei, eo, torch.from_numpy(eligible).cuda() if eligible is not None else None
 
@@ -67,7 +57,7 @@ def _topk(U, T, bias, cls, k, excl=None, eligible=None, slices=0, cap=None):
 def _ranks(U, T, bias, cls, targets, excl=None, eligible=None, slices=0):
     from newsreclib_amd import ops
     args = [torch.from_numpy(x).cuda() for x in (U, T, bias, cls)]
-    ti, to = _ragged(targets)
+    ti, to = C.ragged(targets)
     rank, score, ranked, status = ops.catalogue_bias_ranks(*args, ti.cuda(), to.cuda(), *_masks(excl, eligible), slices)
     return rank, score, ranked, int(status)
 
@@ -95,29 +85,29 @@ def _sweep_case(B, V, D, S, k):
     targets = [rng.integers(0, V, int(rng.integers(0, 4))).tolist() for _ in range(B)]
     targets[0] = targets[0] + excl[0][:1]                                      # a target in the history
     s, flags = R.scores(U, T, bias, cls)
-    pop, nan = R.population(s, excl, eligible)
-    assert flags == 0 and nan == 0
+    pop, nan = C.population(s, excl, eligible)
+    assert flags == 0 and not nan
     kc, m = min(k, 64), 2
-    return (U, T, bias, cls, cap_cls, excl, eligible, targets), R.topk(s, pop, k), R.ranks(s, pop, targets), \
-        R.capped(s, pop, cap_cls, kc, m), R.topk(s, pop, kc)
+    return (U, T, bias, cls, cap_cls, excl, eligible, targets), C.topk(s, pop, k), C.ranks(s, pop, targets), \
+        topk_capped_ref.reference(s, pop, torch.from_numpy(cap_cls), kc, m), C.topk(s, pop, kc)
 
 
 @pytest.mark.parametrize("B,V,D,S,k,slices", _SWEEP)
 def test_edge_sweep_rows_and_score_bits(B, V, D, S, k, slices):
     (U, T, bias, cls, cap_cls, excl, eligible, targets), want, want_rank, want_cap, want_kc = _sweep_case(B, V, D, S, k)
     idx, score, status = _topk(U, T, bias, cls, k, excl, eligible, slices)
-    assert status == 0 and _same(idx, want[0]) and _same(score, want[1])
+    assert status == 0 and C.same(idx, want[0]) and C.same(score, want[1])
     if excl[0]:
         assert len(excl[0]) > 64 or V <= 65
     # the rank entry: ranks, score bits and populations
     rank, tscore, ranked, status = _ranks(U, T, bias, cls, targets, excl, eligible, slices)
-    assert status == 0 and _same(rank, want_rank[0]) and _same(tscore, want_rank[1]) and _same(ranked, want_rank[2])
+    assert status == 0 and C.same(rank, want_rank[0]) and C.same(tscore, want_rank[1]) and C.same(ranked, want_rank[2])
     # the capped entry, its classes another array than the bias's: the greedy definition; m >= k: the uncapped new entry
     kc = min(k, 64)
     idx, score, status = _topk(U, T, bias, cls, kc, excl, eligible, slices, cap=(cap_cls, 2))
-    assert status == 0 and _same(idx, want_cap[0]) and _same(score, want_cap[1])
+    assert status == 0 and C.same(idx, want_cap[0]) and C.same(score, want_cap[1])
     idx, score, status = _topk(U, T, bias, cls, kc, excl, eligible, slices, cap=(cap_cls, kc))
-    assert status == 0 and _same(idx, want_kc[0]) and _same(score, want_kc[1])
+    assert status == 0 and C.same(idx, want_kc[0]) and C.same(score, want_kc[1])
 
 
 # ---- 2. ties made by the bias --------------------------------------------------------------------------------------------------------------
@@ -154,8 +144,8 @@ def _effect_case():
 
 def _expect(U, T, bias, cls, k, **kw):
     s, flags = R.scores(U, T, bias, cls)
-    pop, nan = R.population(s, **kw)
-    return R.topk(s, pop, k), flags | nan, s, pop
+    pop, nan = C.population(s, **kw)
+    return C.topk(s, pop, k), flags | (E_NAN if nan else 0), s, pop
 
 
 @pytest.mark.parametrize("slices", [0, 3])
@@ -165,7 +155,7 @@ def test_a_class_bias_lifts_a_row_of_the_last_tile_to_the_top(slices):
     bias[:, 18] = 512.0
     idx, score, status = _topk(U, T, bias, cls, 5, slices=slices)
     want, flags, _, _ = _expect(U, T, bias, cls, 5)
-    assert status == flags == 0 and _same(idx, want[0]) and _same(score, want[1])
+    assert status == flags == 0 and C.same(idx, want[0]) and C.same(score, want[1])
     assert idx[:, 0].tolist() == [999] * 5 and bool((score[:, 0] > 400).all())
 
 
@@ -175,7 +165,7 @@ def test_a_large_negative_bias_empties_a_class_from_every_list():
     bias[:, 3] = -1e30
     idx, score, status = _topk(U, T, bias, cls, 128, slices=2)
     want, flags, _, _ = _expect(U, T, bias, cls, 128)
-    assert status == flags == 0 and _same(idx, want[0]) and _same(score, want[1])
+    assert status == flags == 0 and C.same(idx, want[0]) and C.same(score, want[1])
     assert int((cls == 3).sum()) > 10 and not bool((torch.from_numpy(cls)[idx.cpu()] == 3).any())
 
 
@@ -185,15 +175,15 @@ def test_a_nan_bias_drops_that_class_for_that_user_only():
     bias[2, 3] = np.nan
     idx, score, status = _topk(U, T, bias, cls, 128, slices=2)
     want, flags, s, pop = _expect(U, T, bias, cls, 128)
-    assert status == flags == E_NAN and _same(idx, want[0]) and _same(score, want[1])
+    assert status == flags == E_NAN and C.same(idx, want[0]) and C.same(score, want[1])
     per_user = (torch.from_numpy(cls)[idx.cpu()] == 3).sum(1).tolist()
     assert per_user[2] == 0 and all(n > 0 for b, n in enumerate(per_user) if b != 2)
     # the rank entry drops the same rows from the population and gives a target among them rank 0
     gone = int(np.nonzero(cls == 3)[0][0])
     targets = [[gone], [], [gone, 5], [], []]
     rank, tscore, ranked, status = _ranks(U, T, bias, cls, targets, slices=2)
-    want_rank = R.ranks(s, pop, targets)
-    assert status == E_NAN and _same(rank, want_rank[0]) and _same(tscore, want_rank[1]) and _same(ranked, want_rank[2])
+    want_rank = C.ranks(s, pop, targets)
+    assert status == E_NAN and C.same(rank, want_rank[0]) and C.same(tscore, want_rank[1]) and C.same(ranked, want_rank[2])
     assert rank.tolist()[1] == 0 and rank.tolist()[0] > 0 and ranked.tolist()[2] == 1000 - int((cls == 3).sum())
 
 
@@ -206,11 +196,11 @@ def test_class_ids_outside_the_bias_are_scored_with_zero_and_flagged(slices):
     cls[64] = -2 ** 31
     idx, score, status = _topk(U, T, bias, cls, 128, slices=slices)
     want, flags, s, pop = _expect(U, T, bias, cls, 128)
-    assert status == flags == E_CLASS and _same(idx, want[0]) and _same(score, want[1])
+    assert status == flags == E_CLASS and C.same(idx, want[0]) and C.same(score, want[1])
     targets = [[0, 5], [700], [], [64], [998, 1]]
     rank, tscore, ranked, status = _ranks(U, T, bias, cls, targets, slices=slices)
-    want_rank = R.ranks(s, pop, targets)
-    assert status == E_CLASS and _same(rank, want_rank[0]) and _same(tscore, want_rank[1]) and _same(ranked, want_rank[2])
+    want_rank = C.ranks(s, pop, targets)
+    assert status == E_CLASS and C.same(rank, want_rank[0]) and C.same(tscore, want_rank[1]) and C.same(ranked, want_rank[2])
     plain = (U.astype(np.float64) @ T.astype(np.float64).T)[0, 0]
     assert float(tscore[0]) == plain                        # bias 0: the dot product itself
 
@@ -227,7 +217,7 @@ def test_a_zero_bias_returns_topk_scores(B, V, D, S, k, slices):
     from newsreclib_amd import ops
     U, T, bias, cls = _real(B + V, B, V, D, S)
     T[5] = T[9]                                              # (a tie between real values)
-    ei, eo = _ragged([[5, 7]] + [[] for _ in range(B - 1)])
+    ei, eo = C.ragged([[5, 7]] + [[] for _ in range(B - 1)])
     got = ops.topk_bias_scores(U, T, torch.zeros_like(bias), cls, k, ei.cuda(), eo.cuda(), slices=slices)
     want = ops.topk_scores(U, T, k, ei.cuda(), eo.cuda(), slices=slices)
     assert int(got[2]) == int(want[2]) == 0 and torch.equal(got[0], want[0]) and bool((got[1] == want[1]).all())
@@ -247,11 +237,11 @@ def test_every_score_is_the_dot_product_of_topk_scores_plus_one_fp32_add(B, V, D
     total = dots + bias[:, cls.long()]                       # ONE fp32 add per element
     want_score, want_idx = torch.sort(total, dim=1, descending=True, stable=True)
     idx, score, status = ops.topk_bias_scores(U, T, bias, cls, V)
-    assert int(status) == 0 and torch.equal(idx, want_idx) and torch.equal(_bits(score), _bits(want_score + 0.0))
+    assert int(status) == 0 and torch.equal(idx, want_idx) and torch.equal(C.bits(score), C.bits(want_score + 0.0))
     tgt = torch.arange(V, dtype=torch.int64).cuda().repeat(B)[:32 * B].reshape(B, 32)
     rank, tscore, ranked, status = ops.catalogue_bias_ranks(U, T, bias, cls, tgt.reshape(-1), torch.arange(B + 1).cuda() * 32)
     assert int(status) == 0 and bool((ranked == V).all())
-    assert torch.equal(_bits(tscore.reshape(B, 32)), _bits(total.gather(1, tgt) + 0.0))
+    assert torch.equal(C.bits(tscore.reshape(B, 32)), C.bits(total.gather(1, tgt) + 0.0))
     assert torch.equal(idx.gather(1, rank.reshape(B, 32).long() - 1), tgt)
 
 
@@ -265,8 +255,8 @@ def test_invariance_under_batch_slicing_and_engine():
     assert int(base[2]) == 0 and int(base_rank[3]) == 0
 
     def same(got, got_rank, sel=slice(None), tsel=slice(None)):
-        return torch.equal(got[0], base[0][sel]) and torch.equal(_bits(got[1]), _bits(base[1][sel])) and \
-            torch.equal(got_rank[0], base_rank[0][tsel]) and torch.equal(_bits(got_rank[1]), _bits(base_rank[1][tsel])) and \
+        return torch.equal(got[0], base[0][sel]) and torch.equal(C.bits(got[1]), C.bits(base[1][sel])) and \
+            torch.equal(got_rank[0], base_rank[0][tsel]) and torch.equal(C.bits(got_rank[1]), C.bits(base_rank[1][tsel])) and \
             torch.equal(got_rank[2], base_rank[2][sel])
 
     for slices in (1, 2, 7):
@@ -286,7 +276,7 @@ def test_invariance_under_batch_slicing_and_engine():
     assert same(ops.topk_bias_scores(U, T, bias, cls.long(), k), base_rank)      # int64 classes are the same classes
     # a score's bits do not depend on k either
     wide = ops.topk_bias_scores(U, T, bias, cls, 128)
-    assert torch.equal(wide[0][:, :k], base[0]) and torch.equal(_bits(wide[1][:, :k]), _bits(base[1]))
+    assert torch.equal(wide[0][:, :k], base[0]) and torch.equal(C.bits(wide[1][:, :k]), C.bits(base[1]))
 
 
 # ---- 5. the rank entry against the list ------------------------------------------------------------------------------------------------------
@@ -295,7 +285,7 @@ def test_a_rank_of_at_most_k_is_the_slot_of_the_list():
     B, V, D, S, k = 70, 700, 300, 19, 16
     U, T, bias, cls = _real(5, B, V, D, S)
     hist = [[(b * 13 + j) % V for j in range(b % 5)] for b in range(B)]
-    ei, eo = _ragged(hist)
+    ei, eo = C.ragged(hist)
     elig = torch.ones(V, dtype=torch.uint8)
     elig[0] = 0
     tail = (ei.cuda(), eo.cuda(), elig.cuda())
@@ -305,7 +295,7 @@ def test_a_rank_of_at_most_k_is_the_slot_of_the_list():
     g = torch.Generator().manual_seed(8)
     clicks = [[int(idx_c[b, 0]), int(idx_c[b, k - 1])] + torch.randint(0, V, (3,), generator=g).tolist() + hist[b][:1] + [0, V, -1]
               for b in range(B)]
-    ti, to = _ragged(clicks)
+    ti, to = C.ragged(clicks)
     rank, tscore, ranked, status = ops.catalogue_bias_ranks(U, T, bias, cls, ti.cuda(), to.cuda(), *tail)
     assert int(status) == E_TARGET_ROW                       # the targets V and -1, as for catalogue_ranks
     rank, tscore, ranked = rank.cpu(), tscore.cpu(), ranked.cpu()
@@ -317,7 +307,7 @@ def test_a_rank_of_at_most_k_is_the_slot_of_the_list():
             r = int(rank[at])
             assert (1 <= r <= k) == bool((idx_c[b] == c).any()), (b, c, r)
             if 1 <= r <= k:
-                assert int(idx_c[b, r - 1]) == c and torch.equal(_bits(tscore[at]), _bits(score_c[b, r - 1]))
+                assert int(idx_c[b, r - 1]) == c and torch.equal(C.bits(tscore[at]), C.bits(score_c[b, r - 1]))
             if c in hist[b] or c == 0 or not 0 <= c < V:
                 assert r == 0 and float(tscore[at]) == NEG_INF
             at += 1
@@ -326,18 +316,17 @@ def test_a_rank_of_at_most_k_is_the_slot_of_the_list():
 # ---- 6. the capped entry -----------------------------------------------------------------------------------------------------------------------
 def test_a_cap_of_k_or_more_returns_the_bits_of_the_uncapped_entry_and_a_smaller_one_walks_its_list():
     from newsreclib_amd import ops
-    from tests import topk_capped_ref
     B, V, D, S, k = 66, 128, 300, 4, 8
     U, T, bias, cls = _real(12, B, V, D, S)
     cap_cls = (torch.arange(V) % 5).to(torch.int32).cuda()   # the cap goes by another array than the bias
     for m in (k, 2 ** 31 - 1):
         got, want = ops.topk_bias_scores_capped(U, T, bias, cls, k, cap_cls, m), ops.topk_bias_scores(U, T, bias, cls, k)
-        assert int(got[2]) == 0 and torch.equal(got[0], want[0]) and torch.equal(_bits(got[1]), _bits(want[1]))
+        assert int(got[2]) == 0 and torch.equal(got[0], want[0]) and torch.equal(C.bits(got[1]), C.bits(want[1]))
     idx, score, status = ops.topk_bias_scores_capped(U, T, bias, cls, k, cap_cls.long(), 1, slices=1)
     all_idx, all_score, _ = ops.topk_bias_scores(U, T, bias, cls, V)
     want_idx, want_score, _ = topk_capped_ref.walk_listed(all_idx.cpu(), all_score.cpu(), cap_cls.cpu(), k, 1)
     assert int(status) == 0 and bool((all_idx >= 0).all())   # (the list of V rows is every user's whole population)
-    assert torch.equal(idx.cpu(), want_idx) and torch.equal(_bits(score.cpu()), _bits(want_score))
+    assert torch.equal(idx.cpu(), want_idx) and torch.equal(C.bits(score.cpu()), C.bits(want_score))
     assert bool((idx[:, 5:] == -1).all()) and bool((idx[:, :5] >= 0).all())      # five classes, one row each
 
 
@@ -372,13 +361,13 @@ def test_bad_arguments_are_refused_before_any_launch():
 def test_biased_entries_do_not_synchronise_with_the_host():
     from newsreclib_amd import ops
     U, T, bias, cls = _real(3, 5, 200, 12, 4)
-    ei, eo = _ragged([[1, 2], [], [5], [7, 7], []])
+    ei, eo = C.ragged([[1, 2], [], [5], [7, 7], []])
     ei, eo, elig = ei.cuda(), eo.cuda(), torch.ones(200, dtype=torch.uint8).cuda()
     tgt, off, cls64 = torch.arange(5, dtype=torch.int64).cuda(), torch.arange(6, dtype=torch.int64).cuda(), cls.long()
     torch.cuda.synchronize()
     torch.cuda.set_sync_debug_mode("error")
     try:
-        if not _sync_debug_honoured():
+        if not C.sync_debug_honoured():
             pytest.skip("this torch build does not raise on synchronising calls under set_sync_debug_mode('error')")
         idx, score, status = ops.topk_bias_scores(U, T, bias, cls, 4, ei, eo, elig)
         idx64, _, _ = ops.topk_bias_scores(U, T, bias, cls64, 4, ei, eo, elig)
@@ -425,7 +414,7 @@ def test_sentidebias_is_ranked_by_its_bias_free_and_by_its_combined_score(late_f
         free, none = mod.generator.user_vectors(hv, meta, None)
     want = ops.topk_scores(free, cache.vectors, k, hist, meta["hist_offsets"], eligible.cuda())
     assert none is None and int(status) == int(want[2]) == 0
-    assert torch.equal(idx, want[0]) and torch.equal(_bits(score), _bits(want[1]))
+    assert torch.equal(idx, want[0]) and torch.equal(C.bits(score), C.bits(want[1]))
     # combined=True: every returned (user, row) against the module's own forward over those rows as the candidate lists
     cidx, cscore, status = cache.recommend_biased(hist, hs, k, eligible=eligible, combined=True)
     assert int(status) == 0 and bool((cidx >= 0).all())
@@ -443,7 +432,7 @@ def test_sentidebias_is_ranked_by_its_bias_free_and_by_its_combined_score(late_f
         rank, tscore, ranked, status = cache.rank_clicks_biased(hist, hs, clicks, torch.full((B,), 3), eligible=eligible, combined=comb)
         assert int(status) == 0 and rank.reshape(B, 3).tolist() == [[1, k, 0]] * B
         assert ranked.tolist() == [V - 1 - int(n) for n in hs]
-        assert torch.equal(_bits(tscore.reshape(B, 3)[:, :2]), _bits(lscore[:, [0, k - 1]]))
+        assert torch.equal(C.bits(tscore.reshape(B, 3)[:, :2]), C.bits(lscore[:, [0, k - 1]]))
     # recommend_users and evaluate_full_rank pick the biased methods; the dictionary and the metric keys are the usual ones
     users = [{"hist": lists[b], "clicks": idx[b, :2].cpu(), "user_id": 100 + b} for b in range(B)]
     recs = recommend_users(cache, users, k, batch_size=4, eligible=eligible)
@@ -469,11 +458,10 @@ def test_sentidebias_is_ranked_by_its_bias_free_and_by_its_combined_score(late_f
 def test_a_dot_product_module_with_the_callers_bias():
     from newsreclib_amd import ops
     from newsreclib_amd.evaluation import DeviceNewsTable, NewsVectorCache
-    from tests.test_gpu_topk import _hist_batch, _tiny
-    mod, attrs = _tiny("nrms")
+    mod, attrs = builders.tiny("nrms")
     cache = NewsVectorCache(mod, DeviceNewsTable(attrs), chunk=32)
     V, B, k = 50, 6, 10
-    lists, hist, hs, uidx = _hist_batch(V)
+    lists, hist, hs, uidx = builders.hist_batch(V)
     categ = cache.table.attrs["category"]
     S = int(categ.max()) + 1
     bias = torch.randn(B, S, generator=torch.Generator().manual_seed(2)).cuda() * 3
@@ -487,18 +475,18 @@ def test_a_dot_product_module_with_the_callers_bias():
         user = mod.user_vectors(ops.embedding_gather(cache.vectors, hist.cuda().reshape(-1, 1)).reshape(-1, cache.vectors.shape[1]), meta)
         mod.train()
     s, flags = R.scores(user.cpu().numpy(), cache.vectors.cpu().numpy(), bias.cpu().numpy(), categ.cpu().numpy())
-    pop, _ = R.population(s, [x.tolist() for x in lists])
-    want_idx, want_score = R.topk(s, pop, k)
+    pop, _ = C.population(s, [x.tolist() for x in lists])
+    want_idx, want_score = C.topk(s, pop, k)
     # (a user without a near-tie among its first k + 1 float64 scores: fp32 cannot reorder them)
-    clear = np.abs(np.diff(np.sort(np.where(pop, -s, np.inf), axis=1)[:, :k + 1], axis=1)).min(1) > 1e-4
+    clear = torch.sort(C.masked(s, pop), dim=1, descending=True)[0][:, :k + 1].diff(dim=1).abs().min(1)[0] > 1e-4
     assert flags == 0 and clear.sum() >= B - 1
-    assert np.array_equal(idx.cpu().numpy()[clear], want_idx[clear])
-    assert float(np.abs(score.cpu().numpy()[clear] - want_score[clear]).max()) <= 1e-4
+    assert torch.equal(idx.cpu()[clear], want_idx[clear])
+    assert float((score.cpu()[clear] - want_score[clear]).abs().max()) <= 1e-4
     # the same call by hand, the capped one, the rank
     want = ops.topk_bias_scores(user, cache.vectors, bias, categ, k, hist.cuda(), meta["hist_offsets"])
-    assert torch.equal(idx, want[0]) and torch.equal(_bits(score), _bits(want[1]))
+    assert torch.equal(idx, want[0]) and torch.equal(C.bits(score), C.bits(want[1]))
     cidx, _, status = cache.recommend_biased(hist.cuda(), hs, k, user_idx=uidx, aspect="category", bias=bias, cap=("category", 2))
     assert int(status) == 0 and int(torch.stack([(categ[cidx.clamp(min=0)] == c).sum(1) for c in range(S)]).max()) <= 2
     rank, tscore, _, status = cache.rank_clicks_biased(hist.cuda(), hs, idx[:, 3].contiguous(), torch.ones(B, dtype=torch.int64),
                                                        user_idx=uidx, aspect="category", bias=bias)
-    assert int(status) == 0 and rank.tolist() == [4] * B and torch.equal(_bits(tscore), _bits(score[:, 3]))
+    assert int(status) == 0 and rank.tolist() == [4] * B and torch.equal(C.bits(tscore), C.bits(score[:, 3]))

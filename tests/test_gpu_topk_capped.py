@@ -1,15 +1,16 @@
 """Class-capped full-catalogue top-k (``nrl_topk_scores_capped`` / ``nrl_topk_ensemble_scores_capped``, ``ops.topk_scores_capped``
 / ``ops.topk_ensemble_scores_capped``, ``NewsVectorCache.recommend_capped`` / ``MannerVectorCache.recommend_ensemble_capped``).
 
-Expected values come from the greedy definition on the CPU (``tests/topk_capped_ref.py``): the float64 scores of
-``test_gpu_topk._masked_scores``, walked in the family's order, a row taken iff fewer than m rows of its class have been.
+Expected values come from the greedy definition on the CPU (``tests/topk_capped_ref.py``): the float64 scores and the
+population of ``tests/catalogue_ref.py``, walked in the family's order, a row taken iff fewer than m rows of its class have been.
 Integer-valued vectors in [-4, 4] make every fp32 dot product exact, so the lists compare with ``torch.equal``.  The ensemble's
 scores are real-valued: there the walk runs over the bit-equal scores the uncapped entry returns for the same call."""
 import pytest
 import torch
 
+from tests import builders
+from tests import catalogue_ref as C
 from tests import topk_capped_ref as R
-from tests.test_gpu_topk import _int_vectors, _masked_scores, _ragged, _sync_debug_honoured
 
 pytestmark = pytest.mark.gpu
 
@@ -34,15 +35,16 @@ def _run(U, T, k, cls, m, excl=None, eligible=None, slices=0):
     from newsreclib_amd import ops
     ei = eo = None
     if excl is not None:
-        ei, eo = _ragged(excl)
+        ei, eo = C.ragged(excl)
         ei, eo = ei.cuda(), eo.cuda()
     idx, score, status = ops.topk_scores_capped(U.cuda(), T.cuda(), k, cls.cuda(), m, ei, eo,
                                                 eligible.cuda() if eligible is not None else None, slices)
     return idx.cpu(), score.cpu(), int(status)
 
 
-def _bits(x):
-    return x.view(torch.int32)
+def _reference(U, T, cls, k, m, excl=None, eligible=None):
+    s = U.double() @ T.double().T
+    return R.reference(s, C.population(s, excl, eligible)[0], cls, k, m)
 
 
 # ---- 1. exact, with ties: every B, V, D, k, m, class count and slicing of the issue appears ------------------------------------------
@@ -54,10 +56,10 @@ _EXACT = [(130, 1000, 300, 64, 2, 19, 7), (130, 1000, 4, 5, 1, 3, 0), (3, 1000, 
 
 @pytest.mark.parametrize("B,V,D,k,m,n_cls,slices", _EXACT)
 def test_exact_with_ties(B, V, D, k, m, n_cls, slices):
-    U, T = _int_vectors(B * 7 + V + D + k + m, B, V, D)
+    U, T = C.int_vectors(B * 7 + V + D + k + m, B, V, D)
     cls = _classes(V + n_cls, V, n_cls)
     idx, score, status = _run(U, T, k, cls, m, slices=slices)
-    want_idx, want_score = R.reference(_masked_scores(U, T), cls, k, m)
+    want_idx, want_score = _reference(U, T, cls, k, m)
     assert status == 0
     assert torch.equal(idx, want_idx)
     assert torch.equal(score, want_score)
@@ -65,12 +67,11 @@ def test_exact_with_ties(B, V, D, k, m, n_cls, slices):
 
 @pytest.mark.parametrize("slices", [0, 3])
 def test_one_class_and_a_cap_of_one_return_one_row(slices):
-    U, T = _int_vectors(8, 5, 700, 12)
+    U, T = C.int_vectors(8, 5, 700, 12)
     cls = torch.full((700,), 11, dtype=torch.int32)
     idx, score, status = _run(U, T, 6, cls, 1, slices=slices)
-    best = _masked_scores(U, T)
     assert status == 0
-    assert torch.equal(idx[:, 0], torch.sort(-best, dim=1, stable=True)[1][:, 0])
+    assert torch.equal(idx[:, 0], C.expected_topk(U.double() @ T.double().T, 1)[0][:, 0])
     assert torch.equal(idx[:, 1:], torch.full((5, 5), -1)) and bool((score[:, 1:] == float("-inf")).all())
 
 
@@ -94,7 +95,7 @@ def test_a_full_class_is_displaced_by_better_rows_and_rejects_worse_ones(descend
     V, k, m = 700, 8, 3                                     # six tiles; three slices of two
     U, T, cls = _ramp(V, descending)
     idx, score, status = _run(U, T, k, cls, m, slices=slices)
-    want_idx, want_score = R.reference(_masked_scores(U, T), cls, k, m)
+    want_idx, want_score = _reference(U, T, cls, k, m)
     assert status == 0 and torch.equal(idx, want_idx) and torch.equal(score, want_score)
     top5 = [1, 2, 4] if descending else [698, 697, 695]
     assert idx[0].tolist() == top5 + [0, 3, 6, -1, -1]      # three of class 5, then class 9's first three (ties: lowest rows)
@@ -125,19 +126,20 @@ def test_ties_across_tile_and_slice_borders_go_to_the_lower_row(slices):
 # ---- 3. exclusion, eligibility, NaN: what is removed never counts toward a cap -----------------------------------------------------------
 def _removal_case():
     B, V, D, k, m = 4, 300, 12, 10, 2
-    U, T = _int_vectors(77, B, V, D)
+    U, T = C.int_vectors(77, B, V, D)
     cls = _classes(5, V, 4)
-    base_idx, _ = R.reference(_masked_scores(U, T), cls, k, m)
+    base_idx, _ = _reference(U, T, cls, k, m)
     return B, V, k, m, U, T, cls, base_idx
 
 
 def _next_of_class(U, T, cls, b, row, k, m, excl=None):
     """user b's capped list once `row` is gone, and the rows in it that were not there before (``excl``: lists in force
     before and after)"""
-    s = _masked_scores(U, T, excl)
-    before = set(R.reference(s, cls, k, m)[0][b].tolist())
-    s[b, row] = float("-inf")
-    after = R.reference(s, cls, k, m)[0][b].tolist()
+    s = U.double() @ T.double().T
+    pop = C.population(s, excl)[0]
+    before = set(R.reference(s, pop, cls, k, m)[0][b].tolist())
+    pop[b, row] = False
+    after = R.reference(s, pop, cls, k, m)[0][b].tolist()
     return after, [v for v in after if v not in before]
 
 
@@ -151,7 +153,7 @@ def test_excluding_the_best_row_of_a_full_class_admits_the_next(slices):
     others = [[], [], [], long_list]
     excl = [[first[0]], [], [first[2]] * 3, long_list + [first[3]]]
     idx, score, status = _run(U, T, k, cls, m, excl=excl, slices=slices)
-    want_idx, want_score = R.reference(_masked_scores(U, T, excl), cls, k, m)
+    want_idx, want_score = _reference(U, T, cls, k, m, excl)
     assert status == 0 and torch.equal(idx, want_idx) and torch.equal(score, want_score)
     for b in (0, 2, 3):
         after, new = _next_of_class(U, T, cls, b, first[b], k, m, others)
@@ -166,7 +168,7 @@ def test_an_ineligible_row_does_not_count_toward_the_cap():
     elig = torch.ones(V, dtype=torch.uint8)
     elig[gone] = 0
     idx, score, status = _run(U, T, k, cls, m, eligible=elig, slices=2)
-    want_idx, want_score = R.reference(_masked_scores(U, T, eligible=elig), cls, k, m)
+    want_idx, want_score = _reference(U, T, cls, k, m, eligible=elig)
     assert status == 0 and torch.equal(idx, want_idx) and torch.equal(score, want_score)
     _, new = _next_of_class(U, T, cls, 0, gone, k, m)
     assert len(new) == 1 and int(cls[new[0]]) == int(cls[gone]) and new[0] in idx[0].tolist()
@@ -181,7 +183,7 @@ def test_a_nan_row_is_flagged_left_out_and_does_not_count_toward_the_cap():
     idx, score, status = _run(U, Tn, k, cls, m, slices=2)
     elig = torch.ones(V, dtype=torch.uint8)
     elig[gone] = 0
-    want_idx, want_score = R.reference(_masked_scores(U, T, eligible=elig), cls, k, m)      # every other position unchanged
+    want_idx, want_score = _reference(U, T, cls, k, m, eligible=elig)      # every other position unchanged
     assert status == E_NAN
     assert torch.equal(idx, want_idx) and torch.equal(score, want_score)
     assert not bool((idx == gone).any())
@@ -196,11 +198,11 @@ def test_a_cap_of_k_or_more_returns_the_bits_of_topk_scores(B, V, D, k, m, slice
     U, T = torch.randn(B, D, generator=g).cuda(), torch.randn(V, D, generator=g).cuda()
     T[5] = T[9]                                              # (a tie between real values)
     cls = _classes(3, V, 3).cuda()
-    excl_idx, excl_off = _ragged([[5, 7]] + [[] for _ in range(B - 1)])
+    excl_idx, excl_off = C.ragged([[5, 7]] + [[] for _ in range(B - 1)])
     got = ops.topk_scores_capped(U, T, k, cls, m, excl_idx.cuda(), excl_off.cuda(), slices=slices)
     want = ops.topk_scores(U, T, k, excl_idx.cuda(), excl_off.cuda(), slices=slices)
     assert int(got[2]) == int(want[2]) == 0
-    assert torch.equal(got[0], want[0]) and torch.equal(_bits(got[1]), _bits(want[1]))
+    assert torch.equal(got[0], want[0]) and torch.equal(C.bits(got[1]), C.bits(want[1]))
 
 
 def test_every_returned_score_has_the_bits_of_the_uncapped_entry():
@@ -214,7 +216,7 @@ def test_every_returned_score_has_the_bits_of_the_uncapped_entry():
     assert int(status) == 0
     want_idx, want_score, decided = R.walk_listed(all_idx.cpu(), all_score.cpu(), cls, k, m)
     assert decided
-    assert torch.equal(idx.cpu(), want_idx) and torch.equal(_bits(score.cpu()), _bits(want_score))
+    assert torch.equal(idx.cpu(), want_idx) and torch.equal(C.bits(score.cpu()), C.bits(want_score))
 
 
 # ---- 5. invariance ---------------------------------------------------------------------------------------------------------------------------
@@ -230,27 +232,27 @@ def test_invariance_under_batch_slicing_and_engine():
     assert int(per.max()) <= m and bool((base_idx >= 0).all())
     for slices in (1, 2, 7, 0):
         idx, score, _ = ops.topk_scores_capped(U, T, k, cls, m, slices=slices)
-        assert torch.equal(idx, base_idx) and torch.equal(_bits(score), _bits(base_score)), slices
+        assert torch.equal(idx, base_idx) and torch.equal(C.bits(score), C.bits(base_score)), slices
     for b in (0, 63, 64, 129):                               # a user alone against the same user inside the batch of 130
         idx, score, _ = ops.topk_scores_capped(U[b:b + 1], T, k, cls, m)
-        assert torch.equal(idx[0], base_idx[b]) and torch.equal(_bits(score[0]), _bits(base_score[b])), b
+        assert torch.equal(idx[0], base_idx[b]) and torch.equal(C.bits(score[0]), C.bits(base_score[b])), b
     prev = _lib.get_gemm_engine()
     try:
         for name in ("f32", "bf16x3"):
             _lib.set_gemm_engine(name)
             idx, score, _ = ops.topk_scores_capped(U, T, k, cls, m)
-            assert torch.equal(idx, base_idx) and torch.equal(_bits(score), _bits(base_score)), name
+            assert torch.equal(idx, base_idx) and torch.equal(C.bits(score), C.bits(base_score)), name
     finally:
         _lib.set_gemm_engine(prev)
     # int64 classes are the same classes
     idx, score, _ = ops.topk_scores_capped(U, T, k, cls.long(), m)
-    assert torch.equal(idx, base_idx) and torch.equal(_bits(score), _bits(base_score))
+    assert torch.equal(idx, base_idx) and torch.equal(C.bits(score), C.bits(base_score))
 
 
 # ---- 6. argument checks, no read-back ---------------------------------------------------------------------------------------------------------
 def test_bad_arguments_are_refused_before_any_launch():
     from newsreclib_amd import ops
-    U, T = _int_vectors(3, 5, 200, 12)
+    U, T = C.int_vectors(3, 5, 200, 12)
     U, T, cls = U.cuda(), T.cuda(), _classes(1, 200, 3).cuda()
     with pytest.raises(RuntimeError, match=r"k in \[1, 64\]"):
         ops.topk_scores_capped(U, T, 65, cls, 2)
@@ -273,15 +275,15 @@ def test_bad_arguments_are_refused_before_any_launch():
 
 def test_capped_entries_do_not_synchronise_with_the_host():
     from newsreclib_amd import ops
-    U, T = _int_vectors(3, 5, 200, 12)
+    U, T = C.int_vectors(3, 5, 200, 12)
     U, T = U.cuda(), T.cuda()
-    ei, eo = _ragged([[1, 2], [], [5], [7, 7], []])
+    ei, eo = C.ragged([[1, 2], [], [5], [7, 7], []])
     ei, eo, elig = ei.cuda(), eo.cuda(), torch.ones(200, dtype=torch.uint8).cuda()
     cls32, cls64 = _classes(1, 200, 3).cuda(), _classes(1, 200, 3).long().cuda()
     torch.cuda.synchronize()
     torch.cuda.set_sync_debug_mode("error")
     try:
-        if not _sync_debug_honoured():
+        if not C.sync_debug_honoured():
             pytest.skip("this torch build does not raise on synchronising calls under set_sync_debug_mode('error')")
         idx, score, status = ops.topk_scores_capped(U, T, 4, cls32, 1, ei, eo, elig)
         idx64, _, _ = ops.topk_scores_capped(U, T, 4, cls64, 1, ei, eo, elig)
@@ -306,17 +308,17 @@ def test_ensemble_is_the_greedy_walk_over_the_uncapped_scores(V, k, m, slices):
     users, tables, weights = _ensemble_case(V, B, V, D)
     users[0][4] = float("nan")                              # user 4 cannot be standardised
     cls = _classes(2, V, 3)
-    excl_idx, excl_off = _ragged([[1, 2, 3]] + [[] for _ in range(B - 1)])
+    excl_idx, excl_off = C.ragged([[1, 2, 3]] + [[] for _ in range(B - 1)])
     elig = torch.ones(V, dtype=torch.uint8)
     elig[0] = 0
     tail = (excl_idx.cuda(), excl_off.cuda(), elig.cuda())
     idx, score, status, stats = ops.topk_ensemble_scores_capped(users, tables, weights, k, cls.cuda(), m, *tail, slices=slices)
     all_idx, all_score, all_status, all_stats = ops.topk_ensemble_scores(users, tables, weights, V, *tail)
     assert int(status) == int(all_status) and int(status) & E_STATS
-    assert torch.equal(_bits(stats), _bits(all_stats))
+    assert torch.equal(C.bits(stats), C.bits(all_stats))
     want_idx, want_score, decided = R.walk_listed(all_idx.cpu(), all_score.cpu(), cls, k, m)
     assert decided
-    assert torch.equal(idx.cpu(), want_idx) and torch.equal(_bits(score.cpu()), _bits(want_score))
+    assert torch.equal(idx.cpu(), want_idx) and torch.equal(C.bits(score.cpu()), C.bits(want_score))
     assert torch.equal(idx[4].cpu(), torch.full((k,), -1)) and bool((score[4] == float("-inf")).all())      # blank and flagged
     assert bool((idx[:4] >= 0)[:, :min(k, 3 * m)].all())
 
@@ -330,10 +332,10 @@ def test_ensemble_over_a_long_table_walks_the_uncapped_list():
     cls = _classes(19, V, 19)
     idx, score, status, stats = ops.topk_ensemble_scores_capped(users, tables, weights, k, cls.cuda(), m, slices=3)
     all_idx, all_score, _, all_stats = ops.topk_ensemble_scores(users, tables, weights, 128)
-    assert int(status) == 0 and torch.equal(_bits(stats), _bits(all_stats))
+    assert int(status) == 0 and torch.equal(C.bits(stats), C.bits(all_stats))
     want_idx, want_score, decided = R.walk_listed(all_idx.cpu(), all_score.cpu(), cls, k, m)
     assert decided
-    assert torch.equal(idx.cpu(), want_idx) and torch.equal(_bits(score.cpu()), _bits(want_score))
+    assert torch.equal(idx.cpu(), want_idx) and torch.equal(C.bits(score.cpu()), C.bits(want_score))
 
 
 # ---- 8. cache level -----------------------------------------------------------------------------------------------------------------------------
@@ -351,18 +353,17 @@ def _per_class_max(idx, cls):
 def test_recommend_capped_is_the_walk_over_recommend():
     from newsreclib_amd.evaluation import DeviceNewsTable, NewsVectorCache, recommend_users
     from newsreclib_amd.metrics import aspect_metrics, recommendation_aspect_metrics
-    from tests.test_gpu_topk import _hist_batch, _tiny
-    mod, attrs = _tiny("nrms")
+    mod, attrs = builders.tiny("nrms")
     cache = NewsVectorCache(mod, DeviceNewsTable(attrs), chunk=32)
     V, B, k, m = 50, 6, 10, 2
-    lists, hist, hs, uidx = _hist_batch(V)
+    lists, hist, hs, uidx = builders.hist_batch(V)
     cls = cache.table.attrs["category"].cpu()
     mod.train()
     idx, score, status = cache.recommend_capped(hist.cuda(), hs, k, "category", m, user_idx=uidx)
     assert mod.training and int(status) == 0
     all_idx, all_score, _ = cache.recommend(hist.cuda(), hs, 128, user_idx=uidx)
     want_idx, want_score, decided = R.walk_listed(all_idx.cpu(), all_score.cpu(), cls, k, m)
-    assert decided and torch.equal(idx.cpu(), want_idx) and torch.equal(_bits(score.cpu()), _bits(want_score))
+    assert decided and torch.equal(idx.cpu(), want_idx) and torch.equal(C.bits(score.cpu()), C.bits(want_score))
     assert _per_class_max(idx.cpu(), cls) <= m
     kept = cache._row_class["category"]
     assert kept.dtype == torch.int32
@@ -404,10 +405,9 @@ def test_recommend_users_refuses_a_cap_for_the_other_scorers():
 
 def test_recommend_ensemble_capped_is_the_walk_over_recommend_ensemble(tmp_path):
     from newsreclib_amd.evaluation import MannerVectorCache, recommend_users
-    from tests.test_gpu_manner import _ensemble, _modules, _table_and_impressions
-    cr, ac, asent = _modules(tmp_path)
-    ens = _ensemble(cr, ac, asent)
-    table, imps = _table_and_impressions()
+    cr, ac, asent = builders.manner_modules(tmp_path)
+    ens = builders.manner_ensemble(cr, ac, asent)
+    table, imps = builders.manner_table_and_impressions()
     B, k, m = len(imps), 10, 2
     cache = MannerVectorCache(ens, table)
     lists = [i["hist"] for i in imps]
@@ -415,9 +415,9 @@ def test_recommend_ensemble_capped_is_the_walk_over_recommend_ensemble(tmp_path)
     cls = table.attrs["category"].cpu()
     idx, score, status, stats = cache.recommend_ensemble_capped(hist.cuda(), hs, k, "category", m, return_stats=True)
     all_idx, all_score, _, all_stats = cache.recommend_ensemble(hist.cuda(), hs, 128, return_stats=True)
-    assert int(status) == 0 and torch.equal(_bits(stats), _bits(all_stats))
+    assert int(status) == 0 and torch.equal(C.bits(stats), C.bits(all_stats))
     want_idx, want_score, decided = R.walk_listed(all_idx.cpu(), all_score.cpu(), cls, k, m)
-    assert decided and torch.equal(idx.cpu(), want_idx) and torch.equal(_bits(score.cpu()), _bits(want_score))
+    assert decided and torch.equal(idx.cpu(), want_idx) and torch.equal(C.bits(score.cpu()), C.bits(want_score))
     assert _per_class_max(idx.cpu(), cls) <= m and len(cache.recommend_ensemble_capped(hist.cuda(), hs, k, "category", m)) == 3
     users = [{"hist": lists[b], "user_id": 100 + b} for b in range(B)]
     capped = recommend_users(cache, users, k, batch_size=B + 3, cap=("category", m))

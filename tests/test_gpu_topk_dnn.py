@@ -8,10 +8,11 @@ bound, so row sets are never compared with float64."""
 import ctypes
 import functools
 
-import numpy as np
 import pytest
 import torch
 
+from tests import builders
+from tests import catalogue_ref as C
 from tests import topk_dnn_ref as R
 
 pytestmark = pytest.mark.gpu
@@ -37,17 +38,11 @@ def _int_case(seed, B, V, Hd):
     return q, proj, w2, b2, R.relu_scores64(q, proj, w2, b2)
 
 
-def _ragged(lists):
-    off = torch.tensor([0] + [len(x) for x in lists]).cumsum(0)
-    idx = torch.tensor([v for x in lists for v in x], dtype=torch.int64)
-    return idx, off
-
-
 def _run(q, proj, w2, b2, k, excl=None, eligible=None, slices=0, off=None):
     from newsreclib_amd import ops
     ei = eo = None
     if excl is not None:
-        ei, eo = _ragged(excl)
+        ei, eo = C.ragged(excl)
         ei, eo = ei.cuda(), (off if off is not None else eo).cuda()
     idx, score, status = ops.topk_relu_scores(q.cuda(), proj.cuda(), w2.cuda(), b2.cuda(), k, ei, eo,
                                               eligible.cuda() if eligible is not None else None, slices)
@@ -60,7 +55,7 @@ def _run(q, proj, w2, b2, k, excl=None, eligible=None, slices=0, off=None):
 def test_exact_with_ties(Hd, k):
     """Three user tiles (the last of 2 users), eight table tiles (the last of 104 rows), every slicing."""
     q, proj, w2, b2, s = _int_case(100 + Hd, 130, 1000, Hd)
-    want_idx, want_score = R.ranking(s, k)
+    want_idx, want_score = C.expected_topk(s, k)
     for slices in (0, 1, 2, 7):
         idx, score, status = _run(q, proj, w2, b2, k, slices=slices)
         assert status == 0, slices
@@ -80,7 +75,7 @@ def test_all_equal_scores_return_the_first_rows(slices):
 def test_fewer_rows_than_k_and_an_empty_table():
     q, proj, w2, b2, s = _int_case(7, 3, 5, 16)
     idx, score, status = _run(q, proj, w2, b2, 8)
-    want_idx, want_score = R.ranking(s, 8)
+    want_idx, want_score = C.expected_topk(s, 8)
     assert status == 0 and torch.equal(idx, want_idx) and torch.equal(score, want_score)
     assert bool((idx[:, 5:] == -1).all()) and bool((score[:, 5:] == float("-inf")).all()) and bool((idx[:, :5] >= 0).all())
     idx, score, status = _run(q, proj[:0], w2, b2, 8)
@@ -93,7 +88,7 @@ def _excl_case():
     q, proj, w2, b2, s = _int_case(91, B, V, Hd)
     eligible = torch.ones(V, dtype=torch.uint8)
     eligible[[0, 7, 8, 31]] = 0
-    first = R.ranking(R.mask(s, None, eligible), k)[0][:, 0]           # every user's would-be first place
+    first = C.expected_topk(s, k, None, eligible)[0][:, 0]           # every user's would-be first place
     everything = [v for v in range(V) if eligible[v]]
     excl = [[], [3, 3, 9, 3, 9], [int(first[2]), 5], everything, [int(first[4])] * 3 + [39, 1]]
     return (q, proj, w2, b2), s, k, excl, eligible
@@ -103,7 +98,7 @@ def _excl_case():
 def test_exclusion_and_eligibility(slices):
     ops_in, s, k, excl, eligible = _excl_case()
     idx, score, status = _run(*ops_in, k, excl, eligible, slices)
-    want_idx, want_score = R.ranking(R.mask(s, excl, eligible), k)
+    want_idx, want_score = C.expected_topk(s, k, excl, eligible)
     assert status == 0
     assert torch.equal(idx, want_idx) and torch.equal(score, want_score)
     assert torch.equal(idx[3], torch.full((k,), -1)) and bool(torch.isinf(score[3]).all())
@@ -117,10 +112,10 @@ def test_exclusion_list_longer_than_the_cached_part():
     B, V, Hd, k = 3, 700, 7, 20
     q, proj, w2, b2, s = _int_case(5, B, V, Hd)
     g = torch.Generator().manual_seed(3)
-    best = R.ranking(s, 150)[0][2].tolist()
+    best = C.expected_topk(s, 150)[0][2].tolist()
     excl = [torch.randperm(V, generator=g)[:150].tolist(), [], best + best[:40]]
     idx, score, status = _run(q, proj, w2, b2, k, excl, slices=3)
-    want_idx, want_score = R.ranking(R.mask(s, excl), k)
+    want_idx, want_score = C.expected_topk(s, k, excl)
     assert status == 0 and torch.equal(idx, want_idx) and torch.equal(score, want_score)
 
 
@@ -131,7 +126,7 @@ def test_status_bad_exclusion_index_is_ignored():
     bad[1] = [-1] + bad[1]
     bad[2] = bad[2] + [s.shape[1]]
     idx, score, status = _run(*ops_in, k, bad, eligible)
-    want_idx, want_score = R.ranking(R.mask(s, excl, eligible), k)
+    want_idx, want_score = C.expected_topk(s, k, excl, eligible)
     assert status == E_EXCLUDE
     assert torch.equal(idx, want_idx) and torch.equal(score, want_score)
 
@@ -142,7 +137,7 @@ def test_status_decreasing_offsets_blank_that_user_alone():
     off = torch.tensor([0, 5, 3, 8, 12])                    # user 1 runs backwards
     idx, score, status = _run(q, proj, w2, b2, k, [flat], off=off)
     assert status == E_OFFSETS
-    want_idx, want_score = R.ranking(R.mask(s, [flat[0:5], [], flat[3:8], flat[8:12]]), k)
+    want_idx, want_score = C.expected_topk(s, k, [flat[0:5], [], flat[3:8], flat[8:12]])
     for b in (0, 2, 3):
         assert torch.equal(idx[b], want_idx[b]) and torch.equal(score[b], want_score[b])
     assert torch.equal(idx[1], torch.full((k,), -1)) and bool((score[1] == float("-inf")).all())
@@ -153,7 +148,7 @@ def test_status_offsets_beyond_the_list():
     k = 6
     idx, score, status = _run(q, proj, w2, b2, k, [list(range(6))], off=torch.tensor([0, 2, 9, 6]))
     assert status == E_OFFSETS
-    want_idx, _ = R.ranking(R.mask(s, [[0, 1], [], []]), k)
+    want_idx, _ = C.expected_topk(s, k, [[0, 1], [], []])
     assert torch.equal(idx[0], want_idx[0])
     assert torch.equal(idx[1:], torch.full((2, k), -1))
 
@@ -165,7 +160,7 @@ def test_status_nan_row_is_left_out():
     w2 = w2.abs() + 1                                       # every w2[j] != 0, so the NaN reaches every user's score
     s = R.relu_scores64(q, proj, w2, b2)
     clean_idx, clean_score, status = _run(q, proj, w2, b2, k, slices=2)
-    assert status == 0 and torch.equal(clean_idx, R.ranking(s, k)[0])
+    assert status == 0 and torch.equal(clean_idx, C.expected_topk(s, k)[0])
     nan_row = int(clean_idx[0, 0])                          # a row that would be returned
     pn = proj.clone()
     pn[nan_row, 3] = float("nan")
@@ -174,7 +169,7 @@ def test_status_nan_row_is_left_out():
     assert not bool((idx == nan_row).any())
     elig = torch.ones(300, dtype=torch.uint8)
     elig[nan_row] = 0
-    want_idx, want_score = R.ranking(R.mask(s, None, elig), k)          # every other position unchanged
+    want_idx, want_score = C.expected_topk(s, k, None, elig)          # every other position unchanged
     assert torch.equal(idx, want_idx) and torch.equal(score, want_score)
     # not eligible: nobody is told
     idx, score, status = _run(q, pn, w2, b2, k, eligible=elig, slices=2)
@@ -190,13 +185,13 @@ def test_real_values_against_float64():
     att, pred = [t.cuda() for t in c["att"]], [t.cuda() for t in c["pred"]]
     proj = ops_dkn.dkn_cand_project(c["table"].cuda(), pred)
     user, q = ops_dkn.dkn_user_query(c["hist"].cuda(), c["off"].cuda(), int(c["sizes"].max()), att, pred)
-    ei, eo = _ragged(c["excl"])
+    ei, eo = C.ragged(c["excl"])
     idx, score, status = ops.topk_relu_scores(q, proj, pred[2], pred[3], k, ei.cuda(), eo.cuda())
     assert int(status) == 0
     user = user.cpu()
     assert bool((user[3] == 0).all()) and torch.equal(q[3].cpu(), c["pred"][1])          # the empty history: u = 0, q = b1
     raw, bound = R.scores64(user, c["table"], c["pred"])
-    R.check_floor(idx.cpu(), score.cpu(), raw, bound, R.mask(raw, c["excl"]), c["excl"], k)
+    C.check_floor(idx.cpu(), score.cpu(), raw, bound, C.population(raw, c["excl"])[0], k)
 
 
 # ---- 5. the user vector is the click kernel's -------------------------------------------------------------------------------------
@@ -304,24 +299,16 @@ def test_peak_memory_is_far_below_the_hidden_activations():
 
 
 # ---- 8. no read-back ---------------------------------------------------------------------------------------------------------------------
-def _sync_debug_honoured():
-    try:
-        float(torch.ones(1, device="cuda").sum())
-    except RuntimeError:
-        return True
-    return False
-
-
 def test_topk_relu_scores_does_not_synchronise_with_the_host():
     from newsreclib_amd import ops
     q, proj, w2, b2, _ = _int_case(3, 5, 200, 12)
     q, proj, w2, b2 = q.cuda(), proj.cuda(), w2.cuda(), b2.cuda()
-    ei, eo = _ragged([[1, 2], [], [5], [7, 7], []])
+    ei, eo = C.ragged([[1, 2], [], [5], [7, 7], []])
     ei, eo, elig = ei.cuda(), eo.cuda(), torch.ones(200, dtype=torch.uint8).cuda()
     torch.cuda.synchronize()
     torch.cuda.set_sync_debug_mode("error")
     try:
-        if not _sync_debug_honoured():
+        if not C.sync_debug_honoured():
             pytest.skip("this torch build does not raise on synchronising calls under set_sync_debug_mode('error')")
         idx, score, status = ops.topk_relu_scores(q, proj, w2, b2, 4, ei, eo, elig)
     finally:
@@ -330,23 +317,6 @@ def test_topk_relu_scores_does_not_synchronise_with_the_host():
 
 
 # ---- 9. wiring -----------------------------------------------------------------------------------------------------------------------------
-def _tiny(late_fusion=False, n_news=50, Hd=6):
-    """(DKNModule in eval mode, table attributes) from the synthetic builders of the DKN tests: dim = 24."""
-    from tests import dkn_oracle as DO
-    cfg = dict(vocab=120, n_ent=30, D=16, Ed=8, F=8, Hd=Hd, windows=[1, 2, 3], use_context=True, late_fusion=late_fusion)
-    params = DO.make_dkn_params(cfg["vocab"], cfg["n_ent"], cfg["D"], cfg["Ed"], cfg["F"], cfg["windows"], Hd,
-                                use_context=True, late_fusion=late_fusion, seed=8)
-    rng = np.random.default_rng(11)
-    attrs = {"title": torch.from_numpy(rng.integers(1, cfg["vocab"], (n_news, 12))),
-             "title_entities": torch.from_numpy(rng.integers(0, cfg["n_ent"], (n_news, 12)))}
-    return DO.build_module(cfg, params).eval(), attrs
-
-
-def _hist_batch(n_news, B=6, seed=3):
-    rng = np.random.default_rng(seed)
-    sizes = rng.integers(1, 9, B)
-    hist = [torch.from_numpy(rng.choice(np.arange(1, n_news), int(n), replace=False)) for n in sizes]
-    return hist, torch.cat(hist), torch.tensor([len(h) for h in hist])
 
 
 def _click_bound(user, vec, pred):
@@ -371,11 +341,11 @@ def test_recommend_dnn_against_the_cache_scores():
     """Early fusion: the factored ranking against ``cache.scores`` (the unfactored nrl_dkn_click_fwd) over the whole small table."""
     from newsreclib_amd import ops
     from newsreclib_amd.evaluation import DeviceNewsTable, NewsVectorCache, recommend_users
-    mod, attrs = _tiny()
+    mod, attrs = builders.tiny_dkn()
     mod.train()
     cache = NewsVectorCache(mod, DeviceNewsTable(attrs), chunk=32)
     V, B, k = 50, 6, 10
-    lists, hist, hs = _hist_batch(V)
+    lists, hist, hs = builders.hist_batch(V)[:3]
     with pytest.raises(NotImplementedError, match="dot product"):
         cache.recommend(hist.cuda(), hs, k)
     idx, score, status = cache.recommend_dnn(hist.cuda(), hs, k)
@@ -424,10 +394,10 @@ def test_recommend_dnn_against_the_cache_scores():
 
 def test_recommend_dnn_under_late_fusion_is_the_dot_product_ranking():
     from newsreclib_amd.evaluation import DeviceNewsTable, NewsVectorCache, recommend_users
-    mod, attrs = _tiny(late_fusion=True)
+    mod, attrs = builders.tiny_dkn(late_fusion=True)
     cache = NewsVectorCache(mod, DeviceNewsTable(attrs), chunk=32)
     V, B, k = 50, 6, 10
-    lists, hist, hs = _hist_batch(V)
+    lists, hist, hs = builders.hist_batch(V)[:3]
     idx, score, status = cache.recommend_dnn(hist.cuda(), hs, k)
     assert int(status) == 0 and cache.projection is None
     full = cache.scores(hist, hs, torch.arange(V).repeat(B), torch.full((B,), V)).double().cpu()
@@ -455,15 +425,15 @@ def test_recommend_dnn_under_late_fusion_is_the_dot_product_ranking():
 
 def test_recommend_dnn_does_not_synchronise_with_the_host():
     from newsreclib_amd.evaluation import DeviceNewsTable, NewsVectorCache
-    mod, attrs = _tiny()
+    mod, attrs = builders.tiny_dkn()
     cache = NewsVectorCache(mod, DeviceNewsTable(attrs), chunk=32)
     cache.build()
-    _, hist, hs = _hist_batch(50)
+    _, hist, hs = builders.hist_batch(50)[:3]
     hist = hist.cuda()                                           # the sizes stay on the host, as evaluate_impressions builds them
     torch.cuda.synchronize()
     torch.cuda.set_sync_debug_mode("error")
     try:
-        if not _sync_debug_honoured():
+        if not C.sync_debug_honoured():
             pytest.skip("this torch build does not raise on synchronising calls under set_sync_debug_mode('error')")
         idx, score, status = cache.recommend_dnn(hist, hs, 5)      # (the first call: the projection is built inside)
     finally:

@@ -19,14 +19,13 @@ import warnings
 import pytest
 import torch
 
+from tests import builders
+from tests import catalogue_ref as C
 from tests import topk_ensemble_ref as R
-from tests.test_gpu_topk import _ragged, _sync_debug_honoured
-from tests.test_gpu_topk_interests import _check_real, _rank
 
 pytestmark = pytest.mark.gpu
 
 E_EXCLUDE, E_OFFSETS, E_NAN, E_STATS = 1, 2, 4, 8
-EPS = 2.0 ** -23
 WEIGHTS = (1.0, 0.2, -0.25)
 
 
@@ -49,7 +48,7 @@ def _run(users, tables, weights, k, excl=None, eligible=None, slices=0, off=None
     from newsreclib_amd import ops
     ei = eo = None
     if excl is not None:
-        ei, eo = _ragged([list(x) for x in excl])
+        ei, eo = C.ragged([list(x) for x in excl])
         ei, eo = ei.cuda(), (off if off is not None else eo).cuda()
     idx, score, status, stats = ops.topk_ensemble_scores([u.cuda() for u in users], [t.cuda() for t in tables], list(weights), k, ei,
                                                          eo, eligible.cuda() if eligible is not None else None, slices)
@@ -60,15 +59,11 @@ def _blank(idx, score, b):
     return bool((idx[b] == -1).all()) and bool((score[b] == float("-inf")).all())
 
 
-def _bits(x):
-    return x.view(torch.int32)
-
-
 # ---- 1. statistics against float64 -----------------------------------------------------------------------------------------------------
 @functools.lru_cache(maxsize=None)
 def _stats_expected(V, D):
     users, tables, eligible, excl = R.stats_case(V, D)
-    pop = R.population(R.STATS_B, V, excl, eligible)
+    pop = C.allowed(R.STATS_B, V, excl, eligible)
     per_t = R.stats64(users, tables, pop)
     return users, tables, eligible, excl, [(n, mean, sd) + R.stat_bounds(s, bs, n, sd, pop, V) for s, bs, n, mean, sd in per_t]
 
@@ -113,14 +108,15 @@ def test_exact_ranking_of_one_table(B, V, D, k, slices):
         eligible[[0, 77, V - 1]] = 0
     s = (U.double() @ T.double().T).float()                 # exact
     assert bool((s.max(1)[0] > s.min(1)[0]).all())          # (no user's scores are all equal: every sd is positive)
-    ei, eo = _ragged(excl) if excl is not None else (None, None)
+    ei, eo = C.ragged(excl) if excl is not None else (None, None)
     cuda = lambda t: t.cuda() if t is not None else None  # noqa: E731
     for sign in (1.0, -1.0):
         want_idx, _, want_status = ops.topk_scores((sign * U).cuda(), T.cuda(), k, cuda(ei), cuda(eo), cuda(eligible))
         idx, score, status, stats = _run([U], [T], [sign], k, excl, eligible, slices)
         assert status == 0 and int(want_status) == 0
         assert torch.equal(idx, want_idx.cpu()), sign
-        assert torch.equal(idx, _rank(sign * s.double(), k, excl, eligible)[0]), sign      # (z is strictly increasing in sign * s)
+        z64 = sign * s.double()                             # (z is strictly increasing in sign * s)
+        assert torch.equal(idx, C.topk(z64, C.population(z64, excl, eligible)[0], k)[0]), sign
         mu, sd = stats[:, 0, 0:1], stats[:, 0, 1:2]
         z = sign * ((s - mu) / sd)                          # fp32, every operation rounded on its own, as the kernel
         want_score = torch.where(idx >= 0, z.gather(1, idx.clamp(min=0)), torch.full_like(z[:, :1], float("-inf")).expand_as(idx))
@@ -139,40 +135,28 @@ def test_copies_of_one_row_lead_in_ascending_row_order_with_equal_bits():
     idx, score, status, _ = _run(users, tables, WEIGHTS, k, slices=3)
     assert status == 0
     assert torch.equal(idx[:, :3], torch.tensor([5, 130, 700]).expand(B, 3))
-    assert torch.equal(_bits(score[:, 0]), _bits(score[:, 1])) and torch.equal(_bits(score[:, 0]), _bits(score[:, 2]))
+    assert torch.equal(C.bits(score[:, 0]), C.bits(score[:, 1])) and torch.equal(C.bits(score[:, 0]), C.bits(score[:, 2]))
     assert bool((score[:, 3] < score[:, 2]).all())
 
 
 # ---- 4. real values against float64 ----------------------------------------------------------------------------------------------------
-def _ensemble64(users, tables, weights, pop):
-    """float64 (B, V) ensemble scores over the population and the derived tolerance of the module docstring."""
-    V = tables[0].shape[0]
-    agg, tol, mag = 0.0, 0.0, 0.0
-    for w, (s, bs, n, mean, sd) in zip(weights, R.stats64(users, tables, pop)):
-        dmu, dsd = R.stat_bounds(s, bs, n, sd, pop, V)
-        z = (s - mean[:, None]) / sd[:, None]
-        agg = agg + w * z
-        tol = tol + abs(w) * ((bs + dmu[:, None]) / sd[:, None] + z.abs() * (dsd / sd)[:, None])
-        mag = mag + (w * z).abs()
-    return agg, tol + 8 * EPS * mag
-
-
 @functools.lru_cache(maxsize=None)
 def _real_expected(D):
     B, V = 9, 5000
     users, tables = R.real_case(31 + D, 3, B, V, D)
     g = torch.Generator().manual_seed(D)
     excl = tuple(tuple(torch.randint(0, V, (int(n),), generator=g).tolist()) for n in torch.randint(0, 51, (B,), generator=g))
-    return users, tables, excl, _ensemble64(users, tables, WEIGHTS, R.population(B, V, excl))
+    pop = C.allowed(B, V, excl)
+    return users, tables, excl, pop, R.ensemble64(users, tables, WEIGHTS, pop)
 
 
 @pytest.mark.parametrize("D", [8, 256, 768])
 def test_real_values_against_float64(D):
     k = 10
-    users, tables, excl, (agg, tol) = _real_expected(D)
+    users, tables, excl, pop, (agg, tol) = _real_expected(D)
     idx, score, status, _ = _run(users, tables, WEIGHTS, k, excl)
     assert status == 0
-    _check_real(agg, tol, idx, score, excl, k)
+    C.check_floor(idx, score, agg, tol, pop, k)
 
 
 # ---- 5. agreement with the impression scorer ---------------------------------------------------------------------------------------------
@@ -195,7 +179,7 @@ def _check_against_impression_scorer(tables, weights, lists, idx, score, scorer)
     list of user b is its whole population.  Both sides carry the derived error, so the bound is twice ``tol``."""
     B, V = len(lists), tables[0].shape[0]
     hs = torch.tensor([len(x) for x in lists])
-    pop = R.population(B, V, [x.tolist() for x in lists])
+    pop = C.allowed(B, V, [x.tolist() for x in lists])
     cand = [torch.nonzero(pop[b]).reshape(-1) for b in range(B)]
     cs = torch.tensor([len(c) for c in cand])
     out = scorer(torch.cat(cand), cs).double().cpu()
@@ -203,8 +187,8 @@ def _check_against_impression_scorer(tables, weights, lists, idx, score, scorer)
     for b in range(B):
         full[b, cand[b]] = out[b, :len(cand[b])]
     users = [u.cpu() for u in _history_means(tables, torch.cat(lists), hs)]
-    _, tol = _ensemble64(users, [t.cpu() for t in tables], weights, pop)
-    _check_real(full, 2 * tol, idx.cpu(), score.cpu(), [x.tolist() for x in lists], idx.shape[1])
+    _, tol = R.ensemble64(users, [t.cpu() for t in tables], weights, pop)
+    C.check_floor(idx.cpu(), score.cpu(), full, 2 * tol, pop, idx.shape[1])
 
 
 def test_agreement_with_the_impression_scorer():
@@ -239,8 +223,8 @@ def _status_case(seed, T=2):
 
 
 def _same_users(a, b, users):
-    return torch.equal(a[0][users], b[0][users]) and torch.equal(_bits(a[1][users]), _bits(b[1][users])) and \
-        torch.equal(_bits(a[3][users]), _bits(b[3][users]))
+    return torch.equal(a[0][users], b[0][users]) and torch.equal(C.bits(a[1][users]), C.bits(b[1][users])) and \
+        torch.equal(C.bits(a[3][users]), C.bits(b[3][users]))
 
 
 def test_status_a_population_of_one_row_blanks_that_user_alone():
@@ -289,7 +273,7 @@ def test_status_nan_table_row_is_left_out_for_every_user():
     out = _run(users, tn, WEIGHTS[:2], k, slices=2)
     assert out[2] == E_NAN
     assert not bool((out[0] == nan_row).any())
-    assert torch.equal(_bits(out[3][:, 0]), _bits(clean[3][:, 0])) and torch.equal(_bits(out[3][:, 1]), _bits(want[3][:, 1]))
+    assert torch.equal(C.bits(out[3][:, 0]), C.bits(clean[3][:, 0])) and torch.equal(C.bits(out[3][:, 1]), C.bits(want[3][:, 1]))
 
 
 def test_status_nan_in_one_users_vector_blanks_that_user_alone():
@@ -330,8 +314,8 @@ def test_invariance_and_determinism(V):
     users, tables = [u.cuda() for u in users], [t.cuda() for t in tables]
     g = torch.Generator().manual_seed(V)
     excl = [torch.randint(0, V, (int(n),), generator=g).tolist() for n in torch.randint(0, 80, (B,), generator=g)]
-    ragged = [tuple(t.cuda() for t in _ragged([x])) for x in excl]
-    ei, eo = (t.cuda() for t in _ragged(excl))
+    ragged = [tuple(t.cuda() for t in C.ragged([x])) for x in excl]
+    ei, eo = (t.cuda() for t in C.ragged(excl))
     elig = torch.ones(V, dtype=torch.uint8)
     elig[[0, 500, V - 1]] = 0
     elig = elig.cuda()
@@ -341,8 +325,8 @@ def test_invariance_and_determinism(V):
 
     def same(out, name):
         assert int(out[2]) == 0, name
-        assert torch.equal(out[0], base[0]) and torch.equal(_bits(out[1]), _bits(base[1])), name
-        assert torch.equal(_bits(out[3]), _bits(base[3])), name
+        assert torch.equal(out[0], base[0]) and torch.equal(C.bits(out[1]), C.bits(base[1])), name
+        assert torch.equal(C.bits(out[3]), C.bits(base[3])), name
 
     base = run()
     assert int(base[2]) == 0 and bool((base[0] >= 0).all())
@@ -383,12 +367,12 @@ def test_topk_ensemble_scores_does_not_synchronise_with_the_host():
     from newsreclib_amd import ops
     users, tables = _int_case(3, 3, 5, 200, 12)
     users, tables = [u.cuda() for u in users], [t.cuda() for t in tables]
-    ei, eo = _ragged([[1, 2], [], [5], [7, 7], []])
+    ei, eo = C.ragged([[1, 2], [], [5], [7, 7], []])
     ei, eo, elig = ei.cuda(), eo.cuda(), torch.ones(200, dtype=torch.bool).cuda()
     torch.cuda.synchronize()
     torch.cuda.set_sync_debug_mode("error")
     try:
-        if not _sync_debug_honoured():
+        if not C.sync_debug_honoured():
             pytest.skip("this torch build does not raise on synchronising calls under set_sync_debug_mode('error')")
         out = ops.topk_ensemble_scores(users, tables, list(WEIGHTS), 4, ei, eo, elig)
     finally:
@@ -399,10 +383,9 @@ def test_topk_ensemble_scores_does_not_synchronise_with_the_host():
 # ---- 10. wiring ------------------------------------------------------------------------------------------------------------------------------
 def test_recommend_ensemble_against_the_cache_scores(tmp_path):
     from newsreclib_amd.evaluation import MannerVectorCache, recommend_users
-    from tests.test_gpu_manner import _ensemble, _modules, _table_and_impressions
-    cr, ac, asent = _modules(tmp_path)
-    ens = _ensemble(cr, ac, asent)
-    table, imps = _table_and_impressions()
+    cr, ac, asent = builders.manner_modules(tmp_path)
+    ens = builders.manner_ensemble(cr, ac, asent)
+    table, imps = builders.manner_table_and_impressions()
     V, B, k = table.num_news, len(imps), 10
     cache = MannerVectorCache(ens, table)
     lists = [i["hist"] for i in imps]
@@ -433,7 +416,7 @@ def test_recommend_ensemble_against_the_cache_scores(tmp_path):
         recs = recommend_users(cache, users + [{"hist": torch.zeros(0, dtype=torch.int64), "user_id": 7}], k, batch_size=B + 3)
     assert recs["U7"] == {} and list(recs["U100"]) == [f"N{int(i)}" for i in idx[0]]
     # the weight-0 ensemble is the CR-Module alone (T = 1)
-    only = MannerVectorCache(_ensemble(cr, None, None, cw=0, sw=0), table)
+    only = MannerVectorCache(builders.manner_ensemble(cr, None, None, cw=0, sw=0), table)
     idx1, score1, status1, stats1 = only.recommend_ensemble(hist.cuda(), hs, k, return_stats=True)
     assert int(status1) == 0 and stats1.shape == (B, 1, 2) and only.weights == [1.0]
     _check_against_impression_scorer(only.vectors, only.weights, lists, idx1, score1,

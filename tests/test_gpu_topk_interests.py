@@ -1,11 +1,11 @@
 """Multi-interest full-catalogue top-k (``nrl_topk_interest_scores`` / ``ops.topk_interest_scores`` /
 ``NewsVectorCache.recommend_interests``): a user is K interest vectors, a table row's score their max, mean or gate-weighted sum.
 
-Expected values are computed here on the CPU in float64: ``s[b, j, v] = E64[b, j] . T64[v]``, the aggregate over j, ineligible and
-excluded positions at ``-inf``, ``torch.sort(-s, stable=True)`` = score descending with equal scores by ascending row.
+Expected values are computed on the CPU in float64: ``s[b, j, v] = E64[b, j] . T64[v]``, the aggregate over j
+(``catalogue_rank_scorers_ref.interest_scores64``), under the population and the order of ``tests/catalogue_ref.py``.
 Integer-valued vectors in [-4, 4] make every fp32 dot product exact (|s| <= 16 * 768), every sum over K <= 64 of them exact
 (< 2^24) and the division by a power of two exact, so the max cases and the mean cases with K a power of two compare with
-``torch.equal``.  Real-valued cases use derived worst cases (``_aggregate``), not measurements: with
+``torch.equal``.  Real-valued cases use derived worst cases (``interest_scores64``), not measurements: with
 ``bs_j = D 2^-23 sum_i |e_ji| |t_i|`` the error of one fp32 dot product of length D (``bl_j`` likewise from the gate),
 
   max       max_j bs_j                                     (the maximum of perturbed values moves by at most the largest perturbation)
@@ -20,13 +20,14 @@ import functools
 import pytest
 import torch
 
-from tests.test_gpu_topk import _ragged, _sync_debug_honoured
+from tests import builders
+from tests import catalogue_ref as C
+from tests.catalogue_rank_scorers_ref import interest_scores64
 
 pytestmark = pytest.mark.gpu
 
 E_EXCLUDE, E_OFFSETS, E_NAN = 1, 2, 4
 MODES = ("max", "mean", "weighted")
-EPS = 2.0 ** -23
 
 
 @pytest.fixture(autouse=True, params=["f32", "bf16x3"])
@@ -49,56 +50,11 @@ def _real_case(seed, B, K, V, D):
     return (torch.randn(B, K, D, generator=g), torch.randn(B, K, D, generator=g), torch.randn(V, D, generator=g))
 
 
-def _aggregate(E, G, T, mode):
-    """float64 (B, V) aggregated scores and the derived worst-case error of the fp32 computation (module docstring)."""
-    K, D = E.shape[1], E.shape[2]
-    s = torch.einsum("bkd,vd->bkv", E.double(), T.double())
-    bs = D * EPS * torch.einsum("bkd,vd->bkv", E.double().abs(), T.double().abs())
-    if mode == "max":
-        return s.max(dim=1)[0], bs.max(dim=1)[0]
-    if mode == "mean":
-        return s.sum(dim=1) / K, bs.max(dim=1)[0] + K * EPS * s.abs().max(dim=1)[0]
-    lg = torch.einsum("bkd,vd->bkv", G.double(), T.double())
-    bl = D * EPS * torch.einsum("bkd,vd->bkv", G.double().abs(), T.double().abs())
-    agg = (torch.softmax(lg, dim=1) * s).sum(dim=1)
-    spread = s.max(dim=1)[0] - s.min(dim=1)[0]
-    tol = bs.max(dim=1)[0] + spread * (torch.expm1(2 * bl.max(dim=1)[0]) + (K + 8) * EPS) + K * EPS * s.abs().max(dim=1)[0]
-    return agg, tol
-
-
-def _mask(agg, excl=None, eligible=None):
-    s = agg.clone()
-    V = s.shape[1]
-    if eligible is not None:
-        s[:, ~eligible.bool()] = float("-inf")
-    if excl is not None:
-        for b, rows in enumerate(excl):
-            rows = [r for r in rows if 0 <= r < V]
-            if rows:
-                s[b, torch.tensor(rows)] = float("-inf")
-    return s
-
-
-def _rank(agg, k, excl=None, eligible=None):
-    """idx (B, k) int64 and score (B, k) float32 of the exact cases; -1 / -inf where fewer than k rows qualify."""
-    s = _mask(agg, excl, eligible)
-    B, V = s.shape
-    neg, order = torch.sort(-s, dim=1, stable=True)
-    idx = torch.full((B, k), -1, dtype=torch.int64)
-    score = torch.full((B, k), float("-inf"), dtype=torch.float32)
-    n = min(k, V)
-    val = -neg[:, :n]
-    keep = val > float("-inf")
-    idx[:, :n] = torch.where(keep, order[:, :n], torch.full_like(order[:, :n], -1))
-    score[:, :n] = torch.where(keep, val, torch.full_like(val, float("-inf"))).float()
-    return idx, score
-
-
 def _run(E, G, T, k, mode, excl=None, eligible=None, slices=0, off=None):
     from newsreclib_amd import ops
     ei = eo = None
     if excl is not None:
-        ei, eo = _ragged(excl)
+        ei, eo = C.ragged(excl)
         ei, eo = ei.cuda(), (off if off is not None else eo).cuda()
     idx, score, status = ops.topk_interest_scores(E.cuda(), T.cuda(), k, mode, G.cuda() if mode == "weighted" else None, ei, eo,
                                                   eligible.cuda() if eligible is not None else None, slices)
@@ -120,7 +76,7 @@ _EXACT_MEAN = [(1, 65, 129, 300, 5, 0), (2, 33, 1000, 768, 65, 2), (4, 17, 127, 
 @functools.lru_cache(maxsize=None)
 def _exact_expected(mode, K, B, V, D, k):
     E, G, T = _int_case(K * 1000 + B * 7 + V + D + k, B, K, V, D)
-    return E, G, T, _rank(_aggregate(E, G, T, mode)[0], k)
+    return E, G, T, C.expected_topk(interest_scores64(E, T, mode, G)[0], k)
 
 
 def _check_exact(mode, K, B, V, D, k, slices):
@@ -148,7 +104,7 @@ def test_one_interest_returns_the_bits_of_topk_scores():
     E, G, T = _real_case(41, B, 1, V, D)
     g = torch.Generator().manual_seed(4)
     excl = [torch.randint(0, V, (int(n),), generator=g).tolist() for n in torch.randint(0, 51, (B,), generator=g)]
-    ei, eo = _ragged(excl)
+    ei, eo = C.ragged(excl)
     E, G, T, ei, eo = E.cuda(), G.cuda(), T.cuda(), ei.cuda(), eo.cuda()
     want_idx, want_score, want_status = ops.topk_scores(E[:, 0], T, k, ei, eo)
     assert int(want_status) == 0
@@ -166,31 +122,11 @@ def _real_expected(K, D):
     E, G, T = _real_case(K * 31 + D, B, K, V, D)
     g = torch.Generator().manual_seed(K + D)
     excl = tuple(tuple(torch.randint(0, V, (int(n),), generator=g).tolist()) for n in torch.randint(0, 51, (B,), generator=g))
-    return E, G, T, excl, {mode: _aggregate(E, G, T, mode) for mode in MODES}
+    return E, G, T, excl, {mode: interest_scores64(E, T, mode, G) for mode in MODES}
 
 
 def _check_real(agg, tol, idx, score, excl, k):
-    """Every returned score within tol of float64; rows distinct, not excluded, descending, equal scores by ascending row; no row
-    left out whose float64 score is above the floor by more than twice its tolerance."""
-    B, V = agg.shape
-    for b in range(B):
-        rows = idx[b]
-        assert bool((rows >= 0).all())
-        got = score[b].double()
-        err = (got - agg[b, rows]).abs()
-        print(f"user {b}: max |score - float64| = {float(err.max()):.3e}, tol >= {float(tol[b, rows].min()):.3e}, "
-              f"worst err / tol = {float((err / tol[b, rows]).max()):.3f}")
-        assert bool((err <= tol[b, rows]).all())
-        assert bool((got[1:] <= got[:-1]).all())
-        tie = got[1:] == got[:-1]
-        assert bool((rows[1:][tie] > rows[:-1][tie]).all())
-        assert len(set(rows.tolist())) == k and not (set(rows.tolist()) & set(excl[b]))
-        rest = torch.ones(V, dtype=torch.bool)
-        rest[rows] = False
-        if excl[b]:
-            rest[torch.tensor(sorted(set(excl[b])))] = False
-        floor = agg[b, rows].min()
-        assert bool((agg[b][rest] <= floor + 2 * tol[b][rest]).all())
+    C.check_floor(idx, score, agg, tol, C.population(agg, excl)[0], k)
 
 
 @pytest.mark.parametrize("mode", MODES)
@@ -208,31 +144,31 @@ def test_exclusion_list_longer_than_the_cached_part_and_eligibility():
     """150 exclusion entries (64 are cached in LDS), several table tiles, an eligibility mask, two users per workgroup and more."""
     B, K, V, D, k = 5, 3, 700, 8, 20
     E, G, T = _int_case(5, B, K, V, D)
-    agg = _aggregate(E, G, T, "max")[0]
+    agg = interest_scores64(E, T, "max", G)[0]
     g = torch.Generator().manual_seed(3)
     eligible = torch.ones(V, dtype=torch.uint8)
     eligible[[0, 7, 130, 699]] = 0
-    excl = [torch.randperm(V, generator=g)[:150].tolist(), [], _rank(agg, 150)[0][2].tolist(), [3, 3, 9, 3], list(range(V))]
+    excl = [torch.randperm(V, generator=g)[:150].tolist(), [], C.expected_topk(agg, 150)[0][2].tolist(), [3, 3, 9, 3], list(range(V))]
     idx, score, status = _run(E, G, T, k, "max", excl, eligible, slices=3)
-    want_idx, want_score = _rank(agg, k, excl, eligible)
+    want_idx, want_score = C.expected_topk(agg, k, excl, eligible)
     assert status == 0 and torch.equal(idx, want_idx) and torch.equal(score, want_score)
     assert torch.equal(idx[4], torch.full((k,), -1)) and bool(torch.isinf(score[4]).all())
     # mean over K = 4 (exact): the same selection code after the other aggregate
     E, G, T = _int_case(6, B, 4, V, D)
-    agg = _aggregate(E, G, T, "mean")[0]
+    agg = interest_scores64(E, T, "mean", G)[0]
     idx, score, status = _run(E, G, T, k, "mean", excl, eligible.bool(), slices=0)
-    want_idx, want_score = _rank(agg, k, excl, eligible)
+    want_idx, want_score = C.expected_topk(agg, k, excl, eligible)
     assert status == 0 and torch.equal(idx, want_idx) and torch.equal(score, want_score)
 
 
 def test_status_bad_exclusion_index_is_ignored():
     B, K, V, D, k = 4, 3, 300, 12, 6
     E, G, T = _int_case(17, B, K, V, D)
-    agg = _aggregate(E, G, T, "max")[0]
+    agg = interest_scores64(E, T, "max", G)[0]
     excl = [[1, 2], [5], [], [7, 7]]
     bad = [[-1, 1, 2], [5, V], [], [7, 7]]
     idx, score, status = _run(E, G, T, k, "max", bad)
-    want_idx, want_score = _rank(agg, k, excl)
+    want_idx, want_score = C.expected_topk(agg, k, excl)
     assert status == E_EXCLUDE
     assert torch.equal(idx, want_idx) and torch.equal(score, want_score)
 
@@ -240,12 +176,12 @@ def test_status_bad_exclusion_index_is_ignored():
 def test_status_decreasing_offsets_blank_that_user_alone():
     B, K, V, D, k = 4, 3, 300, 12, 6
     E, G, T = _int_case(18, B, K, V, D)
-    agg = _aggregate(E, G, T, "max")[0]
+    agg = interest_scores64(E, T, "max", G)[0]
     flat = list(range(12))
     off = torch.tensor([0, 5, 3, 8, 12])                    # user 1 runs backwards
     idx, score, status = _run(E, G, T, k, "max", [flat], off=off)
     assert status == E_OFFSETS
-    want_idx, want_score = _rank(agg, k, [flat[0:5], [], flat[3:8], flat[8:12]])
+    want_idx, want_score = C.expected_topk(agg, k, [flat[0:5], [], flat[3:8], flat[8:12]])
     for b in (0, 2, 3):
         assert torch.equal(idx[b], want_idx[b]) and torch.equal(score[b], want_score[b])
     assert torch.equal(idx[1], torch.full((k,), -1)) and bool((score[1] == float("-inf")).all())
@@ -269,7 +205,7 @@ def test_status_nan_table_row_is_left_out_for_every_user(mode):
     assert status == 0
     assert torch.equal(idx, want_idx) and torch.equal(score.view(torch.int32), want_score.view(torch.int32))
     if mode != "weighted":
-        ref_idx, ref_score = _rank(_aggregate(E, G, T, mode)[0], k, eligible=elig)
+        ref_idx, ref_score = C.expected_topk(interest_scores64(E, T, mode, G)[0], k, eligible=elig)
         assert torch.equal(idx, ref_idx)
         assert mode == "mean" or torch.equal(score, ref_score)
 
@@ -344,12 +280,12 @@ def test_peak_memory_is_far_below_the_score_matrix():
 def test_topk_interest_scores_does_not_synchronise_with_the_host():
     from newsreclib_amd import ops
     E, G, T = (t.cuda() for t in _int_case(3, 5, 3, 200, 12))
-    ei, eo = _ragged([[1, 2], [], [5], [7, 7], []])
+    ei, eo = C.ragged([[1, 2], [], [5], [7, 7], []])
     ei, eo, elig = ei.cuda(), eo.cuda(), torch.ones(200, dtype=torch.bool).cuda()
     torch.cuda.synchronize()
     torch.cuda.set_sync_debug_mode("error")
     try:
-        if not _sync_debug_honoured():
+        if not C.sync_debug_honoured():
             pytest.skip("this torch build does not raise on synchronising calls under set_sync_debug_mode('error')")
         outs = [ops.topk_interest_scores(E, T, 4, mode, G, ei, eo, elig) for mode in MODES]
     finally:
@@ -358,25 +294,6 @@ def test_topk_interest_scores_does_not_synchronise_with_the_host():
 
 
 # ---- 8. wiring -----------------------------------------------------------------------------------------------------------------------------
-def _miner_cache(name, score_type, tmp_path):
-    """(module, NewsVectorCache over one table row per history / candidate row of the fixture, host index lists)."""
-    from newsreclib_amd.evaluation import DeviceNewsTable, NewsVectorCache
-    from tests import miner_oracle as MO
-    from tests.helpers import load_golden
-    from tests.test_gpu_miner import _golden_module, _table_case
-    if score_type is None:
-        g, cfg, mod = _golden_module(name, tmp_path)
-    else:              # (the fixture's parameters are drawn per score type: the module is built from its configuration)
-        g = load_golden(name)
-        cfg = dict(MO.golden_cfg(g), score_type=score_type)
-        mod = MO.build_module(cfg, MO.golden_params(cfg), MO.make_body(str(tmp_path), cfg))
-    batch, title, categ = _table_case(g)
-    table = DeviceNewsTable({"title": title, "category": categ}, device="cuda")
-    B = batch["batch_size"]
-    nh = batch["batch_hist"].shape[0]
-    hs = torch.bincount(batch["batch_hist"], minlength=B)
-    return mod, cfg, NewsVectorCache(mod, table, chunk=5), torch.arange(nh), hs
-
 
 _WIRING = [("miner_tiny_no_bias", "max"), ("miner_tiny_no_bias", "mean"), ("miner_tiny_no_bias", "weighted"),
            ("miner_tiny_late_fusion", None), ("miner_tiny_eval", None)]
@@ -386,7 +303,7 @@ _WIRING = [("miner_tiny_no_bias", "max"), ("miner_tiny_no_bias", "mean"), ("mine
 def test_recommend_interests_against_the_cache_scores(name, score_type, tmp_path):
     from newsreclib_amd import ops
     from newsreclib_amd.evaluation import recommend_users
-    mod, cfg, cache, hist, hs = _miner_cache(name, score_type, tmp_path)
+    mod, cfg, cache, hist, hs = builders.miner_cache(name, score_type, tmp_path)
     mod.train()
     V, B = cache.table.num_news, int(hs.numel())
     k = min(10, V - int(hs.max()))
@@ -414,7 +331,7 @@ def test_recommend_interests_against_the_cache_scores(name, score_type, tmp_path
         mod.train()
     assert interests.shape == (B, 1 if cfg["late_fusion"] else cfg["K"], vec.shape[1])
     assert (gate is not None) == (mode == "weighted")
-    _, tol = _aggregate(interests.cpu(), gate.cpu() if gate is not None else None, vec.cpu(), mode)
+    _, tol = interest_scores64(interests.cpu(), vec.cpu(), mode, gate.cpu() if gate is not None else None)
     for b in range(B):
         rows = idx[b]
         assert bool((rows >= 0).all()) and not (set(rows.tolist()) & set(lists[b].tolist()))
@@ -441,7 +358,7 @@ def test_recommend_interests_against_the_cache_scores(name, score_type, tmp_path
 
 
 def test_recommend_interests_does_not_synchronise_with_the_host(tmp_path):
-    mod, cfg, cache, hist, hs = _miner_cache("miner_tiny_no_bias", "weighted", tmp_path)
+    mod, cfg, cache, hist, hs = builders.miner_cache("miner_tiny_no_bias", "weighted", tmp_path)
     mod.eval()
     cache.build()
     hist = hist.cuda()                                           # the sizes stay on the host, as recommend_users builds them
@@ -449,7 +366,7 @@ def test_recommend_interests_does_not_synchronise_with_the_host(tmp_path):
     torch.cuda.synchronize()
     torch.cuda.set_sync_debug_mode("error")
     try:
-        if not _sync_debug_honoured():
+        if not C.sync_debug_honoured():
             pytest.skip("this torch build does not raise on synchronising calls under set_sync_debug_mode('error')")
         idx, score, status = cache.recommend_interests(hist, hs, 5)
     finally:

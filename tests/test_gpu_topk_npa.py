@@ -7,10 +7,11 @@ weights exactly 1 / n on a peak set of n tokens and the score an integer sum ove
 user's k-th and (k + 1)-th score can be below the bound, so row sets are never compared with float64."""
 import functools
 
-import numpy as np
 import pytest
 import torch
 
+from tests import builders
+from tests import catalogue_ref as C
 from tests import topk_npa_ref as R
 
 pytestmark = pytest.mark.gpu
@@ -27,12 +28,6 @@ def engine(request):
     _lib.set_gemm_engine(prev)
 
 
-def _ragged(lists):
-    off = torch.tensor([0] + [len(x) for x in lists]).cumsum(0)
-    idx = torch.tensor([v for x in lists for v in x], dtype=torch.int64)
-    return idx, off
-
-
 @functools.lru_cache(maxsize=None)
 def _on_gpu(seed, B, V, L, F):
     """The exact case and its features on the device (uploaded once per case)."""
@@ -44,7 +39,7 @@ def _run(q, user, feat, k, excl=None, eligible=None, slices=0, off=None):
     from newsreclib_amd import ops
     ei = eo = None
     if excl is not None:
-        ei, eo = _ragged(excl)
+        ei, eo = C.ragged(excl)
         ei, eo = ei.cuda(), (off if off is not None else eo).cuda()
     idx, score, status = ops.topk_pooled_scores(q.cuda(), user.cuda(), feat.cuda(), k, ei, eo,
                                                 eligible.cuda() if eligible is not None else None, slices)
@@ -58,7 +53,7 @@ def test_exact_with_ties(L, F, k):
     """Three user tiles (the last of 2 users), eight table tiles (the last of 104 rows), every slicing; one token, F below one
     k-tile, F no multiple of 16, L no multiple of anything."""
     q, user, _, s, feat = _on_gpu(200 + L, 130, 1000, L, F)
-    want_idx, want_score = R.ranking(s, k)
+    want_idx, want_score = C.expected_topk(s, k)
     for slices in (0, 1, 2, 7):
         idx, score, status = _run(q, user, feat, k, slices=slices)
         assert status == 0, slices
@@ -79,7 +74,7 @@ def test_all_equal_scores_return_the_first_rows(slices):
 def test_fewer_rows_than_k_and_an_empty_table():
     q, user, feat, s = R.exact_case(7, 3, 5, 8, 16)
     idx, score, status = _run(q, user, feat, 8)
-    want_idx, want_score = R.ranking(s, 8)
+    want_idx, want_score = C.expected_topk(s, 8)
     assert status == 0 and torch.equal(idx, want_idx) and torch.equal(score, want_score)
     assert bool((idx[:, 5:] == -1).all()) and bool((score[:, 5:] == float("-inf")).all()) and bool((idx[:, :5] >= 0).all())
     idx, score, status = _run(q, user, feat[:0], 8)
@@ -92,7 +87,7 @@ def _excl_case():
     q, user, feat, s = R.exact_case(91, B, V, L, F)
     eligible = torch.ones(V, dtype=torch.uint8)
     eligible[[0, 7, 8, 31]] = 0
-    first = R.ranking(R.mask(s, None, eligible), k)[0][:, 0]           # every user's would-be first place
+    first = C.expected_topk(s, k, None, eligible)[0][:, 0]           # every user's would-be first place
     everything = [v for v in range(V) if eligible[v]]
     excl = [[], [3, 3, 9, 3, 9], [int(first[2]), 5], everything, [int(first[4])] * 3 + [39, 1]]
     return (q, user, feat), s, k, excl, eligible
@@ -102,7 +97,7 @@ def _excl_case():
 def test_exclusion_and_eligibility(slices):
     ops_in, s, k, excl, eligible = _excl_case()
     idx, score, status = _run(*ops_in, k, excl, eligible, slices)
-    want_idx, want_score = R.ranking(R.mask(s, excl, eligible), k)
+    want_idx, want_score = C.expected_topk(s, k, excl, eligible)
     assert status == 0
     assert torch.equal(idx, want_idx) and torch.equal(score, want_score)
     assert torch.equal(idx[3], torch.full((k,), -1)) and bool(torch.isinf(score[3]).all())
@@ -116,10 +111,10 @@ def test_exclusion_list_longer_than_the_cached_part():
     B, V, L, F, k = 3, 700, 4, 8, 20
     q, user, feat, s = R.exact_case(5, B, V, L, F)
     g = torch.Generator().manual_seed(3)
-    best = R.ranking(s, 150)[0][2].tolist()
+    best = C.expected_topk(s, 150)[0][2].tolist()
     excl = [torch.randperm(V, generator=g)[:150].tolist(), [], best + best[:40]]
     idx, score, status = _run(q, user, feat, k, excl, slices=3)
-    want_idx, want_score = R.ranking(R.mask(s, excl), k)
+    want_idx, want_score = C.expected_topk(s, k, excl)
     assert status == 0 and torch.equal(idx, want_idx) and torch.equal(score, want_score)
 
 
@@ -129,7 +124,7 @@ def test_status_bad_exclusion_index_is_ignored():
     bad[1] = [-1] + bad[1]
     bad[2] = bad[2] + [s.shape[1]]
     idx, score, status = _run(*ops_in, k, bad, eligible)
-    want_idx, want_score = R.ranking(R.mask(s, excl, eligible), k)
+    want_idx, want_score = C.expected_topk(s, k, excl, eligible)
     assert status == E_EXCLUDE
     assert torch.equal(idx, want_idx) and torch.equal(score, want_score)
 
@@ -140,7 +135,7 @@ def test_status_decreasing_offsets_blank_that_user_alone():
     off = torch.tensor([0, 5, 3, 8, 12])                    # user 1 runs backwards
     idx, score, status = _run(q, user, feat, k, [flat], off=off)
     assert status == E_OFFSETS
-    want_idx, want_score = R.ranking(R.mask(s, [flat[0:5], [], flat[3:8], flat[8:12]]), k)
+    want_idx, want_score = C.expected_topk(s, k, [flat[0:5], [], flat[3:8], flat[8:12]])
     for b in (0, 2, 3):
         assert torch.equal(idx[b], want_idx[b]) and torch.equal(score[b], want_score[b])
     assert torch.equal(idx[1], torch.full((k,), -1)) and bool((score[1] == float("-inf")).all())
@@ -151,7 +146,7 @@ def test_status_offsets_beyond_the_list():
     k = 6
     idx, score, status = _run(q, user, feat, k, [list(range(6))], off=torch.tensor([0, 2, 9, 6]))
     assert status == E_OFFSETS
-    want_idx, _ = R.ranking(R.mask(s, [[0, 1], [], []]), k)
+    want_idx, _ = C.expected_topk(s, k, [[0, 1], [], []])
     assert torch.equal(idx[0], want_idx[0])
     assert torch.equal(idx[1:], torch.full((2, k), -1))
 
@@ -163,7 +158,7 @@ def test_status_nan_row_is_left_out(where):
     B, V, L, F, k = 5, 300, 8, 16, 9
     q, user, feat, s = R.exact_case(23, B, V, L, F)
     clean_idx, clean_score, status = _run(q, user, feat, k, slices=2)
-    assert status == 0 and torch.equal(clean_idx, R.ranking(s, k)[0])
+    assert status == 0 and torch.equal(clean_idx, C.expected_topk(s, k)[0])
     in_peak = (feat[:, :, 0] > 0) | (feat[:, :, 1] > 0)     # (V, L)
     wanted = in_peak if where == "peak token" else ~in_peak
     nan_row = next(int(r) for r in clean_idx[0] if bool(wanted[int(r)].any()))      # a row that would be returned
@@ -175,7 +170,7 @@ def test_status_nan_row_is_left_out(where):
     assert not bool((idx == nan_row).any())
     elig = torch.ones(V, dtype=torch.uint8)
     elig[nan_row] = 0
-    want_idx, want_score = R.ranking(R.mask(s, None, elig), k)          # every other position unchanged
+    want_idx, want_score = C.expected_topk(s, k, None, elig)          # every other position unchanged
     assert torch.equal(idx, want_idx) and torch.equal(score, want_score)
     # not eligible: nobody is told
     idx, score, status = _run(q, user, fn, k, eligible=elig, slices=2)
@@ -190,26 +185,10 @@ def test_real_values_against_float64():
     rows = idx.clamp(min=0)
     ratio = ((score.double() - c["raw"].gather(1, rows)).abs() / c["bound"].gather(1, rows)).max(dim=1)[0]
     print("max |score - float64| / bound per user: " + " ".join(f"{float(x):.1e}" for x in ratio))
-    R.check_floor(idx, score, c["raw"], c["bound"], R.mask(c["raw"], c["excl"]), c["excl"], k)
+    C.check_floor(idx, score, c["raw"], c["bound"], C.population(c["raw"], c["excl"])[0], k)
 
 
 # ---- 5. agreement with the existing scorer ------------------------------------------------------------------------------------------
-def _tiny(late_fusion=False, n_news=50, L=6, F_=8):
-    """(NPAModule in eval mode, DeviceNewsTable) from the synthetic builders of the NPA tests."""
-    from newsreclib_amd.evaluation import DeviceNewsTable
-    from tests import npa_oracle as NO
-    vocab, n_users = 60, 9
-    cfg = dict(vocab=vocab, n_users=n_users, D=12, U=6, F=F_, W=3, Pw=8, Pn=8, late_fusion=late_fusion)
-    params = NO.make_npa_params(vocab, n_users, 12, 6, F_, 3, 8, 8, late_fusion=late_fusion, seed=4)
-    titles = torch.randint(1, vocab, (n_news, L), generator=torch.Generator().manual_seed(104))
-    return NO.build_module(cfg, params).eval(), DeviceNewsTable({"title": titles})
-
-
-def _hist_batch(n_news, B=6, seed=3, sizes=None):
-    rng = np.random.default_rng(seed)
-    sizes = rng.integers(1, 9, B) if sizes is None else sizes
-    hist = [torch.from_numpy(rng.choice(np.arange(1, n_news), int(n), replace=False)) for n in sizes]
-    return hist, torch.cat(hist), torch.tensor([len(h) for h in hist])
 
 
 def _cached_side_bound(cache, user, q_cand):
@@ -231,11 +210,11 @@ def _cached_side_bound(cache, user, q_cand):
 def test_recommend_pooled_against_the_cache_scores(late_fusion):
     """The fused ranking against ``cache.scores`` (nrl_npa_cached_scores: pooled vectors, then dot products) with the whole small
     table as every user's candidate list."""
-    mod, table = _tiny(late_fusion)
+    mod, table = builders.tiny_npa(late_fusion)
     mod.train()
     cache = mod.feature_cache(table, chunk=32)
     V, B, k = 50, 6, 10
-    lists, hist, hs = _hist_batch(V)
+    lists, hist, hs = builders.hist_batch(V)[:3]
     uidx = torch.tensor([3, 1, 4, 1, 5, 8])
     with pytest.raises(NotImplementedError, match="depend on the user"):
         cache.recommend(hist.cuda(), hs, k)
@@ -276,10 +255,10 @@ def test_recommend_users_routes_an_npa_cache_to_recommend_pooled():
     """Users of equal history length, so the batch's longest history (the ``max_hist`` quirk) cannot differ between batchings:
     identical dictionaries for two batches (the second partial) and for one."""
     from newsreclib_amd.evaluation import recommend_users
-    mod, table = _tiny()
+    mod, table = builders.tiny_npa()
     cache = mod.feature_cache(table)
     V, B, k = 50, 6, 10
-    lists, hist, hs = _hist_batch(V, sizes=[4] * B)
+    lists, hist, hs = builders.hist_batch(V, sizes=[4] * B)[:3]
     uidx = torch.tensor([3, 1, 4, 1, 5, 8])
     idx, score, status = cache.recommend_pooled(hist.cuda(), hs, k, user_idx=uidx)
     assert int(status) == 0
@@ -344,24 +323,16 @@ def test_peak_memory_is_far_below_one_logit_tensor():
 
 
 # ---- 8. no read-back ---------------------------------------------------------------------------------------------------------------------
-def _sync_debug_honoured():
-    try:
-        float(torch.ones(1, device="cuda").sum())
-    except RuntimeError:
-        return True
-    return False
-
-
 def test_topk_pooled_scores_does_not_synchronise_with_the_host():
     from newsreclib_amd import ops
     q, user, feat, _ = R.exact_case(3, 5, 200, 8, 16)
     q, user, feat = q.cuda(), user.cuda(), feat.cuda()
-    ei, eo = _ragged([[1, 2], [], [5], [7, 7], []])
+    ei, eo = C.ragged([[1, 2], [], [5], [7, 7], []])
     ei, eo, elig = ei.cuda(), eo.cuda(), torch.ones(200, dtype=torch.uint8).cuda()
     torch.cuda.synchronize()
     torch.cuda.set_sync_debug_mode("error")
     try:
-        if not _sync_debug_honoured():
+        if not C.sync_debug_honoured():
             pytest.skip("this torch build does not raise on synchronising calls under set_sync_debug_mode('error')")
         idx, score, status = ops.topk_pooled_scores(q, user, feat, 4, ei, eo, elig)
     finally:
@@ -370,15 +341,15 @@ def test_topk_pooled_scores_does_not_synchronise_with_the_host():
 
 
 def test_recommend_pooled_does_not_synchronise_with_the_host():
-    mod, table = _tiny()
+    mod, table = builders.tiny_npa()
     cache = mod.feature_cache(table)
     cache.build()
-    _, hist, hs = _hist_batch(50)
+    _, hist, hs = builders.hist_batch(50)[:3]
     hist, uidx = hist.cuda(), torch.tensor([3, 1, 4, 1, 5, 8]).cuda()      # the sizes stay on the host
     torch.cuda.synchronize()
     torch.cuda.set_sync_debug_mode("error")
     try:
-        if not _sync_debug_honoured():
+        if not C.sync_debug_honoured():
             pytest.skip("this torch build does not raise on synchronising calls under set_sync_debug_mode('error')")
         idx, score, status = cache.recommend_pooled(hist, hs, 5, user_idx=uidx)
     finally:

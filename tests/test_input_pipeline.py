@@ -2,46 +2,12 @@
 dataset + collate (oracle/input_oracle.py) on hand-made known-answer data.  CPU-only (the pipeline is index
 plumbing on torch tensors; the GPU tier runs it on the device in tests/test_gpu_eval.py)."""
 import numpy as np
-import pandas as pd
 import pytest
 import torch
 
 from newsreclib_amd import input_pipeline as IP
 from oracle import input_oracle as IO
-
-ATTRS = ["title", "abstract", "category", "sentiment_class"]
-
-
-def make_frames(n_news=40, n_imp=23, seed=0):
-    rng = np.random.default_rng(seed)
-    nids = [f"N{int(i)}" for i in rng.permutation(np.arange(1000, 1000 + n_news))]
-    news = pd.DataFrame({
-        "tokenized_title": [list(rng.integers(1, 500, rng.integers(0, 9))) for _ in nids],     # some empty, some > max
-        "tokenized_abstract": [list(rng.integers(1, 500, rng.integers(1, 14))) for _ in nids],
-        "category_class": rng.integers(0, 18, n_news), "subcategory_class": rng.integers(0, 200, n_news),
-        "sentiment_class": rng.integers(0, 3, n_news), "sentiment_score": rng.random(n_news).astype(np.float32),
-    }, index=nids)
-    rows = []
-    for i in range(n_imp):
-        nc = int(rng.integers(2, 12))
-        labels = np.zeros(nc, dtype=np.int64)
-        labels[rng.choice(nc, int(rng.integers(1, max(2, nc // 3 + 1))), replace=False)] = 1
-        if labels.all():
-            labels[0] = 0
-        rows.append({"uid": f"U{int(rng.integers(1, 99999))}", "user": int(rng.integers(0, 50)),
-                     "history": list(rng.choice(nids, int(rng.integers(1, 9)))),
-                     "candidates": list(rng.choice(nids, nc, replace=False)), "labels": list(labels)})
-    return news, pd.DataFrame(rows)
-
-
-def assert_batches_equal(a, b):
-    assert set(a) >= {"batch_hist", "batch_cand", "x_hist", "x_cand", "labels", "user_ids", "user_idx"}
-    for k in ("batch_hist", "batch_cand", "labels", "user_ids", "user_idx"):
-        assert a[k].dtype == b[k].dtype and torch.equal(a[k].cpu(), b[k]), k
-    for part in ("x_hist", "x_cand"):
-        assert set(a[part]) == set(b[part]), (part, set(a[part]), set(b[part]))
-        for k in b[part]:
-            assert a[part][k].dtype == b[part][k].dtype and torch.equal(a[part][k].cpu(), b[part][k]), (part, k)
+from tests.builders import ATTRS, assert_batches_equal, make_frames
 
 
 def test_pad_token_lists_known_answers():

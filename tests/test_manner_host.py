@@ -9,44 +9,15 @@ import pytest
 import torch
 
 from tests import manner_oracle as MO
-from tests.helpers import PLM_HEADS, PLM_Q, make_tiny_roberta
+from tests.builders import MANNER_D as D, MANNER_DE as DE, N_ENT, a_kwargs, cr_kwargs, entity_table
+from tests.helpers import make_tiny_roberta
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
-D, DE, N_ENT = 96, 96, 40          # (entity heads of 96 / 6 = 16: a head width the attention kernels have)
 
 
 def _contract():
     with open(os.path.join(GOLDEN, "manner_contract.json")) as f:
         return json.load(f)
-
-
-def common_kwargs(plm_path, use_entities=True, p_drop=0.2):
-    return dict(dataset_attributes=["title", "abstract", "title_entities", "abstract_entities", "category", "sentiment"],
-                attributes2encode=["title", "abstract", "title_entities", "abstract_entities"] if use_entities
-                else ["title", "abstract"],
-                plm_model=plm_path, frozen_layers=[0], text_embed_dim=D, num_heads=PLM_HEADS, query_dim=PLM_Q,
-                dropout_probability=p_drop, use_entities=use_entities, pretrained_entity_embeddings_path="",
-                entity_embed_dim=DE, optimizer=None, scheduler=None)
-
-
-def cr_kwargs(plm_path, loss="cross_entropy_loss", late_fusion=False, **kw):
-    out = common_kwargs(plm_path, **kw)
-    out.update(outputs={"train": ["preds", "targets", "cand_news_size"], "val": ["preds", "targets", "cand_news_size"],
-                        "test": ["preds", "targets", "cand_news_size", "hist_news_size"]},
-               loss=loss, late_fusion=late_fusion, temperature=0.36, top_k_list=[5, 10], num_categ_classes=18,
-               num_sent_classes=3, save_recs=False, recs_fpath=None)
-    return out
-
-
-def a_kwargs(plm_path, temperature=0.9, **kw):
-    out = common_kwargs(plm_path, **kw)
-    out.update(outputs={"val": ["embeddings", "labels"], "test": ["embeddings", "labels"]}, temperature=temperature,
-               labels_path="")
-    return out
-
-
-def entity_table(seed=3):
-    return torch.randn(N_ENT, DE, generator=torch.Generator().manual_seed(seed))
 
 
 def test_constructor_kwargs_match_reference():

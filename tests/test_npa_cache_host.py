@@ -2,7 +2,7 @@
 import pytest
 import torch
 
-from tests.test_npa_host import _module
+from tests import builders
 
 
 def _table():
@@ -18,7 +18,7 @@ def test_npa_feature_cache_refuses_other_modules():
 
 def test_npa_feature_cache_requires_user_idx():
     """raised before the table is encoded: the CPU table would fail the kernels' device check with a RuntimeError"""
-    cache = _module().feature_cache(_table())
+    cache = builders.npa_contract_module().feature_cache(_table())
     sizes = torch.tensor([1, 1])
     with pytest.raises(ValueError):
         cache.scores(torch.tensor([0, 1]), sizes, torch.tensor([2, 3]), sizes, None)
@@ -30,4 +30,4 @@ def test_npa_feature_cache_requires_user_idx():
 def test_news_vector_cache_still_refuses_npa_and_names_the_feature_cache():
     from newsreclib_amd.evaluation import NewsVectorCache
     with pytest.raises(NotImplementedError, match="NpaFeatureCache"):
-        NewsVectorCache(_module(), _table()).build()
+        NewsVectorCache(builders.npa_contract_module(), _table()).build()

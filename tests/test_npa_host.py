@@ -1,36 +1,10 @@
 """NPA drop-in contract on the host: constructor, state-dict keys and shapes against the reference
 (tests/golden/npa_contract.json), the window-size restriction, and the encode-once cache's refusal."""
-import json
-import os
-
 import pytest
 import torch
 
+from tests import builders
 from tests import npa_oracle as NO
-
-GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
-
-
-def _contract():
-    with open(os.path.join(GOLDEN, "npa_contract.json")) as f:
-        return json.load(f)
-
-
-def _module(**over):
-    c = _contract()["config"]
-    cfg = dict(vocab=c["vocab"], n_users=c["num_users"] + 1, D=c["text_embed_dim"], U=c["user_embed_dim"],
-               F=c["num_filters"], W=c["window_size"], Pw=c["word_pref_query_dim"], Pn=c["news_pref_query_dim"],
-               late_fusion=False)
-    from newsreclib_amd.npa_module import NPAModule
-    kw = dict(outputs={"train": [], "val": [], "test": []}, dual_loss_training=False, dual_loss_coef=None,
-              loss="cross_entropy_loss", late_fusion=False, temperature=None, pretrained_embeddings_path=None,
-              text_embed_dim=cfg["D"], user_embed_dim=cfg["U"], num_users=c["num_users"], num_filters=cfg["F"],
-              window_size=cfg["W"], word_pref_query_dim=cfg["Pw"], news_pref_query_dim=cfg["Pn"],
-              dropout_probability=0.2, top_k_list=[5, 10], num_categ_classes=18, num_sent_classes=3, save_recs=False,
-              recs_fpath=None, optimizer=None, scheduler=None,
-              pretrained_embeddings=torch.zeros(cfg["vocab"], cfg["D"]))
-    kw.update(over)
-    return NPAModule(**kw)
 
 
 def test_npa_module_kwargs_match_reference():
@@ -38,31 +12,31 @@ def test_npa_module_kwargs_match_reference():
 
     from newsreclib_amd.npa_module import NPAModule
     ours = [p for p in inspect.signature(NPAModule.__init__).parameters if p != "self"]
-    assert ours[:-1] == _contract()["init_kwargs"]
+    assert ours[:-1] == builders.npa_contract()["init_kwargs"]
     assert ours[-1] == "pretrained_embeddings"
-    assert set(_contract()["init_kwargs"]) >= set(_contract()["yaml_keys"]) - {"_target_"}
+    assert set(builders.npa_contract()["init_kwargs"]) >= set(builders.npa_contract()["yaml_keys"]) - {"_target_"}
 
 
 def test_npa_state_dict_matches_reference():
-    mod = _module()
+    mod = builders.npa_contract_module()
     got = {k: list(v.shape) for k, v in mod.state_dict().items()}
-    assert got == _contract()["state_dict"]
+    assert got == builders.npa_contract()["state_dict"]
     assert float(mod.user_projection.user_embed.detach().min()) >= 0.0     # torch.rand, as projection.py:40
 
 
 def test_npa_late_fusion_has_no_user_encoder():
-    mod = _module(late_fusion=True)
+    mod = builders.npa_contract_module(late_fusion=True)
     assert not any(k.startswith("user_encoder.") for k in mod.state_dict())
 
 
 def test_npa_window_size_other_than_3_raises():
     with pytest.raises(NotImplementedError):
-        _module(window_size=5)
+        builders.npa_contract_module(window_size=5)
 
 
 def test_news_vector_cache_refuses_npa():
     from newsreclib_amd.evaluation import DeviceNewsTable, NewsVectorCache
-    mod = _module()
+    mod = builders.npa_contract_module()
     table = DeviceNewsTable({"title": torch.ones(4, 6, dtype=torch.int64)}, device="cpu")   # refused before any device work
     with pytest.raises(NotImplementedError):
         NewsVectorCache(mod, table).build()

@@ -1,6 +1,6 @@
 """CPU tier of the class-biased full-catalogue top-k and rank: the ABI (header against ``_lib.SIGNATURES``), the limits and the
 flag, the markers of the modules, the refusals that come before any device work, and the properties of the float64
-restatement (``tests/topk_bias_ref.py``) the GPU tests compare against."""
+scores (``tests/topk_bias_ref.py``) under the shared contract (``tests/catalogue_ref.py``) the GPU tests compare against."""
 import os
 import re
 from types import SimpleNamespace
@@ -9,7 +9,9 @@ import numpy as np
 import pytest
 import torch
 
+from tests import catalogue_ref as C
 from tests import topk_bias_ref as R
+from tests import topk_capped_ref
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAMES = ("nrl_topk_bias_scores", "nrl_topk_bias_scores_capped", "nrl_catalogue_bias_ranks")
@@ -162,20 +164,21 @@ def _case(rng):
 
 
 def test_a_zero_bias_is_the_plain_reference():
-    from tests.test_gpu_topk import _reference
+    """``topk_bias_ref.scores`` with a zero bias is ``U @ T.T`` whatever the class ids, so the shared order over it returns the
+    plain dot-product lists (the order itself is pinned in test_catalogue_ref_host.py), and a bad class id adds nothing."""
     rng = np.random.default_rng(40)
     for _ in range(500):
         U, T, bias, cls, excl, elig, k = _case(rng)
         s, flags = R.scores(U, T, np.zeros_like(bias), cls)
         assert flags == (R.E_CLASS if ((cls < 0) | (cls >= bias.shape[1])).any() else 0)
-        pop, nan = R.population(s, excl, elig)
-        idx, score = R.topk(s, pop, k)
-        want_idx, want_score = _reference(torch.from_numpy(U), torch.from_numpy(T), k, excl, torch.from_numpy(elig))
-        assert nan == 0 and np.array_equal(idx, want_idx.numpy()) and np.array_equal(score, want_score.numpy())
+        pop, nan = C.population(s, excl, elig)
+        idx, score = C.topk(s, pop, k)
+        want_idx, want_score = C.expected_topk(torch.from_numpy(U) @ torch.from_numpy(T).T, k, excl, elig)
+        assert not nan and torch.equal(idx, want_idx) and torch.equal(score, want_score)
         # a bad class id adds nothing: the scores with the bias differ from the plain ones only in the good columns
         sb, _ = R.scores(U, T, bias, cls)
         bad = (cls < 0) | (cls >= bias.shape[1])
-        assert np.array_equal(sb[:, bad], s[:, bad])
+        assert torch.equal(sb[:, bad], s[:, bad])
 
 
 def test_ranks_are_consistent_with_the_lists():
@@ -186,26 +189,26 @@ def test_ranks_are_consistent_with_the_lists():
         if rng.random() < 0.2:
             bias[0, 0] = np.nan                         # a NaN bias drops that class for that user
         s, _ = R.scores(U, T, bias, cls)
-        pop, nan = R.population(s, excl, elig)
-        assert (nan == R.E_NAN) == bool((np.isnan(s) & ~pop & (elig.astype(bool))[None, :]
-                                         & np.array([[v not in excl[b] for v in range(V)] for b in range(B)])).any())
-        idx, score = R.topk(s, pop, k)
+        pop, nan = C.population(s, excl, elig)
+        assert nan == bool((torch.isnan(s) & ~pop & torch.from_numpy(elig.astype(bool))[None, :]
+                            & torch.tensor([[v not in excl[b] for v in range(V)] for b in range(B)])).any())
+        idx, score = C.topk(s, pop, k)
         targets = [rng.integers(-1, V + 1, int(rng.integers(0, 4))).tolist() for _ in range(B)]
-        rank, tscore, ranked = R.ranks(s, pop, targets)
-        assert np.array_equal(ranked, (idx >= 0).sum(1)) or k < V
+        rank, tscore, ranked = C.ranks(s, pop, targets)
+        assert torch.equal(ranked, (idx >= 0).sum(1).to(torch.int32)) or k < V
         j = 0
         for b in range(B):
             assert int(ranked[b]) == int(pop[b].sum())
             for r in targets[b]:
-                listed = np.nonzero((idx[b] == r) & (idx[b] >= 0))[0]
+                listed = torch.nonzero((idx[b] == r) & (idx[b] >= 0)).reshape(-1)
                 if rank[j] == 0:
-                    assert listed.size == 0 and tscore[j] == -np.inf
+                    assert listed.numel() == 0 and tscore[j] == -np.inf
                 elif rank[j] <= k:
-                    assert listed.size == 1 and int(listed[0]) == rank[j] - 1 and score[b, rank[j] - 1] == tscore[j]
+                    assert listed.numel() == 1 and int(listed[0]) == rank[j] - 1 and score[b, rank[j] - 1] == tscore[j]
                 else:
-                    assert listed.size == 0
+                    assert listed.numel() == 0
                 j += 1
         # the capped walk with m >= k is the uncapped list
         kc = min(k, 64)
-        c_idx, c_score = R.capped(s, pop, cls * 3, kc, kc)
-        assert np.array_equal(c_idx, idx[:, :kc]) and np.array_equal(c_score, score[:, :kc])
+        c_idx, c_score = topk_capped_ref.reference(s, pop, torch.from_numpy(cls * 3), kc, kc)
+        assert torch.equal(c_idx, idx[:, :kc]) and torch.equal(c_score, score[:, :kc])

@@ -72,7 +72,7 @@ def test_tensor_reference_is_the_greedy_definition():
     s[0, 5:40] = float("-inf")
     s[1, 7] = float("nan")
     cls = torch.randint(0, 5, (V,), generator=g)
-    idx, score = R.reference(s, cls, k, m)
+    idx, score = R.reference(s, torch.isfinite(s), cls, k, m)
     for b in range(B):
         row = [None if (x != x or x == float("-inf")) else x for x in s[b].tolist()]
         want = R.greedy(row, cls.tolist(), k, m)

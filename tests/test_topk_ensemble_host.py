@@ -10,6 +10,7 @@ import subprocess
 import pytest
 import torch
 
+from tests import catalogue_ref as C
 from tests import topk_ensemble_ref as R
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -114,7 +115,7 @@ def test_fp32_statistics_in_the_prescribed_order_stay_inside_the_derived_bound(V
     """The tile -> chunk -> user order of the kernels, emulated in fp32 on the CPU over the inputs of the GPU statistics test,
     against float64: inside the bound those tests use, and the bound is below 1 % of sd, so it cannot be vacuous."""
     users, tables, eligible, excl = R.stats_case(V, D)
-    pop = R.population(R.STATS_B, V, excl, eligible)
+    pop = C.allowed(R.STATS_B, V, excl, eligible)
     worst = 0.0
     for t, (s, bs, n, mean, sd) in enumerate(R.stats64(users, tables, pop)):
         dmu, dsd = R.stat_bounds(s, bs, n, sd, pop, V)

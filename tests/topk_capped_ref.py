@@ -9,10 +9,12 @@ share, all on the CPU:
   worst entry at ``w`` (63 when the class is not full) and the one lane-select that shifts the positions ``pos .. w``.
   Positions from ``k`` on hold what fell off and are masked out of every count.
 * ``stream`` / ``merge``: a list fed in any order, and the slices' first ``k`` positions fed into a fresh list.
-* ``reference``: ``greedy`` over a (B, V) float64 score matrix with the rows that may not be returned at ``-inf`` (or NaN), as
-  (idx (B, k) int64, score (B, k) float32) with ``-1`` / ``-inf`` where the walk runs out.
+* ``reference``: ``greedy`` over a (B, V) float64 score matrix and its population, in the order of ``tests/catalogue_ref.py``,
+  as (idx (B, k) int64, score (B, k) float32) with ``-1`` / ``-inf`` where the walk runs out.
 """
 import torch
+
+from tests import catalogue_ref as C
 
 LANES = 64
 
@@ -85,28 +87,9 @@ def merge(lists, scores, classes, k, m):
     return out
 
 
-def reference(s, row_class, k, m):
-    """``greedy`` over s (B, V) float64 (-inf or NaN: may not be returned) -> idx (B, k) int64, score (B, k) float32"""
-    B, V = s.shape
-    idx = torch.full((B, k), -1, dtype=torch.int64)
-    score = torch.full((B, k), float("-inf"), dtype=torch.float32)
-    if V == 0:
-        return idx, score
-    s = torch.where(torch.isnan(s), torch.full_like(s, float("-inf")), s)
-    neg, order = torch.sort(-s, dim=1, stable=True)
-    cls = [int(c) for c in row_class.tolist()]
-    neg, order = neg.tolist(), order.tolist()
-    for b in range(B):
-        taken, n = {}, 0
-        for val, v in zip(neg[b], order[b]):
-            if n == k or val == float("inf"):
-                break
-            c = cls[v]
-            if taken.get(c, 0) < m:
-                taken[c] = taken.get(c, 0) + 1
-                idx[b, n], score[b, n] = v, -val
-                n += 1
-    return idx, score
+def reference(s, pop, row_class, k, m):
+    """``greedy`` over s (B, V) float64 and the population ``pop`` -> idx (B, k) int64, score (B, k) float32"""
+    return walk_listed(*C.topk(s, pop, s.shape[1]), row_class, k, m)[:2]
 
 
 def walk_listed(idx, score, row_class, k, m):
@@ -129,5 +112,5 @@ def walk_listed(idx, score, row_class, k, m):
                 taken[c] = taken.get(c, 0) + 1
                 out_idx[b, n], out_score[b, n] = v, score[b, j]
                 n += 1
-        decided = decided and (n == k or rows[-1] < 0)
+        decided = decided and (n == k or not rows or rows[-1] < 0)
     return out_idx, out_score, decided

@@ -1,5 +1,5 @@
 """Shared by test_topk_dnn_host.py and test_gpu_topk_dnn.py: the inputs of the real-value case, the float64 value of DKN's
-factored click score and its derived fp32 error bound, and the masked float64 ranking the exact cases compare with.
+factored click score and its derived fp32 error bound.  Population, order and the floor check are ``tests/catalogue_ref.py``'s.
 
 The factored score: with ``pred_w1 = [Wc | Wu]``, ``P = T Wc^T`` (V, Hd) and ``q = U Wu^T + b1`` (B, Hd),
 
@@ -103,56 +103,3 @@ def relu_scores64(q, proj, w2, b2):
     """(B, V) float64 scores from q (B, Hd), proj (V, Hd): exact for the small-integer cases."""
     h = torch.relu(proj.double()[None, :, :] + q.double()[:, None, :])
     return h @ w2.double().reshape(-1) + b2.double().reshape(())
-
-
-def mask(s, excl=None, eligible=None):
-    """The positions that may not be returned at -inf (a copy)."""
-    s = s.clone()
-    V = s.shape[1]
-    if eligible is not None:
-        s[:, ~eligible.bool()] = float("-inf")
-    if excl is not None:
-        for b, rows in enumerate(excl):
-            rows = [r for r in rows if 0 <= r < V]
-            if rows:
-                s[b, torch.tensor(rows)] = float("-inf")
-    return s
-
-
-def ranking(s, k):
-    """idx (B, k) int64 and score (B, k) float32 of masked float64 scores: descending, equal scores by ascending row, -1 / -inf
-    where fewer than k rows qualify."""
-    B, V = s.shape
-    neg, order = torch.sort(-s, dim=1, stable=True) if V else (s, torch.empty((B, 0), dtype=torch.int64))
-    idx = torch.full((B, k), -1, dtype=torch.int64)
-    score = torch.full((B, k), float("-inf"), dtype=torch.float32)
-    n = min(k, V)
-    if n:
-        val = -neg[:, :n]
-        keep = val > float("-inf")
-        idx[:, :n] = torch.where(keep, order[:, :n], torch.full_like(order[:, :n], -1))
-        score[:, :n] = torch.where(keep, val, torch.full_like(val, float("-inf"))).float()
-    return idx, score
-
-
-def check_floor(idx, score, raw, bound, masked, excl, k):
-    """The floor form of a real-value comparison: the gap between the k-th and the (k + 1)-th score can be below the bound, so row
-    sets are never compared.  Every returned score is within the bound of float64, the order is descending with ties by
-    ascending row, no excluded row is returned, and no left-out row that may be returned exceeds the k-th by more than twice the
-    bound."""
-    B, V = raw.shape
-    for b in range(B):
-        rows = idx[b]
-        assert bool((rows >= 0).all()), b
-        got = score[b].double()
-        err = (got - raw[b, rows]).abs()
-        print(f"user {b}: max |score - float64| = {float(err.max()):.3e}, bound >= {float(bound[b, rows].min()):.3e}")
-        assert bool((err <= bound[b, rows]).all()), b
-        assert bool((got[1:] <= got[:-1]).all()), b
-        tie = got[1:] == got[:-1]
-        assert bool((rows[1:][tie] > rows[:-1][tie]).all()), b
-        assert len(set(rows.tolist())) == k and not (set(rows.tolist()) & set(excl[b])), b
-        rest = torch.ones(V, dtype=torch.bool)
-        rest[rows] = False
-        rest &= masked[b] > float("-inf")
-        assert bool((masked[b][rest] <= raw[b, rows].min() + 2 * bound[b][rest]).all()), b

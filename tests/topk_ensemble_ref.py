@@ -27,6 +27,8 @@ import functools
 
 import torch
 
+from tests import catalogue_ref as C
+
 EPS = 2.0 ** -23
 BV, STAT_CHUNKS = 128, 64
 STATS_V, STATS_D = (2, 127, 128, 129, 1000, 8200), (4, 300, 768)
@@ -62,26 +64,12 @@ def stats_case(V, D):
     return users, tables, eligible, tuple(tuple(x) for x in excl)
 
 
-def population(B, V, excl=None, eligible=None):
-    """(B, V) bool: the rows user b may be recommended."""
-    pop = torch.ones(B, V, dtype=torch.bool)
-    if eligible is not None:
-        pop &= eligible.bool()[None, :]
-    if excl is not None:
-        for b, rows in enumerate(excl):
-            rows = sorted({r for r in rows if 0 <= r < V})
-            if rows:
-                pop[b, torch.tensor(rows)] = False
-    return pop
-
-
 def stats64(users, tables, pop):
     """Per table t: float64 scores s (B, V), bs (B, V), and over the population n (B), mean (B), unbiased sd (B)."""
     out = []
-    D = users[0].shape[1]
     for U, Tb in zip(users, tables):
         s = U.double() @ Tb.double().T
-        bs = D * EPS * (U.double().abs() @ Tb.double().abs().T)
+        bs = C.dot_bound(U, Tb)
         n = pop.sum(1).double()
         mean = (s * pop).sum(1) / n
         sd = (((s - mean[:, None]) ** 2 * pop).sum(1) / (n - 1)).sqrt()
@@ -100,6 +88,21 @@ def stat_bounds(s, bs, n, sd, pop, V):
     dmu = (bs * pop).sum(1) / n + r
     dsd = (bs + neg).max(1)[0] * q + sd * (3 * L + 4) * EPS + 3 * r * q
     return dmu, dsd
+
+
+def ensemble64(users, tables, weights, pop):
+    """float64 (B, V) ensemble scores over the population and their derived tolerance:
+
+      tol[v] = sum_t |w_t| ((bs_t[v] + dmu_t) / sd_t + |z_t[v]| dsd_t / sd_t) + 8 EPS sum_t |w_t z_t[v]|"""
+    V = tables[0].shape[0]
+    agg, tol, mag = 0.0, 0.0, 0.0
+    for w, (s, bs, n, mean, sd) in zip(weights, stats64(users, tables, pop)):
+        dmu, dsd = stat_bounds(s, bs, n, sd, pop, V)
+        z = (s - mean[:, None]) / sd[:, None]
+        agg = agg + w * z
+        tol = tol + abs(w) * ((bs + dmu[:, None]) / sd[:, None] + z.abs() * (dsd / sd)[:, None])
+        mag = mag + (w * z).abs()
+    return agg, tol + 8 * EPS * mag
 
 
 def _wave_sum(v):

@@ -1,6 +1,6 @@
 """Shared by test_topk_npa_host.py and test_gpu_topk_npa.py: the float64 value of NPA's personalized-pooling score over cached
-feature maps, its derived fp32 error bound, an fp32 emulation on the CPU, and the two input families.  ``mask`` / ``ranking`` /
-``check_floor`` are those of tests/topk_dnn_ref.py.
+feature maps, its derived fp32 error bound, an fp32 emulation on the CPU, and the two input families.  Population, order and the
+floor check are ``tests/catalogue_ref.py``'s.
 
 The score: with ``c`` (V, L, F) the feature maps, ``q`` (B, F) the users' text queries and ``user`` (B, F) the user vectors,
 
@@ -33,8 +33,6 @@ dominates: the exact value of U_EXP decides no assertion."""
 import functools
 
 import torch
-
-from tests.topk_dnn_ref import check_floor, mask, ranking  # noqa: F401  (re-exported: the tests take them from here)
 
 EPS = 2.0 ** -23
 U_EXP = 4
