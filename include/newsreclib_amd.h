@@ -1245,6 +1245,56 @@ int nrl_mmr_rerank(const int64_t* pool_idx, const float* pool_score, const float
                    int32_t k, float lambda, int32_t similarity, int32_t normalize, int64_t* out_idx, float* out_score,
                    float* out_mmr, int32_t* status, void* stream);
 
+/* nrl_calibrated_rerank (symbol added to ABI v19): greedy re-ranking of a pool by relevance, MMR's redundancy penalty and a class
+ *   calibration term: how close the class counts of the list come to a per-user class target (calibrated recommendation, Steck
+ *   2018, with the generalised Jaccard overlap that Personalization@k measures as the closeness).
+ *   Inputs: pool_idx (B, N) int64, pool_score (B, N) fp32, table (V, D) fp32, k, lambda, similarity, normalize as for
+ *     nrl_mmr_rerank; row_class (V) int32 the class of every table row; target (B, S) fp32 the users' class targets; mu, gamma fp32.
+ *   Limits: 1 <= k <= N <= NRL_MMR_MAX_POOL; 1 <= S <= NRL_CAL_MAX_CLASSES = 64; lambda, mu, gamma each in [0, 1] and not NaN;
+ *     with mu != 0, D as for nrl_mmr_rerank.
+ *   Live slots, rel_i (normalize 0 / 1), the Gram matrix G, sim (cosine / dot), the tie order (equal obj: the lower slot) and the
+ *     NaN order (a NaN obj ranks below every number) are word for word those of nrl_mmr_rerank, with its flags NRL_MMR_E_ROW (1)
+ *     and NRL_TOPK_E_NAN (4).
+ *   mu == 0: no Gram matrix is computed, table may be null and is never read, D and similarity are neither checked nor used (V
+ *     still bounds the rows), the launch needs no tile LDS, and pen_i is +0 at every step.  A slot is then dead only for a row
+ *     outside [0, V) or a non-finite score: there is no Gram diagonal to be non-finite.
+ *   Class of a slot: class_i = row_class[row_i] for a live slot.  Outside [0, S), negative ids included, the slot stays live, its
+ *     calibration term is +0, it counts for no class and NRL_TOPK_E_CLASS (64) is ORed into status.
+ *   Target: t_j = target[u][j] where that is finite and >= 0; otherwise t_j = +0 and NRL_CAL_E_TARGET (128) is ORed.
+ *   Calibration term: with n_j the number of already selected slots of class j (an integer <= k, exact in fp32), for a class c
+ *     M_c = sum_j min(n_j + [j == c], t_j), X_c = sum_j max(n_j + [j == c], t_j), each sum a chain of single fp32 additions in
+ *     ascending j = 0 ... S - 1 from +0, and cal_c = fl(M_c / X_c), one correctly rounded division.  X_c >= 1, so nothing divides
+ *     by zero, and 0 <= cal_c <= 1.  cal_c is the Personalization value of the list after adding a slot of class c.
+ *   Greedy steps t = 0 ... k - 1, pen as in nrl_mmr_rerank (+0 before anything is selected, the true maximum of sim afterwards):
+ *     obj_i = fl( fl( fl(lambda * rel_i) - fl(mu * pen_i) ) + fl(gamma * cal_{class_i}) ), every operation one correctly rounded
+ *     fp32 operation, none contracted to an fma.  The step selects the live, unselected slot of largest obj.
+ *   Outputs: out_idx (B, k) int64 the row; out_score (B, k) fp32 that slot's pool_score, bits unchanged; out_obj (B, k) fp32 the
+ *     winning obj; out_cal (B, k) fp32 the winner's calibration term (+0 for a class outside [0, S)); -1 / -inf / -inf / -inf once
+ *     the live slots run out.  status (one int32, required): integer atomicOr only.  No workspace, no float atomics, no
+ *     allocation, no host synchronisation.
+ *   Properties:
+ *     1. The result for k is a prefix of the result for k' > k.
+ *     2. Nothing depends on B, on the user's place in the batch, on the GEMM engine setting or on the run.
+ *     3. With gamma = 0 and mu = fl(1 - lambda) the rows and scores are those of nrl_mmr_rerank(lambda) and out_obj compares equal
+ *        to its out_mmr (a -0 there may be +0 here).  At lambda = 1 that is the mu == 0 form, which computes no Gram matrix: the
+ *        statement then needs a pool whose Gram matrix is finite.
+ *     4. With gamma = 0, mu = 0, lambda = 1, normalize = 0 the output is the pool's live slots in (score descending, slot
+ *        ascending) order, and out_obj compares equal to out_score.
+ *     5. For a user who raised no flag and whose list is full, out_cal[u][k - 1] has the bits of
+ *        fl( sum_j min(cnt_j, t_j) / sum_j max(cnt_j, t_j) ) over the class counts cnt of the k listed slots (the sums as above).
+ *        With the integer class counts of the user's history as the target that is Personalization@k of the list.
+ *   Checks, in this order, each NRL_E_INVALID before any launch: negative sizes (B, N, V, S, k); N outside [1, 128]; k outside
+ *     [1, N]; S outside [1, 64]; V, B outside the limits of nrl_topk_scores; lambda, then mu, then gamma outside [0, 1] or NaN;
+ *     normalize outside {0, 1}; with mu != 0 only: D outside the limits of nrl_topk_scores, then similarity outside {0, 1}; a null
+ *     status.  B == 0 returns success without a launch.  After that, null pointers among the rest return NRL_E_INVALID;
+ *     row_class may be null only when V == 0, table only when V == 0 or mu == 0. */
+#define NRL_CAL_MAX_CLASSES 64
+#define NRL_CAL_E_TARGET 128 /* a target entry is negative, NaN or infinite: it is taken as +0 */
+int nrl_calibrated_rerank(const int64_t* pool_idx, const float* pool_score, const float* table, int64_t B, int32_t N, int64_t V,
+                          int32_t D, const int32_t* row_class, const float* target, int32_t S, int32_t k, float lambda, float mu,
+                          float gamma, int32_t similarity, int32_t normalize, int64_t* out_idx, float* out_score, float* out_obj,
+                          float* out_cal, int32_t* status, void* stream);
+
 /* nrl_topk_relu_scores: the same ranking by DKN's DNN click predictor (click_predictor.py:14-45: Linear(2 dim, Hd) -> ReLU ->
  *   Linear(Hd, 1) on [cand; user]) with the candidate list replaced by the table.  The first layer splits by columns,
  *   pred_w1 = [Wc | Wu], so with q (B, Hd) = user Wu^T + b1 (nrl_dkn_user_query) and proj (V, Hd) = table Wc^T

@@ -39,6 +39,7 @@
 // No float atomics, no allocation, no host read-back; the workspace holds the partial lists, O(B * slices * k), or the counts.
 // Behind the walk kernels, mmr_rerank_kernel (nrl_mmr_rerank) re-ranks a pool any of the top-k entries returned by greedy MMR: it is
 // no walk (one workgroup per user, the pool's Gram matrix by tk_tile_accumulate<1, true>, then k steps) and needs no workspace.
+// cal_rerank_kernel (nrl_calibrated_rerank) is that kernel with a class-calibration term; its mu == 0 form has no Gram stage.
 #include <math.h>
 
 #include "nrl_common.h"
@@ -2080,6 +2081,246 @@ __global__ __launch_bounds__(TK_THREADS) void mmr_rerank_kernel(MmrArgs A) {
   }
 }
 
+// ---- calibrated greedy re-ranking of a pool (nrl_calibrated_rerank) ----------------------------------------------------------------
+// mmr_rerank_kernel's workgroup (one per user, thread i owns slot i) with a third term in the objective: gamma times the
+// Personalization value the list would have after adding a slot of class c, cal_c.  GRAM = false is the mu == 0 form: no Gram
+// matrix, no tile LDS, the table is never read.  Dynamic LDS, behind the `halves` Gram tiles of the GRAM form:
+//   wk[2][4] u64     the waves' best entries of a step, double-buffered by the step's parity
+//   rows[128] i64    the slots' table rows (the Gram stage gathers by them)
+//   rn[128] f32      1 / sqrt(G[i][i])
+//   cls[128] i32     the slots' classes, -1 where the slot is dead or its class is outside [0, S)
+//   tgt[64] f32      the user's target with the refused entries as +0
+//   cnt[2][64] f32   n_j, one copy per wave that owns slots;  cal[2][64] f32  cal_c, likewise
+// Only waves 0 and 1 own slots (N <= 128).  Each keeps the class state for itself: lane j holds n_j in a register and stores it
+// to its wave's cnt row, lane c < S sums its two chains over broadcast reads of cnt and tgt (every lane the same word: no
+// conflict) and stores cal_c, lane i reads cal[class_i].  A wave's LDS operations complete in order, so inside one wave these
+// stores and reads need a compiler fence and no barrier; the redundant copy costs no time, the two waves run side by side.  That
+// leaves ONE barrier a step, the one that publishes the waves' best entries, as in mmr_rerank_kernel.  The winner's thread
+// writes the step's outputs from its own registers, so there is no objs array.  The gathered read cal[class_i] is a ds_read_b32:
+// lanes of one 32-lane half conflict when their classes differ by 32 (same class: a broadcast), so it is conflict-free for
+// S <= 32 and at worst 2-way above.
+constexpr int CAL_MAX_CLASSES = NRL_CAL_MAX_CLASSES;
+constexpr int CAL_SLOT_WAVES = MMR_MAX_POOL / 64;
+constexpr size_t CAL_SLOT_BYTES = 2 * 4 * 8 + (size_t)MMR_MAX_POOL * (8 + 4 + 4) + (size_t)CAL_MAX_CLASSES * 4 * (1 + 2 * CAL_SLOT_WAVES);
+constexpr size_t cal_lds_bytes(int halves) { return (size_t)halves * TK_TILE_BYTES + CAL_SLOT_BYTES; }
+static_assert(CAL_MAX_CLASSES == 64, "lane j of a wave owns class j");
+static_assert(2 * cal_lds_bytes(2) <= 160 * 1024, "two workgroups of the largest layout fit a CU");
+
+struct CalArgs {
+  const int64_t* pool_idx;
+  const float* pool_score;
+  const float* table;
+  int32_t N, D, k;
+  int64_t V;
+  const int32_t* row_class;
+  const float* target;
+  int32_t S;
+  float lambda, mu, gamma;
+  int32_t similarity, normalize;
+  int64_t* out_idx;
+  float* out_score;
+  float* out_obj;
+  float* out_cal;
+  int32_t* status;
+};
+
+__device__ __forceinline__ float cal_add(float a, float b) {
+#pragma clang fp contract(off)
+  return a + b;
+}
+
+template <bool GRAM>
+__global__ __launch_bounds__(TK_THREADS) void cal_rerank_kernel(CalArgs A) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char tk_smem[];
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int N = A.N, k = A.k, S = A.S;
+  const int halves = GRAM ? (N + TK_BU - 1) / TK_BU : 0;
+  const int64_t u = blockIdx.x;
+  float* const sim = reinterpret_cast<float*>(tk_smem);
+  unsigned long long* const wk = reinterpret_cast<unsigned long long*>(tk_smem + (size_t)halves * TK_TILE_BYTES);
+  int64_t* const rows = reinterpret_cast<int64_t*>(wk + 8);
+  float* const rn = reinterpret_cast<float*>(rows + MMR_MAX_POOL);
+  int32_t* const cls = reinterpret_cast<int32_t*>(rn + MMR_MAX_POOL);
+  float* const tgt = reinterpret_cast<float*>(cls + MMR_MAX_POOL);
+  float* const cnt = tgt + CAL_MAX_CLASSES;
+  float* const cal = cnt + CAL_SLOT_WAVES * CAL_MAX_CLASSES;
+  const int64_t* const pool = A.pool_idx + u * N;
+
+  // the slots: thread i owns slot i; the target: thread j its entry j
+  bool live = false;
+  float score = 0.f;
+  int64_t row = -1;
+  int flags = 0;
+  if (tid < MMR_MAX_POOL) {
+    if (tid < N) {
+      row = pool[tid];
+      score = A.pool_score[u * N + tid];
+    }
+    const bool row_ok = row >= 0 && row < A.V;
+    const bool fin = fabsf(score) < INFINITY;
+    if (row != -1 && !row_ok) flags |= NRL_MMR_E_ROW;
+    if (row_ok && !fin) flags |= NRL_TOPK_E_NAN;
+    live = row_ok && fin;
+    rows[tid] = live ? row : -1;
+    rn[tid] = 0.f;
+  }
+  if (tid < CAL_MAX_CLASSES) {
+    float g = 0.f;
+    if (tid < S) {
+      g = A.target[u * S + tid];
+      if (!(fabsf(g) < INFINITY && g >= 0.f)) {
+        g = 0.f;
+        flags |= NRL_CAL_E_TARGET;
+      }
+    }
+    tgt[tid] = g;
+  }
+  __syncthreads();
+
+  if (GRAM) {
+    // the Gram matrix, as in mmr_rerank_kernel
+    if (A.V > 0) {
+      for (int h = 0; h < halves; ++h) {
+        const int64_t ar = rows[h * TK_BU + (tid >> 2)];                      // (-1: an empty, bad or non-finite slot)
+        const bool ua_ok = ar >= 0;
+        const float* const pa[1] = {A.table + (ua_ok ? ar : 0) * A.D};
+        float* const tile = sim + h * TK_BU * TK_SCLD;
+        tk_f32x4 acc[1][2][4];
+        tk_tile_accumulate<1, true>(pa, ua_ok, A.table, A.D, 0, N, A.D, tile, acc, pool, A.V);
+        tk_store_fragments(acc[0], tile);
+        __syncthreads();
+      }
+    }
+    // the diagonal: a slot whose own product is not finite is dead; r
+    if (tid < N && live) {
+      const float g = sim[tid * TK_SCLD + tid];
+      if (!(fabsf(g) < INFINITY)) {
+        live = false;
+        flags |= NRL_TOPK_E_NAN;
+      } else {
+        rn[tid] = g == 0.f ? 0.f : mmr_div(1.f, __builtin_sqrtf(g));
+      }
+    }
+  }
+  // the class of a live slot
+  int cl = -1;
+  if (live) {
+    cl = A.row_class[row];
+    if (cl < 0 || cl >= S) {
+      cl = -1;
+      flags |= NRL_TOPK_E_CLASS;
+    }
+  }
+  if (tid < MMR_MAX_POOL) cls[tid] = cl;
+  {
+    int f = flags;
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) f |= __shfl_xor(f, off, 64);
+    if (f && lane == 0) atomicOr(A.status, f);
+  }
+  // relevance: the extremes of the live scores as keys (-0 counts as +0), through the waves' slots of wk
+  const uint32_t key = score_key(score);
+  if (A.normalize) {
+    uint32_t lo = live ? key : 0xFFFFFFFFu, hi = live ? key : 0u;
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+      const uint32_t l2 = (uint32_t)__shfl_xor((int)lo, off, 64), h2 = (uint32_t)__shfl_xor((int)hi, off, 64);
+      lo = l2 < lo ? l2 : lo;
+      hi = h2 > hi ? h2 : hi;
+    }
+    if (lane == 0) wk[wave] = ((unsigned long long)hi << 32) | lo;
+  }
+  __syncthreads();                                    // publishes rn, cls and the extremes
+  float rel = score;
+  if (A.normalize) {
+    uint32_t lo = 0xFFFFFFFFu, hi = 0u;
+#pragma unroll
+    for (int w = 0; w < TK_THREADS / 64; ++w) {
+      const unsigned long long e = wk[w];
+      const uint32_t l2 = (uint32_t)e, h2 = (uint32_t)(e >> 32);
+      lo = l2 < lo ? l2 : lo;
+      hi = h2 > hi ? h2 : hi;
+    }
+    if (hi == lo || hi == 0u) {
+      rel = 0.f;
+    } else {
+      const float s_min = tk_unkey(lo), s_max = tk_unkey(hi);
+      rel = mmr_div(mmr_sub(score, s_min), mmr_sub(s_max, s_min));
+    }
+  }
+  if (GRAM && A.similarity == 0) {
+    for (int e = tid; e < N * TK_BV; e += TK_THREADS) {
+      const int i = e / TK_BV, j = e % TK_BV;
+      float* const p = sim + i * TK_SCLD + j;
+      *p = mmr_mul(*p, mmr_mul(rn[i], rn[j]));
+    }
+  }
+  __syncthreads();                                    // sim is final; wk is free for the steps
+
+  const float lrel = mmr_mul(A.lambda, rel);
+  const bool slot_wave = wave < CAL_SLOT_WAVES && wave * 64 < N;           // (uniform: this wave owns slots)
+  float* const my_cnt = cnt + (wave & (CAL_SLOT_WAVES - 1)) * CAL_MAX_CLASSES;
+  float* const my_cal = cal + (wave & (CAL_SLOT_WAVES - 1)) * CAL_MAX_CLASSES;
+  float pen = 0.f, nj = 0.f;
+  bool sel = false;
+  int c = -1, t = 0;
+  for (; t < k; ++t) {
+    if (t > 0) {
+      if (GRAM) {
+        const float s = tid < N ? sim[c * TK_SCLD + tid] : 0.f;
+        pen = t == 1 ? s : fmaxf(pen, s);
+      }
+      if (lane == cls[c]) nj += 1.f;                  // (cls[c] == -1: the winner counts for no class)
+    }
+    float calv = 0.f;
+    if (slot_wave) {
+      my_cnt[lane] = nj;
+      __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+      if (lane < S) {
+        float m = 0.f, x = 0.f;
+        for (int j = 0; j < S; ++j) {
+          const float n1 = my_cnt[j] + (j == lane ? 1.f : 0.f), g = tgt[j];
+          m = cal_add(m, fminf(n1, g));
+          x = cal_add(x, fmaxf(n1, g));
+        }
+        my_cal[lane] = mmr_div(m, x);
+      }
+      __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+      if (cl >= 0) calv = my_cal[cl];
+      __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    }
+    const float obj = cal_add(mmr_sub(lrel, mmr_mul(A.mu, pen)), mmr_mul(A.gamma, calv));
+    unsigned long long e = 0ull;
+    if (live && !sel) e = obj != obj ? ((1ull << 32) | (uint32_t)~(uint32_t)tid) : tk_entry(obj, (uint32_t)tid);
+    e = mmr_wave_max(e, lane);
+    const int par = t & 1;
+    if (lane == 0) wk[par * 4 + wave] = e;
+    __syncthreads();
+    unsigned long long best = wk[par * 4];
+#pragma unroll
+    for (int w = 1; w < TK_THREADS / 64; ++w) {
+      const unsigned long long y = wk[par * 4 + w];
+      best = y > best ? y : best;
+    }
+    if (best == 0ull) break;                          // the live slots have run out (uniform)
+    c = (int)~(uint32_t)best;
+    if (tid == c) {
+      sel = true;
+      A.out_idx[u * k + t] = row;
+      A.out_score[u * k + t] = score;
+      A.out_obj[u * k + t] = obj;
+      A.out_cal[u * k + t] = calv;
+    }
+  }
+  for (int p = t + tid; p < k; p += TK_THREADS) {
+    A.out_idx[u * k + p] = -1;
+    A.out_score[u * k + p] = -INFINITY;
+    A.out_obj[u * k + p] = -INFINITY;
+    A.out_cal[u * k + p] = -INFINITY;
+  }
+}
+
 static bool tk_shape_ok(int64_t B, int64_t V, int32_t D, int32_t k) {
   return B >= 0 && V >= 0 && V < ((int64_t)1 << 31) && D > 0 && D % 4 == 0 && D <= NRL_TOPK_MAX_D && k >= 1 && k <= NRL_TOPK_MAX_K;
 }
@@ -2716,6 +2957,48 @@ int nrl_mmr_rerank(const int64_t* pool_idx, const float* pool_score, const float
   if (smem > 64 * 1024)
     NRL_HIP(hipFuncSetAttribute((const void*)mmr_rerank_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
   mmr_rerank_kernel<<<(unsigned)B, TK_THREADS, smem, (hipStream_t)stream>>>(A);
+  NRL_LAUNCH_CHECK();
+  return NRL_OK;
+}
+
+// ---- nrl_calibrated_rerank (header: semantics) -------------------------------------------------------------------------------------
+int nrl_calibrated_rerank(const int64_t* pool_idx, const float* pool_score, const float* table, int64_t B, int32_t N, int64_t V,
+                          int32_t D, const int32_t* row_class, const float* target, int32_t S, int32_t k, float lambda, float mu,
+                          float gamma, int32_t similarity, int32_t normalize, int64_t* out_idx, float* out_score, float* out_obj,
+                          float* out_cal, int32_t* status, void* stream) {
+  NRL_REQUIRE(B >= 0 && N >= 0 && V >= 0 && S >= 0 && k >= 0, "calibrated_rerank: negative size");
+  NRL_REQUIRE(N >= 1 && N <= NRL_MMR_MAX_POOL, "calibrated_rerank: N in [1, %d] (got %d)", NRL_MMR_MAX_POOL, N);
+  NRL_REQUIRE(k >= 1 && k <= N, "calibrated_rerank: k in [1, N = %d] (got %d)", N, k);
+  NRL_REQUIRE(S >= 1 && S <= NRL_CAL_MAX_CLASSES, "calibrated_rerank: S in [1, %d] (got %d)", NRL_CAL_MAX_CLASSES, S);
+  NRL_REQUIRE(V < ((int64_t)1 << 31), "calibrated_rerank: at most 2^31 - 1 table rows (got %lld)", (long long)V);
+  NRL_REQUIRE(B < ((int64_t)1 << 31), "calibrated_rerank: at most 2^31 - 1 users per call (got %lld)", (long long)B);
+  NRL_REQUIRE(lambda >= 0.f && lambda <= 1.f, "calibrated_rerank: lambda in [0, 1] (got %g)", (double)lambda);
+  NRL_REQUIRE(mu >= 0.f && mu <= 1.f, "calibrated_rerank: mu in [0, 1] (got %g)", (double)mu);
+  NRL_REQUIRE(gamma >= 0.f && gamma <= 1.f, "calibrated_rerank: gamma in [0, 1] (got %g)", (double)gamma);
+  NRL_REQUIRE(normalize == 0 || normalize == 1, "calibrated_rerank: normalize in {0, 1} (got %d)", normalize);
+  const bool gram = mu != 0.f;
+  if (gram) {
+    NRL_REQUIRE(D > 0 && D % 4 == 0 && D <= NRL_TOPK_MAX_D, "calibrated_rerank: with mu != 0, D a multiple of 4 in [4, %d] (got %d)",
+                NRL_TOPK_MAX_D, D);
+    NRL_REQUIRE(similarity == 0 || similarity == 1, "calibrated_rerank: with mu != 0, similarity (0 cosine, 1 dot) in {0, 1} (got %d)",
+                similarity);
+  }
+  NRL_REQUIRE(status, "calibrated_rerank: the status word is required");
+  if (B == 0) return NRL_OK;
+  NRL_REQUIRE(pool_idx && pool_score && target && out_idx && out_score && out_obj && out_cal && (V == 0 || row_class) &&
+                  (V == 0 || !gram || table),
+              "calibrated_rerank: null argument");
+  const CalArgs A{pool_idx, pool_score, table,     N,          D,       k,         V,       row_class, target, S,
+                  lambda,   mu,         gamma,     similarity, normalize, out_idx, out_score, out_obj, out_cal, status};
+  if (gram) {
+    const size_t smem = cal_lds_bytes((N + TK_BU - 1) / TK_BU);
+    // more than 64 KB of dynamic LDS needs the attribute; it belongs to the current device, so it is set per call
+    if (smem > 64 * 1024)
+      NRL_HIP(hipFuncSetAttribute((const void*)cal_rerank_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    cal_rerank_kernel<true><<<(unsigned)B, TK_THREADS, smem, (hipStream_t)stream>>>(A);
+  } else {
+    cal_rerank_kernel<false><<<(unsigned)B, TK_THREADS, cal_lds_bytes(0), (hipStream_t)stream>>>(A);
+  }
   NRL_LAUNCH_CHECK();
   return NRL_OK;
 }

@@ -441,6 +441,22 @@ class NewsVectorCache(_ImpressionCache):
         return ops.mmr_rerank(pool_idx, pool_score, self.vectors, k, lam, similarity, normalize)
 
     @torch.no_grad()
+    def rerank_calibrated(self, pool_idx: torch.Tensor, pool_score: torch.Tensor, k: int, aspect: str, target: torch.Tensor,
+                          lam: float, mu: float, gamma: float, similarity: str = "cosine", normalize: bool = True):
+        """Calibrated greedy re-ranking of a pool any ``recommend*`` of this cache returned -> (news_idx (B, k) int64, scores
+        (B, k) fp32: the pool's own, obj (B, k) fp32, cal (B, k) fp32, status: ``ops.CAL_FLAGS``): ``ops.calibrated_rerank`` with
+        the table's ``aspect`` column as the classes and ``target`` (B, S) fp32 (``ops.class_targets``) as the class mix to pull
+        the list towards.  ``mu != 0`` adds MMR's penalty by the cached news vectors, built when they are missing; ``mu == 0``
+        touches no vectors.  Nothing is read back."""
+        table = None
+        if float(mu) != 0.0:
+            if self.vectors is None:
+                self.build()
+            table = self.vectors
+        return ops.calibrated_rerank(pool_idx, pool_score, table, _aspect_classes(self, aspect), target, k, lam, mu, gamma, similarity,
+                                     normalize)
+
+    @torch.no_grad()
     def rank_clicks(self, hist_idx: torch.Tensor, hist_sizes: torch.Tensor, click_idx: torch.Tensor, click_sizes: torch.Tensor,
                     user_idx: Optional[torch.Tensor] = None, exclude_history: bool = True,
                     eligible: Optional[torch.Tensor] = None):
@@ -603,6 +619,19 @@ class MannerVectorCache(_ImpressionCache):
             self.build()
         return ops.mmr_rerank(pool_idx, pool_score, self.vectors[submodel], k, lam, similarity, normalize)
 
+    @torch.no_grad()
+    def rerank_calibrated(self, pool_idx: torch.Tensor, pool_score: torch.Tensor, k: int, aspect: str, target: torch.Tensor,
+                          lam: float, mu: float, gamma: float, similarity: str = "cosine", normalize: bool = True, which: int = 0):
+        """``NewsVectorCache.rerank_calibrated`` of a pool ``recommend_ensemble*`` returned; with ``mu != 0`` the similarity is
+        taken in the table of sub-model ``which``, as ``rerank_diverse`` takes it in that of ``submodel``."""
+        table = None
+        if float(mu) != 0.0:
+            if self.vectors is None:
+                self.build()
+            table = self.vectors[which]
+        return ops.calibrated_rerank(pool_idx, pool_score, table, _aspect_classes(self, aspect), target, k, lam, mu, gamma, similarity,
+                                     normalize)
+
     def _ensemble_users(self, who: str, hist_idx, hist_sizes, user_idx, exclude_history: bool, eligible, clicks):
         """The user side of ``recommend_ensemble`` and ``rank_clicks_ensemble`` (``who``): the caller's side of the call checked and
         on the device (``_catalogue_side``) -> (the user matrix of every sub-model: the mean of the gathered history rows of its
@@ -662,6 +691,7 @@ class NpaFeatureCache(_ImpressionCache):
         self.module, self.table, self.chunk = module, table, int(chunk)
         self.features: Optional[torch.Tensor] = None
         self.engine: Optional[str] = None
+        self._row_class: Dict[str, torch.Tensor] = {}       # aspect -> (num_news) int32: ``rerank_calibrated``'s classes
 
     @torch.no_grad()
     def build(self) -> torch.Tensor:
@@ -712,6 +742,18 @@ class NpaFeatureCache(_ImpressionCache):
         raise NotImplementedError("MMR trades relevance against the similarity of two news vectors, and an NPA news vector depends "
                                   "on the user (personalized attention pooling, text.py:385-390): the cache holds feature maps, not "
                                   "a (V, D) table of news vectors to take that similarity in")
+
+    @torch.no_grad()
+    def rerank_calibrated(self, pool_idx: torch.Tensor, pool_score: torch.Tensor, k: int, aspect: str, target: torch.Tensor,
+                          lam: float, mu: float, gamma: float, similarity: str = "cosine", normalize: bool = True):
+        """``NewsVectorCache.rerank_calibrated`` of a pool ``recommend_pooled`` returned, without a table: calibration needs the
+        classes of the news, not their vectors.  ``ValueError`` unless ``mu == 0``: the redundancy penalty is what
+        ``rerank_diverse`` refuses."""
+        if float(mu) != 0.0:
+            raise ValueError("NpaFeatureCache.rerank_calibrated serves mu == 0 only: the penalty mu weighs is a similarity of news "
+                             "vectors, and an NPA news vector depends on the user (`rerank_diverse` says why)")
+        return ops.calibrated_rerank(pool_idx, pool_score, None, _aspect_classes(self, aspect), target, k, lam, 0.0, gamma, similarity,
+                                     normalize)
 
     @torch.no_grad()
     def recommend_pooled(self, hist_idx: torch.Tensor, hist_sizes: torch.Tensor, k: int, user_idx: Optional[torch.Tensor] = None,
@@ -821,7 +863,7 @@ def format_recommendations(user_ids: Sequence, news_idx: torch.Tensor, scores: t
 
 def recommend_users(cache: NewsVectorCache, users: Sequence[Dict], k: int, batch_size: int = 512,
                     eligible: Optional[torch.Tensor] = None, cap: Optional[Tuple[str, int]] = None,
-                    diversify: Optional[Tuple[int, float]] = None) -> Dict[str, Dict[str, float]]:
+                    diversify: Optional[Tuple[int, float]] = None, calibrate: Optional[Dict] = None) -> Dict[str, Dict[str, float]]:
     """``cache.recommend`` (``cache.recommend_interests`` where the cache's module is a ``multi_interest_scorer``,
     ``cache.recommend_dnn`` where it is a ``dnn_predictor_scorer``, ``cache.recommend_pooled`` where it is a
     ``personalized_pooling_scorer``: ``NpaFeatureCache``, whose users need ``user_idx``,
@@ -839,7 +881,32 @@ def recommend_users(cache: NewsVectorCache, users: Sequence[Dict], k: int, batch
     ops.MMR_MAX_POOL``; under ``cap`` at most ``ops.TOPK_CAP_MAX_K``) and ``cache.rerank_diverse(idx, score, k, lam)`` -- greedy
     MMR by the cosine of the cached news vectors, the relevance min-max scaled -- picks the ``k`` that are listed, in its order,
     with the scores the scorer gave them.  Its status word (``ops.MMR_FLAGS``) is OR-ed into the batch's on the device, 16 bits
-    up, so there is still one device-to-host copy per batch.  ``None`` is the path without it, launch for launch."""
+    up, so there is still one device-to-host copy per batch.  ``None`` is the path without it, launch for launch.
+
+    ``calibrate`` = dict(pool=, aspect=, gamma=, lam=1.0, mu=0.0, target="history" | "proportional"): the method picked above
+    returns each user's ``pool`` best news and ``cache.rerank_calibrated`` picks the ``k`` that are listed, pulling the list's
+    mix of the classes of the table's ``aspect`` column towards the user's own with weight ``gamma``.  The target is
+    ``ops.class_targets`` of the batch's histories over ``ops.CAL_MAX_CLASSES`` classes (no read-back is needed to count them;
+    a class id beyond is flagged): the integer class counts (``"history"``, the default: the term is the list's
+    Personalization@k) or the class proportions times ``k`` (``"proportional"``).  ``mu`` adds MMR's penalty, so ``calibrate``
+    together with ``diversify`` is a ``ValueError``; an ``NpaFeatureCache`` is served with ``mu == 0``.  The status word
+    (``ops.CAL_FLAGS``) is OR-ed in 16 bits up like ``diversify``'s.  ``None`` is the path without it, launch for launch."""
+    if calibrate is not None:
+        if diversify is not None:
+            raise ValueError("recommend_users: `calibrate` and `diversify` exclude each other; calibrate=dict(..., mu=...) is MMR's "
+                             "penalty beside the calibration term")
+        unknown = set(calibrate) - {"pool", "aspect", "gamma", "lam", "mu", "target"}
+        if unknown or not {"pool", "aspect", "gamma"} <= set(calibrate):
+            raise ValueError("recommend_users(calibrate=dict(pool=, aspect=, gamma=, lam=1.0, mu=0.0, target=\"history\")): got "
+                             f"{sorted(calibrate)}")
+        pool, cal_aspect, cal_how = int(calibrate["pool"]), calibrate["aspect"], calibrate.get("target", "history")
+        cal_weights = (float(calibrate.get("lam", 1.0)), float(calibrate.get("mu", 0.0)), float(calibrate["gamma"]))
+        if pool < k:
+            raise ValueError(f"recommend_users(calibrate=dict(pool=...)): the pool ({pool}) must hold at least k = {k} news")
+        if cal_how not in ("history", "proportional"):
+            raise ValueError(f"recommend_users(calibrate=dict(target=...)): \"history\" or \"proportional\", got {cal_how!r}")
+        if getattr(cache.module, "personalized_pooling_scorer", False) and cal_weights[1] != 0.0:
+            cache.rerank_calibrated(None, None, k, cal_aspect, None, *cal_weights)      # (NpaFeatureCache: refuses and says why)
     if diversify is not None:
         pool, lam = int(diversify[0]), float(diversify[1])
         if pool < k:
@@ -873,16 +940,22 @@ def recommend_users(cache: NewsVectorCache, users: Sequence[Dict], k: int, batch
         elif cap is not None:
             capped = getattr(cache, "recommend_ensemble_capped", None) or cache.recommend_capped
             rank = lambda hist, hs, k, **kw: capped(hist, hs, k, aspect, max_per_class, **kw)  # noqa: E731
-        idx, score, status = rank(hist, hs, k if diversify is None else pool, user_idx=uidx, eligible=eligible)
+        idx, score, status = rank(hist, hs, k if diversify is None and calibrate is None else pool, user_idx=uidx, eligible=eligible)
         if diversify is not None:
             idx, score, _, mmr_status = cache.rerank_diverse(idx, score, k, lam)
             status = status | (mmr_status << 16)
+        if calibrate is not None:
+            target = ops.class_targets(hist, _click_offsets(hs.long(), dev), _aspect_classes(cache, cal_aspect), ops.CAL_MAX_CLASSES,
+                                       k if cal_how == "proportional" else None)
+            idx, score, _, _, cal_status = cache.rerank_calibrated(idx, score, k, cal_aspect, target, *cal_weights)
+            status = status | (cal_status << 16)
         packed = torch.cat([idx.double(), score.double(), status.double().expand(idx.shape[0], 1)], dim=1).cpu()      # the one copy
         word = int(packed[0, -1]) if packed.shape[0] else 0
         if word:                                            # the kernel has dealt with each of these; the caller should know
             import warnings
             flags = ops.TOPK_BIAS_FLAGS if biased else ops.TOPK_FLAGS
-            said = [msg for bit, msg in flags.items() if word & bit] + [msg for bit, msg in ops.MMR_FLAGS.items() if (word >> 16) & bit]
+            second = ops.CAL_FLAGS if calibrate is not None else ops.MMR_FLAGS
+            said = [msg for bit, msg in flags.items() if word & bit] + [msg for bit, msg in second.items() if (word >> 16) & bit]
             warnings.warn("recommend_users: " + "; ".join(said))
         ids = [int(u["user_id"]) if "user_id" in u else lo + j + 1 for j, u in enumerate(chunk)]
         out.update(format_recommendations(ids, packed[:, :k].long(), packed[:, k:2 * k].float(), news_ids))

@@ -984,6 +984,103 @@ def mmr_rerank(pool_idx: torch.Tensor, pool_score: torch.Tensor, table: torch.Te
     return idx, score, mmr, status
 
 
+# ---- calibrated greedy re-ranking of a top-k pool (nrl_topk.hip: cal_rerank_kernel) ---------------------------------------------------
+CAL_MAX_CLASSES = 64
+# the status word of ``calibrated_rerank``; a dictionary of its own: the key sets of ``MMR_FLAGS`` and ``TOPK_FLAGS`` are pinned
+CAL_FLAGS = {1: MMR_FLAGS[1], 4: MMR_FLAGS[4],
+             64: "a class id outside [0, S) (that slot stays in the pool with a calibration term of 0 and counts for no class)",
+             128: "a negative, NaN or infinite target entry (taken as 0)"}
+
+
+def calibrated_rerank(pool_idx: torch.Tensor, pool_score: torch.Tensor, table: Optional[torch.Tensor], row_class: torch.Tensor,
+                      target: torch.Tensor, k: int, lam: float, mu: float, gamma: float, similarity: str = "cosine",
+                      normalize: bool = True):
+    """``nrl_calibrated_rerank``: greedy re-ranking of a pool of table rows per user by ``lam * rel_i - mu * max_{c selected}
+    sim(c, i) + gamma * cal(class_i)`` -> (idx (B, k) int64, score (B, k) fp32, obj (B, k) fp32, cal (B, k) fp32, status (1)
+    int32).  ``pool_idx`` / ``pool_score`` / ``table`` / ``similarity`` / ``normalize`` as for ``mmr_rerank``; ``row_class`` (V
+    int32, or int64: converted by one device op) gives every table row its class, ``target`` (B, S) fp32 every user's class target
+    (``class_targets``), S at most ``CAL_MAX_CLASSES``.  ``cal(c)`` is the generalised Jaccard overlap ``sum(min) / sum(max)``
+    between the class counts of the list with a slot of class ``c`` added and the target: with the history's class counts as the
+    target, the list's Personalization@k.  ``lam``, ``mu``, ``gamma`` each in [0, 1].  ``mu == 0`` needs no news vectors: ``table``
+    may be ``None`` and no similarity is computed.  ``gamma = 0`` with ``mu = 1 - lam`` is ``mmr_rerank``.  ``obj`` is the objective
+    a slot won with, ``cal`` its calibration term; ``-1`` / ``-inf`` / ``-inf`` / ``-inf`` once the live slots run out.  The native
+    header states every rounding.  ``status``: ``CAL_FLAGS``; it stays on the device -- nothing here synchronises with the host."""
+    checked = [(pool_idx, torch.int64, "pool_idx"), (pool_score, torch.float32, "pool_score"), (target, torch.float32, "target")]
+    if table is not None:
+        checked.append((table, torch.float32, "table"))
+    for t, dt, name in checked:
+        if t.dtype != dt:
+            raise ValueError(f"newsreclib_amd: `{name}` must be {dt}, got {t.dtype}")
+    if row_class is None or row_class.dtype not in (torch.int32, torch.int64):
+        raise ValueError("newsreclib_amd: row_class (one int32 or int64 class id per table row) is required")
+    if pool_idx.dim() != 2 or pool_score.shape != pool_idx.shape or (table is not None and table.dim() != 2) or row_class.dim() != 1:
+        raise ValueError(f"newsreclib_amd: pool_idx (B, N), pool_score (B, N), table (V, D) and row_class (V) expected, got "
+                         f"{tuple(pool_idx.shape)}, {tuple(pool_score.shape)}, {None if table is None else tuple(table.shape)} and "
+                         f"{tuple(row_class.shape)}")
+    B, N, V, k = int(pool_idx.shape[0]), int(pool_idx.shape[1]), int(row_class.numel()), int(k)
+    if target.dim() != 2 or int(target.shape[0]) != B:
+        raise ValueError(f"newsreclib_amd: target (B = {B}, S) expected, got {tuple(target.shape)}")
+    S = int(target.shape[1])
+    if table is not None and int(table.shape[0]) != V:
+        raise ValueError(f"newsreclib_amd: row_class must have one entry per table row ({int(table.shape[0])}), got {V}")
+    if similarity not in MMR_SIMILARITIES:
+        raise ValueError(f"newsreclib_amd: similarity is one of {sorted(MMR_SIMILARITIES)}, got {similarity!r}")
+    if N > MMR_MAX_POOL:
+        raise NotImplementedError(f"newsreclib_amd: calibrated_rerank takes a pool of at most {MMR_MAX_POOL} slots (got {N})")
+    if S > CAL_MAX_CLASSES:
+        raise NotImplementedError(f"newsreclib_amd: calibrated_rerank takes at most {CAL_MAX_CLASSES} classes (got {S})")
+    if S < 1:
+        raise ValueError("newsreclib_amd: target needs at least one class column")
+    if not 1 <= k <= N:
+        raise ValueError(f"newsreclib_amd: k in [1, N = {N}] expected, got {k}")
+    for name, value in (("lam", lam), ("mu", mu), ("gamma", gamma)):
+        if not 0.0 <= float(value) <= 1.0:
+            raise ValueError(f"newsreclib_amd: {name} in [0, 1] expected, got {value}")
+    if float(mu) != 0.0 and table is None:
+        raise ValueError("newsreclib_amd: mu != 0 penalises the similarity of news vectors: it needs the table")
+    pool_idx, pool_score, target = _chk(pool_idx, torch.int64, "pool_idx"), _chk(pool_score, torch.float32, "pool_score"), \
+        _chk(target, torch.float32, "target")
+    if table is not None:
+        table = _chk(table, torch.float32, "table")
+    if row_class.dtype == torch.int64 and row_class.is_cuda:
+        row_class = row_class.to(torch.int32)
+    row_class = _chk(row_class, torch.int32, "row_class")
+    lib = _lib.load()
+    dev = pool_idx.device
+    idx, score, status = _topk_outputs(B, k, dev)
+    obj, cal = torch.empty((B, k), dtype=torch.float32, device=dev), torch.empty((B, k), dtype=torch.float32, device=dev)
+    D = int(table.shape[1]) if table is not None else 0
+    _lib.check(lib.nrl_calibrated_rerank(pool_idx.data_ptr(), pool_score.data_ptr(), table.data_ptr() if table is not None and V else None,
+                                         B, N, V, D, row_class.data_ptr() if V else None, target.data_ptr(), S, k, float(lam),
+                                         float(mu), float(gamma), MMR_SIMILARITIES[similarity], int(bool(normalize)), idx.data_ptr(),
+                                         score.data_ptr(), obj.data_ptr(), cal.data_ptr(), status.data_ptr(), _stream()),
+               "nrl_calibrated_rerank")
+    return idx, score, obj, cal, status
+
+
+def class_targets(hist_idx: torch.Tensor, hist_off: torch.Tensor, row_class: torch.Tensor, S: int, k: Optional[int] = None):
+    """The class targets ``calibrated_rerank`` takes -> (B, S) fp32: the class counts of each user's ragged history (``hist_idx``:
+    the concatenated table rows, ``hist_off`` (B + 1) its offsets; ``row_class`` (V) the class of every row).  A history row
+    outside the table, or whose class is outside [0, S), counts for nothing.  ``k``: the counts times ``k`` over ``max(1, history
+    size)`` -- the history's class proportions as quotas of a list of ``k`` (Steck, 2018) -- instead of the integer counts, which
+    make ``calibrated_rerank``'s term the list's Personalization@k.  Torch ops on the tensors' device; nothing is read back."""
+    dev = hist_idx.device
+    S, V = int(S), int(row_class.numel())
+    hist_idx, hist_off, row_class = hist_idx.long(), hist_off.to(dev).long(), row_class.to(dev).long()
+    B = int(hist_off.numel()) - 1
+    sizes = hist_off[1:] - hist_off[:-1]
+    owner = torch.repeat_interleave(torch.arange(B, device=dev), sizes, output_size=int(hist_idx.numel()))
+    row_ok = (hist_idx >= 0) & (hist_idx < V)
+    cls = row_class[hist_idx.clamp(0, max(V - 1, 0))] if V else torch.full_like(hist_idx, -1)
+    ok = row_ok & (cls >= 0) & (cls < S)
+    counts = torch.zeros(B * S, dtype=torch.float32, device=dev)
+    counts.index_put_((owner * S + torch.where(ok, cls, torch.zeros_like(cls)),), ok.float(), accumulate=True)
+    counts = counts.view(B, S)
+    if k is not None:
+        counts = (counts * float(k)) / sizes.clamp_min(1).float()[:, None]      # (count * k is exact: one rounding per entry)
+    return counts
+
+
 TOPK_MAX_INTERESTS = 64
 
 
