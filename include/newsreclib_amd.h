@@ -1295,6 +1295,62 @@ int nrl_calibrated_rerank(const int64_t* pool_idx, const float* pool_score, cons
                           float gamma, int32_t similarity, int32_t normalize, int64_t* out_idx, float* out_score, float* out_obj,
                           float* out_cal, int32_t* status, void* stream);
 
+/* nrl_dpp_rerank (symbol added to ABI v19): greedy re-ranking of a pool by a determinantal point process (DPP), the set-level
+ *   diversifier beside the pairwise nrl_mmr_rerank: the fast greedy MAP inference of Chen, Zhang and Zhou (NeurIPS 2018), an
+ *   incremental Cholesky factorisation of the kernel matrix L = diag(q) sim diag(q), q_i a slot's quality and sim the similarity of
+ *   the pool's table rows.  Each step lists the slot that multiplies det L_S of the listed set S by the most: a slot that is a
+ *   mixture of listed ones gains little even where it is close to none of them.
+ *   Inputs: pool_idx (B, N) int64, pool_score (B, N) fp32, table (V, D) fp32, k, similarity, normalize as for nrl_mmr_rerank;
+ *     quality (B, N) fp32 or NULL; alpha, eps fp32.
+ *   Limits: 1 <= k <= min(N, NRL_DPP_MAX_K = 64); N <= NRL_MMR_MAX_POOL; D, V, B as for nrl_mmr_rerank; alpha finite and >= 0;
+ *     eps in [0, 1); similarity and normalize in {0, 1}.
+ *   Live slots, the Gram matrix G, sim (cosine / dot, r_i) and rel_i (normalize 0 / 1) are word for word those of nrl_mmr_rerank,
+ *     with its flags NRL_MMR_E_ROW (1) and NRL_TOPK_E_NAN (4): the row range check, the finite-score check, then (after the
+ *     quality check below) the Gram diagonal check.
+ *   Quality: with quality given, q_i = quality[u][i], read for a slot with a valid row and a finite score; a NaN, infinite or
+ *     negative entry makes that slot dead and ORs NRL_DPP_E_QUALITY (256); -0 is taken as a zero.  alpha and normalize are then
+ *     checked but not used.  With quality NULL, q_i = expf(fl(alpha * rel_i)): the device expf of the single product.  This is the
+ *     ONE operation whose bits this header does not fix; every bit-for-bit statement here holds for a given quality.
+ *     alpha = theta / (2 (1 - theta)) is the trade-off theta of Chen et al. (their kernel has q_i = exp(alpha r_i)): alpha = 0
+ *     ranks by diversity alone, a large alpha by relevance.
+ *   Kernel matrix: L[i][j] = fl(fl(q_i * q_j) * sim[i][j]), bit-symmetric.  A live slot whose L[i][i] is not finite is dead and
+ *     ORs 4.
+ *   State of slot i: d2_i = L[i][i], thr_i = fl(eps * L[i][i]); cv[s][i] the Cholesky rows.
+ *   Greedy step t = 0, 1, ...: a slot is eligible when it is live, unselected, d2_i > 0 and d2_i >= thr_i (a NaN d2 satisfies
+ *     neither, so it ranks below every number).  The step selects the eligible slot c of largest d2; equal d2 goes to the lower
+ *     slot.  Then, for every other live, unselected slot i:
+ *       acc     = the chain from +0 over s = 0 ... t - 1, ascending, of acc = fl(acc + fl(cv[s][c] * cv[s][i]))
+ *       e_i     = fl(fl(L[c][i] - acc) / fl(sqrt(d2_c)))
+ *       cv[t][i] = e_i
+ *       d2_i    = fl(d2_i - fl(e_i * e_i))
+ *     Every operation is one correctly rounded fp32 operation (the operations __fadd_rn, __fsub_rn, __fmul_rn, __fdiv_rn,
+ *     __fsqrt_rn name), subnormal results kept; nothing contracts to an fma.  A float32 numpy restatement reproduces the bits.
+ *   Fill phase: at the first step with no eligible slot the DPP phase is over for good (in exact arithmetic the listed set then
+ *     spans every slot left, up to eps).  The remaining live, unselected slots are listed by pool_score descending, slot ascending
+ *     (-0 counts as +0) with out_gain +0, and NRL_DPP_E_RANK (512) is ORed if at least one slot among the k is listed this way.
+ *   Outputs: out_idx (B, k) int64 the row; out_score (B, k) fp32 that slot's pool_score, bits unchanged; out_gain (B, k) fp32 the
+ *     winning d2, the marginal determinant ratio det L_{S + c} / det L_S; -1 / -inf / -inf once the live slots run out.  status
+ *     (one int32, required): integer atomicOr only.
+ *   Properties:
+ *     1. The result for k is a prefix of the result for k' > k (the status word may gain NRL_DPP_E_RANK).
+ *     2. Nothing depends on B, on the user's place in the batch, on the GEMM engine setting or on the run.
+ *     3. The product of a user's DPP-phase gains is det L_S of the listed set S up to rounding.
+ *     4. Cosine: after a row is listed, a live slot that duplicates it has a d2 at rounding-noise level (a few 2^-24 L[i][i]; +0
+ *        where the step's arithmetic is exact), so with eps above that level -- 1e-4 is -- it is never chosen in the DPP phase.
+ *        With eps = 0 the sign of that noise decides.
+ *     5. No workspace, no float atomics, no allocation, no host synchronisation.
+ *   Checks, in this order, each NRL_E_INVALID before any launch: negative sizes; N outside [1, 128]; k outside [1, min(N, 64)];
+ *     alpha negative, infinite or NaN; eps outside [0, 1) or NaN; D, V, B outside the limits of nrl_topk_scores; similarity /
+ *     normalize outside {0, 1}; a null status.  B == 0 returns success without a launch.  After that, null pointers among the
+ *     rest return NRL_E_INVALID; quality may be null (see above); table may be null only when V == 0. */
+#define NRL_DPP_MAX_K 64
+#define NRL_DPP_E_QUALITY 256 /* a quality entry is negative, NaN or infinite: that slot is dead */
+#define NRL_DPP_E_RANK 512    /* no slot was eligible before the list was full: the rest is listed by pool score, gain +0 */
+int nrl_dpp_rerank(const int64_t* pool_idx, const float* pool_score, const float* quality /* (B, N) or null */,
+                   const float* table, int64_t B, int32_t N, int64_t V, int32_t D, int32_t k, float alpha, float eps,
+                   int32_t similarity, int32_t normalize, int64_t* out_idx, float* out_score, float* out_gain,
+                   int32_t* status, void* stream);
+
 /* nrl_topk_relu_scores: the same ranking by DKN's DNN click predictor (click_predictor.py:14-45: Linear(2 dim, Hd) -> ReLU ->
  *   Linear(Hd, 1) on [cand; user]) with the candidate list replaced by the table.  The first layer splits by columns,
  *   pred_w1 = [Wc | Wu], so with q (B, Hd) = user Wu^T + b1 (nrl_dkn_user_query) and proj (V, Hd) = table Wc^T

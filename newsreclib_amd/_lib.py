@@ -331,6 +331,8 @@ SIGNATURES = {
     "nrl_calibrated_rerank": (c_int32, [c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_int64, c_int32, c_void_p, c_void_p, c_int32,
                                         c_int32, c_float, c_float, c_float, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p,
                                         c_void_p, c_void_p]),
+    "nrl_dpp_rerank": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_int64, c_int32, c_int32, c_float, c_float,
+                                 c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "nrl_topk_relu_scores": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int32, c_int32, c_void_p,
                                        c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "nrl_topk_pooled_scores": (c_int32, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int32, c_int32, c_int32, c_void_p,

@@ -40,6 +40,7 @@
 // Behind the walk kernels, mmr_rerank_kernel (nrl_mmr_rerank) re-ranks a pool any of the top-k entries returned by greedy MMR: it is
 // no walk (one workgroup per user, the pool's Gram matrix by tk_tile_accumulate<1, true>, then k steps) and needs no workspace.
 // cal_rerank_kernel (nrl_calibrated_rerank) is that kernel with a class-calibration term; its mu == 0 form has no Gram stage.
+// dpp_rerank_kernel (nrl_dpp_rerank) is its workgroup running the greedy MAP inference of a determinantal point process instead.
 #include <math.h>
 
 #include "nrl_common.h"
@@ -2321,6 +2322,233 @@ __global__ __launch_bounds__(TK_THREADS) void cal_rerank_kernel(CalArgs A) {
   }
 }
 
+// ---- greedy DPP re-ranking of a pool (nrl_dpp_rerank) ------------------------------------------------------------------------------
+// mmr_rerank_kernel's workgroup (one per user, thread i owns slot i) running the fast greedy MAP inference of a determinantal point
+// process (Chen, Zhang, Zhou 2018): an incremental Cholesky factorisation of L = diag(q) sim diag(q), formed in place over the Gram
+// tiles in the pass that applies the cosine scaling.  Dynamic LDS, behind the `halves` Gram tiles:
+//   wk[2][4] u64     the waves' best entries of a step, double-buffered by the parity of the barrier count
+//   rows[128] i64    the slots' table rows (the Gram stage gathers by them)
+//   rn[128] f32      1 / sqrt(G[i][i]);  qs[128] f32  the slots' qualities, +0 where the slot is dead
+//   cv[k][128] f32   the Cholesky rows, step-major and sized from k at launch: cv[s][i] = e_i of step s
+// d2_i, thr_i and the live / selected flags of slot i live in the registers of thread i.  After the barrier of step t has named the
+// winner c, thread i walks s = 0 ... t - 1 reading cv[s][i] (lane i word s * 128 + i: consecutive lanes consecutive banks) and
+// cv[s][c] (every lane the same word: a broadcast), then L[c][i], the ROW of the winner as MMR reads sim[c][i], and stores
+// cv[t][i].  Thread i alone writes column i of cv, and cv[t][.] is first read after the NEXT step's barrier, so a step costs ONE
+// barrier, the one that publishes the waves' best entries; the winner's d2 travels in the key of its entry (it is positive, so
+// tk_unkey returns its bits).  When no slot is eligible the fill phase lists the rest by pool score through the same entries.
+constexpr int DPP_MAX_K = NRL_DPP_MAX_K;
+constexpr size_t DPP_SLOT_BYTES = 2 * 4 * 8 + (size_t)MMR_MAX_POOL * (8 + 4 + 4);
+constexpr size_t dpp_lds_bytes(int halves, int k) { return (size_t)halves * TK_TILE_BYTES + DPP_SLOT_BYTES + (size_t)k * MMR_MAX_POOL * 4; }
+static_assert(DPP_MAX_K <= MMR_MAX_POOL, "a list is no longer than a pool");
+static_assert((2 * TK_TILE_BYTES + DPP_SLOT_BYTES) % 16 == 0, "the Cholesky rows start 16-byte aligned");
+static_assert(dpp_lds_bytes(2, DPP_MAX_K) <= 160 * 1024, "the largest layout (two tiles, 64 Cholesky rows, the slots) fits a CU");
+static_assert(2 * dpp_lds_bytes(2, 16) <= 160 * 1024, "up to k = 16 two workgroups of the largest pool fit a CU");
+
+struct DppArgs {
+  const int64_t* pool_idx;
+  const float* pool_score;
+  const float* quality;
+  const float* table;
+  int32_t N, D, k;
+  int64_t V;
+  float alpha, eps;
+  int32_t similarity, normalize;
+  int64_t* out_idx;
+  float* out_score;
+  float* out_gain;
+  int32_t* status;
+};
+
+__global__ __launch_bounds__(TK_THREADS) void dpp_rerank_kernel(DppArgs A) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char tk_smem[];
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int N = A.N, k = A.k;
+  const int halves = (N + TK_BU - 1) / TK_BU;
+  const int64_t u = blockIdx.x;
+  float* const sim = reinterpret_cast<float*>(tk_smem);
+  unsigned long long* const wk = reinterpret_cast<unsigned long long*>(tk_smem + (size_t)halves * TK_TILE_BYTES);
+  int64_t* const rows = reinterpret_cast<int64_t*>(wk + 8);
+  float* const rn = reinterpret_cast<float*>(rows + MMR_MAX_POOL);
+  float* const qs = rn + MMR_MAX_POOL;
+  float* const cv = qs + MMR_MAX_POOL;
+  const int64_t* const pool = A.pool_idx + u * N;
+
+  // the slots: thread i owns slot i
+  bool live = false;
+  float score = 0.f, q = 0.f;
+  int64_t row = -1;
+  int flags = 0;
+  if (tid < MMR_MAX_POOL) {
+    if (tid < N) {
+      row = pool[tid];
+      score = A.pool_score[u * N + tid];
+    }
+    const bool row_ok = row >= 0 && row < A.V;
+    const bool fin = fabsf(score) < INFINITY;
+    if (row != -1 && !row_ok) flags |= NRL_MMR_E_ROW;
+    if (row_ok && !fin) flags |= NRL_TOPK_E_NAN;
+    live = row_ok && fin;
+    if (live && A.quality) {
+      q = A.quality[u * N + tid];
+      if (!(q >= 0.f && q < INFINITY)) {
+        live = false;
+        flags |= NRL_DPP_E_QUALITY;
+      }
+    }
+    rows[tid] = live ? row : -1;
+    rn[tid] = 0.f;
+  }
+  __syncthreads();
+
+  // the Gram matrix, as in mmr_rerank_kernel
+  if (A.V > 0) {
+    for (int h = 0; h < halves; ++h) {
+      const int64_t ar = rows[h * TK_BU + (tid >> 2)];                        // (-1: an empty, bad or non-finite slot)
+      const bool ua_ok = ar >= 0;
+      const float* const pa[1] = {A.table + (ua_ok ? ar : 0) * A.D};
+      float* const tile = sim + h * TK_BU * TK_SCLD;
+      tk_f32x4 acc[1][2][4];
+      tk_tile_accumulate<1, true>(pa, ua_ok, A.table, A.D, 0, N, A.D, tile, acc, pool, A.V);
+      tk_store_fragments(acc[0], tile);
+      __syncthreads();
+    }
+  }
+
+  // the diagonal: a slot whose own product is not finite is dead; r
+  if (tid < N && live) {
+    const float g = sim[tid * TK_SCLD + tid];
+    if (!(fabsf(g) < INFINITY)) {
+      live = false;
+      flags |= NRL_TOPK_E_NAN;
+    } else {
+      rn[tid] = g == 0.f ? 0.f : mmr_div(1.f, __builtin_sqrtf(g));
+    }
+  }
+  // without a given quality: relevance as in mmr_rerank_kernel (the extremes of the live scores as keys, through the waves' slots
+  // of wk), then q = exp(alpha rel)
+  const bool from_rel = A.quality == nullptr;
+  if (from_rel && A.normalize) {
+    const uint32_t key = score_key(score);
+    uint32_t lo = live ? key : 0xFFFFFFFFu, hi = live ? key : 0u;
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+      const uint32_t l2 = (uint32_t)__shfl_xor((int)lo, off, 64), h2 = (uint32_t)__shfl_xor((int)hi, off, 64);
+      lo = l2 < lo ? l2 : lo;
+      hi = h2 > hi ? h2 : hi;
+    }
+    if (lane == 0) wk[wave] = ((unsigned long long)hi << 32) | lo;
+    __syncthreads();                                  // publishes the extremes (uniform branch)
+  }
+  if (from_rel) {
+    float rel = score;
+    if (A.normalize) {
+      uint32_t lo = 0xFFFFFFFFu, hi = 0u;
+#pragma unroll
+      for (int w = 0; w < TK_THREADS / 64; ++w) {
+        const unsigned long long e = wk[w];
+        const uint32_t l2 = (uint32_t)e, h2 = (uint32_t)(e >> 32);
+        lo = l2 < lo ? l2 : lo;
+        hi = h2 > hi ? h2 : hi;
+      }
+      if (hi == lo || hi == 0u) {
+        rel = 0.f;
+      } else {
+        const float s_min = tk_unkey(lo), s_max = tk_unkey(hi);
+        rel = mmr_div(mmr_sub(score, s_min), mmr_sub(s_max, s_min));
+      }
+    }
+    q = expf(mmr_mul(A.alpha, rel));
+  }
+  if (tid < MMR_MAX_POOL) qs[tid] = live ? q : 0.f;
+  __syncthreads();                                    // publishes rn and qs; the extremes in wk have been read
+
+  // the kernel matrix, in place: L[i][j] = (q_i q_j) sim[i][j]
+  const bool cosine = A.similarity == 0;
+  for (int e = tid; e < N * TK_BV; e += TK_THREADS) {
+    const int i = e / TK_BV, j = e % TK_BV;
+    float* const p = sim + i * TK_SCLD + j;
+    float s = *p;
+    if (cosine) s = mmr_mul(s, mmr_mul(rn[i], rn[j]));
+    *p = mmr_mul(mmr_mul(qs[i], qs[j]), s);
+  }
+  __syncthreads();                                    // L is final; wk is free for the steps
+
+  float d2 = 0.f, thr = 0.f;
+  if (tid < N && live) {
+    d2 = sim[tid * TK_SCLD + tid];
+    if (!(fabsf(d2) < INFINITY)) {
+      live = false;
+      flags |= NRL_TOPK_E_NAN;
+    }
+    thr = mmr_mul(A.eps, d2);
+  }
+  {
+    int f = flags;
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) f |= __shfl_xor(f, off, 64);
+    if (f && lane == 0) atomicOr(A.status, f);
+  }
+
+  // a step's ONE barrier: the largest of the threads' entries, through the waves' slots of wk; par counts the barriers
+  int par = 0;
+  auto best_entry = [&](unsigned long long e) {
+    e = mmr_wave_max(e, lane);
+    if (lane == 0) wk[par * 4 + wave] = e;
+    __syncthreads();
+    unsigned long long best = wk[par * 4];
+#pragma unroll
+    for (int w = 1; w < TK_THREADS / 64; ++w) {
+      const unsigned long long y = wk[par * 4 + w];
+      best = y > best ? y : best;
+    }
+    par ^= 1;
+    return best;
+  };
+
+  // the DPP phase
+  bool sel = false;
+  int c = -1, t = 0;
+  float d2c = 0.f;
+  for (; t < k; ++t) {
+    if (t > 0 && tid < N && live && !sel) {
+      float acc = 0.f;
+      for (int s = 0; s < t - 1; ++s) acc = cal_add(acc, mmr_mul(cv[s * MMR_MAX_POOL + c], cv[s * MMR_MAX_POOL + tid]));
+      const float e = mmr_div(mmr_sub(sim[c * TK_SCLD + tid], acc), __builtin_sqrtf(d2c));
+      cv[(t - 1) * MMR_MAX_POOL + tid] = e;
+      d2 = mmr_sub(d2, mmr_mul(e, e));
+    }
+    const bool eligible = live && !sel && d2 > 0.f && d2 >= thr;
+    const unsigned long long best = best_entry(eligible ? tk_entry(d2, (uint32_t)tid) : 0ull);
+    if (best == 0ull) break;                          // no slot is eligible: the DPP phase is over for good (uniform)
+    c = (int)~(uint32_t)best;
+    d2c = tk_unkey((uint32_t)(best >> 32));           // (d2_c > 0: the key gives its bits back)
+    if (tid == c) {
+      sel = true;
+      A.out_idx[u * k + t] = row;
+      A.out_score[u * k + t] = score;
+      A.out_gain[u * k + t] = d2;
+    }
+  }
+  // the fill phase: the live slots left over, by (pool score descending, slot ascending)
+  for (const int t0 = t; t < k; ++t) {
+    const unsigned long long best = best_entry(live && !sel ? tk_entry(score, (uint32_t)tid) : 0ull);
+    if (best == 0ull) break;                          // the live slots have run out (uniform)
+    if (tid == (int)~(uint32_t)best) {
+      sel = true;
+      A.out_idx[u * k + t] = row;
+      A.out_score[u * k + t] = score;
+      A.out_gain[u * k + t] = 0.f;
+      if (t == t0) atomicOr(A.status, NRL_DPP_E_RANK);
+    }
+  }
+  for (int p = t + tid; p < k; p += TK_THREADS) {
+    A.out_idx[u * k + p] = -1;
+    A.out_score[u * k + p] = -INFINITY;
+    A.out_gain[u * k + p] = -INFINITY;
+  }
+}
+
 static bool tk_shape_ok(int64_t B, int64_t V, int32_t D, int32_t k) {
   return B >= 0 && V >= 0 && V < ((int64_t)1 << 31) && D > 0 && D % 4 == 0 && D <= NRL_TOPK_MAX_D && k >= 1 && k <= NRL_TOPK_MAX_K;
 }
@@ -2999,6 +3227,33 @@ int nrl_calibrated_rerank(const int64_t* pool_idx, const float* pool_score, cons
   } else {
     cal_rerank_kernel<false><<<(unsigned)B, TK_THREADS, cal_lds_bytes(0), (hipStream_t)stream>>>(A);
   }
+  NRL_LAUNCH_CHECK();
+  return NRL_OK;
+}
+
+// ---- nrl_dpp_rerank (header: semantics) --------------------------------------------------------------------------------------------
+int nrl_dpp_rerank(const int64_t* pool_idx, const float* pool_score, const float* quality, const float* table, int64_t B, int32_t N,
+                   int64_t V, int32_t D, int32_t k, float alpha, float eps, int32_t similarity, int32_t normalize, int64_t* out_idx,
+                   float* out_score, float* out_gain, int32_t* status, void* stream) {
+  NRL_REQUIRE(B >= 0 && N >= 0 && V >= 0 && D >= 0 && k >= 0, "dpp_rerank: negative size");
+  NRL_REQUIRE(N >= 1 && N <= NRL_MMR_MAX_POOL, "dpp_rerank: N in [1, %d] (got %d)", NRL_MMR_MAX_POOL, N);
+  NRL_REQUIRE(k >= 1 && k <= N && k <= NRL_DPP_MAX_K, "dpp_rerank: k in [1, min(N = %d, %d)] (got %d)", N, NRL_DPP_MAX_K, k);
+  NRL_REQUIRE(alpha >= 0.f && alpha < INFINITY, "dpp_rerank: alpha finite and >= 0 (got %g)", (double)alpha);
+  NRL_REQUIRE(eps >= 0.f && eps < 1.f, "dpp_rerank: eps in [0, 1) (got %g)", (double)eps);
+  NRL_REQUIRE(D > 0 && D % 4 == 0 && D <= NRL_TOPK_MAX_D, "dpp_rerank: D a multiple of 4 in [4, %d] (got %d)", NRL_TOPK_MAX_D, D);
+  NRL_REQUIRE(V < ((int64_t)1 << 31), "dpp_rerank: at most 2^31 - 1 table rows (got %lld)", (long long)V);
+  NRL_REQUIRE(B < ((int64_t)1 << 31), "dpp_rerank: at most 2^31 - 1 users per call (got %lld)", (long long)B);
+  NRL_REQUIRE((similarity == 0 || similarity == 1) && (normalize == 0 || normalize == 1),
+              "dpp_rerank: similarity (0 cosine, 1 dot) and normalize in {0, 1} (got %d, %d)", similarity, normalize);
+  NRL_REQUIRE(status, "dpp_rerank: the status word is required");
+  if (B == 0) return NRL_OK;
+  NRL_REQUIRE(pool_idx && pool_score && out_idx && out_score && out_gain && (V == 0 || table), "dpp_rerank: null argument");
+  const DppArgs A{pool_idx, pool_score, quality, table, N, D, k, V, alpha, eps, similarity, normalize, out_idx, out_score, out_gain, status};
+  const size_t smem = dpp_lds_bytes((N + TK_BU - 1) / TK_BU, k);
+  // more than 64 KB of dynamic LDS needs the attribute; it belongs to the current device, so it is set per call
+  if (smem > 64 * 1024)
+    NRL_HIP(hipFuncSetAttribute((const void*)dpp_rerank_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+  dpp_rerank_kernel<<<(unsigned)B, TK_THREADS, smem, (hipStream_t)stream>>>(A);
   NRL_LAUNCH_CHECK();
   return NRL_OK;
 }

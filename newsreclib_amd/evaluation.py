@@ -441,6 +441,18 @@ class NewsVectorCache(_ImpressionCache):
         return ops.mmr_rerank(pool_idx, pool_score, self.vectors, k, lam, similarity, normalize)
 
     @torch.no_grad()
+    def rerank_dpp(self, pool_idx: torch.Tensor, pool_score: torch.Tensor, k: int, alpha: float = 1.0, similarity: str = "cosine",
+                   normalize: bool = True, quality: Optional[torch.Tensor] = None, eps: float = 1e-4):
+        """Greedy DPP re-ranking of a pool any ``recommend*`` of this cache returned (``pool_idx`` / ``pool_score`` (B, N), N at
+        most ``ops.MMR_MAX_POOL``, ``k`` at most ``ops.DPP_MAX_K``) -> (news_idx (B, k) int64, scores (B, k) fp32: the pool's own,
+        gain (B, k) fp32, status: ``ops.DPP_FLAGS``): ``ops.dpp_rerank`` against the cached news vectors, built when they are
+        missing.  Where ``rerank_diverse`` penalises a news by its one nearest neighbour in the list, this penalises what the
+        listed news span together.  Nothing is read back."""
+        if self.vectors is None:
+            self.build()
+        return ops.dpp_rerank(pool_idx, pool_score, self.vectors, k, alpha, similarity, normalize, quality, eps)
+
+    @torch.no_grad()
     def rerank_calibrated(self, pool_idx: torch.Tensor, pool_score: torch.Tensor, k: int, aspect: str, target: torch.Tensor,
                           lam: float, mu: float, gamma: float, similarity: str = "cosine", normalize: bool = True):
         """Calibrated greedy re-ranking of a pool any ``recommend*`` of this cache returned -> (news_idx (B, k) int64, scores
@@ -620,6 +632,15 @@ class MannerVectorCache(_ImpressionCache):
         return ops.mmr_rerank(pool_idx, pool_score, self.vectors[submodel], k, lam, similarity, normalize)
 
     @torch.no_grad()
+    def rerank_dpp(self, pool_idx: torch.Tensor, pool_score: torch.Tensor, k: int, alpha: float = 1.0, similarity: str = "cosine",
+                   normalize: bool = True, quality: Optional[torch.Tensor] = None, eps: float = 1e-4, submodel: int = 0):
+        """``NewsVectorCache.rerank_dpp`` of a pool ``recommend_ensemble*`` returned, against the table of sub-model ``submodel``,
+        as ``rerank_diverse`` takes its similarity there."""
+        if self.vectors is None:
+            self.build()
+        return ops.dpp_rerank(pool_idx, pool_score, self.vectors[submodel], k, alpha, similarity, normalize, quality, eps)
+
+    @torch.no_grad()
     def rerank_calibrated(self, pool_idx: torch.Tensor, pool_score: torch.Tensor, k: int, aspect: str, target: torch.Tensor,
                           lam: float, mu: float, gamma: float, similarity: str = "cosine", normalize: bool = True, which: int = 0):
         """``NewsVectorCache.rerank_calibrated`` of a pool ``recommend_ensemble*`` returned; with ``mu != 0`` the similarity is
@@ -743,6 +764,11 @@ class NpaFeatureCache(_ImpressionCache):
                                   "on the user (personalized attention pooling, text.py:385-390): the cache holds feature maps, not "
                                   "a (V, D) table of news vectors to take that similarity in")
 
+    def rerank_dpp(self, *args, **kwargs):
+        raise NotImplementedError("a DPP's kernel matrix is built from the similarity of two news vectors, and an NPA news vector "
+                                  "depends on the user (personalized attention pooling, text.py:385-390): the cache holds feature "
+                                  "maps, not a (V, D) table of news vectors to take that similarity in")
+
     @torch.no_grad()
     def rerank_calibrated(self, pool_idx: torch.Tensor, pool_score: torch.Tensor, k: int, aspect: str, target: torch.Tensor,
                           lam: float, mu: float, gamma: float, similarity: str = "cosine", normalize: bool = True):
@@ -863,7 +889,8 @@ def format_recommendations(user_ids: Sequence, news_idx: torch.Tensor, scores: t
 
 def recommend_users(cache: NewsVectorCache, users: Sequence[Dict], k: int, batch_size: int = 512,
                     eligible: Optional[torch.Tensor] = None, cap: Optional[Tuple[str, int]] = None,
-                    diversify: Optional[Tuple[int, float]] = None, calibrate: Optional[Dict] = None) -> Dict[str, Dict[str, float]]:
+                    diversify: Optional[Tuple[int, float]] = None, calibrate: Optional[Dict] = None,
+                    dpp: Optional[Dict] = None) -> Dict[str, Dict[str, float]]:
     """``cache.recommend`` (``cache.recommend_interests`` where the cache's module is a ``multi_interest_scorer``,
     ``cache.recommend_dnn`` where it is a ``dnn_predictor_scorer``, ``cache.recommend_pooled`` where it is a
     ``personalized_pooling_scorer``: ``NpaFeatureCache``, whose users need ``user_idx``,
@@ -890,7 +917,25 @@ def recommend_users(cache: NewsVectorCache, users: Sequence[Dict], k: int, batch
     a class id beyond is flagged): the integer class counts (``"history"``, the default: the term is the list's
     Personalization@k) or the class proportions times ``k`` (``"proportional"``).  ``mu`` adds MMR's penalty, so ``calibrate``
     together with ``diversify`` is a ``ValueError``; an ``NpaFeatureCache`` is served with ``mu == 0``.  The status word
-    (``ops.CAL_FLAGS``) is OR-ed in 16 bits up like ``diversify``'s.  ``None`` is the path without it, launch for launch."""
+    (``ops.CAL_FLAGS``) is OR-ed in 16 bits up like ``diversify``'s.  ``None`` is the path without it, launch for launch.
+
+    ``dpp`` = dict(pool=, alpha=1.0, eps=1e-4): the method picked above returns each user's ``pool`` best news (``k <= pool``,
+    ``k <= ops.DPP_MAX_K``) and ``cache.rerank_dpp(idx, score, k, alpha, eps=eps)`` -- greedy DPP inference by the cosine of the
+    cached news vectors with quality ``exp(alpha * rel)``, the relevance min-max scaled -- picks the ``k`` that are listed.  It is
+    a diversifier of its own, so together with ``diversify`` or ``calibrate`` it is a ``ValueError``.  The status word
+    (``ops.DPP_FLAGS``) is OR-ed in 16 bits up like theirs.  ``None`` is the path without it, launch for launch."""
+    if dpp is not None:
+        if diversify is not None or calibrate is not None:
+            raise ValueError("recommend_users: `dpp` excludes `diversify` and `calibrate`: each of the three picks the k listed "
+                             "news from the pool by an objective of its own")
+        unknown = set(dpp) - {"pool", "alpha", "eps"}
+        if unknown or "pool" not in dpp:
+            raise ValueError(f"recommend_users(dpp=dict(pool=, alpha=1.0, eps=1e-4)): got {sorted(dpp)}")
+        pool, dpp_alpha, dpp_eps = int(dpp["pool"]), float(dpp.get("alpha", 1.0)), float(dpp.get("eps", 1e-4))
+        if pool < k:
+            raise ValueError(f"recommend_users(dpp=dict(pool=...)): the pool ({pool}) must hold at least k = {k} news")
+        if getattr(cache.module, "personalized_pooling_scorer", False):
+            cache.rerank_dpp()                              # (NpaFeatureCache: refuses and says why, before any device work)
     if calibrate is not None:
         if diversify is not None:
             raise ValueError("recommend_users: `calibrate` and `diversify` exclude each other; calibrate=dict(..., mu=...) is MMR's "
@@ -940,7 +985,11 @@ def recommend_users(cache: NewsVectorCache, users: Sequence[Dict], k: int, batch
         elif cap is not None:
             capped = getattr(cache, "recommend_ensemble_capped", None) or cache.recommend_capped
             rank = lambda hist, hs, k, **kw: capped(hist, hs, k, aspect, max_per_class, **kw)  # noqa: E731
-        idx, score, status = rank(hist, hs, k if diversify is None and calibrate is None else pool, user_idx=uidx, eligible=eligible)
+        reranked = diversify is not None or calibrate is not None or dpp is not None
+        idx, score, status = rank(hist, hs, pool if reranked else k, user_idx=uidx, eligible=eligible)
+        if dpp is not None:
+            idx, score, _, dpp_status = cache.rerank_dpp(idx, score, k, dpp_alpha, eps=dpp_eps)
+            status = status | (dpp_status << 16)
         if diversify is not None:
             idx, score, _, mmr_status = cache.rerank_diverse(idx, score, k, lam)
             status = status | (mmr_status << 16)
@@ -954,7 +1003,7 @@ def recommend_users(cache: NewsVectorCache, users: Sequence[Dict], k: int, batch
         if word:                                            # the kernel has dealt with each of these; the caller should know
             import warnings
             flags = ops.TOPK_BIAS_FLAGS if biased else ops.TOPK_FLAGS
-            second = ops.CAL_FLAGS if calibrate is not None else ops.MMR_FLAGS
+            second = ops.DPP_FLAGS if dpp is not None else ops.CAL_FLAGS if calibrate is not None else ops.MMR_FLAGS
             said = [msg for bit, msg in flags.items() if word & bit] + [msg for bit, msg in second.items() if (word >> 16) & bit]
             warnings.warn("recommend_users: " + "; ".join(said))
         ids = [int(u["user_id"]) if "user_id" in u else lo + j + 1 for j, u in enumerate(chunk)]

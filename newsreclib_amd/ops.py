@@ -1058,6 +1058,67 @@ def calibrated_rerank(pool_idx: torch.Tensor, pool_score: torch.Tensor, table: O
     return idx, score, obj, cal, status
 
 
+# ---- greedy DPP re-ranking of a top-k pool (nrl_topk.hip: dpp_rerank_kernel) ----------------------------------------------------------
+DPP_MAX_K = 64
+# the status word of ``dpp_rerank``; a dictionary of its own: the key sets of ``MMR_FLAGS``, ``CAL_FLAGS`` and ``TOPK_FLAGS`` are pinned
+DPP_FLAGS = {1: MMR_FLAGS[1], 4: MMR_FLAGS[4],
+             256: "a negative, NaN or infinite quality entry (that slot is dead)",
+             512: "the pool's kernel matrix ran out of rank before the list was full (the rest is listed by pool score, gain 0)"}
+
+
+def dpp_rerank(pool_idx: torch.Tensor, pool_score: torch.Tensor, table: torch.Tensor, k: int, alpha: float = 1.0,
+               similarity: str = "cosine", normalize: bool = True, quality: Optional[torch.Tensor] = None, eps: float = 1e-4):
+    """``nrl_dpp_rerank``: greedy MAP inference of a determinantal point process over a pool of table rows per user (Chen, Zhang,
+    Zhou 2018) -> (idx (B, k) int64, score (B, k) fp32, gain (B, k) fp32, status (1) int32).  ``pool_idx`` / ``pool_score`` /
+    ``table`` / ``similarity`` / ``normalize`` as for ``mmr_rerank``, ``k`` at most ``DPP_MAX_K``.  The kernel matrix is
+    ``L = diag(q) sim diag(q)``; step by step the slot that multiplies ``det L_S`` of the listed set by the most is taken (ties:
+    the lower slot), so a news that is a mixture of listed ones is penalised even where it is close to none of them, which MMR's
+    pairwise penalty cannot see.  ``quality`` (B, N) fp32 gives ``q`` itself (finite and >= 0); without it ``q_i = exp(alpha *
+    rel_i)``, ``rel`` the score min-max scaled over the user's live slots (``normalize``) or the score itself:
+    ``alpha = theta / (2 (1 - theta))`` is the paper's trade-off, 0 diversity alone.  A slot whose remaining gain is not above
+    ``eps`` times its own ``L_ii`` is never taken by gain: once no slot is, the rest of the list is filled by pool score with gain
+    0 and flag 512.  ``gain`` is the determinant ratio a slot won with; ``-1`` / ``-inf`` / ``-inf`` once the live slots run out.
+    The native header states every rounding.  ``status``: ``DPP_FLAGS``; it stays on the device -- nothing here synchronises with
+    the host."""
+    checked = [(pool_idx, torch.int64, "pool_idx"), (pool_score, torch.float32, "pool_score"), (table, torch.float32, "table")]
+    if quality is not None:
+        checked.append((quality, torch.float32, "quality"))
+    for t, dt, name in checked:
+        if t.dtype != dt:
+            raise ValueError(f"newsreclib_amd: `{name}` must be {dt}, got {t.dtype}")
+    if pool_idx.dim() != 2 or pool_score.shape != pool_idx.shape or table.dim() != 2:
+        raise ValueError(f"newsreclib_amd: pool_idx (B, N), pool_score (B, N) and table (V, D) expected, got {tuple(pool_idx.shape)}, "
+                         f"{tuple(pool_score.shape)} and {tuple(table.shape)}")
+    if quality is not None and quality.shape != pool_idx.shape:
+        raise ValueError(f"newsreclib_amd: quality {tuple(pool_idx.shape)} expected, one entry per pool slot, got {tuple(quality.shape)}")
+    if similarity not in MMR_SIMILARITIES:
+        raise ValueError(f"newsreclib_amd: similarity is one of {sorted(MMR_SIMILARITIES)}, got {similarity!r}")
+    B, N, V, D, k = int(pool_idx.shape[0]), int(pool_idx.shape[1]), int(table.shape[0]), int(table.shape[1]), int(k)
+    if N > MMR_MAX_POOL:
+        raise NotImplementedError(f"newsreclib_amd: dpp_rerank takes a pool of at most {MMR_MAX_POOL} slots (got {N})")
+    if k > DPP_MAX_K:
+        raise NotImplementedError(f"newsreclib_amd: dpp_rerank lists at most {DPP_MAX_K} news (got k = {k})")
+    if not 1 <= k <= N:
+        raise ValueError(f"newsreclib_amd: k in [1, N = {N}] expected, got {k}")
+    if not 0.0 <= float(alpha) < float("inf"):
+        raise ValueError(f"newsreclib_amd: alpha finite and >= 0 expected, got {alpha}")
+    if not 0.0 <= float(eps) < 1.0:
+        raise ValueError(f"newsreclib_amd: eps in [0, 1) expected, got {eps}")
+    pool_idx, pool_score, table = _chk(pool_idx, torch.int64, "pool_idx"), _chk(pool_score, torch.float32, "pool_score"), \
+        _chk(table, torch.float32, "table")
+    if quality is not None:
+        quality = _chk(quality, torch.float32, "quality")
+    lib = _lib.load()
+    dev = pool_idx.device
+    idx, score, status = _topk_outputs(B, k, dev)
+    gain = torch.empty((B, k), dtype=torch.float32, device=dev)
+    _lib.check(lib.nrl_dpp_rerank(pool_idx.data_ptr(), pool_score.data_ptr(), quality.data_ptr() if quality is not None else None,
+                                  table.data_ptr() if V else None, B, N, V, D, k, float(alpha), float(eps),
+                                  MMR_SIMILARITIES[similarity], int(bool(normalize)), idx.data_ptr(), score.data_ptr(), gain.data_ptr(),
+                                  status.data_ptr(), _stream()), "nrl_dpp_rerank")
+    return idx, score, gain, status
+
+
 def class_targets(hist_idx: torch.Tensor, hist_off: torch.Tensor, row_class: torch.Tensor, S: int, k: Optional[int] = None):
     """The class targets ``calibrated_rerank`` takes -> (B, S) fp32: the class counts of each user's ragged history (``hist_idx``:
     the concatenated table rows, ``hist_off`` (B + 1) its offsets; ``row_class`` (V) the class of every row).  A history row
