@@ -1038,6 +1038,43 @@ int nrl_impression_metrics(const float* preds, const float* targets, const int64
                            const int64_t* hist_offsets, int64_t n_hist, const int32_t* top_k, int32_t n_k, int32_t* rank,
                            float* rows, double* sums, int64_t* count, int32_t* status, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- a grid of ensemble weights in one pass over the impressions (symbols added to ABI v19).  Replaces: one full evaluation per
+ * (categ_weight, sent_weight) point of manner_module.py:152-204 -- the reference, too, re-scores and re-ranks everything per point.
+ * nrl_manner_zscores: nrl_manner_scores with the combination left out.  out (k, N) fp32: out[t * N + cand_offsets[b] + c] = the
+ *   z-score of candidate c of impression b under table t, flat and ragged in cand_offsets order (N = cand_offsets[B], the length
+ *   of cand_idx); no padded block.  Row t has the bits nrl_manner_scores gives table t alone under weight 1.  The same quirks (one
+ *   candidate, zero variance, an empty history: non-finite), the same clamping of indices, the same limits; candidates beyond
+ *   max_cand or outside [0, N) are not written.
+ * nrl_grid_metrics: nrl_impression_metrics for G score vectors that are linear combinations of T component vectors.  comp (T, N)
+ *   fp32, T in [1, 4]; weights (G, T) fp32 ON THE DEVICE, G in [1, 4096]; targets, cand_offsets, the aspects, hist_offsets, top_k
+ *   and status exactly as nrl_impression_metrics (same limits, same flags).  The score of candidate i under config g, over t
+ *   ascending: terms with weights[g, t] == 0 are skipped (a NaN component cannot poison a config that does not use it), the first
+ *   remaining term is the product w * comp[t, i], every later one fma(w, comp[t, i], acc) -- nrl_manner_scores's rounding; a row
+ *   of zeros scores +0 everywhere.
+ *   rows (G, B, n_cols fp32, nullable): row (g, b) has the bits nrl_impression_metrics writes for impression b when fed config
+ *     g's scores.  preds (G, N fp32, nullable): those scores (a flagged impression's are not written).
+ *   sums (G, n_cols doubles) and count (ONE int64), nullable together: ADDS, per config, the column sums of its rows by the fixed
+ *     reduction of nrl_impression_metrics (same bits), and once the number of unflagged impressions (it does not depend on g).
+ *   A flagged impression writes zero rows under every config and is absent from every sum and from count.
+ *   configs_per_block: 0 = nrl_grid_metrics_configs_per_block(B, G), the plan (from G and B alone: about 2048 workgroups); a
+ *     positive value overrides it.  No value changes a bit of the results.
+ *   Workspace: nrl_grid_metrics_workspace_size (the name keeps it out of the *_workspace_bytes table), 256-byte aligned; it holds
+ *   the (G, B, n_cols) rows only when the caller keeps none: caller_rows != 0 says that `rows` will be given and leaves them out.  B == 0 returns success without a launch; sizes beyond the limits return
+ *   NRL_E_INVALID.  Three launches whatever G; no float atomics, no allocation, no host synchronisation. */
+#define NRL_GRID_MAX_COMPONENTS 4
+#define NRL_GRID_MAX_CONFIGS 4096
+int nrl_manner_zscores(const float* const* tables, int32_t k, int64_t V, const int64_t* hist_idx, const int64_t* hist_offsets,
+                       const int64_t* cand_idx, const int64_t* cand_offsets, int64_t N, int64_t B, int32_t max_cand, int32_t D,
+                       float* out, void* stream);
+int32_t nrl_grid_metrics_configs_per_block(int64_t B, int32_t G);
+size_t nrl_grid_metrics_workspace_size(int64_t B, int32_t G, int32_t n_aspects, int32_t n_k, int32_t caller_rows);
+int nrl_grid_metrics(const float* comp, int32_t T, const float* weights, int32_t G, const float* targets, const int64_t* cand_offsets,
+                     int64_t N, int64_t B, int32_t n_aspects, const int64_t* cand_aspects0, const int64_t* hist_aspects0,
+                     int32_t num_classes0, const int64_t* cand_aspects1, const int64_t* hist_aspects1, int32_t num_classes1,
+                     const int64_t* hist_offsets, int64_t n_hist, const int32_t* top_k, int32_t n_k, int32_t configs_per_block,
+                     float* rows, float* preds, double* sums, int64_t* count, int32_t* status, void* ws, size_t ws_bytes,
+                     void* stream);
+
 /* ---- full-catalogue top-k recommendation (symbols added to ABI v19; nothing of the reference is replaced: it can only re-rank the
  * candidates an impression lists).
  * nrl_topk_scores: for each of B users the k rows of `table` with the highest dot product with the user's vector, without ever

@@ -304,6 +304,13 @@ SIGNATURES = {
     "nrl_impression_metrics": (c_int32, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int32, c_void_p, c_void_p, c_int32,
                                          c_void_p, c_void_p, c_int32, c_void_p, c_int64, POINTER(c_int32), c_int32, c_void_p,
                                          c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "nrl_manner_zscores": (c_int32, [POINTER(c_void_p), c_int32, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64,
+                                     c_int32, c_int32, c_void_p, c_void_p]),
+    "nrl_grid_metrics_configs_per_block": (c_int32, [c_int64, c_int32]),
+    "nrl_grid_metrics_workspace_size": (c_size_t, [c_int64, c_int32, c_int32, c_int32, c_int32]),
+    "nrl_grid_metrics": (c_int32, [c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_void_p, c_int64, c_int64, c_int32, c_void_p,
+                                   c_void_p, c_int32, c_void_p, c_void_p, c_int32, c_void_p, c_int64, POINTER(c_int32), c_int32,
+                                   c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "nrl_topk_scores_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int32, c_int32, c_int32]),
     "nrl_topk_scores": (c_int32, [c_void_p, c_void_p, c_int64, c_int64, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_int32,
                                   c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),

@@ -579,6 +579,19 @@ class MannerVectorCache(_ImpressionCache):
         return manner_scores(self.vectors, self.weights, hist_idx.to(dev).long(), hist_off, cand_idx.to(dev).long(), cand_off,
                              max_cand)
 
+    @torch.no_grad()
+    def zscores(self, hist_idx: torch.Tensor, hist_sizes: torch.Tensor, cand_idx: torch.Tensor, cand_sizes: torch.Tensor) -> torch.Tensor:
+        """(T, N) standardised scores of every loaded sub-model, flat in candidate order: what ``scores`` combines with
+        ``self.weights``, uncombined (``ops_manner.manner_zscores``, one launch).  The components ``evaluate_weight_grid`` hands
+        to ``metrics.GridStreamingMetrics``; sizes on the host as in ``scores``."""
+        from .ops_manner import manner_zscores
+        if self.vectors is None:
+            self.build()
+        dev = self.table.device
+        max_cand = int(cand_sizes.max())                       # the true largest count: no impression is truncated
+        hist_off, cand_off = ragged_offsets(hist_sizes, dev), ragged_offsets(cand_sizes, dev)
+        return manner_zscores(self.vectors, hist_idx.to(dev).long(), hist_off, cand_idx.to(dev).long(), cand_off, max_cand)
+
     def _step_loss(self, scores: torch.Tensor, meta: Dict) -> torch.Tensor:
         return scores.new_zeros(())                            # MANNeR has no loss
 
@@ -873,6 +886,46 @@ def evaluate_impressions(cache: NewsVectorCache, impressions: Sequence[Dict], ba
         if ncls and cat(tj).numel() and cat(hj).numel():
             logs.update(aspect_metrics(cat(1), cat(tj), cat(hj), cat(3), cat(4), ncls, top_k_list, prefix=name))
     return logs
+
+
+def evaluate_weight_grid(cache, impressions: Sequence[Dict], weights, batch_size: int = 512, top_k_list: Sequence[int] = (5, 10),
+                         num_categ_classes: Optional[int] = None, num_sent_classes: Optional[int] = None) -> Dict:
+    """``evaluate_impressions(..., device_metrics=True)`` for a whole grid of ensemble weights in one pass over the impressions
+    -> ``metrics.GridStreamingMetrics.compute()``: {"weights", "columns", "values" (G, columns)}, row g being, to the bit, the
+    means ``evaluate_impressions`` returns for an ensemble whose sub-model weights are ``weights[g]`` (no "auc", no "loss").
+    ``weights`` (G, T): one entry per LOADED sub-model of ``cache.module``, in ``module.submodels()`` order (the CR-Module
+    first, where the reference's weight is 1) -- so the module must be built with every sub-model the grid is to cover, at any
+    non-zero weight; a weight of 0 in a row leaves that sub-model out of the row, as the reference's ``if categ_weight != 0``.
+    Batches exactly as ``evaluate_impressions``; per batch one ``cache.zscores``, one ``GridStreamingMetrics.update`` and no
+    device-to-host copy; one read at the end."""
+    from .metrics import GridStreamingMetrics
+    if not hasattr(cache, "zscores"):
+        raise TypeError(f"evaluate_weight_grid needs a cache with `zscores` (MannerVectorCache): the grid combines the standardised "
+                        f"scores of an ensemble's sub-models, and {type(cache).__name__} has none")
+    n_sub = len(cache.weights)
+    w = torch.as_tensor(weights, dtype=torch.float32)
+    if w.dim() != 2 or w.shape[1] != n_sub:
+        raise ValueError(f"evaluate_weight_grid: every weight row needs one entry per loaded sub-model, in module.submodels() order: "
+                         f"{n_sub} here, got weights of shape {tuple(w.shape)}; build the module with every sub-model the grid is "
+                         "to cover (any non-zero weight loads it)")
+    grid = GridStreamingMetrics(w, top_k_list, num_categ_classes, num_sent_classes)
+    dev = cache.table.device
+    empty = torch.empty(0, dtype=torch.int64, device=dev)
+
+    def attr(idx, name):
+        return cache.table.attrs[name].index_select(0, idx) if name in cache.table.attrs else empty
+
+    for lo in range(0, len(impressions), batch_size):
+        chunk = impressions[lo:lo + batch_size]
+        hs = torch.tensor([len(i["hist"]) for i in chunk])
+        cs = torch.tensor([len(i["cand"]) for i in chunk])
+        hist_idx = torch.cat([torch.as_tensor(i["hist"]) for i in chunk]).to(dev).long()
+        cand_idx = torch.cat([torch.as_tensor(i["cand"]) for i in chunk]).to(dev).long()
+        labels = torch.cat([torch.as_tensor(i["labels"]).float() for i in chunk]).to(dev)
+        comp = cache.zscores(hist_idx, hs, cand_idx, cs)
+        grid.update(comp, (None, None, labels, cs, hs, attr(cand_idx, "category"), attr(cand_idx, "sentiment"),
+                           attr(hist_idx, "category"), attr(hist_idx, "sentiment")))
+    return grid.compute() or {"weights": w.tolist(), "columns": [], "values": [[] for _ in range(w.shape[0])]}
 
 
 def format_recommendations(user_ids: Sequence, news_idx: torch.Tensor, scores: torch.Tensor,

@@ -335,3 +335,87 @@ class StreamingMetrics:
                     out[f"{p}_div@{k}"] = vals[f"{p}_div@{k}"]
                     out[f"{p}_pers@{k}"] = vals[f"{p}_pers@{k}"]
         return out
+
+
+class GridStreamingMetrics:
+    """``StreamingMetrics`` for a grid of ensemble weights: G weight rows over T score components are ranked and scored in ONE
+    ``nrl_grid_metrics`` launch per batch, into a (G, columns) float64 accumulator.  ``update(comp, step_output)`` takes the
+    batch's (T, N) components (``MannerVectorCache.zscores``) and the tuple ``model_step`` returns (its ``preds`` slot is not
+    read: every row of the grid has its own); ``compute()`` returns ``{"weights": (G, T) list, "columns": [...], "values":
+    (G, columns) float64 list}`` with ``values = sums / count``, row g being to the bit what a ``StreamingMetrics`` fed row g's
+    scores accumulates.  The weights are checked on the host once, here (``ops.grid_weights``).  ``update`` performs no
+    device-to-host transfer; ``compute`` reads the status word first and raises ``ValueError`` when the kernel refused an
+    impression.  There is no AUC: the global AUC is a sort over every (score, target) pair of the epoch PER ROW, so it needs all G
+    flat score vectors kept -- G x 2.7 M floats on a MIND-small-dev epoch, 4.8 GB at G = 441; evaluate the rows that matter with
+    ``evaluate_impressions`` for it."""
+
+    def __init__(self, weights, top_k_list: Sequence[int] = (5, 10), num_categ_classes: Optional[int] = None,
+                 num_sent_classes: Optional[int] = None):
+        from . import ops
+        self.weights = ops.grid_weights(weights)
+        self.top_k_list = tuple(int(k) for k in top_k_list)
+        self.num_classes = {"categ": num_categ_classes, "sent": num_sent_classes}
+        self.reset()
+
+    def reset(self) -> None:
+        self.prefixes: Optional[Tuple[str, ...]] = None
+        self.sums = self.count = self.status = self._dev_weights = None
+
+    def _alloc(self, prefixes, device) -> None:
+        from . import ops
+        self.prefixes = tuple(prefixes)
+        self.columns = ops.metrics_columns(self.top_k_list, self.prefixes)
+        self.sums = torch.zeros((self.weights.shape[0], len(self.columns)), dtype=torch.float64, device=device)
+        self.count = torch.zeros(1, dtype=torch.int64, device=device)
+        self.status = torch.zeros(1, dtype=torch.int32, device=device)
+        self._dev_weights = self.weights.pin_memory().to(device, non_blocking=True)      # (a pageable copy would synchronise)
+
+    def update(self, comp: torch.Tensor, step_output: Sequence) -> None:
+        from . import ops
+        (_, _, targets, cand_news_size, hist_news_size, target_categories, target_sentiments, hist_categories,
+         hist_sentiments, *_) = step_output
+        if not comp.is_cuda:
+            raise RuntimeError(f"newsreclib_amd: GridStreamingMetrics.update needs GPU components (got {comp.device}); there is no "
+                               "CPU path")
+        if comp.dim() != 2 or comp.shape[0] != self.weights.shape[1]:
+            raise ValueError(f"GridStreamingMetrics.update: the weight rows have {self.weights.shape[1]} entries, the batch "
+                             f"carries components of shape {tuple(comp.shape)}")
+        dev = comp.device
+        given = {"categ": (target_categories, hist_categories), "sent": (target_sentiments, hist_sentiments)}
+        prefixes = tuple(p for p in ("categ", "sent") if self.num_classes[p] and given[p][0].numel())
+        if self.prefixes is None:
+            self._alloc(prefixes, dev)
+        elif prefixes != self.prefixes:
+            raise ValueError(f"GridStreamingMetrics.update: this step carries the aspects {prefixes}, the accumulator was started "
+                             f"with {self.prefixes}")
+        aspects = [(given[p][0].to(dev).long(), given[p][1].to(dev).long(), self.num_classes[p]) for p in prefixes]
+        ops.grid_metrics(comp.detach().float(), self._dev_weights, targets.detach().to(dev).float(), _offsets(cand_news_size, dev),
+                         self.top_k_list, aspects, _offsets(hist_news_size, dev) if aspects else None, status=self.status,
+                         sums=self.sums, count=self.count)
+
+    def merge(self, other: "GridStreamingMetrics") -> "GridStreamingMetrics":
+        """Adds another accumulator of the same grid and configuration (a second evaluation stream over other impressions)."""
+        if (other.top_k_list != self.top_k_list or other.num_classes != self.num_classes
+                or not torch.equal(other.weights, self.weights)):
+            raise ValueError("GridStreamingMetrics.merge: the two accumulators were configured differently")
+        if other.prefixes is None:
+            return self
+        if self.prefixes is None:
+            self._alloc(other.prefixes, other.sums.device)
+        elif other.prefixes != self.prefixes:
+            raise ValueError(f"GridStreamingMetrics.merge: aspects {other.prefixes} against {self.prefixes}")
+        self.sums += other.sums.to(self.sums.device)
+        self.count += other.count.to(self.sums.device)
+        self.status |= other.status.to(self.sums.device)
+        return self
+
+    def compute(self) -> Dict:
+        from . import ops
+        if self.prefixes is None:
+            return {}
+        flags = int(self.status)                   # the one read of the status word
+        if flags:
+            raise ValueError("GridStreamingMetrics: the metrics kernel refused input: " +
+                             "; ".join(msg for bit, msg in ops.METRICS_FLAGS.items() if flags & bit))
+        n = int(self.count)
+        return {"weights": self.weights.tolist(), "columns": list(self.columns), "values": (self.sums / max(n, 1)).tolist()}

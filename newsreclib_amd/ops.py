@@ -710,6 +710,110 @@ def impression_metrics(preds: torch.Tensor, targets: torch.Tensor, cand_offsets:
     return rank, rows, status
 
 
+# ---- a grid of ensemble weights in one pass (nrl_metrics.hip: mt_grid_kernel) ---------------------------------------------------
+GRID_MAX_COMPONENTS, GRID_MAX_CONFIGS = 4, 4096
+
+
+def grid_weights(weights, n_components: Optional[int] = None) -> torch.Tensor:
+    """The weight rows of a grid, checked on the HOST -> (G, T) fp32 CPU tensor.  ``ValueError`` for a row of zeros (it would
+    score every candidate 0: no ranking to evaluate), a non-finite weight or rows of the wrong length; ``NotImplementedError``
+    beyond ``GRID_MAX_COMPONENTS`` / ``GRID_MAX_CONFIGS``."""
+    w = torch.as_tensor(weights, dtype=torch.float32).detach().cpu()
+    if w.dim() != 2 or w.shape[0] < 1 or w.shape[1] < 1:
+        raise ValueError(f"newsreclib_amd: weights must be (G, T) with at least one row and one component, got {tuple(w.shape)}")
+    G, T = w.shape
+    if n_components is not None and T != int(n_components):
+        raise ValueError(f"newsreclib_amd: every weight row needs one entry per component: {int(n_components)}, got {T}")
+    if T > GRID_MAX_COMPONENTS or G > GRID_MAX_CONFIGS:
+        raise NotImplementedError(f"newsreclib_amd: a weight grid takes at most {GRID_MAX_COMPONENTS} components and "
+                                  f"{GRID_MAX_CONFIGS} rows per call; got ({G}, {T})")
+    if not bool(torch.isfinite(w).all()):
+        raise ValueError("newsreclib_amd: non-finite weight in the grid")
+    zero = (w == 0).all(1)
+    if bool(zero.any()):
+        raise ValueError(f"newsreclib_amd: weight row {int(zero.nonzero()[0])} of the grid is all zeros")
+    return w.contiguous()
+
+
+def grid_metrics(comp: torch.Tensor, weights, targets: torch.Tensor, cand_offsets: torch.Tensor, top_k: Sequence[int],
+                 aspects: Sequence[Tuple[torch.Tensor, torch.Tensor, int]] = (), hist_offsets: Optional[torch.Tensor] = None,
+                 status: Optional[torch.Tensor] = None, sums: Optional[torch.Tensor] = None, count: Optional[torch.Tensor] = None,
+                 want_rows: bool = False, want_preds: bool = False, configs_per_block: int = 0):
+    """``nrl_grid_metrics``: ``impression_metrics`` for the G score vectors ``weights[g] . comp`` of one batch of ragged impressions
+    -> (rows (G, B, cols) fp32 | None, preds (G, N) fp32 | None, status).  ``comp`` (T, N): the components (``manner_zscores``);
+    ``weights`` (G, T): a host tensor or nested list, checked by ``grid_weights`` and uploaded, or a GPU fp32 tensor that the
+    caller has checked that way (nothing here reads the device).  A term with weight 0 is skipped, so a NaN component does not
+    reach a row that does not use it.  ``sums`` (G, cols float64) / ``count`` (1 int64) are accumulated into: ``sums[g]`` gets what
+    ``impression_metrics`` adds when fed row g's scores, to the bit; ``count`` once.  Everything else as ``impression_metrics``.
+    ``configs_per_block`` overrides the launch plan (0: from G and B); it changes no result."""
+    lib = _lib.load()
+    comp, targets = _chk(comp, torch.float32, "comp"), _chk(targets, torch.float32, "targets")
+    cand_offsets = _chk(cand_offsets, torch.int64, "cand_offsets")
+    if comp.dim() != 2 or targets.dim() != 1:
+        raise ValueError("newsreclib_amd: comp (T, N) and flat targets (N) expected")
+    T, N = int(comp.shape[0]), int(comp.shape[1])
+    B = int(cand_offsets.numel()) - 1
+    if targets.numel() != N or B < 0:
+        raise ValueError("newsreclib_amd: comp (T, N), targets of N entries and cand_offsets of B + 1 entries expected")
+    dev = comp.device
+    if torch.is_tensor(weights) and weights.is_cuda:
+        weights = _chk(weights, torch.float32, "weights")
+        if weights.dim() != 2 or weights.shape[1] != T:
+            raise ValueError(f"newsreclib_amd: every weight row needs one entry per component: {T}, got {tuple(weights.shape)}")
+        if T > GRID_MAX_COMPONENTS or weights.shape[0] > GRID_MAX_CONFIGS or weights.shape[0] < 1:
+            raise NotImplementedError(f"newsreclib_amd: a weight grid takes at most {GRID_MAX_COMPONENTS} components and 1 to "
+                                      f"{GRID_MAX_CONFIGS} rows per call; got {tuple(weights.shape)}")
+    else:
+        weights = grid_weights(weights, T).pin_memory().to(dev, non_blocking=True)      # (a pageable copy would synchronise)
+    G = int(weights.shape[0])
+    top_k = [int(k) for k in top_k]
+    if len(top_k) > METRICS_MAX_NK or any(not 1 <= k <= METRICS_MAX_K for k in top_k):
+        raise ValueError(f"newsreclib_amd: at most {METRICS_MAX_NK} top_k values, each in [1, {METRICS_MAX_K}]; got {top_k}")
+    if len(aspects) > 2:
+        raise ValueError("newsreclib_amd: at most two aspects per call")
+    asp, n_hist = [], 0
+    if aspects:
+        if hist_offsets is None:
+            raise ValueError("newsreclib_amd: aspects need hist_offsets")
+        hist_offsets = _chk(hist_offsets, torch.int64, "hist_offsets")
+        if hist_offsets.numel() != B + 1:
+            raise ValueError("newsreclib_amd: hist_offsets must have B + 1 entries")
+        n_hist = int(aspects[0][1].numel())
+        for ca, ha, ncls in aspects:
+            ca, ha = _chk(ca, torch.int64, "cand_aspects"), _chk(ha, torch.int64, "hist_aspects")
+            if ca.numel() != N or ha.numel() != n_hist or not 2 <= int(ncls) <= METRICS_MAX_CLASSES:
+                raise ValueError(f"newsreclib_amd: every aspect needs N candidate ids, one history length and 2 <= num_classes <= "
+                                 f"{METRICS_MAX_CLASSES}; got {ca.numel()} / {ha.numel()} ids, num_classes {ncls}")
+            asp.append((ca, ha, int(ncls)))
+    cols = 1 + len(top_k) * (1 + 2 * len(asp))
+    if status is None:
+        status = torch.zeros(1, dtype=torch.int32, device=dev)
+    status = _chk(status, torch.int32, "status")
+    if (sums is None) != (count is None):
+        raise ValueError("newsreclib_amd: sums and count go together")
+    if sums is not None:
+        sums, count = _chk(sums, torch.float64, "sums"), _chk(count, torch.int64, "count")
+        if tuple(sums.shape) != (G, cols) or count.numel() != 1:
+            raise ValueError(f"newsreclib_amd: sums must be ({G}, {cols}) and count one entry")
+    if int(configs_per_block) < 0:
+        raise ValueError("newsreclib_amd: configs_per_block >= 0 (0: the plan)")
+    rows = torch.zeros((G, B, cols), dtype=torch.float32, device=dev) if want_rows else None
+    preds = torch.zeros((G, N), dtype=torch.float32, device=dev) if want_preds else None
+    if B == 0:
+        return rows, preds, status
+    ws = workspace(lib.nrl_grid_metrics_workspace_size(B, G, len(asp), len(top_k), int(want_rows)), dev)
+    ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
+    a0 = asp[0] if len(asp) > 0 else (None, None, 0)
+    a1 = asp[1] if len(asp) > 1 else (None, None, 0)
+    ks = (ctypes.c_int32 * max(len(top_k), 1))(*top_k)
+    _lib.check(lib.nrl_grid_metrics(comp.data_ptr(), T, weights.data_ptr(), G, targets.data_ptr(), cand_offsets.data_ptr(), N, B,
+                                    len(asp), ptr(a0[0]), ptr(a0[1]), a0[2], ptr(a1[0]), ptr(a1[1]), a1[2],
+                                    ptr(hist_offsets) if asp else None, n_hist, ks, len(top_k), int(configs_per_block), ptr(rows),
+                                    ptr(preds), ptr(sums), ptr(count), status.data_ptr(), ws.data_ptr(), ws.numel(), _stream()),
+               "nrl_grid_metrics")
+    return rows, preds, status
+
+
 # ---- full-catalogue top-k recommendation (nrl_topk.hip) ------------------------------------------------------------------------
 TOPK_MAX_K, TOPK_MAX_D = 128, 1024
 TOPK_FLAGS = {1: "an exclusion index is outside [0, V) (ignored)",

@@ -1,10 +1,11 @@
-"""``torch.autograd.Function`` wrappers of the MANNeR entry points (``nrl_manner.hip``).  Same conventions as ``ops.py``: GPU tensors
-only, no eager fallback, nothing synchronises with the host.
+"""``torch.autograd.Function`` wrappers of the MANNeR entry points (``nrl_manner.hip``, ``nrl_manner_zscores.hip``).  Same
+conventions as ``ops.py``: GPU tensors only, no eager fallback, nothing synchronises with the host.
 
 ``SupConEmbedFn`` / ``SupConEmbedLoss``  the A-Module loss (manner_a_module.py:151-153): pytorch-metric-learning's ``SupConLoss``
     over ``DotProductSimilarity(normalize_embeddings=False)`` of a batch of embeddings with integer labels; loss and gradient come
     from one call, the backward scales the saved gradient.
 ``manner_scores``                        the ensemble scorer (manner_module.py:152-204) over up to three cached news-vector tables.
+``manner_zscores``                       its per-table z-scores, flat and uncombined: the components of a weight grid (``ops.grid_metrics``).
 """
 from __future__ import annotations
 
@@ -92,4 +93,33 @@ def manner_scores(tables: Sequence[torch.Tensor], weights: Sequence[float], hist
     wts = (ctypes.c_float * k)(*[float(w) for w in weights])
     _lib.check(lib.nrl_manner_scores(ptrs, wts, k, V, hist_idx.data_ptr(), hist_offsets.data_ptr(), cand_idx.data_ptr(),
                                      cand_offsets.data_ptr(), B, int(max_cand), D, out.data_ptr(), _stream()), "nrl_manner_scores")
+    return out
+
+
+def manner_zscores(tables: Sequence[torch.Tensor], hist_idx: torch.Tensor, hist_offsets: torch.Tensor, cand_idx: torch.Tensor,
+                   cand_offsets: torch.Tensor, max_cand: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """(T, N) per-table z-scores ``zscore(mean(tables[t][hist]) . tables[t][cand])``, flat and ragged in ``cand_offsets`` order
+    (N = ``cand_idx.numel()``): what ``manner_scores`` combines, written out instead -- row t has the bits of ``manner_scores``
+    with table t alone and weight 1.  The components ``ops.grid_metrics`` evaluates a grid of weight rows over.  ``max_cand`` as
+    in ``manner_scores``; a fresh ``out`` starts at zero (candidates beyond ``max_cand`` are not written)."""
+    lib = _lib.load()
+    k = len(tables)
+    if not 1 <= k <= MAX_TABLES:
+        raise ValueError(f"newsreclib_amd: 1 to {MAX_TABLES} news-vector tables")
+    tables = [_chk(t, torch.float32, "news-vector table") for t in tables]
+    V, D = tables[0].shape
+    if any(t.shape != (V, D) for t in tables) or D % 4 or not 4 <= D <= MAX_DIM:
+        raise ValueError(f"newsreclib_amd: the tables must share one (V, D) shape with D a multiple of 4 up to {MAX_DIM}")
+    hist_idx, cand_idx = _chk(hist_idx, torch.int64, "hist_idx"), _chk(cand_idx, torch.int64, "cand_idx")
+    hist_offsets, cand_offsets = _chk(hist_offsets, torch.int64, "hist_offsets"), _chk(cand_offsets, torch.int64, "cand_offsets")
+    B, N = int(hist_offsets.numel()) - 1, int(cand_idx.numel())
+    if B < 0 or cand_offsets.numel() != B + 1 or not 1 <= int(max_cand) <= MAX_CAND:
+        raise ValueError(f"newsreclib_amd: offsets of B + 1 entries each and 1 <= max_cand <= {MAX_CAND}")
+    if out is None:
+        out = torch.zeros((k, N), dtype=torch.float32, device=tables[0].device)
+    elif _chk(out, torch.float32, "out").shape != (k, N):
+        raise ValueError(f"newsreclib_amd: out must be ({k}, {N})")
+    ptrs = (ctypes.c_void_p * k)(*[t.data_ptr() for t in tables])
+    _lib.check(lib.nrl_manner_zscores(ptrs, k, V, hist_idx.data_ptr(), hist_offsets.data_ptr(), cand_idx.data_ptr(),
+                                      cand_offsets.data_ptr(), N, B, int(max_cand), D, out.data_ptr(), _stream()), "nrl_manner_zscores")
     return out
