@@ -123,8 +123,8 @@ int nrl_additive_attention_fwd(const NrlAddAttParams* p, const float* y, int64_t
                                int32_t save_for_backward, float* out, void* ws, size_t ws_bytes, void* stream) {
   (void)save_for_backward;
   NRL_TRY(addatt_check(p, groups, len));
+  if (groups == 0) return NRL_OK;   // (an empty tensor has no storage: its pointers are null)
   NRL_REQUIRE(y && out && ((uintptr_t)y & 15) == 0, "additive_attention_fwd: bad arguments");
-  if (groups == 0) return NRL_OK;
   const int D = p->dim, Q = p->query_dim;
   const int64_t M = groups * len;
   AddAttWs w;
@@ -144,8 +144,8 @@ int nrl_additive_attention_bwd(const NrlAddAttParams* p, const NrlAddAttGrads* g
                                void* stream) {
   NRL_TRY(addatt_check(p, groups, len));
   NRL_REQUIRE(g && g->att_weight && g->att_bias && g->att_query, "null additive-attention gradient pointer");
+  if (groups == 0) return NRL_OK;   // (the gradient buffers are added into: nothing to add)
   NRL_REQUIRE(y && d_out && d_y, "additive_attention_bwd: null argument");
-  if (groups == 0) return NRL_OK;
   const int D = p->dim, Q = p->query_dim;
   const int64_t M = groups * len;
   AddAttWs w;
@@ -166,7 +166,8 @@ size_t nrl_linear_act_workspace_bytes(int64_t m, int32_t n, int32_t k) {
 
 int nrl_linear_act_fwd(const float* a, const float* w, const float* bias, int64_t m, int32_t n, int32_t k,
                        int32_t act, float* c, void* ws, size_t ws_bytes, void* stream) {
-  NRL_REQUIRE(a && w && c && m >= 0 && n > 0 && k > 0 && k % 4 == 0 && n % 4 == 0,
+  // (m == 0: the input and the output are empty tensors without storage -- null pointers)
+  NRL_REQUIRE(w && (m == 0 || (a && c)) && m >= 0 && n > 0 && k > 0 && k % 4 == 0 && n % 4 == 0,
               "linear_act_fwd: bad arguments (n, k multiples of 4)");
   NRL_REQUIRE(act >= 0 && act <= 2, "linear_act: act must be 0 (none), 1 (tanh) or 2 (relu)");
   NRL_REQUIRE((((uintptr_t)a | (uintptr_t)w) & 15) == 0, "linear_act_fwd: operands misaligned");
@@ -183,7 +184,7 @@ int nrl_linear_act_fwd(const float* a, const float* w, const float* bias, int64_
 int nrl_linear_act_bwd(const float* a, const float* w, const float* c, const float* d_c, int64_t m, int32_t n,
                        int32_t k, int32_t act, float* d_a, float* d_w, float* d_bias, void* ws, size_t ws_bytes,
                        void* stream) {
-  NRL_REQUIRE(a && w && c && d_c && d_w && m >= 0 && n > 0 && k > 0 && k % 4 == 0 && n % 4 == 0,
+  NRL_REQUIRE(w && d_w && (m == 0 || (a && c && d_c)) && m >= 0 && n > 0 && k > 0 && k % 4 == 0 && n % 4 == 0,
               "linear_act_bwd: bad arguments");
   NRL_REQUIRE(act >= 0 && act <= 2, "linear_act: act must be 0 (none), 1 (tanh) or 2 (relu)");
   LinearActWs lw;

@@ -132,6 +132,13 @@ static int cnn_rp_images(const NrlCnnParams* p, const CnnShape& s, const CnnWs& 
 
 static size_t conv_t_plane_elems(int D, int F, int W) { return (size_t)2 * D * ((W * F + 31) / 32 * 32); }
 
+// The tanh / d_pre buffer also holds the live-row list of the table gradient once d_pre is dead (cnn_dx_table_grad): sized for both,
+// so that the backward has room at every shape the forward accepts (M Q < 2 M + 9: one short title at a narrow Q).
+static size_t cnn_t_floats(const CnnShape& s) {
+  const size_t t = (size_t)s.M * s.Q, live = s.M > 0 ? live_compact_ints(s.M) : 0;
+  return t > live ? t : live;
+}
+
 // (the dense buffers carry W rows of slack on both sides, nrl_conv.h; dx needs none, kept symmetric)
 static void cnn_layout(Arena& a, const CnnShape& s, CnnWs* o) {
   const size_t slack_x = (size_t)s.W * s.D, slack_c = (size_t)s.W * s.F;
@@ -139,7 +146,7 @@ static void cnn_layout(Arena& a, const CnnShape& s, CnnWs* o) {
   o->dx = a.take_after<float>(slack_x, (size_t)s.M * s.D + 2 * slack_x);
   o->c = a.take_after<float>(slack_c, (size_t)s.M * s.F + 2 * slack_c);
   o->dc = a.take_after<float>(slack_c, (size_t)s.M * s.F + 2 * slack_c);
-  o->t = a.take<float>((size_t)s.M * s.Q);       // t / d_pre
+  o->t = a.take<float>(cnn_t_floats(s));         // t / d_pre, then the live-row list
   o->w = a.take<float>((size_t)s.M);
   o->planes_conv = a.take<uint16_t>(split_weight_elems(s.F, s.W * s.D));
   o->planes_att = a.take<uint16_t>(split_weight_elems(s.Q, s.F));
@@ -275,8 +282,7 @@ static int cnn_dx_table_grad(const NrlCnnParams* p, const CnnShape& s, const Cnn
   static const bool live_env = [] { const char* e = getenv("NRL_LIVE_ROWS"); return !(e != nullptr && e[0] == '0'); }();
   if (sorted_positions != nullptr && rpd != nullptr && live_env) {
     // dx for the LIVE token rows only (id != 0), compact in position order: the padding id has no table gradient and
-    // nothing else reads dx.  The list of live positions goes into the tanh / d_pre buffer (dead by now).
-    NRL_REQUIRE((size_t)s.M * s.Q >= live_compact_ints(s.M), "cnn_encoder_bwd: scratch for the live-row list");
+    // nothing else reads dx.  The list of live positions goes into the tanh / d_pre buffer (dead by now; cnn_t_floats has the room).
     const int32_t *list = nullptr, *cidx = nullptr, *n_live = nullptr;
     NRL_TRY(live_compact(ids, s.M, reinterpret_cast<int32_t*>(w.t), &list, &cidx, &n_live, st));
     if (dc_pl) {
@@ -545,7 +551,8 @@ int nrl_cnn_mhsa_encoder_bwd(const NrlCnnParams* cp, const NrlCnnGrads* cg, cons
 
 int nrl_embedding_rows_fwd(const float* table, const int64_t* ids, int64_t n_ids, int32_t dim, double p_row,
                            uint64_t seed, uint32_t stream_id, float* out, void* stream) {
-  NRL_REQUIRE(table && ids && out && n_ids >= 0 && dim > 0, "embedding_rows_fwd: bad arguments");
+  // (n_ids == 0: ids and out are empty tensors without storage -- null pointers)
+  NRL_REQUIRE(table && (n_ids == 0 || (ids && out)) && n_ids >= 0 && dim > 0, "embedding_rows_fwd: bad arguments");
   NRL_REQUIRE(p_row >= 0.0 && p_row < 1.0, "p_row must be in [0, 1)");
   return embedding_rows_fwd(table, ids, n_ids, dim, make_dropout(p_row, seed, stream_id), 1, out,
                             (hipStream_t)stream);
@@ -553,7 +560,7 @@ int nrl_embedding_rows_fwd(const float* table, const int64_t* ids, int64_t n_ids
 
 int nrl_embedding_rows_bwd(const float* d_out, const int64_t* ids, int64_t n_ids, int32_t dim, double p_row,
                            uint64_t seed, uint32_t stream_id, float* d_table, void* stream) {
-  NRL_REQUIRE(d_out && ids && d_table && n_ids >= 0 && dim > 0, "embedding_rows_bwd: bad arguments");
+  NRL_REQUIRE(d_table && (n_ids == 0 || (d_out && ids)) && n_ids >= 0 && dim > 0, "embedding_rows_bwd: bad arguments");
   NRL_REQUIRE(p_row >= 0.0 && p_row < 1.0, "p_row must be in [0, 1)");
   return embedding_rows_bwd(d_out, ids, n_ids, dim, make_dropout(p_row, seed, stream_id), d_table,
                             (hipStream_t)stream);

@@ -483,7 +483,9 @@ __global__ void __launch_bounds__(256)
       }
     }
     if (RG == 1) {
-      o4[c4] = acc;
+      // (129 <= D4 <= 255: the threads past D4 are idle -- rg = 1 -- yet walk a column of their own, tid - D4; their zero must
+      //  not be stored beside the owner's sum)
+      if (rg == 0) o4[c4] = acc;
     } else {
       part[tid] = acc;
       __syncthreads();
@@ -636,7 +638,9 @@ __global__ void __launch_bounds__(256)
       if (rg == 0) part[cc] = acc;
       __syncthreads();
       const float* pf = reinterpret_cast<const float*>(part);
-      if (tid < 4 * cpp) atomicAdd(dq_a + 4 * (c4 - cc) + tid, pf[tid]);
+      // (RG > 1 goes up to cpp = 128 columns, 512 floats: more than the 256 threads when Q > 256 -- one float per thread left
+      //  dq_a[256 .. Q) of 256 < Q <= 512 without its sum)
+      for (int i = tid; i < 4 * cpp; i += 256) atomicAdd(dq_a + 4 * (c4 - cc) + i, pf[i]);
       __syncthreads();
     } else {
       atomicAdd(dq_a + 4 * c4 + 0, acc.x);

@@ -1,5 +1,9 @@
 """GPU parity of the LSTUR path (BASELINE config 5) against the CPU oracle and the golden vectors made
-from the reference's own components.  Every call goes through the C ABI."""
+from the reference's own components.  Every call goes through the C ABI.
+
+The op tests here compare a handful of shapes with the float32 oracle on random inputs.  The shape predicates of
+``CnnEncoderFn``, ``GruFn`` and ``EmbeddingRowsFn`` -- both sides of every one, against float64, on inputs no ReLU decides
+differently on -- are swept in tests/test_gpu_lstur_naml_sweep.py."""
 import numpy as np
 import pytest
 import torch

@@ -1,5 +1,9 @@
 """GPU parity of the generic blocks (standalone additive attention, linear + activation) and of the NAML
-module against the CPU oracle and the golden vectors made from the reference's own components."""
+module against the CPU oracle and the golden vectors made from the reference's own components.
+
+``AdditiveAttentionFn`` and ``LinearActFn`` are swept over their shape predicates against float64 in
+tests/test_gpu_lstur_naml_sweep.py; its ``relu`` cases are grid-valued, so no gate flips and none has to be counted as
+``test_linear_act_matches_torch`` does on random inputs."""
 import numpy as np
 import pytest
 import torch
