@@ -1479,6 +1479,33 @@ int nrl_catalogue_ranks(const float* user_vec, const float* table, int64_t B, in
                         int32_t* out_rank /* n_targets */, float* out_score /* n_targets */, int32_t* out_ranked /* B */,
                         int32_t* status, void* ws, size_t ws_bytes, void* stream);
 
+/* nrl_topk_window_scores / nrl_catalogue_window_ranks: nrl_topk_scores / nrl_catalogue_ranks with a time window of its own per user.
+ *   Row v belongs to user u's population iff it does under the plain entries' rules (inside V, eligible, not on u's exclusion list,
+ *   a score that is not NaN) and win_lo[u] <= row_time[v] <= win_hi[u].
+ *     row_time (V) int32, win_lo / win_hi (B) int32, in any one unit; the interval is closed; (INT32_MIN, INT32_MAX) is no window;
+ *     win_lo[u] > win_hi[u] is an empty window and a legitimate answer: a list of -1 / -inf, population 0, every rank 0, no flag.
+ *   Scores, order (ties by ascending row, +0 for -0), slots beyond the population, determinism and the status bits are those of the
+ *     plain entries; the score bits are theirs too (the window is applied to what the dot product has produced, never inside it).
+ *     A target outside its owner's window has rank 0 and score -inf without a flag, like an ineligible target; NRL_TOPK_E_NAN is
+ *     set only for a NaN score of a row inside that user's window.
+ *   A table tile none of whose eligible rows has a time inside the union of the windows of the workgroup's 64 users is not read and
+ *     not multiplied: on a table stored in time order the cost falls with the width of the windows.
+ *   Workspace: nrl_topk_scores_workspace_bytes(B, V, D, k, slices) / nrl_catalogue_ranks_workspace_size(B, V, D, n_targets, slices),
+ *     with the layouts of the plain entries.
+ *   Checks (NRL_E_INVALID before any launch): those of the plain entry in its order, then row_time with V > 0, then win_lo and
+ *     win_hi with B > 0. */
+int nrl_topk_window_scores(const float* user_vec, const float* table, int64_t B, int64_t V, int32_t D, int32_t k,
+                           const int32_t* row_time /* V */, const int32_t* win_lo /* B */, const int32_t* win_hi /* B */,
+                           const int64_t* excl_idx, const int64_t* excl_off, const uint8_t* eligible, int32_t slices,
+                           int64_t* out_idx /* B, k */, float* out_score /* B, k */, int32_t* status, void* ws, size_t ws_bytes,
+                           void* stream);
+int nrl_catalogue_window_ranks(const float* user_vec, const float* table, int64_t B, int64_t V, int32_t D,
+                               const int64_t* tgt_idx, const int64_t* tgt_off, int64_t n_targets,
+                               const int32_t* row_time /* V */, const int32_t* win_lo /* B */, const int32_t* win_hi /* B */,
+                               const int64_t* excl_idx, const int64_t* excl_off, const uint8_t* eligible, int32_t slices,
+                               int32_t* out_rank /* n_targets */, float* out_score /* n_targets */, int32_t* out_ranked /* B */,
+                               int32_t* status, void* ws, size_t ws_bytes, void* stream);
+
 /* nrl_catalogue_interest_ranks / nrl_catalogue_relu_ranks / nrl_catalogue_pooled_ranks: nrl_catalogue_ranks under the scores of
  *   nrl_topk_interest_scores (MINER: interests (B, K, D), gate (B, K, D) or null, mode 0 max / 1 mean / 2 weighted), of
  *   nrl_topk_relu_scores (DKN: q (B, Hd), proj (V, Hd), w2 (Hd), b2 (1), all on the device) and of nrl_topk_pooled_scores (NPA:

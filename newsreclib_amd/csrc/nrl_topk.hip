@@ -12,6 +12,9 @@
 //   TkCount  (rank)    tkc_count_kernel    tkic_count_kernel    tkec_count_kernel   tkrc_count_kernel   tkpc_count_kernel
 //   TkSelectCapped     tkcap_scores_kernel -                    tkecap_scores_kernel -                  -
 //     (top-k, at most m rows per class; k <= 64; merged by tk_merge_capped_kernel)
+// tkw_scores_kernel / tkwc_count_kernel (nrl_topk_window_scores / nrl_catalogue_window_ranks: a time window per user) run TkDot with
+// TkSelect / TkCount under a walk of their own, tkw_walk: tk_walk with the window ANDed into the eligibility the consumer sees and
+// table tiles outside every window of the workgroup skipped.  The plain kernels' text is untouched by it; see its section.
 // 256 threads, one workgroup per (slice of V, tile of users).  Per table tile of TK_BV = 128 rows:
 //   * the PRODUCER leaves the tile's scores in LDS.  TkDot: exact-fp32 MFMA (v_mfma_f32_16x16x4_f32) over LDS tiles of both
 //     operands (k-major, double-buffered, register-staged global loads as nrl_gemm.h); every score is ONE accumulator chain over
@@ -1843,7 +1846,15 @@ __device__ __forceinline__ int tkc_wave_sum(int v) {
   return v;
 }
 
-__global__ __launch_bounds__(64) void tkc_finish_kernel(TkcArgs A) {
+// per-user time windows (the section below): row v is in user u's population only when win_lo[u] <= row_time[v] <= win_hi[u]
+struct TkwFields {
+  const int32_t* row_time;                     // (V)
+  const int32_t* win_lo;                       // (B) closed bounds; lo > hi: an empty window
+  const int32_t* win_hi;
+};
+
+// one wave per user; W: the windowed entry's one extra test of a target (null for every other entry)
+__device__ __forceinline__ void tkc_finish_user(const TkcArgs& A, const TkwFields* W) {
   const int64_t u = blockIdx.x;
   const int lane = threadIdx.x;
   int64_t xs, xn, ts;
@@ -1876,6 +1887,10 @@ __global__ __launch_bounds__(64) void tkc_finish_kernel(TkcArgs A) {
   }
   if (__ballot(bad) && lane == 0) atomicOr(A.status, NRL_TOPK_E_EXCLUDE);
   if (!mine || !inside || excluded || (A.eligible && !A.eligible[row])) return;
+  if (W) {                                            // a target outside its owner's window: rank 0 / -inf, no flag
+    const int32_t t = W->row_time[row];
+    if (t < W->win_lo[u] || t > W->win_hi[u]) return;
+  }
   const float s = A.tscore[ts + lane];
   if (s != s) return;
   int above = 0;
@@ -1883,6 +1898,132 @@ __global__ __launch_bounds__(64) void tkc_finish_kernel(TkcArgs A) {
   A.out_rank[ts + lane] = 1 + above;
   A.out_score[ts + lane] = tk_unkey(score_key(s));    // (-0 comes back as +0, as from tk_merge_kernel)
 }
+
+__global__ __launch_bounds__(64) void tkc_finish_kernel(TkcArgs A) { tkc_finish_user(A, nullptr); }
+
+// ---- per-user time windows: nrl_topk_window_scores, nrl_catalogue_window_ranks ----------------------------------------------------
+// Row v belongs to user u's population iff it does under the plain entries' rules and win_lo[u] <= row_time[v] <= win_hi[u] (int32,
+// closed; lo > hi is an empty window: an empty list, population 0, every rank 0 and no flag).  The window is a property of the WALK:
+// TkDot, TkSelect and TkCount run as they are, so a score has the bits of the plain entries, and tkw_walk is tk_walk with
+//   * the users' bounds staged once (lo / hi [slots]; an empty window for the slots past the last user) and their union
+//     [min lo, max hi] over the non-empty windows, read back from LDS behind the prologue's barrier: the same in every thread;
+//   * per table tile the 128 row times staged next to `el` by the threads that fill `el`; the wave that serves user ul ANDs
+//     lo <= t <= hi into the two eligibility booleans of its lanes before the consumer sees them;
+//   * the TILE SKIP: a thread whose row is inside V, eligible and inside the union window writes the tile's number into hit[vt & 1];
+//     after one barrier every thread reads the same word, and a tile nobody marked is left before its product, its table read and
+//     its per-user loop.  Such a tile holds no row of any user's population, so it contributes no entry and no count: the skip
+//     cannot change a result.  Two words, by the tile's parity: a thread that has skipped tile vt marks tile vt + 1 in the other
+//     word while a slower one still reads vt's, and nobody reaches tile vt + 2 before everyone passed the barrier of vt + 1.  A
+//     workgroup whose windows are all empty walks no tile and flushes empty lists / zero counts.
+// A user whose window misses the tile costs its wave two loads and a ballot.  The merge is tk_merge_kernel (a partial list never
+// holds a row outside the window), the target scores are tkc_target_kernel's, and the finish makes the one extra test above.
+struct TkWindow {
+  int32_t* tt;                                 // [TK_BV] row times of the table tile
+  int32_t* lo;                                 // [slots]
+  int32_t* hi;                                 // [slots]
+  int32_t* hit;                                // [2] (+ 2 words of padding): the last tile somebody marked, by parity
+  __device__ __forceinline__ TkWindow(unsigned char* p, int slots) {
+    tt = reinterpret_cast<int32_t*>(p);
+    lo = tt + TK_BV;
+    hi = lo + slots;
+    hit = hi + slots;
+  }
+};
+// behind the consumer's arrays, which end 4-byte aligned for any `slots` and 16-byte aligned for TK_BU
+constexpr size_t tkw_lds_bytes(int slots) { return (size_t)TK_BV * 4 + (size_t)slots * 8 + 16; }
+static_assert(tk_lds_bytes(1, TK_BU, 1) % 16 == 0 && (TK_BU * 8) % 16 == 0 && TKC_LDS % 16 == 0 && tkw_lds_bytes(TK_BU) % 16 == 0,
+              "the window's arrays start and end 16-byte aligned behind either consumer, for every k");
+// 1040 B: two workgroups of the scores kernel fit a CU up to k = 58 (plain: 60), more than 64 KB from k = 27 on (plain: 29)
+static_assert(2 * (tk_lds_bytes(1, TK_BU, 58) + tkw_lds_bytes(TK_BU)) <= 160 * 1024 &&
+                  2 * (tk_lds_bytes(1, TK_BU, 59) + tkw_lds_bytes(TK_BU)) > 160 * 1024,
+              "two workgroups of the windowed scores kernel fit a CU up to k = 58");
+static_assert(tk_lds_bytes(1, TK_BU, 26) + tkw_lds_bytes(TK_BU) <= 64 * 1024 && tk_lds_bytes(1, TK_BU, 27) + tkw_lds_bytes(TK_BU) > 64 * 1024,
+              "the windowed scores kernel needs the LDS attribute from k = 27 on");
+static_assert(2 * (TKC_LDS + tkw_lds_bytes(TK_BU)) <= 160 * 1024, "two workgroups of the windowed count kernel fit a CU");
+static_assert(tk_lds_bytes(1, TK_BU, NRL_TOPK_MAX_K) + tkw_lds_bytes(TK_BU) <= 160 * 1024, "the largest windowed layout fits");
+
+constexpr int32_t TKW_MIN = -0x7FFFFFFF - 1, TKW_MAX = 0x7FFFFFFF;
+
+template <class Args, class Producer, class Consumer>
+__device__ __forceinline__ void tkw_walk(const Args& A, Producer& P, Consumer& C, const TkWindow& W) {
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int slots = P.slots();
+  const int sl = (int)(blockIdx.x % (unsigned)A.slices);
+  const int64_t u0 = (int64_t)(blockIdx.x / (unsigned)A.slices) * slots;
+  const int nu = A.B - u0 < slots ? (int)(A.B - u0) : slots;
+  int v_begin, nvt;
+  tk_slice(A, sl, v_begin, nvt);
+
+  P.stage(A, u0, nu);
+  if (tid < slots) {
+    W.lo[tid] = tid < nu ? A.win_lo[u0 + tid] : TKW_MAX;
+    W.hi[tid] = tid < nu ? A.win_hi[u0 + tid] : TKW_MIN;
+  }
+  if (tid < 2) W.hit[tid] = 0;
+  C.prologue(A, u0, nu, slots);                       // (its barrier also publishes lo, hi and hit)
+  int32_t ulo = TKW_MAX, uhi = TKW_MIN;               // the union of the non-empty windows, from LDS: the same in every thread
+  for (int i = 0; i < nu; ++i) {
+    const int32_t l = W.lo[i], h = W.hi[i];
+    if (l <= h) {
+      ulo = l < ulo ? l : ulo;
+      uhi = h > uhi ? h : uhi;
+    }
+  }
+  ulo = __builtin_amdgcn_readfirstlane(ulo);
+  uhi = __builtin_amdgcn_readfirstlane(uhi);
+  if (ulo > uhi) nvt = 0;                             // every window is empty
+  const int ul_begin = Producer::first(wave), ul_end = Producer::end(wave, nu);
+  bool nan = false;
+
+  for (int vt = 0; vt < nvt; ++vt) {
+    const int v0 = v_begin + vt * TK_BV;
+    if (tid < TK_BV) {
+      const int64_t v = (int64_t)v0 + tid;
+      const bool e = v < A.V && (!A.eligible || A.eligible[v]);
+      const int32_t t = v < A.V ? A.row_time[v] : 0;
+      C.el[tid] = e ? 1 : 0;
+      W.tt[tid] = t;
+      if (e && ulo <= t && t <= uhi) W.hit[vt & 1] = vt + 1;
+    }
+    __syncthreads();
+    if (W.hit[vt & 1] != vt + 1) continue;            // (uniform: one LDS word behind a barrier)
+    P.tile(A, v0, nu);
+
+    const bool e_0 = C.el[lane] != 0, e_1 = C.el[64 + lane] != 0;
+    const int32_t t_0 = W.tt[lane], t_1 = W.tt[64 + lane];
+    for (int ul = ul_begin; ul < ul_end; ul += Producer::STEP) {
+      if (P.skip(ul)) continue;
+      const int32_t lo = W.lo[ul], hi = W.hi[ul];
+      const bool w_0 = e_0 && lo <= t_0 && t_0 <= hi, w_1 = e_1 && lo <= t_1 && t_1 <= hi;
+      if (!__ballot(w_0 || w_1)) continue;
+      C.user(P.row(ul), ul, A.excl_idx, v0, w_0, w_1, lane, nan);
+    }
+    __syncthreads();                                  // the score tile, `el` and `tt` are free for the next tile
+  }
+
+  if (nan && lane == 0) atomicOr(A.status, NRL_TOPK_E_NAN);
+  wave_lds_sync();
+  for (int ul = ul_begin; ul < ul_end; ul += Producer::STEP) C.flush(A, ul, u0 + ul, sl, lane);
+}
+
+__global__ __launch_bounds__(TK_THREADS) void tkw_scores_kernel(TkWith<TkArgs, TkwFields> A) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char tk_smem[];
+  TkDot P(tk_smem);
+  TkSelect C(P.rest, TK_BU, A.k);
+  TkWindow W(P.rest + tk_lds_bytes(0, TK_BU, A.k), TK_BU);
+  tkw_walk(A, P, C, W);
+}
+
+__global__ __launch_bounds__(TK_THREADS) void tkwc_count_kernel(TkWith<TkcArgs, TkwFields> A) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char tk_smem[];
+  TkDot P(tk_smem);
+  TkCount C(P.rest, TK_BU);
+  TkWindow W(P.rest + tkc_lds_bytes(TK_BU), TK_BU);
+  tkw_walk(A, P, C, W);
+}
+
+__global__ __launch_bounds__(64) void tkwc_finish_kernel(TkWith<TkcArgs, TkwFields> A) { tkc_finish_user(A, &A); }
 
 // ---- greedy MMR re-ranking of a pool (nrl_mmr_rerank) ------------------------------------------------------------------------------
 // One workgroup per user.  The pool's Gram matrix is ceil(N / 64) calls of tk_tile_accumulate<1, true>: the A rows are pool slots
@@ -2631,8 +2772,18 @@ static int tk_launch(const char* who, void (*kernel)(Args), Args& A, int32_t sli
 
 // The launches of a rank entry: slots and owners, `target` (the entry's target kernel: a callable that launches it), the count
 // kernel with `smem` bytes of dynamic LDS over `blocks` workgroups, the finish.
-template <class Args, class Target>
-static int tkc_launch(void (*count)(Args), Args& A, int64_t blocks, size_t smem, void* stream, Target target) {
+struct TkcFinish {
+  void operator()(const TkcArgs& A, hipStream_t st) const { tkc_finish_kernel<<<(unsigned)A.B, 64, 0, st>>>(A); }
+};
+struct TkcFinishWindow {
+  TkwFields F;
+  void operator()(const TkcArgs& A, hipStream_t st) const {
+    tkwc_finish_kernel<<<(unsigned)A.B, 64, 0, st>>>(TkWith<TkcArgs, TkwFields>{A, F});
+  }
+};
+template <class Args, class Target, class Finish = TkcFinish>
+static int tkc_launch(void (*count)(Args), Args& A, int64_t blocks, size_t smem, void* stream, Target target,
+                      Finish finish = Finish{}) {
   hipStream_t st = (hipStream_t)stream;
   if (A.n_targets > 0) {
     tkc_init_kernel<<<(unsigned)A.n_targets, 64, 0, st>>>(static_cast<const TkcArgs&>(A));
@@ -2647,8 +2798,15 @@ static int tkc_launch(void (*count)(Args), Args& A, int64_t blocks, size_t smem,
     count<<<(unsigned)blocks, TK_THREADS, smem, st>>>(A);
     NRL_LAUNCH_CHECK();
   }
-  tkc_finish_kernel<<<(unsigned)A.B, 64, 0, st>>>(static_cast<const TkcArgs&>(A));
+  finish(static_cast<const TkcArgs&>(A), st);
   NRL_LAUNCH_CHECK();
+  return NRL_OK;
+}
+
+// the checks of a windowed entry, after those of the entry it windows
+static int tk_window_check(const char* who, int64_t B, int64_t V, const TkwFields& win) {
+  NRL_REQUIRE(win.row_time || V == 0, "%s: row_time is required", who);
+  NRL_REQUIRE((win.win_lo && win.win_hi) || B == 0, "%s: win_lo and win_hi are required", who);
   return NRL_OK;
 }
 
@@ -2671,9 +2829,10 @@ size_t nrl_topk_scores_workspace_bytes(int64_t B, int64_t V, int32_t D, int32_t 
   return measure_workspace<unsigned long long*>([&](Arena& a, auto* w) { tk_layout(a, B, V, k, slices, TK_BU, w); });
 }
 
-// nrl_topk_scores (`cap` null) and nrl_topk_scores_capped: one sequence of checks, one layout; the cap picks the kernels
+// nrl_topk_scores (`cap` and `win` null), nrl_topk_scores_capped and nrl_topk_window_scores: one sequence of checks, one layout; the
+// cap or the window picks the kernels
 static int tk_scores_entry(const char* who, const float* user_vec, const float* table, int64_t B, int64_t V, int32_t D, int32_t k,
-                           const TkCapFields* cap, const int64_t* excl_idx, const int64_t* excl_off, const uint8_t* eligible,
+                           const TkCapFields* cap, const TkwFields* win, const int64_t* excl_idx, const int64_t* excl_off, const uint8_t* eligible,
                            int32_t slices, int64_t* out_idx, float* out_score, int32_t* status, void* ws, size_t ws_bytes,
                            void* stream) {
   NRL_REQUIRE(B >= 0 && V >= 0 && D >= 0 && slices >= 0, "%s: negative size", who);
@@ -2682,9 +2841,14 @@ static int tk_scores_entry(const char* who, const float* user_vec, const float* 
   if (cap) NRL_TRY(tk_cap_check(who, V, k, cap->row_class, cap->m));
   if (B == 0) return NRL_OK;
   NRL_REQUIRE(out_idx && out_score && user_vec && (V == 0 || table), "%s: null argument", who);
+  if (win) NRL_TRY(tk_window_check(who, B, V, *win));
   unsigned long long* partial;
   NRL_TRY(carve_workspace(ws, ws_bytes, [&](Arena& a) { tk_layout(a, B, V, k, slices, TK_BU, &partial); }));
   TkArgs A = tk_args(user_vec, table, B, V, D, k, excl_idx, excl_off, eligible, partial, out_idx, out_score, status);
+  if (win) {
+    TkWith<TkArgs, TkwFields> W{A, *win};
+    return tk_launch(who, tkw_scores_kernel, W, slices, 1, TK_BU, stream, tkw_lds_bytes(TK_BU));
+  }
   if (!cap) return tk_launch(who, tk_scores_kernel, A, slices, 1, TK_BU, stream);
   TkWith<TkArgs, TkCapFields> C{A, *cap};
   return tk_launch(who, tkcap_scores_kernel, C, slices, 1, TK_BU, stream, 0, TkMergeCapped{*cap});
@@ -2693,7 +2857,7 @@ static int tk_scores_entry(const char* who, const float* user_vec, const float* 
 int nrl_topk_scores(const float* user_vec, const float* table, int64_t B, int64_t V, int32_t D, int32_t k, const int64_t* excl_idx,
                     const int64_t* excl_off, const uint8_t* eligible, int32_t slices, int64_t* out_idx, float* out_score,
                     int32_t* status, void* ws, size_t ws_bytes, void* stream) {
-  return tk_scores_entry("topk_scores", user_vec, table, B, V, D, k, nullptr, excl_idx, excl_off, eligible, slices, out_idx, out_score,
+  return tk_scores_entry("topk_scores", user_vec, table, B, V, D, k, nullptr, nullptr, excl_idx, excl_off, eligible, slices, out_idx, out_score,
                          status, ws, ws_bytes, stream);
 }
 
@@ -2702,8 +2866,17 @@ int nrl_topk_scores_capped(const float* user_vec, const float* table, int64_t B,
                            const uint8_t* eligible, int32_t slices, int64_t* out_idx, float* out_score, int32_t* status, void* ws,
                            size_t ws_bytes, void* stream) {
   const TkCapFields cap{row_class, max_per_class};
-  return tk_scores_entry("topk_scores_capped", user_vec, table, B, V, D, k, &cap, excl_idx, excl_off, eligible, slices, out_idx,
+  return tk_scores_entry("topk_scores_capped", user_vec, table, B, V, D, k, &cap, nullptr, excl_idx, excl_off, eligible, slices, out_idx,
                          out_score, status, ws, ws_bytes, stream);
+}
+
+int nrl_topk_window_scores(const float* user_vec, const float* table, int64_t B, int64_t V, int32_t D, int32_t k,
+                           const int32_t* row_time, const int32_t* win_lo, const int32_t* win_hi, const int64_t* excl_idx,
+                           const int64_t* excl_off, const uint8_t* eligible, int32_t slices, int64_t* out_idx, float* out_score,
+                           int32_t* status, void* ws, size_t ws_bytes, void* stream) {
+  const TkwFields win{row_time, win_lo, win_hi};
+  return tk_scores_entry("topk_window_scores", user_vec, table, B, V, D, k, nullptr, &win, excl_idx, excl_off, eligible, slices,
+                         out_idx, out_score, status, ws, ws_bytes, stream);
 }
 
 // the workspace of nrl_catalogue_ranks: the gathered target rows and their scores and owners, then the per-slice counts
@@ -2764,25 +2937,49 @@ static int tkc_prepare(const char* who, TkcArgs& A, const float* user, const flo
   return NRL_OK;
 }
 
+// nrl_catalogue_ranks (`win` null) and nrl_catalogue_window_ranks: one sequence of checks, one layout; the window picks the kernels
+static int tkc_ranks_entry(const char* who, const float* user_vec, const float* table, int64_t B, int64_t V, int32_t D,
+                           const int64_t* tgt_idx, const int64_t* tgt_off, int64_t n_targets, const TkwFields* win,
+                           const int64_t* excl_idx, const int64_t* excl_off, const uint8_t* eligible, int32_t slices,
+                           int32_t* out_rank, float* out_score, int32_t* out_ranked, int32_t* status, void* ws, size_t ws_bytes,
+                           void* stream) {
+  NRL_REQUIRE(B >= 0 && V >= 0 && D >= 0 && slices >= 0 && n_targets >= 0, "%s: negative size", who);
+  NRL_TRY(tk_check(who, B, V, D, 1, excl_idx, excl_off));
+  NRL_TRY(tkc_check(who, n_targets, tgt_idx, tgt_off, status));
+  if (B == 0) return NRL_OK;
+  NRL_REQUIRE(out_ranked && user_vec && (V == 0 || table) && (n_targets == 0 || (tgt_idx && out_rank && out_score)),
+              "%s: null argument", who);
+  if (win) NRL_TRY(tk_window_check(who, B, V, *win));
+  TkWith<TkcArgs, TkwFields> A{};
+  int64_t blocks;
+  NRL_TRY(tkc_prepare(who, A, user_vec, table, B, V, D, D, true, tgt_idx, tgt_off, n_targets, excl_idx, excl_off, eligible, slices,
+                      TK_BU, out_rank, out_score, out_ranked, status, ws, ws_bytes, &blocks));
+  auto target = [&](hipStream_t st) {
+    tkc_target_kernel<<<(unsigned)ceil_div(n_targets, TK_BU), TK_THREADS, 0, st>>>(A);
+    NRL_LAUNCH_CHECK();
+    return NRL_OK;
+  };
+  if (!win) return tkc_launch(tkc_count_kernel, static_cast<TkcArgs&>(A), blocks, TKC_LDS, stream, target);
+  static_cast<TkwFields&>(A) = *win;
+  return tkc_launch(tkwc_count_kernel, A, blocks, TKC_LDS + tkw_lds_bytes(TK_BU), stream, target, TkcFinishWindow{*win});
+}
+
 int nrl_catalogue_ranks(const float* user_vec, const float* table, int64_t B, int64_t V, int32_t D, const int64_t* tgt_idx,
                         const int64_t* tgt_off, int64_t n_targets, const int64_t* excl_idx, const int64_t* excl_off,
                         const uint8_t* eligible, int32_t slices, int32_t* out_rank, float* out_score, int32_t* out_ranked,
                         int32_t* status, void* ws, size_t ws_bytes, void* stream) {
-  NRL_REQUIRE(B >= 0 && V >= 0 && D >= 0 && slices >= 0 && n_targets >= 0, "catalogue_ranks: negative size");
-  NRL_TRY(tk_check("catalogue_ranks", B, V, D, 1, excl_idx, excl_off));
-  NRL_TRY(tkc_check("catalogue_ranks", n_targets, tgt_idx, tgt_off, status));
-  if (B == 0) return NRL_OK;
-  NRL_REQUIRE(out_ranked && user_vec && (V == 0 || table) && (n_targets == 0 || (tgt_idx && out_rank && out_score)),
-              "catalogue_ranks: null argument");
-  TkcArgs A;
-  int64_t blocks;
-  NRL_TRY(tkc_prepare("catalogue_ranks", A, user_vec, table, B, V, D, D, true, tgt_idx, tgt_off, n_targets, excl_idx, excl_off,
-                      eligible, slices, TK_BU, out_rank, out_score, out_ranked, status, ws, ws_bytes, &blocks));
-  return tkc_launch(tkc_count_kernel, A, blocks, TKC_LDS, stream, [&](hipStream_t st) {
-    tkc_target_kernel<<<(unsigned)ceil_div(n_targets, TK_BU), TK_THREADS, 0, st>>>(A);
-    NRL_LAUNCH_CHECK();
-    return NRL_OK;
-  });
+  return tkc_ranks_entry("catalogue_ranks", user_vec, table, B, V, D, tgt_idx, tgt_off, n_targets, nullptr, excl_idx, excl_off,
+                         eligible, slices, out_rank, out_score, out_ranked, status, ws, ws_bytes, stream);
+}
+
+int nrl_catalogue_window_ranks(const float* user_vec, const float* table, int64_t B, int64_t V, int32_t D, const int64_t* tgt_idx,
+                               const int64_t* tgt_off, int64_t n_targets, const int32_t* row_time, const int32_t* win_lo,
+                               const int32_t* win_hi, const int64_t* excl_idx, const int64_t* excl_off, const uint8_t* eligible,
+                               int32_t slices, int32_t* out_rank, float* out_score, int32_t* out_ranked, int32_t* status, void* ws,
+                               size_t ws_bytes, void* stream) {
+  const TkwFields win{row_time, win_lo, win_hi};
+  return tkc_ranks_entry("catalogue_window_ranks", user_vec, table, B, V, D, tgt_idx, tgt_off, n_targets, &win, excl_idx, excl_off,
+                         eligible, slices, out_rank, out_score, out_ranked, status, ws, ws_bytes, stream);
 }
 
 // ---- the other scorers: each one's own checks and its fields, written once for its two entries ------------------------------------

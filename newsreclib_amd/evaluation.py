@@ -195,6 +195,63 @@ def _aspect_classes(cache, aspect: str) -> torch.Tensor:
     return got
 
 
+def _row_times(cache) -> torch.Tensor:
+    """The time of every news as the windowed entries take it: ``cache.table.attrs["time"]`` (one integer per news, in any unit)
+    as int32, converted once and kept on the cache.  The values must already fit int32: the conversion is one device op and
+    checking the range would cost a read-back, so a wider value (epoch milliseconds in int64) wraps silently -- rebase or rescale
+    such a column on the host first."""
+    if cache._row_time is None:
+        col = cache.table.attrs.get("time")
+        if not isinstance(col, torch.Tensor) or col.dim() != 1 or col.is_floating_point():
+            raise ValueError("newsreclib_amd: a time window needs an integer news attribute `time` with one value per news (or the "
+                             "times as the window's third member); the table has none")
+        cache._row_time = col.to(torch.int32)
+    return cache._row_time
+
+
+def _window_arrays(cache, window):
+    """``window`` = (win_lo, win_hi[, row_time]) of ``recommend`` / ``rank_clicks`` as ``ops.topk_window_scores`` takes it ->
+    (row_time, win_lo, win_hi), int32 on the table's device.  Host bounds go through pinned memory; nothing is read back."""
+    if not isinstance(window, (tuple, list)) or len(window) not in (2, 3):
+        raise ValueError("newsreclib_amd: window = (win_lo, win_hi) or (win_lo, win_hi, row_time)")
+    dev = cache.table.device
+    row_time = _row_times(cache) if len(window) == 2 else window[2]
+
+    def up(t, name):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.int32:
+            raise TypeError(f"newsreclib_amd: the window's `{name}` must be an int32 tensor")
+        return t if t.is_cuda else t.pin_memory().to(dev, non_blocking=True)
+
+    return up(row_time, "row_time"), up(window[0], "win_lo"), up(window[1], "win_hi")
+
+
+def user_windows(users: Sequence[Dict], before, after):
+    """The window of each user dictionary around its request: ``[time - before, time + after]`` in Python integers, clamped to
+    int32 (``None`` for a side: unbounded) -> (win_lo, win_hi) host int32 tensors.  ``ValueError`` when a user has no ``"time"``."""
+    lo, hi = [], []
+    for j, u in enumerate(users):
+        if "time" not in u:
+            raise ValueError(f"newsreclib_amd: a time window needs every user's request time: user {j} of the list has no \"time\"")
+        t = int(u["time"])
+        lo.append(ops.INT32_MIN if before is None else min(max(t - int(before), ops.INT32_MIN), ops.INT32_MAX))
+        hi.append(ops.INT32_MAX if after is None else min(max(t + int(after), ops.INT32_MIN), ops.INT32_MAX))
+    return torch.tensor(lo, dtype=torch.int32), torch.tensor(hi, dtype=torch.int32)
+
+
+def _window_refusal(who: str, cache) -> None:
+    """``NotImplementedError`` where the windowed walk has no kernel: only the plain dot-product producer runs under it."""
+    module = getattr(cache, "module", None)
+    kind = [a for a in ("multi_interest_scorer", "dnn_predictor_scorer", "personalized_pooling_scorer", "class_biased_scorer")
+            if getattr(module, a, False)]
+    if hasattr(cache, "recommend_ensemble"):
+        kind.append("z-scored ensemble (MannerVectorCache)")
+    if kind:
+        raise NotImplementedError(f"{who} serves the plain dot-product caches: {type(cache).__name__} over {type(module).__name__} "
+                                  f"is a `{kind[0]}`, and "
+                                  "the windowed walk (tkw_scores_kernel / tkwc_count_kernel) runs under the dot-product producer "
+                                  "alone; a windowed kernel for that scorer does not exist yet")
+
+
 class NewsVectorCache(_ImpressionCache):
     """Encode-once evaluation of a drop-in recommender (any of the module mirrors: NRMS, LSTUR, NAML, TANR,
     CenNewsRec, MINS -- whatever exposes ``news_encoder`` and ``score_news_vectors``)."""
@@ -204,6 +261,7 @@ class NewsVectorCache(_ImpressionCache):
         self.vectors: Optional[torch.Tensor] = None
         self.projection: Optional[torch.Tensor] = None      # (num_news, Hd): ``recommend_dnn``'s share of the table, built lazily
         self._row_class: Dict[str, torch.Tensor] = {}       # aspect -> (num_news) int32: ``recommend_capped``'s classes
+        self._row_time: Optional[torch.Tensor] = None       # (num_news) int32: the ``time`` column, for ``window=``
 
     @torch.no_grad()
     def build(self) -> torch.Tensor:
@@ -406,14 +464,21 @@ class NewsVectorCache(_ImpressionCache):
 
     @torch.no_grad()
     def recommend(self, hist_idx: torch.Tensor, hist_sizes: torch.Tensor, k: int, user_idx: Optional[torch.Tensor] = None,
-                  exclude_history: bool = True, eligible: Optional[torch.Tensor] = None):
+                  exclude_history: bool = True, eligible: Optional[torch.Tensor] = None, window=None):
         """The ``k`` news of the WHOLE table each user scores highest -> (news_idx (B, k) int64, scores (B, k) fp32, status):
         the module's ``user_vectors`` over the gathered history vectors (eval mode, restored afterwards), then
         ``ops.topk_scores`` against the cached table with the history as the exclusion list (``exclude_history``) and
         ``eligible`` (num_news, uint8 / bool: 0 = never recommended, e.g. the padding row 0).  Slots beyond the rows that
         qualify hold ``-1`` / ``-inf``; ``status`` (``ops.TOPK_FLAGS``) stays on the device.  ``hist_idx`` is a GPU tensor (the
-        library has no CPU path), ``hist_sizes`` a HOST tensor as ``evaluate_impressions`` builds it: nothing is read back."""
+        library has no CPU path), ``hist_sizes`` a HOST tensor as ``evaluate_impressions`` builds it: nothing is read back.
+
+        ``window`` = (win_lo, win_hi) or (win_lo, win_hi, row_time), int32, host or device: user ``b`` is recommended only news
+        with ``win_lo[b] <= time <= win_hi[b]`` (``ops.topk_window_scores``); without the third member the times are the table's
+        ``time`` column (``ValueError`` when it has none).  ``None`` is the call without it, launch for launch."""
+        times = None if window is None else _window_arrays(self, window)
         user, _, tail = self._dot_users("recommend", hist_idx, hist_sizes, user_idx, exclude_history, eligible, None)
+        if times is not None:
+            return ops.topk_window_scores(user, self.vectors, k, *times, *tail)
         return ops.topk_scores(user, self.vectors, k, *tail)
 
     @torch.no_grad()
@@ -471,7 +536,7 @@ class NewsVectorCache(_ImpressionCache):
     @torch.no_grad()
     def rank_clicks(self, hist_idx: torch.Tensor, hist_sizes: torch.Tensor, click_idx: torch.Tensor, click_sizes: torch.Tensor,
                     user_idx: Optional[torch.Tensor] = None, exclude_history: bool = True,
-                    eligible: Optional[torch.Tensor] = None):
+                    eligible: Optional[torch.Tensor] = None, window=None):
         """Where each user's held-out clicks land when the user is ranked against the WHOLE table -> (rank int32 (n_clicks),
         score fp32 (n_clicks), ranked int32 (B), status): ``recommend``'s user vectors, scores, order, exclusion of the history
         and ``eligible``, with ``ops.catalogue_ranks`` counting where ``recommend`` selects.  ``rank`` is the click's 1-based
@@ -479,9 +544,15 @@ class NewsVectorCache(_ImpressionCache):
         ineligible, outside the table); ``rank <= k`` exactly when the click is slot ``rank - 1`` of ``recommend(k)``.  At most
         ``ops.RANK_MAX_TARGETS`` clicks per user (``ValueError`` otherwise, from the host sizes).  Same contract as ``recommend``:
         ``hist_idx`` and ``click_idx`` on the GPU, ``hist_sizes`` and ``click_sizes`` on the host, nothing read back; ``status``
-        (``ops.RANK_FLAGS``) stays on the device.  ``metrics.full_rank_metrics`` turns the result into MRR / nDCG@k / recall@k."""
+        (``ops.RANK_FLAGS``) stays on the device.  ``metrics.full_rank_metrics`` turns the result into MRR / nDCG@k / recall@k.
+
+        ``window``: as for ``recommend`` (``ops.catalogue_window_ranks``): the population is the news inside the user's window,
+        and a click outside it has rank 0."""
+        times = None if window is None else _window_arrays(self, window)
         user, targets, tail = self._dot_users("rank_clicks",
                                               hist_idx, hist_sizes, user_idx, exclude_history, eligible, (click_idx, click_sizes))
+        if times is not None:
+            return ops.catalogue_window_ranks(user, self.vectors, *targets, *times, *tail)
         return ops.catalogue_ranks(user, self.vectors, *targets, *tail)
 
     @torch.no_grad()
@@ -943,7 +1014,7 @@ def format_recommendations(user_ids: Sequence, news_idx: torch.Tensor, scores: t
 def recommend_users(cache: NewsVectorCache, users: Sequence[Dict], k: int, batch_size: int = 512,
                     eligible: Optional[torch.Tensor] = None, cap: Optional[Tuple[str, int]] = None,
                     diversify: Optional[Tuple[int, float]] = None, calibrate: Optional[Dict] = None,
-                    dpp: Optional[Dict] = None) -> Dict[str, Dict[str, float]]:
+                    dpp: Optional[Dict] = None, window: Optional[Tuple[int, int]] = None) -> Dict[str, Dict[str, float]]:
     """``cache.recommend`` (``cache.recommend_interests`` where the cache's module is a ``multi_interest_scorer``,
     ``cache.recommend_dnn`` where it is a ``dnn_predictor_scorer``, ``cache.recommend_pooled`` where it is a
     ``personalized_pooling_scorer``: ``NpaFeatureCache``, whose users need ``user_idx``,
@@ -976,7 +1047,20 @@ def recommend_users(cache: NewsVectorCache, users: Sequence[Dict], k: int, batch
     ``k <= ops.DPP_MAX_K``) and ``cache.rerank_dpp(idx, score, k, alpha, eps=eps)`` -- greedy DPP inference by the cosine of the
     cached news vectors with quality ``exp(alpha * rel)``, the relevance min-max scaled -- picks the ``k`` that are listed.  It is
     a diversifier of its own, so together with ``diversify`` or ``calibrate`` it is a ``ValueError``.  The status word
-    (``ops.DPP_FLAGS``) is OR-ed in 16 bits up like theirs.  ``None`` is the path without it, launch for launch."""
+    (``ops.DPP_FLAGS``) is OR-ed in 16 bits up like theirs.  ``None`` is the path without it, launch for launch.
+
+    ``window`` = (before, after), in the unit of the table's ``time`` column: every user dictionary carries ``"time"`` (the time of
+    the request; ``ValueError`` otherwise) and is recommended only news published in ``[time - before, time + after]`` (``None``
+    for a side: unbounded), computed on the host and clamped to int32 (``user_windows``): ``cache.recommend(..., window=...)``.
+    The pool of ``diversify`` / ``calibrate`` / ``dpp`` comes from the windowed call.  ``NotImplementedError`` together with
+    ``cap`` and for every cache but a plain dot-product one: the windowed walk has no capped consumer and no other producer yet."""
+    if window is not None:
+        if cap is not None:
+            raise NotImplementedError("recommend_users(window=..., cap=...): the windowed walk runs the plain selecting consumer; a "
+                                      "windowed class-capped kernel (tkcap_scores_kernel under a window) does not exist yet")
+        _window_refusal("recommend_users(window=...)", cache)
+        win_lo, win_hi = user_windows(users, *window)
+        _row_times(cache)
     if dpp is not None:
         if diversify is not None or calibrate is not None:
             raise ValueError("recommend_users: `dpp` excludes `diversify` and `calibrate`: each of the three picks the k listed "
@@ -1039,7 +1123,11 @@ def recommend_users(cache: NewsVectorCache, users: Sequence[Dict], k: int, batch
             capped = getattr(cache, "recommend_ensemble_capped", None) or cache.recommend_capped
             rank = lambda hist, hs, k, **kw: capped(hist, hs, k, aspect, max_per_class, **kw)  # noqa: E731
         reranked = diversify is not None or calibrate is not None or dpp is not None
-        idx, score, status = rank(hist, hs, pool if reranked else k, user_idx=uidx, eligible=eligible)
+        if window is not None:
+            idx, score, status = cache.recommend(hist, hs, pool if reranked else k, user_idx=uidx, eligible=eligible,
+                                                 window=(win_lo[lo:lo + batch_size], win_hi[lo:lo + batch_size]))
+        else:
+            idx, score, status = rank(hist, hs, pool if reranked else k, user_idx=uidx, eligible=eligible)
         if dpp is not None:
             idx, score, _, dpp_status = cache.rerank_dpp(idx, score, k, dpp_alpha, eps=dpp_eps)
             status = status | (dpp_status << 16)
@@ -1065,7 +1153,8 @@ def recommend_users(cache: NewsVectorCache, users: Sequence[Dict], k: int, batch
 
 
 def evaluate_full_rank(cache: NewsVectorCache, users: Sequence[Dict], top_k_list: Sequence[int] = (5, 10), batch_size: int = 512,
-                       eligible: Optional[torch.Tensor] = None, ensemble: bool = False) -> Dict[str, float]:
+                       eligible: Optional[torch.Tensor] = None, ensemble: bool = False,
+                       until_request: bool = False) -> Dict[str, float]:
     """Full-catalogue ranking metrics of held-out clicks: ``cache.rank_clicks`` (``cache.rank_clicks_interests`` where the cache's
     module is a ``multi_interest_scorer``, ``cache.rank_clicks_dnn`` where it is a ``dnn_predictor_scorer``,
     ``cache.rank_clicks_pooled`` where it is a ``personalized_pooling_scorer``, ``cache.rank_clicks_biased`` -- the bias-free score --
@@ -1081,8 +1170,20 @@ def evaluate_full_rank(cache: NewsVectorCache, users: Sequence[Dict], top_k_list
     a cache without one), the warning worded from ``ops.ENSEMBLE_RANK_FLAGS``.  It is opt-in, where ``recommend_users`` picks
     ``recommend_ensemble`` by itself, because the z-score over the whole catalogue is a different number from the z-score over an
     impression's candidates that MANNeR's ``scores`` returns: the default must not silently change what ``rank_clicks`` means for
-    MANNeR, so without the flag ``MannerVectorCache.rank_clicks`` keeps refusing and says where to go."""
+    MANNeR, so without the flag ``MannerVectorCache.rank_clicks`` keeps refusing and says where to go.
+
+    ``until_request=True`` is the temporal protocol: every user dictionary carries ``"time"`` (``ValueError`` otherwise) and its
+    clicks are ranked against the news of the table's ``time`` column up to that time -- the window ``[INT32_MIN, time]`` of
+    ``cache.rank_clicks(..., window=...)`` -- not against news that did not exist yet.  Served and refused as
+    ``recommend_users(window=...)``."""
     from .metrics import full_rank_metrics
+    if until_request:
+        if ensemble:
+            raise NotImplementedError("evaluate_full_rank(until_request=True, ensemble=True): a window changes the population the "
+                                      "ensemble's statistics pass standardises over; a windowed tkec_count_kernel does not exist yet")
+        _window_refusal("evaluate_full_rank(until_request=True)", cache)
+        win_lo, win_hi = user_windows(users, None, 0)
+        _row_times(cache)
     if ensemble and not callable(getattr(cache, "rank_clicks_ensemble", None)):
         raise TypeError(f"evaluate_full_rank(ensemble=True) needs a cache with `rank_clicks_ensemble` (MannerVectorCache), got "
                         f"{type(cache).__name__}")
@@ -1102,7 +1203,11 @@ def evaluate_full_rank(cache: NewsVectorCache, users: Sequence[Dict], top_k_list
             cache.rank_clicks_biased if getattr(cache.module, "class_biased_scorer", False) else cache.rank_clicks
         if ensemble:
             rank_clicks = cache.rank_clicks_ensemble
-        rank, _, ranked, status = rank_clicks(hist, hs, clicks, cs, user_idx=uidx, eligible=eligible)
+        if until_request:
+            rank, _, ranked, status = cache.rank_clicks(hist, hs, clicks, cs, user_idx=uidx, eligible=eligible,
+                                                        window=(win_lo[lo:lo + batch_size], win_hi[lo:lo + batch_size]))
+        else:
+            rank, _, ranked, status = rank_clicks(hist, hs, clicks, cs, user_idx=uidx, eligible=eligible)
         ranks.append(rank)
         sizes.append(cs.pin_memory().to(dev, non_blocking=True))
         pops.append(ranked)

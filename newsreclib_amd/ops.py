@@ -893,17 +893,18 @@ def _run_topk(entry: str, s: _Scorer, k: int, excl_idx, excl_off, eligible, slic
     return idx, score, status
 
 
-def _run_ranks(entry: str, s: _Scorer, tgt_idx, tgt_off, excl_idx, excl_off, eligible, slices: int, extra=(), ws_lead=()):
+def _run_ranks(entry: str, s: _Scorer, tgt_idx, tgt_off, excl_idx, excl_off, eligible, slices: int, extra=(), ws_lead=(), after=()):
     """The rank entry ``entry`` under scorer ``s``; ``extra``: the outputs of its own between ``ranked`` and ``status``; ``ws_lead``
-    (with it the entry has a workspace function of its own): that function's arguments before B."""
+    (with it the entry has a workspace function of its own): that function's arguments before B; ``after``: the inputs of its own
+    between the targets and the exclusion lists."""
     lib = _lib.load()
     tgt_idx, tgt_off, n_tgt = _rank_targets(tgt_idx, tgt_off, s.B)
     excl_idx, excl_off, eligible = _topk_masks(excl_idx, excl_off, eligible, s.B, s.V)
     rank, score, ranked, status = _rank_outputs(n_tgt, s.B, s.dev)
     ws_size = getattr(lib, entry + "_workspace_size") if ws_lead else lib.nrl_catalogue_ranks_workspace_size
     ws = workspace(ws_size(*ws_lead, s.B, s.V, s.D, n_tgt, int(slices)), s.dev)
-    _lib.check(getattr(lib, entry)(*s.lead, *s.trail, tgt_idx.data_ptr(), tgt_off.data_ptr(), n_tgt, _ptr(excl_idx), _ptr(excl_off),
-                                   _ptr(eligible), int(slices), rank.data_ptr(), score.data_ptr(), ranked.data_ptr(),
+    _lib.check(getattr(lib, entry)(*s.lead, *s.trail, tgt_idx.data_ptr(), tgt_off.data_ptr(), n_tgt, *after, _ptr(excl_idx),
+                                   _ptr(excl_off), _ptr(eligible), int(slices), rank.data_ptr(), score.data_ptr(), ranked.data_ptr(),
                                    *(t.data_ptr() for t in extra), status.data_ptr(), ws.data_ptr(), ws.numel(), _stream()), entry)
     return rank, score, ranked, status
 
@@ -979,6 +980,53 @@ def catalogue_ranks(user_vec: torch.Tensor, table: torch.Tensor, tgt_idx: torch.
     slot ``rank - 1`` of the user's top-k list.  The (B, V) score matrix is never materialised.  ``status`` (``RANK_FLAGS``)
     stays on the device -- nothing here synchronises with the host."""
     return _run_ranks("nrl_catalogue_ranks", _dot_scorer(user_vec, table), tgt_idx, tgt_off, excl_idx, excl_off, eligible, slices)
+
+
+INT32_MIN, INT32_MAX = -2 ** 31, 2 ** 31 - 1
+
+
+def _window(user_vec, table, row_time, win_lo, win_hi):
+    """The three int32 arrays of a windowed entry: dtype (``TypeError``) and lengths (``ValueError``) are refused before anything
+    looks at a device, then the scorer's own checks and ``_chk`` -> (the scorer, the arrays' pointers, the tensors to keep alive)."""
+    B = int(user_vec.shape[0]) if user_vec.dim() else -1
+    V = int(table.shape[0]) if table.dim() else -1
+    named = ((row_time, "row_time", V, "table row"), (win_lo, "win_lo", B, "user"), (win_hi, "win_hi", B, "user"))
+    for t, name, n, what in named:
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.int32:
+            raise TypeError(f"newsreclib_amd: `{name}` must be an int32 tensor, got "
+                            f"{t.dtype if isinstance(t, torch.Tensor) else type(t).__name__}")
+    for t, name, n, what in named:
+        if t.dim() != 1 or t.numel() != n:
+            raise ValueError(f"newsreclib_amd: `{name}` must have one entry per {what} ({n}), got {tuple(t.shape)}")
+    s = _dot_scorer(user_vec, table)
+    keep = tuple(_chk(t, torch.int32, name) for t, name, _, _ in named)
+    return s._replace(keep=(*s.keep, *keep)), tuple(t.data_ptr() for t in keep)
+
+
+def topk_window_scores(user_vec: torch.Tensor, table: torch.Tensor, k: int, row_time: torch.Tensor, win_lo: torch.Tensor,
+                       win_hi: torch.Tensor, excl_idx: Optional[torch.Tensor] = None, excl_off: Optional[torch.Tensor] = None,
+                       eligible: Optional[torch.Tensor] = None, slices: int = 0):
+    """``nrl_topk_window_scores``: ``topk_scores`` with a time window of its own per user.  Row ``v`` can be returned for user ``u``
+    only when ``win_lo[u] <= row_time[v] <= win_hi[u]`` -- ``row_time`` (V) and ``win_lo`` / ``win_hi`` (B) int32 in any one unit,
+    the interval closed, ``(INT32_MIN, INT32_MAX)`` no window, ``win_lo[u] > win_hi[u]`` an empty one (a row of ``-1`` / ``-inf``,
+    no flag).  Returns, order, masks, flags (``TOPK_FLAGS``) and the score bits are those of ``topk_scores``; a NaN score is
+    flagged only for a row inside that user's window.  A table tile outside the windows of all 64 users of a workgroup is neither
+    read nor multiplied, so on a table in time order the cost falls with the windows.  Nothing here synchronises with the host."""
+    s, ptrs = _window(user_vec, table, row_time, win_lo, win_hi)
+    return _run_topk("nrl_topk_window_scores", s._replace(trail=ptrs), k, excl_idx, excl_off, eligible, slices)
+
+
+def catalogue_window_ranks(user_vec: torch.Tensor, table: torch.Tensor, tgt_idx: torch.Tensor, tgt_off: torch.Tensor,
+                           row_time: torch.Tensor, win_lo: torch.Tensor, win_hi: torch.Tensor,
+                           excl_idx: Optional[torch.Tensor] = None, excl_off: Optional[torch.Tensor] = None,
+                           eligible: Optional[torch.Tensor] = None, slices: int = 0):
+    """``nrl_catalogue_window_ranks``: ``catalogue_ranks`` against the population of ``topk_window_scores`` -> (rank int32 (n_tgt),
+    score fp32 (n_tgt), ranked int32 (B), status (1) int32).  A target outside its owner's window has rank 0 and score ``-inf``
+    without a flag, like an ineligible one; ``ranked`` counts the rows inside the window.  ``rank <= k`` exactly when the target is
+    slot ``rank - 1`` of ``topk_window_scores(k)``, with the same score bits.  Flags: ``RANK_FLAGS``.  Nothing here synchronises
+    with the host."""
+    s, ptrs = _window(user_vec, table, row_time, win_lo, win_hi)
+    return _run_ranks("nrl_catalogue_window_ranks", s, tgt_idx, tgt_off, excl_idx, excl_off, eligible, slices, after=ptrs)
 
 
 TOPK_MAX_BIAS_CLASSES = 64

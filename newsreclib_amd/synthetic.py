@@ -180,3 +180,19 @@ def make_news_batch(n_classes: int, samples_per_class: int, vocab_size: int = 50
         news["entities"] = torch.from_numpy(ents)
     labels = np.repeat(np.arange(n_classes, dtype=np.int64), samples_per_class)
     return {"news": news, "labels": torch.from_numpy(rng.permutation(labels))}
+
+
+def news_times(n_news: int, span: int = 28 * 24, seed: int = 31) -> torch.Tensor:
+    """A non-decreasing int64 ``time`` column for a table of ``n_news`` news: publication times uniform over ``[0, span)`` (the
+    default unit: hours over 28 days), sorted, as a news table that grows by appending is stored (the behaviours' ``time`` column,
+    ``mind_dataframe.py:528-581``, is what a split goes by)."""
+    rng = np.random.default_rng(seed)
+    return torch.from_numpy(np.sort(rng.integers(0, max(int(span), 1), int(n_news))).astype(np.int64))
+
+
+def add_request_times(users, span: int = 28 * 24, last: int = 7 * 24, seed: int = 37):
+    """The user dictionaries of ``recommend_users`` / ``evaluate_full_rank`` with a ``"time"`` each: a request time drawn from the
+    last ``last`` units of ``[0, span)`` (in the unit of ``news_times``) -> a new list; the dictionaries are copied."""
+    rng = np.random.default_rng(seed)
+    t = rng.integers(max(int(span) - int(last), 0), max(int(span), 1), len(users))
+    return [{**u, "time": int(t[j])} for j, u in enumerate(users)]
