@@ -1506,6 +1506,45 @@ int nrl_catalogue_window_ranks(const float* user_vec, const float* table, int64_
                                int32_t* out_rank /* n_targets */, float* out_score /* n_targets */, int32_t* out_ranked /* B */,
                                int32_t* status, void* ws, size_t ws_bytes, void* stream);
 
+/* nrl_topk_sampled_scores / nrl_gumbel_noise: Gumbel top-k.  One draw without replacement from the Plackett-Luce policy over
+ *   softmax(s / temperature) per user -- the k rows of the user's population with the largest perturbed key z = s * inv_temp + g --
+ *   without the (B, V) score matrix and without a (B, V) matrix of noise.
+ *   The noise (normative).  M = 2^32, lowbias32 the hash of the dropout masks (x ^= x >> 16; x *= 0x7FEB352D; x ^= x >> 15;
+ *     x *= 0x846CA68B; x ^= x >> 16, mod M), seed uint64, key = user_key[u] reinterpreted as uint64, row the table row (< 2^31):
+ *       k0 = lowbias32((seed & 0xFFFFFFFF) ^ lowbias32(((seed >> 32) + 0x9E3779B9) mod M))          per call
+ *       ku = lowbias32((key & 0xFFFFFFFF) ^ lowbias32((key >> 32) ^ k0))                             per user
+ *       h  = lowbias32((row * 0x9E3779B1 + ku) mod M)                                               per (user, row)
+ *       m  = h >> 9;  u = (2 m + 1) * 2^-24  (exact in fp32, 2^-24 <= u <= 1 - 2^-24: both logs are finite)
+ *       x  = fl32(-log(u));  g = fl32(-log(x)): fp32, an accurate logf twice -- each log is evaluated in float64 and rounded once to
+ *            fp32 (within half an ulp and a bit; the library's logf, up to 2 ulp, lets the two errors add up to 2^-21.9 max(1, |g|),
+ *            and the fast intrinsic is off by the size of g itself near u = 1).
+ *     z = fadd_rn(fmul_rn(s, inv_temp), g): s the bits nrl_topk_scores computes for the pair, two separate roundings, no fma.
+ *     inv_temp (fp32, finite, >= 0) is 1 / temperature; 0 is legitimate: a uniformly random ordered k-subset of the population.
+ *     u has 23 random bits, so two rows of one user can share a g; equal z then rank by ascending row like equal scores.
+ *   Population, excl_idx / excl_off, eligible, slices, the order (z descending, equal z by ascending row), the -1 / -inf fill and
+ *     the status bits are those of nrl_topk_scores with z in place of the score: a NaN z (a NaN s, or an infinite s with
+ *     inv_temp == 0) is left out and sets NRL_TOPK_E_NAN.
+ *   out_idx (B, k) int64; out_key (B, k) fp32: z; out_score (B, k) fp32: the raw score -- the bits nrl_topk_scores reports for
+ *     (b, out_idx[b, j]) (the same accumulator chain over the same two rows, -0 as +0), -inf where out_idx is -1.
+ *   Determinism: a user's lists are a pure function of (seed, its key, its vector, the table, its masks, inv_temp): they do not
+ *     depend on B, the user's place in the batch, slices, the grid, the GEMM engine setting or what was sampled before.  No
+ *     floating-point atomics, no allocation, no host synchronisation.
+ *   Workspace: nrl_topk_sampled_scores_workspace_size (`_size`, as the rank entries' functions: the set of *_workspace_bytes names
+ *     is pinned) == nrl_topk_scores_workspace_bytes: the partial lists; the raw scores read the selected rows in place, nothing is
+ *     gathered.
+ *   Checks (NRL_E_INVALID before any launch): those of nrl_topk_scores in its order, then inv_temp not finite or negative,
+ *     B * k >= 2^31, and with B > 0 a null output or user_key; a short workspace NRL_E_WORKSPACE.  B == 0 succeeds without a launch.
+ * nrl_gumbel_noise: the noise above for n pairs (user_key[i], row[i]) (int64, device; the low 32 bits of row are used) ->
+ *   out_u (n) / out_g (n) fp32, either nullable: the device function the sampled walk calls, so the same bits. */
+size_t nrl_topk_sampled_scores_workspace_size(int64_t B, int64_t V, int32_t D, int32_t k, int32_t slices);
+int nrl_topk_sampled_scores(const float* user_vec, const float* table, int64_t B, int64_t V, int32_t D, int32_t k,
+                            const int64_t* user_key /* B */, uint64_t seed, float inv_temp, const int64_t* excl_idx,
+                            const int64_t* excl_off, const uint8_t* eligible, int32_t slices, int64_t* out_idx /* B, k */,
+                            float* out_key /* B, k */, float* out_score /* B, k */, int32_t* status, void* ws, size_t ws_bytes,
+                            void* stream);
+int nrl_gumbel_noise(const int64_t* user_key /* n */, const int64_t* row /* n */, int64_t n, uint64_t seed, float* out_u /* n */,
+                     float* out_g /* n */, void* stream);
+
 /* nrl_catalogue_interest_ranks / nrl_catalogue_relu_ranks / nrl_catalogue_pooled_ranks: nrl_catalogue_ranks under the scores of
  *   nrl_topk_interest_scores (MINER: interests (B, K, D), gate (B, K, D) or null, mode 0 max / 1 mean / 2 weighted), of
  *   nrl_topk_relu_scores (DKN: q (B, Hd), proj (V, Hd), w2 (Hd), b2 (1), all on the device) and of nrl_topk_pooled_scores (NPA:

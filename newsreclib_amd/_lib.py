@@ -352,6 +352,11 @@ SIGNATURES = {
     "nrl_catalogue_window_ranks": (c_int32, [c_void_p, c_void_p, c_int64, c_int64, c_int32, c_void_p, c_void_p, c_int64, c_void_p,
                                              c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p,
                                              c_void_p, c_void_p, c_size_t, c_void_p]),
+    "nrl_topk_sampled_scores_workspace_size": (c_size_t, [c_int64, c_int64, c_int32, c_int32, c_int32]),
+    "nrl_topk_sampled_scores": (c_int32, [c_void_p, c_void_p, c_int64, c_int64, c_int32, c_int32, c_void_p, c_uint64, c_float, c_void_p,
+                                          c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,
+                                          c_void_p]),
+    "nrl_gumbel_noise": (c_int32, [c_void_p, c_void_p, c_int64, c_uint64, c_void_p, c_void_p, c_void_p]),
     "nrl_catalogue_interest_ranks": (c_int32, [c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_int64, c_int32, c_int32, c_void_p,
                                                c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_void_p,
                                                c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),

@@ -3,9 +3,11 @@
 // list (the history) and the rows an `eligible` mask removes.  The (B, V) score matrix is never written: every workgroup walks its
 // slice of the table once, tile by tile, and keeps per user only what its consumer needs.
 //
-// ONE WALK (tk_walk), six tile producers, three consumers; fourteen of the fifteen walk kernels are its instantiations and nothing
+// ONE WALK (tk_walk), seven tile producers, three consumers; fifteen of the sixteen walk kernels are its instantiations and nothing
 // else (tkr_scores_kernel keeps its own text, for its speed: see there).  The sixth producer, TkBiasProducer (the dot product plus
-// a per-(user, class) bias: tkb_scores_kernel, tkbc_count_kernel, tkbcap_scores_kernel), is TkDot's column with one add behind it:
+// a per-(user, class) bias: tkb_scores_kernel, tkbc_count_kernel, tkbcap_scores_kernel), is TkDot's column with one add behind it;
+// the seventh, TksProducer (Gumbel top-k: the dot product times inv_temp plus a hashed Gumbel variable per (seed, user key, row):
+// tks_scores_kernel under TkSelect, nrl_topk_sampled_scores), is TkDot's column with a multiply, the noise and an add behind it:
 //                      plain dot product   MINER interests      MANNeR ensemble     DKN factored DNN    NPA pooling
 //   producer           TkDot               TkiProducer<GATE>    TkeProducer         TkrProducer         TkpProducer
 //   TkSelect (top-k)   tk_scores_kernel    tki_scores_kernel    tke_scores_kernel   tkr_scores_kernel   tkp_scores_kernel
@@ -2025,6 +2027,154 @@ __global__ __launch_bounds__(TK_THREADS) void tkwc_count_kernel(TkWith<TkcArgs, 
 
 __global__ __launch_bounds__(64) void tkwc_finish_kernel(TkWith<TkcArgs, TkwFields> A) { tkc_finish_user(A, &A); }
 
+// ---- Gumbel top-k: nrl_topk_sampled_scores, nrl_gumbel_noise ----------------------------------------------------------------------------
+// One Plackett-Luce draw without replacement from softmax(s * inv_temp) per user: the k rows with the largest
+// z = fadd_rn(fmul_rn(s, inv_temp), g), g a standard Gumbel variable per (seed, user key, row) from the counter-based hash of the
+// dropout masks (the header has the normative statement).  The noise is a property of the PRODUCER: TksProducer is TkDot's tile with the
+// perturbation on the accumulator fragments before they are stored, the way TkBiasProducer adds its bias, so tk_walk, TkSelect, the
+// partial lists and tk_merge_kernel run as they are over z instead of s.
+//   * where: behind the MFMA chain, in registers.  A lane holds 32 elements of the tile (8 users x 4 columns), so the hash and the two
+//     logs are spread evenly over all 256 threads whatever the number of users, and the tile is written once.  The alternative -- the
+//     serving wave rewrites its user's row in place -- costs a second LDS read and write of every element (64 KB per tile) for the
+//     same arithmetic and leaves the lanes of a short user tile idle; it would save nothing: columns past V and users past B are
+//     perturbed here too (harmless: they are never consumed) rather than branched around;
+//   * ku, the 64 users' hashed keys, are staged once per workgroup (256 B behind the score tile; the consumer's prologue publishes
+//     them); k0, the per-call key, comes from the host.  A lane reads 8 of them per tile: 4 addresses per wave and read, a broadcast;
+//   * the lists hold z only.  The raw scores of the selected rows are computed afterwards by tks_raw_kernel: tkc_target_kernel's
+//     diagonal of the tile product of (owner's row, selected row), the selected rows read in place through out_idx
+//     (tk_tile_accumulate<1, true>: nothing is gathered, no workspace beyond the partial lists) -- the same chain on the same
+//     operands, so the bits nrl_topk_scores reports for that pair.
+struct TksFields {
+  const int64_t* user_key;                     // (B)
+  uint32_t k0;                                 // the per-call key (tks_call_key)
+  float inv_temp;
+};
+
+__host__ __device__ __forceinline__ uint32_t tks_call_key(uint64_t seed) {
+  return lowbias32((uint32_t)(seed & 0xFFFFFFFFu) ^ lowbias32((uint32_t)(seed >> 32) + 0x9E3779B9u));
+}
+__host__ __device__ __forceinline__ uint32_t tks_user_key(uint32_t k0, uint64_t key) {
+  return lowbias32((uint32_t)(key & 0xFFFFFFFFu) ^ lowbias32((uint32_t)(key >> 32) ^ k0));
+}
+// u = (2 m + 1) 2^-24 with m the top 23 bits of the pair's hash: exact in fp32 and inside [2^-24, 1 - 2^-24]
+__device__ __forceinline__ float tks_uniform(uint32_t ku, uint32_t row) {
+  const uint32_t m = lowbias32(row * 0x9E3779B1u + ku) >> 9;
+  return (float)(2u * m + 1u) * 0x1p-24f;
+}
+// g = -log(-log(u)) in fp32 by an accurate logf, twice.  Never the fast intrinsic: its absolute error near u = 1 exceeds -log(u)
+// itself, and those are the rows that receive the largest perturbations.  And not the library's logf either: its errors of up to
+// 2 ulp in -log(u) and in g add up to 2^-21.9 max(1, |g|) (measured), which four times over is above the 2^-20 the noise test
+// allows.  tks_logf is the float64 log rounded once to fp32, a logf within half an ulp and a bit; through both, 2^-23.
+__device__ __forceinline__ float tks_logf(float x) { return (float)log((double)x); }
+__device__ __forceinline__ float tks_gumbel(float u) { return -tks_logf(-tks_logf(u)); }
+// the perturbed key of a pair: two roundings, never an fma (the unit is compiled with contraction on, and __fmul_rn is a plain `*`)
+__device__ __forceinline__ float tks_perturb(float s, float inv_temp, float g) {
+#pragma clang fp contract(off)
+  const float scaled = s * inv_temp;
+  return scaled + g;
+}
+
+constexpr size_t TKS_EXTRA_LDS = (size_t)TK_BU * 4;                          // ku
+static_assert(TKS_EXTRA_LDS % 16 == 0, "what follows the hashed keys is 16-byte aligned");
+// 256 B: two workgroups of the sampled scores kernel fit a CU up to k = 59 (plain: 60), more than 64 KB from k = 28 on (plain: 29)
+static_assert(2 * (tk_lds_bytes(1, TK_BU, 59) + TKS_EXTRA_LDS) <= 160 * 1024 && 2 * (tk_lds_bytes(1, TK_BU, 60) + TKS_EXTRA_LDS) > 160 * 1024,
+              "two workgroups of the sampled scores kernel fit a CU up to k = 59");
+static_assert(tk_lds_bytes(1, TK_BU, 27) + TKS_EXTRA_LDS <= 64 * 1024 && tk_lds_bytes(1, TK_BU, 28) + TKS_EXTRA_LDS > 64 * 1024,
+              "the sampled scores kernel needs the LDS attribute from k = 28 on");
+static_assert(tk_lds_bytes(1, TK_BU, NRL_TOPK_MAX_K) + TKS_EXTRA_LDS <= 160 * 1024, "the largest sampled layout fits");
+
+// The producer of the sampled kernel: TkDot's tile, every element scaled by inv_temp and perturbed by its pair's Gumbel noise.
+struct TksProducer : TkBlocked {
+  float* sc;                                   // [TK_BU][TK_SCLD]; until the keys exist, the operand tiles
+  uint32_t* kul;                               // [TK_BU] the users' hashed keys
+  unsigned char* rest;
+  const TksFields& F;
+  const float* pa[1];
+  bool ua_ok;
+  __device__ __forceinline__ TksProducer(unsigned char* p, const TksFields& f)
+      : sc(reinterpret_cast<float*>(p)), kul(reinterpret_cast<uint32_t*>(p + TK_TILE_BYTES)), rest(p + TK_TILE_BYTES + TKS_EXTRA_LDS),
+        F(f) {}
+  __device__ __forceinline__ int slots() const { return TK_BU; }
+  __device__ __forceinline__ void stage(const TkArgs& A, int64_t u0, int nu) {
+    const int srow = threadIdx.x >> 2;
+    ua_ok = srow < nu;
+    pa[0] = A.user + (ua_ok ? u0 + srow : A.B - 1) * A.D;
+    if (threadIdx.x < TK_BU)                          // (the consumer's prologue publishes the keys)
+      kul[threadIdx.x] = (int)threadIdx.x < nu ? tks_user_key(F.k0, (uint64_t)F.user_key[u0 + threadIdx.x]) : 0u;
+  }
+  __device__ __forceinline__ void tile(const TkArgs& A, int v0, int) const {
+    const int tid = threadIdx.x, lane = tid & 63;
+    tk_f32x4 acc[1][2][4];
+    tk_tile_accumulate<1>(pa, ua_ok, A.table, A.D, v0, A.V, A.D, sc, acc);
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int wm = wave >> 1, wn = wave & 1, l15 = lane & 15, g = lane >> 4;
+    uint32_t ku[2][4];
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) ku[i][r] = kul[wm * 32 + i * 16 + 4 * g + r];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const uint32_t row = (uint32_t)v0 + wn * 64 + j * 16 + l15;
+#pragma unroll
+      for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) acc[0][i][j][r] = tks_perturb(acc[0][i][j][r], F.inv_temp, tks_gumbel(tks_uniform(ku[i][r], row)));
+    }
+    tk_store_fragments(acc[0], sc);
+    __syncthreads();
+  }
+  __device__ __forceinline__ const float* row(int ul) const { return sc + ul * TK_SCLD; }
+  __device__ __forceinline__ bool skip(int) const { return false; }
+};
+
+__global__ __launch_bounds__(TK_THREADS) void tks_scores_kernel(TkWith<TkArgs, TksFields> A) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char tk_smem[];
+  TksProducer P(tk_smem, A);
+  TkSelect C(P.rest, TK_BU, A.k);
+  tk_walk(A, P, C);
+}
+
+// The raw scores of the selected rows, one workgroup per 64 slots of the (B, k) lists: tile row r is the user row of slot j0 + r
+// (user (j0 + r) / k), tile column c is table row out_idx[j0 + c] read in place (a zero row for -1), and slot j0 + r's score is the
+// diagonal: the bits tk_scores_kernel computes for that (user, row), reported as tk_merge_kernel reports them (-0 as +0).
+struct TksRawArgs {
+  const float* user;
+  const float* table;
+  const int64_t* idx;                          // (B, k) the merged lists' rows
+  float* out_score;                            // (B, k)
+  int64_t V;
+  int32_t n, D, k;                             // n = B * k slots
+};
+__global__ __launch_bounds__(TK_THREADS) void tks_raw_kernel(TksRawArgs A) {
+  __shared__ __attribute__((aligned(16))) float sc[TK_BU * TK_SCLD];
+  const int tid = threadIdx.x;
+  const int j0 = (int)blockIdx.x * TK_BU;
+  if (A.V == 0) {                                     // (uniform: no table to read, every slot is empty)
+    if (tid < TK_BU && j0 + tid < A.n) A.out_score[j0 + tid] = -INFINITY;
+    return;
+  }
+  const int srow = tid >> 2;
+  const bool ua_ok = j0 + srow < A.n;
+  const float* const pa[1] = {A.user + (int64_t)(ua_ok ? (j0 + srow) / A.k : 0) * A.D};
+  tk_f32x4 acc[1][2][4];
+  tk_tile_accumulate<1, true>(pa, ua_ok, A.table, A.D, j0, A.n, A.D, sc, acc, A.idx, A.V);
+  tk_store_fragments(acc[0], sc);
+  __syncthreads();
+  if (tid < TK_BU && j0 + tid < A.n)
+    A.out_score[j0 + tid] = A.idx[j0 + tid] >= 0 ? tk_unkey(score_key(sc[tid * TK_SCLD + tid])) : -INFINITY;
+}
+
+// the public statement of the noise: element i is the pair (user_key[i], row[i]) under the call key k0
+__global__ __launch_bounds__(256) void tks_noise_kernel(const int64_t* user_key, const int64_t* row, int64_t n, uint32_t k0, float* out_u,
+                                                        float* out_g) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const float u = tks_uniform(tks_user_key(k0, (uint64_t)user_key[i]), (uint32_t)row[i]);
+  if (out_u) out_u[i] = u;
+  if (out_g) out_g[i] = tks_gumbel(u);
+}
+
 // ---- greedy MMR re-ranking of a pool (nrl_mmr_rerank) ------------------------------------------------------------------------------
 // One workgroup per user.  The pool's Gram matrix is ceil(N / 64) calls of tk_tile_accumulate<1, true>: the A rows are pool slots
 // 64 h ... 64 h + 63 read in place, the gathered B rows the whole pool, so G[i][j] is the chain of nrl_topk_scores over the two
@@ -2877,6 +3027,52 @@ int nrl_topk_window_scores(const float* user_vec, const float* table, int64_t B,
   const TkwFields win{row_time, win_lo, win_hi};
   return tk_scores_entry("topk_window_scores", user_vec, table, B, V, D, k, nullptr, &win, excl_idx, excl_off, eligible, slices,
                          out_idx, out_score, status, ws, ws_bytes, stream);
+}
+
+// nrl_topk_sampled_scores: the checks and the layout of nrl_topk_scores, then its own; tks_scores_kernel over the slices, the plain
+// merge (out_key takes the place of out_score), then the raw scores of the merged rows
+struct TkMergeSampled {
+  float* out_score;
+  int operator()(const TkArgs& A, hipStream_t st) const {
+    NRL_TRY(TkMerge{}(A, st));
+    const int64_t n = A.B * A.k;
+    tks_raw_kernel<<<(unsigned)ceil_div(n, TK_BU), TK_THREADS, 0, st>>>(TksRawArgs{A.user, A.table, A.out_idx, out_score, A.V, (int32_t)n, A.D, A.k});
+    NRL_LAUNCH_CHECK();
+    return NRL_OK;
+  }
+};
+
+size_t nrl_topk_sampled_scores_workspace_size(int64_t B, int64_t V, int32_t D, int32_t k, int32_t slices) {
+  return nrl_topk_scores_workspace_bytes(B, V, D, k, slices);                // (the raw scores read their rows in place)
+}
+
+int nrl_topk_sampled_scores(const float* user_vec, const float* table, int64_t B, int64_t V, int32_t D, int32_t k,
+                            const int64_t* user_key, uint64_t seed, float inv_temp, const int64_t* excl_idx, const int64_t* excl_off,
+                            const uint8_t* eligible, int32_t slices, int64_t* out_idx, float* out_key, float* out_score, int32_t* status,
+                            void* ws, size_t ws_bytes, void* stream) {
+  const char* who = "topk_sampled_scores";
+  NRL_REQUIRE(B >= 0 && V >= 0 && D >= 0 && slices >= 0, "%s: negative size", who);
+  NRL_TRY(tk_check(who, B, V, D, k, excl_idx, excl_off));
+  NRL_REQUIRE(status, "%s: the status word is required", who);
+  NRL_REQUIRE(inv_temp >= 0.f && inv_temp < INFINITY, "%s: inv_temp finite and >= 0 (got %g)", who, (double)inv_temp);
+  NRL_REQUIRE(B * (int64_t)k < ((int64_t)1 << 31), "%s: at most 2^31 - 1 list slots per call (got %lld)", who, (long long)(B * k));
+  if (B == 0) return NRL_OK;
+  NRL_REQUIRE(out_idx && out_key && out_score && user_vec && (V == 0 || table), "%s: null argument", who);
+  NRL_REQUIRE(user_key, "%s: user_key is required", who);
+  unsigned long long* partial;
+  NRL_TRY(carve_workspace(ws, ws_bytes, [&](Arena& a) { tk_layout(a, B, V, k, slices, TK_BU, &partial); }));
+  TkWith<TkArgs, TksFields> A{tk_args(user_vec, table, B, V, D, k, excl_idx, excl_off, eligible, partial, out_idx, out_key, status),
+                              TksFields{user_key, tks_call_key(seed), inv_temp}};
+  return tk_launch(who, tks_scores_kernel, A, slices, 1, TK_BU, stream, TKS_EXTRA_LDS, TkMergeSampled{out_score});
+}
+
+int nrl_gumbel_noise(const int64_t* user_key, const int64_t* row, int64_t n, uint64_t seed, float* out_u, float* out_g, void* stream) {
+  NRL_REQUIRE(n >= 0 && ceil_div(n, 256) < ((int64_t)1 << 31), "gumbel_noise: n in [0, 2^39) (got %lld)", (long long)n);
+  if (n == 0) return NRL_OK;
+  NRL_REQUIRE(user_key && row && (out_u || out_g), "gumbel_noise: null argument");
+  tks_noise_kernel<<<(unsigned)ceil_div(n, 256), 256, 0, (hipStream_t)stream>>>(user_key, row, n, tks_call_key(seed), out_u, out_g);
+  NRL_LAUNCH_CHECK();
+  return NRL_OK;
 }
 
 // the workspace of nrl_catalogue_ranks: the gathered target rows and their scores and owners, then the per-slice counts

@@ -23,7 +23,8 @@ Everything runs through the same C-ABI kernels; nothing here is a second impleme
 from __future__ import annotations
 
 import contextlib
-from typing import Dict, Optional, Sequence, Tuple
+import math
+from typing import Dict, List, Optional, Sequence, Tuple
 
 import torch
 
@@ -252,6 +253,52 @@ def _window_refusal(who: str, cache) -> None:
                                   "alone; a windowed kernel for that scorer does not exist yet")
 
 
+def _sample_triple(sample, n_users: int):
+    """``sample`` = (inv_temp, seed, user_key) of ``recommend`` checked before any device work (``ops._sample_args``: the key
+    tensor int64 with one entry per user, the seed in [0, 2^64), ``inv_temp`` finite and >= 0) -> (inv_temp, seed, user_key)."""
+    if not isinstance(sample, (tuple, list)) or len(sample) != 3:
+        raise ValueError("newsreclib_amd: sample = (inv_temp, seed, user_key)")
+    seed, inv_temp = ops._sample_args(sample[2], n_users, sample[1], sample[0])
+    return inv_temp, seed, sample[2]
+
+
+def _sample_policy(who: str, cache, sample, cap=None, window=None, rerankers=()):
+    """``sample`` = (temperature, seed) of ``recommend_users`` / ``sample_recommendations`` -> (inv_temp, seed), after the refusals:
+    ``NotImplementedError`` where the sampled walk has no kernel (under a cap, under a window, under every producer but the plain
+    dot product), ``ValueError`` beside a re-ranker and for a temperature that is not positive or a seed outside [0, 2^64)."""
+    if not isinstance(sample, (tuple, list)) or len(sample) != 2:
+        raise ValueError(f"{who}: sample = (temperature, seed)")
+    if cap is not None:
+        raise NotImplementedError(f"{who} with cap=...: the sampled producer (tks_scores_kernel) feeds the plain selecting consumer; "
+                                  "a sampled kernel with the class-capped consumer (TkSelectCapped) does not exist yet")
+    if window is not None:
+        raise NotImplementedError(f"{who} with window=...: the sampled producer (tks_scores_kernel) runs under the plain walk; a "
+                                  "sampled kernel under the windowed walk (tkw_walk) does not exist yet")
+    if any(r is not None for r in rerankers):
+        raise ValueError(f"{who}: `sample` excludes `diversify`, `calibrate` and `dpp`: each of those picks the listed news from a "
+                         "pool by an objective of its own, a sampled list is a draw from the policy and stays as drawn")
+    module = getattr(cache, "module", None)
+    kind = [a for a in ("multi_interest_scorer", "dnn_predictor_scorer", "personalized_pooling_scorer", "class_biased_scorer")
+            if getattr(module, a, False)]
+    if hasattr(cache, "recommend_ensemble"):
+        kind.append("z-scored ensemble (MannerVectorCache)")
+    if kind:
+        raise NotImplementedError(f"{who} draws from the Plackett-Luce policy over plain dot-product scores: {type(cache).__name__} "
+                                  f"over {type(module).__name__} is a `{kind[0]}`, and the Gumbel perturbation (tks_scores_kernel) "
+                                  "sits behind the dot-product producer alone; a sampled kernel for that scorer does not exist yet")
+    temperature, seed = float(sample[0]), sample[1]
+    if not math.isfinite(temperature) or temperature <= 0:
+        raise ValueError(f"{who}: the temperature must be finite and > 0, got {sample[0]!r}")
+    if isinstance(seed, bool) or not isinstance(seed, int) or not 0 <= seed < 2 ** 64:
+        raise ValueError(f"{who}: the seed must be an integer in [0, 2^64), got {seed!r}")
+    return 1.0 / temperature, seed
+
+
+def _user_ids(chunk: Sequence[Dict], lo: int) -> List[int]:
+    """The id of each user dictionary of a batch that starts at position ``lo`` of the list: its ``user_id``, or position + 1."""
+    return [int(u["user_id"]) if "user_id" in u else lo + j + 1 for j, u in enumerate(chunk)]
+
+
 class NewsVectorCache(_ImpressionCache):
     """Encode-once evaluation of a drop-in recommender (any of the module mirrors: NRMS, LSTUR, NAML, TANR,
     CenNewsRec, MINS -- whatever exposes ``news_encoder`` and ``score_news_vectors``)."""
@@ -464,7 +511,7 @@ class NewsVectorCache(_ImpressionCache):
 
     @torch.no_grad()
     def recommend(self, hist_idx: torch.Tensor, hist_sizes: torch.Tensor, k: int, user_idx: Optional[torch.Tensor] = None,
-                  exclude_history: bool = True, eligible: Optional[torch.Tensor] = None, window=None):
+                  exclude_history: bool = True, eligible: Optional[torch.Tensor] = None, window=None, sample=None):
         """The ``k`` news of the WHOLE table each user scores highest -> (news_idx (B, k) int64, scores (B, k) fp32, status):
         the module's ``user_vectors`` over the gathered history vectors (eval mode, restored afterwards), then
         ``ops.topk_scores`` against the cached table with the history as the exclusion list (``exclude_history``) and
@@ -474,9 +521,25 @@ class NewsVectorCache(_ImpressionCache):
 
         ``window`` = (win_lo, win_hi) or (win_lo, win_hi, row_time), int32, host or device: user ``b`` is recommended only news
         with ``win_lo[b] <= time <= win_hi[b]`` (``ops.topk_window_scores``); without the third member the times are the table's
-        ``time`` column (``ValueError`` when it has none).  ``None`` is the call without it, launch for launch."""
+        ``time`` column (``ValueError`` when it has none).  ``None`` is the call without it, launch for launch.
+
+        ``sample`` = (inv_temp, seed, user_key): instead of the ``k`` best news, ONE draw without replacement from the
+        Plackett-Luce policy over ``softmax(score * inv_temp)`` (``ops.topk_sampled_scores``: Gumbel top-k); ``user_key`` is one
+        int64 key per user, host (through pinned memory) or device, and a user's list depends on ``(seed, its key)`` and its own
+        inputs alone.  The returned scores are the raw scores of the drawn news, in the order drawn.  ``NotImplementedError``
+        together with ``window``.  ``None`` is the call without it, launch for launch."""
+        if sample is not None:
+            if window is not None:
+                raise NotImplementedError("recommend(sample=..., window=...): the sampled producer (tks_scores_kernel) runs under the "
+                                          "plain walk; a sampled kernel under the windowed walk (tkw_walk) does not exist yet")
+            inv_temp, seed, user_key = _sample_triple(sample, int(hist_sizes.numel()))
         times = None if window is None else _window_arrays(self, window)
         user, _, tail = self._dot_users("recommend", hist_idx, hist_sizes, user_idx, exclude_history, eligible, None)
+        if sample is not None:
+            if not user_key.is_cuda:
+                user_key = user_key.pin_memory().to(user.device, non_blocking=True)
+            idx, _, score, status = ops.topk_sampled_scores(user, self.vectors, k, user_key, seed, inv_temp, *tail)
+            return idx, score, status
         if times is not None:
             return ops.topk_window_scores(user, self.vectors, k, *times, *tail)
         return ops.topk_scores(user, self.vectors, k, *tail)
@@ -1014,7 +1077,8 @@ def format_recommendations(user_ids: Sequence, news_idx: torch.Tensor, scores: t
 def recommend_users(cache: NewsVectorCache, users: Sequence[Dict], k: int, batch_size: int = 512,
                     eligible: Optional[torch.Tensor] = None, cap: Optional[Tuple[str, int]] = None,
                     diversify: Optional[Tuple[int, float]] = None, calibrate: Optional[Dict] = None,
-                    dpp: Optional[Dict] = None, window: Optional[Tuple[int, int]] = None) -> Dict[str, Dict[str, float]]:
+                    dpp: Optional[Dict] = None, window: Optional[Tuple[int, int]] = None,
+                    sample: Optional[Tuple[float, int]] = None) -> Dict[str, Dict[str, float]]:
     """``cache.recommend`` (``cache.recommend_interests`` where the cache's module is a ``multi_interest_scorer``,
     ``cache.recommend_dnn`` where it is a ``dnn_predictor_scorer``, ``cache.recommend_pooled`` where it is a
     ``personalized_pooling_scorer``: ``NpaFeatureCache``, whose users need ``user_idx``,
@@ -1053,7 +1117,17 @@ def recommend_users(cache: NewsVectorCache, users: Sequence[Dict], k: int, batch
     the request; ``ValueError`` otherwise) and is recommended only news published in ``[time - before, time + after]`` (``None``
     for a side: unbounded), computed on the host and clamped to int32 (``user_windows``): ``cache.recommend(..., window=...)``.
     The pool of ``diversify`` / ``calibrate`` / ``dpp`` comes from the windowed call.  ``NotImplementedError`` together with
-    ``cap`` and for every cache but a plain dot-product one: the windowed walk has no capped consumer and no other producer yet."""
+    ``cap`` and for every cache but a plain dot-product one: the windowed walk has no capped consumer and no other producer yet.
+
+    ``sample`` = (temperature, seed): every user's list is ONE draw without replacement from the Plackett-Luce policy over
+    ``softmax(score / temperature)`` instead of the ``k`` best news (``cache.recommend(..., sample=...)``: Gumbel top-k), in the
+    order drawn, with the raw scores.  ``temperature > 0``; its inverse is taken on the host.  The key of a user is its
+    ``user_id``, so a user's draw is a function of ``(seed, user_id)`` and its own history: it does not depend on ``batch_size`` or
+    on the other users of the list (given a user encoder that does not couple the users of a batch; NRMS' seq-first user attention
+    does).  ``NotImplementedError`` together with ``cap`` or ``window`` and for every cache but a plain
+    dot-product one (the sampled kernels do not exist yet), ``ValueError`` together with ``diversify`` / ``calibrate`` / ``dpp``."""
+    if sample is not None:
+        inv_temp, sample_seed = _sample_policy("recommend_users(sample=...)", cache, sample, cap, window, (diversify, calibrate, dpp))
     if window is not None:
         if cap is not None:
             raise NotImplementedError("recommend_users(window=..., cap=...): the windowed walk runs the plain selecting consumer; a "
@@ -1123,7 +1197,10 @@ def recommend_users(cache: NewsVectorCache, users: Sequence[Dict], k: int, batch
             capped = getattr(cache, "recommend_ensemble_capped", None) or cache.recommend_capped
             rank = lambda hist, hs, k, **kw: capped(hist, hs, k, aspect, max_per_class, **kw)  # noqa: E731
         reranked = diversify is not None or calibrate is not None or dpp is not None
-        if window is not None:
+        if sample is not None:
+            idx, score, status = cache.recommend(hist, hs, k, user_idx=uidx, eligible=eligible,
+                                                 sample=(inv_temp, sample_seed, torch.tensor(_user_ids(chunk, lo), dtype=torch.int64)))
+        elif window is not None:
             idx, score, status = cache.recommend(hist, hs, pool if reranked else k, user_idx=uidx, eligible=eligible,
                                                  window=(win_lo[lo:lo + batch_size], win_hi[lo:lo + batch_size]))
         else:
@@ -1147,8 +1224,42 @@ def recommend_users(cache: NewsVectorCache, users: Sequence[Dict], k: int, batch
             second = ops.DPP_FLAGS if dpp is not None else ops.CAL_FLAGS if calibrate is not None else ops.MMR_FLAGS
             said = [msg for bit, msg in flags.items() if word & bit] + [msg for bit, msg in second.items() if (word >> 16) & bit]
             warnings.warn("recommend_users: " + "; ".join(said))
-        ids = [int(u["user_id"]) if "user_id" in u else lo + j + 1 for j, u in enumerate(chunk)]
-        out.update(format_recommendations(ids, packed[:, :k].long(), packed[:, k:2 * k].float(), news_ids))
+        out.update(format_recommendations(_user_ids(chunk, lo), packed[:, :k].long(), packed[:, k:2 * k].float(), news_ids))
+    return out
+
+
+def sample_recommendations(cache: NewsVectorCache, users: Sequence[Dict], k: int, draws: int, temperature: float, seed: int,
+                           batch_size: int = 512, eligible: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``draws`` independent lists per user from the Plackett-Luce policy over ``softmax(score / temperature)`` -> news rows
+    (n_users, draws, k) int64 on the host, ``-1`` beyond a user's population.  Draw ``j`` is the list
+    ``recommend_users(..., sample=(temperature, (seed + j) mod 2^64))`` gives the user -- the same keys (``user_id``, or position
+    + 1), the same refusals -- so it is reproducible user by user whatever the batching.  A batch's histories are uploaded once and
+    serve all its draws; one device-to-host copy per batch and draw; a status flag (``ops.TOPK_FLAGS``) is passed on as a warning.
+    The cost is ``draws`` full passes over the table: every draw recomputes the scores.  Reusing a score tile for several draws
+    inside the kernel is the obvious next step and is not done here."""
+    who = "sample_recommendations"
+    inv_temp, seed = _sample_policy(who, cache, (temperature, seed))
+    draws = int(draws)
+    if draws < 0:
+        raise ValueError(f"{who}: draws >= 0, got {draws}")
+    dev = cache.table.device
+    out = torch.full((len(users), draws, max(int(k), 0)), -1, dtype=torch.int64)
+    word = 0
+    for lo in range(0, len(users), batch_size):
+        chunk = users[lo:lo + batch_size]
+        hs = torch.tensor([len(u["hist"]) for u in chunk])
+        hist = torch.cat([torch.as_tensor(u["hist"]).long() for u in chunk]).to(dev)
+        uidx = torch.stack([torch.as_tensor(u["user_idx"]) for u in chunk]) if "user_idx" in chunk[0] else None
+        keys = torch.tensor(_user_ids(chunk, lo), dtype=torch.int64).to(dev)
+        for j in range(draws):
+            idx, _, status = cache.recommend(hist, hs, k, user_idx=uidx, eligible=eligible,
+                                             sample=(inv_temp, (seed + j) % 2 ** 64, keys))
+            packed = torch.cat([idx, status.long().expand(idx.shape[0], 1)], dim=1).cpu()                 # the one copy
+            out[lo:lo + len(chunk), j] = packed[:, :-1]
+            word |= int(packed[0, -1]) if packed.shape[0] else 0
+    if word:                                                # the kernel has dealt with each of these; the caller should know
+        import warnings
+        warnings.warn(f"{who}: " + "; ".join(msg for bit, msg in ops.TOPK_FLAGS.items() if word & bit))
     return out
 
 

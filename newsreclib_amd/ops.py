@@ -11,6 +11,7 @@ no 84 MB zero-fill + add per encoder call.  Without it the functions return ordi
 from __future__ import annotations
 
 import ctypes
+import math
 import os
 from typing import NamedTuple, Optional, Sequence, Tuple
 
@@ -1027,6 +1028,64 @@ def catalogue_window_ranks(user_vec: torch.Tensor, table: torch.Tensor, tgt_idx:
     with the host."""
     s, ptrs = _window(user_vec, table, row_time, win_lo, win_hi)
     return _run_ranks("nrl_catalogue_window_ranks", s, tgt_idx, tgt_off, excl_idx, excl_off, eligible, slices, after=ptrs)
+
+
+def _sample_args(user_key, n: int, seed, inv_temp=None):
+    """The arguments of the Gumbel entries, refused before anything looks at a device: an int64 key tensor of ``n`` entries
+    (``TypeError`` / ``ValueError``), a seed in [0, 2^64) and a finite ``inv_temp >= 0`` (``ValueError``) -> (seed, inv_temp)."""
+    if not isinstance(user_key, torch.Tensor) or user_key.dtype != torch.int64:
+        raise TypeError(f"newsreclib_amd: `user_key` must be an int64 tensor, got "
+                        f"{user_key.dtype if isinstance(user_key, torch.Tensor) else type(user_key).__name__}")
+    if user_key.dim() != 1 or user_key.numel() != n:
+        raise ValueError(f"newsreclib_amd: `user_key` must have one entry per user ({n}), got {tuple(user_key.shape)}")
+    if isinstance(seed, bool) or not isinstance(seed, int) or not 0 <= seed < 2 ** 64:
+        raise ValueError(f"newsreclib_amd: `seed` must be an integer in [0, 2^64), got {seed!r}")
+    if inv_temp is not None:
+        inv_temp = float(inv_temp)
+        if not math.isfinite(inv_temp) or inv_temp < 0 or inv_temp > 3.4028234663852886e38:
+            raise ValueError(f"newsreclib_amd: `inv_temp` must be finite (in fp32) and >= 0, got {inv_temp!r}")
+    return seed, inv_temp
+
+
+def gumbel_noise(user_key: torch.Tensor, row: torch.Tensor, seed: int):
+    """``nrl_gumbel_noise``: the noise of ``topk_sampled_scores`` for the pairs ``(user_key[i], row[i])`` (int64, equal lengths) under
+    ``seed`` -> (u, g) fp32: ``u = (2 m + 1) 2^-24`` with ``m`` the top 23 bits of the pair's hash, ``g = -log(-log(u))``.  The
+    device function the sampled walk calls: the same bits."""
+    if not isinstance(row, torch.Tensor) or row.dtype != torch.int64:
+        raise TypeError(f"newsreclib_amd: `row` must be an int64 tensor, got "
+                        f"{row.dtype if isinstance(row, torch.Tensor) else type(row).__name__}")
+    if row.dim() != 1:
+        raise ValueError(f"newsreclib_amd: `row` must be one-dimensional, got {tuple(row.shape)}")
+    n = int(row.numel())
+    seed, _ = _sample_args(user_key, n, seed)
+    user_key, row = _chk(user_key, torch.int64, "user_key"), _chk(row, torch.int64, "row")
+    u = torch.empty(n, dtype=torch.float32, device=row.device)
+    g = torch.empty(n, dtype=torch.float32, device=row.device)
+    _lib.check(_lib.load().nrl_gumbel_noise(user_key.data_ptr(), row.data_ptr(), n, seed, u.data_ptr(), g.data_ptr(), _stream()),
+               "nrl_gumbel_noise")
+    return u, g
+
+
+def topk_sampled_scores(user_vec: torch.Tensor, table: torch.Tensor, k: int, user_key: torch.Tensor, seed: int,
+                        inv_temp: float = 1.0, excl_idx: Optional[torch.Tensor] = None, excl_off: Optional[torch.Tensor] = None,
+                        eligible: Optional[torch.Tensor] = None, slices: int = 0):
+    """``nrl_topk_sampled_scores``: Gumbel top-k, one Plackett-Luce draw without replacement from ``softmax(score * inv_temp)`` per
+    user -> (idx (B, k) int64, key (B, k) fp32, score (B, k) fp32, status (1) int32).  The list is ``topk_scores``' over the
+    perturbed key ``z = fl(fl(score * inv_temp) + g)``, ``g`` the Gumbel noise of ``(seed, user_key[b], row)`` (``gumbel_noise``),
+    generated where the score is consumed: neither the (B, V) scores nor a (B, V) noise matrix is materialised.  ``key`` is ``z``
+    (descending; equal ``z`` -- 23 random bits per pair, so it happens -- by ascending row), ``score`` the raw score with the bits
+    ``topk_scores`` reports for that (user, row), ``-1`` / ``-inf`` / ``-inf`` beyond the population.  ``user_key`` (B int64) names
+    the users: a user's lists depend on ``(seed, its key, its vector, the table, its masks, inv_temp)`` and on nothing else -- not
+    on B, its place in the batch, ``slices`` or earlier calls.  ``inv_temp = 0`` is a uniformly random ordered k-subset.  Masks and
+    flags (``TOPK_FLAGS``) are those of ``topk_scores``.  Nothing here synchronises with the host."""
+    B = int(user_vec.shape[0]) if isinstance(user_vec, torch.Tensor) and user_vec.dim() else -1
+    seed, inv_temp = _sample_args(user_key, B, seed, inv_temp)
+    s = _dot_scorer(user_vec, table)
+    user_key = _chk(user_key, torch.int64, "user_key")
+    score = torch.empty((s.B, max(int(k), 0)), dtype=torch.float32, device=s.dev)
+    s = s._replace(trail=(user_key.data_ptr(), seed, inv_temp), keep=(*s.keep, user_key))
+    idx, key, status = _run_topk("nrl_topk_sampled_scores", s, k, excl_idx, excl_off, eligible, slices, extra=(score,))
+    return idx, key, score, status
 
 
 TOPK_MAX_BIAS_CLASSES = 64
