@@ -1545,6 +1545,59 @@ int nrl_topk_sampled_scores(const float* user_vec, const float* table, int64_t B
 int nrl_gumbel_noise(const int64_t* user_key /* n */, const int64_t* row /* n */, int64_t n, uint64_t seed, float* out_u /* n */,
                      float* out_g /* n */, void* stream);
 
+/* nrl_catalogue_logz / nrl_list_logprob: how probable a list drawn by nrl_topk_sampled_scores was.  The policy is Plackett-Luce over
+ *   softmax(t), t = fmul_rn(s, inv_temp): s the bits nrl_topk_scores computes for the pair, t the first rounding of the sampled
+ *   entry's key (-0 counts as +0).  Neither the (B, V) scores nor their exponentials are written.
+ * nrl_catalogue_logz: per user, over P'_u = the rows inside V that are eligible, not excluded and whose t is finite, minus the rows
+ *   of drop_idx[u] (kd slots, -1 an empty slot; null with kd == 0; duplicates and rows outside P_u are harmless):
+ *     out_pop[u] = n = |P'_u|;  out_max[u] = m = max t (the bits of one scaled score);  out_logsum[u] = log sum exp(t - m), inside
+ *     [0, log n];  out_entropy[u] = log S - (sum (t - m) exp(t - m)) / S, the entropy of softmax(t) over P'_u in nats;
+ *     out_dropped[u] (may be null when kd == 0) = the distinct rows of drop_idx[u] that were eligible, not excluded and finite.
+ *     log Z = max + logsum; they are returned separately so that log p(row) = (t - max) - logsum keeps its precision.
+ *     An empty P'_u: max -inf, logsum -inf, entropy 0, pop 0.
+ *   status (one int32, required): NRL_TOPK_E_EXCLUDE / NRL_TOPK_E_OFFSETS as for nrl_topk_scores (a user with bad offsets gets the
+ *     outputs of an empty population); a NaN t of a row that is eligible, not excluded and not dropped sets NRL_TOPK_E_NAN, an
+ *     infinite one NRL_POLICY_E_INF, and the row is left out.
+ *   Determinism: the table is cut into ceil(nvt / tiles_per_chunk) chunks of tiles_per_chunk = ceil(nvt / NRL_TOPK_STAT_CHUNKS)
+ *     tiles of 128 rows (nvt = ceil(V / 128)): a function of V alone.  Inside a chunk, lane l of a wave folds columns l and 64 + l of
+ *     the tiles in ascending order into its own (m, S, W) -- a new maximum m' rescales by r = exp(m - m'): S' = S r,
+ *     W' = (W + (m - m') S) r -- the 64 lane states are merged by a butterfly over lane distances 1, 2, ..., 32, and the chunks are
+ *     folded in ascending order in float64, each output rounded to fp32 once.  Every fp32 operation is rounded on its own; exp is the
+ *     fast one (for a sum of exponentials the absolute error of a term counts, and |x| e^x <= 1 / e for x <= 0).  So a user's outputs
+ *     have the same bits whatever B, the user's place in the batch, the GEMM engine setting and whether eligible is null or all
+ *     ones.  No floating-point atomics, no allocation, no host synchronisation.
+ *   Workspace: nrl_catalogue_logz_workspace_size(B, V, D) (`_size`: the set of *_workspace_bytes names is pinned): 5 words per (user,
+ *     chunk).  Layout and carve are the same code; a short buffer is refused with NRL_E_WORKSPACE before any launch.
+ *   Checks (NRL_E_INVALID before any launch): those of nrl_topk_scores on B, V, D and the exclusion pointers, then inv_temp not
+ *     finite or negative, kd outside [0, NRL_TOPK_MAX_K], a null status; with B > 0 a null output, and with kd > 0 a null drop_idx or
+ *     out_dropped.  B == 0 succeeds without a launch; V == 0 gives empty populations.
+ * nrl_list_logprob: the log-probabilities of given lists, list_idx (B, k) int64 with -1 in TRAILING empty slots, against the tail
+ *   nrl_catalogue_logz returned under drop_idx = list_idx (the same masks and inv_temp): tail_max / tail_logsum / tail_pop /
+ *   tail_dropped (B).  out_score (B, k): the raw scores -- the bits nrl_topk_scores reports for (b, list_idx[b, j]), -inf in an
+ *   empty slot.  Then per user in float64, with a_j = fmul_rn(score_j, inv_temp):
+ *     R_j = exp(tail_max + tail_logsum) + sum_{i >= j} exp(a_i), accumulated from the last slot backwards and carried as its
+ *       logarithm against the running maximum (L' = max(L, a) + log1p(exp(-|L - a|))), so that no term underflows;
+ *     out_logp[b, j] = fl32(a_j - log R_j), +0 where slot j is all that is left (and in an empty slot);
+ *     out_total[b] = fl32(sum_j of them).
+ *   This tail form adds positive terms only; Z - sum_{i < j} exp(t_i) cancels to nothing once the first slots hold the mass.
+ *   A list is invalid when it has a hole before a row, a row outside [0, V), a row twice, or a row that is not in the user's
+ *     population (tail_dropped[b] differs from the number of its rows): that user's out_logp and out_total are NaN and
+ *     NRL_POLICY_E_LIST is ORed into status.
+ *   Checks (NRL_E_INVALID before any launch): those of nrl_topk_scores on B, V, D and k, inv_temp, a null status, B * k >= 2^31, and
+ *     with B > 0 a null argument.  B == 0 succeeds without a launch.  No workspace. */
+#define NRL_POLICY_E_LIST 128 /* an invalid list: that user's log-probabilities are NaN */
+#define NRL_POLICY_E_INF 256  /* an infinite scaled score of an eligible, not excluded row: the row is left out for that user */
+size_t nrl_catalogue_logz_workspace_size(int64_t B, int64_t V, int32_t D);
+int nrl_catalogue_logz(const float* user_vec, const float* table, int64_t B, int64_t V, int32_t D, float inv_temp,
+                       const int64_t* excl_idx, const int64_t* excl_off, const uint8_t* eligible,
+                       const int64_t* drop_idx /* (B, kd) or null */, int32_t kd, float* out_max /* B */, float* out_logsum /* B */,
+                       float* out_entropy /* B */, int32_t* out_pop /* B */, int32_t* out_dropped /* B, may be null when kd == 0 */,
+                       int32_t* status, void* ws, size_t ws_bytes, void* stream);
+int nrl_list_logprob(const float* user_vec, const float* table, int64_t B, int64_t V, int32_t D, float inv_temp,
+                     const int64_t* list_idx /* B, k */, int32_t k, const float* tail_max /* B */, const float* tail_logsum /* B */,
+                     const int32_t* tail_pop /* B */, const int32_t* tail_dropped /* B */, float* out_score /* B, k */,
+                     float* out_logp /* B, k */, float* out_total /* B */, int32_t* status, void* stream);
+
 /* nrl_catalogue_interest_ranks / nrl_catalogue_relu_ranks / nrl_catalogue_pooled_ranks: nrl_catalogue_ranks under the scores of
  *   nrl_topk_interest_scores (MINER: interests (B, K, D), gate (B, K, D) or null, mode 0 max / 1 mean / 2 weighted), of
  *   nrl_topk_relu_scores (DKN: q (B, Hd), proj (V, Hd), w2 (Hd), b2 (1), all on the device) and of nrl_topk_pooled_scores (NPA:

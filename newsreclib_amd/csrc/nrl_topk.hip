@@ -3,8 +3,8 @@
 // list (the history) and the rows an `eligible` mask removes.  The (B, V) score matrix is never written: every workgroup walks its
 // slice of the table once, tile by tile, and keeps per user only what its consumer needs.
 //
-// ONE WALK (tk_walk), seven tile producers, three consumers; fifteen of the sixteen walk kernels are its instantiations and nothing
-// else (tkr_scores_kernel keeps its own text, for its speed: see there).  The sixth producer, TkBiasProducer (the dot product plus
+// ONE WALK (tk_walk), seven tile producers, four consumers; fifteen of the seventeen walk kernels are its instantiations and nothing
+// else (tkr_scores_kernel keeps its own text, for its speed: see there; tkz_sum_kernel runs the walk with its user loop unrolled).  The sixth producer, TkBiasProducer (the dot product plus
 // a per-(user, class) bias: tkb_scores_kernel, tkbc_count_kernel, tkbcap_scores_kernel), is TkDot's column with one add behind it;
 // the seventh, TksProducer (Gumbel top-k: the dot product times inv_temp plus a hashed Gumbel variable per (seed, user key, row):
 // tks_scores_kernel under TkSelect, nrl_topk_sampled_scores), is TkDot's column with a multiply, the noise and an add behind it:
@@ -14,6 +14,9 @@
 //   TkCount  (rank)    tkc_count_kernel    tkic_count_kernel    tkec_count_kernel   tkrc_count_kernel   tkpc_count_kernel
 //   TkSelectCapped     tkcap_scores_kernel -                    tkecap_scores_kernel -                  -
 //     (top-k, at most m rows per class; k <= 64; merged by tk_merge_capped_kernel)
+//   TkLogZ (sums)      tkz_sum_kernel      -                    -                   -                   -
+//     (nrl_catalogue_logz: per user n, max t, sum exp(t - max), sum (t - max) exp(t - max) over t = score * inv_temp, the policy of
+//     the sampled entry; its slices are the statistics chunks, a function of V alone; folded by tkz_finish_kernel)
 // tkw_scores_kernel / tkwc_count_kernel (nrl_topk_window_scores / nrl_catalogue_window_ranks: a time window per user) run TkDot with
 // TkSelect / TkCount under a walk of their own, tkw_walk: tk_walk with the window ANDed into the eligibility the consumer sees and
 // table tiles outside every window of the workgroup skipped.  The plain kernels' text is untouched by it; see its section.
@@ -2175,6 +2178,340 @@ __global__ __launch_bounds__(256) void tks_noise_kernel(const int64_t* user_key,
   if (out_g) out_g[i] = tks_gumbel(u);
 }
 
+// ---- the log-partition of the sampled policy: nrl_catalogue_logz, nrl_list_logprob -----------------------------------------------------
+// What the Plackett-Luce policy of nrl_topk_sampled_scores needs to say how probable a drawn list was: per user, over the rows of the
+// user's population whose scaled score t = fmul_rn(s, inv_temp) (the first rounding of tks_perturb) is finite, minus the rows of an
+// optional per-user drop list: n, m = max t, S = sum exp(t - m), W = sum (t - m) exp(t - m).  TkLogZ is the SUMMING consumer of the
+// walk, under TkDot (tkz_sum_kernel); tkz_finish_kernel folds the chunks.
+//   * the slices of this walk are the statistics chunks of tke_statistics, a function of V alone, so the order of every reduction is:
+//     a user's outputs have the same bits whatever B, its place in the batch and the mask's form (null or all ones);
+//   * no cross-lane reduction per (user, table tile): where TkSelect nearly always leaves a user after a few instructions, this
+//     consumer has work for every user of every tile.  A lane owns columns lane and 64 + lane as elsewhere and keeps its own running
+//     (m, S, W) of each of its wave's 16 users IN REGISTERS (48 VGPRs); per tile the wave only counts (ballots: the population and
+//     the dropped rows).  Registers need the user loop unrolled, so the kernel runs tkz_walk, tk_walk's skeleton with that loop
+//     unrolled over TK_USERS_PER_WAVE and predicated; tk_walk's text is untouched.  The states in LDS instead (st[3][64][64], 48 KB,
+//     through tk_walk itself) gave the same bits at one workgroup per CU instead of two and 1.36 - 1.42x the time.
+//     flush reduces the 64 lane states once, by a butterfly over lane distances 1, 2, ..., 32 whose merge is symmetric bit for bit,
+//     and writes the chunk's (n, dropped, m, S, W);
+//   * rescaling a state from m to m' > m: r = exp(m - m'), S' = S r, W' = (W + (m - m') S) r; a state that underflows (r == 0) is 0;
+//   * mask order: exclusion sweep, drop sweep (tk_clear_excluded over the drop list: its first TK_XCAP entries cached in LDS, the
+//     rest read from global memory), NaN drop (NRL_TOPK_E_NAN), non-finite drop (NRL_POLICY_E_INF).  `dropped` counts the drop
+//     rows that were eligible, not excluded and finite, once each;
+//   * every add and multiply below is one rounded fp32 operation (contraction off, as tke_fold_z); tkz_exp is the fast exponential:
+//     for a sum of exponentials a term's ABSOLUTE error counts and |x| e^x <= 1 / e for x <= 0, so v_exp_f32 of x log2(e) is as good
+//     here as the library's expf (DESIGN.md 7y has both measured);
+//   * tkz_finish_kernel, one wave per user: the flags of tk_merge_kernel, then the chunks folded in ascending order in float64 (at most
+//     64) and each output rounded to fp32 once.
+// LDS of tkz_sum_kernel: the score tile (33 KB), the two caches (16.75 KB each), the counters: 67.1 KB, two workgroups per CU.
+struct TkzFields {
+  const int64_t* drop_idx;                     // (B, kd) or null: -1 an empty slot
+  int32_t kd;
+  float inv_temp;
+  float* parts;                                // (B, chunks, TKZ_WORDS): n, dropped (int32 bits), m, S, W
+  float *out_max, *out_logsum, *out_entropy;   // (B)
+  int32_t *out_pop, *out_dropped;              // (B); out_dropped may be null
+};
+constexpr int TKZ_WORDS = 5;
+
+constexpr size_t tkz_lds_bytes(int slots) {
+  return (size_t)slots * (8 + 8) + (size_t)slots * TK_XCAP * 4 * 2 + (size_t)slots * (4 + 4 + 8) + TK_BV;
+}
+constexpr size_t TKZ_LDS = TK_TILE_BYTES + tkz_lds_bytes(TK_BU);
+static_assert(2 * TKZ_LDS <= 160 * 1024, "two workgroups of the summing kernel fit a CU");
+
+__device__ __forceinline__ float tkz_exp(float x) { return __expf(x); }
+// the scaled score: the first rounding of tks_perturb, -0 as +0 (so that a maximum has one bit pattern)
+__device__ __forceinline__ float tkz_scale(float s, float inv_temp) {
+#pragma clang fp contract(off)
+  const float t = s * inv_temp;
+  return t == 0.f ? 0.f : t;
+}
+
+struct TkzState {                              // m == -inf: empty, and then S == W == 0
+  float m, S, W;
+};
+// the state rescaled to the maximum m2 > a.m (finite)
+__device__ __forceinline__ void tkz_rescale(TkzState& a, float m2) {
+#pragma clang fp contract(off)
+  if (a.m != -INFINITY) {
+    const float d = a.m - m2, r = tkz_exp(d);
+    if (r > 0.f) {
+      a.W = (a.W + d * a.S) * r;
+      a.S = a.S * r;
+    } else {
+      a.S = a.W = 0.f;
+    }
+  }
+  a.m = m2;
+}
+// one more term t <= a.m (finite)
+__device__ __forceinline__ void tkz_term(TkzState& a, float t) {
+#pragma clang fp contract(off)
+  const float x = t - a.m, e = tkz_exp(x);
+  a.S = a.S + e;
+  if (e > 0.f) a.W = a.W + x * e;
+}
+// the two columns of a lane: the valid ones among t0, t1, in that order
+__device__ __forceinline__ void tkz_add2(TkzState& a, bool b0, float t0, bool b1, float t1) {
+  float mt = b0 ? t0 : -INFINITY;
+  if (b1 && t1 > mt) mt = t1;
+  if (mt == -INFINITY) return;
+  if (mt > a.m) tkz_rescale(a, mt);
+  if (b0) tkz_term(a, t0);
+  if (b1) tkz_term(a, t1);
+}
+// two states as one; merge(a, b) and merge(b, a) have the same bits
+__device__ __forceinline__ TkzState tkz_merge(const TkzState& a, const TkzState& b) {
+#pragma clang fp contract(off)
+  if (b.m == -INFINITY) return a;
+  if (a.m == -INFINITY) return b;
+  TkzState o;
+  o.m = a.m > b.m ? a.m : b.m;
+  const float da = a.m - o.m, db = b.m - o.m, ra = tkz_exp(da), rb = tkz_exp(db);
+  const float Sa = ra > 0.f ? a.S * ra : 0.f, Sb = rb > 0.f ? b.S * rb : 0.f;
+  const float Wa = ra > 0.f ? (a.W + da * a.S) * ra : 0.f, Wb = rb > 0.f ? (b.W + db * b.S) * rb : 0.f;
+  o.S = Sa + Sb;
+  o.W = Wa + Wb;
+  return o;
+}
+
+// The summing consumer: per user of the tile two counters, the exclusion cache and the drop cache; the lane states are the caller's
+// registers, handed to user() and flush().
+struct TkLogZ {
+  int64_t* xs;                                 // [slots] exclusion cache: start
+  int64_t* ds;                                 // [slots] drop cache: start (u * kd)
+  int32_t* xl;                                 // [slots][TK_XCAP] exclusion cache: first rows
+  int32_t* dl;                                 // [slots][TK_XCAP] drop cache: first rows
+  int32_t* xn;                                 // [slots] exclusion cache: length
+  int32_t* dn;                                 // [slots] drop cache: length (kd, 0 for a slot without a user)
+  int32_t* cnt;                                // [slots][2] population, dropped rows
+  uint8_t* el;                                 // [TK_BV]
+  const TkzFields& F;
+  int slots;
+  bool inf = false;
+  __device__ __forceinline__ TkLogZ(unsigned char* p, int slots_, const TkzFields& f) : F(f), slots(slots_) {
+    xs = reinterpret_cast<int64_t*>(p);
+    ds = xs + slots;
+    xl = reinterpret_cast<int32_t*>(ds + slots);
+    dl = xl + slots * TK_XCAP;
+    xn = dl + slots * TK_XCAP;
+    dn = xn + slots;
+    cnt = dn + slots;
+    el = reinterpret_cast<uint8_t*>(cnt + 2 * slots);
+  }
+  __device__ __forceinline__ void prologue(const TkArgs& A, int64_t u0, int nu, int) const {
+    const int tid = threadIdx.x;
+    for (int i = tid; i < 2 * slots; i += TK_THREADS) cnt[i] = 0;
+    if (tid < slots) {
+      ds[tid] = (u0 + tid) * (int64_t)F.kd;
+      dn[tid] = tid < nu ? F.kd : 0;
+    }
+    tk_cache_exclusions(A, u0, nu, slots, xs, xn, xl);                       // (its barrier also publishes `ds` and `dn`)
+    for (int i = tid; i < slots * TK_XCAP; i += TK_THREADS) {
+      const int ul = i / TK_XCAP, j = i % TK_XCAP;
+      int32_t x = -1;
+      if (j < dn[ul]) {
+        const int64_t r = F.drop_idx[ds[ul] + j];
+        if (r >= 0 && r < A.V) x = (int32_t)r;
+      }
+      dl[i] = x;
+    }
+  }
+  // one user against one table tile, by the wave that serves the user; a: the lane's state of that user
+  __device__ __forceinline__ void user(const float* row, int ul, const int64_t* excl_idx, int v0, bool e_0, bool e_1, int lane, bool& nan,
+                                       TkzState& a) {
+    const float t0 = tkz_scale(row[lane], F.inv_temp), t1 = tkz_scale(row[64 + lane], F.inv_temp);
+    unsigned long long m0 = __ballot(e_0), m1 = __ballot(e_1);
+    tk_clear_excluded(xn + ul, xs + ul, xl + ul * TK_XCAP, excl_idx, v0, lane, m0, m1);
+    const unsigned long long a0 = m0, a1 = m1;
+    tk_clear_excluded(dn + ul, ds + ul, dl + ul * TK_XCAP, F.drop_idx, v0, lane, m0, m1);
+    const unsigned long long q0 = __ballot(t0 != t0), q1 = __ballot(t1 != t1);
+    if ((m0 & q0) | (m1 & q1)) nan = true;            // a NaN scaled score of a row of the population: flagged and left out
+    m0 &= ~q0;
+    m1 &= ~q1;
+    const unsigned long long i0 = __ballot(fabsf(t0) == INFINITY), i1 = __ballot(fabsf(t1) == INFINITY);
+    if ((m0 & i0) | (m1 & i1)) inf = true;            // an infinite one: flagged and left out
+    m0 &= ~i0;
+    m1 &= ~i1;
+    const int np = __popcll(m0) + __popcll(m1);
+    const int nd = __popcll(a0 & ~m0 & ~(q0 | i0)) + __popcll(a1 & ~m1 & ~(q1 | i1));
+    if ((np | nd) && lane == 0) {
+      cnt[2 * ul] += np;
+      cnt[2 * ul + 1] += nd;
+    }
+    if (np) tkz_add2(a, (m0 >> lane) & 1, t0, (m1 >> lane) & 1, t1);
+  }
+  __device__ __forceinline__ void flush(const TkArgs& A, int ul, int64_t u, int sl, int lane, TkzState a) {
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+      const TkzState b{__shfl_xor(a.m, off, 64), __shfl_xor(a.S, off, 64), __shfl_xor(a.W, off, 64)};
+      a = tkz_merge(a, b);
+    }
+    if (lane == 0) {
+      float* const o = F.parts + (u * A.slices + sl) * TKZ_WORDS;
+      o[0] = __int_as_float(cnt[2 * ul]);
+      o[1] = __int_as_float(cnt[2 * ul + 1]);
+      o[2] = a.m;
+      o[3] = a.S;
+      o[4] = a.W;
+      if (inf) atomicOr(A.status, NRL_POLICY_E_INF);
+    }
+    inf = false;
+  }
+};
+static_assert(tkz_lds_bytes(1) == 8 + 8 + 2 * TK_XCAP * 4 + 4 + 4 + 8 + TK_BV, "tkz_lds_bytes counts the members of TkLogZ");
+
+// tkz_walk: tk_walk for TkDot under TkLogZ with the user loop unrolled over the wave's TK_USERS_PER_WAVE users and predicated, so that
+// user i's lane state a[i] is indexed by a compile-time constant and stays in registers (no scratch).  The stages, their order and
+// the barriers are tk_walk's.
+__global__ __launch_bounds__(TK_THREADS) void tkz_sum_kernel(TkWith<TkArgs, TkzFields> A) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char tk_smem[];
+  TkDot P(tk_smem);
+  TkLogZ C(P.rest, TK_BU, A);
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int sl = (int)(blockIdx.x % (unsigned)A.slices);
+  const int64_t u0 = (int64_t)(blockIdx.x / (unsigned)A.slices) * TK_BU;
+  const int nu = A.B - u0 < TK_BU ? (int)(A.B - u0) : TK_BU;
+  int v_begin, nvt;
+  tk_slice(A, sl, v_begin, nvt);
+  P.stage(A, u0, nu);
+  C.prologue(A, u0, nu, TK_BU);
+  const int ul_begin = TkDot::first(wave), ul_end = TkDot::end(wave, nu);
+  bool nan = false;
+  TkzState a[TK_USERS_PER_WAVE];
+#pragma unroll
+  for (int i = 0; i < TK_USERS_PER_WAVE; ++i) a[i] = TkzState{-INFINITY, 0.f, 0.f};
+  for (int vt = 0; vt < nvt; ++vt) {
+    const int v0 = v_begin + vt * TK_BV;
+    tk_fill_eligible(A.eligible, v0, A.V, C.el);
+    P.tile(A, v0, nu);
+    const bool e_0 = C.el[lane] != 0, e_1 = C.el[64 + lane] != 0;
+#pragma unroll
+    for (int i = 0; i < TK_USERS_PER_WAVE; ++i)
+      if (ul_begin + i < ul_end) C.user(P.row(ul_begin + i), ul_begin + i, A.excl_idx, v0, e_0, e_1, lane, nan, a[i]);
+    __syncthreads();
+  }
+  if (nan && lane == 0) atomicOr(A.status, NRL_TOPK_E_NAN);
+  wave_lds_sync();
+#pragma unroll
+  for (int i = 0; i < TK_USERS_PER_WAVE; ++i)
+    if (ul_begin + i < ul_end) C.flush(A, ul_begin + i, u0 + ul_begin + i, sl, lane, a[i]);
+}
+
+// one wave per user: status flags, the fold of the user's chunks in float64, the outputs
+__global__ __launch_bounds__(64) void tkz_finish_kernel(TkWith<TkArgs, TkzFields> A) {
+#pragma clang fp contract(off)
+  const int64_t u = blockIdx.x;
+  const int lane = threadIdx.x;
+  int64_t s, n;
+  const bool ok = tk_excl_range(A, u, s, n);
+  if (!ok) {
+    if (lane == 0) atomicOr(A.status, NRL_TOPK_E_OFFSETS);
+  } else {
+    int bad = 0;
+    for (int64_t i = lane; i < n; i += 64) {
+      const int64_t x = A.excl_idx[s + i];
+      bad |= (x < 0 || x >= A.V);
+    }
+    if (__ballot(bad) && lane == 0) atomicOr(A.status, NRL_TOPK_E_EXCLUDE);
+  }
+  if (lane != 0) return;
+  int64_t pop = 0, dropped = 0;
+  double m = -INFINITY, S = 0.0, W = 0.0;
+  for (int c = 0; ok && c < A.slices; ++c) {
+    const float* const p = A.parts + (u * A.slices + c) * TKZ_WORDS;
+    const int nb = __float_as_int(p[0]);
+    dropped += __float_as_int(p[1]);
+    if (nb == 0) continue;
+    pop += nb;
+    const double mb = p[2], Sb = p[3], Wb = p[4];
+    if (m == -INFINITY) {
+      m = mb;
+      S = Sb;
+      W = Wb;
+      continue;
+    }
+    const double m2 = m > mb ? m : mb, da = m - m2, db = mb - m2, ra = exp(da), rb = exp(db);
+    const double Wa = ra > 0.0 ? (W + da * S) * ra : 0.0, Wc = rb > 0.0 ? (Wb + db * Sb) * rb : 0.0;
+    S = (ra > 0.0 ? S * ra : 0.0) + (rb > 0.0 ? Sb * rb : 0.0);
+    W = Wa + Wc;
+    m = m2;
+  }
+  const double ls = pop ? log(S) : -INFINITY, h = pop ? ls - W / S : 0.0;
+  A.out_max[u] = (float)m;
+  A.out_logsum[u] = (float)ls;
+  A.out_entropy[u] = (float)(h > 0.0 ? h : 0.0);
+  A.out_pop[u] = (int32_t)pop;
+  if (A.out_dropped) A.out_dropped[u] = (int32_t)dropped;
+}
+
+// The log-probabilities of the lists, one wave per user, in float64 and in the TAIL form: with a_j the scaled score of slot j, the
+// denominator of slot j is R_j = exp(tail_max + tail_logsum) + sum_{i >= j} exp(a_i), accumulated from the last slot backwards
+// (positive terms only: Z - sum_{i < j} cancels to nothing once the first slots hold the mass), and log p_j = a_j - log R_j.  log R_j
+// is carried as a running log-sum-exp, L' = max(L, a) + log1p(exp(-|L - a|)), i.e. against the running maximum rather than one M for
+// the whole list: the same sum, and no term underflows however far the scores spread.  Where slot j is all that is left, L' = a_j
+// and log p_j is exactly 0.  `score` are the raw scores tks_raw_kernel wrote.
+struct TkzListArgs {
+  const int64_t* idx;                          // (B, k): rows, -1 in trailing empty slots
+  const float* score;                          // (B, k)
+  const float *tail_max, *tail_logsum;         // (B)
+  const int32_t *tail_pop, *tail_dropped;      // (B)
+  float *out_logp, *out_total;                 // (B, k), (B)
+  int32_t* status;
+  int64_t V;
+  int32_t k;
+  float inv_temp;
+};
+__global__ __launch_bounds__(64) void tkz_list_kernel(TkzListArgs A) {
+  __shared__ double sa[NRL_TOPK_MAX_K];
+  const int64_t u = blockIdx.x;
+  const int lane = threadIdx.x, k = A.k;
+  const int64_t* const L = A.idx + u * k;
+  const int64_t r0 = lane < k ? L[lane] : -1, r1 = lane + 64 < k ? L[lane + 64] : -1;
+  const unsigned long long f0 = __ballot(r0 != -1), f1 = __ballot(r1 != -1);
+  const int cnt = __popcll(f0) + __popcll(f1);
+  // valid: no hole before a row, every row inside [0, V), no row twice, and every row found in the user's population
+  const unsigned long long w0 = cnt >= 64 ? ~0ull : (1ull << cnt) - 1, w1 = cnt <= 64 ? 0ull : (cnt >= 128 ? ~0ull : (1ull << (cnt - 64)) - 1);
+  bool bad = (r0 != -1 && (r0 < 0 || r0 >= A.V)) || (r1 != -1 && (r1 < 0 || r1 >= A.V));
+  for (int j = 0; j < cnt; ++j) {
+    const int64_t v = (int64_t)tk_shfl((unsigned long long)(j < 64 ? r0 : r1), j & 63);
+    bad |= (lane != j && r0 == v) || (lane + 64 != j && r1 == v);
+  }
+  const bool valid = f0 == w0 && f1 == w1 && !__ballot(bad) && A.tail_dropped[u] == cnt;
+  if (!valid) {
+    const float nanv = __uint_as_float(0x7FC00000u);
+    for (int p = lane; p < k; p += 64) A.out_logp[u * k + p] = nanv;
+    if (lane == 0) {
+      A.out_total[u] = nanv;
+      atomicOr(A.status, NRL_POLICY_E_LIST);
+    }
+    return;
+  }
+  for (int p = lane; p < cnt; p += 64) sa[p] = (double)tkz_scale(A.score[u * k + p], A.inv_temp);
+  __syncthreads();
+  if (lane == 0) {
+    double L = A.tail_pop[u] > 0 ? (double)A.tail_max[u] + (double)A.tail_logsum[u] : -INFINITY;
+    for (int j = cnt - 1; j >= 0; --j) {
+      const double a = sa[j];
+      if (L == -INFINITY) {
+        L = a;
+      } else {
+        const double hi = L > a ? L : a, lo = L > a ? a : L;
+        L = hi + log1p(exp(lo - hi));
+      }
+      sa[j] = a - L;
+    }
+  }
+  __syncthreads();
+  for (int p = lane; p < k; p += 64) A.out_logp[u * k + p] = p < cnt ? (float)sa[p] : 0.f;
+  if (lane == 0) {
+    double total = 0.0;
+    for (int j = 0; j < cnt; ++j) total += sa[j];
+    A.out_total[u] = (float)total;
+  }
+}
+
 // ---- greedy MMR re-ranking of a pool (nrl_mmr_rerank) ------------------------------------------------------------------------------
 // One workgroup per user.  The pool's Gram matrix is ceil(N / 64) calls of tk_tile_accumulate<1, true>: the A rows are pool slots
 // 64 h ... 64 h + 63 read in place, the gathered B rows the whole pool, so G[i][j] is the chain of nrl_topk_scores over the two
@@ -3071,6 +3408,82 @@ int nrl_gumbel_noise(const int64_t* user_key, const int64_t* row, int64_t n, uin
   if (n == 0) return NRL_OK;
   NRL_REQUIRE(user_key && row && (out_u || out_g), "gumbel_noise: null argument");
   tks_noise_kernel<<<(unsigned)ceil_div(n, 256), 256, 0, (hipStream_t)stream>>>(user_key, row, n, tks_call_key(seed), out_u, out_g);
+  NRL_LAUNCH_CHECK();
+  return NRL_OK;
+}
+
+// nrl_catalogue_logz: the chunks of tke_statistics (a function of V alone: no `slices`), tkz_sum_kernel over them, tkz_finish_kernel
+static void tkz_plan(int64_t V, int32_t& chunks, int32_t& tiles_per_chunk) {
+  const int64_t nvt = ceil_div(V, TK_BV);
+  tiles_per_chunk = (int32_t)(nvt > 0 ? ceil_div(nvt, NRL_TOPK_STAT_CHUNKS) : 1);
+  chunks = (int32_t)(nvt > 0 ? ceil_div(nvt, tiles_per_chunk) : 0);
+}
+// (n, dropped, m, S, W) per (user, chunk); never empty
+static void tkz_layout(Arena& a, int64_t B, int64_t V, float** parts) {
+  int32_t chunks, tpc;
+  tkz_plan(V, chunks, tpc);
+  const size_t words = (size_t)B * (size_t)chunks * TKZ_WORDS;
+  *parts = a.take<float>(words > 0 ? words : 1);
+}
+
+size_t nrl_catalogue_logz_workspace_size(int64_t B, int64_t V, int32_t D) {
+  if (!tk_shape_ok(B, V, D, 1)) return 256;
+  return measure_workspace<float*>([&](Arena& a, auto* w) { tkz_layout(a, B, V, w); });
+}
+
+int nrl_catalogue_logz(const float* user_vec, const float* table, int64_t B, int64_t V, int32_t D, float inv_temp,
+                       const int64_t* excl_idx, const int64_t* excl_off, const uint8_t* eligible, const int64_t* drop_idx, int32_t kd,
+                       float* out_max, float* out_logsum, float* out_entropy, int32_t* out_pop, int32_t* out_dropped, int32_t* status,
+                       void* ws, size_t ws_bytes, void* stream) {
+  const char* who = "catalogue_logz";
+  NRL_REQUIRE(B >= 0 && V >= 0 && D >= 0, "%s: negative size", who);
+  NRL_TRY(tk_check(who, B, V, D, 1, excl_idx, excl_off));
+  NRL_REQUIRE(inv_temp >= 0.f && inv_temp < INFINITY, "%s: inv_temp finite and >= 0 (got %g)", who, (double)inv_temp);
+  NRL_REQUIRE(kd >= 0 && kd <= NRL_TOPK_MAX_K, "%s: kd in [0, %d] (got %d)", who, NRL_TOPK_MAX_K, kd);
+  NRL_REQUIRE(status, "%s: the status word is required", who);
+  if (B == 0) return NRL_OK;
+  NRL_REQUIRE(out_max && out_logsum && out_entropy && out_pop && user_vec && (V == 0 || table), "%s: null argument", who);
+  NRL_REQUIRE(kd == 0 || (drop_idx && out_dropped), "%s: kd > 0 needs drop_idx and out_dropped", who);
+  float* parts;
+  NRL_TRY(carve_workspace(ws, ws_bytes, [&](Arena& a) { tkz_layout(a, B, V, &parts); }));
+  TkWith<TkArgs, TkzFields> A;
+  static_cast<TkArgs&>(A) = tk_args(user_vec, table, B, V, D, 1, excl_idx, excl_off, eligible, nullptr, nullptr, nullptr, status);
+  static_cast<TkzFields&>(A) = TkzFields{kd > 0 ? drop_idx : nullptr, kd, inv_temp, parts, out_max, out_logsum, out_entropy, out_pop, out_dropped};
+  tkz_plan(V, A.slices, A.tiles_per_slice);
+  const int64_t blocks = ceil_div(B, TK_BU) * A.slices;
+  NRL_REQUIRE(blocks < ((int64_t)1 << 31), "%s: grid too large (%lld workgroups)", who, (long long)blocks);
+  hipStream_t st = (hipStream_t)stream;
+  if (blocks > 0) {
+    // more than 64 KB of dynamic LDS needs the attribute; it belongs to the current device, so it is set per call
+    NRL_HIP(hipFuncSetAttribute((const void*)tkz_sum_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    tkz_sum_kernel<<<(unsigned)blocks, TK_THREADS, TKZ_LDS, st>>>(A);
+    NRL_LAUNCH_CHECK();
+  }
+  tkz_finish_kernel<<<(unsigned)B, 64, 0, st>>>(A);
+  NRL_LAUNCH_CHECK();
+  return NRL_OK;
+}
+
+// nrl_list_logprob: the raw scores of the listed rows as nrl_topk_sampled_scores computes those of the drawn rows, then tkz_list_kernel
+int nrl_list_logprob(const float* user_vec, const float* table, int64_t B, int64_t V, int32_t D, float inv_temp, const int64_t* list_idx,
+                     int32_t k, const float* tail_max, const float* tail_logsum, const int32_t* tail_pop, const int32_t* tail_dropped,
+                     float* out_score, float* out_logp, float* out_total, int32_t* status, void* stream) {
+  const char* who = "list_logprob";
+  NRL_REQUIRE(B >= 0 && V >= 0 && D >= 0, "%s: negative size", who);
+  NRL_TRY(tk_check(who, B, V, D, k, nullptr, nullptr));
+  NRL_REQUIRE(inv_temp >= 0.f && inv_temp < INFINITY, "%s: inv_temp finite and >= 0 (got %g)", who, (double)inv_temp);
+  NRL_REQUIRE(status, "%s: the status word is required", who);
+  NRL_REQUIRE(B * (int64_t)k < ((int64_t)1 << 31), "%s: at most 2^31 - 1 list slots per call (got %lld)", who, (long long)(B * k));
+  if (B == 0) return NRL_OK;
+  NRL_REQUIRE(list_idx && tail_max && tail_logsum && tail_pop && tail_dropped && out_score && out_logp && out_total && user_vec &&
+                  (V == 0 || table),
+              "%s: null argument", who);
+  hipStream_t st = (hipStream_t)stream;
+  const int64_t n = B * k;
+  tks_raw_kernel<<<(unsigned)ceil_div(n, TK_BU), TK_THREADS, 0, st>>>(TksRawArgs{user_vec, table, list_idx, out_score, V, (int32_t)n, D, k});
+  NRL_LAUNCH_CHECK();
+  tkz_list_kernel<<<(unsigned)B, 64, 0, st>>>(
+      TkzListArgs{list_idx, out_score, tail_max, tail_logsum, tail_pop, tail_dropped, out_logp, out_total, status, V, k, inv_temp});
   NRL_LAUNCH_CHECK();
   return NRL_OK;
 }

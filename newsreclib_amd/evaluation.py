@@ -294,6 +294,45 @@ def _sample_policy(who: str, cache, sample, cap=None, window=None, rerankers=())
     return 1.0 / temperature, seed
 
 
+def _policy_refusal(who: str, cache, window=None) -> None:
+    """``NotImplementedError`` where the log-partition has no kernel: the summing consumer (``TkLogZ``) is instantiated under the
+    plain dot-product producer and the plain walk alone."""
+    if window is not None:
+        raise NotImplementedError(f"{who} with window=...: the summing consumer (tkz_sum_kernel) runs under the plain walk; a "
+                                  "log-partition kernel under the windowed walk (tkw_walk) does not exist yet")
+    module = getattr(cache, "module", None)
+    kind = [a for a in ("multi_interest_scorer", "dnn_predictor_scorer", "personalized_pooling_scorer", "class_biased_scorer")
+            if getattr(module, a, False)]
+    if hasattr(cache, "recommend_ensemble"):
+        kind.append("z-scored ensemble (MannerVectorCache)")
+    if hasattr(cache, "recommend_pooled"):
+        kind.append("personalized_pooling_scorer (NpaFeatureCache)")
+    if kind:
+        raise NotImplementedError(f"{who} is the log-partition of the Plackett-Luce policy over plain dot-product scores: "
+                                  f"{type(cache).__name__} over {type(module).__name__} is a `{kind[0]}`, and the summing consumer "
+                                  "(tkz_sum_kernel: TkLogZ under TkDot) is instantiated under the dot-product producer alone; a "
+                                  "log-partition kernel for that scorer does not exist yet")
+
+
+def _policy_lists(lists, n_users: int) -> torch.Tensor:
+    """``lists`` of ``list_log_probs`` checked before any device work: int64 (``TypeError``), (n_users, k <= ops.TOPK_MAX_K)
+    (``ValueError``)."""
+    if not isinstance(lists, torch.Tensor) or lists.dtype != torch.int64:
+        raise TypeError(f"newsreclib_amd: `lists` must be an int64 tensor, got "
+                        f"{lists.dtype if isinstance(lists, torch.Tensor) else type(lists).__name__}")
+    if lists.dim() != 2 or lists.shape[0] != n_users or not 1 <= lists.shape[1] <= ops.TOPK_MAX_K:
+        raise ValueError(f"newsreclib_amd: `lists` must be (B, k) with one list per user ({n_users}) and 1 <= k <= "
+                         f"{ops.TOPK_MAX_K}, got {tuple(lists.shape)}")
+    return lists
+
+
+def _policy_inv_temp(inv_temp) -> float:
+    inv_temp = float(inv_temp)
+    if not math.isfinite(inv_temp) or inv_temp < 0:
+        raise ValueError(f"newsreclib_amd: `inv_temp` must be finite and >= 0, got {inv_temp!r}")
+    return inv_temp
+
+
 def _user_ids(chunk: Sequence[Dict], lo: int) -> List[int]:
     """The id of each user dictionary of a batch that starts at position ``lo`` of the list: its ``user_id``, or position + 1."""
     return [int(u["user_id"]) if "user_id" in u else lo + j + 1 for j, u in enumerate(chunk)]
@@ -545,6 +584,38 @@ class NewsVectorCache(_ImpressionCache):
         return ops.topk_scores(user, self.vectors, k, *tail)
 
     @torch.no_grad()
+    def policy_stats(self, hist_idx: torch.Tensor, hist_sizes: torch.Tensor, inv_temp: float, user_idx: Optional[torch.Tensor] = None,
+                     exclude_history: bool = True, eligible: Optional[torch.Tensor] = None, window=None) -> Dict[str, torch.Tensor]:
+        """What the sampled policy of ``recommend(sample=(inv_temp, ...))`` looks like per user, over the population ``recommend``
+        selects from: {"max", "log_sum" (``log sum exp(t - max)``), "log_z" (= max + log_sum, fp32), "entropy" (nats),
+        "population" (int32), "status" (``ops.POLICY_FLAGS``)}, all on the device (``ops.catalogue_logz``).  ``exp(entropy)`` is the
+        effective catalogue size, ``exp(-log_sum)`` the probability of the user's best news.  The caller's side is ``recommend``'s
+        (``hist_idx`` on the GPU, ``hist_sizes`` on the host); nothing is read back.  ``NotImplementedError`` with ``window`` and
+        for every scorer but the plain dot product: their log-partition kernels do not exist yet."""
+        _policy_refusal("policy_stats", self, window)
+        inv_temp = _policy_inv_temp(inv_temp)
+        user, _, tail = self._dot_users("recommend", hist_idx, hist_sizes, user_idx, exclude_history, eligible, None)
+        mx, ls, ent, pop, _, status = ops.catalogue_logz(user, self.vectors, inv_temp, *tail)
+        return {"max": mx, "log_sum": ls, "log_z": mx + ls, "entropy": ent, "population": pop, "status": status}
+
+    @torch.no_grad()
+    def list_log_probs(self, hist_idx: torch.Tensor, hist_sizes: torch.Tensor, lists: torch.Tensor, inv_temp: float,
+                       user_idx: Optional[torch.Tensor] = None, exclude_history: bool = True,
+                       eligible: Optional[torch.Tensor] = None, window=None):
+        """The log-probability of ``lists`` ((B, k) int64 news rows, host or device, ``-1`` in trailing empty slots) under the
+        policy ``recommend(sample=(inv_temp, ...))`` draws from -> (logp (B, k) fp32, total (B) fp32, score (B, k) fp32, status):
+        ``ops.list_logprob`` against the cached table with ``recommend``'s user side, exclusion of the history and ``eligible``.
+        A list the policy could not have drawn (a news of the history, an ineligible one, one listed twice) is NaN for that user
+        and sets bit 128 of ``status`` (``ops.POLICY_FLAGS``).  Nothing is read back.  Refusals as ``policy_stats``."""
+        _policy_refusal("list_log_probs", self, window)
+        inv_temp = _policy_inv_temp(inv_temp)
+        lists = _policy_lists(lists, int(hist_sizes.numel()))
+        user, _, tail = self._dot_users("recommend", hist_idx, hist_sizes, user_idx, exclude_history, eligible, None)
+        if not lists.is_cuda:
+            lists = lists.pin_memory().to(user.device, non_blocking=True)
+        return ops.list_logprob(user, self.vectors, lists, inv_temp, *tail)
+
+    @torch.no_grad()
     def recommend_capped(self, hist_idx: torch.Tensor, hist_sizes: torch.Tensor, k: int, aspect: str, max_per_class: int,
                          user_idx: Optional[torch.Tensor] = None, exclude_history: bool = True,
                          eligible: Optional[torch.Tensor] = None):
@@ -742,6 +813,12 @@ class MannerVectorCache(_ImpressionCache):
                                   "one sub-model's NewsVectorCache instead, or name the population: `rank_clicks_ensemble` "
                                   "z-scores over every row a user may be recommended, as `recommend_ensemble` does")
 
+    def policy_stats(self, *args, **kwargs):
+        _policy_refusal("policy_stats", self)
+
+    def list_log_probs(self, *args, **kwargs):
+        _policy_refusal("list_log_probs", self)
+
     @torch.no_grad()
     def recommend_ensemble(self, hist_idx: torch.Tensor, hist_sizes: torch.Tensor, k: int, user_idx: Optional[torch.Tensor] = None,
                            exclude_history: bool = True, eligible: Optional[torch.Tensor] = None, return_stats: bool = False):
@@ -905,6 +982,12 @@ class NpaFeatureCache(_ImpressionCache):
         raise NotImplementedError("only the dot-product families are served by `rank_clicks` so far (NewsVectorCache over a "
                                   "`dot_product_scorer` module): NPA's personalized-pooling score is counted by "
                                   "`rank_clicks_pooled`")
+
+    def policy_stats(self, *args, **kwargs):
+        _policy_refusal("policy_stats", self)
+
+    def list_log_probs(self, *args, **kwargs):
+        _policy_refusal("list_log_probs", self)
 
     def rerank_diverse(self, *args, **kwargs):
         raise NotImplementedError("MMR trades relevance against the similarity of two news vectors, and an NPA news vector depends "
@@ -1229,14 +1312,20 @@ def recommend_users(cache: NewsVectorCache, users: Sequence[Dict], k: int, batch
 
 
 def sample_recommendations(cache: NewsVectorCache, users: Sequence[Dict], k: int, draws: int, temperature: float, seed: int,
-                           batch_size: int = 512, eligible: Optional[torch.Tensor] = None) -> torch.Tensor:
+                           batch_size: int = 512, eligible: Optional[torch.Tensor] = None, log_probs: bool = False):
     """``draws`` independent lists per user from the Plackett-Luce policy over ``softmax(score / temperature)`` -> news rows
     (n_users, draws, k) int64 on the host, ``-1`` beyond a user's population.  Draw ``j`` is the list
     ``recommend_users(..., sample=(temperature, (seed + j) mod 2^64))`` gives the user -- the same keys (``user_id``, or position
     + 1), the same refusals -- so it is reproducible user by user whatever the batching.  A batch's histories are uploaded once and
     serve all its draws; one device-to-host copy per batch and draw; a status flag (``ops.TOPK_FLAGS``) is passed on as a warning.
     The cost is ``draws`` full passes over the table: every draw recomputes the scores.  Reusing a score tile for several draws
-    inside the kernel is the obvious next step and is not done here."""
+    inside the kernel is the obvious next step and is not done here.
+
+    ``log_probs=True`` returns ``(lists, logp)``: ``logp`` (n_users, draws, k) float32 on the host, slot by slot the log-probability
+    ``cache.list_log_probs`` gives the drawn list under the same temperature (``+0`` in an empty slot; a list's propensity is the
+    sum over its slots).  The histories are still uploaded once per batch; every draw costs one more pass over the table (the
+    tail of its list) and its copy carries the log-probabilities as well.  The default returns exactly what it returned without
+    the argument."""
     who = "sample_recommendations"
     inv_temp, seed = _sample_policy(who, cache, (temperature, seed))
     draws = int(draws)
@@ -1244,6 +1333,7 @@ def sample_recommendations(cache: NewsVectorCache, users: Sequence[Dict], k: int
         raise ValueError(f"{who}: draws >= 0, got {draws}")
     dev = cache.table.device
     out = torch.full((len(users), draws, max(int(k), 0)), -1, dtype=torch.int64)
+    logp = torch.zeros((len(users), draws, max(int(k), 0)), dtype=torch.float32) if log_probs else None
     word = 0
     for lo in range(0, len(users), batch_size):
         chunk = users[lo:lo + batch_size]
@@ -1254,12 +1344,64 @@ def sample_recommendations(cache: NewsVectorCache, users: Sequence[Dict], k: int
         for j in range(draws):
             idx, _, status = cache.recommend(hist, hs, k, user_idx=uidx, eligible=eligible,
                                              sample=(inv_temp, (seed + j) % 2 ** 64, keys))
-            packed = torch.cat([idx, status.long().expand(idx.shape[0], 1)], dim=1).cpu()                 # the one copy
+            if log_probs:
+                lp, _, _, lp_status = cache.list_log_probs(hist, hs, idx, inv_temp, user_idx=uidx, eligible=eligible)
+                packed = torch.cat([idx.double(), lp.double(), (status | lp_status).double().expand(idx.shape[0], 1)], dim=1).cpu()
+                logp[lo:lo + len(chunk), j] = packed[:, idx.shape[1]:-1].float()
+                packed = torch.cat([packed[:, :idx.shape[1]], packed[:, -1:]], dim=1).long()
+            else:
+                packed = torch.cat([idx, status.long().expand(idx.shape[0], 1)], dim=1).cpu()             # the one copy
             out[lo:lo + len(chunk), j] = packed[:, :-1]
             word |= int(packed[0, -1]) if packed.shape[0] else 0
     if word:                                                # the kernel has dealt with each of these; the caller should know
         import warnings
-        warnings.warn(f"{who}: " + "; ".join(msg for bit, msg in ops.TOPK_FLAGS.items() if word & bit))
+        flags = ops.POLICY_FLAGS if log_probs else ops.TOPK_FLAGS
+        warnings.warn(f"{who}: " + "; ".join(msg for bit, msg in flags.items() if word & bit))
+    return (out, logp) if log_probs else out
+
+
+def policy_report(cache: NewsVectorCache, users: Sequence[Dict], temperatures: Sequence[float], batch_size: int = 512,
+                  eligible: Optional[torch.Tensor] = None) -> Dict[float, Dict[str, float]]:
+    """How peaked the sampled policy is at each of ``temperatures`` (each finite and > 0), averaged over ``users`` ({"hist": idx
+    tensor[, "user_idx"]}) -> {temperature: {"entropy": mean entropy in nats, "perplexity": mean ``exp(entropy)`` -- the effective
+    catalogue size --, "top1": mean probability of the user's best news, ``exp(-log_sum)``}}: ``cache.policy_stats`` per batch and
+    temperature, the histories of a batch uploaded once.  The per-user values of all batches stay on the device; one
+    device-to-host copy per temperature, at the end.  Users with an empty population count with entropy 0, perplexity 1 and
+    top1 0.  A status flag (``ops.POLICY_FLAGS``) is passed on as one warning.  Refusals as ``policy_stats``."""
+    _policy_refusal("policy_report", cache)
+    temps = [float(t) for t in temperatures]
+    for t in temps:
+        if not math.isfinite(t) or t <= 0:
+            raise ValueError(f"policy_report: every temperature must be finite and > 0, got {t!r}")
+    dev = cache.table.device
+    kept = {t: [] for t in temps}
+    for lo in range(0, len(users), batch_size):
+        chunk = users[lo:lo + batch_size]
+        hs = torch.tensor([len(u["hist"]) for u in chunk])
+        hist = torch.cat([torch.as_tensor(u["hist"]).long() for u in chunk]).to(dev)
+        uidx = torch.stack([torch.as_tensor(u["user_idx"]) for u in chunk]) if "user_idx" in chunk[0] else None
+        for t in temps:
+            st = cache.policy_stats(hist, hs, 1.0 / t, user_idx=uidx, eligible=eligible)
+            ent, ls = st["entropy"].double(), st["log_sum"].double()
+            top1 = torch.where(st["population"] > 0, torch.exp(-ls), torch.zeros_like(ls))
+            kept[t].append(torch.cat([ent, torch.exp(ent), top1, st["status"].double()]))
+    out, word = {}, 0
+    for t in temps:
+        if not kept[t]:
+            out[t] = {"entropy": float("nan"), "perplexity": float("nan"), "top1": float("nan")}
+            continue
+        ent, ppl, top1 = [], [], []
+        for part in torch.cat(kept[t]).cpu().split([p.numel() for p in kept[t]]):                      # the one copy
+            n = (part.numel() - 1) // 3
+            ent.append(part[:n])
+            ppl.append(part[n:2 * n])
+            top1.append(part[2 * n:3 * n])
+            word |= int(part[-1])
+        out[t] = {"entropy": float(torch.cat(ent).mean()), "perplexity": float(torch.cat(ppl).mean()),
+                  "top1": float(torch.cat(top1).mean())}
+    if word:                                                # the kernel has dealt with each of these; the caller should know
+        import warnings
+        warnings.warn("policy_report: " + "; ".join(msg for bit, msg in ops.POLICY_FLAGS.items() if word & bit))
     return out
 
 

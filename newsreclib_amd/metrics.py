@@ -419,3 +419,31 @@ class GridStreamingMetrics:
                              "; ".join(msg for bit, msg in ops.METRICS_FLAGS.items() if flags & bit))
         n = int(self.count)
         return {"weights": self.weights.tolist(), "columns": list(self.columns), "values": (self.sums / max(n, 1)).tolist()}
+
+
+def snips_value(reward, logp_target, logp_logging, clip: Optional[float] = None) -> Tuple[float, float]:
+    """Self-normalised importance sampling (SNIPS) over logged lists -> (value, effective sample size), on the host in float64.
+    ``reward`` (n): the reward each logged list earned; ``logp_target`` / ``logp_logging`` (n): the list's log-probability under
+    the policy being evaluated and under the policy that drew it (``list_log_probs``' totals, or the sum of
+    ``sample_recommendations(log_probs=True)``'s slots).  The weights are ``w = exp(logp_target - logp_logging)``, computed after
+    subtracting the largest log-ratio (self-normalisation cancels the shift, and no weight overflows); ``clip`` caps ``w``, in
+    its own units, before it is normalised.  ``value = sum w r / sum w``; ``effective sample size = (sum w)^2 / sum w^2``, between
+    1 and n.  No lists: ``(nan, 0.0)``.  ``ValueError`` for lengths that differ, a non-finite log-probability or ``clip <= 0``."""
+    r = torch.as_tensor(reward, dtype=torch.float64).reshape(-1).cpu()
+    lt = torch.as_tensor(logp_target, dtype=torch.float64).reshape(-1).cpu()
+    ll = torch.as_tensor(logp_logging, dtype=torch.float64).reshape(-1).cpu()
+    if not (r.numel() == lt.numel() == ll.numel()):
+        raise ValueError(f"snips_value: one reward and two log-probabilities per list, got {r.numel()}, {lt.numel()} and {ll.numel()}")
+    if clip is not None and not float(clip) > 0:
+        raise ValueError(f"snips_value: clip > 0, got {clip!r}")
+    if r.numel() == 0:
+        return float("nan"), 0.0
+    if not bool(torch.isfinite(lt).all() and torch.isfinite(ll).all()):
+        raise ValueError("snips_value: a log-probability is not finite (an invalid list, or one the logging policy could not draw)")
+    ratio = lt - ll
+    shift = ratio.max()
+    w = torch.exp(ratio - shift)
+    if clip is not None:
+        w = torch.minimum(w, torch.exp(torch.log(torch.tensor(float(clip), dtype=torch.float64)) - shift))
+    total = w.sum()
+    return float((w * r).sum() / total), float(total * total / (w * w).sum())

@@ -1088,6 +1088,94 @@ def topk_sampled_scores(user_vec: torch.Tensor, table: torch.Tensor, k: int, use
     return idx, key, score, status
 
 
+# the status word of ``catalogue_logz`` / ``list_logprob``: the flags of ``topk_scores`` they share, in their own words, and their
+# two own bits (a dictionary of its own: the key set of ``TOPK_FLAGS`` is pinned)
+POLICY_FLAGS = {1: TOPK_FLAGS[1],
+                2: "excl_off decreases or leaves its range (that user's population is empty)",
+                4: "a NaN scaled score of an eligible, not excluded row (that row is left out of that user's sums)",
+                128: "an invalid list: a hole before a row, a row outside [0, V), a row twice or a row outside the user's population "
+                     "(that user's log-probabilities are NaN)",
+                256: "an infinite scaled score of an eligible, not excluded row (that row is left out of that user's sums)"}
+
+
+def _policy_args(inv_temp, lists, name: str, user_vec):
+    """The arguments of the policy entries, refused before anything looks at a device: a finite ``inv_temp >= 0`` (``ValueError``)
+    and, when given, an int64 tensor ``lists`` (``TypeError``) of shape (B, k <= TOPK_MAX_K) (``ValueError``) -> inv_temp."""
+    if not isinstance(user_vec, torch.Tensor) or user_vec.dtype != torch.float32:
+        raise TypeError(f"newsreclib_amd: `user_vec` must be a float32 tensor, got "
+                        f"{user_vec.dtype if isinstance(user_vec, torch.Tensor) else type(user_vec).__name__}")
+    if lists is not None:
+        if not isinstance(lists, torch.Tensor) or lists.dtype != torch.int64:
+            raise TypeError(f"newsreclib_amd: `{name}` must be an int64 tensor, got "
+                            f"{lists.dtype if isinstance(lists, torch.Tensor) else type(lists).__name__}")
+        B = int(user_vec.shape[0]) if user_vec.dim() else -1
+        if lists.dim() != 2 or lists.shape[0] != B:
+            raise ValueError(f"newsreclib_amd: `{name}` must be (B, k) with one list per user ({B}), got {tuple(lists.shape)}")
+        if lists.shape[1] > TOPK_MAX_K:
+            raise ValueError(f"newsreclib_amd: `{name}` holds at most {TOPK_MAX_K} rows per user, got {int(lists.shape[1])}")
+    inv_temp = float(inv_temp)
+    if not math.isfinite(inv_temp) or inv_temp < 0 or inv_temp > 3.4028234663852886e38:
+        raise ValueError(f"newsreclib_amd: `inv_temp` must be finite (in fp32) and >= 0, got {inv_temp!r}")
+    return inv_temp
+
+
+def catalogue_logz(user_vec: torch.Tensor, table: torch.Tensor, inv_temp: float = 1.0, excl_idx: Optional[torch.Tensor] = None,
+                   excl_off: Optional[torch.Tensor] = None, eligible: Optional[torch.Tensor] = None,
+                   drop_idx: Optional[torch.Tensor] = None):
+    """``nrl_catalogue_logz``: the log-partition of the policy ``topk_sampled_scores`` draws from, ``softmax(t)`` with
+    ``t = fl(score * inv_temp)`` over each user's population (eligible, not excluded, ``t`` finite) minus the rows of
+    ``drop_idx`` ((B, kd) int64, ``-1`` an empty slot) -> (max (B) fp32, logsum (B) fp32: ``log sum exp(t - max)``, entropy (B)
+    fp32 in nats, pop (B) int32, dropped (B) int32: the rows of ``drop_idx`` found in the population, status (1) int32).
+    ``log Z = max + logsum``; ``log p(row) = (t - max) - logsum``.  The (B, V) score matrix is never materialised, and a user's
+    outputs do not depend on B, its place in the batch or the form of the mask, bit for bit.  An empty population gives
+    ``-inf, -inf, 0, 0``.  ``status`` (``POLICY_FLAGS``) stays on the device -- nothing here synchronises with the host."""
+    inv_temp = _policy_args(inv_temp, drop_idx, "drop_idx", user_vec)
+    s = _dot_scorer(user_vec, table)
+    lib = _lib.load()
+    excl_idx, excl_off, eligible = _topk_masks(excl_idx, excl_off, eligible, s.B, s.V)
+    kd = 0
+    if drop_idx is not None:
+        drop_idx, kd = _chk(drop_idx, torch.int64, "drop_idx"), int(drop_idx.shape[1])
+    mx, ls, ent = (torch.empty(s.B, dtype=torch.float32, device=s.dev) for _ in range(3))
+    pop = torch.empty(s.B, dtype=torch.int32, device=s.dev)
+    dropped = torch.zeros(s.B, dtype=torch.int32, device=s.dev)
+    status = torch.zeros(1, dtype=torch.int32, device=s.dev)
+    ws = workspace(lib.nrl_catalogue_logz_workspace_size(s.B, s.V, s.D), s.dev)
+    _lib.check(lib.nrl_catalogue_logz(*s.lead, inv_temp, _ptr(excl_idx), _ptr(excl_off), _ptr(eligible), _ptr(drop_idx) if kd else None,
+                                      kd, mx.data_ptr(), ls.data_ptr(), ent.data_ptr(), pop.data_ptr(), dropped.data_ptr(),
+                                      status.data_ptr(), ws.data_ptr(), ws.numel(), _stream()), "nrl_catalogue_logz")
+    return mx, ls, ent, pop, dropped, status
+
+
+def list_logprob(user_vec: torch.Tensor, table: torch.Tensor, list_idx: torch.Tensor, inv_temp: float = 1.0,
+                 excl_idx: Optional[torch.Tensor] = None, excl_off: Optional[torch.Tensor] = None,
+                 eligible: Optional[torch.Tensor] = None):
+    """The Plackett-Luce log-probability of given lists under the policy ``topk_sampled_scores`` draws from: ``list_idx`` (B, k)
+    int64, ``-1`` in trailing empty slots -> (logp (B, k) fp32: slot j's log-probability given the slots before it, total (B)
+    fp32: the list's, score (B, k) fp32: the raw scores with the bits ``topk_scores`` reports, status (1) int32).
+    ``catalogue_logz`` with ``drop_idx = list_idx`` gives the tail -- the population without the listed rows -- and
+    ``nrl_list_logprob`` adds the listed rows back from the last slot, in float64: positive terms only, so a slot keeps its
+    precision when the slots before it hold almost all the mass.  An empty slot has logp ``+0`` and score ``-inf``.  A list with a
+    hole, a row outside the table, a row twice or a row outside the user's population (excluded, ineligible, non-finite) makes
+    that user's ``logp`` and ``total`` NaN and sets bit 128 of ``status`` (``POLICY_FLAGS``).  Nothing here synchronises with the
+    host."""
+    if list_idx is None:
+        raise TypeError("newsreclib_amd: `list_idx` must be an int64 tensor, got NoneType")
+    inv_temp = _policy_args(inv_temp, list_idx, "list_idx", user_vec)
+    if list_idx.shape[1] < 1:
+        raise ValueError("newsreclib_amd: `list_idx` must hold at least one slot per user")
+    mx, ls, _, pop, dropped, status = catalogue_logz(user_vec, table, inv_temp, excl_idx, excl_off, eligible, list_idx)
+    s = _dot_scorer(user_vec, table)
+    list_idx = _chk(list_idx, torch.int64, "list_idx")
+    k = int(list_idx.shape[1])
+    score, logp = (torch.empty((s.B, k), dtype=torch.float32, device=s.dev) for _ in range(2))
+    total = torch.empty(s.B, dtype=torch.float32, device=s.dev)
+    _lib.check(_lib.load().nrl_list_logprob(*s.lead, inv_temp, list_idx.data_ptr(), k, mx.data_ptr(), ls.data_ptr(), pop.data_ptr(),
+                                            dropped.data_ptr(), score.data_ptr(), logp.data_ptr(), total.data_ptr(),
+                                            status.data_ptr(), _stream()), "nrl_list_logprob")
+    return logp, total, score, status
+
+
 TOPK_MAX_BIAS_CLASSES = 64
 # the status words of the class-biased entries: the flags of ``topk_scores`` / ``catalogue_ranks`` and one more (bit 64).  They are
 # dictionaries of their own, as ``ENSEMBLE_RANK_FLAGS`` is: the key sets of ``TOPK_FLAGS`` and ``RANK_FLAGS`` are pinned.
