@@ -1545,6 +1545,45 @@ int nrl_topk_sampled_scores(const float* user_vec, const float* table, int64_t B
 int nrl_gumbel_noise(const int64_t* user_key /* n */, const int64_t* row /* n */, int64_t n, uint64_t seed, float* out_u /* n */,
                      float* out_g /* n */, void* stream);
 
+/* nrl_topk_sampled_draws: R Gumbel top-k draws per user from ONE walk over the table.
+ *   The contract (normative).  Draw r (0 <= r < R) of every user is what nrl_topk_sampled_scores returns for that user under seed
+ *     (seed + r) mod 2^64 with every other argument equal: out_idx[b, r, :], out_key[b, r, :] and out_score[b, r, :] match that
+ *     call's out_idx[b, :], out_key[b, :] and out_score[b, :] bit for bit, and `status` is the OR of those R calls' words.
+ *     Everything nrl_topk_sampled_scores promises therefore holds per draw: the noise statement above (k0 from seed + r), the tie
+ *     rule (equal z by ascending row), NaN handling (a NaN z is left out and sets NRL_TOPK_E_NAN), the -1 / -inf / -inf fill, raw
+ *     scores with the bits nrl_topk_scores reports, and independence from B, the user's place in the batch, slices, the grid and
+ *     the GEMM engine setting.  The dot products are computed once per table tile and perturbed R times; the entry may run the
+ *     draws in several walks of fewer draws each, which changes no output bit.
+ *   out_idx (B, R, k) int64; out_key (B, R, k) fp32; out_score (B, R, k) fp32.
+ *   Limits: R in [1, NRL_TOPK_MAX_DRAWS], R * k <= NRL_TOPK_MAX_K, B * R * k < 2^31.
+ *   Workspace: nrl_topk_sampled_draws_workspace_size(B, V, D, k, R, slices) == nrl_topk_scores_workspace_bytes(B, V, D, R * k,
+ *     slices): R lists of k entries are one list of R k (`_size`: the set of *_workspace_bytes names is pinned).  A shorter buffer
+ *     is refused with NRL_E_WORKSPACE before any launch.
+ *   Checks (NRL_E_INVALID before any launch): those of nrl_topk_sampled_scores in its order up to B * k >= 2^31, then the limits
+ *     above, then with B > 0 a null output or user_key.  B == 0 succeeds without a launch; V == 0 gives -1 / -inf / -inf.
+ *   No floating-point atomics, no allocation, no host synchronisation. */
+#define NRL_TOPK_MAX_DRAWS 32
+size_t nrl_topk_sampled_draws_workspace_size(int64_t B, int64_t V, int32_t D, int32_t k, int32_t R, int32_t slices);
+int nrl_topk_sampled_draws(const float* user_vec, const float* table, int64_t B, int64_t V, int32_t D, int32_t k, int32_t R,
+                           const int64_t* excl_idx, const int64_t* excl_off, const uint8_t* eligible,
+                           const int64_t* user_key /* B */, uint64_t seed, float inv_temp, int32_t slices,
+                           int64_t* out_idx /* B, R, k */, float* out_key /* B, R, k */, float* out_score /* B, R, k */,
+                           int32_t* status, void* ws, size_t ws_bytes, void* stream);
+
+/* nrl_list_class_exposure: how much position-weighted exposure L lists per user give each of S classes of table rows.
+ *   list_idx (B, L, k) int64, -1 an empty slot (the L draws of nrl_topk_sampled_draws, or any lists); row_class (V) int32;
+ *   pos_weight (k) fp32; out (B, S) fp32:
+ *     out[b, s] = fl32((sum over l ascending, then j ascending, of (double)pos_weight[j] where row_class[list_idx[b, l, j]] == s) / L)
+ *   accumulated in float64 in exactly that order, divided by L in float64 and rounded once: a pure function of the user's lists.
+ *   A row outside [0, V) other than -1 counts for no class and ORs NRL_MMR_E_ROW (1) into status; a class outside [0, S) counts
+ *     for no class and ORs NRL_TOPK_E_CLASS (64).
+ *   Checks (NRL_E_INVALID before any launch): S outside [1, NRL_TOPK_MAX_BIAS_CLASSES], k outside [1, NRL_TOPK_MAX_K], L < 1,
+ *     B >= 2^31, a null status, and with B > 0 a null argument.  B == 0 succeeds without a launch.  No workspace, no atomics on
+ *     floats, no host synchronisation. */
+int nrl_list_class_exposure(const int64_t* list_idx /* B, L, k */, const int32_t* row_class /* V */, const float* pos_weight /* k */,
+                            int64_t B, int32_t L, int32_t k, int64_t V, int32_t S, float* out /* B, S */, int32_t* status,
+                            void* stream);
+
 /* nrl_catalogue_logz / nrl_list_logprob: how probable a list drawn by nrl_topk_sampled_scores was.  The policy is Plackett-Luce over
  *   softmax(t), t = fmul_rn(s, inv_temp): s the bits nrl_topk_scores computes for the pair, t the first rounding of the sampled
  *   entry's key (-0 counts as +0).  Neither the (B, V) scores nor their exponentials are written.

@@ -357,6 +357,12 @@ SIGNATURES = {
                                           c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,
                                           c_void_p]),
     "nrl_gumbel_noise": (c_int32, [c_void_p, c_void_p, c_int64, c_uint64, c_void_p, c_void_p, c_void_p]),
+    "nrl_topk_sampled_draws_workspace_size": (c_size_t, [c_int64, c_int64, c_int32, c_int32, c_int32, c_int32]),
+    "nrl_topk_sampled_draws": (c_int32, [c_void_p, c_void_p, c_int64, c_int64, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p,
+                                         c_void_p, c_uint64, c_float, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                         c_size_t, c_void_p]),
+    "nrl_list_class_exposure": (c_int32, [c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_int32, c_int64, c_int32, c_void_p, c_void_p,
+                                          c_void_p]),
     "nrl_catalogue_logz_workspace_size": (c_size_t, [c_int64, c_int64, c_int32]),
     "nrl_catalogue_logz": (c_int32, [c_void_p, c_void_p, c_int64, c_int64, c_int32, c_float, c_void_p, c_void_p, c_void_p, c_void_p,
                                      c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,

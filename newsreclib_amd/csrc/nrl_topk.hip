@@ -2178,6 +2178,196 @@ __global__ __launch_bounds__(256) void tks_noise_kernel(const int64_t* user_key,
   if (out_g) out_g[i] = tks_gumbel(u);
 }
 
+// ---- several Gumbel top-k draws per walk: nrl_topk_sampled_draws --------------------------------------------------------------------
+// R draws of nrl_topk_sampled_scores, draw r under seed + r (mod 2^64), from ONE pass over the table: the dot products of draw r and
+// draw r + 1 are the same bits and only the noise differs, so the MFMA chain, the table reads and the operand staging are paid once
+// per tile and a draw costs its noise, a store of the tile and its selection.  tkd_walk is a walk of its own beside tk_walk (whose
+// text, like TkDot's, TkSelect's and TksProducer's, is untouched):
+//   * per table tile tk_tile_accumulate<1> runs once and the accumulator fragments stay in registers; for r = 0 ... R - 1 a COPY of
+//     them is perturbed with draw r's noise (tks_perturb / tks_gumbel / tks_uniform as they stand, the same operands in the same
+//     order as TksProducer::tile), stored to the one score tile, and each wave selects its users' rows into list (user, r) with
+//     tk_select_user.  Two barriers per draw: the tile published, the tile free;
+//   * the exclusion cache, the eligibility bytes and the slice plan belong to the user and the tile, not to the draw: filled once;
+//   * the hashed user keys of all draws, kud[R][64], are staged in the prologue; the per-draw call keys k0[r] = tks_call_key(seed + r)
+//     come from the host in the kernel arguments;
+//   * LDS: TkSelect carves its members for lists of R k entries (list (ul, r) at lists + (ul R + r) k), so the layout is
+//     tk_lds_bytes(1, TK_BU, R k) + R * 256; the partial lists are (B, slices, R, k);
+//   * tkd_merge_kernel, one wave per (user, draw): the flags and the merge of tk_merge_kernel over that draw's partial lists (the
+//     flags are raised once per draw of a user instead of once: an OR either way);
+//   * the raw scores are tks_raw_kernel over the (B, R k) lists: its k only divides a slot number by the slots per user.
+// A NaN key is seen per draw exactly where the single entry sees it, so the status word is the OR of the R single calls' words.
+constexpr size_t tkd_lds_bytes(int R, int k) { return tk_lds_bytes(1, TK_BU, R * k) + (size_t)R * TK_BU * 4; }
+static_assert(NRL_TOPK_MAX_DRAWS * TK_BU * 4 % 16 == 0 && (TK_BU * 4) % 16 == 0, "what follows the hashed keys is 16-byte aligned");
+static_assert(tkd_lds_bytes(NRL_TOPK_MAX_DRAWS, NRL_TOPK_MAX_K / NRL_TOPK_MAX_DRAWS) == 124800 &&
+                  tkd_lds_bytes(NRL_TOPK_MAX_DRAWS, NRL_TOPK_MAX_K / NRL_TOPK_MAX_DRAWS) <= 160 * 1024,
+              "the largest layout of the draws kernel (32 draws of 4) fits");
+static_assert(tkd_lds_bytes(1, NRL_TOPK_MAX_K) <= tkd_lds_bytes(NRL_TOPK_MAX_DRAWS, NRL_TOPK_MAX_K / NRL_TOPK_MAX_DRAWS),
+              "no R with R k <= NRL_TOPK_MAX_K needs more than 32 draws of 4");
+// two workgroups per CU: 512 R k + 256 R <= 30,848 -- R k <= 59 for one draw, 58 for two, 50 for five draws of 10
+static_assert(2 * tkd_lds_bytes(1, 59) <= 160 * 1024 && 2 * tkd_lds_bytes(1, 60) > 160 * 1024, "one draw: two workgroups per CU up to k = 59");
+static_assert(2 * tkd_lds_bytes(2, 29) <= 160 * 1024 && 2 * tkd_lds_bytes(2, 30) > 160 * 1024, "two draws: up to k = 29");
+static_assert(2 * tkd_lds_bytes(5, 10) <= 160 * 1024 && 2 * tkd_lds_bytes(6, 10) > 160 * 1024, "k = 10: up to five draws");
+static_assert(2 * tkd_lds_bytes(13, 4) <= 160 * 1024 && 2 * tkd_lds_bytes(14, 4) > 160 * 1024, "k = 4: up to thirteen draws");
+
+struct TkdFields {
+  const int64_t* user_key;                     // (B)
+  float inv_temp;
+  int32_t R, R_all, r0;                        // this launch serves draws r0 ... r0 + R - 1 of the call's R_all
+  uint32_t k0[NRL_TOPK_MAX_DRAWS];             // tks_call_key(seed + r0 + r)
+};
+
+__device__ __forceinline__ void tkd_walk(const TkWith<TkArgs, TkdFields>& A, unsigned char* smem) {
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int R = A.R, k = A.k, rk = R * k;
+  float* const sc = reinterpret_cast<float*>(smem);                          // [TK_BU][TK_SCLD]; until the keys exist, the operand tiles
+  uint32_t* const kud = reinterpret_cast<uint32_t*>(smem + TK_TILE_BYTES);   // [R][TK_BU] the users' hashed keys per draw
+  TkSelect C(smem + TK_TILE_BYTES + (size_t)R * TK_BU * 4, TK_BU, rk);
+  const int sl = (int)(blockIdx.x % (unsigned)A.slices);
+  const int64_t u0 = (int64_t)(blockIdx.x / (unsigned)A.slices) * TK_BU;
+  const int nu = A.B - u0 < TK_BU ? (int)(A.B - u0) : TK_BU;
+  int v_begin, nvt;
+  tk_slice(A, sl, v_begin, nvt);
+
+  const int srow = tid >> 2;
+  const bool ua_ok = srow < nu;
+  const float* const pa[1] = {A.user + (ua_ok ? u0 + srow : A.B - 1) * A.D};
+  if (tid < TK_BU) {
+    const uint64_t key = tid < nu ? (uint64_t)A.user_key[u0 + tid] : 0ull;
+    for (int r = 0; r < R; ++r) kud[r * TK_BU + tid] = tid < nu ? tks_user_key(A.k0[r], key) : 0u;
+  }
+  C.prologue(A, u0, nu, TK_BU);                       // (its barrier also publishes the keys)
+  const int ul_begin = TkBlocked::first(wave), ul_end = TkBlocked::end(wave, nu);
+  const int wm = wave >> 1, wn = wave & 1, l15 = lane & 15, g = lane >> 4;
+  bool nan = false;
+
+  for (int vt = 0; vt < nvt; ++vt) {
+    const int v0 = v_begin + vt * TK_BV;
+    tk_fill_eligible(A.eligible, v0, A.V, C.el);
+    tk_f32x4 acc[1][2][4];
+    tk_tile_accumulate<1>(pa, ua_ok, A.table, A.D, v0, A.V, A.D, sc, acc);   // (its barriers publish `el`)
+    const bool e_0 = C.el[lane] != 0, e_1 = C.el[64 + lane] != 0;
+    for (int r = 0; r < R; ++r) {
+      const uint32_t* const kul = kud + r * TK_BU;
+      uint32_t ku[2][4];
+#pragma unroll
+      for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int q = 0; q < 4; ++q) ku[i][q] = kul[wm * 32 + i * 16 + 4 * g + q];
+      tk_f32x4 z[2][4];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const uint32_t row = (uint32_t)v0 + wn * 64 + j * 16 + l15;
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+          for (int q = 0; q < 4; ++q) z[i][j][q] = tks_perturb(acc[0][i][j][q], A.inv_temp, tks_gumbel(tks_uniform(ku[i][q], row)));
+      }
+      tk_store_fragments(z, sc);
+      __syncthreads();
+      for (int ul = ul_begin; ul < ul_end; ++ul)
+        tk_select_user(sc + ul * TK_SCLD, C.lists + (ul * R + r) * k, C.xn + ul, C.xs + ul, C.xl + ul * TK_XCAP, A.excl_idx, v0, e_0, e_1,
+                       k, lane, nan);
+      __syncthreads();                                // the score tile is free for the next draw, or the next tile's operands
+    }
+  }
+
+  if (nan && lane == 0) atomicOr(A.status, NRL_TOPK_E_NAN);
+  wave_lds_sync();
+  for (int ul = ul_begin; ul < ul_end; ++ul)
+    tk_flush_user(C.lists + ul * rk, A.partial + ((u0 + ul) * A.slices + sl) * rk, rk, lane);
+}
+
+__global__ __launch_bounds__(TK_THREADS) void tkd_scores_kernel(TkWith<TkArgs, TkdFields> A) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char tk_smem[];
+  tkd_walk(A, tk_smem);
+}
+
+// one wave per (user, draw): tk_merge_kernel's flags and merge over draw r's partial lists, written to list (u, r0 + r) of (B, R_all, k)
+__global__ __launch_bounds__(64) void tkd_merge_kernel(TkWith<TkArgs, TkdFields> A) {
+  const int64_t u = blockIdx.x / (unsigned)A.R;
+  const int r = (int)(blockIdx.x % (unsigned)A.R);
+  const int lane = threadIdx.x, k = A.k;
+  int64_t s, n;
+  const bool ok = tk_excl_range(A, u, s, n);
+  TkList S;
+  S.e0 = S.e1 = 0ull;
+  if (!ok) {
+    if (lane == 0) atomicOr(A.status, NRL_TOPK_E_OFFSETS);
+  } else {
+    int bad = 0;
+    for (int64_t i = lane; i < n; i += 64) {
+      const int64_t x = A.excl_idx[s + i];
+      bad |= (x < 0 || x >= A.V);
+    }
+    if (__ballot(bad) && lane == 0) atomicOr(A.status, NRL_TOPK_E_EXCLUDE);
+    bool nan = false;
+    for (int sl = 0; sl < A.slices; ++sl) {
+      const unsigned long long* P = A.partial + ((u * A.slices + sl) * A.R + r) * k;
+      for (int base = 0; base < k; base += 64) {
+        const unsigned long long c = base + lane < k ? P[base + lane] : 0ull;
+        const unsigned long long m = __ballot(c > S.kth(k));
+        if (m) S.take(c, m, k, lane, nan);
+      }
+    }
+  }
+  const int64_t o = (u * A.R_all + A.r0 + r) * k;
+  for (int p = lane; p < k; p += 64) {
+    const unsigned long long e = p < 64 ? S.e0 : S.e1;
+    A.out_idx[o + p] = e ? (int64_t)(uint32_t)~(uint32_t)e : -1;
+    A.out_score[o + p] = e ? tk_unkey((uint32_t)(e >> 32)) : -INFINITY;
+  }
+}
+
+// ---- class exposure of lists: nrl_list_class_exposure ----------------------------------------------------------------------------------
+// out[b, s] = fl32((sum over the slots (l, j) of user b in ascending order of (double)pos_weight[j] where the slot's row has class s)
+// / L).  One wave per user; lane s owns class s and adds in float64 in slot order, so no atomics and one order.  64 slots at a time:
+// lane i reads slot base + i's row and its class once, and the slots that count are broadcast one by one.
+struct TkxArgs {
+  const int64_t* list_idx;                     // (B, L, k)
+  const int32_t* row_class;                    // (V)
+  const float* pos_weight;                     // (k)
+  int64_t V;
+  int32_t L, k, S;
+  float* out;                                  // (B, S)
+  int32_t* status;
+};
+__global__ __launch_bounds__(64) void tkx_exposure_kernel(TkxArgs A) {
+  const int64_t u = blockIdx.x;
+  const int lane = threadIdx.x;
+  const int64_t n = (int64_t)A.L * A.k;
+  const int64_t* const list = A.list_idx + u * n;
+  double sum = 0.0;
+  int flags = 0;
+  for (int64_t base = 0; base < n; base += 64) {
+    const int64_t i = base + lane;
+    int cls = -1;
+    if (i < n) {
+      const int64_t row = list[i];
+      if (row >= 0 && row < A.V) {
+        const int32_t c = A.row_class[row];
+        if (c >= 0 && c < A.S)
+          cls = c;
+        else
+          flags |= NRL_TOPK_E_CLASS;
+      } else if (row != -1) {
+        flags |= NRL_MMR_E_ROW;
+      }
+    }
+    unsigned long long m = __ballot(cls >= 0);
+    while (m) {
+      const int b = __ffsll((long long)m) - 1;
+      m &= m - 1;
+      const int c = __shfl(cls, b, 64);
+      const double w = (double)A.pos_weight[(int)((base + b) % A.k)];
+      if (c == lane) sum += w;
+    }
+  }
+  if (lane < A.S) A.out[u * A.S + lane] = (float)(sum / (double)A.L);
+  const unsigned long long f1 = __ballot(flags & NRL_MMR_E_ROW), f2 = __ballot(flags & NRL_TOPK_E_CLASS);
+  if (lane == 0 && (f1 | f2)) atomicOr(A.status, (f1 ? NRL_MMR_E_ROW : 0) | (f2 ? NRL_TOPK_E_CLASS : 0));
+}
+
 // ---- the log-partition of the sampled policy: nrl_catalogue_logz, nrl_list_logprob -----------------------------------------------------
 // What the Plackett-Luce policy of nrl_topk_sampled_scores needs to say how probable a drawn list was: per user, over the rows of the
 // user's population whose scaled score t = fmul_rn(s, inv_temp) (the first rounding of tks_perturb) is finite, minus the rows of an
@@ -3408,6 +3598,91 @@ int nrl_gumbel_noise(const int64_t* user_key, const int64_t* row, int64_t n, uin
   if (n == 0) return NRL_OK;
   NRL_REQUIRE(user_key && row && (out_u || out_g), "gumbel_noise: null argument");
   tks_noise_kernel<<<(unsigned)ceil_div(n, 256), 256, 0, (hipStream_t)stream>>>(user_key, row, n, tks_call_key(seed), out_u, out_g);
+  NRL_LAUNCH_CHECK();
+  return NRL_OK;
+}
+
+// nrl_topk_sampled_draws: the checks of nrl_topk_sampled_scores, then its own; the R draws in groups of tkd_group draws per walk
+// (tkd_scores_kernel, tkd_merge_kernel; no output bit depends on the grouping), then tks_raw_kernel over all B R k slots
+size_t nrl_topk_sampled_draws_workspace_size(int64_t B, int64_t V, int32_t D, int32_t k, int32_t R, int32_t slices) {
+  if (R < 1 || R > NRL_TOPK_MAX_DRAWS || k < 1 || k > NRL_TOPK_MAX_K) return 256;
+  return nrl_topk_scores_workspace_bytes(B, V, D, R * k, slices);            // (R lists of k entries are one list of R k)
+}
+
+// draws per walk: the most that leave two workgroups resident per CU, at least one.  Measured (B = 512, V = 65,536,
+// k = 10): 8 draws in walks of 4 or 5 take 0.68 - 0.73x the time of 8 single calls, in walks of 6 or 8 (one workgroup per CU)
+// 0.94 - 1.04x -- a second resident workgroup is worth more than the walks it costs.
+static int32_t tkd_group(int32_t k, int32_t R) {
+  int32_t G = 1;
+  while (G < R && 2 * tkd_lds_bytes(G + 1, k) <= 160 * 1024) ++G;
+  return G;
+}
+
+int nrl_topk_sampled_draws(const float* user_vec, const float* table, int64_t B, int64_t V, int32_t D, int32_t k, int32_t R,
+                           const int64_t* excl_idx, const int64_t* excl_off, const uint8_t* eligible, const int64_t* user_key,
+                           uint64_t seed, float inv_temp, int32_t slices, int64_t* out_idx, float* out_key, float* out_score,
+                           int32_t* status, void* ws, size_t ws_bytes, void* stream) {
+  const char* who = "topk_sampled_draws";
+  NRL_REQUIRE(B >= 0 && V >= 0 && D >= 0 && slices >= 0, "%s: negative size", who);
+  NRL_TRY(tk_check(who, B, V, D, k, excl_idx, excl_off));
+  NRL_REQUIRE(status, "%s: the status word is required", who);
+  NRL_REQUIRE(inv_temp >= 0.f && inv_temp < INFINITY, "%s: inv_temp finite and >= 0 (got %g)", who, (double)inv_temp);
+  NRL_REQUIRE(B * (int64_t)k < ((int64_t)1 << 31), "%s: at most 2^31 - 1 list slots per call (got %lld)", who, (long long)(B * k));
+  NRL_REQUIRE(R >= 1 && R <= NRL_TOPK_MAX_DRAWS, "%s: R in [1, %d] (got %d)", who, NRL_TOPK_MAX_DRAWS, R);
+  NRL_REQUIRE(R * k <= NRL_TOPK_MAX_K, "%s: R * k at most %d (got %d)", who, NRL_TOPK_MAX_K, R * k);
+  NRL_REQUIRE(B * (int64_t)R * k < ((int64_t)1 << 31), "%s: at most 2^31 - 1 list slots per call (got %lld)", who,
+              (long long)(B * R * k));
+  if (B == 0) return NRL_OK;
+  NRL_REQUIRE(out_idx && out_key && out_score && user_vec && (V == 0 || table), "%s: null argument", who);
+  NRL_REQUIRE(user_key, "%s: user_key is required", who);
+  unsigned long long* partial;
+  NRL_TRY(carve_workspace(ws, ws_bytes, [&](Arena& a) { tk_layout(a, B, V, R * k, slices, TK_BU, &partial); }));
+  int64_t lists, used, tps;
+  tk_plan(B, V, slices, TK_BU, lists, used, tps);
+  const int64_t blocks = ceil_div(B, TK_BU) * used;
+  NRL_REQUIRE(blocks < ((int64_t)1 << 31), "%s: grid too large (%lld workgroups)", who, (long long)blocks);
+  hipStream_t st = (hipStream_t)stream;
+  const int32_t G = tkd_group(k, R);
+  for (int32_t r0 = 0; r0 < R; r0 += G) {
+    TkWith<TkArgs, TkdFields> A;
+    static_cast<TkArgs&>(A) = tk_args(user_vec, table, B, V, D, k, excl_idx, excl_off, eligible, partial, out_idx, out_key, status);
+    A.slices = (int32_t)used;
+    A.tiles_per_slice = (int32_t)tps;
+    A.user_key = user_key;
+    A.inv_temp = inv_temp;
+    A.R = R - r0 < G ? R - r0 : G;
+    A.R_all = R;
+    A.r0 = r0;
+    for (int32_t r = 0; r < NRL_TOPK_MAX_DRAWS; ++r) A.k0[r] = r < A.R ? tks_call_key(seed + (uint64_t)(r0 + r)) : 0u;
+    if (used > 0) {
+      const size_t smem = tkd_lds_bytes(A.R, k);
+      // more than 64 KB of dynamic LDS needs the attribute; it belongs to the current device, so it is set per call
+      if (smem > 64 * 1024)
+        NRL_HIP(hipFuncSetAttribute((const void*)tkd_scores_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+      tkd_scores_kernel<<<(unsigned)blocks, TK_THREADS, smem, st>>>(A);
+      NRL_LAUNCH_CHECK();
+    }
+    tkd_merge_kernel<<<(unsigned)(B * A.R), 64, 0, st>>>(A);
+    NRL_LAUNCH_CHECK();
+  }
+  const int64_t n = B * (int64_t)R * k;
+  tks_raw_kernel<<<(unsigned)ceil_div(n, TK_BU), TK_THREADS, 0, st>>>(TksRawArgs{user_vec, table, out_idx, out_score, V, (int32_t)n, D, R * k});
+  NRL_LAUNCH_CHECK();
+  return NRL_OK;
+}
+
+int nrl_list_class_exposure(const int64_t* list_idx, const int32_t* row_class, const float* pos_weight, int64_t B, int32_t L, int32_t k,
+                            int64_t V, int32_t S, float* out, int32_t* status, void* stream) {
+  const char* who = "list_class_exposure";
+  NRL_REQUIRE(B >= 0 && V >= 0, "%s: negative size", who);
+  NRL_REQUIRE(S >= 1 && S <= NRL_TOPK_MAX_BIAS_CLASSES, "%s: S in [1, %d] (got %d)", who, NRL_TOPK_MAX_BIAS_CLASSES, S);
+  NRL_REQUIRE(k >= 1 && k <= NRL_TOPK_MAX_K, "%s: k in [1, %d] (got %d)", who, NRL_TOPK_MAX_K, k);
+  NRL_REQUIRE(L >= 1, "%s: L >= 1 (got %d)", who, L);
+  NRL_REQUIRE(B < ((int64_t)1 << 31), "%s: at most 2^31 - 1 users per call (got %lld)", who, (long long)B);
+  NRL_REQUIRE(status, "%s: the status word is required", who);
+  if (B == 0) return NRL_OK;
+  NRL_REQUIRE(list_idx && pos_weight && out && (V == 0 || row_class), "%s: null argument", who);
+  tkx_exposure_kernel<<<(unsigned)B, 64, 0, (hipStream_t)stream>>>(TkxArgs{list_idx, row_class, pos_weight, V, L, k, S, out, status});
   NRL_LAUNCH_CHECK();
   return NRL_OK;
 }

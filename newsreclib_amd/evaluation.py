@@ -584,6 +584,37 @@ class NewsVectorCache(_ImpressionCache):
         return ops.topk_scores(user, self.vectors, k, *tail)
 
     @torch.no_grad()
+    def recommend_draws(self, hist_idx: torch.Tensor, hist_sizes: torch.Tensor, k: int, draws: int, policy,
+                        user_idx: Optional[torch.Tensor] = None, exclude_history: bool = True,
+                        eligible: Optional[torch.Tensor] = None):
+        """``draws`` lists per user from the policy of ``recommend(sample=...)`` -> (news_idx (B, draws, k) int64, raw scores
+        (B, draws, k) fp32, status).  ``policy`` = (inv_temp, seed, user_key) is ``recommend``'s ``sample`` triple (the argument has
+        a name of its own because ``recommend`` alone takes a ``sample``: here it is the first of ``draws`` seeds), and draw ``r``
+        is, bit for bit, ``recommend(..., sample=(inv_temp, (seed + r) mod 2^64, user_key))``.  The user encoder runs once;
+        ``ops.topk_sampled_draws`` (tkd_scores_kernel) computes every dot product once per group of at most
+        ``min(ops.TOPK_MAX_DRAWS, ops.TOPK_MAX_K // k)`` draws, group ``g`` starting at seed ``seed + r0``; the groups' status words
+        are ORed on the device and nothing is read back.  The caller's side and the refusals are ``recommend``'s."""
+        draws = int(draws)
+        if draws < 1:
+            raise ValueError(f"recommend_draws: draws >= 1, got {draws}")
+        inv_temp, seed, user_key = _sample_triple(policy, int(hist_sizes.numel()))
+        k = int(k)
+        group = max(1, min(ops.TOPK_MAX_DRAWS, ops.TOPK_MAX_K // max(k, 1)))
+        user, _, tail = self._dot_users("recommend", hist_idx, hist_sizes, user_idx, exclude_history, eligible, None)
+        if not user_key.is_cuda:
+            user_key = user_key.pin_memory().to(user.device, non_blocking=True)
+        idx, score, status = [], [], None
+        for r0 in range(0, draws, group):
+            i, _, s, st = ops.topk_sampled_draws(user, self.vectors, k, min(group, draws - r0), user_key, (seed + r0) % 2 ** 64,
+                                                 inv_temp, *tail)
+            idx.append(i)
+            score.append(s)
+            status = st if status is None else status | st
+        if len(idx) == 1:
+            return idx[0], score[0], status
+        return torch.cat(idx, dim=1), torch.cat(score, dim=1), status
+
+    @torch.no_grad()
     def policy_stats(self, hist_idx: torch.Tensor, hist_sizes: torch.Tensor, inv_temp: float, user_idx: Optional[torch.Tensor] = None,
                      exclude_history: bool = True, eligible: Optional[torch.Tensor] = None, window=None) -> Dict[str, torch.Tensor]:
         """What the sampled policy of ``recommend(sample=(inv_temp, ...))`` looks like per user, over the population ``recommend``
@@ -1317,15 +1348,16 @@ def sample_recommendations(cache: NewsVectorCache, users: Sequence[Dict], k: int
     (n_users, draws, k) int64 on the host, ``-1`` beyond a user's population.  Draw ``j`` is the list
     ``recommend_users(..., sample=(temperature, (seed + j) mod 2^64))`` gives the user -- the same keys (``user_id``, or position
     + 1), the same refusals -- so it is reproducible user by user whatever the batching.  A batch's histories are uploaded once and
-    serve all its draws; one device-to-host copy per batch and draw; a status flag (``ops.TOPK_FLAGS``) is passed on as a warning.
-    The cost is ``draws`` full passes over the table: every draw recomputes the scores.  Reusing a score tile for several draws
-    inside the kernel is the obvious next step and is not done here.
+    serve all its draws; a status flag (``ops.TOPK_FLAGS``) is passed on as a warning.  With ``draws >= 2`` a batch goes through
+    ``cache.recommend_draws`` (where the cache has one): one pass of the user encoder, every dot product computed once per group of
+    draws (``ops.topk_sampled_draws``) and one device-to-host copy per batch.  A single draw, and a cache without
+    ``recommend_draws``, is one ``cache.recommend(sample=...)`` and one copy per draw; the lists are the same bits either way.
 
     ``log_probs=True`` returns ``(lists, logp)``: ``logp`` (n_users, draws, k) float32 on the host, slot by slot the log-probability
     ``cache.list_log_probs`` gives the drawn list under the same temperature (``+0`` in an empty slot; a list's propensity is the
-    sum over its slots).  The histories are still uploaded once per batch; every draw costs one more pass over the table (the
-    tail of its list) and its copy carries the log-probabilities as well.  The default returns exactly what it returned without
-    the argument."""
+    sum over its slots).  The histories are still uploaded once per batch; every draw costs one ``cache.list_log_probs`` call, one
+    more pass over the table (the tail of its list), and the batch's copy carries the log-probabilities as well.  The default
+    returns exactly what it returned without the argument."""
     who = "sample_recommendations"
     inv_temp, seed = _sample_policy(who, cache, (temperature, seed))
     draws = int(draws)
@@ -1341,6 +1373,22 @@ def sample_recommendations(cache: NewsVectorCache, users: Sequence[Dict], k: int
         hist = torch.cat([torch.as_tensor(u["hist"]).long() for u in chunk]).to(dev)
         uidx = torch.stack([torch.as_tensor(u["user_idx"]) for u in chunk]) if "user_idx" in chunk[0] else None
         keys = torch.tensor(_user_ids(chunk, lo), dtype=torch.int64).to(dev)
+        together = getattr(cache, "recommend_draws", None) if draws >= 2 else None
+        if together is not None:
+            idx, _, status = together(hist, hs, k, draws, (inv_temp, seed, keys), user_idx=uidx, eligible=eligible)
+            n, flat = idx.shape[0], [idx.reshape(idx.shape[0], -1).double()]
+            if log_probs:
+                for j in range(draws):
+                    lp, _, _, lp_status = cache.list_log_probs(hist, hs, idx[:, j].contiguous(), inv_temp, user_idx=uidx, eligible=eligible)
+                    flat.append(lp.double())
+                    status = status | lp_status
+            packed = torch.cat(flat + [status.double().expand(n, 1)], dim=1).cpu()                        # the one copy
+            cells = draws * idx.shape[2]
+            out[lo:lo + len(chunk)] = packed[:, :cells].long().reshape(n, draws, -1)
+            if log_probs:
+                logp[lo:lo + len(chunk)] = packed[:, cells:-1].float().reshape(n, draws, -1)
+            word |= int(packed[0, -1]) if packed.shape[0] else 0
+            continue
         for j in range(draws):
             idx, _, status = cache.recommend(hist, hs, k, user_idx=uidx, eligible=eligible,
                                              sample=(inv_temp, (seed + j) % 2 ** 64, keys))
@@ -1358,6 +1406,73 @@ def sample_recommendations(cache: NewsVectorCache, users: Sequence[Dict], k: int
         flags = ops.POLICY_FLAGS if log_probs else ops.TOPK_FLAGS
         warnings.warn(f"{who}: " + "; ".join(msg for bit, msg in flags.items() if word & bit))
     return (out, logp) if log_probs else out
+
+
+def exposure_weights(k: int, weights="rbp", patience: float = 0.8) -> torch.Tensor:
+    """The position weights of ``exposure_report`` -> (k) float32 on the host: ``"rbp"``: ``patience ** j`` (rank-biased precision's
+    browsing model), ``"dcg"``: ``1 / log2(j + 2)``, or a given tensor of ``k`` weights.  Computed in float64 and rounded once."""
+    k = int(k)
+    if isinstance(weights, torch.Tensor):
+        if weights.dim() != 1 or weights.numel() != k:
+            raise ValueError(f"exposure_report: `weights` must have one entry per slot ({k}), got {tuple(weights.shape)}")
+        return weights.detach().to("cpu", torch.float32)
+    j = torch.arange(max(k, 0), dtype=torch.float64)
+    if weights == "rbp":
+        patience = float(patience)
+        if not 0.0 < patience <= 1.0:
+            raise ValueError(f"exposure_report: the patience must be in (0, 1], got {patience!r}")
+        return (patience ** j).float()
+    if weights == "dcg":
+        return (1.0 / torch.log2(j + 2.0)).float()
+    raise ValueError(f"exposure_report: weights = \"rbp\", \"dcg\" or a tensor of k weights, got {weights!r}")
+
+
+def exposure_report(cache: NewsVectorCache, users: Sequence[Dict], k: int, draws: int, temperature: float, seed: int, aspect: str,
+                    weights="rbp", patience: float = 0.8, batch_size: int = 512, eligible: Optional[torch.Tensor] = None):
+    """How much position-weighted exposure the Plackett-Luce policy over ``softmax(score / temperature)`` gives each class of the
+    table's ``aspect`` column (``category``, ``sentiment``, ...; class ids in ``[0, ops.TOPK_MAX_BIAS_CLASSES)``), estimated from
+    ``draws`` lists of ``k`` per user -> {"per_user": (n_users, S) float32 -- user by user the mean over its draws of the summed
+    weights of the slots that show class ``s`` --, "mean": (S) its mean over the users, "share": mean / mean.sum()}, on the host;
+    ``S`` is 1 + the largest class id of the column (a class id outside the range is flagged and counts for no class).  The draws are ``sample_recommendations``' (the same seeds, keys and refusals:
+    ``cache.recommend_draws``) and never leave the device: ``ops.list_class_exposure`` reduces a batch's lists to its (B, S) rows,
+    which stay on the device until one copy at the end.  Position weights: ``exposure_weights(k, weights, patience)``.  A status
+    flag of the draws (``ops.TOPK_FLAGS``) or of the reduction (``ops.EXPOSURE_FLAGS``, 16 bits up) is passed on as one warning."""
+    who = "exposure_report"
+    inv_temp, seed = _sample_policy(who, cache, (temperature, seed))
+    draws = int(draws)
+    if draws < 1:
+        raise ValueError(f"{who}: draws >= 1, got {draws}")
+    w = exposure_weights(k, weights, patience)
+    classes = _aspect_classes(cache, aspect)
+    dev = cache.table.device
+    S = ops.TOPK_MAX_BIAS_CLASSES                           # (reduced over every class a lane can own; cut to the column's on the host)
+    w = w.to(dev)
+    rows, status = [], torch.zeros(1, dtype=torch.int32, device=dev)
+    for lo in range(0, len(users), batch_size):
+        chunk = users[lo:lo + batch_size]
+        hs = torch.tensor([len(u["hist"]) for u in chunk])
+        hist = torch.cat([torch.as_tensor(u["hist"]).long() for u in chunk]).to(dev)
+        uidx = torch.stack([torch.as_tensor(u["user_idx"]) for u in chunk]) if "user_idx" in chunk[0] else None
+        keys = torch.tensor(_user_ids(chunk, lo), dtype=torch.int64).to(dev)
+        idx, _, st = cache.recommend_draws(hist, hs, k, draws, (inv_temp, seed, keys), user_idx=uidx, eligible=eligible)
+        exposure, est = ops.list_class_exposure(idx, classes, w, S)
+        rows.append(exposure)
+        status = status | st | (est << 16)
+    top = classes.max().reshape(1) if classes.numel() else torch.zeros(1, dtype=torch.int32, device=dev)
+    if not rows:
+        S = min(max(int(top), 0) + 1, S)
+        empty = torch.zeros((0, S), dtype=torch.float32)
+        return {"per_user": empty, "mean": torch.full((S,), float("nan")), "share": torch.full((S,), float("nan"))}
+    packed = torch.cat([torch.cat(rows).double().reshape(-1), top.double(), status.double()]).cpu()       # the one copy
+    word, S = int(packed[-1]), min(max(int(packed[-2]), 0) + 1, S)
+    per_user = packed[:-2].float().reshape(-1, ops.TOPK_MAX_BIAS_CLASSES)[:, :S].contiguous()
+    if word:                                                # the kernels have dealt with each of these; the caller should know
+        import warnings
+        said = [msg for bit, msg in ops.TOPK_FLAGS.items() if word & bit] + \
+               [msg for bit, msg in ops.EXPOSURE_FLAGS.items() if (word >> 16) & bit]
+        warnings.warn(f"{who}: " + "; ".join(said))
+    mean = per_user.double().mean(dim=0)
+    return {"per_user": per_user, "mean": mean.float(), "share": (mean / mean.sum()).float()}
 
 
 def policy_report(cache: NewsVectorCache, users: Sequence[Dict], temperatures: Sequence[float], batch_size: int = 512,

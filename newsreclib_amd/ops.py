@@ -1088,6 +1088,97 @@ def topk_sampled_scores(user_vec: torch.Tensor, table: torch.Tensor, k: int, use
     return idx, key, score, status
 
 
+TOPK_MAX_DRAWS = 32
+
+
+def _draws_arg(k, draws) -> int:
+    """``draws`` of ``topk_sampled_draws`` against ``k``, refused before anything looks at a device -> draws."""
+    if isinstance(draws, bool) or not isinstance(draws, int):
+        raise TypeError(f"newsreclib_amd: `draws` must be an integer, got {type(draws).__name__}")
+    if not 1 <= draws <= TOPK_MAX_DRAWS:
+        raise ValueError(f"newsreclib_amd: `draws` must be in [1, {TOPK_MAX_DRAWS}], got {draws}")
+    if isinstance(k, bool) or not isinstance(k, int):
+        raise TypeError(f"newsreclib_amd: `k` must be an integer, got {type(k).__name__}")
+    if k >= 1 and draws * k > TOPK_MAX_K:
+        raise ValueError(f"newsreclib_amd: `draws * k` must be at most {TOPK_MAX_K}, got {draws} * {k}")
+    return draws
+
+
+def topk_sampled_draws(user_vec: torch.Tensor, table: torch.Tensor, k: int, draws: int, user_key: torch.Tensor, seed: int,
+                       inv_temp: float = 1.0, excl_idx: Optional[torch.Tensor] = None, excl_off: Optional[torch.Tensor] = None,
+                       eligible: Optional[torch.Tensor] = None, slices: int = 0):
+    """``nrl_topk_sampled_draws``: ``draws`` Gumbel top-k lists per user from ONE walk over the table -> (idx (B, draws, k) int64,
+    key (B, draws, k) fp32, score (B, draws, k) fp32, status (1) int32).  Draw ``r`` is, bit for bit in all three outputs, what
+    ``topk_sampled_scores`` returns under ``(seed + r) mod 2^64`` with everything else equal, and ``status`` is the OR of those
+    calls' words: the dot products are computed once per table tile and perturbed ``draws`` times.  ``draws`` in
+    ``[1, TOPK_MAX_DRAWS]`` and ``draws * k <= TOPK_MAX_K``; the other arguments, their checks and the flags (``TOPK_FLAGS``) are
+    those of ``topk_sampled_scores``.  Nothing here synchronises with the host."""
+    draws = _draws_arg(k, draws)
+    B = int(user_vec.shape[0]) if isinstance(user_vec, torch.Tensor) and user_vec.dim() else -1
+    seed, inv_temp = _sample_args(user_key, B, seed, inv_temp)
+    s = _dot_scorer(user_vec, table)
+    user_key = _chk(user_key, torch.int64, "user_key")
+    lib = _lib.load()
+    excl_idx, excl_off, eligible = _topk_masks(excl_idx, excl_off, eligible, s.B, s.V)
+    shape = (s.B, draws, max(k, 0))
+    idx = torch.empty(shape, dtype=torch.int64, device=s.dev)
+    key, score = (torch.empty(shape, dtype=torch.float32, device=s.dev) for _ in range(2))
+    status = torch.zeros(1, dtype=torch.int32, device=s.dev)
+    ws = workspace(lib.nrl_topk_sampled_draws_workspace_size(s.B, s.V, s.D, k, draws, int(slices)), s.dev)
+    _lib.check(lib.nrl_topk_sampled_draws(*s.lead, k, draws, _ptr(excl_idx), _ptr(excl_off), _ptr(eligible), user_key.data_ptr(), seed,
+                                          inv_temp, int(slices), idx.data_ptr(), key.data_ptr(), score.data_ptr(), status.data_ptr(),
+                                          ws.data_ptr(), ws.numel(), _stream()), "nrl_topk_sampled_draws")
+    return idx, key, score, status
+
+
+# the status word of ``list_class_exposure`` (a dictionary of its own: the key sets of the other flag dictionaries are pinned)
+EXPOSURE_FLAGS = {1: "a listed row other than -1 is outside [0, V) (it counts for no class)",
+                  64: "a class id is outside [0, S) (that row counts for no class)"}
+
+
+def list_class_exposure(list_idx: torch.Tensor, row_class: torch.Tensor, pos_weight: torch.Tensor, S: int):
+    """``nrl_list_class_exposure``: the position-weighted exposure that ``L`` lists per user give each of ``S`` classes ->
+    (exposure (B, S) fp32, status (1) int32).  ``list_idx`` (B, L, k) int64, ``-1`` an empty slot (the draws of
+    ``topk_sampled_draws``; (B, k) is taken as L = 1); ``row_class`` (V int32, or int64: converted by one device op); ``pos_weight``
+    (k) fp32.  ``exposure[b, s]`` is the sum, over the lists in order and their slots in order, of ``pos_weight[j]`` where the
+    slot's row has class ``s``, accumulated in float64, divided by ``L`` and rounded once.  ``S`` in ``[1, TOPK_MAX_BIAS_CLASSES]``,
+    ``k`` in ``[1, TOPK_MAX_K]``.  A row outside the table or a class outside ``[0, S)`` counts for no class and is flagged
+    (``EXPOSURE_FLAGS``).  Nothing here synchronises with the host."""
+    if not isinstance(list_idx, torch.Tensor) or list_idx.dtype != torch.int64:
+        raise TypeError(f"newsreclib_amd: `list_idx` must be an int64 tensor, got "
+                        f"{list_idx.dtype if isinstance(list_idx, torch.Tensor) else type(list_idx).__name__}")
+    if not isinstance(row_class, torch.Tensor) or row_class.dtype not in (torch.int32, torch.int64):
+        raise TypeError(f"newsreclib_amd: `row_class` must be an int32 tensor, got "
+                        f"{row_class.dtype if isinstance(row_class, torch.Tensor) else type(row_class).__name__}")
+    if not isinstance(pos_weight, torch.Tensor) or pos_weight.dtype != torch.float32:
+        raise TypeError(f"newsreclib_amd: `pos_weight` must be a float32 tensor, got "
+                        f"{pos_weight.dtype if isinstance(pos_weight, torch.Tensor) else type(pos_weight).__name__}")
+    if list_idx.dim() == 2:
+        list_idx = list_idx.unsqueeze(1)
+    if list_idx.dim() != 3:
+        raise ValueError(f"newsreclib_amd: `list_idx` must be (B, L, k), got {tuple(list_idx.shape)}")
+    B, L, k = (int(n) for n in list_idx.shape)
+    S = int(S)
+    if not 1 <= S <= TOPK_MAX_BIAS_CLASSES:
+        raise ValueError(f"newsreclib_amd: `S` must be in [1, {TOPK_MAX_BIAS_CLASSES}], got {S}")
+    if L < 1 or not 1 <= k <= TOPK_MAX_K:
+        raise ValueError(f"newsreclib_amd: `list_idx` must hold L >= 1 lists of 1 <= k <= {TOPK_MAX_K} slots, got {tuple(list_idx.shape)}")
+    if row_class.dim() != 1:
+        raise ValueError(f"newsreclib_amd: `row_class` must be one-dimensional, got {tuple(row_class.shape)}")
+    if pos_weight.dim() != 1 or pos_weight.numel() != k:
+        raise ValueError(f"newsreclib_amd: `pos_weight` must have one entry per slot ({k}), got {tuple(pos_weight.shape)}")
+    if row_class.dtype == torch.int64 and row_class.is_cuda:
+        row_class = row_class.to(torch.int32)
+    list_idx, row_class = _chk(list_idx, torch.int64, "list_idx"), _chk(row_class, torch.int32, "row_class")
+    pos_weight = _chk(pos_weight, torch.float32, "pos_weight")
+    out = torch.empty((B, S), dtype=torch.float32, device=list_idx.device)
+    status = torch.zeros(1, dtype=torch.int32, device=list_idx.device)
+    _lib.check(_lib.load().nrl_list_class_exposure(list_idx.data_ptr(), row_class.data_ptr(), pos_weight.data_ptr(), B, L, k,
+                                                   int(row_class.numel()), S, out.data_ptr(), status.data_ptr(), _stream()),
+               "nrl_list_class_exposure")
+    return out, status
+
+
 # the status word of ``catalogue_logz`` / ``list_logprob``: the flags of ``topk_scores`` they share, in their own words, and their
 # two own bits (a dictionary of its own: the key set of ``TOPK_FLAGS`` is pinned)
 POLICY_FLAGS = {1: TOPK_FLAGS[1],
